@@ -16,6 +16,11 @@ exchange).  --scaling weak gives every rank its own 1 Gbp instead.
 (`python -m torch.distributed.run`, one process per GPU, 127.0.0.1 rendezvous) BEFORE anything touches
 the GPU and exits with the launcher's code; under a launcher, WORLD_SIZE must equal --gpus.
 
+A plain run sets up, warms up, times --steps steps and prints the headline.  --full adds what the headline does
+not need: the instrumented launch behind the "roofline" figures, the CPU baseline with the oracle parity of the
+full-size scan, BASELINE configs 2 and 5 ("extra_configs") and, for N > 1 with --no-gather-hits, the hit-gather
+probe.  --dump-outputs DIR writes the records of the last timed step to DIR/<name>.npy (float64; see dump_records).
+
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
 """
 from __future__ import annotations
@@ -65,7 +70,7 @@ def main():
     ap.add_argument("--no-gather-hits", dest="gather_hits", action="store_false",
                     help="N > 1, secondary mode: only the CALL / OTU records (the report's content) travel inside the timed "
                          "steps; the hit records, which only the -d stream prints, stay sharded in HBM and their gather is "
-                         "exercised and timed in two extra steps after the timed region ('hits_gather_probe')")
+                         "exercised and timed, with --full, in two extra steps after the timed region ('hits_gather_probe')")
     ap.add_argument("--no-overlap-exchange", dest="overlap_exchange", action="store_false", default=True,
                     help="N > 1: finish every step's exchange before the next scan starts (default: the record buffers of step i "
                          "travel while step i + 1 is scanned)")
@@ -82,10 +87,20 @@ def main():
                     help="scan strategy of the library (KG_PARTITION): auto picks partitioned probing for large inputs")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for "
                                                       "rehearsing the multi-rank path on a one-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline figures (one instrumented launch), "
+                         "the CPU baseline and oracle parity (unless --no-cpu-baseline), BASELINE configs 2 and 5 (unless "
+                         "--no-extra-configs), and with --no-gather-hits the hit-gather probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last timed step (rank 0's, in global order) to "
+                         "DIR/<name>.npy as float64: CALL and OTU records, the per-container start arrays, and a fixed "
+                         "seeded sample of the hit records with its row index")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not under a launcher: start the ranks (nothing has touched the GPU yet: torch.cuda is not initialised)
         import socket
@@ -163,14 +178,17 @@ def main():
     # posted when scan i ends and collected when scan i + 1 has ended: the buffers travel over xGMI while the next
     # shard is scanned (--no-overlap-exchange collects at once).  Every exchange is finished, and rank 0 has the
     # records of every step in global order, before the timed region ends.
-    in_flight = []                                         # [(ScanResult, RecordExchange, with_hits)]
+    in_flight = []                                         # [(ScanResult, RecordExchange, with_hits, keep)]
     last = {"hits_gathered": None}                         # hit records rank 0 received in the latest collected step
+    # --dump-outputs: the last timed step's ScanResult is left open (and, N > 1, rank 0's gathered records are kept) until
+    # its records have been written after the timed region
+    kept = {"result": None, "records": None}
 
     restore_ms = []                                        # rank 0: what finish() cost it per step (waits + reordering)
 
     def collect():
         while in_flight:
-            r, ex, with_hits = in_flight.pop(0)
+            r, ex, with_hits, keep = in_flight.pop(0)
             t_f = time.perf_counter()
             got = ex.finish()              # rank 0: the records in global order (the hit records stay in HBM; their
             if with_hits and rank == 0:    # reordering is enqueued on torch's stream, beside the scan that follows)
@@ -183,9 +201,12 @@ def main():
                 torch.cuda.current_stream().synchronize()
             if rank == 0:
                 restore_ms.append((time.perf_counter() - t_f) * 1e3)
-            r.close()
+            if keep:
+                kept["result"], kept["records"] = r, got
+            else:
+                r.close()
 
-    def step(with_hits=False):
+    def step(with_hits=False, keep=False):
         r = tab.scan(None, off, params, device_ptr=seq.data_ptr())
         st = r.stats
         if multi:
@@ -193,21 +214,24 @@ def main():
             local = {k: (r.device_view(k) if on_gpu else r.device_view(k).cpu()) for k in kinds}
             ex = kd.exchange_start(local, mine, n_total, 6, gather_dev, keep=r)
             collect()                                      # the previous step's exchange: done by now
-            in_flight.append((r, ex, with_hits))
+            in_flight.append((r, ex, with_hits, keep))
             if not args.overlap_exchange:
                 collect()
         else:
             r.calls(copy=False); r.otu(copy=False)         # the records the report needs leave HBM
-            r.close()
+            if keep:
+                kept["result"] = r
+            else:
+                r.close()
         return st
 
-    # one instrumented launch: algorithmic bytes per residue, not timed
-    with tab.scan(None, off, hotpath.Params(counters=True), device_ptr=seq.data_ptr()) as r:
-        cst = r.stats
-    residues = cst["residues"]
-    p_bar = cst["slots_inspected"] / residues
-    h_bar = cst["n_hits"] / residues
-    b_alg = 0.5 + 24.0 * p_bar + 24.0 * h_bar
+    if args.full:
+        # one instrumented launch: algorithmic bytes per residue, not timed
+        with tab.scan(None, off, hotpath.Params(counters=True), device_ptr=seq.data_ptr()) as r:
+            cst = r.stats
+        p_bar = cst["slots_inspected"] / cst["residues"]
+        h_bar = cst["n_hits"] / cst["residues"]
+        b_alg = 0.5 + 24.0 * p_bar + 24.0 * h_bar
 
     for _ in range(args.warmup):
         step(args.gather_hits and multi)
@@ -225,13 +249,13 @@ def main():
     pass_ms = {"scatter_until_last_chunk": [], "tag_verify_tail": []}
     hits = calls = 0
     partitioned = False
-    for _ in range(args.steps):
-        st = step(args.gather_hits and multi)
+    for i in range(args.steps):
+        st = step(args.gather_hits and multi, keep=bool(args.dump_outputs) and i == args.steps - 1)
         partitioned = bool(st["partitioned"])
         pass_ms["scatter_until_last_chunk"].append(st["ms_part_scatter"]); pass_ms["tag_verify_tail"].append(st["ms_part_verify"])
         scan_ms.append(st["ms_scan"]); total_ms.append(st["ms_total"])
         agg_ms.append(st["ms_aggregate"]); order_ms.append(st["ms_order"])
-        hits, calls = st["n_hits"], st["n_calls"]
+        residues, hits, calls = st["residues"], st["n_hits"], st["n_calls"]
         assert st["scan_launches"] == 1, "staging buffer resized inside the timed region"
     collect()                                              # the last step's exchange ends inside the timed region
     barrier()
@@ -239,8 +263,22 @@ def main():
     hits_gathered_timed = last["hits_gathered"]
     rank0_restore_ms = float(np.mean(restore_ms)) if restore_ms else None
 
+    if args.dump_outputs:
+        r = kept["result"]
+        if rank == 0:
+            if multi:
+                recs = kept["records"]
+            else:
+                recs = {"calls": r.calls(), "container_call_start": r.container_call_start(), "otu": r.otu(),
+                        "hits": r.device_view("hits").view(torch.int32).view(-1, 6),
+                        "container_hit_start": r.container_hit_start()}
+            dump_records(args.dump_outputs, recs)
+            log("[bench] records of the last timed step written to %s" % args.dump_outputs)
+        r.close()
+        kept["result"] = kept["records"] = None
+
     hits_probe = None
-    if multi and not args.gather_hits:
+    if args.full and multi and not args.gather_hits:
         # outside the timed region: the same step with the per-rank hit buffers gathered to rank 0 as well
         step(True)
         collect()
@@ -262,21 +300,44 @@ def main():
 
     if rank == 0:
         ms_scan = float(np.mean(scan_ms))
-        achieved = b_alg * residues / (ms_scan * 1e-3) / 1e9          # GB/s, algorithmic bytes / scan-kernel time
-        achieved_step = b_alg * residues / (elapsed / args.steps) / 1e9   # ... / whole step (rank 0's bytes, max-over-ranks time)
-        traffic, traffic_source = None, None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")        # PMC-derived HBM bytes per launch, if collected
-        if os.path.exists(tpath) and world == 1:
-            try:
-                tj = json.load(open(tpath))
-                if (tj.get("total_bp") == args.total_bp and tj.get("num_sigs") == args.num_sigs and
-                        tj.get("strategy") == ("partitioned" if partitioned else "direct")):
-                    traffic = tj.get("hbm_bytes_per_launch")
-                    traffic_source = ("profiles/traffic.json (%s): rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                      "command, FETCH doubled per MI355X_MICROARCH.md; not measured in this run"
-                                      % tj.get("round", "?"))
-            except Exception:
-                traffic = None
+        roofline = None
+        if args.full:
+            achieved = b_alg * residues / (ms_scan * 1e-3) / 1e9          # GB/s, algorithmic bytes / scan-kernel time
+            achieved_step = b_alg * residues / (elapsed / args.steps) / 1e9   # ... / whole step (rank 0's bytes, max-over-ranks time)
+            traffic, traffic_source = None, None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")        # PMC-derived HBM bytes per launch, if collected
+            if os.path.exists(tpath) and world == 1:
+                try:
+                    tj = json.load(open(tpath))
+                    if (tj.get("total_bp") == args.total_bp and tj.get("num_sigs") == args.num_sigs and
+                            tj.get("strategy") == ("partitioned" if partitioned else "direct")):
+                        traffic = tj.get("hbm_bytes_per_launch")
+                        traffic_source = ("profiles/traffic.json (%s): rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                          "command, FETCH doubled per MI355X_MICROARCH.md; not measured in this run"
+                                          % tj.get("round", "?"))
+                except Exception:
+                    traffic = None
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS,
+                        "peak_measured": HBM_MEASURED_GBS, "frac_vs_measured_peak": achieved / HBM_MEASURED_GBS,
+                        "achieved_step": achieved_step, "frac_step": achieved_step / HBM_PEAK_GBS,
+                        "frac_note": "frac = algorithmic bytes / scan-stage time (HIP events on the library's streams); "
+                                     "frac_step = the same bytes / ms_per_step (ordering, aggregation, records to host / "
+                                     "exchange included)",
+                        "traffic": traffic, "traffic_source": traffic_source,
+                        "bound_note": ("priced against HBM as SURVEY 8d prescribes; the partitioned scan moves fewer HBM "
+                                       "bytes than the algorithmic count and its passes are bound by VALU/LDS issue "
+                                       "(scatter), the L2's line-gather rate (index pass: one byte of the table's home index per query) and random HBM lines (verification): "
+                                       "DESIGN.md section 6") if partitioned else
+                                      "direct probing: every 16-byte probe moves a 128-byte line from HBM",
+                        "kernel": ("scan stage = kg::part_scatter_kernel || kg::bucket_index_kernel || kg::verify_kernel + "
+                                   "ordered placement (kg::hit_partition_kernel x 2, kg::group_place_kernel): chunks of whole "
+                                   "contigs on three streams" if partitioned else "kg::scan_kernel<false,false,3>"),
+                        "kernel_ms": ms_scan,
+                        "passes_ms": ({k: float(np.mean(v)) for k, v in pass_ms.items()} if partitioned else None),
+                        "strategy": "partitioned" if partitioned else "direct",
+                        "alg_bytes_per_residue": b_alg, "slots_per_residue": p_bar, "hits_per_residue": h_bar,
+                        "residues_per_launch": int(residues)}
         out = {
             "metric": "amino-acid residues/sec scanned (and hits/sec) on 1 Gbp synthetic, 1/2/4/8 MI355X",
             "value": residues_all * args.steps / elapsed,
@@ -310,35 +371,15 @@ def main():
                        # back in FASTA order, the hit records' segmented copy into global order (enqueued + waited for)
                        "rank0_restore_ms": rank0_restore_ms,
                        "parallelism": "contig shards x%d, table replicated" % world},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "peak_measured": HBM_MEASURED_GBS, "frac_vs_measured_peak": achieved / HBM_MEASURED_GBS,
-                         "achieved_step": achieved_step, "frac_step": achieved_step / HBM_PEAK_GBS,
-                         "frac_note": "frac = algorithmic bytes / scan-stage time (HIP events on the library's streams); "
-                                      "frac_step = the same bytes / ms_per_step (ordering, aggregation, records to host / "
-                                      "exchange included)",
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "bound_note": ("priced against HBM as SURVEY 8d prescribes; the partitioned scan moves fewer HBM "
-                                        "bytes than the algorithmic count and its passes are bound by VALU/LDS issue "
-                                        "(scatter), the L2's line-gather rate (index pass: one byte of the table's home index per query) and random HBM lines (verification): "
-                                        "DESIGN.md section 6") if partitioned else
-                                       "direct probing: every 16-byte probe moves a 128-byte line from HBM",
-                         "kernel": ("scan stage = kg::part_scatter_kernel || kg::bucket_index_kernel || kg::verify_kernel + "
-                                    "ordered placement (kg::hit_partition_kernel x 2, kg::group_place_kernel): chunks of whole "
-                                    "contigs on three streams" if partitioned else "kg::scan_kernel<false,false,3>"),
-                         "kernel_ms": ms_scan,
-                         "passes_ms": ({k: float(np.mean(v)) for k, v in pass_ms.items()} if partitioned else None),
-                         "strategy": "partitioned" if partitioned else "direct",
-                         "alg_bytes_per_residue": b_alg, "slots_per_residue": p_bar, "hits_per_residue": h_bar,
-                         "residues_per_launch": int(residues)},
+            "roofline": roofline,
             "stage_ms": {"scan": ms_scan, "order": float(np.mean(order_ms)), "aggregate": float(np.mean(agg_ms)),
                          "device_total": float(np.mean(total_ms))},
         }
         host = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             host = host_table(args, rec)
             out["cpu_baseline"] = cpu_baseline(args, rec, seq, off, tab, host)
-        if world == 1 and not args.no_extra_configs:
+        if args.full and world == 1 and not args.no_extra_configs:
             del seq
             torch.cuda.empty_cache()
             out["extra_configs"] = extra_configs(args, tab, host, dev)
@@ -347,6 +388,47 @@ def main():
     tab.close()
     if multi:
         dist.destroy_process_group()
+
+
+DUMP_SEED = 20250101           # --dump-outputs: seed of the hit-record sample
+DUMP_BYTES_PER_ARRAY = 10 << 20  # at most this much float64 per dumped array, its sample index included (5 arrays < 64 MB)
+
+
+def _as_rows(a):
+    """Records (numpy structured array) or a plain array -> float64[n, k], field by field in declaration order; every
+    field is an int32 / uint32 / int64 below 2^53 or a float32, so float64 holds it exactly."""
+    cols = [np.asarray(a[f]) for f in a.dtype.names] if a.dtype.names else [np.asarray(a)]
+    return np.concatenate([c.reshape(len(c), int(np.prod(c.shape[1:]))).astype(np.float64) for c in cols], axis=1)
+
+
+def dump_records(out_dir, recs):
+    """--dump-outputs: what a caller of the timed path receives, as DIR/<name>.npy in float64.  `recs`: "calls", "otu",
+    "container_call_start" (numpy) and, when present, "hits" (int32[n, 6] torch tensor, host or device) and
+    "container_hit_start" (numpy or torch).  An array with more rows than DUMP_BYTES_PER_ARRAY allows is replaced by
+    the rows at a fixed sorted sample of row indices (seeded by DUMP_SEED and the row count only), written beside it as
+    <name>_index.npy; the headline's hit records (36.7 M) are sampled, its other arrays are written whole."""
+    from kmergutsjava_amd import _native as N
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in recs.items():
+        if a is None:
+            continue
+        is_hits = name == "hits"
+        if isinstance(a, torch.Tensor) and not is_hits:
+            a = a.cpu().numpy()
+        n = int(a.shape[0])
+        cols = 6 if is_hits else _as_rows(a[:1]).shape[1]
+        cap = DUMP_BYTES_PER_ARRAY // (8 * (cols + 1))
+        idx = None
+        if n > cap:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, n]).choice(n, size=cap, replace=False))
+        if is_hits:                                       # sample on the device, then records -> rows
+            sel = a if idx is None else a[torch.from_numpy(idx).to(a.device)]
+            rows = _as_rows(sel.contiguous().cpu().numpy().reshape(-1).view(N.HIT_DTYPE))
+        else:
+            rows = _as_rows(a if idx is None else a[idx])
+        np.save(os.path.join(out_dir, name + ".npy"), rows)
+        if idx is not None:
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
 
 
 def host_table(args, rec):

@@ -44,7 +44,7 @@ def test_bench_self_launch_ranks_share_the_gpu(ranks, gather, overlap):
     env = _clean_env()
     env["KG_BENCH_DEVICE"] = "0"                       # all ranks on the one GPU
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--backend", "gloo", "--total-bp", "40000000",
-           "--num-sigs", "20000003", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + ([] if gather else ["--no-gather-hits"]) + ([] if overlap else ["--no-overlap-exchange"])
+           "--num-sigs", "20000003", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"] + ([] if gather else ["--no-gather-hits"]) + ([] if overlap else ["--no-overlap-exchange"])
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
     assert r.returncode == 0, r.stdout.decode()[-2000:] + r.stderr.decode()[-4000:]
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])

@@ -11,7 +11,7 @@ cd /tmp
 pmc() {
     local name=$1; shift
     timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-include-regex "bucket_tag|part_scatter|verify_kernel|place_unordered" --output-format csv -d $OUT/pmc_$name -- \
-        python3 $ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err || echo "pmc $name rc=$?"
+        python3 $ROOT/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err || echo "pmc $name rc=$?"
 }
 pmc tcc1 TCC_REQ_sum TCC_READ_sum TCC_READ_SECTORS_sum &&
 pmc tcc2 TCC_BUSY_sum TCC_TAG_STALL_sum TCC_IB_STALL_sum &&

@@ -54,7 +54,7 @@ out = {"round": rnd, "total_bp": bench["config"].get("total_bp_rank0", bench["co
                      "double FETCH_SIZE; confirmed in this access pattern by profiles/r01 calibration: aligned random 16-B loads make 1.000 "
                      "request per load, unaligned 1.114 = 1 + 15/128).  WRITE_SIZE is exact.  'per launch' = per scan stage (one bench step).",
        "per_kernel": per_kernel,
-       "collected_with": "rocprofv3 --pmc <group> --kernel-include-regex kg:: -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline "
+       "collected_with": "rocprofv3 --pmc <group> --kernel-include-regex kg:: -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "
                          "(separate passes: FETCH_SIZE; WRITE_SIZE; TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum; TCC_HIT_sum TCC_MISS_sum)"}
 json.dump(out, open(os.path.join(ROOT, "profiles", "traffic.json"), "w"), indent=1)
 shutil.copy(glob.glob(R + "/trace/runc/*_kernel_stats.csv")[0], os.path.join(ROOT, "profiles", rnd + "_kernel_stats.csv"))

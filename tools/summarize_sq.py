@@ -15,7 +15,7 @@ def agg(path):
     return a, n
 ins, n1 = agg(R + "/pmc_insts/runc/*_counter_collection.csv")
 cyc, n2 = agg(R + "/pmc_cycles/runc/*_counter_collection.csv")
-out = {"round": rnd, "note": "rocprofv3 --pmc, bench.py --steps 1 --warmup 0 --no-cpu-baseline: TWO scans of the 1 Gbp workload (the "
+out = {"round": rnd, "note": "rocprofv3 --pmc, bench.py --full --steps 1 --warmup 0 --no-cpu-baseline: TWO scans of the 1 Gbp workload (the "
        "counters scan with KG_F_COUNTERS kernels and one timed scan); kernels without a COUNTERS variant appear with both scans' "
        "launches.  SQ_ACTIVE_INST_* / SQ_WAVE_CYCLES / SQ_WAIT_* are quad-cycles (MI355X_MICROARCH.md): one wave64 VALU instruction "
        "holds its SIMD for one quad-cycle = 4 clocks.", "kernels": {}}
