@@ -71,8 +71,12 @@ typedef struct kg_params {
 #define KG_F_PROGRESS        4u  /* also record what the reference's table stream would have reported  */
                                  /* (kg_result_progress, kg_result_hit_slots): the "Processed: NN%"    */
                                  /* lines of KGJ:1016-1025 and where a short table file fails,          */
-                                 /* KGJ:985-988 / 1036-1049.  Runs the walking kernels of KG_F_COUNTERS */
-                                 /* (the stats' counters are filled too); tables of < 2^32 records      */
+                                 /* KGJ:985-988 / 1036-1049.  Tables of < 2^32 records.  On the          */
+                                 /* partitioned strategy with the table's byte home index (part_levels  */
+                                 /* 4) the index pass summarises the walks of the k-mers it rules out    */
+                                 /* and the verify pass notes the rest; otherwise (direct strategy,      */
+                                 /* KG_BIDX=0, with KG_F_COUNTERS) the walking kernels of KG_F_COUNTERS  */
+                                 /* run and the stats' counters are filled too                           */
 
 /* Event byte per hit record (kg_result_hit_events) and per container (kg_result_container_tail_events):
  * what gatherHits (KGJ:457-514) did at that record, so that a host can print the -d stream (HIT, after-hit,
@@ -144,8 +148,9 @@ typedef struct kg_stats {
     int32_t agg_pieces;          /* pieces beyond the first that long containers were cut into for gatherHits (cuts  */
                                  /* at gaps > maxGap, where the reference's list restarts anyway: KGJ:477-484)       */
     int32_t part_levels;         /* partitioned only: what the tag pass probed in the L2 -- 1 = the tags (bucket_tag_kernel: scans  */
-                                 /* with KG_F_COUNTERS, KG_BIDX=0), 4 = the table's byte home index (bucket_index_kernel, the       */
-                                 /* default).  (2 and 3 were round 3's second partition level, removed in round 4.)                 */
+                                 /* with KG_F_COUNTERS, KG_BIDX=0, tables without the index), 4 = the table's byte home index      */
+                                 /* (bucket_index_kernel, the default; KG_F_PROGRESS scans too).  (2 and 3 were round 3's second    */
+                                 /* partition level, removed in round 4.)                                                           */
 } kg_stats;
 
 /* KG_F_PROGRESS: the slots the reference's merge-join (KGJ:959-1029) visits = the slots some query's walk reads, summed up

@@ -563,6 +563,8 @@ struct Progress {
                                       // arithmetic, KGJ:1018); lo[0] = 0, ~0 when no slot reaches d
     unsigned long long found_upto[11];// distinct k-mers found at slots <= first[d] (count_found_kernel): "found-so-far"
     unsigned long long kmers_found;   // distinct k-mers found = distinct slots among the hit records (KGJ:1004-1006)
+    unsigned long long miss_max1[11]; // byte home index path: 1 + the largest home slot in tenth d of a query k-mer the index
+                                      // lists as a certain miss (0: none); progress_finish_kernel follows its walk
 };
 
 // kmersFound: a k-mer counts once however many query positions carry it (KGJ:1004-1015), and a k-mer is found at one slot:
@@ -619,6 +621,76 @@ __device__ __forceinline__ void progress_note_walk(Progress *p, uint64_t home, u
 __device__ __forceinline__ void progress_note_beyond(Progress *p, uint64_t home)
 {
     if (home < *const_cast<volatile unsigned long long *>(&p->first_beyond)) atomicMin(&p->first_beyond, (unsigned long long)home);
+}
+// One wave's summary of a segment of tenth d (the byte home index pass): mn = the smallest home slot of its entries (~0u:
+// none), mx1 = 1 + the largest home slot of its certain misses (0: none).  Called by all 64 lanes; one read-then-atomic pair.
+__device__ __forceinline__ void progress_note_homes(Progress *p, uint32_t d, uint32_t mn, uint32_t mx1)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mn = min(mn, (uint32_t)__shfl_xor((int)mn, off));
+        mx1 = max(mx1, (uint32_t)__shfl_xor((int)mx1, off));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (mn != ~0u && mn < *const_cast<volatile unsigned long long *>(&p->first[d])) atomicMin(&p->first[d], (unsigned long long)mn);
+        if (mx1 > *const_cast<volatile unsigned long long *>(&p->miss_max1[d])) atomicMax(&p->miss_max1[d], (unsigned long long)mx1);
+    }
+}
+
+// The same for one entry of a bucket that spans the tenths d_lo .. d_hi (small tables): home h, listed or a certain miss.
+__device__ __forceinline__ void progress_note_home(Progress *p, uint32_t d_lo, uint32_t d_hi, uint32_t h, uint32_t listed)
+{
+    uint32_t d = d_lo;
+    while (d < d_hi && p->lo[d + 1] <= h) d++;
+    if (h < *const_cast<volatile unsigned long long *>(&p->first[d])) atomicMin(&p->first[d], (unsigned long long)h);
+    if (!listed && h + 1u > *const_cast<volatile unsigned long long *>(&p->miss_max1[d])) atomicMax(&p->miss_max1[d], (unsigned long long)h + 1u);
+}
+
+// The first empty slot in [h, bound) (bound <= the stream's records), bound when there is none.  All threads of the workgroup
+// call it together; 4096 slots per step, so that long occupied runs stay cheap (nothing here is capped: the answer is exact).
+__device__ uint64_t first_empty_block(const uint8_t *__restrict__ tags, uint64_t h, uint64_t bound)
+{
+    __shared__ unsigned long long s_end;
+    for (uint64_t base = h; base < bound; base += 4096) {
+        if (threadIdx.x == 0) s_end = ~0ull;
+        __syncthreads();
+        unsigned long long mine = ~0ull;
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const uint64_t s = base + (uint64_t)j * 256u + threadIdx.x;
+            if (s < bound && (uint32_t)tags[s] == kTagEmpty && s < mine) mine = s;
+        }
+        if (mine != ~0ull) atomicMin(&s_end, mine);
+        __syncthreads();
+        const unsigned long long e = s_end;
+        __syncthreads();
+        if (e != ~0ull) return e;
+    }
+    return bound;
+}
+
+// Byte home index path, behind the last chunk's passes: the walks of the certain misses, from the segment summaries.  A miss
+// homed at h reads h .. runend(h) (the first empty slot at or after h, capped at the end of the stream), and runend is monotone
+// in h, so the largest home decides: below lo[k] it reaches lo[k] -- the first slot of tenth k -- iff the slots between are all
+// occupied, and overall it gives the last slot visited and whether a walk ran off the end (EOFException, KGJ:1097-1126).
+// One workgroup; runs before count_found_kernel (which reads first[]).
+__global__ __launch_bounds__(256) void progress_finish_kernel(Progress *p, const uint8_t *__restrict__ tags, uint64_t limit)
+{
+    unsigned long long m1 = 0;                                  // 1 + the largest miss home in the tenths below k
+    for (int k = 1; k <= 10; k++) {
+        m1 = max(m1, p->miss_max1[k - 1]);
+        const unsigned long long lo = p->lo[k];
+        if (m1 == 0 || lo >= limit || p->first[k] <= lo) continue;     // (uniform)
+        if (first_empty_block(tags, m1 - 1, lo) == lo && threadIdx.x == 0) p->first[k] = lo;
+    }
+    m1 = max(m1, p->miss_max1[10]);
+    if (m1 == 0) return;
+    const uint64_t e = first_empty_block(tags, m1 - 1, limit);
+    if (threadIdx.x == 0) {
+        const uint64_t last = e < limit ? e : limit - 1;
+        if (last + 1 > p->last_plus1) p->last_plus1 = last + 1;
+        if (e >= limit) p->walk_ran_off = 1ull;
+    }
 }
 
 // ---------------------------------------------------------------------------------------

@@ -810,14 +810,18 @@ __global__ __launch_bounds__(256) KG_TAG_REGS void bucket_tag_kernel(
 // walked side by side, 256 * N / R slots of each per iteration: full lanes and half / a quarter of the hand-outs.
 // EXACT: the table's quotients are all below 19, a class IS the quotient (no q % 19: two quarter-rate multiplies per entry,
 // which the compiler otherwise computes for every entry and then selects away -- half of the pass's VALU time, r04 ISA).
-template <int N, int R, bool EXACT>
+// PROG (KG_F_PROGRESS): the walks of the certain misses, [home, first empty slot at or after it], are the one thing no other
+// pass sees.  Per segment = bucket x tenth of the table (a bucket usually lies in one tenth: the segment is the hand-out) the
+// lanes keep the smallest home slot of any entry and the largest home slot of a miss, reduced over the wave once per hand-out
+// (progress_note_homes); progress_finish_kernel turns the misses' largest homes into the slots their walks reach.
+template <int N, int R, bool EXACT, bool PROG = false>
 __global__ __launch_bounds__(256) KG_TAG_REGS void bucket_index_kernel(
     const uint8_t *__restrict__ bidx, uint32_t tail_start,
     const uint64_t *__restrict__ ent, const uint32_t *__restrict__ fill, uint32_t n_regions /* multiple of R */, uint32_t cap, uint32_t n_buckets,
     uint32_t shift, uint32_t grab /* entry slots (of every region) per hand-out, multiple of 256 * N / R */,
     uint32_t *next_region /* ticket counter of group x at [32 * x], zeroed */,
     CandRec *__restrict__ cand, uint32_t *__restrict__ cand_used, unsigned long long *cand_cursor, uint64_t cand_cap,
-    unsigned long long *ctr, uint32_t prio /* wave priority (0..3) */)
+    unsigned long long *ctr, uint32_t prio /* wave priority (0..3) */, Progress *prog /* PROG kernels, else null */)
 {
     static_assert(N % R == 0, "R must divide N");
     constexpr int PER = N / R;                          // entries per lane, region and iteration
@@ -854,6 +858,12 @@ __global__ __launch_bounds__(256) KG_TAG_REGS void bucket_index_kernel(
         for (int r = 0; r < R; r++) { fraw[r] = fill[(uint64_t)b * n_regions + w + r]; n[r] = cap; }
         const uint64_t *src = ent + ((uint64_t)b * n_regions + w) * cap;          // region r of the hand-out: src + r * cap
         const uint32_t smask = (1u << shift) - 1u, bbase = b << shift;
+        uint32_t d_lo = 0, d_hi = 0, pmin = ~0u, pmax1 = 0;     // PROG: tenths of the bucket's first / last slot (uniform), lane minima
+        if (PROG) {
+            const uint64_t s0 = (uint64_t)b << shift, s1 = (((uint64_t)b + 1) << shift) - 1;
+#pragma unroll
+            for (int k = 1; k <= 10; k++) { d_lo += prog->lo[k] <= s0 ? 1u : 0u; d_hi += prog->lo[k] <= s1 ? 1u : 0u; }
+        }
         for (uint32_t c0 = g0; c0 < nmax && c0 < g0 + kGrab; c0 += 256u * PER) {
             uint64_t ev[N];
 #pragma unroll
@@ -895,6 +905,19 @@ __global__ __launch_bounds__(256) KG_TAG_REGS void bucket_index_kernel(
                 walkm |= (listed & ((wd[k] | all_walk) >> 31)) << k;
                 ran_off = ran_off || (((vmask >> k) & 1u) && !listed && (bbase | ((uint32_t)ev[k] & smask)) >= tail_start);
             }
+            if (PROG) {
+                if (d_lo == d_hi) {                                        // (uniform) the usual case: one segment per hand-out
+#pragma unroll
+                    for (int k = 0; k < N; k++) {
+                        const uint32_t h = bbase | ((uint32_t)ev[k] & smask);
+                        if ((vmask >> k) & 1u) pmin = min(pmin, h);
+                        if (((vmask & ~candm) >> k) & 1u) pmax1 = max(pmax1, h + 1u);
+                    }
+                } else {                                                   // small tables: the bucket spans tenth boundaries
+                    for (int k = 0; k < N; k++)                                // (one read-then-atomic pair per entry)
+                        if ((vmask >> k) & 1u) progress_note_home(prog, d_lo, d_hi, bbase | ((uint32_t)ev[k] & smask), (candm >> k) & 1u);
+                }
+            }
 #pragma unroll
             for (int k = 0; k < N; k++) {
                 const unsigned long long m = __ballot((candm >> k) & 1u);
@@ -923,6 +946,7 @@ __global__ __launch_bounds__(256) KG_TAG_REGS void bucket_index_kernel(
                 }
             }
         }
+        if (PROG && d_lo == d_hi) progress_note_homes(prog, d_lo, pmin, pmax1);
     }
     if (sfill) {                                                           // the wave's last, partial group
         wave_sync();
@@ -935,12 +959,13 @@ __global__ __launch_bounds__(256) KG_TAG_REGS void bucket_index_kernel(
 }
 
 // Verify pass: one wave per candidate chunk at a time, one lane per candidate.
-template <bool AA, bool COUNTERS>
+// PROG (KG_F_PROGRESS on the byte home index, without KG_F_COUNTERS): every candidate's walk is noted in *prog, nothing counted.
+template <bool AA, bool COUNTERS, bool PROG = false>
 __global__ __launch_bounds__(256) void verify_kernel(
     const uint8_t *__restrict__ entries, const uint8_t *__restrict__ tags, uint64_t limit, uint64_t num_sigs, uint64_t magic,
     const CandRec *__restrict__ cand, const uint32_t *__restrict__ cand_used, const unsigned long long *cand_cursor,
     uint64_t cand_cap, kg_hit *__restrict__ ulist, uint32_t *__restrict__ chunk_used, unsigned long long *cursor,
-    uint64_t ulist_cap, unsigned long long *ctr, Progress *prog /* KG_F_PROGRESS (COUNTERS kernels), else null */,
+    uint64_t ulist_cap, unsigned long long *ctr, Progress *prog /* KG_F_PROGRESS (COUNTERS and PROG kernels), else null */,
     uint32_t prio /* wave priority (0..3) */)
 {
     const int lane = threadIdx.x & 63;
@@ -1008,6 +1033,8 @@ __global__ __launch_bounds__(256) void verify_kernel(
                 if (COUNTERS) {
                     ctr_slots += (s < limit ? s + 1 : limit) - home;
                     if (prog) progress_note_walk(prog, home, s, limit);
+                } else if (PROG) {
+                    progress_note_walk(prog, home, s, limit);
                 }
             } else if (act) {
                 if (!(r.walked & kWalkOn)) {               // a fingerprint match at s: check the record
@@ -1033,6 +1060,8 @@ __global__ __launch_bounds__(256) void verify_kernel(
                 if (COUNTERS) {
                     ctr_slots += (s < limit ? s + 1 : limit) - home;
                     if (prog) progress_note_walk(prog, home, s, limit);
+                } else if (PROG) {
+                    progress_note_walk(prog, home, s, limit);
                 }
             }
             const unsigned long long m = __ballot(found);
@@ -1058,7 +1087,8 @@ __global__ __launch_bounds__(256) void verify_kernel(
 }
 
 // Overflow groups (regions that filled up: heavily repeated k-mers): one wave per 16-entry group.
-template <bool AA, bool COUNTERS>
+// PROG: the walks noted and the found slots kept as by the COUNTERS kernel (probe_n), nothing counted.
+template <bool AA, bool COUNTERS, bool PROG = false>
 __global__ __launch_bounds__(256) void overflow_probe_kernel(
     const uint8_t *__restrict__ entries, const uint8_t *__restrict__ tags, uint64_t limit, uint64_t num_sigs, uint64_t magic,
     const uint32_t *__restrict__ ovf_bucket, const uint64_t *__restrict__ ovf_ent, const uint32_t *__restrict__ ovf_cursor,
@@ -1079,7 +1109,7 @@ __global__ __launch_bounds__(256) void overflow_probe_kernel(
         const uint32_t b = ovf_bucket[g];
         uint64_t e[1];
         e[0] = lane < (int)kGroup ? ovf_ent[(uint64_t)g * kGroup + lane] : kEntInvalid;
-        probe_entries<AA, 1, COUNTERS>(tab, b, shift, e, ulist, chunk_used, cursor, ulist_cap, u, ctr_slots, ran_off, lane, prog);
+        probe_entries<AA, 1, COUNTERS || PROG>(tab, b, shift, e, ulist, chunk_used, cursor, ulist_cap, u, ctr_slots, ran_off, lane, prog);
     }
     if (lane == 0 && u.have && u.base + kUChunk <= ulist_cap) chunk_used[u.base / kUChunk] = u.used;
     flush_ran_off(ran_off, ctr, lane);

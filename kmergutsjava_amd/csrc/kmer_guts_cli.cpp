@@ -440,18 +440,104 @@ int main(int argc, char **argv)
         const int per = o.aa ? 1 : 6;
         // KG_CLI_BATCH_CHARS: test hook (smaller batches)
         const int64_t kMaxBatchChars = getenv("KG_CLI_BATCH_CHARS") ? std::max(1ll, atoll(getenv("KG_CLI_BATCH_CHARS"))) : 1500000000ll;   // below the ABI's 2^32-256 windows per call
+        // One batch's results as the report needs them (host views, copied from the device on first use).
+        struct View {
+            kg_result *res;
+            const kg_call *calls; const int64_t *ccs; const kg_otu *otu;
+            const kg_hit *hits; const int64_t *chs; const uint8_t *ev, *tail;      // -d only
+        };
+        auto view_of = [&](kg_result *res) {
+            View v{res, kg_result_calls(res), kg_result_container_call_start(res), kg_result_otu(res), nullptr, nullptr, nullptr, nullptr};
+            if (!v.ccs || !v.otu) die(std::string("libkmerguts_hip: ") + kg_last_error());
+            if (o.debug) {                                         // -d: hit records + what gatherHits did at each
+                v.hits = kg_result_hits(res); v.chs = kg_result_container_hit_start(res);
+                v.ev = kg_result_hit_events(res); v.tail = kg_result_container_tail_events(res);
+                if (!v.hits || !v.chs || !v.ev || !v.tail) die(std::string("libkmerguts_hip: ") + kg_last_error());
+            }
+            return v;
+        };
+        char num[64];
+        // the report of sequence j of a batch: its id and length, the CALL lines of its containers (with -d the HIT stream
+        // around them) and its OTU counts
+        auto emit = [&](const View &v, int64_t j, const std::string &id, long long len) {
+            const kg_call *calls = v.calls;
+            const int64_t *ccs = v.ccs, *chs = v.chs;
+            const kg_hit *hits = v.hits;
+            const uint8_t *ev = v.ev, *tail = v.tail;
+            std::string r;
+            if (o.aa) r += "PROTEIN-ID\t" + id + "\t" + std::to_string(len) + "\n";              // KGJ:529
+            else r += "processing " + id + "[" + std::to_string(len) + "]\n";                    // KGJ:541
+            for (int f = 0; f < per; f++) {
+                if (!o.aa)                                                                         // KGJ:545
+                    r += "TRANSLATION\t" + id + "\t" + std::to_string(len) + "\t" + (f < 3 ? "+" : "-") + "\t" +
+                         std::to_string(f % 3) + "\n";
+                const int64_t cont = j * per + f;
+                auto put_call = [&](int64_t c) {                                                  // KGJ:398-404
+                    const kg_call &cl = calls[c];
+                    if (cl.fI < 0 || (size_t)cl.fI >= functions.size())
+                        die("Index: " + std::to_string(cl.fI) + ", Size: " + std::to_string(functions.size()));
+                    format_java_f(cl.weightedHits, 6, num, sizeof num);
+                    r += "CALL\t" + std::to_string(cl.start) + "\t" + std::to_string(cl.end) + "\t" + std::to_string(cl.count) +
+                         "\t" + std::to_string(cl.fI) + "\t" + functions[(size_t)cl.fI] + "\t" + num + "\n";
+                };
+                if (!o.debug) {
+                    for (int64_t c = ccs[cont]; c < ccs[cont + 1]; c++) put_call(c);
+                    continue;
+                }
+                // -d stream (KGJ:470-473 HIT, 498-501 after-hit, 406-409 after-call, displayHits KGJ:376-383).
+                // Nothing is decided here: the event bytes say when the reference's hits list grew, was
+                // processed, kept its last two members or was emptied.
+                std::vector<int64_t> live;
+                int64_t nxt = ccs[cont];
+                auto show = [&](const char *tag) {
+                    r += tag;
+                    r += "hits: ";
+                    for (int64_t i : live) {
+                        format_java_f(hits[i].functionWt, 6, num, sizeof num);
+                        r += std::to_string(hits[i].from0InProt) + "/" + num + "/" + std::to_string(hits[i].fI) + " ";
+                    }
+                    r += "\n";
+                };
+                auto reset = [&](bool called, bool keep2) {
+                    if (called) { put_call(nxt++); show("after-call: "); }
+                    if (keep2 && live.size() >= 2) live.erase(live.begin(), live.end() - 2);
+                    else live.clear();
+                };
+                for (int64_t i = chs[cont]; i < chs[cont + 1]; i++) {
+                    const kg_hit &h = hits[i];
+                    const uint8_t e = ev[i];
+                    format_java_f(h.functionWt, 3, num, sizeof num);
+                    r += "HIT\t" + std::to_string(h.from0InProt) + "\t0\t" + std::to_string(h.avgOffFromEnd) + "\t" +
+                         std::to_string(h.fI) + "\t" + num + "\t" + std::to_string(h.oI) + "\n";
+                    if (e & KG_EV_RESET_BEFORE) reset(e & KG_EV_CALL_BEFORE, e & KG_EV_KEEP2_BEFORE);
+                    if (e & KG_EV_ACCEPTED) { live.push_back(i); show("after-hit: "); }
+                    if (e & KG_EV_RESET_AFTER) reset(e & KG_EV_CALL_AFTER, e & KG_EV_KEEP2_AFTER);
+                    if (r.size() > (4u << 20)) { out.put(r); r.clear(); }
+                }
+                if (tail[cont] & KG_EV_TAIL_CALL) reset(true, false);
+                if (nxt != ccs[cont + 1]) die("event bytes and CALL records disagree");
+            }
+            r += "OTU-COUNTS\t" + id + "[" + std::to_string(len) + "]";                          // KGJ:518-522
+            for (int k2 = 0; k2 < v.otu[j].n; k2++) r += "\t" + std::to_string(v.otu[j].count[k2]) + "-" + std::to_string(v.otu[j].oI[k2]);
+            r += "\n";
+            out.put(r);
+        };
+        long long t_group = 0;
         if (o.debug || !to_stdout) {
             // What lookup prints besides the records -- "Processed: NN%, time=..., found-so-far=K" once per tenth of the table
             // the merge-join visits (KGJ:1016-1025), with -d "Kmers found: N (pos-count=M)" (KGJ:1031-1033) -- and how run()
             // reports the stream's failure (KGJ:797-802).  All of it is about EVERY FASTA record (the reference's lookup fills the
             // containers of records that a later record of the same id shadows in the report too, KGJ:805-809) and precedes
-            // the report, so the records are scanned once more here, hit records only, with KG_F_PROGRESS: the library notes
-            // which table slots the reference's stream would have visited and counts the distinct k-mers found.
+            // the report.  So every record is scanned, once, with KG_F_PROGRESS (the library notes which table slots the
+            // reference's stream would have visited and counts the distinct k-mers found) and the aggregation; the batches'
+            // results are kept until the lines are out, and the report is written from the records of `order`.
             kg_params pc = p;
-            pc.flags = KG_F_SKIP_AGGREGATE | KG_F_PROGRESS;
+            pc.flags = KG_F_PROGRESS;
             long long pos_count = 0;
             std::vector<kg_progress> prog;
             std::vector<uint32_t> slots;                           // (several batches only: a k-mer found in two counts once)
+            std::vector<View> views;
+            std::vector<int64_t> batch_lo;                         // batch i = records [batch_lo[i], batch_lo[i + 1])
             int64_t a = 0;
             while (a < n) {
                 int64_t b = a;
@@ -460,6 +546,8 @@ int main(int argc, char **argv)
                 for (int64_t k = a; k <= b; k++) boff[(size_t)(k - a)] = fa.off[(size_t)k] - fa.off[(size_t)a];
                 kg_result *res = nullptr;
                 check(kg_scan(tab, &pc, fa.seq.data() + fa.off[(size_t)a], boff.data(), b - a, &res));
+                views.push_back(view_of(res));
+                batch_lo.push_back(a);
                 kg_stats stc;
                 check(kg_result_stats(res, &stc));
                 kg_progress g;
@@ -471,9 +559,9 @@ int main(int argc, char **argv)
                     if (!hs) die(std::string("libkmerguts_hip: ") + kg_last_error());
                     slots.insert(slots.end(), hs, hs + stc.n_hits);
                 }
-                kg_result_free(res);
                 a = b;
             }
+            batch_lo.push_back(n);
             if (!prog.empty()) {
                 int64_t first[11], found_upto[11], last = -1, beyond = -1, kmers_found = 0;
                 bool walk_ran_off = false;
@@ -515,10 +603,16 @@ int main(int argc, char **argv)
                     out.put("Kmers found: " + std::to_string(kmers_found) + " (pos-count=" + std::to_string(pos_count) + ")\n");
                 }
             }
-        }
-        long long t_group = 0;
+            info("Lookup time: " + std::to_string(now_ms() - t2) + " ms.");
+            long long t3 = now_ms();
+            for (int64_t k : order) {                              // the last record of each id, at the place of its first
+                const size_t i = (size_t)(std::upper_bound(batch_lo.begin(), batch_lo.end(), k) - batch_lo.begin()) - 1;
+                emit(views[i], k - batch_lo[i], fa.ids[(size_t)k], (long long)(fa.off[(size_t)k + 1] - fa.off[(size_t)k]));
+            }
+            t_group += now_ms() - t3;
+            for (View &v : views) kg_result_free(v.res);
+        } else {
         size_t at = 0;
-        char num[64];
         while (at < order.size()) {
             // one batch: the next records, in report order.  No repeated ids and everything in one batch (the
             // usual case): scan the parsed buffer in place; otherwise gather the batch's records into one buffer.
@@ -542,84 +636,15 @@ int main(int argc, char **argv)
             const std::vector<int64_t> &boffr = in_place ? fa.off : boff;
             kg_result *res = nullptr;
             check(kg_scan(tab, &p, sptr, boffr.data(), (int64_t)(end - at), &res));
-            const kg_call *calls = kg_result_calls(res);
-            const int64_t *ccs = kg_result_container_call_start(res);
-            const kg_otu *otu = kg_result_otu(res);
-            if (!ccs || !otu) die(std::string("libkmerguts_hip: ") + kg_last_error());
-            const kg_hit *hits = nullptr;                          // -d: hit records + what gatherHits did at each
-            const int64_t *chs = nullptr;
-            const uint8_t *ev = nullptr, *tail = nullptr;
-            if (o.debug) {
-                hits = kg_result_hits(res); chs = kg_result_container_hit_start(res);
-                ev = kg_result_hit_events(res); tail = kg_result_container_tail_events(res);
-                if (!hits || !chs || !ev || !tail) die(std::string("libkmerguts_hip: ") + kg_last_error());
-            }
+            const View v = view_of(res);
             if (at == 0) info("Lookup time: " + std::to_string(now_ms() - t2) + " ms.");
             long long t3 = now_ms();
-            for (size_t j = 0; j < end - at; j++) {
-                const std::string &id = fa.ids[(size_t)order[at + j]];
-                const long long len = (long long)(boffr[j + 1] - boffr[j]);
-                std::string r;
-                if (o.aa) r += "PROTEIN-ID\t" + id + "\t" + std::to_string(len) + "\n";              // KGJ:529
-                else r += "processing " + id + "[" + std::to_string(len) + "]\n";                    // KGJ:541
-                for (int f = 0; f < per; f++) {
-                    if (!o.aa)                                                                         // KGJ:545
-                        r += "TRANSLATION\t" + id + "\t" + std::to_string(len) + "\t" + (f < 3 ? "+" : "-") + "\t" +
-                             std::to_string(f % 3) + "\n";
-                    const int64_t cont = (int64_t)j * per + f;
-                    auto put_call = [&](int64_t c) {                                                  // KGJ:398-404
-                        const kg_call &cl = calls[c];
-                        if (cl.fI < 0 || (size_t)cl.fI >= functions.size())
-                            die("Index: " + std::to_string(cl.fI) + ", Size: " + std::to_string(functions.size()));
-                        format_java_f(cl.weightedHits, 6, num, sizeof num);
-                        r += "CALL\t" + std::to_string(cl.start) + "\t" + std::to_string(cl.end) + "\t" + std::to_string(cl.count) +
-                             "\t" + std::to_string(cl.fI) + "\t" + functions[(size_t)cl.fI] + "\t" + num + "\n";
-                    };
-                    if (!o.debug) {
-                        for (int64_t c = ccs[cont]; c < ccs[cont + 1]; c++) put_call(c);
-                        continue;
-                    }
-                    // -d stream (KGJ:470-473 HIT, 498-501 after-hit, 406-409 after-call, displayHits KGJ:376-383).
-                    // Nothing is decided here: the event bytes say when the reference's hits list grew, was
-                    // processed, kept its last two members or was emptied.
-                    std::vector<int64_t> live;
-                    int64_t nxt = ccs[cont];
-                    auto show = [&](const char *tag) {
-                        r += tag;
-                        r += "hits: ";
-                        for (int64_t i : live) {
-                            format_java_f(hits[i].functionWt, 6, num, sizeof num);
-                            r += std::to_string(hits[i].from0InProt) + "/" + num + "/" + std::to_string(hits[i].fI) + " ";
-                        }
-                        r += "\n";
-                    };
-                    auto reset = [&](bool called, bool keep2) {
-                        if (called) { put_call(nxt++); show("after-call: "); }
-                        if (keep2 && live.size() >= 2) live.erase(live.begin(), live.end() - 2);
-                        else live.clear();
-                    };
-                    for (int64_t i = chs[cont]; i < chs[cont + 1]; i++) {
-                        const kg_hit &h = hits[i];
-                        const uint8_t e = ev[i];
-                        format_java_f(h.functionWt, 3, num, sizeof num);
-                        r += "HIT\t" + std::to_string(h.from0InProt) + "\t0\t" + std::to_string(h.avgOffFromEnd) + "\t" +
-                             std::to_string(h.fI) + "\t" + num + "\t" + std::to_string(h.oI) + "\n";
-                        if (e & KG_EV_RESET_BEFORE) reset(e & KG_EV_CALL_BEFORE, e & KG_EV_KEEP2_BEFORE);
-                        if (e & KG_EV_ACCEPTED) { live.push_back(i); show("after-hit: "); }
-                        if (e & KG_EV_RESET_AFTER) reset(e & KG_EV_CALL_AFTER, e & KG_EV_KEEP2_AFTER);
-                        if (r.size() > (4u << 20)) { out.put(r); r.clear(); }
-                    }
-                    if (tail[cont] & KG_EV_TAIL_CALL) reset(true, false);
-                    if (nxt != ccs[cont + 1]) die("event bytes and CALL records disagree");
-                }
-                r += "OTU-COUNTS\t" + id + "[" + std::to_string(len) + "]";                          // KGJ:518-522
-                for (int k2 = 0; k2 < otu[j].n; k2++) r += "\t" + std::to_string(otu[j].count[k2]) + "-" + std::to_string(otu[j].oI[k2]);
-                r += "\n";
-                out.put(r);
-            }
+            for (size_t j = 0; j < end - at; j++)
+                emit(v, (int64_t)j, fa.ids[(size_t)order[at + j]], (long long)(boffr[j + 1] - boffr[j]));
             t_group += now_ms() - t3;
             kg_result_free(res);
             at = end;
+        }
         }
         info("Grouping time: " + std::to_string(t_group) + " ms.");
         out.flush();

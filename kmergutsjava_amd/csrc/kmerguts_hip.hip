@@ -785,7 +785,9 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
     };
     constexpr uint32_t PER = AA ? 1 : 6;
     const bool progress = (p->flags & KG_F_PROGRESS) != 0;
-    const bool counters = (p->flags & KG_F_COUNTERS) != 0 || progress;       // the walks are noted by the counting kernels
+    const bool counters_req = (p->flags & KG_F_COUNTERS) != 0;
+    // the walks are noted by the counting kernels -- except on the partitioned path's byte home index (below: prog_index)
+    const bool counters = counters_req || progress;
     kg_stats &st = res->st;
     res->per = PER;
 
@@ -856,6 +858,7 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
         h.last_plus1 = 0; h.first_beyond = ~0ull; h.walk_ran_off = 0;
         for (auto &x : h.found_upto) x = 0;
         h.kmers_found = 0;
+        for (auto &x : h.miss_max1) x = 0;
         const double n = (double)t->num_sigs;
         auto tenth = [&](uint64_t s) { return (int)(10.0 * ((double)(s + 1) / n)); };
         for (int f = 0; f <= 10; f++) {
@@ -906,6 +909,7 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
         part_buckets = (uint32_t)((t->limit + (1ull << shift) - 1) >> shift);
     }
     bool part_done = false;
+    bool prog_index = false;                     // KG_F_PROGRESS noted by the byte home index pass (progress_finish_kernel is due)
     if (use_part) do {
         constexpr uint32_t WIN = AA ? 64u : 384u;                                    // windows per block
         constexpr uint32_t kMaxChunks = 8;
@@ -1011,8 +1015,11 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
         if ((rc = sc.get(&d_pc, 48))) return rc;
         unsigned long long *d_ctr = (unsigned long long *)(d_totals + 2);
         // the tag pass on the byte home index instead of the tags (bucket_index_kernel) unless the scan counts the slots it
-        // inspects (the walk the index avoids) or KG_BIDX=0
-        const bool use_bidx = t->d_bidx != nullptr && !counters && env_u32("KG_BIDX", 1u) != 0;
+        // inspects (the walk the index avoids) or KG_BIDX=0.  KG_F_PROGRESS alone runs the index pass's PROG variant (it
+        // summarises the certain misses' walks) and the verify / overflow passes' PROG variants (they note theirs), nothing counted.
+        const bool use_bidx = t->d_bidx != nullptr && !counters_req && env_u32("KG_BIDX", 1u) != 0;
+        const bool part_counters = counters && !use_bidx;
+        prog_index = progress && use_bidx;
         const size_t lds = kg::scatter_lds_bytes<AA>(part_buckets);
         if (t->scatter_lds[AA ? 1 : 0] < lds) {         // once per table (and geometry): the call costs tens of microseconds
             HIP_TRY(hipFuncSetAttribute((const void *)kg::part_scatter_kernel<AA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1138,22 +1145,35 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
                 if (use_bidx) {
 #define KG_INDEX_ARGS t->d_bidx, (uint32_t)std::min<uint64_t>(t->tail_start, 0xFFFFFFFFull), ent_c, fill_c, n_wg, cap, \
                       part_buckets, part_shift, probe_grab, next_c, cand_c, candused_c, ccur_c, ccap, d_ctr, index_prio
-#define KG_INDEX_LAUNCH(R, X) hipLaunchKernelGGL((kg::bucket_index_kernel<kg::kIndexN, R, X>), dim3(index_grid), dim3(256), 0, s2, KG_INDEX_ARGS)
+#define KG_INDEX_LAUNCH(R, X) hipLaunchKernelGGL((kg::bucket_index_kernel<kg::kIndexN, R, X>), dim3(index_grid), dim3(256), 0, s2, KG_INDEX_ARGS, \
+                                                 (kg::Progress *)nullptr)
+#define KG_INDEX_LAUNCH_P(R, X) hipLaunchKernelGGL((kg::bucket_index_kernel<kg::kIndexN, R, X, true>), dim3(index_grid), dim3(256), 0, s2, \
+                                                   KG_INDEX_ARGS, d_prog)
                     // regions per hand-out by their expected fill (an iteration covers 256 * N / R entry slots of each); the
                     // kernel for tables whose classes are their quotients has no q % 19
-                    if (t->bidx_exact) { if (index_r <= 1) KG_INDEX_LAUNCH(1, true); else if (index_r == 2) KG_INDEX_LAUNCH(2, true); else KG_INDEX_LAUNCH(4, true); }
+                    if (prog_index) {
+                        if (t->bidx_exact) { if (index_r <= 1) KG_INDEX_LAUNCH_P(1, true); else if (index_r == 2) KG_INDEX_LAUNCH_P(2, true); else KG_INDEX_LAUNCH_P(4, true); }
+                        else { if (index_r <= 1) KG_INDEX_LAUNCH_P(1, false); else if (index_r == 2) KG_INDEX_LAUNCH_P(2, false); else KG_INDEX_LAUNCH_P(4, false); }
+                    }
+                    else if (t->bidx_exact) { if (index_r <= 1) KG_INDEX_LAUNCH(1, true); else if (index_r == 2) KG_INDEX_LAUNCH(2, true); else KG_INDEX_LAUNCH(4, true); }
                     else { if (index_r <= 1) KG_INDEX_LAUNCH(1, false); else if (index_r == 2) KG_INDEX_LAUNCH(2, false); else KG_INDEX_LAUNCH(4, false); }
+#undef KG_INDEX_LAUNCH_P
 #undef KG_INDEX_LAUNCH
 #undef KG_INDEX_ARGS
                 }
-                else if (counters) hipLaunchKernelGGL((kg::bucket_tag_kernel<true>), dim3(probe_grid), dim3(256), 0, s2, KG_TAG_ARGS, d_prog);
+                else if (part_counters) hipLaunchKernelGGL((kg::bucket_tag_kernel<true>), dim3(probe_grid), dim3(256), 0, s2, KG_TAG_ARGS, d_prog);
                 else hipLaunchKernelGGL((kg::bucket_tag_kernel<false>), dim3(probe_grid), dim3(256), 0, s2, KG_TAG_ARGS, (kg::Progress *)nullptr);
                 HIP_TRY(hipEventRecord(t->pev[2 * c + 1], s2));
                 HIP_TRY(hipStreamWaitEvent(s3, t->pev[2 * c + 1], 0));
-                if (counters) {
+                if (part_counters) {
                     hipLaunchKernelGGL((kg::verify_kernel<AA, true>), dim3(verify_grid), dim3(256), 0, s3, KG_PROBE_ARGS, cand_c,
                                        candused_c, ccur_c, ccap, KG_ULIST_ARGS, verify_prio);
                     hipLaunchKernelGGL((kg::overflow_probe_kernel<AA, true>), dim3(ovf_grid), dim3(256), 0, s3, KG_PROBE_ARGS,
+                                       ovf_bucket_c, ovf_ent_c, ovfc_c, ovf_cap, part_shift, KG_ULIST_ARGS);
+                } else if (prog_index) {
+                    hipLaunchKernelGGL((kg::verify_kernel<AA, false, true>), dim3(verify_grid), dim3(256), 0, s3, KG_PROBE_ARGS, cand_c,
+                                       candused_c, ccur_c, ccap, KG_ULIST_ARGS, verify_prio);
+                    hipLaunchKernelGGL((kg::overflow_probe_kernel<AA, false, true>), dim3(ovf_grid), dim3(256), 0, s3, KG_PROBE_ARGS,
                                        ovf_bucket_c, ovf_ent_c, ovfc_c, ovf_cap, part_shift, KG_ULIST_ARGS);
                 } else {
                     hipLaunchKernelGGL((kg::verify_kernel<AA, false>), dim3(verify_grid), dim3(256), 0, s3, KG_PROBE_ARGS, cand_c,
@@ -1298,8 +1318,8 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
             dfree(t, res->d_hits); dfree(t, res->d_hit_slots);
             res->d_hits = nullptr; res->d_hit_slots = nullptr;
         } else {
-            st.windows_valid = counters ? (int64_t)h_tot[2] : -1;
-            st.slots_inspected = counters ? (int64_t)h_tot[3] : -1;
+            st.windows_valid = part_counters ? (int64_t)h_tot[2] : -1;
+            st.slots_inspected = part_counters ? (int64_t)h_tot[3] : -1;
             st.lookup_ran_off = h_tot[5] ? 1 : 0;
             if (windows) {
                 double ratio = (double)n_hits / (double)windows * 1.1 + 1e-3;
@@ -1400,6 +1420,9 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
     }
     }
     if (progress) {
+        // the certain misses' walks of the byte home index pass (all chunks are behind us: stream2 and stream3 were joined)
+        if (part_done && prog_index)
+            hipLaunchKernelGGL(kg::progress_finish_kernel, dim3(1), dim3(256), 0, t->stream, d_prog, t->d_tags, t->limit);
         // kmersFound / found-so-far: the distinct slots of the hit records (a bitmap over the stream's slots)
         uint32_t *d_bitmap = nullptr;
         const uint64_t n_words = (t->limit + 31) / 32 + 1;
