@@ -5,7 +5,9 @@
  * This is the drop-in boundary.  The reference has no FFI of its own (it is one Java class);
  * every entry point below names the reference interface it replaces.  "KGJ:n" =
  * lib/src/kmergutsjava/KmerGutsJava.java line n of the reference.  The Java (JNA) and Python
- * (ctypes) bindings that call these are shown in INTEGRATION.md.
+ * (ctypes) bindings that call these are shown in INTEGRATION.md.  Beyond the reference, the library also makes the
+ * tables it reads: kg_table_build* places a signature list the way the lookup finds it, kg_table_save writes a resident
+ * table back to kmer.table.mem_map[.gz].
  *
  * Conventions: plain pointers and sizes only; every function returns an int status
  * (KG_OK == 0, negative == error) and never throws or aborts across the boundary; the text
@@ -188,6 +190,32 @@ int kg_table_from_memory(const void *image, size_t nbytes, int device, kg_table 
 /* Adopt num_sigs 24-byte entries that already sit in device memory (not copied, not freed; must stay
  * unchanged while the table lives).  Synchronises the device once before reading them. */
 int kg_table_from_device(const void *d_entries, int64_t num_sigs, int device, kg_table **out);
+/* ---- building a table: a signature list -> the records of kmer.table.mem_map, and a resident table -> a file ---- */
+typedef struct kg_signature {    /* 24 B: the layout of one kmer.table.mem_map record (KGJ:995-999) */
+    int64_t kmer;                /* encodedKmer (KGJ:274-292), 0 <= kmer < 20^8 */
+    int32_t otu_index, avg_from_end, function_index;
+    float   function_wt;
+} kg_signature;
+/* Place n signatures (any order) into a table of num_sigs slots the way the reference's lookup finds them (KGJ:944-1034):
+ * home = kmer % num_sigs; in (home, kmer) order each signature takes slot pos = max(home, previous pos + 1); a signature
+ * with pos >= num_sigs is dropped; every other slot holds the empty record (whichKmer = 20^8 + 1, all other bytes 0).
+ * Header {num_sigs, 24, 1}.  The records equal kmergutsjava_amd.synth.build_table's byte for byte.  *n_placed = signatures
+ * placed (= kg_table_info's occupied).  KG_ERR_ARG: a k-mer outside [0, 20^8) (the message names the smallest such input
+ * index), a k-mer that occurs twice (the message names the smallest one), num_sigs <= 0; KG_ERR_LIMIT: n >= 2^32;
+ * KG_ERR_NOMEM.  n = 0 gives an all-empty table.  kg_table_build reads a host array (pageable or pinned), uploaded through
+ * pinned pieces; kg_table_build_device an 8-byte aligned device array, complete before the call (the device is synchronised
+ * once).  Scratch (about 24 bytes per signature) is returned to the driver before the call returns.  KG_TEST_FAIL_ALLOC
+ * applies to the build's device allocations. */
+int kg_table_build(const kg_signature *sigs, int64_t n, int64_t num_sigs, int device, int64_t *n_placed, kg_table **out);
+int kg_table_build_device(const kg_signature *d_sigs, int64_t n, int64_t num_sigs, int device, int64_t *n_placed, kg_table **out);
+/* Write the table to <path>: the header, then every whole record that is resident -- a table opened from a plain file saves
+ * to that file's bytes cut to whole records.  gzip when <path> ends in ".gz".  Written under a temporary name next to
+ * <path> and renamed: a failed save (KG_ERR_IO) leaves no file under <path>.  KG_ERR_BUSY while a kg_scan* is in flight. */
+int kg_table_save(kg_table *t, const char *path);
+/* the resident 24-byte records, valid until kg_table_close, and how many there are: num_sigs for a built or adopted table, the
+ * whole records of the file for an opened one (fewer than num_sigs for a truncated file, more for a longer one) */
+const void *kg_table_device_entries(const kg_table *t);
+int64_t kg_table_records(const kg_table *t);
 /* header fields (KmerMemoryInfo, KGJ:1194-1198) and the number of occupied slots */
 int kg_table_info(const kg_table *t, int64_t *num_sigs, int64_t *entry_size, int64_t *version, int64_t *occupied);
 /* Bytes of device scratch / result blocks the table's block cache has handed out and not got back: the blocks of the

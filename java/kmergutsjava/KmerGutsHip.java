@@ -70,6 +70,12 @@ public interface KmerGutsHip extends Library {
     int kg_table_open(String path, int device, PointerByReference out);
     int kg_table_from_memory(Pointer image, long nbytes, int device, PointerByReference out);
     int kg_table_from_device(Pointer dEntries, long numSigs, int device, PointerByReference out);
+    /** sigs: n packed 24-byte kg_signature records (long kmer, int otu_index, avg_from_end, function_index, float function_wt). */
+    int kg_table_build(Pointer sigs, long n, long numSigs, int device, long[] nPlaced, PointerByReference out);
+    int kg_table_build_device(Pointer dSigs, long n, long numSigs, int device, long[] nPlaced, PointerByReference out);
+    int kg_table_save(Pointer table, String path);
+    Pointer kg_table_device_entries(Pointer table);
+    long kg_table_records(Pointer table);
     int kg_table_info(Pointer table, long[] numSigs, long[] entrySize, long[] version, long[] occupied);
     long kg_table_live_device_bytes(Pointer table);
     void kg_table_close(Pointer table);

@@ -14,7 +14,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KG_LIB_PATH") or os.path.join(HERE, "libkmerguts_hip.so")   # KG_LIB_PATH: tuning builds only
 
 KG_OK = 0
+KG_ERR_ARG = -1
+KG_ERR_IO = -2
 KG_ERR_NOMEM = -5
+KG_ERR_LIMIT = -7
 KG_ERR_BUSY = -8
 KG_F_COUNTERS = 1
 KG_F_SKIP_AGGREGATE = 2
@@ -23,7 +26,8 @@ KG_OI_BUFSZ = 5
 
 # every symbol include/kmerguts_hip.h declares
 EXPORTS = (
-    "kg_table_open", "kg_table_from_memory", "kg_table_from_device", "kg_table_info", "kg_table_live_device_bytes", "kg_table_close",
+    "kg_table_open", "kg_table_from_memory", "kg_table_from_device", "kg_table_build", "kg_table_build_device", "kg_table_save",
+    "kg_table_device_entries", "kg_table_records", "kg_table_info", "kg_table_live_device_bytes", "kg_table_close",
     "kg_scan", "kg_scan_device", "kg_aggregate_hits", "kg_process_set_of_hits", "kg_result_stats", "kg_result_hits", "kg_result_container_hit_start",
     "kg_result_calls", "kg_result_container_call_start", "kg_result_otu", "kg_result_hit_events",
     "kg_result_container_tail_events", "kg_result_copy_hits", "kg_result_hit_slots", "kg_result_progress", "kg_result_device_hits", "kg_result_device_calls", "kg_result_device_otu",
@@ -41,6 +45,10 @@ HIT_DTYPE = np.dtype([("container", "<u4"), ("from0InProt", "<i4"), ("oI", "<i4"
 CALL_DTYPE = np.dtype([("container", "<u4"), ("start", "<i4"), ("end", "<i4"), ("count", "<i4"),
                        ("fI", "<i4"), ("weightedHits", "<f4")])
 OTU_DTYPE = np.dtype([("n", "<i4"), ("count", "<i4", (KG_OI_BUFSZ,)), ("oI", "<i4", (KG_OI_BUFSZ,))])
+# struct kg_signature: the field layout of one kmer.table.mem_map record (KGJ:995-999)
+SIGNATURE_DTYPE = np.dtype([("kmer", "<i8"), ("otuIndex", "<i4"), ("avgFromEnd", "<i4"), ("functionIndex", "<i4"),
+                            ("functionWt", "<f4")])
+assert SIGNATURE_DTYPE.itemsize == 24
 assert HIT_DTYPE.itemsize == 24 and CALL_DTYPE.itemsize == 24 and OTU_DTYPE.itemsize == 44
 
 
@@ -108,6 +116,13 @@ def load() -> C.CDLL:
     lib.kg_table_open.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
     lib.kg_table_from_memory.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp)]
     lib.kg_table_from_device.argtypes = [vp, C.c_int64, C.c_int, C.POINTER(vp)]
+    lib.kg_table_build.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, i64p, C.POINTER(vp)]
+    lib.kg_table_build_device.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, i64p, C.POINTER(vp)]
+    lib.kg_table_save.argtypes = [vp, C.c_char_p]
+    lib.kg_table_device_entries.argtypes = [vp]
+    lib.kg_table_device_entries.restype = vp
+    lib.kg_table_records.argtypes = [vp]
+    lib.kg_table_records.restype = C.c_int64
     lib.kg_table_info.argtypes = [vp, i64p, i64p, i64p, i64p]
     lib.kg_table_live_device_bytes.argtypes = [vp]
     lib.kg_table_live_device_bytes.restype = C.c_int64

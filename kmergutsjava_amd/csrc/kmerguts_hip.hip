@@ -9,8 +9,10 @@
 #include "kg_aggregate.hpp"
 #include "kg_partition.hpp"
 #include "kg_order.hpp"
+#include "kg_build.hpp"
 
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 #include <zlib.h>
 
@@ -90,6 +92,12 @@ struct DevCache {
         if (it == live.end()) return;
         free_.emplace(it->second, p);
         live.erase(it);
+    }
+    // hand a live block over to its user for good (kg_table_build: the table's records, freed with hipFree by kg_table_close)
+    void detach(void *p)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        live.erase(p);
     }
     size_t live_bytes()
     {
@@ -1771,5 +1779,322 @@ const void *kg_result_device_calls(const kg_result *r) { return r ? r->d_calls :
 const void *kg_result_device_otu(const kg_result *r) { return r ? r->d_otu : nullptr; }
 const void *kg_result_device_container_hit_start(const kg_result *r) { return r ? r->d_chs : nullptr; }
 const void *kg_result_device_container_call_start(const kg_result *r) { return r ? r->d_ccs : nullptr; }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// kg_table_build / kg_table_build_device / kg_table_save: a signature list -> a resident table (kernels: kg_build.hpp), and a
+// resident table -> kmer.table.mem_map[.gz].
+namespace {
+
+uint64_t magic_of(uint64_t d)
+{
+    return d == 1 ? ~0ull : (uint64_t)(((unsigned __int128)1 << 64) / d);
+}
+
+std::string kmer_text(int64_t v)
+{
+    char b[32];
+    snprintf(b, sizeof b, "%lld", (long long)v);
+    return b;
+}
+
+// Host signatures -> d_dst (n * 24 bytes) through pinned pieces: several threads copy disjoint 32 MiB pieces of the caller's
+// (possibly pageable) buffer into two pinned buffers each and hand them to the copy engine, as kg_table_open does.
+int upload_signatures(kg_table *t, const uint8_t *src, size_t bytes, uint8_t *d_dst)
+{
+    const size_t CH = 32u << 20;
+    const size_t n_pieces = (bytes + CH - 1) / CH;
+    const unsigned hw = std::thread::hardware_concurrency();
+    const size_t n_thr = std::max<size_t>(1, std::min<size_t>({(size_t)8, (size_t)(hw ? hw : 4), n_pieces}));
+    std::atomic<size_t> next{0};
+    std::atomic<bool> ok{true};
+    auto worker = [&]() {
+        if (hipSetDevice(t->device) != hipSuccess) { ok = false; return; }
+        hipStream_t s = nullptr;
+        uint8_t *pin[2] = {nullptr, nullptr};
+        hipEvent_t done[2] = {nullptr, nullptr};
+        bool good = hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess &&
+                    hipHostMalloc((void **)&pin[0], CH) == hipSuccess && hipHostMalloc((void **)&pin[1], CH) == hipSuccess &&
+                    hipEventCreate(&done[0]) == hipSuccess && hipEventCreate(&done[1]) == hipSuccess;
+        bool used[2] = {false, false};
+        int which = 0;
+        while (good && ok.load()) {
+            const size_t k = next.fetch_add(1);
+            if (k >= n_pieces) break;
+            const size_t at = k * CH, n = std::min(CH, bytes - at);
+            if (used[which]) good = hipEventSynchronize(done[which]) == hipSuccess;
+            if (!good) break;
+            memcpy(pin[which], src + at, n);
+            good = hipMemcpyAsync(d_dst + at, pin[which], n, hipMemcpyHostToDevice, s) == hipSuccess &&
+                   hipEventRecord(done[which], s) == hipSuccess;
+            used[which] = true;
+            which ^= 1;
+        }
+        if (s && hipStreamSynchronize(s) != hipSuccess) good = false;
+        if (!good) ok = false;
+        for (int i = 0; i < 2; i++) { if (pin[i]) (void)hipHostFree(pin[i]); if (done[i]) (void)hipEventDestroy(done[i]); }
+        if (s) (void)hipStreamDestroy(s);
+    };
+    {
+        std::vector<std::thread> pool;
+        for (size_t i = 1; i < n_thr; i++) pool.emplace_back(worker);
+        worker();
+        for (auto &th : pool) th.join();
+    }
+    return ok.load() ? KG_OK : fail(KG_ERR_DEVICE, "uploading the signatures failed (pinned staging or host-to-device copy)");
+}
+
+// Everything up to table_finish.  Scratch comes from the table's block cache (dalloc: KG_TEST_FAIL_ALLOC applies) and is
+// back in it when this returns; the records are taken out of the cache and owned by the table.
+int build_records(kg_table *t, const uint8_t *h_sigs, const uint8_t *d_sigs, uint64_t n, uint64_t *n_placed, float ms[4])
+{
+    const uint64_t S = (uint64_t)t->num_sigs;
+    Scratch sc(t);
+    {
+        void *e = nullptr;
+        int rc = dalloc(t, &e, (S * 24 + 15) / 16 * 16);
+        if (rc) return rc;
+        t->cache.detach(e);
+        t->d_entries = (uint8_t *)e;
+        t->own_entries = true;
+    }
+    int rc;
+    if (h_sigs && n) {
+        uint8_t *d = nullptr;
+        if ((rc = sc.get(&d, n * 24))) return rc;
+        if ((rc = upload_signatures(t, h_sigs, n * 24, d))) return rc;
+        d_sigs = d;
+    }
+    hipEvent_t ev[5];
+    for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 5; i++) (void)hipEventDestroy(e[i]); } } ev_guard{ev};
+    // (home, kmer) order == (home, q) order; c = home * Q + q < 20^8 + S
+    const uint64_t Q = (uint64_t)(KG_MAX_ENCODED - 1) / S + 1, magic = magic_of(S), magic_q = magic_of(Q);
+    const uint64_t c_max = (uint64_t)((unsigned __int128)S * Q - 1);
+    uint32_t key_bits = 1;
+    while (key_bits < 64 && (c_max >> key_bits) != 0) key_bits++;
+    const uint32_t n_tiles = (uint32_t)((n + kg::kBuildTile - 1) / kg::kBuildTile);
+    unsigned long long *d_cnt = nullptr;                // [0] first bad index, [1] smallest duplicate, [2] placed
+    if ((rc = sc.get(&d_cnt, 4))) return rc;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0xFF, 16, t->stream));
+    HIP_TRY(hipMemsetAsync(d_cnt + 2, 0, 8, t->stream));
+    HIP_TRY(hipEventRecord(ev[0], t->stream));
+    uint64_t *keys[2] = {nullptr, nullptr};
+    uint32_t *vals[2] = {nullptr, nullptr};
+    int cur = 0;
+    if (n) {
+        if ((rc = sc.get(&keys[0], n)) || (rc = sc.get(&vals[0], n))) return rc;
+        const uint64_t want = (n + kg::kBuildThreads - 1) / kg::kBuildThreads;
+        hipLaunchKernelGGL(kg::build_keys_kernel, dim3((uint32_t)std::min<uint64_t>(want, 256ull * 32)), dim3(kg::kBuildThreads), 0,
+                           t->stream, d_sigs, n, S, magic, Q, keys[0], vals[0], d_cnt);
+        HIP_TRY(hipGetLastError());
+        unsigned long long bad = 0;
+        HIP_TRY(hipMemcpyAsync(&bad, d_cnt, 8, hipMemcpyDeviceToHost, t->stream));
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        if (bad != ~0ull) {
+            int64_t kmer = 0;
+            if (h_sigs) memcpy(&kmer, h_sigs + bad * 24, 8);
+            else HIP_TRY(hipMemcpy(&kmer, d_sigs + bad * 24, 8, hipMemcpyDeviceToHost));
+            return fail(KG_ERR_ARG, "signature " + kmer_text((int64_t)bad) + ": k-mer " + kmer_text(kmer) +
+                                        " is outside [0, 20^8) (the smallest such input index)");
+        }
+        if (n > 1) {
+            const uint32_t passes = (key_bits + 7) / 8, bits = (key_bits + passes - 1) / passes, radix = 1u << bits;
+            const uint64_t n_hist = (uint64_t)radix * n_tiles;
+            const uint64_t nb = (n_hist + kg::kScanChunk - 1) / kg::kScanChunk;
+            uint32_t *hist = nullptr, *offs = nullptr;
+            uint64_t *partial = nullptr;
+            if ((rc = sc.get(&keys[1], n)) || (rc = sc.get(&vals[1], n)) || (rc = sc.get(&hist, n_hist)) ||
+                (rc = sc.get(&offs, n_hist)) || (rc = sc.get(&partial, nb + 2)))
+                return rc;
+            for (uint32_t p = 0; p < passes; p++) {
+                const uint32_t shift = p * bits;
+                hipLaunchKernelGGL(kg::build_hist_kernel, dim3(n_tiles), dim3(kg::kBuildThreads), 0, t->stream, keys[cur], n, shift, radix,
+                                   n_tiles, hist);
+                HIP_TRY(hipGetLastError());
+                if ((rc = prefix_sum(t, hist, n_hist, offs, partial, partial + nb + 1))) return rc;
+                hipLaunchKernelGGL(kg::build_scatter_kernel, dim3(n_tiles), dim3(kg::kBuildThreads), 0, t->stream, keys[cur], vals[cur], n,
+                                   shift, bits, n_tiles, offs, keys[cur ^ 1], vals[cur ^ 1]);
+                HIP_TRY(hipGetLastError());
+                cur ^= 1;
+            }
+        }
+    }
+    HIP_TRY(hipEventRecord(ev[1], t->stream));
+    int64_t *tile_max = nullptr, *tile_pre = nullptr;
+    if (n) {
+        if ((rc = sc.get(&tile_max, n_tiles)) || (rc = sc.get(&tile_pre, n_tiles))) return rc;
+        hipLaunchKernelGGL(kg::build_tile_max_kernel, dim3(n_tiles), dim3(kg::kBuildThreads), 0, t->stream, keys[cur], n, Q, magic_q, S,
+                           tile_max, d_cnt + 1);
+        hipLaunchKernelGGL(kg::build_tile_scan_kernel, dim3(1), dim3(kg::kBuildThreads), 0, t->stream, tile_max, n_tiles, tile_pre);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(ev[2], t->stream));
+    const uint64_t n_chunks = (S * 24 + 15) / 16;
+    hipLaunchKernelGGL(kg::build_fill_kernel, dim3((uint32_t)std::min<uint64_t>((n_chunks + 255) / 256, 256ull * 64)),
+                       dim3(kg::kBuildThreads), 0, t->stream, (uint4 *)t->d_entries, n_chunks);
+    HIP_TRY(hipGetLastError());
+    if (n) {
+        hipLaunchKernelGGL(kg::build_place_kernel, dim3(n_tiles), dim3(kg::kBuildThreads), 0, t->stream, keys[cur], vals[cur], n, Q,
+                           magic_q, tile_pre, d_sigs, S, t->d_entries, d_cnt + 2);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(ev[3], t->stream));
+    unsigned long long cnt[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, d_cnt, 24, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    if (cnt[1] != ~0ull)
+        return fail(KG_ERR_ARG, "duplicate k-mer " + kmer_text((int64_t)cnt[1]) + " (the smallest k-mer that occurs more than once)");
+    for (int i = 0; i < 3; i++) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    *n_placed = cnt[2];
+    return KG_OK;
+}
+
+int build_entry(const uint8_t *h_sigs, const uint8_t *d_sigs, int64_t n, int64_t num_sigs, int device, int64_t *n_placed, kg_table **out)
+{
+    if (!out) return fail(KG_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (n < 0) return fail(KG_ERR_ARG, "n < 0");
+    if (num_sigs <= 0) return fail(KG_ERR_ARG, "num_sigs <= 0");
+    if ((uint64_t)n >= (1ull << 32)) return fail(KG_ERR_LIMIT, "kg_table_build: 2^32 or more signatures in one call");
+    if (n > 0 && !h_sigs && !d_sigs) return fail(KG_ERR_ARG, "null signature array");
+    if (d_sigs && ((uintptr_t)d_sigs & 7)) return fail(KG_ERR_ARG, "kg_table_build_device: the signatures must be 8-byte aligned");
+    if ((uint64_t)num_sigs > (~0ull >> 1) / 24) return fail(KG_ERR_LIMIT, "num_sigs too large");
+    kg_table *t = nullptr;
+    int rc = table_new(device, &t);
+    if (rc) return rc;
+    t->num_sigs = num_sigs;
+    t->entry_size = KG_TABLE_ENTRY_SIZE;
+    t->version = 1;
+    t->limit = (uint64_t)num_sigs;
+    t->fail_alloc_at = test_hook("KG_TEST_FAIL_ALLOC");
+    t->alloc_count = 0;
+    // a device input may still be written by another (blocking or non-blocking) stream
+    if (d_sigs && hipDeviceSynchronize() != hipSuccess) { kg_table_close(t); return fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed"); }
+    uint64_t placed = 0;
+    float ms[5] = {0, 0, 0, 0, 0};
+    rc = build_records(t, h_sigs, d_sigs, (uint64_t)n, &placed, ms);
+    t->fail_alloc_at = 0;
+    t->cache.release_all();                             // the build's scratch goes back to the driver, not to the table
+    if (rc) { kg_table_close(t); return rc; }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const bool timed = getenv("KG_DEBUG") && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess &&
+                       hipEventRecord(e0, t->stream) == hipSuccess;
+    rc = table_finish(t);
+    if (timed && rc == KG_OK && hipEventRecord(e1, t->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess)
+        (void)hipEventElapsedTime(&ms[3], e0, e1);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (rc) { kg_table_close(t); return rc; }
+    if (getenv("KG_DEBUG"))
+        fprintf(stderr, "[kg] kg_table_build: n=%lld num_sigs=%lld placed=%llu sort_ms=%.3f place_ms=%.3f fill_scatter_ms=%.3f finish_ms=%.3f\n",
+                (long long)n, (long long)num_sigs, (unsigned long long)placed, ms[0], ms[1], ms[2], ms[3]);
+    if (n_placed) *n_placed = (int64_t)placed;
+    *out = t;
+    return KG_OK;
+}
+
+bool write_all(int fd, gzFile g, const uint8_t *p, size_t n)
+{
+    while (n) {
+        const size_t piece = std::min<size_t>(n, 1u << 30);
+        long got;
+        if (g) got = gzwrite(g, p, (unsigned)piece);
+        else got = (long)write(fd, p, piece);
+        if (got <= 0) {
+            if (!g && got < 0 && errno == EINTR) continue;
+            return false;
+        }
+        p += got;
+        n -= (size_t)got;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kg_table_build(const kg_signature *sigs, int64_t n, int64_t num_sigs, int device, int64_t *n_placed, kg_table **out)
+{
+    return build_entry((const uint8_t *)sigs, nullptr, n, num_sigs, device, n_placed, out);
+}
+
+int kg_table_build_device(const kg_signature *d_sigs, int64_t n, int64_t num_sigs, int device, int64_t *n_placed, kg_table **out)
+{
+    return build_entry(nullptr, (const uint8_t *)d_sigs, n, num_sigs, device, n_placed, out);
+}
+
+const void *kg_table_device_entries(const kg_table *t) { return t ? t->d_entries : nullptr; }
+int64_t kg_table_records(const kg_table *t) { return t ? (int64_t)t->limit : 0; }
+
+int kg_table_save(kg_table *t, const char *path)
+{
+    if (!t || !path) return fail(KG_ERR_ARG, "null argument");
+    if (t->busy.exchange(1) != 0) return fail(KG_ERR_BUSY, "a kg_scan* is in flight on this kg_table");
+    struct BusyGuard { kg_table *t; ~BusyGuard() { t->busy.store(0); } } busy_guard{t};
+    HIP_TRY(hipSetDevice(t->device));
+    const size_t plen = strlen(path);
+    const bool gz = plen >= 3 && strcmp(path + plen - 3, ".gz") == 0;
+    // written under a temporary name next to the target and renamed at the end: a failed save leaves no file under `path`
+    std::string tmp = std::string(path) + ".tmpXXXXXX";
+    const int fd = mkstemp(&tmp[0]);
+    if (fd < 0) return fail(KG_ERR_IO, std::string("cannot create a file next to ") + path + ": " + strerror(errno));
+    const mode_t um = umask(0);
+    umask(um);
+    (void)fchmod(fd, 0666 & ~um);
+    gzFile g = nullptr;
+    bool ok = true;
+    std::string why;
+    if (gz) {
+        g = gzdopen(fd, "wb1");
+        if (!g) { ok = false; why = "gzdopen failed"; }
+    }
+    uint8_t hdr[24];
+    const int64_t h3[3] = {t->num_sigs, t->entry_size, t->version};
+    for (int f = 0; f < 3; f++)
+        for (int b = 0; b < 8; b++) hdr[f * 8 + b] = (uint8_t)((uint64_t)h3[f] >> (8 * b));
+    if (ok && !write_all(fd, g, hdr, 24)) { ok = false; why = strerror(errno); }
+    // the records come down through two of the table's pinned blocks: piece k + 1 is copied while piece k is written
+    const size_t bytes = (size_t)t->limit * KG_TABLE_ENTRY_SIZE, CH = 32u << 20;
+    const size_t n_pieces = (bytes + CH - 1) / CH;
+    void *pin[2] = {nullptr, nullptr};
+    hipEvent_t done[2] = {nullptr, nullptr};
+    if (ok && n_pieces) {
+        ok = t->pins.get(&pin[0], CH) == hipSuccess && t->pins.get(&pin[1], CH) == hipSuccess &&
+             hipEventCreateWithFlags(&done[0], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&done[1], hipEventDisableTiming) == hipSuccess;
+        if (!ok) why = "pinned staging allocation failed";
+    }
+    auto issue = [&](size_t k) {
+        const size_t at = k * CH, n = std::min(CH, bytes - at);
+        return hipMemcpyAsync(pin[k & 1], t->d_entries + at, n, hipMemcpyDeviceToHost, t->stream) == hipSuccess &&
+               hipEventRecord(done[k & 1], t->stream) == hipSuccess;
+    };
+    if (ok && n_pieces && !issue(0)) { ok = false; why = "device-to-host copy failed"; }
+    for (size_t k = 0; ok && k < n_pieces; k++) {
+        if (k + 1 < n_pieces && !issue(k + 1)) { ok = false; why = "device-to-host copy failed"; break; }
+        if (hipEventSynchronize(done[k & 1]) != hipSuccess) { ok = false; why = "device-to-host copy failed"; break; }
+        if (!write_all(fd, g, (const uint8_t *)pin[k & 1], std::min(CH, bytes - k * CH))) { ok = false; why = strerror(errno); }
+    }
+    (void)hipStreamSynchronize(t->stream);
+    for (int i = 0; i < 2; i++) {
+        if (pin[i]) t->pins.put(pin[i]);
+        if (done[i]) (void)hipEventDestroy(done[i]);
+    }
+    if (g) {
+        if (gzclose(g) != Z_OK && ok) { ok = false; why = "gzip stream could not be completed"; }
+    } else if (close(fd) != 0 && ok) {
+        ok = false;
+        why = strerror(errno);
+    }
+    if (ok && rename(tmp.c_str(), path) != 0) { ok = false; why = std::string("rename: ") + strerror(errno); }
+    if (!ok) {
+        (void)unlink(tmp.c_str());
+        return fail(KG_ERR_IO, std::string("writing ") + path + " failed" + (why.empty() ? std::string() : ": " + why));
+    }
+    return KG_OK;
+}
 
 }  // extern "C"

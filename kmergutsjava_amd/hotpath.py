@@ -8,6 +8,7 @@ libkmerguts_hip.so on the GPU; this file only moves pointers.
 from __future__ import annotations
 
 import ctypes as C
+import os
 import weakref
 from dataclasses import dataclass
 from typing import Optional
@@ -248,6 +249,49 @@ class SignatureTable:
         out = C.c_void_p()
         N.check(N.load().kg_table_from_device(C.c_void_p(ptr), num_sigs, device, C.byref(out)))
         return cls(out.value, keepalive)
+
+    @classmethod
+    def build(cls, signatures, num_sigs: int, device: int = 0) -> "SignatureTable":
+        """Place a signature list into a table of num_sigs slots the way the reference's lookup finds them (no-wrap linear
+        probing in (kmer % num_sigs, kmer) order; include/kmerguts_hip.h kg_table_build).  signatures: a numpy array of
+        _native.SIGNATURE_DTYPE or raw bytes of 24-byte records (kg_table_build), or a contiguous CUDA tensor of 24 * n
+        bytes (kg_table_build_device).  The number placed is `placed` on the result (= info()["occupied"])."""
+        out, placed = C.c_void_p(), C.c_int64()
+        lib = N.load()
+        if hasattr(signatures, "is_cuda") and signatures.is_cuda:
+            if not signatures.is_contiguous():
+                raise ValueError("the signature tensor must be contiguous")
+            nbytes = signatures.numel() * signatures.element_size()
+            if nbytes % 24:
+                raise ValueError("the signature tensor must hold 24 * n bytes")
+            dev = signatures.device.index if signatures.device.index is not None else device
+            N.check(lib.kg_table_build_device(C.c_void_p(signatures.data_ptr() if nbytes else None), nbytes // 24, int(num_sigs),
+                                              dev, C.byref(placed), C.byref(out)))
+        else:
+            arr = signatures if isinstance(signatures, np.ndarray) else np.frombuffer(signatures, dtype=np.uint8)
+            arr = np.ascontiguousarray(arr)
+            if arr.dtype != N.SIGNATURE_DTYPE:
+                arr = arr.reshape(-1).view(np.uint8)
+                if arr.size % 24:
+                    raise ValueError("signature bytes must be a multiple of 24")
+            n = arr.nbytes // 24
+            N.check(lib.kg_table_build(arr.ctypes.data if n else None, n, int(num_sigs), device, C.byref(placed), C.byref(out)))
+        tab = cls(out.value)
+        tab.placed = int(placed.value)
+        return tab
+
+    def save(self, path: str) -> None:
+        """Write kmer.table.mem_map (gzip when path ends in .gz): the header and every whole record that is resident."""
+        if not self._h:
+            raise ValueError("SignatureTable is closed")
+        N.check(N.load().kg_table_save(self._h, os.fspath(path).encode()))
+
+    def device_entries(self):
+        """Zero-copy torch view (uint8, 24 bytes per record) of the resident records, valid until close()."""
+        if not self._h:
+            raise ValueError("SignatureTable is closed")
+        lib = N.load()
+        return device_tensor(lib.kg_table_device_entries(self._h) or 0, int(lib.kg_table_records(self._h)) * 24, "|u1", owner=self)
 
     def info(self) -> dict:
         a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
