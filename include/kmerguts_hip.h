@@ -7,7 +7,7 @@
  * lib/src/kmergutsjava/KmerGutsJava.java line n of the reference.  The Java (JNA) and Python
  * (ctypes) bindings that call these are shown in INTEGRATION.md.  Beyond the reference, the library also makes the
  * tables it reads: kg_table_build* places a signature list the way the lookup finds it, kg_table_save writes a resident
- * table back to kmer.table.mem_map[.gz].
+ * table back to kmer.table.mem_map[.gz], and kg_signatures_derive* makes that list from annotated proteins.
  *
  * Conventions: plain pointers and sizes only; every function returns an int status
  * (KG_OK == 0, negative == error) and never throws or aborts across the boundary; the text
@@ -212,6 +212,76 @@ int kg_table_build_device(const kg_signature *d_sigs, int64_t n, int64_t num_sig
  * to that file's bytes cut to whole records.  gzip when <path> ends in ".gz".  Written under a temporary name next to
  * <path> and renamed: a failed save (KG_ERR_IO) leaves no file under <path>.  KG_ERR_BUSY while a kg_scan* is in flight. */
 int kg_table_save(kg_table *t, const char *path);
+/* ---- deriving the signatures: annotated proteins -> the signature k-mers of a table (kernels: kg_derive.hpp) ----
+ *
+ * Input: n_prot proteins as raw characters seq plus offsets[n_prot + 1] (host, non-decreasing), the layout of kg_scan.  Each
+ * protein p has a function index fn[p] and an OTU index otu[p] (host arrays).  fn[p] is -1 for an unannotated protein,
+ * otherwise >= 0.  otu[p] must be >= 0 where fn[p] >= 0, and is ignored otherwise.  len_p = offsets[p+1] - offsets[p].
+ *
+ *   Windows: exactly the windows an -a scan sees: toAminoAcidOff codes, positions i in [0, len_p - 8) (the reference's
+ *   off-by-one bound, KGJ:912), windows containing a code >= 20 skipped (KGJ:283-285); the device encode is the scan's own
+ *   (encode_init / encode_block<true>).
+ *   For a k-mer v: P(v) is the set of distinct proteins with a window equal to v, and n_v = |P(v)|.  Unannotated proteins
+ *   count in n_v.  i_p(v) is the smallest position of v in protein p.  c_f is the number of proteins in P(v) with fn = f.
+ *   f* is the f >= 0 with the largest c_f.  On a tie, take the smallest f.
+ *   v is a signature iff both of these hold: f* exists and n_v >= min_proteins; 100 * c_f* >= purity_pct * n_v, computed in
+ *   int64.
+ *   Fields of the emitted kg_signature:
+ *     kmer = v;  function_index = f*;
+ *     otu_index = the most frequent otu[p] among the proteins of P(v) with fn = f*.  On a tie, take the smallest.
+ *     avg_from_end = floor(sum (len_p - i_p(v)) / c_f*) over the same proteins.  This is consistent with the -O check
+ *       |dpos - (last.avgOffFromEnd - ph.avgOffFromEnd)| <= 20 (KGJ:490-494).
+ *     function_wt = the float32 quotient (float)c_f* / (float)n_v, correctly rounded (numpy's np.float32(c) / np.float32(n);
+ *       __fdiv_rn on the device).
+ *   Output: the signatures in ascending kmer order.  The output depends only on the multiset of (sequence, fn, otu).  It does
+ *   not depend on protein order, pass count or launch geometry.
+ *
+ * Parameters: min_proteins >= 1, 1 <= purity_pct <= 100.  max_windows_per_pass = 0: the library sizes the pass from free device
+ * memory (about 160 bytes per valid window); any other value caps the valid windows held at once (values above 2^32 - 2^22 act
+ * as that limit).  The k-mer space is then processed in several passes over k-mer ranges, with range bounds taken from a
+ * histogram of the windows' leading digits (refined where one bin alone is over the cap).  If one k-mer alone exceeds the
+ * cap, the call returns KG_ERR_LIMIT and says so.
+ * Limits (KG_ERR_LIMIT): n_prot < 2^29, len_p < 2^31, fewer than 2^31 window blocks of 64 windows, fewer than 2^32 signatures.
+ * KG_ERR_ARG: fn < -1, otu < 0 on an annotated protein, decreasing offsets (each message names the first offending protein),
+ * bad parameters, null pointers.  KG_ERR_NOMEM.  KG_TEST_FAIL_ALLOC applies to the call's device allocations; scratch goes back
+ * to the driver before the call returns.
+ * kg_signatures_derive reads a host sequence, uploaded through pinned pieces; kg_signatures_derive_device a device sequence
+ * (complete before the call: the device is synchronised once); offsets, fn and otu are host arrays in both. */
+typedef struct kg_derive_params {
+    int32_t min_proteins;            /* >= 1 (this project's default: 2)     */
+    int32_t purity_pct;              /* 1..100 (this project's default: 80)  */
+    int64_t max_windows_per_pass;    /* 0: sized from free device memory     */
+} kg_derive_params;
+
+typedef struct kg_derive_stats {
+    int64_t proteins;                /* n_prot                                                        */
+    int64_t windows;                 /* sum over proteins of max(len_p - 8, 0)                        */
+    int64_t valid_windows;           /* windows without a code >= 20                                  */
+    int64_t pairs;                   /* distinct (k-mer, protein) pairs                               */
+    int64_t kmers;                   /* distinct k-mers                                               */
+    int64_t signatures;
+    int32_t passes;                  /* k-mer range passes                                            */
+    float   ms_encode;               /* histograms + encode / emit kernels                            */
+    float   ms_sort;                 /* protein ranking + the window sorts                            */
+    float   ms_reduce;               /* collapse, run reductions, selection, compaction               */
+    float   ms_total;                /* the call, after the upload of the sequence, to its last kernel */
+} kg_derive_stats;
+
+typedef struct kg_sigset kg_sigset;
+
+int kg_signatures_derive(int device, const kg_derive_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
+                         const int32_t *fn, const int32_t *otu, kg_sigset **out);
+int kg_signatures_derive_device(int device, const kg_derive_params *p, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
+                                const int32_t *fn, const int32_t *otu, kg_sigset **out);
+int64_t kg_sigset_count(const kg_sigset *s);
+/* device array of kg_sigset_count(s) kg_signature records (8-byte aligned), valid until kg_sigset_free: kg_table_build_device
+ * takes it as it is */
+const kg_signature *kg_sigset_device(const kg_sigset *s);
+/* records [first, first + count) into dst (host or device memory) */
+int kg_sigset_copy(const kg_sigset *s, int64_t first, int64_t count, kg_signature *dst);
+int kg_sigset_stats(const kg_sigset *s, kg_derive_stats *out);
+void kg_sigset_free(kg_sigset *s);
+
 /* the resident 24-byte records, valid until kg_table_close, and how many there are: num_sigs for a built or adopted table, the
  * whole records of the file for an opened one (fewer than num_sigs for a truncated file, more for a longer one) */
 const void *kg_table_device_entries(const kg_table *t);

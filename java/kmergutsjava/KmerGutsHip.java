@@ -66,6 +66,26 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_derive_params (kg_signatures_derive*). */
+    class KgDeriveParams extends Structure {
+        public int min_proteins, purity_pct;
+        public long max_windows_per_pass;
+        public KgDeriveParams() {
+            setFieldOrder(new String[] {"min_proteins", "purity_pct", "max_windows_per_pass"});
+        }
+    }
+
+    /** struct kg_derive_stats */
+    class KgDeriveStats extends Structure {
+        public long proteins, windows, valid_windows, pairs, kmers, signatures;
+        public int passes;
+        public float ms_encode, ms_sort, ms_reduce, ms_total;
+        public KgDeriveStats() {
+            setFieldOrder(new String[] {"proteins", "windows", "valid_windows", "pairs", "kmers", "signatures", "passes", "ms_encode",
+                    "ms_sort", "ms_reduce", "ms_total"});
+        }
+    }
+
     // replaces readKmerTableHeader + the table stream of lookup (KmerGutsJava.java:924-942, 944-1034)
     int kg_table_open(String path, int device, PointerByReference out);
     int kg_table_from_memory(Pointer image, long nbytes, int device, PointerByReference out);
@@ -74,6 +94,16 @@ public interface KmerGutsHip extends Library {
     int kg_table_build(Pointer sigs, long n, long numSigs, int device, long[] nPlaced, PointerByReference out);
     int kg_table_build_device(Pointer dSigs, long n, long numSigs, int device, long[] nPlaced, PointerByReference out);
     int kg_table_save(Pointer table, String path);
+    /** annotated proteins -> signature set: fn[p] = -1 for an unannotated protein, otu[p] >= 0 where fn[p] >= 0. */
+    int kg_signatures_derive(int device, KgDeriveParams params, byte[] seq, long[] offsets, long nProt, int[] fn, int[] otu,
+                             PointerByReference out);
+    int kg_signatures_derive_device(int device, KgDeriveParams params, Pointer dSeq, long[] offsets, long nProt, int[] fn, int[] otu,
+                                    PointerByReference out);
+    long kg_sigset_count(Pointer set);
+    Pointer kg_sigset_device(Pointer set);                   // kg_signature[count] in device memory: kg_table_build_device takes it
+    int kg_sigset_copy(Pointer set, long first, long count, Pointer dst);
+    int kg_sigset_stats(Pointer set, KgDeriveStats out);
+    void kg_sigset_free(Pointer set);
     Pointer kg_table_device_entries(Pointer table);
     long kg_table_records(Pointer table);
     int kg_table_info(Pointer table, long[] numSigs, long[] entrySize, long[] version, long[] occupied);

@@ -32,6 +32,8 @@ EXPORTS = (
     "kg_result_calls", "kg_result_container_call_start", "kg_result_otu", "kg_result_hit_events",
     "kg_result_container_tail_events", "kg_result_copy_hits", "kg_result_hit_slots", "kg_result_progress", "kg_result_device_hits", "kg_result_device_calls", "kg_result_device_otu",
     "kg_result_device_container_hit_start", "kg_result_device_container_call_start", "kg_result_free", "kg_restore_hits_device",
+    "kg_signatures_derive", "kg_signatures_derive_device", "kg_sigset_count", "kg_sigset_device", "kg_sigset_copy",
+    "kg_sigset_stats", "kg_sigset_free",
     "kg_last_error", "kg_version",
 )
 
@@ -81,6 +83,21 @@ class KgProgress(C.Structure):
         return {"first_visited": [int(x) for x in self.first_visited], "last_visited": int(self.last_visited),
                 "first_beyond": int(self.first_beyond), "walk_ran_off": int(self.walk_ran_off), "stream_slots": int(self.stream_slots),
                 "found_upto": [int(x) for x in self.found_upto], "kmers_found": int(self.kmers_found)}
+
+
+class KgDeriveParams(C.Structure):
+    """struct kg_derive_params (kg_signatures_derive*)."""
+    _fields_ = [("min_proteins", C.c_int32), ("purity_pct", C.c_int32), ("max_windows_per_pass", C.c_int64)]
+
+
+class KgDeriveStats(C.Structure):
+    """struct kg_derive_stats."""
+    _fields_ = [("proteins", C.c_int64), ("windows", C.c_int64), ("valid_windows", C.c_int64), ("pairs", C.c_int64),
+                ("kmers", C.c_int64), ("signatures", C.c_int64), ("passes", C.c_int32), ("ms_encode", C.c_float),
+                ("ms_sort", C.c_float), ("ms_reduce", C.c_float), ("ms_total", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class KmerGutsNativeError(RuntimeError):
@@ -147,6 +164,16 @@ def load() -> C.CDLL:
     lib.kg_restore_hits_device.argtypes = [C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp]
     lib.kg_result_free.argtypes = [vp]
     lib.kg_result_free.restype = None
+    for name in ("kg_signatures_derive", "kg_signatures_derive_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgDeriveParams), vp, vp, C.c_int64, vp, vp, C.POINTER(vp)]
+    lib.kg_sigset_count.argtypes = [vp]
+    lib.kg_sigset_count.restype = C.c_int64
+    lib.kg_sigset_device.argtypes = [vp]
+    lib.kg_sigset_device.restype = vp
+    lib.kg_sigset_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.kg_sigset_stats.argtypes = [vp, C.POINTER(KgDeriveStats)]
+    lib.kg_sigset_free.argtypes = [vp]
+    lib.kg_sigset_free.restype = None
     lib.kg_last_error.restype = C.c_char_p
     lib.kg_version.restype = C.c_char_p
     for name in EXPORTS:

@@ -347,3 +347,92 @@ class SignatureTable:
             self.close()
         except Exception:
             pass
+
+
+class SignatureSet:
+    """The signatures kg_signatures_derive* made from annotated proteins, resident on the GPU, in ascending k-mer order."""
+
+    def __init__(self, handle: int, device: int):
+        self._h = C.c_void_p(handle)
+        self.device = device
+
+    def _need(self):
+        if not self._h:
+            raise ValueError("SignatureSet is closed")
+
+    @property
+    def count(self) -> int:
+        self._need()
+        return int(N.load().kg_sigset_count(self._h))
+
+    def numpy(self) -> np.ndarray:
+        """The records as a numpy array of _native.SIGNATURE_DTYPE."""
+        self._need()
+        n = self.count
+        out = np.zeros(n, dtype=N.SIGNATURE_DTYPE)
+        if n:
+            N.check(N.load().kg_sigset_copy(self._h, 0, n, out.ctypes.data))
+        return out
+
+    def device_tensor(self):
+        """Zero-copy torch view (uint8, 24 bytes per record) of the records, valid until close(); SignatureTable.build
+        takes it as it is (kg_table_build_device)."""
+        self._need()
+        return device_tensor(N.load().kg_sigset_device(self._h) or 0, self.count * 24, "|u1", owner=self, device=self.device)
+
+    def stats(self) -> dict:
+        self._need()
+        st = N.KgDeriveStats()
+        N.check(N.load().kg_sigset_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self) -> None:
+        if self._h:
+            N.load().kg_sigset_free(self._h)
+            self._h = C.c_void_p(None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def derive_signatures(seq, offsets, fn, otu, min_proteins: int = 2, purity_pct: int = 80, max_windows_per_pass: int = 0,
+                      device: int = 0, device_ptr: Optional[int] = None) -> SignatureSet:
+    """Annotated proteins -> their signature k-mers, on the GPU (include/kmerguts_hip.h kg_signatures_derive states the
+    semantics).  seq: bytes / uint8 ndarray of the concatenated protein characters, or None when device_ptr gives their
+    address in HBM; offsets: int64[n_prot + 1]; fn / otu: int32[n_prot] (fn = -1: unannotated).  The defaults
+    min_proteins = 2 and purity_pct = 80 are this project's choice (the reference only reads signatures);
+    max_windows_per_pass = 0 sizes the passes from free device memory."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_prot + 1]")
+    n = off.size - 1
+    f = np.ascontiguousarray(np.asarray(fn, dtype=np.int64))
+    o = np.ascontiguousarray(np.asarray(otu, dtype=np.int64))
+    if f.shape != (n,) or o.shape != (n,):
+        raise ValueError("fn and otu must hold one entry per protein")
+    if n and (f.min() < -2 ** 31 or f.max() >= 2 ** 31 or o.min() < -2 ** 31 or o.max() >= 2 ** 31):
+        raise ValueError("fn and otu must fit in 32 bits")
+    f32, o32 = f.astype(np.int32), o.astype(np.int32)
+    p = N.KgDeriveParams(int(min_proteins), int(purity_pct), int(max_windows_per_pass))
+    out = C.c_void_p()
+    lib = N.load()
+    fp, op = (f32.ctypes.data if n else None), (o32.ctypes.data if n else None)
+    if device_ptr is not None:
+        N.check(lib.kg_signatures_derive_device(device, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, fp, op, C.byref(out)))
+    else:
+        arr = np.frombuffer(seq, dtype=np.uint8) if not isinstance(seq, np.ndarray) else seq
+        arr = np.ascontiguousarray(arr.view(np.uint8).reshape(-1))
+        if n and arr.size < int(off[-1]):
+            raise ValueError("sequence buffer shorter than offsets[-1]")
+        ptr = arr.ctypes.data if arr.size else None
+        N.check(lib.kg_signatures_derive(device, C.byref(p), ptr, off.ctypes.data, n, fp, op, C.byref(out)))
+    return SignatureSet(out.value, device)
