@@ -8,6 +8,7 @@
  * (ctypes) bindings that call these are shown in INTEGRATION.md.  Beyond the reference, the library also makes the
  * tables it reads: kg_table_build* places a signature list the way the lookup finds it, kg_table_save writes a resident
  * table back to kmer.table.mem_map[.gz], and kg_signatures_derive* makes that list from annotated proteins.
+ * kg_result_assign / kg_assign_calls turn the CALL records of an -a scan into one function per protein.
  *
  * Conventions: plain pointers and sizes only; every function returns an int status
  * (KG_OK == 0, negative == error) and never throws or aborts across the boundary; the text
@@ -281,6 +282,50 @@ const kg_signature *kg_sigset_device(const kg_sigset *s);
 int kg_sigset_copy(const kg_sigset *s, int64_t first, int64_t count, kg_signature *dst);
 int kg_sigset_stats(const kg_sigset *s, kg_derive_stats *out);
 void kg_sigset_free(kg_sigset *s);
+
+/* ---- assigning functions: the CALL records of an -a scan -> one function per protein (kernels: kg_assign.hpp) ----
+ *
+ * The reference stops at the CALL lines (KGJ:398-404, 526-536); this rule is the project's own.
+ * Protein p is one container of an -a scan.  Its CALLs are calls[call_start[p] .. call_start[p+1]), in emission order.
+ *   For each function f among those CALLs:
+ *     S_f = the sum of count over the protein's CALLs with fI == f, computed in int64;
+ *     W_f = the float32 sum of weightedHits over the same CALLs: start from 0.0f, add one CALL at a time in emission order,
+ *           each add rounded to nearest.
+ *   T = sum over f of S_f.
+ *   The best function is the f with the largest S_f; ties go to the largest W_f, then to the smallest f.  The runner-up is
+ *   the next function in that same order.
+ *   The protein is assigned iff both hold: it has at least one CALL and S_best >= min_score; 100 * S_best >= min_share_pct * T,
+ *   computed in int64.
+ *   otu = oI[0] of the protein's kg_otu record (the bubble at KGJ:432-437 keeps the largest count first); -1 when n == 0 or
+ *   when no OTU array was given.
+ * The output depends only on each protein's CALL sequence: not on launch geometry, nor on how many proteins are in the batch.
+ * Defaults (this project's choice): min_score = 0, min_share_pct = 50.  Valid: min_score >= 0, 0 <= min_share_pct <= 100;
+ * anything else is KG_ERR_ARG.
+ * Errors: KG_ERR_ARG for a decreasing call_start or a negative count (the message names the first such protein), for
+ * kg_result_assign on a DNA result or a KG_F_SKIP_AGGREGATE result; KG_ERR_LIMIT when S_best or T of a protein is 2^31 or more
+ * (the message names the first such protein), or kg_assign_calls gets 2^31 or more proteins or 2^32 or more CALLs.  KG_ERR_BUSY
+ * while a kg_scan* is in flight on the result's table.  Device allocations come from the table's block cache (a table-less
+ * context for kg_assign_calls), so KG_TEST_FAIL_ALLOC applies; scratch is back in the cache when the call returns
+ * (kg_table_live_device_bytes reads the same before and after). */
+typedef struct kg_assign_params { int32_t min_score; int32_t min_share_pct; } kg_assign_params;
+typedef struct kg_assignment {   /* 40 B */
+    int32_t fI;            /* best function, -1 when the protein has no CALL          */
+    int32_t assigned;      /* 1 iff the thresholds above hold                          */
+    int32_t score;         /* S_best                                                   */
+    int32_t total;         /* T                                                        */
+    float   weighted;      /* W_best                                                   */
+    int32_t n_calls;
+    int32_t n_functions;   /* distinct fI among its CALLs                              */
+    int32_t second_fi;     /* runner-up, -1 when none                                  */
+    int32_t second_score;
+    int32_t otu;
+} kg_assignment;
+/* an -a result of kg_scan* / kg_aggregate_hits -> n_seqs records into dst (host or device memory); *ms = device time
+   of the assignment kernels (may be NULL) */
+int kg_result_assign(kg_result *r, const kg_assign_params *p, kg_assignment *dst, float *ms);
+/* caller-held CALL lists: host arrays calls[call_start[n_prot]], call_start[n_prot + 1], otu[n_prot] or NULL */
+int kg_assign_calls(int device, const kg_assign_params *p, const kg_call *calls, const int64_t *call_start,
+                    int64_t n_prot, const kg_otu *otu, kg_assignment *dst);
 
 /* the resident 24-byte records, valid until kg_table_close, and how many there are: num_sigs for a built or adopted table, the
  * whole records of the file for an opened one (fewer than num_sigs for a truncated file, more for a longer one) */

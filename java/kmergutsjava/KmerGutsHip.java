@@ -86,6 +86,25 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_assign_params (kg_result_assign / kg_assign_calls); this project's defaults: 0 and 50. */
+    class KgAssignParams extends Structure {
+        public int min_score, min_share_pct;
+        public KgAssignParams() {
+            setFieldOrder(new String[] {"min_score", "min_share_pct"});
+        }
+    }
+
+    /** struct kg_assignment (40 B): one function per protein of an -a scan. */
+    class KgAssignment extends Structure {
+        public int fI, assigned, score, total;
+        public float weighted;
+        public int n_calls, n_functions, second_fi, second_score, otu;
+        public KgAssignment() {
+            setFieldOrder(new String[] {"fI", "assigned", "score", "total", "weighted", "n_calls", "n_functions", "second_fi",
+                    "second_score", "otu"});
+        }
+    }
+
     // replaces readKmerTableHeader + the table stream of lookup (KmerGutsJava.java:924-942, 944-1034)
     int kg_table_open(String path, int device, PointerByReference out);
     int kg_table_from_memory(Pointer image, long nbytes, int device, PointerByReference out);
@@ -135,6 +154,9 @@ public interface KmerGutsHip extends Library {
     Pointer kg_result_device_otu(Pointer result);
     Pointer kg_result_device_container_hit_start(Pointer result);
     Pointer kg_result_device_container_call_start(Pointer result);
+    /** one function per protein: dst = kg_assignment[n_seqs] (40 B each; host or device memory), ms = float[1] or null */
+    int kg_result_assign(Pointer result, KgAssignParams params, Pointer dst, float[] ms);
+    int kg_assign_calls(int device, KgAssignParams params, Pointer calls, long[] callStart, long nProt, Pointer otu, Pointer dst);
     void kg_result_free(Pointer result);
     int kg_restore_hits_device(int device, Pointer dSrc, long nHits, Pointer dSeqFirst, long nSeqs, Pointer dDstFirst,
                                Pointer dContainerShift, Pointer dDst, Pointer stream);

@@ -33,7 +33,7 @@ EXPORTS = (
     "kg_result_container_tail_events", "kg_result_copy_hits", "kg_result_hit_slots", "kg_result_progress", "kg_result_device_hits", "kg_result_device_calls", "kg_result_device_otu",
     "kg_result_device_container_hit_start", "kg_result_device_container_call_start", "kg_result_free", "kg_restore_hits_device",
     "kg_signatures_derive", "kg_signatures_derive_device", "kg_sigset_count", "kg_sigset_device", "kg_sigset_copy",
-    "kg_sigset_stats", "kg_sigset_free",
+    "kg_sigset_stats", "kg_sigset_free", "kg_result_assign", "kg_assign_calls",
     "kg_last_error", "kg_version",
 )
 
@@ -51,6 +51,11 @@ OTU_DTYPE = np.dtype([("n", "<i4"), ("count", "<i4", (KG_OI_BUFSZ,)), ("oI", "<i
 SIGNATURE_DTYPE = np.dtype([("kmer", "<i8"), ("otuIndex", "<i4"), ("avgFromEnd", "<i4"), ("functionIndex", "<i4"),
                             ("functionWt", "<f4")])
 assert SIGNATURE_DTYPE.itemsize == 24
+# struct kg_assignment (kg_result_assign / kg_assign_calls): one function per protein of an -a scan
+ASSIGNMENT_DTYPE = np.dtype([("fI", "<i4"), ("assigned", "<i4"), ("score", "<i4"), ("total", "<i4"), ("weighted", "<f4"),
+                             ("n_calls", "<i4"), ("n_functions", "<i4"), ("second_fi", "<i4"), ("second_score", "<i4"),
+                             ("otu", "<i4")])
+assert ASSIGNMENT_DTYPE.itemsize == 40
 assert HIT_DTYPE.itemsize == 24 and CALL_DTYPE.itemsize == 24 and OTU_DTYPE.itemsize == 44
 
 
@@ -98,6 +103,11 @@ class KgDeriveStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class KgAssignParams(C.Structure):
+    """struct kg_assign_params (kg_result_assign / kg_assign_calls)."""
+    _fields_ = [("min_score", C.c_int32), ("min_share_pct", C.c_int32)]
 
 
 class KmerGutsNativeError(RuntimeError):
@@ -174,6 +184,8 @@ def load() -> C.CDLL:
     lib.kg_sigset_stats.argtypes = [vp, C.POINTER(KgDeriveStats)]
     lib.kg_sigset_free.argtypes = [vp]
     lib.kg_sigset_free.restype = None
+    lib.kg_result_assign.argtypes = [vp, C.POINTER(KgAssignParams), vp, C.POINTER(C.c_float)]
+    lib.kg_assign_calls.argtypes = [C.c_int, C.POINTER(KgAssignParams), vp, vp, C.c_int64, vp, vp]
     lib.kg_last_error.restype = C.c_char_p
     lib.kg_version.restype = C.c_char_p
     for name in EXPORTS:

@@ -185,6 +185,25 @@ class ScanResult:
             out["container_tail_events"] = self.container_tail_events()[cont]
         return out
 
+    def assign(self, min_score: int = 0, min_share_pct: int = 50, device_out: bool = False):
+        """One function per protein of an -a result, on the GPU (include/kmerguts_hip.h kg_result_assign states the rule):
+        a numpy array of _native.ASSIGNMENT_DTYPE, or with device_out=True a CUDA uint8 tensor of 40 bytes per protein.  The
+        device time of the assignment kernels is left in `assign_ms`."""
+        lib = self._need()
+        n = self.stats["n_seqs"]
+        p = N.KgAssignParams(int(min_score), int(min_share_pct))
+        ms = C.c_float()
+        if device_out:
+            import torch
+            out = torch.empty(n * N.ASSIGNMENT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()            # the library works on its own stream
+            N.check(lib.kg_result_assign(self._h, C.byref(p), C.c_void_p(out.data_ptr() if n else None), C.byref(ms)))
+        else:
+            out = np.zeros(n, dtype=N.ASSIGNMENT_DTYPE)
+            N.check(lib.kg_result_assign(self._h, C.byref(p), out.ctypes.data if n else None, C.byref(ms)))
+        self.assign_ms = float(ms.value)
+        return out
+
     def close(self) -> None:
         if self._h:
             N.load().kg_result_free(self._h)
@@ -436,3 +455,24 @@ def derive_signatures(seq, offsets, fn, otu, min_proteins: int = 2, purity_pct: 
         ptr = arr.ctypes.data if arr.size else None
         N.check(lib.kg_signatures_derive(device, C.byref(p), ptr, off.ctypes.data, n, fp, op, C.byref(out)))
     return SignatureSet(out.value, device)
+
+
+def assign_calls(calls, call_start, otu=None, min_score: int = 0, min_share_pct: int = 50, device: int = 0) -> np.ndarray:
+    """One function per protein from caller-held CALL lists, on the GPU (kg_assign_calls): calls CALL_DTYPE[call_start[-1]],
+    call_start int64[n_prot + 1] (protein p's CALLs are calls[call_start[p] : call_start[p + 1]], in emission order), otu
+    OTU_DTYPE[n_prot] or None.  -> ASSIGNMENT_DTYPE[n_prot]."""
+    cs = np.ascontiguousarray(np.asarray(call_start, dtype=np.int64))
+    if cs.ndim != 1 or cs.size < 1:
+        raise ValueError("call_start must be int64[n_prot + 1]")
+    n = cs.size - 1
+    c = np.ascontiguousarray(calls, dtype=N.CALL_DTYPE)
+    if n and cs[-1] > c.size:
+        raise ValueError("call_start[-1] is beyond the CALL records")
+    o = None if otu is None else np.ascontiguousarray(otu, dtype=N.OTU_DTYPE)
+    if o is not None and o.shape != (n,):
+        raise ValueError("otu must hold one record per protein")
+    out = np.zeros(n, dtype=N.ASSIGNMENT_DTYPE)
+    p = N.KgAssignParams(int(min_score), int(min_share_pct))
+    N.check(N.load().kg_assign_calls(device, C.byref(p), c.ctypes.data if c.size else None, cs.ctypes.data, n,
+                                     o.ctypes.data if o is not None and n else None, out.ctypes.data if n else None))
+    return out

@@ -1,0 +1,305 @@
+"""Function assignment on the GPU (kg_result_assign / kg_assign_calls): the device records must equal the numpy model of
+tests/assign_model.py byte for byte, on random CALL lists, known answers, edge shapes, -a scans of family sets and of the
+E. coli proteome under every scan strategy, and through the annotate front end; errors name the protein and failed
+allocations leave nothing behind."""
+import gzip
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import assign_model as A  # noqa: E402
+import signature_model as M  # noqa: E402
+
+from kmergutsjava_amd import _native as N  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+def _dev(calls, cs, otu=None, ms=0, share=50, dst="host"):
+    from kmergutsjava_amd import hotpath
+    if dst == "host":
+        return hotpath.assign_calls(calls, cs, otu, ms, share)
+    # device destination: the raw entry point with a CUDA buffer
+    n = len(cs) - 1
+    out = torch.full((max(n, 1) * 40,), 0xAB, dtype=torch.uint8, device="cuda")
+    c = np.ascontiguousarray(calls, dtype=N.CALL_DTYPE)
+    csa = np.ascontiguousarray(cs, dtype=np.int64)
+    o = None if otu is None else np.ascontiguousarray(otu, dtype=N.OTU_DTYPE)
+    p = N.KgAssignParams(ms, share)
+    import ctypes as C
+    torch.cuda.synchronize()
+    N.check(N.load().kg_assign_calls(0, C.byref(p), c.ctypes.data if c.size else None, csa.ctypes.data, n,
+                                     o.ctypes.data if o is not None and n else None, out.data_ptr() if n else None))
+    return out[:n * 40].cpu().numpy().view(N.ASSIGNMENT_DTYPE)
+
+
+def _calls(rows):
+    c = np.zeros(len(rows), dtype=N.CALL_DTYPE)
+    for i, (f, k, w) in enumerate(rows):
+        c[i]["fI"], c[i]["count"], c[i]["weightedHits"] = f, k, w
+    return c
+
+
+@pytest.mark.parametrize("dst", ["host", "device"])
+@pytest.mark.parametrize("seed", range(24))
+def test_random_lists_equal_the_model(seed, dst):
+    rng = np.random.default_rng(seed)
+    # short lists (one lane), long lists (sorted path) and both mixed
+    max_calls = [3, 9, 40, 120][seed % 4]
+    calls, cs, otu = A.random_lists(rng, int(rng.integers(1, 400)), max_calls=max_calls, n_fn=int(rng.choice([1, 3, 8, 60])))
+    ms, share = int(rng.choice([0, 5, 40])), int(rng.choice([0, 34, 50, 67, 100]))
+    o = otu if seed % 3 else None
+    want = A.assign(calls, cs, o, ms, share)
+    got = _dev(calls, cs, o, ms, share, dst)
+    assert got.tobytes() == want.tobytes()
+
+
+@pytest.mark.parametrize("dst", ["host", "device"])
+def test_float_order_known_answers(dst):
+    big = float(2 ** 24)
+    for pad in (0, 30):                       # pad: more CALLs of another function, so that the protein takes the long path
+        rows_a = [(0, 2, big), (0, 2, 1.0), (0, 2, 1.0)] + [(5, 0, 0.0)] * pad
+        rows_b = [(0, 2, 1.0), (0, 2, 1.0), (0, 2, big)] + [(5, 0, 0.0)] * pad
+        c = np.concatenate([_calls(rows_a), _calls(rows_b)])
+        cs = np.array([0, len(rows_a), len(rows_a) + len(rows_b)], np.int64)
+        got = _dev(c, cs, dst=dst)
+        assert got["weighted"][0] == np.float32(2 ** 24) and got["weighted"][1] == np.float32(2 ** 24 + 2)
+        assert got.tobytes() == A.assign(c, cs).tobytes()
+
+
+def test_edge_shapes():
+    empty = np.zeros(0, N.CALL_DTYPE)
+    assert len(_dev(empty, np.zeros(1, np.int64))) == 0
+    got = _dev(empty, np.zeros(7, np.int64))
+    assert got.tobytes() == A.assign(empty, np.zeros(7, np.int64)).tobytes() and (got["fI"] == -1).all()
+    # 2e4 CALLs of distinct functions next to 2e4 alternating between two, between proteins without CALLs
+    n = 20_000
+    rng = np.random.default_rng(5)
+    a = np.zeros(n, N.CALL_DTYPE)
+    a["fI"] = rng.permutation(n) * 7 - 50_000
+    a["count"] = rng.integers(2, 9, size=n)
+    a["weightedHits"] = rng.random(n).astype(np.float32)
+    b = np.zeros(n, N.CALL_DTYPE)
+    b["fI"] = np.arange(n) % 2 + 3
+    b["count"] = rng.integers(2, 9, size=n)
+    b["weightedHits"] = rng.random(n).astype(np.float32) * 3
+    c = np.concatenate([a, b])
+    cs = np.array([0, 0, n, n, 2 * n, 2 * n], np.int64)
+    got = _dev(c, cs)
+    assert got.tobytes() == A.assign(c, cs).tobytes()
+    assert got["n_functions"][1] == n and got["n_functions"][3] == 2 and got["n_calls"][3] == n
+
+
+def test_two_million_proteins():
+    rng = np.random.default_rng(9)
+    n = 2_000_000
+    cnt = np.minimum(rng.geometric(0.5, size=n) - 1, 60)       # mostly 0..3, a tail of longer lists
+    cnt[rng.integers(0, n, size=20)] = 500
+    cs = np.zeros(n + 1, np.int64)
+    cs[1:] = np.cumsum(cnt)
+    m = int(cs[-1])
+    calls = np.zeros(m, N.CALL_DTYPE)
+    calls["fI"] = rng.integers(0, 4000, size=m)
+    calls["fI"][rng.random(m) < 0.5] = 7
+    calls["count"] = rng.integers(2, 30, size=m)
+    calls["weightedHits"] = (rng.random(m) * 10).astype(np.float32)
+    otu = np.zeros(n, N.OTU_DTYPE)
+    otu["n"] = rng.integers(0, 5, size=n)
+    otu["oI"][:, 0] = rng.integers(0, 100, size=n)
+    got = _dev(calls, cs, otu)
+    assert got.tobytes() == A.assign(calls, cs, otu).tobytes()
+
+
+@pytest.fixture(params=["direct", "partitioned", "partitioned_tags"])
+def strategy(request, monkeypatch):
+    """The scan strategies of the parity tests (tests/test_gpu_parity.py)."""
+    monkeypatch.setenv("KG_PARTITION", "0" if request.param == "direct" else "1")
+    monkeypatch.setenv("KG_DIRECT_FILTER", "2")
+    if request.param == "partitioned_tags":
+        monkeypatch.setenv("KG_BIDX", "0")
+    return request.param
+
+
+def _table(seq, off, fn, otu, minp=2, pur=80):
+    from kmergutsjava_amd import hotpath, synth
+    from kmergutsjava_amd.make_table import default_num_sigs
+    sigs = M.derive(seq, off, fn, otu, minp, pur)
+    S = default_num_sigs(len(sigs))
+    rec, _ = synth.build_table(torch.from_numpy(sigs["kmer"].copy()),
+                               tuple(torch.from_numpy(sigs[k].copy()) for k in ("otuIndex", "avgFromEnd", "functionIndex", "functionWt")), S)
+    img = synth.table_image(rec)
+    return img, hotpath.SignatureTable.from_bytes(img, 0)
+
+
+def _ecoli():
+    from kmergutsjava_amd.make_signatures import parse_fasta
+    ids, seqs = parse_fasta(gzip.decompress(open(os.path.join(HERE, "golden", "Ecoli_K12_W3110.faa.gz"), "rb").read()))
+    off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(s) for s in seqs])
+    rng = np.random.default_rng(77)
+    n = len(seqs)
+    fn = rng.integers(0, 300, size=n).astype(np.int32)
+    fn[rng.random(n) < 0.2] = -1
+    otu = rng.integers(0, 4, size=n).astype(np.int32)
+    return b"".join(seqs), off, fn, otu
+
+
+@pytest.mark.parametrize("oc", [False, True])
+@pytest.mark.parametrize("workload", ["families", "ecoli"])
+def test_scan_assignments_equal_the_model_on_oracle_records(oracle, strategy, workload, oc):
+    from kmergutsjava_amd import hotpath
+    if workload == "families":
+        seq, off, fn, otu = M.family_set(80, 10, 300, 0.04, 91)
+        img, tab = _table(seq, off, fn, otu)
+    else:
+        # random labels share few k-mers: every k-mer of an annotated protein is kept, so that most proteins have CALLs
+        seq, off, fn, otu = _ecoli()
+        img, tab = _table(seq, off, fn, otu, 1, 1)
+    sb = np.frombuffer(seq, dtype=np.uint8)
+    ora = oracle.run(img, sb, off, aa=True, lookup_mode=1, order_constraint=oc)
+    with tab:
+        live0 = tab.live_device_bytes()
+        with tab.scan(sb, off, hotpath.Params(aa=True, order_constraint=oc)) as r:
+            live1 = tab.live_device_bytes()
+            for ms, share in ((0, 50), (10, 80), (0, 0)):
+                want = A.assign(ora["calls"], ora["container_call_start"], ora["otu"], ms, share)
+                got = r.assign(ms, share)
+                assert got.tobytes() == want.tobytes()
+                assert r.assign_ms > 0
+                d = r.assign(ms, share, device_out=True)
+                assert d.cpu().numpy().tobytes() == want.tobytes()
+                assert tab.live_device_bytes() == live1
+            assert (got["n_calls"] > 0).sum() > 100
+        assert tab.live_device_bytes() == live0
+
+
+def test_errors_name_the_protein():
+    from kmergutsjava_amd import hotpath
+    c = _calls([(0, 3, 1.0)] * 6)
+
+    def err(calls=c, cs=(0, 2, 4, 6), **kw):
+        with pytest.raises(N.KmerGutsNativeError) as ei:
+            hotpath.assign_calls(calls, np.array(cs, np.int64), **kw)
+        return ei.value
+
+    e = err(cs=(0, 2, 1, 6))
+    assert e.code == N.KG_ERR_ARG and "protein 1" in str(e)
+    bad = c.copy()
+    bad["count"][4] = -1
+    e = err(calls=bad)
+    assert e.code == N.KG_ERR_ARG and "protein 2" in str(e)
+    long_bad = np.concatenate([c, _calls([(k, 1, 1.0) for k in range(40)])])
+    long_bad["count"][30] = -2
+    e = err(calls=long_bad, cs=(0, 2, 4, 6, 46))
+    assert e.code == N.KG_ERR_ARG and "protein 3" in str(e)
+    huge = c.copy()
+    huge["count"][2:4] = 2 ** 30
+    e = err(calls=huge)
+    assert e.code == N.KG_ERR_LIMIT and "protein 1" in str(e)
+    for kw in ({"min_score": -1}, {"min_share_pct": -1}, {"min_share_pct": 101}):
+        assert err(**kw).code == N.KG_ERR_ARG
+
+
+def test_dna_and_skip_aggregate_results_are_refused():
+    from kmergutsjava_amd import hotpath
+    seq, off, fn, otu = M.family_set(10, 4, 200, 0.04, 3)
+    img, tab = _table(seq, off, fn, otu)
+    with tab:
+        for params in (hotpath.Params(aa=False), hotpath.Params(aa=True, skip_aggregate=True)):
+            with tab.scan(np.frombuffer(seq, dtype=np.uint8), off, params) as r:
+                with pytest.raises(N.KmerGutsNativeError) as ei:
+                    r.assign()
+                assert ei.value.code == N.KG_ERR_ARG
+        assert tab.live_device_bytes() == 0
+
+
+def test_failed_allocations_leave_nothing_behind(monkeypatch):
+    from kmergutsjava_amd import hotpath
+    rng = np.random.default_rng(4)
+    calls, cs, otu = A.random_lists(rng, 3000, max_calls=40, n_fn=30)
+    want = A.assign(calls, cs, otu)
+    seq, off, fn, otu2 = M.family_set(30, 8, 300, 0.04, 13)
+    img, tab = _table(seq, off, fn, otu2)
+    with tab, tab.scan(np.frombuffer(seq, dtype=np.uint8), off, hotpath.Params(aa=True)) as r:
+        want_r = r.assign()
+        # once on the device first, so that what the runtime sets up on first use is not counted (as the derive test does)
+        assert hotpath.assign_calls(calls, cs, otu).tobytes() == want.tobytes()
+        torch.cuda.synchronize()
+        free0 = torch.cuda.mem_get_info()[0]
+        live0 = tab.live_device_bytes()
+        for which in ("calls", "result"):
+            failed = 0
+            for n in range(1, 200):
+                monkeypatch.setenv("KG_TEST_FAIL_ALLOC", str(n))
+                try:
+                    got = hotpath.assign_calls(calls, cs, otu) if which == "calls" else r.assign()
+                    break
+                except N.KmerGutsNativeError as e:
+                    assert e.code == N.KG_ERR_NOMEM, e
+                    failed += 1
+                    assert tab.live_device_bytes() == live0
+                    if which == "calls":
+                        assert torch.cuda.mem_get_info()[0] == free0, "allocation %d failed and device memory stayed in use" % n
+            monkeypatch.delenv("KG_TEST_FAIL_ALLOC")
+            assert failed >= 8
+            assert got.tobytes() == (want if which == "calls" else want_r).tobytes()
+            assert tab.live_device_bytes() == live0
+
+
+def _expected_lines(ids, want, fnames, onames, write_all):
+    lines = []
+    for pid, a in zip(ids, want):
+        if not (a["assigned"] or write_all):
+            continue
+        st = b"assigned" if a["assigned"] else (b"below" if a["n_calls"] else b"none")
+        f = fnames[a["fI"]] if a["fI"] >= 0 else b"-"
+        o = onames[a["otu"]] if onames is not None and a["otu"] >= 0 else b"%d" % a["otu"]
+        lines.append(b"%s\t%s\t%s\t%d\t%d\t%s\t%s\n" % (pid, st, f, a["score"], a["total"], b"%.9g" % float(a["weighted"]), o))
+    return b"".join(lines)
+
+
+@pytest.mark.parametrize("with_otu_index", [True, False])
+def test_annotate_front_end(oracle, tmp_path, with_otu_index):
+    seq, off, fn, otu = M.family_set(40, 8, 300, 0.04, 61, n_fn=12)
+    names = [b"fn_%02d" % (11 - f) for f in range(12)]
+    ids = [b"prot%d" % i for i in range(len(fn))]
+    fa = b"".join(b">%s desc\n%s\n" % (ids[i], seq[off[i]:off[i + 1]]) for i in range(len(fn)))
+    (tmp_path / "p.faa.gz").write_bytes(gzip.compress(fa))
+    tsv = b"".join(b"prot%d\t%s\tO%d\n" % (i, names[f], otu[i]) for i, f in enumerate(fn) if f >= 0)
+    (tmp_path / "a.tsv").write_bytes(tsv)
+    d = tmp_path / "d"
+    root = os.path.dirname(HERE)
+    subprocess.run([sys.executable, "-m", "kmergutsjava_amd.make_signatures", "-p", str(tmp_path / "p.faa.gz"), "-A",
+                    str(tmp_path / "a.tsv"), "-o", str(tmp_path / "s.txt"), "-D", str(d)], check=True, cwd=root,
+                   stdout=subprocess.DEVNULL)
+    if not with_otu_index:
+        os.remove(d / "otu.index")
+    fnames = [ln.split(b"\t", 1)[1] for ln in (d / "function.index").read_bytes().splitlines()]
+    onames = [ln.split(b"\t", 1)[1] for ln in (d / "otu.index").read_bytes().splitlines()] if with_otu_index else None
+    img = open(d / "kmer.table.mem_map", "rb").read()
+    ora = oracle.run(img, np.frombuffer(seq, dtype=np.uint8), off, aa=True, lookup_mode=1)
+    want = A.assign(ora["calls"], ora["container_call_start"], ora["otu"], 0, 50)
+    (tmp_path / "q.faa").write_bytes(fa)
+    for inp, extra, write_all in (("p.faa.gz", ["--all"], True), ("q.faa", ["--truth", str(tmp_path / "a.tsv")], False)):
+        out = tmp_path / "o.tsv"
+        p = subprocess.run([sys.executable, "-m", "kmergutsjava_amd.annotate", "-D", str(d), "-p", str(tmp_path / inp), "-o",
+                            str(out)] + extra, capture_output=True, text=True, cwd=root)
+        assert p.returncode == 0, p.stderr
+        assert out.read_bytes() == _expected_lines(ids, want, fnames, onames, write_all)
+        line = "Proteins: %d, with calls: %d, assigned: %d" % (len(fn), (want["n_calls"] > 0).sum(), want["assigned"].sum())
+        if "--truth" in extra:
+            ann = fn >= 0
+            got_name = np.array([fnames[f] if f >= 0 else b"" for f in want["fI"]], dtype=object)
+            true_name = np.array([names[f] if f >= 0 else b"" for f in fn], dtype=object)
+            asg = want["assigned"] == 1
+            agree = int((ann & asg & (got_name == true_name)).sum())
+            line += ", annotated: %d, agree: %d, disagree: %d, missed: %d" % (ann.sum(), agree, int((ann & asg).sum()) - agree,
+                                                                              int((ann & ~asg).sum()))
+            assert agree > 0.7 * ann.sum()
+        assert p.stdout.strip() == line
