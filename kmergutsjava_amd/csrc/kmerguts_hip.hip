@@ -248,6 +248,23 @@ uint32_t env_u32(const char *name, uint32_t dflt)
     return (end != v && x >= 0) ? (uint32_t)x : dflt;
 }
 
+constexpr uint32_t kMaxGrid = 256u * 32u;      // the most workgroups a geometry knob asks for (the defaults: 256 .. 2048)
+
+// A geometry knob (tuning aid): env_u32 held to [lo, hi], the range its kernels run with, and rounded up to a multiple of
+// `mult` (ticketed grids: one hand-out counter per eight workgroups).  0, a value below lo or one beyond 2^32 become a
+// legal geometry instead of an empty launch, a division by zero or a wrapped shift.
+uint32_t env_knob(const char *name, uint32_t dflt, uint32_t lo, uint32_t hi, uint32_t mult = 1)
+{
+    uint32_t x = dflt;
+    if (const char *v = getenv(name); v && *v) {
+        char *end = nullptr;
+        const long long y = strtoll(v, &end, 10);
+        if (end != v && y >= 0) x = y > (long long)hi ? hi : (uint32_t)y;
+    }
+    x = std::min(hi, std::max(lo, x));
+    return (x + mult - 1) / mult * mult;
+}
+
 // The two test hooks (KG_TEST_TINY_LISTS, KG_TEST_FAIL_ALLOC; include/kmerguts_hip.h) are read only when the process opted in
 // with KG_ENABLE_TEST_HOOKS=1 -- looked at ONCE, at the first scan: a stray KG_TEST_* variable in a server's environment
 // does nothing.
@@ -896,7 +913,7 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
     bool use_part = false;
     {
         // bucket = 2^shift slots (= bytes of tags); at most kMaxBuckets buckets; quotient must fit 32 - shift bits
-        uint32_t shift = env_u32("KG_PART_SHIFT", 21u);
+        uint32_t shift = env_knob("KG_PART_SHIFT", 21u, 4u, 31u);
         const uint64_t qmax = (uint64_t)KG_MAX_ENCODED / (uint64_t)t->num_sigs + 1;
         while (shift > 4 && qmax >= (1ull << (32 - shift))) shift--;     // small tables: large quotients, small buckets
         while (((t->limit + (1ull << shift) - 1) >> shift) > (uint64_t)kg::kMaxBuckets) shift++;
@@ -973,7 +990,7 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
         for (uint32_t c = 0; c < n_chunks_p; c++) max_chunk = std::max(max_chunk, clo[c + 1] - clo[c]);
         const uint64_t chunk_blocks = (max_chunk + per_iter - 1) / per_iter * per_iter;
         const double max_frac = (double)max_chunk / (double)nblocks;
-        uint32_t n_wg = env_u32("KG_PART_WGS", 256u);
+        uint32_t n_wg = env_knob("KG_PART_WGS", 256u, 1u, kMaxGrid);
         if ((uint64_t)n_wg * per_iter > chunk_blocks) n_wg = (uint32_t)((chunk_blocks + per_iter - 1) / per_iter);
         const uint64_t blocks_per_wg = ((chunk_blocks + (uint64_t)n_wg * per_iter - 1) / ((uint64_t)n_wg * per_iter)) * per_iter;
         // region capacity: the mean if every window were valid and hashed uniformly, plus 6 sigma, in 16-entry groups
@@ -1040,10 +1057,10 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
         // workgroup to leave; the hand-out is by ticket, so the count only decides how fast freed registers are taken up.
         // Round 2 (one tag wave per SIMD beside the scatter pass): 4 per CU 20.4 ms, 8 per CU 20.8 (profiles/r02_pipeline.md);
         // round 3 (two): 4 per CU 19.78 ms, 8 per CU 19.56, bench.py 20.5 -> 20.25 ms per step (profiles/r03_experiments.md).
-        const uint32_t probe_grid = env_u32("KG_PROBE_GRID", 256u * 8u) & ~7u;
+        const uint32_t probe_grid = env_knob("KG_PROBE_GRID", 256u * 8u, 8u, kMaxGrid, 8u);
         // the byte-index pass: four workgroups per CU -- at 32 VGPRs they are the four waves per SIMD that fit beside a scatter
         // workgroup (4 x 96 + 4 x 32 = 512); with eight queued the stage is 0.4 ms slower (16.37 against 15.93 ms, r04 c04)
-        const uint32_t index_grid = env_u32("KG_INDEX_GRID", 256u * 4u) & ~7u;
+        const uint32_t index_grid = env_knob("KG_INDEX_GRID", 256u * 4u, 8u, kMaxGrid, 8u);
         // ... and the regions it takes per hand-out: regions expected to hold fewer than ~640 / ~320 entries (about 0.7 of the
         // mean the capacity was computed from is valid DNA) are handed out two / four at a time (bucket_index_kernel)
         // wave priorities (s_setprio) of the two passes that share the CUs: kg_device.hpp, set_wave_prio
@@ -1056,12 +1073,12 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
         // verify workgroups: two per CU.  With eight (until round 3) the pass alone is 15 % faster, but its workgroups take all the
         // registers an ending tag pass frees, and the next tag pass -- the critical chain -- starts behind them: stage 18.3 ->
         // 18.15 ms, 125 Mbp shard 3.18 -> 3.10 (profiles/r03_experiments.md)
-        const uint32_t verify_grid = env_u32("KG_VERIFY_GRID", 256u * 2u);
+        const uint32_t verify_grid = env_knob("KG_VERIFY_GRID", 256u * 2u, 1u, kMaxGrid);
         // The two kernels that usually find nothing to do (no low-complexity block set aside, no overflow group) sit on the
         // stage's critical chain -- in front of every tag pass and behind every verify pass -- and beside the other passes a
         // grid of 2048 / 1024 workgroups takes 0.1 / 0.35 ms just to be scheduled and leave (profiles/r03_kernel_stats.csv);
         // one workgroup per CU leaves in microseconds and is still the whole chip when there is work.
-        const uint32_t lowc_grid = env_u32("KG_LOWC_GRID", 256u), ovf_grid = env_u32("KG_OVF_GRID", 256u);
+        const uint32_t lowc_grid = env_knob("KG_LOWC_GRID", 256u, 1u, kMaxGrid), ovf_grid = env_knob("KG_OVF_GRID", 256u, 1u, kMaxGrid);
         // per-chunk lists: hits (unordered) and candidates = fingerprint matches (hits + ~0.4 % of the probes) + the
         // ~2 % of the probes whose first tag window decides nothing
         const uint64_t list_slack = (uint64_t)(std::max(std::max(probe_grid, index_grid), verify_grid) + 64) * 4 * kg::kUChunk + 4096;
@@ -1081,7 +1098,7 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
         } list_guard{sc, {(void **)&d_ulist, (void **)&d_cused, (void **)&d_cand, (void **)&d_candused, (void **)&d_sortA, (void **)&d_sortB}};
         bool too_skewed = false;
         const uint32_t grab_unit = 256u * (uint32_t)std::max(kg::kProbeN, kg::kIndexN);      // (powers of two: the larger is a multiple of the other)
-        const uint32_t probe_grab = (std::max(env_u32("KG_PROBE_GRAB", cap), grab_unit) + grab_unit - 1) / grab_unit * grab_unit;
+        const uint32_t probe_grab = env_knob("KG_PROBE_GRAB", cap, grab_unit, 1u << 24, grab_unit);
         uint64_t h_tot[6] = {0, 0, 0, 0, 0, 0};
         HIP_TRY(hipEventRecord(t->ev[1], t->stream));
         for (int attempt = 0; attempt < 3; attempt++) {
@@ -1238,7 +1255,7 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
                     uint32_t *gcur1_c = d_gcur1 + (size_t)c * (kg::kHDigits + 1), *gcur2_c = d_gcur2 + (size_t)c * groups_stride,
                              *gtile_c = d_gtile + (size_t)c * (kg::kHDigits + 1);
                     kg_hit *sortA_c = d_sortA + (uint64_t)c * ucap, *sortB_c = d_sortB + (uint64_t)c * ucap;
-                    const uint32_t ogrid = env_u32("KG_ORDER_GRID", 256u * 3u);
+                    const uint32_t ogrid = env_knob("KG_ORDER_GRID", 256u * 3u, 1u, kMaxGrid);
                     hipLaunchKernelGGL(kg::hit_hist_kernel, dim3(ogrid), dim3(kg::kHThreads), (size_t)n_groups * 4, s3, ulist_c, cused_c, ucur_c, ucap,
                                        g0, 6u + gshift, n_groups, ghist_c);
                     hipLaunchKernelGGL(kg::group_scan_kernel, dim3(1), dim3(kg::kGsThreads), 0, s3, ghist_c, n_groups, gbase_c, gcur1_c, gcur2_c, ctot_c, gtile_c);
@@ -1347,8 +1364,8 @@ int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8
         if (!seq_uploaded) { if ((rc = upload(offsets[0], offsets[n_seqs]))) return rc; seq_uploaded = true; }
     // ---- scan: encode + probe + staged compaction; re-run once if the staging area was too small ----
     // persistent grid: enough workgroups to fill 256 CUs, few enough that per-wave staging chunks stay small
-    const uint32_t scan_grid = env_u32("KG_SCAN_GRID", 256u * 8u);
-    const uint32_t stage_chunk = env_u32("KG_STAGE_CHUNK", 256u);
+    const uint32_t scan_grid = env_knob("KG_SCAN_GRID", 256u * 8u, 1u, kMaxGrid);
+    const uint32_t stage_chunk = env_knob("KG_STAGE_CHUNK", 256u, 1u, 1u << 12);
     // the table's bit-per-slot digest as the direct kernel's first question (tables of <= kHbitsMaxSlots slots; not for scans
     // that count the slots they inspect): config 5's scan 2.28 -> 1.80 ms (r04 c34)
     // KG_DIRECT_FILTER: 0 never, 1 (default) when the tags no longer fit an XCD's 4 MB L2 (below that the bit is one more
