@@ -183,14 +183,51 @@ struct PinCache {
 
 constexpr uint64_t kHbitsMaxSlots = 1ull << 26;     // tables up to this many slots get the bit-per-slot digest (8 MB of bits)
 
+// ---- names for the numbered slots a scan uses: events, pinned words, device counter words ----
+constexpr uint32_t kMaxChunks = 8;          // chunks of a partitioned scan (KG_PART_CHUNKS)
+constexpr uint32_t kMaxOrderStreams = 4;    // KG_ORDER_STREAMS
+// kg_table::pev, the edges between the streams of a partitioned scan
+enum : int {
+    kPevChunk = 0,                      // [+ 2c] chunk c scattered, [+ 2c + 1] chunk c tag-probed
+    kPevFork = 16,                      // the attempt's clears are enqueued: stream2 and stream3 start behind them
+    kPevJoin2 = 17, kPevJoin3 = 18,     // everything of the attempt on stream2 / stream3
+    kPevTotals = 19,                    // the early totals are in their pinned words
+    kPevVerified = 20,                  // [+ c] chunk c verified
+    kPevBase = 32,                      // [+ c] ordering streams: chunk c's total is known (the base of chunk c + 1 follows)
+    kPevOrdered = 40,                   // [+ k] everything of the attempt on ordering stream k
+    kPevCount = 48
+};
+static_assert(kPevChunk + 2 * kMaxChunks <= kPevFork && kPevVerified + kMaxChunks <= kPevBase && kPevBase + kMaxChunks <= kPevOrdered &&
+              kPevOrdered + kMaxOrderStreams <= kPevCount, "event slots overlap");
+// kg_table::ev, the timing events of a scan (outside a scan they are free: kg_result_copy_hits, assign_impl)
+enum : int { kEvBegin = 0, kEvScanBegin = 1, kEvScanEnd = 2, kEvOrderEnd = 3, kEvAggEnd = 4, kEvScattered = 5 /* all chunks */, kEvSpare = 6,
+             kEvJoined = 7 /* stream2 and stream3 joined */, kEvCount = 8 };
+// d_totals, the counter words of a scan
+enum : int { kTotHits = 0, kTotCursor = 1 /* staging records asked for */, kTotValid = 2, kTotSlots = 3 /* windows / slots counted */,
+             kTotCalls = 4, kTotRanOff = 5 /* a lookup ran off the stream (sticky) */, kTotPieces = 6, kTotVoters = 7, kTotWords = 8,
+             kTotSent = 6 /* the first words: what the host reads back per attempt */ };
+// d_pc, the per-chunk words of a partitioned scan; [kPcBase + n_chunks] = all hits
+enum : int { kPcUcur = 0 /* [+ c] hit-list cursors */, kPcCcur = 8 /* candidate cursors */, kPcBase = 16 /* first hit record */,
+             kPcCtot = 32 /* hit totals */, kPcWords = 48 };
+static_assert(kPcUcur + kMaxChunks <= kPcCcur && kPcCcur + kMaxChunks <= kPcBase && kPcBase + kMaxChunks + 1 <= kPcCtot &&
+              kPcCtot + kMaxChunks <= kPcWords, "per-chunk words overlap");
+// d_ovfc, 32-bit words per chunk
+enum : int { kOvfGroups = 0 /* overflow groups */, kOvfLowc = 1 /* low-complexity blocks set aside */, kOvfGuard = 2 /* spin guard fired */,
+             kOvfWords = 8 };
+// kg_table::h_pin, pinned host words for the few counters a call reads back (a hipMemcpyAsync to pageable memory blocks the
+// host per copy; to pinned memory it does not)
+enum : int { kPinPc = 0 /* d_pc */, kPinOvf = 48 /* d_ovfc */, kPinTotals = 80 /* d_totals[0 .. kTotSent) */, kPinCalls = 88 /* CALL total */,
+             kPinPieces = 89, /* 90 .. 94: kPinAssign */ kPinWords = 96 };
+static_assert(kPinPc + kPcWords <= kPinOvf && kOvfWords * kMaxChunks * 4 <= (kPinTotals - kPinOvf) * 8 && kPinTotals + kTotSent <= kPinCalls,
+              "counters must fit their pinned words");
+
 struct kg_table {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;      // partitioned scan: tag pass of chunk c while chunk c+1 is scattered (stream)
     hipStream_t stream3 = nullptr;      // ... and while chunk c-1 is verified and placed
-    hipStream_t ostream[4] = {};        // ordering streams (KG_ORDER_STREAMS), lowest priority: queues of their own
-    hipEvent_t pev[48] = {};            // [2c] chunk c scattered, [2c+1] chunk c tag-probed (c < 8); [16],[17],[18] fork / joins;
-                                        // [20+c] chunk c verified
+    hipStream_t ostream[kMaxOrderStreams] = {};   // ordering streams (KG_ORDER_STREAMS), lowest priority: queues of their own
+    hipEvent_t pev[kPevCount] = {};     // kPev*
     bool own_entries = false;
     uint8_t *d_entries = nullptr;
     uint8_t *d_tags = nullptr;
@@ -207,10 +244,8 @@ struct kg_table {
     size_t scatter_lds[2] = {0, 0};  // dynamic LDS the scatter kernel (DNA / protein) has been allowed so far
     size_t hist_lds = 48 * 1024;     // ... and the hit histogram kernel (kg_order.hpp)
     size_t place_lds[2] = {48 * 1024, 48 * 1024};   // ... and group_place_kernel<DNA / AA>
-    hipEvent_t ev[8] = {};
-    // Pinned host words for the few counters a scan reads back (a hipMemcpyAsync to pageable memory blocks the host per
-    // copy; to pinned memory it does not): [0..47] d_pc, [48..79] d_ovfc (as 64 x u32), [80..87] d_totals, [88] CALL total
-    uint64_t *h_pin = nullptr;
+    hipEvent_t ev[kEvCount] = {};       // kEv*
+    uint64_t *h_pin = nullptr;          // kPin*
     std::atomic<int> busy{0};    // a kg_scan* is in flight on this table (its streams, events and pinned words are per table)
     uint32_t fail_alloc_at = 0, alloc_count = 0;   // test hook KG_TEST_FAIL_ALLOC (include/kmerguts_hip.h)
     DevCache cache;
@@ -354,7 +389,7 @@ int table_new(int device, kg_table **out)
     if (!t) return fail(KG_ERR_NOMEM, "out of host memory");
     t->device = device;
     hipError_t e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&t->h_pin, 96 * 8);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&t->h_pin, kPinWords * 8);
     for (auto &ev : t->ev)
         if (e == hipSuccess) e = hipEventCreate(&ev);               // (a table-less context of kg_aggregate_hits uses them too)
     if (e != hipSuccess) { kg_table_close(t); return fail(KG_ERR_DEVICE, std::string("hipStreamCreate / hipEventCreate: ") + hipGetErrorString(e)); }
@@ -677,827 +712,1013 @@ struct Scratch {
 };
 
 // gatherHits / processSetOfHits / the OTU buffer (KGJ:385-524) over res->d_hits + res->d_chs: fills the CALL, OTU and event
-// arrays of res.  d_partial: prefix-sum scratch for n_cont items, d_totals[4]: the CALL total.  otu_init (device, one record
+// arrays of res.  d_partial: prefix-sum scratch for n_cont items, d_totals: the counter words (kTotCalls: the CALL total).
+// otu_init (device, one record
 // per sequence, or null): the oICounts buffers the sequences start with (kg_aggregate_hits; the scan starts them empty).
 // Everything is enqueued on t->stream and nothing is waited for: calls[] is allocated for the most CALLs n_hits records can
 // make (n_hits / minHits), so the host does not need the CALL total before the records are compacted; the total arrives in
 // t->h_pin[kPinCalls] once the caller has synchronised the stream.
-constexpr int kPinCalls = 88, kPinPieces = 89;
 int aggregate_stage(kg_table *t, const kg_params *p, kg_result *res, Scratch &sc, int64_t n_seqs, uint64_t n_cont, uint64_t n_hits,
                     uint32_t PER, uint64_t *d_partial, uint64_t *d_totals, const kg_otu *d_otu_init, bool allow_pieces)
 {
+    // KG_AGG_BLOCK_SHIFT: log2 of the records per block of the pieces below (at most one piece start per block; tests lower it)
+    const uint32_t pshift = std::min(20u, std::max(6u, env_u32("KG_AGG_BLOCK_SHIFT", 9u)));
+    const bool pieces_on = env_u32("KG_AGG_PIECES", 1u) != 0;
+    const uint32_t agg_pairs = env_u32("KG_AGG_PAIRS", 1u);
     int rc;
-    {
-        kg::AggParams ap;
-        ap.min_hits = p->min_hits; ap.min_weighted_hits = p->min_weighted_hits;
-        ap.max_gap = p->max_gap; ap.order_constraint = p->order_constraint ? 1 : 0;
-        uint32_t *d_ccnt = nullptr, *d_coff = nullptr, *d_first = nullptr;
-        kg_call *d_staged = nullptr;
-        uint8_t *d_vote = nullptr;
-        if ((rc = dalloc(t, (void **)&res->d_ev, n_hits))) return rc;
-        if ((rc = dalloc(t, (void **)&res->d_tail_ev, n_cont))) return rc;
-        uint8_t *d_acc = res->d_ev;
-        if ((rc = sc.get(&d_ccnt, n_cont))) return rc;
-        if ((rc = sc.get(&d_first, n_cont))) return rc;
-        if ((rc = sc.get(&d_coff, n_cont))) return rc;
-        if ((rc = sc.get(&d_vote, n_hits))) return rc;
-        // a hit votes for at most one CALL and a CALL needs >= minHits voters: the CALLs of a unit (a container, or a piece of a
-        // long one) that starts at record b and ends before record e fit in [b / minHits, e / minHits) of the staging array
-        if ((rc = sc.get(&d_staged, (size_t)(n_hits / (uint64_t)p->min_hits + 1)))) return rc;
-        if ((rc = dalloc(t, (void **)&res->d_ccs, (n_cont + 1) * 8))) return rc;
-        if ((rc = dalloc(t, (void **)&res->d_otu, (size_t)(n_seqs ? n_seqs : 1) * sizeof(kg_otu)))) return rc;
-        // Long containers in pieces that start behind a gap > maxGap (kg_aggregate.hpp): exact when no -O (with it the gap
-        // is measured from the last ACCEPTED record) and position + maxGap cannot wrap (the caller vouches for positions
-        // < 2^30).  KG_AGG_BLOCK_SHIFT: log2 of the records per block (at most one piece start per block; tests lower it).
-        const uint32_t pshift = std::min(20u, std::max(6u, env_u32("KG_AGG_BLOCK_SHIFT", 9u)));
-        const bool pieces = allow_pieces && !p->order_constraint && p->max_gap >= 0 && p->max_gap < (1 << 30) && n_cont &&
-                            n_hits > (2ull << pshift) && env_u32("KG_AGG_PIECES", 1u) != 0;
-        const uint32_t n_pblocks = pieces ? (uint32_t)((n_hits + (1ull << pshift) - 1) >> pshift) : 0u;
-        uint32_t *d_pstart = nullptr, *d_pcnt = nullptr;
-        uint8_t *d_before = nullptr, *d_ppair = nullptr;
-        t->h_pin[kPinCalls] = 0;
-        t->h_pin[kPinPieces] = 0;
-        {   // clears: the containers' CALL totals (units add to them), the pieces' counts and hand-over bytes
-            kg::ClearList cl;
-            cl.n = 0;
-            for (int k = 0; k < 8; k++) { cl.p[k] = nullptr; cl.words[k] = 0; }
-            if (n_cont) { cl.p[cl.n] = d_ccnt; cl.words[cl.n++] = n_cont; }
-            if (pieces) {
-                if ((rc = sc.get(&d_pstart, (size_t)n_pblocks + 1))) return rc;
-                if ((rc = sc.get(&d_pcnt, (size_t)n_pblocks + 1))) return rc;
-                if ((rc = sc.get(&d_before, ((size_t)n_pblocks + 4) & ~(size_t)3))) return rc;
-                if ((rc = sc.get(&d_ppair, ((size_t)n_pblocks + 4) & ~(size_t)3))) return rc;
-                cl.p[cl.n] = d_pcnt; cl.words[cl.n++] = (uint64_t)n_pblocks + 1;
-                cl.p[cl.n] = reinterpret_cast<uint32_t *>(d_before); cl.words[cl.n++] = ((uint64_t)n_pblocks + 4) / 4;
-            }
-            if (cl.n) {
-                uint64_t most = 0;
-                for (int k = 0; k < cl.n; k++) most = std::max(most, cl.words[k]);
-                hipLaunchKernelGGL(kg::clear_many_kernel, dim3((uint32_t)std::min<uint64_t>(1024, most / 1024 + 1)), dim3(256), 0, t->stream, cl);
-            }
+    kg::AggParams ap;
+    ap.min_hits = p->min_hits; ap.min_weighted_hits = p->min_weighted_hits;
+    ap.max_gap = p->max_gap; ap.order_constraint = p->order_constraint ? 1 : 0;
+    uint32_t *d_ccnt = nullptr, *d_coff = nullptr, *d_first = nullptr;
+    kg_call *d_staged = nullptr;
+    uint8_t *d_vote = nullptr;
+    if ((rc = dalloc(t, (void **)&res->d_ev, n_hits))) return rc;
+    if ((rc = dalloc(t, (void **)&res->d_tail_ev, n_cont))) return rc;
+    uint8_t *d_acc = res->d_ev;
+    if ((rc = sc.get(&d_ccnt, n_cont))) return rc;
+    if ((rc = sc.get(&d_first, n_cont))) return rc;
+    if ((rc = sc.get(&d_coff, n_cont))) return rc;
+    if ((rc = sc.get(&d_vote, n_hits))) return rc;
+    // a hit votes for at most one CALL and a CALL needs >= minHits voters: the CALLs of a unit (a container, or a piece of a
+    // long one) that starts at record b and ends before record e fit in [b / minHits, e / minHits) of the staging array
+    if ((rc = sc.get(&d_staged, (size_t)(n_hits / (uint64_t)p->min_hits + 1)))) return rc;
+    if ((rc = dalloc(t, (void **)&res->d_ccs, (n_cont + 1) * 8))) return rc;
+    if ((rc = dalloc(t, (void **)&res->d_otu, (size_t)(n_seqs ? n_seqs : 1) * sizeof(kg_otu)))) return rc;
+    // Long containers in pieces that start behind a gap > maxGap (kg_aggregate.hpp): exact when no -O (with it the gap
+    // is measured from the last ACCEPTED record) and position + maxGap cannot wrap (the caller vouches for positions
+    // < 2^30).
+    const bool pieces = allow_pieces && !p->order_constraint && p->max_gap >= 0 && p->max_gap < (1 << 30) && n_cont &&
+                        n_hits > (2ull << pshift) && pieces_on;
+    const uint32_t n_pblocks = pieces ? (uint32_t)((n_hits + (1ull << pshift) - 1) >> pshift) : 0u;
+    uint32_t *d_pstart = nullptr, *d_pcnt = nullptr;
+    uint8_t *d_before = nullptr, *d_ppair = nullptr;
+    t->h_pin[kPinCalls] = 0;
+    t->h_pin[kPinPieces] = 0;
+    {   // clears: the containers' CALL totals (units add to them), the pieces' counts and hand-over bytes
+        kg::ClearList cl;
+        cl.n = 0;
+        for (int k = 0; k < 8; k++) { cl.p[k] = nullptr; cl.words[k] = 0; }
+        if (n_cont) { cl.p[cl.n] = d_ccnt; cl.words[cl.n++] = n_cont; }
+        if (pieces) {
+            if ((rc = sc.get(&d_pstart, (size_t)n_pblocks + 1))) return rc;
+            if ((rc = sc.get(&d_pcnt, (size_t)n_pblocks + 1))) return rc;
+            if ((rc = sc.get(&d_before, ((size_t)n_pblocks + 4) & ~(size_t)3))) return rc;
+            if ((rc = sc.get(&d_ppair, ((size_t)n_pblocks + 4) & ~(size_t)3))) return rc;
+            cl.p[cl.n] = d_pcnt; cl.words[cl.n++] = (uint64_t)n_pblocks + 1;
+            cl.p[cl.n] = reinterpret_cast<uint32_t *>(d_before); cl.words[cl.n++] = ((uint64_t)n_pblocks + 4) / 4;
         }
+        if (cl.n) {
+            uint64_t most = 0;
+            for (int k = 0; k < cl.n; k++) most = std::max(most, cl.words[k]);
+            hipLaunchKernelGGL(kg::clear_many_kernel, dim3((uint32_t)std::min<uint64_t>(1024, most / 1024 + 1)), dim3(256), 0, t->stream, cl);
+        }
+    }
+    if (pieces)
+        hipLaunchKernelGGL(kg::piece_starts_kernel, dim3((n_pblocks + 3) / 4), dim3(256), 0, t->stream, res->d_hits, res->d_chs,
+                           (uint32_t)n_hits, pshift, ap.max_gap, d_pstart, d_ppair, n_pblocks, agg_pairs);
+    // one wave per unit: the containers' first pieces (several consecutive containers per wave when there are millions of
+    // them: short reads), then one per block of hits[] that a later piece may start in
+    const uint32_t cpw = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, n_cont / (1u << 17)));
+    const uint32_t n_cwaves = (uint32_t)((n_cont + cpw - 1) / cpw);
+    if (n_cont) {
+        hipLaunchKernelGGL(kg::calls_wave_kernel, dim3((n_cwaves + n_pblocks + 3) / 4), dim3(256), 0, t->stream, res->d_hits, res->d_chs,
+                           (uint32_t)n_cont, ap, d_acc, d_vote, res->d_tail_ev, d_ccnt, d_first, d_staged, cpw, n_cwaves, d_pstart,
+                           pshift, n_pblocks, d_pcnt, d_before, d_ppair);
         if (pieces)
-            hipLaunchKernelGGL(kg::piece_starts_kernel, dim3((n_pblocks + 3) / 4), dim3(256), 0, t->stream, res->d_hits, res->d_chs,
-                               (uint32_t)n_hits, pshift, ap.max_gap, d_pstart, d_ppair, n_pblocks, env_u32("KG_AGG_PAIRS", 1u));
-        // one wave per unit: the containers' first pieces (several consecutive containers per wave when there are millions of
-        // them: short reads), then one per block of hits[] that a later piece may start in
-        const uint32_t cpw = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, n_cont / (1u << 17)));
-        const uint32_t n_cwaves = (uint32_t)((n_cont + cpw - 1) / cpw);
-        if (n_cont) {
-            hipLaunchKernelGGL(kg::calls_wave_kernel, dim3((n_cwaves + n_pblocks + 3) / 4), dim3(256), 0, t->stream, res->d_hits, res->d_chs,
-                               (uint32_t)n_cont, ap, d_acc, d_vote, res->d_tail_ev, d_ccnt, d_first, d_staged, cpw, n_cwaves, d_pstart,
-                               pshift, n_pblocks, d_pcnt, d_before, d_ppair);
-            if (pieces)
-                hipLaunchKernelGGL(kg::merge_before_kernel, dim3((n_pblocks + 255) / 256), dim3(256), 0, t->stream, d_pstart, d_ppair, d_before,
-                                   n_pblocks, res->d_ev, (unsigned long long *)(d_totals + 6));
-            HIP_TRY(hipGetLastError());
-        }
-        if ((rc = prefix_sum(t, d_ccnt, n_cont, d_coff, d_partial, d_totals + 4))) return rc;
-        if (n_cont) HIP_TRY(hipMemcpyAsync(t->h_pin + kPinCalls, d_totals + 4, 8, hipMemcpyDeviceToHost, t->stream));
-        if (pieces) HIP_TRY(hipMemcpyAsync(t->h_pin + kPinPieces, d_totals + 6, 8, hipMemcpyDeviceToHost, t->stream));
-        if (n_seqs) {
-            // the voters of all CALLs as one dense list of otuIndex values in record order, then the replay per sequence
-            const uint32_t n_vchunks = (uint32_t)((n_hits + 63) / 64);
-            uint32_t *d_vcnt = nullptr, *d_voff = nullptr;
-            int32_t *d_vlist = nullptr;
-            uint64_t *d_vpartial = nullptr;
-            if ((rc = sc.get(&d_vcnt, (size_t)n_vchunks + 1))) return rc;
-            if ((rc = sc.get(&d_voff, (size_t)n_vchunks + 1))) return rc;
-            if ((rc = sc.get(&d_vlist, (size_t)n_hits + 1))) return rc;
-            if ((rc = sc.get(&d_vpartial, (size_t)((n_vchunks + 1) / kg::kScanChunk + 2)))) return rc;
-            if (n_hits) {
-                const uint32_t vgrid = (uint32_t)((n_hits + 255) / 256);
-                // (n_vchunks + 1 items: the kernel zeroes the entry behind the last chunk; its prefix is the total, read for
-                //  "behind the last record")
-                hipLaunchKernelGGL(kg::voter_count_kernel, dim3(vgrid), dim3(256), 0, t->stream, d_vote, (uint32_t)n_hits, d_vcnt);
-                if ((rc = prefix_sum(t, d_vcnt, (uint64_t)n_vchunks + 1, d_voff, d_vpartial, d_totals + 7))) return rc;
-                hipLaunchKernelGGL(kg::voter_scatter_kernel, dim3(vgrid), dim3(256), 0, t->stream, res->d_hits, d_vote, (uint32_t)n_hits, d_voff,
-                                   d_vlist);
-            } else {
-                HIP_TRY(hipMemsetAsync(d_voff, 0, 4, t->stream));
-            }
-            const uint32_t spw = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, (uint64_t)n_seqs / (1u << 17)));
-            hipLaunchKernelGGL(kg::otu_wave_kernel, dim3((uint32_t)((((uint64_t)n_seqs + spw - 1) / spw + 3) / 4)), dim3(256), 0, t->stream,
-                               d_vlist, d_voff, d_vote, res->d_chs, (uint32_t)n_hits, (uint32_t)n_seqs, PER, res->d_otu, spw, d_otu_init);
-        }
-        hipLaunchKernelGGL(kg::call_starts_kernel, dim3((uint32_t)((n_cont + 1 + 255) / 256)), dim3(256), 0, t->stream, d_coff,
-                           n_cont, d_totals + 4, res->d_ccs);
-        if ((rc = dalloc(t, (void **)&res->d_calls, (size_t)(n_hits / (uint64_t)p->min_hits + 1) * sizeof(kg_call)))) return rc;
-        if (n_cont) {
-            if (n_cont < (1u << 17))
-                hipLaunchKernelGGL((kg::compact_calls_kernel<64>), dim3((uint32_t)((n_cont * 64 + 255) / 256)), dim3(256), 0, t->stream,
-                                   d_staged, res->d_chs, d_first, d_coff, (uint32_t)n_cont, (uint32_t)p->min_hits, res->d_calls,
-                                   d_pstart, d_pcnt, pshift);
-            else
-                hipLaunchKernelGGL((kg::compact_calls_kernel<1>), dim3((uint32_t)((n_cont + 255) / 256)), dim3(256), 0, t->stream,
-                                   d_staged, res->d_chs, d_first, d_coff, (uint32_t)n_cont, (uint32_t)p->min_hits, res->d_calls,
-                                   d_pstart, d_pcnt, pshift);
-        }
+            hipLaunchKernelGGL(kg::merge_before_kernel, dim3((n_pblocks + 255) / 256), dim3(256), 0, t->stream, d_pstart, d_ppair, d_before,
+                               n_pblocks, res->d_ev, (unsigned long long *)(d_totals + kTotPieces));
         HIP_TRY(hipGetLastError());
     }
+    if ((rc = prefix_sum(t, d_ccnt, n_cont, d_coff, d_partial, d_totals + kTotCalls))) return rc;
+    if (n_cont) HIP_TRY(hipMemcpyAsync(t->h_pin + kPinCalls, d_totals + kTotCalls, 8, hipMemcpyDeviceToHost, t->stream));
+    if (pieces) HIP_TRY(hipMemcpyAsync(t->h_pin + kPinPieces, d_totals + kTotPieces, 8, hipMemcpyDeviceToHost, t->stream));
+    if (n_seqs) {
+        // the voters of all CALLs as one dense list of otuIndex values in record order, then the replay per sequence
+        const uint32_t n_vchunks = (uint32_t)((n_hits + 63) / 64);
+        uint32_t *d_vcnt = nullptr, *d_voff = nullptr;
+        int32_t *d_vlist = nullptr;
+        uint64_t *d_vpartial = nullptr;
+        if ((rc = sc.get(&d_vcnt, (size_t)n_vchunks + 1))) return rc;
+        if ((rc = sc.get(&d_voff, (size_t)n_vchunks + 1))) return rc;
+        if ((rc = sc.get(&d_vlist, (size_t)n_hits + 1))) return rc;
+        if ((rc = sc.get(&d_vpartial, (size_t)((n_vchunks + 1) / kg::kScanChunk + 2)))) return rc;
+        if (n_hits) {
+            const uint32_t vgrid = (uint32_t)((n_hits + 255) / 256);
+            // (n_vchunks + 1 items: the kernel zeroes the entry behind the last chunk; its prefix is the total, read for
+            //  "behind the last record")
+            hipLaunchKernelGGL(kg::voter_count_kernel, dim3(vgrid), dim3(256), 0, t->stream, d_vote, (uint32_t)n_hits, d_vcnt);
+            if ((rc = prefix_sum(t, d_vcnt, (uint64_t)n_vchunks + 1, d_voff, d_vpartial, d_totals + kTotVoters))) return rc;
+            hipLaunchKernelGGL(kg::voter_scatter_kernel, dim3(vgrid), dim3(256), 0, t->stream, res->d_hits, d_vote, (uint32_t)n_hits, d_voff,
+                               d_vlist);
+        } else {
+            HIP_TRY(hipMemsetAsync(d_voff, 0, 4, t->stream));
+        }
+        const uint32_t spw = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, (uint64_t)n_seqs / (1u << 17)));
+        hipLaunchKernelGGL(kg::otu_wave_kernel, dim3((uint32_t)((((uint64_t)n_seqs + spw - 1) / spw + 3) / 4)), dim3(256), 0, t->stream,
+                           d_vlist, d_voff, d_vote, res->d_chs, (uint32_t)n_hits, (uint32_t)n_seqs, PER, res->d_otu, spw, d_otu_init);
+    }
+    hipLaunchKernelGGL(kg::call_starts_kernel, dim3((uint32_t)((n_cont + 1 + 255) / 256)), dim3(256), 0, t->stream, d_coff,
+                       n_cont, d_totals + kTotCalls, res->d_ccs);
+    if ((rc = dalloc(t, (void **)&res->d_calls, (size_t)(n_hits / (uint64_t)p->min_hits + 1) * sizeof(kg_call)))) return rc;
+    if (n_cont) {
+        if (n_cont < (1u << 17))
+            hipLaunchKernelGGL((kg::compact_calls_kernel<64>), dim3((uint32_t)((n_cont * 64 + 255) / 256)), dim3(256), 0, t->stream,
+                               d_staged, res->d_chs, d_first, d_coff, (uint32_t)n_cont, (uint32_t)p->min_hits, res->d_calls,
+                               d_pstart, d_pcnt, pshift);
+        else
+            hipLaunchKernelGGL((kg::compact_calls_kernel<1>), dim3((uint32_t)((n_cont + 255) / 256)), dim3(256), 0, t->stream,
+                               d_staged, res->d_chs, d_first, d_coff, (uint32_t)n_cont, (uint32_t)p->min_hits, res->d_calls,
+                               d_pstart, d_pcnt, pshift);
+    }
+    HIP_TRY(hipGetLastError());
     return KG_OK;
 }
 
-template <bool AA>
-int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8_t *h_seq /* host copy still to upload, or null */,
-              const int64_t *offsets, int64_t n_seqs, kg_result *res)
-{
-    // h_seq != null: d_seq is an empty device buffer of offsets[n_seqs] bytes; the characters are uploaded here -- chunk
-    // by chunk in front of each chunk's scatter pass (partitioned strategy: the upload of chunk c+1 runs while chunk c is
-    // scanned), or in one piece
-    bool seq_uploaded = h_seq == nullptr;
-    auto upload = [&](int64_t a, int64_t b) -> int {
-        if (h_seq && b > a) HIP_TRY(hipMemcpyAsync(const_cast<uint8_t *>(d_seq) + a, h_seq + a, (size_t)(b - a), hipMemcpyHostToDevice, t->stream));
-        return KG_OK;
-    };
-    constexpr uint32_t PER = AA ? 1 : 6;
-    const bool progress = (p->flags & KG_F_PROGRESS) != 0;
-    const bool counters_req = (p->flags & KG_F_COUNTERS) != 0;
-    // the walks are noted by the counting kernels -- except on the partitioned path's byte home index (below: prog_index)
-    const bool counters = counters_req || progress;
-    kg_stats &st = res->st;
-    res->per = PER;
+// ---- kg_scan*: plan (host arithmetic and every environment read), then the stages that enqueue ----
 
-    // ---- host: window blocks per sequence (KGJ:912 trip counts) ----
-    std::vector<uint32_t> ibase((size_t)n_seqs + 1);
+// Run-time value -> template argument: calls f(std::integral_constant<T, V>) for the V among the listed values that equals
+// x, the last one listed when none does.
+template <typename T, T V, T... Vs, typename F>
+void dispatch(T x, F &&f)
+{
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<T, V>{});
+    else if (x == V) f(std::integral_constant<T, V>{});
+    else dispatch<T, Vs...>(x, f);
+}
+
+// Window blocks per sequence (KGJ:912 trip counts) and what follows from them.
+struct BatchPlan {
+    std::vector<uint32_t> ibase;                    // first block of sequence k; [n_seqs] = nblocks
     uint64_t nblocks = 0, windows = 0, residues = 0;
+    uint64_t n_rows = 0, n_cont = 0;                // nblocks x PER window rows, n_seqs x PER containers
     int64_t longest = 0;                            // (record positions are below the length of their sequence)
+};
+
+template <bool AA>
+int plan_batch(const int64_t *offsets, int64_t n_seqs, BatchPlan &b)
+{
+    constexpr uint32_t PER = AA ? 1 : 6;
+    b.ibase.resize((size_t)n_seqs + 1);
     for (int64_t k = 0; k < n_seqs; k++) {
         int64_t L = offsets[k + 1] - offsets[k];
         if (L < 0) return fail(KG_ERR_ARG, "offsets must be non-decreasing");
-        longest = std::max(longest, L);
+        b.longest = std::max(b.longest, L);
         if (L > 0xFFFFFFF0ll) return fail(KG_ERR_LIMIT, "a single sequence longer than 2^32-16 characters");
-        ibase[(size_t)k] = (uint32_t)nblocks;
+        b.ibase[(size_t)k] = (uint32_t)b.nblocks;
         uint64_t nb;
         if (AA) {
             uint64_t nwin = L >= 9 ? (uint64_t)L - 8 : 0;       // i < len - 8
-            windows += nwin;
-            residues += (uint64_t)L;
+            b.windows += nwin;
+            b.residues += (uint64_t)L;
             nb = (nwin + kg::kAaWinPerBlock - 1) / kg::kAaWinPerBlock;
         } else {
             uint64_t npos = L >= 24 ? (uint64_t)L - 23 : 0;     // forward positions that start a 24-base window
-            windows += 2 * npos;
+            b.windows += 2 * npos;
             for (int f = 0; f < 3; f++)
-                if (L - f >= 3) residues += 2 * (uint64_t)((L - f) / 3);
+                if (L - f >= 3) b.residues += 2 * (uint64_t)((L - f) / 3);
             nb = (npos + kg::kDnaPosPerBlock - 1) / kg::kDnaPosPerBlock;
         }
-        nblocks += nb;
-        if (nblocks > 0x7FFFFFFFull / PER) return fail(KG_ERR_LIMIT, "batch too large: more than 2^31-1 window rows; split the batch");
+        b.nblocks += nb;
+        if (b.nblocks > 0x7FFFFFFFull / PER) return fail(KG_ERR_LIMIT, "batch too large: more than 2^31-1 window rows; split the batch");
     }
-    ibase[(size_t)n_seqs] = (uint32_t)nblocks;
-    if (windows > 0xFFFFFF00ull) return fail(KG_ERR_LIMIT, "batch too large: more than 2^32-256 windows; split the batch");
-    const uint64_t n_rows = nblocks * PER;
-    const uint64_t n_cont = (uint64_t)n_seqs * PER;
-    st.n_seqs = n_seqs; st.n_containers = (int64_t)n_cont; st.n_blocks = (int64_t)nblocks;
-    st.residues = (int64_t)residues; st.windows = (int64_t)windows;
-    st.table_bytes = t->num_sigs * (int64_t)KG_TABLE_ENTRY_SIZE;
+    b.ibase[(size_t)n_seqs] = (uint32_t)b.nblocks;
+    if (b.windows > 0xFFFFFF00ull) return fail(KG_ERR_LIMIT, "batch too large: more than 2^32-256 windows; split the batch");
+    b.n_rows = b.nblocks * PER;
+    b.n_cont = (uint64_t)n_seqs * PER;
+    return KG_OK;
+}
 
-    Scratch sc(t);
-    int rc;
-    int64_t *d_off = nullptr; uint32_t *d_ibase = nullptr;
-    if ((rc = sc.get(&d_off, (size_t)n_seqs + 1))) return rc;
-    if ((rc = sc.get(&d_ibase, (size_t)n_seqs + 1))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)n_seqs + 1) * 8, hipMemcpyHostToDevice, t->stream));
-    HIP_TRY(hipMemcpyAsync(d_ibase, ibase.data(), ((size_t)n_seqs + 1) * 4, hipMemcpyHostToDevice, t->stream));
+// Buckets of 2^shift slots that cover a record stream of `limit` slots.
+uint64_t bucket_count(uint64_t limit, uint32_t shift) { return (limit + (1ull << shift) - 1) >> shift; }
 
-    kg::BlockDesc *d_blocks = nullptr;
-    uint32_t *d_counts = nullptr, *d_offs = nullptr, *d_bsb = nullptr;
-    uint64_t *d_partial = nullptr, *d_totals = nullptr;   // totals[0] hits, [1] cursor, [2] ctr_valid, [3] ctr_slots, [4] calls, [5] ran off (sticky)
-    if ((rc = sc.get(&d_blocks, nblocks))) return rc;
-    if ((rc = sc.get(&d_counts, n_rows))) return rc;
-    if ((rc = sc.get(&d_offs, n_rows))) return rc;
-    if ((rc = sc.get(&d_bsb, nblocks * 6))) return rc;      // one staging base per (block, row group)
-    uint64_t max_scan = n_rows > n_cont ? n_rows : n_cont;
-    if ((rc = sc.get(&d_partial, (size_t)(max_scan / kg::kScanChunk + 2)))) return rc;
-    if ((rc = sc.get(&d_totals, 8))) return rc;
-    HIP_TRY(hipMemsetAsync(d_totals, 0, 64, t->stream));
+// Geometry of the partitioned strategy (queries bucketed by slot range first; kg_partition.hpp) for one batch: arithmetic on
+// the table, the batch and the environment, nothing else.
+struct PartPlan {
+    bool applicable = false;            // false: the batch takes the direct strategy (nothing below shift / buckets is set)
+    uint32_t shift = 0, buckets = 0;    // bucket = 2^shift slots (= bytes of tags)
+    uint32_t n_chunks = 0;
+    std::vector<uint64_t> clo;          // chunk c = blocks [clo[c], clo[c+1])
+    std::vector<int64_t> cseq;          //         = sequences [cseq[c], cseq[c+1])
+    uint64_t max_chunk = 0;             // blocks of the largest chunk
+    uint32_t n_wg = 0, cap = 0;         // scatter workgroups; entries per region (bucket x workgroup)
+    uint64_t n_regions = 0;             // per chunk
+    uint32_t ovf_cap = 0;               // overflow list of one chunk (groups)
+    uint32_t gshift = 10, groups_stride = 0;        // ordered placement: groups of 2^gshift rows, groups provisioned per chunk
+    size_t next_stride = 0;             // tag pass: hand-out counters per chunk
+    size_t scatter_lds = 0;
+    bool use_bidx = false, part_counters = false, prog_index = false;
+    uint32_t probe_grid = 0, index_grid = 0, verify_grid = 0, lowc_grid = 0, ovf_grid = 0, order_grid = 0;
+    uint32_t scatter_prio = 0, index_prio = 0, verify_prio = 0, index_r = 1, probe_grab = 0;
+    uint64_t list_slack = 0, ucap = 0, ccap = 0;    // hit / candidate list capacities per chunk the first attempt starts with
+    uint32_t n_os = 0;                  // ordering streams (KG_ORDER_STREAMS)
+    bool early_totals = false, place_staged = false, debug = false;
+};
 
-    if ((rc = dalloc(t, (void **)&res->d_chs, (n_cont + 1) * 8))) return rc;
+template <bool AA>
+int plan_partition(const kg_table *t, const BatchPlan &b, bool progress, bool counters_req, PartPlan &pl)
+{
+    constexpr uint32_t PER = AA ? 1 : 6;
+    const uint64_t nblocks = b.nblocks;
+    // bucket = 2^shift slots (= bytes of tags); at most kMaxBuckets buckets; quotient must fit 32 - shift bits
+    uint32_t shift = env_knob("KG_PART_SHIFT", 21u, 4u, 31u);
+    const uint64_t qmax = (uint64_t)KG_MAX_ENCODED / (uint64_t)t->num_sigs + 1;
+    while (shift > 4 && qmax >= (1ull << (32 - shift))) shift--;     // small tables: large quotients, small buckets
+    while (bucket_count(t->limit, shift) > (uint64_t)kg::kMaxBuckets) shift++;
+    // the scatter workgroup keeps a 128-byte buffer per bucket in LDS: at most 160 KiB with its encode scratch
+    while (kg::scatter_lds_bytes<AA>((uint32_t)bucket_count(t->limit, shift)) > 160u * 1024) shift++;
+    // the scatter pass splits k-mers with kg::split_fast: 64 <= numSigs < 2^31
+    // (and the tag / verify passes keep slots in 32 bits: a table FILE may be longer than numSigs, KGJ:964-999)
+    const bool fits = shift < 32 && qmax < (1ull << (32 - shift)) && nblocks <= (1ull << 23) && t->m35 != 0 &&
+                      t->limit < (1ull << 32) - 64;
+    // Measured against the 33.6 GB table (profiles/r01_partition_path.md), whole scan incl. ordering, direct vs
+    // partitioned: 1 Gbp 35.0 / 21.4 ms, 600 Mbp 21.8 / 13.6, 400 Mbp 14.6 / 9.4, 200 Mbp 7.0 / 5.4, 100 Mbp 3.6 / 3.4 (one chunk).
+    // Small inputs and L2/MALL-sized tables stay on the direct kernel.
+    // KG_PARTITION: 0 direct, 1 partitioned whenever possible, 2 (default) auto.
+    const uint32_t mode = env_u32("KG_PARTITION", 2u);
+    const bool worth = t->limit >= (64ull << 20) && b.windows >= (1ull << 27);
+    if (!(fits && nblocks > 0 && (mode == 1 || (mode == 2 && worth)))) return KG_OK;
+    pl.shift = shift;
+    pl.buckets = (uint32_t)bucket_count(t->limit, shift);
 
-    // KG_F_PROGRESS: the walks' summary (kg_device.hpp, Progress).  lo[f] = the smallest slot of tenth >= f, found with the
-    // reference's own double arithmetic (KGJ:1018) around ceil(f * numSigs / 10) - 1
-    kg::Progress *d_prog = nullptr;
-    if (progress) {
-        if (t->limit > 0xFFFFFFFFull) return fail(KG_ERR_UNSUPPORTED, "KG_F_PROGRESS: table streams of 2^32 records or more");
-        if ((rc = sc.get(&d_prog, 1))) return rc;
-        kg::Progress h;
-        for (auto &x : h.first) x = ~0ull;
-        h.last_plus1 = 0; h.first_beyond = ~0ull; h.walk_ran_off = 0;
-        for (auto &x : h.found_upto) x = 0;
-        h.kmers_found = 0;
-        for (auto &x : h.miss_max1) x = 0;
-        const double n = (double)t->num_sigs;
-        auto tenth = [&](uint64_t s) { return (int)(10.0 * ((double)(s + 1) / n)); };
-        for (int f = 0; f <= 10; f++) {
-            const unsigned __int128 num = (unsigned __int128)(uint64_t)t->num_sigs * (unsigned)f;
-            uint64_t s = (uint64_t)((num + 9) / 10);
-            s = s > 3 ? s - 3 : 0;
-            while (tenth(s) < f) s++;
-            h.lo[f] = s;
-        }
-        HIP_TRY(hipMemcpyAsync(d_prog, &h, sizeof h, hipMemcpyHostToDevice, t->stream));
-        HIP_TRY(hipStreamSynchronize(t->stream));                             // (h is a stack object)
+    constexpr uint32_t WIN = AA ? 64u : 384u;                                    // windows per block
+    // The batch is cut into chunks of whole sequences.  Chunk c goes through scatter (stream), tag pass (stream2),
+    // then verification and ordered placement (stream3) while the chunks behind it are scattered and probed: the scatter pass is LDS/issue-
+    // bound with one 16-wave workgroup per CU, the tag pass is L2-bound with few registers and no LDS, verification
+    // and placement wait on random HBM lines, so they share the CUs.  A chunk's hits are a contiguous range of
+    // hits[] (whole sequences), chained by a device-side running total.
+    uint32_t want = env_u32("KG_PART_CHUNKS", 4u);
+    if (want < 1) want = 1;
+    if (want > kMaxChunks) want = kMaxChunks;
+    // How many: a pass has costs that do not shrink with the chunk, so small batches take few.  Measured with the wave
+    // priorities in place (r04 c59; ms per scan in 1 / 2 / 3 / 4 chunks): 100 Mbp 2.50 / 2.46 / 2.72 / -, 125 Mbp 2.94 / 2.87 /
+    // 3.17 / -, 250 Mbp 5.15 / 4.83 / 5.17 / -, 500 Mbp - / - / 8.63 / 9.0, 1 Gbp - / - / 16.0 / 15.1 (five: 15.45):
+    // round(sqrt(blocks / 325 000)) but at least two, one below 450 000 blocks (~85 Mbp).  KG_PART_MIN_CHUNK_BLOCKS (tests) replaces the
+    // rule by "as many as KG_PART_CHUNKS allows with at least that many blocks each".
+    if (getenv("KG_PART_MIN_CHUNK_BLOCKS")) {
+        const uint64_t min_chunk = std::max(1u, env_u32("KG_PART_MIN_CHUNK_BLOCKS", 600000u));
+        while (want > 1 && nblocks / want < min_chunk) want--;
+    } else {
+        const uint32_t by_size = nblocks < 450000 ? 1u : std::max(2u, (uint32_t)std::lround(std::sqrt((double)nblocks / 325000.0)));
+        want = std::min(want, std::max(1u, by_size));
     }
-    HIP_TRY(hipEventRecord(t->ev[0], t->stream));
-    if (nblocks) {
-        hipLaunchKernelGGL(kg::build_blocks_kernel, dim3((uint32_t)((nblocks + 255) / 256)), dim3(256), 0, t->stream,
-                           d_off, d_ibase, (uint32_t)n_seqs, (uint32_t)nblocks, d_blocks);
-        HIP_TRY(hipGetLastError());
+    pl.clo.push_back(0); pl.cseq.push_back(0);
+    // KG_PART_TAPER="30,30,25,15": chunk sizes in percent instead of equal chunks (tuning aid)
+    std::vector<double> cum;
+    if (const char *tp = getenv("KG_PART_TAPER")) {
+        double acc = 0;
+        for (const char *q = tp; *q;) {
+            char *endp = nullptr;
+            const double v = strtod(q, &endp);
+            if (endp == q) break;
+            acc += v; cum.push_back(acc);
+            q = *endp == ',' ? endp + 1 : endp;
+        }
+        if (cum.size() >= 2 && cum.size() <= kMaxChunks && acc > 0) { for (auto &x : cum) x /= acc; want = (uint32_t)cum.size(); }
+        else cum.clear();
     }
-
-    // ---- strategy: direct probing (every probe a random 128-byte line from HBM unless the tag array is
-    //      L2-sized) or partitioned probing (queries bucketed by slot range first; kg_partition.hpp) ----
-    uint64_t n_hits = 0;
-    st.scan_launches = 0;
-    uint32_t part_shift = 0, part_buckets = 0;
-    bool use_part = false;
-    {
-        // bucket = 2^shift slots (= bytes of tags); at most kMaxBuckets buckets; quotient must fit 32 - shift bits
-        uint32_t shift = env_knob("KG_PART_SHIFT", 21u, 4u, 31u);
-        const uint64_t qmax = (uint64_t)KG_MAX_ENCODED / (uint64_t)t->num_sigs + 1;
-        while (shift > 4 && qmax >= (1ull << (32 - shift))) shift--;     // small tables: large quotients, small buckets
-        while (((t->limit + (1ull << shift) - 1) >> shift) > (uint64_t)kg::kMaxBuckets) shift++;
-        // the scatter workgroup keeps a 128-byte buffer per bucket in LDS: at most 160 KiB with its encode scratch
-        while (AA ? kg::scatter_lds_bytes<true>((uint32_t)((t->limit + (1ull << shift) - 1) >> shift)) > 160u * 1024
-                  : kg::scatter_lds_bytes<false>((uint32_t)((t->limit + (1ull << shift) - 1) >> shift)) > 160u * 1024)
-            shift++;
-        // the scatter pass splits k-mers with kg::split_fast: 64 <= numSigs < 2^31
-        // (and the tag / verify passes keep slots in 32 bits: a table FILE may be longer than numSigs, KGJ:964-999)
-        const bool fits = shift < 32 && qmax < (1ull << (32 - shift)) && nblocks <= (1ull << 23) && t->m35 != 0 &&
-                          t->limit < (1ull << 32) - 64;
-        // Measured against the 33.6 GB table (profiles/r01_partition_path.md), whole scan incl. ordering, direct vs
-        // partitioned: 1 Gbp 35.0 / 21.4 ms, 600 Mbp 21.8 / 13.6, 400 Mbp 14.6 / 9.4, 200 Mbp 7.0 / 5.4, 100 Mbp 3.6 / 3.4 (one chunk).
-        // Small inputs and L2/MALL-sized tables stay on the direct kernel.
-        // KG_PARTITION: 0 direct, 1 partitioned whenever possible, 2 (default) auto.
-        const uint32_t mode = env_u32("KG_PARTITION", 2u);
-        const bool worth = t->limit >= (64ull << 20) && windows >= (1ull << 27);
-        use_part = fits && nblocks > 0 && (mode == 1 || (mode == 2 && worth));
-        part_shift = shift;
-        part_buckets = (uint32_t)((t->limit + (1ull << shift) - 1) >> shift);
+    for (uint32_t c = 1; c < want; c++) {
+        const uint64_t target = cum.empty() ? nblocks * c / want : (uint64_t)((double)nblocks * cum[c - 1]);
+        const auto it = std::lower_bound(b.ibase.begin(), b.ibase.end(), (uint32_t)target);        // a sequence start
+        const uint64_t cut = *it;
+        if (cut > pl.clo.back() && cut < nblocks) { pl.clo.push_back(cut); pl.cseq.push_back((int64_t)(it - b.ibase.begin())); }
     }
-    bool part_done = false;
-    bool prog_index = false;                     // KG_F_PROGRESS noted by the byte home index pass (progress_finish_kernel is due)
-    if (use_part) do {
-        constexpr uint32_t WIN = AA ? 64u : 384u;                                    // windows per block
-        constexpr uint32_t kMaxChunks = 8;
-        const uint32_t per_iter = kg::kScatterWaves;
-        // The batch is cut into chunks of whole sequences.  Chunk c goes through scatter (stream), tag pass (stream2),
-        // then verification and ordered placement (stream3) while the chunks behind it are scattered and probed: the scatter pass is LDS/issue-
-        // bound with one 16-wave workgroup per CU, the tag pass is L2-bound with few registers and no LDS, verification
-        // and placement wait on random HBM lines, so they share the CUs.  A chunk's hits are a contiguous range of
-        // hits[] (whole sequences), chained by a device-side running total.
-        uint32_t want = env_u32("KG_PART_CHUNKS", 4u);
-        if (want < 1) want = 1;
-        if (want > kMaxChunks) want = kMaxChunks;
-        // How many: a pass has costs that do not shrink with the chunk, so small batches take few.  Measured with the wave
-        // priorities in place (r04 c59; ms per scan in 1 / 2 / 3 / 4 chunks): 100 Mbp 2.50 / 2.46 / 2.72 / -, 125 Mbp 2.94 / 2.87 /
-        // 3.17 / -, 250 Mbp 5.15 / 4.83 / 5.17 / -, 500 Mbp - / - / 8.63 / 9.0, 1 Gbp - / - / 16.0 / 15.1 (five: 15.45):
-        // round(sqrt(blocks / 325 000)) but at least two, one below 450 000 blocks (~85 Mbp).  KG_PART_MIN_CHUNK_BLOCKS (tests) replaces the
-        // rule by "as many as KG_PART_CHUNKS allows with at least that many blocks each".
-        if (getenv("KG_PART_MIN_CHUNK_BLOCKS")) {
-            const uint64_t min_chunk = std::max(1u, env_u32("KG_PART_MIN_CHUNK_BLOCKS", 600000u));
-            while (want > 1 && nblocks / want < min_chunk) want--;
-        } else {
-            const uint32_t by_size = nblocks < 450000 ? 1u : std::max(2u, (uint32_t)std::lround(std::sqrt((double)nblocks / 325000.0)));
-            want = std::min(want, std::max(1u, by_size));
-        }
-        std::vector<uint64_t> clo;                                                    // chunk c = blocks [clo[c], clo[c+1])
-        std::vector<int64_t> cseq;                                                    //         = sequences [cseq[c], cseq[c+1])
-        clo.push_back(0); cseq.push_back(0);
-        // KG_PART_TAPER="30,30,25,15": chunk sizes in percent instead of equal chunks (tuning aid)
-        std::vector<double> cum;
-        if (const char *tp = getenv("KG_PART_TAPER")) {
-            double acc = 0;
-            for (const char *q = tp; *q;) {
-                char *endp = nullptr;
-                const double v = strtod(q, &endp);
-                if (endp == q) break;
-                acc += v; cum.push_back(acc);
-                q = *endp == ',' ? endp + 1 : endp;
-            }
-            if (cum.size() >= 2 && cum.size() <= kMaxChunks && acc > 0) { for (auto &x : cum) x /= acc; want = (uint32_t)cum.size(); }
-            else cum.clear();
-        }
-        for (uint32_t c = 1; c < want; c++) {
-            const uint64_t target = cum.empty() ? nblocks * c / want : (uint64_t)((double)nblocks * cum[c - 1]);
-            const auto it = std::lower_bound(ibase.begin(), ibase.end(), (uint32_t)target);        // a sequence start
-            const uint64_t cut = *it;
-            if (cut > clo.back() && cut < nblocks) { clo.push_back(cut); cseq.push_back((int64_t)(it - ibase.begin())); }
-        }
-        clo.push_back(nblocks); cseq.push_back(n_seqs);
-        const uint32_t n_chunks_p = (uint32_t)clo.size() - 1;
-        uint64_t max_chunk = 0;
-        for (uint32_t c = 0; c < n_chunks_p; c++) max_chunk = std::max(max_chunk, clo[c + 1] - clo[c]);
-        const uint64_t chunk_blocks = (max_chunk + per_iter - 1) / per_iter * per_iter;
-        const double max_frac = (double)max_chunk / (double)nblocks;
-        uint32_t n_wg = env_knob("KG_PART_WGS", 256u, 1u, kMaxGrid);
-        if ((uint64_t)n_wg * per_iter > chunk_blocks) n_wg = (uint32_t)((chunk_blocks + per_iter - 1) / per_iter);
-        const uint64_t blocks_per_wg = ((chunk_blocks + (uint64_t)n_wg * per_iter - 1) / ((uint64_t)n_wg * per_iter)) * per_iter;
-        // region capacity: the mean if every window were valid and hashed uniformly, plus 6 sigma, in 16-entry groups
-        const double mean = (double)blocks_per_wg * WIN / (double)part_buckets * (env_u32("KG_PART_SLACK", 100u) / 100.0);
-        const uint64_t cap64 = ((uint64_t)(mean + 6.0 * std::sqrt(mean) + 32.0) + 15) / 16 * 16;
-        // the scatter pass's address arithmetic is in 24-bit multiplies (region number x capacity): geometries beyond that
-        // (one bucket and millions of blocks per scatter workgroup; not reachable with the default knobs) take the direct path
-        if (cap64 >= (1ull << 24) || (uint64_t)part_buckets * n_wg >= (1ull << 24)) break;
-        const uint32_t cap = (uint32_t)cap64;
-        const uint64_t n_regions_total = (uint64_t)part_buckets * n_wg;               // per chunk
-        // overflow list of one chunk (groups): an eighth of the regions' capacity (low-complexity sequence: 3 % of the
-        // bases in homopolymer runs overflow ~5 % of the entries; beyond the list the scan falls back to direct probing)
-        const uint32_t ovf_cap = env_u32("KG_PART_OVF_GROUPS", (uint32_t)std::min<uint64_t>(1u << 23, std::max<uint64_t>(65536, n_regions_total * cap / 16 / 8)));
-        uint64_t *d_ent = nullptr, *d_ovf_ent = nullptr;
-        uint32_t *d_fill = nullptr, *d_ovf_bucket = nullptr, *d_next = nullptr, *d_ovfc = nullptr;
-        kg::RowGeo *d_geo = nullptr;         // per row: container and position of its first window (kg_order.hpp)
-        uint64_t *d_pc = nullptr;            // [0..7] hit-list cursors, [8..15] candidate cursors, [16..24] base, [32..39] chunk totals
-        // ordered placement (kg_order.hpp): groups of 2^gshift rows, at most kMaxGroups per chunk (8192 while 4096-row groups allow it)
-        uint32_t gshift = 10;
-        while (gshift < 12 && ((max_chunk * PER) >> gshift) + 2 > 8192) gshift++;
-        const uint32_t groups_stride = (uint32_t)(((max_chunk * PER) >> gshift) + 2);      // a chunk's rows start anywhere inside a group
-        if (groups_stride > kg::kMaxGroups) return fail(KG_ERR_LIMIT, "a chunk of the batch holds more than 2^26 window rows");
-        uint32_t *d_ghist = nullptr, *d_gbase = nullptr, *d_gcur1 = nullptr, *d_gcur2 = nullptr, *d_gtile = nullptr;
-        kg_hit *d_sortA = nullptr, *d_sortB = nullptr;
-        if ((rc = sc.get(&d_ent, (size_t)(n_regions_total * cap * n_chunks_p)))) return rc;
-        if ((rc = sc.get(&d_fill, (size_t)n_regions_total * n_chunks_p))) return rc;
-        if ((rc = sc.get(&d_ovf_ent, (size_t)ovf_cap * kg::kGroup * n_chunks_p))) return rc;
-        if ((rc = sc.get(&d_ovf_bucket, (size_t)ovf_cap * n_chunks_p))) return rc;
-        const size_t next_stride = std::max<size_t>((size_t)part_buckets + 8, 256);   // tag pass: one hand-out counter per XCD group, 128 B apart
-        if ((rc = sc.get(&d_next, next_stride * n_chunks_p))) return rc;
-        if ((rc = sc.get(&d_ovfc, 8 * kMaxChunks))) return rc;       // per chunk: [0] overflow groups, [1] low-complexity blocks
-        uint32_t *d_lowc = nullptr;                                    // block numbers set aside by the scatter pass
-        if ((rc = sc.get(&d_lowc, (size_t)nblocks + 1))) return rc;
-        if ((rc = sc.get(&d_geo, (size_t)n_rows))) return rc;
-        if ((rc = sc.get(&d_ghist, (size_t)groups_stride * n_chunks_p))) return rc;
-        if ((rc = sc.get(&d_gbase, (size_t)(groups_stride + 1) * n_chunks_p))) return rc;
-        if ((rc = sc.get(&d_gcur1, (size_t)(kg::kHDigits + 1) * n_chunks_p))) return rc;
-        if ((rc = sc.get(&d_gcur2, (size_t)groups_stride * n_chunks_p))) return rc;
-        if ((rc = sc.get(&d_gtile, (size_t)(kg::kHDigits + 1) * n_chunks_p))) return rc;
-        if (kg::group_place_lds(gshift, gshift == 10) > t->place_lds[AA ? 1 : 0]) {
-            const size_t want_lds = kg::group_place_lds(gshift, gshift == 10);
-            HIP_TRY(hipFuncSetAttribute((const void *)kg::group_place_kernel<AA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want_lds));
-            t->place_lds[AA ? 1 : 0] = want_lds;
-        }
-        if (groups_stride * 4u > t->hist_lds) {
-            HIP_TRY(hipFuncSetAttribute((const void *)kg::hit_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(groups_stride * 4u)));
-            t->hist_lds = groups_stride * 4u;
-        }
-        if ((rc = sc.get(&d_pc, 48))) return rc;
-        unsigned long long *d_ctr = (unsigned long long *)(d_totals + 2);
-        // the tag pass on the byte home index instead of the tags (bucket_index_kernel) unless the scan counts the slots it
-        // inspects (the walk the index avoids) or KG_BIDX=0.  KG_F_PROGRESS alone runs the index pass's PROG variant (it
-        // summarises the certain misses' walks) and the verify / overflow passes' PROG variants (they note theirs), nothing counted.
-        const bool use_bidx = t->d_bidx != nullptr && !counters_req && env_u32("KG_BIDX", 1u) != 0;
-        const bool part_counters = counters && !use_bidx;
-        prog_index = progress && use_bidx;
-        const size_t lds = kg::scatter_lds_bytes<AA>(part_buckets);
-        if (t->scatter_lds[AA ? 1 : 0] < lds) {         // once per table (and geometry): the call costs tens of microseconds
-            HIP_TRY(hipFuncSetAttribute((const void *)kg::part_scatter_kernel<AA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            t->scatter_lds[AA ? 1 : 0] = lds;
-        }
-        // Tag workgroups per CU.  How many of them run beside a scatter workgroup of the next chunk is decided by the SIMDs'
-        // VGPRs (kg_partition.hpp, "Register budgets": two per CU since round 3, one before), the rest wait for the scatter
-        // workgroup to leave; the hand-out is by ticket, so the count only decides how fast freed registers are taken up.
-        // Round 2 (one tag wave per SIMD beside the scatter pass): 4 per CU 20.4 ms, 8 per CU 20.8 (profiles/r02_pipeline.md);
-        // round 3 (two): 4 per CU 19.78 ms, 8 per CU 19.56, bench.py 20.5 -> 20.25 ms per step (profiles/r03_experiments.md).
-        const uint32_t probe_grid = env_knob("KG_PROBE_GRID", 256u * 8u, 8u, kMaxGrid, 8u);
-        // the byte-index pass: four workgroups per CU -- at 32 VGPRs they are the four waves per SIMD that fit beside a scatter
-        // workgroup (4 x 96 + 4 x 32 = 512); with eight queued the stage is 0.4 ms slower (16.37 against 15.93 ms, r04 c04)
-        const uint32_t index_grid = env_knob("KG_INDEX_GRID", 256u * 4u, 8u, kMaxGrid, 8u);
-        // ... and the regions it takes per hand-out: regions expected to hold fewer than ~640 / ~320 entries (about 0.7 of the
-        // mean the capacity was computed from is valid DNA) are handed out two / four at a time (bucket_index_kernel)
-        // wave priorities (s_setprio) of the two passes that share the CUs: kg_device.hpp, set_wave_prio
-        const uint32_t scatter_prio = std::min(3u, env_u32("KG_SCATTER_PRIO", 1u)), index_prio = std::min(3u, env_u32("KG_INDEX_PRIO", 2u)),
-                       verify_prio = std::min(3u, env_u32("KG_VERIFY_PRIO", n_chunks_p == 1 ? 2u : 0u));
-        uint32_t index_r = env_u32("KG_INDEX_R", 0u);
-        if (index_r == 0) index_r = mean * 0.7 >= 640.0 ? 1u : mean * 0.7 >= 320.0 ? 2u : 4u;
-        if (index_r != 1 && index_r != 2) index_r = 4;
-        while (index_r > 1 && (n_wg % index_r != 0 || kg::kIndexN % index_r != 0)) index_r /= 2;
-        // verify workgroups: two per CU.  With eight (until round 3) the pass alone is 15 % faster, but its workgroups take all the
-        // registers an ending tag pass frees, and the next tag pass -- the critical chain -- starts behind them: stage 18.3 ->
-        // 18.15 ms, 125 Mbp shard 3.18 -> 3.10 (profiles/r03_experiments.md)
-        const uint32_t verify_grid = env_knob("KG_VERIFY_GRID", 256u * 2u, 1u, kMaxGrid);
-        // The two kernels that usually find nothing to do (no low-complexity block set aside, no overflow group) sit on the
-        // stage's critical chain -- in front of every tag pass and behind every verify pass -- and beside the other passes a
-        // grid of 2048 / 1024 workgroups takes 0.1 / 0.35 ms just to be scheduled and leave (profiles/r03_kernel_stats.csv);
-        // one workgroup per CU leaves in microseconds and is still the whole chip when there is work.
-        const uint32_t lowc_grid = env_knob("KG_LOWC_GRID", 256u, 1u, kMaxGrid), ovf_grid = env_knob("KG_OVF_GRID", 256u, 1u, kMaxGrid);
-        // per-chunk lists: hits (unordered) and candidates = fingerprint matches (hits + ~0.4 % of the probes) + the
-        // ~2 % of the probes whose first tag window decides nothing
-        const uint64_t list_slack = (uint64_t)(std::max(std::max(probe_grid, index_grid), verify_grid) + 64) * 4 * kg::kUChunk + 4096;
-        uint64_t ucap = ((uint64_t)((double)windows * t->stage_ratio * max_frac) + list_slack + kg::kUChunk - 1) / kg::kUChunk * kg::kUChunk;
-        uint64_t ccap = ((uint64_t)((double)windows * (t->stage_ratio * 1.25 + 0.03) * max_frac) + list_slack + kg::kUChunk - 1) /
-                        kg::kUChunk * kg::kUChunk;
-        if (test_hook("KG_TEST_TINY_LISTS")) ucap = ccap = kg::kUChunk;      // tests: force the resize-and-rerun path
-        kg_hit *d_ulist = nullptr;
-        uint32_t *d_cused = nullptr, *d_candused = nullptr;
-        kg::CandRec *d_cand = nullptr;
-        // whatever way this block is left (an error return in the middle of an attempt included), the list blocks go
-        // back to the cache with the rest of the scratch once the streams are idle (Scratch's destructor runs later)
-        struct ListGuard {
-            Scratch &sc;
-            void **slot[6];
-            ~ListGuard() { for (void **q : slot) if (*q) { sc.adopt(*q); *q = nullptr; } }
-        } list_guard{sc, {(void **)&d_ulist, (void **)&d_cused, (void **)&d_cand, (void **)&d_candused, (void **)&d_sortA, (void **)&d_sortB}};
-        bool too_skewed = false;
-        const uint32_t grab_unit = 256u * (uint32_t)std::max(kg::kProbeN, kg::kIndexN);      // (powers of two: the larger is a multiple of the other)
-        const uint32_t probe_grab = env_knob("KG_PROBE_GRAB", cap, grab_unit, 1u << 24, grab_unit);
-        uint64_t h_tot[6] = {0, 0, 0, 0, 0, 0};
-        HIP_TRY(hipEventRecord(t->ev[1], t->stream));
-        for (int attempt = 0; attempt < 3; attempt++) {
-            const uint64_t hits_cap = ucap * n_chunks_p;
-            const size_t cused_stride = (size_t)(ucap / kg::kUChunk + 1), candused_stride = (size_t)(ccap / kg::kUChunk + 1);
-            if ((rc = dalloc(t, (void **)&res->d_hits, hits_cap * sizeof(kg_hit)))) return rc;
-            if (progress && (rc = dalloc(t, (void **)&res->d_hit_slots, hits_cap * 4))) return rc;
-            if ((rc = dalloc(t, (void **)&d_ulist, ucap * n_chunks_p * sizeof(kg_hit)))) return rc;
-            if ((rc = dalloc(t, (void **)&d_cused, cused_stride * n_chunks_p * 4))) return rc;
-            if ((rc = dalloc(t, (void **)&d_cand, ccap * n_chunks_p * sizeof(kg::CandRec)))) return rc;
-            if ((rc = dalloc(t, (void **)&d_candused, candused_stride * n_chunks_p * 4))) return rc;
-            if ((rc = dalloc(t, (void **)&d_sortA, ucap * n_chunks_p * sizeof(kg_hit)))) return rc;
-            if ((rc = dalloc(t, (void **)&d_sortB, ucap * n_chunks_p * sizeof(kg_hit)))) return rc;
-            {   // one launch for all clears (d_totals: totals, counters and flags of a re-run start over)
-                kg::ClearList cl;
-                cl.n = 7;
-                cl.p[0] = d_cused; cl.words[0] = (uint64_t)cused_stride * n_chunks_p;
-                cl.p[1] = d_candused; cl.words[1] = (uint64_t)candused_stride * n_chunks_p;
-                cl.p[2] = reinterpret_cast<uint32_t *>(d_pc); cl.words[2] = 48 * 2;
-                cl.p[3] = reinterpret_cast<uint32_t *>(d_totals); cl.words[3] = 16;
-                cl.p[4] = d_ovfc; cl.words[4] = 8 * kMaxChunks;
-                cl.p[5] = d_next; cl.words[5] = (uint64_t)next_stride * n_chunks_p;
-                cl.p[6] = d_ghist; cl.words[6] = (uint64_t)groups_stride * n_chunks_p;
-                cl.p[7] = nullptr; cl.words[7] = 0;
-                uint64_t most = 1;                                      // the grid follows the LARGEST list (the kernel strides)
-                for (int k = 0; k < cl.n; k++) most = std::max(most, cl.words[k]);
-                most /= 4;
-                hipLaunchKernelGGL(kg::clear_many_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (most + 255) / 256 + 1)), dim3(256), 0,
-                                   t->stream, cl);
-            }
-            HIP_TRY(hipEventRecord(t->pev[16], t->stream));               // fork: stream2 starts behind the clears
-            HIP_TRY(hipStreamWaitEvent(t->stream2, t->pev[16], 0));
-            HIP_TRY(hipStreamWaitEvent(t->stream3, t->pev[16], 0));
-            {   // the rows' geometry records (kg_order.hpp): they depend on the batch only, and the verify stream has nothing to do
-                // until the first chunk is scattered and probed
-                const uint64_t nthr = nblocks * PER;
-                hipLaunchKernelGGL((kg::row_geo_kernel<AA>), dim3((uint32_t)((nthr + 255) / 256)), dim3(256), 0, t->stream3, d_blocks,
-                                   (uint32_t)nblocks, d_geo);
-            }
-#define KG_PROBE_ARGS t->d_entries, t->d_tags, t->limit, (uint64_t)t->num_sigs, t->magic
-            for (uint32_t c = 0; c < n_chunks_p; c++) {
-                const uint32_t lo = (uint32_t)clo[c], nb = (uint32_t)(clo[c + 1] - clo[c]);
-                uint64_t *ent_c = d_ent + (uint64_t)c * n_regions_total * cap;
-                uint32_t *fill_c = d_fill + (uint64_t)c * n_regions_total;
-                uint32_t *next_c = d_next + (size_t)c * next_stride;
-                uint32_t *ovfc_c = d_ovfc + 8 * c, *ovf_bucket_c = d_ovf_bucket + (size_t)c * ovf_cap;
-                uint64_t *ovf_ent_c = d_ovf_ent + (size_t)c * ovf_cap * kg::kGroup;
-                kg_hit *ulist_c = d_ulist + (uint64_t)c * ucap;
-                uint32_t *cused_c = d_cused + c * cused_stride, *candused_c = d_candused + c * candused_stride;
-                kg::CandRec *cand_c = d_cand + (uint64_t)c * ccap;
-                unsigned long long *ucur_c = (unsigned long long *)(d_pc + c), *ccur_c = (unsigned long long *)(d_pc + 8 + c);
-                (void)0;
-                if (!seq_uploaded && (rc = upload(offsets[cseq[c]], offsets[cseq[c + 1]]))) return rc;
-                hipLaunchKernelGGL((kg::part_scatter_kernel<AA>), dim3(n_wg), dim3(kg::kWave * kg::kScatterWaves), lds, t->stream, d_seq,
-                                   d_blocks, lo, nb, t->limit, (uint32_t)t->num_sigs, t->m35, part_shift, part_buckets,
-                                   cap, ent_c, fill_c, ovfc_c, ovf_cap, ovf_bucket_c, ovf_ent_c, ovfc_c + 1, d_lowc + lo, d_ctr, d_prog, scatter_prio);
-                hipStream_t s2 = t->stream2, s3 = t->stream3;
-                HIP_TRY(hipEventRecord(t->pev[2 * c], t->stream));
-                HIP_TRY(hipStreamWaitEvent(t->stream2, t->pev[2 * c], 0));
-                // the low-complexity blocks the scatter pass set aside (usually none: every workgroup reads the count and
-                // leaves).  In front of the chunk's tag pass, not behind its scatter pass, and in one-wave workgroups whose
-                // 4.9 KB of LDS fit beside a resident scatter workgroup (153 KB of a CU's 160): with four-wave workgroups
-                // (15.8 KB) the kernel -- and the tag pass behind it -- waited for the NEXT chunk's scatter pass to leave
-                // the CUs (profiles/r02_pipeline.md).
-                hipLaunchKernelGGL((kg::lowc_blocks_kernel<AA>), dim3(lowc_grid), dim3(64 * kg::kLowcWaves), 0, s2, d_seq, d_blocks, ovfc_c + 1, d_lowc + lo,
-                                   t->limit, (uint32_t)t->num_sigs, t->m35, part_shift, n_wg, cap, ent_c, fill_c, ovfc_c, ovf_cap,
-                                   ovf_bucket_c, ovf_ent_c, d_ctr, d_prog);
-#define KG_TAG_ARGS t->d_tags, t->limit, (uint64_t)t->num_sigs, ent_c, fill_c, n_wg, cap, part_buckets, part_shift, probe_grab, next_c, cand_c, \
-                    candused_c, ccur_c, ccap, d_ctr
-#define KG_ULIST_ARGS ulist_c, cused_c, ucur_c, ucap, d_ctr, d_prog
-                if (use_bidx) {
-#define KG_INDEX_ARGS t->d_bidx, (uint32_t)std::min<uint64_t>(t->tail_start, 0xFFFFFFFFull), ent_c, fill_c, n_wg, cap, \
-                      part_buckets, part_shift, probe_grab, next_c, cand_c, candused_c, ccur_c, ccap, d_ctr, index_prio
-#define KG_INDEX_LAUNCH(R, X) hipLaunchKernelGGL((kg::bucket_index_kernel<kg::kIndexN, R, X>), dim3(index_grid), dim3(256), 0, s2, KG_INDEX_ARGS, \
-                                                 (kg::Progress *)nullptr)
-#define KG_INDEX_LAUNCH_P(R, X) hipLaunchKernelGGL((kg::bucket_index_kernel<kg::kIndexN, R, X, true>), dim3(index_grid), dim3(256), 0, s2, \
-                                                   KG_INDEX_ARGS, d_prog)
-                    // regions per hand-out by their expected fill (an iteration covers 256 * N / R entry slots of each); the
-                    // kernel for tables whose classes are their quotients has no q % 19
-                    if (prog_index) {
-                        if (t->bidx_exact) { if (index_r <= 1) KG_INDEX_LAUNCH_P(1, true); else if (index_r == 2) KG_INDEX_LAUNCH_P(2, true); else KG_INDEX_LAUNCH_P(4, true); }
-                        else { if (index_r <= 1) KG_INDEX_LAUNCH_P(1, false); else if (index_r == 2) KG_INDEX_LAUNCH_P(2, false); else KG_INDEX_LAUNCH_P(4, false); }
-                    }
-                    else if (t->bidx_exact) { if (index_r <= 1) KG_INDEX_LAUNCH(1, true); else if (index_r == 2) KG_INDEX_LAUNCH(2, true); else KG_INDEX_LAUNCH(4, true); }
-                    else { if (index_r <= 1) KG_INDEX_LAUNCH(1, false); else if (index_r == 2) KG_INDEX_LAUNCH(2, false); else KG_INDEX_LAUNCH(4, false); }
-#undef KG_INDEX_LAUNCH_P
-#undef KG_INDEX_LAUNCH
-#undef KG_INDEX_ARGS
-                }
-                else if (part_counters) hipLaunchKernelGGL((kg::bucket_tag_kernel<true>), dim3(probe_grid), dim3(256), 0, s2, KG_TAG_ARGS, d_prog);
-                else hipLaunchKernelGGL((kg::bucket_tag_kernel<false>), dim3(probe_grid), dim3(256), 0, s2, KG_TAG_ARGS, (kg::Progress *)nullptr);
-                HIP_TRY(hipEventRecord(t->pev[2 * c + 1], s2));
-                HIP_TRY(hipStreamWaitEvent(s3, t->pev[2 * c + 1], 0));
-                if (part_counters) {
-                    hipLaunchKernelGGL((kg::verify_kernel<AA, true>), dim3(verify_grid), dim3(256), 0, s3, KG_PROBE_ARGS, cand_c,
-                                       candused_c, ccur_c, ccap, KG_ULIST_ARGS, verify_prio);
-                    hipLaunchKernelGGL((kg::overflow_probe_kernel<AA, true>), dim3(ovf_grid), dim3(256), 0, s3, KG_PROBE_ARGS,
-                                       ovf_bucket_c, ovf_ent_c, ovfc_c, ovf_cap, part_shift, KG_ULIST_ARGS);
-                } else if (prog_index) {
-                    hipLaunchKernelGGL((kg::verify_kernel<AA, false, true>), dim3(verify_grid), dim3(256), 0, s3, KG_PROBE_ARGS, cand_c,
-                                       candused_c, ccur_c, ccap, KG_ULIST_ARGS, verify_prio);
-                    hipLaunchKernelGGL((kg::overflow_probe_kernel<AA, false, true>), dim3(ovf_grid), dim3(256), 0, s3, KG_PROBE_ARGS,
-                                       ovf_bucket_c, ovf_ent_c, ovfc_c, ovf_cap, part_shift, KG_ULIST_ARGS);
-                } else {
-                    hipLaunchKernelGGL((kg::verify_kernel<AA, false>), dim3(verify_grid), dim3(256), 0, s3, KG_PROBE_ARGS, cand_c,
-                                       candused_c, ccur_c, ccap, KG_ULIST_ARGS, verify_prio);
-                    hipLaunchKernelGGL((kg::overflow_probe_kernel<AA, false>), dim3(ovf_grid), dim3(256), 0, s3, KG_PROBE_ARGS,
-                                       ovf_bucket_c, ovf_ent_c, ovfc_c, ovf_cap, part_shift, KG_ULIST_ARGS);
-                }
-#undef KG_TAG_ARGS
-#undef KG_ULIST_ARGS
-                HIP_TRY(hipEventRecord(t->pev[20 + c], s3));                // chunk c verified
-                HIP_TRY(hipGetLastError());
-                if (c + 1 == n_chunks_p) HIP_TRY(hipEventRecord(t->ev[5], t->stream));   // all chunks scattered
-            }
-#undef KG_PROBE_ARGS
-            seq_uploaded = true;
-            // Ordered placement (kg_order.hpp), chunk by chunk, behind the LAST scatter pass and beside the tag passes that are
-            // still running: its partition workgroups hold 51 KB of LDS and eight wave slots each, and started beside a scatter
-            // pass (105 KB and 16 wave slots of every CU) the two starve each other -- chunk 0's two partition passes took
-            // 2.2 + 4.3 ms instead of 0.15 + 0.55 and the scatter pass beside them 7.8 ms instead of 2 (profiles/r03_ordering.md).
-            // Beside a tag pass the ordering kernels crawl (a partition pass 1.7-3.9 ms instead of 0.13: every memory access
-            // queues behind the tag pass's line gathers) while the tag pass hardly notices them.  KG_ORDER_STREAMS=n (1..4; not
-            // the default) gives the chunks' orderings n streams of their own, of the LOWEST priority because that gives them
-            // hardware queues of their own (a fourth stream of normal priority shares a queue with the third): the orderings
-            // of chunks 0-2 then all crawl beside the last tag passes, single scans 20.1-20.25 ms against 20.4, but twenty
-            // scans back to back (bench.py) 21.45 against 21.23 ms per step (profiles/r03_experiments.md).
-            const uint32_t n_os = n_chunks_p < 2 ? 0u : std::min(env_u32("KG_ORDER_STREAMS", 0u), 4u);
-            const bool early_totals = n_os == 0 && env_u32("KG_EARLY_TOTALS", 1u) != 0;     // (every chunk's ordering on stream3: in order behind every verify pass)
-            for (uint32_t k = 0; k < n_os; k++)
-                if (!t->ostream[k]) {
-                    int pr_least = 0, pr_greatest = 0;
-                    HIP_TRY(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
-                    HIP_TRY(hipStreamCreateWithPriority(&t->ostream[k], hipStreamNonBlocking, pr_least));
-                }
-            for (uint32_t c = 0; c < n_chunks_p; c++) {
-                const uint32_t lo = (uint32_t)clo[c], nb = (uint32_t)(clo[c + 1] - clo[c]);
-                kg_hit *ulist_c = d_ulist + (uint64_t)c * ucap;
-                uint32_t *cused_c = d_cused + c * cused_stride;
-                unsigned long long *ucur_c = (unsigned long long *)(d_pc + c);
-                uint64_t *base_c = d_pc + 16 + c, *ctot_c = d_pc + 32 + c;
-                hipStream_t s3 = t->stream;
-                if (n_os) {
-                    s3 = t->ostream[c % n_os];
-                    HIP_TRY(hipStreamWaitEvent(s3, t->ev[5], 0));          // behind the last scatter pass
-                }
-                HIP_TRY(hipStreamWaitEvent(s3, t->pev[20 + c], 0));
-                // group histogram -> group starts -> two partition passes by key range -> ranking inside each group of rows
-                {
-                    const uint64_t row_lo = (uint64_t)lo * PER, row_hi = row_lo + (uint64_t)nb * PER;
-                    const uint32_t g0 = (uint32_t)(row_lo >> gshift);
-                    const uint32_t n_groups = nb ? (uint32_t)(((row_hi - 1) >> gshift) - g0 + 1) : 1u;
-                    uint32_t *ghist_c = d_ghist + (size_t)c * groups_stride, *gbase_c = d_gbase + (size_t)c * (groups_stride + 1);
-                    uint32_t *gcur1_c = d_gcur1 + (size_t)c * (kg::kHDigits + 1), *gcur2_c = d_gcur2 + (size_t)c * groups_stride,
-                             *gtile_c = d_gtile + (size_t)c * (kg::kHDigits + 1);
-                    kg_hit *sortA_c = d_sortA + (uint64_t)c * ucap, *sortB_c = d_sortB + (uint64_t)c * ucap;
-                    const uint32_t ogrid = env_knob("KG_ORDER_GRID", 256u * 3u, 1u, kMaxGrid);
-                    hipLaunchKernelGGL(kg::hit_hist_kernel, dim3(ogrid), dim3(kg::kHThreads), (size_t)n_groups * 4, s3, ulist_c, cused_c, ucur_c, ucap,
-                                       g0, 6u + gshift, n_groups, ghist_c);
-                    hipLaunchKernelGGL(kg::group_scan_kernel, dim3(1), dim3(kg::kGsThreads), 0, s3, ghist_c, n_groups, gbase_c, gcur1_c, gcur2_c, ctot_c, gtile_c);
-                    if (n_os && c) HIP_TRY(hipStreamWaitEvent(s3, t->pev[32 + c - 1], 0));      // base of chunk c = base + total of c - 1
-                    hipLaunchKernelGGL(kg::chunk_base_kernel, dim3(1), dim3(1), 0, s3, ctot_c, base_c,
-                                       c + 1 == n_chunks_p ? d_totals : (uint64_t *)nullptr);
-                    if (n_os) HIP_TRY(hipEventRecord(t->pev[32 + c], s3));
-                    if (early_totals && c + 1 == n_chunks_p) {
-                        // Everything the host wants to know about this attempt is final here -- the list cursors (the last verify
-                        // pass is behind us on this stream), the overflow counters, the exact hit total (chunk_base_kernel just
-                        // above): it is sent now, and the host reads it, makes the aggregation's allocations and enqueues its
-                        // kernels while the last chunk's partition passes and placement still run (the round trip was ~70 us
-                        // of every scan, behind the ordering).
-                        HIP_TRY(hipMemcpyAsync(t->h_pin, d_pc, 48 * 8, hipMemcpyDeviceToHost, s3));
-                        HIP_TRY(hipMemcpyAsync(t->h_pin + 48, d_ovfc, 8 * kMaxChunks * 4, hipMemcpyDeviceToHost, s3));
-                        HIP_TRY(hipMemcpyAsync(t->h_pin + 80, d_totals, 48, hipMemcpyDeviceToHost, s3));
-                        HIP_TRY(hipEventRecord(t->pev[19], s3));
-                    }
-                    hipLaunchKernelGGL((kg::hit_partition_kernel<true>), dim3(ogrid), dim3(kg::kHThreads), 0, s3, ulist_c, cused_c, ucur_c, ucap,
-                                       gbase_c, n_groups, g0, 6u + gshift, gcur1_c, sortA_c, ucap, gtile_c);
-                    hipLaunchKernelGGL((kg::hit_partition_kernel<false>), dim3(ogrid), dim3(kg::kHThreads), 0, s3, sortA_c, cused_c, ucur_c, ucap,
-                                       gbase_c, n_groups, g0, 6u + gshift, gcur2_c, sortB_c, ucap, gtile_c);
-                    const bool place_staged = gshift == 10 && env_u32("KG_PLACE_STAGED", 1u) != 0;
-                    hipLaunchKernelGGL((kg::group_place_kernel<AA>), dim3(std::min(n_groups, 256u * 8u)), dim3(kg::kHThreads),
-                                       kg::group_place_lds(gshift, place_staged), s3,
-                                       sortB_c, gbase_c, n_groups, g0, gshift, (uint32_t)row_lo, (uint32_t)row_hi, d_geo, (uint64_t)n_rows,
-                                       place_staged ? 1u : 0u, base_c, res->d_hits, hits_cap, d_offs, res->d_hit_slots);
-                }
-                HIP_TRY(hipGetLastError());
-            }
+    pl.clo.push_back(nblocks); pl.cseq.push_back((int64_t)b.ibase.size() - 1);
+    pl.n_chunks = (uint32_t)pl.clo.size() - 1;
+    for (uint32_t c = 0; c < pl.n_chunks; c++) pl.max_chunk = std::max(pl.max_chunk, pl.clo[c + 1] - pl.clo[c]);
+    const uint64_t max_chunk = pl.max_chunk;
+    const uint64_t chunk_blocks = (max_chunk + kg::kScatterWaves - 1) / kg::kScatterWaves * kg::kScatterWaves;
+    const double max_frac = (double)max_chunk / (double)nblocks;
+    uint32_t n_wg = env_knob("KG_PART_WGS", 256u, 1u, kMaxGrid);
+    if ((uint64_t)n_wg * kg::kScatterWaves > chunk_blocks) n_wg = (uint32_t)((chunk_blocks + kg::kScatterWaves - 1) / kg::kScatterWaves);
+    const uint64_t blocks_per_wg = ((chunk_blocks + (uint64_t)n_wg * kg::kScatterWaves - 1) / ((uint64_t)n_wg * kg::kScatterWaves)) * kg::kScatterWaves;
+    // region capacity: the mean if every window were valid and hashed uniformly, plus 6 sigma, in 16-entry groups
+    const double mean = (double)blocks_per_wg * WIN / (double)pl.buckets * (env_u32("KG_PART_SLACK", 100u) / 100.0);
+    const uint64_t cap64 = ((uint64_t)(mean + 6.0 * std::sqrt(mean) + 32.0) + 15) / 16 * 16;
+    // the scatter pass's address arithmetic is in 24-bit multiplies (region number x capacity): geometries beyond that
+    // (one bucket and millions of blocks per scatter workgroup; not reachable with the default knobs) take the direct path
+    if (cap64 >= (1ull << 24) || (uint64_t)pl.buckets * n_wg >= (1ull << 24)) return KG_OK;
+    pl.n_wg = n_wg;
+    pl.cap = (uint32_t)cap64;
+    pl.n_regions = (uint64_t)pl.buckets * n_wg;
+    // overflow list of one chunk (groups): an eighth of the regions' capacity (low-complexity sequence: 3 % of the
+    // bases in homopolymer runs overflow ~5 % of the entries; beyond the list the scan falls back to direct probing)
+    pl.ovf_cap = env_u32("KG_PART_OVF_GROUPS", (uint32_t)std::min<uint64_t>(1u << 23, std::max<uint64_t>(65536, pl.n_regions * pl.cap / 16 / 8)));
+    // ordered placement (kg_order.hpp): groups of 2^gshift rows, at most kMaxGroups per chunk (8192 while 4096-row groups allow it)
+    while (pl.gshift < 12 && ((max_chunk * PER) >> pl.gshift) + 2 > 8192) pl.gshift++;
+    pl.groups_stride = (uint32_t)(((max_chunk * PER) >> pl.gshift) + 2);      // a chunk's rows start anywhere inside a group
+    if (pl.groups_stride > kg::kMaxGroups) return fail(KG_ERR_LIMIT, "a chunk of the batch holds more than 2^26 window rows");
+    pl.next_stride = std::max<size_t>((size_t)pl.buckets + 8, 256);   // tag pass: one hand-out counter per XCD group, 128 B apart
+    // the tag pass on the byte home index instead of the tags (bucket_index_kernel) unless the scan counts the slots it
+    // inspects (the walk the index avoids) or KG_BIDX=0.  KG_F_PROGRESS alone runs the index pass's PROG variant (it
+    // summarises the certain misses' walks) and the verify / overflow passes' PROG variants (they note theirs), nothing counted.
+    pl.use_bidx = t->d_bidx != nullptr && !counters_req && env_u32("KG_BIDX", 1u) != 0;
+    pl.part_counters = (counters_req || progress) && !pl.use_bidx;
+    pl.prog_index = progress && pl.use_bidx;
+    pl.scatter_lds = kg::scatter_lds_bytes<AA>(pl.buckets);
+    // Tag workgroups per CU.  How many of them run beside a scatter workgroup of the next chunk is decided by the SIMDs'
+    // VGPRs (kg_partition.hpp, "Register budgets": two per CU since round 3, one before), the rest wait for the scatter
+    // workgroup to leave; the hand-out is by ticket, so the count only decides how fast freed registers are taken up.
+    // Round 2 (one tag wave per SIMD beside the scatter pass): 4 per CU 20.4 ms, 8 per CU 20.8 (profiles/r02_pipeline.md);
+    // round 3 (two): 4 per CU 19.78 ms, 8 per CU 19.56, bench.py 20.5 -> 20.25 ms per step (profiles/r03_experiments.md).
+    pl.probe_grid = env_knob("KG_PROBE_GRID", 256u * 8u, 8u, kMaxGrid, 8u);
+    // the byte-index pass: four workgroups per CU -- at 32 VGPRs they are the four waves per SIMD that fit beside a scatter
+    // workgroup (4 x 96 + 4 x 32 = 512); with eight queued the stage is 0.4 ms slower (16.37 against 15.93 ms, r04 c04)
+    pl.index_grid = env_knob("KG_INDEX_GRID", 256u * 4u, 8u, kMaxGrid, 8u);
+    // wave priorities (s_setprio) of the passes that share the CUs: kg_device.hpp, set_wave_prio
+    pl.scatter_prio = std::min(3u, env_u32("KG_SCATTER_PRIO", 1u));
+    pl.index_prio = std::min(3u, env_u32("KG_INDEX_PRIO", 2u));
+    pl.verify_prio = std::min(3u, env_u32("KG_VERIFY_PRIO", pl.n_chunks == 1 ? 2u : 0u));
+    // ... and the regions the byte-index pass takes per hand-out: regions expected to hold fewer than ~640 / ~320 entries
+    // (about 0.7 of the mean the capacity was computed from is valid DNA) are handed out two / four at a time
+    // (bucket_index_kernel)
+    uint32_t index_r = env_u32("KG_INDEX_R", 0u);
+    if (index_r == 0) index_r = mean * 0.7 >= 640.0 ? 1u : mean * 0.7 >= 320.0 ? 2u : 4u;
+    if (index_r != 1 && index_r != 2) index_r = 4;
+    while (index_r > 1 && (n_wg % index_r != 0 || kg::kIndexN % index_r != 0)) index_r /= 2;
+    pl.index_r = index_r;
+    // verify workgroups: two per CU.  With eight (until round 3) the pass alone is 15 % faster, but its workgroups take all the
+    // registers an ending tag pass frees, and the next tag pass -- the critical chain -- starts behind them: stage 18.3 ->
+    // 18.15 ms, 125 Mbp shard 3.18 -> 3.10 (profiles/r03_experiments.md)
+    pl.verify_grid = env_knob("KG_VERIFY_GRID", 256u * 2u, 1u, kMaxGrid);
+    // The two kernels that usually find nothing to do (no low-complexity block set aside, no overflow group) sit on the
+    // stage's critical chain -- in front of every tag pass and behind every verify pass -- and beside the other passes a
+    // grid of 2048 / 1024 workgroups takes 0.1 / 0.35 ms just to be scheduled and leave (profiles/r03_kernel_stats.csv);
+    // one workgroup per CU leaves in microseconds and is still the whole chip when there is work.
+    pl.lowc_grid = env_knob("KG_LOWC_GRID", 256u, 1u, kMaxGrid);
+    pl.ovf_grid = env_knob("KG_OVF_GRID", 256u, 1u, kMaxGrid);
+    // per-chunk lists: hits (unordered) and candidates = fingerprint matches (hits + ~0.4 % of the probes) + the
+    // ~2 % of the probes whose first tag window decides nothing
+    pl.list_slack = (uint64_t)(std::max(std::max(pl.probe_grid, pl.index_grid), pl.verify_grid) + 64) * 4 * kg::kUChunk + 4096;
+    pl.ucap = ((uint64_t)((double)b.windows * t->stage_ratio * max_frac) + pl.list_slack + kg::kUChunk - 1) / kg::kUChunk * kg::kUChunk;
+    pl.ccap = ((uint64_t)((double)b.windows * (t->stage_ratio * 1.25 + 0.03) * max_frac) + pl.list_slack + kg::kUChunk - 1) /
+              kg::kUChunk * kg::kUChunk;
+    if (test_hook("KG_TEST_TINY_LISTS")) pl.ucap = pl.ccap = kg::kUChunk;      // tests: force the resize-and-rerun path
+    const uint32_t grab_unit = 256u * (uint32_t)std::max(kg::kProbeN, kg::kIndexN);      // (powers of two: the larger is a multiple of the other)
+    pl.probe_grab = env_knob("KG_PROBE_GRAB", pl.cap, grab_unit, 1u << 24, grab_unit);
+    // Ordering streams and early totals: scan_partitioned, in front of the chunks' orderings
+    pl.n_os = pl.n_chunks < 2 ? 0u : std::min(env_u32("KG_ORDER_STREAMS", 0u), kMaxOrderStreams);
+    pl.early_totals = pl.n_os == 0 && env_u32("KG_EARLY_TOTALS", 1u) != 0;     // (every chunk's ordering on one stream, in order: behind every verify pass)
+    pl.order_grid = env_knob("KG_ORDER_GRID", 256u * 3u, 1u, kMaxGrid);
+    pl.place_staged = pl.gshift == 10 && env_u32("KG_PLACE_STAGED", 1u) != 0;
+    pl.debug = getenv("KG_DEBUG") != nullptr;
+    pl.applicable = true;
+    return KG_OK;
+}
 
-            for (uint32_t k = 0; k < n_os; k++) {
-                HIP_TRY(hipEventRecord(t->pev[40 + k], t->ostream[k]));
-                HIP_TRY(hipStreamWaitEvent(t->stream, t->pev[40 + k], 0));
-            }
-            HIP_TRY(hipEventRecord(t->pev[17], t->stream2));              // join
-            HIP_TRY(hipStreamWaitEvent(t->stream, t->pev[17], 0));
-            HIP_TRY(hipEventRecord(t->pev[18], t->stream3));
-            HIP_TRY(hipStreamWaitEvent(t->stream, t->pev[18], 0));
-            HIP_TRY(hipEventRecord(t->ev[7], t->stream));
-            st.scan_launches++;
-            const uint64_t *h_pc = t->h_pin;
-            const uint32_t *h_ovf = reinterpret_cast<const uint32_t *>(t->h_pin + 48);
-            static_assert(8 * kMaxChunks * 4 <= 32 * 8, "overflow counters must fit their pinned words");
-            HIP_TRY(hipEventRecord(t->ev[2], t->stream));                 // end of the scan stage (of this attempt)
-            if (early_totals) {
-                HIP_TRY(hipEventSynchronize(t->pev[19]));                 // (the ordering of the last chunk may still be running)
-            } else {
-                HIP_TRY(hipMemcpyAsync(t->h_pin, d_pc, 48 * 8, hipMemcpyDeviceToHost, t->stream));
-                HIP_TRY(hipMemcpyAsync(t->h_pin + 48, d_ovfc, 8 * kMaxChunks * 4, hipMemcpyDeviceToHost, t->stream));
-                HIP_TRY(hipMemcpyAsync(t->h_pin + 80, d_totals, 48, hipMemcpyDeviceToHost, t->stream));   // pinned: one host round trip for all three
-                HIP_TRY(hipStreamSynchronize(t->stream));
-            }
-            for (int k = 0; k < 6; k++) h_tot[k] = t->h_pin[80 + k];
-            uint64_t need_u = 0, need_c = 0;
-            uint32_t max_ovf = 0, guard = 0;
-            for (uint32_t c = 0; c < n_chunks_p; c++) {
-                need_u = std::max(need_u, h_pc[c]); need_c = std::max(need_c, h_pc[8 + c]);
-                max_ovf = std::max(max_ovf, h_ovf[8 * c]);
-                guard |= h_ovf[8 * c + 2];
-            }
-            if (getenv("KG_DEBUG"))
-                fprintf(stderr, "[kg] partition attempt %d: %u chunks (largest %llu of %llu blocks), overflow groups <= %u (cap %u), hit list <= %llu "
-                                "(cap %llu), candidates <= %llu (cap %llu), regions/chunk %llu x %u entries, %u buckets, shift %u, %u scatter "
-                                "workgroups, hits %llu, %s\n",
-                        attempt, n_chunks_p, (unsigned long long)max_chunk, (unsigned long long)nblocks, max_ovf, ovf_cap,
-                        (unsigned long long)need_u, (unsigned long long)ucap, (unsigned long long)need_c, (unsigned long long)ccap,
-                        (unsigned long long)n_regions_total, cap, part_buckets, part_shift, n_wg, (unsigned long long)h_pc[16 + n_chunks_p], use_bidx ? "byte home index" : "tags");
-            const bool redo = guard || max_ovf > ovf_cap || need_u > ucap || need_c > ccap;
-            if (redo && early_totals) HIP_TRY(hipStreamSynchronize(t->stream));   // the attempt is thrown away: its last kernels first
-            if (guard) { too_skewed = true; st.fallback = 2; break; }    // the scatter pass's spin guard fired: direct path
-            if (max_ovf > ovf_cap) { too_skewed = true; st.fallback = 1; break; }   // more overflow than provisioned: direct path
-            n_hits = h_pc[16 + n_chunks_p];
-            if (need_u <= ucap && need_c <= ccap) break;
-            // a list was too small: now the exact need is known (masks are cleared and everything is redone)
-            dfree(t, d_ulist); dfree(t, d_cused); dfree(t, d_cand); dfree(t, d_candused); dfree(t, res->d_hits);   // both streams are idle
-            dfree(t, d_sortA); dfree(t, d_sortB);                         // (the ordering buffers are sized by ucap as well)
-            dfree(t, res->d_hit_slots); res->d_hit_slots = nullptr;
-            d_ulist = nullptr; d_cused = nullptr; d_cand = nullptr; d_candused = nullptr; res->d_hits = nullptr;
-            d_sortA = nullptr; d_sortB = nullptr;
-            if (attempt == 2) return fail(KG_ERR_DEVICE, "hit list overflow after resize (internal error)");
-            // which wave fills which reservation chunk differs from run to run: one partly used chunk per wave on top
-            if (need_c > ccap) { ccap = (need_c + list_slack + kg::kUChunk - 1) / kg::kUChunk * kg::kUChunk; ucap = std::max(ucap, ccap); }   // hits <= candidates
-            else ucap = (need_u + list_slack + kg::kUChunk - 1) / kg::kUChunk * kg::kUChunk;
-        }
-        if (too_skewed) {
-            dfree(t, res->d_hits); dfree(t, res->d_hit_slots);
-            res->d_hits = nullptr; res->d_hit_slots = nullptr;
-        } else {
-            st.windows_valid = part_counters ? (int64_t)h_tot[2] : -1;
-            st.slots_inspected = part_counters ? (int64_t)h_tot[3] : -1;
-            st.lookup_ran_off = h_tot[5] ? 1 : 0;
-            if (windows) {
-                double ratio = (double)n_hits / (double)windows * 1.1 + 1e-3;
-                if (ratio > t->stage_ratio) t->stage_ratio = ratio > 1.0 ? 1.0 : ratio;
-            }
-            st.n_hits = (int64_t)n_hits;
-            part_done = true;
-            st.partitioned = 1;
-            st.part_chunks = (int32_t)n_chunks_p; st.part_buckets = (int32_t)part_buckets; st.part_shift = (int32_t)part_shift;
-            st.part_levels = use_bidx ? 4 : 1;
-        }
-    } while (0);
-    if (!part_done) {
-        st.scan_launches = 0;
-        if (!seq_uploaded) { if ((rc = upload(offsets[0], offsets[n_seqs]))) return rc; seq_uploaded = true; }
-    // ---- scan: encode + probe + staged compaction; re-run once if the staging area was too small ----
+// Geometry of the direct strategy (every probe a random 128-byte line from HBM unless the tag array is L2-sized).
+struct DirectPlan {
+    uint32_t scan_grid, stage_chunk;
+    const uint32_t *d_hbits;            // the table's bit-per-slot digest, or null
+    uint32_t rpg;                       // rows probed together per lane
+    uint64_t stage_cap;                 // staging records the first attempt starts with
+};
+
+template <bool AA>
+DirectPlan plan_direct(const kg_table *t, const BatchPlan &b, bool counters)
+{
+    DirectPlan pl;
     // persistent grid: enough workgroups to fill 256 CUs, few enough that per-wave staging chunks stay small
-    const uint32_t scan_grid = env_knob("KG_SCAN_GRID", 256u * 8u, 1u, kMaxGrid);
-    const uint32_t stage_chunk = env_knob("KG_STAGE_CHUNK", 256u, 1u, 1u << 12);
+    pl.scan_grid = env_knob("KG_SCAN_GRID", 256u * 8u, 1u, kMaxGrid);
+    pl.stage_chunk = env_knob("KG_STAGE_CHUNK", 256u, 1u, 1u << 12);
     // the table's bit-per-slot digest as the direct kernel's first question (tables of <= kHbitsMaxSlots slots; not for scans
     // that count the slots they inspect): config 5's scan 2.28 -> 1.80 ms (r04 c34)
     // KG_DIRECT_FILTER: 0 never, 1 (default) when the tags no longer fit an XCD's 4 MB L2 (below that the bit is one more
     // dependent load in front of an L2 hit), 2 whenever the table has the digest (tests)
     const uint32_t filter_mode = env_u32("KG_DIRECT_FILTER", 1u);
-    const uint32_t *d_hbits_scan = (counters || filter_mode == 0 || (filter_mode == 1 && t->limit <= (4ull << 20))) ? nullptr : t->d_hbits;
+    pl.d_hbits = (counters || filter_mode == 0 || (filter_mode == 1 && t->limit <= (4ull << 20))) ? nullptr : t->d_hbits;
     // rows probed together per lane: three; six behind the digest, where two probes out of three end at the bit (1.80 -> 1.75 ms)
-    uint32_t rpg = AA ? 1u : env_u32("KG_SCAN_RPG", d_hbits_scan ? 6u : 3u);
-    if (rpg != 1 && rpg != 2 && rpg != 3 && rpg != 6) rpg = 3;
-    uint64_t stage_cap = (uint64_t)((double)windows * t->stage_ratio) + 4096 +
-                         (uint64_t)scan_grid * kg::kWavesPerWG * stage_chunk;
-    if (stage_cap > 0xFFFFFF00ull) stage_cap = 0xFFFFFF00ull;
-    if (test_hook("KG_TEST_TINY_LISTS")) stage_cap = 256;                    // tests: force the resize-and-rerun path
-    kg_hit *d_stage = nullptr;
-    uint32_t *d_stage_slot = nullptr;                                        // KG_F_PROGRESS: the found slots, parallel to d_stage
-    struct StageGuard { Scratch &sc; kg_hit *&p; uint32_t *&q; ~StageGuard() { if (p) sc.adopt(p); if (q) sc.adopt(q); } } stage_guard{sc, d_stage, d_stage_slot};
-    for (int attempt = 0; attempt < 2; attempt++) {
-        if ((rc = dalloc(t, (void **)&d_stage, stage_cap * sizeof(kg_hit)))) return rc;
-        if (progress && (rc = dalloc(t, (void **)&d_stage_slot, stage_cap * 4))) return rc;
-        unsigned long long *d_cursor = (unsigned long long *)(d_totals + 1);
-        unsigned long long *d_ctr = (unsigned long long *)(d_totals + 2);
-        HIP_TRY(hipMemsetAsync(d_totals, 0, 64, t->stream));
-        HIP_TRY(hipEventRecord(t->ev[1], t->stream));
-        if (nblocks) {
-            uint64_t wgs = (nblocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG;
-            uint32_t grid = (uint32_t)(wgs < scan_grid ? wgs : scan_grid);      // persistent waves stride over the blocks
-#define KG_SCAN_ARGS t->d_entries, t->d_tags, t->limit, (uint64_t)t->num_sigs, t->magic, t->m35, d_seq, d_blocks, (uint32_t)nblocks, \
-                     d_counts, d_bsb, d_stage, d_cursor, stage_cap, stage_chunk, d_ctr, d_prog, d_stage_slot, \
-                     d_hbits_scan, t->tail_start
-#define KG_SCAN_LAUNCH(C, R) hipLaunchKernelGGL((kg::scan_kernel<AA, C, R>), dim3(grid), dim3(kg::kWave * kg::kWavesPerWG), 0, \
-                                                t->stream, KG_SCAN_ARGS)
-            if (AA) {
-                if (counters) KG_SCAN_LAUNCH(true, 1); else KG_SCAN_LAUNCH(false, 1);
-            } else {
-                constexpr int R1 = AA ? 1 : 1, R2 = AA ? 1 : 2, R3 = AA ? 1 : 3, R6 = AA ? 1 : 6;
-                if (counters) {
-                    if (rpg == 1) KG_SCAN_LAUNCH(true, R1); else if (rpg == 2) KG_SCAN_LAUNCH(true, R2);
-                    else if (rpg == 3) KG_SCAN_LAUNCH(true, R3); else KG_SCAN_LAUNCH(true, R6);
-                } else {
-                    if (rpg == 1) KG_SCAN_LAUNCH(false, R1); else if (rpg == 2) KG_SCAN_LAUNCH(false, R2);
-                    else if (rpg == 3) KG_SCAN_LAUNCH(false, R3); else KG_SCAN_LAUNCH(false, R6);
-                }
-            }
-#undef KG_SCAN_LAUNCH
-#undef KG_SCAN_ARGS
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(t->ev[2], t->stream));
-        st.scan_launches++;
-        if ((rc = prefix_sum(t, d_counts, n_rows, d_offs, d_partial, d_totals))) return rc;
-        uint64_t h_tot[6] = {0, 0, 0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(t->h_pin + 80, d_totals, 48, hipMemcpyDeviceToHost, t->stream));    // (pinned words: no staging copy on the host)
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        for (int k = 0; k < 6; k++) h_tot[k] = t->h_pin[80 + k];
-        n_hits = n_rows ? h_tot[0] : 0;
-        st.windows_valid = counters ? (int64_t)h_tot[2] : -1;
-        st.slots_inspected = counters ? (int64_t)h_tot[3] : -1;
-        st.lookup_ran_off = h_tot[5] ? 1 : 0;
-        if (h_tot[1] <= stage_cap) break;
-        // staging overflow: now the exact need is known
-        dfree(t, d_stage); d_stage = nullptr;
-        dfree(t, d_stage_slot); d_stage_slot = nullptr;
-        if (attempt == 1) return fail(KG_ERR_DEVICE, "staging overflow after resize (internal error)");
-        stage_cap = h_tot[1];
+    pl.rpg = AA ? 1u : env_u32("KG_SCAN_RPG", pl.d_hbits ? 6u : 3u);
+    if (pl.rpg != 1 && pl.rpg != 2 && pl.rpg != 3 && pl.rpg != 6) pl.rpg = 3;
+    pl.stage_cap = (uint64_t)((double)b.windows * t->stage_ratio) + 4096 + (uint64_t)pl.scan_grid * kg::kWavesPerWG * pl.stage_chunk;
+    if (pl.stage_cap > 0xFFFFFF00ull) pl.stage_cap = 0xFFFFFF00ull;
+    if (test_hook("KG_TEST_TINY_LISTS")) pl.stage_cap = 256;                    // tests: force the resize-and-rerun path
+    return pl;
+}
+
+// What every stage of one kg_scan* call works on.
+struct ScanCtx {
+    kg_table *t;
+    kg_result *res;
+    Scratch &sc;
+    const BatchPlan &b;
+    const uint8_t *d_seq, *h_seq;       // h_seq != null: d_seq is an empty device buffer; the characters are still to upload
+    const int64_t *offsets;
+    int64_t n_seqs;
+    bool progress, counters;            // KG_F_PROGRESS; the walks are noted by the counting kernels (KG_F_COUNTERS or progress)
+    bool seq_uploaded;
+    uint64_t n_hits = 0;
+    // device, shared by the strategies
+    int64_t *d_off = nullptr;
+    uint32_t *d_ibase = nullptr;
+    kg::BlockDesc *d_blocks = nullptr;
+    uint32_t *d_counts = nullptr, *d_offs = nullptr, *d_bsb = nullptr;      // direct: hits per row, their prefix, one staging base per (block, row group)
+    uint64_t *d_partial = nullptr, *d_totals = nullptr;                     // prefix-sum scratch; the kTot* words
+    kg::Progress *d_prog = nullptr;
+};
+
+// The characters [a, b) of the batch, where the caller's copy is still on the host.
+int upload_seq(const ScanCtx &cx, int64_t a, int64_t b)
+{
+    if (cx.h_seq && b > a)
+        HIP_TRY(hipMemcpyAsync(const_cast<uint8_t *>(cx.d_seq) + a, cx.h_seq + a, (size_t)(b - a), hipMemcpyHostToDevice, cx.t->stream));
+    return KG_OK;
+}
+
+// Device blocks that are sized per attempt.  release(): straight back to the cache, for a resized attempt to reuse -- only
+// while all streams are idle.  However else the owner's scope is left (an error return in the middle of an attempt included),
+// the blocks go back with the rest of the scratch once the streams are idle (Scratch's destructor runs later).
+template <int N>
+struct BlockGuard {
+    Scratch &sc;
+    void **slot[N];
+    void release() { for (void **q : slot) { dfree(sc.t, *q); *q = nullptr; } }
+    ~BlockGuard() { for (void **q : slot) if (*q) { sc.adopt(*q); *q = nullptr; } }
+};
+
+// ... and the result's hit records of an attempt that is thrown away (all streams idle)
+void drop_hits(kg_table *t, kg_result *res)
+{
+    dfree(t, res->d_hits); dfree(t, res->d_hit_slots);
+    res->d_hits = nullptr; res->d_hit_slots = nullptr;
+}
+
+// The counters the host decides on, to their pinned words (a hipMemcpyAsync to pageable memory blocks the host per copy; to
+// pinned memory it does not: one host round trip for all of them).  d_pc / d_ovfc: null for the direct strategy.
+int send_counters(kg_table *t, const uint64_t *d_pc, const uint32_t *d_ovfc, const uint64_t *d_totals, hipStream_t s)
+{
+    if (d_pc) {
+        HIP_TRY(hipMemcpyAsync(t->h_pin + kPinPc, d_pc, kPcWords * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(t->h_pin + kPinOvf, d_ovfc, kOvfWords * kMaxChunks * 4, hipMemcpyDeviceToHost, s));
     }
-    if (windows) {
-        double ratio = (double)n_hits / (double)windows * 1.1 + 1e-3;
+    HIP_TRY(hipMemcpyAsync(t->h_pin + kPinTotals, d_totals, kTotSent * 8, hipMemcpyDeviceToHost, s));
+    return KG_OK;
+}
+
+// The finished scan's totals (in their pinned words) into the stats, and the staging ratio's high-water mark into the table.
+void note_totals(ScanCtx &cx, uint64_t n_hits, bool counted)
+{
+    kg_table *t = cx.t;
+    kg_stats &st = cx.res->st;
+    const uint64_t *h_tot = t->h_pin + kPinTotals;
+    st.windows_valid = counted ? (int64_t)h_tot[kTotValid] : -1;
+    st.slots_inspected = counted ? (int64_t)h_tot[kTotSlots] : -1;
+    st.lookup_ran_off = h_tot[kTotRanOff] ? 1 : 0;
+    if (cx.b.windows) {
+        double ratio = (double)n_hits / (double)cx.b.windows * 1.1 + 1e-3;
         if (ratio > t->stage_ratio) t->stage_ratio = ratio > 1.0 ? 1.0 : ratio;
     }
+    cx.n_hits = n_hits;
     st.n_hits = (int64_t)n_hits;
+}
+
+// KG_F_PROGRESS: the walks' summary (kg_device.hpp, Progress).  lo[f] = the smallest slot of tenth >= f, found with the
+// reference's own double arithmetic (KGJ:1018) around ceil(f * numSigs / 10) - 1
+int progress_begin(ScanCtx &cx)
+{
+    kg_table *t = cx.t;
+    int rc;
+    if (t->limit > 0xFFFFFFFFull) return fail(KG_ERR_UNSUPPORTED, "KG_F_PROGRESS: table streams of 2^32 records or more");
+    if ((rc = cx.sc.get(&cx.d_prog, 1))) return rc;
+    kg::Progress h;
+    for (auto &x : h.first) x = ~0ull;
+    h.last_plus1 = 0; h.first_beyond = ~0ull; h.walk_ran_off = 0;
+    for (auto &x : h.found_upto) x = 0;
+    h.kmers_found = 0;
+    for (auto &x : h.miss_max1) x = 0;
+    const double n = (double)t->num_sigs;
+    auto tenth = [&](uint64_t s) { return (int)(10.0 * ((double)(s + 1) / n)); };
+    for (int f = 0; f <= 10; f++) {
+        const unsigned __int128 num = (unsigned __int128)(uint64_t)t->num_sigs * (unsigned)f;
+        uint64_t s = (uint64_t)((num + 9) / 10);
+        s = s > 3 ? s - 3 : 0;
+        while (tenth(s) < f) s++;
+        h.lo[f] = s;
+    }
+    HIP_TRY(hipMemcpyAsync(cx.d_prog, &h, sizeof h, hipMemcpyHostToDevice, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));                             // (h is a stack object)
+    return KG_OK;
+}
+
+// ... behind the scan: index_walks = the byte home index pass noted the certain misses' walks (all chunks are behind us:
+// stream2 and stream3 were joined)
+int progress_finish(ScanCtx &cx, bool index_walks)
+{
+    kg_table *t = cx.t;
+    int rc;
+    if (index_walks)
+        hipLaunchKernelGGL(kg::progress_finish_kernel, dim3(1), dim3(256), 0, t->stream, cx.d_prog, t->d_tags, t->limit);
+    // kmersFound / found-so-far: the distinct slots of the hit records (a bitmap over the stream's slots)
+    uint32_t *d_bitmap = nullptr;
+    const uint64_t n_words = (t->limit + 31) / 32 + 1;
+    if ((rc = cx.sc.get(&d_bitmap, (size_t)n_words))) return rc;
+    HIP_TRY(hipMemsetAsync(d_bitmap, 0, n_words * 4, t->stream));
+    if (cx.n_hits)
+        hipLaunchKernelGGL(kg::mark_found_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (cx.n_hits + 255) / 256)), dim3(256), 0, t->stream,
+                           cx.res->d_hit_slots, cx.n_hits, d_bitmap);
+    hipLaunchKernelGGL(kg::count_found_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (n_words + 255) / 256)), dim3(256), 0, t->stream,
+                       d_bitmap, n_words, cx.d_prog);
+    return KG_OK;
+}
+
+// ... and once the stream is idle: the summary into the result
+int progress_fetch(ScanCtx &cx)
+{
+    kg::Progress h;
+    HIP_TRY(hipMemcpy(&h, cx.d_prog, sizeof h, hipMemcpyDeviceToHost));
+    kg_progress &g = cx.res->progress;
+    for (int f = 0; f <= 10; f++) g.first_visited[f] = h.first[f] == ~0ull ? -1 : (int64_t)h.first[f];
+    g.last_visited = (int64_t)h.last_plus1 - 1;
+    g.first_beyond = h.first_beyond == ~0ull ? -1 : (int64_t)h.first_beyond;
+    g.walk_ran_off = h.walk_ran_off ? 1 : 0;
+    g.stream_slots = (int64_t)cx.t->limit;
+    for (int f = 0; f <= 10; f++) g.found_upto[f] = g.first_visited[f] < 0 ? 0 : (int64_t)h.found_upto[f];
+    g.kmers_found = (int64_t)h.kmers_found;
+    cx.res->has_progress = true;
+    return KG_OK;
+}
+
+// Device blocks of the partitioned pipeline: every array holds n_chunks slices (ChunkView).
+struct PartBuffers {
+    uint64_t *d_ent = nullptr, *d_ovf_ent = nullptr;
+    uint32_t *d_fill = nullptr, *d_ovf_bucket = nullptr, *d_next = nullptr;
+    uint32_t *d_ovfc = nullptr;          // kOvfWords per chunk (kOvf*)
+    uint32_t *d_lowc = nullptr;          // block numbers set aside by the scatter pass
+    kg::RowGeo *d_geo = nullptr;         // per row: container and position of its first window (kg_order.hpp)
+    uint64_t *d_pc = nullptr;            // the kPc* words
+    uint32_t *d_ghist = nullptr, *d_gbase = nullptr, *d_gcur1 = nullptr, *d_gcur2 = nullptr, *d_gtile = nullptr;
+    // the lists, sized per attempt (BlockGuard): capacities per chunk
+    uint64_t ucap = 0, ccap = 0;
+    size_t cused_stride = 0, candused_stride = 0;
+    kg_hit *d_ulist = nullptr, *d_sortA = nullptr, *d_sortB = nullptr;
+    uint32_t *d_cused = nullptr, *d_candused = nullptr;
+    kg::CandRec *d_cand = nullptr;
+};
+
+// Chunk c's slices of them.
+struct ChunkView {
+    uint32_t c, lo, nb;                  // blocks [lo, lo + nb)
+    uint64_t *ent, *ovf_ent;
+    uint32_t *fill, *next, *ovfc, *ovf_bucket;
+    kg_hit *ulist, *sortA, *sortB;
+    uint32_t *cused, *candused;
+    kg::CandRec *cand;
+    unsigned long long *ucur, *ccur;
+    uint64_t *base, *ctot;
+    uint32_t *ghist, *gbase, *gcur1, *gcur2, *gtile;
+};
+
+ChunkView chunk_view(const PartPlan &pl, const PartBuffers &pb, uint32_t c)
+{
+    ChunkView v;
+    v.c = c; v.lo = (uint32_t)pl.clo[c]; v.nb = (uint32_t)(pl.clo[c + 1] - pl.clo[c]);
+    v.ent = pb.d_ent + (uint64_t)c * pl.n_regions * pl.cap;
+    v.fill = pb.d_fill + (uint64_t)c * pl.n_regions;
+    v.next = pb.d_next + (size_t)c * pl.next_stride;
+    v.ovfc = pb.d_ovfc + kOvfWords * c; v.ovf_bucket = pb.d_ovf_bucket + (size_t)c * pl.ovf_cap;
+    v.ovf_ent = pb.d_ovf_ent + (size_t)c * pl.ovf_cap * kg::kGroup;
+    v.ulist = pb.d_ulist + (uint64_t)c * pb.ucap;
+    v.cused = pb.d_cused + c * pb.cused_stride; v.candused = pb.d_candused + c * pb.candused_stride;
+    v.cand = pb.d_cand + (uint64_t)c * pb.ccap;
+    v.ucur = (unsigned long long *)(pb.d_pc + kPcUcur + c); v.ccur = (unsigned long long *)(pb.d_pc + kPcCcur + c);
+    v.base = pb.d_pc + kPcBase + c; v.ctot = pb.d_pc + kPcCtot + c;
+    v.ghist = pb.d_ghist + (size_t)c * pl.groups_stride; v.gbase = pb.d_gbase + (size_t)c * (pl.groups_stride + 1);
+    v.gcur1 = pb.d_gcur1 + (size_t)c * (kg::kHDigits + 1); v.gcur2 = pb.d_gcur2 + (size_t)c * pl.groups_stride;
+    v.gtile = pb.d_gtile + (size_t)c * (kg::kHDigits + 1);
+    v.sortA = pb.d_sortA + (uint64_t)c * pb.ucap; v.sortB = pb.d_sortB + (uint64_t)c * pb.ucap;
+    return v;
+}
+
+// One chunk through scatter (stream) -> low-complexity blocks, tag or index pass (stream2) -> verify, overflow (stream3).
+template <bool AA>
+int chunk_passes(const ScanCtx &cx, const PartPlan &pl, const PartBuffers &pb, const ChunkView &v)
+{
+    kg_table *t = cx.t;
+    kg::Progress *d_prog = cx.d_prog;
+    unsigned long long *d_ctr = (unsigned long long *)(cx.d_totals + kTotValid);
+    const hipStream_t s2 = t->stream2, s3 = t->stream3;
+    uint32_t *lowc_cursor = v.ovfc + kOvfLowc, *lowc = pb.d_lowc + v.lo;
+    hipLaunchKernelGGL((kg::part_scatter_kernel<AA>), dim3(pl.n_wg), dim3(kg::kWave * kg::kScatterWaves), pl.scatter_lds, t->stream, cx.d_seq,
+                       cx.d_blocks, v.lo, v.nb, t->limit, (uint32_t)t->num_sigs, t->m35, pl.shift, pl.buckets,
+                       pl.cap, v.ent, v.fill, v.ovfc, pl.ovf_cap, v.ovf_bucket, v.ovf_ent, lowc_cursor, lowc, d_ctr, d_prog, pl.scatter_prio);
+    HIP_TRY(hipEventRecord(t->pev[kPevChunk + 2 * v.c], t->stream));
+    HIP_TRY(hipStreamWaitEvent(s2, t->pev[kPevChunk + 2 * v.c], 0));
+    // the low-complexity blocks the scatter pass set aside (usually none: every workgroup reads the count and
+    // leaves).  In front of the chunk's tag pass, not behind its scatter pass, and in one-wave workgroups whose
+    // 4.9 KB of LDS fit beside a resident scatter workgroup (153 KB of a CU's 160): with four-wave workgroups
+    // (15.8 KB) the kernel -- and the tag pass behind it -- waited for the NEXT chunk's scatter pass to leave
+    // the CUs (profiles/r02_pipeline.md).
+    hipLaunchKernelGGL((kg::lowc_blocks_kernel<AA>), dim3(pl.lowc_grid), dim3(64 * kg::kLowcWaves), 0, s2, cx.d_seq, cx.d_blocks, lowc_cursor, lowc,
+                       t->limit, (uint32_t)t->num_sigs, t->m35, pl.shift, pl.n_wg, pl.cap, v.ent, v.fill, v.ovfc, pl.ovf_cap,
+                       v.ovf_bucket, v.ovf_ent, d_ctr, d_prog);
+    if (pl.use_bidx) {
+        // regions per hand-out by their expected fill (an iteration covers 256 * N / R entry slots of each); the
+        // kernel for tables whose classes are their quotients has no q % 19
+        const uint32_t tail_start = (uint32_t)std::min<uint64_t>(t->tail_start, 0xFFFFFFFFull);
+        dispatch<int, 1, 2, 4>((int)pl.index_r, [&](auto r) {
+            dispatch<bool, true, false>(t->bidx_exact, [&](auto exact) {
+                dispatch<bool, true, false>(pl.prog_index, [&](auto prog) {
+                    constexpr int R = decltype(r)::value;
+                    constexpr bool EXACT = decltype(exact)::value, PROG = decltype(prog)::value;
+                    hipLaunchKernelGGL((kg::bucket_index_kernel<kg::kIndexN, R, EXACT, PROG>), dim3(pl.index_grid), dim3(256), 0, s2,
+                                       t->d_bidx, tail_start, v.ent, v.fill, pl.n_wg, pl.cap, pl.buckets, pl.shift, pl.probe_grab, v.next,
+                                       v.cand, v.candused, v.ccur, pb.ccap, d_ctr, pl.index_prio, PROG ? d_prog : (kg::Progress *)nullptr);
+                });
+            });
+        });
+    } else {
+        dispatch<bool, true, false>(pl.part_counters, [&](auto counters) {
+            constexpr bool COUNTERS = decltype(counters)::value;
+            hipLaunchKernelGGL((kg::bucket_tag_kernel<COUNTERS>), dim3(pl.probe_grid), dim3(256), 0, s2, t->d_tags, t->limit,
+                               (uint64_t)t->num_sigs, v.ent, v.fill, pl.n_wg, pl.cap, pl.buckets, pl.shift, pl.probe_grab, v.next, v.cand,
+                               v.candused, v.ccur, pb.ccap, d_ctr, COUNTERS ? d_prog : (kg::Progress *)nullptr);
+        });
+    }
+    HIP_TRY(hipEventRecord(t->pev[kPevChunk + 2 * v.c + 1], s2));
+    HIP_TRY(hipStreamWaitEvent(s3, t->pev[kPevChunk + 2 * v.c + 1], 0));
+    // the walks: counted (0: no, 1: yes), or summarised for KG_F_PROGRESS without counting (2)
+    dispatch<int, 1, 2, 0>(pl.part_counters ? 1 : pl.prog_index ? 2 : 0, [&](auto walks) {
+        constexpr bool COUNTERS = decltype(walks)::value == 1, PROG = decltype(walks)::value == 2;
+        hipLaunchKernelGGL((kg::verify_kernel<AA, COUNTERS, PROG>), dim3(pl.verify_grid), dim3(256), 0, s3, t->d_entries, t->d_tags, t->limit,
+                           (uint64_t)t->num_sigs, t->magic, v.cand, v.candused, v.ccur, pb.ccap, v.ulist, v.cused, v.ucur, pb.ucap, d_ctr,
+                           d_prog, pl.verify_prio);
+        hipLaunchKernelGGL((kg::overflow_probe_kernel<AA, COUNTERS, PROG>), dim3(pl.ovf_grid), dim3(256), 0, s3, t->d_entries, t->d_tags,
+                           t->limit, (uint64_t)t->num_sigs, t->magic, v.ovf_bucket, v.ovf_ent, v.ovfc, pl.ovf_cap, pl.shift, v.ulist,
+                           v.cused, v.ucur, pb.ucap, d_ctr, d_prog);
+    });
+    HIP_TRY(hipEventRecord(t->pev[kPevVerified + v.c], s3));
+    HIP_TRY(hipGetLastError());
+    return KG_OK;
+}
+
+// One chunk's ordered placement (kg_order.hpp) behind its verify pass, on the scatter stream or an ordering stream: group histogram -> group starts -> two partition
+// passes by key range -> ranking inside each group of rows.  hits_cap: records res->d_hits has room for.
+template <bool AA>
+int chunk_order(const ScanCtx &cx, const PartPlan &pl, const PartBuffers &pb, const ChunkView &v, uint64_t hits_cap)
+{
+    constexpr uint32_t PER = AA ? 1 : 6;
+    kg_table *t = cx.t;
+    kg_result *res = cx.res;
+    const uint32_t c = v.c, gshift = pl.gshift;
+    const bool last = c + 1 == pl.n_chunks;
+    hipStream_t s = t->stream;           // (behind every scatter pass as it is)
+    if (pl.n_os) {
+        s = t->ostream[c % pl.n_os];
+        HIP_TRY(hipStreamWaitEvent(s, t->ev[kEvScattered], 0));          // behind the last scatter pass
+    }
+    HIP_TRY(hipStreamWaitEvent(s, t->pev[kPevVerified + c], 0));
+    const uint64_t row_lo = (uint64_t)v.lo * PER, row_hi = row_lo + (uint64_t)v.nb * PER;
+    const uint32_t g0 = (uint32_t)(row_lo >> gshift);
+    const uint32_t n_groups = v.nb ? (uint32_t)(((row_hi - 1) >> gshift) - g0 + 1) : 1u;
+    hipLaunchKernelGGL(kg::hit_hist_kernel, dim3(pl.order_grid), dim3(kg::kHThreads), (size_t)n_groups * 4, s, v.ulist, v.cused, v.ucur, pb.ucap,
+                       g0, 6u + gshift, n_groups, v.ghist);
+    hipLaunchKernelGGL(kg::group_scan_kernel, dim3(1), dim3(kg::kGsThreads), 0, s, v.ghist, n_groups, v.gbase, v.gcur1, v.gcur2, v.ctot, v.gtile);
+    if (pl.n_os && c) HIP_TRY(hipStreamWaitEvent(s, t->pev[kPevBase + c - 1], 0));      // base of chunk c = base + total of c - 1
+    hipLaunchKernelGGL(kg::chunk_base_kernel, dim3(1), dim3(1), 0, s, v.ctot, v.base, last ? cx.d_totals : (uint64_t *)nullptr);
+    if (pl.n_os) HIP_TRY(hipEventRecord(t->pev[kPevBase + c], s));
+    if (pl.early_totals && last) {
+        // Everything the host wants to know about this attempt is final here -- the list cursors (the last verify
+        // pass is behind us on this stream), the overflow counters, the exact hit total (chunk_base_kernel just
+        // above): it is sent now, and the host reads it, makes the aggregation's allocations and enqueues its
+        // kernels while the last chunk's partition passes and placement still run (the round trip was ~70 us
+        // of every scan, behind the ordering).
+        int rc;
+        if ((rc = send_counters(t, pb.d_pc, pb.d_ovfc, cx.d_totals, s))) return rc;
+        HIP_TRY(hipEventRecord(t->pev[kPevTotals], s));
+    }
+    hipLaunchKernelGGL((kg::hit_partition_kernel<true>), dim3(pl.order_grid), dim3(kg::kHThreads), 0, s, v.ulist, v.cused, v.ucur, pb.ucap,
+                       v.gbase, n_groups, g0, 6u + gshift, v.gcur1, v.sortA, pb.ucap, v.gtile);
+    hipLaunchKernelGGL((kg::hit_partition_kernel<false>), dim3(pl.order_grid), dim3(kg::kHThreads), 0, s, v.sortA, v.cused, v.ucur, pb.ucap,
+                       v.gbase, n_groups, g0, 6u + gshift, v.gcur2, v.sortB, pb.ucap, v.gtile);
+    hipLaunchKernelGGL((kg::group_place_kernel<AA>), dim3(std::min(n_groups, 256u * 8u)), dim3(kg::kHThreads),
+                       kg::group_place_lds(gshift, pl.place_staged), s,
+                       v.sortB, v.gbase, n_groups, g0, gshift, (uint32_t)row_lo, (uint32_t)row_hi, pb.d_geo, (uint64_t)cx.b.n_rows,
+                       pl.place_staged ? 1u : 0u, v.base, res->d_hits, hits_cap, cx.d_offs, res->d_hit_slots);
+    HIP_TRY(hipGetLastError());
+    return KG_OK;
+}
+
+// The blocks of the partitioned pipeline that do not depend on the attempt, and the dynamic LDS its kernels may ask for.
+template <bool AA>
+int part_allocate(ScanCtx &cx, const PartPlan &pl, PartBuffers &pb)
+{
+    kg_table *t = cx.t;
+    Scratch &sc = cx.sc;
+    const uint32_t n_chunks = pl.n_chunks, groups_stride = pl.groups_stride;
+    int rc;
+    if ((rc = sc.get(&pb.d_ent, (size_t)(pl.n_regions * pl.cap * n_chunks)))) return rc;
+    if ((rc = sc.get(&pb.d_fill, (size_t)pl.n_regions * n_chunks))) return rc;
+    if ((rc = sc.get(&pb.d_ovf_ent, (size_t)pl.ovf_cap * kg::kGroup * n_chunks))) return rc;
+    if ((rc = sc.get(&pb.d_ovf_bucket, (size_t)pl.ovf_cap * n_chunks))) return rc;
+    if ((rc = sc.get(&pb.d_next, pl.next_stride * n_chunks))) return rc;
+    if ((rc = sc.get(&pb.d_ovfc, kOvfWords * kMaxChunks))) return rc;
+    if ((rc = sc.get(&pb.d_lowc, (size_t)cx.b.nblocks + 1))) return rc;
+    if ((rc = sc.get(&pb.d_geo, (size_t)cx.b.n_rows))) return rc;
+    if ((rc = sc.get(&pb.d_ghist, (size_t)groups_stride * n_chunks))) return rc;
+    if ((rc = sc.get(&pb.d_gbase, (size_t)(groups_stride + 1) * n_chunks))) return rc;
+    if ((rc = sc.get(&pb.d_gcur1, (size_t)(kg::kHDigits + 1) * n_chunks))) return rc;
+    if ((rc = sc.get(&pb.d_gcur2, (size_t)groups_stride * n_chunks))) return rc;
+    if ((rc = sc.get(&pb.d_gtile, (size_t)(kg::kHDigits + 1) * n_chunks))) return rc;
+    if (kg::group_place_lds(pl.gshift, pl.gshift == 10) > t->place_lds[AA ? 1 : 0]) {
+        const size_t want_lds = kg::group_place_lds(pl.gshift, pl.gshift == 10);
+        HIP_TRY(hipFuncSetAttribute((const void *)kg::group_place_kernel<AA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want_lds));
+        t->place_lds[AA ? 1 : 0] = want_lds;
+    }
+    if (groups_stride * 4u > t->hist_lds) {
+        HIP_TRY(hipFuncSetAttribute((const void *)kg::hit_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(groups_stride * 4u)));
+        t->hist_lds = groups_stride * 4u;
+    }
+    if ((rc = sc.get(&pb.d_pc, kPcWords))) return rc;
+    if (t->scatter_lds[AA ? 1 : 0] < pl.scatter_lds) {         // once per table (and geometry): the call costs tens of microseconds
+        HIP_TRY(hipFuncSetAttribute((const void *)kg::part_scatter_kernel<AA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.scatter_lds));
+        t->scatter_lds[AA ? 1 : 0] = pl.scatter_lds;
+    }
+    return KG_OK;
+}
+
+// The partitioned strategy.  done = true: the hit records are placed (res->d_hits, cx.n_hits).  done = false with KG_OK: the
+// batch is too skewed for the provisioned lists (st.fallback says how) and goes to the direct strategy.
+template <bool AA>
+int scan_partitioned(ScanCtx &cx, const PartPlan &pl, bool &done)
+{
+    constexpr uint32_t PER = AA ? 1 : 6;
+    kg_table *t = cx.t;
+    kg_result *res = cx.res;
+    kg_stats &st = res->st;
+    const uint32_t n_chunks = pl.n_chunks;
+    const uint64_t nblocks = cx.b.nblocks;
+    int rc;
+    PartBuffers pb;
+    if ((rc = part_allocate<AA>(cx, pl, pb))) return rc;
+    BlockGuard<6> lists{cx.sc, {(void **)&pb.d_ulist, (void **)&pb.d_cused, (void **)&pb.d_cand, (void **)&pb.d_candused,
+                                (void **)&pb.d_sortA, (void **)&pb.d_sortB}};
+    pb.ucap = pl.ucap; pb.ccap = pl.ccap;
+    HIP_TRY(hipEventRecord(t->ev[kEvScanBegin], t->stream));
+    for (int attempt = 0; attempt < 3; attempt++) {
+        const uint64_t ucap = pb.ucap, ccap = pb.ccap;
+        const uint64_t hits_cap = ucap * n_chunks;
+        pb.cused_stride = (size_t)(ucap / kg::kUChunk + 1); pb.candused_stride = (size_t)(ccap / kg::kUChunk + 1);
+        if ((rc = dalloc(t, (void **)&res->d_hits, hits_cap * sizeof(kg_hit)))) return rc;
+        if (cx.progress && (rc = dalloc(t, (void **)&res->d_hit_slots, hits_cap * 4))) return rc;
+        if ((rc = dalloc(t, (void **)&pb.d_ulist, ucap * n_chunks * sizeof(kg_hit)))) return rc;
+        if ((rc = dalloc(t, (void **)&pb.d_cused, pb.cused_stride * n_chunks * 4))) return rc;
+        if ((rc = dalloc(t, (void **)&pb.d_cand, ccap * n_chunks * sizeof(kg::CandRec)))) return rc;
+        if ((rc = dalloc(t, (void **)&pb.d_candused, pb.candused_stride * n_chunks * 4))) return rc;
+        if ((rc = dalloc(t, (void **)&pb.d_sortA, ucap * n_chunks * sizeof(kg_hit)))) return rc;
+        if ((rc = dalloc(t, (void **)&pb.d_sortB, ucap * n_chunks * sizeof(kg_hit)))) return rc;
+        {   // one launch for all clears (d_totals: totals, counters and flags of a re-run start over)
+            kg::ClearList cl;
+            cl.n = 7;
+            cl.p[0] = pb.d_cused; cl.words[0] = (uint64_t)pb.cused_stride * n_chunks;
+            cl.p[1] = pb.d_candused; cl.words[1] = (uint64_t)pb.candused_stride * n_chunks;
+            cl.p[2] = reinterpret_cast<uint32_t *>(pb.d_pc); cl.words[2] = kPcWords * 2;
+            cl.p[3] = reinterpret_cast<uint32_t *>(cx.d_totals); cl.words[3] = kTotWords * 2;
+            cl.p[4] = pb.d_ovfc; cl.words[4] = kOvfWords * kMaxChunks;
+            cl.p[5] = pb.d_next; cl.words[5] = (uint64_t)pl.next_stride * n_chunks;
+            cl.p[6] = pb.d_ghist; cl.words[6] = (uint64_t)pl.groups_stride * n_chunks;
+            cl.p[7] = nullptr; cl.words[7] = 0;
+            uint64_t most = 1;                                      // the grid follows the LARGEST list (the kernel strides)
+            for (int k = 0; k < cl.n; k++) most = std::max(most, cl.words[k]);
+            most /= 4;
+            hipLaunchKernelGGL(kg::clear_many_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (most + 255) / 256 + 1)), dim3(256), 0,
+                               t->stream, cl);
+        }
+        HIP_TRY(hipEventRecord(t->pev[kPevFork], t->stream));               // fork: stream2 starts behind the clears
+        HIP_TRY(hipStreamWaitEvent(t->stream2, t->pev[kPevFork], 0));
+        HIP_TRY(hipStreamWaitEvent(t->stream3, t->pev[kPevFork], 0));
+        // the rows' geometry records (kg_order.hpp): they depend on the batch only, and the verify stream has nothing to do
+        // until the first chunk is scattered and probed
+        hipLaunchKernelGGL((kg::row_geo_kernel<AA>), dim3((uint32_t)((nblocks * PER + 255) / 256)), dim3(256), 0, t->stream3, cx.d_blocks,
+                           (uint32_t)nblocks, pb.d_geo);
+        for (uint32_t c = 0; c < n_chunks; c++) {
+            // (the upload of chunk c+1 runs while chunk c is scanned)
+            if (!cx.seq_uploaded && (rc = upload_seq(cx, cx.offsets[pl.cseq[c]], cx.offsets[pl.cseq[c + 1]]))) return rc;
+            if ((rc = chunk_passes<AA>(cx, pl, pb, chunk_view(pl, pb, c)))) return rc;
+        }
+        HIP_TRY(hipEventRecord(t->ev[kEvScattered], t->stream));   // all chunks scattered
+        cx.seq_uploaded = true;
+        // Ordered placement (kg_order.hpp), chunk by chunk, behind the LAST scatter pass and beside the tag passes that are
+        // still running: its partition workgroups hold 51 KB of LDS and eight wave slots each, and started beside a scatter
+        // pass (105 KB and 16 wave slots of every CU) the two starve each other -- chunk 0's two partition passes took
+        // 2.2 + 4.3 ms instead of 0.15 + 0.55 and the scatter pass beside them 7.8 ms instead of 2 (profiles/r03_ordering.md).
+        // Beside a tag pass the ordering kernels crawl (a partition pass 1.7-3.9 ms instead of 0.13: every memory access
+        // queues behind the tag pass's line gathers) while the tag pass hardly notices them.  KG_ORDER_STREAMS=n (1..4; not
+        // the default) gives the chunks' orderings n streams of their own, of the LOWEST priority because that gives them
+        // hardware queues of their own (a fourth stream of normal priority shares a queue with the third): the orderings
+        // of chunks 0-2 then all crawl beside the last tag passes, single scans 20.1-20.25 ms against 20.4, but twenty
+        // scans back to back (bench.py) 21.45 against 21.23 ms per step (profiles/r03_experiments.md).
+        for (uint32_t k = 0; k < pl.n_os; k++)
+            if (!t->ostream[k]) {
+                int pr_least = 0, pr_greatest = 0;
+                HIP_TRY(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
+                HIP_TRY(hipStreamCreateWithPriority(&t->ostream[k], hipStreamNonBlocking, pr_least));
+            }
+        for (uint32_t c = 0; c < n_chunks; c++)
+            if ((rc = chunk_order<AA>(cx, pl, pb, chunk_view(pl, pb, c), hits_cap))) return rc;
+
+        for (uint32_t k = 0; k < pl.n_os; k++) {
+            HIP_TRY(hipEventRecord(t->pev[kPevOrdered + k], t->ostream[k]));
+            HIP_TRY(hipStreamWaitEvent(t->stream, t->pev[kPevOrdered + k], 0));
+        }
+        HIP_TRY(hipEventRecord(t->pev[kPevJoin2], t->stream2));              // join
+        HIP_TRY(hipStreamWaitEvent(t->stream, t->pev[kPevJoin2], 0));
+        HIP_TRY(hipEventRecord(t->pev[kPevJoin3], t->stream3));
+        HIP_TRY(hipStreamWaitEvent(t->stream, t->pev[kPevJoin3], 0));
+        HIP_TRY(hipEventRecord(t->ev[kEvJoined], t->stream));
+        st.scan_launches++;
+        HIP_TRY(hipEventRecord(t->ev[kEvScanEnd], t->stream));                 // end of the scan stage (of this attempt)
+        if (pl.early_totals) {
+            HIP_TRY(hipEventSynchronize(t->pev[kPevTotals]));                 // (the ordering of the last chunk may still be running)
+        } else {
+            if ((rc = send_counters(t, pb.d_pc, pb.d_ovfc, cx.d_totals, t->stream))) return rc;
+            HIP_TRY(hipStreamSynchronize(t->stream));
+        }
+        const uint64_t *h_pc = t->h_pin + kPinPc;
+        const uint32_t *h_ovf = reinterpret_cast<const uint32_t *>(t->h_pin + kPinOvf);
+        uint64_t need_u = 0, need_c = 0;
+        uint32_t max_ovf = 0, guard = 0;
+        for (uint32_t c = 0; c < n_chunks; c++) {
+            need_u = std::max(need_u, h_pc[kPcUcur + c]); need_c = std::max(need_c, h_pc[kPcCcur + c]);
+            max_ovf = std::max(max_ovf, h_ovf[kOvfWords * c + kOvfGroups]);
+            guard |= h_ovf[kOvfWords * c + kOvfGuard];
+        }
+        const uint64_t n_hits = h_pc[kPcBase + n_chunks];
+        if (pl.debug)
+            fprintf(stderr, "[kg] partition attempt %d: %u chunks (largest %llu of %llu blocks), overflow groups <= %u (cap %u), hit list <= %llu "
+                            "(cap %llu), candidates <= %llu (cap %llu), regions/chunk %llu x %u entries, %u buckets, shift %u, %u scatter "
+                            "workgroups, hits %llu, %s\n",
+                    attempt, n_chunks, (unsigned long long)pl.max_chunk, (unsigned long long)nblocks, max_ovf, pl.ovf_cap,
+                    (unsigned long long)need_u, (unsigned long long)ucap, (unsigned long long)need_c, (unsigned long long)ccap,
+                    (unsigned long long)pl.n_regions, pl.cap, pl.buckets, pl.shift, pl.n_wg, (unsigned long long)n_hits, pl.use_bidx ? "byte home index" : "tags");
+        const bool redo = guard || max_ovf > pl.ovf_cap || need_u > ucap || need_c > ccap;
+        if (redo && pl.early_totals) HIP_TRY(hipStreamSynchronize(t->stream));   // the attempt is thrown away: its last kernels first
+        if (guard || max_ovf > pl.ovf_cap) {
+            // the scatter pass's spin guard fired (2), or more overflow than provisioned (1): direct path
+            st.fallback = guard ? 2 : 1;
+            lists.release();
+            drop_hits(t, res);
+            return KG_OK;
+        }
+        if (!redo) {
+            note_totals(cx, n_hits, pl.part_counters);
+            st.partitioned = 1;
+            st.part_chunks = (int32_t)n_chunks; st.part_buckets = (int32_t)pl.buckets; st.part_shift = (int32_t)pl.shift;
+            st.part_levels = pl.use_bidx ? 4 : 1;
+            done = true;
+            return KG_OK;
+        }
+        // a list was too small: now the exact need is known (masks are cleared and everything is redone; all streams are
+        // idle, and the ordering buffers are sized by ucap as well)
+        lists.release();
+        drop_hits(t, res);
+        if (attempt == 2) break;
+        // which wave fills which reservation chunk differs from run to run: one partly used chunk per wave on top
+        if (need_c > ccap) { pb.ccap = (need_c + pl.list_slack + kg::kUChunk - 1) / kg::kUChunk * kg::kUChunk; pb.ucap = std::max(ucap, pb.ccap); }   // hits <= candidates
+        else pb.ucap = (need_u + pl.list_slack + kg::kUChunk - 1) / kg::kUChunk * kg::kUChunk;
+    }
+    return fail(KG_ERR_DEVICE, "hit list overflow after resize (internal error)");
+}
+
+// The direct strategy: encode + probe + staged compaction, then ordered placement; re-run once if the staging area was too small.
+template <bool AA>
+int scan_direct(ScanCtx &cx, const DirectPlan &pl)
+{
+    kg_table *t = cx.t;
+    kg_result *res = cx.res;
+    kg_stats &st = res->st;
+    const uint64_t nblocks = cx.b.nblocks, n_rows = cx.b.n_rows;
+    int rc;
+    st.scan_launches = 0;
+    // (the whole batch, when the partitioned strategy did not run or fell back before uploading everything)
+    if (!cx.seq_uploaded) { if ((rc = upload_seq(cx, cx.offsets[0], cx.offsets[cx.n_seqs]))) return rc; cx.seq_uploaded = true; }
+    uint64_t stage_cap = pl.stage_cap;
+    kg_hit *d_stage = nullptr;
+    uint32_t *d_stage_slot = nullptr;                                        // KG_F_PROGRESS: the found slots, parallel to d_stage
+    BlockGuard<2> stage{cx.sc, {(void **)&d_stage, (void **)&d_stage_slot}};
+    unsigned long long *d_cursor = (unsigned long long *)(cx.d_totals + kTotCursor);
+    unsigned long long *d_ctr = (unsigned long long *)(cx.d_totals + kTotValid);
+    for (int attempt = 0;; attempt++) {
+        if ((rc = dalloc(t, (void **)&d_stage, stage_cap * sizeof(kg_hit)))) return rc;
+        if (cx.progress && (rc = dalloc(t, (void **)&d_stage_slot, stage_cap * 4))) return rc;
+        HIP_TRY(hipMemsetAsync(cx.d_totals, 0, kTotWords * 8, t->stream));
+        HIP_TRY(hipEventRecord(t->ev[kEvScanBegin], t->stream));
+        if (nblocks) {
+            const uint64_t wgs = (nblocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG;
+            const uint32_t grid = (uint32_t)(wgs < pl.scan_grid ? wgs : pl.scan_grid);      // persistent waves stride over the blocks
+            dispatch<bool, true, false>(cx.counters, [&](auto counters) {
+                dispatch<int, 1, 2, 3, 6>((int)pl.rpg, [&](auto rpg) {
+                    constexpr bool COUNTERS = decltype(counters)::value;
+                    constexpr int RPG = AA ? 1 : decltype(rpg)::value;           // (a protein block has one row)
+                    hipLaunchKernelGGL((kg::scan_kernel<AA, COUNTERS, RPG>), dim3(grid), dim3(kg::kWave * kg::kWavesPerWG), 0, t->stream,
+                                       t->d_entries, t->d_tags, t->limit, (uint64_t)t->num_sigs, t->magic, t->m35, cx.d_seq, cx.d_blocks,
+                                       (uint32_t)nblocks, cx.d_counts, cx.d_bsb, d_stage, d_cursor, stage_cap, pl.stage_chunk, d_ctr, cx.d_prog,
+                                       d_stage_slot, pl.d_hbits, t->tail_start);
+                });
+            });
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(t->ev[kEvScanEnd], t->stream));
+        st.scan_launches++;
+        if ((rc = prefix_sum(t, cx.d_counts, n_rows, cx.d_offs, cx.d_partial, cx.d_totals + kTotHits))) return rc;
+        if ((rc = send_counters(t, nullptr, nullptr, cx.d_totals, t->stream))) return rc;
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        const uint64_t need = t->h_pin[kPinTotals + kTotCursor];
+        if (need <= stage_cap) break;
+        // staging overflow: now the exact need is known
+        stage.release();
+        if (attempt == 1) return fail(KG_ERR_DEVICE, "staging overflow after resize (internal error)");
+        stage_cap = need;
+    }
+    const uint64_t n_hits = n_rows ? t->h_pin[kPinTotals + kTotHits] : 0;
+    note_totals(cx, n_hits, cx.counters);
 
     // ---- ordered placement ----
     if ((rc = dalloc(t, (void **)&res->d_hits, n_hits * sizeof(kg_hit)))) return rc;
-    if (progress && (rc = dalloc(t, (void **)&res->d_hit_slots, (n_hits ? n_hits : 1) * 4))) return rc;
+    if (cx.progress && (rc = dalloc(t, (void **)&res->d_hit_slots, (n_hits ? n_hits : 1) * 4))) return rc;
     if (nblocks) {
-        uint32_t grid = (uint32_t)((nblocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG);
-        hipLaunchKernelGGL((kg::place_kernel<AA>), dim3(grid), dim3(kg::kWave * kg::kWavesPerWG), 0, t->stream, d_blocks,
-                           (uint32_t)nblocks, d_counts, d_offs, d_bsb, rpg, d_stage, res->d_hits, d_stage_slot, res->d_hit_slots);
+        const uint32_t grid = (uint32_t)((nblocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG);
+        hipLaunchKernelGGL((kg::place_kernel<AA>), dim3(grid), dim3(kg::kWave * kg::kWavesPerWG), 0, t->stream, cx.d_blocks,
+                           (uint32_t)nblocks, cx.d_counts, cx.d_offs, cx.d_bsb, pl.rpg, d_stage, res->d_hits, d_stage_slot, res->d_hit_slots);
     }
+    return KG_OK;
+}
+
+// One batch: plan, the shared buffers, one of the two strategies, then container starts, aggregation and the timings.
+template <bool AA>
+int scan_impl(kg_table *t, const kg_params *p, const uint8_t *d_seq, const uint8_t *h_seq /* host copy still to upload, or null */,
+              const int64_t *offsets, int64_t n_seqs, kg_result *res)
+{
+    constexpr uint32_t PER = AA ? 1 : 6;
+    const bool progress = (p->flags & KG_F_PROGRESS) != 0;
+    const bool counters_req = (p->flags & KG_F_COUNTERS) != 0;
+    const bool aggregate = !(p->flags & KG_F_SKIP_AGGREGATE);
+    kg_stats &st = res->st;
+    res->per = PER;
+    int rc;
+
+    BatchPlan b;
+    if ((rc = plan_batch<AA>(offsets, n_seqs, b))) return rc;
+    const uint64_t nblocks = b.nblocks, n_rows = b.n_rows, n_cont = b.n_cont;
+    st.n_seqs = n_seqs; st.n_containers = (int64_t)n_cont; st.n_blocks = (int64_t)nblocks;
+    st.residues = (int64_t)b.residues; st.windows = (int64_t)b.windows;
+    st.table_bytes = t->num_sigs * (int64_t)KG_TABLE_ENTRY_SIZE;
+
+    // ---- the buffers both strategies use, the offsets, the window blocks ----
+    Scratch sc(t);
+    // the walks are noted by the counting kernels -- except on the partitioned path's byte home index (PartPlan::prog_index)
+    ScanCtx cx{t, res, sc, b, d_seq, h_seq, offsets, n_seqs, progress, counters_req || progress, h_seq == nullptr};
+    if ((rc = sc.get(&cx.d_off, (size_t)n_seqs + 1))) return rc;
+    if ((rc = sc.get(&cx.d_ibase, (size_t)n_seqs + 1))) return rc;
+    HIP_TRY(hipMemcpyAsync(cx.d_off, offsets, ((size_t)n_seqs + 1) * 8, hipMemcpyHostToDevice, t->stream));
+    HIP_TRY(hipMemcpyAsync(cx.d_ibase, b.ibase.data(), ((size_t)n_seqs + 1) * 4, hipMemcpyHostToDevice, t->stream));
+    if ((rc = sc.get(&cx.d_blocks, nblocks))) return rc;
+    if ((rc = sc.get(&cx.d_counts, n_rows))) return rc;
+    if ((rc = sc.get(&cx.d_offs, n_rows))) return rc;
+    if ((rc = sc.get(&cx.d_bsb, nblocks * 6))) return rc;      // one staging base per (block, row group)
+    if ((rc = sc.get(&cx.d_partial, (size_t)(std::max(n_rows, n_cont) / kg::kScanChunk + 2)))) return rc;
+    if ((rc = sc.get(&cx.d_totals, kTotWords))) return rc;
+    HIP_TRY(hipMemsetAsync(cx.d_totals, 0, kTotWords * 8, t->stream));
+    if ((rc = dalloc(t, (void **)&res->d_chs, (n_cont + 1) * 8))) return rc;
+    if (progress && (rc = progress_begin(cx))) return rc;
+    HIP_TRY(hipEventRecord(t->ev[kEvBegin], t->stream));
+    if (nblocks) {
+        hipLaunchKernelGGL(kg::build_blocks_kernel, dim3((uint32_t)((nblocks + 255) / 256)), dim3(256), 0, t->stream,
+                           cx.d_off, cx.d_ibase, (uint32_t)n_seqs, (uint32_t)nblocks, cx.d_blocks);
+        HIP_TRY(hipGetLastError());
     }
-    if (progress) {
-        // the certain misses' walks of the byte home index pass (all chunks are behind us: stream2 and stream3 were joined)
-        if (part_done && prog_index)
-            hipLaunchKernelGGL(kg::progress_finish_kernel, dim3(1), dim3(256), 0, t->stream, d_prog, t->d_tags, t->limit);
-        // kmersFound / found-so-far: the distinct slots of the hit records (a bitmap over the stream's slots)
-        uint32_t *d_bitmap = nullptr;
-        const uint64_t n_words = (t->limit + 31) / 32 + 1;
-        if ((rc = sc.get(&d_bitmap, (size_t)n_words))) return rc;
-        HIP_TRY(hipMemsetAsync(d_bitmap, 0, n_words * 4, t->stream));
-        if (n_hits)
-            hipLaunchKernelGGL(kg::mark_found_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (n_hits + 255) / 256)), dim3(256), 0, t->stream,
-                               res->d_hit_slots, n_hits, d_bitmap);
-        hipLaunchKernelGGL(kg::count_found_kernel, dim3((uint32_t)std::min<uint64_t>(2048, (n_words + 255) / 256)), dim3(256), 0, t->stream,
-                           d_bitmap, n_words, d_prog);
-    }
+
+    // ---- strategy: partitioned probing where it applies and pays, else (or when the batch turns out too skewed) direct ----
+    st.scan_launches = 0;
+    PartPlan part;
+    if ((rc = plan_partition<AA>(t, b, progress, counters_req, part))) return rc;
+    bool part_done = false;
+    if (part.applicable && (rc = scan_partitioned<AA>(cx, part, part_done))) return rc;
+    if (!part_done && (rc = scan_direct<AA>(cx, plan_direct<AA>(t, b, cx.counters)))) return rc;
+
+    if (progress && (rc = progress_finish(cx, part_done && part.prog_index))) return rc;
     hipLaunchKernelGGL((kg::container_starts_kernel<AA>), dim3((uint32_t)((n_cont + 1 + 255) / 256)), dim3(256), 0, t->stream,
-                       d_ibase, (uint32_t)n_seqs, d_offs, n_rows, d_totals, res->d_chs);
+                       cx.d_ibase, (uint32_t)n_seqs, cx.d_offs, n_rows, cx.d_totals, res->d_chs);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t->ev[3], t->stream));
+    HIP_TRY(hipEventRecord(t->ev[kEvOrderEnd], t->stream));
 
     // ---- aggregation: CALL records and OTU votes ----
-    const bool aggregate = !(p->flags & KG_F_SKIP_AGGREGATE);
-    if (aggregate && (rc = aggregate_stage(t, p, res, sc, n_seqs, n_cont, n_hits, PER, d_partial, d_totals, nullptr, longest < (1ll << 30))))
+    if (aggregate && (rc = aggregate_stage(t, p, res, sc, n_seqs, n_cont, cx.n_hits, PER, cx.d_partial, cx.d_totals, nullptr, b.longest < (1ll << 30))))
         return rc;
-    HIP_TRY(hipEventRecord(t->ev[4], t->stream));
+    HIP_TRY(hipEventRecord(t->ev[kEvAggEnd], t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     st.n_calls = aggregate ? (int64_t)t->h_pin[kPinCalls] : 0;
-    if (progress) {
-        kg::Progress h;
-        HIP_TRY(hipMemcpy(&h, d_prog, sizeof h, hipMemcpyDeviceToHost));
-        kg_progress &g = res->progress;
-        for (int f = 0; f <= 10; f++) g.first_visited[f] = h.first[f] == ~0ull ? -1 : (int64_t)h.first[f];
-        g.last_visited = (int64_t)h.last_plus1 - 1;
-        g.first_beyond = h.first_beyond == ~0ull ? -1 : (int64_t)h.first_beyond;
-        g.walk_ran_off = h.walk_ran_off ? 1 : 0;
-        g.stream_slots = (int64_t)t->limit;
-        for (int f = 0; f <= 10; f++) g.found_upto[f] = g.first_visited[f] < 0 ? 0 : (int64_t)h.found_upto[f];
-        g.kmers_found = (int64_t)h.kmers_found;
-        res->has_progress = true;
-    }
+    if (progress && (rc = progress_fetch(cx))) return rc;
     st.agg_pieces = aggregate ? (int32_t)std::min<uint64_t>(t->h_pin[kPinPieces], 0x7FFFFFFF) : 0;
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, t->ev[1], t->ev[2])); st.ms_scan = ms;
-    HIP_TRY(hipEventElapsedTime(&ms, t->ev[2], t->ev[3])); st.ms_order = ms;
-    HIP_TRY(hipEventElapsedTime(&ms, t->ev[3], t->ev[4])); st.ms_aggregate = ms;
-    HIP_TRY(hipEventElapsedTime(&ms, t->ev[0], t->ev[4])); st.ms_total = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, t->ev[kEvScanBegin], t->ev[kEvScanEnd])); st.ms_scan = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, t->ev[kEvScanEnd], t->ev[kEvOrderEnd])); st.ms_order = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, t->ev[kEvOrderEnd], t->ev[kEvAggEnd])); st.ms_aggregate = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, t->ev[kEvBegin], t->ev[kEvAggEnd])); st.ms_total = ms;
     if (st.partitioned) {
         // the passes of different chunks overlap: "scatter" = until the last chunk is scattered, "tail" = what is left
         // of the tag / verify passes after that; ms_part_tag is kept for layout compatibility
-        HIP_TRY(hipEventElapsedTime(&ms, t->ev[1], t->ev[5])); st.ms_part_scatter = ms;
+        HIP_TRY(hipEventElapsedTime(&ms, t->ev[kEvScanBegin], t->ev[kEvScattered])); st.ms_part_scatter = ms;
         st.ms_part_tag = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, t->ev[5], t->ev[7])); st.ms_part_verify = ms;
+        HIP_TRY(hipEventElapsedTime(&ms, t->ev[kEvScattered], t->ev[kEvJoined])); st.ms_part_verify = ms;
     }
     return KG_OK;
 }
@@ -1748,7 +1969,7 @@ int kg_result_copy_hits(kg_result *r, int64_t first, int64_t count, kg_hit *dst)
             return fail(KG_ERR_NOMEM, "pinned staging allocation failed");
         }
     hipStream_t s = r->tab->stream;
-    hipEvent_t done[2] = {r->tab->ev[6], r->tab->ev[0]};      // idle outside a scan
+    hipEvent_t done[2] = {r->tab->ev[kEvSpare], r->tab->ev[kEvBegin]};      // idle outside a scan
     int rc = KG_OK;
     int64_t sent = 0, got = 0;
     int which = 0;
