@@ -9,6 +9,7 @@
  * tables it reads: kg_table_build* places a signature list the way the lookup finds it, kg_table_save writes a resident
  * table back to kmer.table.mem_map[.gz], and kg_signatures_derive* makes that list from annotated proteins.
  * kg_result_assign / kg_assign_calls turn the CALL records of an -a scan into one function per protein.
+ * kg_result_regions / kg_regions_calls merge the CALL records of a DNA scan into function regions in contig coordinates.
  *
  * Conventions: plain pointers and sizes only; every function returns an int status
  * (KG_OK == 0, negative == error) and never throws or aborts across the boundary; the text
@@ -326,6 +327,83 @@ int kg_result_assign(kg_result *r, const kg_assign_params *p, kg_assignment *dst
 /* caller-held CALL lists: host arrays calls[call_start[n_prot]], call_start[n_prot + 1], otu[n_prot] or NULL */
 int kg_assign_calls(int device, const kg_assign_params *p, const kg_call *calls, const int64_t *call_start,
                     int64_t n_prot, const kg_otu *otu, kg_assignment *dst);
+
+/* ---- locating functions: the CALL records of a DNA scan -> function regions on the contigs (kernels: kg_regions.hpp) ----
+ *
+ * The reference stops at the CALL lines, one list per (contig, strand, frame); this rule is the project's own.
+ * Input: the CALL records of a DNA scan (aa == 0) in calls[] order (by container, emission order inside one), and the contig
+ * lengths L_s = offsets[s+1] - offsets[s].  Container 6s + c is sequence s, strand '+' for c in {0,1,2} and '-' for c in
+ * {3,4,5}, frame f = c mod 3 (kg_hit.container, KGJ:907-911, 1064-1072).
+ *   1. Strand coordinates.  A CALL with start = a, end = b (residues; end already includes the K-1, KGJ:399-400) covers
+ *      nucleotides x0 = f + 3a to x1 = f + 3b + 2, inclusive, counted from the 5' end of its own strand.  For records that come
+ *      from a scan 0 <= x0 <= x1 <= L_s - 1 always holds (translate, KGJ:320-343, never yields a valid residue from an
+ *      incomplete codon); for caller-held lists a record that breaks it is an error.
+ *   2. Groups.  CALLs are grouped by (sequence, strand, fI) -- the three frames of a strand together.  Inside a group they are
+ *      ordered by x0, ties by their index in calls[] (which is frame, then emission order).
+ *   3. Regions.  Walking a group in that order with R = the largest x1 seen so far in the current region, a CALL joins the
+ *      current region iff x0 - R - 1 <= merge_gap (int64); otherwise it opens a new one.  R is a running maximum, not the
+ *      predecessor's end: a long CALL that contains a later short one keeps the region open.
+ *   4. A region's record (kg_region, fixed layout, all int32 / float32 / uint32): seq; strand (0 '+', 1 '-'); left, right --
+ *      0-based inclusive positions on the contig as given ('+': min x0, R; '-': L_s - 1 - R, L_s - 1 - min x0); fI;
+ *      score = sum of count (int64, must be below 2^31); weighted = the float32 sum of weightedHits from 0.0f, one CALL at a
+ *      time in the group order, each add rounded to nearest; n_calls; frames = bit f set for every frame among its CALLs (more
+ *      than one bit: a frameshift candidate); best_frame = the frame of its CALL with the largest count (ties: the first in
+ *      group order); first_call = index in calls[] of its first CALL in group order; kept = 1 iff score >= min_score and
+ *      right - left + 1 >= min_len.
+ *   5. Output order: by (seq, left, right, strand, fI) ascending -- a total order, since two regions of one group are
+ *      disjoint -- plus region_start[n_seqs + 1] so that a contig's regions are one slice.  Every region is written, kept or
+ *      not.
+ *   6. Parameters kg_region_params { merge_gap, min_score, min_len }, all >= 0, else KG_ERR_ARG.  Defaults (this project's
+ *      choice): merge_gap = 600 -- the scan's default -g 200 residues in nucleotides, i.e. two CALLs the scan would have kept
+ *      in one list had they been in one frame -- and min_score = 0, min_len = 0.
+ *   7. The output depends only on the multiset of (CALL, index) and the lengths: not on launch geometry, not on how many
+ *      contigs share the batch.
+ * Errors: KG_ERR_ARG for a protein (-a) result, a KG_F_SKIP_AGGREGATE result, null pointers, decreasing offsets, calls[] not
+ * in non-decreasing container order, a container >= 6 * n_seqs, a negative count, a record outside [0, L_s) -- each message
+ * names the first offending CALL (or contig); KG_ERR_LIMIT for a region whose score reaches 2^31 (the message names its
+ * first_call), for n_calls >= 2^32, for a contig of 2^31 or more nucleotides or 2^31 or more contigs; KG_ERR_BUSY while a
+ * kg_scan* is in flight on the result's table; KG_ERR_NOMEM.  A bad record is clamped before it is used as an index, so it
+ * cannot make a kernel read or write outside its arrays.  Zero CALLs and zero sequences are valid and give an empty set.
+ * Device allocations come from the table's block cache (a table-less context for kg_regions_calls), so KG_TEST_FAIL_ALLOC
+ * applies; everything but the region set is back in the cache when the call returns.  A set made by kg_result_regions holds
+ * blocks of the result's table (kg_table_live_device_bytes counts them) and must be freed before that table is closed. */
+typedef struct kg_region_params { int32_t merge_gap; int32_t min_score; int32_t min_len; } kg_region_params;
+typedef struct kg_region {       /* 48 B */
+    int32_t  seq;
+    int32_t  strand;       /* 0 '+', 1 '-'                                              */
+    int32_t  left;         /* 0-based, inclusive, on the contig as given                */
+    int32_t  right;
+    int32_t  fI;
+    int32_t  score;        /* sum of count                                              */
+    float    weighted;     /* float32 sum of weightedHits in group order                */
+    int32_t  n_calls;
+    uint32_t frames;       /* bit f: a CALL of frame f                                  */
+    int32_t  best_frame;
+    uint32_t first_call;   /* index in calls[]                                          */
+    int32_t  kept;
+} kg_region;
+typedef struct kg_region_stats {
+    int64_t calls, groups, regions, kept;
+    int64_t multi_frame;   /* regions with more than one frame bit                      */
+    float   ms;            /* device time of the call's kernels                         */
+    int32_t reserved;
+} kg_region_stats;
+typedef struct kg_regionset kg_regionset;
+/* a DNA result of kg_scan* / kg_aggregate_hits plus the host offsets[n_seqs + 1] the scan was given (the result does not keep
+   the lengths) */
+int kg_result_regions(kg_result *r, const kg_region_params *p, const int64_t *offsets, kg_regionset **out);
+/* caller-held host lists: calls[n_calls] in non-decreasing container order, offsets[n_seqs + 1] */
+int kg_regions_calls(int device, const kg_region_params *p, const kg_call *calls, int64_t n_calls, const int64_t *offsets,
+                     int64_t n_seqs, kg_regionset **out);
+int64_t kg_regionset_count(const kg_regionset *s);
+/* device array of kg_regionset_count(s) kg_region records in output order, valid until kg_regionset_free */
+const kg_region *kg_regionset_device(const kg_regionset *s);
+/* records [first, first + count) into dst (host or device memory) */
+int kg_regionset_copy(const kg_regionset *s, int64_t first, int64_t count, kg_region *dst);
+/* region_start[n_seqs + 1] into dst (host or device memory): contig s owns records [region_start[s], region_start[s+1]) */
+int kg_regionset_seq_start(const kg_regionset *s, int64_t *dst);
+int kg_regionset_stats(const kg_regionset *s, kg_region_stats *out);
+void kg_regionset_free(kg_regionset *s);
 
 /* the resident 24-byte records, valid until kg_table_close, and how many there are: num_sigs for a built or adopted table, the
  * whole records of the file for an opened one (fewer than num_sigs for a truncated file, more for a longer one) */

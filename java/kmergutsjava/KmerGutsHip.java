@@ -105,6 +105,35 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_region_params (kg_result_regions / kg_regions_calls); this project's defaults: 600, 0 and 0. */
+    class KgRegionParams extends Structure {
+        public int merge_gap, min_score, min_len;
+        public KgRegionParams() {
+            setFieldOrder(new String[] {"merge_gap", "min_score", "min_len"});
+        }
+    }
+
+    /** struct kg_region (48 B): one function region of a contig, 0-based inclusive left / right. */
+    class KgRegion extends Structure {
+        public int seq, strand, left, right, fI, score;
+        public float weighted;
+        public int n_calls, frames, best_frame, first_call, kept;
+        public KgRegion() {
+            setFieldOrder(new String[] {"seq", "strand", "left", "right", "fI", "score", "weighted", "n_calls", "frames",
+                    "best_frame", "first_call", "kept"});
+        }
+    }
+
+    /** struct kg_region_stats. */
+    class KgRegionStats extends Structure {
+        public long calls, groups, regions, kept, multi_frame;
+        public float ms;
+        public int reserved;
+        public KgRegionStats() {
+            setFieldOrder(new String[] {"calls", "groups", "regions", "kept", "multi_frame", "ms", "reserved"});
+        }
+    }
+
     // replaces readKmerTableHeader + the table stream of lookup (KmerGutsJava.java:924-942, 944-1034)
     int kg_table_open(String path, int device, PointerByReference out);
     int kg_table_from_memory(Pointer image, long nbytes, int device, PointerByReference out);
@@ -157,6 +186,16 @@ public interface KmerGutsHip extends Library {
     /** one function per protein: dst = kg_assignment[n_seqs] (40 B each; host or device memory), ms = float[1] or null */
     int kg_result_assign(Pointer result, KgAssignParams params, Pointer dst, float[] ms);
     int kg_assign_calls(int device, KgAssignParams params, Pointer calls, long[] callStart, long nProt, Pointer otu, Pointer dst);
+    /** the CALLs of a DNA result -> function regions on the contigs; offsets = the long[nSeqs + 1] the scan was given */
+    int kg_result_regions(Pointer result, KgRegionParams params, long[] offsets, PointerByReference out);
+    int kg_regions_calls(int device, KgRegionParams params, Pointer calls, long nCalls, long[] offsets, long nSeqs,
+                         PointerByReference out);
+    long kg_regionset_count(Pointer set);
+    Pointer kg_regionset_device(Pointer set);                // kg_region[count] in device memory, output order
+    int kg_regionset_copy(Pointer set, long first, long count, Pointer dst);
+    int kg_regionset_seq_start(Pointer set, long[] dst);     // long[nSeqs + 1]
+    int kg_regionset_stats(Pointer set, KgRegionStats out);
+    void kg_regionset_free(Pointer set);
     void kg_result_free(Pointer result);
     int kg_restore_hits_device(int device, Pointer dSrc, long nHits, Pointer dSeqFirst, long nSeqs, Pointer dDstFirst,
                                Pointer dContainerShift, Pointer dDst, Pointer stream);

@@ -34,6 +34,8 @@ EXPORTS = (
     "kg_result_device_container_hit_start", "kg_result_device_container_call_start", "kg_result_free", "kg_restore_hits_device",
     "kg_signatures_derive", "kg_signatures_derive_device", "kg_sigset_count", "kg_sigset_device", "kg_sigset_copy",
     "kg_sigset_stats", "kg_sigset_free", "kg_result_assign", "kg_assign_calls",
+    "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
+    "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_last_error", "kg_version",
 )
 
@@ -56,6 +58,11 @@ ASSIGNMENT_DTYPE = np.dtype([("fI", "<i4"), ("assigned", "<i4"), ("score", "<i4"
                              ("n_calls", "<i4"), ("n_functions", "<i4"), ("second_fi", "<i4"), ("second_score", "<i4"),
                              ("otu", "<i4")])
 assert ASSIGNMENT_DTYPE.itemsize == 40
+# struct kg_region (kg_result_regions / kg_regions_calls): one function region of a contig
+REGION_DTYPE = np.dtype([("seq", "<i4"), ("strand", "<i4"), ("left", "<i4"), ("right", "<i4"), ("fI", "<i4"), ("score", "<i4"),
+                         ("weighted", "<f4"), ("n_calls", "<i4"), ("frames", "<u4"), ("best_frame", "<i4"),
+                         ("first_call", "<u4"), ("kept", "<i4")])
+assert REGION_DTYPE.itemsize == 48
 assert HIT_DTYPE.itemsize == 24 and CALL_DTYPE.itemsize == 24 and OTU_DTYPE.itemsize == 44
 
 
@@ -108,6 +115,20 @@ class KgDeriveStats(C.Structure):
 class KgAssignParams(C.Structure):
     """struct kg_assign_params (kg_result_assign / kg_assign_calls)."""
     _fields_ = [("min_score", C.c_int32), ("min_share_pct", C.c_int32)]
+
+
+class KgRegionParams(C.Structure):
+    """struct kg_region_params (kg_result_regions / kg_regions_calls)."""
+    _fields_ = [("merge_gap", C.c_int32), ("min_score", C.c_int32), ("min_len", C.c_int32)]
+
+
+class KgRegionStats(C.Structure):
+    """struct kg_region_stats."""
+    _fields_ = [("calls", C.c_int64), ("groups", C.c_int64), ("regions", C.c_int64), ("kept", C.c_int64),
+                ("multi_frame", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
 class KmerGutsNativeError(RuntimeError):
@@ -186,6 +207,17 @@ def load() -> C.CDLL:
     lib.kg_sigset_free.restype = None
     lib.kg_result_assign.argtypes = [vp, C.POINTER(KgAssignParams), vp, C.POINTER(C.c_float)]
     lib.kg_assign_calls.argtypes = [C.c_int, C.POINTER(KgAssignParams), vp, vp, C.c_int64, vp, vp]
+    lib.kg_result_regions.argtypes = [vp, C.POINTER(KgRegionParams), vp, C.POINTER(vp)]
+    lib.kg_regions_calls.argtypes = [C.c_int, C.POINTER(KgRegionParams), vp, C.c_int64, vp, C.c_int64, C.POINTER(vp)]
+    lib.kg_regionset_count.argtypes = [vp]
+    lib.kg_regionset_count.restype = C.c_int64
+    lib.kg_regionset_device.argtypes = [vp]
+    lib.kg_regionset_device.restype = vp
+    lib.kg_regionset_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.kg_regionset_seq_start.argtypes = [vp, vp]
+    lib.kg_regionset_stats.argtypes = [vp, C.POINTER(KgRegionStats)]
+    lib.kg_regionset_free.argtypes = [vp]
+    lib.kg_regionset_free.restype = None
     lib.kg_last_error.restype = C.c_char_p
     lib.kg_version.restype = C.c_char_p
     for name in EXPORTS:

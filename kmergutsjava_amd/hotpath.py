@@ -204,6 +204,22 @@ class ScanResult:
         self.assign_ms = float(ms.value)
         return out
 
+    def regions(self, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, device_out: bool = False):
+        """The CALL records of a DNA result merged into function regions in contig coordinates, on the GPU
+        (include/kmerguts_hip.h kg_result_regions states the rule).  offsets: the int64[n_seqs + 1] the scan was given.
+        -> (records, region_start): records a numpy array of _native.REGION_DTYPE in output order, or with device_out=True a
+        CUDA uint8 tensor of 48 bytes per region; region_start int64[n_seqs + 1], contig s owning records
+        [region_start[s], region_start[s + 1]).  The call's counts and device time are left in `region_stats`."""
+        lib = self._need()
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+        if off.shape != (self.stats["n_seqs"] + 1,):
+            raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
+        p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
+        h = C.c_void_p()
+        N.check(lib.kg_result_regions(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
+        out, start, self.region_stats = _take_regionset(h, self.stats["n_seqs"], device_out)
+        return out, start
+
     def close(self) -> None:
         if self._h:
             N.load().kg_result_free(self._h)
@@ -476,3 +492,45 @@ def assign_calls(calls, call_start, otu=None, min_score: int = 0, min_share_pct:
     N.check(N.load().kg_assign_calls(device, C.byref(p), c.ctypes.data if c.size else None, cs.ctypes.data, n,
                                      o.ctypes.data if o is not None and n else None, out.ctypes.data if n else None))
     return out
+
+
+def _take_regionset(h, n_seqs: int, device_out: bool):
+    """Copy a kg_regionset out (records to the host or into a CUDA tensor, region_start to the host) and free it.
+    -> (records, region_start, statistics)."""
+    lib = N.load()
+    try:
+        st = N.KgRegionStats()
+        N.check(lib.kg_regionset_stats(h, C.byref(st)))
+        n = int(lib.kg_regionset_count(h))
+        start = np.zeros(n_seqs + 1, dtype=np.int64)
+        N.check(lib.kg_regionset_seq_start(h, start.ctypes.data))
+        if device_out:
+            import torch
+            out = torch.empty(n * N.REGION_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            N.check(lib.kg_regionset_copy(h, 0, n, C.c_void_p(out.data_ptr() if n else None)))
+        else:
+            out = np.zeros(n, dtype=N.REGION_DTYPE)
+            N.check(lib.kg_regionset_copy(h, 0, n, out.ctypes.data if n else None))
+        return out, start, st.as_dict()
+    finally:
+        lib.kg_regionset_free(h)
+
+
+def region_calls(calls, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, device: int = 0,
+                 device_out: bool = False, stats: Optional[dict] = None):
+    """Function regions from caller-held CALL records of a DNA scan, on the GPU (kg_regions_calls): calls CALL_DTYPE in
+    non-decreasing container order, offsets int64[n_seqs + 1].  -> (records, region_start) as ScanResult.regions; `stats`, when
+    given, receives the call's counts and device time."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_seqs + 1]")
+    c = np.ascontiguousarray(calls, dtype=N.CALL_DTYPE)
+    p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
+    h = C.c_void_p()
+    N.check(N.load().kg_regions_calls(device, C.byref(p), c.ctypes.data if c.size else None, c.size, off.ctypes.data,
+                                      off.size - 1, C.byref(h)))
+    out, start, st = _take_regionset(h, off.size - 1, device_out)
+    if stats is not None:
+        stats.update(st)
+    return out, start
