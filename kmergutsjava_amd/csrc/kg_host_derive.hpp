@@ -1,0 +1,397 @@
+// kg_host_derive.hpp -- kg_signatures_derive / kg_signatures_derive_device: annotated proteins -> a signature set (kernels:
+// kg_derive.hpp).
+// Part of kmerguts_hip.hip's translation unit: included at its end, behind kg_host.hpp and the kernel headers.
+#pragma once
+
+struct kg_sigset {
+    int device = 0;
+    uint8_t *d_sigs = nullptr;          // count * 24 bytes (hipMalloc, owned)
+    int64_t count = 0;
+    kg_derive_stats st = {};
+};
+
+namespace {
+
+constexpr uint64_t kDeriveBytesPerWindow = 160;                       // device bytes one valid window of a pass needs, at most
+constexpr uint64_t kDerivePassMax = (1ull << 32) - (1ull << 22);      // the 32-bit scans and indices of one pass
+
+struct DeriveRange { uint64_t lo, hi, count; };
+
+struct Deriver {
+    kg_table *t;                        // the call's context: stream, block cache, KG_TEST_FAIL_ALLOC
+    Scratch &sc;
+    const uint8_t *d_seq;
+    kg::BlockDesc *d_blocks = nullptr;
+    uint32_t n_blocks = 0;
+    unsigned long long *d_bins = nullptr;
+    uint64_t cap = 0;
+    std::vector<DeriveRange> elems;     // k-mer ranges in order, each within the cap
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float ms_hist = 0;
+
+    // counts of the valid windows with k-mers in [lo, hi), in bins of 2^shift k-mers
+    int histogram(uint64_t lo, uint64_t hi, uint32_t shift, std::vector<unsigned long long> &out)
+    {
+        HIP_TRY(hipMemsetAsync(d_bins, 0, kg::kDeriveBins * 8, t->stream));
+        HIP_TRY(hipEventRecord(ev[0], t->stream));
+        if (n_blocks) {
+            const uint32_t grid = std::min<uint32_t>((n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16);
+            hipLaunchKernelGGL(kg::derive_windows_kernel<false>, dim3(grid), dim3(kg::kDeriveThreads), 0, t->stream, d_seq, d_blocks,
+                               n_blocks, lo, hi, shift, d_bins, nullptr, 0u, nullptr, nullptr, nullptr, (uint64_t)0);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(ev[1], t->stream));
+        out.assign(kg::kDeriveBins, 0);
+        HIP_TRY(hipMemcpyAsync(out.data(), d_bins, kg::kDeriveBins * 8, hipMemcpyDeviceToHost, t->stream));
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        ms_hist += ms;
+        return KG_OK;
+    }
+
+    static uint32_t shift_for(uint64_t width)
+    {
+        uint32_t s = 0;
+        while (((width - 1) >> s) >= kg::kDeriveBins) s++;
+        return s;
+    }
+
+    // the range [lo, hi) holds `count` windows: keep it, or cut it finer until every piece fits the cap
+    int split(uint64_t lo, uint64_t hi, uint64_t count)
+    {
+        if (count <= cap) { elems.push_back({lo, hi, count}); return KG_OK; }
+        if (hi - lo == 1)
+            return fail(KG_ERR_LIMIT, "k-mer " + kmer_text((int64_t)lo) + " alone occurs in " + kmer_text((int64_t)count) +
+                                          " valid windows, more than max_windows_per_pass = " + kmer_text((int64_t)cap));
+        const uint32_t shift = shift_for(hi - lo);
+        std::vector<unsigned long long> bins;
+        int rc = histogram(lo, hi, shift, bins);
+        if (rc) return rc;
+        for (uint64_t i = 0; i < kg::kDeriveBins; i++) {
+            const uint64_t a = lo + (i << shift);
+            if (a >= hi) break;
+            if (bins[i] && (rc = split(a, std::min<uint64_t>(hi, a + (1ull << shift)), bins[i]))) return rc;
+        }
+        return KG_OK;
+    }
+};
+
+int derive_impl(kg_table *t, const kg_derive_params *prm, const uint8_t *h_seq, const uint8_t *d_seq_in, const int64_t *offsets,
+                int64_t n_prot, const int32_t *fn, const int32_t *otu, kg_sigset *set)
+{
+    kg_derive_stats &st = set->st;
+    // ---- host: block counts (kg_scan's -a trip counts, KGJ:912) ----
+    std::vector<uint32_t> ibase((size_t)n_prot + 1);
+    uint64_t nblocks = 0, windows = 0;
+    for (int64_t k = 0; k < n_prot; k++) {
+        const int64_t L = offsets[k + 1] - offsets[k];
+        ibase[(size_t)k] = (uint32_t)nblocks;
+        const uint64_t nwin = L >= 9 ? (uint64_t)L - 8 : 0;
+        windows += nwin;
+        nblocks += (nwin + kg::kAaWinPerBlock - 1) / kg::kAaWinPerBlock;
+        if (nblocks > 0x7FFFFFFFull) return fail(KG_ERR_LIMIT, "2^31 or more window blocks of 64 windows in one call");
+    }
+    ibase[(size_t)n_prot] = (uint32_t)nblocks;
+    st.proteins = n_prot;
+    st.windows = (int64_t)windows;
+    const uint32_t b = bits_for((uint64_t)n_prot);
+
+    Scratch sc(t);
+    int rc;
+    Events<8> ev;
+    if ((rc = ev.create())) return rc;
+
+    // ---- the sequence on the device ----
+    const uint8_t *d_seq = d_seq_in;
+    const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
+    if (h_seq && seq_bytes) {
+        uint8_t *d = nullptr;
+        if ((rc = sc.get(&d, seq_bytes))) return rc;
+        if ((rc = upload_pinned(t, h_seq, seq_bytes, d))) return rc;
+        d_seq = d;
+    }
+    HIP_TRY(hipEventRecord(ev[0], t->stream));
+
+    Deriver dv{t, sc, d_seq};
+    dv.ev[0] = ev[6]; dv.ev[1] = ev[7];
+    dv.n_blocks = (uint32_t)nblocks;
+    if ((rc = sc.get(&dv.d_bins, kg::kDeriveBins))) return rc;
+    int32_t *d_fn = nullptr, *d_otu = nullptr, *fn_r = nullptr, *otu_r = nullptr;
+    uint32_t *rank_of = nullptr;
+    if (n_prot) {
+        int64_t *d_off = nullptr;
+        uint32_t *d_ibase = nullptr;
+        if ((rc = sc.get(&d_off, (size_t)n_prot + 1)) || (rc = sc.get(&d_ibase, (size_t)n_prot + 1)) ||
+            (rc = sc.get(&d_fn, (size_t)n_prot)) || (rc = sc.get(&d_otu, (size_t)n_prot)) || (rc = sc.get(&fn_r, (size_t)n_prot)) ||
+            (rc = sc.get(&otu_r, (size_t)n_prot)) || (rc = sc.get(&rank_of, (size_t)n_prot)))
+            return rc;
+        if (nblocks && (rc = sc.get(&dv.d_blocks, nblocks))) return rc;
+        HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)n_prot + 1) * 8, hipMemcpyHostToDevice, t->stream));
+        HIP_TRY(hipMemcpyAsync(d_ibase, ibase.data(), ((size_t)n_prot + 1) * 4, hipMemcpyHostToDevice, t->stream));
+        HIP_TRY(hipMemcpyAsync(d_fn, fn, (size_t)n_prot * 4, hipMemcpyHostToDevice, t->stream));
+        HIP_TRY(hipMemcpyAsync(d_otu, otu, (size_t)n_prot * 4, hipMemcpyHostToDevice, t->stream));
+        if (nblocks) {
+            hipLaunchKernelGGL(kg::build_blocks_kernel, dim3(grid_of(nblocks)), dim3(256), 0, t->stream, d_off, d_ibase, (uint32_t)n_prot,
+                               (uint32_t)nblocks, dv.d_blocks);
+            HIP_TRY(hipGetLastError());
+        }
+        // ---- rank the proteins by (fn, otu, p): a stable sort of (fn + 1, otu) keys carrying p ----
+        HIP_TRY(hipEventRecord(ev[1], t->stream));
+        SortPairs sp;
+        if ((rc = sp.alloc(sc, (uint64_t)n_prot))) return rc;
+        hipLaunchKernelGGL(kg::derive_rank_keys_kernel, dim3(grid_of(n_prot)), dim3(256), 0, t->stream, d_fn, d_otu, (uint64_t)n_prot,
+                           sp.keys(), sp.vals());
+        HIP_TRY(hipGetLastError());
+        int32_t fmax = -1, omax = 0;
+        for (int64_t k = 0; k < n_prot; k++) {
+            fmax = std::max(fmax, fn[k]);
+            if (fn[k] >= 0) omax = std::max(omax, otu[k]);
+        }
+        const uint64_t kmax = ((uint64_t)((uint32_t)fmax + 1u) << 31) | (uint64_t)(uint32_t)omax;
+        if ((rc = sp.sort(t, sc, (uint64_t)n_prot, bit_width(kmax)))) return rc;
+        hipLaunchKernelGGL(kg::derive_rank_scatter_kernel, dim3(grid_of(n_prot)), dim3(256), 0, t->stream, sp.vals(), d_fn, d_otu,
+                           (uint64_t)n_prot, rank_of, fn_r, otu_r);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev[2], t->stream));
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        st.ms_sort += ev.ms(1, 2);
+    }
+
+    // ---- the pass plan: a histogram of the valid windows over the whole k-mer space, bins cut finer where needed ----
+    {
+        uint64_t cap = (uint64_t)prm->max_windows_per_pass;
+        if (cap == 0) {
+            size_t free_b = 0, total_b = 0;
+            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+            cap = std::max<uint64_t>(1u << 20, (uint64_t)(free_b * 0.8) / kDeriveBytesPerWindow);
+        }
+        dv.cap = std::min(cap, kDerivePassMax);
+    }
+    std::vector<unsigned long long> bins;
+    const uint64_t space = (uint64_t)KG_MAX_ENCODED;
+    const uint32_t shift0 = Deriver::shift_for(space);
+    if ((rc = dv.histogram(0, space, shift0, bins))) return rc;
+    uint64_t valid = 0;
+    for (auto c : bins) valid += c;
+    st.valid_windows = (int64_t)valid;
+    for (uint64_t i = 0; i < kg::kDeriveBins; i++) {
+        const uint64_t a = i << shift0;
+        if (a >= space) break;
+        if (bins[i] && (rc = dv.split(a, std::min<uint64_t>(space, a + (1ull << shift0)), bins[i]))) return rc;
+    }
+    std::vector<DeriveRange> passes;
+    for (const auto &e : dv.elems) {
+        if (!passes.empty() && passes.back().count + e.count <= dv.cap) {
+            passes.back().hi = e.hi;
+            passes.back().count += e.count;
+        } else {
+            passes.push_back(e);
+        }
+    }
+    st.passes = (int32_t)passes.size();
+
+    // ---- one pass per k-mer range ----
+    std::vector<std::pair<uint8_t *, uint64_t>> outs;       // each pass's signatures (sc blocks), in k-mer order
+    unsigned long long *d_cur = nullptr;
+    uint64_t *d_tot = nullptr;
+    if ((rc = sc.get(&d_cur, 2)) || (rc = sc.get(&d_tot, 8))) return rc;
+    uint64_t total_sigs = 0;
+    for (const DeriveRange &ps : passes) {
+        const uint64_t n = ps.count;
+        Scratch pass(t);                                    // this pass's scratch, back in the cache at its end
+        SortPairs sp;
+        if ((rc = sp.alloc(pass, n))) return rc;
+        HIP_TRY(hipMemsetAsync(d_cur, 0, 8, t->stream));
+        HIP_TRY(hipEventRecord(ev[1], t->stream));
+        {
+            const uint32_t grid = std::min<uint32_t>((dv.n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16);
+            hipLaunchKernelGGL(kg::derive_windows_kernel<true>, dim3(std::max(grid, 1u)), dim3(kg::kDeriveThreads), 0, t->stream, d_seq,
+                               dv.d_blocks, dv.n_blocks, ps.lo, ps.hi, 0u, nullptr, rank_of, b, sp.keys(), sp.vals(), d_cur, n);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(ev[2], t->stream));
+        if ((rc = sp.sort(t, pass, n, bit_width(ps.hi - ps.lo - 1) + b))) return rc;
+        HIP_TRY(hipEventRecord(ev[3], t->stream));
+        // collapse equal keys into (k-mer, protein) pairs
+        const uint64_t nb = n / kg::kScanChunk + 2;
+        uint32_t *flags = nullptr, *pidx = nullptr;
+        uint64_t *partial = nullptr;
+        if ((rc = pass.get(&flags, n)) || (rc = pass.get(&pidx, n)) || (rc = pass.get(&partial, nb + 1))) return rc;
+        hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(n)), dim3(256), 0, t->stream, sp.keys(), n, flags);
+        HIP_TRY(hipGetLastError());
+        if ((rc = prefix_sum(t, flags, n, pidx, partial, d_tot + 0))) return rc;
+        unsigned long long host_cur = 0;
+        uint64_t P = 0;
+        HIP_TRY(hipMemcpyAsync(&host_cur, d_cur, 8, hipMemcpyDeviceToHost, t->stream));
+        HIP_TRY(hipMemcpyAsync(&P, d_tot, 8, hipMemcpyDeviceToHost, t->stream));
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        if (host_cur != n) return fail(KG_ERR_DEVICE, "internal: a pass emitted a different number of windows than its histogram counted");
+        uint64_t *pk = nullptr;
+        uint32_t *pv = nullptr;
+        if ((rc = pass.get(&pk, P)) || (rc = pass.get(&pv, P))) return rc;
+        HIP_TRY(hipMemsetAsync(pv, 0, P * 4, t->stream));
+        hipLaunchKernelGGL(kg::derive_collapse_kernel, dim3(grid_of((n + kg::kDeriveChunk - 1) / kg::kDeriveChunk)), dim3(256), 0, t->stream,
+                           sp.keys(), sp.vals(), n, pidx, pk, pv);
+        HIP_TRY(hipGetLastError());
+        // run heads and numbers at the three levels (flags / pidx / partial are reused: P <= n)
+        uint32_t *kh = flags, *fh = nullptr, *oh = nullptr, *kx = pidx, *fx = nullptr, *ox = nullptr;
+        if ((rc = pass.get(&fh, P)) || (rc = pass.get(&oh, P)) || (rc = pass.get(&fx, P)) || (rc = pass.get(&ox, P))) return rc;
+        hipLaunchKernelGGL(kg::derive_run_flags_kernel, dim3(grid_of(P)), dim3(256), 0, t->stream, pk, P, b, fn_r, otu_r, kh, fh, oh);
+        HIP_TRY(hipGetLastError());
+        if ((rc = prefix_sum(t, kh, P, kx, partial, d_tot + 1)) || (rc = prefix_sum(t, fh, P, fx, partial, d_tot + 2)) ||
+            (rc = prefix_sum(t, oh, P, ox, partial, d_tot + 3)))
+            return rc;
+        uint64_t tot[3] = {0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(tot, d_tot + 1, 24, hipMemcpyDeviceToHost, t->stream));
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        const uint64_t K = tot[0], F = tot[1], O = tot[2];
+        uint32_t *kstart = nullptr, *fstart = nullptr, *f_kmer = nullptr, *ostart = nullptr, *o_frun = nullptr;
+        int32_t *f_fn = nullptr, *o_otu = nullptr;
+        unsigned long long *fsum = nullptr, *kbest = nullptr, *kotu = nullptr;
+        if ((rc = pass.get(&kstart, K + 1)) || (rc = pass.get(&fstart, F + 1)) || (rc = pass.get(&f_kmer, F)) ||
+            (rc = pass.get(&f_fn, F)) || (rc = pass.get(&ostart, O + 1)) || (rc = pass.get(&o_frun, O)) || (rc = pass.get(&o_otu, O)) ||
+            (rc = pass.get(&fsum, F)) || (rc = pass.get(&kbest, K)) || (rc = pass.get(&kotu, K)))
+            return rc;
+        hipLaunchKernelGGL(kg::derive_run_starts_kernel, dim3(grid_of(P)), dim3(256), 0, t->stream, pk, P, b, fn_r, otu_r, kx, fx, ox,
+                           d_tot + 1, d_tot + 2, d_tot + 3, kstart, fstart, f_kmer, f_fn, ostart, o_frun, o_otu);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(fsum, 0, F * 8, t->stream));
+        HIP_TRY(hipMemsetAsync(kbest, 0, K * 8, t->stream));
+        HIP_TRY(hipMemsetAsync(kotu, 0, K * 8, t->stream));
+        hipLaunchKernelGGL(kg::derive_run_sums_kernel, dim3(grid_of((P + kg::kDeriveChunk - 1) / kg::kDeriveChunk)), dim3(256), 0, t->stream,
+                           pv, P, fh, fx, fsum);
+        hipLaunchKernelGGL(kg::derive_fn_best_kernel, dim3(grid_of(F)), dim3(256), 0, t->stream, fstart, f_kmer, f_fn, F, kbest);
+        hipLaunchKernelGGL(kg::derive_otu_best_kernel, dim3(grid_of(O)), dim3(256), 0, t->stream, ostart, o_frun, o_otu, O, f_kmer, kbest, kotu);
+        HIP_TRY(hipGetLastError());
+        // the signatures of the pass, in k-mer order (kflags / kidx reuse fh / fx: K <= P)
+        uint32_t *kflags = fh, *kidx = fx;
+        hipLaunchKernelGGL(kg::derive_select_kernel<false>, dim3(grid_of(K)), dim3(256), 0, t->stream, K, kstart, kbest, kotu, fsum, f_fn,
+                           pk, b, ps.lo, (int64_t)prm->min_proteins, (int64_t)prm->purity_pct, kflags, nullptr, nullptr);
+        HIP_TRY(hipGetLastError());
+        if ((rc = prefix_sum(t, kflags, K, kidx, partial, d_tot + 4))) return rc;
+        uint64_t S = 0;
+        HIP_TRY(hipMemcpyAsync(&S, d_tot + 4, 8, hipMemcpyDeviceToHost, t->stream));
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        if (S) {
+            uint8_t *o = nullptr;
+            if ((rc = sc.get(&o, S * 24))) return rc;
+            hipLaunchKernelGGL(kg::derive_select_kernel<true>, dim3(grid_of(K)), dim3(256), 0, t->stream, K, kstart, kbest, kotu, fsum, f_fn,
+                               pk, b, ps.lo, (int64_t)prm->min_proteins, (int64_t)prm->purity_pct, nullptr, kidx, o);
+            HIP_TRY(hipGetLastError());
+            outs.emplace_back(o, S);
+        }
+        HIP_TRY(hipEventRecord(ev[4], t->stream));
+        HIP_TRY(hipStreamSynchronize(t->stream));
+        st.ms_encode += ev.ms(1, 2);
+        st.ms_sort += ev.ms(2, 3);
+        st.ms_reduce += ev.ms(3, 4);
+        st.pairs += (int64_t)P;
+        st.kmers += (int64_t)K;
+        total_sigs += S;
+    }
+    if (total_sigs >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more signatures");
+    // ---- the set: the passes' signatures back to back ----
+    if ((rc = dalloc_detached(t, &set->d_sigs, std::max<uint64_t>(total_sigs * 24, 24)))) return rc;
+    uint64_t at = 0;
+    for (auto &o : outs) {
+        HIP_TRY(hipMemcpyAsync(set->d_sigs + at * 24, o.first, o.second * 24, hipMemcpyDeviceToDevice, t->stream));
+        at += o.second;
+    }
+    HIP_TRY(hipEventRecord(ev[5], t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    st.ms_encode += dv.ms_hist;
+    st.ms_total = ev.ms(0, 5);
+    st.signatures = (int64_t)total_sigs;
+    set->count = (int64_t)total_sigs;
+    return KG_OK;
+}
+
+int derive_entry(int device, const kg_derive_params *prm, const uint8_t *h_seq, const uint8_t *d_seq, const int64_t *offsets,
+                 int64_t n_prot, const int32_t *fn, const int32_t *otu, kg_sigset **out)
+{
+    if (!out) return fail(KG_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!prm) return fail(KG_ERR_ARG, "null kg_derive_params");
+    if (prm->min_proteins < 1) return fail(KG_ERR_ARG, "min_proteins must be >= 1");
+    if (prm->purity_pct < 1 || prm->purity_pct > 100) return fail(KG_ERR_ARG, "purity_pct must be in 1..100");
+    if (prm->max_windows_per_pass < 0) return fail(KG_ERR_ARG, "max_windows_per_pass must be >= 0");
+    if (n_prot < 0) return fail(KG_ERR_ARG, "n_prot < 0");
+    if (n_prot >= (1ll << 29)) return fail(KG_ERR_LIMIT, "2^29 or more proteins in one call");
+    if (!offsets) return fail(KG_ERR_ARG, "null offsets");
+    if (n_prot > 0 && (!fn || !otu)) return fail(KG_ERR_ARG, "null fn / otu array");
+    if (offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
+    for (int64_t k = 0; k < n_prot; k++) {
+        const int64_t L = offsets[k + 1] - offsets[k];
+        if (L < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": offsets decrease (offsets[p+1] < offsets[p])");
+        if (L >= (1ll << 31)) return fail(KG_ERR_LIMIT, "protein " + kmer_text(k) + ": 2^31 or more characters");
+        if (fn[k] < -1) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": fn = " + kmer_text(fn[k]) + " < -1");
+        if (fn[k] >= 0 && otu[k] < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": otu = " + kmer_text(otu[k]) + " < 0 on an annotated protein");
+    }
+    const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
+    if (seq_bytes && !h_seq && !d_seq) return fail(KG_ERR_ARG, "null sequence");
+    CallScope cs(device);               // the call's context: closed when the call returns, the set keeps only its signatures
+    if (cs.rc) return cs.rc;
+    kg_sigset *set = new (std::nothrow) kg_sigset();
+    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
+    set->device = device;
+    int rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
+    if (!rc) rc = derive_impl(cs.t, prm, h_seq, d_seq, offsets, n_prot, fn, otu, set);
+    cs.t->cache.release_all();                          // scratch goes back to the driver
+    if (rc) { kg_sigset_free(set); return rc; }
+    if (getenv("KG_DEBUG"))
+        fprintf(stderr, "[kg] kg_signatures_derive: proteins=%lld valid=%lld pairs=%lld kmers=%lld sigs=%lld passes=%d encode_ms=%.3f sort_ms=%.3f reduce_ms=%.3f total_ms=%.3f\n",
+                (long long)set->st.proteins, (long long)set->st.valid_windows, (long long)set->st.pairs, (long long)set->st.kmers,
+                (long long)set->st.signatures, set->st.passes, set->st.ms_encode, set->st.ms_sort, set->st.ms_reduce, set->st.ms_total);
+    *out = set;
+    return KG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kg_signatures_derive(int device, const kg_derive_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
+                         const int32_t *fn, const int32_t *otu, kg_sigset **out)
+{
+    return derive_entry(device, p, seq, nullptr, offsets, n_prot, fn, otu, out);
+}
+
+int kg_signatures_derive_device(int device, const kg_derive_params *p, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
+                                const int32_t *fn, const int32_t *otu, kg_sigset **out)
+{
+    return derive_entry(device, p, nullptr, d_seq, offsets, n_prot, fn, otu, out);
+}
+
+int64_t kg_sigset_count(const kg_sigset *s) { return s ? s->count : 0; }
+
+const kg_signature *kg_sigset_device(const kg_sigset *s) { return s ? (const kg_signature *)s->d_sigs : nullptr; }
+
+int kg_sigset_copy(const kg_sigset *s, int64_t first, int64_t count, kg_signature *dst)
+{
+    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
+    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_sigset_copy: range outside the set");
+    if (count == 0) return KG_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpy(dst, s->d_sigs + first * 24, (size_t)count * 24, hipMemcpyDefault));
+    return KG_OK;
+}
+
+int kg_sigset_stats(const kg_sigset *s, kg_derive_stats *out)
+{
+    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
+    *out = s->st;
+    return KG_OK;
+}
+
+void kg_sigset_free(kg_sigset *s)
+{
+    if (!s) return;
+    if (s->d_sigs) {
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->d_sigs);
+    }
+    delete s;
+}
+
+}  // extern "C"

@@ -19,318 +19,12 @@
 #include <unistd.h>
 #include <zlib.h>
 
-#include <algorithm>
-#include <atomic>
 #include <cerrno>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <new>
-#include <string>
-#include <thread>
-#include <unordered_map>
-#include <vector>
+
+#include "kg_host.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string &msg)
-{
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(KG_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));         \
-    } while (0)
-
-// Device-memory cache of one table object.  Every scan ends with a stream synchronisation, and
-// blocks are handed back only when the stream is idle, so a freed block can be reused by the next
-// request without any ordering concern.  Keeps the working set of repeated scans resident in HBM
-// (no hipMalloc/hipFree in the steady state).
-struct DevCache {
-    std::mutex mu;
-    std::multimap<size_t, void *> free_;
-    std::unordered_map<void *, size_t> live;
-
-    static size_t round_up(size_t b)
-    {
-        if (b < 256) return 256;
-        size_t g = b >= (8u << 20) ? (2u << 20) : 256;       // 2 MiB granules for large blocks
-        return (b + g - 1) / g * g;
-    }
-    hipError_t get(void **p, size_t bytes)
-    {
-        bytes = round_up(bytes);
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = free_.lower_bound(bytes);
-        if (it != free_.end() && it->first <= bytes + bytes / 2 + (1u << 20)) {
-            *p = it->second;
-            live[*p] = it->first;
-            free_.erase(it);
-            return hipSuccess;
-        }
-        hipError_t e = hipMalloc(p, bytes);
-        if (e != hipSuccess) {
-            // give cached blocks back to the driver and retry once
-            for (auto &kv : free_) (void)hipFree(kv.second);
-            free_.clear();
-            e = hipMalloc(p, bytes);
-            if (e != hipSuccess) return e;
-        }
-        live[*p] = bytes;
-        return hipSuccess;
-    }
-    void put(void *p)
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = live.find(p);
-        if (it == live.end()) return;
-        free_.emplace(it->second, p);
-        live.erase(it);
-    }
-    // hand a live block over to its user for good (kg_table_build: the table's records, freed with hipFree by kg_table_close)
-    void detach(void *p)
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        live.erase(p);
-    }
-    size_t live_bytes()
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        size_t n = 0;
-        for (auto &kv : live) n += kv.second;
-        return n;
-    }
-    void release_all()
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        for (auto &kv : free_) (void)hipFree(kv.second);
-        for (auto &kv : live) (void)hipFree(kv.first);
-        free_.clear();
-        live.clear();
-    }
-    // the cached blocks back to the driver, the live ones kept (kg_regions_calls: the set keeps its context, not the scratch)
-    void release_free()
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        for (auto &kv : free_) (void)hipFree(kv.second);
-        free_.clear();
-    }
-};
-
-// Pinned host blocks for the result views.  hipHostMalloc / hipHostFree cost ~0.1-0.2 ms for a small block (more than
-// a small scan) and ~0.5 s for the 880 MB of hit records of a 1 Gbp batch (page pinning: the copy itself takes 20 ms at
-// PCIe rate), so blocks are kept for the next result: up to kKeepTotal bytes, largest dropped first.
-struct PinCache {
-    std::mutex mu;
-    std::multimap<size_t, void *> free_;
-    std::unordered_map<void *, size_t> live;
-    size_t kept = 0;
-    static constexpr size_t kKeepTotal = 6ull << 30;
-
-    hipError_t get(void **p, size_t bytes)
-    {
-        bytes = bytes < 4096 ? 4096 : (bytes + 4095) / 4096 * 4096;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            auto it = free_.lower_bound(bytes);
-            if (it != free_.end() && it->first <= 2 * bytes + (1u << 16)) {
-                *p = it->second;
-                live[*p] = it->first;
-                kept -= it->first;
-                free_.erase(it);
-                return hipSuccess;
-            }
-        }
-        hipError_t e = hipHostMalloc(p, bytes);
-        if (e != hipSuccess) return e;
-        std::lock_guard<std::mutex> lk(mu);
-        live[*p] = bytes;
-        return hipSuccess;
-    }
-    void put(void *p)
-    {
-        std::vector<void *> drop;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            auto it = live.find(p);
-            if (it == live.end()) return;
-            const size_t bytes = it->second;
-            live.erase(it);
-            free_.emplace(bytes, p);
-            kept += bytes;
-            while (kept > kKeepTotal && !free_.empty()) {          // largest first
-                auto big = std::prev(free_.end());
-                kept -= big->first;
-                drop.push_back(big->second);
-                free_.erase(big);
-            }
-        }
-        for (void *d : drop) (void)hipHostFree(d);
-    }
-    void release_all()
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        for (auto &kv : free_) (void)hipHostFree(kv.second);
-        for (auto &kv : live) (void)hipHostFree(kv.first);
-        free_.clear();
-        live.clear();
-        kept = 0;
-    }
-};
-
-}  // namespace
-
-constexpr uint64_t kHbitsMaxSlots = 1ull << 26;     // tables up to this many slots get the bit-per-slot digest (8 MB of bits)
-
-// ---- names for the numbered slots a scan uses: events, pinned words, device counter words ----
-constexpr uint32_t kMaxChunks = 8;          // chunks of a partitioned scan (KG_PART_CHUNKS)
-constexpr uint32_t kMaxOrderStreams = 4;    // KG_ORDER_STREAMS
-// kg_table::pev, the edges between the streams of a partitioned scan
-enum : int {
-    kPevChunk = 0,                      // [+ 2c] chunk c scattered, [+ 2c + 1] chunk c tag-probed
-    kPevFork = 16,                      // the attempt's clears are enqueued: stream2 and stream3 start behind them
-    kPevJoin2 = 17, kPevJoin3 = 18,     // everything of the attempt on stream2 / stream3
-    kPevTotals = 19,                    // the early totals are in their pinned words
-    kPevVerified = 20,                  // [+ c] chunk c verified
-    kPevBase = 32,                      // [+ c] ordering streams: chunk c's total is known (the base of chunk c + 1 follows)
-    kPevOrdered = 40,                   // [+ k] everything of the attempt on ordering stream k
-    kPevCount = 48
-};
-static_assert(kPevChunk + 2 * kMaxChunks <= kPevFork && kPevVerified + kMaxChunks <= kPevBase && kPevBase + kMaxChunks <= kPevOrdered &&
-              kPevOrdered + kMaxOrderStreams <= kPevCount, "event slots overlap");
-// kg_table::ev, the timing events of a scan (outside a scan they are free: kg_result_copy_hits, assign_impl)
-enum : int { kEvBegin = 0, kEvScanBegin = 1, kEvScanEnd = 2, kEvOrderEnd = 3, kEvAggEnd = 4, kEvScattered = 5 /* all chunks */, kEvSpare = 6,
-             kEvJoined = 7 /* stream2 and stream3 joined */, kEvCount = 8 };
-// d_totals, the counter words of a scan
-enum : int { kTotHits = 0, kTotCursor = 1 /* staging records asked for */, kTotValid = 2, kTotSlots = 3 /* windows / slots counted */,
-             kTotCalls = 4, kTotRanOff = 5 /* a lookup ran off the stream (sticky) */, kTotPieces = 6, kTotVoters = 7, kTotWords = 8,
-             kTotSent = 6 /* the first words: what the host reads back per attempt */ };
-// d_pc, the per-chunk words of a partitioned scan; [kPcBase + n_chunks] = all hits
-enum : int { kPcUcur = 0 /* [+ c] hit-list cursors */, kPcCcur = 8 /* candidate cursors */, kPcBase = 16 /* first hit record */,
-             kPcCtot = 32 /* hit totals */, kPcWords = 48 };
-static_assert(kPcUcur + kMaxChunks <= kPcCcur && kPcCcur + kMaxChunks <= kPcBase && kPcBase + kMaxChunks + 1 <= kPcCtot &&
-              kPcCtot + kMaxChunks <= kPcWords, "per-chunk words overlap");
-// d_ovfc, 32-bit words per chunk
-enum : int { kOvfGroups = 0 /* overflow groups */, kOvfLowc = 1 /* low-complexity blocks set aside */, kOvfGuard = 2 /* spin guard fired */,
-             kOvfWords = 8 };
-// kg_table::h_pin, pinned host words for the few counters a call reads back (a hipMemcpyAsync to pageable memory blocks the
-// host per copy; to pinned memory it does not)
-enum : int { kPinPc = 0 /* d_pc */, kPinOvf = 48 /* d_ovfc */, kPinTotals = 80 /* d_totals[0 .. kTotSent) */, kPinCalls = 88 /* CALL total */,
-             kPinPieces = 89, /* 90 .. 94: kPinAssign */ kPinWords = 96 };
-static_assert(kPinPc + kPcWords <= kPinOvf && kOvfWords * kMaxChunks * 4 <= (kPinTotals - kPinOvf) * 8 && kPinTotals + kTotSent <= kPinCalls,
-              "counters must fit their pinned words");
-
-struct kg_table {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;      // partitioned scan: tag pass of chunk c while chunk c+1 is scattered (stream)
-    hipStream_t stream3 = nullptr;      // ... and while chunk c-1 is verified and placed
-    hipStream_t ostream[kMaxOrderStreams] = {};   // ordering streams (KG_ORDER_STREAMS), lowest priority: queues of their own
-    hipEvent_t pev[kPevCount] = {};     // kPev*
-    bool own_entries = false;
-    uint8_t *d_entries = nullptr;
-    uint8_t *d_tags = nullptr;
-    uint8_t *d_bidx = nullptr;          // byte home index (kg_device.hpp, build_bidx_kernel): 1 byte per slot, limit + 64 bytes
-    bool bidx_exact = false;            // every quotient < 19: its classes are quotients
-    uint32_t *d_hbits = nullptr;        // one bit per slot: the byte above is not 0 (tables of at most kHbitsMaxSlots slots: the direct kernel's prefilter)
-    uint64_t tail_start = 0;            // first slot of the occupied run that ends at the end of the record stream
-    int64_t num_sigs = 0, entry_size = 0, version = 0;
-    uint64_t limit = 0;          // complete 24-byte records present
-    uint64_t magic = 0;          // floor(2^64 / num_sigs)
-    uint32_t m35 = 0;            // floor(2^35 / num_sigs) when 64 <= num_sigs < 2^31 (kg::split_fast), else 0
-    uint64_t occupied = 0;
-    double stage_ratio = 1.0 / 16;   // staging records per window, grown to the high-water mark
-    size_t scatter_lds[2] = {0, 0};  // dynamic LDS the scatter kernel (DNA / protein) has been allowed so far
-    size_t hist_lds = 48 * 1024;     // ... and the hit histogram kernel (kg_order.hpp)
-    size_t place_lds[2] = {48 * 1024, 48 * 1024};   // ... and group_place_kernel<DNA / AA>
-    hipEvent_t ev[kEvCount] = {};       // kEv*
-    uint64_t *h_pin = nullptr;          // kPin*
-    std::atomic<int> busy{0};    // a kg_scan* is in flight on this table (its streams, events and pinned words are per table)
-    uint32_t fail_alloc_at = 0, alloc_count = 0;   // test hook KG_TEST_FAIL_ALLOC (include/kmerguts_hip.h)
-    DevCache cache;
-    PinCache pins;
-};
-
-struct kg_result {
-    kg_table *tab = nullptr;
-    bool own_tab = false;        // kg_aggregate_hits: the result owns a table-less context (stream + block caches)
-    kg_stats st = {};
-    uint32_t per = 6;
-    // device
-    kg_hit *d_hits = nullptr;
-    int64_t *d_chs = nullptr;
-    kg_call *d_calls = nullptr;
-    int64_t *d_ccs = nullptr;
-    kg_otu *d_otu = nullptr;
-    uint8_t *d_ev = nullptr, *d_tail_ev = nullptr;   // KG_EV_* per hit / per container
-    uint32_t *d_hit_slots = nullptr;                 // KG_F_PROGRESS: the slot every hit was found at
-    bool has_progress = false;
-    kg_progress progress = {};
-    // host copies (lazy), in pinned memory so the copy runs at PCIe rate
-    void *h_hits = nullptr, *h_chs = nullptr, *h_ccs = nullptr, *h_calls = nullptr, *h_otu = nullptr, *h_ev = nullptr,
-         *h_tail_ev = nullptr, *h_hit_slots = nullptr;
-};
-
-namespace {
-
-uint32_t env_u32(const char *name, uint32_t dflt)
-{
-    const char *v = getenv(name);
-    if (!v || !*v) return dflt;
-    char *end = nullptr;
-    long x = strtol(v, &end, 10);
-    return (end != v && x >= 0) ? (uint32_t)x : dflt;
-}
-
-constexpr uint32_t kMaxGrid = 256u * 32u;      // the most workgroups a geometry knob asks for (the defaults: 256 .. 2048)
-
-// A geometry knob (tuning aid): env_u32 held to [lo, hi], the range its kernels run with, and rounded up to a multiple of
-// `mult` (ticketed grids: one hand-out counter per eight workgroups).  0, a value below lo or one beyond 2^32 become a
-// legal geometry instead of an empty launch, a division by zero or a wrapped shift.
-uint32_t env_knob(const char *name, uint32_t dflt, uint32_t lo, uint32_t hi, uint32_t mult = 1)
-{
-    uint32_t x = dflt;
-    if (const char *v = getenv(name); v && *v) {
-        char *end = nullptr;
-        const long long y = strtoll(v, &end, 10);
-        if (end != v && y >= 0) x = y > (long long)hi ? hi : (uint32_t)y;
-    }
-    x = std::min(hi, std::max(lo, x));
-    return (x + mult - 1) / mult * mult;
-}
-
-// The two test hooks (KG_TEST_TINY_LISTS, KG_TEST_FAIL_ALLOC; include/kmerguts_hip.h) are read only when the process opted in
-// with KG_ENABLE_TEST_HOOKS=1 -- looked at ONCE, at the first scan: a stray KG_TEST_* variable in a server's environment
-// does nothing.
-uint32_t test_hook(const char *name)
-{
-    static const bool enabled = env_u32("KG_ENABLE_TEST_HOOKS", 0u) != 0;
-    return enabled ? env_u32(name, 0u) : 0u;
-}
-
-int dalloc(kg_table *t, void **p, size_t bytes)
-{
-    if (t->fail_alloc_at && ++t->alloc_count == t->fail_alloc_at)
-        return fail(KG_ERR_NOMEM, "device allocation failed: KG_TEST_FAIL_ALLOC test hook");
-    hipError_t e = t->cache.get(p, bytes);
-    if (e != hipSuccess) return fail(KG_ERR_NOMEM, std::string("device allocation failed: ") + hipGetErrorString(e));
-    return KG_OK;
-}
-
-// Only call while the table's stream is idle (see DevCache).
-void dfree(kg_table *t, void *p)
-{
-    if (p) t->cache.put(p);
-}
 
 int table_finish(kg_table *t)
 {
@@ -680,44 +374,6 @@ void kg_result_free(kg_result *r)
 }  // extern "C"
 
 namespace {
-
-// exclusive prefix sum of d_in[n] -> d_out[n], total -> d_total (device uint64)
-int prefix_sum(kg_table *t, const uint32_t *d_in, uint64_t n, uint32_t *d_out, uint64_t *d_partial, uint64_t *d_total,
-               hipStream_t stream = nullptr)
-{
-    if (!stream) stream = t->stream;
-    uint32_t nb = (uint32_t)((n + kg::kScanChunk - 1) / kg::kScanChunk);
-    if (nb == 0) nb = 1;
-    hipLaunchKernelGGL(kg::scan_partials_kernel, dim3(nb), dim3(kg::kScanThreads), 0, stream, d_in, n, d_partial);
-    hipLaunchKernelGGL(kg::scan_top_kernel, dim3(1), dim3(kg::kScanThreads), 0, stream, d_partial, nb, d_total);
-    hipLaunchKernelGGL(kg::scan_final_kernel, dim3(nb), dim3(kg::kScanThreads), 0, stream, d_in, n, d_partial, d_out);
-    HIP_TRY(hipGetLastError());
-    return KG_OK;
-}
-
-struct Scratch {
-    kg_table *t;
-    std::vector<void *> ptrs;
-    explicit Scratch(kg_table *tt) : t(tt) {}
-    ~Scratch()
-    {
-        (void)hipStreamSynchronize(t->stream);      // blocks go back to the cache only when both streams are idle
-        if (t->stream2) (void)hipStreamSynchronize(t->stream2);
-        if (t->stream3) (void)hipStreamSynchronize(t->stream3);
-        for (auto &os : t->ostream) if (os) (void)hipStreamSynchronize(os);
-        for (void *p : ptrs) dfree(t, p);
-    }
-    void adopt(void *p) { ptrs.push_back(p); }
-    template <typename T> int get(T **p, size_t count)
-    {
-        void *v = nullptr;
-        int rc = dalloc(t, &v, count * sizeof(T));
-        if (rc) return rc;
-        ptrs.push_back(v);
-        *p = (T *)v;
-        return KG_OK;
-    }
-};
 
 // gatherHits / processSetOfHits / the OTU buffer (KGJ:385-524) over res->d_hits + res->d_chs: fills the CALL, OTU and event
 // arrays of res.  d_partial: prefix-sum scratch for n_cont items, d_totals: the counter words (kTotCalls: the CALL total).
@@ -1740,13 +1396,9 @@ int scan_entry(kg_table *t, const kg_params *p, const uint8_t *seq, bool on_devi
         return fail(KG_ERR_UNSUPPORTED, "minHits < 2: the reference throws in processSetOfHits (KGJ:442); refusing");
     // One scan at a time per table: the streams, events, pinned counter words and the block cache's "freed when the
     // stream is idle" rule are per table.  A second thread is turned away instead of corrupting them.
-    if (t->busy.exchange(1) != 0)
-        return fail(KG_ERR_BUSY, "another kg_scan* is in flight on this kg_table (one scan at a time per table; open a second table "
-                                 "object for concurrent scans)");
-    struct BusyGuard { kg_table *t; ~BusyGuard() { t->busy.store(0); } } busy_guard{t};
-    t->fail_alloc_at = test_hook("KG_TEST_FAIL_ALLOC");
-    t->alloc_count = 0;
-    HIP_TRY(hipSetDevice(t->device));
+    CallScope cs(t, "another kg_scan* is in flight on this kg_table (one scan at a time per table; open a second table "
+                    "object for concurrent scans)");
+    if (cs.rc) return cs.rc;
     int64_t total = offsets[n_seqs] - offsets[0];
     if (total < 0) return fail(KG_ERR_ARG, "offsets must be non-decreasing");
     if (!seq && total > 0) return fail(KG_ERR_ARG, "null sequence buffer");
@@ -1766,13 +1418,35 @@ int scan_entry(kg_table *t, const kg_params *p, const uint8_t *seq, bool on_devi
     }
     (void)hipStreamSynchronize(t->stream);
     if (d_seq) dfree(t, d_seq);
-    if (rc != KG_OK) {
-        std::string keep = g_err;
-        kg_result_free(r);
-        g_err = keep;
-        return rc;
-    }
+    if (rc != KG_OK) return fail_and_free(r, rc);
     *out = r;
+    return KG_OK;
+}
+
+// kg_aggregate_hits on its context t: the caller's records into r, the aggregation, r's statistics
+int aggregate_records(kg_table *t, const kg_params *p, const kg_hit *hits, const int64_t *container_hit_start, int64_t n_seqs,
+                      const kg_otu *otu_init, kg_result *r)
+{
+    const uint64_t n_cont = (uint64_t)n_seqs * r->per, n_hits = (uint64_t)container_hit_start[n_cont];
+    Scratch sc(t);
+    int rc;
+    uint64_t *d_partial = nullptr, *d_totals = nullptr;
+    kg_otu *d_init = nullptr;
+    if ((rc = dalloc(t, (void **)&r->d_hits, (n_hits ? n_hits : 1) * sizeof(kg_hit)))) return rc;
+    if ((rc = dalloc(t, (void **)&r->d_chs, (n_cont + 1) * 8))) return rc;
+    if ((rc = sc.get(&d_partial, (size_t)(n_cont / kg::kScanChunk + 2)))) return rc;
+    if ((rc = sc.get(&d_totals, 8))) return rc;
+    if (otu_init && n_seqs && (rc = sc.get(&d_init, (size_t)n_seqs))) return rc;
+    HIP_TRY(hipMemsetAsync(d_totals, 0, 64, t->stream));
+    if (n_hits) HIP_TRY(hipMemcpyAsync(r->d_hits, hits, n_hits * sizeof(kg_hit), hipMemcpyHostToDevice, t->stream));
+    HIP_TRY(hipMemcpyAsync(r->d_chs, container_hit_start, (n_cont + 1) * 8, hipMemcpyHostToDevice, t->stream));
+    if (d_init) HIP_TRY(hipMemcpyAsync(d_init, otu_init, (size_t)n_seqs * sizeof(kg_otu), hipMemcpyHostToDevice, t->stream));
+    // (caller-supplied records: positions are whatever the caller says, so long containers stay in one piece)
+    if ((rc = aggregate_stage(t, p, r, sc, n_seqs, n_cont, n_hits, r->per, d_partial, d_totals, d_init, false))) return rc;
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    r->st.n_seqs = n_seqs; r->st.n_containers = (int64_t)n_cont; r->st.n_hits = (int64_t)n_hits;
+    r->st.n_calls = (int64_t)t->h_pin[kPinCalls];
+    r->st.windows_valid = -1; r->st.slots_inspected = -1;
     return KG_OK;
 }
 
@@ -1791,6 +1465,24 @@ const T *host_view(kg_result *r, void *&slot, const T *d, size_t n)
     }
     slot = h;
     return (const T *)h;
+}
+
+// kg_table_save: all of p[n] into the file, plain or gzip
+bool write_all(int fd, gzFile g, const uint8_t *p, size_t n)
+{
+    while (n) {
+        const size_t piece = std::min<size_t>(n, 1u << 30);
+        long got;
+        if (g) got = gzwrite(g, p, (unsigned)piece);
+        else got = (long)write(fd, p, piece);
+        if (got <= 0) {
+            if (!g && got < 0 && errno == EINTR) continue;
+            return false;
+        }
+        p += got;
+        n -= (size_t)got;
+    }
+    return true;
 }
 
 }  // namespace
@@ -1823,35 +1515,14 @@ int kg_aggregate_hits(int device, const kg_params *p, const kg_hit *hits, const 
     const uint64_t n_hits = (uint64_t)container_hit_start[n_cont];
     if (n_hits && !hits) return fail(KG_ERR_ARG, "null hit records");
     if (n_hits > 0xFFFFFF00ull) return fail(KG_ERR_LIMIT, "more than 2^32-256 hit records");
-    kg_table *t = nullptr;
-    int rc = table_new(device, &t);
-    if (rc) return rc;
+    CallScope cs(device, /* hook = */ false);          // (this call has never armed KG_TEST_FAIL_ALLOC)
+    if (cs.rc) return cs.rc;
     kg_result *r = new (std::nothrow) kg_result();
-    if (!r) { kg_table_close(t); return fail(KG_ERR_NOMEM, "out of host memory"); }
-    r->tab = t; r->own_tab = true; r->per = PER;
-    rc = [&]() -> int {                 // (the scratch blocks go back to the context's cache before the context can be closed)
-        Scratch sc(t);
-        int rc2;
-        uint64_t *d_partial = nullptr, *d_totals = nullptr;
-        kg_otu *d_init = nullptr;
-        if ((rc2 = dalloc(t, (void **)&r->d_hits, (n_hits ? n_hits : 1) * sizeof(kg_hit)))) return rc2;
-        if ((rc2 = dalloc(t, (void **)&r->d_chs, (n_cont + 1) * 8))) return rc2;
-        if ((rc2 = sc.get(&d_partial, (size_t)(n_cont / kg::kScanChunk + 2)))) return rc2;
-        if ((rc2 = sc.get(&d_totals, 8))) return rc2;
-        if (otu_init && n_seqs && (rc2 = sc.get(&d_init, (size_t)n_seqs))) return rc2;
-        HIP_TRY(hipMemsetAsync(d_totals, 0, 64, t->stream));
-        if (n_hits) HIP_TRY(hipMemcpyAsync(r->d_hits, hits, n_hits * sizeof(kg_hit), hipMemcpyHostToDevice, t->stream));
-        HIP_TRY(hipMemcpyAsync(r->d_chs, container_hit_start, (n_cont + 1) * 8, hipMemcpyHostToDevice, t->stream));
-        if (d_init) HIP_TRY(hipMemcpyAsync(d_init, otu_init, (size_t)n_seqs * sizeof(kg_otu), hipMemcpyHostToDevice, t->stream));
-        // (caller-supplied records: positions are whatever the caller says, so long containers stay in one piece)
-        if ((rc2 = aggregate_stage(t, p, r, sc, n_seqs, n_cont, n_hits, PER, d_partial, d_totals, d_init, false))) return rc2;
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        r->st.n_seqs = n_seqs; r->st.n_containers = (int64_t)n_cont; r->st.n_hits = (int64_t)n_hits;
-        r->st.n_calls = (int64_t)t->h_pin[kPinCalls];
-        r->st.windows_valid = -1; r->st.slots_inspected = -1;
-        return KG_OK;
-    }();
-    if (rc != KG_OK) { std::string keep = g_err; kg_result_free(r); g_err = keep; return rc; }
+    if (!r) return fail(KG_ERR_NOMEM, "out of host memory");
+    r->tab = cs.t; r->per = PER;
+    if (const int rc = aggregate_records(cs.t, p, hits, container_hit_start, n_seqs, otu_init, r)) return fail_and_free(r, rc);
+    r->own_tab = true;                  // the result keeps the context
+    cs.disown();
     *out = r;
     return KG_OK;
 }
@@ -2028,269 +1699,15 @@ const void *kg_result_device_otu(const kg_result *r) { return r ? r->d_otu : nul
 const void *kg_result_device_container_hit_start(const kg_result *r) { return r ? r->d_chs : nullptr; }
 const void *kg_result_device_container_call_start(const kg_result *r) { return r ? r->d_ccs : nullptr; }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// kg_table_build / kg_table_build_device / kg_table_save: a signature list -> a resident table (kernels: kg_build.hpp), and a
-// resident table -> kmer.table.mem_map[.gz].
-namespace {
-
-uint64_t magic_of(uint64_t d)
-{
-    return d == 1 ? ~0ull : (uint64_t)(((unsigned __int128)1 << 64) / d);
-}
-
-std::string kmer_text(int64_t v)
-{
-    char b[32];
-    snprintf(b, sizeof b, "%lld", (long long)v);
-    return b;
-}
-
-// Host signatures -> d_dst (n * 24 bytes) through pinned pieces: several threads copy disjoint 32 MiB pieces of the caller's
-// (possibly pageable) buffer into two pinned buffers each and hand them to the copy engine, as kg_table_open does.
-int upload_signatures(kg_table *t, const uint8_t *src, size_t bytes, uint8_t *d_dst)
-{
-    const size_t CH = 32u << 20;
-    const size_t n_pieces = (bytes + CH - 1) / CH;
-    const unsigned hw = std::thread::hardware_concurrency();
-    const size_t n_thr = std::max<size_t>(1, std::min<size_t>({(size_t)8, (size_t)(hw ? hw : 4), n_pieces}));
-    std::atomic<size_t> next{0};
-    std::atomic<bool> ok{true};
-    auto worker = [&]() {
-        if (hipSetDevice(t->device) != hipSuccess) { ok = false; return; }
-        hipStream_t s = nullptr;
-        uint8_t *pin[2] = {nullptr, nullptr};
-        hipEvent_t done[2] = {nullptr, nullptr};
-        bool good = hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess &&
-                    hipHostMalloc((void **)&pin[0], CH) == hipSuccess && hipHostMalloc((void **)&pin[1], CH) == hipSuccess &&
-                    hipEventCreate(&done[0]) == hipSuccess && hipEventCreate(&done[1]) == hipSuccess;
-        bool used[2] = {false, false};
-        int which = 0;
-        while (good && ok.load()) {
-            const size_t k = next.fetch_add(1);
-            if (k >= n_pieces) break;
-            const size_t at = k * CH, n = std::min(CH, bytes - at);
-            if (used[which]) good = hipEventSynchronize(done[which]) == hipSuccess;
-            if (!good) break;
-            memcpy(pin[which], src + at, n);
-            good = hipMemcpyAsync(d_dst + at, pin[which], n, hipMemcpyHostToDevice, s) == hipSuccess &&
-                   hipEventRecord(done[which], s) == hipSuccess;
-            used[which] = true;
-            which ^= 1;
-        }
-        if (s && hipStreamSynchronize(s) != hipSuccess) good = false;
-        if (!good) ok = false;
-        for (int i = 0; i < 2; i++) { if (pin[i]) (void)hipHostFree(pin[i]); if (done[i]) (void)hipEventDestroy(done[i]); }
-        if (s) (void)hipStreamDestroy(s);
-    };
-    {
-        std::vector<std::thread> pool;
-        for (size_t i = 1; i < n_thr; i++) pool.emplace_back(worker);
-        worker();
-        for (auto &th : pool) th.join();
-    }
-    return ok.load() ? KG_OK : fail(KG_ERR_DEVICE, "uploading the signatures failed (pinned staging or host-to-device copy)");
-}
-
-// Stable LSD radix sort (kg_build.hpp: build_hist_kernel / prefix_sum / build_scatter_kernel, <= 8 bits a pass) of the n > 1
-// pairs (keys[0], vals[0]) by their low key_bits key bits; keys[1] / vals[1] come from sc.  *cur: the buffer that holds the result.
-int radix_sort(kg_table *t, Scratch &sc, uint64_t *keys[2], uint32_t *vals[2], uint64_t n, uint32_t key_bits, int *cur)
-{
-    const uint32_t n_tiles = (uint32_t)((n + kg::kBuildTile - 1) / kg::kBuildTile);
-    const uint32_t passes = (key_bits + 7) / 8, bits = passes ? (key_bits + passes - 1) / passes : 1, radix = 1u << bits;
-    const uint64_t n_hist = (uint64_t)radix * n_tiles;
-    const uint64_t nb = (n_hist + kg::kScanChunk - 1) / kg::kScanChunk;
-    uint32_t *hist = nullptr, *offs = nullptr;
-    uint64_t *partial = nullptr;
-    int rc;
-    if ((rc = sc.get(&keys[1], n)) || (rc = sc.get(&vals[1], n)) || (rc = sc.get(&hist, n_hist)) ||
-        (rc = sc.get(&offs, n_hist)) || (rc = sc.get(&partial, nb + 2)))
-        return rc;
-    for (uint32_t p = 0; p < passes; p++) {
-        const uint32_t shift = p * bits;
-        hipLaunchKernelGGL(kg::build_hist_kernel, dim3(n_tiles), dim3(kg::kBuildThreads), 0, t->stream, keys[*cur], n, shift, radix,
-                           n_tiles, hist);
-        HIP_TRY(hipGetLastError());
-        if ((rc = prefix_sum(t, hist, n_hist, offs, partial, partial + nb + 1))) return rc;
-        hipLaunchKernelGGL(kg::build_scatter_kernel, dim3(n_tiles), dim3(kg::kBuildThreads), 0, t->stream, keys[*cur], vals[*cur], n,
-                           shift, bits, n_tiles, offs, keys[*cur ^ 1], vals[*cur ^ 1]);
-        HIP_TRY(hipGetLastError());
-        *cur ^= 1;
-    }
-    return KG_OK;
-}
-
-// Everything up to table_finish.  Scratch comes from the table's block cache (dalloc: KG_TEST_FAIL_ALLOC applies) and is
-// back in it when this returns; the records are taken out of the cache and owned by the table.
-int build_records(kg_table *t, const uint8_t *h_sigs, const uint8_t *d_sigs, uint64_t n, uint64_t *n_placed, float ms[4])
-{
-    const uint64_t S = (uint64_t)t->num_sigs;
-    Scratch sc(t);
-    {
-        void *e = nullptr;
-        int rc = dalloc(t, &e, (S * 24 + 15) / 16 * 16);
-        if (rc) return rc;
-        t->cache.detach(e);
-        t->d_entries = (uint8_t *)e;
-        t->own_entries = true;
-    }
-    int rc;
-    if (h_sigs && n) {
-        uint8_t *d = nullptr;
-        if ((rc = sc.get(&d, n * 24))) return rc;
-        if ((rc = upload_signatures(t, h_sigs, n * 24, d))) return rc;
-        d_sigs = d;
-    }
-    hipEvent_t ev[5];
-    for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 5; i++) (void)hipEventDestroy(e[i]); } } ev_guard{ev};
-    // (home, kmer) order == (home, q) order; c = home * Q + q < 20^8 + S
-    const uint64_t Q = (uint64_t)(KG_MAX_ENCODED - 1) / S + 1, magic = magic_of(S), magic_q = magic_of(Q);
-    const uint64_t c_max = (uint64_t)((unsigned __int128)S * Q - 1);
-    uint32_t key_bits = 1;
-    while (key_bits < 64 && (c_max >> key_bits) != 0) key_bits++;
-    const uint32_t n_tiles = (uint32_t)((n + kg::kBuildTile - 1) / kg::kBuildTile);
-    unsigned long long *d_cnt = nullptr;                // [0] first bad index, [1] smallest duplicate, [2] placed
-    if ((rc = sc.get(&d_cnt, 4))) return rc;
-    HIP_TRY(hipMemsetAsync(d_cnt, 0xFF, 16, t->stream));
-    HIP_TRY(hipMemsetAsync(d_cnt + 2, 0, 8, t->stream));
-    HIP_TRY(hipEventRecord(ev[0], t->stream));
-    uint64_t *keys[2] = {nullptr, nullptr};
-    uint32_t *vals[2] = {nullptr, nullptr};
-    int cur = 0;
-    if (n) {
-        if ((rc = sc.get(&keys[0], n)) || (rc = sc.get(&vals[0], n))) return rc;
-        const uint64_t want = (n + kg::kBuildThreads - 1) / kg::kBuildThreads;
-        hipLaunchKernelGGL(kg::build_keys_kernel, dim3((uint32_t)std::min<uint64_t>(want, 256ull * 32)), dim3(kg::kBuildThreads), 0,
-                           t->stream, d_sigs, n, S, magic, Q, keys[0], vals[0], d_cnt);
-        HIP_TRY(hipGetLastError());
-        unsigned long long bad = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, d_cnt, 8, hipMemcpyDeviceToHost, t->stream));
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        if (bad != ~0ull) {
-            int64_t kmer = 0;
-            if (h_sigs) memcpy(&kmer, h_sigs + bad * 24, 8);
-            else HIP_TRY(hipMemcpy(&kmer, d_sigs + bad * 24, 8, hipMemcpyDeviceToHost));
-            return fail(KG_ERR_ARG, "signature " + kmer_text((int64_t)bad) + ": k-mer " + kmer_text(kmer) +
-                                        " is outside [0, 20^8) (the smallest such input index)");
-        }
-        if (n > 1 && (rc = radix_sort(t, sc, keys, vals, n, key_bits, &cur))) return rc;
-    }
-    HIP_TRY(hipEventRecord(ev[1], t->stream));
-    int64_t *tile_max = nullptr, *tile_pre = nullptr;
-    if (n) {
-        if ((rc = sc.get(&tile_max, n_tiles)) || (rc = sc.get(&tile_pre, n_tiles))) return rc;
-        hipLaunchKernelGGL(kg::build_tile_max_kernel, dim3(n_tiles), dim3(kg::kBuildThreads), 0, t->stream, keys[cur], n, Q, magic_q, S,
-                           tile_max, d_cnt + 1);
-        hipLaunchKernelGGL(kg::build_tile_scan_kernel, dim3(1), dim3(kg::kBuildThreads), 0, t->stream, tile_max, n_tiles, tile_pre);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(ev[2], t->stream));
-    const uint64_t n_chunks = (S * 24 + 15) / 16;
-    hipLaunchKernelGGL(kg::build_fill_kernel, dim3((uint32_t)std::min<uint64_t>((n_chunks + 255) / 256, 256ull * 64)),
-                       dim3(kg::kBuildThreads), 0, t->stream, (uint4 *)t->d_entries, n_chunks);
-    HIP_TRY(hipGetLastError());
-    if (n) {
-        hipLaunchKernelGGL(kg::build_place_kernel, dim3(n_tiles), dim3(kg::kBuildThreads), 0, t->stream, keys[cur], vals[cur], n, Q,
-                           magic_q, tile_pre, d_sigs, S, t->d_entries, d_cnt + 2);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(ev[3], t->stream));
-    unsigned long long cnt[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(cnt, d_cnt, 24, hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    if (cnt[1] != ~0ull)
-        return fail(KG_ERR_ARG, "duplicate k-mer " + kmer_text((int64_t)cnt[1]) + " (the smallest k-mer that occurs more than once)");
-    for (int i = 0; i < 3; i++) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
-    *n_placed = cnt[2];
-    return KG_OK;
-}
-
-int build_entry(const uint8_t *h_sigs, const uint8_t *d_sigs, int64_t n, int64_t num_sigs, int device, int64_t *n_placed, kg_table **out)
-{
-    if (!out) return fail(KG_ERR_ARG, "null argument");
-    *out = nullptr;
-    if (n < 0) return fail(KG_ERR_ARG, "n < 0");
-    if (num_sigs <= 0) return fail(KG_ERR_ARG, "num_sigs <= 0");
-    if ((uint64_t)n >= (1ull << 32)) return fail(KG_ERR_LIMIT, "kg_table_build: 2^32 or more signatures in one call");
-    if (n > 0 && !h_sigs && !d_sigs) return fail(KG_ERR_ARG, "null signature array");
-    if (d_sigs && ((uintptr_t)d_sigs & 7)) return fail(KG_ERR_ARG, "kg_table_build_device: the signatures must be 8-byte aligned");
-    if ((uint64_t)num_sigs > (~0ull >> 1) / 24) return fail(KG_ERR_LIMIT, "num_sigs too large");
-    kg_table *t = nullptr;
-    int rc = table_new(device, &t);
-    if (rc) return rc;
-    t->num_sigs = num_sigs;
-    t->entry_size = KG_TABLE_ENTRY_SIZE;
-    t->version = 1;
-    t->limit = (uint64_t)num_sigs;
-    t->fail_alloc_at = test_hook("KG_TEST_FAIL_ALLOC");
-    t->alloc_count = 0;
-    // a device input may still be written by another (blocking or non-blocking) stream
-    if (d_sigs && hipDeviceSynchronize() != hipSuccess) { kg_table_close(t); return fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed"); }
-    uint64_t placed = 0;
-    float ms[5] = {0, 0, 0, 0, 0};
-    rc = build_records(t, h_sigs, d_sigs, (uint64_t)n, &placed, ms);
-    t->fail_alloc_at = 0;
-    t->cache.release_all();                             // the build's scratch goes back to the driver, not to the table
-    if (rc) { kg_table_close(t); return rc; }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timed = getenv("KG_DEBUG") && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess &&
-                       hipEventRecord(e0, t->stream) == hipSuccess;
-    rc = table_finish(t);
-    if (timed && rc == KG_OK && hipEventRecord(e1, t->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess)
-        (void)hipEventElapsedTime(&ms[3], e0, e1);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (rc) { kg_table_close(t); return rc; }
-    if (getenv("KG_DEBUG"))
-        fprintf(stderr, "[kg] kg_table_build: n=%lld num_sigs=%lld placed=%llu sort_ms=%.3f place_ms=%.3f fill_scatter_ms=%.3f finish_ms=%.3f\n",
-                (long long)n, (long long)num_sigs, (unsigned long long)placed, ms[0], ms[1], ms[2], ms[3]);
-    if (n_placed) *n_placed = (int64_t)placed;
-    *out = t;
-    return KG_OK;
-}
-
-bool write_all(int fd, gzFile g, const uint8_t *p, size_t n)
-{
-    while (n) {
-        const size_t piece = std::min<size_t>(n, 1u << 30);
-        long got;
-        if (g) got = gzwrite(g, p, (unsigned)piece);
-        else got = (long)write(fd, p, piece);
-        if (got <= 0) {
-            if (!g && got < 0 && errno == EINTR) continue;
-            return false;
-        }
-        p += got;
-        n -= (size_t)got;
-    }
-    return true;
-}
-
-}  // namespace
-
-extern "C" {
-
-int kg_table_build(const kg_signature *sigs, int64_t n, int64_t num_sigs, int device, int64_t *n_placed, kg_table **out)
-{
-    return build_entry((const uint8_t *)sigs, nullptr, n, num_sigs, device, n_placed, out);
-}
-
-int kg_table_build_device(const kg_signature *d_sigs, int64_t n, int64_t num_sigs, int device, int64_t *n_placed, kg_table **out)
-{
-    return build_entry(nullptr, (const uint8_t *)d_sigs, n, num_sigs, device, n_placed, out);
-}
-
+// ---- a resident table -> kmer.table.mem_map[.gz] ----
 const void *kg_table_device_entries(const kg_table *t) { return t ? t->d_entries : nullptr; }
 int64_t kg_table_records(const kg_table *t) { return t ? (int64_t)t->limit : 0; }
 
 int kg_table_save(kg_table *t, const char *path)
 {
     if (!t || !path) return fail(KG_ERR_ARG, "null argument");
-    if (t->busy.exchange(1) != 0) return fail(KG_ERR_BUSY, "a kg_scan* is in flight on this kg_table");
-    struct BusyGuard { kg_table *t; ~BusyGuard() { t->busy.store(0); } } busy_guard{t};
-    HIP_TRY(hipSetDevice(t->device));
+    CallScope cs(t, "a kg_scan* is in flight on this kg_table");
+    if (cs.rc) return cs.rc;
     const size_t plen = strlen(path);
     const bool gz = plen >= 3 && strcmp(path + plen - 3, ".gz") == 0;
     // written under a temporary name next to the target and renamed at the end: a failed save leaves no file under `path`
@@ -2355,850 +1772,8 @@ int kg_table_save(kg_table *t, const char *path)
 
 }  // extern "C"
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// kg_signatures_derive / kg_signatures_derive_device: annotated proteins -> a signature set (kernels: kg_derive.hpp).
-struct kg_sigset {
-    int device = 0;
-    uint8_t *d_sigs = nullptr;          // count * 24 bytes (hipMalloc, owned)
-    int64_t count = 0;
-    kg_derive_stats st = {};
-};
-
-namespace {
-
-constexpr uint64_t kDeriveBytesPerWindow = 160;                       // device bytes one valid window of a pass needs, at most
-constexpr uint64_t kDerivePassMax = (1ull << 32) - (1ull << 22);      // the 32-bit scans and indices of one pass
-
-uint32_t grid_of(uint64_t n, uint32_t threads = 256)
-{
-    return (uint32_t)std::max<uint64_t>(1, (n + threads - 1) / threads);
-}
-
-struct DeriveRange { uint64_t lo, hi, count; };
-
-struct Deriver {
-    kg_table *t;                        // the call's context: stream, block cache, KG_TEST_FAIL_ALLOC
-    Scratch &sc;
-    const uint8_t *d_seq;
-    kg::BlockDesc *d_blocks = nullptr;
-    uint32_t n_blocks = 0;
-    unsigned long long *d_bins = nullptr;
-    uint64_t cap = 0;
-    std::vector<DeriveRange> elems;     // k-mer ranges in order, each within the cap
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    float ms_hist = 0;
-
-    // counts of the valid windows with k-mers in [lo, hi), in bins of 2^shift k-mers
-    int histogram(uint64_t lo, uint64_t hi, uint32_t shift, std::vector<unsigned long long> &out)
-    {
-        HIP_TRY(hipMemsetAsync(d_bins, 0, kg::kDeriveBins * 8, t->stream));
-        HIP_TRY(hipEventRecord(ev[0], t->stream));
-        if (n_blocks) {
-            const uint32_t grid = std::min<uint32_t>((n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16);
-            hipLaunchKernelGGL(kg::derive_windows_kernel<false>, dim3(grid), dim3(kg::kDeriveThreads), 0, t->stream, d_seq, d_blocks,
-                               n_blocks, lo, hi, shift, d_bins, nullptr, 0u, nullptr, nullptr, nullptr, (uint64_t)0);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(ev[1], t->stream));
-        out.assign(kg::kDeriveBins, 0);
-        HIP_TRY(hipMemcpyAsync(out.data(), d_bins, kg::kDeriveBins * 8, hipMemcpyDeviceToHost, t->stream));
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        ms_hist += ms;
-        return KG_OK;
-    }
-
-    static uint32_t shift_for(uint64_t width)
-    {
-        uint32_t s = 0;
-        while (((width - 1) >> s) >= kg::kDeriveBins) s++;
-        return s;
-    }
-
-    // the range [lo, hi) holds `count` windows: keep it, or cut it finer until every piece fits the cap
-    int split(uint64_t lo, uint64_t hi, uint64_t count)
-    {
-        if (count <= cap) { elems.push_back({lo, hi, count}); return KG_OK; }
-        if (hi - lo == 1)
-            return fail(KG_ERR_LIMIT, "k-mer " + kmer_text((int64_t)lo) + " alone occurs in " + kmer_text((int64_t)count) +
-                                          " valid windows, more than max_windows_per_pass = " + kmer_text((int64_t)cap));
-        const uint32_t shift = shift_for(hi - lo);
-        std::vector<unsigned long long> bins;
-        int rc = histogram(lo, hi, shift, bins);
-        if (rc) return rc;
-        for (uint64_t i = 0; i < kg::kDeriveBins; i++) {
-            const uint64_t a = lo + (i << shift);
-            if (a >= hi) break;
-            if (bins[i] && (rc = split(a, std::min<uint64_t>(hi, a + (1ull << shift)), bins[i]))) return rc;
-        }
-        return KG_OK;
-    }
-};
-
-int derive_impl(kg_table *t, const kg_derive_params *prm, const uint8_t *h_seq, const uint8_t *d_seq_in, const int64_t *offsets,
-                int64_t n_prot, const int32_t *fn, const int32_t *otu, kg_sigset *set)
-{
-    kg_derive_stats &st = set->st;
-    // ---- host: block counts (kg_scan's -a trip counts, KGJ:912) ----
-    std::vector<uint32_t> ibase((size_t)n_prot + 1);
-    uint64_t nblocks = 0, windows = 0;
-    for (int64_t k = 0; k < n_prot; k++) {
-        const int64_t L = offsets[k + 1] - offsets[k];
-        ibase[(size_t)k] = (uint32_t)nblocks;
-        const uint64_t nwin = L >= 9 ? (uint64_t)L - 8 : 0;
-        windows += nwin;
-        nblocks += (nwin + kg::kAaWinPerBlock - 1) / kg::kAaWinPerBlock;
-        if (nblocks > 0x7FFFFFFFull) return fail(KG_ERR_LIMIT, "2^31 or more window blocks of 64 windows in one call");
-    }
-    ibase[(size_t)n_prot] = (uint32_t)nblocks;
-    st.proteins = n_prot;
-    st.windows = (int64_t)windows;
-    uint32_t b = 0;
-    while ((1ull << b) < (uint64_t)n_prot) b++;
-
-    Scratch sc(t);
-    int rc;
-    hipEvent_t ev[8] = {};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 8; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{ev};
-    for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
-    auto elapsed = [&](int a, int c) { float ms = 0; (void)hipEventElapsedTime(&ms, ev[a], ev[c]); return ms; };
-
-    // ---- the sequence on the device ----
-    const uint8_t *d_seq = d_seq_in;
-    const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
-    if (h_seq && seq_bytes) {
-        uint8_t *d = nullptr;
-        if ((rc = sc.get(&d, seq_bytes))) return rc;
-        if ((rc = upload_signatures(t, h_seq, seq_bytes, d))) return rc;
-        d_seq = d;
-    }
-    HIP_TRY(hipEventRecord(ev[0], t->stream));
-
-    Deriver dv{t, sc, d_seq};
-    dv.ev[0] = ev[6]; dv.ev[1] = ev[7];
-    dv.n_blocks = (uint32_t)nblocks;
-    if ((rc = sc.get(&dv.d_bins, kg::kDeriveBins))) return rc;
-    int32_t *d_fn = nullptr, *d_otu = nullptr, *fn_r = nullptr, *otu_r = nullptr;
-    uint32_t *rank_of = nullptr;
-    if (n_prot) {
-        int64_t *d_off = nullptr;
-        uint32_t *d_ibase = nullptr;
-        if ((rc = sc.get(&d_off, (size_t)n_prot + 1)) || (rc = sc.get(&d_ibase, (size_t)n_prot + 1)) ||
-            (rc = sc.get(&d_fn, (size_t)n_prot)) || (rc = sc.get(&d_otu, (size_t)n_prot)) || (rc = sc.get(&fn_r, (size_t)n_prot)) ||
-            (rc = sc.get(&otu_r, (size_t)n_prot)) || (rc = sc.get(&rank_of, (size_t)n_prot)))
-            return rc;
-        if (nblocks && (rc = sc.get(&dv.d_blocks, nblocks))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)n_prot + 1) * 8, hipMemcpyHostToDevice, t->stream));
-        HIP_TRY(hipMemcpyAsync(d_ibase, ibase.data(), ((size_t)n_prot + 1) * 4, hipMemcpyHostToDevice, t->stream));
-        HIP_TRY(hipMemcpyAsync(d_fn, fn, (size_t)n_prot * 4, hipMemcpyHostToDevice, t->stream));
-        HIP_TRY(hipMemcpyAsync(d_otu, otu, (size_t)n_prot * 4, hipMemcpyHostToDevice, t->stream));
-        if (nblocks) {
-            hipLaunchKernelGGL(kg::build_blocks_kernel, dim3(grid_of(nblocks)), dim3(256), 0, t->stream, d_off, d_ibase, (uint32_t)n_prot,
-                               (uint32_t)nblocks, dv.d_blocks);
-            HIP_TRY(hipGetLastError());
-        }
-        // ---- rank the proteins by (fn, otu, p): a stable sort of (fn + 1, otu) keys carrying p ----
-        HIP_TRY(hipEventRecord(ev[1], t->stream));
-        uint64_t *keys[2] = {nullptr, nullptr};
-        uint32_t *vals[2] = {nullptr, nullptr};
-        if ((rc = sc.get(&keys[0], (size_t)n_prot)) || (rc = sc.get(&vals[0], (size_t)n_prot))) return rc;
-        hipLaunchKernelGGL(kg::derive_rank_keys_kernel, dim3(grid_of(n_prot)), dim3(256), 0, t->stream, d_fn, d_otu, (uint64_t)n_prot,
-                           keys[0], vals[0]);
-        HIP_TRY(hipGetLastError());
-        int32_t fmax = -1, omax = 0;
-        for (int64_t k = 0; k < n_prot; k++) {
-            fmax = std::max(fmax, fn[k]);
-            if (fn[k] >= 0) omax = std::max(omax, otu[k]);
-        }
-        const uint64_t kmax = ((uint64_t)((uint32_t)fmax + 1u) << 31) | (uint64_t)(uint32_t)omax;
-        uint32_t kbits = 0;
-        while (kbits < 64 && (kmax >> kbits) != 0) kbits++;
-        int cur = 0;
-        if (n_prot > 1 && kbits && (rc = radix_sort(t, sc, keys, vals, (uint64_t)n_prot, kbits, &cur))) return rc;
-        hipLaunchKernelGGL(kg::derive_rank_scatter_kernel, dim3(grid_of(n_prot)), dim3(256), 0, t->stream, vals[cur], d_fn, d_otu,
-                           (uint64_t)n_prot, rank_of, fn_r, otu_r);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev[2], t->stream));
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        st.ms_sort += elapsed(1, 2);
-    }
-
-    // ---- the pass plan: a histogram of the valid windows over the whole k-mer space, bins cut finer where needed ----
-    {
-        uint64_t cap = (uint64_t)prm->max_windows_per_pass;
-        if (cap == 0) {
-            size_t free_b = 0, total_b = 0;
-            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-            cap = std::max<uint64_t>(1u << 20, (uint64_t)(free_b * 0.8) / kDeriveBytesPerWindow);
-        }
-        dv.cap = std::min(cap, kDerivePassMax);
-    }
-    std::vector<unsigned long long> bins;
-    const uint64_t space = (uint64_t)KG_MAX_ENCODED;
-    const uint32_t shift0 = Deriver::shift_for(space);
-    if ((rc = dv.histogram(0, space, shift0, bins))) return rc;
-    uint64_t valid = 0;
-    for (auto c : bins) valid += c;
-    st.valid_windows = (int64_t)valid;
-    for (uint64_t i = 0; i < kg::kDeriveBins; i++) {
-        const uint64_t a = i << shift0;
-        if (a >= space) break;
-        if (bins[i] && (rc = dv.split(a, std::min<uint64_t>(space, a + (1ull << shift0)), bins[i]))) return rc;
-    }
-    std::vector<DeriveRange> passes;
-    for (const auto &e : dv.elems) {
-        if (!passes.empty() && passes.back().count + e.count <= dv.cap) {
-            passes.back().hi = e.hi;
-            passes.back().count += e.count;
-        } else {
-            passes.push_back(e);
-        }
-    }
-    st.passes = (int32_t)passes.size();
-
-    // ---- one pass per k-mer range ----
-    std::vector<std::pair<uint8_t *, uint64_t>> outs;       // each pass's signatures (sc blocks), in k-mer order
-    unsigned long long *d_cur = nullptr;
-    uint64_t *d_tot = nullptr;
-    if ((rc = sc.get(&d_cur, 2)) || (rc = sc.get(&d_tot, 8))) return rc;
-    uint64_t total_sigs = 0;
-    for (const DeriveRange &ps : passes) {
-        const uint64_t n = ps.count;
-        Scratch pass(t);                                    // this pass's scratch, back in the cache at its end
-        uint64_t *keys[2] = {nullptr, nullptr};
-        uint32_t *vals[2] = {nullptr, nullptr};
-        if ((rc = pass.get(&keys[0], n)) || (rc = pass.get(&vals[0], n))) return rc;
-        HIP_TRY(hipMemsetAsync(d_cur, 0, 8, t->stream));
-        HIP_TRY(hipEventRecord(ev[1], t->stream));
-        {
-            const uint32_t grid = std::min<uint32_t>((dv.n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16);
-            hipLaunchKernelGGL(kg::derive_windows_kernel<true>, dim3(std::max(grid, 1u)), dim3(kg::kDeriveThreads), 0, t->stream, d_seq,
-                               dv.d_blocks, dv.n_blocks, ps.lo, ps.hi, 0u, nullptr, rank_of, b, keys[0], vals[0], d_cur, n);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(ev[2], t->stream));
-        uint32_t vbits = 0;
-        while (((ps.hi - ps.lo - 1) >> vbits) != 0) vbits++;
-        int cur = 0;
-        if (n > 1 && vbits + b > 0 && (rc = radix_sort(t, pass, keys, vals, n, vbits + b, &cur))) return rc;
-        HIP_TRY(hipEventRecord(ev[3], t->stream));
-        // collapse equal keys into (k-mer, protein) pairs
-        const uint64_t nb = n / kg::kScanChunk + 2;
-        uint32_t *flags = nullptr, *pidx = nullptr;
-        uint64_t *partial = nullptr;
-        if ((rc = pass.get(&flags, n)) || (rc = pass.get(&pidx, n)) || (rc = pass.get(&partial, nb + 1))) return rc;
-        hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(n)), dim3(256), 0, t->stream, keys[cur], n, flags);
-        HIP_TRY(hipGetLastError());
-        if ((rc = prefix_sum(t, flags, n, pidx, partial, d_tot + 0))) return rc;
-        unsigned long long host_cur = 0;
-        uint64_t P = 0;
-        HIP_TRY(hipMemcpyAsync(&host_cur, d_cur, 8, hipMemcpyDeviceToHost, t->stream));
-        HIP_TRY(hipMemcpyAsync(&P, d_tot, 8, hipMemcpyDeviceToHost, t->stream));
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        if (host_cur != n) return fail(KG_ERR_DEVICE, "internal: a pass emitted a different number of windows than its histogram counted");
-        uint64_t *pk = nullptr;
-        uint32_t *pv = nullptr;
-        if ((rc = pass.get(&pk, P)) || (rc = pass.get(&pv, P))) return rc;
-        HIP_TRY(hipMemsetAsync(pv, 0, P * 4, t->stream));
-        hipLaunchKernelGGL(kg::derive_collapse_kernel, dim3(grid_of((n + kg::kDeriveChunk - 1) / kg::kDeriveChunk)), dim3(256), 0, t->stream,
-                           keys[cur], vals[cur], n, pidx, pk, pv);
-        HIP_TRY(hipGetLastError());
-        // run heads and numbers at the three levels (flags / pidx / partial are reused: P <= n)
-        uint32_t *kh = flags, *fh = nullptr, *oh = nullptr, *kx = pidx, *fx = nullptr, *ox = nullptr;
-        if ((rc = pass.get(&fh, P)) || (rc = pass.get(&oh, P)) || (rc = pass.get(&fx, P)) || (rc = pass.get(&ox, P))) return rc;
-        hipLaunchKernelGGL(kg::derive_run_flags_kernel, dim3(grid_of(P)), dim3(256), 0, t->stream, pk, P, b, fn_r, otu_r, kh, fh, oh);
-        HIP_TRY(hipGetLastError());
-        if ((rc = prefix_sum(t, kh, P, kx, partial, d_tot + 1)) || (rc = prefix_sum(t, fh, P, fx, partial, d_tot + 2)) ||
-            (rc = prefix_sum(t, oh, P, ox, partial, d_tot + 3)))
-            return rc;
-        uint64_t tot[3] = {0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(tot, d_tot + 1, 24, hipMemcpyDeviceToHost, t->stream));
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        const uint64_t K = tot[0], F = tot[1], O = tot[2];
-        uint32_t *kstart = nullptr, *fstart = nullptr, *f_kmer = nullptr, *ostart = nullptr, *o_frun = nullptr;
-        int32_t *f_fn = nullptr, *o_otu = nullptr;
-        unsigned long long *fsum = nullptr, *kbest = nullptr, *kotu = nullptr;
-        if ((rc = pass.get(&kstart, K + 1)) || (rc = pass.get(&fstart, F + 1)) || (rc = pass.get(&f_kmer, F)) ||
-            (rc = pass.get(&f_fn, F)) || (rc = pass.get(&ostart, O + 1)) || (rc = pass.get(&o_frun, O)) || (rc = pass.get(&o_otu, O)) ||
-            (rc = pass.get(&fsum, F)) || (rc = pass.get(&kbest, K)) || (rc = pass.get(&kotu, K)))
-            return rc;
-        hipLaunchKernelGGL(kg::derive_run_starts_kernel, dim3(grid_of(P)), dim3(256), 0, t->stream, pk, P, b, fn_r, otu_r, kx, fx, ox,
-                           d_tot + 1, d_tot + 2, d_tot + 3, kstart, fstart, f_kmer, f_fn, ostart, o_frun, o_otu);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemsetAsync(fsum, 0, F * 8, t->stream));
-        HIP_TRY(hipMemsetAsync(kbest, 0, K * 8, t->stream));
-        HIP_TRY(hipMemsetAsync(kotu, 0, K * 8, t->stream));
-        hipLaunchKernelGGL(kg::derive_run_sums_kernel, dim3(grid_of((P + kg::kDeriveChunk - 1) / kg::kDeriveChunk)), dim3(256), 0, t->stream,
-                           pv, P, fh, fx, fsum);
-        hipLaunchKernelGGL(kg::derive_fn_best_kernel, dim3(grid_of(F)), dim3(256), 0, t->stream, fstart, f_kmer, f_fn, F, kbest);
-        hipLaunchKernelGGL(kg::derive_otu_best_kernel, dim3(grid_of(O)), dim3(256), 0, t->stream, ostart, o_frun, o_otu, O, f_kmer, kbest, kotu);
-        HIP_TRY(hipGetLastError());
-        // the signatures of the pass, in k-mer order (kflags / kidx reuse fh / fx: K <= P)
-        uint32_t *kflags = fh, *kidx = fx;
-        hipLaunchKernelGGL(kg::derive_select_kernel<false>, dim3(grid_of(K)), dim3(256), 0, t->stream, K, kstart, kbest, kotu, fsum, f_fn,
-                           pk, b, ps.lo, (int64_t)prm->min_proteins, (int64_t)prm->purity_pct, kflags, nullptr, nullptr);
-        HIP_TRY(hipGetLastError());
-        if ((rc = prefix_sum(t, kflags, K, kidx, partial, d_tot + 4))) return rc;
-        uint64_t S = 0;
-        HIP_TRY(hipMemcpyAsync(&S, d_tot + 4, 8, hipMemcpyDeviceToHost, t->stream));
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        if (S) {
-            uint8_t *o = nullptr;
-            if ((rc = sc.get(&o, S * 24))) return rc;
-            hipLaunchKernelGGL(kg::derive_select_kernel<true>, dim3(grid_of(K)), dim3(256), 0, t->stream, K, kstart, kbest, kotu, fsum, f_fn,
-                               pk, b, ps.lo, (int64_t)prm->min_proteins, (int64_t)prm->purity_pct, nullptr, kidx, o);
-            HIP_TRY(hipGetLastError());
-            outs.emplace_back(o, S);
-        }
-        HIP_TRY(hipEventRecord(ev[4], t->stream));
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        st.ms_encode += elapsed(1, 2);
-        st.ms_sort += elapsed(2, 3);
-        st.ms_reduce += elapsed(3, 4);
-        st.pairs += (int64_t)P;
-        st.kmers += (int64_t)K;
-        total_sigs += S;
-    }
-    if (total_sigs >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more signatures");
-    // ---- the set: the passes' signatures back to back ----
-    {
-        void *e = nullptr;
-        if ((rc = dalloc(t, &e, std::max<uint64_t>(total_sigs * 24, 24)))) return rc;
-        t->cache.detach(e);
-        set->d_sigs = (uint8_t *)e;
-    }
-    uint64_t at = 0;
-    for (auto &o : outs) {
-        HIP_TRY(hipMemcpyAsync(set->d_sigs + at * 24, o.first, o.second * 24, hipMemcpyDeviceToDevice, t->stream));
-        at += o.second;
-    }
-    HIP_TRY(hipEventRecord(ev[5], t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    st.ms_encode += dv.ms_hist;
-    st.ms_total = elapsed(0, 5);
-    st.signatures = (int64_t)total_sigs;
-    set->count = (int64_t)total_sigs;
-    return KG_OK;
-}
-
-int derive_entry(int device, const kg_derive_params *prm, const uint8_t *h_seq, const uint8_t *d_seq, const int64_t *offsets,
-                 int64_t n_prot, const int32_t *fn, const int32_t *otu, kg_sigset **out)
-{
-    if (!out) return fail(KG_ERR_ARG, "null argument");
-    *out = nullptr;
-    if (!prm) return fail(KG_ERR_ARG, "null kg_derive_params");
-    if (prm->min_proteins < 1) return fail(KG_ERR_ARG, "min_proteins must be >= 1");
-    if (prm->purity_pct < 1 || prm->purity_pct > 100) return fail(KG_ERR_ARG, "purity_pct must be in 1..100");
-    if (prm->max_windows_per_pass < 0) return fail(KG_ERR_ARG, "max_windows_per_pass must be >= 0");
-    if (n_prot < 0) return fail(KG_ERR_ARG, "n_prot < 0");
-    if (n_prot >= (1ll << 29)) return fail(KG_ERR_LIMIT, "2^29 or more proteins in one call");
-    if (!offsets) return fail(KG_ERR_ARG, "null offsets");
-    if (n_prot > 0 && (!fn || !otu)) return fail(KG_ERR_ARG, "null fn / otu array");
-    if (offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
-    for (int64_t k = 0; k < n_prot; k++) {
-        const int64_t L = offsets[k + 1] - offsets[k];
-        if (L < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": offsets decrease (offsets[p+1] < offsets[p])");
-        if (L >= (1ll << 31)) return fail(KG_ERR_LIMIT, "protein " + kmer_text(k) + ": 2^31 or more characters");
-        if (fn[k] < -1) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": fn = " + kmer_text(fn[k]) + " < -1");
-        if (fn[k] >= 0 && otu[k] < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": otu = " + kmer_text(otu[k]) + " < 0 on an annotated protein");
-    }
-    const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
-    if (seq_bytes && !h_seq && !d_seq) return fail(KG_ERR_ARG, "null sequence");
-    kg_table *t = nullptr;
-    int rc = table_new(device, &t);
-    if (rc) return rc;
-    kg_sigset *set = new (std::nothrow) kg_sigset();
-    if (!set) { kg_table_close(t); return fail(KG_ERR_NOMEM, "out of host memory"); }
-    set->device = device;
-    t->fail_alloc_at = test_hook("KG_TEST_FAIL_ALLOC");
-    t->alloc_count = 0;
-    if (d_seq && hipDeviceSynchronize() != hipSuccess) rc = fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed");
-    if (!rc) rc = derive_impl(t, prm, h_seq, d_seq, offsets, n_prot, fn, otu, set);
-    t->fail_alloc_at = 0;
-    t->cache.release_all();                             // scratch goes back to the driver
-    kg_table_close(t);
-    if (rc) { kg_sigset_free(set); return rc; }
-    if (getenv("KG_DEBUG"))
-        fprintf(stderr, "[kg] kg_signatures_derive: proteins=%lld valid=%lld pairs=%lld kmers=%lld sigs=%lld passes=%d encode_ms=%.3f sort_ms=%.3f reduce_ms=%.3f total_ms=%.3f\n",
-                (long long)set->st.proteins, (long long)set->st.valid_windows, (long long)set->st.pairs, (long long)set->st.kmers,
-                (long long)set->st.signatures, set->st.passes, set->st.ms_encode, set->st.ms_sort, set->st.ms_reduce, set->st.ms_total);
-    *out = set;
-    return KG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int kg_signatures_derive(int device, const kg_derive_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
-                         const int32_t *fn, const int32_t *otu, kg_sigset **out)
-{
-    return derive_entry(device, p, seq, nullptr, offsets, n_prot, fn, otu, out);
-}
-
-int kg_signatures_derive_device(int device, const kg_derive_params *p, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
-                                const int32_t *fn, const int32_t *otu, kg_sigset **out)
-{
-    return derive_entry(device, p, nullptr, d_seq, offsets, n_prot, fn, otu, out);
-}
-
-int64_t kg_sigset_count(const kg_sigset *s) { return s ? s->count : 0; }
-
-const kg_signature *kg_sigset_device(const kg_sigset *s) { return s ? (const kg_signature *)s->d_sigs : nullptr; }
-
-int kg_sigset_copy(const kg_sigset *s, int64_t first, int64_t count, kg_signature *dst)
-{
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_sigset_copy: range outside the set");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipMemcpy(dst, s->d_sigs + first * 24, (size_t)count * 24, hipMemcpyDefault));
-    return KG_OK;
-}
-
-int kg_sigset_stats(const kg_sigset *s, kg_derive_stats *out)
-{
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    *out = s->st;
-    return KG_OK;
-}
-
-void kg_sigset_free(kg_sigset *s)
-{
-    if (!s) return;
-    if (s->d_sigs) {
-        (void)hipSetDevice(s->device);
-        (void)hipFree(s->d_sigs);
-    }
-    delete s;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// kg_result_assign / kg_assign_calls: the CALL records of an -a scan -> one kg_assignment per protein (kernels: kg_assign.hpp).
-namespace {
-
-constexpr int kPinAssign = 90;          // h_pin[90..91]: long proteins, their CALLs; [92..94]: the error words
-
-uint32_t bits_for(uint64_t n)
-{
-    uint32_t b = 0;
-    while (b < 64 && (n >> b) > 1) b++;
-    return n > 1 ? b + ((n & (n - 1)) ? 1 : 0) : 0;
-}
-
-int check_assign_params(const kg_assign_params *p)
-{
-    if (!p) return fail(KG_ERR_ARG, "null kg_assign_params");
-    if (p->min_score < 0) return fail(KG_ERR_ARG, "min_score must be >= 0");
-    if (p->min_share_pct < 0 || p->min_share_pct > 100) return fail(KG_ERR_ARG, "min_share_pct must be in 0..100");
-    return KG_OK;
-}
-
-// d_calls[n_calls], d_cs[n_prot + 1], d_otu[n_prot] (or null): device arrays complete on t->stream.  Writes dst (host or device).
-int assign_impl(kg_table *t, const kg_assign_params *prm, const kg_call *d_calls, uint64_t n_calls, const int64_t *d_cs,
-                uint64_t n_prot, const kg_otu *d_otu, kg_assignment *dst, float *ms)
-{
-    if (ms) *ms = 0;
-    if (n_prot == 0) return KG_OK;
-    hipPointerAttribute_t attr;
-    const bool dev_dst = hipPointerGetAttributes(&attr, dst) == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == t->device;
-    (void)hipGetLastError();
-    Scratch sc(t);
-    int rc;
-    kg_assignment *d_out = dev_dst ? dst : nullptr;
-    uint32_t *flag = nullptr, *len = nullptr, *rank = nullptr, *base = nullptr;
-    uint64_t *partial = nullptr, *totals = nullptr;
-    unsigned long long *err = nullptr;
-    const uint64_t nb = n_prot / kg::kScanChunk + 2;
-    if ((!dev_dst && (rc = sc.get(&d_out, n_prot))) || (rc = sc.get(&flag, n_prot)) || (rc = sc.get(&len, n_prot)) ||
-        (rc = sc.get(&rank, n_prot)) || (rc = sc.get(&base, n_prot)) || (rc = sc.get(&partial, nb)) || (rc = sc.get(&totals, 4)) ||
-        (rc = sc.get(&err, 4)))
-        return rc;
-    hipStream_t s = t->stream;
-    HIP_TRY(hipMemsetAsync(err, 0x7F, 4 * 8, s));
-    HIP_TRY(hipEventRecord(t->ev[0], s));
-    hipLaunchKernelGGL(kg::assign_short_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, d_calls, n_calls, d_cs, n_prot, d_otu,
-                       prm->min_score, prm->min_share_pct, d_out, flag, len, err);
-    HIP_TRY(hipGetLastError());
-    if ((rc = prefix_sum(t, flag, n_prot, rank, partial, totals))) return rc;
-    if ((rc = prefix_sum(t, len, n_prot, base, partial, totals + 1))) return rc;
-    HIP_TRY(hipMemcpyAsync(t->h_pin + kPinAssign, totals, 16, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const uint64_t n_long = t->h_pin[kPinAssign], n_items = t->h_pin[kPinAssign + 1];
-    if (n_long > 0) {
-        uint32_t *ids = nullptr, *lbase = nullptr, *vals[2] = {nullptr, nullptr};
-        uint64_t *keys[2] = {nullptr, nullptr};
-        int64_t *run_s = nullptr;
-        float *run_w = nullptr;
-        if ((rc = sc.get(&ids, n_long)) || (rc = sc.get(&lbase, n_long)) || (rc = sc.get(&keys[0], n_items)) ||
-            (rc = sc.get(&vals[0], n_items)) || (rc = sc.get(&run_s, n_items)) || (rc = sc.get(&run_w, n_items)))
-            return rc;
-        hipLaunchKernelGGL(kg::assign_long_scatter_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, flag, rank, base, n_prot, ids, lbase);
-        const uint32_t wgrid = (uint32_t)std::min<uint64_t>((n_long + 3) / 4, 256ull * 64);
-        hipLaunchKernelGGL(kg::assign_long_keys_kernel, dim3(wgrid), dim3(256), 0, s, d_calls, n_calls, d_cs, ids, lbase,
-                           (uint32_t)n_long, keys[0], vals[0], err);
-        HIP_TRY(hipGetLastError());
-        int cur = 0;
-        if ((rc = radix_sort(t, sc, keys, vals, n_items, 32 + bits_for(n_long), &cur))) return rc;
-        hipLaunchKernelGGL(kg::assign_long_runs_kernel, dim3(grid_of(n_items)), dim3(256), 0, s, keys[cur], vals[cur], n_items, d_calls,
-                           run_s, run_w);
-        hipLaunchKernelGGL(kg::assign_long_reduce_kernel, dim3(wgrid), dim3(256), 0, s, keys[cur], run_s, run_w, d_calls, n_calls,
-                           d_cs, d_otu, ids, lbase, (uint32_t)n_long, prm->min_score, prm->min_share_pct, d_out, err);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(t->ev[1], s));
-    HIP_TRY(hipMemcpyAsync(t->h_pin + kPinAssign + 2, err, 24, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const uint64_t *e = t->h_pin + kPinAssign + 2;
-    if (e[kg::kAssignErrOrder] != kg::kAssignNoErr)
-        return fail(KG_ERR_ARG, "protein " + kmer_text((int64_t)e[kg::kAssignErrOrder]) + ": call_start decreases (call_start[p+1] < call_start[p])");
-    if (e[kg::kAssignErrCount] != kg::kAssignNoErr)
-        return fail(KG_ERR_ARG, "protein " + kmer_text((int64_t)e[kg::kAssignErrCount]) + ": a CALL has a negative count");
-    if (e[kg::kAssignErrLimit] != kg::kAssignNoErr)
-        return fail(KG_ERR_LIMIT, "protein " + kmer_text((int64_t)e[kg::kAssignErrLimit]) + ": S_best or T is 2^31 or more");
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, t->ev[0], t->ev[1]));
-    if (!dev_dst) HIP_TRY(hipMemcpy(dst, d_out, n_prot * sizeof(kg_assignment), hipMemcpyDefault));
-    return KG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int kg_result_assign(kg_result *r, const kg_assign_params *p, kg_assignment *dst, float *ms)
-{
-    if (ms) *ms = 0;
-    if (!r) return fail(KG_ERR_ARG, "null kg_result");
-    int rc = check_assign_params(p);
-    if (rc) return rc;
-    if (!r->d_ccs || !r->d_otu) return fail(KG_ERR_ARG, "a KG_F_SKIP_AGGREGATE result has no CALL records to assign from");
-    if (r->per != 1 || r->st.n_containers != r->st.n_seqs)
-        return fail(KG_ERR_ARG, "a DNA result: assignment needs an -a (protein) scan, one container per sequence");
-    if (r->st.n_seqs > 0 && !dst) return fail(KG_ERR_ARG, "null destination");
-    kg_table *t = r->tab;
-    if (t->busy.exchange(1) != 0) return fail(KG_ERR_BUSY, "a kg_scan* is in flight on this result's kg_table");
-    struct BusyGuard { kg_table *t; ~BusyGuard() { t->fail_alloc_at = 0; t->busy.store(0); } } busy_guard{t};
-    t->fail_alloc_at = test_hook("KG_TEST_FAIL_ALLOC");
-    t->alloc_count = 0;
-    HIP_TRY(hipSetDevice(t->device));
-    return assign_impl(t, p, r->d_calls, (uint64_t)r->st.n_calls, r->d_ccs, (uint64_t)r->st.n_seqs, r->d_otu, dst, ms);
-}
-
-int kg_assign_calls(int device, const kg_assign_params *p, const kg_call *calls, const int64_t *call_start, int64_t n_prot,
-                    const kg_otu *otu, kg_assignment *dst)
-{
-    int rc = check_assign_params(p);
-    if (rc) return rc;
-    if (n_prot < 0 || !call_start) return fail(KG_ERR_ARG, "null call_start or n_prot < 0");
-    if (n_prot >= (1ll << 31)) return fail(KG_ERR_LIMIT, "2^31 or more proteins in one call");
-    if (n_prot > 0 && !dst) return fail(KG_ERR_ARG, "null destination");
-    if (call_start[0] < 0) return fail(KG_ERR_ARG, "protein 0: call_start[0] < 0");
-    const uint64_t n_calls = call_start[n_prot] > 0 ? (uint64_t)call_start[n_prot] : 0;
-    if (n_calls >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more CALL records in one call");
-    if (n_calls && !calls) return fail(KG_ERR_ARG, "null CALL records");
-    if (n_prot == 0) return KG_OK;
-    kg_table *t = nullptr;
-    if ((rc = table_new(device, &t))) return rc;
-    t->fail_alloc_at = test_hook("KG_TEST_FAIL_ALLOC");
-    t->alloc_count = 0;
-    rc = [&]() -> int {                 // (the scratch blocks go back to the context's cache before the context is closed)
-        Scratch sc(t);
-        kg_call *d_calls = nullptr;
-        int64_t *d_cs = nullptr;
-        kg_otu *d_otu = nullptr;
-        int rc2;
-        if ((rc2 = sc.get(&d_calls, n_calls ? n_calls : 1)) || (rc2 = sc.get(&d_cs, (size_t)n_prot + 1)) ||
-            (otu && (rc2 = sc.get(&d_otu, (size_t)n_prot))))
-            return rc2;
-        if (n_calls) HIP_TRY(hipMemcpyAsync(d_calls, calls, n_calls * sizeof(kg_call), hipMemcpyHostToDevice, t->stream));
-        HIP_TRY(hipMemcpyAsync(d_cs, call_start, ((size_t)n_prot + 1) * 8, hipMemcpyHostToDevice, t->stream));
-        if (otu) HIP_TRY(hipMemcpyAsync(d_otu, otu, (size_t)n_prot * sizeof(kg_otu), hipMemcpyHostToDevice, t->stream));
-        return assign_impl(t, p, d_calls, n_calls, d_cs, (uint64_t)n_prot, d_otu, dst, nullptr);
-    }();
-    t->fail_alloc_at = 0;
-    kg_table_close(t);
-    return rc;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// kg_result_regions / kg_regions_calls: the CALL records of a DNA scan -> function regions on the contigs (kernels: kg_regions.hpp).
-struct kg_regionset {
-    kg_table *tab = nullptr;            // the context whose block cache the two arrays came from
-    bool own_tab = false;               // kg_regions_calls: the set owns a table-less context
-    kg_region *d_regions = nullptr;     // count records, output order
-    int64_t *d_seq_start = nullptr;     // n_seqs + 1
-    int64_t count = 0, n_seqs = 0;
-    kg_region_stats st = {};
-};
-
-namespace {
-
-constexpr int kPinRegions = 80;         // h_pin[80..]: the totals, then the error and counter words (no scan is in flight: the call holds the table)
-
-int check_region_params(const kg_region_params *p)
-{
-    if (!p) return fail(KG_ERR_ARG, "null kg_region_params");
-    if (p->merge_gap < 0) return fail(KG_ERR_ARG, "merge_gap must be >= 0");
-    if (p->min_score < 0) return fail(KG_ERR_ARG, "min_score must be >= 0");
-    if (p->min_len < 0) return fail(KG_ERR_ARG, "min_len must be >= 0");
-    return KG_OK;
-}
-
-// the host checks of offsets[n_seqs + 1]; *l_max = the longest contig
-int check_region_offsets(const int64_t *offsets, int64_t n_seqs, int64_t *l_max)
-{
-    if (n_seqs < 0) return fail(KG_ERR_ARG, "n_seqs < 0");
-    if (!offsets) return fail(KG_ERR_ARG, "null offsets");
-    if (n_seqs >= (1ll << 31)) return fail(KG_ERR_LIMIT, "2^31 or more contigs in one call");
-    *l_max = 0;
-    for (int64_t k = 0; k < n_seqs; k++) {
-        const int64_t L = offsets[k + 1] - offsets[k];
-        if (L < 0) return fail(KG_ERR_ARG, "contig " + kmer_text(k) + ": offsets decrease (offsets[s+1] < offsets[s])");
-        if (L >= (1ll << 31)) return fail(KG_ERR_LIMIT, "contig " + kmer_text(k) + ": 2^31 or more nucleotides");
-        *l_max = std::max(*l_max, L);
-    }
-    return KG_OK;
-}
-
-// stable sort of n (keys[0], vals[0]) pairs; n <= 1 and key_bits == 0 need none
-int region_sort(kg_table *t, Scratch &sc, uint64_t *keys[2], uint32_t *vals[2], uint64_t n, uint32_t key_bits, int *cur)
-{
-    *cur = 0;
-    if (n <= 1 || key_bits == 0) return KG_OK;
-    return radix_sort(t, sc, keys, vals, n, key_bits, cur);
-}
-
-// d_calls[n_calls]: device array complete on t->stream; offsets: host, checked.  Fills set (its arrays come out of the cache
-// with the call's scratch and are kept only on success).
-int regions_impl(kg_table *t, const kg_region_params *prm, const kg_call *d_calls, uint64_t n, const int64_t *offsets,
-                 uint64_t n_seqs, int64_t l_max, kg_regionset *set)
-{
-    Scratch sc(t);
-    hipStream_t s = t->stream;
-    int rc;
-    int64_t *d_off = nullptr, *d_start = nullptr;
-    unsigned long long *words = nullptr;           // [0 .. kRegionErrWords): error words, then 2 counters, then 2 totals
-    if ((rc = sc.get(&d_off, n_seqs + 1)) || (rc = sc.get(&d_start, n_seqs + 1)) || (rc = sc.get(&words, 16))) return rc;
-    unsigned long long *err = words, *cnt = words + kg::kRegionErrWords;
-    uint64_t *totals = (uint64_t *)(words + kg::kRegionErrWords + 2);
-    HIP_TRY(hipMemcpyAsync(d_off, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(err, 0x7F, kg::kRegionErrWords * 8, s));
-    HIP_TRY(hipMemsetAsync(cnt, 0, 4 * 8, s));
-    HIP_TRY(hipEventRecord(t->ev[0], s));
-    uint64_t *h = t->h_pin + kPinRegions;
-    uint64_t n_groups = 0, n_regions = 0;
-    kg_region *d_out = nullptr;
-    const uint32_t left_bits = bits_for((uint64_t)std::max<int64_t>(l_max, 1));
-    uint64_t *rkeys[2] = {nullptr, nullptr};
-    uint32_t *rvals[2] = {nullptr, nullptr};
-    int rcur = 0;
-    if (n > 0) {
-        uint64_t *keys[2] = {nullptr, nullptr}, *partial = nullptr;
-        uint32_t *vals[2] = {nullptr, nullptr};
-        if ((rc = sc.get(&keys[0], n)) || (rc = sc.get(&vals[0], n))) return rc;
-        hipLaunchKernelGGL(kg::region_keys_kernel, dim3(grid_of(n)), dim3(256), 0, s, d_calls, n, d_off, n_seqs, keys[0], vals[0], err);
-        HIP_TRY(hipGetLastError());
-        int cur = 0;
-        if ((rc = region_sort(t, sc, keys, vals, n, left_bits, &cur))) return rc;
-        // second sort: the group keys, in x0 order, into the buffer the first sort left free (or a new one)
-        uint64_t *gk[2] = {keys[cur ^ 1], nullptr};
-        uint32_t *gv[2] = {vals[cur], nullptr};
-        if (!gk[0] && (rc = sc.get(&gk[0], n))) return rc;
-        hipLaunchKernelGGL(kg::region_group_keys_kernel, dim3(grid_of(n)), dim3(256), 0, s, d_calls, n, n_seqs, gv[0], gk[0]);
-        HIP_TRY(hipGetLastError());
-        if ((rc = region_sort(t, sc, gk, gv, n, 32 + bits_for(2 * n_seqs), &cur))) return rc;
-        const uint64_t *gkeys = gk[cur];
-        const uint32_t *perm = gv[cur];
-        uint32_t *sx0 = nullptr, *sx1 = nullptr, *ghead = nullptr, *gexcl = nullptr, *rhead = nullptr, *rexcl = nullptr, *rmax = nullptr;
-        int32_t *scount = nullptr;
-        float *sweight = nullptr;
-        uint8_t *sframe = nullptr;
-        int64_t *tile_max = nullptr, *tile_pre = nullptr;
-        const uint32_t n_tiles = (uint32_t)((n + kg::kBuildTile - 1) / kg::kBuildTile);
-        if ((rc = sc.get(&sx0, n)) || (rc = sc.get(&sx1, n)) || (rc = sc.get(&scount, n)) || (rc = sc.get(&sweight, n)) ||
-            (rc = sc.get(&sframe, n)) || (rc = sc.get(&ghead, n)) || (rc = sc.get(&gexcl, n)) || (rc = sc.get(&rhead, n)) ||
-            (rc = sc.get(&rexcl, n)) || (rc = sc.get(&rmax, n)) || (rc = sc.get(&tile_max, n_tiles)) ||
-            (rc = sc.get(&tile_pre, n_tiles)) || (rc = sc.get(&partial, n / kg::kScanChunk + 2)))
-            return rc;
-        hipLaunchKernelGGL(kg::region_gather_kernel, dim3(grid_of(n)), dim3(256), 0, s, d_calls, n, d_off, n_seqs, gkeys, perm, sx0, sx1,
-                           scount, sweight, sframe, ghead);
-        HIP_TRY(hipGetLastError());
-        if ((rc = prefix_sum(t, ghead, n, gexcl, partial, totals))) return rc;
-        hipLaunchKernelGGL(kg::region_tile_max_kernel, dim3(n_tiles), dim3(kg::kBuildThreads), 0, s, ghead, gexcl, sx1, n, tile_max);
-        hipLaunchKernelGGL(kg::build_tile_scan_kernel, dim3(1), dim3(kg::kBuildThreads), 0, s, tile_max, n_tiles, tile_pre);
-        hipLaunchKernelGGL(kg::region_heads_kernel, dim3(n_tiles), dim3(kg::kBuildThreads), 0, s, ghead, gexcl, sx0, sx1, n, tile_pre,
-                           (int64_t)prm->merge_gap, rhead, rmax);
-        HIP_TRY(hipGetLastError());
-        if ((rc = prefix_sum(t, rhead, n, rexcl, partial, totals + 1))) return rc;
-        HIP_TRY(hipMemcpyAsync(h, totals, 16, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        n_groups = h[0];
-        n_regions = h[1];
-        kg_region *unsorted = nullptr;
-        uint64_t *k2 = nullptr;
-        if ((rc = sc.get(&d_out, n_regions)) || (rc = sc.get(&unsorted, n_regions)) || (rc = sc.get(&rkeys[0], n_regions)) ||
-            (rc = sc.get(&k2, n_regions)) || (rc = sc.get(&rvals[0], n_regions)))
-            return rc;
-        hipLaunchKernelGGL(kg::region_walk_kernel, dim3(grid_of(n)), dim3(256), 0, s, rhead, rexcl, rmax, sx0, scount, sweight, sframe,
-                           gkeys, perm, n, d_off, prm->min_score, prm->min_len, left_bits, unsorted,
-                           kg::RegionKeys{rkeys[0], k2, rvals[0]}, err);
-        HIP_TRY(hipGetLastError());
-        if ((rc = region_sort(t, sc, rkeys, rvals, n_regions, 33 + left_bits, &rcur))) return rc;
-        uint64_t *fk[2] = {rkeys[rcur ^ 1], nullptr};
-        uint32_t *fv[2] = {rvals[rcur], nullptr};
-        if (!fk[0] && (rc = sc.get(&fk[0], n_regions))) return rc;
-        hipLaunchKernelGGL(kg::region_rekey_kernel, dim3(grid_of(n_regions)), dim3(256), 0, s, k2, fv[0], n_regions, fk[0]);
-        HIP_TRY(hipGetLastError());
-        if ((rc = region_sort(t, sc, fk, fv, n_regions, left_bits + bits_for(n_seqs), &rcur))) return rc;
-        rkeys[0] = fk[rcur];
-        hipLaunchKernelGGL(kg::region_emit_kernel, dim3(grid_of(n_regions)), dim3(256), 0, s, unsorted, fv[rcur], n_regions, d_out, cnt);
-        HIP_TRY(hipGetLastError());
-    } else if ((rc = sc.get(&d_out, 1))) {
-        return rc;
-    }
-    hipLaunchKernelGGL(kg::region_seq_start_kernel, dim3(grid_of(n_seqs + 1)), dim3(256), 0, s, rkeys[0], n_regions, left_bits, n_seqs,
-                       d_start);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(t->ev[1], s));
-    HIP_TRY(hipMemcpyAsync(h, words, (kg::kRegionErrWords + 2) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const uint64_t *e = h;
-    if (e[kg::kRegionErrContainer] != kg::kRegionNoErr)
-        return fail(KG_ERR_ARG, "CALL " + kmer_text((int64_t)e[kg::kRegionErrContainer]) + ": container >= 6 * n_seqs");
-    if (e[kg::kRegionErrOrder] != kg::kRegionNoErr)
-        return fail(KG_ERR_ARG, "CALL " + kmer_text((int64_t)e[kg::kRegionErrOrder]) + ": container below its predecessor's (calls[] must be in container order)");
-    if (e[kg::kRegionErrCount] != kg::kRegionNoErr)
-        return fail(KG_ERR_ARG, "CALL " + kmer_text((int64_t)e[kg::kRegionErrCount]) + ": negative count");
-    if (e[kg::kRegionErrRange] != kg::kRegionNoErr)
-        return fail(KG_ERR_ARG, "CALL " + kmer_text((int64_t)e[kg::kRegionErrRange]) + ": outside its contig (0 <= x0 <= x1 <= L - 1 does not hold)");
-    if (e[kg::kRegionErrLimit] != kg::kRegionNoErr)
-        return fail(KG_ERR_LIMIT, "the region of CALL " + kmer_text((int64_t)e[kg::kRegionErrLimit]) + " (its first_call): score or CALL count is 2^31 or more");
-    set->st.calls = (int64_t)n;
-    set->st.groups = (int64_t)n_groups;
-    set->st.regions = (int64_t)n_regions;
-    set->st.kept = (int64_t)e[kg::kRegionErrWords + kg::kRegionCntKept];
-    set->st.multi_frame = (int64_t)e[kg::kRegionErrWords + kg::kRegionCntMulti];
-    HIP_TRY(hipEventElapsedTime(&set->st.ms, t->ev[0], t->ev[1]));
-    // the two arrays of the set leave the scratch: everything else goes back to the cache
-    for (void *keep : {(void *)d_out, (void *)d_start}) sc.ptrs.erase(std::find(sc.ptrs.begin(), sc.ptrs.end(), keep));
-    set->d_regions = d_out;
-    set->d_seq_start = d_start;
-    set->count = (int64_t)n_regions;
-    set->n_seqs = (int64_t)n_seqs;
-    return KG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int kg_result_regions(kg_result *r, const kg_region_params *p, const int64_t *offsets, kg_regionset **out)
-{
-    if (!out) return fail(KG_ERR_ARG, "null argument");
-    *out = nullptr;
-    if (!r) return fail(KG_ERR_ARG, "null kg_result");
-    int rc = check_region_params(p);
-    if (rc) return rc;
-    if (!r->d_ccs) return fail(KG_ERR_ARG, "a KG_F_SKIP_AGGREGATE result has no CALL records to merge");
-    if (r->per != 6) return fail(KG_ERR_ARG, "a protein (-a) result: regions need a DNA scan, six containers per sequence");
-    int64_t l_max = 0;
-    if ((rc = check_region_offsets(offsets, r->st.n_seqs, &l_max))) return rc;
-    if ((uint64_t)r->st.n_calls >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more CALL records in one call");
-    kg_table *t = r->tab;
-    if (t->busy.exchange(1) != 0) return fail(KG_ERR_BUSY, "a kg_scan* is in flight on this result's kg_table");
-    struct BusyGuard { kg_table *t; ~BusyGuard() { t->fail_alloc_at = 0; t->busy.store(0); } } busy_guard{t};
-    t->fail_alloc_at = test_hook("KG_TEST_FAIL_ALLOC");
-    t->alloc_count = 0;
-    HIP_TRY(hipSetDevice(t->device));
-    kg_regionset *set = new (std::nothrow) kg_regionset();
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = t;
-    rc = regions_impl(t, p, r->d_calls, (uint64_t)r->st.n_calls, offsets, (uint64_t)r->st.n_seqs, l_max, set);
-    if (rc) { delete set; return rc; }
-    *out = set;
-    return KG_OK;
-}
-
-int kg_regions_calls(int device, const kg_region_params *p, const kg_call *calls, int64_t n_calls, const int64_t *offsets,
-                     int64_t n_seqs, kg_regionset **out)
-{
-    if (!out) return fail(KG_ERR_ARG, "null argument");
-    *out = nullptr;
-    int rc = check_region_params(p);
-    if (rc) return rc;
-    if (n_calls < 0) return fail(KG_ERR_ARG, "n_calls < 0");
-    if ((uint64_t)n_calls >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more CALL records in one call");
-    if (n_calls && !calls) return fail(KG_ERR_ARG, "null CALL records");
-    int64_t l_max = 0;
-    if ((rc = check_region_offsets(offsets, n_seqs, &l_max))) return rc;
-    if (n_calls && n_seqs == 0) return fail(KG_ERR_ARG, "CALL 0: container >= 6 * n_seqs");
-    kg_table *t = nullptr;
-    if ((rc = table_new(device, &t))) return rc;
-    kg_regionset *set = new (std::nothrow) kg_regionset();
-    if (!set) { kg_table_close(t); return fail(KG_ERR_NOMEM, "out of host memory"); }
-    set->tab = t;
-    set->own_tab = true;
-    t->fail_alloc_at = test_hook("KG_TEST_FAIL_ALLOC");
-    t->alloc_count = 0;
-    rc = [&]() -> int {                 // (the scratch blocks go back to the context's cache before the context is closed)
-        Scratch sc(t);
-        kg_call *d_calls = nullptr;
-        int rc2;
-        if ((rc2 = sc.get(&d_calls, n_calls ? (size_t)n_calls : 1))) return rc2;
-        if (n_calls) HIP_TRY(hipMemcpyAsync(d_calls, calls, (size_t)n_calls * sizeof(kg_call), hipMemcpyHostToDevice, t->stream));
-        return regions_impl(t, p, d_calls, (uint64_t)n_calls, offsets, (uint64_t)n_seqs, l_max, set);
-    }();
-    t->fail_alloc_at = 0;
-    if (rc) { delete set; kg_table_close(t); return rc; }
-    t->cache.release_free();
-    *out = set;
-    return KG_OK;
-}
-
-int64_t kg_regionset_count(const kg_regionset *s) { return s ? s->count : 0; }
-
-const kg_region *kg_regionset_device(const kg_regionset *s) { return s ? s->d_regions : nullptr; }
-
-int kg_regionset_copy(const kg_regionset *s, int64_t first, int64_t count, kg_region *dst)
-{
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_regionset_copy: range outside the set");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_regions + first, (size_t)count * sizeof(kg_region), hipMemcpyDefault));
-    return KG_OK;
-}
-
-int kg_regionset_seq_start(const kg_regionset *s, int64_t *dst)
-{
-    if (!s || !dst) return fail(KG_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_seq_start, ((size_t)s->n_seqs + 1) * 8, hipMemcpyDefault));
-    return KG_OK;
-}
-
-int kg_regionset_stats(const kg_regionset *s, kg_region_stats *out)
-{
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    *out = s->st;
-    return KG_OK;
-}
-
-void kg_regionset_free(kg_regionset *s)
-{
-    if (!s) return;
-    if (s->tab) {
-        (void)hipSetDevice(s->tab->device);
-        dfree(s->tab, s->d_regions);
-        dfree(s->tab, s->d_seq_start);
-        if (s->own_tab) kg_table_close(s->tab);
-    }
-    delete s;
-}
-
-}  // extern "C"
+// ---- the batch stages: each host beside its kernels ----
+#include "kg_host_build.hpp"
+#include "kg_host_derive.hpp"
+#include "kg_host_assign.hpp"
+#include "kg_host_regions.hpp"

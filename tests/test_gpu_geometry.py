@@ -63,7 +63,7 @@ OUT_OF_RANGE_DIRECT = {
 
 
 def _clamp(v, lo, hi, mult=1):
-    """kmerguts_hip.hip env_knob"""
+    """kg_host.hpp env_knob"""
     x = min(hi, max(lo, int(v)))
     return (x + mult - 1) // mult * mult
 
