@@ -104,3 +104,31 @@ def chunk_seq_ranges(off, want=4, dna=True, min_chunk_blocks=None):
             cuts.append(k)
     cuts.append(len(L))
     return [(cuts[i], cuts[i + 1]) for i in range(len(cuts) - 1)]
+
+
+def front_end_batches(lens, cap):
+    """[first, end) of the batches call_regions and annotate cut their input into: whole sequences, at most `cap` characters
+    a batch, a longer sequence alone in its own."""
+    out, k = [], 0
+    while k < len(lens):
+        j, size = k, 0
+        while j < len(lens) and (j == k or size + lens[j] <= cap):
+            size += lens[j]
+            j += 1
+        out.append((k, j))
+        k = j
+    return out
+
+
+def batch_caps(lens):
+    """Caps for a front end's input of these lengths, and what each is for: every sequence in a batch of its own; about half
+    of the sequences longer than the cap; several sequences a batch; everything but the last sequence in the first batch."""
+    lens = [int(x) for x in lens]
+    caps = {"one_each": min(a + b for a, b in zip(lens, lens[1:])) - 1, "median": sorted(lens)[len(lens) // 2],
+            "several": 4 * sorted(lens)[len(lens) // 2], "all_but_last": sum(lens[:-1])}
+    assert all(j - k == 1 for k, j in front_end_batches(lens, caps["one_each"]))
+    assert any(j - k == 1 and lens[k] > caps["median"] for k, j in front_end_batches(lens, caps["median"]))
+    assert any(j - k > 1 for k, j in front_end_batches(lens, caps["several"]))
+    assert front_end_batches(lens, caps["all_but_last"]) == [(0, len(lens) - 1), (len(lens) - 1, len(lens))]
+    assert all(len(front_end_batches(lens, c)) > 1 for c in caps.values())
+    return caps

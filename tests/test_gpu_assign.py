@@ -1,6 +1,6 @@
 """Function assignment on the GPU (kg_result_assign / kg_assign_calls): the device records must equal the numpy model of
 tests/assign_model.py byte for byte, on random CALL lists, known answers, edge shapes, -a scans of family sets and of the
-E. coli proteome under every scan strategy, and through the annotate front end; errors name the protein and failed
+E. coli proteome under every scan strategy, and through the annotate front end, in one batch and in several; errors name the protein and failed
 allocations leave nothing behind."""
 import gzip
 import os
@@ -303,3 +303,58 @@ def test_annotate_front_end(oracle, tmp_path, with_otu_index):
                                                                               int((ann & ~asg).sum()))
             assert agree > 0.7 * ann.sum()
         assert p.stdout.strip() == line
+
+
+def test_annotate_front_end_in_several_batches(oracle, tmp_path):
+    """annotate cuts its input at KmerGutsJava.MAX_BATCH_CHARS and copies each batch's assignments into its slice: the file
+    and the summary line do not depend on the cap, and equal the model's on the oracle's records of the whole input."""
+    from helpers import batch_caps, front_end_batches
+    from kmergutsjava_amd import annotate as AN
+    from kmergutsjava_amd import make_signatures as MS
+    from kmergutsjava_amd.kmer_guts_java import KmerGutsJava
+    seq, off, fn, otu = M.family_set(40, 8, 300, 0.04, 61, n_fn=12)
+    names = [b"fn_%02d" % (11 - f) for f in range(12)]
+    fam_ids = [b"prot%d" % i for i in range(len(fn))]
+    seqs = [seq[off[i]:off[i + 1]] for i in range(len(fn))]
+    (tmp_path / "p.faa").write_bytes(b"".join(b">%s desc\n%s\n" % (fam_ids[i], seqs[i]) for i in range(len(fn))))
+    (tmp_path / "a.tsv").write_bytes(b"".join(b"prot%d\t%s\tO%d\n" % (i, names[f], otu[i]) for i, f in enumerate(fn) if f >= 0))
+    d = tmp_path / "d"
+    MS.make_signatures(str(tmp_path / "p.faa"), str(tmp_path / "a.tsv"), str(tmp_path / "s.txt"), str(d))
+    fnames = [ln.split(b"\t", 1)[1] for ln in (d / "function.index").read_bytes().splitlines()]
+    onames = [ln.split(b"\t", 1)[1] for ln in (d / "otu.index").read_bytes().splitlines()]
+    img = open(d / "kmer.table.mem_map", "rb").read()
+    # the query: the families with proteins of no family between them (no CALL: a batch without any assignment when alone)
+    rng = np.random.default_rng(12)
+
+    def stranger(n):
+        return np.frombuffer(M.ALPHA, dtype=np.uint8)[rng.integers(0, 20, size=n)].tobytes()
+
+    ids = list(fam_ids)
+    for at, length, name in ((100, 200, b"stranger_a"), (200, 2000, b"stranger_long")):
+        seqs.insert(at, stranger(length))
+        ids.insert(at, name)
+    seqs.append(stranger(50))
+    ids.append(b"stranger_last")
+    n = len(seqs)
+    lens = [len(x) for x in seqs]
+    (tmp_path / "q.faa").write_bytes(b"".join(b">%s\n%s\n" % (ids[i], seqs[i]) for i in range(n)))
+    off2 = np.zeros(n + 1, dtype=np.int64)
+    off2[1:] = np.cumsum(lens)
+    ora = oracle.run(img, np.frombuffer(b"".join(seqs), dtype=np.uint8), off2, aa=True, lookup_mode=1)
+    want = A.assign(ora["calls"], ora["container_call_start"], ora["otu"], 0, 50)
+    assert want["n_calls"][100] == 0 and want["n_calls"][200] == 0 and want["assigned"].sum() > 100
+    assert 0 < (want["assigned"] == 0).sum()
+    caps = batch_caps(lens)
+    assert len(front_end_batches(lens, KmerGutsJava.MAX_BATCH_CHARS)) == 1
+    assert (100, 101) in front_end_batches(lens, caps["one_each"]) and (200, 201) in front_end_batches(lens, caps["several"])
+    line = "Proteins: %d, with calls: %d, assigned: %d" % (n, (want["n_calls"] > 0).sum(), want["assigned"].sum())
+    keep = KmerGutsJava.MAX_BATCH_CHARS
+    try:
+        for what, cap in [("default", keep)] + sorted(caps.items()):
+            KmerGutsJava.MAX_BATCH_CHARS = cap
+            out = tmp_path / "o.tsv"
+            got = AN.annotate(str(d), str(tmp_path / "q.faa"), str(out), write_all=True)
+            assert out.read_bytes() == _expected_lines(ids, want, fnames, onames, True), (what, cap)
+            assert got == line, (what, cap)
+    finally:
+        KmerGutsJava.MAX_BATCH_CHARS = keep

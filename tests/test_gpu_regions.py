@@ -1,6 +1,6 @@
 """Function regions on the GPU (kg_result_regions / kg_regions_calls): the device records must equal the numpy model of
 tests/regions_model.py byte for byte, on random CALL lists, known answers, edge shapes, DNA scans of planted contigs and of the
-E. coli genome under every scan strategy, and through the call_regions front end; the records of a contig do not depend on its
+E. coli genome under every scan strategy, and through the call_regions front end, in one batch and in several; the records of a contig do not depend on its
 batch; errors name the CALL or contig and failed allocations leave nothing behind."""
 import gzip
 import os
@@ -346,3 +346,50 @@ def test_call_regions_front_end(oracle, tmp_path, gz):
     p = subprocess.run([sys.executable, "-m", "kmergutsjava_amd.call_regions", "-D", str(tmp_path / "nothing"), "-q", str(q), "-o",
                         str(tmp_path / "x")], capture_output=True, text=True, cwd=root)
     assert p.returncode == 1 and p.stderr.startswith("Error:")
+
+
+def test_call_regions_front_end_in_several_batches(oracle, tmp_path):
+    """call_regions cuts its input at KmerGutsJava.MAX_BATCH_CHARS, rebases seq and joins region_start: the file and the
+    summary line do not depend on the cap, and equal the model's on the oracle's CALLs of the whole input."""
+    from helpers import batch_caps, front_end_batches
+    from kmergutsjava_amd import call_regions as CR
+    from kmergutsjava_amd import synth
+    from kmergutsjava_amd.kmer_guts_java import KmerGutsJava
+    img, dna, off, _ = _workload("planted")
+    rng = np.random.default_rng(11)
+    seqs = [dna[off[k]:off[k + 1]] for k in range(len(off) - 1)]
+
+    def spacer(n):
+        return bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), size=n))
+
+    seqs.insert(10, spacer(3000))           # no gene: a batch without any region when it is alone
+    seqs.insert(20, spacer(40_000))         # longer than the "several" cap
+    seqs.append(spacer(700))
+    n = len(seqs)
+    lens = [len(x) for x in seqs]
+    ids = [b"contig_%d" % k for k in range(n)]
+    q = tmp_path / "c.fna"
+    q.write_bytes(b"".join(b">%s planted genes\n%s\n" % (ids[k], seqs[k]) for k in range(n)))
+    d = tmp_path / "d"
+    synth.write_data_dir(str(d), img, 50)
+    fnames = [b"synthetic function %d" % i for i in range(50)]
+    off2 = np.zeros(n + 1, dtype=np.int64)
+    off2[1:] = np.cumsum(lens)
+    calls = oracle.run(img, np.frombuffer(b"".join(seqs), dtype=np.uint8), off2, lookup_mode=1, min_hits=4)["calls"]
+    want = R.regions(calls, off2, 300, 12, 100)
+    per = np.diff(want[1])
+    assert per[10] == 0 and per[:10].sum() > 0 and per[11:20].sum() > 0 and 0 < want[0]["kept"].sum() < len(want[0])
+    caps = batch_caps(lens)
+    assert len(front_end_batches(lens, KmerGutsJava.MAX_BATCH_CHARS)) == 1
+    assert (10, 11) in front_end_batches(lens, caps["one_each"]) and (20, 21) in front_end_batches(lens, caps["several"])
+    keep = KmerGutsJava.MAX_BATCH_CHARS
+    try:
+        for what, cap in [("default", keep)] + sorted(caps.items()):
+            KmerGutsJava.MAX_BATCH_CHARS = cap
+            for kw in ({"write_all": True}, {"gff": True}):
+                out = tmp_path / "o.txt"
+                line = CR.call_regions(str(d), str(q), str(out), min_hits=4, merge_gap=300, min_score=12, min_len=100, **kw)
+                assert out.read_bytes() == CR.format_regions(ids, want[0], fnames, **kw), (what, cap, kw)
+                assert line == CR.summary_of(*want), (what, cap, kw)
+    finally:
+        KmerGutsJava.MAX_BATCH_CHARS = keep

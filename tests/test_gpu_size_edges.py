@@ -1,8 +1,15 @@
-"""Size boundaries of the device primitives that the table build, signature derivation and assignment share: the radix
-sort's 4096-item tiles, 1024-item waves and 64-item ballot steps, the tile scan's steps of 256 tiles, the 16 items per thread
-of the derive's segmented passes, the key width ceil(log2 n_prot), the 64-window blocks, and kAssignShort / kAssignWalk.
-Each case sits on, or next to, one of those edges and is checked against an exact reference written here with Python
-integers (and against the torch / numpy models of tests/)."""
+"""Size boundaries of the device primitives that the table build, signature derivation, assignment and function regions
+share: the radix sort's 4096-item tiles, 1024-item waves and 64-item ballot steps, the tile scan's steps of 256 tiles, the 16
+items per thread of the derive's segmented passes, the key width ceil(log2 n_prot), the 64-window blocks, and kAssignShort /
+kAssignWalk.  Each case sits on, or next to, one of those edges and is checked against an exact reference written here with
+Python integers (and against the torch / numpy models of tests/).
+
+The region stage (kg_regions.hpp, kg_host_regions.hpp) adds edges of its own, with the cases of tests/region_cases.py: the
+running maximum of region_heads_kernel carried over a thread's 16 items, a wave's 1024, a tile's 4096 and the tile scan's step at
+item 256 * 4096, by nested runs and by runs that split, or just do not, at the boundary; region_walk_kernel's loads of 16
+items, with regions of 15, 16, 17, 32 and 33 CALLs and a last region that ends at n; list sizes at the sort's edges where
+every x0 is equal; and the key widths of its four sorts, with contigs of 3 to 2^31 - 1 nt (left_bits up to 31, 33 + left_bits
+up to 64) and 1 to 32769 contigs."""
 import os
 import sys
 from fractions import Fraction
@@ -14,6 +21,8 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import assign_model as A  # noqa: E402
+import region_cases as RC  # noqa: E402
+import regions_model as R  # noqa: E402
 import signature_model as M  # noqa: E402
 
 from kmergutsjava_amd import _native as N  # noqa: E402
@@ -405,3 +414,95 @@ def test_assign_long_proteins_per_batch(n_long):
     calls, cs = _batch(prots)
     assert int(((cs[1:] - cs[:-1]) > 16).sum()) == n_long
     _check_assign(calls, cs)
+
+
+# ---------------------------------------------------------------- function regions ----
+
+REGION_BRUTE_MAX = 20_000          # CALLs up to which the plain loops are the reference; the numpy model above
+
+
+def _check_regions(case):
+    from kmergutsjava_amd import hotpath
+    want = (R.brute_force if len(case.calls) <= REGION_BRUTE_MAX else R.regions)(*case.args)
+    RC.check_expect(case, *want)
+    counted = RC.counted(case.calls, want[0])
+    for device_out in (False, True):
+        st = {}
+        regs, start = hotpath.region_calls(*case.args, device_out=device_out, stats=st)
+        if device_out:
+            regs = regs.cpu().numpy().view(N.REGION_DTYPE)
+        assert regs.tobytes() == want[0].tobytes(), (case.name, device_out, len(regs), len(want[0]))
+        assert start.tobytes() == want[1].tobytes(), (case.name, device_out)
+        assert {k: st[k] for k in counted} == counted, (case.name, device_out)
+
+
+def _region_params(family):
+    return [pytest.param(v, id=RC.case_id(v)) for v in RC.CASES[family]]
+
+
+@pytest.mark.parametrize("values", _region_params("nested"))
+def test_regions_nested_run_across_slices(values):
+    """(lead, run, follow): one CALL covers the `run` - 1 behind it, from item `lead` on: one region, whose maximum comes over
+    every thread, wave and tile edge inside the run; follow: the next group starts under that maximum and is three regions"""
+    _check_regions(RC.make("nested", values))
+
+
+@pytest.mark.parametrize("values", _region_params("split"))
+def test_regions_split_run_at_a_slice_edge(values):
+    """(boundary, where, merge_gap, twin): the first item behind the boundary, or the last in front, lies merge_gap + 2 nt
+    behind the maximum (a new region) or merge_gap + 1 (none)"""
+    _check_regions(RC.make("split", values))
+
+
+def test_regions_run_across_the_tile_scan_step():
+    """a nested run of 4001 CALLs over item 256 * 4096, its maximum in front: tile_pre of the tile scan's second step"""
+    _check_regions(RC.make("step", ()))
+
+
+@pytest.mark.parametrize("values", _region_params("walk"))
+def test_regions_walk_lengths_and_list_end(values):
+    """(lead, tail): regions of 15, 16, 17, 32, 33 CALLs and `tail`, the last one ending at n"""
+    _check_regions(RC.make("walk", values))
+
+
+@pytest.mark.parametrize("values", _region_params("sizes"))
+def test_regions_list_sizes_with_equal_keys(values):
+    """(n, flavour): n CALLs with x0 = 0 on contigs of 3 nt: the order inside a region is the sorts' stability"""
+    _check_regions(RC.make("sizes", values))
+
+
+@pytest.mark.parametrize("values", _region_params("lmax"))
+def test_regions_contig_length_key_widths(values):
+    """(L, merge_gap, min_len): the longest contig where the pass counts of the x0 sort (left_bits) and of the
+    (right, strand, fI) sort (33 + left_bits) change, up to 2^31 - 1 nt"""
+    _check_regions(RC.make("lmax", values))
+
+
+@pytest.mark.parametrize("values", _region_params("nseqs"))
+def test_regions_contig_count_key_widths(values):
+    """(n_seqs, L): the number of contigs where 32 + bits_for(2 n_seqs) and left_bits + bits_for(n_seqs) pass 8, 16, 24,
+    40 and 48 bits"""
+    _check_regions(RC.make("nseqs", values))
+
+
+def test_regions_contig_length_limit():
+    """2^31 nt in one contig is KG_ERR_LIMIT and names the contig; 2^31 - 1 nt with a CALL ending at L - 1 is fine; a CALL
+    ending at L is outside its contig"""
+    from kmergutsjava_amd import hotpath
+    L = RC.INT_MAX
+    c = np.zeros(2, dtype=N.CALL_DTYPE)                 # contig 1, '+': frame 0 codon 0, and frame 1 up to x1 = L - 1
+    c["container"], c["start"], c["end"], c["count"], c["fI"] = [6, 7], [0, (L - 4) // 3], [0, (L - 4) // 3], 3, 1
+    assert 1 + 3 * int(c["end"][1]) + 2 == L - 1
+    off = np.array([0, 5, 5 + L], np.int64)
+    regs, start = hotpath.region_calls(c, off, 0)
+    assert regs["right"].tolist() == [2, L - 1] and start.tolist() == [0, 0, 2]
+    assert regs.tobytes() == R.brute_force(c, off, 0)[0].tobytes()
+    with pytest.raises(N.KmerGutsNativeError) as ei:
+        hotpath.region_calls(c, np.array([0, 5, 5 + L + 1], np.int64), 0)
+    assert ei.value.code == N.KG_ERR_LIMIT and "contig 1" in str(ei.value) and "2^31" in str(ei.value)
+    bad = c.copy()
+    bad["container"][1], bad["start"][1], bad["end"][1] = 8, (L - 4) // 3, (L - 4) // 3          # frame 2: x1 = L
+    assert 2 + 3 * int(bad["end"][1]) + 2 == L
+    with pytest.raises(N.KmerGutsNativeError) as ei:
+        hotpath.region_calls(bad, off, 0)
+    assert ei.value.code == N.KG_ERR_ARG and "CALL 1" in str(ei.value) and "outside" in str(ei.value)

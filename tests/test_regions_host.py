@@ -1,5 +1,5 @@
-"""Function regions without a GPU: the numpy model of tests/regions_model.py against plain loops, known answers worked out by
-hand, the round trip (family proteins -> signatures -> table -> genes planted on contigs -> the CPU oracle's DNA scan -> the
+"""Function regions without a GPU: the numpy model of tests/regions_model.py against plain loops (on random lists and on the
+size-edge cases of tests/region_cases.py, before a GPU sees them), known answers worked out by hand, the round trip (family proteins -> signatures -> table -> genes planted on contigs -> the CPU oracle's DNA scan -> the
 model finds the genes, frameshifted ones as one region), the new structures against the C layout, and the call_regions
 writers."""
 import os
@@ -12,6 +12,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import region_cases as RC  # noqa: E402
 import regions_model as R  # noqa: E402
 
 from kmergutsjava_amd import _native as N  # noqa: E402
@@ -45,6 +46,38 @@ def test_model_matches_brute_force(seed):
     b, sb = R.brute_force(calls, off, gap, ms, ml)
     assert a.tobytes() == b.tobytes() and sa.tobytes() == sb.tobytes()
     assert sa[0] == 0 and sa[-1] == len(a) and (np.diff(sa) >= 0).all()
+
+
+@pytest.mark.parametrize("family,values", [pytest.param(f, v, id="%s-%s" % (f, RC.case_id(v)))
+                                           for f in RC.CASES if f != "step" for v in RC.CASES[f]])
+def test_edge_cases_model_matches_brute_force(family, values):
+    """Every size-edge case but the tile scan's step: both references give the same bytes, and the answers the case states."""
+    case = RC.make(family, values)
+    assert (np.diff(case.calls["container"].astype(np.int64)) >= 0).all()
+    a, sa = R.regions(*case.args)
+    b, sb = R.brute_force(*case.args)
+    assert a.tobytes() == b.tobytes() and sa.tobytes() == sb.tobytes()
+    RC.check_expect(case, a, sa)
+    RC.check_expect(case, b, sb)
+
+
+def test_edge_case_step_model_matches_brute_force_on_its_contig():
+    """The tile scan's step: the run really crosses item 256 * 4096 of the group order, and the model's records of the run's
+    contig equal the plain loops' over that contig alone (seq and first_call are relative to the list)."""
+    case = RC.make("step", ())
+    s, lead = case.expect["contig"], case.expect["lead"]
+    assert len(case.calls) == RC.STEP + 2002 and lead < RC.STEP < lead + RC.STEP_RUN - 1
+    on = case.calls["container"] // 6 == s
+    assert np.array_equal(np.flatnonzero(on), np.arange(lead, len(case.calls)))       # every filler group lies in front
+    a, sa = R.regions(*case.args)
+    RC.check_expect(case, a, sa)
+    sub = case.calls[on].copy()
+    sub["container"] -= 6 * s
+    b, sb = R.brute_force(sub, case.offsets[s:s + 2] - case.offsets[s], *case.args[2:])
+    mine = a[sa[s]:sa[s + 1]].copy()
+    mine["seq"] -= s
+    mine["first_call"] -= lead
+    assert mine.tobytes() == b.tobytes() and sb.tolist() == [0, len(mine)] and sa[-1] == len(a)
 
 
 KNOWN_OFF = np.array([0, 50, 150], np.int64)      # contig 1 has 100 nt
