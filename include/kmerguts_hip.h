@@ -10,6 +10,7 @@
  * table back to kmer.table.mem_map[.gz], and kg_signatures_derive* makes that list from annotated proteins.
  * kg_result_assign / kg_assign_calls turn the CALL records of an -a scan into one function per protein.
  * kg_result_regions / kg_regions_calls merge the CALL records of a DNA scan into function regions in contig coordinates.
+ * kg_regionset_orfs / kg_orfs_regions extend every region to its open reading frame and extract the translated protein.
  *
  * Conventions: plain pointers and sizes only; every function returns an int status
  * (KG_OK == 0, negative == error) and never throws or aborts across the boundary; the text
@@ -404,6 +405,93 @@ int kg_regionset_copy(const kg_regionset *s, int64_t first, int64_t count, kg_re
 int kg_regionset_seq_start(const kg_regionset *s, int64_t *dst);
 int kg_regionset_stats(const kg_regionset *s, kg_region_stats *out);
 void kg_regionset_free(kg_regionset *s);
+
+/* ---- open reading frames: function regions -> the ORF around each and its translated protein (kernels: kg_orfs.hpp) ----
+ *
+ * The reference stops at the CALL lines; this rule is the project's own.
+ * Input: a region set in output order, the batch's sequence bytes exactly as the scan got them, and offsets[n_seqs + 1].
+ * One ORF record per region, index-aligned: orf[i] belongs to region[i].
+ *   1. Strand and frame.  The strand is the region's, the frame is f = best_frame.  L = offsets[s+1] - offsets[s].  Strand
+ *      nucleotide x is seq[x] on '+'; on '-' it is the complement of seq[L-1-x], taken on dna_code values (3 - c for c < 4, and
+ *      4 stays 4): the reverse complement is never materialised.  Codon j of frame f is x = f+3j .. f+3j+2, for
+ *      0 <= j < n_f = floor((L-f)/3) (n_f = 0 when L < f).  Codon classes by dna_code (a/A c/C g/G t/T/u/U, as the scan reads
+ *      them): stop = TAA, TAG, TGA; start = the members of start_codons, a bit mask with 1 = ATG, 2 = GTG, 4 = TTG (default 7;
+ *      with 0 there is no start search); unknown = any base of code 4 -- an unknown codon is neither stop nor start.
+ *   2. Anchor.  The region's strand extent is [xa, xb]: left and right on '+', mirrored with L - 1 - x on '-'.
+ *      j0 = ceil((xa - f)/3) is the first codon of frame f that lies wholly inside the region, j1 = floor((xb - 2 - f)/3) the
+ *      last.  A region that comes from kg_result_regions always has 0 <= j0 <= j1 < n_f, because its best-frame CALL lies
+ *      inside it.  For caller-held regions, a region that breaks this is an error; so are a bad seq, strand or best_frame,
+ *      left > right and right >= L.
+ *   3. Extension.  u = the largest j < j0 that is a stop, else -1.  e = the smallest j > j1 that is a stop, else n_f.
+ *      b = the smallest j in (u, j0] that is a start, else u + 1.  i* = the smallest j >= j0 that is a stop; the region is
+ *      interrupted when i* <= j1.  The ORF is codons b .. e: the stop codon is inside the coordinates, not inside the protein.
+ *      When e == n_f it is b .. n_f - 1.
+ *   4. Record kg_orf (48 bytes, twelve 32-bit fields): seq, strand, frame; left, right -- 0-based inclusive on the contig as
+ *      given, mirrored for '-'; n_res = min(e, n_f) - b; start_codon -- 0 none, 1 ATG, 2 GTG, 3 TTG; first_inner -- the index in
+ *      the protein of codon i* when interrupted, else -1; flags -- KG_ORF_HAS_STOP when e < n_f, KG_ORF_PARTIAL5 when u == -1,
+ *      KG_ORF_INTERRUPTED, KG_ORF_MULTI_FRAME when the region has more than one frame bit; fI, score, kept -- copied from the
+ *      region.  A multi-frame region gets its best frame's ORF and will usually be interrupted: frameshifts are reported, not
+ *      repaired.
+ *   5. Protein.  The residues of codons b .. min(e, n_f) - 1: each is the genetic code's letter (KGJ:88-93), an inner stop is
+ *      '*', an unknown codon is 'X', and residue 0 is 'M' whenever start_codon != 0.  Proteins are laid end to end in ORF order
+ *      behind prot_start[n_orfs + 1] (int64).  With only_kept = 1 (the default), an ORF whose region is not kept has length 0
+ *      there; its record is still written.
+ *   6. Independence.  The output depends only on (regions, bytes, offsets): not on launch geometry, tile size or batch
+ *      neighbours.  Identical ORFs from regions of different functions are not merged.
+ * Errors: KG_ERR_ARG for bad params (start_codons outside 0..7, only_kept outside 0..1), null pointers, n_seqs that is not the
+ * set's, decreasing offsets, and the region errors of rule 2 -- each message names the first offending region (or contig);
+ * KG_ERR_LIMIT for 2^31 or more regions, contigs or nucleotides of one contig, or 2^32 or more residues; KG_ERR_BUSY while a
+ * kg_scan* is in flight on the set's table; KG_ERR_NOMEM.  A bad region is never used as an index.  Zero regions and zero
+ * sequences are valid.  Device allocations come from the block cache of the region set's context (a table-less one for
+ * kg_orfs_regions), so KG_TEST_FAIL_ALLOC applies; everything but the ORF set's three arrays is back in the cache when the call
+ * returns.  An ORF set made by kg_regionset_orfs holds blocks of the region set's context and must be freed before it. */
+#define KG_ORF_HAS_STOP     1u
+#define KG_ORF_PARTIAL5     2u
+#define KG_ORF_INTERRUPTED  4u
+#define KG_ORF_MULTI_FRAME  8u
+typedef struct kg_orf_params { int32_t start_codons; int32_t only_kept; int32_t reserved; } kg_orf_params;
+typedef struct kg_orf {          /* 48 B */
+    int32_t  seq;
+    int32_t  strand;       /* 0 '+', 1 '-'                                              */
+    int32_t  frame;
+    int32_t  left;         /* 0-based, inclusive, on the contig as given                */
+    int32_t  right;
+    int32_t  n_res;        /* residues of the protein (the stop codon is not one)       */
+    int32_t  start_codon;  /* 0 none, 1 ATG, 2 GTG, 3 TTG                               */
+    int32_t  first_inner;  /* protein index of the first stop inside the region, or -1  */
+    uint32_t flags;        /* KG_ORF_*                                                  */
+    int32_t  fI;
+    int32_t  score;
+    int32_t  kept;
+} kg_orf;
+typedef struct kg_orf_stats {
+    int64_t orfs;
+    int64_t complete;      /* stop, start and not interrupted                           */
+    int64_t interrupted;
+    int64_t partial5;
+    int64_t residues;      /* bytes behind prot_start                                   */
+    int64_t tiles;         /* tile summaries written per scanned array                  */
+    float   ms;            /* device time of the call's kernels                         */
+    int32_t reserved;
+} kg_orf_stats;
+typedef struct kg_orfset kg_orfset;
+/* the regions stay in HBM; seq: the batch's bytes, in device memory when seq_on_device != 0; offsets: host, n_seqs + 1 */
+int kg_regionset_orfs(kg_regionset *set, const kg_orf_params *p, const uint8_t *seq, int seq_on_device, const int64_t *offsets,
+                      int64_t n_seqs, kg_orfset **out);
+/* caller-held host lists: regions[n_regions] in any order, seq and offsets[n_seqs + 1] on the host */
+int kg_orfs_regions(int device, const kg_orf_params *p, const kg_region *regions, int64_t n_regions, const uint8_t *seq,
+                    const int64_t *offsets, int64_t n_seqs, kg_orfset **out);
+int64_t kg_orfset_count(const kg_orfset *s);
+/* device array of kg_orfset_count(s) kg_orf records, valid until kg_orfset_free */
+const kg_orf *kg_orfset_device(const kg_orfset *s);
+/* records [first, first + count) into dst (host or device memory) */
+int kg_orfset_copy(const kg_orfset *s, int64_t first, int64_t count, kg_orf *dst);
+/* prot_start[count + 1] into dst (host or device memory) */
+int kg_orfset_prot_start(const kg_orfset *s, int64_t *dst);
+/* residue bytes [first, first + count) of the concatenated proteins into dst (host or device memory) */
+int kg_orfset_residues(const kg_orfset *s, int64_t first, int64_t count, uint8_t *dst);
+int kg_orfset_stats(const kg_orfset *s, kg_orf_stats *out);
+void kg_orfset_free(kg_orfset *s);
 
 /* the resident 24-byte records, valid until kg_table_close, and how many there are: num_sigs for a built or adopted table, the
  * whole records of the file for an opened one (fewer than num_sigs for a truncated file, more for a longer one) */

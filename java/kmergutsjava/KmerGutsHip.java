@@ -134,6 +134,33 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_orf_params (kg_regionset_orfs / kg_orfs_regions); this project's defaults: 7 (ATG, GTG, TTG), 1 and 0. */
+    class KgOrfParams extends Structure {
+        public int start_codons, only_kept, reserved;
+        public KgOrfParams() {
+            setFieldOrder(new String[] {"start_codons", "only_kept", "reserved"});
+        }
+    }
+
+    /** struct kg_orf (48 B): the open reading frame around one function region, 0-based inclusive left / right. */
+    class KgOrf extends Structure {
+        public int seq, strand, frame, left, right, n_res, start_codon, first_inner, flags, fI, score, kept;
+        public KgOrf() {
+            setFieldOrder(new String[] {"seq", "strand", "frame", "left", "right", "n_res", "start_codon", "first_inner", "flags",
+                    "fI", "score", "kept"});
+        }
+    }
+
+    /** struct kg_orf_stats. */
+    class KgOrfStats extends Structure {
+        public long orfs, complete, interrupted, partial5, residues, tiles;
+        public float ms;
+        public int reserved;
+        public KgOrfStats() {
+            setFieldOrder(new String[] {"orfs", "complete", "interrupted", "partial5", "residues", "tiles", "ms", "reserved"});
+        }
+    }
+
     // replaces readKmerTableHeader + the table stream of lookup (KmerGutsJava.java:924-942, 944-1034)
     int kg_table_open(String path, int device, PointerByReference out);
     int kg_table_from_memory(Pointer image, long nbytes, int device, PointerByReference out);
@@ -196,6 +223,18 @@ public interface KmerGutsHip extends Library {
     int kg_regionset_seq_start(Pointer set, long[] dst);     // long[nSeqs + 1]
     int kg_regionset_stats(Pointer set, KgRegionStats out);
     void kg_regionset_free(Pointer set);
+    /** function regions -> the open reading frame around each and its protein; seq = the bytes the scan was given */
+    int kg_regionset_orfs(Pointer set, KgOrfParams params, Pointer seq, int seqOnDevice, long[] offsets, long nSeqs,
+                          PointerByReference out);
+    int kg_orfs_regions(int device, KgOrfParams params, Pointer regions, long nRegions, Pointer seq, long[] offsets, long nSeqs,
+                        PointerByReference out);
+    long kg_orfset_count(Pointer set);
+    Pointer kg_orfset_device(Pointer set);                   // kg_orf[count] in device memory, index-aligned with the regions
+    int kg_orfset_copy(Pointer set, long first, long count, Pointer dst);
+    int kg_orfset_prot_start(Pointer set, long[] dst);       // long[count + 1]
+    int kg_orfset_residues(Pointer set, long first, long count, Pointer dst);
+    int kg_orfset_stats(Pointer set, KgOrfStats out);
+    void kg_orfset_free(Pointer set);
     void kg_result_free(Pointer result);
     int kg_restore_hits_device(int device, Pointer dSrc, long nHits, Pointer dSeqFirst, long nSeqs, Pointer dDstFirst,
                                Pointer dContainerShift, Pointer dDst, Pointer stream);

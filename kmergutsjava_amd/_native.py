@@ -36,6 +36,8 @@ EXPORTS = (
     "kg_sigset_stats", "kg_sigset_free", "kg_result_assign", "kg_assign_calls",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
+    "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
+    "kg_orfset_residues", "kg_orfset_stats", "kg_orfset_free",
     "kg_last_error", "kg_version",
 )
 
@@ -63,6 +65,13 @@ REGION_DTYPE = np.dtype([("seq", "<i4"), ("strand", "<i4"), ("left", "<i4"), ("r
                          ("weighted", "<f4"), ("n_calls", "<i4"), ("frames", "<u4"), ("best_frame", "<i4"),
                          ("first_call", "<u4"), ("kept", "<i4")])
 assert REGION_DTYPE.itemsize == 48
+# struct kg_orf (kg_regionset_orfs / kg_orfs_regions): the open reading frame around one function region
+ORF_DTYPE = np.dtype([("seq", "<i4"), ("strand", "<i4"), ("frame", "<i4"), ("left", "<i4"), ("right", "<i4"), ("n_res", "<i4"),
+                      ("start_codon", "<i4"), ("first_inner", "<i4"), ("flags", "<u4"), ("fI", "<i4"), ("score", "<i4"),
+                      ("kept", "<i4")])
+assert ORF_DTYPE.itemsize == 48
+ORF_HAS_STOP, ORF_PARTIAL5, ORF_INTERRUPTED, ORF_MULTI_FRAME = 1, 2, 4, 8
+ORF_TILE_CODONS = 128       # kg_orfs.hpp kOrfTile: the codons of one tile summary (tests aim at its edges)
 assert HIT_DTYPE.itemsize == 24 and CALL_DTYPE.itemsize == 24 and OTU_DTYPE.itemsize == 44
 
 
@@ -126,6 +135,20 @@ class KgRegionStats(C.Structure):
     """struct kg_region_stats."""
     _fields_ = [("calls", C.c_int64), ("groups", C.c_int64), ("regions", C.c_int64), ("kept", C.c_int64),
                 ("multi_frame", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
+class KgOrfParams(C.Structure):
+    """struct kg_orf_params (kg_regionset_orfs / kg_orfs_regions)."""
+    _fields_ = [("start_codons", C.c_int32), ("only_kept", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgOrfStats(C.Structure):
+    """struct kg_orf_stats."""
+    _fields_ = [("orfs", C.c_int64), ("complete", C.c_int64), ("interrupted", C.c_int64), ("partial5", C.c_int64),
+                ("residues", C.c_int64), ("tiles", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
@@ -218,6 +241,18 @@ def load() -> C.CDLL:
     lib.kg_regionset_stats.argtypes = [vp, C.POINTER(KgRegionStats)]
     lib.kg_regionset_free.argtypes = [vp]
     lib.kg_regionset_free.restype = None
+    lib.kg_regionset_orfs.argtypes = [vp, C.POINTER(KgOrfParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
+    lib.kg_orfs_regions.argtypes = [C.c_int, C.POINTER(KgOrfParams), vp, C.c_int64, vp, vp, C.c_int64, C.POINTER(vp)]
+    lib.kg_orfset_count.argtypes = [vp]
+    lib.kg_orfset_count.restype = C.c_int64
+    lib.kg_orfset_device.argtypes = [vp]
+    lib.kg_orfset_device.restype = vp
+    lib.kg_orfset_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.kg_orfset_prot_start.argtypes = [vp, vp]
+    lib.kg_orfset_residues.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.kg_orfset_stats.argtypes = [vp, C.POINTER(KgOrfStats)]
+    lib.kg_orfset_free.argtypes = [vp]
+    lib.kg_orfset_free.restype = None
     lib.kg_last_error.restype = C.c_char_p
     lib.kg_version.restype = C.c_char_p
     for name in EXPORTS:

@@ -3,6 +3,7 @@
 
     python -m kmergutsjava_amd.call_regions -D KmerData -q contigs.fna[.gz] -o regions.tsv [-m 5] [-M 0] [-g 200] [-O]
                                             [--merge-gap 600] [--min-score 0] [--min-len 0] [--all] [--gff]
+                                            [--orfs ORFS.tsv] [--faa PROTEINS.faa] [--start-codons ATG,GTG,TTG]
 
 The table and function.index[.gz] are loaded the way annotate loads them.  Contigs are read with
 make_signatures.parse_fasta (a duplicate id is an error) and scanned whole, in batches of at most
@@ -12,6 +13,16 @@ KmerGutsJava.MAX_BATCH_CHARS characters.  Output, in FASTA order and inside a co
 with 1-based inclusive coordinates on the contig as given, strand + or -, weighted as %.9g, frames the frames of the region's
 CALLs (e.g. `0` or `0,2`; more than one: a frameshift candidate) and status kept or below.  --gff writes GFF3 lines with the
 same content instead.  Stdout: `Contigs: N, with calls: K, regions: R, kept: A, multi-frame: F`.
+
+--orfs and --faa extend every region to its open reading frame on the GPU (kg_regionset_orfs; include/kmerguts_hip.h states the
+rule) with the start codons of --start-codons (default ATG,GTG,TTG; `none` for no start search).  --orfs writes one line per
+written region:
+    contig_id<TAB>left+1<TAB>right+1<TAB>strand<TAB>frame<TAB>function<TAB>score<TAB>n_res<TAB>start<TAB>flags
+with start the start codon or `-`, and flags the words stop, partial5, interrupted, multi-frame joined by commas (or `-`).
+--faa writes `>contig_left+1_right+1_strand function` and the protein in 60-column lines, what annotate -p and
+make_signatures -p read; an ORF with the contig, strand, left and right of an earlier written one is written once, under the
+region with the largest score (ties: the first).  With either flag the summary line gains `, orfs: N, complete: C,
+interrupted: I` (complete: stop, start and not interrupted).
 """
 from __future__ import annotations
 
@@ -69,10 +80,73 @@ def format_regions(ids, regs, fnames, write_all: bool = False, gff: bool = False
     return b"".join(lines)
 
 
+START_NAMES = (b"ATG", b"GTG", b"TTG")
+FLAG_WORDS = ((1, b"stop"), (2, b"partial5"), (4, b"interrupted"), (8, b"multi-frame"))
+
+
+def parse_start_codons(text: str) -> int:
+    """`ATG,GTG,TTG` -> the start_codons mask (1 ATG, 2 GTG, 4 TTG); `none` or an empty text -> 0."""
+    mask = 0
+    for word in text.split(","):
+        w = word.strip().upper().encode()
+        if not w or w == b"NONE":
+            continue
+        if w not in START_NAMES:
+            raise ValueError("--start-codons: %r is none of ATG, GTG, TTG" % word)
+        mask |= 1 << START_NAMES.index(w)
+    return mask
+
+
+def orf_summary(orfs) -> str:
+    """What the summary line gains with --orfs / --faa, from ORF records (ORF_DTYPE)."""
+    fl = orfs["flags"]
+    complete = ((fl & 1) != 0) & (orfs["start_codon"] != 0) & ((fl & 4) == 0)
+    return ", orfs: %d, complete: %d, interrupted: %d" % (len(orfs), int(complete.sum()), int(((fl & 4) != 0).sum()))
+
+
+def format_orfs(ids, regs, orfs, fnames, write_all: bool = False) -> bytes:
+    """ORF records (ORF_DTYPE, index-aligned with regs) as text, one line per written region."""
+    lines = []
+    for r, o in zip(regs, orfs):
+        if not (r["kept"] or write_all):
+            continue
+        words = b",".join(w for bit, w in FLAG_WORDS if int(o["flags"]) & bit) or b"-"
+        start = START_NAMES[int(o["start_codon"]) - 1] if o["start_codon"] else b"-"
+        lines.append(b"%s\t%d\t%d\t%s\t%d\t%s\t%d\t%d\t%s\t%s\n" %
+                     (ids[int(o["seq"])], o["left"] + 1, o["right"] + 1, b"-" if o["strand"] else b"+", o["frame"],
+                      _fname(fnames, int(o["fI"])), o["score"], o["n_res"], start, words))
+    return b"".join(lines)
+
+
+def format_faa(ids, regs, orfs, prot_start, residues, fnames, write_all: bool = False) -> bytes:
+    """The proteins of the written regions as FASTA: an ORF with the (contig, strand, left, right) of an earlier written one is
+    written once, where the first of them stands, under the region with the largest score (ties: the first)."""
+    res = np.asarray(residues, dtype=np.uint8).tobytes()
+    best, order = {}, []
+    for i, (r, o) in enumerate(zip(regs, orfs)):
+        if not (r["kept"] or write_all) or prot_start[i + 1] == prot_start[i]:
+            continue
+        key = (int(o["seq"]), int(o["strand"]), int(o["left"]), int(o["right"]))
+        if key not in best:
+            best[key] = i
+            order.append(key)
+        elif o["score"] > orfs[best[key]]["score"]:
+            best[key] = i
+    out = []
+    for key in order:
+        i = best[key]
+        o = orfs[i]
+        out.append(b">%s_%d_%d_%s %s\n" % (ids[key[0]], key[2] + 1, key[3] + 1, b"-" if key[1] else b"+", _fname(fnames, int(o["fI"]))))
+        p = res[int(prot_start[i]):int(prot_start[i + 1])]
+        out += [p[k:k + 60] + b"\n" for k in range(0, len(p), 60)]
+    return b"".join(out)
+
+
 def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_weighted_hits: int = 0, max_gap: int = 200,
                  order_constraint: bool = False, merge_gap: int = 600, min_score: int = 0, min_len: int = 0,
-                 write_all: bool = False, gff: bool = False, device: int = 0) -> str:
-    """Write the regions; returns the summary line."""
+                 write_all: bool = False, gff: bool = False, device: int = 0, orfs_out: str = None, faa_out: str = None,
+                 start_codons: int = 7) -> str:
+    """Write the regions (and, with orfs_out / faa_out, their open reading frames and proteins); returns the summary line."""
     from . import hotpath
     from .kmer_guts_java import KmerGutsJava, _resident_table
     table_path = _data_file(data_dir, "kmer.table.mem_map")
@@ -85,6 +159,8 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
     params = hotpath.Params(aa=False, order_constraint=order_constraint, min_hits=min_hits, min_weighted_hits=min_weighted_hits,
                             max_gap=max_gap)
     parts, starts = [], [np.zeros(1, dtype=np.int64)]
+    want_orfs = orfs_out is not None or faa_out is not None
+    oparts, lens, residues = [], [], []
     k = 0
     while k < len(ids):
         j, size = k, 0
@@ -93,8 +169,16 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
             j += 1
         off = np.zeros(j - k + 1, dtype=np.int64)
         off[1:] = np.cumsum([len(s) for s in seqs[k:j]])
-        with tab.scan(b"".join(seqs[k:j]), off, params) as r:
-            regs, start = r.regions(off, merge_gap, min_score, min_len)
+        batch = b"".join(seqs[k:j])
+        with tab.scan(batch, off, params) as r:
+            if want_orfs:
+                regs, start, orfs, pstart, res = r.orfs(batch, off, merge_gap, min_score, min_len, start_codons, not write_all)
+                orfs["seq"] += k
+                oparts.append(orfs)
+                lens.append(np.diff(pstart))
+                residues.append(res)
+            else:
+                regs, start = r.regions(off, merge_gap, min_score, min_len)
         regs["seq"] += k
         parts.append(regs)
         starts.append(start[1:] + starts[-1][-1])
@@ -102,7 +186,21 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
     regs = np.concatenate(parts) if parts else np.zeros(0, dtype=hotpath.N.REGION_DTYPE)
     with open(out, "wb") as f:
         f.write(format_regions(ids, regs, fnames, write_all, gff))
-    return summary_of(regs, np.concatenate(starts))
+    line = summary_of(regs, np.concatenate(starts))
+    if want_orfs:
+        orfs = np.concatenate(oparts) if oparts else np.zeros(0, dtype=hotpath.N.ORF_DTYPE)
+        pstart = np.zeros(len(orfs) + 1, dtype=np.int64)
+        if lens:
+            np.cumsum(np.concatenate(lens), out=pstart[1:])
+        if orfs_out is not None:
+            with open(orfs_out, "wb") as f:
+                f.write(format_orfs(ids, regs, orfs, fnames, write_all))
+        if faa_out is not None:
+            with open(faa_out, "wb") as f:
+                f.write(format_faa(ids, regs, orfs, pstart, np.concatenate(residues) if residues else np.zeros(0, np.uint8),
+                                   fnames, write_all))
+        line += orf_summary(orfs)
+    return line
 
 
 def main(argv=None) -> int:
@@ -120,10 +218,14 @@ def main(argv=None) -> int:
     ap.add_argument("--min-len", type=int, default=0, help="... and at least this many nucleotides long (default 0)")
     ap.add_argument("--all", action="store_true", help="write every region, not only the kept ones")
     ap.add_argument("--gff", action="store_true", help="write GFF3 instead of TSV")
+    ap.add_argument("--orfs", metavar="ORFS.tsv", help="also write the open reading frame around every written region")
+    ap.add_argument("--faa", metavar="PROTEINS.faa", help="also write the translated proteins (FASTA, for annotate -p / make_signatures -p)")
+    ap.add_argument("--start-codons", default="ATG,GTG,TTG", help="start codons of the ORF extension (default ATG,GTG,TTG; none: no start search)")
     a = ap.parse_args(argv)
     from . import _native as N
     try:
-        line = call_regions(a.D, a.q, a.o, a.m, a.M, a.g, a.O, a.merge_gap, a.min_score, a.min_len, a.all, a.gff)
+        line = call_regions(a.D, a.q, a.o, a.m, a.M, a.g, a.O, a.merge_gap, a.min_score, a.min_len, a.all, a.gff,
+                            orfs_out=a.orfs, faa_out=a.faa, start_codons=parse_start_codons(a.start_codons))
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1

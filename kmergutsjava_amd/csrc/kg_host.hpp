@@ -7,6 +7,7 @@
 #include "kg_build.hpp"
 #include "kg_assign.hpp"
 #include "kg_regions.hpp"
+#include "kg_orfs.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -195,7 +196,7 @@ enum : int {
 };
 static_assert(kPevChunk + 2 * kMaxChunks <= kPevFork && kPevVerified + kMaxChunks <= kPevBase && kPevBase + kMaxChunks <= kPevOrdered &&
               kPevOrdered + kMaxOrderStreams <= kPevCount, "event slots overlap");
-// kg_table::ev, the timing events of a scan (outside a scan they are free: kg_result_copy_hits, assign_impl, regions_impl)
+// kg_table::ev, the timing events of a scan (outside a scan they are free: kg_result_copy_hits, assign_impl, regions_impl, orfs_impl)
 enum : int { kEvBegin = 0, kEvScanBegin = 1, kEvScanEnd = 2, kEvOrderEnd = 3, kEvAggEnd = 4, kEvScattered = 5 /* all chunks */, kEvSpare = 6,
              kEvJoined = 7 /* stream2 and stream3 joined */, kEvCount = 8, kEvStageBegin = kEvBegin, kEvStageEnd = kEvScanBegin };
 // d_totals, the counter words of a scan
@@ -214,12 +215,14 @@ enum : int { kOvfGroups = 0 /* overflow groups */, kOvfLowc = 1 /* low-complexit
 // host per copy; to pinned memory it does not)
 enum : int { kPinPc = 0 /* d_pc */, kPinOvf = 48 /* d_ovfc */, kPinTotals = 80 /* d_totals[0 .. kTotSent) */, kPinCalls = 88 /* CALL total */,
              kPinPieces = 89, kPinWords = 96,
-             // the stage area (assign_impl, regions_impl) lies over the scan's totals: such a call holds the table, no scan is in flight
+             // the stage area (assign_impl, regions_impl, orfs_impl) lies over the scan's totals: such a call holds the table, no scan is in flight
              kPinRegions = 80 /* two totals, then the error and counter words */,
-             kPinAssign = 90 /* long proteins, their CALLs, then the error words */ };
+             kPinAssign = 90 /* long proteins, their CALLs, then the error words */,
+             kPinOrfs = 80 /* the error and counter words, then the residue total */ };
 static_assert(kPinPc + kPcWords <= kPinOvf && kOvfWords * kMaxChunks * 4 <= (kPinTotals - kPinOvf) * 8 && kPinTotals + kTotSent <= kPinCalls,
               "counters must fit their pinned words");
-static_assert(kPinRegions + kg::kRegionErrWords + 2 <= kPinAssign && kPinAssign + 2 + 3 <= kPinWords, "stage words must fit their pinned words");
+static_assert(kPinRegions + kg::kRegionErrWords + 2 <= kPinAssign && kPinAssign + 2 + 3 <= kPinWords &&
+              kPinOrfs + kg::kOrfErrWords + kg::kOrfCntWords + 1 <= kPinWords, "stage words must fit their pinned words");
 
 struct kg_table {
     int device = 0;
@@ -502,7 +505,7 @@ int upload_pinned(kg_table *t, const uint8_t *src, size_t bytes, uint8_t *d_dst)
         worker();
         for (auto &th : pool) th.join();
     }
-    return ok.load() ? KG_OK : fail(KG_ERR_DEVICE, "uploading the signatures failed (pinned staging or host-to-device copy)");
+    return ok.load() ? KG_OK : fail(KG_ERR_DEVICE, "uploading to the device failed (pinned staging or host-to-device copy)");
 }
 
 // (key, value) pairs and their stable sort.  Side `cur` of the two buffer pairs holds the pairs; the other side is allocated by

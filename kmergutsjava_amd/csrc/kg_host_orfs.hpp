@@ -1,0 +1,264 @@
+// kg_host_orfs.hpp -- kg_regionset_orfs / kg_orfs_regions: function regions -> open reading frames and their proteins
+// (kernels: kg_orfs.hpp).
+// Part of kmerguts_hip.hip's translation unit: included at its end, behind kg_host_regions.hpp (it reads kg_regionset).
+#pragma once
+
+struct kg_orfset {
+    kg_table *tab = nullptr;            // the context whose block cache the three arrays came from
+    bool own_tab = false;               // kg_orfs_regions: the set owns a table-less context
+    kg_orf *d_orfs = nullptr;           // count records, index-aligned with the regions
+    int64_t *d_prot_start = nullptr;    // count + 1
+    uint8_t *d_res = nullptr;           // residues bytes
+    int64_t count = 0, residues = 0;
+    kg_orf_stats st = {};
+};
+
+namespace {
+
+int check_orf_params(const kg_orf_params *p)
+{
+    if (!p) return fail(KG_ERR_ARG, "null kg_orf_params");
+    if (p->start_codons < 0 || p->start_codons > 7) return fail(KG_ERR_ARG, "start_codons must be a mask of 1 (ATG), 2 (GTG), 4 (TTG)");
+    if (p->only_kept < 0 || p->only_kept > 1) return fail(KG_ERR_ARG, "only_kept must be 0 or 1");
+    return KG_OK;
+}
+
+// d_regions[n]: device array complete on t->stream; d_seq: the batch's bytes on the device (null when there are none);
+// offsets: host, checked.  Fills set (its arrays come out of the cache with the call's scratch and are kept only on success).
+int orfs_impl(kg_table *t, const kg_orf_params *prm, const kg_region *d_regions, uint64_t n, const uint8_t *d_seq,
+              const int64_t *offsets, uint64_t n_seqs, kg_orfset *set)
+{
+    // the tile rows in front of every contig: a row is kOrfTile codons of each of its three phases (declared in front of the
+    // scratch, whose destructor waits for the stream that copies it)
+    std::vector<int64_t> tile_base(n_seqs + 1, 0);
+    Scratch sc(t);
+    hipStream_t s = t->stream;
+    int rc;
+    for (uint64_t k = 0; k < n_seqs; k++)
+        tile_base[k + 1] = tile_base[k] + ((offsets[k + 1] - offsets[k]) / 3 + kg::kOrfTile - 1) / kg::kOrfTile;
+    const uint64_t n_rows = (uint64_t)tile_base[n_seqs], n_tiles = 3 * n_rows;
+    const uint64_t total = n_seqs ? (uint64_t)offsets[n_seqs] : 0;
+    if (n_rows >= (1ull << 31)) return fail(KG_ERR_LIMIT, "2^31 or more tile rows in one call");
+    const uint32_t n_scan = (uint32_t)((n_tiles + kg::kBuildTile - 1) / kg::kBuildTile);
+    int64_t *d_off = nullptr, *d_tb = nullptr, *keys = nullptr, *tile_max = nullptr, *tile_pre = nullptr, *d_start = nullptr;
+    unsigned long long *words = nullptr;           // error words, counter words, then the residue total
+    kg_orf *d_out = nullptr;
+    uint32_t *lens = nullptr, *excl = nullptr;
+    uint64_t *partial = nullptr;
+    if ((rc = sc.get(&d_off, n_seqs + 1)) || (rc = sc.get(&d_tb, n_seqs + 1)) || (rc = sc.get(&words, 16)) ||
+        (rc = sc.get(&keys, std::max<uint64_t>(kg::kOrfPlanes * n_tiles, 1))) ||
+        (rc = sc.get(&tile_max, std::max<uint64_t>((uint64_t)kg::kOrfPlanes * n_scan, 1))) ||
+        (rc = sc.get(&tile_pre, std::max<uint64_t>((uint64_t)kg::kOrfPlanes * n_scan, 1))) ||
+        (rc = sc.get(&d_out, std::max<uint64_t>(n, 1))) || (rc = sc.get(&d_start, n + 1)) || (rc = sc.get(&lens, std::max<uint64_t>(n, 1))) ||
+        (rc = sc.get(&excl, std::max<uint64_t>(n, 1))) || (rc = sc.get(&partial, n / kg::kScanChunk + 2)))
+        return rc;
+    unsigned long long *err = words, *cnt = words + kg::kOrfErrWords;
+    uint64_t *d_total = (uint64_t *)(words + kg::kOrfErrWords + kg::kOrfCntWords);
+    HIP_TRY(hipMemcpyAsync(d_off, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_tb, tile_base.data(), (n_seqs + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(err, 0x7F, kg::kOrfErrWords * 8, s));
+    HIP_TRY(hipMemsetAsync(cnt, 0, (kg::kOrfCntWords + 1) * 8, s));
+    HIP_TRY(hipEventRecord(t->ev[kEvStageBegin], s));
+    const kg::OrfGeometry geo{d_off, d_tb, n_seqs, n_tiles};
+    const uint32_t sc_mask = (uint32_t)prm->start_codons;
+    if (n_rows > 0) {
+        hipLaunchKernelGGL(kg::orf_summary_kernel, dim3((uint32_t)((n_rows + 3) / 4)), dim3(256), 0, s, d_seq, total, geo, n_rows, sc_mask, keys);
+        hipLaunchKernelGGL(kg::orf_tile_max_kernel, dim3(n_scan, kg::kOrfPlanes), dim3(kg::kBuildThreads), 0, s, keys, n_tiles, tile_max);
+        for (int a = 0; a < kg::kOrfPlanes; a++)
+            hipLaunchKernelGGL(kg::build_tile_scan_kernel, dim3(1), dim3(kg::kBuildThreads), 0, s, tile_max + (uint64_t)a * n_scan, n_scan,
+                               tile_pre + (uint64_t)a * n_scan);
+        hipLaunchKernelGGL(kg::orf_scan_apply_kernel, dim3(n_scan, kg::kOrfPlanes), dim3(kg::kBuildThreads), 0, s, keys, n_tiles, tile_pre);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n > 0) {
+        hipLaunchKernelGGL(kg::orf_region_kernel, dim3(grid_of(n)), dim3(256), 0, s, d_regions, n, d_seq, geo, keys, sc_mask,
+                           (int)prm->only_kept, d_out, lens, err, cnt);
+        HIP_TRY(hipGetLastError());
+        if ((rc = prefix_sum(t, lens, n, excl, partial, d_total))) return rc;
+    }
+    hipLaunchKernelGGL(kg::orf_prot_start_kernel, dim3(grid_of(n + 1)), dim3(256), 0, s, excl, d_total, n, d_start);
+    HIP_TRY(hipGetLastError());
+    // the one wait of the call: the residue total (and, with it, the error and counter words)
+    constexpr int kWords = kg::kOrfErrWords + kg::kOrfCntWords + 1;
+    if ((rc = read_error_words(t, words, kWords, kPinOrfs,                          // (in the order they are reported)
+                               {{kg::kOrfErrSeq, KG_ERR_ARG, "region ", ": seq outside [0, n_seqs)"},
+                                {kg::kOrfErrStrand, KG_ERR_ARG, "region ", ": strand is neither 0 nor 1"},
+                                {kg::kOrfErrFrame, KG_ERR_ARG, "region ", ": best_frame outside 0..2"},
+                                {kg::kOrfErrRange, KG_ERR_ARG, "region ", ": outside its contig (0 <= left <= right <= L - 1 does not hold)"},
+                                {kg::kOrfErrAnchor, KG_ERR_ARG, "region ", ": holds no whole codon of its best_frame"}})))
+        return rc;
+    const uint64_t *h = t->h_pin + kPinOrfs;
+    const uint64_t n_res = h[kg::kOrfErrWords + kg::kOrfCntWords];
+    if (n_res >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more residues in one call");
+    uint8_t *d_res = nullptr;
+    if ((rc = sc.get(&d_res, std::max<uint64_t>(n_res, 1)))) return rc;
+    if (n_res > 0) {
+        hipLaunchKernelGGL(kg::orf_residues_kernel, dim3(grid_of((n_res + kg::kOrfResPerLane - 1) / kg::kOrfResPerLane)), dim3(256), 0, s,
+                           d_out, n, d_start, n_res, d_seq, d_off, d_res);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(t->ev[kEvStageEnd], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    set->st.orfs = (int64_t)n;
+    set->st.complete = (int64_t)h[kg::kOrfErrWords + kg::kOrfCntComplete];
+    set->st.interrupted = (int64_t)h[kg::kOrfErrWords + kg::kOrfCntInterrupted];
+    set->st.partial5 = (int64_t)h[kg::kOrfErrWords + kg::kOrfCntPartial5];
+    set->st.residues = (int64_t)n_res;
+    set->st.tiles = (int64_t)n_tiles;
+    HIP_TRY(hipEventElapsedTime(&set->st.ms, t->ev[kEvStageBegin], t->ev[kEvStageEnd]));
+    // the three arrays of the set leave the scratch: everything else goes back to the cache
+    sc.release(d_out); sc.release(d_start); sc.release(d_res);
+    set->d_orfs = d_out;
+    set->d_prot_start = d_start;
+    set->d_res = d_res;
+    set->count = (int64_t)n;
+    set->residues = (int64_t)n_res;
+    return KG_OK;
+}
+
+// the batch's bytes from (possibly pageable) host memory: large ones through pinned pieces on several threads, as a table's
+// signatures go up (complete on return); small ones as one copy on the call's stream
+int upload_batch(kg_table *t, const uint8_t *src, uint64_t bytes, uint8_t *d_dst)
+{
+    if (bytes >= (64ull << 20)) return upload_pinned(t, src, (size_t)bytes, d_dst);
+    HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, t->stream));
+    return KG_OK;
+}
+
+// the host checks both entry points share; *total = the batch's bytes
+int check_orf_batch(const uint8_t *seq, const int64_t *offsets, int64_t n_seqs, uint64_t *total)
+{
+    int64_t l_max = 0;
+    int rc = check_region_offsets(offsets, n_seqs, &l_max);
+    if (rc) return rc;
+    if (n_seqs && offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
+    *total = n_seqs ? (uint64_t)offsets[n_seqs] : 0;
+    if (*total && !seq) return fail(KG_ERR_ARG, "null sequence bytes");
+    return KG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kg_regionset_orfs(kg_regionset *rs, const kg_orf_params *p, const uint8_t *seq, int seq_on_device, const int64_t *offsets,
+                      int64_t n_seqs, kg_orfset **out)
+{
+    if (!out) return fail(KG_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!rs) return fail(KG_ERR_ARG, "null kg_regionset");
+    int rc = check_orf_params(p);
+    if (rc) return rc;
+    uint64_t total = 0;
+    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total))) return rc;
+    if (n_seqs != rs->n_seqs) return fail(KG_ERR_ARG, "n_seqs is not the region set's");
+    if (rs->count >= (1ll << 31)) return fail(KG_ERR_LIMIT, "2^31 or more regions in one call");
+    CallScope cs(rs->tab, "a kg_scan* is in flight on this region set's kg_table");
+    if (cs.rc) return cs.rc;
+    kg_table *t = cs.t;
+    std::unique_ptr<kg_orfset> set(new (std::nothrow) kg_orfset());
+    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
+    set->tab = t;
+    Scratch sc(t);
+    const uint8_t *d_seq = seq;
+    if (!seq_on_device && total) {
+        uint8_t *up = nullptr;
+        if ((rc = sc.get(&up, total))) return rc;
+        if ((rc = upload_batch(t, seq, total, up))) return rc;
+        d_seq = up;
+    } else if (seq_on_device) {
+        HIP_TRY(hipDeviceSynchronize());            // the bytes may have been produced on another stream
+    }
+    if ((rc = orfs_impl(t, p, rs->d_regions, (uint64_t)rs->count, d_seq, offsets, (uint64_t)n_seqs, set.get()))) return rc;
+    *out = set.release();
+    return KG_OK;
+}
+
+int kg_orfs_regions(int device, const kg_orf_params *p, const kg_region *regions, int64_t n_regions, const uint8_t *seq,
+                    const int64_t *offsets, int64_t n_seqs, kg_orfset **out)
+{
+    if (!out) return fail(KG_ERR_ARG, "null argument");
+    *out = nullptr;
+    int rc = check_orf_params(p);
+    if (rc) return rc;
+    if (n_regions < 0) return fail(KG_ERR_ARG, "n_regions < 0");
+    if (n_regions >= (1ll << 31)) return fail(KG_ERR_LIMIT, "2^31 or more regions in one call");
+    if (n_regions && !regions) return fail(KG_ERR_ARG, "null region records");
+    uint64_t total = 0;
+    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total))) return rc;
+    if (n_regions && n_seqs == 0) return fail(KG_ERR_ARG, "region 0: seq outside [0, n_seqs)");
+    CallScope cs(device);               // the call's context: closed on every failure below, kept by the set on success
+    if (cs.rc) return cs.rc;
+    kg_table *t = cs.t;
+    std::unique_ptr<kg_orfset> set(new (std::nothrow) kg_orfset());
+    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
+    set->tab = t;
+    {
+        Scratch sc(t);
+        kg_region *d_regions = nullptr;
+        uint8_t *d_seq = nullptr;
+        if ((rc = sc.get(&d_regions, n_regions ? (size_t)n_regions : 1)) || (rc = sc.get(&d_seq, total ? total : 1))) return rc;
+        if (n_regions) HIP_TRY(hipMemcpyAsync(d_regions, regions, (size_t)n_regions * sizeof(kg_region), hipMemcpyHostToDevice, t->stream));
+        if (total && (rc = upload_batch(t, seq, total, d_seq))) return rc;
+        if ((rc = orfs_impl(t, p, d_regions, (uint64_t)n_regions, d_seq, offsets, (uint64_t)n_seqs, set.get()))) return rc;
+    }
+    t->cache.release_free();            // (the scratch is back in the cache: it goes to the driver, the set's three arrays stay)
+    set->own_tab = true;
+    cs.disown();
+    *out = set.release();
+    return KG_OK;
+}
+
+int64_t kg_orfset_count(const kg_orfset *s) { return s ? s->count : 0; }
+
+const kg_orf *kg_orfset_device(const kg_orfset *s) { return s ? s->d_orfs : nullptr; }
+
+int kg_orfset_copy(const kg_orfset *s, int64_t first, int64_t count, kg_orf *dst)
+{
+    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
+    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_orfset_copy: range outside the set");
+    if (count == 0) return KG_OK;
+    HIP_TRY(hipSetDevice(s->tab->device));
+    HIP_TRY(hipMemcpy(dst, s->d_orfs + first, (size_t)count * sizeof(kg_orf), hipMemcpyDefault));
+    return KG_OK;
+}
+
+int kg_orfset_prot_start(const kg_orfset *s, int64_t *dst)
+{
+    if (!s || !dst) return fail(KG_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(s->tab->device));
+    HIP_TRY(hipMemcpy(dst, s->d_prot_start, ((size_t)s->count + 1) * 8, hipMemcpyDefault));
+    return KG_OK;
+}
+
+int kg_orfset_residues(const kg_orfset *s, int64_t first, int64_t count, uint8_t *dst)
+{
+    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
+    if (first < 0 || count < 0 || first + count > s->residues) return fail(KG_ERR_ARG, "kg_orfset_residues: range outside the proteins");
+    if (count == 0) return KG_OK;
+    HIP_TRY(hipSetDevice(s->tab->device));
+    HIP_TRY(hipMemcpy(dst, s->d_res + first, (size_t)count, hipMemcpyDefault));
+    return KG_OK;
+}
+
+int kg_orfset_stats(const kg_orfset *s, kg_orf_stats *out)
+{
+    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
+    *out = s->st;
+    return KG_OK;
+}
+
+void kg_orfset_free(kg_orfset *s)
+{
+    if (!s) return;
+    if (s->tab) {
+        (void)hipSetDevice(s->tab->device);
+        dfree(s->tab, s->d_orfs);
+        dfree(s->tab, s->d_prot_start);
+        dfree(s->tab, s->d_res);
+        if (s->own_tab) kg_table_close(s->tab);
+    }
+    delete s;
+}
+
+}  // extern "C"

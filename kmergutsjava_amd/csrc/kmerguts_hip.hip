@@ -13,6 +13,7 @@
 #include "kg_derive.hpp"
 #include "kg_assign.hpp"
 #include "kg_regions.hpp"
+#include "kg_orfs.hpp"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -1777,3 +1778,4 @@ int kg_table_save(kg_table *t, const char *path)
 #include "kg_host_derive.hpp"
 #include "kg_host_assign.hpp"
 #include "kg_host_regions.hpp"
+#include "kg_host_orfs.hpp"

@@ -220,6 +220,37 @@ class ScanResult:
         out, start, self.region_stats = _take_regionset(h, self.stats["n_seqs"], device_out)
         return out, start
 
+    def orfs(self, seq, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, start_codons: int = 7,
+             only_kept: bool = True, device_ptr: Optional[int] = None):
+        """regions() and then the open reading frame around every region with its translated protein, on the GPU, without a
+        host trip between the two (include/kmerguts_hip.h kg_regionset_orfs states the rule).  seq / offsets: what the scan was
+        given; device_ptr: the address of the bytes in HBM instead of seq.
+        -> (regions, region_start, orfs, prot_start, residues): orfs a numpy array of _native.ORF_DTYPE, index-aligned with
+        regions; the protein of ORF i is residues[prot_start[i] : prot_start[i + 1]] (uint8).  The two calls' counts and device
+        times are left in `region_stats` and `orf_stats`."""
+        lib = self._need()
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+        if off.shape != (self.stats["n_seqs"] + 1,):
+            raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
+        p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
+        h = C.c_void_p()
+        N.check(lib.kg_result_regions(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
+        try:
+            if device_ptr is not None:
+                ptr, on_device, keep = C.c_void_p(device_ptr), 1, None
+            else:
+                keep = _seq_bytes(seq, off)
+                ptr, on_device = (keep.ctypes.data if keep.size else None), 0
+            op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
+            oh = C.c_void_p()
+            N.check(lib.kg_regionset_orfs(h, C.byref(op), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(oh)))
+            orfs, prot_start, residues, self.orf_stats = _take_orfset(oh, False)
+        except BaseException:
+            lib.kg_regionset_free(h)
+            raise
+        regs, start, self.region_stats = _take_regionset(h, self.stats["n_seqs"], False)
+        return regs, start, orfs, prot_start, residues
+
     def close(self) -> None:
         if self._h:
             N.load().kg_result_free(self._h)
@@ -534,3 +565,60 @@ def region_calls(calls, offsets, merge_gap: int = 600, min_score: int = 0, min_l
     if stats is not None:
         stats.update(st)
     return out, start
+
+
+def _seq_bytes(seq, off) -> np.ndarray:
+    arr = np.frombuffer(seq, dtype=np.uint8) if not isinstance(seq, np.ndarray) else seq
+    arr = np.ascontiguousarray(arr.view(np.uint8).reshape(-1))
+    if off.size > 1 and arr.size < int(off[-1]):
+        raise ValueError("sequence buffer shorter than offsets[-1]")
+    return arr
+
+
+def _take_orfset(h, device_out: bool):
+    """Copy a kg_orfset out (to the host, or into CUDA tensors) and free it.  -> (records, prot_start, residues, statistics)."""
+    lib = N.load()
+    try:
+        st = N.KgOrfStats()
+        N.check(lib.kg_orfset_stats(h, C.byref(st)))
+        n, n_res = int(lib.kg_orfset_count(h)), int(st.residues)
+        if device_out:
+            import torch
+            out = torch.empty(n * N.ORF_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+            start = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+            res = torch.empty(n_res, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            N.check(lib.kg_orfset_copy(h, 0, n, C.c_void_p(out.data_ptr() if n else None)))
+            N.check(lib.kg_orfset_prot_start(h, C.c_void_p(start.data_ptr())))
+            N.check(lib.kg_orfset_residues(h, 0, n_res, C.c_void_p(res.data_ptr() if n_res else None)))
+        else:
+            out = np.zeros(n, dtype=N.ORF_DTYPE)
+            start = np.zeros(n + 1, dtype=np.int64)
+            res = np.zeros(n_res, dtype=np.uint8)
+            N.check(lib.kg_orfset_copy(h, 0, n, out.ctypes.data if n else None))
+            N.check(lib.kg_orfset_prot_start(h, start.ctypes.data))
+            N.check(lib.kg_orfset_residues(h, 0, n_res, res.ctypes.data if n_res else None))
+        return out, start, res, st.as_dict()
+    finally:
+        lib.kg_orfset_free(h)
+
+
+def orf_regions(regs, seq, offsets, start_codons: int = 7, only_kept: bool = True, device: int = 0, device_out: bool = False,
+                stats: Optional[dict] = None):
+    """The open reading frame around every caller-held region and its translated protein, on the GPU (kg_orfs_regions): regs
+    REGION_DTYPE, seq the batch's bytes, offsets int64[n_seqs + 1].  -> (orfs, prot_start, residues): numpy arrays of
+    _native.ORF_DTYPE, int64[n + 1] and uint8, or with device_out=True CUDA tensors (uint8 of 48 bytes per ORF, int64, uint8);
+    `stats`, when given, receives the call's counts and device time."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_seqs + 1]")
+    r = np.ascontiguousarray(regs, dtype=N.REGION_DTYPE)
+    arr = _seq_bytes(seq, off)
+    p = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
+    h = C.c_void_p()
+    N.check(N.load().kg_orfs_regions(device, C.byref(p), r.ctypes.data if r.size else None, r.size,
+                                     arr.ctypes.data if arr.size else None, off.ctypes.data, off.size - 1, C.byref(h)))
+    out, start, res, st = _take_orfset(h, device_out)
+    if stats is not None:
+        stats.update(st)
+    return out, start, res
