@@ -28,7 +28,7 @@
  *   KG_PROBE_GRID, KG_INDEX_GRID, KG_INDEX_R, KG_PROBE_GRAB, KG_VERIFY_GRID, KG_LOWC_GRID, KG_OVF_GRID,
  *   KG_ORDER_GRID, KG_ORDER_STREAMS, KG_EARLY_TOTALS, KG_PLACE_STAGED, KG_SCAN_GRID, KG_SCAN_RPG, KG_DIRECT_FILTER, KG_SCATTER_PRIO, KG_INDEX_PRIO, KG_VERIFY_PRIO, KG_STAGE_CHUNK, KG_AGG_PIECES, KG_AGG_PAIRS, KG_AGG_BLOCK_SHIFT:
  *   geometry of the
- *   scan strategies (kmerguts_hip.hip: plan_partition, plan_direct, aggregate_stage); results never depend on them.  KG_DEBUG: one stderr line per attempt.
+ *   scan strategies (kg_host_plan.hpp: plan_partition, plan_direct, plan_aggregate); results never depend on them.  KG_DEBUG: one stderr line per attempt.
  *   TEST HOOKS (used by tests/ only; inert unless the process set KG_ENABLE_TEST_HOOKS=1 before its FIRST kg_scan* -- that
  *   one is read once, so a stray KG_TEST_* variable in a server's environment does nothing): KG_TEST_TINY_LISTS=1 starts the hit / candidate lists at one chunk, so that the
  *   resize-and-rerun path runs; KG_TEST_FAIL_ALLOC=n makes the n-th device allocation of the call fail with

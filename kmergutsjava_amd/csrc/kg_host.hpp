@@ -1,13 +1,9 @@
 // kg_host.hpp -- what the host side of every stage needs: the error text, the device and pinned block caches, kg_table and
-// kg_result with the names of their numbered slots, the per-call scratch, and the helpers the batch stages share (prefix sum,
-// radix sort of pairs, pinned upload).  Included by kmerguts_hip.hip, which includes the stages' hosts (kg_host_*.hpp) at its end.
+// kg_result with the names of their numbered slots, the environment readers, the per-call scope and scratch, and the helpers the
+// stages share (prefix sum, one launch for several clears, radix sort of pairs, pinned upload).
+// Part of kmerguts_hip.hip's translation unit: the first host file, behind the kernel headers; the hosts of the table, the
+// result, the scan and the batch stages (kg_host_*.hpp) follow it.
 #pragma once
-
-#include "kg_device.hpp"
-#include "kg_build.hpp"
-#include "kg_assign.hpp"
-#include "kg_regions.hpp"
-#include "kg_orfs.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -335,7 +331,7 @@ int dalloc_detached(kg_table *t, uint8_t **p, size_t bytes)
     return rc;
 }
 
-int table_new(int device, kg_table **out);       // kmerguts_hip.hip, beside kg_table_close
+int table_new(int device, kg_table **out);       // kg_host_table.hpp, beside kg_table_close
 
 // One C ABI call at work on a table, constructed after the argument checks; `rc` says whether the call may go on.  Either it
 // borrows an open table (takes the busy flag, or reports KG_ERR_BUSY with the caller's words) or it owns a fresh table-less
@@ -383,6 +379,25 @@ int prefix_sum(kg_table *t, const uint32_t *d_in, uint64_t n, uint32_t *d_out, u
     hipLaunchKernelGGL(kg::scan_top_kernel, dim3(1), dim3(kg::kScanThreads), 0, stream, d_partial, nb, d_total);
     hipLaunchKernelGGL(kg::scan_final_kernel, dim3(nb), dim3(kg::kScanThreads), 0, stream, d_in, n, d_partial, d_out);
     HIP_TRY(hipGetLastError());
+    return KG_OK;
+}
+
+// Several arrays of 32-bit words zeroed by one launch (kg_device.hpp, clear_many_kernel: eight slots).  Entries of no words are
+// left out, and nothing is launched when none is left.  grid(most): the workgroups for `most` words, the largest entry.
+struct ClearItem { void *p; uint64_t words; };
+
+template <typename G>
+int clear_words(hipStream_t stream, G grid, std::initializer_list<ClearItem> items)
+{
+    kg::ClearList cl = {};              // (unused slots: null, no words)
+    uint64_t most = 0;
+    for (const ClearItem &it : items) {
+        if (!it.words) continue;
+        if (cl.n == (int)std::size(cl.p)) return fail(KG_ERR_DEVICE, "more than eight arrays in one clear (internal error)");
+        cl.p[cl.n] = (uint32_t *)it.p; cl.words[cl.n++] = it.words;
+        most = std::max(most, it.words);
+    }
+    if (cl.n) hipLaunchKernelGGL(kg::clear_many_kernel, dim3(grid(most)), dim3(256), 0, stream, cl);
     return KG_OK;
 }
 

@@ -1,6 +1,7 @@
 // kg_host_assign.hpp -- kg_result_assign / kg_assign_calls: the CALL records of an -a scan -> one kg_assignment per protein
 // (kernels: kg_assign.hpp).
-// Part of kmerguts_hip.hip's translation unit: included at its end, behind kg_host.hpp and the kernel headers.
+// Part of kmerguts_hip.hip's translation unit: one of the batch stages, included behind the kernel headers, kg_host.hpp and the
+// hosts of the table, the result and the scan.
 #pragma once
 
 namespace {

@@ -1,5 +1,6 @@
 // kg_host_build.hpp -- kg_table_build / kg_table_build_device: a signature list -> a resident table (kernels: kg_build.hpp).
-// Part of kmerguts_hip.hip's translation unit: included at its end, behind kg_host.hpp and the kernel headers.
+// Part of kmerguts_hip.hip's translation unit: one of the batch stages, included behind the kernel headers, kg_host.hpp and the
+// hosts of the table, the result and the scan.
 #pragma once
 
 namespace {

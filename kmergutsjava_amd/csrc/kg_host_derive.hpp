@@ -1,6 +1,7 @@
 // kg_host_derive.hpp -- kg_signatures_derive / kg_signatures_derive_device: annotated proteins -> a signature set (kernels:
 // kg_derive.hpp).
-// Part of kmerguts_hip.hip's translation unit: included at its end, behind kg_host.hpp and the kernel headers.
+// Part of kmerguts_hip.hip's translation unit: one of the batch stages, included behind the kernel headers, kg_host.hpp and the
+// hosts of the table, the result and the scan.
 #pragma once
 
 struct kg_sigset {

@@ -1,6 +1,6 @@
 // kg_host_orfs.hpp -- kg_regionset_orfs / kg_orfs_regions: function regions -> open reading frames and their proteins
 // (kernels: kg_orfs.hpp).
-// Part of kmerguts_hip.hip's translation unit: included at its end, behind kg_host_regions.hpp (it reads kg_regionset).
+// Part of kmerguts_hip.hip's translation unit: the last of the batch stages, behind kg_host_regions.hpp (it reads kg_regionset).
 #pragma once
 
 struct kg_orfset {

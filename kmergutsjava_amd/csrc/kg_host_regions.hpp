@@ -1,6 +1,7 @@
 // kg_host_regions.hpp -- kg_result_regions / kg_regions_calls: the CALL records of a DNA scan -> function regions on the contigs
 // (kernels: kg_regions.hpp).
-// Part of kmerguts_hip.hip's translation unit: included at its end, behind kg_host.hpp and the kernel headers.
+// Part of kmerguts_hip.hip's translation unit: one of the batch stages, included behind the kernel headers, kg_host.hpp and the
+// hosts of the table, the result and the scan.
 #pragma once
 
 struct kg_regionset {

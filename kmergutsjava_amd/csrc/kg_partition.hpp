@@ -25,7 +25,7 @@
 //   kg_order.hpp         : unordered list -> hits[] in (container, from0InProt) order: two partition passes by key range
 //                          and an in-LDS ranking per group of rows, all streaming
 // The batch is processed in chunks of whole sequences; scatter, tag pass and verification + placement of successive
-// chunks run on three streams (kmerguts_hip.hip, scan_impl).
+// chunks run on three streams (kg_host_scan.hpp, scan_partitioned).
 //
 // Entry (64 bit): low word = quotient << shift | slot_low, high word = id = the window's key (window_key: its rank in the
 // final order of the hit records);

@@ -38,7 +38,7 @@ def assert_same_records(gpu, ora, what=""):
 
 
 def _partition_fits(stats) -> bool:
-    """The library's own eligibility rule for the partitioned strategy (kmerguts_hip.hip, plan_partition)."""
+    """The library's own eligibility rule for the partitioned strategy (kg_host_plan.hpp, plan_partition)."""
     num_sigs = stats["table_bytes"] // 24
     qmax = 20 ** 8 // num_sigs + 1
     shift = 21
@@ -79,7 +79,7 @@ def plant(seq_bytes: bytes, off, keys, every=40, dna=True, start=10):
 
 
 def chunk_seq_ranges(off, want=4, dna=True, min_chunk_blocks=None):
-    """The sequence ranges [a, b) of the chunks the partitioned scan cuts a batch into (kmerguts_hip.hip, plan_partition:
+    """The sequence ranges [a, b) of the chunks the partitioned scan cuts a batch into (kg_host_plan.hpp, plan_partition:
     chunk c starts at the first sequence whose first window block is >= nblocks * c / want; the number of chunks by
     the batch's size -- round(sqrt(blocks / 325 000)), at least two, one below 450 000 blocks -- or, with
     KG_PART_MIN_CHUNK_BLOCKS = min_chunk_blocks, fewer chunks while a chunk would hold fewer blocks than that).

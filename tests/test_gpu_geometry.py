@@ -69,7 +69,7 @@ def _clamp(v, lo, hi, mult=1):
 
 
 def _expected_shift(start, num_sigs, limit, aa):
-    """the partitioned scan's bucket shift (kmerguts_hip.hip, plan_partition) from KG_PART_SHIFT = start"""
+    """the partitioned scan's bucket shift (kg_host_plan.hpp, plan_partition) from KG_PART_SHIFT = start"""
     shift = _clamp(start, 4, 31)
     qmax = MAX_ENCODED // num_sigs + 1
     while shift > 4 and qmax >= (1 << (32 - shift)):
