@@ -493,6 +493,74 @@ int kg_orfset_residues(const kg_orfset *s, int64_t first, int64_t count, uint8_t
 int kg_orfset_stats(const kg_orfset *s, kg_orf_stats *out);
 void kg_orfset_free(kg_orfset *s);
 
+/* ---- a gene set: the non-overlapping selection among regions or ORFs (kernels: kg_select.hpp) ----
+ *
+ * The reference stops at the CALL lines; this rule is the project's own.
+ * Input: n candidates, index-aligned with a region set or an ORF set.  Each candidate has seq, left <= right (0-based,
+ * inclusive, on the contig as given), score, and eligible.  eligible is the record's kept.
+ *   1. Length and overlap.  len = right - left + 1.  Two candidates of the same seq overlap by
+ *      ov = min(right_i, right_j) - max(left_i, left_j) + 1, when that is positive.
+ *   2. Conflict.  Two eligible candidates conflict iff ov > max_overlap or 100 * ov > max_overlap_pct * min(len_i, len_j).
+ *      The arithmetic is int64.  Strand and function play no part: two functions on one ORF conflict, and so do genes on
+ *      opposite strands.  Candidates of different contigs never conflict.  A non-eligible candidate conflicts with nothing.
+ *   3. Strength.  This is a total order: larger score first, then larger len, then smaller index in the set.
+ *   4. Selection.  Going through the eligible candidates from strongest to weakest, a candidate is selected iff it conflicts
+ *      with no stronger selected candidate.  This is the greedy fixed point.  It is unique and it is what the model computes
+ *      with a plain loop.  It is not one-shot dominance: a candidate that conflicts only with a stronger candidate that itself
+ *      lost is selected.
+ *   5. Record.  kg_selection is 8 bytes: { int32 state; int32 by; }.  state is 0 for not eligible, 1 for selected, 2 for
+ *      overlapped.  by is the smallest set index among the selected, stronger candidates the overlapped one conflicts with,
+ *      and -1 otherwise.
+ *   6. Parameters.  kg_select_params { max_overlap, max_overlap_pct, reserved }.  Both values must be at least 0,
+ *      max_overlap_pct must be at most 100, and reserved must be 0.  Anything else is KG_ERR_ARG.  The defaults are 60
+ *      nucleotides and 50 percent.  They are this project's choice.
+ *   7. Independence.  The output depends only on the candidate list and the parameters.  It does not depend on launch
+ *      geometry, on the number of rounds, or on batch neighbours.
+ *   8. Errors.  KG_ERR_ARG for null pointers.  KG_ERR_ARG for a caller-held candidate with seq outside [0, n_seqs), left < 0 or
+ *      right < left: the message names the first such candidate, and the candidate is never used as an index.  KG_ERR_LIMIT
+ *      for 2^31 or more candidates, or 2^31 or more overlapping pairs (pairs of eligible candidates of one contig with ov > 0,
+ *      conflicting or not): this is found from the counts, before the pair list is allocated.  KG_ERR_BUSY while a kg_scan* is
+ *      in flight on the set's table.  KG_ERR_NOMEM.  Zero candidates are valid.
+ * Device allocations come from the block cache of the set's context (a table-less one for kg_select_intervals), so
+ * KG_TEST_FAIL_ALLOC applies; everything but the selection array is back in the cache on every path out.  A select set made
+ * from a region set or an ORF set holds a block of that set's context and must be freed before it. */
+#define KG_SEL_NOT_ELIGIBLE 0
+#define KG_SEL_SELECTED     1
+#define KG_SEL_OVERLAPPED   2
+typedef struct kg_select_params { int32_t max_overlap; int32_t max_overlap_pct; int32_t reserved; } kg_select_params;
+typedef struct kg_interval {     /* 20 B */
+    int32_t  seq;
+    int32_t  left;         /* 0-based, inclusive                                        */
+    int32_t  right;
+    int32_t  score;
+    int32_t  eligible;     /* 0: takes no part                                          */
+} kg_interval;
+typedef struct kg_selection {    /* 8 B */
+    int32_t  state;        /* KG_SEL_*                                                  */
+    int32_t  by;           /* overlapped: the winner's index in the set, else -1        */
+} kg_selection;
+typedef struct kg_select_stats {
+    int64_t candidates, eligible, selected, overlapped;
+    int64_t pairs;         /* overlapping pairs of eligible candidates                  */
+    int64_t conflicts;     /* ... of which conflict (rule 2)                            */
+    int32_t rounds;        /* rounds until no candidate was undecided                   */
+    float   ms;            /* device time of the call's kernels                         */
+} kg_select_stats;
+typedef struct kg_selectset kg_selectset;
+/* interval = the region's left..right, eligible = its kept; selection[i] belongs to region[i] */
+int kg_regionset_select(kg_regionset *set, const kg_select_params *p, kg_selectset **out);
+/* interval = the ORF's left..right, eligible = its kept; selection[i] belongs to orf[i] */
+int kg_orfset_select(kg_orfset *set, const kg_select_params *p, kg_selectset **out);
+/* caller-held host list iv[n] in any order; selection[i] belongs to iv[i] */
+int kg_select_intervals(int device, const kg_select_params *p, const kg_interval *iv, int64_t n, int64_t n_seqs, kg_selectset **out);
+int64_t kg_selectset_count(const kg_selectset *s);
+/* device array of kg_selectset_count(s) kg_selection records, valid until kg_selectset_free */
+const kg_selection *kg_selectset_device(const kg_selectset *s);
+/* records [first, first + count) into dst (host or device memory) */
+int kg_selectset_copy(const kg_selectset *s, int64_t first, int64_t count, kg_selection *dst);
+int kg_selectset_stats(const kg_selectset *s, kg_select_stats *out);
+void kg_selectset_free(kg_selectset *s);
+
 /* the resident 24-byte records, valid until kg_table_close, and how many there are: num_sigs for a built or adopted table, the
  * whole records of the file for an opened one (fewer than num_sigs for a truncated file, more for a longer one) */
 const void *kg_table_device_entries(const kg_table *t);

@@ -161,6 +161,40 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_select_params (kg_regionset_select / kg_orfset_select / kg_select_intervals); this project's defaults: 60, 50 and 0. */
+    class KgSelectParams extends Structure {
+        public int max_overlap, max_overlap_pct, reserved;
+        public KgSelectParams() {
+            setFieldOrder(new String[] {"max_overlap", "max_overlap_pct", "reserved"});
+        }
+    }
+
+    /** struct kg_interval (20 B): one candidate of kg_select_intervals, 0-based inclusive left / right. */
+    class KgInterval extends Structure {
+        public int seq, left, right, score, eligible;
+        public KgInterval() {
+            setFieldOrder(new String[] {"seq", "left", "right", "score", "eligible"});
+        }
+    }
+
+    /** struct kg_selection (8 B): state 0 not eligible, 1 selected, 2 overlapped; by = the winner's index in the set or -1. */
+    class KgSelection extends Structure {
+        public int state, by;
+        public KgSelection() {
+            setFieldOrder(new String[] {"state", "by"});
+        }
+    }
+
+    /** struct kg_select_stats. */
+    class KgSelectStats extends Structure {
+        public long candidates, eligible, selected, overlapped, pairs, conflicts;
+        public int rounds;
+        public float ms;
+        public KgSelectStats() {
+            setFieldOrder(new String[] {"candidates", "eligible", "selected", "overlapped", "pairs", "conflicts", "rounds", "ms"});
+        }
+    }
+
     // replaces readKmerTableHeader + the table stream of lookup (KmerGutsJava.java:924-942, 944-1034)
     int kg_table_open(String path, int device, PointerByReference out);
     int kg_table_from_memory(Pointer image, long nbytes, int device, PointerByReference out);
@@ -235,6 +269,16 @@ public interface KmerGutsHip extends Library {
     int kg_orfset_residues(Pointer set, long first, long count, Pointer dst);
     int kg_orfset_stats(Pointer set, KgOrfStats out);
     void kg_orfset_free(Pointer set);
+    /** the non-overlapping selection among the kept regions / ORFs of a set; free the select set before the set it came from */
+    int kg_regionset_select(Pointer set, KgSelectParams params, PointerByReference out);
+    int kg_orfset_select(Pointer set, KgSelectParams params, PointerByReference out);
+    /** iv: n packed 20-byte kg_interval records (int seq, left, right, score, eligible) in host memory, any order */
+    int kg_select_intervals(int device, KgSelectParams params, Pointer iv, long n, long nSeqs, PointerByReference out);
+    long kg_selectset_count(Pointer set);
+    Pointer kg_selectset_device(Pointer set);                // kg_selection[count] in device memory, index-aligned with the candidates
+    int kg_selectset_copy(Pointer set, long first, long count, Pointer dst);
+    int kg_selectset_stats(Pointer set, KgSelectStats out);
+    void kg_selectset_free(Pointer set);
     void kg_result_free(Pointer result);
     int kg_restore_hits_device(int device, Pointer dSrc, long nHits, Pointer dSeqFirst, long nSeqs, Pointer dDstFirst,
                                Pointer dContainerShift, Pointer dDst, Pointer stream);

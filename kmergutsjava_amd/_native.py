@@ -38,6 +38,8 @@ EXPORTS = (
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
     "kg_orfset_residues", "kg_orfset_stats", "kg_orfset_free",
+    "kg_regionset_select", "kg_orfset_select", "kg_select_intervals", "kg_selectset_count", "kg_selectset_device",
+    "kg_selectset_copy", "kg_selectset_stats", "kg_selectset_free",
     "kg_last_error", "kg_version",
 )
 
@@ -72,6 +74,12 @@ ORF_DTYPE = np.dtype([("seq", "<i4"), ("strand", "<i4"), ("frame", "<i4"), ("lef
 assert ORF_DTYPE.itemsize == 48
 ORF_HAS_STOP, ORF_PARTIAL5, ORF_INTERRUPTED, ORF_MULTI_FRAME = 1, 2, 4, 8
 ORF_TILE_CODONS = 128       # kg_orfs.hpp kOrfTile: the codons of one tile summary (tests aim at its edges)
+# struct kg_interval (kg_select_intervals) and struct kg_selection (kg_*_select): a candidate and what became of it
+INTERVAL_DTYPE = np.dtype([("seq", "<i4"), ("left", "<i4"), ("right", "<i4"), ("score", "<i4"), ("eligible", "<i4")])
+SELECTION_DTYPE = np.dtype([("state", "<i4"), ("by", "<i4")])
+assert INTERVAL_DTYPE.itemsize == 20 and SELECTION_DTYPE.itemsize == 8
+SEL_NOT_ELIGIBLE, SEL_SELECTED, SEL_OVERLAPPED = 0, 1, 2
+SELECT_PAIRS_PER_LANE = 8   # kg_select.hpp kSelectPairsPerLane: the pair slots of one lane (tests aim at its edges)
 assert HIT_DTYPE.itemsize == 24 and CALL_DTYPE.itemsize == 24 and OTU_DTYPE.itemsize == 44
 
 
@@ -152,6 +160,20 @@ class KgOrfStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
+class KgSelectParams(C.Structure):
+    """struct kg_select_params (kg_regionset_select / kg_orfset_select / kg_select_intervals)."""
+    _fields_ = [("max_overlap", C.c_int32), ("max_overlap_pct", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgSelectStats(C.Structure):
+    """struct kg_select_stats."""
+    _fields_ = [("candidates", C.c_int64), ("eligible", C.c_int64), ("selected", C.c_int64), ("overlapped", C.c_int64),
+                ("pairs", C.c_int64), ("conflicts", C.c_int64), ("rounds", C.c_int32), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class KmerGutsNativeError(RuntimeError):
@@ -253,6 +275,17 @@ def load() -> C.CDLL:
     lib.kg_orfset_stats.argtypes = [vp, C.POINTER(KgOrfStats)]
     lib.kg_orfset_free.argtypes = [vp]
     lib.kg_orfset_free.restype = None
+    lib.kg_regionset_select.argtypes = [vp, C.POINTER(KgSelectParams), C.POINTER(vp)]
+    lib.kg_orfset_select.argtypes = [vp, C.POINTER(KgSelectParams), C.POINTER(vp)]
+    lib.kg_select_intervals.argtypes = [C.c_int, C.POINTER(KgSelectParams), vp, C.c_int64, C.c_int64, C.POINTER(vp)]
+    lib.kg_selectset_count.argtypes = [vp]
+    lib.kg_selectset_count.restype = C.c_int64
+    lib.kg_selectset_device.argtypes = [vp]
+    lib.kg_selectset_device.restype = vp
+    lib.kg_selectset_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.kg_selectset_stats.argtypes = [vp, C.POINTER(KgSelectStats)]
+    lib.kg_selectset_free.argtypes = [vp]
+    lib.kg_selectset_free.restype = None
     lib.kg_last_error.restype = C.c_char_p
     lib.kg_version.restype = C.c_char_p
     for name in EXPORTS:

@@ -4,6 +4,7 @@
     python -m kmergutsjava_amd.call_regions -D KmerData -q contigs.fna[.gz] -o regions.tsv [-m 5] [-M 0] [-g 200] [-O]
                                             [--merge-gap 600] [--min-score 0] [--min-len 0] [--all] [--gff]
                                             [--orfs ORFS.tsv] [--faa PROTEINS.faa] [--start-codons ATG,GTG,TTG]
+                                            [--select [--max-overlap 60] [--max-overlap-pct 50]]
 
 The table and function.index[.gz] are loaded the way annotate loads them.  Contigs are read with
 make_signatures.parse_fasta (a duplicate id is an error) and scanned whole, in batches of at most
@@ -23,6 +24,15 @@ with start the start codon or `-`, and flags the words stop, partial5, interrupt
 make_signatures -p read; an ORF with the contig, strand, left and right of an earlier written one is written once, under the
 region with the largest score (ties: the first).  With either flag the summary line gains `, orfs: N, complete: C,
 interrupted: I` (complete: stop, start and not interrupted).
+
+--select makes the output a gene set: among the kept candidates -- the ORFs' extents with --orfs or --faa, else the regions'
+extents -- the non-overlapping selection is taken on the GPU (kg_orfset_select / kg_regionset_select; include/kmerguts_hip.h
+states the rule: two candidates of a contig conflict when they share more than --max-overlap nucleotides or more than
+--max-overlap-pct percent of the shorter one, whatever their strands and functions, and the stronger one -- score, then
+length, then position in the output -- wins).  Only selected candidates are written to the three outputs.  With --all every
+candidate is written, the status is kept, below or overlapped, and the TSV and GFF lines gain one trailing field (GFF: the
+attribute overlapped_by) that names the winner an overlapped candidate lost to as left+1..right+1:strand, or `-`.  The summary
+line gains `, selected: S, overlapped: V`.
 """
 from __future__ import annotations
 
@@ -60,13 +70,37 @@ def _gff_escape(s: bytes) -> bytes:
     return s
 
 
-def format_regions(ids, regs, fnames, write_all: bool = False, gff: bool = False) -> bytes:
-    """Region records (REGION_DTYPE, `seq` indexing ids) as text, in the order given."""
+def select_summary(sel) -> str:
+    """What the summary line gains with --select, from selection records (SELECTION_DTYPE)."""
+    return ", selected: %d, overlapped: %d" % (int((sel["state"] == 1).sum()), int((sel["state"] == 2).sum()))
+
+
+def _written(r, write_all: bool, sel, i: int) -> bool:
+    return bool(write_all or (r["kept"] if sel is None else sel["state"][i] == 1))
+
+
+def _winner(sel, i: int, cands) -> bytes:
+    """`left+1..right+1:strand` of the candidate (a region or ORF record of cands) that candidate i lost to, or `-`."""
+    by = int(sel["by"][i])
+    if by < 0:
+        return b"-"
+    w = cands[by]
+    return b"%d..%d:%s" % (w["left"] + 1, w["right"] + 1, b"-" if w["strand"] else b"+")
+
+
+def format_regions(ids, regs, fnames, write_all: bool = False, gff: bool = False, sel=None, cands=None) -> bytes:
+    """Region records (REGION_DTYPE, `seq` indexing ids) as text, in the order given.  sel: the selection records of --select,
+    index-aligned with regs; cands: the records the selection ran on (the ORFs, default the regions)."""
     lines = [b"##gff-version 3\n"] if gff else []
-    for r in regs:
-        if not (r["kept"] or write_all):
+    cands = regs if cands is None else cands
+    for i, r in enumerate(regs):
+        if not _written(r, write_all, sel, i):
             continue
         status = b"kept" if r["kept"] else b"below"
+        if sel is not None and sel["state"][i] == 2:
+            status = b"overlapped"
+        if sel is not None and write_all:
+            status += (b";overlapped_by=" if gff else b"\t") + _winner(sel, i, cands)
         strand = b"-" if r["strand"] else b"+"
         name, w = _fname(fnames, int(r["fI"])), b"%.9g" % float(r["weighted"])
         cid = ids[int(r["seq"])]
@@ -104,11 +138,11 @@ def orf_summary(orfs) -> str:
     return ", orfs: %d, complete: %d, interrupted: %d" % (len(orfs), int(complete.sum()), int(((fl & 4) != 0).sum()))
 
 
-def format_orfs(ids, regs, orfs, fnames, write_all: bool = False) -> bytes:
+def format_orfs(ids, regs, orfs, fnames, write_all: bool = False, sel=None) -> bytes:
     """ORF records (ORF_DTYPE, index-aligned with regs) as text, one line per written region."""
     lines = []
-    for r, o in zip(regs, orfs):
-        if not (r["kept"] or write_all):
+    for i, (r, o) in enumerate(zip(regs, orfs)):
+        if not _written(r, write_all, sel, i):
             continue
         words = b",".join(w for bit, w in FLAG_WORDS if int(o["flags"]) & bit) or b"-"
         start = START_NAMES[int(o["start_codon"]) - 1] if o["start_codon"] else b"-"
@@ -118,13 +152,13 @@ def format_orfs(ids, regs, orfs, fnames, write_all: bool = False) -> bytes:
     return b"".join(lines)
 
 
-def format_faa(ids, regs, orfs, prot_start, residues, fnames, write_all: bool = False) -> bytes:
+def format_faa(ids, regs, orfs, prot_start, residues, fnames, write_all: bool = False, sel=None) -> bytes:
     """The proteins of the written regions as FASTA: an ORF with the (contig, strand, left, right) of an earlier written one is
     written once, where the first of them stands, under the region with the largest score (ties: the first)."""
     res = np.asarray(residues, dtype=np.uint8).tobytes()
     best, order = {}, []
     for i, (r, o) in enumerate(zip(regs, orfs)):
-        if not (r["kept"] or write_all) or prot_start[i + 1] == prot_start[i]:
+        if not _written(r, write_all, sel, i) or prot_start[i + 1] == prot_start[i]:
             continue
         key = (int(o["seq"]), int(o["strand"]), int(o["left"]), int(o["right"]))
         if key not in best:
@@ -145,7 +179,7 @@ def format_faa(ids, regs, orfs, prot_start, residues, fnames, write_all: bool = 
 def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_weighted_hits: int = 0, max_gap: int = 200,
                  order_constraint: bool = False, merge_gap: int = 600, min_score: int = 0, min_len: int = 0,
                  write_all: bool = False, gff: bool = False, device: int = 0, orfs_out: str = None, faa_out: str = None,
-                 start_codons: int = 7) -> str:
+                 start_codons: int = 7, select: bool = False, max_overlap: int = 60, max_overlap_pct: int = 50) -> str:
     """Write the regions (and, with orfs_out / faa_out, their open reading frames and proteins); returns the summary line."""
     from . import hotpath
     from .kmer_guts_java import KmerGutsJava, _resident_table
@@ -160,8 +194,8 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                             max_gap=max_gap)
     parts, starts = [], [np.zeros(1, dtype=np.int64)]
     want_orfs = orfs_out is not None or faa_out is not None
-    oparts, lens, residues = [], [], []
-    k = 0
+    oparts, lens, residues, sparts = [], [], [], []
+    k = n_before = 0
     while k < len(ids):
         j, size = k, 0
         while j < len(ids) and (j == k or size + len(seqs[j]) <= KmerGutsJava.MAX_BATCH_CHARS):
@@ -171,7 +205,19 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         off[1:] = np.cumsum([len(s) for s in seqs[k:j]])
         batch = b"".join(seqs[k:j])
         with tab.scan(batch, off, params) as r:
-            if want_orfs:
+            if select:
+                got = r.select(off, batch, merge_gap, min_score, min_len, want_orfs, start_codons, not write_all,
+                               max_overlap=max_overlap, max_overlap_pct=max_overlap_pct)
+                regs, start, sel = got[0], got[1], got[-1]
+                sel["by"][sel["by"] >= 0] += n_before       # (selection is per contig: a batch's winners are its own records)
+                sparts.append(sel)
+                if want_orfs:
+                    orfs, pstart, res = got[2:5]
+                    orfs["seq"] += k
+                    oparts.append(orfs)
+                    lens.append(np.diff(pstart))
+                    residues.append(res)
+            elif want_orfs:
                 regs, start, orfs, pstart, res = r.orfs(batch, off, merge_gap, min_score, min_len, start_codons, not write_all)
                 orfs["seq"] += k
                 oparts.append(orfs)
@@ -180,26 +226,34 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
             else:
                 regs, start = r.regions(off, merge_gap, min_score, min_len)
         regs["seq"] += k
+        n_before += len(regs)
         parts.append(regs)
         starts.append(start[1:] + starts[-1][-1])
         k = j
     regs = np.concatenate(parts) if parts else np.zeros(0, dtype=hotpath.N.REGION_DTYPE)
-    with open(out, "wb") as f:
-        f.write(format_regions(ids, regs, fnames, write_all, gff))
-    line = summary_of(regs, np.concatenate(starts))
+    sel = None
+    if select:
+        sel = np.concatenate(sparts) if sparts else np.zeros(0, dtype=hotpath.N.SELECTION_DTYPE)
+    orfs = None
     if want_orfs:
         orfs = np.concatenate(oparts) if oparts else np.zeros(0, dtype=hotpath.N.ORF_DTYPE)
+    with open(out, "wb") as f:
+        f.write(format_regions(ids, regs, fnames, write_all, gff, sel, orfs))
+    line = summary_of(regs, np.concatenate(starts))
+    if want_orfs:
         pstart = np.zeros(len(orfs) + 1, dtype=np.int64)
         if lens:
             np.cumsum(np.concatenate(lens), out=pstart[1:])
         if orfs_out is not None:
             with open(orfs_out, "wb") as f:
-                f.write(format_orfs(ids, regs, orfs, fnames, write_all))
+                f.write(format_orfs(ids, regs, orfs, fnames, write_all, sel))
         if faa_out is not None:
             with open(faa_out, "wb") as f:
                 f.write(format_faa(ids, regs, orfs, pstart, np.concatenate(residues) if residues else np.zeros(0, np.uint8),
-                                   fnames, write_all))
+                                   fnames, write_all, sel))
         line += orf_summary(orfs)
+    if select:
+        line += select_summary(sel)
     return line
 
 
@@ -221,11 +275,15 @@ def main(argv=None) -> int:
     ap.add_argument("--orfs", metavar="ORFS.tsv", help="also write the open reading frame around every written region")
     ap.add_argument("--faa", metavar="PROTEINS.faa", help="also write the translated proteins (FASTA, for annotate -p / make_signatures -p)")
     ap.add_argument("--start-codons", default="ATG,GTG,TTG", help="start codons of the ORF extension (default ATG,GTG,TTG; none: no start search)")
+    ap.add_argument("--select", action="store_true", help="write a gene set: only the non-overlapping selection among the kept candidates")
+    ap.add_argument("--max-overlap", type=int, default=60, help="nucleotides two selected candidates may share (default 60, this project's choice)")
+    ap.add_argument("--max-overlap-pct", type=int, default=50, help="... and percent of the shorter one (default 50)")
     a = ap.parse_args(argv)
     from . import _native as N
     try:
         line = call_regions(a.D, a.q, a.o, a.m, a.M, a.g, a.O, a.merge_gap, a.min_score, a.min_len, a.all, a.gff,
-                            orfs_out=a.orfs, faa_out=a.faa, start_codons=parse_start_codons(a.start_codons))
+                            orfs_out=a.orfs, faa_out=a.faa, start_codons=parse_start_codons(a.start_codons), select=a.select,
+                            max_overlap=a.max_overlap, max_overlap_pct=a.max_overlap_pct)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1

@@ -10,6 +10,7 @@ struct kg_orfset {
     int64_t *d_prot_start = nullptr;    // count + 1
     uint8_t *d_res = nullptr;           // residues bytes
     int64_t count = 0, residues = 0;
+    int64_t n_seqs = 0, l_max = 0;      // the batch's contigs and the longest of them (kg_orfset_select)
     kg_orf_stats st = {};
 };
 
@@ -34,8 +35,10 @@ int orfs_impl(kg_table *t, const kg_orf_params *prm, const kg_region *d_regions,
     Scratch sc(t);
     hipStream_t s = t->stream;
     int rc;
-    for (uint64_t k = 0; k < n_seqs; k++)
+    for (uint64_t k = 0; k < n_seqs; k++) {
         tile_base[k + 1] = tile_base[k] + ((offsets[k + 1] - offsets[k]) / 3 + kg::kOrfTile - 1) / kg::kOrfTile;
+        set->l_max = std::max(set->l_max, offsets[k + 1] - offsets[k]);
+    }
     const uint64_t n_rows = (uint64_t)tile_base[n_seqs], n_tiles = 3 * n_rows;
     const uint64_t total = n_seqs ? (uint64_t)offsets[n_seqs] : 0;
     if (n_rows >= (1ull << 31)) return fail(KG_ERR_LIMIT, "2^31 or more tile rows in one call");
@@ -113,6 +116,7 @@ int orfs_impl(kg_table *t, const kg_orf_params *prm, const kg_region *d_regions,
     set->d_res = d_res;
     set->count = (int64_t)n;
     set->residues = (int64_t)n_res;
+    set->n_seqs = (int64_t)n_seqs;
     return KG_OK;
 }
 

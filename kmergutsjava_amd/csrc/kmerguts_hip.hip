@@ -16,6 +16,7 @@
 #include "kg_assign.hpp"
 #include "kg_regions.hpp"
 #include "kg_orfs.hpp"
+#include "kg_select.hpp"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -39,3 +40,4 @@
 #include "kg_host_assign.hpp"
 #include "kg_host_regions.hpp"
 #include "kg_host_orfs.hpp"
+#include "kg_host_select.hpp"

@@ -251,6 +251,52 @@ class ScanResult:
         regs, start, self.region_stats = _take_regionset(h, self.stats["n_seqs"], False)
         return regs, start, orfs, prot_start, residues
 
+    def select(self, offsets, seq=None, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, orfs: bool = False,
+               start_codons: int = 7, only_kept: bool = True, device_ptr: Optional[int] = None, max_overlap: int = 60,
+               max_overlap_pct: int = 50):
+        """regions() -- with orfs=True, orfs() -- and then the non-overlapping selection among the kept records, on the GPU and
+        without a host trip or a second scan in between (include/kmerguts_hip.h kg_regionset_select states the rule).  The
+        candidates are the regions' extents, or with orfs=True the ORFs' extents.
+        -> (regions, region_start, selection), or with orfs=True (regions, region_start, orfs, prot_start, residues, selection):
+        selection a numpy array of _native.SELECTION_DTYPE, index-aligned with the regions (and the ORFs).  The calls' counts and
+        device times are left in `region_stats`, `orf_stats` and `select_stats`."""
+        lib = self._need()
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+        if off.shape != (self.stats["n_seqs"] + 1,):
+            raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
+        p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
+        sp = N.KgSelectParams(int(max_overlap), int(max_overlap_pct), 0)
+        h, oh, sh = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        N.check(lib.kg_result_regions(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
+        try:
+            if orfs:
+                if device_ptr is not None:
+                    ptr, on_device, keep = C.c_void_p(device_ptr), 1, None
+                else:
+                    keep = _seq_bytes(seq, off)
+                    ptr, on_device = (keep.ctypes.data if keep.size else None), 0
+                op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
+                N.check(lib.kg_regionset_orfs(h, C.byref(op), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(oh)))
+                N.check(lib.kg_orfset_select(oh, C.byref(sp), C.byref(sh)))
+            else:
+                N.check(lib.kg_regionset_select(h, C.byref(sp), C.byref(sh)))
+            taken, sh = sh, C.c_void_p()                # (_take_* frees what it is given, also when it raises)
+            sel, self.select_stats = _take_selectset(taken, False)      # a select set is freed before the set it came from
+            if orfs:
+                taken, oh = oh, C.c_void_p()
+                orf_recs, prot_start, residues, self.orf_stats = _take_orfset(taken, False)
+        except BaseException:
+            if sh:
+                lib.kg_selectset_free(sh)
+            if oh:
+                lib.kg_orfset_free(oh)
+            lib.kg_regionset_free(h)
+            raise
+        regs, start, self.region_stats = _take_regionset(h, self.stats["n_seqs"], False)
+        if orfs:
+            return regs, start, orf_recs, prot_start, residues, sel
+        return regs, start, sel
+
     def close(self) -> None:
         if self._h:
             N.load().kg_result_free(self._h)
@@ -622,3 +668,38 @@ def orf_regions(regs, seq, offsets, start_codons: int = 7, only_kept: bool = Tru
     if stats is not None:
         stats.update(st)
     return out, start, res
+
+
+def _take_selectset(h, device_out: bool):
+    """Copy a kg_selectset out (to the host, or into a CUDA tensor) and free it.  -> (records, statistics)."""
+    lib = N.load()
+    try:
+        st = N.KgSelectStats()
+        N.check(lib.kg_selectset_stats(h, C.byref(st)))
+        n = int(lib.kg_selectset_count(h))
+        if device_out:
+            import torch
+            out = torch.empty(n * N.SELECTION_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            N.check(lib.kg_selectset_copy(h, 0, n, C.c_void_p(out.data_ptr() if n else None)))
+        else:
+            out = np.zeros(n, dtype=N.SELECTION_DTYPE)
+            N.check(lib.kg_selectset_copy(h, 0, n, out.ctypes.data if n else None))
+        return out, st.as_dict()
+    finally:
+        lib.kg_selectset_free(h)
+
+
+def select_intervals(iv, n_seqs: int, max_overlap: int = 60, max_overlap_pct: int = 50, device_out: bool = False,
+                     stats: Optional[dict] = None, device: int = 0):
+    """The non-overlapping selection among caller-held candidates, on the GPU (kg_select_intervals): iv INTERVAL_DTYPE in any
+    order, `seq` in [0, n_seqs).  -> a numpy array of _native.SELECTION_DTYPE index-aligned with iv, or with device_out=True a
+    CUDA uint8 tensor of 8 bytes per candidate; `stats`, when given, receives the call's counts, rounds and device time."""
+    a = np.ascontiguousarray(iv, dtype=N.INTERVAL_DTYPE)
+    p = N.KgSelectParams(int(max_overlap), int(max_overlap_pct), 0)
+    h = C.c_void_p()
+    N.check(N.load().kg_select_intervals(device, C.byref(p), a.ctypes.data if a.size else None, a.size, int(n_seqs), C.byref(h)))
+    out, st = _take_selectset(h, device_out)
+    if stats is not None:
+        stats.update(st)
+    return out
