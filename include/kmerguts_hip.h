@@ -11,6 +11,7 @@
  * kg_result_assign / kg_assign_calls turn the CALL records of an -a scan into one function per protein.
  * kg_result_regions / kg_regions_calls merge the CALL records of a DNA scan into function regions in contig coordinates.
  * kg_regionset_orfs / kg_orfs_regions extend every region to its open reading frame and extract the translated protein.
+ * kg_orfs_free / kg_orfset_add_free enumerate the evidence-free open reading frames of the six frames.
  *
  * Conventions: plain pointers and sizes only; every function returns an int status
  * (KG_OK == 0, negative == error) and never throws or aborts across the boundary; the text
@@ -492,6 +493,54 @@ int kg_orfset_prot_start(const kg_orfset *s, int64_t *dst);
 int kg_orfset_residues(const kg_orfset *s, int64_t first, int64_t count, uint8_t *dst);
 int kg_orfset_stats(const kg_orfset *s, kg_orf_stats *out);
 void kg_orfset_free(kg_orfset *s);
+
+/* ---- evidence-free open reading frames: every long stop-free run of the six frames (kernels: kg_orfs.hpp) ----
+ *
+ * The reference stops at the CALL lines; this rule is the project's own.  It fills a gene set with ab initio candidates
+ * ("hypothetical protein") where the table knows no family.
+ * Input: the batch's sequence bytes exactly as the scan got them, and offsets[n_seqs + 1].  No table and no region takes part.
+ * Strand, frame, codon j of frame f, n_f and the codon classes (stop, start by the start_codons mask, unknown) are exactly
+ * rule 1 of the ORF section above.
+ *   1. Runs.  For every contig, strand and frame (the scan's six containers), the stops of the frame are the codons j that are
+ *      stops.  A run is (u, e): e is a stop, or e = n_f once per container (the run that reaches the contig's end); u is the
+ *      largest stop < e, else -1.  A container with n_f = 0 has no run.
+ *   2. Start.  b is the smallest start in (u, e).  Without one, b = u + 1 when u == -1 or start_codons == 0; otherwise the run
+ *      gives no candidate.
+ *   3. Length.  n_res = min(e, n_f) - b.  The run gives a candidate iff n_res >= min_res.
+ *   4. Record.  The candidate is a kg_orf with the fields and the coordinate rule of rule 4 of the ORF section: left .. right
+ *      covers codons b .. e, or b .. n_f - 1 when e == n_f, mirrored on '-'; start_codon as there; first_inner = -1, fI = -1,
+ *      score = 0, kept = 1; flags = KG_ORF_FREE, plus KG_ORF_HAS_STOP when e < n_f, plus KG_ORF_PARTIAL5 when u == -1.  It is
+ *      never INTERRUPTED or MULTI_FRAME.
+ *   5. Protein.  Exactly rule 5 of the ORF section: 'M' first when start_codon != 0, 'X' for an unknown codon.  By construction
+ *      there is no '*'.  An unknown codon is neither stop nor start, so a run of N's is a run: that is stated, not repaired.
+ *   6. Order.  By contig, then strand ('+' first), then frame 0, 1, 2, then increasing b: the scan's container order.
+ *   7. Independence.  The output depends only on (bytes, offsets, parameters): not on launch geometry, tile size or batch
+ *      neighbours.
+ * Parameters kg_free_params { min_res, start_codons, reserved }: min_res >= 1 (default 100, this project's choice),
+ * start_codons in 0..7 (default 7), reserved == 0; anything else is KG_ERR_ARG.
+ * Selection.  score = 0 is this project's choice too.  Every kept evidence region has a score of at least minHits >= 2, so under
+ * the selection rule below an evidence candidate never loses to a free one, and among free ones the longer wins: adding free
+ * ORFs to an ORF set cannot change the selection state (or `by`) of any evidence ORF.  A weak evidence region therefore still
+ * beats a long free ORF; the region stage's min_score is the caller's lever.
+ * kg_orfs_free is table-less and gives an ordinary ORF set of the free candidates alone: every kg_orfset_* call works on it.
+ * kg_orfset_add_free gives a NEW ORF set in the given set's context: the given set's records first, index-aligned and
+ * unchanged (its only_kept zero lengths too), then the free candidates of the same batch in rule-6 order; prot_start and the
+ * residues cover both parts.  The given set stays valid; the new one holds blocks of the same context, so it is freed before
+ * the given set when that one owns its context (kg_orfs_regions, kg_orfs_free) and before the region set otherwise, as its
+ * parent is.  kg_orfset_stats keeps its layout: orfs, complete, partial5 and residues count the whole set (the free ones are
+ * the count minus the parent's), interrupted is the parent's.
+ * Errors: KG_ERR_ARG for bad params, null pointers, n_seqs that is not the given set's, decreasing offsets; KG_ERR_LIMIT for
+ * 2^31 or more contigs, nucleotides of one contig or candidates (the given set's included), or 2^32 or more residues;
+ * KG_ERR_BUSY while a kg_scan* is in flight on the given set's table; KG_ERR_NOMEM.  Zero sequences are valid.  Device
+ * allocations come from the context's block cache, so KG_TEST_FAIL_ALLOC applies; everything but the new set's three arrays is
+ * back in the cache on every path out. */
+#define KG_ORF_FREE        16u
+typedef struct kg_free_params { int32_t min_res; int32_t start_codons; int32_t reserved; } kg_free_params;
+/* seq: the batch's bytes, in device memory when seq_on_device != 0; offsets: host, n_seqs + 1 */
+int kg_orfs_free(int device, const kg_free_params *p, const uint8_t *seq, int seq_on_device, const int64_t *offsets,
+                 int64_t n_seqs, kg_orfset **out);
+int kg_orfset_add_free(kg_orfset *set, const kg_free_params *p, const uint8_t *seq, int seq_on_device, const int64_t *offsets,
+                       int64_t n_seqs, kg_orfset **out);
 
 /* ---- a gene set: the non-overlapping selection among regions or ORFs (kernels: kg_select.hpp) ----
  *

@@ -161,6 +161,14 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_free_params (kg_orfs_free / kg_orfset_add_free); this project's defaults: 100, 7 (ATG, GTG, TTG) and 0. */
+    class KgFreeParams extends Structure {
+        public int min_res, start_codons, reserved;
+        public KgFreeParams() {
+            setFieldOrder(new String[] {"min_res", "start_codons", "reserved"});
+        }
+    }
+
     /** struct kg_select_params (kg_regionset_select / kg_orfset_select / kg_select_intervals); this project's defaults: 60, 50 and 0. */
     class KgSelectParams extends Structure {
         public int max_overlap, max_overlap_pct, reserved;
@@ -269,6 +277,11 @@ public interface KmerGutsHip extends Library {
     int kg_orfset_residues(Pointer set, long first, long count, Pointer dst);
     int kg_orfset_stats(Pointer set, KgOrfStats out);
     void kg_orfset_free(Pointer set);
+    /** the evidence-free open reading frames of a batch (flag 16 = KG_ORF_FREE): alone, or behind the records of an ORF set */
+    int kg_orfs_free(int device, KgFreeParams params, Pointer seq, int seqOnDevice, long[] offsets, long nSeqs,
+                     PointerByReference out);
+    int kg_orfset_add_free(Pointer set, KgFreeParams params, Pointer seq, int seqOnDevice, long[] offsets, long nSeqs,
+                           PointerByReference out);
     /** the non-overlapping selection among the kept regions / ORFs of a set; free the select set before the set it came from */
     int kg_regionset_select(Pointer set, KgSelectParams params, PointerByReference out);
     int kg_orfset_select(Pointer set, KgSelectParams params, PointerByReference out);

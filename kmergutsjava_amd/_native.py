@@ -37,7 +37,7 @@ EXPORTS = (
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
-    "kg_orfset_residues", "kg_orfset_stats", "kg_orfset_free",
+    "kg_orfset_residues", "kg_orfset_stats", "kg_orfset_free", "kg_orfs_free", "kg_orfset_add_free",
     "kg_regionset_select", "kg_orfset_select", "kg_select_intervals", "kg_selectset_count", "kg_selectset_device",
     "kg_selectset_copy", "kg_selectset_stats", "kg_selectset_free",
     "kg_last_error", "kg_version",
@@ -73,6 +73,7 @@ ORF_DTYPE = np.dtype([("seq", "<i4"), ("strand", "<i4"), ("frame", "<i4"), ("lef
                       ("kept", "<i4")])
 assert ORF_DTYPE.itemsize == 48
 ORF_HAS_STOP, ORF_PARTIAL5, ORF_INTERRUPTED, ORF_MULTI_FRAME = 1, 2, 4, 8
+ORF_FREE = 16               # an evidence-free candidate (kg_orfs_free / kg_orfset_add_free)
 ORF_TILE_CODONS = 128       # kg_orfs.hpp kOrfTile: the codons of one tile summary (tests aim at its edges)
 # struct kg_interval (kg_select_intervals) and struct kg_selection (kg_*_select): a candidate and what became of it
 INTERVAL_DTYPE = np.dtype([("seq", "<i4"), ("left", "<i4"), ("right", "<i4"), ("score", "<i4"), ("eligible", "<i4")])
@@ -160,6 +161,14 @@ class KgOrfStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
+class KgFreeParams(C.Structure):
+    """struct kg_free_params (kg_orfs_free / kg_orfset_add_free)."""
+    _fields_ = [("min_res", C.c_int32), ("start_codons", C.c_int32), ("reserved", C.c_int32)]
+
+
+FREE_PARAMS = KgFreeParams
 
 
 class KgSelectParams(C.Structure):
@@ -275,6 +284,8 @@ def load() -> C.CDLL:
     lib.kg_orfset_stats.argtypes = [vp, C.POINTER(KgOrfStats)]
     lib.kg_orfset_free.argtypes = [vp]
     lib.kg_orfset_free.restype = None
+    lib.kg_orfs_free.argtypes = [C.c_int, C.POINTER(KgFreeParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
+    lib.kg_orfset_add_free.argtypes = [vp, C.POINTER(KgFreeParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
     lib.kg_regionset_select.argtypes = [vp, C.POINTER(KgSelectParams), C.POINTER(vp)]
     lib.kg_orfset_select.argtypes = [vp, C.POINTER(KgSelectParams), C.POINTER(vp)]
     lib.kg_select_intervals.argtypes = [C.c_int, C.POINTER(KgSelectParams), vp, C.c_int64, C.c_int64, C.POINTER(vp)]

@@ -5,6 +5,7 @@
                                             [--merge-gap 600] [--min-score 0] [--min-len 0] [--all] [--gff]
                                             [--orfs ORFS.tsv] [--faa PROTEINS.faa] [--start-codons ATG,GTG,TTG]
                                             [--select [--max-overlap 60] [--max-overlap-pct 50]]
+                                            [--free-orfs [--min-res 100]]
 
 The table and function.index[.gz] are loaded the way annotate loads them.  Contigs are read with
 make_signatures.parse_fasta (a duplicate id is an error) and scanned whole, in batches of at most
@@ -33,6 +34,17 @@ length, then position in the output -- wins).  Only selected candidates are writ
 candidate is written, the status is kept, below or overlapped, and the TSV and GFF lines gain one trailing field (GFF: the
 attribute overlapped_by) that names the winner an overlapped candidate lost to as left+1..right+1:strand, or `-`.  The summary
 line gains `, selected: S, overlapped: V`.
+
+--free-orfs (with --orfs or --faa) fills the output with evidence-free candidates: every stop-free run of the six frames that
+gives at least --min-res residues (default 100, this project's choice) from its first start codon of --start-codons, found on
+the GPU (kg_orfset_add_free; include/kmerguts_hip.h states the rule).  The regions file never gains a line.  In the ORF file a
+contig's lines are followed by its free ORFs in the library's order (strand, frame, position), each with function
+`hypothetical protein`, score 0 and the extra flag word `free`; the protein file gets them as
+`>contig_left+1_right+1_strand hypothetical protein` behind the contig's other proteins, an extent that is already written
+being written once.  With --select they are candidates like the others: their score is 0, so a free ORF never beats a region's
+ORF (raise --min-score to let long free ORFs replace weak regions) and among free ORFs the longer wins; with --all a free ORF's
+line gains two trailing fields, its status kept or overlapped and the winner as in the regions file.  The summary line counts
+the free ORFs among selected and overlapped and gains `, free: F` at its end.
 """
 from __future__ import annotations
 
@@ -115,7 +127,8 @@ def format_regions(ids, regs, fnames, write_all: bool = False, gff: bool = False
 
 
 START_NAMES = (b"ATG", b"GTG", b"TTG")
-FLAG_WORDS = ((1, b"stop"), (2, b"partial5"), (4, b"interrupted"), (8, b"multi-frame"))
+FLAG_WORDS = ((1, b"stop"), (2, b"partial5"), (4, b"interrupted"), (8, b"multi-frame"), (16, b"free"))
+FREE_NAME = b"hypothetical protein"
 
 
 def parse_start_codons(text: str) -> int:
@@ -138,23 +151,51 @@ def orf_summary(orfs) -> str:
     return ", orfs: %d, complete: %d, interrupted: %d" % (len(orfs), int(complete.sum()), int(((fl & 4) != 0).sum()))
 
 
-def format_orfs(ids, regs, orfs, fnames, write_all: bool = False, sel=None) -> bytes:
-    """ORF records (ORF_DTYPE, index-aligned with regs) as text, one line per written region."""
+def _orf_line(ids, o, name: bytes) -> bytes:
+    words = b",".join(w for bit, w in FLAG_WORDS if int(o["flags"]) & bit) or b"-"
+    start = START_NAMES[int(o["start_codon"]) - 1] if o["start_codon"] else b"-"
+    return b"%s\t%d\t%d\t%s\t%d\t%s\t%d\t%d\t%s\t%s" % (ids[int(o["seq"])], o["left"] + 1, o["right"] + 1, b"-" if o["strand"] else b"+",
+                                                        o["frame"], name, o["score"], o["n_res"], start, words)
+
+
+def _by_contig(first, second) -> list:
+    """Two lists of (contig, text), each in contig order -> the texts contig by contig, the first list's in front."""
+    return [x[2] for x in sorted([(c, 0, t) for c, t in first] + [(c, 1, t) for c, t in second], key=lambda x: x[:2])]
+
+
+def format_orfs(ids, regs, orfs, fnames, write_all: bool = False, sel=None, free=None, free_sel=None, cands=None) -> bytes:
+    """ORF records (ORF_DTYPE, index-aligned with regs) as text, one line per written region.  free: the free ORFs of
+    --free-orfs, written behind their contig's lines; free_sel: their selection records; cands: the records the selection ran on
+    (the winners of --all are named from them)."""
     lines = []
     for i, (r, o) in enumerate(zip(regs, orfs)):
         if not _written(r, write_all, sel, i):
             continue
-        words = b",".join(w for bit, w in FLAG_WORDS if int(o["flags"]) & bit) or b"-"
-        start = START_NAMES[int(o["start_codon"]) - 1] if o["start_codon"] else b"-"
-        lines.append(b"%s\t%d\t%d\t%s\t%d\t%s\t%d\t%d\t%s\t%s\n" %
-                     (ids[int(o["seq"])], o["left"] + 1, o["right"] + 1, b"-" if o["strand"] else b"+", o["frame"],
-                      _fname(fnames, int(o["fI"])), o["score"], o["n_res"], start, words))
-    return b"".join(lines)
+        lines.append((int(o["seq"]), _orf_line(ids, o, _fname(fnames, int(o["fI"]))) + b"\n"))
+    if free is None:
+        return b"".join(t for _, t in lines)
+    flines = []
+    for i, o in enumerate(free):
+        if not (write_all or free_sel is None or free_sel["state"][i] == 1):
+            continue
+        tail = b""
+        if free_sel is not None and write_all:
+            tail = b"\t%s\t%s" % (b"overlapped" if free_sel["state"][i] == 2 else b"kept", _winner(free_sel, i, cands))
+        flines.append((int(o["seq"]), _orf_line(ids, o, FREE_NAME) + tail + b"\n"))
+    return b"".join(_by_contig(lines, flines))
 
 
-def format_faa(ids, regs, orfs, prot_start, residues, fnames, write_all: bool = False, sel=None) -> bytes:
+def _fasta(ids, key, name: bytes, p: bytes) -> bytes:
+    head = b">%s_%d_%d_%s %s\n" % (ids[key[0]], key[2] + 1, key[3] + 1, b"-" if key[1] else b"+", name)
+    return head + b"".join(p[k:k + 60] + b"\n" for k in range(0, len(p), 60))
+
+
+def format_faa(ids, regs, orfs, prot_start, residues, fnames, write_all: bool = False, sel=None, free=None, free_sel=None,
+               free_prot_start=None, free_residues=None) -> bytes:
     """The proteins of the written regions as FASTA: an ORF with the (contig, strand, left, right) of an earlier written one is
-    written once, where the first of them stands, under the region with the largest score (ties: the first)."""
+    written once, where the first of them stands, under the region with the largest score (ties: the first).  free, free_sel,
+    free_prot_start, free_residues: the free ORFs of --free-orfs, written behind their contig's proteins unless their extent is
+    there already."""
     res = np.asarray(residues, dtype=np.uint8).tobytes()
     best, order = {}, []
     for i, (r, o) in enumerate(zip(regs, orfs)):
@@ -169,18 +210,30 @@ def format_faa(ids, regs, orfs, prot_start, residues, fnames, write_all: bool = 
     out = []
     for key in order:
         i = best[key]
-        o = orfs[i]
-        out.append(b">%s_%d_%d_%s %s\n" % (ids[key[0]], key[2] + 1, key[3] + 1, b"-" if key[1] else b"+", _fname(fnames, int(o["fI"]))))
-        p = res[int(prot_start[i]):int(prot_start[i + 1])]
-        out += [p[k:k + 60] + b"\n" for k in range(0, len(p), 60)]
-    return b"".join(out)
+        out.append((key[0], _fasta(ids, key, _fname(fnames, int(orfs[i]["fI"])), res[int(prot_start[i]):int(prot_start[i + 1])])))
+    if free is None:
+        return b"".join(t for _, t in out)
+    fres = np.asarray(free_residues, dtype=np.uint8).tobytes()
+    fout = []
+    for i, o in enumerate(free):
+        key = (int(o["seq"]), int(o["strand"]), int(o["left"]), int(o["right"]))
+        if not (write_all or free_sel is None or free_sel["state"][i] == 1) or key in best:
+            continue
+        best[key] = -1
+        fout.append((key[0], _fasta(ids, key, FREE_NAME, fres[int(free_prot_start[i]):int(free_prot_start[i + 1])])))
+    return b"".join(_by_contig(out, fout))
 
 
 def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_weighted_hits: int = 0, max_gap: int = 200,
                  order_constraint: bool = False, merge_gap: int = 600, min_score: int = 0, min_len: int = 0,
                  write_all: bool = False, gff: bool = False, device: int = 0, orfs_out: str = None, faa_out: str = None,
-                 start_codons: int = 7, select: bool = False, max_overlap: int = 60, max_overlap_pct: int = 50) -> str:
-    """Write the regions (and, with orfs_out / faa_out, their open reading frames and proteins); returns the summary line."""
+                 start_codons: int = 7, select: bool = False, max_overlap: int = 60, max_overlap_pct: int = 50,
+                 free_min_res: int = None) -> str:
+    """Write the regions (and, with orfs_out / faa_out, their open reading frames and proteins; with free_min_res also the
+    evidence-free ORFs of at least that many residues); returns the summary line."""
+    want_orfs = orfs_out is not None or faa_out is not None
+    if free_min_res is not None and not want_orfs:
+        raise ValueError("--free-orfs needs --orfs or --faa: free ORFs are written to those files only")
     from . import hotpath
     from .kmer_guts_java import KmerGutsJava, _resident_table
     table_path = _data_file(data_dir, "kmer.table.mem_map")
@@ -193,9 +246,9 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
     params = hotpath.Params(aa=False, order_constraint=order_constraint, min_hits=min_hits, min_weighted_hits=min_weighted_hits,
                             max_gap=max_gap)
     parts, starts = [], [np.zeros(1, dtype=np.int64)]
-    want_orfs = orfs_out is not None or faa_out is not None
     oparts, lens, residues, sparts = [], [], [], []
-    k = n_before = 0
+    fparts, flens, fresidues, fsparts = [], [], [], []          # the free ORFs, and per batch (selection, first free record)
+    k = n_before = n_free = 0
     while k < len(ids):
         j, size = k, 0
         while j < len(ids) and (j == k or size + len(seqs[j]) <= KmerGutsJava.MAX_BATCH_CHARS):
@@ -207,22 +260,30 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         with tab.scan(batch, off, params) as r:
             if select:
                 got = r.select(off, batch, merge_gap, min_score, min_len, want_orfs, start_codons, not write_all,
-                               max_overlap=max_overlap, max_overlap_pct=max_overlap_pct)
+                               max_overlap=max_overlap, max_overlap_pct=max_overlap_pct, free_min_res=free_min_res)
                 regs, start, sel = got[0], got[1], got[-1]
-                sel["by"][sel["by"] >= 0] += n_before       # (selection is per contig: a batch's winners are its own records)
-                sparts.append(sel)
+                # (selection is per contig: a batch's winners are its own records; a free winner is marked by -2 - its index
+                # among all free ORFs until the regions of every batch are counted)
+                by, nr = sel["by"], len(regs)
+                by[by >= nr] = -2 - (by[by >= nr] - nr + n_free)
+                by[by >= 0] += n_before
+                sparts.append(sel[:nr])
+                fsparts.append(sel[nr:])
                 if want_orfs:
                     orfs, pstart, res = got[2:5]
-                    orfs["seq"] += k
-                    oparts.append(orfs)
-                    lens.append(np.diff(pstart))
-                    residues.append(res)
             elif want_orfs:
-                regs, start, orfs, pstart, res = r.orfs(batch, off, merge_gap, min_score, min_len, start_codons, not write_all)
+                regs, start, orfs, pstart, res = r.orfs(batch, off, merge_gap, min_score, min_len, start_codons, not write_all,
+                                                        free_min_res=free_min_res)
+            if want_orfs:
+                nr = len(regs)                              # the regions' ORFs, then the batch's free ones
                 orfs["seq"] += k
-                oparts.append(orfs)
-                lens.append(np.diff(pstart))
-                residues.append(res)
+                oparts.append(orfs[:nr])
+                lens.append(np.diff(pstart[:nr + 1]))
+                residues.append(res[:pstart[nr]])
+                fparts.append(orfs[nr:])
+                flens.append(np.diff(pstart[nr:]))
+                fresidues.append(res[pstart[nr]:])
+                n_free += len(orfs) - nr
             else:
                 regs, start = r.regions(off, merge_gap, min_score, min_len)
         regs["seq"] += k
@@ -234,26 +295,42 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
     sel = None
     if select:
         sel = np.concatenate(sparts) if sparts else np.zeros(0, dtype=hotpath.N.SELECTION_DTYPE)
-    orfs = None
+    orfs = free = free_sel = cands = None
     if want_orfs:
-        orfs = np.concatenate(oparts) if oparts else np.zeros(0, dtype=hotpath.N.ORF_DTYPE)
+        orfs = cands = np.concatenate(oparts) if oparts else np.zeros(0, dtype=hotpath.N.ORF_DTYPE)
+    if free_min_res is not None:
+        free = np.concatenate(fparts) if fparts else np.zeros(0, dtype=hotpath.N.ORF_DTYPE)
+        cands = np.concatenate([orfs, free])
+        if select:
+            free_sel = np.concatenate(fsparts) if fsparts else np.zeros(0, dtype=hotpath.N.SELECTION_DTYPE)
+            for part in (sel, free_sel):
+                by = part["by"]
+                by[by <= -2] = len(orfs) + (-2 - by[by <= -2])
     with open(out, "wb") as f:
-        f.write(format_regions(ids, regs, fnames, write_all, gff, sel, orfs))
+        f.write(format_regions(ids, regs, fnames, write_all, gff, sel, cands))
     line = summary_of(regs, np.concatenate(starts))
     if want_orfs:
         pstart = np.zeros(len(orfs) + 1, dtype=np.int64)
         if lens:
             np.cumsum(np.concatenate(lens), out=pstart[1:])
+        fstart = None
+        if free is not None:
+            fstart = np.zeros(len(free) + 1, dtype=np.int64)
+            if flens:
+                np.cumsum(np.concatenate(flens), out=fstart[1:])
         if orfs_out is not None:
             with open(orfs_out, "wb") as f:
-                f.write(format_orfs(ids, regs, orfs, fnames, write_all, sel))
+                f.write(format_orfs(ids, regs, orfs, fnames, write_all, sel, free, free_sel, cands))
         if faa_out is not None:
             with open(faa_out, "wb") as f:
                 f.write(format_faa(ids, regs, orfs, pstart, np.concatenate(residues) if residues else np.zeros(0, np.uint8),
-                                   fnames, write_all, sel))
+                                   fnames, write_all, sel, free, free_sel, fstart,
+                                   np.concatenate(fresidues) if fresidues else np.zeros(0, np.uint8)))
         line += orf_summary(orfs)
     if select:
-        line += select_summary(sel)
+        line += select_summary(sel if free_sel is None else np.concatenate([sel, free_sel]))
+    if free is not None:
+        line += ", free: %d" % len(free)
     return line
 
 
@@ -278,12 +355,17 @@ def main(argv=None) -> int:
     ap.add_argument("--select", action="store_true", help="write a gene set: only the non-overlapping selection among the kept candidates")
     ap.add_argument("--max-overlap", type=int, default=60, help="nucleotides two selected candidates may share (default 60, this project's choice)")
     ap.add_argument("--max-overlap-pct", type=int, default=50, help="... and percent of the shorter one (default 50)")
+    ap.add_argument("--free-orfs", action="store_true", help="with --orfs / --faa: also write the evidence-free ORFs (hypothetical protein)")
+    ap.add_argument("--min-res", type=int, default=100, help="residues a free ORF has at least (default 100, this project's choice)")
     a = ap.parse_args(argv)
+    if a.free_orfs and a.orfs is None and a.faa is None:
+        ap.error("--free-orfs needs --orfs or --faa")
     from . import _native as N
     try:
         line = call_regions(a.D, a.q, a.o, a.m, a.M, a.g, a.O, a.merge_gap, a.min_score, a.min_len, a.all, a.gff,
                             orfs_out=a.orfs, faa_out=a.faa, start_codons=parse_start_codons(a.start_codons), select=a.select,
-                            max_overlap=a.max_overlap, max_overlap_pct=a.max_overlap_pct)
+                            max_overlap=a.max_overlap, max_overlap_pct=a.max_overlap_pct,
+                            free_min_res=a.min_res if a.free_orfs else None)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1

@@ -1,5 +1,5 @@
-// kg_host_orfs.hpp -- kg_regionset_orfs / kg_orfs_regions: function regions -> open reading frames and their proteins
-// (kernels: kg_orfs.hpp).
+// kg_host_orfs.hpp -- kg_regionset_orfs / kg_orfs_regions: function regions -> open reading frames and their proteins;
+// kg_orfs_free / kg_orfset_add_free: the evidence-free open reading frames of the six frames (kernels: kg_orfs.hpp).
 // Part of kmerguts_hip.hip's translation unit: the last of the batch stages, behind kg_host_regions.hpp (it reads kg_regionset).
 #pragma once
 
@@ -24,55 +24,109 @@ int check_orf_params(const kg_orf_params *p)
     return KG_OK;
 }
 
-// d_regions[n]: device array complete on t->stream; d_seq: the batch's bytes on the device (null when there are none);
-// offsets: host, checked.  Fills set (its arrays come out of the cache with the call's scratch and are kept only on success).
-int orfs_impl(kg_table *t, const kg_orf_params *prm, const kg_region *d_regions, uint64_t n, const uint8_t *d_seq,
-              const int64_t *offsets, uint64_t n_seqs, kg_orfset *set)
+int check_free_params(const kg_free_params *p)
 {
-    // the tile rows in front of every contig: a row is kOrfTile codons of each of its three phases (declared in front of the
-    // scratch, whose destructor waits for the stream that copies it)
-    std::vector<int64_t> tile_base(n_seqs + 1, 0);
-    Scratch sc(t);
-    hipStream_t s = t->stream;
-    int rc;
-    for (uint64_t k = 0; k < n_seqs; k++) {
-        tile_base[k + 1] = tile_base[k] + ((offsets[k + 1] - offsets[k]) / 3 + kg::kOrfTile - 1) / kg::kOrfTile;
-        set->l_max = std::max(set->l_max, offsets[k + 1] - offsets[k]);
+    if (!p) return fail(KG_ERR_ARG, "null kg_free_params");
+    if (p->min_res < 1) return fail(KG_ERR_ARG, "min_res must be >= 1");
+    if (p->start_codons < 0 || p->start_codons > 7) return fail(KG_ERR_ARG, "start_codons must be a mask of 1 (ATG), 2 (GTG), 4 (TTG)");
+    if (p->reserved != 0) return fail(KG_ERR_ARG, "kg_free_params.reserved must be 0");
+    return KG_OK;
+}
+
+// The tile rows of a batch and the six scanned arrays over them (kg_orfs.hpp, steps 1 and 2): what the region kernel and the
+// free enumerator both walk.  Declare it in front of the call's scratch, whose destructor waits for the stream that copies
+// tile_base.
+struct OrfPlanes {
+    // the tile rows in front of every contig: a row is kOrfTile codons of each of its three phases
+    std::vector<int64_t> tile_base;
+    uint64_t n_seqs = 0, n_rows = 0, n_tiles = 0, total = 0;
+    uint32_t n_scan = 0;
+    int64_t l_max = 0;
+    int64_t *d_off = nullptr, *d_tb = nullptr, *keys = nullptr, *tile_max = nullptr, *tile_pre = nullptr;
+
+    int plan(const int64_t *offsets, uint64_t n)
+    {
+        n_seqs = n;
+        tile_base.assign(n_seqs + 1, 0);
+        for (uint64_t k = 0; k < n_seqs; k++) {
+            tile_base[k + 1] = tile_base[k] + ((offsets[k + 1] - offsets[k]) / 3 + kg::kOrfTile - 1) / kg::kOrfTile;
+            l_max = std::max(l_max, offsets[k + 1] - offsets[k]);
+        }
+        n_rows = (uint64_t)tile_base[n_seqs];
+        n_tiles = 3 * n_rows;
+        total = n_seqs ? (uint64_t)offsets[n_seqs] : 0;
+        if (n_rows >= (1ull << 31)) return fail(KG_ERR_LIMIT, "2^31 or more tile rows in one call");
+        n_scan = (uint32_t)((n_tiles + kg::kBuildTile - 1) / kg::kBuildTile);
+        return KG_OK;
     }
-    const uint64_t n_rows = (uint64_t)tile_base[n_seqs], n_tiles = 3 * n_rows;
-    const uint64_t total = n_seqs ? (uint64_t)offsets[n_seqs] : 0;
-    if (n_rows >= (1ull << 31)) return fail(KG_ERR_LIMIT, "2^31 or more tile rows in one call");
-    const uint32_t n_scan = (uint32_t)((n_tiles + kg::kBuildTile - 1) / kg::kBuildTile);
-    int64_t *d_off = nullptr, *d_tb = nullptr, *keys = nullptr, *tile_max = nullptr, *tile_pre = nullptr, *d_start = nullptr;
-    unsigned long long *words = nullptr;           // error words, counter words, then the residue total
-    kg_orf *d_out = nullptr;
-    uint32_t *lens = nullptr, *excl = nullptr;
-    uint64_t *partial = nullptr;
-    if ((rc = sc.get(&d_off, n_seqs + 1)) || (rc = sc.get(&d_tb, n_seqs + 1)) || (rc = sc.get(&words, 16)) ||
-        (rc = sc.get(&keys, std::max<uint64_t>(kg::kOrfPlanes * n_tiles, 1))) ||
-        (rc = sc.get(&tile_max, std::max<uint64_t>((uint64_t)kg::kOrfPlanes * n_scan, 1))) ||
-        (rc = sc.get(&tile_pre, std::max<uint64_t>((uint64_t)kg::kOrfPlanes * n_scan, 1))) ||
-        (rc = sc.get(&d_out, std::max<uint64_t>(n, 1))) || (rc = sc.get(&d_start, n + 1)) || (rc = sc.get(&lens, std::max<uint64_t>(n, 1))) ||
-        (rc = sc.get(&excl, std::max<uint64_t>(n, 1))) || (rc = sc.get(&partial, n / kg::kScanChunk + 2)))
-        return rc;
-    unsigned long long *err = words, *cnt = words + kg::kOrfErrWords;
-    uint64_t *d_total = (uint64_t *)(words + kg::kOrfErrWords + kg::kOrfCntWords);
-    HIP_TRY(hipMemcpyAsync(d_off, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_tb, tile_base.data(), (n_seqs + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(err, 0x7F, kg::kOrfErrWords * 8, s));
-    HIP_TRY(hipMemsetAsync(cnt, 0, (kg::kOrfCntWords + 1) * 8, s));
-    HIP_TRY(hipEventRecord(t->ev[kEvStageBegin], s));
-    const kg::OrfGeometry geo{d_off, d_tb, n_seqs, n_tiles};
-    const uint32_t sc_mask = (uint32_t)prm->start_codons;
-    if (n_rows > 0) {
-        hipLaunchKernelGGL(kg::orf_summary_kernel, dim3((uint32_t)((n_rows + 3) / 4)), dim3(256), 0, s, d_seq, total, geo, n_rows, sc_mask, keys);
+    int alloc_geometry(Scratch &sc)
+    {
+        int rc;
+        if ((rc = sc.get(&d_off, n_seqs + 1)) || (rc = sc.get(&d_tb, n_seqs + 1))) return rc;
+        return KG_OK;
+    }
+    int alloc_keys(Scratch &sc)
+    {
+        int rc;
+        if ((rc = sc.get(&keys, std::max<uint64_t>(kg::kOrfPlanes * n_tiles, 1))) ||
+            (rc = sc.get(&tile_max, std::max<uint64_t>((uint64_t)kg::kOrfPlanes * n_scan, 1))) ||
+            (rc = sc.get(&tile_pre, std::max<uint64_t>((uint64_t)kg::kOrfPlanes * n_scan, 1))))
+            return rc;
+        return KG_OK;
+    }
+    int upload(hipStream_t s, const int64_t *offsets)
+    {
+        HIP_TRY(hipMemcpyAsync(d_off, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_tb, tile_base.data(), (n_seqs + 1) * 8, hipMemcpyHostToDevice, s));
+        return KG_OK;
+    }
+    kg::OrfGeometry geometry() const { return kg::OrfGeometry{d_off, d_tb, n_seqs, n_tiles}; }
+    // the summaries and their six prefix maxima
+    int launch(hipStream_t s, const uint8_t *d_seq, uint32_t sc_mask)
+    {
+        if (n_rows == 0) return KG_OK;
+        hipLaunchKernelGGL(kg::orf_summary_kernel, dim3((uint32_t)((n_rows + 3) / 4)), dim3(256), 0, s, d_seq, total, geometry(), n_rows, sc_mask, keys);
         hipLaunchKernelGGL(kg::orf_tile_max_kernel, dim3(n_scan, kg::kOrfPlanes), dim3(kg::kBuildThreads), 0, s, keys, n_tiles, tile_max);
         for (int a = 0; a < kg::kOrfPlanes; a++)
             hipLaunchKernelGGL(kg::build_tile_scan_kernel, dim3(1), dim3(kg::kBuildThreads), 0, s, tile_max + (uint64_t)a * n_scan, n_scan,
                                tile_pre + (uint64_t)a * n_scan);
         hipLaunchKernelGGL(kg::orf_scan_apply_kernel, dim3(n_scan, kg::kOrfPlanes), dim3(kg::kBuildThreads), 0, s, keys, n_tiles, tile_pre);
         HIP_TRY(hipGetLastError());
+        return KG_OK;
     }
+};
+
+// d_regions[n]: device array complete on t->stream; d_seq: the batch's bytes on the device (null when there are none);
+// offsets: host, checked.  Fills set (its arrays come out of the cache with the call's scratch and are kept only on success).
+int orfs_impl(kg_table *t, const kg_orf_params *prm, const kg_region *d_regions, uint64_t n, const uint8_t *d_seq,
+              const int64_t *offsets, uint64_t n_seqs, kg_orfset *set)
+{
+    OrfPlanes pl;
+    Scratch sc(t);
+    hipStream_t s = t->stream;
+    int rc;
+    if ((rc = pl.plan(offsets, n_seqs))) return rc;
+    set->l_max = std::max(set->l_max, pl.l_max);
+    const uint64_t n_tiles = pl.n_tiles;
+    int64_t *d_start = nullptr;
+    unsigned long long *words = nullptr;           // error words, counter words, then the residue total
+    kg_orf *d_out = nullptr;
+    uint32_t *lens = nullptr, *excl = nullptr;
+    uint64_t *partial = nullptr;
+    if ((rc = pl.alloc_geometry(sc)) || (rc = sc.get(&words, 16)) || (rc = pl.alloc_keys(sc)) ||
+        (rc = sc.get(&d_out, std::max<uint64_t>(n, 1))) || (rc = sc.get(&d_start, n + 1)) || (rc = sc.get(&lens, std::max<uint64_t>(n, 1))) ||
+        (rc = sc.get(&excl, std::max<uint64_t>(n, 1))) || (rc = sc.get(&partial, n / kg::kScanChunk + 2)))
+        return rc;
+    unsigned long long *err = words, *cnt = words + kg::kOrfErrWords;
+    uint64_t *d_total = (uint64_t *)(words + kg::kOrfErrWords + kg::kOrfCntWords);
+    if ((rc = pl.upload(s, offsets))) return rc;
+    HIP_TRY(hipMemsetAsync(err, 0x7F, kg::kOrfErrWords * 8, s));
+    HIP_TRY(hipMemsetAsync(cnt, 0, (kg::kOrfCntWords + 1) * 8, s));
+    HIP_TRY(hipEventRecord(t->ev[kEvStageBegin], s));
+    const kg::OrfGeometry geo = pl.geometry();
+    const int64_t *keys = pl.keys, *d_off = pl.d_off;
+    const uint32_t sc_mask = (uint32_t)prm->start_codons;
+    if ((rc = pl.launch(s, d_seq, sc_mask))) return rc;
     if (n > 0) {
         hipLaunchKernelGGL(kg::orf_region_kernel, dim3(grid_of(n)), dim3(256), 0, s, d_regions, n, d_seq, geo, keys, sc_mask,
                            (int)prm->only_kept, d_out, lens, err, cnt);
@@ -138,6 +192,107 @@ int check_orf_batch(const uint8_t *seq, const int64_t *offsets, int64_t n_seqs, 
     if (n_seqs && offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
     *total = n_seqs ? (uint64_t)offsets[n_seqs] : 0;
     if (*total && !seq) return fail(KG_ERR_ARG, "null sequence bytes");
+    return KG_OK;
+}
+
+// The free candidates of the batch behind the records of `parent` (null: alone).  d_seq, offsets and set as orfs_impl has them.
+int free_impl(kg_table *t, const kg_free_params *prm, const kg_orfset *parent, const uint8_t *d_seq, const int64_t *offsets,
+              uint64_t n_seqs, kg_orfset *set)
+{
+    OrfPlanes pl;
+    Scratch sc(t);
+    hipStream_t s = t->stream;
+    int rc;
+    if ((rc = pl.plan(offsets, n_seqs))) return rc;
+    set->l_max = std::max(parent ? parent->l_max : 0, pl.l_max);
+    const uint64_t n0 = parent ? (uint64_t)parent->count : 0, n_slots = 6 * pl.n_rows;
+    unsigned long long *words = nullptr;           // kg::kOrfFree*
+    uint32_t *slots = nullptr, *slot_first = nullptr;
+    uint64_t *slot_partial = nullptr;
+    if ((rc = pl.alloc_geometry(sc)) || (rc = sc.get(&words, 16)) || (rc = pl.alloc_keys(sc)) ||
+        (rc = sc.get(&slots, std::max<uint64_t>(n_slots, 1))) || (rc = sc.get(&slot_first, std::max<uint64_t>(n_slots, 1))) ||
+        (rc = sc.get(&slot_partial, n_slots / kg::kScanChunk + 2)))
+        return rc;
+    if ((rc = pl.upload(s, offsets))) return rc;
+    HIP_TRY(hipMemsetAsync(words, 0, kg::kOrfFreeWords * 8, s));
+    HIP_TRY(hipEventRecord(t->ev[kEvStageBegin], s));
+    const kg::OrfGeometry geo = pl.geometry();
+    const uint32_t sc_mask = (uint32_t)prm->start_codons, row_grid = (uint32_t)((pl.n_rows + 3) / 4);
+    if ((rc = pl.launch(s, d_seq, sc_mask))) return rc;
+    if (pl.n_rows > 0) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(kg::orf_free_kernel<false>), dim3(row_grid), dim3(256), 0, s, d_seq, pl.total, geo, pl.n_rows, pl.keys,
+                           prm->min_res, sc_mask, slots, (kg_orf *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr);
+        HIP_TRY(hipGetLastError());
+        if ((rc = prefix_sum(t, slots, n_slots, slot_first, slot_partial, (uint64_t *)(words + kg::kOrfFreeCount)))) return rc;
+    }
+    // the first wait: how many candidates there are
+    if ((rc = read_error_words(t, words, kg::kOrfFreeWords, kPinOrfs, {}))) return rc;
+    const uint64_t *h = t->h_pin + kPinOrfs;
+    const uint64_t n_free = h[kg::kOrfFreeCount], n = n0 + n_free;
+    if (n >= (1ull << 31)) return fail(KG_ERR_LIMIT, "2^31 or more candidates in one call");
+    kg_orf *d_out = nullptr;
+    int64_t *d_start = nullptr;
+    uint32_t *lens = nullptr, *excl = nullptr;
+    uint64_t *partial = nullptr;
+    if ((rc = sc.get(&d_out, std::max<uint64_t>(n, 1))) || (rc = sc.get(&d_start, n + 1)) || (rc = sc.get(&lens, std::max<uint64_t>(n, 1))) ||
+        (rc = sc.get(&excl, std::max<uint64_t>(n, 1))) || (rc = sc.get(&partial, n / kg::kScanChunk + 2)))
+        return rc;
+    uint64_t *d_total = (uint64_t *)(words + kg::kOrfFreeResidues);
+    if (n0 > 0) {
+        HIP_TRY(hipMemcpyAsync(d_out, parent->d_orfs, n0 * sizeof(kg_orf), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(kg::orf_lens_kernel, dim3(grid_of(n0)), dim3(256), 0, s, parent->d_prot_start, n0, lens);
+    }
+    if (n_free > 0)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(kg::orf_free_kernel<true>), dim3(row_grid), dim3(256), 0, s, d_seq, pl.total, geo, pl.n_rows, pl.keys,
+                           prm->min_res, sc_mask, slot_first, d_out + n0, lens + n0, words);
+    HIP_TRY(hipGetLastError());
+    if (n > 0 && (rc = prefix_sum(t, lens, n, excl, partial, d_total))) return rc;
+    hipLaunchKernelGGL(kg::orf_prot_start_kernel, dim3(grid_of(n + 1)), dim3(256), 0, s, excl, d_total, n, d_start);
+    HIP_TRY(hipGetLastError());
+    // the second wait: the residue total and the counters
+    if ((rc = read_error_words(t, words, kg::kOrfFreeWords, kPinOrfs, {}))) return rc;
+    const uint64_t n_res = h[kg::kOrfFreeResidues];
+    if (n_res >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more residues in one call");
+    uint8_t *d_res = nullptr;
+    if ((rc = sc.get(&d_res, std::max<uint64_t>(n_res, 1)))) return rc;
+    if (n_res > 0) {
+        hipLaunchKernelGGL(kg::orf_residues_kernel, dim3(grid_of((n_res + kg::kOrfResPerLane - 1) / kg::kOrfResPerLane)), dim3(256), 0, s,
+                           d_out, n, d_start, n_res, d_seq, pl.d_off, d_res);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(t->ev[kEvStageEnd], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (parent) set->st = parent->st;
+    set->st.orfs = (int64_t)n;
+    set->st.complete += (int64_t)h[kg::kOrfFreeComplete];
+    set->st.partial5 += (int64_t)h[kg::kOrfFreePartial5];
+    set->st.residues = (int64_t)n_res;
+    set->st.tiles = (int64_t)pl.n_tiles;
+    HIP_TRY(hipEventElapsedTime(&set->st.ms, t->ev[kEvStageBegin], t->ev[kEvStageEnd]));
+    // the three arrays of the set leave the scratch: everything else goes back to the cache
+    sc.release(d_out); sc.release(d_start); sc.release(d_res);
+    set->d_orfs = d_out;
+    set->d_prot_start = d_start;
+    set->d_res = d_res;
+    set->count = (int64_t)n;
+    set->residues = (int64_t)n_res;
+    set->n_seqs = (int64_t)n_seqs;
+    return KG_OK;
+}
+
+// the batch's bytes where the kernels read them: the caller's device memory, or a copy in the call's scratch
+int batch_on_device(kg_table *t, Scratch &sc, const uint8_t *seq, int seq_on_device, uint64_t total, const uint8_t **d_seq)
+{
+    *d_seq = seq;
+    if (seq_on_device) {
+        HIP_TRY(hipDeviceSynchronize());            // the bytes may have been produced on another stream
+        return KG_OK;
+    }
+    uint8_t *up = nullptr;
+    int rc = sc.get(&up, total ? total : 1);
+    if (rc) return rc;
+    if (total && (rc = upload_batch(t, seq, total, up))) return rc;
+    *d_seq = up;
     return KG_OK;
 }
 
@@ -209,6 +364,59 @@ int kg_orfs_regions(int device, const kg_orf_params *p, const kg_region *regions
     t->cache.release_free();            // (the scratch is back in the cache: it goes to the driver, the set's three arrays stay)
     set->own_tab = true;
     cs.disown();
+    *out = set.release();
+    return KG_OK;
+}
+
+int kg_orfs_free(int device, const kg_free_params *p, const uint8_t *seq, int seq_on_device, const int64_t *offsets, int64_t n_seqs,
+                 kg_orfset **out)
+{
+    if (!out) return fail(KG_ERR_ARG, "null argument");
+    *out = nullptr;
+    int rc = check_free_params(p);
+    if (rc) return rc;
+    uint64_t total = 0;
+    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total))) return rc;
+    CallScope cs(device);               // the call's context: closed on every failure below, kept by the set on success
+    if (cs.rc) return cs.rc;
+    kg_table *t = cs.t;
+    std::unique_ptr<kg_orfset> set(new (std::nothrow) kg_orfset());
+    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
+    set->tab = t;
+    {
+        Scratch sc(t);
+        const uint8_t *d_seq = nullptr;
+        if ((rc = batch_on_device(t, sc, seq, seq_on_device, total, &d_seq))) return rc;
+        if ((rc = free_impl(t, p, nullptr, d_seq, offsets, (uint64_t)n_seqs, set.get()))) return rc;
+    }
+    t->cache.release_free();            // (the scratch is back in the cache: it goes to the driver, the set's three arrays stay)
+    set->own_tab = true;
+    cs.disown();
+    *out = set.release();
+    return KG_OK;
+}
+
+int kg_orfset_add_free(kg_orfset *os, const kg_free_params *p, const uint8_t *seq, int seq_on_device, const int64_t *offsets,
+                       int64_t n_seqs, kg_orfset **out)
+{
+    if (!out) return fail(KG_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!os) return fail(KG_ERR_ARG, "null kg_orfset");
+    int rc = check_free_params(p);
+    if (rc) return rc;
+    uint64_t total = 0;
+    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total))) return rc;
+    if (n_seqs != os->n_seqs) return fail(KG_ERR_ARG, "n_seqs is not the ORF set's");
+    CallScope cs(os->tab, "a kg_scan* is in flight on this ORF set's kg_table");
+    if (cs.rc) return cs.rc;
+    kg_table *t = cs.t;
+    std::unique_ptr<kg_orfset> set(new (std::nothrow) kg_orfset());
+    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
+    set->tab = t;
+    Scratch sc(t);
+    const uint8_t *d_seq = nullptr;
+    if ((rc = batch_on_device(t, sc, seq, seq_on_device, total, &d_seq))) return rc;
+    if ((rc = free_impl(t, p, os, d_seq, offsets, (uint64_t)n_seqs, set.get()))) return rc;
     *out = set.release();
     return KG_OK;
 }

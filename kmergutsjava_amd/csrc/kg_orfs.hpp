@@ -20,6 +20,16 @@
 //                             codons) plus one read of a scanned array -- the record and the protein's length.
 //   4. prefix_sum of the lengths -> prot_start (orf_prot_start_kernel); orf_residues_kernel, divided by output position: a lane
 //      owns kOrfResPerLane consecutive residues and finds its ORF by binary search in prot_start.
+//
+// kg_orfs_free / kg_orfset_add_free (evidence-free candidates, the rule is in the header too) use 1, 2 and 4 as they are and put
+//   3'. orf_free_kernel<false / true>  in the place of 3: one wave per tile row again.  A candidate is owned by its closing stop
+//                             (the run that reaches the contig's end: by lane 0 of the container's last tile in codon order), so
+//                             a lane owns at most two stops of each of the six containers.  u comes from the tile's ballots or one
+//                             scanned key; only a run of min_res codons or more then looks for its start, one walk inside one
+//                             tile plus one scanned key.  The first pass counts per (container, tile) in output order -- on '-'
+//                             the tiles mirrored -- prefix_sum turns the counts into first indices, and the second pass writes
+//                             every record at its final index with in-tile ranks from ballots: no sort, no wait between
+//                             workgroups, and one non-returning add per wave and counter.
 #pragma once
 
 #include "kg_build.hpp"
@@ -37,6 +47,8 @@ enum { kOrfDownFStop = 0, kOrfDownRStop = 1, kOrfDownRStart = 2, kOrfUpFStop = 3
 enum { kOrfErrSeq = 0, kOrfErrStrand = 1, kOrfErrFrame = 2, kOrfErrRange = 3, kOrfErrAnchor = 4, kOrfErrWords = 5 };
 // counter words
 enum { kOrfCntComplete = 0, kOrfCntInterrupted = 1, kOrfCntPartial5 = 2, kOrfCntWords = 3 };
+// the words of orf_free_kernel's host: the candidates, two counters, then the residue total
+enum { kOrfFreeCount = 0, kOrfFreeComplete = 1, kOrfFreePartial5 = 2, kOrfFreeResidues = 3, kOrfFreeWords = 4 };
 
 // codon classes, by b0 * 25 + b1 * 5 + b2 (dna_code values): bit 0 forward stop, bits 1-3 forward start (ATG, GTG, TTG),
 // bit 4 reverse stop, bits 5-7 reverse start (of ATG, GTG, TTG)
@@ -122,13 +134,14 @@ __device__ inline int orf_last2(uint64_t b0, uint64_t b1)
     return x0 > x1 ? x0 : x1;
 }
 
-// One wave per tile row.  keys: kOrfPlanes arrays of geo.n_tiles items.
-__global__ __launch_bounds__(256) void orf_summary_kernel(const uint8_t *__restrict__ seq, uint64_t total, OrfGeometry geo,
-                                                          uint64_t n_rows, uint32_t start_codons, int64_t *__restrict__ keys)
+// the tile row a wave works on: tile t of the nt of contig s
+struct OrfRow {
+    uint64_t s, tb, nt, t;
+    int64_t off, L;
+};
+
+__device__ inline OrfRow orf_row_of(const OrfGeometry &geo, uint64_t row)
 {
-    const int lane = threadIdx.x & 63;
-    const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n_rows) return;
     // the contig of the row: the last s with tile_base[s] <= row
     uint64_t lo = 0, hi = geo.n_seqs;
     while (hi - lo > 1) {
@@ -136,16 +149,39 @@ __global__ __launch_bounds__(256) void orf_summary_kernel(const uint8_t *__restr
         if ((uint64_t)geo.tile_base[mid] <= row) lo = mid;
         else hi = mid;
     }
-    const uint64_t s = lo;
-    const int64_t off = geo.offsets[s], L = geo.offsets[s + 1] - off;
-    const uint64_t tb = (uint64_t)geo.tile_base[s], nt = (uint64_t)geo.tile_base[s + 1] - tb, t = row - tb;
-    const uint64_t m0 = t * kOrfTile + 2 * (uint64_t)lane;                     // the lane's first codon of every phase
+    OrfRow r;
+    r.s = lo;
+    r.off = geo.offsets[lo];
+    r.L = geo.offsets[lo + 1] - r.off;
+    r.tb = (uint64_t)geo.tile_base[lo];
+    r.nt = (uint64_t)geo.tile_base[lo + 1] - r.tb;
+    r.t = row - r.tb;
+    return r;
+}
+
+// the dna_code values of the eight bytes that hold the lane's two codons (2 * lane, 2 * lane + 1 of the tile) of every phase;
+// 4 behind the contig's end
+__device__ inline void orf_row_codes(const uint8_t *__restrict__ seq, uint64_t total, const OrfRow &r, int lane, uint32_t (&code)[8])
+{
+    const uint64_t m0 = r.t * kOrfTile + 2 * (uint64_t)lane;                   // the lane's first codon of every phase
     const uint64_t at = 3 * m0;                                                // its first byte in the contig
     uint64_t w = 0;
-    if ((int64_t)at < L) w = orf_load8(seq, total, (uint64_t)off + at);
-    uint32_t code[8];
+    if ((int64_t)at < r.L) w = orf_load8(seq, total, (uint64_t)r.off + at);
 #pragma unroll
-    for (int k = 0; k < 8; k++) code[k] = ((int64_t)(at + k) < L) ? dna_code((uint32_t)(w >> (8 * k)) & 255u) : 4u;
+    for (int k = 0; k < 8; k++) code[k] = ((int64_t)(at + k) < r.L) ? dna_code((uint32_t)(w >> (8 * k)) & 255u) : 4u;
+}
+
+// One wave per tile row.  keys: kOrfPlanes arrays of geo.n_tiles items.
+__global__ __launch_bounds__(256) void orf_summary_kernel(const uint8_t *__restrict__ seq, uint64_t total, OrfGeometry geo,
+                                                          uint64_t n_rows, uint32_t start_codons, int64_t *__restrict__ keys)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const OrfRow rw = orf_row_of(geo, row);
+    const uint64_t s = rw.s, tb = rw.tb, nt = rw.nt, t = rw.t;
+    uint32_t code[8];
+    orf_row_codes(seq, total, rw, lane, code);
     const uint32_t fstart = (start_codons & 7u) << 1, rstart = (start_codons & 7u) << 5;
 #pragma unroll
     for (int g = 0; g < 3; g++) {
@@ -371,6 +407,155 @@ __global__ __launch_bounds__(256) void orf_region_kernel(const kg_region *__rest
         if (ni) atomicAdd(&cnt[kOrfCntInterrupted], (unsigned long long)ni);
         if (np) atomicAdd(&cnt[kOrfCntPartial5], (unsigned long long)np);
     }
+}
+
+// Rules 2 and 3 of the free candidates for the run between two neighbouring stops of one container, in forward codons m of
+// its phase.  '+': mu < me, mu = -1 without a stop in front, me = n for the run that reaches the contig's end.  '-': mu > me,
+// mu = n and me = -1 in the same places.  -> whether the run gives a candidate; *mb its first codon, *bcls that codon's start bits.
+__device__ inline bool orf_free_run(const OrfSegment &sg, int strand, int32_t me, int32_t mu, int32_t min_res, uint32_t start_codons,
+                                    int32_t *mb, uint32_t *bcls)
+{
+    if ((strand ? mu - me : me - mu) - 1 < min_res) return false;             // the cheap necessary test: most stops end here
+    const int shift = strand ? 5 : 1;
+    const uint32_t want = (start_codons & 7u) << shift;
+    int32_t x = -1;
+    if (want) x = strand ? orf_find_down(sg, want, kOrfDownRStart, me + 1, mu - 1) : orf_find_up(sg, want, kOrfUpFStart, mu + 1, me - 1);
+    const bool first = strand ? mu == sg.n : mu == -1;                        // u == -1
+    if (x < 0 && want && !first) return false;
+    *bcls = x < 0 ? 0u : (kOrfTables.cls[orf_codon_index(sg, x)] & want) >> shift;
+    *mb = x >= 0 ? x : strand ? mu - 1 : mu + 1;
+    return (strand ? *mb - me : me - *mb) >= min_res;
+}
+
+// rule 4 of the free candidates
+__device__ inline kg_orf orf_free_record(int32_t seq, int strand, int32_t f, int64_t L, int32_t n, int32_t me, int32_t mu, int32_t mb,
+                                         uint32_t bcls)
+{
+    const int32_t e = strand ? n - 1 - me : me, b = strand ? n - 1 - mb : mb;   // in j: e == n for the run that reaches the end
+    const bool first = strand ? mu == n : mu == -1;
+    const int32_t last = e < n ? e : n - 1;
+    const int64_t xs = (int64_t)f + 3 * (int64_t)b, xe = (int64_t)f + 3 * (int64_t)last + 2;
+    kg_orf o = {};
+    o.seq = seq;
+    o.strand = strand;
+    o.frame = f;
+    o.left = (int32_t)(strand ? L - 1 - xe : xs);
+    o.right = (int32_t)(strand ? L - 1 - xs : xe);
+    o.n_res = (e < n ? e : n) - b;
+    o.start_codon = bcls & 1u ? 1 : bcls & 2u ? 2 : bcls & 4u ? 3 : 0;
+    o.first_inner = -1;
+    o.flags = KG_ORF_FREE | (e < n ? KG_ORF_HAS_STOP : 0u) | (first ? KG_ORF_PARTIAL5 : 0u);
+    o.fI = -1;
+    o.score = 0;
+    o.kept = 1;
+    return o;
+}
+
+// One wave per tile row, as orf_summary_kernel; keys: the scanned arrays.  slots: 6 * n_rows words, one per (container, tile) in
+// output order: contig, strand, frame, and the tiles in the strand's codon order.  kEmit = false writes every slot's candidates
+// there; kEmit = true reads the slot's first index from it and writes out[] and lens[] (= n_res) and adds to cnt[kOrfFree*].
+template <bool kEmit>
+__global__ __launch_bounds__(256) void orf_free_kernel(const uint8_t *__restrict__ seq, uint64_t total, OrfGeometry geo, uint64_t n_rows,
+                                                       const int64_t *__restrict__ keys, int32_t min_res, uint32_t start_codons,
+                                                       uint32_t *__restrict__ slots, kg_orf *__restrict__ out,
+                                                       uint32_t *__restrict__ lens, unsigned long long *cnt)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const OrfRow rw = orf_row_of(geo, row);
+    uint32_t code[8];
+    orf_row_codes(seq, total, rw, lane, code);
+    const uint64_t below = (1ull << lane) - 1, above = lane == 63 ? 0ull : ~0ull << (lane + 1), self = 1ull << lane;
+    const int32_t base = (int32_t)(rw.t * kOrfTile);
+    uint32_t complete = 0, partial5 = 0;
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+        uint32_t c[2];
+#pragma unroll
+        for (int k = 0; k < 2; k++) c[k] = kOrfTables.cls[code[g + 3 * k] * 25 + code[g + 3 * k + 1] * 5 + code[g + 3 * k + 2]];
+        const uint64_t fs0 = __ballot(c[0] & kOrfFStop), fs1 = __ballot(c[1] & kOrfFStop);
+        const uint64_t rs0 = __ballot(c[0] & kOrfRStop), rs1 = __ballot(c[1] & kOrfRStop);
+        OrfSegment sg;
+        sg.bytes = seq + rw.off + g;
+        sg.keys = keys;
+        sg.n_tiles = geo.n_tiles;
+        sg.seg = 3 * rw.s + g;
+        sg.mseg = 3 * geo.n_seqs - 1 - sg.seg;
+        sg.gt0 = 3 * rw.tb + (uint64_t)g * rw.nt;
+        sg.n = rw.L >= g ? (int32_t)((rw.L - g) / 3) : 0;
+        const int32_t n = sg.n;
+        const uint64_t gt = sg.gt0 + rw.t;
+        for (int strand = 0; strand < 2; strand++) {
+            const uint64_t s0 = strand ? rs0 : fs0, s1 = strand ? rs1 : fs1;
+            // the neighbouring stop outside the tile: '+' the last one below it (-1: none), '-' the first one above it (n: none)
+            int32_t outer = strand ? n : -1;
+            if (!strand && rw.t > 0) {
+                const int64_t k = keys[(uint64_t)kOrfDownFStop * geo.n_tiles + gt - 1];
+                if (orf_key_seg(k) == sg.seg && orf_key_low(k) != 0) outer = (int32_t)orf_key_low(k) - 1;
+            } else if (strand && rw.t + 1 < rw.nt) {
+                const int64_t k = keys[(uint64_t)kOrfUpRStop * geo.n_tiles + (geo.n_tiles - 1 - (gt + 1))];
+                if (orf_key_seg(k) == sg.mseg && orf_key_low(k) != 0) outer = (int32_t)(0x7FFFFFFFu - orf_key_low(k));
+            }
+            // [0], [1]: the lane's two codons as closing stops; [2]: lane 0 of the owning tile for the run that reaches the end
+            bool has[3] = {false, false, false};
+            int32_t me[3], mu[3], mb[3] = {0, 0, 0};
+            uint32_t bc[3] = {0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                me[k] = base + 2 * lane + k;
+                const int x = strand ? orf_first2(s0 & above, s1 & (k ? above : above | self))
+                                     : orf_last2(s0 & (k ? below | self : below), s1 & below);
+                mu[k] = x < 0 ? outer : base + x;
+                if (c[k] & (strand ? kOrfRStop : kOrfFStop)) has[k] = orf_free_run(sg, strand, me[k], mu[k], min_res, start_codons, &mb[k], &bc[k]);
+            }
+            {
+                me[2] = strand ? -1 : n;
+                const int x = strand ? orf_first2(s0, s1) : orf_last2(s0, s1);
+                mu[2] = x < 0 ? outer : base + x;
+                const bool owner = strand ? rw.t == 0 : rw.t + 1 == rw.nt;
+                if (owner && lane == 0 && n > 0) has[2] = orf_free_run(sg, strand, me[2], mu[2], min_res, start_codons, &mb[2], &bc[2]);
+            }
+            const uint64_t b0 = __ballot(has[0]), b1 = __ballot(has[1]), b2 = __ballot(has[2]);
+            const int32_t f = strand ? (int32_t)((rw.L - g) % 3) : g;
+            const uint64_t slot = 6 * rw.tb + (uint64_t)(3 * strand + f) * rw.nt + (strand ? rw.nt - 1 - rw.t : rw.t);
+            if (!kEmit) {
+                if (lane == 0) slots[slot] = (uint32_t)(__popcll(b0) + __popcll(b1) + __popcll(b2));
+                continue;
+            }
+            // the ranks inside the slot, in the strand's codon order; the run that reaches the end comes last
+            const uint64_t before = strand ? above : below;
+            const uint32_t first = slots[slot], r = (uint32_t)(__popcll(b0 & before) + __popcll(b1 & before));
+            const uint32_t rank[3] = {r + (strand && has[1] ? 1u : 0u), r + (!strand && has[0] ? 1u : 0u),
+                                      (uint32_t)(__popcll(b0) + __popcll(b1))};
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                if (!has[k]) continue;
+                const kg_orf o = orf_free_record((int32_t)rw.s, strand, f, rw.L, n, me[k], mu[k], mb[k], bc[k]);
+                out[first + rank[k]] = o;
+                lens[first + rank[k]] = (uint32_t)o.n_res;
+                complete += (o.flags & KG_ORF_HAS_STOP) && o.start_codon != 0 ? 1u : 0u;
+                partial5 += o.flags & KG_ORF_PARTIAL5 ? 1u : 0u;
+            }
+        }
+    }
+    if (kEmit) {
+        for (int off = 32; off > 0; off >>= 1) {
+            complete += __shfl_down(complete, off);
+            partial5 += __shfl_down(partial5, off);
+        }
+        if (lane == 0) {
+            if (complete) atomicAdd(&cnt[kOrfFreeComplete], (unsigned long long)complete);
+            if (partial5) atomicAdd(&cnt[kOrfFreePartial5], (unsigned long long)partial5);
+        }
+    }
+}
+
+// lens[i] = the bytes ORF i takes behind prot_start (kg_orfset_add_free: the given set's lengths, zeros of only_kept included)
+__global__ __launch_bounds__(256) void orf_lens_kernel(const int64_t *__restrict__ prot_start, uint64_t n, uint32_t *__restrict__ lens)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) lens[i] = (uint32_t)(prot_start[i + 1] - prot_start[i]);
 }
 
 // prot_start[i] = excl[i] for i < n, prot_start[n] = *total

@@ -221,13 +221,15 @@ class ScanResult:
         return out, start
 
     def orfs(self, seq, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, start_codons: int = 7,
-             only_kept: bool = True, device_ptr: Optional[int] = None):
+             only_kept: bool = True, device_ptr: Optional[int] = None, free_min_res: Optional[int] = None):
         """regions() and then the open reading frame around every region with its translated protein, on the GPU, without a
         host trip between the two (include/kmerguts_hip.h kg_regionset_orfs states the rule).  seq / offsets: what the scan was
         given; device_ptr: the address of the bytes in HBM instead of seq.
         -> (regions, region_start, orfs, prot_start, residues): orfs a numpy array of _native.ORF_DTYPE, index-aligned with
         regions; the protein of ORF i is residues[prot_start[i] : prot_start[i + 1]] (uint8).  The two calls' counts and device
-        times are left in `region_stats` and `orf_stats`."""
+        times are left in `region_stats` and `orf_stats`.
+        free_min_res: when given, the evidence-free candidates of at least that many residues (kg_orfset_add_free, flag
+        _native.ORF_FREE) follow the regions' ORFs in orfs, prot_start and residues; `orf_stats` is then the whole set's."""
         lib = self._need()
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
         if off.shape != (self.stats["n_seqs"] + 1,):
@@ -244,6 +246,8 @@ class ScanResult:
             op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
             oh = C.c_void_p()
             N.check(lib.kg_regionset_orfs(h, C.byref(op), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(oh)))
+            if free_min_res is not None:
+                oh = _add_free(oh, free_min_res, start_codons, ptr, on_device, off)
             orfs, prot_start, residues, self.orf_stats = _take_orfset(oh, False)
         except BaseException:
             lib.kg_regionset_free(h)
@@ -253,14 +257,18 @@ class ScanResult:
 
     def select(self, offsets, seq=None, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, orfs: bool = False,
                start_codons: int = 7, only_kept: bool = True, device_ptr: Optional[int] = None, max_overlap: int = 60,
-               max_overlap_pct: int = 50):
+               max_overlap_pct: int = 50, free_min_res: Optional[int] = None):
         """regions() -- with orfs=True, orfs() -- and then the non-overlapping selection among the kept records, on the GPU and
         without a host trip or a second scan in between (include/kmerguts_hip.h kg_regionset_select states the rule).  The
         candidates are the regions' extents, or with orfs=True the ORFs' extents.
         -> (regions, region_start, selection), or with orfs=True (regions, region_start, orfs, prot_start, residues, selection):
         selection a numpy array of _native.SELECTION_DTYPE, index-aligned with the regions (and the ORFs).  The calls' counts and
-        device times are left in `region_stats`, `orf_stats` and `select_stats`."""
+        device times are left in `region_stats`, `orf_stats` and `select_stats`.
+        free_min_res (with orfs=True): the evidence-free candidates are appended on the device before the selection, as orfs()
+        appends them; orfs, prot_start, residues and selection then hold them behind the regions' records."""
         lib = self._need()
+        if free_min_res is not None and not orfs:
+            raise ValueError("free_min_res needs orfs=True: the free candidates are ORFs")
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
         if off.shape != (self.stats["n_seqs"] + 1,):
             raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
@@ -277,6 +285,8 @@ class ScanResult:
                     ptr, on_device = (keep.ctypes.data if keep.size else None), 0
                 op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
                 N.check(lib.kg_regionset_orfs(h, C.byref(op), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(oh)))
+                if free_min_res is not None:
+                    oh = _add_free(oh, free_min_res, start_codons, ptr, on_device, off)
                 N.check(lib.kg_orfset_select(oh, C.byref(sp), C.byref(sh)))
             else:
                 N.check(lib.kg_regionset_select(h, C.byref(sp), C.byref(sh)))
@@ -647,6 +657,39 @@ def _take_orfset(h, device_out: bool):
         return out, start, res, st.as_dict()
     finally:
         lib.kg_orfset_free(h)
+
+
+def _add_free(oh, min_res: int, start_codons: int, ptr, on_device: int, off):
+    """kg_orfset_add_free on the ORF set oh, which is freed: -> the new set's handle (it lives in the same context)."""
+    lib = N.load()
+    fp = N.KgFreeParams(int(min_res), int(start_codons), 0)
+    both = C.c_void_p()
+    try:
+        N.check(lib.kg_orfset_add_free(oh, C.byref(fp), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(both)))
+    finally:
+        lib.kg_orfset_free(oh)          # (the new set holds copies: the given one is not needed any more)
+        oh.value = None
+    return both
+
+
+def free_orfs(seq, offsets, min_res: int = 100, start_codons: int = 7, device: int = 0, device_out: bool = False,
+              stats: Optional[dict] = None):
+    """The evidence-free open reading frames of a batch and their proteins, on the GPU and without a table (kg_orfs_free;
+    include/kmerguts_hip.h states the rule): every stop-free run of the six frames that gives at least min_res residues from
+    its first start codon.  seq the batch's bytes, offsets int64[n_seqs + 1].  -> (orfs, prot_start, residues) as orf_regions;
+    `stats`, when given, receives the call's counts and device time."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_seqs + 1]")
+    arr = _seq_bytes(seq, off)
+    p = N.KgFreeParams(int(min_res), int(start_codons), 0)
+    h = C.c_void_p()
+    N.check(N.load().kg_orfs_free(device, C.byref(p), arr.ctypes.data if arr.size else None, 0, off.ctypes.data, off.size - 1,
+                                  C.byref(h)))
+    out, start, res, st = _take_orfset(h, device_out)
+    if stats is not None:
+        stats.update(st)
+    return out, start, res
 
 
 def orf_regions(regs, seq, offsets, start_codons: int = 7, only_kept: bool = True, device: int = 0, device_out: bool = False,
