@@ -286,6 +286,76 @@ int kg_sigset_copy(const kg_sigset *s, int64_t first, int64_t count, kg_signatur
 int kg_sigset_stats(const kg_sigset *s, kg_derive_stats *out);
 void kg_sigset_free(kg_sigset *s);
 
+/* ---- protein families: proteins -> connected components of shared 8-mers (kernels: kg_cluster.hpp) ----
+ *
+ * The reference only reads signatures; this rule is the project's own.  It is the step between the proteins of evidence-free
+ * ORFs and kg_signatures_derive: it says which hypothetical proteins of several genomes are the same protein.  Integers only.
+ * Input: as for kg_signatures_derive, without fn and otu: seq, offsets[n_prot + 1] (host, non-decreasing),
+ * len_p = offsets[p+1] - offsets[p].
+ *   Windows: exactly the derive windows: toAminoAcidOff codes, positions i in [0, len_p - 8), windows with a code >= 20 skipped;
+ *   the device encode is the scan's own (encode_init / encode_block<true>).
+ *   P(v) is the set of distinct proteins that have a window equal to v.  d_p is the number of distinct k-mers of protein p.
+ *   Centre.  For a k-mer v with |P(v)| >= 2, c(v) is the member of P(v) with the largest len_p.  On a tie it is the smallest
+ *   index.  Every other member m of P(v) gives one link (m, c(v)).  This is Linclust's star: the work is linear in the
+ *   (k-mer, protein) pairs whatever the size of P(v).
+ *   Shared count.  s(m, c) is the number of distinct k-mers v with m in P(v), c(v) = c and m != c.
+ *   Edge.  {m, c} is an edge iff both hold, computed in int64: s(m, c) >= min_shared; 100 * s(m, c) >= min_cover_pct * d_m.
+ *   Family.  A family is a connected component of the edge graph.  A protein without an edge is a family of one; proteins
+ *   with d_p = 0 are included in that.  A family's root is its smallest member index.  Families are numbered densely, 0..,
+ *   in ascending root.
+ *   Output: one 16-byte kg_family per protein, in protein order: family; root; best = the centre c with the largest s(p, c)
+ *   among p's links that pass both tests, on a tie the smaller c, -1 when none passes; shared = that s, else 0.
+ * Parameters kg_cluster_params { min_shared, min_cover_pct, reserved }: min_shared >= 1 (default 5), 0 <= min_cover_pct <= 100
+ * (default 20), reserved == 0; anything else is KG_ERR_ARG.  The defaults are this project's choice: with exact 8-mers, a fifth
+ * of the k-mers shared means roughly 80 % identity, the identity at which signatures of one member still hit another.
+ * Dependence on order.  The partition depends on protein order only through ties of len_p in the centre choice.  The numbering
+ * (family, root, best) depends on order by definition.  Nothing depends on launch geometry or scheduling.
+ * Known weakness: single linkage chains, and a repeat or a domain shared by two families can join them.  That is stated, not
+ * repaired; min_cover_pct is the lever.
+ * One pass.  A call whose valid windows do not fit the device returns KG_ERR_LIMIT and says so.  max_windows = 0: the capacity
+ * is sized from free device memory as the derive call does (about 160 bytes per valid window, at most 2^32 - 2^22 windows); any
+ * other value caps it.
+ * Limits (KG_ERR_LIMIT): n_prot < 2^29, len_p < 2^31, fewer than 2^31 window blocks of 64 windows.  KG_ERR_ARG: decreasing
+ * offsets (the message names the first offending protein), bad parameters (the message names the first), max_windows < 0, null
+ * pointers.  KG_ERR_NOMEM.  KG_TEST_FAIL_ALLOC applies to the call's device allocations; everything but the result array goes
+ * back to the driver before the call returns.  Zero proteins are valid.
+ * kg_proteins_cluster reads a host sequence, uploaded through pinned pieces; kg_proteins_cluster_device a device sequence
+ * (complete before the call: the device is synchronised once); offsets is a host array in both. */
+typedef struct kg_cluster_params { int32_t min_shared; int32_t min_cover_pct; int32_t reserved; } kg_cluster_params;
+typedef struct kg_family {       /* 16 B */
+    int32_t family;        /* dense number, in ascending root                           */
+    int32_t root;          /* the family's smallest member index                        */
+    int32_t best;          /* the centre of the protein's strongest edge, -1 when none  */
+    int32_t shared;        /* s(p, best), else 0                                        */
+} kg_family;
+typedef struct kg_cluster_stats {
+    int64_t proteins;
+    int64_t valid_windows;
+    int64_t pairs;         /* distinct (k-mer, protein) pairs                           */
+    int64_t kmers;         /* distinct k-mers                                           */
+    int64_t links;         /* distinct (m, c)                                           */
+    int64_t edges;         /* links that pass both tests                                */
+    int64_t families;
+    int64_t families_multi;/* families of two or more proteins                          */
+    int64_t largest;       /* members of the largest family                             */
+    int32_t rounds;        /* hook-and-jump rounds until nothing changed                */
+    float   ms_encode;     /* the histogram + the encode / emit kernel                  */
+    float   ms_sort;       /* the window sort                                           */
+    float   ms_link;       /* collapse, d_p, centres, link emit and sort, the two tests */
+    float   ms_components; /* the rounds, the compress, the numbering                   */
+    float   ms_total;      /* the call, after the upload of the sequence, to its last kernel */
+} kg_cluster_stats;
+typedef struct kg_familyset kg_familyset;
+int kg_proteins_cluster(int device, const kg_cluster_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
+                        int64_t max_windows, kg_familyset **out);
+int kg_proteins_cluster_device(int device, const kg_cluster_params *p, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
+                               int64_t max_windows, kg_familyset **out);
+int64_t kg_familyset_count(const kg_familyset *s);
+/* records [first, first + count) into dst (host or device memory) */
+int kg_familyset_copy(const kg_familyset *s, int64_t first, int64_t count, kg_family *dst);
+int kg_familyset_stats(const kg_familyset *s, kg_cluster_stats *out);
+void kg_familyset_free(kg_familyset *s);
+
 /* ---- assigning functions: the CALL records of an -a scan -> one function per protein (kernels: kg_assign.hpp) ----
  *
  * The reference stops at the CALL lines (KGJ:398-404, 526-536); this rule is the project's own.

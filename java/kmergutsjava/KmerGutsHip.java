@@ -203,6 +203,33 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_cluster_params (kg_proteins_cluster*); this project's defaults: 5, 20 and 0. */
+    class KgClusterParams extends Structure {
+        public int min_shared, min_cover_pct, reserved;
+        public KgClusterParams() {
+            setFieldOrder(new String[] {"min_shared", "min_cover_pct", "reserved"});
+        }
+    }
+
+    /** struct kg_family (16 B): the family's dense number and root, the centre of the protein's strongest edge or -1, its shared k-mers. */
+    class KgFamily extends Structure {
+        public int family, root, best, shared;
+        public KgFamily() {
+            setFieldOrder(new String[] {"family", "root", "best", "shared"});
+        }
+    }
+
+    /** struct kg_cluster_stats. */
+    class KgClusterStats extends Structure {
+        public long proteins, valid_windows, pairs, kmers, links, edges, families, families_multi, largest;
+        public int rounds;
+        public float ms_encode, ms_sort, ms_link, ms_components, ms_total;
+        public KgClusterStats() {
+            setFieldOrder(new String[] {"proteins", "valid_windows", "pairs", "kmers", "links", "edges", "families", "families_multi",
+                    "largest", "rounds", "ms_encode", "ms_sort", "ms_link", "ms_components", "ms_total"});
+        }
+    }
+
     // replaces readKmerTableHeader + the table stream of lookup (KmerGutsJava.java:924-942, 944-1034)
     int kg_table_open(String path, int device, PointerByReference out);
     int kg_table_from_memory(Pointer image, long nbytes, int device, PointerByReference out);
@@ -221,6 +248,15 @@ public interface KmerGutsHip extends Library {
     int kg_sigset_copy(Pointer set, long first, long count, Pointer dst);
     int kg_sigset_stats(Pointer set, KgDeriveStats out);
     void kg_sigset_free(Pointer set);
+    /** proteins -> families by shared 8-mers (connected components): maxWindows = 0 sizes the one pass from free device memory */
+    int kg_proteins_cluster(int device, KgClusterParams params, byte[] seq, long[] offsets, long nProt, long maxWindows,
+                            PointerByReference out);
+    int kg_proteins_cluster_device(int device, KgClusterParams params, Pointer dSeq, long[] offsets, long nProt, long maxWindows,
+                                   PointerByReference out);
+    long kg_familyset_count(Pointer set);
+    int kg_familyset_copy(Pointer set, long first, long count, Pointer dst);   // kg_family[count], 16 B each, protein order
+    int kg_familyset_stats(Pointer set, KgClusterStats out);
+    void kg_familyset_free(Pointer set);
     Pointer kg_table_device_entries(Pointer table);
     long kg_table_records(Pointer table);
     int kg_table_info(Pointer table, long[] numSigs, long[] entrySize, long[] version, long[] occupied);

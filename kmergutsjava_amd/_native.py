@@ -34,6 +34,8 @@ EXPORTS = (
     "kg_result_device_container_hit_start", "kg_result_device_container_call_start", "kg_result_free", "kg_restore_hits_device",
     "kg_signatures_derive", "kg_signatures_derive_device", "kg_sigset_count", "kg_sigset_device", "kg_sigset_copy",
     "kg_sigset_stats", "kg_sigset_free", "kg_result_assign", "kg_assign_calls",
+    "kg_proteins_cluster", "kg_proteins_cluster_device", "kg_familyset_count", "kg_familyset_copy", "kg_familyset_stats",
+    "kg_familyset_free",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
@@ -81,6 +83,9 @@ SELECTION_DTYPE = np.dtype([("state", "<i4"), ("by", "<i4")])
 assert INTERVAL_DTYPE.itemsize == 20 and SELECTION_DTYPE.itemsize == 8
 SEL_NOT_ELIGIBLE, SEL_SELECTED, SEL_OVERLAPPED = 0, 1, 2
 SELECT_PAIRS_PER_LANE = 8   # kg_select.hpp kSelectPairsPerLane: the pair slots of one lane (tests aim at its edges)
+# struct kg_family (kg_proteins_cluster*): one protein's family
+FAMILY_DTYPE = np.dtype([("family", "<i4"), ("root", "<i4"), ("best", "<i4"), ("shared", "<i4")])
+assert FAMILY_DTYPE.itemsize == 16
 assert HIT_DTYPE.itemsize == 24 and CALL_DTYPE.itemsize == 24 and OTU_DTYPE.itemsize == 44
 
 
@@ -180,6 +185,22 @@ class KgSelectStats(C.Structure):
     """struct kg_select_stats."""
     _fields_ = [("candidates", C.c_int64), ("eligible", C.c_int64), ("selected", C.c_int64), ("overlapped", C.c_int64),
                 ("pairs", C.c_int64), ("conflicts", C.c_int64), ("rounds", C.c_int32), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class KgClusterParams(C.Structure):
+    """struct kg_cluster_params (kg_proteins_cluster*)."""
+    _fields_ = [("min_shared", C.c_int32), ("min_cover_pct", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgClusterStats(C.Structure):
+    """struct kg_cluster_stats."""
+    _fields_ = [("proteins", C.c_int64), ("valid_windows", C.c_int64), ("pairs", C.c_int64), ("kmers", C.c_int64),
+                ("links", C.c_int64), ("edges", C.c_int64), ("families", C.c_int64), ("families_multi", C.c_int64),
+                ("largest", C.c_int64), ("rounds", C.c_int32), ("ms_encode", C.c_float), ("ms_sort", C.c_float),
+                ("ms_link", C.c_float), ("ms_components", C.c_float), ("ms_total", C.c_float)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -297,6 +318,14 @@ def load() -> C.CDLL:
     lib.kg_selectset_stats.argtypes = [vp, C.POINTER(KgSelectStats)]
     lib.kg_selectset_free.argtypes = [vp]
     lib.kg_selectset_free.restype = None
+    for name in ("kg_proteins_cluster", "kg_proteins_cluster_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), vp, vp, C.c_int64, C.c_int64, C.POINTER(vp)]
+    lib.kg_familyset_count.argtypes = [vp]
+    lib.kg_familyset_count.restype = C.c_int64
+    lib.kg_familyset_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.kg_familyset_stats.argtypes = [vp, C.POINTER(KgClusterStats)]
+    lib.kg_familyset_free.argtypes = [vp]
+    lib.kg_familyset_free.restype = None
     lib.kg_last_error.restype = C.c_char_p
     lib.kg_version.restype = C.c_char_p
     for name in EXPORTS:

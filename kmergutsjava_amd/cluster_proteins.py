@@ -1,0 +1,123 @@
+"""Cluster proteins into families by shared 8-mers on the GPU (kg_proteins_cluster), and name the families: the step between
+`call_regions --free-orfs --faa` and `make_signatures -A`.
+
+    python -m kmergutsjava_amd.cluster_proteins -p proteins.faa[.gz] [-p more.faa ...] -o families.tsv [--min-shared 5]
+                                                [--min-cover 20] [--min-size 2] [--all] [-A annotations.tsv] [--known known.tsv]
+
+The proteins of all -p files form one batch, in the order given (FASTA as make_signatures reads it); a protein id that occurs
+twice, in one file or across files, is an error.  include/kmerguts_hip.h states the rule: every protein of a k-mer is linked to
+the k-mer's longest protein, a link is an edge when the two share at least --min-shared distinct 8-mers and at least
+--min-cover percent of the member's distinct 8-mers, a family is a connected component.  The defaults 5 and 20 are this
+project's choice (a fifth of the exact 8-mers shared is roughly 80 % identity).  Single linkage chains, and a repeat or a
+domain can join two families: --min-cover is the lever.
+
+-o lines: `protein_id<TAB>family_<root id><TAB>size<TAB>root id<TAB>best id or -<TAB>shared`, in FASTA order; only the proteins
+of families of at least --min-size (default 2) are written, every protein with --all.
+-A writes make_signatures' annotation format, `protein_id<TAB>function`: first the lines of --known, copied unchanged, then for
+each protein absent from --known and in a family of at least --min-size one line `id<TAB>hypothetical protein family_<root id>`.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+from typing import Optional
+
+import numpy as np
+
+from .make_signatures import InputError, _read, parse_annotations, parse_fasta
+
+FAMILY_PREFIX = b"family_"
+FUNCTION_PREFIX = b"hypothetical protein "
+
+
+def read_proteins(paths):
+    """-> (ids, sequences) of all files in order.  Raises InputError naming an id that occurs twice."""
+    ids, seqs, where = [], [], {}
+    for path in paths:
+        i, s = parse_fasta(_read(path), path)
+        for pid in i:
+            if pid in where:
+                raise InputError("%s: duplicate protein id %s (first in %s)" % (path, pid.decode("latin-1"), where[pid]))
+            where[pid] = path
+        ids += i
+        seqs += s
+    return ids, seqs
+
+
+def family_sizes(rec) -> np.ndarray:
+    """The size of every protein's family."""
+    return np.bincount(rec["root"], minlength=len(rec))[rec["root"]] if len(rec) else np.zeros(0, dtype=np.int64)
+
+
+def format_families(ids, rec, min_size: int = 2, write_all: bool = False) -> bytes:
+    size = family_sizes(rec)
+    out = []
+    for k, pid in enumerate(ids):
+        if not write_all and size[k] < min_size:
+            continue
+        best = int(rec["best"][k])
+        out.append(b"%s\t%s%s\t%d\t%s\t%s\t%d\n" % (pid, FAMILY_PREFIX, ids[int(rec["root"][k])], int(size[k]), ids[int(rec["root"][k])],
+                                                    ids[best] if best >= 0 else b"-", int(rec["shared"][k])))
+    return b"".join(out)
+
+
+def format_annotations(ids, rec, known: bytes = b"", min_size: int = 2, known_name: str = "known") -> bytes:
+    """The --known lines unchanged, then one line per protein absent from them whose family has at least min_size members."""
+    have = parse_annotations(known, known_name)
+    size = family_sizes(rec)
+    out = [known if not known or known.endswith(b"\n") else known + b"\n"]
+    for k, pid in enumerate(ids):
+        if pid not in have and size[k] >= min_size:
+            out.append(b"%s\t%s%s%s\n" % (pid, FUNCTION_PREFIX, FAMILY_PREFIX, ids[int(rec["root"][k])]))
+    return b"".join(out)
+
+
+def cluster_proteins(proteins, out: str, min_shared: int = 5, min_cover: int = 20, min_size: int = 2, write_all: bool = False,
+                     annotations: Optional[str] = None, known: Optional[str] = None, device: int = 0, cluster=None) -> str:
+    """Write the files; returns the summary line.  `cluster` replaces hotpath.cluster_proteins (tests)."""
+    if min_size < 1:
+        raise ValueError("--min-size must be >= 1")
+    if known is not None and annotations is None:
+        raise ValueError("--known needs -A")
+    ids, seqs = read_proteins(proteins)
+    offsets = np.zeros(len(seqs) + 1, dtype=np.int64)
+    if seqs:
+        offsets[1:] = np.cumsum([len(s) for s in seqs])
+    if cluster is None:
+        from . import hotpath
+        cluster = hotpath.cluster_proteins
+    rec, st = cluster(b"".join(seqs), offsets, min_shared=min_shared, min_cover_pct=min_cover, device=device)
+    with open(out, "wb") as f:
+        f.write(format_families(ids, rec, min_size, write_all))
+    if annotations is not None:
+        text = format_annotations(ids, rec, _read(known) if known is not None else b"", min_size, known or "known")
+        with open(annotations, "wb") as f:
+            f.write(text)
+    return "Proteins: %d, families: %d, multi: %d, largest: %d, edges: %d, rounds: %d, ms: %.3f" % (
+        st["proteins"], st["families"], st["families_multi"], st["largest"], st["edges"], st["rounds"], st.get("ms_total", 0.0))
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m kmergutsjava_amd.cluster_proteins",
+                                 description="Cluster proteins into families by shared 8-mers on the GPU.")
+    ap.add_argument("-p", required=True, action="append", metavar="PROTEINS", help="protein FASTA (.gz allowed); may be given several times")
+    ap.add_argument("-o", required=True, metavar="FAMILIES", help="families TSV to write")
+    ap.add_argument("--min-shared", type=int, default=5, help="distinct 8-mers an edge shares at least (default 5, this project's choice)")
+    ap.add_argument("--min-cover", type=int, default=20, help="... and percent of the member's distinct 8-mers (default 20, this project's choice)")
+    ap.add_argument("--min-size", type=int, default=2, help="families of fewer proteins are not written (default 2)")
+    ap.add_argument("--all", action="store_true", help="write every protein to -o, whatever its family's size")
+    ap.add_argument("-A", default=None, metavar="ANNOTATIONS", help="also write protein_id<TAB>function lines for make_signatures -A")
+    ap.add_argument("--known", default=None, metavar="KNOWN", help="with -A: annotations to copy unchanged; their proteins get no family line")
+    a = ap.parse_args(argv)
+    from . import _native as N
+    try:
+        line = cluster_proteins(a.p, a.o, a.min_shared, a.min_cover, a.min_size, a.all, a.A, a.known)
+    except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
+        print("Error: %s" % e, file=sys.stderr)
+        return 1
+    print(line, file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

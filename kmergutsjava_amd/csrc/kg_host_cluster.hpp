@@ -1,0 +1,314 @@
+// kg_host_cluster.hpp -- kg_proteins_cluster / kg_proteins_cluster_device: proteins -> families by shared 8-mers (kernels:
+// kg_cluster.hpp; the window encode, the sort and the collapse are the derive call's, kg_derive.hpp).
+// Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_derive.hpp (it uses the derive call's block
+// counts, its histogram and its bytes-per-window figure).
+#pragma once
+
+struct kg_familyset {
+    int device = 0;
+    uint8_t *d_fam = nullptr;           // count * 16 bytes (hipMalloc, owned)
+    int64_t count = 0;
+    kg_cluster_stats st = {};
+};
+
+static_assert(sizeof(kg_family) == 16 && sizeof(kg_cluster_params) == 12, "record layouts of include/kmerguts_hip.h");
+
+namespace {
+
+int cluster_impl(kg_table *t, const kg_cluster_params *prm, const uint8_t *h_seq, const uint8_t *d_seq_in, const int64_t *offsets,
+                 int64_t n_prot, int64_t max_windows, kg_familyset *set)
+{
+    kg_cluster_stats &st = set->st;
+    std::vector<uint32_t> ibase;
+    uint64_t nblocks = 0, windows = 0;
+    int rc;
+    if ((rc = derive_block_bases(offsets, n_prot, ibase, &nblocks, &windows))) return rc;
+    st.proteins = n_prot;
+    const uint32_t b = bits_for((uint64_t)n_prot), np = (uint32_t)n_prot;
+    hipStream_t s = t->stream;
+
+    Scratch sc(t);
+    Events<8> ev;
+    if ((rc = ev.create())) return rc;
+    const uint8_t *d_seq = d_seq_in;
+    const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
+    if (h_seq && seq_bytes) {
+        uint8_t *d = nullptr;
+        if ((rc = sc.get(&d, seq_bytes))) return rc;
+        if ((rc = upload_pinned(t, h_seq, seq_bytes, d))) return rc;
+        d_seq = d;
+    }
+    HIP_TRY(hipEventRecord(ev[0], s));
+    unsigned long long *words = nullptr;
+    uint64_t *d_tot = nullptr;
+    if ((rc = sc.get(&words, kg::kClusterWords)) || (rc = sc.get(&d_tot, 4))) return rc;
+    HIP_TRY(hipMemsetAsync(words, 0, kg::kClusterWords * 8, s));
+    // ---- the result array: with the call's scratch until the call has succeeded ----
+    uint8_t *d_out = nullptr;
+    if ((rc = dalloc_detached(t, &d_out, std::max<uint64_t>((uint64_t)n_prot * 16, 16)))) return rc;
+    struct OutGuard {                   // (detached: the cache does not give it back on a failure)
+        uint8_t *p;
+        ~OutGuard() { if (p) (void)hipFree(p); }
+    } guard{d_out};
+    if (n_prot == 0) {
+        HIP_TRY(hipEventRecord(ev[5], s));
+        HIP_TRY(hipStreamSynchronize(s));
+        st.ms_total = ev.ms(0, 5);
+        set->d_fam = d_out; guard.p = nullptr;
+        return KG_OK;
+    }
+
+    // ---- per-protein arrays, the window blocks ----
+    Deriver dv{t, sc, d_seq};
+    dv.ev[0] = ev[6]; dv.ev[1] = ev[7];
+    dv.n_blocks = (uint32_t)nblocks;
+    int64_t *d_off = nullptr;
+    uint32_t *d_ibase = nullptr, *rank_of = nullptr, *parent = nullptr, *d_cnt = nullptr, *size = nullptr, *root = nullptr, *rflag = nullptr,
+             *fx = nullptr;
+    unsigned long long *best = nullptr;
+    uint64_t *fpartial = nullptr;
+    if ((rc = sc.get(&dv.d_bins, kg::kDeriveBins)) || (rc = sc.get(&d_off, (size_t)n_prot + 1)) || (rc = sc.get(&d_ibase, (size_t)n_prot + 1)) ||
+        (rc = sc.get(&rank_of, (size_t)n_prot)) || (rc = sc.get(&parent, (size_t)n_prot)) || (rc = sc.get(&d_cnt, (size_t)n_prot)) ||
+        (rc = sc.get(&size, (size_t)n_prot)) || (rc = sc.get(&root, (size_t)n_prot)) || (rc = sc.get(&rflag, (size_t)n_prot)) ||
+        (rc = sc.get(&fx, (size_t)n_prot)) || (rc = sc.get(&best, (size_t)n_prot)) ||
+        (rc = sc.get(&fpartial, (size_t)n_prot / kg::kScanChunk + 3)))
+        return rc;
+    if (nblocks && (rc = sc.get(&dv.d_blocks, nblocks))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)n_prot + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_ibase, ibase.data(), ((size_t)n_prot + 1) * 4, hipMemcpyHostToDevice, s));
+    if (nblocks) hipLaunchKernelGGL(kg::build_blocks_kernel, dim3(grid_of(nblocks)), dim3(256), 0, s, d_off, d_ibase, np, (uint32_t)nblocks, dv.d_blocks);
+    hipLaunchKernelGGL(kg::cluster_init_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, np, rank_of, parent, d_cnt, size, best);
+    HIP_TRY(hipGetLastError());
+
+    // ---- the valid windows, and whether they fit: one pass ----
+    const uint64_t space = (uint64_t)KG_MAX_ENCODED;
+    std::vector<unsigned long long> bins;
+    if ((rc = dv.histogram(0, space, Deriver::shift_for(space), bins))) return rc;
+    uint64_t n = 0;
+    for (auto c : bins) n += c;
+    st.valid_windows = (int64_t)n;
+    {
+        uint64_t cap = (uint64_t)max_windows;
+        if (cap == 0) {
+            size_t free_b = 0, total_b = 0;
+            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+            cap = std::max<uint64_t>(1u << 20, (uint64_t)(free_b * 0.8) / kDeriveBytesPerWindow);
+        }
+        cap = std::min(cap, kDerivePassMax);
+        if (n > cap)
+            return fail(KG_ERR_LIMIT, kmer_text((int64_t)n) + " valid windows do not fit the one pass of this call, which holds " +
+                                          kmer_text((int64_t)cap) + (max_windows ? " (max_windows)" : " (sized from free device memory)"));
+    }
+
+    uint64_t P = 0, K = 0, NL = 0, ND = 0;
+    uint64_t *edge = nullptr;
+    HIP_TRY(hipEventRecord(ev[1], s));
+    HIP_TRY(hipEventRecord(ev[2], s));
+    HIP_TRY(hipEventRecord(ev[3], s));
+    if (n > 0) {
+        // ---- encode and emit (key = v << b | p), sort, collapse to the distinct pairs: the derive call's kernels ----
+        SortPairs sp;
+        unsigned long long *d_cur = nullptr;
+        if ((rc = sp.alloc(sc, n)) || (rc = sc.get(&d_cur, 1))) return rc;
+        HIP_TRY(hipMemsetAsync(d_cur, 0, 8, s));
+        HIP_TRY(hipEventRecord(ev[1], s));
+        {
+            const uint32_t grid = std::min<uint32_t>((dv.n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16);
+            hipLaunchKernelGGL(kg::derive_windows_kernel<true>, dim3(std::max(grid, 1u)), dim3(kg::kDeriveThreads), 0, s, d_seq, dv.d_blocks,
+                               dv.n_blocks, (uint64_t)0, space, 0u, nullptr, rank_of, b, sp.keys(), sp.vals(), d_cur, n);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(ev[2], s));
+        if ((rc = sp.sort(t, sc, n, bit_width(space - 1) + b))) return rc;
+        HIP_TRY(hipEventRecord(ev[3], s));
+        const uint64_t nb = n / kg::kScanChunk + 2;
+        uint32_t *flags = nullptr, *pidx = nullptr;
+        uint64_t *partial = nullptr;
+        if ((rc = sc.get(&flags, n)) || (rc = sc.get(&pidx, n)) || (rc = sc.get(&partial, nb + 1))) return rc;
+        hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(n)), dim3(256), 0, s, sp.keys(), n, flags);
+        HIP_TRY(hipGetLastError());
+        if ((rc = prefix_sum(t, flags, n, pidx, partial, d_tot + 0))) return rc;
+        unsigned long long host_cur = 0;
+        HIP_TRY(hipMemcpyAsync(&host_cur, d_cur, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&P, d_tot, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (host_cur != n) return fail(KG_ERR_DEVICE, "internal: the emit pass wrote a different number of windows than the histogram counted");
+        uint64_t *pk = nullptr;
+        uint32_t *pv = nullptr;
+        if ((rc = sc.get(&pk, P)) || (rc = sc.get(&pv, P))) return rc;
+        HIP_TRY(hipMemsetAsync(pv, 0, P * 4, s));
+        hipLaunchKernelGGL(kg::derive_collapse_kernel, dim3(grid_of((n + kg::kDeriveChunk - 1) / kg::kDeriveChunk)), dim3(256), 0, s, sp.keys(),
+                           sp.vals(), n, pidx, pk, pv);
+        HIP_TRY(hipGetLastError());
+        // ---- d_p, the k-mer runs and their centres (flags / pidx / partial are reused: P <= n) ----
+        uint32_t *kh = flags, *kx = pidx, *lf = pv, *lx = nullptr;
+        unsigned long long *kbest = nullptr;
+        if ((rc = sc.get(&lx, P))) return rc;
+        hipLaunchKernelGGL(kg::cluster_pair_kernel, dim3(grid_of(P)), dim3(256), 0, s, pk, P, b, np, kh, d_cnt);
+        HIP_TRY(hipGetLastError());
+        if ((rc = prefix_sum(t, kh, P, kx, partial, d_tot + 1))) return rc;
+        HIP_TRY(hipMemcpyAsync(&K, d_tot + 1, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if ((rc = sc.get(&kbest, K))) return rc;
+        HIP_TRY(hipMemsetAsync(kbest, 0, K * 8, s));
+        hipLaunchKernelGGL(kg::cluster_centre_kernel, dim3(grid_of((P + kg::kDeriveChunk - 1) / kg::kDeriveChunk)), dim3(256), 0, s, pk, P, b, np,
+                           d_off, kh, kx, kbest);
+        // ---- the links: every pair beside its run's centre (the collapse's values are not needed any more: lf reuses pv) ----
+        hipLaunchKernelGGL(kg::cluster_link_flags_kernel, dim3(grid_of(P)), dim3(256), 0, s, pk, P, b, kh, kx, kbest, lf);
+        HIP_TRY(hipGetLastError());
+        if ((rc = prefix_sum(t, lf, P, lx, partial, d_tot + 2))) return rc;
+        HIP_TRY(hipMemcpyAsync(&NL, d_tot + 2, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (NL > 0) {
+            // the window sort's buffers are free: the link keys go there (NL <= P <= n)
+            SortPairs lk;
+            lk.k[0] = sp.keys(); lk.v[0] = sp.vals();
+            hipLaunchKernelGGL(kg::cluster_link_emit_kernel, dim3(grid_of(P)), dim3(256), 0, s, pk, P, b, kh, kx, kbest, lf, lx, NL, lk.keys(),
+                               lk.vals());
+            HIP_TRY(hipGetLastError());
+            if ((rc = lk.sort(t, sc, NL, 32 + b))) return rc;
+            // runs of equal keys = distinct links (kh / kx are free from here on: NL <= P)
+            uint32_t *lh = kh, *lr = kx, *lstart = nullptr;
+            hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(NL)), dim3(256), 0, s, lk.keys(), NL, lh);
+            HIP_TRY(hipGetLastError());
+            if ((rc = prefix_sum(t, lh, NL, lr, partial, d_tot + 3))) return rc;
+            HIP_TRY(hipMemcpyAsync(&ND, d_tot + 3, 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if ((rc = sc.get(&lstart, ND + 1)) || (rc = sc.get(&edge, ND))) return rc;
+            hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(NL)), dim3(256), 0, s, lh, lr, NL, d_tot + 3, lstart);
+            hipLaunchKernelGGL(kg::cluster_edge_kernel, dim3(grid_of(ND)), dim3(256), 0, s, lk.keys(), lstart, ND, np, d_cnt,
+                               (int64_t)prm->min_shared, (int64_t)prm->min_cover_pct, edge, best, words);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipEventRecord(ev[4], s));
+
+    // ---- connected components: hook and jump while the flag says something changed ----
+    uint32_t rounds = 0;
+    for (bool changed = ND > 0; changed;) {
+        if (rounds > np) return fail(KG_ERR_DEVICE, "internal: the component rounds did not settle");
+        HIP_TRY(hipMemsetAsync(words + kg::kClusterChanged, 0, 8, s));
+        hipLaunchKernelGGL(kg::cluster_hook_kernel, dim3(grid_of(ND)), dim3(256), 0, s, edge, ND, parent, words);
+        hipLaunchKernelGGL(kg::cluster_jump_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, np, parent, words);
+        HIP_TRY(hipGetLastError());
+        unsigned long long flag = 0;
+        HIP_TRY(hipMemcpyAsync(&flag, words + kg::kClusterChanged, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        changed = flag != 0;
+        rounds++;
+    }
+    hipLaunchKernelGGL(kg::cluster_compress_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, np, parent, root, size, rflag);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, rflag, (uint64_t)n_prot, fx, fpartial, d_tot + 0))) return rc;
+    hipLaunchKernelGGL(kg::cluster_emit_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, np, root, fx, size, best, (int4 *)d_out, words);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[5], s));
+    unsigned long long hw[kg::kClusterWords] = {};
+    uint64_t families = 0;
+    HIP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&families, d_tot, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.pairs = (int64_t)P;
+    st.kmers = (int64_t)K;
+    st.links = (int64_t)ND;
+    st.edges = (int64_t)hw[kg::kClusterEdges];
+    st.families = (int64_t)families;
+    st.families_multi = (int64_t)hw[kg::kClusterMulti];
+    st.largest = (int64_t)hw[kg::kClusterLargest];
+    st.rounds = (int32_t)rounds;
+    st.ms_encode = dv.ms_hist + ev.ms(1, 2);
+    st.ms_sort = ev.ms(2, 3);
+    st.ms_link = ev.ms(3, 4);
+    st.ms_components = ev.ms(4, 5);
+    st.ms_total = ev.ms(0, 5);
+    set->d_fam = d_out; guard.p = nullptr;
+    set->count = n_prot;
+    return KG_OK;
+}
+
+int cluster_entry(int device, const kg_cluster_params *prm, const uint8_t *h_seq, const uint8_t *d_seq, const int64_t *offsets,
+                  int64_t n_prot, int64_t max_windows, kg_familyset **out)
+{
+    if (!out) return fail(KG_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!prm) return fail(KG_ERR_ARG, "null kg_cluster_params");
+    if (prm->min_shared < 1) return fail(KG_ERR_ARG, "min_shared must be >= 1");
+    if (prm->min_cover_pct < 0 || prm->min_cover_pct > 100) return fail(KG_ERR_ARG, "min_cover_pct must be in 0..100");
+    if (prm->reserved != 0) return fail(KG_ERR_ARG, "kg_cluster_params.reserved must be 0");
+    if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
+    if (n_prot < 0) return fail(KG_ERR_ARG, "n_prot < 0");
+    if (n_prot >= (1ll << 29)) return fail(KG_ERR_LIMIT, "2^29 or more proteins in one call");
+    if (!offsets) return fail(KG_ERR_ARG, "null offsets");
+    if (offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
+    for (int64_t k = 0; k < n_prot; k++) {
+        const int64_t L = offsets[k + 1] - offsets[k];
+        if (L < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": offsets decrease (offsets[p+1] < offsets[p])");
+        if (L >= (1ll << 31)) return fail(KG_ERR_LIMIT, "protein " + kmer_text(k) + ": 2^31 or more characters");
+    }
+    const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
+    if (seq_bytes && !h_seq && !d_seq) return fail(KG_ERR_ARG, "null sequence");
+    CallScope cs(device);               // the call's context: closed when the call returns, the set keeps only its records
+    if (cs.rc) return cs.rc;
+    kg_familyset *set = new (std::nothrow) kg_familyset();
+    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
+    set->device = device;
+    int rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
+    if (!rc) rc = cluster_impl(cs.t, prm, h_seq, d_seq, offsets, n_prot, max_windows, set);
+    cs.t->cache.release_all();                          // scratch goes back to the driver
+    if (rc) { std::string keep = g_err; kg_familyset_free(set); g_err = keep; return rc; }
+    if (getenv("KG_DEBUG"))
+        fprintf(stderr, "[kg] kg_proteins_cluster: proteins=%lld valid=%lld pairs=%lld kmers=%lld links=%lld edges=%lld families=%lld multi=%lld largest=%lld rounds=%d encode_ms=%.3f sort_ms=%.3f link_ms=%.3f components_ms=%.3f total_ms=%.3f\n",
+                (long long)set->st.proteins, (long long)set->st.valid_windows, (long long)set->st.pairs, (long long)set->st.kmers,
+                (long long)set->st.links, (long long)set->st.edges, (long long)set->st.families, (long long)set->st.families_multi,
+                (long long)set->st.largest, set->st.rounds, set->st.ms_encode, set->st.ms_sort, set->st.ms_link, set->st.ms_components,
+                set->st.ms_total);
+    *out = set;
+    return KG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kg_proteins_cluster(int device, const kg_cluster_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
+                        int64_t max_windows, kg_familyset **out)
+{
+    return cluster_entry(device, p, seq, nullptr, offsets, n_prot, max_windows, out);
+}
+
+int kg_proteins_cluster_device(int device, const kg_cluster_params *p, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
+                               int64_t max_windows, kg_familyset **out)
+{
+    return cluster_entry(device, p, nullptr, d_seq, offsets, n_prot, max_windows, out);
+}
+
+int64_t kg_familyset_count(const kg_familyset *s) { return s ? s->count : 0; }
+
+int kg_familyset_copy(const kg_familyset *s, int64_t first, int64_t count, kg_family *dst)
+{
+    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
+    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_familyset_copy: range outside the set");
+    if (count == 0) return KG_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpy(dst, s->d_fam + first * 16, (size_t)count * 16, hipMemcpyDefault));
+    return KG_OK;
+}
+
+int kg_familyset_stats(const kg_familyset *s, kg_cluster_stats *out)
+{
+    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
+    *out = s->st;
+    return KG_OK;
+}
+
+void kg_familyset_free(kg_familyset *s)
+{
+    if (!s) return;
+    if (s->d_fam) {
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->d_fam);
+    }
+    delete s;
+}
+
+}  // extern "C"

@@ -78,12 +78,11 @@ struct Deriver {
     }
 };
 
-int derive_impl(kg_table *t, const kg_derive_params *prm, const uint8_t *h_seq, const uint8_t *d_seq_in, const int64_t *offsets,
-                int64_t n_prot, const int32_t *fn, const int32_t *otu, kg_sigset *set)
+// host: block counts (kg_scan's -a trip counts, KGJ:912).  ibase[p] = the first window block of 64 windows of protein p,
+// ibase[n_prot] = *nblocks; *windows = sum of max(len_p - 8, 0).  Shared with kg_host_cluster.hpp.
+int derive_block_bases(const int64_t *offsets, int64_t n_prot, std::vector<uint32_t> &ibase, uint64_t *nblocks_out, uint64_t *windows_out)
 {
-    kg_derive_stats &st = set->st;
-    // ---- host: block counts (kg_scan's -a trip counts, KGJ:912) ----
-    std::vector<uint32_t> ibase((size_t)n_prot + 1);
+    ibase.assign((size_t)n_prot + 1, 0);
     uint64_t nblocks = 0, windows = 0;
     for (int64_t k = 0; k < n_prot; k++) {
         const int64_t L = offsets[k + 1] - offsets[k];
@@ -94,6 +93,18 @@ int derive_impl(kg_table *t, const kg_derive_params *prm, const uint8_t *h_seq, 
         if (nblocks > 0x7FFFFFFFull) return fail(KG_ERR_LIMIT, "2^31 or more window blocks of 64 windows in one call");
     }
     ibase[(size_t)n_prot] = (uint32_t)nblocks;
+    *nblocks_out = nblocks;
+    *windows_out = windows;
+    return KG_OK;
+}
+
+int derive_impl(kg_table *t, const kg_derive_params *prm, const uint8_t *h_seq, const uint8_t *d_seq_in, const int64_t *offsets,
+                int64_t n_prot, const int32_t *fn, const int32_t *otu, kg_sigset *set)
+{
+    kg_derive_stats &st = set->st;
+    std::vector<uint32_t> ibase;
+    uint64_t nblocks = 0, windows = 0;
+    if (int brc = derive_block_bases(offsets, n_prot, ibase, &nblocks, &windows)) return brc;
     st.proteins = n_prot;
     st.windows = (int64_t)windows;
     const uint32_t b = bits_for((uint64_t)n_prot);

@@ -13,6 +13,7 @@
 #include "kg_order.hpp"
 #include "kg_build.hpp"
 #include "kg_derive.hpp"
+#include "kg_cluster.hpp"
 #include "kg_assign.hpp"
 #include "kg_regions.hpp"
 #include "kg_orfs.hpp"
@@ -37,6 +38,7 @@
 // ---- the batch stages: each host beside its kernels ----
 #include "kg_host_build.hpp"
 #include "kg_host_derive.hpp"
+#include "kg_host_cluster.hpp"
 #include "kg_host_assign.hpp"
 #include "kg_host_regions.hpp"
 #include "kg_host_orfs.hpp"

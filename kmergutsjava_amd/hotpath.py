@@ -560,6 +560,38 @@ def derive_signatures(seq, offsets, fn, otu, min_proteins: int = 2, purity_pct: 
     return SignatureSet(out.value, device)
 
 
+def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20, max_windows: int = 0, device: int = 0,
+                     device_ptr: Optional[int] = None):
+    """Proteins -> families by shared 8-mers, on the GPU (include/kmerguts_hip.h kg_proteins_cluster states the rule): a link
+    from every protein of a k-mer to the k-mer's longest protein, an edge where a link's shared k-mers pass min_shared and
+    min_cover_pct of the member's distinct k-mers, a family per connected component.  seq: bytes / uint8 ndarray of the
+    concatenated protein characters, or None when device_ptr gives their address in HBM; offsets: int64[n_prot + 1].  The
+    defaults 5 and 20 are this project's choice; max_windows = 0 sizes the one pass from free device memory.
+    -> (numpy records of _native.FAMILY_DTYPE in protein order, the call's statistics)."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_prot + 1]")
+    n = off.size - 1
+    p = N.KgClusterParams(int(min_shared), int(min_cover_pct), 0)
+    h = C.c_void_p()
+    lib = N.load()
+    if device_ptr is not None:
+        N.check(lib.kg_proteins_cluster_device(device, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, int(max_windows), C.byref(h)))
+    else:
+        arr = _seq_bytes(seq, off)
+        N.check(lib.kg_proteins_cluster(device, C.byref(p), arr.ctypes.data if arr.size else None, off.ctypes.data, n, int(max_windows),
+                                        C.byref(h)))
+    try:
+        st = N.KgClusterStats()
+        N.check(lib.kg_familyset_stats(h, C.byref(st)))
+        count = int(lib.kg_familyset_count(h))
+        out = np.zeros(count, dtype=N.FAMILY_DTYPE)
+        N.check(lib.kg_familyset_copy(h, 0, count, out.ctypes.data if count else None))
+        return out, st.as_dict()
+    finally:
+        lib.kg_familyset_free(h)
+
+
 def assign_calls(calls, call_start, otu=None, min_score: int = 0, min_share_pct: int = 50, device: int = 0) -> np.ndarray:
     """One function per protein from caller-held CALL lists, on the GPU (kg_assign_calls): calls CALL_DTYPE[call_start[-1]],
     call_start int64[n_prot + 1] (protein p's CALLs are calls[call_start[p] : call_start[p + 1]], in emission order), otu

@@ -1,0 +1,234 @@
+"""The family rule of kg_proteins_cluster (include/kmerguts_hip.h) restated twice: with plain loops over Python dicts, one window
+at a time, and with numpy on whole arrays.  The GPU tests compare the device's bytes with the numpy form; the CPU tests compare
+the two forms with each other and with answers worked out by hand."""
+from __future__ import annotations
+
+import numpy as np
+
+from kmergutsjava_amd import _native as N
+
+ALPHA = b"ACDEFGHIKLMNPQRSTVWY"
+K = 8
+COUNTS = ("proteins", "valid_windows", "pairs", "kmers", "links", "edges", "families", "families_multi", "largest")
+
+
+def pack(prots):
+    """list of bytes -> (seq bytes, int64 offsets)."""
+    off = np.zeros(len(prots) + 1, dtype=np.int64)
+    if prots:
+        off[1:] = np.cumsum([len(p) for p in prots])
+    return b"".join(prots), off
+
+
+def _finish(n, root, best, shared, counts):
+    root = np.asarray(root, dtype=np.int64)
+    out = np.zeros(n, dtype=N.FAMILY_DTYPE)
+    is_root = root == np.arange(n)
+    number = np.cumsum(is_root) - 1
+    out["family"] = number[root] if n else []
+    out["root"] = root
+    out["best"] = best
+    out["shared"] = shared
+    size = np.bincount(root, minlength=n) if n else np.zeros(0, dtype=np.int64)
+    counts.update(proteins=n, families=int(is_root.sum()), families_multi=int((size >= 2).sum()), largest=int(size.max()) if n else 0)
+    return out, counts
+
+
+def cluster_loops(seq: bytes, offsets, min_shared: int = 5, min_cover_pct: int = 20):
+    """Plain loops.  -> (FAMILY_DTYPE records, counts)."""
+    seq = bytes(seq)
+    n = len(offsets) - 1
+    code = {ch: j for j, ch in enumerate(ALPHA)}
+    members = {}                                        # v -> set of proteins
+    d = [0] * n
+    valid = 0
+    for p in range(n):
+        s = seq[offsets[p]:offsets[p + 1]]
+        own = set()
+        for i in range(0, len(s) - K):                  # positions [0, len - 8)
+            w = s[i:i + K]
+            if any(ch not in code for ch in w):
+                continue
+            valid += 1
+            v = 0
+            for ch in w:
+                v = v * 20 + code[ch]
+            own.add(v)
+        d[p] = len(own)
+        for v in own:
+            members.setdefault(v, set()).add(p)
+    length = [int(offsets[p + 1] - offsets[p]) for p in range(n)]
+    s_of = {}                                           # (m, c) -> shared count
+    for v, ps in members.items():
+        if len(ps) < 2:
+            continue
+        c = min(ps, key=lambda p: (-length[p], p))
+        for m in ps:
+            if m != c:
+                s_of[(m, c)] = s_of.get((m, c), 0) + 1
+    parent = list(range(n))
+
+    def find(x):
+        while parent[x] != x:
+            x = parent[x]
+        return x
+
+    best, shared = [-1] * n, [0] * n
+    edges = 0
+    for (m, c), s in sorted(s_of.items()):
+        if s >= min_shared and 100 * s >= min_cover_pct * d[m]:
+            edges += 1
+            if s > shared[m]:                           # ascending c: a tie keeps the smaller c
+                best[m], shared[m] = c, s
+            a, b = find(m), find(c)
+            if a != b:
+                parent[max(a, b)] = min(a, b)
+    root = [find(p) for p in range(n)]
+    counts = dict(valid_windows=valid, pairs=sum(d), kmers=len(members), links=len(s_of), edges=edges)
+    return _finish(n, root, best, shared, counts)
+
+
+def cluster_numpy(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20):
+    """Whole arrays.  -> (FAMILY_DTYPE records, counts)."""
+    off = np.asarray(offsets, dtype=np.int64)
+    n = off.size - 1
+    arr = np.frombuffer(bytes(seq), dtype=np.uint8) if not isinstance(seq, np.ndarray) else seq.view(np.uint8).reshape(-1)
+    counts = dict(valid_windows=0, pairs=0, kmers=0, links=0, edges=0)
+    best, shared = np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    label = np.arange(n, dtype=np.int64)
+    lens = off[1:] - off[:-1]
+    nwin = np.maximum(lens - K, 0)
+    total = int(nwin.sum())
+    if total:
+        lut = np.full(256, 20, dtype=np.int64)
+        lut[np.frombuffer(ALPHA, dtype=np.uint8)] = np.arange(20)
+        prot = np.repeat(np.arange(n, dtype=np.int64), nwin)
+        start = off[prot] + np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(nwin) - nwin, nwin)
+        codes = lut[arr]
+        v = np.zeros(total, dtype=np.int64)
+        bad = np.zeros(total, dtype=bool)
+        for k in range(K):
+            c = codes[start + k]
+            v = v * 20 + c
+            bad |= c >= 20
+        v, prot = v[~bad], prot[~bad]
+        counts["valid_windows"] = int(v.size)
+        if v.size:
+            key = np.unique(v * n + prot)                   # the distinct (k-mer, protein) pairs, in (k-mer, protein) order
+            pv, pp = key // n, key % n
+            d = np.bincount(pp, minlength=n)
+            head = np.ones(key.size, dtype=bool)
+            head[1:] = pv[1:] != pv[:-1]
+            first = np.flatnonzero(head)
+            rid = np.cumsum(head) - 1
+            rank = (lens[pp] << 32) | (0xFFFFFFFF - pp)
+            centre = 0xFFFFFFFF - (np.maximum.reduceat(rank, first) & 0xFFFFFFFF)
+            c = centre[rid]
+            link = pp != c
+            lk, s = np.unique((pp[link] << 32) | c[link], return_counts=True)
+            m, c = lk >> 32, lk & 0xFFFFFFFF
+            ok = (s >= min_shared) & (100 * s >= min_cover_pct * d[m])
+            counts.update(pairs=int(key.size), kmers=int(first.size), links=int(lk.size), edges=int(ok.sum()))
+            m, c, s = m[ok], c[ok], s[ok]
+            top = np.zeros(n, dtype=np.int64)
+            np.maximum.at(top, m, (s << 32) | (0xFFFFFFFF - c))
+            has = top > 0
+            best[has] = 0xFFFFFFFF - (top[has] & 0xFFFFFFFF)
+            shared[has] = top[has] >> 32
+            while True:                                     # hook the larger root under the smaller, compress, repeat
+                ru, rv = label[m], label[c]
+                diff = ru != rv
+                if not diff.any():
+                    break
+                np.minimum.at(label, np.maximum(ru, rv)[diff], np.minimum(ru, rv)[diff])
+                while True:
+                    nxt = label[label]
+                    if (nxt == label).all():
+                        break
+                    label = nxt
+    return _finish(n, label, best, shared, counts)
+
+
+# ---- inputs the tests share ---------------------------------------------------------------------------------------------------
+
+def random_protein(rng, length: int) -> bytes:
+    return np.frombuffer(ALPHA, dtype=np.uint8)[rng.integers(0, 20, size=length)].tobytes()
+
+
+def random_batch(rng, n_fam: int = 6, x_rate: float = 0.02):
+    """Families of mutated, trimmed copies plus fragments, unrelated proteins and proteins of 0..9 residues, some with 'X', in a
+    random order.  -> list of bytes."""
+    alpha = np.frombuffer(ALPHA, dtype=np.uint8)
+    prots = []
+    for _ in range(n_fam):
+        length = int(rng.integers(20, 120))
+        base = alpha[rng.integers(0, 20, size=length)]
+        for _ in range(int(rng.integers(1, 6))):
+            s = base.copy()
+            mut = rng.random(length) < rng.choice([0.0, 0.03, 0.1])
+            s[mut] = alpha[rng.integers(0, 20, size=int(mut.sum()))]
+            s[rng.random(length) < x_rate] = ord("X")
+            a = int(rng.integers(0, length // 3))
+            prots.append(s[a:length - int(rng.integers(0, length // 3))].tobytes())
+        if rng.random() < 0.5:                              # two bases joined: a chimera links families
+            prots.append(base[:length // 2].tobytes() + random_protein(rng, int(rng.integers(10, 40))))
+    for _ in range(int(rng.integers(0, 5))):
+        prots.append(random_protein(rng, int(rng.integers(0, 10))))
+    if rng.random() < 0.3:
+        prots.append(b"X" * int(rng.integers(9, 30)))
+    order = rng.permutation(len(prots))
+    return [prots[i] for i in order]
+
+
+def partition(rec) -> set:
+    """The families as a set of frozensets of member indices."""
+    groups = {}
+    for i, r in enumerate(rec["root"]):
+        groups.setdefault(int(r), []).append(i)
+    return {frozenset(g) for g in groups.values()}
+
+
+def shared_pair(rng, s: int, d_m: int, extra_c: int = 5):
+    """Two proteins: m with d_m windows and c, the longer, which share exactly s distinct k-mers (a common head of s + 7
+    residues followed by different residues).  -> [m, c]"""
+    assert 1 <= s < d_m
+    g = random_protein(rng, s + 7)
+    m = g + b"A" + random_protein(rng, d_m + 8 - (s + 7) - 1)
+    c = g + b"C" + random_protein(rng, d_m + 8 - (s + 7) - 1 + extra_c)
+    return [m, c]
+
+
+def one_kmer_batch(lens, w: bytes = b"ACDEFGHI"):
+    """Proteins that share the one k-mer w and have no other valid window: w, then 'X' up to the given length (>= 9 each).
+    -> (seq bytes, offsets)"""
+    lens = np.asarray(lens, dtype=np.int64)
+    off = np.zeros(lens.size + 1, dtype=np.int64)
+    off[1:] = np.cumsum(lens)
+    seq = np.full(int(off[-1]), ord("X"), dtype=np.uint8)
+    at = off[:-1, None] + np.arange(K)[None, :]
+    seq[at] = np.frombuffer(w, dtype=np.uint8)[None, :]
+    return seq.tobytes(), off
+
+
+def one_kmer_answer(lens):
+    """What min_shared = 1, min_cover_pct = 0 give for one_kmer_batch: every protein linked to the longest (first on a tie)."""
+    lens = np.asarray(lens, dtype=np.int64)
+    n = lens.size
+    c = int(np.argmax(lens))
+    out = np.zeros(n, dtype=N.FAMILY_DTYPE)
+    out["best"], out["shared"] = c, 1
+    out["best"][c], out["shared"][c] = -1, 0
+    return out
+
+
+def path_batch(rng, n: int, seg: int = 20):
+    """Protein i = segment i followed by segment i + 1, under a random permutation of the indices.  -> list of bytes"""
+    segs = [random_protein(rng, seg) for _ in range(n + 1)]
+    order = rng.permutation(n)
+    return [segs[i] + segs[i + 1] for i in order]
+
+
+def star_batch(rng, n: int, seg: int = 20):
+    """One long protein of n segments, and n members: segment j followed by residues of their own.  -> list of bytes"""
+    segs = [random_protein(rng, seg) for _ in range(n)]
+    return [b"".join(segs)] + [s + random_protein(rng, seg) for s in segs]
