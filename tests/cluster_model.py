@@ -232,3 +232,78 @@ def star_batch(rng, n: int, seg: int = 20):
     """One long protein of n segments, and n members: segment j followed by residues of their own.  -> list of bytes"""
     segs = [random_protein(rng, seg) for _ in range(n)]
     return [b"".join(segs)] + [s + random_protein(rng, seg) for s in segs]
+
+
+# ---- inputs with exact control over every protein's k-mer set -----------------------------------------------------------------
+
+def token(v: int) -> bytes:
+    """The 8 residues whose base-20 value over ALPHA is v (0 <= v < 20^8)."""
+    assert 0 <= v < 20 ** K
+    out = bytearray(K)
+    for k in range(K - 1, -1, -1):
+        v, r = divmod(v, 20)
+        out[k] = ALPHA[r]
+    return bytes(out)
+
+
+def _token_seq(count, flat, pad):
+    """count[p] tokens per protein, their values in protein order in flat, pad[p] trailing 'X'.  -> (seq bytes, offsets)"""
+    count, flat, pad = (np.asarray(a, dtype=np.int64) for a in (count, flat, pad))
+    assert flat.size == int(count.sum()) and pad.size == count.size and (pad >= 0).all()
+    assert flat.size == 0 or (0 <= flat.min() and flat.max() < 20 ** K)
+    off = np.zeros(count.size + 1, dtype=np.int64)
+    off[1:] = np.cumsum(count * (K + 1) + pad)
+    seq = np.full(int(off[-1]), ord("X"), dtype=np.uint8)
+    if flat.size:
+        prot = np.repeat(np.arange(count.size), count)
+        at = off[prot] + (np.arange(flat.size) - np.repeat(np.cumsum(count) - count, count)) * (K + 1)
+        digits = (flat[:, None] // 20 ** np.arange(K - 1, -1, -1, dtype=np.int64)[None, :]) % 20
+        seq[at[:, None] + np.arange(K)[None, :]] = np.frombuffer(ALPHA, dtype=np.uint8)[digits]
+    return seq.tobytes(), off
+
+
+def token_batch(members, pad=None):
+    """Protein p = token(v) + 'X' for every v of members[p], then pad[p] further 'X'.  The windows are the positions
+    [0, len - 8) and a window that touches an 'X' is invalid, so every token gives exactly one valid window: members[p] is
+    protein p's k-mer set, 9 * len(members[p]) + pad[p] its length, and the sorted (k-mer, protein) pairs are ordered by token
+    value, then protein index.  -> (seq bytes, offsets)"""
+    if isinstance(members, np.ndarray) and members.ndim == 2:   # the same number of tokens in every protein
+        count, flat = np.full(members.shape[0], members.shape[1], dtype=np.int64), members.reshape(-1)
+        return _token_seq(count, flat, np.zeros(count.size, dtype=np.int64) if pad is None else pad)
+    count = np.fromiter((len(m) for m in members), dtype=np.int64, count=len(members))
+    flat =np.fromiter((int(v) for m in members for v in m), dtype=np.int64, count=int(count.sum()))
+    return _token_seq(count, flat, np.zeros(count.size, dtype=np.int64) if pad is None else pad)
+
+
+def graph_batch(n: int, edges):
+    """n proteins and one private token per edge (edge e's is the token of value e), held by exactly its two ends; a protein
+    without an edge is 9 'X'.  With min_shared = 1, min_cover_pct = 0 every link is an edge between an edge's ends, so the
+    families are the graph's connected components.  -> (seq bytes, offsets)"""
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    assert e.size == 0 or (0 <= e.min() and e.max() < n and (e[:, 0] != e[:, 1]).all())
+    ends = np.concatenate([e[:, 0], e[:, 1]])
+    order = np.argsort(ends, kind="stable")
+    count = np.bincount(ends, minlength=n)
+    return _token_seq(count, np.concatenate([np.arange(len(e))] * 2)[order], np.where(count == 0, K + 1, 0))
+
+
+def components(n: int, edges):
+    """root[i] = the smallest member of i's connected component: a sequential union-find (path halving, the larger root goes
+    under the smaller).  The independent answer for the partition: it shares nothing with the two forms above."""
+    up = list(range(n))
+    for a, b in edges:
+        a, b = int(a), int(b)
+        while up[a] != a:
+            up[a] = up[up[a]]
+            a = up[a]
+        while up[b] != b:
+            up[b] = up[up[b]]
+            b = up[b]
+        if a < b:
+            up[b] = a
+        elif b < a:
+            up[a] = b
+    root = np.zeros(n, dtype=np.int64)
+    for i in range(n):                                      # up[i] < i for every non-root: the roots below i are final
+        root[i] = i if up[i] == i else root[up[i]]
+    return root

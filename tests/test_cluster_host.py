@@ -3,6 +3,7 @@ other, answers worked out by hand, the layouts of the new records, and the front
 by the model."""
 import ctypes as C
 import os
+import re
 import subprocess
 import sys
 
@@ -11,6 +12,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import cluster_edge_cases as E  # noqa: E402
 import cluster_model as M  # noqa: E402
 import test_regions_host as H  # noqa: E402
 
@@ -165,3 +167,124 @@ def test_front_end_writers_and_known_merging(tmp_path, capsys):
     assert CP.main(["-p", str(one), "-p", str(one), "-o", str(out)]) == 1 and "duplicate protein id g1_a" in capsys.readouterr().err
     with pytest.raises(ValueError):
         CP.cluster_proteins([str(one)], str(out), known=str(known), cluster=_model)
+
+
+# ---- the inputs of tests/test_gpu_cluster_edges.py: the model against the answers of tests/cluster_edge_cases.py -------------
+
+LOOPS_CHARS = 20000     # cluster_loops runs on every input of at most this many characters (20 ms), and on a larger one when it
+                        # is the first of its test case: the 32 inputs of one large lane layout would take it 5 s
+
+
+def _both(batch, answer, ms=1, pct=0, first=True, what=""):
+    """cluster_numpy == the answer worked out without it (and == cluster_loops, see LOOPS_CHARS).  -> its records, counts"""
+    seq, off = batch
+    rec, counts = M.cluster_numpy(seq, off, ms, pct)
+    if answer is not None:
+        assert rec.tobytes() == answer[0].tobytes() and counts == answer[1], what
+    if first or len(seq) <= LOOPS_CHARS:
+        a, ca = M.cluster_loops(seq, off, ms, pct)
+        assert a.tobytes() == rec.tobytes() and ca == counts, what
+    return rec, counts
+
+
+def test_the_constants_the_edge_cases_are_built_around():
+    csrc = os.path.join(ROOT, "kmergutsjava_amd", "csrc")
+    text = {name: open(os.path.join(csrc, name)).read() for name in ("kg_device.hpp", "kg_derive.hpp", "kg_build.hpp", "kg_cluster.hpp",
+                                                                     "kg_host.hpp", "kg_host_cluster.hpp")}
+
+    def const(name, var):
+        return int(re.search(r"constexpr int %s = (\d+);" % var, text[name]).group(1))
+
+    assert const("kg_derive.hpp", "kDeriveChunk") == E.LANE == 16
+    assert re.search(r"constexpr int kScanChunk = kScanThreads \* kScanPerThread;", text["kg_device.hpp"])
+    assert const("kg_device.hpp", "kScanThreads") * const("kg_device.hpp", "kScanPerThread") == E.SCAN == 2048
+    assert re.search(r"constexpr int kBuildTile = kBuildThreads \* kBuildItems;", text["kg_build.hpp"])
+    assert const("kg_build.hpp", "kBuildThreads") * const("kg_build.hpp", "kBuildItems") == E.TILE == 4096
+    assert const("kg_device.hpp", "kAaWinPerBlock") == 64 and {64 + 8 - 1, 64 + 8, 64 + 8 + 1, 2 * 64 + 8, 2 * 64 + 8 + 1} < set(E.BLOCK_LENGTHS)
+    # every cluster kernel is launched 256 wide: its bound, the launches' block size and grid_of's divisor
+    bounds = {name: width for width, name in re.findall(r"__launch_bounds__\((\w+)\) void (cluster_\w+_kernel)", text["kg_cluster.hpp"])}
+    assert "cluster_centre_kernel" in bounds and len(bounds) == text["kg_cluster.hpp"].count("__global__")
+    assert set(bounds.values()) == {str(E.THREADS)}
+    launches = {name: width for name, width in re.findall(r"hipLaunchKernelGGL\(kg::(cluster_\w+_kernel), dim3\(grid_of\([^;]*?\)\), dim3\((\d+)\)",
+                                                          text["kg_host_cluster.hpp"])}
+    assert set(launches) == set(bounds) and set(launches.values()) == {str(E.THREADS)}
+    assert text["kg_host_cluster.hpp"].count("kg::cluster_") == len(launches)           # every launch was read
+    assert int(re.search(r"uint32_t grid_of\(uint64_t n, uint32_t threads = (\d+)\)", text["kg_host.hpp"]).group(1)) == E.THREADS
+    assert E.THREADS * E.LANE == E.TILE
+
+
+def test_tokens_and_the_union_find():
+    assert M.token(0) == b"AAAAAAAA" and M.token(20 ** 8 - 1) == b"YYYYYYYY" and M.token(20 * 3 + 1) == b"AAAAAAEC"
+    seq, off = M.token_batch([[5, 0], [], [0]], [0, 3, 2])
+    assert seq == M.token(5) + b"X" + M.token(0) + b"X" + b"XXX" + M.token(0) + b"XXX" and off.tolist() == [0, 18, 21, 32]
+    assert M.token_batch(np.array([[5], [0]]))[0] == M.token(5) + b"X" + M.token(0) + b"X"
+    rec, counts = _both((seq, off), None)
+    assert counts["valid_windows"] == counts["pairs"] == 3 and counts["kmers"] == 2 and rec.tolist() == [(0, 0, -1, 0), (1, 1, -1, 0), (0, 0, 0, 1)]
+    seq, off = M.graph_batch(4, [(3, 1), (1, 0)])
+    assert seq == M.token(1) + b"X" + M.token(1) + b"X" + M.token(0) + b"X" + b"X" * 9 + M.token(0) + b"X" and off.tolist() == [0, 9, 27, 36, 45]
+    assert M.components(6, [(5, 3), (4, 2), (3, 1), (0, 0)]).tolist() == [0, 1, 2, 1, 2, 1]
+    assert M.components(0, []).tolist() == [] and M.components(3, [(2, 1), (1, 0), (0, 2)]).tolist() == [0, 0, 0]
+
+
+def test_the_lane_grid_is_the_one_stated():
+    assert sorted(set(l for l, _ in E.LANE_GRID)) == [0, 1, 15, 16, 17, 4095, 4096, 4097]
+    assert sorted(set(r for _, r in E.LANE_GRID)) == [1, 2, 15, 16, 17, 31, 32, 33, 4095, 4096, 4097, 8192]
+    assert E.lane_places(0, 1) == [0] and E.lane_places(15, 33) == [0, 1, 16, 17, 32] and E.lane_places(1, 17) == [0, 14, 15, 16]
+    at = E.lane_places(17, 8192)                                # pairs 17 .. 8208
+    assert at == [0, 14, 15, 30, 31, 46, 47, 4078, 4079, 8158, 8159, 8174, 8175, 8190, 8191]
+
+
+@pytest.mark.parametrize("lead,run", E.LANE_GRID)
+def test_kmer_runs_at_lane_and_workgroup_borders(lead, run):
+    for k, (name, batch, answer) in enumerate(E.lane_cases(lead, run)):
+        rec, counts = _both(batch, answer, first=k == 0, what=name)
+        assert counts["kmers"] == (lead > 0) + 1 + int(name.startswith("tail 1"))
+
+
+@pytest.mark.parametrize("name,lead,sizes", E.SHORT_RUNS, ids=[c[0] for c in E.SHORT_RUNS])
+def test_many_short_kmer_runs(name, lead, sizes):
+    batch, answer = E.short_runs_case(lead, sizes)
+    rec, counts = _both(batch, answer)
+    assert counts["kmers"] == len(sizes) + (lead > 0) and counts["pairs"] == lead + sum(sizes)
+
+
+@pytest.mark.parametrize("lead_links", E.LINK_LEAD)
+@pytest.mark.parametrize("s", E.LINK_S)
+def test_link_runs_at_the_scan_chunk(s, lead_links):
+    batch, answer = E.link_case(s, lead_links)
+    rec, _ = _both(batch, answer)
+    assert rec[lead_links].tolist()[2:] == (lead_links + 1, s)
+    if s >= 2047:
+        for name, (ms, pct), batch, answer, edge in E.link_threshold_cases(s, lead_links):
+            rec, counts = _both(batch, answer, ms, pct, first=False, what=name)
+            assert rec[lead_links].tolist()[2:] == ((lead_links + 1, s) if edge else (-1, 0))
+
+
+@pytest.mark.parametrize("s,third,m_first", E.THREE_CENTRES)
+def test_one_member_between_three_centres(s, third, m_first):
+    batch, answer = E.three_centres_case(s, third, m_first)
+    rec, _ = _both(batch, answer, first=(s, third) == (2048, 2049))
+    m = 0 if m_first else 3
+    assert rec[m]["best"] == ((3 if m_first else 2) if third > s else (1 if m_first else 0)) and rec[m]["shared"] == max(s, third)
+
+
+@pytest.mark.parametrize("n", E.KEY_WIDTH_N)
+def test_key_width_inputs(n):
+    members, pad = E.key_width_case(n)
+    rec, counts = _both(M.token_batch(members, pad), E.token_answer(members, pad))
+    assert counts["families"] == 1 and counts["kmers"] == min(n, 2) + {1: 0, 2: 1, 3: 3}.get(n, 4)
+
+
+@pytest.mark.parametrize("length", E.BLOCK_LENGTHS)
+def test_window_block_inputs(length):
+    prots = E.block_edge_batch(length)
+    rec, counts = _both(M.pack(prots), None, 5, 20)
+    E.check_block_edge_records(length, rec, counts)
+
+
+@pytest.mark.parametrize("shape", E.COMPONENT_SHAPES)
+def test_component_shapes_against_the_union_find(shape):
+    n, edges = E.component_shapes()[shape]
+    assert set(E.component_shapes()) == set(E.COMPONENT_SHAPES) and 10000 <= n <= 20000
+    rec, counts = _both(M.graph_batch(n, edges), None)
+    E.check_component_records(n, edges, rec, counts)
