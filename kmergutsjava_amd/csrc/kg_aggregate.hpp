@@ -55,8 +55,8 @@ __device__ __forceinline__ int32_t uni(int32_t v) { return __builtin_amdgcn_read
 // processSetOfHits (KGJ:385-455) on the list [s.lo .. s.last].  chunk grid is anchored at `begin`
 // so that the chunk the caller is working on (cur_base, membership bits cur_mask, the lanes' fI and
 // functionWt) is taken from registers instead of memory.  A CALL goes to calls[s.ncalls] (the container's staging
-// range); its voters are marked in vote[] -- those of the caller's chunk in cur_votes, which the caller stores with the
-// chunk's other bytes.
+// range); its voters are marked in vote[] -- those of the caller's chunk in cur_vote (per lane), which the caller stores with
+// the chunk's other bytes.
 // returns bit 0: a CALL was made, bit 1: the last two members were kept
 struct ChunkRegs {               // one 64-record chunk held in registers: base and membership bits wave-uniform, the rest per lane
     uint32_t base;
@@ -67,7 +67,7 @@ struct ChunkRegs {               // one 64-record chunk held in registers: base 
 
 __device__ __forceinline__ uint32_t process_set(const kg_hit *__restrict__ h, const uint8_t *__restrict__ acc, uint8_t *__restrict__ vote,
                                             uint32_t begin, const AggParams &p, AggState &s, const ChunkRegs &cur, const ChunkRegs &prv,
-                                            uint64_t &cur_votes, uint32_t container, kg_call *calls, bool allow_carry)
+                                            bool &cur_vote, uint32_t container, kg_call *calls, bool allow_carry)
 {
     const int lane = threadIdx.x & 63;
     int32_t fICount = 0;
@@ -129,7 +129,7 @@ __device__ __forceinline__ uint32_t process_set(const kg_hit *__restrict__ h, co
             const uint32_t i = b + lane;
             const bool in = i >= s.lo && i <= s.last;
             if (b == cur.base) {
-                cur_votes |= __ballot(in && ((cur.mask >> lane) & 1ull) != 0 && cur.fI == s.currentFI);
+                cur_vote = cur_vote || (in && ((cur.mask >> lane) & 1ull) != 0 && cur.fI == s.currentFI);
             } else if (b == prv.base) {
                 if (in && ((prv.mask >> lane) & 1ull) != 0 && prv.fI == s.currentFI) vote[i] = 1;
             } else if (in && (acc[i] & KG_EV_ACCEPTED) != 0 && h[i].fI == s.currentFI) {
@@ -149,20 +149,19 @@ __device__ __forceinline__ uint32_t process_set(const kg_hit *__restrict__ h, co
     return what;
 }
 
-// per-chunk event masks (wave-uniform; bit k = record base + k)
-struct EvMasks {
-    uint64_t pb, pb_call, pb_keep, pa, pa_call, pa_keep;
+// The event bits of a chunk's records, each lane its own record's (k and what are wave-uniform).  (As six wave-uniform 64-bit
+// masks they held twelve scalar registers through the chunk loop, in a kernel that has none to spare.)
+struct EvBits {
+    uint32_t e;
     __device__ __forceinline__ void before(int k, uint32_t what)
     {
-        pb |= 1ull << k;
-        pb_call |= (uint64_t)(what & 1) << k;
-        pb_keep |= (uint64_t)((what >> 1) & 1) << k;
+        const uint32_t bits = KG_EV_RESET_BEFORE | ((what & 1u) ? KG_EV_CALL_BEFORE : 0u) | ((what & 2u) ? KG_EV_KEEP2_BEFORE : 0u);
+        if ((int)(threadIdx.x & 63) == k) e |= bits;
     }
     __device__ __forceinline__ void after(int k, uint32_t what)
     {
-        pa |= 1ull << k;
-        pa_call |= (uint64_t)(what & 1) << k;
-        pa_keep |= (uint64_t)((what >> 1) & 1) << k;
+        const uint32_t bits = KG_EV_RESET_AFTER | ((what & 1u) ? KG_EV_CALL_AFTER : 0u) | ((what & 2u) ? KG_EV_KEEP2_AFTER : 0u);
+        if ((int)(threadIdx.x & 63) == k) e |= bits;
     }
 };
 
@@ -286,12 +285,23 @@ __global__ void merge_before_kernel(const uint32_t *__restrict__ piece_start, co
     if (m && (threadIdx.x & 63) == 0) atomicAdd(n_pieces, (unsigned long long)__popcll(m));
 }
 
+// What calls_wave_kernel reads only where a unit starts or ends (its staging range, its counts, tail event and hand-over byte):
+// one block in device memory (kg_table::d_calls_cold), loaded there.  As kernel arguments these seven pointers held fourteen
+// scalar registers through the chunk loop, whose state machine lives in scalar registers.
+struct CallsCold {
+    kg_call *staged;               // [n_hits / minHits + 1]
+    uint8_t *tail_ev;
+    uint32_t *call_cnt, *first_cnt, *piece_cnt;
+    uint8_t *before_ev;
+    const uint8_t *piece_pair;
+};
+
 // One unit: the records [begin, end) of container c, or up to the first record of the next piece.  calls = the unit's
 // staging range.  Returns the number of CALLs; *tail_out = the container's tail event when the unit reached `end`.
 __device__ __forceinline__ uint32_t walk_unit(const kg_hit *__restrict__ hits, const AggParams &p, uint8_t *acc, uint8_t *vote,
                                               const uint32_t begin, const uint32_t end, const uint32_t c, kg_call *calls,
-                                              const uint32_t *__restrict__ piece_start, const uint8_t *__restrict__ piece_pair,
-                                              const uint32_t pshift, uint8_t *before_ev, uint32_t *tail_out, bool *reached_end)
+                                              const uint32_t *__restrict__ piece_start, const uint32_t pshift,
+                                              const CallsCold *__restrict__ cold, uint32_t *tail_out, bool *reached_end)
 {
     const int lane = threadIdx.x & 63;
     uint32_t stopped_at = kNoPiece;
@@ -341,8 +351,8 @@ __device__ __forceinline__ uint32_t walk_unit(const kg_hit *__restrict__ hits, c
             m_pos = h2.from0InProt; m_fI = h2.fI; m_avg = h2.avgOffFromEnd; m_wt = h2.functionWt;
         }
         uint64_t accmask;
-        uint64_t votes = 0;                          // records of this chunk whose vote counted towards a CALL
-        EvMasks em = {0, 0, 0, 0, 0, 0};
+        bool votes = false;                          // the lane's record of this chunk voted towards a CALL
+        EvBits em = {0};
         ChunkRegs cu;                                // (cu.mask follows accmask at every call)
         cu.base = base; cu.mask = 0; cu.fI = fI; cu.pos = pos; cu.wt = wt;
 
@@ -442,15 +452,8 @@ __device__ __forceinline__ uint32_t walk_unit(const kg_hit *__restrict__ hits, c
             }
         }
         if (lane < n) {
-            uint32_t e = (uint32_t)((accmask >> lane) & 1ull) * KG_EV_ACCEPTED;
-            e |= (uint32_t)((em.pb >> lane) & 1ull) * KG_EV_RESET_BEFORE;
-            e |= (uint32_t)((em.pb_call >> lane) & 1ull) * KG_EV_CALL_BEFORE;
-            e |= (uint32_t)((em.pb_keep >> lane) & 1ull) * KG_EV_KEEP2_BEFORE;
-            e |= (uint32_t)((em.pa >> lane) & 1ull) * KG_EV_RESET_AFTER;
-            e |= (uint32_t)((em.pa_call >> lane) & 1ull) * KG_EV_CALL_AFTER;
-            e |= (uint32_t)((em.pa_keep >> lane) & 1ull) * KG_EV_KEEP2_AFTER;
-            acc[i] = (uint8_t)e;
-            vote[i] = (uint8_t)((votes >> lane) & 1ull);
+            acc[i] = (uint8_t)(em.e | (uint32_t)((accmask >> lane) & 1ull) * KG_EV_ACCEPTED);
+            vote[i] = votes ? 1 : 0;
         }
         carry_pos = rl(pos, n - 1);
         carry_fI = rl(fI, n - 1);
@@ -460,7 +463,7 @@ __device__ __forceinline__ uint32_t walk_unit(const kg_hit *__restrict__ hits, c
         if (stopped_at != kNoPiece) break;
     }
     uint32_t tail = 0;
-    if (stopped_at != kNoPiece && piece_pair[stopped_at >> pshift]) {
+    if (stopped_at != kNoPiece && cold->piece_pair[stopped_at >> pshift]) {
         // the next piece starts at the first record of a pair whose second record fires the pair rule (KGJ:503-508; see
         // piece_starts_kernel): processSetOfHits on the list as it stands -- the pair's two records would be its last members and
         // cast no vote -- after which the reference keeps exactly those two: the next piece's business.  The event bits go
@@ -468,27 +471,27 @@ __device__ __forceinline__ uint32_t walk_unit(const kg_hit *__restrict__ hits, c
         uint32_t bits = 0;
         if (s.cnt > 0) {
             bits = KG_EV_RESET_AFTER | KG_EV_KEEP2_AFTER;
-            uint64_t tail_votes = 0;
+            bool tail_votes = false;
             if (process_set(hits, acc, vote, begin, p, s, pv, ppv, tail_votes, c, calls, false) & 1u) bits |= KG_EV_CALL_AFTER;
-            if ((tail_votes >> lane) & 1ull) vote[pv.base + lane] = 1;
+            if (tail_votes) vote[pv.base + lane] = 1;
         }
-        if (lane == 0) before_ev[stopped_at >> pshift] = (uint8_t)bits;
+        if (lane == 0) cold->before_ev[stopped_at >> pshift] = (uint8_t)bits;
     } else if (stopped_at != kNoPiece) {
         // the next piece's first record lies behind a gap: what the gap rule does there (KGJ:477-484), no carry
         uint32_t bits = 0;
         if (s.cnt > 0) {
             bits = KG_EV_RESET_BEFORE;
             if (s.cnt >= p.min_hits) {
-                uint64_t tail_votes = 0;
+                bool tail_votes = false;
                 if (process_set(hits, acc, vote, begin, p, s, pv, ppv, tail_votes, c, calls, false) & 1u) bits |= KG_EV_CALL_BEFORE;
-                if ((tail_votes >> lane) & 1ull) vote[pv.base + lane] = 1;
+                if (tail_votes) vote[pv.base + lane] = 1;
             }
         }
-        if (lane == 0) before_ev[stopped_at >> pshift] = (uint8_t)bits;
+        if (lane == 0) cold->before_ev[stopped_at >> pshift] = (uint8_t)bits;
     } else if (s.cnt >= p.min_hits) {                                                                // KGJ:511-513
-        uint64_t tail_votes = 0;                     // voters in the last chunk, whose bytes are already stored
+        bool tail_votes = false;                     // voters in the last chunk, whose bytes are already stored
         tail = process_set(hits, acc, vote, begin, p, s, pv, ppv, tail_votes, c, calls, true) & 1u;
-        if ((tail_votes >> lane) & 1ull) vote[pv.base + lane] = 1;
+        if (tail_votes) vote[pv.base + lane] = 1;
     }
     *tail_out = tail;
     *reached_end = stopped_at == kNoPiece;
@@ -500,11 +503,10 @@ __device__ __forceinline__ uint32_t walk_unit(const kg_hit *__restrict__ hits, c
 // Waves behind them: the piece that starts in block u = wave - n_cwaves, if any.  call_cnt[] (the containers' CALL
 // totals) is zeroed by the caller; first_cnt[c] / piece_cnt[u] = the CALLs of a container's first piece / of block u's.
 __global__ __launch_bounds__(256) void calls_wave_kernel(const kg_hit *__restrict__ hits, const int64_t *__restrict__ chs,
-                                                         uint32_t n_cont, AggParams p, uint8_t *acc, uint8_t *vote, uint8_t *tail_ev,
-                                                         uint32_t *call_cnt, uint32_t *first_cnt, kg_call *staged /* [n_hits / minHits + 1] */,
-                                                         uint32_t per_wave, uint32_t n_cwaves, const uint32_t *__restrict__ piece_start,
-                                                         uint32_t pshift, uint32_t n_pblocks, uint32_t *piece_cnt, uint8_t *before_ev,
-                                                         const uint8_t *__restrict__ piece_pair)
+                                                         uint32_t n_cont, AggParams p, uint8_t *acc, uint8_t *vote,
+                                                         uint32_t per_wave, uint32_t n_cwaves,
+                                                         const uint32_t *__restrict__ piece_start, uint32_t pshift, uint32_t n_pblocks,
+                                                         const CallsCold *__restrict__ cold)
 {
     const int lane = threadIdx.x & 63;
     const uint32_t w = (uint32_t)uni((int32_t)(blockIdx.x * 4 + (threadIdx.x >> 6)));
@@ -517,12 +519,12 @@ __global__ __launch_bounds__(256) void calls_wave_kernel(const kg_hit *__restric
         const uint32_t end = (uint32_t)chs[c + 1];
         uint32_t tail;
         bool reached_end;
-        const uint32_t ncalls = walk_unit(hits, p, acc, vote, begin, end, c, staged + begin / (uint32_t)p.min_hits, piece_start, piece_pair,
-                                          pshift, before_ev, &tail, &reached_end);
+        const uint32_t ncalls = walk_unit(hits, p, acc, vote, begin, end, c, cold->staged + begin / (uint32_t)p.min_hits, piece_start, pshift,
+                                          cold, &tail, &reached_end);
         if (lane == 0) {
-            piece_cnt[u] = ncalls;
-            if (ncalls) atomicAdd(&call_cnt[c], ncalls);
-            if (reached_end) tail_ev[c] = (uint8_t)tail;
+            cold->piece_cnt[u] = ncalls;
+            if (ncalls) atomicAdd(&cold->call_cnt[c], ncalls);
+            if (reached_end) cold->tail_ev[c] = (uint8_t)tail;
         }
         return;
     }
@@ -534,8 +536,8 @@ __global__ __launch_bounds__(256) void calls_wave_kernel(const kg_hit *__restric
     const bool mine = (uint32_t)lane < per_wave && c_first + (uint32_t)lane < n_cont;
     if (mine) { my_begin = (uint32_t)chs[c_first + lane]; my_end = (uint32_t)chs[c_first + lane + 1]; }
     if (mine && my_end - my_begin < 2) {
-        first_cnt[c_first + lane] = 0;
-        tail_ev[c_first + lane] = 0;
+        cold->first_cnt[c_first + lane] = 0;
+        cold->tail_ev[c_first + lane] = 0;
         if (my_end != my_begin) { acc[my_begin] = (uint8_t)KG_EV_ACCEPTED; vote[my_begin] = 0; }
     }
     uint64_t todo = __ballot(mine && my_end - my_begin >= 2);
@@ -546,12 +548,12 @@ __global__ __launch_bounds__(256) void calls_wave_kernel(const kg_hit *__restric
         const uint32_t begin = (uint32_t)rl((int32_t)my_begin, ci), end = (uint32_t)rl((int32_t)my_end, ci);
         uint32_t tail;
         bool reached_end;
-        const uint32_t ncalls = walk_unit(hits, p, acc, vote, begin, end, c, staged + begin / (uint32_t)p.min_hits, piece_start, piece_pair,
-                                          pshift, before_ev, &tail, &reached_end);
+        const uint32_t ncalls = walk_unit(hits, p, acc, vote, begin, end, c, cold->staged + begin / (uint32_t)p.min_hits, piece_start, pshift,
+                                          cold, &tail, &reached_end);
         if (lane == 0) {
-            first_cnt[c] = ncalls;
-            if (ncalls) atomicAdd(&call_cnt[c], ncalls);
-            if (reached_end) tail_ev[c] = (uint8_t)tail;
+            cold->first_cnt[c] = ncalls;
+            if (ncalls) atomicAdd(&cold->call_cnt[c], ncalls);
+            if (reached_end) cold->tail_ev[c] = (uint8_t)tail;
         }
     }
 }

@@ -240,7 +240,11 @@ struct kg_table {
     uint32_t m35 = 0;            // floor(2^35 / num_sigs) when 64 <= num_sigs < 2^31 (kg::split_fast), else 0
     uint64_t occupied = 0;
     double stage_ratio = 1.0 / 16;   // staging records per window, grown to the high-water mark
-    size_t scatter_lds[2] = {0, 0};  // dynamic LDS the scatter kernel (DNA / protein) has been allowed so far
+    size_t scatter_lds[2][3] = {};   // dynamic LDS the scatter kernel (DNA / protein; plain / short stream / + progress) has been allowed so far
+    kg::ScatterCold *d_cold = nullptr;          // the scatter pass's cold-path parameter blocks, one per chunk (kg_partition.hpp) ...
+    kg::ScatterCold h_cold[kMaxChunks] = {};    // ... and what they hold: uploaded again only when a scan's blocks differ
+    kg::CallsCold *d_calls_cold = nullptr;      // the same for the CALL pass (kg_aggregate.hpp)
+    kg::CallsCold h_calls_cold = {};
     size_t hist_lds = 48 * 1024;     // ... and the hit histogram kernel (kg_order.hpp)
     size_t place_lds[2] = {48 * 1024, 48 * 1024};   // ... and group_place_kernel<DNA / AA>
     hipEvent_t ev[kEvCount] = {};       // kEv*

@@ -62,9 +62,16 @@ int aggregate_stage(kg_table *t, const kg_params *p, kg_result *res, Scratch &sc
     const uint32_t cpw = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, n_cont / (1u << 17)));
     const uint32_t n_cwaves = (uint32_t)((n_cont + cpw - 1) / cpw);
     if (n_cont) {
+        // what the kernel reads only where a unit ends: a block in device memory.  Its arrays come out of the table's block
+        // cache, so in a run of like scans they do not change and nothing is sent.
+        const kg::CallsCold cold = {d_staged, res->d_tail_ev, d_ccnt, d_first, d_pcnt, d_before, d_ppair};
+        if (!t->d_calls_cold || memcmp(&cold, &t->h_calls_cold, sizeof cold)) {
+            if (!t->d_calls_cold) HIP_TRY(hipMalloc((void **)&t->d_calls_cold, sizeof cold));
+            t->h_calls_cold = cold;
+            HIP_TRY(hipMemcpyAsync(t->d_calls_cold, &t->h_calls_cold, sizeof cold, hipMemcpyHostToDevice, t->stream));
+        }
         hipLaunchKernelGGL(kg::calls_wave_kernel, dim3((n_cwaves + n_pblocks + 3) / 4), dim3(256), 0, t->stream, res->d_hits, res->d_chs,
-                           (uint32_t)n_cont, ap, d_acc, d_vote, res->d_tail_ev, d_ccnt, d_first, d_staged, cpw, n_cwaves, d_pstart,
-                           ag.pshift, n_pblocks, d_pcnt, d_before, d_ppair);
+                           (uint32_t)n_cont, ap, d_acc, d_vote, cpw, n_cwaves, d_pstart, ag.pshift, n_pblocks, t->d_calls_cold);
         if (pieces)
             hipLaunchKernelGGL(kg::merge_before_kernel, dim3((n_pblocks + 255) / 256), dim3(256), 0, t->stream, d_pstart, d_ppair, d_before,
                                n_pblocks, res->d_ev, (unsigned long long *)(d_totals + kTotPieces));

@@ -199,6 +199,42 @@ ChunkView chunk_view(const PartPlan &pl, const PartBuffers &pb, uint32_t c)
     return v;
 }
 
+// The scatter kernel's instantiation: 0 plain, 1 the record stream ends before numSigs (only then can a home slot lie beyond
+// it), 2 the same with KG_F_PROGRESS (the slots beyond the stream are noted).
+int scatter_variant_of(const ScanCtx &cx)
+{
+    return cx.t->limit >= (uint64_t)cx.t->num_sigs ? 0 : cx.d_prog ? 2 : 1;
+}
+template <typename F>
+void scatter_variant(int variant, F &&f)
+{
+    if (variant == 0) f(std::false_type{}, std::false_type{});
+    else if (variant == 1) f(std::true_type{}, std::false_type{});
+    else f(std::true_type{}, std::true_type{});
+}
+
+// The chunks' cold-path parameter blocks of the scatter pass (kg::ScatterCold), in front of the first scatter pass on its
+// stream.  The blocks they point to come out of the table's block cache, so in a run of like scans they do not change and
+// nothing is sent.
+int upload_scatter_cold(const ScanCtx &cx, const PartPlan &pl, const PartBuffers &pb)
+{
+    kg_table *t = cx.t;
+    kg::ScatterCold h[kMaxChunks] = {};
+    for (uint32_t c = 0; c < pl.n_chunks; c++) {
+        uint32_t *ovfc = pb.d_ovfc + kOvfWords * c;
+        h[c].ovf_cursor = ovfc; h[c].ovf_bucket = pb.d_ovf_bucket + (size_t)c * pl.ovf_cap;
+        h[c].ovf_ent = pb.d_ovf_ent + (size_t)c * pl.ovf_cap * kg::kGroup;
+        h[c].lowc_cursor = ovfc + kOvfLowc; h[c].lowc_blocks = pb.d_lowc + pl.clo[c];
+        h[c].ctr = (unsigned long long *)(cx.d_totals + kTotValid); h[c].prog = cx.d_prog;
+        h[c].ovf_cap = pl.ovf_cap;
+    }
+    if (!t->d_cold) HIP_TRY(hipMalloc((void **)&t->d_cold, sizeof h));
+    else if (!memcmp(h, t->h_cold, sizeof h)) return KG_OK;
+    memcpy(t->h_cold, h, sizeof h);
+    HIP_TRY(hipMemcpyAsync(t->d_cold, t->h_cold, sizeof h, hipMemcpyHostToDevice, t->stream));
+    return KG_OK;
+}
+
 // One chunk through scatter (stream) -> low-complexity blocks, tag or index pass (stream2) -> verify, overflow (stream3).
 template <bool AA>
 int chunk_passes(const ScanCtx &cx, const PartPlan &pl, const PartBuffers &pb, const ChunkView &v)
@@ -208,9 +244,13 @@ int chunk_passes(const ScanCtx &cx, const PartPlan &pl, const PartBuffers &pb, c
     unsigned long long *d_ctr = (unsigned long long *)(cx.d_totals + kTotValid);
     const hipStream_t s2 = t->stream2, s3 = t->stream3;
     uint32_t *lowc_cursor = v.ovfc + kOvfLowc, *lowc = pb.d_lowc + v.lo;
-    hipLaunchKernelGGL((kg::part_scatter_kernel<AA>), dim3(pl.n_wg), dim3(kg::kWave * kg::kScatterWaves), pl.scatter_lds, t->stream, cx.d_seq,
-                       cx.d_blocks, v.lo, v.nb, t->limit, (uint32_t)t->num_sigs, t->m35, pl.shift, pl.buckets,
-                       pl.cap, v.ent, v.fill, v.ovfc, pl.ovf_cap, v.ovf_bucket, v.ovf_ent, lowc_cursor, lowc, d_ctr, d_prog, pl.scatter_prio);
+    const uint32_t limit32 = (uint32_t)std::min<uint64_t>(t->limit, 0xFFFFFFFFull);         // slots are < num_sigs < 2^31
+    scatter_variant(scatter_variant_of(cx), [&](auto is_short, auto prog) {
+        constexpr bool SHORT = decltype(is_short)::value, PROG = decltype(prog)::value;
+        hipLaunchKernelGGL((kg::part_scatter_kernel<AA, SHORT, PROG>), dim3(pl.n_wg), dim3(kg::kWave * kg::kScatterWaves), pl.scatter_lds,
+                           t->stream, cx.d_seq, cx.d_blocks, v.lo, v.nb, limit32, (uint32_t)t->num_sigs, t->m35, pl.shift, pl.buckets, pl.cap,
+                           v.ent, v.fill, t->d_cold + v.c, pl.scatter_prio);
+    });
     HIP_TRY(hipEventRecord(t->pev[kPevChunk + 2 * v.c], t->stream));
     HIP_TRY(hipStreamWaitEvent(s2, t->pev[kPevChunk + 2 * v.c], 0));
     // the low-complexity blocks the scatter pass set aside (usually none: every workgroup reads the count and
@@ -339,9 +379,15 @@ int part_allocate(ScanCtx &cx, const PartPlan &pl, PartBuffers &pb)
         t->hist_lds = groups_stride * 4u;
     }
     if ((rc = sc.get(&pb.d_pc, kPcWords))) return rc;
-    if (t->scatter_lds[AA ? 1 : 0] < pl.scatter_lds) {         // once per table (and geometry): the call costs tens of microseconds
-        HIP_TRY(hipFuncSetAttribute((const void *)kg::part_scatter_kernel<AA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.scatter_lds));
-        t->scatter_lds[AA ? 1 : 0] = pl.scatter_lds;
+    const int sv = scatter_variant_of(cx);
+    if (t->scatter_lds[AA ? 1 : 0][sv] < pl.scatter_lds) {     // once per table (and geometry): the call costs tens of microseconds
+        hipError_t e = hipSuccess;
+        scatter_variant(sv, [&](auto is_short, auto prog) {
+            e = hipFuncSetAttribute((const void *)kg::part_scatter_kernel<AA, decltype(is_short)::value, decltype(prog)::value>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.scatter_lds);
+        });
+        HIP_TRY(e);
+        t->scatter_lds[AA ? 1 : 0][sv] = pl.scatter_lds;
     }
     return KG_OK;
 }
@@ -387,6 +433,7 @@ int scan_partitioned(ScanCtx &cx, const PartPlan &pl, bool &done)
                                {pb.d_next, (uint64_t)pl.next_stride * n_chunks},
                                {pb.d_ghist, (uint64_t)pl.groups_stride * n_chunks}})))
             return rc;
+        if ((rc = upload_scatter_cold(cx, pl, pb))) return rc;
         HIP_TRY(hipEventRecord(t->pev[kPevFork], t->stream));               // fork: stream2 starts behind the clears
         HIP_TRY(hipStreamWaitEvent(t->stream2, t->pev[kPevFork], 0));
         HIP_TRY(hipStreamWaitEvent(t->stream3, t->pev[kPevFork], 0));

@@ -341,6 +341,8 @@ void kg_table_close(kg_table *t)
     if (t->d_tags) (void)hipFree(t->d_tags);
     if (t->d_bidx) (void)hipFree(t->d_bidx);
     if (t->d_hbits) (void)hipFree(t->d_hbits);
+    if (t->d_cold) (void)hipFree(t->d_cold);
+    if (t->d_calls_cold) (void)hipFree(t->d_calls_cold);
     t->cache.release_all();
     t->pins.release_all();
     if (t->h_pin) (void)hipHostFree(t->h_pin);

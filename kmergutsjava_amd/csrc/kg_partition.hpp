@@ -12,7 +12,10 @@
 //   part_scatter_kernel  : encode every window once; entry -> 16-entry (128-byte) write-combining buffer of its
 //                          bucket in the workgroup's LDS -> the workgroup's over-allocated region of the bucket
 //                          (no counting pass, no per-entry global atomics, no workgroup barrier in the main loop;
-//                          overflow list for skewed inputs)
+//                          overflow list for skewed inputs).  Instantiated by what the table's record stream allows
+//                          (<AA, SHORT, PROG>); what only its cold paths read -- overflow and low-complexity lists,
+//                          counters, progress words -- comes from a parameter block in device memory (ScatterCold), and
+//                          those paths are functions of their own: the loop holds no scalar register for them
 //   lowc_blocks_kernel   : the blocks the scatter pass set aside (low-complexity sequence: most windows in one or two
 //                          buckets): their entries are appended to the regions in whole same-bucket sets
 //   bucket_tag_kernel    : persistent workgroups; group x = blockIdx % 8 (XCD under round-robin placement,
@@ -44,7 +47,11 @@ constexpr int kMaxBuckets = 1024;
 // waves run beside a scatter workgroup (16 waves, 4 per SIMD) is the SIMD's 512 VGPRs: 4 x 104 (99 rounded to the
 // allocation granule of 8) left room for ONE tag wave of 72 (66) per SIMD -- the tag pass ran beside a scatter pass with a
 // quarter of its waves.  amdgpu_waves_per_eu(5) holds the scatter kernel to 96 VGPRs (no spill) and the tag kernel's slot
-// arithmetic in 32 bits brings it to 61: 4 x 96 + 2 x 64 = 512, two tag waves per SIMD.
+// arithmetic in 32 bits brings it to 61: 4 x 96 + 2 x 64 = 512, two tag waves per SIMD.  (The index pass: 32 VGPRs, four of its
+// waves per SIMD: 4 x 96 + 4 x 32 = 512.)  Scalar registers are a budget too: a kernel has 102 of them, and one that wants more
+// moves the rest through lanes of a VGPR (v_readlane / v_writelane plus hazard waits) on the wave's issue path -- the scatter
+// kernel did, with 31 (21 arguments, two block descriptors, six 64-bit row masks), until its cold paths' arguments went into
+// ScatterCold; it now uses 83 and spills none.  tests/test_kernel_resources.py holds all of these to the compiler's report.
 #ifndef KG_SCATTER_WPE
 #define KG_SCATTER_WPE 5
 #endif
@@ -133,14 +140,88 @@ __device__ __forceinline__ void store_entry_pair(uint64_t *dst, const ulonglong2
 #endif
 }
 
-template <bool AA>
+// What only the cold paths of the scatter pass read (overflow list, low-complexity list, counters, progress words): one block
+// per chunk in device memory (kg_table::d_cold), loaded where a cold path is entered.  As kernel arguments these eight values
+// held 15 scalar registers through the whole loop; seq, blocks, ent, fill and the geometry -- what the loop reads every trip --
+// stay direct arguments (behind a struct they become flat loads on the hot path: DESIGN section 5).
+struct ScatterCold {
+    uint32_t *ovf_cursor;          // [0] groups on the overflow list, [1] low-complexity blocks, [2] sticky "protocol failure" word
+    uint32_t *ovf_bucket;
+    uint64_t *ovf_ent;
+    uint32_t *lowc_cursor;         // [0] count
+    uint32_t *lowc_blocks;
+    unsigned long long *ctr;
+    Progress *prog;                // KG_F_PROGRESS, else null
+    uint32_t ovf_cap, pad;
+};
+static_assert(sizeof(ScatterCold) == 64, "ScatterCold is one 64-byte line");
+
+// Where a flushed group goes: an entry index in ent, or with kDstOvf set in ovf_ent; kDstNone: the lane flushes nothing;
+// kDstDropped: the overflow list is full (the host falls back to direct probing).
+constexpr unsigned long long kDstOvf = 1ull << 62, kDstNone = ~0ull, kDstDropped = ~0ull - 1;
+
+// ---- cold paths of part_scatter_kernel ----
+// The regions of the lanes in movf are full: their groups go to the overflow list, one atomic per wave.
+__device__ __attribute__((noinline, cold)) unsigned long long scatter_overflow_groups(const ScatterCold *__restrict__ cold,
+                                                                                     unsigned long long movf, bool to_ovf, uint32_t b,
+                                                                                     unsigned long long dst)
+{
+    const int lane = threadIdx.x & 63;
+    uint32_t og = 0;
+    if (lane == 0) og = atomicAdd(cold->ovf_cursor, (uint32_t)__popcll(movf));
+    og = (uint32_t)__builtin_amdgcn_readfirstlane((int)og);
+    if (to_ovf) {
+        const uint32_t g = og + (uint32_t)__popcll(movf & ((1ull << lane) - 1ull));
+        if (g < cold->ovf_cap) { cold->ovf_bucket[g] = b; dst = kDstOvf | ((uint64_t)g * kGroup); }
+        else dst = kDstDropped;
+    }
+    return dst;
+}
+// A low-complexity block is set aside for lowc_blocks_kernel.
+__device__ __attribute__((noinline, cold)) void scatter_set_aside(const ScatterCold *__restrict__ cold, uint32_t block)
+{
+    if ((threadIdx.x & 63) == 0) cold->lowc_blocks[atomicAdd(cold->lowc_cursor, 1u)] = block;
+}
+// The insert protocol failed (never expected): sticky word, the host falls back to the direct strategy (kg_stats.fallback == 2).
+__device__ __attribute__((noinline, cold)) void scatter_protocol_failure(const ScatterCold *__restrict__ cold)
+{
+    if ((threadIdx.x & 63) == 0) atomicOr(cold->ovf_cursor + 2, 1u);         // (ovf_cursor[0] stays a group count)
+}
+// Sixteen bytes of a group go to their place: to the region (the usual case) or to the overflow list.
+__device__ __forceinline__ void store_group_part(uint64_t *__restrict__ ent, const ScatterCold *__restrict__ cold, unsigned long long to,
+                                                 uint32_t sub, const ulonglong2 &v)
+{
+    if (__builtin_expect((to & kDstOvf) != 0, 0)) store_entry_pair(cold->ovf_ent + (to & ~kDstOvf) + 2 * sub, v);
+    else store_entry_pair(ent + to + 2 * sub, v);
+}
+// KG_F_PROGRESS: a query k-mer's home slot lies behind the end of the record stream.
+__device__ __attribute__((noinline, cold)) void scatter_note_beyond(const ScatterCold *__restrict__ cold, uint32_t slot)
+{
+    progress_note_beyond(cold->prog, slot);
+}
+
+// The fields of a block descriptor that are needed once its characters are requested (row_index, window_key, row_halves): the
+// next block travels through the loop as these four words, not as a second whole BlockDesc.
+struct BlockRows { uint32_t len, j, nk, ibase; };
+__device__ __forceinline__ BlockRows rows_of(const BlockDesc &bd) { return BlockRows{bd.len, bd.j, bd.nk, bd.ibase}; }
+__device__ __forceinline__ BlockDesc desc_of(const BlockRows &r)
+{
+    BlockDesc bd;
+    bd.soff = 0; bd.len = r.len; bd.j = r.j; bd.nk = r.nk; bd.ibase = r.ibase; bd.seq = 0; bd.pad = 0;
+    return bd;
+}
+
+// SHORT: the record stream ends before numSigs (a truncated table file: limit32 < num_sigs).  Only then can a home slot lie
+// beyond the stream; the per-row compare, the ran-off flag and (PROG = KG_F_PROGRESS) the progress note exist in these
+// instantiations only.  PROG implies SHORT (with a whole stream the scatter pass has nothing to note).
+template <bool AA, bool SHORT = false, bool PROG = false>
 __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_scatter_kernel(
     const uint8_t *__restrict__ seq, const BlockDesc *__restrict__ blocks, uint32_t block_lo, uint32_t n_blocks /* of this launch */,
-    uint64_t limit, uint32_t num_sigs /* 64 <= num_sigs < 2^31 */, uint32_t m35, uint32_t shift, uint32_t n_buckets, uint32_t cap,
-    uint64_t *__restrict__ ent, uint32_t *__restrict__ fill, uint32_t *ovf_cursor, uint32_t ovf_cap, uint32_t *__restrict__ ovf_bucket,
-    uint64_t *__restrict__ ovf_ent, uint32_t *lowc_cursor /* [0] count */, uint32_t *__restrict__ lowc_blocks, unsigned long long *ctr,
-    Progress *prog /* KG_F_PROGRESS, else null */, uint32_t insert_prio /* wave priority of the insert phase (0..3) */)
+    uint32_t limit32 /* min(limit, 2^32 - 1); SHORT only */, uint32_t num_sigs /* 64 <= num_sigs < 2^31 */, uint32_t m35, uint32_t shift,
+    uint32_t n_buckets, uint32_t cap, uint64_t *__restrict__ ent, uint32_t *__restrict__ fill, const ScatterCold *__restrict__ cold,
+    uint32_t insert_prio /* wave priority of the insert phase (0..3) */)
 {
+    static_assert(SHORT || !PROG, "PROG implies SHORT");
     constexpr int ROWS = AA ? 1 : 6;
     typedef typename WaveLds<AA>::type Enc;
     constexpr size_t enc_bytes = (sizeof(Enc) + 15) & ~(size_t)15;
@@ -158,83 +239,38 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
     uint32_t *wrel = cnt + n_buckets;                 // entries already written to this workgroup's region of bucket b
     uint32_t *written = wrel + n_buckets;             // entries of the current group whose LDS store has been issued
     const uint32_t w = blockIdx.x, n_wg = gridDim.x;
-    const uint32_t limit32 = limit < 0xFFFFFFFFull ? (uint32_t)limit : 0xFFFFFFFFu;      // slots are < num_sigs < 2^31
     for (uint32_t b = threadIdx.x; b < n_buckets; b += blockDim.x) { cnt[b] = 0; wrel[b] = 0; written[b] = 0; }
     encode_init<AA>(enc_tables, threadIdx.x, blockDim.x);
     __syncthreads();
 
-    // Flush: wave v owns the buckets [v * per_wave, (v + 1) * per_wave); one lane looks at one bucket; the wave then
-    // writes its full buffers eight at a time, eight lanes per 128-byte group (16 bytes each: one coalesced line per
-    // group instead of eight scattered 16-byte stores by one lane).  min_fill = kGroup: full buffers only;
-    // min_fill = 1: every non-empty buffer, padded with fillers (end of the kernel).
-    const uint32_t per_wave = (n_buckets + kScatterWaves - 1) / kScatterWaves;
-    auto flush_wave = [&](uint32_t min_fill) {
-        for (uint32_t b0 = (uint32_t)wave * per_wave; b0 < min((uint32_t)(wave + 1) * per_wave, n_buckets); b0 += 64) {
-            const uint32_t b = b0 + (uint32_t)lane;
-            const bool mine = b < min((uint32_t)(wave + 1) * per_wave, n_buckets);
-            const uint32_t c = mine ? cnt[b] : 0u;
-            unsigned long long dst_off = ~0ull;                       // entry index in ent (bit 62: in ovf_ent)
-            if (c >= min_fill && c > 0) {
-                if (c < kGroup)
-                    for (uint32_t k = c; k < kGroup; k++) buf[(size_t)b * kGroup + k] = kEntInvalid;
-                const uint32_t rel = wrel[b];
-                if (rel + kGroup <= cap) {
-                    dst_off = ((uint64_t)b * n_wg + w) * cap + rel;
-                    wrel[b] = rel + kGroup;
-                } else {
-                    const uint32_t g = atomicAdd(ovf_cursor, 1u);
-                    if (g < ovf_cap) { ovf_bucket[g] = b; dst_off = (1ull << 62) | ((uint64_t)g * kGroup); }
-                    else dst_off = ~0ull - 1;                         // dropped (the host falls back to direct probing)
-                }
-                cnt[b] = 0;
-            }
-            unsigned long long m = __ballot(dst_off != ~0ull);
-            wave_sync();                                             // the fillers above are read by other lanes below
-            while (m) {
-                // the next (up to) eight flushing lanes; lane group g = lane / 8 takes the g-th of them
-                int src_lane = -1;
-                unsigned long long mm = m;
-#pragma unroll
-                for (int g = 0; g < 8; g++) {
-                    const int ln = mm ? __builtin_ctzll(mm) : -1;
-                    if (mm) mm &= mm - 1;
-                    if ((lane >> 3) == g) src_lane = ln;
-                }
-                m = mm;
-                const int sl = src_lane < 0 ? 0 : src_lane;
-                const uint32_t fb = (uint32_t)__shfl((int)b, sl);
-                const unsigned long long off = __shfl(dst_off, sl);
-                if (src_lane >= 0 && off != ~0ull - 1) {
-                    const uint32_t sub = (uint32_t)lane & 7u;
-                    const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(buf + (size_t)fb * kGroup + 2 * sub);
-                    uint64_t *base = (off >> 62) & 1 ? ovf_ent + (off & ~(1ull << 62)) : ent + off;
-                    store_entry_pair(base + 2 * sub, v);
-                }
-            }
-        }
-    };
-
     uint32_t n_valid = 0;                             // per lane: <= 6 x the wave's blocks
-    bool ran_off = false;
+    bool ran_off = false;                             // (SHORT)
     const uint32_t n_iter = (n_blocks + n_wg * kScatterWaves - 1) / (n_wg * kScatterWaves);
     // the next block's descriptor and characters are fetched while the current block is encoded
-    BlockDesc bd_next;
+    BlockRows rows_next = {0, 0, 0, 0};
     uint32_t raw_next[4] = {0, 0, 0, 0};
     {
         const uint32_t it0 = w * kScatterWaves + (uint32_t)wave;
-        if (it0 < n_blocks) { bd_next = blocks[block_lo + it0]; load_block_chars<AA>(seq, bd_next, lane, raw_next); }
+        if (it0 < n_blocks) {
+            const BlockDesc bd0 = blocks[block_lo + it0];
+            load_block_chars<AA>(seq, bd0, lane, raw_next);
+            rows_next = rows_of(bd0);
+        }
     }
     constexpr int RG = AA ? 1 : KG_SCATTER_RG;        // rows per group
     static_assert(ROWS % RG == 0, "KG_SCATTER_RG must divide 6");
     for (uint32_t iter = 0; iter < n_iter; iter++) {
         const uint32_t it = (iter * n_wg + w) * kScatterWaves + (uint32_t)wave;      // wave-uniform
-        BlockDesc bd;
+        const BlockDesc bd = desc_of(rows_next);
         const bool have = it < n_blocks;
         if (have) {
-            bd = bd_next;
             uint32_t raw[4] = {raw_next[0], raw_next[1], raw_next[2], raw_next[3]};
             const uint32_t itn = it + n_wg * kScatterWaves;
-            if (itn < n_blocks) { bd_next = blocks[block_lo + itn]; load_block_chars<AA>(seq, bd_next, lane, raw_next); }
+            if (itn < n_blocks) {
+                const BlockDesc bdn = blocks[block_lo + itn];
+                load_block_chars<AA>(seq, bdn, lane, raw_next);
+                rows_next = rows_of(bdn);
+            }
             encode_chars<AA>(l, enc_tables, raw, lane);
         }
         bool lowc = false;                                                  // (wave-uniform) the block was set aside
@@ -242,7 +278,7 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
         for (int g0 = 0; g0 < ROWS; g0 += RG) {
         uint64_t e[RG];
         uint32_t bk[RG];
-        uint32_t pend = 0, vmask = 0;
+        uint32_t pend = 0, nv = 0;                                          // rows to insert; query k-mers (KGJ:913-920) of the group
         if (have && !lowc) {
 #pragma unroll
             for (int k = 0; k < RG; k++) {
@@ -250,9 +286,14 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
                 uint32_t hi, lo, q;
                 bool valid = row_halves<AA>(l, r, lane, bd, &hi, &lo);
                 const uint32_t slot = split_fast(hi, lo, num_sigs, m35, &q);
-                if (valid) vmask |= 1u << k;                            // query k-mers (KGJ:913-920), counted per block below
-                if (valid && slot >= limit32) { ran_off = true; if (prog) progress_note_beyond(prog, slot); }   // (truncated table file)
-                valid = valid && slot < limit32;                        // beyond the stream: never probed
+                if (valid) nv++;
+                if constexpr (SHORT) {
+                    if (valid && slot >= limit32) {                         // (truncated table file)
+                        ran_off = true;
+                        if constexpr (PROG) scatter_note_beyond(cold, slot);
+                    }
+                    valid = valid && slot < limit32;                        // beyond the stream: never probed
+                }
                 bk[k] = slot >> shift;
                 const uint32_t low = (q << shift) | (slot & ((1u << shift) - 1u));
                 const uint32_t id = window_key<AA>(bd, block_lo + it, r, lane);
@@ -269,9 +310,9 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
                 const unsigned long long m0 = __ballot((pend & 1u) != 0);
                 if (__popcll(m0) >= 32) {
                     const uint32_t lead0 = (uint32_t)__builtin_amdgcn_readlane((int)bk[0], __builtin_ctzll(m0));
-                    if (__popcll(__ballot((pend & 1u) && bk[0] == lead0)) >= 24) {
-                        if (lane == 0) lowc_blocks[atomicAdd(lowc_cursor, 1u)] = block_lo + it;
-                        vmask = 0;                                         // counted by lowc_blocks_kernel
+                    if (__builtin_expect(__popcll(__ballot((pend & 1u) && bk[0] == lead0)) >= 24, 0)) {
+                        scatter_set_aside(cold, block_lo + it);
+                        nv = 0;                                            // counted by lowc_blocks_kernel
                         pend = 0;
                         lowc = true;
                         if (RG != ROWS) wave_sync();                       // (the later row groups are skipped)
@@ -279,7 +320,7 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
                 }
             }
         }
-        n_valid += (uint32_t)__popc(vmask);
+        n_valid += nv;
         // Insert without workgroup barriers.  A bucket's buffer is a 16-entry group with two counters:
         //   cnt[b]      tickets: atomicAdd gives the entry's place; >= 16 means "full, try again"
         //   written[b]  stores issued; the lane whose increment makes it 16 owns the group: it (with seven helper
@@ -323,7 +364,7 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
 #pragma unroll
                 for (int r = 1; r < RG; r++)
                     if (r0 == r) b = bk[r];
-                unsigned long long dst_off = ~0ull;                    // entry index in ent (bit 62: in ovf_ent)
+                unsigned long long dst = kDstNone;
                 bool to_ovf = false;
                 if (has) {
                     done &= done - 1;
@@ -331,23 +372,14 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
                     if (rel + kGroup <= cap) {
                         // (b * n_wg + w < 2^18 and cap < 2^24: 24-bit multiplies, full rate; the plain 64-bit expression
                         //  compiles to three quarter-rate v_mad_u64_u32 per flush pass)
-                        dst_off = mul24_wide(b * n_wg + w, cap) + rel;
+                        dst = mul24_wide(b * n_wg + w, cap) + rel;
                         wrel[b] = rel + kGroup;
                     } else {
                         to_ovf = true;
                     }
                 }
                 const unsigned long long movf = __ballot(to_ovf);      // region full: overflow list, one atomic per pass
-                if (movf) {
-                    uint32_t og = 0;
-                    if (lane == 0) og = atomicAdd(ovf_cursor, (uint32_t)__popcll(movf));
-                    og = (uint32_t)__builtin_amdgcn_readfirstlane((int)og);
-                    if (to_ovf) {
-                        const uint32_t g = og + (uint32_t)__popcll(movf & ((1ull << lane) - 1ull));
-                        if (g < ovf_cap) { ovf_bucket[g] = b; dst_off = (1ull << 62) | ((uint64_t)g * kGroup); }
-                        else dst_off = ~0ull - 1;                     // dropped (the host falls back to direct probing)
-                    }
-                }
+                if (__builtin_expect(movf != 0, 0)) dst = scatter_overflow_groups(cold, movf, to_ovf, b, dst);
                 // eight lanes copy one group; lane group g = lane / 8 serves the flushing lane of rank g + 8 * pass.
                 // rank -> lane goes through 64 bytes of the wave's (idle) encode scratch instead of a scalar bit loop
                 uint8_t *rank_lane = reinterpret_cast<uint8_t *>(&l);
@@ -359,12 +391,11 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
                     const bool serve = want < n_flush;
                     const int sl = serve ? (int)rank_lane[want] : 0;
                     const uint32_t fb = (uint32_t)__shfl((int)b, sl);
-                    const unsigned long long off = __shfl(dst_off, sl);
-                    if (serve && off != ~0ull - 1) {
+                    const unsigned long long to = __shfl(dst, sl);
+                    if (serve && to != kDstDropped) {
                         const uint32_t sub = (uint32_t)lane & 7u;
                         const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(buf + (size_t)fb * kGroup + 2 * sub);
-                        uint64_t *base = (off >> 62) & 1 ? ovf_ent + (off & ~(1ull << 62)) : ent + off;
-                        store_entry_pair(base + 2 * sub, v);
+                        store_group_part(ent, cold, to, sub, v);
                     }
                 }
                 wave_sync();                                           // the copies above read buf[b] before it reopens
@@ -379,19 +410,19 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
 #pragma unroll
                 for (int r = 1; r < RG; r++)
                     if (rp == r) pb = bk[r];
-                const volatile uint32_t *pc = &cnt[pb];
+                // (a relaxed load of the LDS word itself: read again at every poll, and never through a generic pointer)
                 for (uint32_t polls = 0; polls < 64; polls++) {
-                    if (__ballot(pend != 0 && *pc < kGroup)) break;
+                    if (__ballot(pend != 0 && __hip_atomic_load(&cnt[pb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < kGroup)) break;
                     __builtin_amdgcn_s_sleep(2);
                 }
             }
             // Never expected (see above).  The second test keeps a ticket counter far from wrapping round to zero,
-            // which would hand out the slots of a full buffer a second time.
-            bool runaway = false;
+            // which would hand out the slots of a full buffer a second time (kGroup, a row that drew nothing, is below it).
+            uint32_t at_max = at[0];
 #pragma unroll
-            for (int r = 0; r < RG; r++) runaway = runaway || (at[r] != kGroup && at[r] >= (1u << 28));
-            if (++spins > (1u << 20) || __ballot(runaway)) {
-                if (lane == 0) atomicOr(ovf_cursor + 2, 1u);           // sticky "protocol failure" word (ovf_cursor stays a group count)
+            for (int r = 1; r < RG; r++) at_max = max(at_max, at[r]);
+            if (__builtin_expect(++spins > (1u << 20) || __ballot(at_max >= (1u << 28)), 0)) {
+                scatter_protocol_failure(cold);
                 break;
             }
         }
@@ -399,13 +430,58 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
         }   // row group
     }
     __syncthreads();
-    // partial groups, padded with fillers
-    flush_wave(1u);
+    // Partial groups, padded with fillers: wave v owns the buckets [v * per_wave, (v + 1) * per_wave); one lane looks at one
+    // bucket; the wave then writes its non-empty buffers eight at a time, eight lanes per 128-byte group (16 bytes each: one
+    // coalesced line per group instead of eight scattered 16-byte stores by one lane).
+    const uint32_t per_wave = (n_buckets + kScatterWaves - 1) / kScatterWaves;
+    const uint32_t b_end = min((uint32_t)(wave + 1) * per_wave, n_buckets);
+    for (uint32_t b0 = (uint32_t)wave * per_wave; b0 < b_end; b0 += 64) {
+        const uint32_t b = b0 + (uint32_t)lane;
+        const uint32_t c = b < b_end ? cnt[b] : 0u;
+        unsigned long long dst = kDstNone;
+        bool to_ovf = false;
+        if (c > 0) {
+            for (uint32_t k = c; k < kGroup; k++) buf[(size_t)b * kGroup + k] = kEntInvalid;
+            const uint32_t rel = wrel[b];
+            if (rel + kGroup <= cap) {
+                dst = ((uint64_t)b * n_wg + w) * cap + rel;
+                wrel[b] = rel + kGroup;
+            } else {
+                to_ovf = true;
+            }
+            cnt[b] = 0;
+        }
+        const unsigned long long movf = __ballot(to_ovf);
+        if (movf) dst = scatter_overflow_groups(cold, movf, to_ovf, b, dst);
+        unsigned long long m = __ballot(dst != kDstNone);
+        wave_sync();                                             // the fillers above are read by other lanes below
+        while (m) {
+            // the next (up to) eight flushing lanes; lane group g = lane / 8 takes the g-th of them
+            int src_lane = -1;
+            unsigned long long mm = m;
+#pragma unroll
+            for (int g = 0; g < 8; g++) {
+                const int ln = mm ? __builtin_ctzll(mm) : -1;
+                if (mm) mm &= mm - 1;
+                if ((lane >> 3) == g) src_lane = ln;
+            }
+            m = mm;
+            const int sl = src_lane < 0 ? 0 : src_lane;
+            const uint32_t fb = (uint32_t)__shfl((int)b, sl);
+            const unsigned long long to = __shfl(dst, sl);
+            if (src_lane >= 0 && to != kDstDropped) {
+                const uint32_t sub = (uint32_t)lane & 7u;
+                const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(buf + (size_t)fb * kGroup + 2 * sub);
+                store_group_part(ent, cold, to, sub, v);
+            }
+        }
+    }
     __syncthreads();
     for (uint32_t b = threadIdx.x; b < n_buckets; b += blockDim.x) fill[(uint64_t)b * n_wg + w] = wrel[b];
     for (int off = 32; off > 0; off >>= 1) n_valid += __shfl_down(n_valid, off);
+    unsigned long long *ctr = cold->ctr;
     if (lane == 0 && n_valid) atomicAdd(&ctr[0], (unsigned long long)n_valid);
-    flush_ran_off(ran_off, ctr, lane);
+    if constexpr (SHORT) flush_ran_off(ran_off, ctr, lane);
 }
 
 // ---------------------------------------------------------------------------------------
