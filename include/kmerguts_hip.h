@@ -8,6 +8,7 @@
  * (ctypes) bindings that call these are shown in INTEGRATION.md.  Beyond the reference, the library also makes the
  * tables it reads: kg_table_build* places a signature list the way the lookup finds it, kg_table_save writes a resident
  * table back to kmer.table.mem_map[.gz], and kg_signatures_derive* makes that list from annotated proteins.
+ * kg_table_merge_signatures* unites a resident table with new signatures (and exports a table's own).
  * kg_result_assign / kg_assign_calls turn the CALL records of an -a scan into one function per protein.
  * kg_result_regions / kg_regions_calls merge the CALL records of a DNA scan into function regions in contig coordinates.
  * kg_regionset_orfs / kg_orfs_regions extend every region to its open reading frame and extract the translated protein.
@@ -285,6 +286,73 @@ const kg_signature *kg_sigset_device(const kg_sigset *s);
 int kg_sigset_copy(const kg_sigset *s, int64_t first, int64_t count, kg_signature *dst);
 int kg_sigset_stats(const kg_sigset *s, kg_derive_stats *out);
 void kg_sigset_free(kg_sigset *s);
+
+/* ---- merging: a resident table plus new signatures -> the signatures of the united table (kernels: kg_merge.hpp) ----
+ *
+ * The reference only reads a table; this rule is the project's own.  It closes the loop scan -> cluster -> derive: the new
+ * signatures go into the table the genome was scanned with, instead of into a table of their own.  Integers only: the 24 record
+ * bytes are moved, never reinterpreted.
+ *   Base set B.  B is every resident record j < kg_table_records(base) with 0 <= kmer < 20^8, with its bytes unchanged.  Records
+ *   with kmer < 0 or kmer == 20^8 are occupied for the reference but can never be found.  They are left out and counted in
+ *   base_ignored.  Empty records (kmer > 20^8) are neither.  B includes records the reference's lookup could not reach, for
+ *   example one in front of its home slot: the merge reads the records, it does not walk them.  Tables made by kg_table_build*
+ *   have none.
+ *   New set N.  N is the n inputs in any order.  function_index is replaced by fn_map[function_index] when fn_map is non-null,
+ *   and otu_index by otu_map[otu_index] likewise.  With a null map the field is kept.  The maps are host arrays of n_fn and
+ *   n_otu entries.
+ *   Result U.
+ *     A k-mer only in B gives B's record.
+ *     A k-mer only in N gives N's mapped record.  These are counted in added.
+ *     A k-mer in both is a conflict, resolved by on_conflict: KG_MERGE_KEEP gives the base's record, KG_MERGE_REPLACE the new
+ *     record, KG_MERGE_DROP the base's record if both name the same function, else neither.  The function comparison is made
+ *     after mapping.
+ *     replaced counts the conflicts where the new record won.  dropped counts the conflicts where neither survived.
+ *     merged = |U|.
+ *   Output: a kg_sigset in ascending k-mer order, so kg_sigset_device, kg_sigset_copy and kg_table_build_device take it as it is.
+ *   For such a set kg_sigset_stats gives zeros except signatures, and kg_sigset_merge_stats gives the counts above (KG_ERR_ARG
+ *   for a derived set).  n = 0 is the table's export.  The output depends only on B, N, the maps and the policy: not on the input
+ *   order, launch geometry or scheduling.
+ * Errors, raised in this order:
+ *   1. KG_ERR_ARG: null table, out or params; a bad policy or reserved != 0; n < 0; a null array with n > 0; a map with a
+ *      negative length; an unaligned device array.
+ *   2. KG_ERR_BUSY: a kg_scan* is in flight on base.
+ *   3. KG_ERR_LIMIT: kg_table_records(base) >= 2^32, or |B| + n >= 2^32.
+ *   4. KG_ERR_ARG: a new k-mer outside [0, 20^8).  The message names the smallest such input index, in kg_table_build's words.
+ *   5. KG_ERR_ARG: a function_index outside [0, n_fn) with a map given, then the same for otu_index.  The message names the
+ *      smallest such input index.
+ *   6. KG_ERR_ARG: a k-mer twice in N.  The message names the smallest such k-mer.
+ *   7. KG_ERR_ARG: a k-mer twice in B, named likewise.
+ *   8. KG_ERR_NOMEM.
+ * base is not modified.  Scratch (about 24 bytes per record of B and N, plus the host input's 24 per signature) comes from the
+ * base table's block cache, so KG_TEST_FAIL_ALLOC applies.  It goes back to the driver before the call returns, together with
+ * the blocks the table's earlier scans left in the cache, and kg_table_live_device_bytes(base) is what it was before the call.
+ * The set's own array is owned by the set, as for a derived set.
+ * kg_table_merge_signatures reads a host array (pageable or pinned), uploaded through pinned pieces;
+ * kg_table_merge_signatures_device an 8-byte aligned device array, complete before the call (the device is synchronised once). */
+#define KG_MERGE_KEEP    0   /* a k-mer in both: the base's record                                   */
+#define KG_MERGE_REPLACE 1   /* ... the new record                                                   */
+#define KG_MERGE_DROP    2   /* ... the base's record if both name the same function, else neither   */
+typedef struct kg_merge_params { int32_t on_conflict; int32_t reserved; } kg_merge_params;
+typedef struct kg_merge_stats {
+    int64_t base;                    /* |B|                                                           */
+    int64_t base_ignored;            /* resident records with kmer < 0 or kmer == 20^8                */
+    int64_t added_in;                /* n                                                             */
+    int64_t added;                   /* k-mers only in N                                              */
+    int64_t conflicts;               /* k-mers in both                                                */
+    int64_t conflicts_same_function; /* ... whose two records name the same function after mapping    */
+    int64_t replaced;                /* conflicts the new record won (KG_MERGE_REPLACE: all)          */
+    int64_t dropped;                 /* conflicts neither record survived (KG_MERGE_DROP)             */
+    int64_t merged;                  /* |U|                                                           */
+    float   ms_extract;              /* the pass over the table and the new signatures' keys          */
+    float   ms_sort;                 /* the sort of the |B| + n pairs (and the call's error read-back) */
+    float   ms_resolve;              /* neighbour compare, prefix sum, the set's allocation, gather   */
+    float   ms_total;
+} kg_merge_stats;
+int kg_table_merge_signatures(kg_table *base, const kg_merge_params *p, const kg_signature *sigs, int64_t n, const int32_t *fn_map,
+                              int64_t n_fn, const int32_t *otu_map, int64_t n_otu, kg_sigset **out);
+int kg_table_merge_signatures_device(kg_table *base, const kg_merge_params *p, const kg_signature *d_sigs, int64_t n,
+                                     const int32_t *fn_map, int64_t n_fn, const int32_t *otu_map, int64_t n_otu, kg_sigset **out);
+int kg_sigset_merge_stats(const kg_sigset *s, kg_merge_stats *out);
 
 /* ---- protein families: proteins -> connected components of shared 8-mers (kernels: kg_cluster.hpp) ----
  *

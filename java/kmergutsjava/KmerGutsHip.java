@@ -230,6 +230,24 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_merge_params (kg_table_merge_signatures*): on_conflict = KG_MERGE_KEEP (0), KG_MERGE_REPLACE (1) or KG_MERGE_DROP (2). */
+    class KgMergeParams extends Structure {
+        public int on_conflict, reserved;
+        public KgMergeParams() {
+            setFieldOrder(new String[] {"on_conflict", "reserved"});
+        }
+    }
+
+    /** struct kg_merge_stats. */
+    class KgMergeStats extends Structure {
+        public long base, base_ignored, added_in, added, conflicts, conflicts_same_function, replaced, dropped, merged;
+        public float ms_extract, ms_sort, ms_resolve, ms_total;
+        public KgMergeStats() {
+            setFieldOrder(new String[] {"base", "base_ignored", "added_in", "added", "conflicts", "conflicts_same_function", "replaced",
+                    "dropped", "merged", "ms_extract", "ms_sort", "ms_resolve", "ms_total"});
+        }
+    }
+
     // replaces readKmerTableHeader + the table stream of lookup (KmerGutsJava.java:924-942, 944-1034)
     int kg_table_open(String path, int device, PointerByReference out);
     int kg_table_from_memory(Pointer image, long nbytes, int device, PointerByReference out);
@@ -248,6 +266,13 @@ public interface KmerGutsHip extends Library {
     int kg_sigset_copy(Pointer set, long first, long count, Pointer dst);
     int kg_sigset_stats(Pointer set, KgDeriveStats out);
     void kg_sigset_free(Pointer set);
+    /** a resident table united with n new signatures (fnMap / otuMap: null keeps the field) -> a signature set in k-mer order; n = 0
+     *  exports the table */
+    int kg_table_merge_signatures(Pointer base, KgMergeParams params, Pointer sigs, long n, int[] fnMap, long nFn, int[] otuMap, long nOtu,
+                                  PointerByReference out);
+    int kg_table_merge_signatures_device(Pointer base, KgMergeParams params, Pointer dSigs, long n, int[] fnMap, long nFn, int[] otuMap,
+                                         long nOtu, PointerByReference out);
+    int kg_sigset_merge_stats(Pointer set, KgMergeStats out);
     /** proteins -> families by shared 8-mers (connected components): maxWindows = 0 sizes the one pass from free device memory */
     int kg_proteins_cluster(int device, KgClusterParams params, byte[] seq, long[] offsets, long nProt, long maxWindows,
                             PointerByReference out);

@@ -34,6 +34,7 @@ EXPORTS = (
     "kg_result_device_container_hit_start", "kg_result_device_container_call_start", "kg_result_free", "kg_restore_hits_device",
     "kg_signatures_derive", "kg_signatures_derive_device", "kg_sigset_count", "kg_sigset_device", "kg_sigset_copy",
     "kg_sigset_stats", "kg_sigset_free", "kg_result_assign", "kg_assign_calls",
+    "kg_table_merge_signatures", "kg_table_merge_signatures_device", "kg_sigset_merge_stats",
     "kg_proteins_cluster", "kg_proteins_cluster_device", "kg_familyset_count", "kg_familyset_copy", "kg_familyset_stats",
     "kg_familyset_free",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
@@ -130,6 +131,26 @@ class KgDeriveStats(C.Structure):
     _fields_ = [("proteins", C.c_int64), ("windows", C.c_int64), ("valid_windows", C.c_int64), ("pairs", C.c_int64),
                 ("kmers", C.c_int64), ("signatures", C.c_int64), ("passes", C.c_int32), ("ms_encode", C.c_float),
                 ("ms_sort", C.c_float), ("ms_reduce", C.c_float), ("ms_total", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+MERGE_KEEP, MERGE_REPLACE, MERGE_DROP = 0, 1, 2
+MERGE_POLICIES = {"keep": MERGE_KEEP, "replace": MERGE_REPLACE, "drop": MERGE_DROP}
+
+
+class KgMergeParams(C.Structure):
+    """struct kg_merge_params (kg_table_merge_signatures*)."""
+    _fields_ = [("on_conflict", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgMergeStats(C.Structure):
+    """struct kg_merge_stats."""
+    _fields_ = [("base", C.c_int64), ("base_ignored", C.c_int64), ("added_in", C.c_int64), ("added", C.c_int64),
+                ("conflicts", C.c_int64), ("conflicts_same_function", C.c_int64), ("replaced", C.c_int64), ("dropped", C.c_int64),
+                ("merged", C.c_int64), ("ms_extract", C.c_float), ("ms_sort", C.c_float), ("ms_resolve", C.c_float),
+                ("ms_total", C.c_float)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -280,6 +301,9 @@ def load() -> C.CDLL:
     lib.kg_sigset_stats.argtypes = [vp, C.POINTER(KgDeriveStats)]
     lib.kg_sigset_free.argtypes = [vp]
     lib.kg_sigset_free.restype = None
+    for name in ("kg_table_merge_signatures", "kg_table_merge_signatures_device"):
+        getattr(lib, name).argtypes = [vp, C.POINTER(KgMergeParams), vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.POINTER(vp)]
+    lib.kg_sigset_merge_stats.argtypes = [vp, C.POINTER(KgMergeStats)]
     lib.kg_result_assign.argtypes = [vp, C.POINTER(KgAssignParams), vp, C.POINTER(C.c_float)]
     lib.kg_assign_calls.argtypes = [C.c_int, C.POINTER(KgAssignParams), vp, vp, C.c_int64, vp, vp]
     lib.kg_result_regions.argtypes = [vp, C.POINTER(KgRegionParams), vp, C.POINTER(vp)]

@@ -9,6 +9,8 @@ struct kg_sigset {
     uint8_t *d_sigs = nullptr;          // count * 24 bytes (hipMalloc, owned)
     int64_t count = 0;
     kg_derive_stats st = {};
+    bool merged = false;                // made by kg_table_merge_signatures* (kg_host_merge.hpp): mst is valid, st holds only `signatures`
+    kg_merge_stats mst = {};
 };
 
 namespace {

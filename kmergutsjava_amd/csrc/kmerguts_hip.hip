@@ -12,6 +12,7 @@
 #include "kg_partition.hpp"
 #include "kg_order.hpp"
 #include "kg_build.hpp"
+#include "kg_merge.hpp"
 #include "kg_derive.hpp"
 #include "kg_cluster.hpp"
 #include "kg_assign.hpp"
@@ -38,6 +39,7 @@
 // ---- the batch stages: each host beside its kernels ----
 #include "kg_host_build.hpp"
 #include "kg_host_derive.hpp"
+#include "kg_host_merge.hpp"
 #include "kg_host_cluster.hpp"
 #include "kg_host_assign.hpp"
 #include "kg_host_regions.hpp"

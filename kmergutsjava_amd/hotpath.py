@@ -345,16 +345,17 @@ def aggregate_hits(hits: np.ndarray, container_hit_start, n_seqs: int, params: O
 class SignatureTable:
     """kmer.table.mem_map resident on one GPU (KGJ:749-753, 924-942)."""
 
-    def __init__(self, handle: int, keepalive=None):
+    def __init__(self, handle: int, keepalive=None, device: Optional[int] = None):
         self._h = C.c_void_p(handle)
         self._keep = keepalive
+        self.device = device                   # None: not recorded (a handle adopted without it), torch's current device is used
         self._results = weakref.WeakSet()      # results still open: closed with the table, before it
 
     @classmethod
     def open(cls, path: str, device: int = 0) -> "SignatureTable":
         out = C.c_void_p()
         N.check(N.load().kg_table_open(path.encode(), device, C.byref(out)))
-        return cls(out.value)
+        return cls(out.value, device=device)
 
     @classmethod
     def from_bytes(cls, image, device: int = 0) -> "SignatureTable":
@@ -363,14 +364,14 @@ class SignatureTable:
         arr = np.ascontiguousarray(arr.view(np.uint8).reshape(-1))
         out = C.c_void_p()
         N.check(N.load().kg_table_from_memory(arr.ctypes.data, arr.nbytes, device, C.byref(out)))
-        return cls(out.value)
+        return cls(out.value, device=device)
 
     @classmethod
     def from_device_ptr(cls, ptr: int, num_sigs: int, device: int = 0, keepalive=None) -> "SignatureTable":
         """Adopt num_sigs 24-byte records already in HBM (e.g. a torch tensor's data_ptr())."""
         out = C.c_void_p()
         N.check(N.load().kg_table_from_device(C.c_void_p(ptr), num_sigs, device, C.byref(out)))
-        return cls(out.value, keepalive)
+        return cls(out.value, keepalive, device=device)
 
     @classmethod
     def build(cls, signatures, num_sigs: int, device: int = 0) -> "SignatureTable":
@@ -380,6 +381,7 @@ class SignatureTable:
         bytes (kg_table_build_device).  The number placed is `placed` on the result (= info()["occupied"])."""
         out, placed = C.c_void_p(), C.c_int64()
         lib = N.load()
+        dev = device
         if hasattr(signatures, "is_cuda") and signatures.is_cuda:
             if not signatures.is_contiguous():
                 raise ValueError("the signature tensor must be contiguous")
@@ -398,9 +400,62 @@ class SignatureTable:
                     raise ValueError("signature bytes must be a multiple of 24")
             n = arr.nbytes // 24
             N.check(lib.kg_table_build(arr.ctypes.data if n else None, n, int(num_sigs), device, C.byref(placed), C.byref(out)))
-        tab = cls(out.value)
+        tab = cls(out.value, device=dev)
         tab.placed = int(placed.value)
         return tab
+
+    def merge_signatures(self, sigs, fn_map=None, otu_map=None, on_conflict: str = "keep") -> "SignatureSet":
+        """This table's findable records united with new signatures, one record per k-mer, in ascending k-mer order
+        (include/kmerguts_hip.h kg_table_merge_signatures states the rule).  sigs: a numpy array of _native.SIGNATURE_DTYPE or
+        raw bytes of 24-byte records, or a contiguous CUDA tensor of 24 * n bytes, as for build; None is no signature.
+        fn_map / otu_map: int32 arrays that rename the new signatures' function_index / otu_index, None keeps the field.
+        on_conflict (a k-mer in both): "keep" the table's record, "replace" it by the new one, "drop" both unless they name the
+        same function.  The table is not modified; SignatureTable.build takes the result's device_tensor()."""
+        if not self._h:
+            raise ValueError("SignatureTable is closed")
+        if on_conflict not in N.MERGE_POLICIES:
+            raise ValueError("on_conflict must be one of keep, replace, drop")
+        p = N.KgMergeParams(N.MERGE_POLICIES[on_conflict], 0)
+        maps = []
+        for m in (fn_map, otu_map):
+            if m is None:
+                maps += [None, 0]
+                continue
+            a = np.asarray(m)
+            if a.ndim != 1 or (a.size and (a.dtype.kind not in "iu" or a.min() < -2 ** 31 or a.max() >= 2 ** 31)):
+                raise ValueError("a map must be a one-dimensional array of integers that fit in 32 bits")
+            a = np.ascontiguousarray(a.astype(np.int32))
+            maps += [a, a.size]
+        fm, n_fn, om, n_otu = maps
+        none = np.zeros(1, dtype=np.int32)     # (an empty map is still a map: every index is outside it)
+        fp = None if fm is None else (fm.ctypes.data if fm.size else none.ctypes.data)
+        op = None if om is None else (om.ctypes.data if om.size else none.ctypes.data)
+        out = C.c_void_p()
+        lib = N.load()
+        if sigs is not None and hasattr(sigs, "is_cuda") and sigs.is_cuda:
+            if not sigs.is_contiguous():
+                raise ValueError("the signature tensor must be contiguous")
+            nbytes = sigs.numel() * sigs.element_size()
+            if nbytes % 24:
+                raise ValueError("the signature tensor must hold 24 * n bytes")
+            N.check(lib.kg_table_merge_signatures_device(self._h, C.byref(p), C.c_void_p(sigs.data_ptr() if nbytes else None),
+                                                         nbytes // 24, fp, n_fn, op, n_otu, C.byref(out)))
+        else:
+            arr = np.zeros(0, dtype=N.SIGNATURE_DTYPE) if sigs is None else sigs
+            arr = arr if isinstance(arr, np.ndarray) else np.frombuffer(arr, dtype=np.uint8)
+            arr = np.ascontiguousarray(arr)
+            if arr.dtype != N.SIGNATURE_DTYPE:
+                arr = arr.reshape(-1).view(np.uint8)
+                if arr.size % 24:
+                    raise ValueError("signature bytes must be a multiple of 24")
+            n = arr.nbytes // 24
+            N.check(lib.kg_table_merge_signatures(self._h, C.byref(p), arr.ctypes.data if n else None, n, fp, n_fn, op, n_otu,
+                                                  C.byref(out)))
+        return SignatureSet(out.value, self.device)
+
+    def signatures(self) -> "SignatureSet":
+        """The table's findable records (0 <= kmer < 20^8) in ascending k-mer order: merge_signatures with no new signature."""
+        return self.merge_signatures(None)
 
     def save(self, path: str) -> None:
         """Write kmer.table.mem_map (gzip when path ends in .gz): the header and every whole record that is resident."""
@@ -506,6 +561,13 @@ class SignatureSet:
         self._need()
         st = N.KgDeriveStats()
         N.check(N.load().kg_sigset_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def merge_stats(self) -> dict:
+        """struct kg_merge_stats of a set made by SignatureTable.merge_signatures / signatures (an error for a derived set)."""
+        self._need()
+        st = N.KgMergeStats()
+        N.check(N.load().kg_sigset_merge_stats(self._h, C.byref(st)))
         return st.as_dict()
 
     def close(self) -> None:
