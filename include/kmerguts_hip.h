@@ -13,6 +13,7 @@
  * kg_result_regions / kg_regions_calls merge the CALL records of a DNA scan into function regions in contig coordinates.
  * kg_regionset_orfs / kg_orfs_regions extend every region to its open reading frame and extract the translated protein.
  * kg_orfs_free / kg_orfset_add_free enumerate the evidence-free open reading frames of the six frames.
+ * kg_orfset_coding scores every ORF by its in-frame hexamers against the genome's background and drops the non-coding free ones.
  *
  * Conventions: plain pointers and sizes only; every function returns an int status
  * (KG_OK == 0, negative == error) and never throws or aborts across the boundary; the text
@@ -679,6 +680,89 @@ int kg_orfs_free(int device, const kg_free_params *p, const uint8_t *seq, int se
                  int64_t n_seqs, kg_orfset **out);
 int kg_orfset_add_free(kg_orfset *set, const kg_free_params *p, const uint8_t *seq, int seq_on_device, const int64_t *offsets,
                        int64_t n_seqs, kg_orfset **out);
+
+/* ---- coding potential: the in-frame hexamer (dicodon) log-odds of every ORF; non-coding free ORFs dropped (kernels: kg_coding.hpp) ----
+ *
+ * The reference stops at the CALL lines; this rule is the project's own.  Integers only: the device's bytes equal a plain-loop
+ * model's.  It is the first filter between kg_orfset_add_free and the families learnt from its proteins: a free ORF on a gene's
+ * other strand, or a random one, is explained better by the genome's background than by its genes.
+ * Input: ORF records, the batch's sequence bytes exactly as the scan got them, and offsets[n_seqs + 1].  Nucleotide codes,
+ * strands, codons and n_f are rule 1 of the ORF section.  The codes are dna_code: A 0, C 1, G 2, T/U 3, anything else 4.  The '-'
+ * strand is read as 3 - c of seq[L-1-x] and is never materialised.
+ *   1. Hexamer index.  Six bases of one strand, all of code < 4, give h = sum b_i * 4^(5-i), with the first base most
+ *      significant.  0 <= h < 4096.  h = 64 * codon_k + codon_(k+1) with codon = 16 b0 + 4 b1 + b2.  A hexamer with a base of
+ *      code 4 does not exist.  It is not counted and it scores 0.
+ *   2. Pairs of an ORF record.  They are taken from the record alone (seq, strand, left, right, n_res), not from prot_start, so
+ *      only_kept zero lengths play no part.  Codon k (0 <= k < n_res) starts at strand position xs + 3k.  xs = left on '+', and
+ *      xs = L - 1 - right on '-'.  Pair k is codons k, k+1, for 0 <= k < n_res - 1.  The stop codon is in no pair.  A record
+ *      with n_res < 2 has no pair.
+ *   3. Coding counts C[4096] (int64).  A training record has kept != 0 and flags & (KG_ORF_FREE | KG_ORF_INTERRUPTED) == 0.
+ *      C[h] is the number of pairs with index h over all training records.  Identical ORFs from regions of different functions
+ *      are each counted.  This is stated, not repaired.
+ *   4. Background counts B[4096] (int64).  For every contig and every x in [0, L - 6] whose six bases seq[x .. x+5] are all
+ *      known, count B[h]++ and B[rc(h)]++.  rc(h) is the index of the reverse complement.  A hexamer never spans two contigs.
+ *      A contig with L < 6 gives none.
+ *   5. Score table T[4096] (int32).  Host code, integers only.  SC = sum C + 4096 and SB = sum B + 4096.
+ *      T[h] = Lg(C[h] + 1) - Lg(SC) - Lg(B[h] + 1) + Lg(SB).  Lg(x) for 1 <= x < 2^63 is defined by this procedure, not by
+ *      log2: n = floor(log2 x) is the bit length minus 1; y = x << (63 - n), f = 0; eight times: y = (y * y) >> 63 as a 128-bit
+ *      product, and if y >= 2^64 then y >>= 1 and f = 2f + 1, else f = 2f; Lg = 256 n + f.  Lg(1) = 0, Lg(2) = 256, Lg(3) = 405,
+ *      Lg(4096) = 3072, Lg(2^63 - 1) = 16127; the procedure is within 1 of floor(256 log2 x).
+ *   6. Score.  S (int64) is the sum of T[h] over the record's pairs.  Every record of the set is scored, whatever its flags
+ *      and kept.
+ *   7. Decision.  A record with KG_ORF_FREE, kept != 0 and S < min_coding gets kept = 0 and the new flag KG_ORF_NONCODING.
+ *      Nothing else in any record changes.  An evidence ORF is never dropped.  min_coding defaults to 0: the background explains
+ *      the ORF at least as well as the coding model.  This is the project's choice.
+ *   8. Trained or not.  A call without a caller's table trains on its own set (rules 3 to 5) when sum C >= min_train_pairs.
+ *      min_train_pairs defaults to 100 000, roughly a hundred average genes.  This is the project's choice.  Below that, the
+ *      call is untrained: all scores are 0 and no record changes.  That is a valid result and not an error.
+ *   9. Independence.  The output depends only on (records, bytes, offsets, parameters, table).  It does not depend on launch
+ *      geometry, tile size or batch neighbours.  All device sums are integer atomics or integer reductions, so order cannot
+ *      matter.
+ * kg_orfset_coding gives a NEW ORF set in the given set's context, as kg_orfset_add_free does: the given set's records under
+ * rule 7, its prot_start and residues unchanged, and an int64 score per record.  The given set stays valid; the new one is
+ * freed before it.  kg_orfset_select on the new set sees the lowered kept, so a non-coding free ORF suppresses nothing.  With
+ * table == NULL the call trains on its own set; that path has one host wait in the middle (counts down, T on the host, T up).
+ * With a table (int32[4096], host memory) no count is made and kg_orfset_coding_model gives zeros.  A caller's table may hold
+ * any int32 values (a large negative entry as a "forbidden hexamer" too): every sum is carried in 64 bits and S is exact.
+ * kg_coding_table is host-only and uses no GPU; a negative count, or counts whose sum is 2^62 or more, are KG_ERR_ARG.
+ * kg_coding_counts_orfs and kg_coding_score_orfs are the table-less twins for caller-held host lists.  A caller-held record must
+ * have seq in [0, n_seqs), strand 0 or 1, 0 <= left <= right < L and 3 * n_res <= right - left + 1; one that breaks any of
+ * these is KG_ERR_ARG, the message names the first such record, and the record is never used as an index.  (The records of a
+ * set are checked the same way against the offsets of the call.)
+ * Errors: KG_ERR_ARG for null pointers, reserved != 0, min_train_pairs < 0, n_seqs that is not the set's, decreasing offsets;
+ * KG_ERR_LIMIT for 2^31 or more records or contigs, 2^32 or more pairs, 2^40 or more bytes; KG_ERR_BUSY while a kg_scan* is in
+ * flight on the set's table; KG_ERR_NOMEM.  Zero records and zero sequences are valid.  Device allocations come from the
+ * context's block cache, so KG_TEST_FAIL_ALLOC applies; everything but the new set's arrays is back in the cache on every path
+ * out. */
+#define KG_ORF_NONCODING   32u
+typedef struct kg_coding_params { int32_t min_coding; int32_t reserved; int64_t min_train_pairs; } kg_coding_params;
+typedef struct kg_coding_model { int64_t coding[4096]; int64_t background[4096]; } kg_coding_model;
+typedef struct kg_coding_stats {
+    int64_t scored;            /* records of the set                                      */
+    int64_t training_records;
+    int64_t training_pairs;    /* sum C                                                   */
+    int64_t background;        /* sum B                                                   */
+    int64_t noncoding;         /* records that rule 7 dropped                             */
+    int32_t trained;           /* 0 untrained, 1 on its own set, 2 the caller's table     */
+    float   ms_count;          /* device time of the counting passes                      */
+    float   ms_score;          /* ... of the scores and the decision                      */
+    int32_t reserved;
+} kg_coding_stats;
+/* table: int32[4096] in host memory, or NULL to train on the set; seq, offsets as kg_orfset_add_free takes them */
+int kg_orfset_coding(kg_orfset *set, const kg_coding_params *p, const int32_t *table, const uint8_t *seq, int seq_on_device,
+                     const int64_t *offsets, int64_t n_seqs, kg_orfset **out);
+/* scores [first, first + count) into dst (host or device memory); KG_ERR_ARG on a set that has no scores */
+int kg_orfset_coding_scores(const kg_orfset *s, int64_t first, int64_t count, int64_t *dst);
+int kg_orfset_coding_stats(const kg_orfset *s, kg_coding_stats *out);
+/* the counts the call made: all zero when the caller gave a table */
+int kg_orfset_coding_model(const kg_orfset *s, kg_coding_model *out);
+/* rule 5 on the host: table = int32[4096] */
+int kg_coding_table(const kg_coding_model *model, int32_t *table);
+/* caller-held host lists: orfs[n] in any order, seq and offsets[n_seqs + 1] on the host */
+int kg_coding_counts_orfs(int device, const kg_orf *orfs, int64_t n, const uint8_t *seq, const int64_t *offsets, int64_t n_seqs,
+                          kg_coding_model *out);
+int kg_coding_score_orfs(int device, const int32_t *table, const kg_orf *orfs, int64_t n, const uint8_t *seq, const int64_t *offsets,
+                         int64_t n_seqs, int64_t *scores);
 
 /* ---- a gene set: the non-overlapping selection among regions or ORFs (kernels: kg_select.hpp) ----
  *

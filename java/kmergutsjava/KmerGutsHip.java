@@ -169,6 +169,36 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_coding_params (kg_orfset_coding); this project's defaults: 0, 0 and 100000. */
+    class KgCodingParams extends Structure {
+        public int min_coding, reserved;
+        public long min_train_pairs;
+        public KgCodingParams() {
+            setFieldOrder(new String[] {"min_coding", "reserved", "min_train_pairs"});
+        }
+    }
+
+    /** struct kg_coding_model: the coding and the background count of every hexamer index (first base most significant). */
+    class KgCodingModel extends Structure {
+        public long[] coding = new long[4096];
+        public long[] background = new long[4096];
+        public KgCodingModel() {
+            setFieldOrder(new String[] {"coding", "background"});
+        }
+    }
+
+    /** struct kg_coding_stats; trained: 0 untrained, 1 on its own set, 2 the caller's table. */
+    class KgCodingStats extends Structure {
+        public long scored, training_records, training_pairs, background, noncoding;
+        public int trained;
+        public float ms_count, ms_score;
+        public int reserved;
+        public KgCodingStats() {
+            setFieldOrder(new String[] {"scored", "training_records", "training_pairs", "background", "noncoding", "trained",
+                    "ms_count", "ms_score", "reserved"});
+        }
+    }
+
     /** struct kg_select_params (kg_regionset_select / kg_orfset_select / kg_select_intervals); this project's defaults: 60, 50 and 0. */
     class KgSelectParams extends Structure {
         public int max_overlap, max_overlap_pct, reserved;
@@ -343,6 +373,16 @@ public interface KmerGutsHip extends Library {
                      PointerByReference out);
     int kg_orfset_add_free(Pointer set, KgFreeParams params, Pointer seq, int seqOnDevice, long[] offsets, long nSeqs,
                            PointerByReference out);
+    /** the hexamer log-odds score of every ORF of a set; a free ORF below min_coding loses kept and gains flag 32 =
+     *  KG_ORF_NONCODING.  table: int[4096] or null to train on the set.  Free the new set before the given one. */
+    int kg_orfset_coding(Pointer set, KgCodingParams params, int[] table, Pointer seq, int seqOnDevice, long[] offsets, long nSeqs,
+                         PointerByReference out);
+    int kg_orfset_coding_scores(Pointer set, long first, long count, Pointer dst);   // long[count]
+    int kg_orfset_coding_stats(Pointer set, KgCodingStats out);
+    int kg_orfset_coding_model(Pointer set, KgCodingModel out);
+    int kg_coding_table(KgCodingModel model, int[] table);   // host only: int[4096]
+    int kg_coding_counts_orfs(int device, Pointer orfs, long n, Pointer seq, long[] offsets, long nSeqs, KgCodingModel out);
+    int kg_coding_score_orfs(int device, int[] table, Pointer orfs, long n, Pointer seq, long[] offsets, long nSeqs, long[] scores);
     /** the non-overlapping selection among the kept regions / ORFs of a set; free the select set before the set it came from */
     int kg_regionset_select(Pointer set, KgSelectParams params, PointerByReference out);
     int kg_orfset_select(Pointer set, KgSelectParams params, PointerByReference out);

@@ -41,6 +41,8 @@ EXPORTS = (
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
     "kg_orfset_residues", "kg_orfset_stats", "kg_orfset_free", "kg_orfs_free", "kg_orfset_add_free",
+    "kg_orfset_coding", "kg_orfset_coding_scores", "kg_orfset_coding_stats", "kg_orfset_coding_model", "kg_coding_table",
+    "kg_coding_counts_orfs", "kg_coding_score_orfs",
     "kg_regionset_select", "kg_orfset_select", "kg_select_intervals", "kg_selectset_count", "kg_selectset_device",
     "kg_selectset_copy", "kg_selectset_stats", "kg_selectset_free",
     "kg_last_error", "kg_version",
@@ -77,6 +79,11 @@ ORF_DTYPE = np.dtype([("seq", "<i4"), ("strand", "<i4"), ("frame", "<i4"), ("lef
 assert ORF_DTYPE.itemsize == 48
 ORF_HAS_STOP, ORF_PARTIAL5, ORF_INTERRUPTED, ORF_MULTI_FRAME = 1, 2, 4, 8
 ORF_FREE = 16               # an evidence-free candidate (kg_orfs_free / kg_orfset_add_free)
+ORF_NONCODING = 32          # a free ORF that kg_orfset_coding dropped (its kept is 0)
+CODING_BINS = 4096          # hexamer indices: the entries of a coding model's two count arrays and of a score table
+CODING_BG_TILE = 2048       # kg_coding.hpp kCodingBgTile: the hexamer starts of one workgroup step (tests aim at its edges) ...
+CODING_BG_PER_LANE = 8      # ... kCodingBgPerLane: of one lane ...
+CODING_MAX_GRID = 2048      # ... and kCodingMaxGrid: the workgroups the striding kernels have at most
 ORF_TILE_CODONS = 128       # kg_orfs.hpp kOrfTile: the codons of one tile summary (tests aim at its edges)
 # struct kg_interval (kg_select_intervals) and struct kg_selection (kg_*_select): a candidate and what became of it
 INTERVAL_DTYPE = np.dtype([("seq", "<i4"), ("left", "<i4"), ("right", "<i4"), ("score", "<i4"), ("eligible", "<i4")])
@@ -195,6 +202,26 @@ class KgFreeParams(C.Structure):
 
 
 FREE_PARAMS = KgFreeParams
+
+
+class KgCodingParams(C.Structure):
+    """struct kg_coding_params (kg_orfset_coding)."""
+    _fields_ = [("min_coding", C.c_int32), ("reserved", C.c_int32), ("min_train_pairs", C.c_int64)]
+
+
+class KgCodingModel(C.Structure):
+    """struct kg_coding_model: the coding and the background count of every hexamer index."""
+    _fields_ = [("coding", C.c_int64 * 4096), ("background", C.c_int64 * 4096)]
+
+
+class KgCodingStats(C.Structure):
+    """struct kg_coding_stats."""
+    _fields_ = [("scored", C.c_int64), ("training_records", C.c_int64), ("training_pairs", C.c_int64), ("background", C.c_int64),
+                ("noncoding", C.c_int64), ("trained", C.c_int32), ("ms_count", C.c_float), ("ms_score", C.c_float),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
 class KgSelectParams(C.Structure):
@@ -331,6 +358,13 @@ def load() -> C.CDLL:
     lib.kg_orfset_free.restype = None
     lib.kg_orfs_free.argtypes = [C.c_int, C.POINTER(KgFreeParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
     lib.kg_orfset_add_free.argtypes = [vp, C.POINTER(KgFreeParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
+    lib.kg_orfset_coding.argtypes = [vp, C.POINTER(KgCodingParams), vp, vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
+    lib.kg_orfset_coding_scores.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.kg_orfset_coding_stats.argtypes = [vp, C.POINTER(KgCodingStats)]
+    lib.kg_orfset_coding_model.argtypes = [vp, C.POINTER(KgCodingModel)]
+    lib.kg_coding_table.argtypes = [C.POINTER(KgCodingModel), vp]
+    lib.kg_coding_counts_orfs.argtypes = [C.c_int, vp, C.c_int64, vp, vp, C.c_int64, C.POINTER(KgCodingModel)]
+    lib.kg_coding_score_orfs.argtypes = [C.c_int, vp, vp, C.c_int64, vp, vp, C.c_int64, vp]
     lib.kg_regionset_select.argtypes = [vp, C.POINTER(KgSelectParams), C.POINTER(vp)]
     lib.kg_orfset_select.argtypes = [vp, C.POINTER(KgSelectParams), C.POINTER(vp)]
     lib.kg_select_intervals.argtypes = [C.c_int, C.POINTER(KgSelectParams), vp, C.c_int64, C.c_int64, C.POINTER(vp)]

@@ -6,6 +6,8 @@
                                             [--orfs ORFS.tsv] [--faa PROTEINS.faa] [--start-codons ATG,GTG,TTG]
                                             [--select [--max-overlap 60] [--max-overlap-pct 50]]
                                             [--free-orfs [--min-res 100]]
+                                            [--coding [--min-coding 0] [--min-train 100000] [--coding-model IN]
+                                             [--save-coding-model OUT]]
 
 The table and function.index[.gz] are loaded the way annotate loads them.  Contigs are read with
 make_signatures.parse_fasta (a duplicate id is an error) and scanned whole, in batches of at most
@@ -45,6 +47,19 @@ being written once.  With --select they are candidates like the others: their sc
 ORF (raise --min-score to let long free ORFs replace weak regions) and among free ORFs the longer wins; with --all a free ORF's
 line gains two trailing fields, its status kept or overlapped and the winner as in the regions file.  The summary line counts
 the free ORFs among selected and overlapped and gains `, free: F` at its end.
+
+--coding (with --orfs or --faa) scores every ORF by its in-frame hexamer log-odds on the GPU (kg_orfset_coding;
+include/kmerguts_hip.h states the rule, integers only) and drops the free ORFs that score below --min-coding (default 0: the
+genome's background explains the ORF at least as well as its genes do).  Without --coding-model every batch trains on its own
+evidence ORFs; a batch is 1.5 * 10^9 characters, so that is one model for nearly every input.  A batch whose evidence ORFs hold
+fewer than --min-train codon pairs (default 100000) is untrained: it prints one warning line on stderr, its scores are 0 and it
+drops nothing.  --save-coding-model writes the counts summed over the batches as text: the line `#kmerguts coding model 1`, then
+4096 lines HEXAMER<TAB>coding<TAB>background in index order.  --coding-model reads such a file and scores with its table
+(kg_coding_table) instead of training: a draft with few known genes can borrow a relative's model.  Every line of the ORF file
+gains its coding score as the last field.  A non-coding free ORF is written to neither the ORF nor the protein file; with --all
+it is written with the flag word `noncoding`, and where --select adds a status the status is `noncoding`.  It is not a
+candidate of --select, so it suppresses nothing.  The summary line gains `, coding: own|model|untrained, noncoding: N` (own: at
+least one batch trained on itself).  Without --coding every output is byte for byte what it was.
 """
 from __future__ import annotations
 
@@ -127,8 +142,47 @@ def format_regions(ids, regs, fnames, write_all: bool = False, gff: bool = False
 
 
 START_NAMES = (b"ATG", b"GTG", b"TTG")
-FLAG_WORDS = ((1, b"stop"), (2, b"partial5"), (4, b"interrupted"), (8, b"multi-frame"), (16, b"free"))
+FLAG_WORDS = ((1, b"stop"), (2, b"partial5"), (4, b"interrupted"), (8, b"multi-frame"), (16, b"free"), (32, b"noncoding"))
 FREE_NAME = b"hypothetical protein"
+NONCODING = 32
+MODEL_HEADER = b"#kmerguts coding model 1"
+
+
+def hexamer_text(h: int) -> bytes:
+    """The six letters of hexamer index h, the first base most significant."""
+    return bytes(b"ACGT"[(h >> (2 * (5 - i))) & 3] for i in range(6))
+
+
+def format_coding_model(coding, background) -> bytes:
+    """The text of --save-coding-model: the header line, then HEXAMER<TAB>coding<TAB>background in index order."""
+    return MODEL_HEADER + b"\n" + b"".join(b"%s\t%d\t%d\n" % (hexamer_text(h), int(coding[h]), int(background[h])) for h in range(4096))
+
+
+def parse_coding_model(text: bytes, where: str = "coding model"):
+    """The counts of a --save-coding-model file -> (coding, background), int64[4096] each."""
+    lines = text.split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    if not lines or lines[0].rstrip(b"\r") != MODEL_HEADER:
+        raise InputError("%s: the first line is not `%s`" % (where, MODEL_HEADER.decode()))
+    if len(lines) != 4097:
+        raise InputError("%s: %d lines behind the header, 4096 expected" % (where, len(lines) - 1))
+    out = np.zeros((2, 4096), dtype=np.int64)
+    for h, line in enumerate(lines[1:]):
+        f = line.rstrip(b"\r").split(b"\t")
+        try:
+            if len(f) != 3 or f[0] != hexamer_text(h):
+                raise ValueError
+            out[0, h], out[1, h] = int(f[1]), int(f[2])
+        except (ValueError, OverflowError):
+            raise InputError("%s, line %d: expected `%s<TAB>coding<TAB>background`" % (where, h + 2, hexamer_text(h).decode())) from None
+    return out[0], out[1]
+
+
+def coding_summary(trained, noncoding: int) -> str:
+    """What the summary line gains with --coding: trained the kg_coding_stats.trained of every batch."""
+    word = "model" if 2 in trained else "own" if 1 in trained else "untrained"
+    return ", coding: %s, noncoding: %d" % (word, noncoding)
 
 
 def parse_start_codons(text: str) -> int:
@@ -163,24 +217,30 @@ def _by_contig(first, second) -> list:
     return [x[2] for x in sorted([(c, 0, t) for c, t in first] + [(c, 1, t) for c, t in second], key=lambda x: x[:2])]
 
 
-def format_orfs(ids, regs, orfs, fnames, write_all: bool = False, sel=None, free=None, free_sel=None, cands=None) -> bytes:
+def format_orfs(ids, regs, orfs, fnames, write_all: bool = False, sel=None, free=None, free_sel=None, cands=None, coding=None,
+                free_coding=None) -> bytes:
     """ORF records (ORF_DTYPE, index-aligned with regs) as text, one line per written region.  free: the free ORFs of
     --free-orfs, written behind their contig's lines; free_sel: their selection records; cands: the records the selection ran on
-    (the winners of --all are named from them)."""
+    (the winners of --all are named from them); coding, free_coding: the coding scores of --coding, each line's last field."""
     lines = []
     for i, (r, o) in enumerate(zip(regs, orfs)):
         if not _written(r, write_all, sel, i):
             continue
-        lines.append((int(o["seq"]), _orf_line(ids, o, _fname(fnames, int(o["fI"]))) + b"\n"))
+        tail = b"" if coding is None else b"\t%d" % int(coding[i])
+        lines.append((int(o["seq"]), _orf_line(ids, o, _fname(fnames, int(o["fI"]))) + tail + b"\n"))
     if free is None:
         return b"".join(t for _, t in lines)
     flines = []
     for i, o in enumerate(free):
-        if not (write_all or free_sel is None or free_sel["state"][i] == 1):
+        noncoding = int(o["flags"]) & NONCODING != 0
+        if not (write_all or ((free_sel is None or free_sel["state"][i] == 1) and not noncoding)):
             continue
         tail = b""
         if free_sel is not None and write_all:
-            tail = b"\t%s\t%s" % (b"overlapped" if free_sel["state"][i] == 2 else b"kept", _winner(free_sel, i, cands))
+            status = b"noncoding" if noncoding else b"overlapped" if free_sel["state"][i] == 2 else b"kept"
+            tail = b"\t%s\t%s" % (status, _winner(free_sel, i, cands))
+        if free_coding is not None:
+            tail += b"\t%d" % int(free_coding[i])
         flines.append((int(o["seq"]), _orf_line(ids, o, FREE_NAME) + tail + b"\n"))
     return b"".join(_by_contig(lines, flines))
 
@@ -217,7 +277,8 @@ def format_faa(ids, regs, orfs, prot_start, residues, fnames, write_all: bool = 
     fout = []
     for i, o in enumerate(free):
         key = (int(o["seq"]), int(o["strand"]), int(o["left"]), int(o["right"]))
-        if not (write_all or free_sel is None or free_sel["state"][i] == 1) or key in best:
+        written = write_all or ((free_sel is None or free_sel["state"][i] == 1) and int(o["flags"]) & NONCODING == 0)
+        if not written or key in best:
             continue
         best[key] = -1
         fout.append((key[0], _fasta(ids, key, FREE_NAME, fres[int(free_prot_start[i]):int(free_prot_start[i + 1])])))
@@ -228,12 +289,18 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                  order_constraint: bool = False, merge_gap: int = 600, min_score: int = 0, min_len: int = 0,
                  write_all: bool = False, gff: bool = False, device: int = 0, orfs_out: str = None, faa_out: str = None,
                  start_codons: int = 7, select: bool = False, max_overlap: int = 60, max_overlap_pct: int = 50,
-                 free_min_res: int = None) -> str:
+                 free_min_res: int = None, coding: bool = False, min_coding: int = 0, min_train: int = 100000,
+                 coding_model_in: str = None, save_coding_model: str = None) -> str:
     """Write the regions (and, with orfs_out / faa_out, their open reading frames and proteins; with free_min_res also the
-    evidence-free ORFs of at least that many residues); returns the summary line."""
+    evidence-free ORFs of at least that many residues; with coding the ORFs' coding scores, the non-coding free ORFs dropped);
+    returns the summary line."""
     want_orfs = orfs_out is not None or faa_out is not None
     if free_min_res is not None and not want_orfs:
         raise ValueError("--free-orfs needs --orfs or --faa: free ORFs are written to those files only")
+    if coding and not want_orfs:
+        raise ValueError("--coding needs --orfs or --faa: the scores are the ORFs'")
+    if (coding_model_in is not None or save_coding_model is not None) and not coding:
+        raise ValueError("--coding-model and --save-coding-model need --coding")
     from . import hotpath
     from .kmer_guts_java import KmerGutsJava, _resident_table
     table_path = _data_file(data_dir, "kmer.table.mem_map")
@@ -245,6 +312,14 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
     tab = _resident_table(table_path, device)
     params = hotpath.Params(aa=False, order_constraint=order_constraint, min_hits=min_hits, min_weighted_hits=min_weighted_hits,
                             max_gap=max_gap)
+    coding_arg = None                   # what ScanResult.orfs / select take: None, True (own training) or a score table
+    if coding:
+        coding_arg = True
+        if coding_model_in is not None:
+            coding_arg = hotpath.coding_table(*parse_coding_model(_read(coding_model_in), coding_model_in))
+    ckw = {"coding": coding_arg, "min_coding": min_coding, "min_train_pairs": min_train} if coding else {}
+    cparts, fcparts, trained = [], [], []                       # the coding scores, and every batch's kg_coding_stats.trained
+    model_sum = np.zeros((2, 4096), dtype=np.int64)
     parts, starts = [], [np.zeros(1, dtype=np.int64)]
     oparts, lens, residues, sparts = [], [], [], []
     fparts, flens, fresidues, fsparts = [], [], [], []          # the free ORFs, and per batch (selection, first free record)
@@ -260,7 +335,7 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         with tab.scan(batch, off, params) as r:
             if select:
                 got = r.select(off, batch, merge_gap, min_score, min_len, want_orfs, start_codons, not write_all,
-                               max_overlap=max_overlap, max_overlap_pct=max_overlap_pct, free_min_res=free_min_res)
+                               max_overlap=max_overlap, max_overlap_pct=max_overlap_pct, free_min_res=free_min_res, **ckw)
                 regs, start, sel = got[0], got[1], got[-1]
                 # (selection is per contig: a batch's winners are its own records; a free winner is marked by -2 - its index
                 # among all free ORFs until the regions of every batch are counted)
@@ -273,7 +348,7 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                     orfs, pstart, res = got[2:5]
             elif want_orfs:
                 regs, start, orfs, pstart, res = r.orfs(batch, off, merge_gap, min_score, min_len, start_codons, not write_all,
-                                                        free_min_res=free_min_res)
+                                                        free_min_res=free_min_res, **ckw)
             if want_orfs:
                 nr = len(regs)                              # the regions' ORFs, then the batch's free ones
                 orfs["seq"] += k
@@ -284,6 +359,14 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                 flens.append(np.diff(pstart[nr:]))
                 fresidues.append(res[pstart[nr]:])
                 n_free += len(orfs) - nr
+                if coding:
+                    cparts.append(r.coding_scores[:nr])
+                    fcparts.append(r.coding_scores[nr:])
+                    trained.append(r.coding_stats["trained"])
+                    model_sum += np.stack(r.coding_model)
+                    if r.coding_stats["trained"] == 0:
+                        print("Warning: contigs %d..%d: %d codon pairs in evidence ORFs, fewer than --min-train %d: no coding model, "
+                              "no ORF scored" % (k + 1, j, r.coding_stats["training_pairs"], min_train), file=sys.stderr)
             else:
                 regs, start = r.regions(off, merge_gap, min_score, min_len)
         regs["seq"] += k
@@ -318,9 +401,13 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
             fstart = np.zeros(len(free) + 1, dtype=np.int64)
             if flens:
                 np.cumsum(np.concatenate(flens), out=fstart[1:])
+        scores = fscores = None
+        if coding:
+            scores = np.concatenate(cparts) if cparts else np.zeros(0, np.int64)
+            fscores = np.concatenate(fcparts) if fcparts and free is not None else None
         if orfs_out is not None:
             with open(orfs_out, "wb") as f:
-                f.write(format_orfs(ids, regs, orfs, fnames, write_all, sel, free, free_sel, cands))
+                f.write(format_orfs(ids, regs, orfs, fnames, write_all, sel, free, free_sel, cands, scores, fscores))
         if faa_out is not None:
             with open(faa_out, "wb") as f:
                 f.write(format_faa(ids, regs, orfs, pstart, np.concatenate(residues) if residues else np.zeros(0, np.uint8),
@@ -331,6 +418,11 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         line += select_summary(sel if free_sel is None else np.concatenate([sel, free_sel]))
     if free is not None:
         line += ", free: %d" % len(free)
+    if coding:
+        line += coding_summary(trained, 0 if free is None else int(((free["flags"] & NONCODING) != 0).sum()))
+        if save_coding_model is not None:
+            with open(save_coding_model, "wb") as f:
+                f.write(format_coding_model(model_sum[0], model_sum[1]))
     return line
 
 
@@ -357,15 +449,28 @@ def main(argv=None) -> int:
     ap.add_argument("--max-overlap-pct", type=int, default=50, help="... and percent of the shorter one (default 50)")
     ap.add_argument("--free-orfs", action="store_true", help="with --orfs / --faa: also write the evidence-free ORFs (hypothetical protein)")
     ap.add_argument("--min-res", type=int, default=100, help="residues a free ORF has at least (default 100, this project's choice)")
+    ap.add_argument("--coding", action="store_true",
+                    help="with --orfs / --faa: score every ORF by in-frame hexamer log-odds and drop the non-coding free ORFs; without "
+                         "--coding-model each batch (1.5e9 characters: one model for nearly every input) trains on its own evidence ORFs")
+    ap.add_argument("--min-coding", type=int, default=0, help="a free ORF is dropped with a coding score below this (default 0, this project's choice)")
+    ap.add_argument("--min-train", type=int, default=100000,
+                    help="codon pairs of evidence ORFs a batch needs to train (default 100000, this project's choice); below: untrained, nothing dropped")
+    ap.add_argument("--coding-model", metavar="IN", help="score with the counts of this file (--save-coding-model of a relative) instead of training")
+    ap.add_argument("--save-coding-model", metavar="OUT", help="write the coding and background hexamer counts, summed over the batches")
     a = ap.parse_args(argv)
     if a.free_orfs and a.orfs is None and a.faa is None:
         ap.error("--free-orfs needs --orfs or --faa")
+    if a.coding and a.orfs is None and a.faa is None:
+        ap.error("--coding needs --orfs or --faa")
+    if not a.coding and (a.coding_model is not None or a.save_coding_model is not None or a.min_coding != 0 or a.min_train != 100000):
+        ap.error("--min-coding, --min-train, --coding-model and --save-coding-model need --coding")
     from . import _native as N
     try:
         line = call_regions(a.D, a.q, a.o, a.m, a.M, a.g, a.O, a.merge_gap, a.min_score, a.min_len, a.all, a.gff,
                             orfs_out=a.orfs, faa_out=a.faa, start_codons=parse_start_codons(a.start_codons), select=a.select,
                             max_overlap=a.max_overlap, max_overlap_pct=a.max_overlap_pct,
-                            free_min_res=a.min_res if a.free_orfs else None)
+                            free_min_res=a.min_res if a.free_orfs else None, coding=a.coding, min_coding=a.min_coding,
+                            min_train=a.min_train, coding_model_in=a.coding_model, save_coding_model=a.save_coding_model)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1

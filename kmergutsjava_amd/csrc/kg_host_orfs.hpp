@@ -12,6 +12,10 @@ struct kg_orfset {
     int64_t count = 0, residues = 0;
     int64_t n_seqs = 0, l_max = 0;      // the batch's contigs and the longest of them (kg_orfset_select)
     kg_orf_stats st = {};
+    // kg_orfset_coding (kg_host_coding.hpp): the score of every record, what the call counted and its statistics
+    int64_t *d_coding = nullptr;        // count, null for a set that has no scores
+    std::unique_ptr<kg_coding_model> coding_model;
+    kg_coding_stats coding_st = {};
 };
 
 namespace {
@@ -468,6 +472,7 @@ void kg_orfset_free(kg_orfset *s)
         dfree(s->tab, s->d_orfs);
         dfree(s->tab, s->d_prot_start);
         dfree(s->tab, s->d_res);
+        dfree(s->tab, s->d_coding);
         if (s->own_tab) kg_table_close(s->tab);
     }
     delete s;

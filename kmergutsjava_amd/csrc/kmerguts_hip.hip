@@ -18,6 +18,7 @@
 #include "kg_assign.hpp"
 #include "kg_regions.hpp"
 #include "kg_orfs.hpp"
+#include "kg_coding.hpp"
 #include "kg_select.hpp"
 
 #include <fcntl.h>
@@ -44,4 +45,5 @@
 #include "kg_host_assign.hpp"
 #include "kg_host_regions.hpp"
 #include "kg_host_orfs.hpp"
+#include "kg_host_coding.hpp"
 #include "kg_host_select.hpp"

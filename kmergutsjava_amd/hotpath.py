@@ -221,7 +221,8 @@ class ScanResult:
         return out, start
 
     def orfs(self, seq, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, start_codons: int = 7,
-             only_kept: bool = True, device_ptr: Optional[int] = None, free_min_res: Optional[int] = None):
+             only_kept: bool = True, device_ptr: Optional[int] = None, free_min_res: Optional[int] = None, coding=None,
+             min_coding: int = 0, min_train_pairs: int = 100000):
         """regions() and then the open reading frame around every region with its translated protein, on the GPU, without a
         host trip between the two (include/kmerguts_hip.h kg_regionset_orfs states the rule).  seq / offsets: what the scan was
         given; device_ptr: the address of the bytes in HBM instead of seq.
@@ -229,8 +230,14 @@ class ScanResult:
         regions; the protein of ORF i is residues[prot_start[i] : prot_start[i + 1]] (uint8).  The two calls' counts and device
         times are left in `region_stats` and `orf_stats`.
         free_min_res: when given, the evidence-free candidates of at least that many residues (kg_orfset_add_free, flag
-        _native.ORF_FREE) follow the regions' ORFs in orfs, prot_start and residues; `orf_stats` is then the whole set's."""
+        _native.ORF_FREE) follow the regions' ORFs in orfs, prot_start and residues; `orf_stats` is then the whole set's.
+        coding: None (or False: off), True or an int32[4096] score table (coding_table): every record is scored by its in-frame hexamer
+        log-odds and a free ORF below min_coding loses kept and gains _native.ORF_NONCODING (kg_orfset_coding, after
+        free_min_res); True trains on the set's own evidence ORFs when they have min_train_pairs codon pairs.  The scores
+        (int64 per record), the statistics and the counts of an own training are left in `coding_scores`, `coding_stats` and
+        `coding_model`."""
         lib = self._need()
+        coding = _coding_arg(coding)
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
         if off.shape != (self.stats["n_seqs"] + 1,):
             raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
@@ -248,6 +255,9 @@ class ScanResult:
             N.check(lib.kg_regionset_orfs(h, C.byref(op), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(oh)))
             if free_min_res is not None:
                 oh = _add_free(oh, free_min_res, start_codons, ptr, on_device, off)
+            if coding is not None:
+                oh = _coding(oh, coding, min_coding, min_train_pairs, ptr, on_device, off)
+                self.coding_scores, self.coding_stats, self.coding_model = _coding_results(oh)
             orfs, prot_start, residues, self.orf_stats = _take_orfset(oh, False)
         except BaseException:
             lib.kg_regionset_free(h)
@@ -257,7 +267,8 @@ class ScanResult:
 
     def select(self, offsets, seq=None, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, orfs: bool = False,
                start_codons: int = 7, only_kept: bool = True, device_ptr: Optional[int] = None, max_overlap: int = 60,
-               max_overlap_pct: int = 50, free_min_res: Optional[int] = None):
+               max_overlap_pct: int = 50, free_min_res: Optional[int] = None, coding=None, min_coding: int = 0,
+               min_train_pairs: int = 100000):
         """regions() -- with orfs=True, orfs() -- and then the non-overlapping selection among the kept records, on the GPU and
         without a host trip or a second scan in between (include/kmerguts_hip.h kg_regionset_select states the rule).  The
         candidates are the regions' extents, or with orfs=True the ORFs' extents.
@@ -265,10 +276,15 @@ class ScanResult:
         selection a numpy array of _native.SELECTION_DTYPE, index-aligned with the regions (and the ORFs).  The calls' counts and
         device times are left in `region_stats`, `orf_stats` and `select_stats`.
         free_min_res (with orfs=True): the evidence-free candidates are appended on the device before the selection, as orfs()
-        appends them; orfs, prot_start, residues and selection then hold them behind the regions' records."""
+        appends them; orfs, prot_start, residues and selection then hold them behind the regions' records.
+        coding, min_coding, min_train_pairs (with orfs=True): as orfs() takes them, applied after free_min_res and before the
+        selection, so a non-coding free ORF is not eligible and suppresses nothing."""
         lib = self._need()
         if free_min_res is not None and not orfs:
             raise ValueError("free_min_res needs orfs=True: the free candidates are ORFs")
+        coding = _coding_arg(coding)
+        if coding is not None and not orfs:
+            raise ValueError("coding needs orfs=True: the scores are the ORFs'")
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
         if off.shape != (self.stats["n_seqs"] + 1,):
             raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
@@ -287,6 +303,9 @@ class ScanResult:
                 N.check(lib.kg_regionset_orfs(h, C.byref(op), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(oh)))
                 if free_min_res is not None:
                     oh = _add_free(oh, free_min_res, start_codons, ptr, on_device, off)
+                if coding is not None:
+                    oh = _coding(oh, coding, min_coding, min_train_pairs, ptr, on_device, off)
+                    self.coding_scores, self.coding_stats, self.coding_model = _coding_results(oh)
                 N.check(lib.kg_orfset_select(oh, C.byref(sp), C.byref(sh)))
             else:
                 N.check(lib.kg_regionset_select(h, C.byref(sp), C.byref(sh)))
@@ -764,6 +783,100 @@ def _add_free(oh, min_res: int, start_codons: int, ptr, on_device: int, off):
         lib.kg_orfset_free(oh)          # (the new set holds copies: the given one is not needed any more)
         oh.value = None
     return both
+
+
+def _table_arg(table) -> np.ndarray:
+    t = np.ascontiguousarray(table, dtype=np.int32)
+    if t.shape != (N.CODING_BINS,):
+        raise ValueError("a coding score table is int32[%d]" % N.CODING_BINS)
+    return t
+
+
+def _coding_arg(coding):
+    """The coding= of ScanResult.orfs / select, checked before any set is made: None or False -> None (off), True -> True (train
+    on the set), anything else -> the int32[4096] table it is."""
+    if coding is None or coding is False:
+        return None
+    return True if coding is True else _table_arg(coding)
+
+
+def _coding(oh, coding, min_coding: int, min_train_pairs: int, ptr, on_device: int, off):
+    """kg_orfset_coding on the ORF set oh, which is freed: -> the new set's handle (it lives in the same context).  coding: what
+    _coding_arg gave, True or a table."""
+    lib = N.load()
+    table = None if coding is True else coding
+    cp = N.KgCodingParams(int(min_coding), 0, int(min_train_pairs))
+    new = C.c_void_p()
+    try:
+        N.check(lib.kg_orfset_coding(oh, C.byref(cp), None if table is None else table.ctypes.data, ptr, on_device, off.ctypes.data,
+                                     off.size - 1, C.byref(new)))
+    finally:
+        lib.kg_orfset_free(oh)          # (the new set holds copies: the given one is not needed any more)
+        oh.value = None
+    return new
+
+
+def _coding_results(h):
+    """-> (scores int64[n], statistics, (coding, background) counts) of a set made by kg_orfset_coding; the set is freed when a
+    call fails."""
+    lib = N.load()
+    try:
+        n = int(lib.kg_orfset_count(h))
+        scores = np.zeros(n, dtype=np.int64)
+        N.check(lib.kg_orfset_coding_scores(h, 0, n, scores.ctypes.data if n else None))
+        st, m = N.KgCodingStats(), N.KgCodingModel()
+        N.check(lib.kg_orfset_coding_stats(h, C.byref(st)))
+        N.check(lib.kg_orfset_coding_model(h, C.byref(m)))
+        return scores, st.as_dict(), (np.array(m.coding, dtype=np.int64), np.array(m.background, dtype=np.int64))
+    except BaseException:
+        lib.kg_orfset_free(h)
+        h.value = None
+        raise
+
+
+def coding_table(coding, background) -> np.ndarray:
+    """The int32[4096] score table of a coding model's counts (kg_coding_table; include/kmerguts_hip.h states the rule: integer
+    log-odds of the in-frame hexamers against the background's).  Host code: no GPU takes part."""
+    m = N.KgCodingModel()
+    for name, src in (("coding", coding), ("background", background)):
+        a = np.ascontiguousarray(src, dtype=np.int64)
+        if a.shape != (N.CODING_BINS,):
+            raise ValueError("%s counts are int64[%d]" % (name, N.CODING_BINS))
+        C.memmove(getattr(m, name), a.ctypes.data, a.nbytes)
+    out = np.zeros(N.CODING_BINS, dtype=np.int32)
+    N.check(N.load().kg_coding_table(C.byref(m), out.ctypes.data))
+    return out
+
+
+def coding_counts(orfs, seq, offsets, device: int = 0):
+    """The coding and background hexamer counts of caller-held ORF records and their batch, on the GPU and without a table
+    (kg_coding_counts_orfs): orfs ORF_DTYPE, seq the batch's bytes, offsets int64[n_seqs + 1].  -> (coding, background), int64[4096]
+    each; a record trains when it is kept and neither free nor interrupted."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_seqs + 1]")
+    o = np.ascontiguousarray(orfs, dtype=N.ORF_DTYPE)
+    arr = _seq_bytes(seq, off)
+    m = N.KgCodingModel()
+    N.check(N.load().kg_coding_counts_orfs(device, o.ctypes.data if o.size else None, o.size, arr.ctypes.data if arr.size else None,
+                                           off.ctypes.data, off.size - 1, C.byref(m)))
+    return np.array(m.coding, dtype=np.int64), np.array(m.background, dtype=np.int64)
+
+
+def coding_scores(table, orfs, seq, offsets, device: int = 0) -> np.ndarray:
+    """The hexamer log-odds score of every caller-held ORF record under an int32[4096] table, on the GPU (kg_coding_score_orfs).
+    -> int64[n]."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_seqs + 1]")
+    t = _table_arg(table)
+    o = np.ascontiguousarray(orfs, dtype=N.ORF_DTYPE)
+    arr = _seq_bytes(seq, off)
+    out = np.zeros(o.size, dtype=np.int64)
+    N.check(N.load().kg_coding_score_orfs(device, t.ctypes.data, o.ctypes.data if o.size else None, o.size,
+                                          arr.ctypes.data if arr.size else None, off.ctypes.data, off.size - 1,
+                                          out.ctypes.data if o.size else None))
+    return out
 
 
 def free_orfs(seq, offsets, min_res: int = 100, start_codons: int = 7, device: int = 0, device_out: bool = False,
