@@ -764,6 +764,97 @@ int kg_coding_counts_orfs(int device, const kg_orf *orfs, int64_t n, const uint8
 int kg_coding_score_orfs(int device, const int32_t *table, const kg_orf *orfs, int64_t n, const uint8_t *seq, const int64_t *offsets,
                          int64_t n_seqs, int64_t *scores);
 
+/* ---- start codons: the start of every complete ORF chosen by a trained start-site score (kernels: kg_starts.hpp) ----
+ *
+ * The reference stops at the CALL lines; this rule is the project's own.  Integers only: the device's bytes equal a plain-loop
+ * model's.  Rule 3 of the ORF section and rule 2 of the free-ORF section take the first start behind the upstream stop (the
+ * longest ORF); this stage moves that start downstream where a score trained on the batch's own evidence ORFs says so.
+ * Input: ORF records, the batch's sequence bytes and offsets[n_seqs + 1] exactly as the scan got them, a coding table
+ * T (int32[4096], rule 5 of the coding section), parameters, optionally start weights, optionally a limit per record.
+ * Codes, strands, codons, xs and the pairs of a record are those of the ORF and coding sections.
+ *   1. Movable records.  A record is movable when kept != 0, start_codon != 0, flags & (KG_ORF_INTERRUPTED | KG_ORF_NONCODING)
+ *      == 0 and n_res >= 1.  Every other record is copied unchanged.
+ *   2. Candidates.  Codon k of a movable record is a candidate when 0 <= k < n_res, codon k is a start of the start_codons mask
+ *      and k <= K.  k = 0, the present start, is always a candidate.  K = limit_i when a limit is given for the record and is
+ *      >= 0; otherwise K = n_res - min_res, and when that is negative k = 0 is the only candidate.  min_res defaults to 100 (the
+ *      free-ORF section's default) and start_codons to 7; both are this project's choices.
+ *   3. Limit of an evidence ORF.  With a region set, record i < n_regions belongs to region i (the sets made by
+ *      kg_orfset_add_free and kg_orfset_coding keep that alignment) and limit_i = ceil((xa - xs_i) / 3) with xa the region's
+ *      strand-left of rule 2 of the ORF section: this is j0 - b, so a start is never moved behind the first codon inside the
+ *      region.  It is KG_ERR_ARG, naming the first such record, when the region's seq or strand differs from the record's or
+ *      when the value is negative; a set shorter than the region set is KG_ERR_ARG too.  Records behind the regions have no
+ *      limit.  Without a region set no record has a limit: evidence ORFs are then bounded by min_res alone.
+ *   4. Upstream window.  The 20 strand positions xs + 3k - 20 + i, 0 <= i < 20; c_i is the dna_code there; a position outside
+ *      the contig has code 4.
+ *   5. Score.  score(k) = Suf(k) + sum_i Wpos[i][c_i] + Wtype[type(k)], carried in int64.  Suf(k) is the sum of T[h] over pairs
+ *      k .. n_res - 2; a pair with an unknown base adds 0.  A code 4 in the window adds 0.  type is 1 for ATG, 2 for GTG, 3 for
+ *      TTG, by the codon's spelling (0 for the k = 0 of a caller-held record whose codon 0 is none of them; type 0 is never
+ *      counted).  The chosen start is the candidate of largest score, on a tie the smallest k.
+ *   6. Counts kg_start_model.  A training record is movable, not KG_ORF_FREE and not KG_ORF_PARTIAL5.  cand and type_cand count
+ *      the window bases and the type of every candidate of every training record; they do not depend on the round.  chosen and
+ *      type_chosen count those of each training record's currently chosen candidate.  Code 4 is never counted; index 0 of the
+ *      type arrays stays 0.
+ *   7. Weights kg_start_weights.  Host code, with the Lg of rule 5 of the coding section.
+ *      pos[i][c] = Lg(chosen[i][c] + 1) - Lg(sum_c chosen[i][c] + 4) - Lg(cand[i][c] + 1) + Lg(sum_c cand[i][c] + 4);
+ *      type[t] likewise over t = 1..3 with + 3 in place of + 4; type[0] = 0.
+ *   8. Rounds.  Without caller's weights, round 0 has every record at k = 0; each of `rounds` rounds counts rule 6, makes the
+ *      weights of rule 7 and re-chooses every movable record by rule 5, the training records included.  rounds defaults to 4
+ *      and must be between 1 and 16.  The call is untrained when fewer than min_train_starts training records exist (default
+ *      200, roughly eighty window parameters at a couple of records each); an untrained call changes no record, sets every
+ *      shift to 0 and is not an error.  With caller's weights there is one choice pass and no counting; any int32 values are
+ *      allowed.  The defaults are this project's choices.
+ *   9. Result.  A moved record is one with chosen k > 0.  It gets left += 3k on '+' and right -= 3k on '-', n_res -= k, the new
+ *      start_codon and the new flag KG_ORF_START_MOVED.  first_inner is -1 for every movable record and stays.  Its protein is
+ *      the old protein from residue k on, with residue 0 set to 'M'; prot_start and the residues are rebuilt (only_kept zero
+ *      lengths stay zero: those records are not movable).  When the set carries coding scores, a moved record's score becomes
+ *      Suf(k), its rule-6 score on the new extent; no record is re-decided against min_coding.  Nothing else changes.
+ *  10. Independence.  The output depends only on (records, bytes, offsets, parameters, tables, limits): not on launch geometry,
+ *      tile size or batch neighbours.  All device sums are integer.
+ * kg_orfset_starts gives a NEW ORF set in the given set's context, as kg_orfset_coding does; the given set stays valid and the
+ * new one is freed before it.  The new set keeps the given set's coding scores (under rule 9), model and statistics.  Without
+ * weights the call has one host wait per round (counts down, weights up).  kg_starts_orfs is the table-less twin for caller-held
+ * host lists; its records are checked as kg_coding_score_orfs checks them.  model and stats may be NULL there.
+ * kg_start_weights_from is host-only and uses no GPU; a negative count, or counts of one position (or of the types) whose sum
+ * is 2^62 or more, are KG_ERR_ARG.
+ * Errors: KG_ERR_ARG for null pointers (a null table too), reserved != 0, min_res < 1, start_codons outside 0..7, rounds outside
+ * 1..16, min_train_starts < 0, n_seqs that is not the set's, a region set of another n_seqs, decreasing offsets and rule 3;
+ * KG_ERR_LIMIT for 2^31 or more records or contigs, 2^32 or more codons, 2^40 or more bytes; KG_ERR_BUSY while a kg_scan* is in
+ * flight on the set's table; KG_ERR_NOMEM.  Zero records and zero sequences are valid.  Device allocations come from the
+ * context's block cache, so KG_TEST_FAIL_ALLOC applies; everything but the new set's arrays is back in the cache on every path
+ * out. */
+#define KG_ORF_START_MOVED 64u
+typedef struct kg_start_params { int32_t min_res; int32_t start_codons; int32_t rounds; int32_t reserved; int64_t min_train_starts; } kg_start_params;
+typedef struct kg_start_model { int64_t chosen[20][4]; int64_t cand[20][4]; int64_t type_chosen[4]; int64_t type_cand[4]; } kg_start_model;
+typedef struct kg_start_weights { int32_t pos[20][4]; int32_t type[4]; } kg_start_weights;
+typedef struct kg_start_stats {
+    int64_t movable;
+    int64_t training_records;
+    int64_t candidates;
+    int64_t moved;
+    int32_t rounds_run;        /* 0 untrained, 1 with the caller's weights                 */
+    int32_t trained;           /* 0 untrained, 1 on its own set, 2 the caller's weights    */
+    float   ms_count;          /* device time of the candidate list and the counts         */
+    float   ms_choose;         /* ... of the choices, the move and the proteins            */
+} kg_start_stats;
+/* table: int32[4096] in host memory; weights: NULL to train on the set; regions: NULL, or the region set the ORFs were made
+   from (rule 3); seq, offsets as kg_orfset_add_free takes them */
+int kg_orfset_starts(kg_orfset *set, const kg_start_params *p, const int32_t *table, const kg_start_weights *weights,
+                     const kg_regionset *regions, const uint8_t *seq, int seq_on_device, const int64_t *offsets, int64_t n_seqs,
+                     kg_orfset **out);
+/* the shift in codons of records [first, first + count) into dst (host or device memory); KG_ERR_ARG on a set that is not from
+   kg_orfset_starts */
+int kg_orfset_start_shifts(const kg_orfset *s, int64_t first, int64_t count, int32_t *dst);
+int kg_orfset_start_stats(const kg_orfset *s, kg_start_stats *out);
+/* the counts of the last round: all zero when the caller gave weights or the call is untrained */
+int kg_orfset_start_model(const kg_orfset *s, kg_start_model *out);
+/* rule 7 on the host */
+int kg_start_weights_from(const kg_start_model *model, kg_start_weights *weights);
+/* caller-held host lists: orfs[n] in any order, limits int32[n] (-1: none) or NULL, seq and offsets[n_seqs + 1] on the host;
+   out[n] and shifts[n] are written */
+int kg_starts_orfs(int device, const kg_start_params *p, const int32_t *table, const kg_start_weights *weights, const kg_orf *orfs,
+                   int64_t n, const int32_t *limits, const uint8_t *seq, const int64_t *offsets, int64_t n_seqs, kg_orf *out,
+                   int32_t *shifts, kg_start_model *model, kg_start_stats *stats);
+
 /* ---- a gene set: the non-overlapping selection among regions or ORFs (kernels: kg_select.hpp) ----
  *
  * The reference stops at the CALL lines; this rule is the project's own.

@@ -199,6 +199,47 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_start_params (kg_orfset_starts / kg_starts_orfs); this project's defaults: 100, 7, 4, 0 and 200. */
+    class KgStartParams extends Structure {
+        public int min_res, start_codons, rounds, reserved;
+        public long min_train_starts;
+        public KgStartParams() {
+            setFieldOrder(new String[] {"min_res", "start_codons", "rounds", "reserved", "min_train_starts"});
+        }
+    }
+
+    /** struct kg_start_model: int64 chosen[20][4], cand[20][4] (JNA has no nested arrays: entry 4 * position + base) and the
+     *  types' type_chosen[4], type_cand[4] (0 unused, 1 ATG, 2 GTG, 3 TTG). */
+    class KgStartModel extends Structure {
+        public long[] chosen = new long[80];
+        public long[] cand = new long[80];
+        public long[] type_chosen = new long[4];
+        public long[] type_cand = new long[4];
+        public KgStartModel() {
+            setFieldOrder(new String[] {"chosen", "cand", "type_chosen", "type_cand"});
+        }
+    }
+
+    /** struct kg_start_weights: int32 pos[20][4] (entry 4 * position + base) and type[4]. */
+    class KgStartWeights extends Structure {
+        public int[] pos = new int[80];
+        public int[] type = new int[4];
+        public KgStartWeights() {
+            setFieldOrder(new String[] {"pos", "type"});
+        }
+    }
+
+    /** struct kg_start_stats; trained: 0 untrained, 1 on its own set, 2 the caller's weights. */
+    class KgStartStats extends Structure {
+        public long movable, training_records, candidates, moved;
+        public int rounds_run, trained;
+        public float ms_count, ms_choose;
+        public KgStartStats() {
+            setFieldOrder(new String[] {"movable", "training_records", "candidates", "moved", "rounds_run", "trained", "ms_count",
+                    "ms_choose"});
+        }
+    }
+
     /** struct kg_select_params (kg_regionset_select / kg_orfset_select / kg_select_intervals); this project's defaults: 60, 50 and 0. */
     class KgSelectParams extends Structure {
         public int max_overlap, max_overlap_pct, reserved;
@@ -383,6 +424,18 @@ public interface KmerGutsHip extends Library {
     int kg_coding_table(KgCodingModel model, int[] table);   // host only: int[4096]
     int kg_coding_counts_orfs(int device, Pointer orfs, long n, Pointer seq, long[] offsets, long nSeqs, KgCodingModel out);
     int kg_coding_score_orfs(int device, int[] table, Pointer orfs, long n, Pointer seq, long[] offsets, long nSeqs, long[] scores);
+    /** the start codon of every movable ORF of a set, chosen by the start-site score; a moved ORF gains flag 64 =
+     *  KG_ORF_START_MOVED.  table: int[4096]; weights: null to train on the set; regions: null or the region set the ORFs
+     *  came from.  Free the new set before the given one. */
+    int kg_orfset_starts(Pointer set, KgStartParams params, int[] table, KgStartWeights weights, Pointer regions, Pointer seq,
+                         int seqOnDevice, long[] offsets, long nSeqs, PointerByReference out);
+    int kg_orfset_start_shifts(Pointer set, long first, long count, Pointer dst);    // int[count]
+    int kg_orfset_start_stats(Pointer set, KgStartStats out);
+    int kg_orfset_start_model(Pointer set, KgStartModel out);
+    int kg_start_weights_from(KgStartModel model, KgStartWeights weights);           // host only
+    /** limits: int[n] (-1: none) or null; out: n packed 48-byte kg_orf records; model, stats: may be null */
+    int kg_starts_orfs(int device, KgStartParams params, int[] table, KgStartWeights weights, Pointer orfs, long n, int[] limits,
+                       Pointer seq, long[] offsets, long nSeqs, Pointer out, int[] shifts, KgStartModel model, KgStartStats stats);
     /** the non-overlapping selection among the kept regions / ORFs of a set; free the select set before the set it came from */
     int kg_regionset_select(Pointer set, KgSelectParams params, PointerByReference out);
     int kg_orfset_select(Pointer set, KgSelectParams params, PointerByReference out);

@@ -43,6 +43,8 @@ EXPORTS = (
     "kg_orfset_residues", "kg_orfset_stats", "kg_orfset_free", "kg_orfs_free", "kg_orfset_add_free",
     "kg_orfset_coding", "kg_orfset_coding_scores", "kg_orfset_coding_stats", "kg_orfset_coding_model", "kg_coding_table",
     "kg_coding_counts_orfs", "kg_coding_score_orfs",
+    "kg_orfset_starts", "kg_orfset_start_shifts", "kg_orfset_start_stats", "kg_orfset_start_model", "kg_start_weights_from",
+    "kg_starts_orfs",
     "kg_regionset_select", "kg_orfset_select", "kg_select_intervals", "kg_selectset_count", "kg_selectset_device",
     "kg_selectset_copy", "kg_selectset_stats", "kg_selectset_free",
     "kg_last_error", "kg_version",
@@ -80,6 +82,9 @@ assert ORF_DTYPE.itemsize == 48
 ORF_HAS_STOP, ORF_PARTIAL5, ORF_INTERRUPTED, ORF_MULTI_FRAME = 1, 2, 4, 8
 ORF_FREE = 16               # an evidence-free candidate (kg_orfs_free / kg_orfset_add_free)
 ORF_NONCODING = 32          # a free ORF that kg_orfset_coding dropped (its kept is 0)
+ORF_START_MOVED = 64        # a record whose start kg_orfset_starts moved downstream
+START_WINDOW = 20           # upstream positions of a start model
+START_CHUNK = 1024          # kg_starts.hpp kStartChunk: the codons of one workgroup of the codon passes (tests aim at its edges)
 CODING_BINS = 4096          # hexamer indices: the entries of a coding model's two count arrays and of a score table
 CODING_BG_TILE = 2048       # kg_coding.hpp kCodingBgTile: the hexamer starts of one workgroup step (tests aim at its edges) ...
 CODING_BG_PER_LANE = 8      # ... kCodingBgPerLane: of one lane ...
@@ -224,6 +229,32 @@ class KgCodingStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class KgStartParams(C.Structure):
+    """struct kg_start_params (kg_orfset_starts / kg_starts_orfs)."""
+    _fields_ = [("min_res", C.c_int32), ("start_codons", C.c_int32), ("rounds", C.c_int32), ("reserved", C.c_int32),
+                ("min_train_starts", C.c_int64)]
+
+
+class KgStartModel(C.Structure):
+    """struct kg_start_model: the chosen and the candidate counts of every window base and of every start type."""
+    _fields_ = [("chosen", C.c_int64 * 4 * 20), ("cand", C.c_int64 * 4 * 20), ("type_chosen", C.c_int64 * 4),
+                ("type_cand", C.c_int64 * 4)]
+
+
+class KgStartWeights(C.Structure):
+    """struct kg_start_weights."""
+    _fields_ = [("pos", C.c_int32 * 4 * 20), ("type", C.c_int32 * 4)]
+
+
+class KgStartStats(C.Structure):
+    """struct kg_start_stats."""
+    _fields_ = [("movable", C.c_int64), ("training_records", C.c_int64), ("candidates", C.c_int64), ("moved", C.c_int64),
+                ("rounds_run", C.c_int32), ("trained", C.c_int32), ("ms_count", C.c_float), ("ms_choose", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class KgSelectParams(C.Structure):
     """struct kg_select_params (kg_regionset_select / kg_orfset_select / kg_select_intervals)."""
     _fields_ = [("max_overlap", C.c_int32), ("max_overlap_pct", C.c_int32), ("reserved", C.c_int32)]
@@ -365,6 +396,12 @@ def load() -> C.CDLL:
     lib.kg_coding_table.argtypes = [C.POINTER(KgCodingModel), vp]
     lib.kg_coding_counts_orfs.argtypes = [C.c_int, vp, C.c_int64, vp, vp, C.c_int64, C.POINTER(KgCodingModel)]
     lib.kg_coding_score_orfs.argtypes = [C.c_int, vp, vp, C.c_int64, vp, vp, C.c_int64, vp]
+    lib.kg_orfset_starts.argtypes = [vp, C.POINTER(KgStartParams), vp, vp, vp, vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
+    lib.kg_orfset_start_shifts.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.kg_orfset_start_stats.argtypes = [vp, C.POINTER(KgStartStats)]
+    lib.kg_orfset_start_model.argtypes = [vp, C.POINTER(KgStartModel)]
+    lib.kg_start_weights_from.argtypes = [C.POINTER(KgStartModel), C.POINTER(KgStartWeights)]
+    lib.kg_starts_orfs.argtypes = [C.c_int, C.POINTER(KgStartParams), vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     lib.kg_regionset_select.argtypes = [vp, C.POINTER(KgSelectParams), C.POINTER(vp)]
     lib.kg_orfset_select.argtypes = [vp, C.POINTER(KgSelectParams), C.POINTER(vp)]
     lib.kg_select_intervals.argtypes = [C.c_int, C.POINTER(KgSelectParams), vp, C.c_int64, C.c_int64, C.POINTER(vp)]

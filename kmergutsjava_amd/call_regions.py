@@ -8,6 +8,8 @@
                                             [--free-orfs [--min-res 100]]
                                             [--coding [--min-coding 0] [--min-train 100000] [--coding-model IN]
                                              [--save-coding-model OUT]]
+                                            [--starts [--start-rounds 4] [--min-train-starts 200] [--start-model IN]
+                                             [--save-start-model OUT]]
 
 The table and function.index[.gz] are loaded the way annotate loads them.  Contigs are read with
 make_signatures.parse_fasta (a duplicate id is an error) and scanned whole, in batches of at most
@@ -60,6 +62,19 @@ gains its coding score as the last field.  A non-coding free ORF is written to n
 it is written with the flag word `noncoding`, and where --select adds a status the status is `noncoding`.  It is not a
 candidate of --select, so it suppresses nothing.  The summary line gains `, coding: own|model|untrained, noncoding: N` (own: at
 least one batch trained on itself).  Without --coding every output is byte for byte what it was.
+
+--starts (with --coding) chooses the start codon of every complete, kept ORF by a start-site score on the GPU (kg_orfset_starts;
+include/kmerguts_hip.h states the rule, integers only): the coding score of the ORF behind the candidate start, plus weights of
+the 20 bases in front of it and of the start codon's spelling, trained in --start-rounds rounds (default 4) on the batch's own
+evidence ORFs.  An evidence ORF's start is never moved into its region, any other start only as far as --min-res residues
+remain.  A batch with fewer than --min-train-starts evidence ORFs with a start and an upstream stop (default 200), or whose
+coding step was untrained, is untrained: it prints one warning line on stderr and moves nothing.  --save-start-model writes
+the counts of the last round summed over the batches as text: the line `#kmerguts start model 1`, then 80 lines
+position<TAB>base<TAB>chosen<TAB>candidates (position 0 is 20 bases in front of the start) and 3 lines
+type<TAB>ATG|GTG|TTG<TAB>chosen<TAB>candidates.  --start-model reads such a file and chooses with its weights
+(kg_start_weights_from) instead of training.  Every line of the ORF file gains the ORF's shift in codons as its last field, and
+a moved ORF the flag word `moved`; the protein file and --select see the new extents.  The summary line gains
+`, starts: own|model|untrained, moved: N`.  Without --starts every output is byte for byte what it was.
 """
 from __future__ import annotations
 
@@ -142,9 +157,10 @@ def format_regions(ids, regs, fnames, write_all: bool = False, gff: bool = False
 
 
 START_NAMES = (b"ATG", b"GTG", b"TTG")
-FLAG_WORDS = ((1, b"stop"), (2, b"partial5"), (4, b"interrupted"), (8, b"multi-frame"), (16, b"free"), (32, b"noncoding"))
+FLAG_WORDS = ((1, b"stop"), (2, b"partial5"), (4, b"interrupted"), (8, b"multi-frame"), (16, b"free"), (32, b"noncoding"), (64, b"moved"))
 FREE_NAME = b"hypothetical protein"
 NONCODING = 32
+MOVED = 64
 MODEL_HEADER = b"#kmerguts coding model 1"
 
 
@@ -185,6 +201,53 @@ def coding_summary(trained, noncoding: int) -> str:
     return ", coding: %s, noncoding: %d" % (word, noncoding)
 
 
+START_MODEL_HEADER = b"#kmerguts start model 1"
+
+
+def format_start_model(chosen, cand, type_chosen, type_cand) -> bytes:
+    """The text of --save-start-model: the header line, 80 lines position<TAB>base<TAB>chosen<TAB>candidates, 3 lines
+    type<TAB>ATG|GTG|TTG<TAB>chosen<TAB>candidates."""
+    lines = [START_MODEL_HEADER + b"\n"]
+    for i in range(20):
+        lines += [b"%d\t%s\t%d\t%d\n" % (i, b"ACGT"[c:c + 1], int(chosen[i][c]), int(cand[i][c])) for c in range(4)]
+    lines += [b"type\t%s\t%d\t%d\n" % (START_NAMES[t - 1], int(type_chosen[t]), int(type_cand[t])) for t in (1, 2, 3)]
+    return b"".join(lines)
+
+
+def parse_start_model(text: bytes, where: str = "start model"):
+    """The counts of a --save-start-model file -> (chosen int64[20][4], cand int64[20][4], type_chosen int64[4], type_cand
+    int64[4])."""
+    lines = text.split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    if not lines or lines[0].rstrip(b"\r") != START_MODEL_HEADER:
+        raise InputError("%s: the first line is not `%s`" % (where, START_MODEL_HEADER.decode()))
+    if len(lines) != 84:
+        raise InputError("%s: %d lines behind the header, 83 expected" % (where, len(lines) - 1))
+    chosen, cand = np.zeros((20, 4), dtype=np.int64), np.zeros((20, 4), dtype=np.int64)
+    tchosen, tcand = np.zeros(4, dtype=np.int64), np.zeros(4, dtype=np.int64)
+    for q, line in enumerate(lines[1:]):
+        f = line.rstrip(b"\r").split(b"\t")
+        want = (b"%d" % (q // 4), b"ACGT"[q % 4:q % 4 + 1]) if q < 80 else (b"type", START_NAMES[q - 80])
+        try:
+            if len(f) != 4 or (f[0], f[1]) != want:
+                raise ValueError
+            if q < 80:
+                chosen[q // 4, q % 4], cand[q // 4, q % 4] = int(f[2]), int(f[3])
+            else:
+                tchosen[q - 79], tcand[q - 79] = int(f[2]), int(f[3])
+        except (ValueError, OverflowError):
+            raise InputError("%s, line %d: expected `%s<TAB>%s<TAB>chosen<TAB>candidates`" %
+                             (where, q + 2, want[0].decode(), want[1].decode())) from None
+    return chosen, cand, tchosen, tcand
+
+
+def starts_summary(trained, moved: int) -> str:
+    """What the summary line gains with --starts: trained the kg_start_stats.trained of every batch."""
+    word = "model" if 2 in trained else "own" if 1 in trained else "untrained"
+    return ", starts: %s, moved: %d" % (word, moved)
+
+
 def parse_start_codons(text: str) -> int:
     """`ATG,GTG,TTG` -> the start_codons mask (1 ATG, 2 GTG, 4 TTG); `none` or an empty text -> 0."""
     mask = 0
@@ -218,15 +281,18 @@ def _by_contig(first, second) -> list:
 
 
 def format_orfs(ids, regs, orfs, fnames, write_all: bool = False, sel=None, free=None, free_sel=None, cands=None, coding=None,
-                free_coding=None) -> bytes:
+                free_coding=None, shifts=None, free_shifts=None) -> bytes:
     """ORF records (ORF_DTYPE, index-aligned with regs) as text, one line per written region.  free: the free ORFs of
     --free-orfs, written behind their contig's lines; free_sel: their selection records; cands: the records the selection ran on
-    (the winners of --all are named from them); coding, free_coding: the coding scores of --coding, each line's last field."""
+    (the winners of --all are named from them); coding, free_coding: the coding scores of --coding, each line's last field;
+    shifts, free_shifts: the shifts of --starts, the last field behind the score."""
     lines = []
     for i, (r, o) in enumerate(zip(regs, orfs)):
         if not _written(r, write_all, sel, i):
             continue
         tail = b"" if coding is None else b"\t%d" % int(coding[i])
+        if shifts is not None:
+            tail += b"\t%d" % int(shifts[i])
         lines.append((int(o["seq"]), _orf_line(ids, o, _fname(fnames, int(o["fI"]))) + tail + b"\n"))
     if free is None:
         return b"".join(t for _, t in lines)
@@ -241,6 +307,8 @@ def format_orfs(ids, regs, orfs, fnames, write_all: bool = False, sel=None, free
             tail = b"\t%s\t%s" % (status, _winner(free_sel, i, cands))
         if free_coding is not None:
             tail += b"\t%d" % int(free_coding[i])
+        if free_shifts is not None:
+            tail += b"\t%d" % int(free_shifts[i])
         flines.append((int(o["seq"]), _orf_line(ids, o, FREE_NAME) + tail + b"\n"))
     return b"".join(_by_contig(lines, flines))
 
@@ -290,10 +358,11 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                  write_all: bool = False, gff: bool = False, device: int = 0, orfs_out: str = None, faa_out: str = None,
                  start_codons: int = 7, select: bool = False, max_overlap: int = 60, max_overlap_pct: int = 50,
                  free_min_res: int = None, coding: bool = False, min_coding: int = 0, min_train: int = 100000,
-                 coding_model_in: str = None, save_coding_model: str = None) -> str:
+                 coding_model_in: str = None, save_coding_model: str = None, starts: bool = False, start_rounds: int = 4,
+                 min_train_starts: int = 200, start_model_in: str = None, save_start_model: str = None) -> str:
     """Write the regions (and, with orfs_out / faa_out, their open reading frames and proteins; with free_min_res also the
-    evidence-free ORFs of at least that many residues; with coding the ORFs' coding scores, the non-coding free ORFs dropped);
-    returns the summary line."""
+    evidence-free ORFs of at least that many residues; with coding the ORFs' coding scores, the non-coding free ORFs dropped;
+    with starts the start codons chosen by the start-site score); returns the summary line."""
     want_orfs = orfs_out is not None or faa_out is not None
     if free_min_res is not None and not want_orfs:
         raise ValueError("--free-orfs needs --orfs or --faa: free ORFs are written to those files only")
@@ -301,6 +370,10 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         raise ValueError("--coding needs --orfs or --faa: the scores are the ORFs'")
     if (coding_model_in is not None or save_coding_model is not None) and not coding:
         raise ValueError("--coding-model and --save-coding-model need --coding")
+    if starts and not coding:
+        raise ValueError("--starts needs --coding: the start-site score's coding half is the coding step's table")
+    if (start_model_in is not None or save_start_model is not None) and not starts:
+        raise ValueError("--start-model and --save-start-model need --starts")
     from . import hotpath
     from .kmer_guts_java import KmerGutsJava, _resident_table
     table_path = _data_file(data_dir, "kmer.table.mem_map")
@@ -318,9 +391,17 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         if coding_model_in is not None:
             coding_arg = hotpath.coding_table(*parse_coding_model(_read(coding_model_in), coding_model_in))
     ckw = {"coding": coding_arg, "min_coding": min_coding, "min_train_pairs": min_train} if coding else {}
+    if starts:
+        starts_arg = True                                       # ... and their starts=: True or a weights pair
+        if start_model_in is not None:
+            starts_arg = hotpath.start_weights(*parse_start_model(_read(start_model_in), start_model_in))
+        ckw.update(starts=starts_arg, start_min_res=100 if free_min_res is None else free_min_res, start_rounds=start_rounds,
+                   min_train_starts=min_train_starts)
+    shparts, fshparts, strained = [], [], []                    # the shifts, and every batch's kg_start_stats.trained
+    start_sum = [np.zeros((20, 4), np.int64), np.zeros((20, 4), np.int64), np.zeros(4, np.int64), np.zeros(4, np.int64)]
     cparts, fcparts, trained = [], [], []                       # the coding scores, and every batch's kg_coding_stats.trained
     model_sum = np.zeros((2, 4096), dtype=np.int64)
-    parts, starts = [], [np.zeros(1, dtype=np.int64)]
+    parts, rstarts = [], [np.zeros(1, dtype=np.int64)]
     oparts, lens, residues, sparts = [], [], [], []
     fparts, flens, fresidues, fsparts = [], [], [], []          # the free ORFs, and per batch (selection, first free record)
     k = n_before = n_free = 0
@@ -367,12 +448,22 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                     if r.coding_stats["trained"] == 0:
                         print("Warning: contigs %d..%d: %d codon pairs in evidence ORFs, fewer than --min-train %d: no coding model, "
                               "no ORF scored" % (k + 1, j, r.coding_stats["training_pairs"], min_train), file=sys.stderr)
+                if starts:
+                    shparts.append(r.start_shifts[:nr])
+                    fshparts.append(r.start_shifts[nr:])
+                    strained.append(r.start_stats["trained"])
+                    for total, part in zip(start_sum, r.start_model):
+                        total += part
+                    if r.start_stats["trained"] == 0:
+                        print("Warning: contigs %d..%d: %d evidence ORFs to train the start model on, fewer than --min-train-starts %d, "
+                              "or no coding model: no start moved" % (k + 1, j, r.start_stats["training_records"], min_train_starts),
+                              file=sys.stderr)
             else:
                 regs, start = r.regions(off, merge_gap, min_score, min_len)
         regs["seq"] += k
         n_before += len(regs)
         parts.append(regs)
-        starts.append(start[1:] + starts[-1][-1])
+        rstarts.append(start[1:] + rstarts[-1][-1])
         k = j
     regs = np.concatenate(parts) if parts else np.zeros(0, dtype=hotpath.N.REGION_DTYPE)
     sel = None
@@ -391,7 +482,7 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                 by[by <= -2] = len(orfs) + (-2 - by[by <= -2])
     with open(out, "wb") as f:
         f.write(format_regions(ids, regs, fnames, write_all, gff, sel, cands))
-    line = summary_of(regs, np.concatenate(starts))
+    line = summary_of(regs, np.concatenate(rstarts))
     if want_orfs:
         pstart = np.zeros(len(orfs) + 1, dtype=np.int64)
         if lens:
@@ -405,9 +496,13 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         if coding:
             scores = np.concatenate(cparts) if cparts else np.zeros(0, np.int64)
             fscores = np.concatenate(fcparts) if fcparts and free is not None else None
+        shifts = fshifts = None
+        if starts:
+            shifts = np.concatenate(shparts) if shparts else np.zeros(0, np.int32)
+            fshifts = np.concatenate(fshparts) if fshparts and free is not None else None
         if orfs_out is not None:
             with open(orfs_out, "wb") as f:
-                f.write(format_orfs(ids, regs, orfs, fnames, write_all, sel, free, free_sel, cands, scores, fscores))
+                f.write(format_orfs(ids, regs, orfs, fnames, write_all, sel, free, free_sel, cands, scores, fscores, shifts, fshifts))
         if faa_out is not None:
             with open(faa_out, "wb") as f:
                 f.write(format_faa(ids, regs, orfs, pstart, np.concatenate(residues) if residues else np.zeros(0, np.uint8),
@@ -423,6 +518,12 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         if save_coding_model is not None:
             with open(save_coding_model, "wb") as f:
                 f.write(format_coding_model(model_sum[0], model_sum[1]))
+    if starts:
+        moved = int(((orfs["flags"] & MOVED) != 0).sum()) + (0 if free is None else int(((free["flags"] & MOVED) != 0).sum()))
+        line += starts_summary(strained, moved)
+        if save_start_model is not None:
+            with open(save_start_model, "wb") as f:
+                f.write(format_start_model(*start_sum))
     return line
 
 
@@ -457,6 +558,13 @@ def main(argv=None) -> int:
                     help="codon pairs of evidence ORFs a batch needs to train (default 100000, this project's choice); below: untrained, nothing dropped")
     ap.add_argument("--coding-model", metavar="IN", help="score with the counts of this file (--save-coding-model of a relative) instead of training")
     ap.add_argument("--save-coding-model", metavar="OUT", help="write the coding and background hexamer counts, summed over the batches")
+    ap.add_argument("--starts", action="store_true",
+                    help="with --coding: choose every complete ORF's start codon by a start-site score trained on the batch's evidence ORFs")
+    ap.add_argument("--start-rounds", type=int, default=4, help="training rounds of --starts (default 4, this project's choice; 1..16)")
+    ap.add_argument("--min-train-starts", type=int, default=200,
+                    help="evidence ORFs a batch needs to train the start model (default 200, this project's choice); below: untrained, nothing moved")
+    ap.add_argument("--start-model", metavar="IN", help="choose with the counts of this file (--save-start-model of a relative) instead of training")
+    ap.add_argument("--save-start-model", metavar="OUT", help="write the start model's counts of the last round, summed over the batches")
     a = ap.parse_args(argv)
     if a.free_orfs and a.orfs is None and a.faa is None:
         ap.error("--free-orfs needs --orfs or --faa")
@@ -464,13 +572,19 @@ def main(argv=None) -> int:
         ap.error("--coding needs --orfs or --faa")
     if not a.coding and (a.coding_model is not None or a.save_coding_model is not None or a.min_coding != 0 or a.min_train != 100000):
         ap.error("--min-coding, --min-train, --coding-model and --save-coding-model need --coding")
+    if a.starts and not a.coding:
+        ap.error("--starts needs --coding")
+    if not a.starts and (a.start_model is not None or a.save_start_model is not None or a.start_rounds != 4 or a.min_train_starts != 200):
+        ap.error("--start-rounds, --min-train-starts, --start-model and --save-start-model need --starts")
     from . import _native as N
     try:
         line = call_regions(a.D, a.q, a.o, a.m, a.M, a.g, a.O, a.merge_gap, a.min_score, a.min_len, a.all, a.gff,
                             orfs_out=a.orfs, faa_out=a.faa, start_codons=parse_start_codons(a.start_codons), select=a.select,
                             max_overlap=a.max_overlap, max_overlap_pct=a.max_overlap_pct,
                             free_min_res=a.min_res if a.free_orfs else None, coding=a.coding, min_coding=a.min_coding,
-                            min_train=a.min_train, coding_model_in=a.coding_model, save_coding_model=a.save_coding_model)
+                            min_train=a.min_train, coding_model_in=a.coding_model, save_coding_model=a.save_coding_model,
+                            starts=a.starts, start_rounds=a.start_rounds, min_train_starts=a.min_train_starts,
+                            start_model_in=a.start_model, save_start_model=a.save_start_model)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1

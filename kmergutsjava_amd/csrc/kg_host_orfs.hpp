@@ -16,6 +16,10 @@ struct kg_orfset {
     int64_t *d_coding = nullptr;        // count, null for a set that has no scores
     std::unique_ptr<kg_coding_model> coding_model;
     kg_coding_stats coding_st = {};
+    // kg_orfset_starts (kg_host_starts.hpp): the shift of every record in codons, the last round's counts and the statistics
+    int32_t *d_shift = nullptr;         // count, null for a set that is not from kg_orfset_starts
+    std::unique_ptr<kg_start_model> start_model;
+    kg_start_stats start_st = {};
 };
 
 namespace {
@@ -473,6 +477,7 @@ void kg_orfset_free(kg_orfset *s)
         dfree(s->tab, s->d_prot_start);
         dfree(s->tab, s->d_res);
         dfree(s->tab, s->d_coding);
+        dfree(s->tab, s->d_shift);
         if (s->own_tab) kg_table_close(s->tab);
     }
     delete s;

@@ -19,6 +19,7 @@
 #include "kg_regions.hpp"
 #include "kg_orfs.hpp"
 #include "kg_coding.hpp"
+#include "kg_starts.hpp"
 #include "kg_select.hpp"
 
 #include <fcntl.h>
@@ -46,4 +47,5 @@
 #include "kg_host_regions.hpp"
 #include "kg_host_orfs.hpp"
 #include "kg_host_coding.hpp"
+#include "kg_host_starts.hpp"
 #include "kg_host_select.hpp"

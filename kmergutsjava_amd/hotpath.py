@@ -222,7 +222,8 @@ class ScanResult:
 
     def orfs(self, seq, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, start_codons: int = 7,
              only_kept: bool = True, device_ptr: Optional[int] = None, free_min_res: Optional[int] = None, coding=None,
-             min_coding: int = 0, min_train_pairs: int = 100000):
+             min_coding: int = 0, min_train_pairs: int = 100000, starts=None, start_min_res: int = 100, start_rounds: int = 4,
+             min_train_starts: int = 200):
         """regions() and then the open reading frame around every region with its translated protein, on the GPU, without a
         host trip between the two (include/kmerguts_hip.h kg_regionset_orfs states the rule).  seq / offsets: what the scan was
         given; device_ptr: the address of the bytes in HBM instead of seq.
@@ -235,9 +236,16 @@ class ScanResult:
         log-odds and a free ORF below min_coding loses kept and gains _native.ORF_NONCODING (kg_orfset_coding, after
         free_min_res); True trains on the set's own evidence ORFs when they have min_train_pairs codon pairs.  The scores
         (int64 per record), the statistics and the counts of an own training are left in `coding_scores`, `coding_stats` and
-        `coding_model`."""
+        `coding_model`.
+        starts: None (or False: off), True or a (pos int32[20][4], type int32[4]) weights pair (start_weights): the start codon of
+        every movable record is chosen by the start-site score (kg_orfset_starts, after coding, which it needs: the score's
+        coding half is the coding step's table).  True trains on the set's own evidence ORFs in start_rounds rounds when there
+        are min_train_starts of them; when the coding step was untrained, so are the starts.  The regions bound the evidence
+        ORFs' moves, start_min_res everything else.  The shifts in codons (int32 per record), the statistics and the last
+        round's counts are left in `start_shifts`, `start_stats` and `start_model`; `coding_scores` are then the new set's."""
         lib = self._need()
         coding = _coding_arg(coding)
+        starts = _starts_arg(starts, coding)
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
         if off.shape != (self.stats["n_seqs"] + 1,):
             raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
@@ -258,6 +266,8 @@ class ScanResult:
             if coding is not None:
                 oh = _coding(oh, coding, min_coding, min_train_pairs, ptr, on_device, off)
                 self.coding_scores, self.coding_stats, self.coding_model = _coding_results(oh)
+            if starts is not None:
+                oh = self._starts(oh, h, coding, starts, start_codons, start_min_res, start_rounds, min_train_starts, ptr, on_device, off)
             orfs, prot_start, residues, self.orf_stats = _take_orfset(oh, False)
         except BaseException:
             lib.kg_regionset_free(h)
@@ -268,7 +278,8 @@ class ScanResult:
     def select(self, offsets, seq=None, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, orfs: bool = False,
                start_codons: int = 7, only_kept: bool = True, device_ptr: Optional[int] = None, max_overlap: int = 60,
                max_overlap_pct: int = 50, free_min_res: Optional[int] = None, coding=None, min_coding: int = 0,
-               min_train_pairs: int = 100000):
+               min_train_pairs: int = 100000, starts=None, start_min_res: int = 100, start_rounds: int = 4,
+               min_train_starts: int = 200):
         """regions() -- with orfs=True, orfs() -- and then the non-overlapping selection among the kept records, on the GPU and
         without a host trip or a second scan in between (include/kmerguts_hip.h kg_regionset_select states the rule).  The
         candidates are the regions' extents, or with orfs=True the ORFs' extents.
@@ -278,13 +289,16 @@ class ScanResult:
         free_min_res (with orfs=True): the evidence-free candidates are appended on the device before the selection, as orfs()
         appends them; orfs, prot_start, residues and selection then hold them behind the regions' records.
         coding, min_coding, min_train_pairs (with orfs=True): as orfs() takes them, applied after free_min_res and before the
-        selection, so a non-coding free ORF is not eligible and suppresses nothing."""
+        selection, so a non-coding free ORF is not eligible and suppresses nothing.
+        starts, start_min_res, start_rounds, min_train_starts (with coding): as orfs() takes them, applied after coding and before
+        the selection, which therefore sees the new extents."""
         lib = self._need()
         if free_min_res is not None and not orfs:
             raise ValueError("free_min_res needs orfs=True: the free candidates are ORFs")
         coding = _coding_arg(coding)
         if coding is not None and not orfs:
             raise ValueError("coding needs orfs=True: the scores are the ORFs'")
+        starts = _starts_arg(starts, coding)
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
         if off.shape != (self.stats["n_seqs"] + 1,):
             raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
@@ -306,6 +320,9 @@ class ScanResult:
                 if coding is not None:
                     oh = _coding(oh, coding, min_coding, min_train_pairs, ptr, on_device, off)
                     self.coding_scores, self.coding_stats, self.coding_model = _coding_results(oh)
+                if starts is not None:
+                    oh = self._starts(oh, h, coding, starts, start_codons, start_min_res, start_rounds, min_train_starts, ptr,
+                                      on_device, off)
                 N.check(lib.kg_orfset_select(oh, C.byref(sp), C.byref(sh)))
             else:
                 N.check(lib.kg_regionset_select(h, C.byref(sp), C.byref(sh)))
@@ -325,6 +342,21 @@ class ScanResult:
         if orfs:
             return regs, start, orf_recs, prot_start, residues, sel
         return regs, start, sel
+
+    def _starts(self, oh, rh, coding, starts, start_codons, min_res, rounds, min_train_starts, ptr, on_device, off):
+        """kg_orfset_starts behind the coding step of orfs() / select(): -> the new set's handle; the results into self."""
+        if coding is True:
+            # the table the coding step trained and used; none when it was untrained, and then the starts are untrained too
+            trained = self.coding_stats["trained"] != 0
+            table = coding_table(*self.coding_model) if trained else np.zeros(N.CODING_BINS, dtype=np.int32)
+            if not trained and starts is True:
+                min_train_starts = 1 << 62
+        else:
+            table = coding
+        oh = _starts(oh, rh, table, None if starts is True else starts, min_res, start_codons, rounds, min_train_starts, ptr, on_device, off)
+        self.start_shifts, self.start_stats, self.start_model = _starts_results(oh)
+        self.coding_scores = _coding_results(oh)[0]
+        return oh
 
     def close(self) -> None:
         if self._h:
@@ -832,6 +864,129 @@ def _coding_results(h):
         lib.kg_orfset_free(h)
         h.value = None
         raise
+
+
+def _weights_arg(weights):
+    """A (pos, type) weights pair -> a KgStartWeights."""
+    try:
+        pos, typ = weights
+    except (TypeError, ValueError):
+        raise ValueError("start weights are a pair (pos int32[%d][4], type int32[4])" % N.START_WINDOW) from None
+    pos = np.ascontiguousarray(pos, dtype=np.int32)
+    typ = np.ascontiguousarray(typ, dtype=np.int32)
+    if pos.shape != (N.START_WINDOW, 4) or typ.shape != (4,):
+        raise ValueError("start weights are a pair (pos int32[%d][4], type int32[4])" % N.START_WINDOW)
+    w = N.KgStartWeights()
+    C.memmove(w.pos, pos.ctypes.data, pos.nbytes)
+    C.memmove(w.type, typ.ctypes.data, typ.nbytes)
+    return w
+
+
+def _starts_arg(starts, coding):
+    """The starts= of ScanResult.orfs / select, checked before any set is made: None or False -> None (off), True -> True (train
+    on the set), anything else -> the KgStartWeights of the pair it is.  coding: what _coding_arg gave."""
+    if starts is None or starts is False:
+        return None
+    if coding is None:
+        raise ValueError("starts needs coding: the start-site score's coding half is the coding step's table")
+    return True if starts is True else _weights_arg(starts)
+
+
+def _start_model_arrays(m):
+    return (np.array(m.chosen, dtype=np.int64).reshape(N.START_WINDOW, 4), np.array(m.cand, dtype=np.int64).reshape(N.START_WINDOW, 4),
+            np.array(m.type_chosen, dtype=np.int64), np.array(m.type_cand, dtype=np.int64))
+
+
+def _starts(oh, rh, table, weights, min_res: int, start_codons: int, rounds: int, min_train_starts: int, ptr, on_device: int, off):
+    """kg_orfset_starts on the ORF set oh, which is freed: -> the new set's handle (it lives in the same context).  rh: the region
+    set's handle or None; weights: a KgStartWeights or None."""
+    lib = N.load()
+    sp = N.KgStartParams(int(min_res), int(start_codons), int(rounds), 0, int(min_train_starts))
+    new = C.c_void_p()
+    try:
+        N.check(lib.kg_orfset_starts(oh, C.byref(sp), table.ctypes.data, None if weights is None else C.addressof(weights), rh, ptr,
+                                     on_device, off.ctypes.data, off.size - 1, C.byref(new)))
+    finally:
+        lib.kg_orfset_free(oh)          # (the new set holds copies: the given one is not needed any more)
+        oh.value = None
+    return new
+
+
+def _starts_results(h):
+    """-> (shifts int32[n], statistics, (chosen, cand, type_chosen, type_cand) counts) of a set made by kg_orfset_starts; the set is
+    freed when a call fails."""
+    lib = N.load()
+    try:
+        n = int(lib.kg_orfset_count(h))
+        shifts = np.zeros(n, dtype=np.int32)
+        N.check(lib.kg_orfset_start_shifts(h, 0, n, shifts.ctypes.data if n else None))
+        st, m = N.KgStartStats(), N.KgStartModel()
+        N.check(lib.kg_orfset_start_stats(h, C.byref(st)))
+        N.check(lib.kg_orfset_start_model(h, C.byref(m)))
+        return shifts, st.as_dict(), _start_model_arrays(m)
+    except BaseException:
+        lib.kg_orfset_free(h)
+        h.value = None
+        raise
+
+
+def start_weights(chosen, cand, type_chosen, type_cand):
+    """The weights of a start model's counts (kg_start_weights_from; include/kmerguts_hip.h states the rule: integer log-odds of
+    the chosen starts' upstream bases and types against all candidates').  Host code: no GPU takes part.
+    -> (pos int32[20][4], type int32[4])."""
+    m = N.KgStartModel()
+    for name, src, shape in (("chosen", chosen, (N.START_WINDOW, 4)), ("cand", cand, (N.START_WINDOW, 4)),
+                             ("type_chosen", type_chosen, (4,)), ("type_cand", type_cand, (4,))):
+        a = np.ascontiguousarray(src, dtype=np.int64)
+        if a.shape != shape:
+            raise ValueError("%s counts are int64%s" % (name, "".join("[%d]" % d for d in shape)))
+        C.memmove(getattr(m, name), a.ctypes.data, a.nbytes)
+    w = N.KgStartWeights()
+    N.check(N.load().kg_start_weights_from(C.byref(m), C.byref(w)))
+    return np.array(w.pos, dtype=np.int32).reshape(N.START_WINDOW, 4), np.array(w.type, dtype=np.int32)
+
+
+def choose_starts(table, orfs, seq, offsets, weights=None, limits=None, min_res: int = 100, start_codons: int = 7, rounds: int = 4,
+                  min_train_starts: int = 200, device: int = 0, stats: Optional[dict] = None, model: Optional[list] = None):
+    """The start codon of every movable caller-held ORF record, chosen by the start-site score on the GPU and without a table
+    (kg_starts_orfs; include/kmerguts_hip.h states the rule).  table: the int32[4096] coding table; weights: None to train on the
+    records in `rounds` rounds, or a (pos, type) pair; limits: None or int32[n], the largest k of every record, -1 for none.
+    -> (orfs, shifts): the records after the move and the shift of each in codons.  `stats`, when given, receives the call's
+    counts and device times; `model`, when given, is extended by the last round's (chosen, cand, type_chosen, type_cand)."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_seqs + 1]")
+    t = _table_arg(table)
+    o = np.ascontiguousarray(orfs, dtype=N.ORF_DTYPE)
+    arr = _seq_bytes(seq, off)
+    w = None if weights is None else _weights_arg(weights)
+    lim = None
+    if limits is not None:
+        lim = np.ascontiguousarray(limits, dtype=np.int32)
+        if lim.shape != o.shape:
+            raise ValueError("limits are int32[n], one per record")
+    sp = N.KgStartParams(int(min_res), int(start_codons), int(rounds), 0, int(min_train_starts))
+    out = np.zeros(o.size, dtype=N.ORF_DTYPE)
+    shifts = np.zeros(o.size, dtype=np.int32)
+    st, m = N.KgStartStats(), N.KgStartModel()
+    N.check(N.load().kg_starts_orfs(device, C.byref(sp), t.ctypes.data, None if w is None else C.addressof(w),
+                                    o.ctypes.data if o.size else None, o.size, lim.ctypes.data if lim is not None and o.size else None,
+                                    arr.ctypes.data if arr.size else None, off.ctypes.data, off.size - 1,
+                                    out.ctypes.data if o.size else None, shifts.ctypes.data if o.size else None, C.byref(m), C.byref(st)))
+    if stats is not None:
+        stats.update(st.as_dict())
+    if model is not None:
+        model.extend(_start_model_arrays(m))
+    return out, shifts
+
+
+def start_counts(table, orfs, seq, offsets, limits=None, min_res: int = 100, start_codons: int = 7, rounds: int = 4, device: int = 0):
+    """The counts of a start model trained on caller-held ORF records in `rounds` rounds (kg_starts_orfs without weights and
+    with min_train_starts = 0): -> (chosen int64[20][4], cand int64[20][4], type_chosen int64[4], type_cand int64[4]), what the
+    last round counted before it chose."""
+    model: list = []
+    choose_starts(table, orfs, seq, offsets, None, limits, min_res, start_codons, rounds, 0, device, None, model)
+    return tuple(model)
 
 
 def coding_table(coding, background) -> np.ndarray:
