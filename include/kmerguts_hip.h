@@ -570,8 +570,8 @@ void kg_regionset_free(kg_regionset *s);
  *      given, mirrored for '-'; n_res = min(e, n_f) - b; start_codon -- 0 none, 1 ATG, 2 GTG, 3 TTG; first_inner -- the index in
  *      the protein of codon i* when interrupted, else -1; flags -- KG_ORF_HAS_STOP when e < n_f, KG_ORF_PARTIAL5 when u == -1,
  *      KG_ORF_INTERRUPTED, KG_ORF_MULTI_FRAME when the region has more than one frame bit; fI, score, kept -- copied from the
- *      region.  A multi-frame region gets its best frame's ORF and will usually be interrupted: frameshifts are reported, not
- *      repaired.
+ *      region.  A multi-frame region gets its best frame's ORF and will usually be interrupted: this stage reports
+ *      frameshifts, kg_regionset_repair below repairs them.
  *   5. Protein.  The residues of codons b .. min(e, n_f) - 1: each is the genetic code's letter (KGJ:88-93), an inner stop is
  *      '*', an unknown codon is 'X', and residue 0 is 'M' whenever start_codon != 0.  Proteins are laid end to end in ORF order
  *      behind prot_start[n_orfs + 1] (int64).  With only_kept = 1 (the default), an ORF whose region is not kept has length 0
@@ -632,6 +632,97 @@ int kg_orfset_prot_start(const kg_orfset *s, int64_t *dst);
 int kg_orfset_residues(const kg_orfset *s, int64_t first, int64_t count, uint8_t *dst);
 int kg_orfset_stats(const kg_orfset *s, kg_orf_stats *out);
 void kg_orfset_free(kg_orfset *s);
+
+/* ---- frameshift repair: the frames of a multi-frame region joined into one protein (kernels: kg_repair.hpp) ----
+ *
+ * The reference stops at the CALL lines; this rule is the project's own.  Integers only: the device's bytes equal a plain-loop
+ * model's.  kg_regionset_orfs gives a region with CALLs in two frames its best frame's ORF alone, half protein and half
+ * read-through; this stage follows the CALLs from frame to frame instead.
+ * Input: a region set, its index-aligned ORF set, the CALL list the region set was made from, the batch's bytes and
+ * offsets[n_seqs + 1].  Strand coordinates, codon j of frame f, n_f and the codon classes are rules 1 of the regions and ORF
+ * sections.
+ *   1. Candidates.  A region is a candidate when it is kept and has more than one frame bit.  Its CALLs are taken in the region
+ *      stage's group order, by x0 and then by index in calls[].  CALLs with count < min_count are ignored for the chain only.
+ *   2. Segments.  A segment is a maximal run of consecutive remaining CALLs of one frame.  Segment k has frame f_k, with
+ *      f_k != f_{k+1}; A_k, the x0 of its first CALL; C_k, the largest x1 among its CALLs.  One segment (or no remaining CALL):
+ *      the region is `single`.  More than max_junctions + 1 segments: it is `skipped`.  Both are left untouched.
+ *   3. Junction k, between segments k and k+1, with p = f_k and q = f_{k+1}.  lp = (C_k - 2 - p)/3.  tp is the smallest stop
+ *      j > lp of frame p, else n_p.  hi = p + 3 tp.  gq = (A_{k+1} - q)/3.  sq is the largest stop j < gq of frame q, else -1.
+ *      lo = q + 3 (sq + 1).  mid = floor((C_k + 1 + A_{k+1}) / 2) in int64: the middle of the evidence gap, or of the overlap.
+ *      If lo > hi the chain has failed.  Otherwise J_k = min(max(mid, lo), hi).  The chain also fails when J_k >= J_{k+1} for
+ *      some k, or when a part below is empty.
+ *   4. Ends.  j0 = (A_1 - f_1)/3.  u is the largest stop < j0 of frame f_1, else -1.  b is the smallest start of the mask in
+ *      (u, j0], else u + 1.  jl = (C_m - 2 - f_m)/3.  e is the smallest stop > jl of frame f_m, else n_{f_m}.
+ *   5. Parts.  Part 1 is the codons j >= b of f_1 with f_1 + 3j + 3 <= J_1.  Part k is the codons of f_k with
+ *      J_{k-1} <= f_k + 3j and f_k + 3j + 3 <= J_k.  Part m is the codons of f_m with f_m + 3j >= J_{m-1} and
+ *      j < min(e, n_{f_m}).  The protein is the parts end to end under the ORF section's rule 5: 'M' first when a start was
+ *      found, 'X' for an unknown codon, '*' for a stop.  A stop can only lie inside a segment's own evidence span.  The one or
+ *      two nucleotides between two parts give no residue, and the parts are disjoint codons inside left .. right, so
+ *      3 * n_res <= right - left + 1 still holds, and kg_orfset_coding and kg_orfset_starts accept the record.
+ *   6. Record, 48 bytes as before.  frame = f_1.  The extent runs from codon b of f_1 to the stop codon e of f_m, or to
+ *      n_f - 1 when e == n_f; it is mirrored on '-'.  n_res is the parts' total.  start_codon is as in rule 4 of the ORF section.
+ *      first_inner is the first '*' of the new protein, or -1.  flags are KG_ORF_HAS_STOP and KG_ORF_PARTIAL5 from the new
+ *      ends, KG_ORF_MULTI_FRAME, the new KG_ORF_REPAIRED, and KG_ORF_INTERRUPTED always set.  A repaired record does not read in
+ *      one frame.  With INTERRUPTED set, coding_is_training and the movable test of kg_starts.hpp go on leaving it alone with
+ *      their code unchanged.  fI, score and kept are copied.  A failed, single or skipped region keeps its given record and
+ *      protein.
+ *   7. Junction record.  kg_junction is six int32, 24 bytes: orf; pos, which is J_k as a 0-based contig coordinate,
+ *      L - 1 - J_k on '-'; from_frame; to_frame; res, the protein index of the 3' part's first residue;
+ *      gap = A_{k+1} - C_k - 1, negative when the evidence overlaps.  Records are in (orf, k) order, with
+ *      junction_start[n_orfs + 1].
+ *   8. Independence.  The output depends only on (regions, ORFs, CALLs, bytes, offsets, parameters): not on launch geometry,
+ *      tile size or batch neighbours.  C_k is an integer maximum, so order cannot matter.
+ * Parameters kg_repair_params { start_codons (0..7, default 7), min_count (>= 0, default 0), max_junctions (1..8, default 4),
+ * reserved == 0 }; anything else is KG_ERR_ARG.  The defaults are this project's choice.
+ * kg_regionset_repair gives a NEW ORF set in the region set's context, as kg_orfset_add_free does: in it the record and protein
+ * of every repaired region are replaced by the chain; every other record, its protein bytes and the only_kept zero lengths are
+ * unchanged byte for byte.  The given sets stay valid; the new one is freed before them.  It runs before kg_orfset_add_free:
+ * the ORF set must have exactly the region set's records.  kg_orfset_stats of the new set is the given set's with residues,
+ * complete, interrupted and partial5 brought up to date.  The junction list stays with the new set only: the sets that
+ * kg_orfset_add_free, kg_orfset_coding and kg_orfset_starts make from it keep the records' indices but not the list.
+ * kg_result_repair passes the result's device CALLs.  The coding score of a repaired record (rule 2 of the coding section) is
+ * that of its first frame read straight through its extent.
+ * Validation.  The CALL list must be the set's: every CALL has to fall inside exactly one region of its group, and every
+ * region's count and summed count have to equal its n_calls and score; otherwise KG_ERR_ARG, and the message names the first
+ * offending CALL or region.  The CALL errors of the regions section apply as well.
+ * Errors: KG_ERR_ARG also for bad params, null pointers, an ORF set that is not index-aligned with the region set or of another
+ * context, n_seqs that is not the set's, decreasing offsets; KG_ERR_LIMIT for 2^32 or more CALLs or residues; KG_ERR_BUSY
+ * while a kg_scan* is in flight on the set's table; KG_ERR_NOMEM.  A bad record is never used as an index.  Zero regions,
+ * CALLs and sequences are valid.  Device allocations come from the context's block cache, so KG_TEST_FAIL_ALLOC applies;
+ * everything but the new set's arrays and the two junction arrays is back in the cache on every path out. */
+#define KG_ORF_REPAIRED   128u
+typedef struct kg_repair_params { int32_t start_codons; int32_t min_count; int32_t max_junctions; int32_t reserved; } kg_repair_params;
+typedef struct kg_junction {     /* 24 B */
+    int32_t  orf;          /* index in the ORF set                                     */
+    int32_t  pos;          /* J_k: 0-based on the contig as given                      */
+    int32_t  from_frame;
+    int32_t  to_frame;
+    int32_t  res;          /* protein index of the 3' part's first residue             */
+    int32_t  gap;          /* A_{k+1} - C_k - 1                                        */
+} kg_junction;
+typedef struct kg_repair_stats {
+    int64_t candidates;    /* kept regions with more than one frame bit                */
+    int64_t repaired, failed, single, skipped;
+    int64_t junctions;
+    int64_t residues;      /* of the repaired proteins                                 */
+    float   ms;            /* device time of the call's kernels                        */
+    int32_t reserved;
+} kg_repair_stats;
+/* calls[n_calls]: the region set's CALL list, in device memory when calls_on_device != 0; seq, offsets as kg_regionset_orfs
+   takes them */
+int kg_regionset_repair(kg_regionset *set, kg_orfset *orfs, const kg_call *calls, int calls_on_device, int64_t n_calls,
+                        const kg_repair_params *p, const uint8_t *seq, int seq_on_device, const int64_t *offsets, int64_t n_seqs,
+                        kg_orfset **out);
+/* the same with the device CALLs of the DNA result the region set was made from */
+int kg_result_repair(kg_result *r, kg_regionset *set, kg_orfset *orfs, const kg_repair_params *p, const uint8_t *seq,
+                     int seq_on_device, const int64_t *offsets, int64_t n_seqs, kg_orfset **out);
+/* the junction list of a set made by kg_regionset_repair (KG_ERR_ARG on any other set, 0 for the count) */
+int64_t kg_orfset_junctions_count(const kg_orfset *s);
+/* records [first, first + count) into dst (host or device memory) */
+int kg_orfset_junctions_copy(const kg_orfset *s, int64_t first, int64_t count, kg_junction *dst);
+/* junction_start[count of ORFs + 1] into dst (host or device memory) */
+int kg_orfset_junctions_start(const kg_orfset *s, int64_t *dst);
+int kg_orfset_junctions_stats(const kg_orfset *s, kg_repair_stats *out);
 
 /* ---- evidence-free open reading frames: every long stop-free run of the six frames (kernels: kg_orfs.hpp) ----
  *

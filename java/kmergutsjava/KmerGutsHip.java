@@ -199,6 +199,25 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_repair_params (kg_regionset_repair / kg_result_repair); this project's defaults: 7, 0, 4 and 0. */
+    class KgRepairParams extends Structure {
+        public int start_codons, min_count, max_junctions, reserved;
+        public KgRepairParams() {
+            setFieldOrder(new String[] {"start_codons", "min_count", "max_junctions", "reserved"});
+        }
+    }
+
+    /** struct kg_repair_stats */
+    class KgRepairStats extends Structure {
+        public long candidates, repaired, failed, single, skipped, junctions, residues;
+        public float ms;
+        public int reserved;
+        public KgRepairStats() {
+            setFieldOrder(new String[] {"candidates", "repaired", "failed", "single", "skipped", "junctions", "residues", "ms",
+                    "reserved"});
+        }
+    }
+
     /** struct kg_start_params (kg_orfset_starts / kg_starts_orfs); this project's defaults: 100, 7, 4, 0 and 200. */
     class KgStartParams extends Structure {
         public int min_res, start_codons, rounds, reserved;
@@ -436,6 +455,18 @@ public interface KmerGutsHip extends Library {
     /** limits: int[n] (-1: none) or null; out: n packed 48-byte kg_orf records; model, stats: may be null */
     int kg_starts_orfs(int device, KgStartParams params, int[] table, KgStartWeights weights, Pointer orfs, long n, int[] limits,
                        Pointer seq, long[] offsets, long nSeqs, Pointer out, int[] shifts, KgStartModel model, KgStartStats stats);
+    /** Frameshift repair (run before kg_orfset_add_free): a NEW ORF set in which the record and protein of every multi-frame
+     *  region are the chain through its frames (flag KG_ORF_REPAIRED = 128), and the junction list.  calls: the region set's
+     *  packed 24-byte kg_call records, in device memory when callsOnDevice != 0.  Free the new set before the given ones. */
+    int kg_regionset_repair(Pointer set, Pointer orfs, Pointer calls, int callsOnDevice, long nCalls, KgRepairParams params, Pointer seq,
+                            int seqOnDevice, long[] offsets, long nSeqs, PointerByReference out);
+    int kg_result_repair(Pointer result, Pointer set, Pointer orfs, KgRepairParams params, Pointer seq, int seqOnDevice, long[] offsets,
+                         long nSeqs, PointerByReference out);
+    long kg_orfset_junctions_count(Pointer set);
+    /** dst: count packed 24-byte kg_junction records (int orf, pos, from_frame, to_frame, res, gap) */
+    int kg_orfset_junctions_copy(Pointer set, long first, long count, Pointer dst);
+    int kg_orfset_junctions_start(Pointer set, long[] dst);                          // long[n_orfs + 1]
+    int kg_orfset_junctions_stats(Pointer set, KgRepairStats out);
     /** the non-overlapping selection among the kept regions / ORFs of a set; free the select set before the set it came from */
     int kg_regionset_select(Pointer set, KgSelectParams params, PointerByReference out);
     int kg_orfset_select(Pointer set, KgSelectParams params, PointerByReference out);

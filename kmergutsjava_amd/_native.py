@@ -41,6 +41,8 @@ EXPORTS = (
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
     "kg_orfset_residues", "kg_orfset_stats", "kg_orfset_free", "kg_orfs_free", "kg_orfset_add_free",
+    "kg_regionset_repair", "kg_result_repair", "kg_orfset_junctions_count", "kg_orfset_junctions_copy", "kg_orfset_junctions_start",
+    "kg_orfset_junctions_stats",
     "kg_orfset_coding", "kg_orfset_coding_scores", "kg_orfset_coding_stats", "kg_orfset_coding_model", "kg_coding_table",
     "kg_coding_counts_orfs", "kg_coding_score_orfs",
     "kg_orfset_starts", "kg_orfset_start_shifts", "kg_orfset_start_stats", "kg_orfset_start_model", "kg_start_weights_from",
@@ -83,6 +85,11 @@ ORF_HAS_STOP, ORF_PARTIAL5, ORF_INTERRUPTED, ORF_MULTI_FRAME = 1, 2, 4, 8
 ORF_FREE = 16               # an evidence-free candidate (kg_orfs_free / kg_orfset_add_free)
 ORF_NONCODING = 32          # a free ORF that kg_orfset_coding dropped (its kept is 0)
 ORF_START_MOVED = 64        # a record whose start kg_orfset_starts moved downstream
+ORF_REPAIRED = 128          # a record kg_regionset_repair replaced by the chain through its region's frames
+# struct kg_junction (kg_regionset_repair): where a repaired ORF changes frame
+JUNCTION_DTYPE = np.dtype([("orf", "<i4"), ("pos", "<i4"), ("from_frame", "<i4"), ("to_frame", "<i4"), ("res", "<i4"), ("gap", "<i4")])
+assert JUNCTION_DTYPE.itemsize == 24
+REPAIR_MAX_JUNCTIONS = 8    # kg_repair.hpp kRepairMaxJunctions: the largest max_junctions
 START_WINDOW = 20           # upstream positions of a start model
 START_CHUNK = 1024          # kg_starts.hpp kStartChunk: the codons of one workgroup of the codon passes (tests aim at its edges)
 CODING_BINS = 4096          # hexamer indices: the entries of a coding model's two count arrays and of a score table
@@ -207,6 +214,20 @@ class KgFreeParams(C.Structure):
 
 
 FREE_PARAMS = KgFreeParams
+
+
+class KgRepairParams(C.Structure):
+    """struct kg_repair_params (kg_regionset_repair / kg_result_repair)."""
+    _fields_ = [("start_codons", C.c_int32), ("min_count", C.c_int32), ("max_junctions", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgRepairStats(C.Structure):
+    """struct kg_repair_stats."""
+    _fields_ = [("candidates", C.c_int64), ("repaired", C.c_int64), ("failed", C.c_int64), ("single", C.c_int64),
+                ("skipped", C.c_int64), ("junctions", C.c_int64), ("residues", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
 class KgCodingParams(C.Structure):
@@ -389,6 +410,13 @@ def load() -> C.CDLL:
     lib.kg_orfset_free.restype = None
     lib.kg_orfs_free.argtypes = [C.c_int, C.POINTER(KgFreeParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
     lib.kg_orfset_add_free.argtypes = [vp, C.POINTER(KgFreeParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
+    lib.kg_regionset_repair.argtypes = [vp, vp, vp, C.c_int, C.c_int64, C.POINTER(KgRepairParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
+    lib.kg_result_repair.argtypes = [vp, vp, vp, C.POINTER(KgRepairParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
+    lib.kg_orfset_junctions_count.argtypes = [vp]
+    lib.kg_orfset_junctions_count.restype = C.c_int64
+    lib.kg_orfset_junctions_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.kg_orfset_junctions_start.argtypes = [vp, vp]
+    lib.kg_orfset_junctions_stats.argtypes = [vp, C.POINTER(KgRepairStats)]
     lib.kg_orfset_coding.argtypes = [vp, C.POINTER(KgCodingParams), vp, vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
     lib.kg_orfset_coding_scores.argtypes = [vp, C.c_int64, C.c_int64, vp]
     lib.kg_orfset_coding_stats.argtypes = [vp, C.POINTER(KgCodingStats)]

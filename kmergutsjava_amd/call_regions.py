@@ -4,6 +4,7 @@
     python -m kmergutsjava_amd.call_regions -D KmerData -q contigs.fna[.gz] -o regions.tsv [-m 5] [-M 0] [-g 200] [-O]
                                             [--merge-gap 600] [--min-score 0] [--min-len 0] [--all] [--gff]
                                             [--orfs ORFS.tsv] [--faa PROTEINS.faa] [--start-codons ATG,GTG,TTG]
+                                            [--repair [--repair-min-count 0] [--max-junctions 4] [--shifts SHIFTS.tsv]]
                                             [--select [--max-overlap 60] [--max-overlap-pct 50]]
                                             [--free-orfs [--min-res 100]]
                                             [--coding [--min-coding 0] [--min-train 100000] [--coding-model IN]
@@ -29,6 +30,20 @@ with start the start codon or `-`, and flags the words stop, partial5, interrupt
 make_signatures -p read; an ORF with the contig, strand, left and right of an earlier written one is written once, under the
 region with the largest score (ties: the first).  With either flag the summary line gains `, orfs: N, complete: C,
 interrupted: I` (complete: stop, start and not interrupted).
+
+--repair (with --orfs or --faa) repairs frameshifted genes on the GPU (kg_result_repair; include/kmerguts_hip.h states the
+rule, integers only): a kept region with CALLs in more than one frame gets, in place of its best frame's ORF, the chain that
+follows its CALLs from frame to frame, each junction put between the stops that bound it, as near the middle of the evidence gap
+as they allow.  CALLs with fewer than --repair-min-count hits take no part; a region that changes frame more than
+--max-junctions times (default 4, at most 8) is left alone.  The step runs before --free-orfs, so --select, --coding and --starts
+see the new extents.  A repaired ORF's line gains the flag word `repaired` (and always has `interrupted`: it does not read in
+one frame, so --coding does not train on it and --starts does not move it); the coding score printed for it is that of its first
+frame read straight through its extent.  --shifts writes one line per junction of a written repaired ORF:
+    contig_id<TAB>left+1<TAB>right+1<TAB>strand<TAB>function<TAB>junction pos+1<TAB>from_frame<TAB>to_frame<TAB>residue<TAB>gap
+with residue the 1-based protein position of the first residue behind the junction and gap the nucleotides between the two
+frames' evidence (negative: it overlaps).  The summary line gains `, repaired: N, unrepaired: M` behind the ORF counts
+(unrepaired: multi-frame regions whose chain failed, had one frame left or too many junctions).  Without --repair every output
+is byte for byte what it was.
 
 --select makes the output a gene set: among the kept candidates -- the ORFs' extents with --orfs or --faa, else the regions'
 extents -- the non-overlapping selection is taken on the GPU (kg_orfset_select / kg_regionset_select; include/kmerguts_hip.h
@@ -157,7 +172,7 @@ def format_regions(ids, regs, fnames, write_all: bool = False, gff: bool = False
 
 
 START_NAMES = (b"ATG", b"GTG", b"TTG")
-FLAG_WORDS = ((1, b"stop"), (2, b"partial5"), (4, b"interrupted"), (8, b"multi-frame"), (16, b"free"), (32, b"noncoding"), (64, b"moved"))
+FLAG_WORDS = ((1, b"stop"), (2, b"partial5"), (4, b"interrupted"), (8, b"multi-frame"), (16, b"free"), (32, b"noncoding"), (64, b"moved"), (128, b"repaired"))
 FREE_NAME = b"hypothetical protein"
 NONCODING = 32
 MOVED = 64
@@ -313,6 +328,25 @@ def format_orfs(ids, regs, orfs, fnames, write_all: bool = False, sel=None, free
     return b"".join(_by_contig(lines, flines))
 
 
+def repair_summary(repaired: int, candidates: int) -> str:
+    """What the summary line gains with --repair."""
+    return ", repaired: %d, unrepaired: %d" % (repaired, candidates - repaired)
+
+
+def format_shifts(ids, regs, orfs, fnames, junctions, write_all: bool = False, sel=None) -> bytes:
+    """The junction records of --repair (JUNCTION_DTYPE, `orf` indexing orfs) as text: one line per junction of a written ORF."""
+    lines = []
+    for j in junctions:
+        i = int(j["orf"])
+        if not _written(regs[i], write_all, sel, i):
+            continue
+        o = orfs[i]
+        lines.append(b"%s\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\n" % (ids[int(o["seq"])], o["left"] + 1, o["right"] + 1, b"-" if o["strand"] else b"+",
+                                                                     _fname(fnames, int(o["fI"])), j["pos"] + 1, j["from_frame"], j["to_frame"],
+                                                                     j["res"] + 1, j["gap"]))
+    return b"".join(lines)
+
+
 def _fasta(ids, key, name: bytes, p: bytes) -> bytes:
     head = b">%s_%d_%d_%s %s\n" % (ids[key[0]], key[2] + 1, key[3] + 1, b"-" if key[1] else b"+", name)
     return head + b"".join(p[k:k + 60] + b"\n" for k in range(0, len(p), 60))
@@ -359,10 +393,12 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                  start_codons: int = 7, select: bool = False, max_overlap: int = 60, max_overlap_pct: int = 50,
                  free_min_res: int = None, coding: bool = False, min_coding: int = 0, min_train: int = 100000,
                  coding_model_in: str = None, save_coding_model: str = None, starts: bool = False, start_rounds: int = 4,
-                 min_train_starts: int = 200, start_model_in: str = None, save_start_model: str = None) -> str:
+                 min_train_starts: int = 200, start_model_in: str = None, save_start_model: str = None, repair: bool = False,
+                 repair_min_count: int = 0, max_junctions: int = 4, shifts_out: str = None) -> str:
     """Write the regions (and, with orfs_out / faa_out, their open reading frames and proteins; with free_min_res also the
     evidence-free ORFs of at least that many residues; with coding the ORFs' coding scores, the non-coding free ORFs dropped;
-    with starts the start codons chosen by the start-site score); returns the summary line."""
+    with starts the start codons chosen by the start-site score; with repair the multi-frame regions' ORFs joined across their
+    frames first, and their junctions written to shifts_out); returns the summary line."""
     want_orfs = orfs_out is not None or faa_out is not None
     if free_min_res is not None and not want_orfs:
         raise ValueError("--free-orfs needs --orfs or --faa: free ORFs are written to those files only")
@@ -370,6 +406,10 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         raise ValueError("--coding needs --orfs or --faa: the scores are the ORFs'")
     if (coding_model_in is not None or save_coding_model is not None) and not coding:
         raise ValueError("--coding-model and --save-coding-model need --coding")
+    if repair and not want_orfs:
+        raise ValueError("--repair needs --orfs or --faa: it rewrites ORFs")
+    if shifts_out is not None and not repair:
+        raise ValueError("--shifts needs --repair")
     if starts and not coding:
         raise ValueError("--starts needs --coding: the start-site score's coding half is the coding step's table")
     if (start_model_in is not None or save_start_model is not None) and not starts:
@@ -397,6 +437,9 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
             starts_arg = hotpath.start_weights(*parse_start_model(_read(start_model_in), start_model_in))
         ckw.update(starts=starts_arg, start_min_res=100 if free_min_res is None else free_min_res, start_rounds=start_rounds,
                    min_train_starts=min_train_starts)
+    if repair:
+        ckw.update(repair=True, repair_min_count=repair_min_count, max_junctions=max_junctions)
+    jparts, n_repaired, n_candidates = [], 0, 0                 # the junction records, `orf` counted over all batches
     shparts, fshparts, strained = [], [], []                    # the shifts, and every batch's kg_start_stats.trained
     start_sum = [np.zeros((20, 4), np.int64), np.zeros((20, 4), np.int64), np.zeros(4, np.int64), np.zeros(4, np.int64)]
     cparts, fcparts, trained = [], [], []                       # the coding scores, and every batch's kg_coding_stats.trained
@@ -440,6 +483,12 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                 flens.append(np.diff(pstart[nr:]))
                 fresidues.append(res[pstart[nr]:])
                 n_free += len(orfs) - nr
+                if repair:
+                    junc = r.junctions.copy()
+                    junc["orf"] += n_before
+                    jparts.append(junc)
+                    n_repaired += r.repair_stats["repaired"]
+                    n_candidates += r.repair_stats["candidates"]
                 if coding:
                     cparts.append(r.coding_scores[:nr])
                     fcparts.append(r.coding_scores[nr:])
@@ -509,6 +558,12 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                                    fnames, write_all, sel, free, free_sel, fstart,
                                    np.concatenate(fresidues) if fresidues else np.zeros(0, np.uint8)))
         line += orf_summary(orfs)
+        if repair:
+            line += repair_summary(n_repaired, n_candidates)
+            if shifts_out is not None:
+                with open(shifts_out, "wb") as f:
+                    f.write(format_shifts(ids, regs, orfs, fnames, np.concatenate(jparts) if jparts else np.zeros(0, hotpath.N.JUNCTION_DTYPE),
+                                          write_all, sel))
     if select:
         line += select_summary(sel if free_sel is None else np.concatenate([sel, free_sel]))
     if free is not None:
@@ -545,6 +600,11 @@ def main(argv=None) -> int:
     ap.add_argument("--orfs", metavar="ORFS.tsv", help="also write the open reading frame around every written region")
     ap.add_argument("--faa", metavar="PROTEINS.faa", help="also write the translated proteins (FASTA, for annotate -p / make_signatures -p)")
     ap.add_argument("--start-codons", default="ATG,GTG,TTG", help="start codons of the ORF extension (default ATG,GTG,TTG; none: no start search)")
+    ap.add_argument("--repair", action="store_true",
+                    help="with --orfs / --faa: join the frames of every kept multi-frame region into one ORF and protein (frameshift repair)")
+    ap.add_argument("--repair-min-count", type=int, default=0, help="CALLs with fewer hits take no part in a chain (default 0, this project's choice)")
+    ap.add_argument("--max-junctions", type=int, default=4, help="frame changes a repaired region has at most (default 4, this project's choice; 1..8)")
+    ap.add_argument("--shifts", metavar="SHIFTS.tsv", help="with --repair: write the junctions of the repaired ORFs")
     ap.add_argument("--select", action="store_true", help="write a gene set: only the non-overlapping selection among the kept candidates")
     ap.add_argument("--max-overlap", type=int, default=60, help="nucleotides two selected candidates may share (default 60, this project's choice)")
     ap.add_argument("--max-overlap-pct", type=int, default=50, help="... and percent of the shorter one (default 50)")
@@ -572,6 +632,10 @@ def main(argv=None) -> int:
         ap.error("--coding needs --orfs or --faa")
     if not a.coding and (a.coding_model is not None or a.save_coding_model is not None or a.min_coding != 0 or a.min_train != 100000):
         ap.error("--min-coding, --min-train, --coding-model and --save-coding-model need --coding")
+    if a.repair and a.orfs is None and a.faa is None:
+        ap.error("--repair needs --orfs or --faa")
+    if not a.repair and (a.shifts is not None or a.repair_min_count != 0 or a.max_junctions != 4):
+        ap.error("--repair-min-count, --max-junctions and --shifts need --repair")
     if a.starts and not a.coding:
         ap.error("--starts needs --coding")
     if not a.starts and (a.start_model is not None or a.save_start_model is not None or a.start_rounds != 4 or a.min_train_starts != 200):
@@ -584,7 +648,8 @@ def main(argv=None) -> int:
                             free_min_res=a.min_res if a.free_orfs else None, coding=a.coding, min_coding=a.min_coding,
                             min_train=a.min_train, coding_model_in=a.coding_model, save_coding_model=a.save_coding_model,
                             starts=a.starts, start_rounds=a.start_rounds, min_train_starts=a.min_train_starts,
-                            start_model_in=a.start_model, save_start_model=a.save_start_model)
+                            start_model_in=a.start_model, save_start_model=a.save_start_model, repair=a.repair,
+                            repair_min_count=a.repair_min_count, max_junctions=a.max_junctions, shifts_out=a.shifts)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1

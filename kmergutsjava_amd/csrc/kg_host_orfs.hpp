@@ -20,6 +20,12 @@ struct kg_orfset {
     int32_t *d_shift = nullptr;         // count, null for a set that is not from kg_orfset_starts
     std::unique_ptr<kg_start_model> start_model;
     kg_start_stats start_st = {};
+    // kg_regionset_repair (kg_host_repair.hpp): the junction list, junction_start[count + 1] and the statistics
+    kg_junction *d_junctions = nullptr; // junctions records, null for a set that is not from kg_regionset_repair
+    int64_t *d_junction_start = nullptr;
+    int64_t junctions = 0;
+    bool repaired = false;
+    kg_repair_stats repair_st = {};
 };
 
 namespace {
@@ -478,6 +484,8 @@ void kg_orfset_free(kg_orfset *s)
         dfree(s->tab, s->d_res);
         dfree(s->tab, s->d_coding);
         dfree(s->tab, s->d_shift);
+        dfree(s->tab, s->d_junctions);
+        dfree(s->tab, s->d_junction_start);
         if (s->own_tab) kg_table_close(s->tab);
     }
     delete s;

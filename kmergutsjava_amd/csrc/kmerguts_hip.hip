@@ -20,6 +20,7 @@
 #include "kg_orfs.hpp"
 #include "kg_coding.hpp"
 #include "kg_starts.hpp"
+#include "kg_repair.hpp"
 #include "kg_select.hpp"
 
 #include <fcntl.h>
@@ -46,6 +47,7 @@
 #include "kg_host_assign.hpp"
 #include "kg_host_regions.hpp"
 #include "kg_host_orfs.hpp"
+#include "kg_host_repair.hpp"
 #include "kg_host_coding.hpp"
 #include "kg_host_starts.hpp"
 #include "kg_host_select.hpp"

@@ -223,7 +223,7 @@ class ScanResult:
     def orfs(self, seq, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, start_codons: int = 7,
              only_kept: bool = True, device_ptr: Optional[int] = None, free_min_res: Optional[int] = None, coding=None,
              min_coding: int = 0, min_train_pairs: int = 100000, starts=None, start_min_res: int = 100, start_rounds: int = 4,
-             min_train_starts: int = 200):
+             min_train_starts: int = 200, repair: bool = False, repair_min_count: int = 0, max_junctions: int = 4):
         """regions() and then the open reading frame around every region with its translated protein, on the GPU, without a
         host trip between the two (include/kmerguts_hip.h kg_regionset_orfs states the rule).  seq / offsets: what the scan was
         given; device_ptr: the address of the bytes in HBM instead of seq.
@@ -242,7 +242,12 @@ class ScanResult:
         coding half is the coding step's table).  True trains on the set's own evidence ORFs in start_rounds rounds when there
         are min_train_starts of them; when the coding step was untrained, so are the starts.  The regions bound the evidence
         ORFs' moves, start_min_res everything else.  The shifts in codons (int32 per record), the statistics and the last
-        round's counts are left in `start_shifts`, `start_stats` and `start_model`; `coding_scores` are then the new set's."""
+        round's counts are left in `start_shifts`, `start_stats` and `start_model`; `coding_scores` are then the new set's.
+        repair: the record and protein of every kept multi-frame region are replaced by the chain through its frames
+        (kg_result_repair, before free_min_res, so every later step sees the new extents; flag _native.ORF_REPAIRED).  CALLs
+        below repair_min_count take no part in a chain; a region of more than max_junctions + 1 segments is left alone.  The
+        junction records (_native.JUNCTION_DTYPE), junction_start int64[n_regions + 1] and the statistics are left in
+        `junctions`, `junction_start` and `repair_stats`."""
         lib = self._need()
         coding = _coding_arg(coding)
         starts = _starts_arg(starts, coding)
@@ -261,6 +266,8 @@ class ScanResult:
             op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
             oh = C.c_void_p()
             N.check(lib.kg_regionset_orfs(h, C.byref(op), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(oh)))
+            if repair:
+                oh = self._repair(h, oh, start_codons, repair_min_count, max_junctions, ptr, on_device, off)
             if free_min_res is not None:
                 oh = _add_free(oh, free_min_res, start_codons, ptr, on_device, off)
             if coding is not None:
@@ -279,7 +286,7 @@ class ScanResult:
                start_codons: int = 7, only_kept: bool = True, device_ptr: Optional[int] = None, max_overlap: int = 60,
                max_overlap_pct: int = 50, free_min_res: Optional[int] = None, coding=None, min_coding: int = 0,
                min_train_pairs: int = 100000, starts=None, start_min_res: int = 100, start_rounds: int = 4,
-               min_train_starts: int = 200):
+               min_train_starts: int = 200, repair: bool = False, repair_min_count: int = 0, max_junctions: int = 4):
         """regions() -- with orfs=True, orfs() -- and then the non-overlapping selection among the kept records, on the GPU and
         without a host trip or a second scan in between (include/kmerguts_hip.h kg_regionset_select states the rule).  The
         candidates are the regions' extents, or with orfs=True the ORFs' extents.
@@ -291,13 +298,16 @@ class ScanResult:
         coding, min_coding, min_train_pairs (with orfs=True): as orfs() takes them, applied after free_min_res and before the
         selection, so a non-coding free ORF is not eligible and suppresses nothing.
         starts, start_min_res, start_rounds, min_train_starts (with coding): as orfs() takes them, applied after coding and before
-        the selection, which therefore sees the new extents."""
+        the selection, which therefore sees the new extents.
+        repair, repair_min_count, max_junctions (with orfs=True): as orfs() takes them, applied before free_min_res."""
         lib = self._need()
         if free_min_res is not None and not orfs:
             raise ValueError("free_min_res needs orfs=True: the free candidates are ORFs")
         coding = _coding_arg(coding)
         if coding is not None and not orfs:
             raise ValueError("coding needs orfs=True: the scores are the ORFs'")
+        if repair and not orfs:
+            raise ValueError("repair needs orfs=True: it rewrites ORFs")
         starts = _starts_arg(starts, coding)
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
         if off.shape != (self.stats["n_seqs"] + 1,):
@@ -315,6 +325,8 @@ class ScanResult:
                     ptr, on_device = (keep.ctypes.data if keep.size else None), 0
                 op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
                 N.check(lib.kg_regionset_orfs(h, C.byref(op), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(oh)))
+                if repair:
+                    oh = self._repair(h, oh, start_codons, repair_min_count, max_junctions, ptr, on_device, off)
                 if free_min_res is not None:
                     oh = _add_free(oh, free_min_res, start_codons, ptr, on_device, off)
                 if coding is not None:
@@ -342,6 +354,24 @@ class ScanResult:
         if orfs:
             return regs, start, orf_recs, prot_start, residues, sel
         return regs, start, sel
+
+    def _repair(self, rh, oh, start_codons, min_count, max_junctions, ptr, on_device, off):
+        """kg_result_repair behind kg_regionset_orfs in orfs() / select(): -> the new set's handle (the given one is freed); the
+        junction list and the statistics into self."""
+        lib = N.load()
+        rp = N.KgRepairParams(int(start_codons), int(min_count), int(max_junctions), 0)
+        new = C.c_void_p()
+        try:
+            N.check(lib.kg_result_repair(self._h, rh, oh, C.byref(rp), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(new)))
+        finally:
+            lib.kg_orfset_free(oh)          # (the new set holds copies: the given one is not needed any more)
+            oh.value = None
+        try:
+            self.junctions, self.junction_start, self.repair_stats = _junctions(new)
+        except BaseException:
+            lib.kg_orfset_free(new)
+            raise
+        return new
 
     def _starts(self, oh, rh, coding, starts, start_codons, min_res, rounds, min_train_starts, ptr, on_device, off):
         """kg_orfset_starts behind the coding step of orfs() / select(): -> the new set's handle; the results into self."""
@@ -802,6 +832,73 @@ def _take_orfset(h, device_out: bool):
         return out, start, res, st.as_dict()
     finally:
         lib.kg_orfset_free(h)
+
+
+def _junctions(h):
+    """The junction list of a set made by kg_regionset_repair -> (records, junction_start, statistics); the set stays."""
+    lib = N.load()
+    st = N.KgRepairStats()
+    N.check(lib.kg_orfset_junctions_stats(h, C.byref(st)))
+    n, nj = int(lib.kg_orfset_count(h)), int(lib.kg_orfset_junctions_count(h))
+    rec = np.zeros(nj, dtype=N.JUNCTION_DTYPE)
+    start = np.zeros(n + 1, dtype=np.int64)
+    N.check(lib.kg_orfset_junctions_copy(h, 0, nj, rec.ctypes.data if nj else None))
+    N.check(lib.kg_orfset_junctions_start(h, start.ctypes.data))
+    return rec, start, st.as_dict()
+
+
+def repair_orfs(calls, seq, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, start_codons: int = 7,
+                only_kept: bool = True, min_count: int = 0, max_junctions: int = 4, device: int = 0, device_inputs: bool = False,
+                repair_calls=None, stats: Optional[dict] = None):
+    """Function regions, their ORFs and the frameshift repair from caller-held CALL records of a DNA scan, on the GPU
+    (kg_regions_calls, kg_regionset_orfs, kg_regionset_repair; include/kmerguts_hip.h states the rule): calls CALL_DTYPE in
+    non-decreasing container order, seq / offsets the batch.
+    -> (regions, region_start, orfs, prot_start, residues, junctions, junction_start): orfs index-aligned with regions, the
+    record and protein of every repaired region replaced by the chain through its frames (flag _native.ORF_REPAIRED);
+    junctions _native.JUNCTION_DTYPE in (orf, k) order, ORF i owning [junction_start[i], junction_start[i + 1]).
+    device_inputs: the CALLs and the bytes are handed to the repair step as device memory (uploaded with torch first).
+    repair_calls: the CALL list the repair step is given, when it is not `calls` (it must describe the same regions, or the
+    call fails with KG_ERR_ARG).  `stats`, when given, receives "regions", "orfs" (the new set's) and "repair"."""
+    lib = N.load()
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_seqs + 1]")
+    c = np.ascontiguousarray(calls, dtype=N.CALL_DTYPE)
+    rc = c if repair_calls is None else np.ascontiguousarray(repair_calls, dtype=N.CALL_DTYPE)
+    keep = _seq_bytes(seq, off)
+    n_seqs = off.size - 1
+    p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
+    op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
+    rp = N.KgRepairParams(int(start_codons), int(min_count), int(max_junctions), 0)
+    h, oh, new = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    N.check(lib.kg_regions_calls(device, C.byref(p), c.ctypes.data if c.size else None, c.size, off.ctypes.data, n_seqs, C.byref(h)))
+    try:
+        sptr = keep.ctypes.data if keep.size else None
+        N.check(lib.kg_regionset_orfs(h, C.byref(op), sptr, 0, off.ctypes.data, n_seqs, C.byref(oh)))
+        cptr, on_device = (rc.ctypes.data if rc.size else None), 0
+        if device_inputs:
+            import torch
+            with torch.cuda.device(device):
+                d_calls = torch.from_numpy(rc.view(np.uint8).reshape(-1).copy()).cuda()
+                d_seq = torch.from_numpy(keep.copy()).cuda()
+                torch.cuda.synchronize()
+            cptr, sptr, on_device = C.c_void_p(d_calls.data_ptr() if rc.size else None), C.c_void_p(d_seq.data_ptr() if keep.size else None), 1
+        N.check(lib.kg_regionset_repair(h, oh, cptr, on_device, rc.size, C.byref(rp), sptr, on_device, off.ctypes.data, n_seqs, C.byref(new)))
+        junc, jstart, rst = _junctions(new)
+        taken, new = new, C.c_void_p()              # (_take_* frees what it is given, also when it raises)
+        orfs, prot_start, residues, ost = _take_orfset(taken, False)
+    except BaseException:
+        if new:
+            lib.kg_orfset_free(new)             # (the new set first: it holds blocks of the region set's context)
+        if oh:
+            lib.kg_orfset_free(oh)
+        lib.kg_regionset_free(h)
+        raise
+    lib.kg_orfset_free(oh)
+    regs, start, rgst = _take_regionset(h, n_seqs, False)
+    if stats is not None:
+        stats.update({"regions": rgst, "orfs": ost, "repair": rst})
+    return regs, start, orfs, prot_start, residues, junc, jstart
 
 
 def _add_free(oh, min_res: int, start_codons: int, ptr, on_device: int, off):
