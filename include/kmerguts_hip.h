@@ -1014,6 +1014,100 @@ int kg_selectset_copy(const kg_selectset *s, int64_t first, int64_t count, kg_se
 int kg_selectset_stats(const kg_selectset *s, kg_select_stats *out);
 void kg_selectset_free(kg_selectset *s);
 
+/* ---- whose contig: every OTU vote of a sequence tallied, one OTU per sequence, the sample's bins (kernels: kg_votes.hpp) ----
+ *
+ * The reference votes for OTUs inside processSetOfHits (KGJ:405-437) and keeps the tally in a buffer of KG_OI_BUFSZ slots
+ * whose last slot every further OTU overwrites (KGJ:432-437); it stops at the OTU-COUNTS line.  Steps 1 and 2 are the
+ * reference's own vote without that buffer; everything from step 3 on is this project's own.  Integers only.
+ * Input: the hit records hits[] in (container, from0InProt) order with container_hit_start, the event byte of every hit,
+ * the CALL records with container_call_start, per = the containers of one sequence (6 for DNA, 1 for -a), and the sequence
+ * lengths L_s = offsets[s+1] - offsets[s].
+ *   1. Votes.  Let c_0 .. c_{m-1} be the CALLs of hit h's container in emission order.  For records that come from a scan
+ *      their start values are strictly ascending; for caller-held lists a container where they are not is an error.  Let k be
+ *      the largest index with c_k.start <= h.from0InProt.  h is a vote iff its event byte has KG_EV_ACCEPTED, k exists,
+ *      c_k.fI == h.fI and h.from0InProt + (KG_K - 1) <= c_k.end (int64).  The vote belongs to CALL c_k and goes to OTU h.oI of
+ *      sequence container / per.  These are exactly the hits KGJ:405-437 feeds into oICounts: the members 0 .. lastHit of a
+ *      list that printed a CALL, with the CALL's function -- so the votes of a CALL number its count.  A voting hit with
+ *      oI < 0 is KG_ERR_ARG, and the message names the hit (a hit that does not vote may carry any oI).
+ *   2. Tally.  For each (sequence, OTU) pair that has a vote: votes = the number of its votes, n_calls = the number of
+ *      distinct CALLs they belong to.
+ *   3. Order.  A sequence's pairs are ordered by votes descending, then oI ascending.  The pairs of all sequences lie end to
+ *      end in sequence order (kg_otu_vote, 16 B), with vote_start[n_seqs + 1] (int64) so that a sequence's pairs are one slice.
+ *   4. Class (kg_otu_class, 40 B, one per sequence): total = the sum of its votes, which must be below 2^31, else
+ *      KG_ERR_LIMIT naming the sequence; total_calls = the CALLs in its containers; n_otus = its pairs; otu / votes / n_calls
+ *      = its first pair, second_otu / second_votes = its second (-1 / 0 when there is none);
+ *      assigned = 1 iff votes >= min_votes and n_calls >= min_calls and 100 * votes >= min_share_pct * total (int64) -- and
+ *      there is a vote at all.  Without a vote otu = second_otu = -1 and everything else is 0 but total_calls.
+ *   5. Bins (kg_otu_bin, 32 B): for each OTU at least one sequence is assigned to, n_seqs = those sequences, length = the
+ *      int64 sum of their lengths, votes and n_calls = the int64 sums of their first-pair values.  Bins are ordered by length
+ *      descending, then votes descending, then oI ascending.
+ *   6. Parameters kg_vote_params { min_votes, min_share_pct, min_calls, reserved }: min_votes >= 0, 0 <= min_share_pct <= 100,
+ *      min_calls >= 0, reserved 0, else KG_ERR_ARG.  Defaults (this project's choice): 10, 50 and 1.
+ *   7. Independence.  The output depends only on the records and the lengths: not on launch geometry, tile sizes or batch
+ *      neighbours.  A sequence's pairs and class are the same in whatever batch it sits; the bins of two batches add up.
+ * Errors: KG_ERR_ARG for a KG_F_SKIP_AGGREGATE result, null pointers, per outside {1, 6}, decreasing container_hit_start,
+ * container_call_start or offsets (or starts that do not begin at 0), a hit or CALL whose container field is not the
+ * container whose slice it lies in, hits of a container not in non-decreasing from0InProt order, CALL starts of a container
+ * that are not strictly ascending, a negative oI on a voting hit -- each message names the first offender; KG_ERR_LIMIT for
+ * 2^32 or more hits, CALLs or pairs, 2^31 or more sequences, a sequence total (or CALL count) of 2^31 or more; KG_ERR_BUSY
+ * while a kg_scan* is in flight on the result's table; KG_ERR_NOMEM.  A bad record is clamped before it is used as an index.
+ * Zero hits, zero CALLs and zero sequences are valid inputs.
+ * Device allocations come from the table's block cache (a table-less context for kg_otu_votes_hits), so KG_TEST_FAIL_ALLOC
+ * applies; everything but the set's four arrays is back in the cache when the call returns.  A set made by
+ * kg_result_otu_votes holds blocks of the result's table (kg_table_live_device_bytes counts them) and must be freed before
+ * that table is closed. */
+typedef struct kg_vote_params { int32_t min_votes, min_share_pct, min_calls, reserved; } kg_vote_params;
+typedef struct kg_otu_vote {     /* 16 B */
+    int32_t  seq;
+    int32_t  oI;
+    int32_t  votes;
+    int32_t  n_calls;      /* distinct CALLs the votes belong to                        */
+} kg_otu_vote;
+typedef struct kg_otu_class {    /* 40 B */
+    int32_t  otu;          /* the first pair's OTU, -1 without a vote                   */
+    int32_t  assigned;     /* rule 4                                                    */
+    int32_t  votes;        /* the first pair's                                          */
+    int32_t  total;        /* all votes of the sequence                                 */
+    int32_t  n_calls;      /* the first pair's                                          */
+    int32_t  total_calls;  /* CALLs in the sequence's containers                        */
+    int32_t  n_otus;       /* pairs of the sequence                                     */
+    int32_t  second_otu;   /* the second pair's OTU, -1 when there is none              */
+    int32_t  second_votes;
+    int32_t  reserved;
+} kg_otu_class;
+typedef struct kg_otu_bin {      /* 32 B */
+    int32_t  oI;
+    int32_t  n_seqs;       /* sequences assigned to the OTU                             */
+    int64_t  length;       /* ... the sum of their lengths                              */
+    int64_t  votes;        /* ... of their first-pair votes                             */
+    int64_t  n_calls;      /* ... of their first-pair n_calls                           */
+} kg_otu_bin;
+typedef struct kg_vote_stats {
+    int64_t hits, accepted, votes, pairs, seqs_with_votes, assigned, bins;
+    int64_t assigned_length, total_length;
+    float   ms;            /* device time of the call's kernels                         */
+    int32_t reserved;
+} kg_vote_stats;
+typedef struct kg_voteset kg_voteset;
+/* a DNA or -a result of kg_scan* / kg_aggregate_hits plus the host offsets[n_seqs + 1] the scan was given */
+int kg_result_otu_votes(kg_result *r, const kg_vote_params *p, const int64_t *offsets, kg_voteset **out);
+/* caller-held host lists: hits[container_hit_start[n_seqs * per]] and hit_events (one byte per hit),
+   calls[container_call_start[n_seqs * per]], both start arrays of n_seqs * per + 1 entries, offsets[n_seqs + 1] */
+int kg_otu_votes_hits(int device, const kg_vote_params *p, const kg_hit *hits, const int64_t *container_hit_start,
+                      const uint8_t *hit_events, const kg_call *calls, const int64_t *container_call_start, int64_t n_seqs,
+                      int32_t per, const int64_t *offsets, kg_voteset **out);
+/* the pairs (kg_otu_vote records) and the bins of the set; it holds one kg_otu_class per sequence */
+int64_t kg_voteset_count(const kg_voteset *s);
+int64_t kg_voteset_bins(const kg_voteset *s);
+/* records [first, first + count) into dst (host or device memory) */
+int kg_voteset_copy_votes(const kg_voteset *s, int64_t first, int64_t count, kg_otu_vote *dst);
+int kg_voteset_copy_classes(const kg_voteset *s, int64_t first, int64_t count, kg_otu_class *dst);
+int kg_voteset_copy_bins(const kg_voteset *s, int64_t first, int64_t count, kg_otu_bin *dst);
+/* vote_start[n_seqs + 1] into dst (host or device memory): sequence s owns pairs [vote_start[s], vote_start[s+1]) */
+int kg_voteset_seq_start(const kg_voteset *s, int64_t *dst);
+int kg_voteset_stats(const kg_voteset *s, kg_vote_stats *out);
+void kg_voteset_free(kg_voteset *s);
+
 /* the resident 24-byte records, valid until kg_table_close, and how many there are: num_sigs for a built or adopted table, the
  * whole records of the file for an opened one (fewer than num_sigs for a truncated file, more for a longer one) */
 const void *kg_table_device_entries(const kg_table *t);

@@ -267,6 +267,25 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_vote_params (kg_result_otu_votes / kg_otu_votes_hits); the defaults are 10, 50 and 1. */
+    class KgVoteParams extends Structure {
+        public int min_votes, min_share_pct, min_calls, reserved;
+        public KgVoteParams() {
+            setFieldOrder(new String[] {"min_votes", "min_share_pct", "min_calls", "reserved"});
+        }
+    }
+
+    /** struct kg_vote_stats. */
+    class KgVoteStats extends Structure {
+        public long hits, accepted, votes, pairs, seqs_with_votes, assigned, bins, assigned_length, total_length;
+        public float ms;
+        public int reserved;
+        public KgVoteStats() {
+            setFieldOrder(new String[] {"hits", "accepted", "votes", "pairs", "seqs_with_votes", "assigned", "bins", "assigned_length",
+                                        "total_length", "ms", "reserved"});
+        }
+    }
+
     /** struct kg_interval (20 B): one candidate of kg_select_intervals, 0-based inclusive left / right. */
     class KgInterval extends Structure {
         public int seq, left, right, score, eligible;
@@ -477,6 +496,23 @@ public interface KmerGutsHip extends Library {
     int kg_selectset_copy(Pointer set, long first, long count, Pointer dst);
     int kg_selectset_stats(Pointer set, KgSelectStats out);
     void kg_selectset_free(Pointer set);
+    /** every OTU vote per sequence, one OTU per sequence, the batch's bins; offsets = the long[nSeqs + 1] the scan was given.
+     *  Free the vote set before the result's table. */
+    int kg_result_otu_votes(Pointer result, KgVoteParams params, long[] offsets, PointerByReference out);
+    /** caller-held host lists: packed 24-byte kg_hit and kg_call records, one event byte per hit, per = 6 (DNA) or 1 (-a) */
+    int kg_otu_votes_hits(int device, KgVoteParams params, Pointer hits, long[] containerHitStart, Pointer hitEvents, Pointer calls,
+                          long[] containerCallStart, long nSeqs, int per, long[] offsets, PointerByReference out);
+    long kg_voteset_count(Pointer set);                      // (sequence, OTU) pairs
+    long kg_voteset_bins(Pointer set);
+    /** dst: count packed 16-byte kg_otu_vote records (int seq, oI, votes, n_calls) */
+    int kg_voteset_copy_votes(Pointer set, long first, long count, Pointer dst);
+    /** dst: count packed 40-byte kg_otu_class records, one per sequence */
+    int kg_voteset_copy_classes(Pointer set, long first, long count, Pointer dst);
+    /** dst: count packed 32-byte kg_otu_bin records (int oI, n_seqs; long length, votes, n_calls) */
+    int kg_voteset_copy_bins(Pointer set, long first, long count, Pointer dst);
+    int kg_voteset_seq_start(Pointer set, long[] dst);       // long[nSeqs + 1]
+    int kg_voteset_stats(Pointer set, KgVoteStats out);
+    void kg_voteset_free(Pointer set);
     void kg_result_free(Pointer result);
     int kg_restore_hits_device(int device, Pointer dSrc, long nHits, Pointer dSeqFirst, long nSeqs, Pointer dDstFirst,
                                Pointer dContainerShift, Pointer dDst, Pointer stream);

@@ -49,6 +49,8 @@ EXPORTS = (
     "kg_starts_orfs",
     "kg_regionset_select", "kg_orfset_select", "kg_select_intervals", "kg_selectset_count", "kg_selectset_device",
     "kg_selectset_copy", "kg_selectset_stats", "kg_selectset_free",
+    "kg_result_otu_votes", "kg_otu_votes_hits", "kg_voteset_count", "kg_voteset_bins", "kg_voteset_copy_votes",
+    "kg_voteset_copy_classes", "kg_voteset_copy_bins", "kg_voteset_seq_start", "kg_voteset_stats", "kg_voteset_free",
     "kg_last_error", "kg_version",
 )
 
@@ -103,6 +105,14 @@ SELECTION_DTYPE = np.dtype([("state", "<i4"), ("by", "<i4")])
 assert INTERVAL_DTYPE.itemsize == 20 and SELECTION_DTYPE.itemsize == 8
 SEL_NOT_ELIGIBLE, SEL_SELECTED, SEL_OVERLAPPED = 0, 1, 2
 SELECT_PAIRS_PER_LANE = 8   # kg_select.hpp kSelectPairsPerLane: the pair slots of one lane (tests aim at its edges)
+# struct kg_otu_vote, kg_otu_class and kg_otu_bin (kg_result_otu_votes / kg_otu_votes_hits): one (sequence, OTU) tally, one
+# sequence's classification, one OTU's bin
+VOTE_DTYPE = np.dtype([("seq", "<i4"), ("oI", "<i4"), ("votes", "<i4"), ("n_calls", "<i4")])
+OTU_CLASS_DTYPE = np.dtype([("otu", "<i4"), ("assigned", "<i4"), ("votes", "<i4"), ("total", "<i4"), ("n_calls", "<i4"),
+                            ("total_calls", "<i4"), ("n_otus", "<i4"), ("second_otu", "<i4"), ("second_votes", "<i4"),
+                            ("reserved", "<i4")])
+OTU_BIN_DTYPE = np.dtype([("oI", "<i4"), ("n_seqs", "<i4"), ("length", "<i8"), ("votes", "<i8"), ("n_calls", "<i8")])
+assert VOTE_DTYPE.itemsize == 16 and OTU_CLASS_DTYPE.itemsize == 40 and OTU_BIN_DTYPE.itemsize == 32
 # struct kg_family (kg_proteins_cluster*): one protein's family
 FAMILY_DTYPE = np.dtype([("family", "<i4"), ("root", "<i4"), ("best", "<i4"), ("shared", "<i4")])
 assert FAMILY_DTYPE.itemsize == 16
@@ -306,6 +316,21 @@ class KgClusterStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KgVoteParams(C.Structure):
+    """struct kg_vote_params (kg_result_otu_votes / kg_otu_votes_hits)."""
+    _fields_ = [("min_votes", C.c_int32), ("min_share_pct", C.c_int32), ("min_calls", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgVoteStats(C.Structure):
+    """struct kg_vote_stats."""
+    _fields_ = [("hits", C.c_int64), ("accepted", C.c_int64), ("votes", C.c_int64), ("pairs", C.c_int64),
+                ("seqs_with_votes", C.c_int64), ("assigned", C.c_int64), ("bins", C.c_int64), ("assigned_length", C.c_int64),
+                ("total_length", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 class KmerGutsNativeError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__("libkmerguts_hip error %d: %s" % (code, msg))
@@ -441,6 +466,17 @@ def load() -> C.CDLL:
     lib.kg_selectset_stats.argtypes = [vp, C.POINTER(KgSelectStats)]
     lib.kg_selectset_free.argtypes = [vp]
     lib.kg_selectset_free.restype = None
+    lib.kg_result_otu_votes.argtypes = [vp, C.POINTER(KgVoteParams), vp, C.POINTER(vp)]
+    lib.kg_otu_votes_hits.argtypes = [C.c_int, C.POINTER(KgVoteParams), vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, C.POINTER(vp)]
+    for name in ("kg_voteset_count", "kg_voteset_bins"):
+        getattr(lib, name).argtypes = [vp]
+        getattr(lib, name).restype = C.c_int64
+    for name in ("kg_voteset_copy_votes", "kg_voteset_copy_classes", "kg_voteset_copy_bins"):
+        getattr(lib, name).argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.kg_voteset_seq_start.argtypes = [vp, vp]
+    lib.kg_voteset_stats.argtypes = [vp, C.POINTER(KgVoteStats)]
+    lib.kg_voteset_free.argtypes = [vp]
+    lib.kg_voteset_free.restype = None
     for name in ("kg_proteins_cluster", "kg_proteins_cluster_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), vp, vp, C.c_int64, C.c_int64, C.POINTER(vp)]
     lib.kg_familyset_count.argtypes = [vp]

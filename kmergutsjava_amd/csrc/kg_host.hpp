@@ -192,7 +192,7 @@ enum : int {
 };
 static_assert(kPevChunk + 2 * kMaxChunks <= kPevFork && kPevVerified + kMaxChunks <= kPevBase && kPevBase + kMaxChunks <= kPevOrdered &&
               kPevOrdered + kMaxOrderStreams <= kPevCount, "event slots overlap");
-// kg_table::ev, the timing events of a scan (outside a scan they are free: kg_result_copy_hits, assign_impl, regions_impl, orfs_impl)
+// kg_table::ev, the timing events of a scan (outside a scan they are free: kg_result_copy_hits, assign_impl, regions_impl, orfs_impl, votes_impl)
 enum : int { kEvBegin = 0, kEvScanBegin = 1, kEvScanEnd = 2, kEvOrderEnd = 3, kEvAggEnd = 4, kEvScattered = 5 /* all chunks */, kEvSpare = 6,
              kEvJoined = 7 /* stream2 and stream3 joined */, kEvCount = 8, kEvStageBegin = kEvBegin, kEvStageEnd = kEvScanBegin };
 // d_totals, the counter words of a scan
@@ -211,7 +211,7 @@ enum : int { kOvfGroups = 0 /* overflow groups */, kOvfLowc = 1 /* low-complexit
 // host per copy; to pinned memory it does not)
 enum : int { kPinPc = 0 /* d_pc */, kPinOvf = 48 /* d_ovfc */, kPinTotals = 80 /* d_totals[0 .. kTotSent) */, kPinCalls = 88 /* CALL total */,
              kPinPieces = 89, kPinWords = 96,
-             // the stage area (assign_impl, regions_impl, orfs_impl) lies over the scan's totals: such a call holds the table, no scan is in flight
+             // the stage area (assign_impl, regions_impl, orfs_impl, votes_impl: kPinVotes in kg_host_votes.hpp) lies over the scan's totals: such a call holds the table, no scan is in flight
              kPinRegions = 80 /* two totals, then the error and counter words */,
              kPinAssign = 90 /* long proteins, their CALLs, then the error words */,
              kPinOrfs = 80 /* the error and counter words, then the residue total */ };

@@ -22,6 +22,7 @@
 #include "kg_starts.hpp"
 #include "kg_repair.hpp"
 #include "kg_select.hpp"
+#include "kg_votes.hpp"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -51,3 +52,4 @@
 #include "kg_host_coding.hpp"
 #include "kg_host_starts.hpp"
 #include "kg_host_select.hpp"
+#include "kg_host_votes.hpp"

@@ -220,6 +220,23 @@ class ScanResult:
         out, start, self.region_stats = _take_regionset(h, self.stats["n_seqs"], device_out)
         return out, start
 
+    def otu_votes(self, offsets, min_votes: int = 10, min_share_pct: int = 50, min_calls: int = 1, device_out: bool = False):
+        """Every OTU vote of the result tallied per sequence, one OTU per sequence and the batch's bins, on the GPU
+        (include/kmerguts_hip.h kg_result_otu_votes states the rule).  offsets: the int64[n_seqs + 1] the scan was given.
+        -> (votes, vote_start, classes, bins): votes _native.VOTE_DTYPE, sequence s owning votes[vote_start[s] :
+        vote_start[s + 1]] (most votes first); classes _native.OTU_CLASS_DTYPE[n_seqs]; bins _native.OTU_BIN_DTYPE (longest
+        first).  With device_out=True the three record arrays are CUDA uint8 tensors.  The call's counts and device time are
+        left in `vote_stats`."""
+        lib = self._need()
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+        if off.shape != (self.stats["n_seqs"] + 1,):
+            raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
+        p = N.KgVoteParams(int(min_votes), int(min_share_pct), int(min_calls), 0)
+        h = C.c_void_p()
+        N.check(lib.kg_result_otu_votes(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
+        votes, start, classes, bins, self.vote_stats = _take_voteset(h, self.stats["n_seqs"], device_out)
+        return votes, start, classes, bins
+
     def orfs(self, seq, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, start_codons: int = 7,
              only_kept: bool = True, device_ptr: Optional[int] = None, free_min_res: Optional[int] = None, coding=None,
              min_coding: int = 0, min_train_pairs: int = 100000, starts=None, start_min_res: int = 100, start_rounds: int = 4,
@@ -796,6 +813,65 @@ def region_calls(calls, offsets, merge_gap: int = 600, min_score: int = 0, min_l
     if stats is not None:
         stats.update(st)
     return out, start
+
+
+def _take_voteset(h, n_seqs: int, device_out: bool):
+    """Copy a kg_voteset out (the three record arrays to the host or into CUDA tensors, vote_start to the host) and free it.
+    -> (votes, vote_start, classes, bins, statistics)."""
+    lib = N.load()
+    try:
+        st = N.KgVoteStats()
+        N.check(lib.kg_voteset_stats(h, C.byref(st)))
+        start = np.zeros(n_seqs + 1, dtype=np.int64)
+        N.check(lib.kg_voteset_seq_start(h, start.ctypes.data))
+        out = []
+        for n, dt, copy in ((int(lib.kg_voteset_count(h)), N.VOTE_DTYPE, lib.kg_voteset_copy_votes),
+                            (n_seqs, N.OTU_CLASS_DTYPE, lib.kg_voteset_copy_classes),
+                            (int(lib.kg_voteset_bins(h)), N.OTU_BIN_DTYPE, lib.kg_voteset_copy_bins)):
+            if device_out:
+                import torch
+                a = torch.empty(n * dt.itemsize, dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()
+                N.check(copy(h, 0, n, C.c_void_p(a.data_ptr() if n else None)))
+            else:
+                a = np.zeros(n, dtype=dt)
+                N.check(copy(h, 0, n, a.ctypes.data if n else None))
+            out.append(a)
+        return out[0], start, out[1], out[2], st.as_dict()
+    finally:
+        lib.kg_voteset_free(h)
+
+
+def otu_votes(hits, container_hit_start, hit_events, calls, container_call_start, n_seqs: int, per: int, offsets,
+              min_votes: int = 10, min_share_pct: int = 50, min_calls: int = 1, device: int = 0, device_out: bool = False,
+              stats: Optional[dict] = None):
+    """The OTU votes of caller-held records, on the GPU (kg_otu_votes_hits): hits HIT_DTYPE in (container, from0InProt) order
+    with container_hit_start int64[n_seqs * per + 1], hit_events one KG_EV_* byte per hit, calls CALL_DTYPE with
+    container_call_start, per 6 (DNA) or 1 (-a), offsets int64[n_seqs + 1].  -> (votes, vote_start, classes, bins) as
+    ScanResult.otu_votes; `stats`, when given, receives the call's counts and device time."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    chs = np.ascontiguousarray(np.asarray(container_hit_start, dtype=np.int64))
+    ccs = np.ascontiguousarray(np.asarray(container_call_start, dtype=np.int64))
+    n_seqs, per = int(n_seqs), int(per)
+    if off.shape != (n_seqs + 1,):
+        raise ValueError("offsets must be int64[n_seqs + 1]")
+    n_cont = n_seqs * per if per > 0 else 0
+    if chs.shape != (n_cont + 1,) or ccs.shape != (n_cont + 1,):
+        raise ValueError("container_hit_start and container_call_start must be int64[n_seqs * per + 1]")
+    hh = np.ascontiguousarray(hits, dtype=N.HIT_DTYPE)
+    ev = np.ascontiguousarray(hit_events, dtype=np.uint8)
+    c = np.ascontiguousarray(calls, dtype=N.CALL_DTYPE)
+    if ev.shape != hh.shape or (chs.size and chs[-1] > hh.size) or (ccs.size and ccs[-1] > c.size):
+        raise ValueError("the start arrays reach beyond the records, or hit_events is not one byte per hit")
+    p = N.KgVoteParams(int(min_votes), int(min_share_pct), int(min_calls), 0)
+    h = C.c_void_p()
+    N.check(N.load().kg_otu_votes_hits(device, C.byref(p), hh.ctypes.data if hh.size else None, chs.ctypes.data,
+                                       ev.ctypes.data if ev.size else None, c.ctypes.data if c.size else None, ccs.ctypes.data,
+                                       n_seqs, per, off.ctypes.data, C.byref(h)))
+    votes, start, classes, bins, st = _take_voteset(h, n_seqs, device_out)
+    if stats is not None:
+        stats.update(st)
+    return votes, start, classes, bins
 
 
 def _seq_bytes(seq, off) -> np.ndarray:
