@@ -83,6 +83,7 @@ struct PartPlan {
     bool use_bidx = false, part_counters = false, prog_index = false;
     uint32_t probe_grid = 0, index_grid = 0, verify_grid = 0, lowc_grid = 0, ovf_grid = 0, order_grid = 0;
     uint32_t scatter_prio = 0, index_prio = 0, verify_prio = 0, index_r = 1, probe_grab = 0;
+    uint32_t flush_list = 0;            // scatter pass: completed groups a wave flushes per pass
     uint64_t list_slack = 0, ucap = 0, ccap = 0;    // hit / candidate list capacities per chunk the first attempt starts with
     uint32_t n_os = 0;                  // ordering streams (KG_ORDER_STREAMS)
     bool early_totals = false, place_staged = false, debug = false;
@@ -189,6 +190,9 @@ int plan_partition(const kg_table *t, const BatchPlan &b, bool progress, bool co
     pl.part_counters = (counters_req || progress) && !pl.use_bidx;
     pl.prog_index = progress && pl.use_bidx;
     pl.scatter_lds = kg::scatter_lds_bytes<AA>(pl.buckets);
+    // the scatter pass's flush list: what a wave's encode scratch holds, at most an entry per lane; KG_SCATTER_FLUSH_LIST (tests)
+    // lowers it, so that a round's completed groups go in several passes
+    pl.flush_list = env_knob("KG_SCATTER_FLUSH_LIST", kg::scatter_flush_list_max<AA>(), 1u, kg::scatter_flush_list_max<AA>());
     // Tag workgroups per CU.  How many of them run beside a scatter workgroup of the next chunk is decided by the SIMDs'
     // VGPRs (kg_partition.hpp, "Register budgets": two per CU since round 3, one before), the rest wait for the scatter
     // workgroup to leave; the hand-out is by ticket, so the count only decides how fast freed registers are taken up.

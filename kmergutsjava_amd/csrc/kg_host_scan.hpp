@@ -249,7 +249,7 @@ int chunk_passes(const ScanCtx &cx, const PartPlan &pl, const PartBuffers &pb, c
         constexpr bool SHORT = decltype(is_short)::value, PROG = decltype(prog)::value;
         hipLaunchKernelGGL((kg::part_scatter_kernel<AA, SHORT, PROG>), dim3(pl.n_wg), dim3(kg::kWave * kg::kScatterWaves), pl.scatter_lds,
                            t->stream, cx.d_seq, cx.d_blocks, v.lo, v.nb, limit32, (uint32_t)t->num_sigs, t->m35, pl.shift, pl.buckets, pl.cap,
-                           v.ent, v.fill, t->d_cold + v.c, pl.scatter_prio);
+                           v.ent, v.fill, t->d_cold + v.c, pl.scatter_prio, pl.flush_list);
     });
     HIP_TRY(hipEventRecord(t->pev[kPevChunk + 2 * v.c], t->stream));
     HIP_TRY(hipStreamWaitEvent(s2, t->pev[kPevChunk + 2 * v.c], 0));

@@ -51,7 +51,7 @@ constexpr int kMaxBuckets = 1024;
 // waves per SIMD: 4 x 96 + 4 x 32 = 512.)  Scalar registers are a budget too: a kernel has 102 of them, and one that wants more
 // moves the rest through lanes of a VGPR (v_readlane / v_writelane plus hazard waits) on the wave's issue path -- the scatter
 // kernel did, with 31 (21 arguments, two block descriptors, six 64-bit row masks), until its cold paths' arguments went into
-// ScatterCold; it now uses 83 and spills none.  tests/test_kernel_resources.py holds all of these to the compiler's report.
+// ScatterCold; it now uses 93 (83 before the one-pass flush of round 6) and spills none.  tests/test_kernel_resources.py holds all of these to the compiler's report.
 #ifndef KG_SCATTER_WPE
 #define KG_SCATTER_WPE 5
 #endif
@@ -112,7 +112,15 @@ inline size_t scatter_lds_bytes(uint32_t n_buckets)
 {
     size_t enc = (sizeof(typename WaveLds<AA>::type) + 15) & ~(size_t)15;
     size_t tab = (sizeof(typename WaveLds<AA>::tables) + 15) & ~(size_t)15;
-    return enc * kScatterWaves + tab + (size_t)n_buckets * (kGroup * 8 + 12);
+    return enc * kScatterWaves + tab + (size_t)n_buckets * (kGroup * 8 + 8);
+}
+// Completed groups a wave can list for one flush pass: 32-bit descriptors in its encode scratch, which is idle while the wave
+// inserts (all of it when every row of the block is in registers, else the base codes only), and no more than it has lanes.
+template <bool AA>
+constexpr uint32_t scatter_flush_list_max()
+{
+    constexpr size_t idle = AA ? sizeof(WaveLdsAa) : KG_SCATTER_RG == 6 ? sizeof(WaveLdsDna) : sizeof(WaveLdsDna::bc);
+    return idle / 4 < 64 ? (uint32_t)(idle / 4) : 64u;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -125,6 +133,11 @@ inline size_t scatter_lds_bytes(uint32_t n_buckets)
 // that bucket.  Regions are over-allocated (cap entries each, no counting pass); a group that does not fit its
 // region goes to the overflow list (skewed inputs), which is probed separately.  Layout of the entry array:
 // region (bucket b, workgroup w) = [ (b * n_wg + w) * cap , + fill[b * n_wg + w] ).
+// A bucket has two LDS counters: tickets into the open buffer, and the count of entries stored since the kernel began, which is
+// never set back -- the lane whose store makes it a multiple of 16 owns the group, and the count tells it which group of the
+// region that is (the same count gives fill[] at the end).  A wave flushes all the groups its lanes completed in an insert round
+// in ONE pass: the owners list {bucket, group number} in the wave's idle encode scratch, then each octet of lanes takes a list
+// entry, copies its 128 bytes with one global store per lane and reopens the buffer (round 6: profiles/r06_scatter_flush.md).
 // 16 bytes of a flushed group.  KG_SCATTER_NT: with the streaming hint (the entries are read once, a pass later, from HBM)
 #ifndef KG_SCATTER_NT
 #define KG_SCATTER_NT 1
@@ -162,9 +175,8 @@ constexpr unsigned long long kDstOvf = 1ull << 62, kDstNone = ~0ull, kDstDropped
 
 // ---- cold paths of part_scatter_kernel ----
 // The regions of the lanes in movf are full: their groups go to the overflow list, one atomic per wave.
-__device__ __attribute__((noinline, cold)) unsigned long long scatter_overflow_groups(const ScatterCold *__restrict__ cold,
-                                                                                     unsigned long long movf, bool to_ovf, uint32_t b,
-                                                                                     unsigned long long dst)
+__device__ __forceinline__ unsigned long long overflow_reserve(const ScatterCold *__restrict__ cold, unsigned long long movf, bool to_ovf,
+                                                               uint32_t b, unsigned long long dst)
 {
     const int lane = threadIdx.x & 63;
     uint32_t og = 0;
@@ -177,6 +189,34 @@ __device__ __attribute__((noinline, cold)) unsigned long long scatter_overflow_g
     }
     return dst;
 }
+__device__ __attribute__((noinline, cold)) unsigned long long scatter_overflow_groups(const ScatterCold *__restrict__ cold,
+                                                                                     unsigned long long movf, bool to_ovf, uint32_t b,
+                                                                                     unsigned long long dst)
+{
+    return overflow_reserve(cold, movf, to_ovf, b, dst);
+}
+// The same for a flush pass, where eight lanes (an octet) hold the 128 bytes of a group of bucket b, 16 bytes (lo, hi) each: the
+// octets in `full` found their regions full; the first lane of each reserves the group, all eight store.  A group the list has
+// no room for is dropped (the host falls back to direct probing).
+__device__ __attribute__((noinline, cold)) void scatter_overflow_octets(const ScatterCold *__restrict__ cold, bool full, uint32_t b,
+                                                                        uint64_t lo, uint64_t hi)
+{
+    const int lane = threadIdx.x & 63;
+    const bool lead = full && (lane & 7) == 0;
+    unsigned long long dst = overflow_reserve(cold, __ballot(lead), lead, b, kDstNone);
+    dst = __shfl(dst, lane & ~7);
+    if (full && dst != kDstDropped) {
+        ulonglong2 v; v.x = lo; v.y = hi;
+        store_entry_pair(cold->ovf_ent + (dst & ~kDstOvf) + 2 * ((uint32_t)lane & 7u), v);
+    }
+}
+// Sixteen bytes of a partial group go to the overflow list.
+__device__ __attribute__((noinline, cold)) void scatter_store_overflow(const ScatterCold *__restrict__ cold, unsigned long long to,
+                                                                       uint32_t sub, uint64_t lo, uint64_t hi)
+{
+    ulonglong2 v; v.x = lo; v.y = hi;
+    store_entry_pair(cold->ovf_ent + (to & ~kDstOvf) + 2 * sub, v);
+}
 // A low-complexity block is set aside for lowc_blocks_kernel.
 __device__ __attribute__((noinline, cold)) void scatter_set_aside(const ScatterCold *__restrict__ cold, uint32_t block)
 {
@@ -186,13 +226,6 @@ __device__ __attribute__((noinline, cold)) void scatter_set_aside(const ScatterC
 __device__ __attribute__((noinline, cold)) void scatter_protocol_failure(const ScatterCold *__restrict__ cold)
 {
     if ((threadIdx.x & 63) == 0) atomicOr(cold->ovf_cursor + 2, 1u);         // (ovf_cursor[0] stays a group count)
-}
-// Sixteen bytes of a group go to their place: to the region (the usual case) or to the overflow list.
-__device__ __forceinline__ void store_group_part(uint64_t *__restrict__ ent, const ScatterCold *__restrict__ cold, unsigned long long to,
-                                                 uint32_t sub, const ulonglong2 &v)
-{
-    if (__builtin_expect((to & kDstOvf) != 0, 0)) store_entry_pair(cold->ovf_ent + (to & ~kDstOvf) + 2 * sub, v);
-    else store_entry_pair(ent + to + 2 * sub, v);
 }
 // KG_F_PROGRESS: a query k-mer's home slot lies behind the end of the record stream.
 __device__ __attribute__((noinline, cold)) void scatter_note_beyond(const ScatterCold *__restrict__ cold, uint32_t slot)
@@ -219,7 +252,7 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
     const uint8_t *__restrict__ seq, const BlockDesc *__restrict__ blocks, uint32_t block_lo, uint32_t n_blocks /* of this launch */,
     uint32_t limit32 /* min(limit, 2^32 - 1); SHORT only */, uint32_t num_sigs /* 64 <= num_sigs < 2^31 */, uint32_t m35, uint32_t shift,
     uint32_t n_buckets, uint32_t cap, uint64_t *__restrict__ ent, uint32_t *__restrict__ fill, const ScatterCold *__restrict__ cold,
-    uint32_t insert_prio /* wave priority of the insert phase (0..3) */)
+    uint32_t insert_prio /* wave priority of the insert phase (0..3) */, uint32_t flush_list /* groups per flush pass (KG_SCATTER_FLUSH_LIST) */)
 {
     static_assert(SHORT || !PROG, "PROG implies SHORT");
     constexpr int ROWS = AA ? 1 : 6;
@@ -236,10 +269,12 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
     Tables &enc_tables = *reinterpret_cast<Tables *>(part_lds + enc_bytes * kScatterWaves);
     uint64_t *buf = reinterpret_cast<uint64_t *>(part_lds + enc_bytes * kScatterWaves + tab_bytes);
     uint32_t *cnt = reinterpret_cast<uint32_t *>(buf + (size_t)n_buckets * kGroup);
-    uint32_t *wrel = cnt + n_buckets;                 // entries already written to this workgroup's region of bucket b
-    uint32_t *written = wrel + n_buckets;             // entries of the current group whose LDS store has been issued
+    uint32_t *written = cnt + n_buckets;              // entries of bucket b whose LDS store has been issued, since the kernel began
+    uint32_t *flist = reinterpret_cast<uint32_t *>(&l);   // the wave's flush list (its encode scratch, idle while it inserts)
     const uint32_t w = blockIdx.x, n_wg = gridDim.x;
-    for (uint32_t b = threadIdx.x; b < n_buckets; b += blockDim.x) { cnt[b] = 0; wrel[b] = 0; written[b] = 0; }
+    const uint32_t gcap = cap >> 4;                   // groups a region holds
+    const uint32_t list_cap = max(min(flush_list, scatter_flush_list_max<AA>()), 1u);
+    for (uint32_t b = threadIdx.x; b < n_buckets; b += blockDim.x) { cnt[b] = 0; written[b] = 0; }
     encode_init<AA>(enc_tables, threadIdx.x, blockDim.x);
     __syncthreads();
 
@@ -323,83 +358,108 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
         n_valid += nv;
         // Insert without workgroup barriers.  A bucket's buffer is a 16-entry group with two counters:
         //   cnt[b]      tickets: atomicAdd gives the entry's place; >= 16 means "full, try again"
-        //   written[b]  stores issued; the lane whose increment makes it 16 owns the group: it (with seven helper
-        //               lanes of its wave) copies the 128 bytes to the region, then reopens the buffer (written = 0,
-        //               then cnt = 0).  Nobody else touches buf[b] / wrel[b] between the 16th ticket and the reopening.
+        //   written[b]  stores issued, never set back: the atomic returns the bucket's running entry count in this workgroup.
+        //               The lane that gets 16 g + 15 owns the group, the g-th of the region: eight lanes of its wave copy the
+        //               128 bytes to the region at 16 g (to the overflow list when 16 (g + 1) > cap) and reopen the buffer
+        //               (cnt = 0).  Nobody else touches buf[b] between the 16th ticket and the reopening.
         // LDS operations of one wave execute in program order and LDS is coherent in the workgroup, so the fences
-        // below only pin the compiler's order.  A lane that keeps failing waits for a flush that the owning wave
+        // below only pin the compiler's order (a workgroup release between a row's store and its second atomic would cost
+        // a wait for the LDS per row).  A lane that keeps failing waits for a flush that the owning wave
         // performs right after its own stores; it polls the counter with plain reads in the meantime: retrying the
         // atomic instead (16 waves on one counter: homopolymer runs) starves the flushing wave and can run the
         // 32-bit ticket counter round to zero, which hands out a full buffer's slots again (seen as an intermittent
         // stall before the polling loop existed).  The guards turn any remaining protocol failure into the host's
         // fallback to the direct strategy (sticky word ovf_cursor[2], kg_stats.fallback == 2) instead of a hang or a
         // wrong result.
-        uint32_t done = 0, spins = 0;
+        uint32_t spins = 0;
         if (insert_prio) set_wave_prio(insert_prio);                   // (uniform) few instructions between long LDS waits
         for (;;) {
-            uint32_t at[RG];
+            uint32_t at[RG], old[RG];
 #pragma unroll
-            for (int r = 0; r < RG; r++)                             // the LDS atomics of all rows in flight together
+            for (int r = 0; r < RG; r++)                             // the ticket atomics of all rows in flight together
                 at[r] = (pend & (1u << r)) ? atomicAdd(&cnt[bk[r]], 1u) : kGroup;
             // (retry rounds look before they draw: a full buffer is polled with plain reads, so that waiting lanes
             //  neither serialise on the counter against the flushing wave nor run the counter round to zero)
+            // ... and so are the second atomics: a row's store and its count in one exec region, the counts read after all
+            // rows.  A row that stored nothing keeps 0, which is no owner's value.
 #pragma unroll
-            for (int r = 0; r < RG; r++)
-                if (at[r] < kGroup) buf[(size_t)bk[r] * kGroup + at[r]] = e[r];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-#pragma unroll
-            for (int r = 0; r < RG; r++)
+            for (int r = 0; r < RG; r++) {
+                old[r] = 0;
                 if (at[r] < kGroup) {
-                    pend &= ~(1u << r);
-                    if (atomicAdd(&written[bk[r]], 1u) == kGroup - 1) done |= 1u << r;
+                    buf[(size_t)bk[r] * kGroup + at[r]] = e[r];
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    old[r] = atomicAdd(&written[bk[r]], 1u);
                 }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            // flush the groups completed by lanes of this wave: one per lane per pass, eight lanes per group
-            for (;;) {
-                const bool has = done != 0;
-                unsigned long long m = __ballot(has);
-                if (!m) break;
-                const int r0 = has ? __builtin_ctz(done) : 0;
-                uint32_t b = bk[0];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-                for (int r = 1; r < RG; r++)
-                    if (r0 == r) b = bk[r];
-                unsigned long long dst = kDstNone;
-                bool to_ovf = false;
-                if (has) {
-                    done &= done - 1;
-                    const uint32_t rel = wrel[b];
-                    if (rel + kGroup <= cap) {
-                        // (b * n_wg + w < 2^18 and cap < 2^24: 24-bit multiplies, full rate; the plain 64-bit expression
-                        //  compiles to three quarter-rate v_mad_u64_u32 per flush pass)
-                        dst = mul24_wide(b * n_wg + w, cap) + rel;
-                        wrel[b] = rel + kGroup;
-                    } else {
-                        to_ovf = true;
+            for (int r = 0; r < RG; r++) pend &= ~((uint32_t)(at[r] < kGroup) << r);
+            uint32_t at_max = at[0];                                  // (for the guard below)
+#pragma unroll
+            for (int r = 1; r < RG; r++) at_max = max(at_max, at[r]);
+            // Flush the groups completed by lanes of this wave, all of them in one pass: every owner puts {bucket, group
+            // number} on the wave's list (rank: one ballot per row), then octet o = lane / 8 copies the group of entry
+            // p0 + o, eight groups per trip.  Owners the list has no room for (list_cap entries) keep their rows in `left`
+            // and go in another pass: never with the default capacity unless more than 64 groups complete at once.  Their
+            // group numbers are read again then: written[b] stays at 16 (g + 1) until the owner has reopened the buffer.
+            uint32_t left = 0;
+            auto list_rows = [&](auto again) -> uint32_t {
+                uint32_t n = 0;                                       // (uniform) owners so far
+#pragma unroll
+                for (int r = 0; r < RG; r++) {
+                    const bool own = decltype(again)::value ? ((left >> r) & 1u) != 0 : (old[r] & 15u) == 15u;
+                    const unsigned long long m = __ballot(own);
+                    if (m) {
+                        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, n));
+                        if (own && rank < list_cap) {
+                            // (bk < kMaxBuckets = 2^10, gcap < 2^20)
+                            const uint32_t g = decltype(again)::value ? (written[bk[r]] >> 4) - 1u : old[r] >> 4;
+                            flist[rank] = (min(g, gcap) << 10) | bk[r];
+                            if (decltype(again)::value) left &= ~(1u << r);
+                        }
+                        n += (uint32_t)__popcll(m);
                     }
                 }
-                const unsigned long long movf = __ballot(to_ovf);      // region full: overflow list, one atomic per pass
-                if (__builtin_expect(movf != 0, 0)) dst = scatter_overflow_groups(cold, movf, to_ovf, b, dst);
-                // eight lanes copy one group; lane group g = lane / 8 serves the flushing lane of rank g + 8 * pass.
-                // rank -> lane goes through 64 bytes of the wave's (idle) encode scratch instead of a scalar bit loop
-                uint8_t *rank_lane = reinterpret_cast<uint8_t *>(&l);
-                const uint32_t n_flush = (uint32_t)__popcll(m);
-                if (has) rank_lane[__popcll(m & ((1ull << lane) - 1ull))] = (uint8_t)lane;
+                return n;
+            };
+            uint32_t n_own = list_rows(std::false_type{});
+            if (__builtin_expect(n_own > list_cap, 0)) {              // (uniform) who is not on the list yet
+                uint32_t k = 0;
+#pragma unroll
+                for (int r = 0; r < RG; r++) {
+                    const bool own = (old[r] & 15u) == 15u;
+                    const unsigned long long m = __ballot(own);
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, k));
+                    if (own && rank >= list_cap) left |= 1u << r;
+                    k += (uint32_t)__popcll(m);
+                }
+            }
+            while (n_own) {
+                const uint32_t n_list = min(n_own, list_cap);
                 wave_sync();
-                for (uint32_t p0 = 0; p0 < n_flush; p0 += 8) {
-                    const uint32_t want = p0 + ((uint32_t)lane >> 3);
-                    const bool serve = want < n_flush;
-                    const int sl = serve ? (int)rank_lane[want] : 0;
-                    const uint32_t fb = (uint32_t)__shfl((int)b, sl);
-                    const unsigned long long to = __shfl(dst, sl);
-                    if (serve && to != kDstDropped) {
-                        const uint32_t sub = (uint32_t)lane & 7u;
+                for (uint32_t p0 = 0; p0 < n_list; p0 += 8) {
+                    const uint32_t want = p0 + ((uint32_t)lane >> 3), sub = (uint32_t)lane & 7u;
+                    if (want < n_list) {                               // (whole octets; the first one always)
+                        const uint32_t d = flist[want];
+                        const uint32_t fb = d & (uint32_t)(kMaxBuckets - 1), g = d >> 10;
                         const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(buf + (size_t)fb * kGroup + 2 * sub);
-                        store_group_part(ent, cold, to, sub, v);
+                        // the buffer reopens behind the octet's reads (same wave: in order); a dropped group reopens it too
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        if (sub == 0) cnt[fb] = 0;
+                        const bool full = g >= gcap;
+                        // (b * n_wg + w < 2^24 and cap < 2^24: 24-bit multiplies, full rate; the plain 64-bit expression
+                        //  compiles to quarter-rate v_mad_u64_u32; the group's place in the region is below 2^24 entries)
+                        if (!full) {
+                            unsigned char *to = reinterpret_cast<unsigned char *>(ent) + (mul24_wide(__umul24(fb, n_wg) + w, cap) << 3);
+                            store_entry_pair(reinterpret_cast<uint64_t *>(to + ((g << 7) | (sub << 4))), v);
+                        }
+                        // region full: overflow list, one atomic per trip that needs it
+                        if (__builtin_expect(__ballot(full) != 0, 0)) scatter_overflow_octets(cold, full, fb, v.x, v.y);
                     }
                 }
-                wave_sync();                                           // the copies above read buf[b] before it reopens
-                if (has) { written[b] = 0; __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); cnt[b] = 0; }
+                wave_sync();                                           // (the list is written again by the next pass or round)
+                if (__builtin_expect(n_own <= list_cap, 1)) break;
+                n_own = list_rows(std::true_type{});
             }
             if (!__ballot(pend != 0)) break;
             // entries left: their buffers were full.  Wait until a lane's first waiting buffer reopens (bounded), then try
@@ -418,9 +478,6 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
             }
             // Never expected (see above).  The second test keeps a ticket counter far from wrapping round to zero,
             // which would hand out the slots of a full buffer a second time (kGroup, a row that drew nothing, is below it).
-            uint32_t at_max = at[0];
-#pragma unroll
-            for (int r = 1; r < RG; r++) at_max = max(at_max, at[r]);
             if (__builtin_expect(++spins > (1u << 20) || __ballot(at_max >= (1u << 28)), 0)) {
                 scatter_protocol_failure(cold);
                 break;
@@ -437,47 +494,48 @@ __global__ __launch_bounds__(kWave *kScatterWaves) KG_SCATTER_REGS void part_sca
     const uint32_t b_end = min((uint32_t)(wave + 1) * per_wave, n_buckets);
     for (uint32_t b0 = (uint32_t)wave * per_wave; b0 < b_end; b0 += 64) {
         const uint32_t b = b0 + (uint32_t)lane;
-        const uint32_t c = b < b_end ? cnt[b] : 0u;
+        const uint32_t wr = b < b_end ? written[b] : 0u;          // 16 g + c: g whole groups flushed, c entries in the buffer
+        const uint32_t c = wr & 15u, g = wr >> 4;
         unsigned long long dst = kDstNone;
         bool to_ovf = false;
         if (c > 0) {
             for (uint32_t k = c; k < kGroup; k++) buf[(size_t)b * kGroup + k] = kEntInvalid;
-            const uint32_t rel = wrel[b];
-            if (rel + kGroup <= cap) {
-                dst = ((uint64_t)b * n_wg + w) * cap + rel;
-                wrel[b] = rel + kGroup;
-            } else {
-                to_ovf = true;
-            }
-            cnt[b] = 0;
+            if (g < gcap) dst = ((uint64_t)b * n_wg + w) * cap + ((uint64_t)g << 4);
+            else to_ovf = true;
         }
         const unsigned long long movf = __ballot(to_ovf);
         if (movf) dst = scatter_overflow_groups(cold, movf, to_ovf, b, dst);
         unsigned long long m = __ballot(dst != kDstNone);
         wave_sync();                                             // the fillers above are read by other lanes below
         while (m) {
-            // the next (up to) eight flushing lanes; lane group g = lane / 8 takes the g-th of them
+            // the next (up to) eight flushing lanes; octet o = lane / 8 takes the o-th of them
             int src_lane = -1;
             unsigned long long mm = m;
 #pragma unroll
-            for (int g = 0; g < 8; g++) {
+            for (int o = 0; o < 8; o++) {
                 const int ln = mm ? __builtin_ctzll(mm) : -1;
                 if (mm) mm &= mm - 1;
-                if ((lane >> 3) == g) src_lane = ln;
+                if ((lane >> 3) == o) src_lane = ln;
             }
             m = mm;
             const int sl = src_lane < 0 ? 0 : src_lane;
             const uint32_t fb = (uint32_t)__shfl((int)b, sl);
             const unsigned long long to = __shfl(dst, sl);
-            if (src_lane >= 0 && to != kDstDropped) {
+            if (src_lane >= 0) {
                 const uint32_t sub = (uint32_t)lane & 7u;
                 const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(buf + (size_t)fb * kGroup + 2 * sub);
-                store_group_part(ent, cold, to, sub, v);
+                if (__builtin_expect((to & kDstOvf) != 0, 0)) {      // (kDstDropped has the bit too)
+                    if (to != kDstDropped) scatter_store_overflow(cold, to, sub, v.x, v.y);
+                } else {
+                    store_entry_pair(ent + to + 2 * sub, v);
+                }
             }
         }
     }
-    __syncthreads();
-    for (uint32_t b = threadIdx.x; b < n_buckets; b += blockDim.x) fill[(uint64_t)b * n_wg + w] = wrel[b];
+    // what the region holds: the whole groups and the partial one, as far as they went to the region (lowc_blocks_kernel
+    // appends behind it, the tag and index passes read up to it)
+    for (uint32_t b = threadIdx.x; b < n_buckets; b += blockDim.x)
+        fill[(uint64_t)b * n_wg + w] = min((written[b] + 15u) >> 4, gcap) << 4;
     for (int off = 32; off > 0; off >>= 1) n_valid += __shfl_down(n_valid, off);
     unsigned long long *ctr = cold->ctr;
     if (lane == 0 && n_valid) atomicAdd(&ctr[0], (unsigned long long)n_valid);
