@@ -1108,6 +1108,78 @@ int kg_voteset_seq_start(const kg_voteset *s, int64_t *dst);
 int kg_voteset_stats(const kg_voteset *s, kg_vote_stats *out);
 void kg_voteset_free(kg_voteset *s);
 
+/* ---- whose contig, without a vote: tetranucleotide composition against the voted contigs' (kernels: kg_compose.hpp) ----
+ *
+ * The reference stops at the OTU-COUNTS line; this stage is this project's own.  A genome's tetranucleotide usage is shared
+ * by its contigs whether or not a protein on them is known, and the contigs the votes stage assigned are a labelled training
+ * set.  Integers only.  Input: the batch's bytes exactly as a scan gets them, offsets[n_seqs + 1], labels[n_seqs] (a value
+ * >= 0 is the bin of a training contig, -1 means unlabelled, a value below -1 is KG_ERR_ARG naming the first such contig;
+ * NULL = all -1), the parameters and optionally a caller's model.
+ *   1. Tetramer index.  Four bases of dna_code < 4 give t = sum b_i * 4^(3-i), 0 <= t < 256.  A tetramer with a base of code 4
+ *      does not exist, a tetramer never spans two contigs, a contig with L < 4 has none.
+ *   2. Contig counts N_s[256] (int32).  F_s[t] = the forward tetramers of contig s with index t; N_s[t] = F_s[t] + F_s[rc(t)],
+ *      where rc complements every 2-bit digit and reverses their order: both strands, so a contig and its reverse complement
+ *      have the same N.  The 16 palindromic tetramers count twice (stated, not repaired).  windows_s = sum_t N_s[t].  A contig
+ *      with L >= 2^30 is KG_ERR_LIMIT.
+ *   3. Label rows.  For every distinct label b >= 0, in ascending order, C_b[t] = the int64 sum of N_s[t] over the contigs
+ *      with label b, SC_b = sum_t C_b[t].  The background row G[t] = the sum of N_s[t] over all contigs, labelled or not.
+ *   4. Models.  A label row is a model when SC_b >= min_train (windows); models keep the ascending label order and are indexed
+ *      0 .. M-1, the background is always present as index M.  A caller's model is a set of rows (labels >= 0 and strictly
+ *      ascending, counts >= 0, every row sum < 2^62, the background last; anything else is KG_ERR_ARG): every one of its rows
+ *      is a model, min_train is ignored, and the call makes no label rows (its rows and its background are all zero).
+ *   5. Weights (host code, the Lg of the coding section): W_m[t] = Lg(C_m[t] + 1) - Lg(SC_m + 256), int32, the same for the
+ *      background row.
+ *   6. Scores.  S[s][m] = sum_t N_s[t] * W_m[t] (int64, exact; |S| < 2^45) for every contig and every m in 0 .. M.
+ *   7. Order.  A contig's rows are ordered by score descending, then m ascending, so on a tie a bin comes before the
+ *      background; best and second are the first two.  With M = 0 there is only the background: best = second = -1,
+ *      score_second = score_best, never decided.
+ *   8. Decision.  decided = 1 iff L_s >= min_len and best is a model (not the background) and S_best - S_second >= min_margin.
+ *      Defaults (this project's choice): min_len = 1500 nt, min_margin = 2560 (ten bits in Lg's units of 1/256 bit),
+ *      min_train = 200000 windows (about 100 kbp).
+ *   9. Labelled contigs are scored and decided like any other; their own tetramers are in their bin's model (stated, not
+ *      corrected).  A labelled contig that is decided for another bin is a conflict: counted, nothing else.
+ *  10. Independence.  The per-contig outputs depend only on that contig's bytes and the models; the label rows and the
+ *      background of two batches add up; nothing depends on launch geometry, tile sizes or batch neighbours.
+ * kg_comp_class: label = the contig's label as given, best / second = label values (-1 = the background).  keep_scores != 0
+ * keeps the matrix S (int64 [n_seqs][M + 1]) for kg_compset_copy_scores; otherwise it does not exist.
+ * Errors: KG_ERR_ARG for null pointers, reserved fields, negative parameters, decreasing offsets, a label below -1, a bad
+ * model (model_labels and model_counts are both given or both NULL) -- each message names the first offender; KG_ERR_LIMIT for
+ * 2^31 or more sequences, 2^40 or more bytes, a contig of 2^30 or more nucleotides, more than 2^20 label rows or model rows,
+ * a kept score matrix of 2^40 bytes or more; KG_ERR_NOMEM.  A bad label is never used as an index.  Zero sequences, zero
+ * labels and zero models are valid.  The call owns a table-less context as kg_otu_votes_hits does, so KG_TEST_FAIL_ALLOC
+ * applies; everything but the set's arrays is back in the cache on every path out.  One host wait in the middle (the rows come
+ * down, W is made on the host and goes up); none with a caller's model. */
+typedef struct kg_comp_params { int32_t min_len; int32_t min_margin; int64_t min_train; int32_t keep_scores; int32_t reserved; } kg_comp_params;
+typedef struct kg_comp_class {   /* 40 B */
+    int32_t  label, best, second, decided;
+    int64_t  windows, score_best, score_second;
+} kg_comp_class;
+typedef struct kg_comp_stats {
+    int64_t seqs, labelled, label_rows, models, windows, decided, decided_unlabelled, conflicts;
+    float   ms_count, ms_score;     /* device time: counts, fold and label rows; scores and decisions */
+} kg_comp_stats;
+typedef struct kg_compset kg_compset;
+/* model_counts: (n_models + 1) * 256 counts, the background row last */
+int kg_contigs_compose(int device, const kg_comp_params *p, const uint8_t *seq, int seq_on_device, const int64_t *offsets,
+                       int64_t n_seqs, const int32_t *labels, const int32_t *model_labels, const int64_t *model_counts,
+                       int64_t n_models, kg_compset **out);
+/* the label rows the call made, and the models it scored with */
+int64_t kg_compset_rows(const kg_compset *s);
+int64_t kg_compset_models(const kg_compset *s);
+/* records [first, first + count) into dst (host or device memory) */
+int kg_compset_copy_classes(const kg_compset *s, int64_t first, int64_t count, kg_comp_class *dst);
+/* N of contigs [first, first + count): int32[256] each */
+int kg_compset_copy_counts(const kg_compset *s, int64_t first, int64_t count, int32_t *dst);
+/* label rows [first, first + count): their labels and their int64[256] counts (either dst may be NULL) */
+int kg_compset_copy_rows(const kg_compset *s, int64_t first, int64_t count, int32_t *labels_dst, int64_t *counts_dst);
+/* G: int64[256] */
+int kg_compset_background(const kg_compset *s, int64_t *dst);
+int kg_compset_model_labels(const kg_compset *s, int64_t first, int64_t count, int32_t *dst);
+/* S of contigs [first, first + count): int64[M + 1] each; KG_ERR_ARG when the call did not keep the matrix */
+int kg_compset_copy_scores(const kg_compset *s, int64_t first, int64_t count, int64_t *dst);
+int kg_compset_stats(const kg_compset *s, kg_comp_stats *out);
+void kg_compset_free(kg_compset *s);
+
 /* the resident 24-byte records, valid until kg_table_close, and how many there are: num_sigs for a built or adopted table, the
  * whole records of the file for an opened one (fewer than num_sigs for a truncated file, more for a longer one) */
 const void *kg_table_device_entries(const kg_table *t);

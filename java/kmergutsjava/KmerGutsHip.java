@@ -286,6 +286,26 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_comp_params (kg_contigs_compose); the defaults are 1500, 2560 and 200000. */
+    class KgCompParams extends Structure {
+        public int min_len, min_margin;
+        public long min_train;
+        public int keep_scores, reserved;
+        public KgCompParams() {
+            setFieldOrder(new String[] {"min_len", "min_margin", "min_train", "keep_scores", "reserved"});
+        }
+    }
+
+    /** struct kg_comp_stats. */
+    class KgCompStats extends Structure {
+        public long seqs, labelled, label_rows, models, windows, decided, decided_unlabelled, conflicts;
+        public float ms_count, ms_score;
+        public KgCompStats() {
+            setFieldOrder(new String[] {"seqs", "labelled", "label_rows", "models", "windows", "decided", "decided_unlabelled",
+                                        "conflicts", "ms_count", "ms_score"});
+        }
+    }
+
     /** struct kg_interval (20 B): one candidate of kg_select_intervals, 0-based inclusive left / right. */
     class KgInterval extends Structure {
         public int seq, left, right, score, eligible;
@@ -513,6 +533,24 @@ public interface KmerGutsHip extends Library {
     int kg_voteset_seq_start(Pointer set, long[] dst);       // long[nSeqs + 1]
     int kg_voteset_stats(Pointer set, KgVoteStats out);
     void kg_voteset_free(Pointer set);
+    /** bins by tetranucleotide composition: labels = int[nSeqs] (>= 0 a training contig's bin, -1 unlabelled) or null; a caller's
+     *  model = modelLabels int[nModels] and modelCounts long[(nModels + 1) * 256], the background row last, or both null */
+    int kg_contigs_compose(int device, KgCompParams params, Pointer seq, int seqOnDevice, long[] offsets, long nSeqs, int[] labels,
+                           int[] modelLabels, long[] modelCounts, long nModels, PointerByReference out);
+    long kg_compset_rows(Pointer set);                       // label rows the call made
+    long kg_compset_models(Pointer set);                     // models the scores are under (the background comes behind them)
+    /** dst: count packed 40-byte kg_comp_class records (int label, best, second, decided; long windows, score_best, score_second) */
+    int kg_compset_copy_classes(Pointer set, long first, long count, Pointer dst);
+    /** dst: count * 256 ints, the tetramer counts of contigs first .. */
+    int kg_compset_copy_counts(Pointer set, long first, long count, Pointer dst);
+    /** labelsDst: count ints; countsDst: count * 256 longs (either may be null) */
+    int kg_compset_copy_rows(Pointer set, long first, long count, Pointer labelsDst, Pointer countsDst);
+    int kg_compset_background(Pointer set, long[] dst);      // long[256]
+    int kg_compset_model_labels(Pointer set, long first, long count, Pointer dst);
+    /** dst: count * (models + 1) longs; only when keep_scores was set */
+    int kg_compset_copy_scores(Pointer set, long first, long count, Pointer dst);
+    int kg_compset_stats(Pointer set, KgCompStats out);
+    void kg_compset_free(Pointer set);
     void kg_result_free(Pointer result);
     int kg_restore_hits_device(int device, Pointer dSrc, long nHits, Pointer dSeqFirst, long nSeqs, Pointer dDstFirst,
                                Pointer dContainerShift, Pointer dDst, Pointer stream);

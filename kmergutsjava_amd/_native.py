@@ -51,6 +51,9 @@ EXPORTS = (
     "kg_selectset_copy", "kg_selectset_stats", "kg_selectset_free",
     "kg_result_otu_votes", "kg_otu_votes_hits", "kg_voteset_count", "kg_voteset_bins", "kg_voteset_copy_votes",
     "kg_voteset_copy_classes", "kg_voteset_copy_bins", "kg_voteset_seq_start", "kg_voteset_stats", "kg_voteset_free",
+    "kg_contigs_compose", "kg_compset_rows", "kg_compset_models", "kg_compset_copy_classes", "kg_compset_copy_counts",
+    "kg_compset_copy_rows", "kg_compset_background", "kg_compset_model_labels", "kg_compset_copy_scores", "kg_compset_stats",
+    "kg_compset_free",
     "kg_last_error", "kg_version",
 )
 
@@ -113,6 +116,14 @@ OTU_CLASS_DTYPE = np.dtype([("otu", "<i4"), ("assigned", "<i4"), ("votes", "<i4"
                             ("reserved", "<i4")])
 OTU_BIN_DTYPE = np.dtype([("oI", "<i4"), ("n_seqs", "<i4"), ("length", "<i8"), ("votes", "<i8"), ("n_calls", "<i8")])
 assert VOTE_DTYPE.itemsize == 16 and OTU_CLASS_DTYPE.itemsize == 40 and OTU_BIN_DTYPE.itemsize == 32
+# struct kg_comp_class (kg_contigs_compose): one contig's bin by tetranucleotide composition
+COMP_CLASS_DTYPE = np.dtype([("label", "<i4"), ("best", "<i4"), ("second", "<i4"), ("decided", "<i4"), ("windows", "<i8"),
+                             ("score_best", "<i8"), ("score_second", "<i8")])
+assert COMP_CLASS_DTYPE.itemsize == 40
+COMP_BINS = 256             # tetramer indices: the entries of a contig's counts and of a model row
+COMP_TILE = 2048            # kg_compose.hpp kCompTile: the tetramer starts of one workgroup step (tests aim at its edges) ...
+COMP_MAX_GRID = 2048        # ... kCompMaxGrid: the workgroups the count pass has at most ...
+COMP_SCORE_TILE = 16        # ... and kCompScoreTile: the models of one LDS tile of the score pass
 # struct kg_family (kg_proteins_cluster*): one protein's family
 FAMILY_DTYPE = np.dtype([("family", "<i4"), ("root", "<i4"), ("best", "<i4"), ("shared", "<i4")])
 assert FAMILY_DTYPE.itemsize == 16
@@ -331,6 +342,22 @@ class KgVoteStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class KgCompParams(C.Structure):
+    """struct kg_comp_params (kg_contigs_compose)."""
+    _fields_ = [("min_len", C.c_int32), ("min_margin", C.c_int32), ("min_train", C.c_int64), ("keep_scores", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class KgCompStats(C.Structure):
+    """struct kg_comp_stats."""
+    _fields_ = [("seqs", C.c_int64), ("labelled", C.c_int64), ("label_rows", C.c_int64), ("models", C.c_int64),
+                ("windows", C.c_int64), ("decided", C.c_int64), ("decided_unlabelled", C.c_int64), ("conflicts", C.c_int64),
+                ("ms_count", C.c_float), ("ms_score", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class KmerGutsNativeError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__("libkmerguts_hip error %d: %s" % (code, msg))
@@ -477,6 +504,17 @@ def load() -> C.CDLL:
     lib.kg_voteset_stats.argtypes = [vp, C.POINTER(KgVoteStats)]
     lib.kg_voteset_free.argtypes = [vp]
     lib.kg_voteset_free.restype = None
+    lib.kg_contigs_compose.argtypes = [C.c_int, C.POINTER(KgCompParams), vp, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, C.POINTER(vp)]
+    for name in ("kg_compset_rows", "kg_compset_models"):
+        getattr(lib, name).argtypes = [vp]
+        getattr(lib, name).restype = C.c_int64
+    for name in ("kg_compset_copy_classes", "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores"):
+        getattr(lib, name).argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.kg_compset_copy_rows.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
+    lib.kg_compset_background.argtypes = [vp, vp]
+    lib.kg_compset_stats.argtypes = [vp, C.POINTER(KgCompStats)]
+    lib.kg_compset_free.argtypes = [vp]
+    lib.kg_compset_free.restype = None
     for name in ("kg_proteins_cluster", "kg_proteins_cluster_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), vp, vp, C.c_int64, C.c_int64, C.POINTER(vp)]
     lib.kg_familyset_count.argtypes = [vp]

@@ -23,6 +23,7 @@
 #include "kg_repair.hpp"
 #include "kg_select.hpp"
 #include "kg_votes.hpp"
+#include "kg_compose.hpp"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -53,3 +54,4 @@
 #include "kg_host_starts.hpp"
 #include "kg_host_select.hpp"
 #include "kg_host_votes.hpp"
+#include "kg_host_compose.hpp"

@@ -882,6 +882,71 @@ def _seq_bytes(seq, off) -> np.ndarray:
     return arr
 
 
+def compose_contigs(seq, offsets, labels=None, model=None, min_len: int = 1500, min_margin: int = 2560, min_train: int = 200000,
+                    keep_scores: bool = False, device: int = 0, device_out: bool = False, stats: Optional[dict] = None) -> dict:
+    """Bin contigs by tetranucleotide composition, on the GPU and without a table (kg_contigs_compose; include/kmerguts_hip.h
+    states the rule).  seq the batch's bytes, offsets int64[n_seqs + 1], labels int32[n_seqs] (>= 0 the bin of a training contig,
+    -1 unlabelled; None = all -1), model None or (labels int32[M], counts int64[M + 1][256], the background row last).
+    -> {"classes": COMP_CLASS_DTYPE[n_seqs], "counts": int32[n_seqs][256], "row_labels": int32[R], "rows": int64[R][256],
+    "background": int64[256], "model_labels": int32[M]} and with keep_scores "scores": int64[n_seqs][M + 1]; classes, counts and
+    scores are CUDA tensors with device_out=True (classes as uint8 of 40 bytes per contig).  `stats`, when given, receives the
+    call's counts and device times."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_seqs + 1]")
+    n = off.size - 1
+    arr = _seq_bytes(seq, off)
+    lab = None
+    if labels is not None:
+        lab = np.ascontiguousarray(np.asarray(labels, dtype=np.int32))
+        if lab.shape != (n,):
+            raise ValueError("labels must be int32[n_seqs]")
+    ml = mc = None
+    n_models = 0
+    if model is not None:
+        ml = np.ascontiguousarray(np.asarray(model[0], dtype=np.int32).reshape(-1))
+        mc = np.ascontiguousarray(np.asarray(model[1], dtype=np.int64))
+        n_models = ml.size
+        if mc.size != (n_models + 1) * N.COMP_BINS:
+            raise ValueError("model counts are int64[n_models + 1][%d], the background row last" % N.COMP_BINS)
+    p = N.KgCompParams(int(min_len), int(min_margin), int(min_train), 1 if keep_scores else 0, 0)
+    lib = N.load()
+    h = C.c_void_p()
+    N.check(lib.kg_contigs_compose(device, C.byref(p), arr.ctypes.data if arr.size else None, 0, off.ctypes.data, n,
+                                   lab.ctypes.data if lab is not None and n else None, ml.ctypes.data if n_models else None,
+                                   mc.ctypes.data if mc is not None else None, n_models, C.byref(h)))
+    try:
+        st = N.KgCompStats()
+        N.check(lib.kg_compset_stats(h, C.byref(st)))
+        R, M = int(lib.kg_compset_rows(h)), int(lib.kg_compset_models(h))
+        out = {"row_labels": np.zeros(R, dtype=np.int32), "rows": np.zeros((R, N.COMP_BINS), dtype=np.int64),
+               "background": np.zeros(N.COMP_BINS, dtype=np.int64), "model_labels": np.zeros(M, dtype=np.int32)}
+        N.check(lib.kg_compset_copy_rows(h, 0, R, out["row_labels"].ctypes.data if R else None, out["rows"].ctypes.data if R else None))
+        N.check(lib.kg_compset_background(h, out["background"].ctypes.data))
+        N.check(lib.kg_compset_model_labels(h, 0, M, out["model_labels"].ctypes.data if M else None))
+        parts = [("classes", lib.kg_compset_copy_classes, N.COMP_CLASS_DTYPE, ()), ("counts", lib.kg_compset_copy_counts, np.dtype(np.int32), (N.COMP_BINS,))]
+        if keep_scores:
+            parts.append(("scores", lib.kg_compset_copy_scores, np.dtype(np.int64), (M + 1,)))
+        for name, copy, dt, shape in parts:
+            if device_out:
+                import torch
+                if name == "classes":
+                    a = torch.empty(n * dt.itemsize, dtype=torch.uint8, device="cuda")
+                else:
+                    a = torch.empty((n,) + shape, dtype=torch.int32 if dt.itemsize == 4 else torch.int64, device="cuda")
+                torch.cuda.synchronize()
+                N.check(copy(h, 0, n, C.c_void_p(a.data_ptr() if n else None)))
+            else:
+                a = np.zeros((n,) + shape, dtype=dt)
+                N.check(copy(h, 0, n, a.ctypes.data if n else None))
+            out[name] = a
+        if stats is not None:
+            stats.update(st.as_dict())
+        return out
+    finally:
+        lib.kg_compset_free(h)
+
+
 def _take_orfset(h, device_out: bool):
     """Copy a kg_orfset out (to the host, or into CUDA tensors) and free it.  -> (records, prot_start, residues, statistics)."""
     lib = N.load()
