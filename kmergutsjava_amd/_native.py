@@ -424,14 +424,7 @@ def load() -> C.CDLL:
     lib.kg_result_free.restype = None
     for name in ("kg_signatures_derive", "kg_signatures_derive_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgDeriveParams), vp, vp, C.c_int64, vp, vp, C.POINTER(vp)]
-    lib.kg_sigset_count.argtypes = [vp]
-    lib.kg_sigset_count.restype = C.c_int64
-    lib.kg_sigset_device.argtypes = [vp]
-    lib.kg_sigset_device.restype = vp
-    lib.kg_sigset_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
     lib.kg_sigset_stats.argtypes = [vp, C.POINTER(KgDeriveStats)]
-    lib.kg_sigset_free.argtypes = [vp]
-    lib.kg_sigset_free.restype = None
     for name in ("kg_table_merge_signatures", "kg_table_merge_signatures_device"):
         getattr(lib, name).argtypes = [vp, C.POINTER(KgMergeParams), vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.POINTER(vp)]
     lib.kg_sigset_merge_stats.argtypes = [vp, C.POINTER(KgMergeStats)]
@@ -439,45 +432,22 @@ def load() -> C.CDLL:
     lib.kg_assign_calls.argtypes = [C.c_int, C.POINTER(KgAssignParams), vp, vp, C.c_int64, vp, vp]
     lib.kg_result_regions.argtypes = [vp, C.POINTER(KgRegionParams), vp, C.POINTER(vp)]
     lib.kg_regions_calls.argtypes = [C.c_int, C.POINTER(KgRegionParams), vp, C.c_int64, vp, C.c_int64, C.POINTER(vp)]
-    lib.kg_regionset_count.argtypes = [vp]
-    lib.kg_regionset_count.restype = C.c_int64
-    lib.kg_regionset_device.argtypes = [vp]
-    lib.kg_regionset_device.restype = vp
-    lib.kg_regionset_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
-    lib.kg_regionset_seq_start.argtypes = [vp, vp]
     lib.kg_regionset_stats.argtypes = [vp, C.POINTER(KgRegionStats)]
-    lib.kg_regionset_free.argtypes = [vp]
-    lib.kg_regionset_free.restype = None
     lib.kg_regionset_orfs.argtypes = [vp, C.POINTER(KgOrfParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
     lib.kg_orfs_regions.argtypes = [C.c_int, C.POINTER(KgOrfParams), vp, C.c_int64, vp, vp, C.c_int64, C.POINTER(vp)]
-    lib.kg_orfset_count.argtypes = [vp]
-    lib.kg_orfset_count.restype = C.c_int64
-    lib.kg_orfset_device.argtypes = [vp]
-    lib.kg_orfset_device.restype = vp
-    lib.kg_orfset_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
-    lib.kg_orfset_prot_start.argtypes = [vp, vp]
-    lib.kg_orfset_residues.argtypes = [vp, C.c_int64, C.c_int64, vp]
     lib.kg_orfset_stats.argtypes = [vp, C.POINTER(KgOrfStats)]
-    lib.kg_orfset_free.argtypes = [vp]
-    lib.kg_orfset_free.restype = None
     lib.kg_orfs_free.argtypes = [C.c_int, C.POINTER(KgFreeParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
     lib.kg_orfset_add_free.argtypes = [vp, C.POINTER(KgFreeParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
     lib.kg_regionset_repair.argtypes = [vp, vp, vp, C.c_int, C.c_int64, C.POINTER(KgRepairParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
     lib.kg_result_repair.argtypes = [vp, vp, vp, C.POINTER(KgRepairParams), vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
-    lib.kg_orfset_junctions_count.argtypes = [vp]
-    lib.kg_orfset_junctions_count.restype = C.c_int64
-    lib.kg_orfset_junctions_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
-    lib.kg_orfset_junctions_start.argtypes = [vp, vp]
     lib.kg_orfset_junctions_stats.argtypes = [vp, C.POINTER(KgRepairStats)]
     lib.kg_orfset_coding.argtypes = [vp, C.POINTER(KgCodingParams), vp, vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
-    lib.kg_orfset_coding_scores.argtypes = [vp, C.c_int64, C.c_int64, vp]
     lib.kg_orfset_coding_stats.argtypes = [vp, C.POINTER(KgCodingStats)]
     lib.kg_orfset_coding_model.argtypes = [vp, C.POINTER(KgCodingModel)]
     lib.kg_coding_table.argtypes = [C.POINTER(KgCodingModel), vp]
     lib.kg_coding_counts_orfs.argtypes = [C.c_int, vp, C.c_int64, vp, vp, C.c_int64, C.POINTER(KgCodingModel)]
     lib.kg_coding_score_orfs.argtypes = [C.c_int, vp, vp, C.c_int64, vp, vp, C.c_int64, vp]
     lib.kg_orfset_starts.argtypes = [vp, C.POINTER(KgStartParams), vp, vp, vp, vp, C.c_int, vp, C.c_int64, C.POINTER(vp)]
-    lib.kg_orfset_start_shifts.argtypes = [vp, C.c_int64, C.c_int64, vp]
     lib.kg_orfset_start_stats.argtypes = [vp, C.POINTER(KgStartStats)]
     lib.kg_orfset_start_model.argtypes = [vp, C.POINTER(KgStartModel)]
     lib.kg_start_weights_from.argtypes = [C.POINTER(KgStartModel), C.POINTER(KgStartWeights)]
@@ -485,44 +455,36 @@ def load() -> C.CDLL:
     lib.kg_regionset_select.argtypes = [vp, C.POINTER(KgSelectParams), C.POINTER(vp)]
     lib.kg_orfset_select.argtypes = [vp, C.POINTER(KgSelectParams), C.POINTER(vp)]
     lib.kg_select_intervals.argtypes = [C.c_int, C.POINTER(KgSelectParams), vp, C.c_int64, C.c_int64, C.POINTER(vp)]
-    lib.kg_selectset_count.argtypes = [vp]
-    lib.kg_selectset_count.restype = C.c_int64
-    lib.kg_selectset_device.argtypes = [vp]
-    lib.kg_selectset_device.restype = vp
-    lib.kg_selectset_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
     lib.kg_selectset_stats.argtypes = [vp, C.POINTER(KgSelectStats)]
-    lib.kg_selectset_free.argtypes = [vp]
-    lib.kg_selectset_free.restype = None
     lib.kg_result_otu_votes.argtypes = [vp, C.POINTER(KgVoteParams), vp, C.POINTER(vp)]
     lib.kg_otu_votes_hits.argtypes = [C.c_int, C.POINTER(KgVoteParams), vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, C.POINTER(vp)]
-    for name in ("kg_voteset_count", "kg_voteset_bins"):
-        getattr(lib, name).argtypes = [vp]
-        getattr(lib, name).restype = C.c_int64
-    for name in ("kg_voteset_copy_votes", "kg_voteset_copy_classes", "kg_voteset_copy_bins"):
-        getattr(lib, name).argtypes = [vp, C.c_int64, C.c_int64, vp]
-    lib.kg_voteset_seq_start.argtypes = [vp, vp]
     lib.kg_voteset_stats.argtypes = [vp, C.POINTER(KgVoteStats)]
-    lib.kg_voteset_free.argtypes = [vp]
-    lib.kg_voteset_free.restype = None
     lib.kg_contigs_compose.argtypes = [C.c_int, C.POINTER(KgCompParams), vp, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, C.POINTER(vp)]
-    for name in ("kg_compset_rows", "kg_compset_models"):
-        getattr(lib, name).argtypes = [vp]
-        getattr(lib, name).restype = C.c_int64
-    for name in ("kg_compset_copy_classes", "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores"):
-        getattr(lib, name).argtypes = [vp, C.c_int64, C.c_int64, vp]
     lib.kg_compset_copy_rows.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
-    lib.kg_compset_background.argtypes = [vp, vp]
     lib.kg_compset_stats.argtypes = [vp, C.POINTER(KgCompStats)]
-    lib.kg_compset_free.argtypes = [vp]
-    lib.kg_compset_free.restype = None
     for name in ("kg_proteins_cluster", "kg_proteins_cluster_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), vp, vp, C.c_int64, C.c_int64, C.POINTER(vp)]
-    lib.kg_familyset_count.argtypes = [vp]
-    lib.kg_familyset_count.restype = C.c_int64
-    lib.kg_familyset_copy.argtypes = [vp, C.c_int64, C.c_int64, vp]
     lib.kg_familyset_stats.argtypes = [vp, C.POINTER(KgClusterStats)]
-    lib.kg_familyset_free.argtypes = [vp]
-    lib.kg_familyset_free.restype = None
+    # the sets' accessors, by signature: (set) -> count, (set) -> device address, (set, first, count, dst), (set, dst), (set)
+    for name in ("kg_sigset_count", "kg_familyset_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
+                 "kg_selectset_count", "kg_voteset_count", "kg_voteset_bins", "kg_compset_rows", "kg_compset_models"):
+        getattr(lib, name).argtypes = [vp]
+        getattr(lib, name).restype = C.c_int64
+    for name in ("kg_sigset_device", "kg_regionset_device", "kg_orfset_device", "kg_selectset_device"):
+        getattr(lib, name).argtypes = [vp]
+        getattr(lib, name).restype = vp
+    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
+                 "kg_orfset_junctions_copy", "kg_orfset_coding_scores", "kg_orfset_start_shifts", "kg_selectset_copy",
+                 "kg_voteset_copy_votes", "kg_voteset_copy_classes", "kg_voteset_copy_bins", "kg_compset_copy_classes",
+                 "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores"):
+        getattr(lib, name).argtypes = [vp, C.c_int64, C.c_int64, vp]
+    for name in ("kg_regionset_seq_start", "kg_orfset_prot_start", "kg_orfset_junctions_start", "kg_voteset_seq_start",
+                 "kg_compset_background"):
+        getattr(lib, name).argtypes = [vp, vp]
+    for name in ("kg_sigset_free", "kg_familyset_free", "kg_regionset_free", "kg_orfset_free", "kg_selectset_free",
+                 "kg_voteset_free", "kg_compset_free"):
+        getattr(lib, name).argtypes = [vp]
+        getattr(lib, name).restype = None
     lib.kg_last_error.restype = C.c_char_p
     lib.kg_version.restype = C.c_char_p
     for name in EXPORTS:

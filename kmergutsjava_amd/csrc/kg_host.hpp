@@ -1,6 +1,7 @@
 // kg_host.hpp -- what the host side of every stage needs: the error text, the device and pinned block caches, kg_table and
-// kg_result with the names of their numbered slots, the environment readers, the per-call scope and scratch, and the helpers the
-// stages share (prefix sum, one launch for several clears, radix sort of pairs, pinned upload).
+// kg_result with the names of their numbered slots, the environment readers, the per-call scope and scratch, the base of the
+// result sets and their getters, and the helpers the stages share (prefix sum, one launch for several clears, radix sort of
+// pairs, pinned upload).
 // Part of kmerguts_hip.hip's translation unit: the first host file, behind the kernel headers; the hosts of the table, the
 // result, the scan and the batch stages (kg_host_*.hpp) follow it.
 #pragma once
@@ -192,7 +193,7 @@ enum : int {
 };
 static_assert(kPevChunk + 2 * kMaxChunks <= kPevFork && kPevVerified + kMaxChunks <= kPevBase && kPevBase + kMaxChunks <= kPevOrdered &&
               kPevOrdered + kMaxOrderStreams <= kPevCount, "event slots overlap");
-// kg_table::ev, the timing events of a scan (outside a scan they are free: kg_result_copy_hits, assign_impl, regions_impl, orfs_impl, votes_impl)
+// kg_table::ev, the timing events of a scan (outside a scan they are free to any call that holds the table)
 enum : int { kEvBegin = 0, kEvScanBegin = 1, kEvScanEnd = 2, kEvOrderEnd = 3, kEvAggEnd = 4, kEvScattered = 5 /* all chunks */, kEvSpare = 6,
              kEvJoined = 7 /* stream2 and stream3 joined */, kEvCount = 8, kEvStageBegin = kEvBegin, kEvStageEnd = kEvScanBegin };
 // d_totals, the counter words of a scan
@@ -211,14 +212,13 @@ enum : int { kOvfGroups = 0 /* overflow groups */, kOvfLowc = 1 /* low-complexit
 // host per copy; to pinned memory it does not)
 enum : int { kPinPc = 0 /* d_pc */, kPinOvf = 48 /* d_ovfc */, kPinTotals = 80 /* d_totals[0 .. kTotSent) */, kPinCalls = 88 /* CALL total */,
              kPinPieces = 89, kPinWords = 96,
-             // the stage area (assign_impl, regions_impl, orfs_impl, votes_impl: kPinVotes in kg_host_votes.hpp) lies over the scan's totals: such a call holds the table, no scan is in flight
-             kPinRegions = 80 /* two totals, then the error and counter words */,
-             kPinAssign = 90 /* long proteins, their CALLs, then the error words */,
-             kPinOrfs = 80 /* the error and counter words, then the residue total */ };
+             // the stage area lies over the scan's totals: any call that holds the table and runs no scan may use it.  A stage
+             // static_asserts the words it needs against kPinStageWords, beside its own word enums.
+             kPinStage = 80, kPinStageWords = kPinWords - kPinStage,
+             kPinAssign = 90 /* inside the stage area: long proteins, their CALLs, then the error words */ };
 static_assert(kPinPc + kPcWords <= kPinOvf && kOvfWords * kMaxChunks * 4 <= (kPinTotals - kPinOvf) * 8 && kPinTotals + kTotSent <= kPinCalls,
               "counters must fit their pinned words");
-static_assert(kPinRegions + kg::kRegionErrWords + 2 <= kPinAssign && kPinAssign + 2 + 3 <= kPinWords &&
-              kPinOrfs + kg::kOrfErrWords + kg::kOrfCntWords + 1 <= kPinWords, "stage words must fit their pinned words");
+static_assert(kPinAssign >= kPinStage && kPinAssign + 2 + 3 <= kPinWords, "stage words must fit their pinned words");
 
 struct kg_table {
     int device = 0;
@@ -368,7 +368,7 @@ struct CallScope {
         if (!owned) HIP_TRY(hipSetDevice(t->device));       // (table_new has set the device of an owned context)
         return KG_OK;
     }
-    // the context goes to what the call hands out (a table, kg_result::own_tab, kg_regionset::own_tab)
+    // the context goes to what the call hands out (a table, kg_result::own_tab, SetBase::own_tab)
     kg_table *disown() { kg_table *out = t; t = nullptr; out->fail_alloc_at = 0; return out; }
 };
 
@@ -429,6 +429,91 @@ struct Scratch {
         return KG_OK;
     }
 };
+
+// What the result sets that live in a context share (kg_regionset, kg_orfset, kg_selectset, kg_voteset, kg_compset): the
+// context, whether the set owns it, and the device blocks the set took out of its cache.  A set keeps typed d_* members
+// for reading; only this list frees.  Delete a set only while its context's stream is idle (see DevCache).
+struct SetBase {
+    kg_table *tab = nullptr;            // the context whose block cache the arrays came from
+    bool own_tab = false;               // the set owns a table-less context (hand_out)
+    std::vector<void *> blocks;
+    SetBase() = default;
+    SetBase(const SetBase &) = delete;
+    SetBase &operator=(const SetBase &) = delete;
+    ~SetBase()
+    {
+        if (!tab) return;
+        (void)hipSetDevice(tab->device);
+        for (void *p : blocks) dfree(tab, p);
+        if (own_tab) kg_table_close(tab);
+    }
+    // p leaves the call's scratch and is the set's from here on (null: nothing to keep)
+    template <typename T> T *keep(Scratch &sc, T *p)
+    {
+        if (p) { blocks.push_back(p); sc.release(p); }
+        return p;
+    }
+};
+
+// The set a call will hand out, in the call's context.  Declare it behind the CallScope and in front of the call's Scratch: on a
+// failure the blocks are back in the cache first, the set goes next and the context last.
+template <typename S>
+int make_set(const CallScope &cs, std::unique_ptr<S> &set)
+{
+    set.reset(new (std::nothrow) S());
+    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
+    set->tab = cs.t;
+    return KG_OK;
+}
+
+// The call succeeded: the caller gets the set.  An owned context goes with it; the scratch, back in the cache by now, goes to
+// the driver and the set's blocks stay.
+template <typename S>
+int hand_out(CallScope &cs, std::unique_ptr<S> &set, S **out)
+{
+    if (cs.owned) {
+        cs.t->cache.release_free();
+        set->own_tab = true;
+        cs.disown();
+    }
+    *out = set.release();
+    return KG_OK;
+}
+
+// the device a getter of such a set selects (a null set: the getter fails before it is used)
+int device_of(const SetBase *s) { return s ? s->tab->device : 0; }
+
+// The range getter of every set: records [first, first + count) of the `have` present, `per` elements of T each, from src
+// (device or host memory) to dst (host or device memory).  s: the set, looked at only for null; what: the getter's name.
+template <typename T>
+int copy_records(const void *s, int device, const T *src, size_t per, int64_t have, int64_t first, int64_t count, T *dst, const char *what,
+                 const char *of = "the set")
+{
+    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
+    if (first < 0 || count < 0 || first + count > have) return fail(KG_ERR_ARG, std::string(what) + ": range outside " + of);
+    if (count == 0) return KG_OK;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMemcpy(dst, src + (size_t)first * per, (size_t)count * per * sizeof(T), hipMemcpyDefault));
+    return KG_OK;
+}
+
+// The getter of a start array: all n + 1 entries
+int copy_starts(const void *s, int device, const int64_t *src, int64_t n, int64_t *dst)
+{
+    if (!s || !dst) return fail(KG_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMemcpy(dst, src, ((size_t)n + 1) * 8, hipMemcpyDefault));
+    return KG_OK;
+}
+
+// The getter of a set's statistics
+template <typename St>
+int copy_stats(const void *s, const St *st, St *out)
+{
+    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
+    *out = *st;
+    return KG_OK;
+}
 
 uint32_t grid_of(uint64_t n, uint32_t threads = 256)
 {

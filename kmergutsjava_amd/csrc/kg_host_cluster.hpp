@@ -286,20 +286,10 @@ int64_t kg_familyset_count(const kg_familyset *s) { return s ? s->count : 0; }
 
 int kg_familyset_copy(const kg_familyset *s, int64_t first, int64_t count, kg_family *dst)
 {
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_familyset_copy: range outside the set");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipMemcpy(dst, s->d_fam + first * 16, (size_t)count * 16, hipMemcpyDefault));
-    return KG_OK;
+    return copy_records(s, s ? s->device : 0, s ? (const kg_family *)s->d_fam : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_familyset_copy");
 }
 
-int kg_familyset_stats(const kg_familyset *s, kg_cluster_stats *out)
-{
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    *out = s->st;
-    return KG_OK;
-}
+int kg_familyset_stats(const kg_familyset *s, kg_cluster_stats *out) { return copy_stats(s, s ? &s->st : nullptr, out); }
 
 void kg_familyset_free(kg_familyset *s)
 {

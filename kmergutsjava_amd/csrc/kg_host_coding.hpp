@@ -3,8 +3,7 @@
 // Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_orfs.hpp (it reads and makes kg_orfset).
 #pragma once
 
-constexpr int kPinCoding = 80;          // kg_table::h_pin: the stage area (kPinRegions), the error and counter words
-static_assert(kPinCoding + kg::kCodingErrWords + kg::kCodingCntWords <= kPinWords, "stage words must fit their pinned words");
+static_assert(kg::kCodingErrWords + kg::kCodingCntWords <= kPinStageWords, "stage words must fit their pinned words");
 static_assert(sizeof(kg_coding_params) == 16 && sizeof(kg_coding_model) == 2 * 8 * kg::kCodingBins && sizeof(kg_coding_stats) == 56,
               "record layouts of include/kmerguts_hip.h");
 static_assert(kg::kCodingNoErr == kNoErr, "the stages' kernels share the error words' \"none\"");
@@ -136,15 +135,15 @@ struct CodingWork {
             ": seq outside [0, n_seqs)", ": strand is neither 0 nor 1", ": outside its contig (0 <= left <= right <= L - 1 does not hold)",
             ": 3 * n_res exceeds right - left + 1"};
         int rc;
-        if ((rc = read_error_words(t, words, kg::kCodingErrWords + kg::kCodingCntWords, kPinCoding, {}))) return rc;
+        if ((rc = read_error_words(t, words, kg::kCodingErrWords + kg::kCodingCntWords, kPinStage, {}))) return rc;
         // every word holds the first record with its error: the message names the first record with any
-        const uint64_t *h = t->h_pin + kPinCoding;
+        const uint64_t *h = t->h_pin + kPinStage;
         const int first = (int)(std::min_element(h, h + kg::kCodingErrWords) - h);
         if (h[first] != kNoErr) return fail(KG_ERR_ARG, "record " + kmer_text((int64_t)h[first]) + what[first]);
         if (counter(kg::kCodingCntPairs) >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more codon pairs in one call");
         return KG_OK;
     }
-    uint64_t counter(int k) const { return t->h_pin[kPinCoding + kg::kCodingErrWords + k]; }
+    uint64_t counter(int k) const { return t->h_pin[kPinStage + kg::kCodingErrWords + k]; }
 };
 
 int64_t coding_sum(const int64_t *c)
@@ -206,11 +205,10 @@ int kg_orfset_coding(kg_orfset *os, const kg_coding_params *p, const int32_t *ta
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;
     hipStream_t s = t->stream;
-    std::unique_ptr<kg_orfset> set(new (std::nothrow) kg_orfset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
+    std::unique_ptr<kg_orfset> set;
+    if ((rc = make_set(cs, set))) return rc;
     set->coding_model.reset(new (std::nothrow) kg_coding_model());
     if (!set->coding_model) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = t;
     if ((rc = ev.create())) return rc;
     CodingWork w(t);
     const uint8_t *d_seq = nullptr;
@@ -264,30 +262,24 @@ int kg_orfset_coding(kg_orfset *os, const kg_coding_params *p, const int32_t *ta
     st.ms_count = ev.ms(0, 1);
     st.ms_score = ev.ms(2, 3);
     // the four arrays of the set leave the scratch: everything else goes back to the cache
-    w.sc.release(d_out); w.sc.release(d_start); w.sc.release(d_res); w.sc.release(d_S);
-    set->d_orfs = d_out;
-    set->d_prot_start = d_start;
-    set->d_res = d_res;
-    set->d_coding = d_S;
+    set->d_orfs = set->keep(w.sc, d_out);
+    set->d_prot_start = set->keep(w.sc, d_start);
+    set->d_res = set->keep(w.sc, d_res);
+    set->d_coding = set->keep(w.sc, d_S);
     set->count = os->count;
     set->residues = os->residues;
     set->n_seqs = os->n_seqs;
     set->l_max = os->l_max;
     set->st = os->st;
     set->coding_st = st;
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int kg_orfset_coding_scores(const kg_orfset *s, int64_t first, int64_t count, int64_t *dst)
 {
     if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
     if (!s->d_coding) return fail(KG_ERR_ARG, "kg_orfset_coding_scores: the set has no scores (it is not from kg_orfset_coding)");
-    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_orfset_coding_scores: range outside the set");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_coding + first, (size_t)count * 8, hipMemcpyDefault));
-    return KG_OK;
+    return copy_records(s, device_of(s), s->d_coding, 1, s->count, first, count, dst, "kg_orfset_coding_scores");
 }
 
 int kg_orfset_coding_stats(const kg_orfset *s, kg_coding_stats *out)

@@ -3,8 +3,7 @@
 // Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_coding.hpp (it uses its Lg) and kg_host_votes.hpp.
 #pragma once
 
-struct kg_compset {
-    kg_table *tab = nullptr;            // the set's own table-less context: its block cache holds the three arrays
+struct kg_compset : SetBase {
     kg_comp_class *d_classes = nullptr; // n_seqs
     uint32_t *d_counts = nullptr;       // N: n_seqs * 256
     int64_t *d_scores = nullptr;        // S: n_seqs * (n_models + 1), only when kept
@@ -20,8 +19,7 @@ static_assert(sizeof(kg_comp_params) == 24 && sizeof(kg_comp_class) == 40 && siz
 
 namespace {
 
-constexpr int kPinCompose = kPinRegions;    // the stage area of kg_table::h_pin: the counter words
-static_assert(kPinCompose + kg::kCompCntWords <= kPinWords, "stage words must fit their pinned words");
+static_assert(kg::kCompCntWords <= kPinStageWords, "stage words must fit their pinned words");
 constexpr int64_t kCompMaxRows = 1ll << 20;
 
 int check_comp_params(const kg_comp_params *p)
@@ -66,17 +64,6 @@ void comp_weights_of(const int64_t *c, int32_t *w)
     for (int t = 0; t < kg::kCompBins; t++) sum += (uint64_t)c[t];
     const int32_t lg_s = coding_lg(sum + kg::kCompBins);
     for (int t = 0; t < kg::kCompBins; t++) w[t] = coding_lg((uint64_t)c[t] + 1) - lg_s;
-}
-
-template <typename T>
-int compset_copy(const kg_compset *s, const T *src, size_t per, int64_t have, int64_t first, int64_t count, T *dst, const char *what)
-{
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (first < 0 || count < 0 || first + count > have) return fail(KG_ERR_ARG, std::string(what) + ": range outside the set");
-    if (count == 0 || per == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, src + (size_t)first * per, (size_t)count * per * sizeof(T), hipMemcpyDefault));
-    return KG_OK;
 }
 
 }  // namespace
@@ -144,8 +131,8 @@ int kg_contigs_compose(int device, const kg_comp_params *p, const uint8_t *seq, 
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;
     hipStream_t s = t->stream;
-    std::unique_ptr<kg_compset> set(new (std::nothrow) kg_compset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
+    std::unique_ptr<kg_compset> set;
+    if ((rc = make_set(cs, set))) return rc;
     if ((rc = ev.create())) return rc;
     {
         Scratch sc(t);
@@ -227,8 +214,8 @@ int kg_contigs_compose(int device, const kg_comp_params *p, const uint8_t *seq, 
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(ev[3], s));
-        if ((rc = read_error_words(t, cnt, kg::kCompCntWords, kPinCompose, {}))) return rc;
-        const uint64_t *h = t->h_pin + kPinCompose;
+        if ((rc = read_error_words(t, cnt, kg::kCompCntWords, kPinStage, {}))) return rc;
+        const uint64_t *h = t->h_pin + kPinStage;
         kg_comp_stats &st = set->st;
         st.seqs = n_seqs;
         st.labelled = n_labelled;
@@ -241,11 +228,9 @@ int kg_contigs_compose(int device, const kg_comp_params *p, const uint8_t *seq, 
         st.ms_count = ev.ms(0, 1);
         st.ms_score = ev.ms(2, 3);
         // the set's arrays leave the scratch: everything else goes back to the cache
-        sc.release(d_cls); sc.release(d_N);
-        if (d_S) sc.release(d_S);
-        set->d_classes = d_cls;
-        set->d_counts = d_N;
-        set->d_scores = d_S;
+        set->d_classes = set->keep(sc, d_cls);
+        set->d_counts = set->keep(sc, d_N);
+        set->d_scores = set->keep(sc, d_S);
     }
     set->n_seqs = n_seqs;
     set->row_labels = std::move(rows);
@@ -255,10 +240,7 @@ int kg_contigs_compose(int device, const kg_comp_params *p, const uint8_t *seq, 
         set->row_counts = std::move(counts);
     }
     set->model_labels = std::move(mlab);
-    t->cache.release_free();            // (the scratch is back in the cache: it goes to the driver, the set's arrays stay)
-    set->tab = cs.disown();
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int64_t kg_compset_rows(const kg_compset *s) { return s ? (int64_t)s->row_labels.size() : 0; }
@@ -267,12 +249,12 @@ int64_t kg_compset_models(const kg_compset *s) { return s ? (int64_t)s->model_la
 
 int kg_compset_copy_classes(const kg_compset *s, int64_t first, int64_t count, kg_comp_class *dst)
 {
-    return compset_copy(s, s ? s->d_classes : nullptr, 1, s ? s->n_seqs : 0, first, count, dst, "kg_compset_copy_classes");
+    return copy_records(s, device_of(s), s ? s->d_classes : nullptr, 1, s ? s->n_seqs : 0, first, count, dst, "kg_compset_copy_classes");
 }
 
 int kg_compset_copy_counts(const kg_compset *s, int64_t first, int64_t count, int32_t *dst)
 {
-    return compset_copy(s, s ? (const int32_t *)s->d_counts : nullptr, kg::kCompBins, s ? s->n_seqs : 0, first, count, dst, "kg_compset_copy_counts");
+    return copy_records(s, device_of(s), s ? (const int32_t *)s->d_counts : nullptr, kg::kCompBins, s ? s->n_seqs : 0, first, count, dst, "kg_compset_copy_counts");
 }
 
 int kg_compset_copy_rows(const kg_compset *s, int64_t first, int64_t count, int32_t *labels_dst, int64_t *counts_dst)
@@ -298,35 +280,19 @@ int kg_compset_background(const kg_compset *s, int64_t *dst)
 
 int kg_compset_model_labels(const kg_compset *s, int64_t first, int64_t count, int32_t *dst)
 {
-    return compset_copy(s, s ? s->model_labels.data() : nullptr, 1, s ? (int64_t)s->model_labels.size() : 0, first, count, dst,
+    return copy_records(s, device_of(s), s ? s->model_labels.data() : nullptr, 1, s ? (int64_t)s->model_labels.size() : 0, first, count, dst,
                         "kg_compset_model_labels");
 }
 
 int kg_compset_copy_scores(const kg_compset *s, int64_t first, int64_t count, int64_t *dst)
 {
     if (s && !s->d_scores) return fail(KG_ERR_ARG, "kg_compset_copy_scores: the call did not keep the score matrix (keep_scores was 0)");
-    return compset_copy(s, s ? s->d_scores : nullptr, s ? s->model_labels.size() + 1 : 0, s ? s->n_seqs : 0, first, count, dst,
+    return copy_records(s, device_of(s), s ? s->d_scores : nullptr, s ? s->model_labels.size() + 1 : 0, s ? s->n_seqs : 0, first, count, dst,
                         "kg_compset_copy_scores");
 }
 
-int kg_compset_stats(const kg_compset *s, kg_comp_stats *out)
-{
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    *out = s->st;
-    return KG_OK;
-}
+int kg_compset_stats(const kg_compset *s, kg_comp_stats *out) { return copy_stats(s, s ? &s->st : nullptr, out); }
 
-void kg_compset_free(kg_compset *s)
-{
-    if (!s) return;
-    if (s->tab) {
-        (void)hipSetDevice(s->tab->device);
-        dfree(s->tab, s->d_classes);
-        dfree(s->tab, s->d_counts);
-        dfree(s->tab, s->d_scores);
-        kg_table_close(s->tab);
-    }
-    delete s;
-}
+void kg_compset_free(kg_compset *s) { delete s; }
 
 }  // extern "C"

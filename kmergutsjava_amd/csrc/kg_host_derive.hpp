@@ -13,6 +13,8 @@ struct kg_sigset {
     kg_merge_stats mst = {};
 };
 
+static_assert(sizeof(kg_signature) == 24, "record layouts of include/kmerguts_hip.h");
+
 namespace {
 
 constexpr uint64_t kDeriveBytesPerWindow = 160;                       // device bytes one valid window of a pass needs, at most
@@ -383,20 +385,10 @@ const kg_signature *kg_sigset_device(const kg_sigset *s) { return s ? (const kg_
 
 int kg_sigset_copy(const kg_sigset *s, int64_t first, int64_t count, kg_signature *dst)
 {
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_sigset_copy: range outside the set");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipMemcpy(dst, s->d_sigs + first * 24, (size_t)count * 24, hipMemcpyDefault));
-    return KG_OK;
+    return copy_records(s, s ? s->device : 0, s ? (const kg_signature *)s->d_sigs : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_sigset_copy");
 }
 
-int kg_sigset_stats(const kg_sigset *s, kg_derive_stats *out)
-{
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    *out = s->st;
-    return KG_OK;
-}
+int kg_sigset_stats(const kg_sigset *s, kg_derive_stats *out) { return copy_stats(s, s ? &s->st : nullptr, out); }
 
 void kg_sigset_free(kg_sigset *s)
 {

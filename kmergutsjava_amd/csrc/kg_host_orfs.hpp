@@ -3,9 +3,7 @@
 // Part of kmerguts_hip.hip's translation unit: the last of the batch stages, behind kg_host_regions.hpp (it reads kg_regionset).
 #pragma once
 
-struct kg_orfset {
-    kg_table *tab = nullptr;            // the context whose block cache the three arrays came from
-    bool own_tab = false;               // kg_orfs_regions: the set owns a table-less context
+struct kg_orfset : SetBase {
     kg_orf *d_orfs = nullptr;           // count records, index-aligned with the regions
     int64_t *d_prot_start = nullptr;    // count + 1
     uint8_t *d_res = nullptr;           // residues bytes
@@ -27,6 +25,9 @@ struct kg_orfset {
     bool repaired = false;
     kg_repair_stats repair_st = {};
 };
+
+static_assert(kg::kOrfErrWords + kg::kOrfCntWords + 1 <= kPinStageWords && kg::kOrfFreeWords <= kPinStageWords,
+              "stage words must fit their pinned words");
 
 namespace {
 
@@ -151,14 +152,14 @@ int orfs_impl(kg_table *t, const kg_orf_params *prm, const kg_region *d_regions,
     HIP_TRY(hipGetLastError());
     // the one wait of the call: the residue total (and, with it, the error and counter words)
     constexpr int kWords = kg::kOrfErrWords + kg::kOrfCntWords + 1;
-    if ((rc = read_error_words(t, words, kWords, kPinOrfs,                          // (in the order they are reported)
+    if ((rc = read_error_words(t, words, kWords, kPinStage,                          // (in the order they are reported)
                                {{kg::kOrfErrSeq, KG_ERR_ARG, "region ", ": seq outside [0, n_seqs)"},
                                 {kg::kOrfErrStrand, KG_ERR_ARG, "region ", ": strand is neither 0 nor 1"},
                                 {kg::kOrfErrFrame, KG_ERR_ARG, "region ", ": best_frame outside 0..2"},
                                 {kg::kOrfErrRange, KG_ERR_ARG, "region ", ": outside its contig (0 <= left <= right <= L - 1 does not hold)"},
                                 {kg::kOrfErrAnchor, KG_ERR_ARG, "region ", ": holds no whole codon of its best_frame"}})))
         return rc;
-    const uint64_t *h = t->h_pin + kPinOrfs;
+    const uint64_t *h = t->h_pin + kPinStage;
     const uint64_t n_res = h[kg::kOrfErrWords + kg::kOrfCntWords];
     if (n_res >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more residues in one call");
     uint8_t *d_res = nullptr;
@@ -178,10 +179,9 @@ int orfs_impl(kg_table *t, const kg_orf_params *prm, const kg_region *d_regions,
     set->st.tiles = (int64_t)n_tiles;
     HIP_TRY(hipEventElapsedTime(&set->st.ms, t->ev[kEvStageBegin], t->ev[kEvStageEnd]));
     // the three arrays of the set leave the scratch: everything else goes back to the cache
-    sc.release(d_out); sc.release(d_start); sc.release(d_res);
-    set->d_orfs = d_out;
-    set->d_prot_start = d_start;
-    set->d_res = d_res;
+    set->d_orfs = set->keep(sc, d_out);
+    set->d_prot_start = set->keep(sc, d_start);
+    set->d_res = set->keep(sc, d_res);
     set->count = (int64_t)n;
     set->residues = (int64_t)n_res;
     set->n_seqs = (int64_t)n_seqs;
@@ -240,8 +240,8 @@ int free_impl(kg_table *t, const kg_free_params *prm, const kg_orfset *parent, c
         if ((rc = prefix_sum(t, slots, n_slots, slot_first, slot_partial, (uint64_t *)(words + kg::kOrfFreeCount)))) return rc;
     }
     // the first wait: how many candidates there are
-    if ((rc = read_error_words(t, words, kg::kOrfFreeWords, kPinOrfs, {}))) return rc;
-    const uint64_t *h = t->h_pin + kPinOrfs;
+    if ((rc = read_error_words(t, words, kg::kOrfFreeWords, kPinStage, {}))) return rc;
+    const uint64_t *h = t->h_pin + kPinStage;
     const uint64_t n_free = h[kg::kOrfFreeCount], n = n0 + n_free;
     if (n >= (1ull << 31)) return fail(KG_ERR_LIMIT, "2^31 or more candidates in one call");
     kg_orf *d_out = nullptr;
@@ -264,7 +264,7 @@ int free_impl(kg_table *t, const kg_free_params *prm, const kg_orfset *parent, c
     hipLaunchKernelGGL(kg::orf_prot_start_kernel, dim3(grid_of(n + 1)), dim3(256), 0, s, excl, d_total, n, d_start);
     HIP_TRY(hipGetLastError());
     // the second wait: the residue total and the counters
-    if ((rc = read_error_words(t, words, kg::kOrfFreeWords, kPinOrfs, {}))) return rc;
+    if ((rc = read_error_words(t, words, kg::kOrfFreeWords, kPinStage, {}))) return rc;
     const uint64_t n_res = h[kg::kOrfFreeResidues];
     if (n_res >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more residues in one call");
     uint8_t *d_res = nullptr;
@@ -284,10 +284,9 @@ int free_impl(kg_table *t, const kg_free_params *prm, const kg_orfset *parent, c
     set->st.tiles = (int64_t)pl.n_tiles;
     HIP_TRY(hipEventElapsedTime(&set->st.ms, t->ev[kEvStageBegin], t->ev[kEvStageEnd]));
     // the three arrays of the set leave the scratch: everything else goes back to the cache
-    sc.release(d_out); sc.release(d_start); sc.release(d_res);
-    set->d_orfs = d_out;
-    set->d_prot_start = d_start;
-    set->d_res = d_res;
+    set->d_orfs = set->keep(sc, d_out);
+    set->d_prot_start = set->keep(sc, d_start);
+    set->d_res = set->keep(sc, d_res);
     set->count = (int64_t)n;
     set->residues = (int64_t)n_res;
     set->n_seqs = (int64_t)n_seqs;
@@ -329,9 +328,8 @@ int kg_regionset_orfs(kg_regionset *rs, const kg_orf_params *p, const uint8_t *s
     CallScope cs(rs->tab, "a kg_scan* is in flight on this region set's kg_table");
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;
-    std::unique_ptr<kg_orfset> set(new (std::nothrow) kg_orfset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = t;
+    std::unique_ptr<kg_orfset> set;
+    if ((rc = make_set(cs, set))) return rc;
     Scratch sc(t);
     const uint8_t *d_seq = seq;
     if (!seq_on_device && total) {
@@ -343,8 +341,7 @@ int kg_regionset_orfs(kg_regionset *rs, const kg_orf_params *p, const uint8_t *s
         HIP_TRY(hipDeviceSynchronize());            // the bytes may have been produced on another stream
     }
     if ((rc = orfs_impl(t, p, rs->d_regions, (uint64_t)rs->count, d_seq, offsets, (uint64_t)n_seqs, set.get()))) return rc;
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int kg_orfs_regions(int device, const kg_orf_params *p, const kg_region *regions, int64_t n_regions, const uint8_t *seq,
@@ -363,9 +360,8 @@ int kg_orfs_regions(int device, const kg_orf_params *p, const kg_region *regions
     CallScope cs(device);               // the call's context: closed on every failure below, kept by the set on success
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;
-    std::unique_ptr<kg_orfset> set(new (std::nothrow) kg_orfset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = t;
+    std::unique_ptr<kg_orfset> set;
+    if ((rc = make_set(cs, set))) return rc;
     {
         Scratch sc(t);
         kg_region *d_regions = nullptr;
@@ -375,11 +371,7 @@ int kg_orfs_regions(int device, const kg_orf_params *p, const kg_region *regions
         if (total && (rc = upload_batch(t, seq, total, d_seq))) return rc;
         if ((rc = orfs_impl(t, p, d_regions, (uint64_t)n_regions, d_seq, offsets, (uint64_t)n_seqs, set.get()))) return rc;
     }
-    t->cache.release_free();            // (the scratch is back in the cache: it goes to the driver, the set's three arrays stay)
-    set->own_tab = true;
-    cs.disown();
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int kg_orfs_free(int device, const kg_free_params *p, const uint8_t *seq, int seq_on_device, const int64_t *offsets, int64_t n_seqs,
@@ -394,20 +386,15 @@ int kg_orfs_free(int device, const kg_free_params *p, const uint8_t *seq, int se
     CallScope cs(device);               // the call's context: closed on every failure below, kept by the set on success
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;
-    std::unique_ptr<kg_orfset> set(new (std::nothrow) kg_orfset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = t;
+    std::unique_ptr<kg_orfset> set;
+    if ((rc = make_set(cs, set))) return rc;
     {
         Scratch sc(t);
         const uint8_t *d_seq = nullptr;
         if ((rc = batch_on_device(t, sc, seq, seq_on_device, total, &d_seq))) return rc;
         if ((rc = free_impl(t, p, nullptr, d_seq, offsets, (uint64_t)n_seqs, set.get()))) return rc;
     }
-    t->cache.release_free();            // (the scratch is back in the cache: it goes to the driver, the set's three arrays stay)
-    set->own_tab = true;
-    cs.disown();
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int kg_orfset_add_free(kg_orfset *os, const kg_free_params *p, const uint8_t *seq, int seq_on_device, const int64_t *offsets,
@@ -424,15 +411,13 @@ int kg_orfset_add_free(kg_orfset *os, const kg_free_params *p, const uint8_t *se
     CallScope cs(os->tab, "a kg_scan* is in flight on this ORF set's kg_table");
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;
-    std::unique_ptr<kg_orfset> set(new (std::nothrow) kg_orfset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = t;
+    std::unique_ptr<kg_orfset> set;
+    if ((rc = make_set(cs, set))) return rc;
     Scratch sc(t);
     const uint8_t *d_seq = nullptr;
     if ((rc = batch_on_device(t, sc, seq, seq_on_device, total, &d_seq))) return rc;
     if ((rc = free_impl(t, p, os, d_seq, offsets, (uint64_t)n_seqs, set.get()))) return rc;
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int64_t kg_orfset_count(const kg_orfset *s) { return s ? s->count : 0; }
@@ -441,54 +426,21 @@ const kg_orf *kg_orfset_device(const kg_orfset *s) { return s ? s->d_orfs : null
 
 int kg_orfset_copy(const kg_orfset *s, int64_t first, int64_t count, kg_orf *dst)
 {
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_orfset_copy: range outside the set");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_orfs + first, (size_t)count * sizeof(kg_orf), hipMemcpyDefault));
-    return KG_OK;
+    return copy_records(s, device_of(s), s ? s->d_orfs : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_orfset_copy");
 }
 
 int kg_orfset_prot_start(const kg_orfset *s, int64_t *dst)
 {
-    if (!s || !dst) return fail(KG_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_prot_start, ((size_t)s->count + 1) * 8, hipMemcpyDefault));
-    return KG_OK;
+    return copy_starts(s, device_of(s), s ? s->d_prot_start : nullptr, s ? s->count : 0, dst);
 }
 
 int kg_orfset_residues(const kg_orfset *s, int64_t first, int64_t count, uint8_t *dst)
 {
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (first < 0 || count < 0 || first + count > s->residues) return fail(KG_ERR_ARG, "kg_orfset_residues: range outside the proteins");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_res + first, (size_t)count, hipMemcpyDefault));
-    return KG_OK;
+    return copy_records(s, device_of(s), s ? s->d_res : nullptr, 1, s ? s->residues : 0, first, count, dst, "kg_orfset_residues", "the proteins");
 }
 
-int kg_orfset_stats(const kg_orfset *s, kg_orf_stats *out)
-{
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    *out = s->st;
-    return KG_OK;
-}
+int kg_orfset_stats(const kg_orfset *s, kg_orf_stats *out) { return copy_stats(s, s ? &s->st : nullptr, out); }
 
-void kg_orfset_free(kg_orfset *s)
-{
-    if (!s) return;
-    if (s->tab) {
-        (void)hipSetDevice(s->tab->device);
-        dfree(s->tab, s->d_orfs);
-        dfree(s->tab, s->d_prot_start);
-        dfree(s->tab, s->d_res);
-        dfree(s->tab, s->d_coding);
-        dfree(s->tab, s->d_shift);
-        dfree(s->tab, s->d_junctions);
-        dfree(s->tab, s->d_junction_start);
-        if (s->own_tab) kg_table_close(s->tab);
-    }
-    delete s;
-}
+void kg_orfset_free(kg_orfset *s) { delete s; }
 
 }  // extern "C"

@@ -4,14 +4,14 @@
 // hosts of the table, the result and the scan.
 #pragma once
 
-struct kg_regionset {
-    kg_table *tab = nullptr;            // the context whose block cache the two arrays came from
-    bool own_tab = false;               // kg_regions_calls: the set owns a table-less context
+struct kg_regionset : SetBase {
     kg_region *d_regions = nullptr;     // count records, output order
     int64_t *d_seq_start = nullptr;     // n_seqs + 1
     int64_t count = 0, n_seqs = 0;
     kg_region_stats st = {};
 };
+
+static_assert(kg::kRegionErrWords + 2 <= kPinStageWords, "stage words must fit their pinned words");
 
 namespace {
 
@@ -57,7 +57,7 @@ int regions_impl(kg_table *t, const kg_region_params *prm, const kg_call *d_call
     HIP_TRY(hipMemsetAsync(err, 0x7F, kg::kRegionErrWords * 8, s));
     HIP_TRY(hipMemsetAsync(cnt, 0, 4 * 8, s));
     HIP_TRY(hipEventRecord(t->ev[kEvStageBegin], s));
-    uint64_t *h = t->h_pin + kPinRegions;
+    uint64_t *h = t->h_pin + kPinStage;
     uint64_t n_groups = 0, n_regions = 0;
     kg_region *d_out = nullptr;
     const uint32_t left_bits = bits_for((uint64_t)std::max<int64_t>(l_max, 1));
@@ -128,7 +128,7 @@ int regions_impl(kg_table *t, const kg_region_params *prm, const kg_call *d_call
                        d_start);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(t->ev[kEvStageEnd], s));
-    if ((rc = read_error_words(t, words, kg::kRegionErrWords + 2, kPinRegions,       // (in the order they are reported)
+    if ((rc = read_error_words(t, words, kg::kRegionErrWords + 2, kPinStage,       // (in the order they are reported)
                                {{kg::kRegionErrContainer, KG_ERR_ARG, "CALL ", ": container >= 6 * n_seqs"},
                                 {kg::kRegionErrOrder, KG_ERR_ARG, "CALL ", ": container below its predecessor's (calls[] must be in container order)"},
                                 {kg::kRegionErrCount, KG_ERR_ARG, "CALL ", ": negative count"},
@@ -142,9 +142,8 @@ int regions_impl(kg_table *t, const kg_region_params *prm, const kg_call *d_call
     set->st.multi_frame = (int64_t)h[kg::kRegionErrWords + kg::kRegionCntMulti];
     HIP_TRY(hipEventElapsedTime(&set->st.ms, t->ev[kEvStageBegin], t->ev[kEvStageEnd]));
     // the two arrays of the set leave the scratch: everything else goes back to the cache
-    sc.release(d_out); sc.release(d_start);
-    set->d_regions = d_out;
-    set->d_seq_start = d_start;
+    set->d_regions = set->keep(sc, d_out);
+    set->d_seq_start = set->keep(sc, d_start);
     set->count = (int64_t)n_regions;
     set->n_seqs = (int64_t)n_seqs;
     return KG_OK;
@@ -168,12 +167,10 @@ int kg_result_regions(kg_result *r, const kg_region_params *p, const int64_t *of
     if ((uint64_t)r->st.n_calls >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more CALL records in one call");
     CallScope cs(r->tab, "a kg_scan* is in flight on this result's kg_table");
     if (cs.rc) return cs.rc;
-    std::unique_ptr<kg_regionset> set(new (std::nothrow) kg_regionset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = cs.t;
+    std::unique_ptr<kg_regionset> set;
+    if ((rc = make_set(cs, set))) return rc;
     if ((rc = regions_impl(cs.t, p, r->d_calls, (uint64_t)r->st.n_calls, offsets, (uint64_t)r->st.n_seqs, l_max, set.get()))) return rc;
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int kg_regions_calls(int device, const kg_region_params *p, const kg_call *calls, int64_t n_calls, const int64_t *offsets,
@@ -192,9 +189,8 @@ int kg_regions_calls(int device, const kg_region_params *p, const kg_call *calls
     CallScope cs(device);               // the call's context: closed on every failure below, kept by the set on success
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;
-    std::unique_ptr<kg_regionset> set(new (std::nothrow) kg_regionset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = t;
+    std::unique_ptr<kg_regionset> set;
+    if ((rc = make_set(cs, set))) return rc;
     {
         Scratch sc(t);
         kg_call *d_calls = nullptr;
@@ -202,11 +198,7 @@ int kg_regions_calls(int device, const kg_region_params *p, const kg_call *calls
         if (n_calls) HIP_TRY(hipMemcpyAsync(d_calls, calls, (size_t)n_calls * sizeof(kg_call), hipMemcpyHostToDevice, t->stream));
         if ((rc = regions_impl(t, p, d_calls, (uint64_t)n_calls, offsets, (uint64_t)n_seqs, l_max, set.get()))) return rc;
     }
-    t->cache.release_free();            // (the scratch is back in the cache: it goes to the driver, the set's two arrays stay)
-    set->own_tab = true;
-    cs.disown();
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int64_t kg_regionset_count(const kg_regionset *s) { return s ? s->count : 0; }
@@ -215,39 +207,16 @@ const kg_region *kg_regionset_device(const kg_regionset *s) { return s ? s->d_re
 
 int kg_regionset_copy(const kg_regionset *s, int64_t first, int64_t count, kg_region *dst)
 {
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_regionset_copy: range outside the set");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_regions + first, (size_t)count * sizeof(kg_region), hipMemcpyDefault));
-    return KG_OK;
+    return copy_records(s, device_of(s), s ? s->d_regions : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_regionset_copy");
 }
 
 int kg_regionset_seq_start(const kg_regionset *s, int64_t *dst)
 {
-    if (!s || !dst) return fail(KG_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_seq_start, ((size_t)s->n_seqs + 1) * 8, hipMemcpyDefault));
-    return KG_OK;
+    return copy_starts(s, device_of(s), s ? s->d_seq_start : nullptr, s ? s->n_seqs : 0, dst);
 }
 
-int kg_regionset_stats(const kg_regionset *s, kg_region_stats *out)
-{
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    *out = s->st;
-    return KG_OK;
-}
+int kg_regionset_stats(const kg_regionset *s, kg_region_stats *out) { return copy_stats(s, s ? &s->st : nullptr, out); }
 
-void kg_regionset_free(kg_regionset *s)
-{
-    if (!s) return;
-    if (s->tab) {
-        (void)hipSetDevice(s->tab->device);
-        dfree(s->tab, s->d_regions);
-        dfree(s->tab, s->d_seq_start);
-        if (s->own_tab) kg_table_close(s->tab);
-    }
-    delete s;
-}
+void kg_regionset_free(kg_regionset *s) { delete s; }
 
 }  // extern "C"

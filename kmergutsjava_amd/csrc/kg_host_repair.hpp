@@ -8,8 +8,8 @@ namespace {
 // device words of a call: the error words, the counters, the two totals the second wait reads, then the totals of the first wait
 enum : int { kRepairWResidues = kg::kRepairErrWords + kg::kRepairCntWords, kRepairWJunctions, kRepairWKept, kRepairWSegments, kRepairWCountSum,
              kRepairWRuns, kRepairWords };
-static_assert(kPinOrfs + kg::kRepairErrWords + 1 <= kPinWords && kPinOrfs + kg::kRepairCntWords + 2 <= kPinWords,
-              "the repair stage's words must fit their pinned words");
+static_assert(kg::kRepairErrWords + 1 <= kPinStageWords && kg::kRepairCntWords + 2 <= kPinStageWords,
+              "stage words must fit their pinned words");
 
 int check_repair_params(const kg_repair_params *p)
 {
@@ -117,9 +117,9 @@ int repair_impl(kg_table *t, const kg_repair_params *prm, const kg_regionset *rs
         HIP_TRY(hipGetLastError());
     }
     // the first wait: the CALL list is the set's, and how many CALLs take part in a chain
-    uint64_t *h = t->h_pin + kPinOrfs;
+    uint64_t *h = t->h_pin + kPinStage;
     HIP_TRY(hipMemcpyAsync(h + kg::kRepairErrWords, words + kRepairWKept, 8, hipMemcpyDeviceToHost, s));
-    if ((rc = read_error_words(t, words, kg::kRepairErrWords, kPinOrfs,                 // (in the order they are reported)
+    if ((rc = read_error_words(t, words, kg::kRepairErrWords, kPinStage,                 // (in the order they are reported)
                                {{kg::kRegionErrContainer, KG_ERR_ARG, "CALL ", ": container >= 6 * n_seqs"},
                                 {kg::kRegionErrOrder, KG_ERR_ARG, "CALL ", ": container below its predecessor's (calls[] must be in container order)"},
                                 {kg::kRegionErrCount, KG_ERR_ARG, "CALL ", ": negative count"},
@@ -163,7 +163,7 @@ int repair_impl(kg_table *t, const kg_repair_params *prm, const kg_regionset *rs
     hipLaunchKernelGGL(kg::orf_prot_start_kernel, dim3(grid_of(nr + 1)), dim3(256), 0, s, jexcl, (const uint64_t *)(words + kRepairWJunctions), nr, d_jstart);
     HIP_TRY(hipGetLastError());
     // the second wait: the residue and junction totals and the counters
-    if ((rc = read_error_words(t, cnt, kg::kRepairCntWords + 2, kPinOrfs, {}))) return rc;
+    if ((rc = read_error_words(t, cnt, kg::kRepairCntWords + 2, kPinStage, {}))) return rc;
     const uint64_t n_res = h[kg::kRepairCntWords], n_junc = h[kg::kRepairCntWords + 1];
     if (n_res >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more residues in one call");
     uint8_t *d_res = nullptr;
@@ -196,12 +196,11 @@ int repair_impl(kg_table *t, const kg_repair_params *prm, const kg_regionset *rs
     st.residues = (int64_t)h[kg::kRepairCntResidues];
     HIP_TRY(hipEventElapsedTime(&st.ms, t->ev[kEvStageBegin], t->ev[kEvStageEnd]));
     // the five arrays of the set leave the scratch: everything else goes back to the cache
-    sc.release(d_out); sc.release(d_start); sc.release(d_res); sc.release(d_junc); sc.release(d_jstart);
-    set->d_orfs = d_out;
-    set->d_prot_start = d_start;
-    set->d_res = d_res;
-    set->d_junctions = d_junc;
-    set->d_junction_start = d_jstart;
+    set->d_orfs = set->keep(sc, d_out);
+    set->d_prot_start = set->keep(sc, d_start);
+    set->d_res = set->keep(sc, d_res);
+    set->d_junctions = set->keep(sc, d_junc);
+    set->d_junction_start = set->keep(sc, d_jstart);
     set->junctions = (int64_t)n_junc;
     set->repaired = true;
     set->count = (int64_t)nr;
@@ -239,9 +238,8 @@ int kg_regionset_repair(kg_regionset *rs, kg_orfset *os, const kg_call *calls, i
     CallScope cs(rs->tab, "a kg_scan* is in flight on this region set's kg_table");
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;
-    std::unique_ptr<kg_orfset> set(new (std::nothrow) kg_orfset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = t;
+    std::unique_ptr<kg_orfset> set;
+    if ((rc = make_set(cs, set))) return rc;
     Scratch sc(t);
     const uint8_t *d_seq = nullptr;
     if ((rc = batch_on_device(t, sc, seq, seq_on_device, total, &d_seq))) return rc;
@@ -255,8 +253,7 @@ int kg_regionset_repair(kg_regionset *rs, kg_orfset *os, const kg_call *calls, i
         HIP_TRY(hipDeviceSynchronize());            // the CALLs may have been produced on another stream
     }
     if ((rc = repair_impl(t, p, rs, os, d_calls, (uint64_t)n_calls, d_seq, offsets, (uint64_t)n_seqs, set.get()))) return rc;
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int kg_result_repair(kg_result *r, kg_regionset *rs, kg_orfset *os, const kg_repair_params *p, const uint8_t *seq, int seq_on_device,
@@ -278,20 +275,14 @@ int kg_orfset_junctions_copy(const kg_orfset *s, int64_t first, int64_t count, k
 {
     if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
     if (!s->repaired) return fail(KG_ERR_ARG, "kg_orfset_junctions_copy: the set is not from kg_regionset_repair");
-    if (first < 0 || count < 0 || first + count > s->junctions) return fail(KG_ERR_ARG, "kg_orfset_junctions_copy: range outside the list");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_junctions + first, (size_t)count * sizeof(kg_junction), hipMemcpyDefault));
-    return KG_OK;
+    return copy_records(s, device_of(s), s->d_junctions, 1, s->junctions, first, count, dst, "kg_orfset_junctions_copy", "the list");
 }
 
 int kg_orfset_junctions_start(const kg_orfset *s, int64_t *dst)
 {
     if (!s || !dst) return fail(KG_ERR_ARG, "null argument");
     if (!s->repaired) return fail(KG_ERR_ARG, "kg_orfset_junctions_start: the set is not from kg_regionset_repair");
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_junction_start, ((size_t)s->count + 1) * 8, hipMemcpyDefault));
-    return KG_OK;
+    return copy_starts(s, device_of(s), s->d_junction_start, s->count, dst);
 }
 
 int kg_orfset_junctions_stats(const kg_orfset *s, kg_repair_stats *out)

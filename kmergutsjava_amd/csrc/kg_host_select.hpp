@@ -4,16 +4,13 @@
 // kg_regionset and kg_orfset).
 #pragma once
 
-struct kg_selectset {
-    kg_table *tab = nullptr;            // the context whose block cache the array came from
-    bool own_tab = false;               // kg_select_intervals: the set owns a table-less context
+struct kg_selectset : SetBase {
     kg_selection *d_sel = nullptr;      // count records, index-aligned with the candidates
     int64_t count = 0;
     kg_select_stats st = {};
 };
 
-constexpr int kPinSelect = 80;          // kg_table::h_pin: the stage area (kPinRegions), kg::kSelectWords words
-static_assert(kPinSelect + kg::kSelectWords <= kPinWords, "stage words must fit their pinned words");
+static_assert(kg::kSelectWords <= kPinStageWords, "stage words must fit their pinned words");
 static_assert(sizeof(kg_selection) == 8 && sizeof(kg_interval) == 20, "record layouts of include/kmerguts_hip.h");
 
 namespace {
@@ -43,7 +40,7 @@ int select_impl(kg_table *t, const kg_select_params *prm, const T *d_in, uint64_
     HIP_TRY(hipMemsetAsync(words, 0x7F, 8, s));
     HIP_TRY(hipMemsetAsync(words + 1, 0, (kg::kSelectWords - 1) * 8, s));
     HIP_TRY(hipEventRecord(t->ev[kEvStageBegin], s));
-    const uint64_t *h = t->h_pin + kPinSelect;
+    const uint64_t *h = t->h_pin + kPinStage;
     uint64_t E = 0, P = 0;
     uint32_t rounds = 0;
     if (n > 0) {
@@ -72,7 +69,7 @@ int select_impl(kg_table *t, const kg_select_params *prm, const T *d_in, uint64_
         // when P < 2^31, where no partial sum can have wrapped)
         if ((rc = prefix_sum(t, count, n, pair_start, partial, (uint64_t *)(words + kg::kSelectScanTotal)))) return rc;
         // the one wait before the rounds: the error word, the eligible candidates and the overlapping pairs
-        if ((rc = read_error_words(t, words, kg::kSelectWords, kPinSelect,
+        if ((rc = read_error_words(t, words, kg::kSelectWords, kPinStage,
                                    {{kg::kSelectErr, KG_ERR_ARG, "candidate ", ": seq outside [0, n_seqs), left < 0 or right < left"}})))
             return rc;
         E = h[kg::kSelectEligible];
@@ -104,7 +101,7 @@ int select_impl(kg_table *t, const kg_select_params *prm, const T *d_in, uint64_
                 hipLaunchKernelGGL(kg::select_node_kernel, dim3(grid_of(E)), dim3(256), 0, s, state, blocked, E, r, und + k);
             }
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(t->h_pin + kPinSelect + kg::kSelectUndecided, und, kg::kSelectRoundsPerRead * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(t->h_pin + kPinStage + kg::kSelectUndecided, und, kg::kSelectRoundsPerRead * 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             int k = 0;
             while (k < kg::kSelectRoundsPerRead && h[kg::kSelectUndecided + k] != 0) k++;
@@ -116,7 +113,7 @@ int select_impl(kg_table *t, const kg_select_params *prm, const T *d_in, uint64_
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(t->ev[kEvStageEnd], s));
-    HIP_TRY(hipMemcpyAsync(t->h_pin + kPinSelect, words, kg::kSelectWords * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(t->h_pin + kPinStage, words, kg::kSelectWords * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     set->st.candidates = (int64_t)n;
     set->st.eligible = (int64_t)E;
@@ -126,8 +123,7 @@ int select_impl(kg_table *t, const kg_select_params *prm, const T *d_in, uint64_
     set->st.conflicts = (int64_t)h[kg::kSelectConflicts];
     set->st.rounds = (int32_t)rounds;
     HIP_TRY(hipEventElapsedTime(&set->st.ms, t->ev[kEvStageBegin], t->ev[kEvStageEnd]));
-    sc.release(d_out);                  // the set's array leaves the scratch: everything else goes back to the cache
-    set->d_sel = d_out;
+    set->d_sel = set->keep(sc, d_out);  // the set's array leaves the scratch: everything else goes back to the cache
     set->count = (int64_t)n;
     return KG_OK;
 }
@@ -142,12 +138,10 @@ int select_of_set(kg_table *tab, const kg_select_params *p, const T *d_in, int64
     if (count >= (1ll << 31)) return fail(KG_ERR_LIMIT, "2^31 or more candidates in one call");
     CallScope cs(tab, busy_text);
     if (cs.rc) return cs.rc;
-    std::unique_ptr<kg_selectset> set(new (std::nothrow) kg_selectset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = cs.t;
+    std::unique_ptr<kg_selectset> set;
+    if ((rc = make_set(cs, set))) return rc;
     if ((rc = select_impl(cs.t, p, d_in, (uint64_t)count, (uint64_t)n_seqs, left_bits, sorted, set.get()))) return rc;
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 }  // namespace
@@ -192,9 +186,8 @@ int kg_select_intervals(int device, const kg_select_params *p, const kg_interval
     CallScope cs(device);               // the call's context: closed on every failure below, kept by the set on success
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;
-    std::unique_ptr<kg_selectset> set(new (std::nothrow) kg_selectset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = t;
+    std::unique_ptr<kg_selectset> set;
+    if ((rc = make_set(cs, set))) return rc;
     {
         Scratch sc(t);
         kg_interval *d_iv = nullptr;
@@ -203,11 +196,7 @@ int kg_select_intervals(int device, const kg_select_params *p, const kg_interval
         if ((rc = select_impl(t, p, d_iv, (uint64_t)n, (uint64_t)n_seqs, std::max(1u, bit_width((uint64_t)left_max)), false, set.get())))
             return rc;
     }
-    t->cache.release_free();            // (the scratch is back in the cache: it goes to the driver, the set's array stays)
-    set->own_tab = true;
-    cs.disown();
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int64_t kg_selectset_count(const kg_selectset *s) { return s ? s->count : 0; }
@@ -216,30 +205,11 @@ const kg_selection *kg_selectset_device(const kg_selectset *s) { return s ? s->d
 
 int kg_selectset_copy(const kg_selectset *s, int64_t first, int64_t count, kg_selection *dst)
 {
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_selectset_copy: range outside the set");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_sel + first, (size_t)count * sizeof(kg_selection), hipMemcpyDefault));
-    return KG_OK;
+    return copy_records(s, device_of(s), s ? s->d_sel : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_selectset_copy");
 }
 
-int kg_selectset_stats(const kg_selectset *s, kg_select_stats *out)
-{
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    *out = s->st;
-    return KG_OK;
-}
+int kg_selectset_stats(const kg_selectset *s, kg_select_stats *out) { return copy_stats(s, s ? &s->st : nullptr, out); }
 
-void kg_selectset_free(kg_selectset *s)
-{
-    if (!s) return;
-    if (s->tab) {
-        (void)hipSetDevice(s->tab->device);
-        dfree(s->tab, s->d_sel);
-        if (s->own_tab) kg_table_close(s->tab);
-    }
-    delete s;
-}
+void kg_selectset_free(kg_selectset *s) { delete s; }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 // that stage's Lg and checks).
 #pragma once
 
-static_assert(kPinCoding + kg::kStartErrWords + kg::kStartCntWords <= kPinWords, "stage words must fit their pinned words");
+static_assert(kg::kStartErrWords + kg::kStartCntWords <= kPinStageWords, "stage words must fit their pinned words");
 static_assert(sizeof(kg_start_params) == 24 && sizeof(kg_start_model) == 8 * 2 * kg::kStartBins &&
               sizeof(kg_start_weights) == 4 * kg::kStartBins && sizeof(kg_start_stats) == 48,
               "record layouts of include/kmerguts_hip.h");
@@ -211,14 +211,14 @@ struct StartsWork {
             ": seq outside [0, n_seqs)", ": strand is neither 0 nor 1", ": outside its contig (0 <= left <= right <= L - 1 does not hold)",
             ": 3 * n_res exceeds right - left + 1", ": its region has another seq or strand, or begins in front of the record's start"};
         int rc;
-        if ((rc = read_error_words(t, words, kg::kStartErrWords + kg::kStartCntWords, kPinCoding, {}))) return rc;
+        if ((rc = read_error_words(t, words, kg::kStartErrWords + kg::kStartCntWords, kPinStage, {}))) return rc;
         // every word holds the first record with its error: the message names the first record with any
-        const uint64_t *h = t->h_pin + kPinCoding;
+        const uint64_t *h = t->h_pin + kPinStage;
         const int first = (int)(std::min_element(h, h + kg::kStartErrWords) - h);
         if (h[first] != kNoErr) return fail(KG_ERR_ARG, "record " + kmer_text((int64_t)h[first]) + what[first]);
         return KG_OK;
     }
-    uint64_t counter(int k) const { return t->h_pin[kPinCoding + kg::kStartErrWords + k]; }
+    uint64_t counter(int k) const { return t->h_pin[kPinStage + kg::kStartErrWords + k]; }
     // trained 0 / 1 / 2 of the statistics
     int decide(const kg_start_params *p, const kg_start_weights *caller)
     {
@@ -259,15 +259,14 @@ int kg_orfset_starts(kg_orfset *os, const kg_start_params *p, const int32_t *tab
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;
     hipStream_t s = t->stream;
-    std::unique_ptr<kg_orfset> set(new (std::nothrow) kg_orfset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
+    std::unique_ptr<kg_orfset> set;
+    if ((rc = make_set(cs, set))) return rc;
     set->start_model.reset(new (std::nothrow) kg_start_model());
     if (!set->start_model) return fail(KG_ERR_NOMEM, "out of host memory");
     if (os->coding_model) {
         set->coding_model.reset(new (std::nothrow) kg_coding_model(*os->coding_model));
         if (!set->coding_model) return fail(KG_ERR_NOMEM, "out of host memory");
     }
-    set->tab = t;
     if ((rc = ev.create())) return rc;
     StartsWork w(t);
     const uint8_t *d_seq = nullptr;
@@ -315,13 +314,11 @@ int kg_orfset_starts(kg_orfset *os, const kg_start_params *p, const int32_t *tab
     w.st.ms_count = ev.ms(0, 1);
     w.st.ms_choose = ev.ms(2, 3);
     // the arrays of the set leave the scratch: everything else goes back to the cache
-    w.sc.release(d_out); w.sc.release(d_start); w.sc.release(d_res); w.sc.release(d_shift);
-    if (d_S) w.sc.release(d_S);
-    set->d_orfs = d_out;
-    set->d_prot_start = d_start;
-    set->d_res = d_res;
-    set->d_coding = d_S;
-    set->d_shift = d_shift;
+    set->d_orfs = set->keep(w.sc, d_out);
+    set->d_prot_start = set->keep(w.sc, d_start);
+    set->d_res = set->keep(w.sc, d_res);
+    set->d_coding = set->keep(w.sc, d_S);
+    set->d_shift = set->keep(w.sc, d_shift);
     set->count = os->count;
     set->residues = (int64_t)n_res;
     set->n_seqs = os->n_seqs;
@@ -331,19 +328,14 @@ int kg_orfset_starts(kg_orfset *os, const kg_start_params *p, const int32_t *tab
     set->coding_st = os->coding_st;
     *set->start_model = w.model;
     set->start_st = w.st;
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int kg_orfset_start_shifts(const kg_orfset *s, int64_t first, int64_t count, int32_t *dst)
 {
     if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
     if (!s->d_shift) return fail(KG_ERR_ARG, "kg_orfset_start_shifts: the set has no shifts (it is not from kg_orfset_starts)");
-    if (first < 0 || count < 0 || first + count > s->count) return fail(KG_ERR_ARG, "kg_orfset_start_shifts: range outside the set");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_shift + first, (size_t)count * 4, hipMemcpyDefault));
-    return KG_OK;
+    return copy_records(s, device_of(s), s->d_shift, 1, s->count, first, count, dst, "kg_orfset_start_shifts");
 }
 
 int kg_orfset_start_stats(const kg_orfset *s, kg_start_stats *out)

@@ -4,9 +4,7 @@
 // hosts of the table, the result and the scan.
 #pragma once
 
-struct kg_voteset {
-    kg_table *tab = nullptr;            // the context whose block cache the four arrays came from
-    bool own_tab = false;               // kg_otu_votes_hits: the set owns a table-less context
+struct kg_voteset : SetBase {
     kg_otu_vote *d_votes = nullptr;     // count records, rule 3's order
     int64_t *d_seq_start = nullptr;     // n_seqs + 1
     kg_otu_class *d_classes = nullptr;  // n_seqs
@@ -17,8 +15,8 @@ struct kg_voteset {
 
 namespace {
 
-constexpr int kPinVotes = kPinRegions;      // the stage area of kg_table::h_pin: the error and counter words, then up to three totals
-static_assert(kPinVotes + kg::kVoteErrWords + kg::kVoteCntWords + 3 <= kPinWords, "stage words must fit their pinned words");
+// the stage area of kg_table::h_pin: the error and counter words, then up to three totals
+static_assert(kg::kVoteErrWords + kg::kVoteCntWords + 3 <= kPinStageWords, "stage words must fit their pinned words");
 static_assert(kNoErr == kg::kVoteNoErr, "the stages' kernels share the error words' \"none\"");
 
 int check_vote_params(const kg_vote_params *p)
@@ -51,10 +49,10 @@ int check_vote_starts(const int64_t *start, int64_t n_cont, const char *name)
     return KG_OK;
 }
 
-// d_words + word .. (+ count) -> h_pin[kPinVotes ..], waited for
+// d_words + word .. (+ count) -> h_pin[kPinStage ..], waited for
 int vote_read_back(kg_table *t, const unsigned long long *d_words, int word, int count)
 {
-    HIP_TRY(hipMemcpyAsync(t->h_pin + kPinVotes, d_words + word, (size_t)count * 8, hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipMemcpyAsync(t->h_pin + kPinStage, d_words + word, (size_t)count * 8, hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     return KG_OK;
 }
@@ -86,7 +84,7 @@ int votes_impl(kg_table *t, const kg_vote_params *prm, const kg_hit *d_hits, con
     HIP_TRY(hipMemsetAsync(err, 0x7F, kg::kVoteErrWords * 8, s));
     HIP_TRY(hipMemsetAsync(cnt, 0, (kg::kVoteCntWords + kSumCount) * 8, s));
     HIP_TRY(hipEventRecord(t->ev[kEvStageBegin], s));
-    const uint64_t *h = t->h_pin + kPinVotes;
+    const uint64_t *h = t->h_pin + kPinStage;
     uint64_t n_votes = 0, n_runs = 0, n_assigned = 0, n_bins = 0;
     uint32_t oi_bits = 0, v_bits = 0;
     const uint64_t *tally_keys = nullptr, *order_keys = nullptr;
@@ -204,7 +202,7 @@ int votes_impl(kg_table *t, const kg_vote_params *prm, const kg_hit *d_hits, con
     }
     if (!d_bins && (rc = sc.get(&d_bins, 1))) return rc;
     HIP_TRY(hipEventRecord(t->ev[kEvStageEnd], s));
-    if ((rc = read_error_words(t, words, kWordsTot, kPinVotes,                      // (in the order they are reported)
+    if ((rc = read_error_words(t, words, kWordsTot, kPinStage,                      // (in the order they are reported)
                                {{kg::kVoteErrHitSlice, KG_ERR_ARG, "hit ", ": its container field is not the container whose slice of hits[] it lies in"},
                                 {kg::kVoteErrHitOrder, KG_ERR_ARG, "hit ", ": from0InProt below its predecessor's (hits[] must be in (container, from0InProt) order)"},
                                 {kg::kVoteErrCallSlice, KG_ERR_ARG, "CALL ", ": its container field is not the container whose slice of calls[] it lies in"},
@@ -223,25 +221,13 @@ int votes_impl(kg_table *t, const kg_vote_params *prm, const kg_hit *d_hits, con
     set->st.total_length = (int64_t)length_top;
     HIP_TRY(hipEventElapsedTime(&set->st.ms, t->ev[kEvStageBegin], t->ev[kEvStageEnd]));
     // the four arrays of the set leave the scratch: everything else goes back to the cache
-    sc.release(d_votes); sc.release(d_start); sc.release(d_cls); sc.release(d_bins);
-    set->d_votes = d_votes;
-    set->d_seq_start = d_start;
-    set->d_classes = d_cls;
-    set->d_bins = d_bins;
+    set->d_votes = set->keep(sc, d_votes);
+    set->d_seq_start = set->keep(sc, d_start);
+    set->d_classes = set->keep(sc, d_cls);
+    set->d_bins = set->keep(sc, d_bins);
     set->count = (int64_t)n_runs;
     set->n_seqs = (int64_t)n_seqs;
     set->n_bins = (int64_t)n_bins;
-    return KG_OK;
-}
-
-template <typename T>
-int voteset_copy(const kg_voteset *s, const T *src, int64_t have, int64_t first, int64_t count, T *dst, const char *what)
-{
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (first < 0 || count < 0 || first + count > have) return fail(KG_ERR_ARG, std::string(what) + ": range outside the set");
-    if (count == 0) return KG_OK;
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, src + first, (size_t)count * sizeof(T), hipMemcpyDefault));
     return KG_OK;
 }
 
@@ -263,14 +249,12 @@ int kg_result_otu_votes(kg_result *r, const kg_vote_params *p, const int64_t *of
     if (r->st.n_hits > 0 && !r->d_ev) return fail(KG_ERR_ARG, "the result has no hit events");
     CallScope cs(r->tab, "a kg_scan* is in flight on this result's kg_table");
     if (cs.rc) return cs.rc;
-    std::unique_ptr<kg_voteset> set(new (std::nothrow) kg_voteset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = cs.t;
+    std::unique_ptr<kg_voteset> set;
+    if ((rc = make_set(cs, set))) return rc;
     if ((rc = votes_impl(cs.t, p, r->d_hits, r->d_ev, (uint64_t)r->st.n_hits, r->d_chs, r->d_calls, (uint64_t)r->st.n_calls, r->d_ccs,
                          (uint64_t)r->st.n_seqs, r->per, offsets, set.get())))
         return rc;
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int kg_otu_votes_hits(int device, const kg_vote_params *p, const kg_hit *hits, const int64_t *container_hit_start,
@@ -296,9 +280,8 @@ int kg_otu_votes_hits(int device, const kg_vote_params *p, const kg_hit *hits, c
     CallScope cs(device);               // the call's context: closed on every failure below, kept by the set on success
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;
-    std::unique_ptr<kg_voteset> set(new (std::nothrow) kg_voteset());
-    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
-    set->tab = t;
+    std::unique_ptr<kg_voteset> set;
+    if ((rc = make_set(cs, set))) return rc;
     {
         Scratch sc(t);
         kg_hit *d_hits = nullptr;
@@ -320,11 +303,7 @@ int kg_otu_votes_hits(int device, const kg_vote_params *p, const kg_hit *hits, c
                              offsets, set.get())))
             return rc;
     }
-    t->cache.release_free();            // (the scratch is back in the cache: it goes to the driver, the set's four arrays stay)
-    set->own_tab = true;
-    cs.disown();
-    *out = set.release();
-    return KG_OK;
+    return hand_out(cs, set, out);
 }
 
 int64_t kg_voteset_count(const kg_voteset *s) { return s ? s->count : 0; }
@@ -333,46 +312,26 @@ int64_t kg_voteset_bins(const kg_voteset *s) { return s ? s->n_bins : 0; }
 
 int kg_voteset_copy_votes(const kg_voteset *s, int64_t first, int64_t count, kg_otu_vote *dst)
 {
-    return voteset_copy(s, s ? s->d_votes : nullptr, s ? s->count : 0, first, count, dst, "kg_voteset_copy_votes");
+    return copy_records(s, device_of(s), s ? s->d_votes : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_voteset_copy_votes");
 }
 
 int kg_voteset_copy_classes(const kg_voteset *s, int64_t first, int64_t count, kg_otu_class *dst)
 {
-    return voteset_copy(s, s ? s->d_classes : nullptr, s ? s->n_seqs : 0, first, count, dst, "kg_voteset_copy_classes");
+    return copy_records(s, device_of(s), s ? s->d_classes : nullptr, 1, s ? s->n_seqs : 0, first, count, dst, "kg_voteset_copy_classes");
 }
 
 int kg_voteset_copy_bins(const kg_voteset *s, int64_t first, int64_t count, kg_otu_bin *dst)
 {
-    return voteset_copy(s, s ? s->d_bins : nullptr, s ? s->n_bins : 0, first, count, dst, "kg_voteset_copy_bins");
+    return copy_records(s, device_of(s), s ? s->d_bins : nullptr, 1, s ? s->n_bins : 0, first, count, dst, "kg_voteset_copy_bins");
 }
 
 int kg_voteset_seq_start(const kg_voteset *s, int64_t *dst)
 {
-    if (!s || !dst) return fail(KG_ERR_ARG, "null argument");
-    HIP_TRY(hipSetDevice(s->tab->device));
-    HIP_TRY(hipMemcpy(dst, s->d_seq_start, ((size_t)s->n_seqs + 1) * 8, hipMemcpyDefault));
-    return KG_OK;
+    return copy_starts(s, device_of(s), s ? s->d_seq_start : nullptr, s ? s->n_seqs : 0, dst);
 }
 
-int kg_voteset_stats(const kg_voteset *s, kg_vote_stats *out)
-{
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    *out = s->st;
-    return KG_OK;
-}
+int kg_voteset_stats(const kg_voteset *s, kg_vote_stats *out) { return copy_stats(s, s ? &s->st : nullptr, out); }
 
-void kg_voteset_free(kg_voteset *s)
-{
-    if (!s) return;
-    if (s->tab) {
-        (void)hipSetDevice(s->tab->device);
-        dfree(s->tab, s->d_votes);
-        dfree(s->tab, s->d_seq_start);
-        dfree(s->tab, s->d_classes);
-        dfree(s->tab, s->d_bins);
-        if (s->own_tab) kg_table_close(s->tab);
-    }
-    delete s;
-}
+void kg_voteset_free(kg_voteset *s) { delete s; }
 
 }  // extern "C"

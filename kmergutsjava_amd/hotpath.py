@@ -57,6 +57,25 @@ def device_tensor(ptr: int, count: int, typestr: str = "|u1", owner=None, device
     return t
 
 
+def _copy_records(copy, h, n: int, dtype, shape=(), device_out: bool = False):
+    """Records [0, n) of a set, each `shape` elements of `dtype`, through the set's range getter `copy`.  -> a numpy array
+    of (n,) + shape; or with device_out a CUDA tensor: uint8 of itemsize bytes per record for a record dtype, the typed
+    (n,) + shape tensor for a plain one."""
+    dtype = np.dtype(dtype)
+    if not device_out:
+        a = np.zeros((n,) + tuple(shape), dtype=dtype)
+        N.check(copy(h, 0, n, a.ctypes.data if n else None))
+        return a
+    import torch
+    if dtype.names:
+        a = torch.empty(n * dtype.itemsize, dtype=torch.uint8, device="cuda")
+    else:
+        a = torch.empty((n,) + tuple(shape), dtype=getattr(torch, dtype.name), device="cuda")
+    torch.cuda.synchronize()            # the library works on its own stream
+    N.check(copy(h, 0, n, C.c_void_p(a.data_ptr() if n else None)))
+    return a
+
+
 class ScanResult:
     """Owns one kg_result.  Record arrays are numpy structured arrays (copies)."""
 
@@ -643,11 +662,7 @@ class SignatureSet:
     def numpy(self) -> np.ndarray:
         """The records as a numpy array of _native.SIGNATURE_DTYPE."""
         self._need()
-        n = self.count
-        out = np.zeros(n, dtype=N.SIGNATURE_DTYPE)
-        if n:
-            N.check(N.load().kg_sigset_copy(self._h, 0, n, out.ctypes.data))
-        return out
+        return _copy_records(N.load().kg_sigset_copy, self._h, self.count, N.SIGNATURE_DTYPE)
 
     def device_tensor(self):
         """Zero-copy torch view (uint8, 24 bytes per record) of the records, valid until close(); SignatureTable.build
@@ -744,10 +759,7 @@ def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20,
     try:
         st = N.KgClusterStats()
         N.check(lib.kg_familyset_stats(h, C.byref(st)))
-        count = int(lib.kg_familyset_count(h))
-        out = np.zeros(count, dtype=N.FAMILY_DTYPE)
-        N.check(lib.kg_familyset_copy(h, 0, count, out.ctypes.data if count else None))
-        return out, st.as_dict()
+        return _copy_records(lib.kg_familyset_copy, h, int(lib.kg_familyset_count(h)), N.FAMILY_DTYPE), st.as_dict()
     finally:
         lib.kg_familyset_free(h)
 
@@ -783,15 +795,7 @@ def _take_regionset(h, n_seqs: int, device_out: bool):
         n = int(lib.kg_regionset_count(h))
         start = np.zeros(n_seqs + 1, dtype=np.int64)
         N.check(lib.kg_regionset_seq_start(h, start.ctypes.data))
-        if device_out:
-            import torch
-            out = torch.empty(n * N.REGION_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-            torch.cuda.synchronize()
-            N.check(lib.kg_regionset_copy(h, 0, n, C.c_void_p(out.data_ptr() if n else None)))
-        else:
-            out = np.zeros(n, dtype=N.REGION_DTYPE)
-            N.check(lib.kg_regionset_copy(h, 0, n, out.ctypes.data if n else None))
-        return out, start, st.as_dict()
+        return _copy_records(lib.kg_regionset_copy, h, n, N.REGION_DTYPE, device_out=device_out), start, st.as_dict()
     finally:
         lib.kg_regionset_free(h)
 
@@ -824,20 +828,10 @@ def _take_voteset(h, n_seqs: int, device_out: bool):
         N.check(lib.kg_voteset_stats(h, C.byref(st)))
         start = np.zeros(n_seqs + 1, dtype=np.int64)
         N.check(lib.kg_voteset_seq_start(h, start.ctypes.data))
-        out = []
-        for n, dt, copy in ((int(lib.kg_voteset_count(h)), N.VOTE_DTYPE, lib.kg_voteset_copy_votes),
-                            (n_seqs, N.OTU_CLASS_DTYPE, lib.kg_voteset_copy_classes),
-                            (int(lib.kg_voteset_bins(h)), N.OTU_BIN_DTYPE, lib.kg_voteset_copy_bins)):
-            if device_out:
-                import torch
-                a = torch.empty(n * dt.itemsize, dtype=torch.uint8, device="cuda")
-                torch.cuda.synchronize()
-                N.check(copy(h, 0, n, C.c_void_p(a.data_ptr() if n else None)))
-            else:
-                a = np.zeros(n, dtype=dt)
-                N.check(copy(h, 0, n, a.ctypes.data if n else None))
-            out.append(a)
-        return out[0], start, out[1], out[2], st.as_dict()
+        votes = _copy_records(lib.kg_voteset_copy_votes, h, int(lib.kg_voteset_count(h)), N.VOTE_DTYPE, device_out=device_out)
+        classes = _copy_records(lib.kg_voteset_copy_classes, h, n_seqs, N.OTU_CLASS_DTYPE, device_out=device_out)
+        bins = _copy_records(lib.kg_voteset_copy_bins, h, int(lib.kg_voteset_bins(h)), N.OTU_BIN_DTYPE, device_out=device_out)
+        return votes, start, classes, bins, st.as_dict()
     finally:
         lib.kg_voteset_free(h)
 
@@ -920,26 +914,14 @@ def compose_contigs(seq, offsets, labels=None, model=None, min_len: int = 1500, 
         N.check(lib.kg_compset_stats(h, C.byref(st)))
         R, M = int(lib.kg_compset_rows(h)), int(lib.kg_compset_models(h))
         out = {"row_labels": np.zeros(R, dtype=np.int32), "rows": np.zeros((R, N.COMP_BINS), dtype=np.int64),
-               "background": np.zeros(N.COMP_BINS, dtype=np.int64), "model_labels": np.zeros(M, dtype=np.int32)}
+               "background": np.zeros(N.COMP_BINS, dtype=np.int64),
+               "model_labels": _copy_records(lib.kg_compset_model_labels, h, M, np.int32)}
         N.check(lib.kg_compset_copy_rows(h, 0, R, out["row_labels"].ctypes.data if R else None, out["rows"].ctypes.data if R else None))
         N.check(lib.kg_compset_background(h, out["background"].ctypes.data))
-        N.check(lib.kg_compset_model_labels(h, 0, M, out["model_labels"].ctypes.data if M else None))
-        parts = [("classes", lib.kg_compset_copy_classes, N.COMP_CLASS_DTYPE, ()), ("counts", lib.kg_compset_copy_counts, np.dtype(np.int32), (N.COMP_BINS,))]
+        out["classes"] = _copy_records(lib.kg_compset_copy_classes, h, n, N.COMP_CLASS_DTYPE, device_out=device_out)
+        out["counts"] = _copy_records(lib.kg_compset_copy_counts, h, n, np.int32, (N.COMP_BINS,), device_out)
         if keep_scores:
-            parts.append(("scores", lib.kg_compset_copy_scores, np.dtype(np.int64), (M + 1,)))
-        for name, copy, dt, shape in parts:
-            if device_out:
-                import torch
-                if name == "classes":
-                    a = torch.empty(n * dt.itemsize, dtype=torch.uint8, device="cuda")
-                else:
-                    a = torch.empty((n,) + shape, dtype=torch.int32 if dt.itemsize == 4 else torch.int64, device="cuda")
-                torch.cuda.synchronize()
-                N.check(copy(h, 0, n, C.c_void_p(a.data_ptr() if n else None)))
-            else:
-                a = np.zeros((n,) + shape, dtype=dt)
-                N.check(copy(h, 0, n, a.ctypes.data if n else None))
-            out[name] = a
+            out["scores"] = _copy_records(lib.kg_compset_copy_scores, h, n, np.int64, (M + 1,), device_out)
         if stats is not None:
             stats.update(st.as_dict())
         return out
@@ -954,22 +936,16 @@ def _take_orfset(h, device_out: bool):
         st = N.KgOrfStats()
         N.check(lib.kg_orfset_stats(h, C.byref(st)))
         n, n_res = int(lib.kg_orfset_count(h)), int(st.residues)
+        out = _copy_records(lib.kg_orfset_copy, h, n, N.ORF_DTYPE, device_out=device_out)
+        res = _copy_records(lib.kg_orfset_residues, h, n_res, np.uint8, device_out=device_out)
         if device_out:
             import torch
-            out = torch.empty(n * N.ORF_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
             start = torch.empty(n + 1, dtype=torch.int64, device="cuda")
-            res = torch.empty(n_res, dtype=torch.uint8, device="cuda")
             torch.cuda.synchronize()
-            N.check(lib.kg_orfset_copy(h, 0, n, C.c_void_p(out.data_ptr() if n else None)))
             N.check(lib.kg_orfset_prot_start(h, C.c_void_p(start.data_ptr())))
-            N.check(lib.kg_orfset_residues(h, 0, n_res, C.c_void_p(res.data_ptr() if n_res else None)))
         else:
-            out = np.zeros(n, dtype=N.ORF_DTYPE)
             start = np.zeros(n + 1, dtype=np.int64)
-            res = np.zeros(n_res, dtype=np.uint8)
-            N.check(lib.kg_orfset_copy(h, 0, n, out.ctypes.data if n else None))
             N.check(lib.kg_orfset_prot_start(h, start.ctypes.data))
-            N.check(lib.kg_orfset_residues(h, 0, n_res, res.ctypes.data if n_res else None))
         return out, start, res, st.as_dict()
     finally:
         lib.kg_orfset_free(h)
@@ -981,9 +957,8 @@ def _junctions(h):
     st = N.KgRepairStats()
     N.check(lib.kg_orfset_junctions_stats(h, C.byref(st)))
     n, nj = int(lib.kg_orfset_count(h)), int(lib.kg_orfset_junctions_count(h))
-    rec = np.zeros(nj, dtype=N.JUNCTION_DTYPE)
+    rec = _copy_records(lib.kg_orfset_junctions_copy, h, nj, N.JUNCTION_DTYPE)
     start = np.zeros(n + 1, dtype=np.int64)
-    N.check(lib.kg_orfset_junctions_copy(h, 0, nj, rec.ctypes.data if nj else None))
     N.check(lib.kg_orfset_junctions_start(h, start.ctypes.data))
     return rec, start, st.as_dict()
 
@@ -1092,8 +1067,7 @@ def _coding_results(h):
     lib = N.load()
     try:
         n = int(lib.kg_orfset_count(h))
-        scores = np.zeros(n, dtype=np.int64)
-        N.check(lib.kg_orfset_coding_scores(h, 0, n, scores.ctypes.data if n else None))
+        scores = _copy_records(lib.kg_orfset_coding_scores, h, n, np.int64)
         st, m = N.KgCodingStats(), N.KgCodingModel()
         N.check(lib.kg_orfset_coding_stats(h, C.byref(st)))
         N.check(lib.kg_orfset_coding_model(h, C.byref(m)))
@@ -1156,8 +1130,7 @@ def _starts_results(h):
     lib = N.load()
     try:
         n = int(lib.kg_orfset_count(h))
-        shifts = np.zeros(n, dtype=np.int32)
-        N.check(lib.kg_orfset_start_shifts(h, 0, n, shifts.ctypes.data if n else None))
+        shifts = _copy_records(lib.kg_orfset_start_shifts, h, n, np.int32)
         st, m = N.KgStartStats(), N.KgStartModel()
         N.check(lib.kg_orfset_start_stats(h, C.byref(st)))
         N.check(lib.kg_orfset_start_model(h, C.byref(m)))
@@ -1319,16 +1292,7 @@ def _take_selectset(h, device_out: bool):
     try:
         st = N.KgSelectStats()
         N.check(lib.kg_selectset_stats(h, C.byref(st)))
-        n = int(lib.kg_selectset_count(h))
-        if device_out:
-            import torch
-            out = torch.empty(n * N.SELECTION_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-            torch.cuda.synchronize()
-            N.check(lib.kg_selectset_copy(h, 0, n, C.c_void_p(out.data_ptr() if n else None)))
-        else:
-            out = np.zeros(n, dtype=N.SELECTION_DTYPE)
-            N.check(lib.kg_selectset_copy(h, 0, n, out.ctypes.data if n else None))
-        return out, st.as_dict()
+        return _copy_records(lib.kg_selectset_copy, h, int(lib.kg_selectset_count(h)), N.SELECTION_DTYPE, device_out=device_out), st.as_dict()
     finally:
         lib.kg_selectset_free(h)
 
