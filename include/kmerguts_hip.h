@@ -380,7 +380,8 @@ int kg_sigset_merge_stats(const kg_sigset *s, kg_merge_stats *out);
  * Dependence on order.  The partition depends on protein order only through ties of len_p in the centre choice.  The numbering
  * (family, root, best) depends on order by definition.  Nothing depends on launch geometry or scheduling.
  * Known weakness: single linkage chains, and a repeat or a domain shared by two families can join them.  That is stated, not
- * repaired; min_cover_pct is the lever.
+ * repaired; min_cover_pct is the lever.  (kg_proteins_cluster_aligned, below, is the repair: it verifies every edge by aligning
+ * its two proteins.  This call stays as it is.)
  * One pass.  A call whose valid windows do not fit the device returns KG_ERR_LIMIT and says so.  max_windows = 0: the capacity
  * is sized from free device memory as the derive call does (about 160 bytes per valid window, at most 2^32 - 2^22 windows); any
  * other value caps it.
@@ -424,6 +425,102 @@ int64_t kg_familyset_count(const kg_familyset *s);
 int kg_familyset_copy(const kg_familyset *s, int64_t first, int64_t count, kg_family *dst);
 int kg_familyset_stats(const kg_familyset *s, kg_cluster_stats *out);
 void kg_familyset_free(kg_familyset *s);
+
+/* ---- verifying family edges: local alignment of the two proteins of a link (kernels: kg_align.hpp) ----
+ *
+ * The reference only reads signatures; this rule is the project's own.  It repairs the known weakness above: behind the 8-mer
+ * tests the two proteins of every link are aligned, and the link stays an edge only if the alignment covers them.  Integers only.
+ *   Residues: toAminoAcidOff codes, ACDEFGHIKLMNPQRSTVWY -> 0..19, everything else -> 20.
+ *   Substitution scores: a symmetric 21 x 21 int8 matrix S, row-major in code order, entries in [-16, 16].  params.matrix gives
+ *   the caller's (441 bytes); NULL means the built-in one: BLOSUM62 permuted into code order, with row and column 20 all -1.
+ *   (BLOSUM62's own X row has 0 and -2 entries as well; one value for every pair with a non-residue is this project's
+ *   simplification.)
+ *   Score: for proteins a (length n) and b (length m), 1-based, boundary rows and columns H = 0 and E = F = -infinity:
+ *       E[i][j] = max(E[i][j-1], H[i][j-1] - gap_open) - gap_extend
+ *       F[i][j] = max(F[i-1][j], H[i-1][j] - gap_open) - gap_extend
+ *       H[i][j] = max(0, H[i-1][j-1] + S[a_i][b_j], E[i][j], F[i][j])
+ *       score(a, b) = the maximum of H over all cells, 0 for an empty protein
+ *   A gap of k residues costs gap_open + k * gap_extend; the defaults are 11 and 1, the usual pairing for this matrix;
+ *   gap_open >= 0, gap_extend >= 1.  (end_a, end_b) is the 0-based cell with H = score that has the smallest i, then the
+ *   smallest j; (-1, -1) when score = 0.  There is no traceback: the score is a maximum and does not depend on how ties inside
+ *   the recurrence are broken; the end has the tie rule above.
+ *   self(p) = the sum of S[x][x] over p's residues with code < 20: what a protein scores against itself, X aside.
+ *   Abstaining: a pair with n * m > max_cells is not aligned: score = -1, end = (-1, -1), status skipped.  The default is
+ *   2^26 cells (8192 x 8192): this project's choice, it bounds the longest wave.  max_cells >= 1.
+ *   Edge test: a link (m, c) that passed the two 8-mer tests is kept iff score >= 1 and 100 * score >= min_ratio_pct * ref,
+ *   computed in int64; ref = max(self(m), self(c)) with KG_ALIGN_REF_LONGER (the default), ref = self(m) with
+ *   KG_ALIGN_REF_MEMBER; 0 <= min_ratio_pct <= 100, default 50.  A skipped pair is kept.  The ratio is the BLAST score ratio.
+ *   Measured against the larger self-score it demands that both proteins are covered, which is what cuts a chain through a
+ *   shared domain.  The price: a true fragment, such as a partial5 ORF at a contig end, falls out of its family;
+ *   KG_ALIGN_REF_MEMBER is the lever.  The defaults 50 and LONGER are this project's choice.
+ *   Families, root, family, best and shared follow the definitions above over the kept edges only: best is the centre of the
+ *   largest s among the member's kept edges.
+ * Nothing depends on launch geometry, pair order or scheduling: the maximum and its end are reduced with a total order
+ * (score, then -i, then -j).
+ *
+ * kg_proteins_align / kg_proteins_align_device: seq and offsets as for kg_proteins_cluster (a host or a device sequence, host
+ * offsets); pairs is a host int32[2 * n_pairs] of (a, b) protein indices: any order, repeats and a == b allowed.  out is a
+ * host array of n_pairs kg_alignment, in pair order; status is 0 for aligned and 1 for skipped; the ratio test is not applied.
+ * KG_ERR_ARG: null pointers, bad parameters (the message names the first), an asymmetric or out-of-range matrix, an index
+ * outside [0, n_prot), decreasing offsets.  KG_ERR_LIMIT: len_p >= 2^24 (so that no score can reach 2^31).  KG_ERR_NOMEM.
+ * KG_TEST_FAIL_ALLOC applies; all scratch goes back to the driver before the call returns.  Zero pairs and zero proteins are
+ * valid.
+ *
+ * kg_proteins_cluster_aligned / _device: kg_proteins_cluster with the alignment step between the edge test and the component
+ * rounds.  align == NULL: the code path, the kernels launched and the result are kg_proteins_cluster's.  The set then also
+ * holds one 32-byte kg_family_edge per link that passed the 8-mer tests, in ascending (member, centre): status 0 kept, 1 cut,
+ * 2 skipped (kg_familyset_edges_count is 0 for a set made without alignment), and kg_familyset_align_stats (KG_ERR_ARG for a set
+ * made without alignment).  kg_cluster_stats.edges counts the kept edges; ms_link does not include ms_align. */
+#define KG_ALIGN_REF_LONGER 0
+#define KG_ALIGN_REF_MEMBER 1
+#define KG_ALIGN_DEFAULT_MAX_CELLS (1ll << 26)
+typedef struct kg_align_params {
+    int32_t min_ratio_pct;
+    int32_t ref;
+    int32_t gap_open;
+    int32_t gap_extend;
+    int64_t max_cells;
+    const int8_t *matrix;
+    int64_t reserved;
+} kg_align_params;
+typedef struct kg_alignment {    /* 24 B */
+    int32_t score;         /* -1 when skipped                                           */
+    int32_t self_a;
+    int32_t self_b;
+    int32_t end_a;         /* 0-based, -1 when score <= 0                               */
+    int32_t end_b;
+    int32_t status;        /* 0 aligned, 1 skipped                                      */
+} kg_alignment;
+typedef struct kg_family_edge {  /* 32 B */
+    int32_t member;
+    int32_t centre;
+    int32_t shared;        /* s(member, centre)                                         */
+    int32_t score;
+    int32_t ref;           /* the self-score the ratio is measured against              */
+    int32_t end_member;
+    int32_t end_centre;
+    int32_t status;        /* 0 kept, 1 cut, 2 skipped (kept)                           */
+} kg_family_edge;
+typedef struct kg_align_stats {
+    int64_t aligned;       /* links that passed the 8-mer tests and were aligned        */
+    int64_t cut;
+    int64_t skipped;
+    int64_t cells;         /* n * m summed over the aligned pairs                       */
+    float   ms_align;      /* compaction, alignment kernels, the cut                    */
+    int32_t reserved;
+} kg_align_stats;
+int kg_proteins_align(int device, const kg_align_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
+                      const int32_t *pairs, int64_t n_pairs, kg_alignment *out);
+int kg_proteins_align_device(int device, const kg_align_params *p, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
+                             const int32_t *pairs, int64_t n_pairs, kg_alignment *out);
+int kg_proteins_cluster_aligned(int device, const kg_cluster_params *p, const kg_align_params *align, const uint8_t *seq,
+                                const int64_t *offsets, int64_t n_prot, int64_t max_windows, kg_familyset **out);
+int kg_proteins_cluster_aligned_device(int device, const kg_cluster_params *p, const kg_align_params *align, const uint8_t *d_seq,
+                                       const int64_t *offsets, int64_t n_prot, int64_t max_windows, kg_familyset **out);
+int64_t kg_familyset_edges_count(const kg_familyset *s);
+/* edge records [first, first + count) into dst (host or device memory) */
+int kg_familyset_edges_copy(const kg_familyset *s, int64_t first, int64_t count, kg_family_edge *dst);
+int kg_familyset_align_stats(const kg_familyset *s, kg_align_stats *out);
 
 /* ---- assigning functions: the CALL records of an -a scan -> one function per protein (kernels: kg_assign.hpp) ----
  *

@@ -359,6 +359,45 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_align_params (kg_proteins_align*, kg_proteins_cluster_aligned*); this project's defaults: 50, KG_ALIGN_REF_LONGER (0;
+     *  KG_ALIGN_REF_MEMBER is 1), 11, 1, 2^26 cells, matrix null (the built-in BLOSUM62; else 441 bytes, 21 x 21 in code order), 0. */
+    class KgAlignParams extends Structure {
+        public int min_ratio_pct, ref, gap_open, gap_extend;
+        public long max_cells;
+        public Pointer matrix;
+        public long reserved;
+        public KgAlignParams() {
+            setFieldOrder(new String[] {"min_ratio_pct", "ref", "gap_open", "gap_extend", "max_cells", "matrix", "reserved"});
+        }
+    }
+
+    /** struct kg_alignment (24 B): the local alignment score (-1: skipped), the two self-scores, the 0-based end cell or (-1, -1),
+     *  status 0 aligned / 1 skipped. */
+    class KgAlignment extends Structure {
+        public int score, self_a, self_b, end_a, end_b, status;
+        public KgAlignment() {
+            setFieldOrder(new String[] {"score", "self_a", "self_b", "end_a", "end_b", "status"});
+        }
+    }
+
+    /** struct kg_family_edge (32 B): one link that passed the 8-mer tests; status 0 kept, 1 cut, 2 skipped. */
+    class KgFamilyEdge extends Structure {
+        public int member, centre, shared, score, ref, end_member, end_centre, status;
+        public KgFamilyEdge() {
+            setFieldOrder(new String[] {"member", "centre", "shared", "score", "ref", "end_member", "end_centre", "status"});
+        }
+    }
+
+    /** struct kg_align_stats. */
+    class KgAlignStats extends Structure {
+        public long aligned, cut, skipped, cells;
+        public float ms_align;
+        public int reserved;
+        public KgAlignStats() {
+            setFieldOrder(new String[] {"aligned", "cut", "skipped", "cells", "ms_align", "reserved"});
+        }
+    }
+
     /** struct kg_merge_params (kg_table_merge_signatures*): on_conflict = KG_MERGE_KEEP (0), KG_MERGE_REPLACE (1) or KG_MERGE_DROP (2). */
     class KgMergeParams extends Structure {
         public int on_conflict, reserved;
@@ -411,6 +450,18 @@ public interface KmerGutsHip extends Library {
     int kg_familyset_copy(Pointer set, long first, long count, Pointer dst);   // kg_family[count], 16 B each, protein order
     int kg_familyset_stats(Pointer set, KgClusterStats out);
     void kg_familyset_free(Pointer set);
+    /** local alignment scores of protein pairs: pairs = int[2 * nPairs] of (a, b) indices, out = kg_alignment[nPairs], 24 B each */
+    int kg_proteins_align(int device, KgAlignParams params, byte[] seq, long[] offsets, long nProt, int[] pairs, long nPairs, Pointer out);
+    int kg_proteins_align_device(int device, KgAlignParams params, Pointer dSeq, long[] offsets, long nProt, int[] pairs, long nPairs,
+                                 Pointer out);
+    /** kg_proteins_cluster with every link that passed the 8-mer tests verified by alignment; align = null: kg_proteins_cluster */
+    int kg_proteins_cluster_aligned(int device, KgClusterParams params, KgAlignParams align, byte[] seq, long[] offsets, long nProt,
+                                    long maxWindows, PointerByReference out);
+    int kg_proteins_cluster_aligned_device(int device, KgClusterParams params, KgAlignParams align, Pointer dSeq, long[] offsets, long nProt,
+                                           long maxWindows, PointerByReference out);
+    long kg_familyset_edges_count(Pointer set);
+    int kg_familyset_edges_copy(Pointer set, long first, long count, Pointer dst);   // kg_family_edge[count], 32 B each, (member, centre) order
+    int kg_familyset_align_stats(Pointer set, KgAlignStats out);
     Pointer kg_table_device_entries(Pointer table);
     long kg_table_records(Pointer table);
     int kg_table_info(Pointer table, long[] numSigs, long[] entrySize, long[] version, long[] occupied);

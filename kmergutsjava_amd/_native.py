@@ -37,6 +37,8 @@ EXPORTS = (
     "kg_table_merge_signatures", "kg_table_merge_signatures_device", "kg_sigset_merge_stats",
     "kg_proteins_cluster", "kg_proteins_cluster_device", "kg_familyset_count", "kg_familyset_copy", "kg_familyset_stats",
     "kg_familyset_free",
+    "kg_proteins_align", "kg_proteins_align_device", "kg_proteins_cluster_aligned", "kg_proteins_cluster_aligned_device",
+    "kg_familyset_edges_count", "kg_familyset_edges_copy", "kg_familyset_align_stats",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
@@ -127,6 +129,17 @@ COMP_SCORE_TILE = 16        # ... and kCompScoreTile: the models of one LDS tile
 # struct kg_family (kg_proteins_cluster*): one protein's family
 FAMILY_DTYPE = np.dtype([("family", "<i4"), ("root", "<i4"), ("best", "<i4"), ("shared", "<i4")])
 assert FAMILY_DTYPE.itemsize == 16
+# struct kg_alignment (kg_proteins_align*) and struct kg_family_edge (kg_proteins_cluster_aligned*)
+ALIGNMENT_DTYPE = np.dtype([("score", "<i4"), ("self_a", "<i4"), ("self_b", "<i4"), ("end_a", "<i4"), ("end_b", "<i4"), ("status", "<i4")])
+FAMILY_EDGE_DTYPE = np.dtype([("member", "<i4"), ("centre", "<i4"), ("shared", "<i4"), ("score", "<i4"), ("ref", "<i4"),
+                              ("end_member", "<i4"), ("end_centre", "<i4"), ("status", "<i4")])
+assert ALIGNMENT_DTYPE.itemsize == 24 and FAMILY_EDGE_DTYPE.itemsize == 32
+ALIGN_REF_LONGER, ALIGN_REF_MEMBER = 0, 1
+ALIGN_REFS = {"longer": ALIGN_REF_LONGER, "member": ALIGN_REF_MEMBER}
+ALIGN_DEFAULT_MAX_CELLS = 1 << 26
+ALIGN_ALIGNED, ALIGN_SKIPPED = 0, 1                     # kg_alignment.status
+EDGE_KEPT, EDGE_CUT, EDGE_SKIPPED = 0, 1, 2             # kg_family_edge.status
+ALIGN_LDS_COLS = 1024       # kg_align.hpp kAlignLdsCols: a longer second protein carries its stripes in device memory (tests aim at it)
 assert HIT_DTYPE.itemsize == 24 and CALL_DTYPE.itemsize == 24 and OTU_DTYPE.itemsize == 44
 
 
@@ -327,6 +340,21 @@ class KgClusterStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KgAlignParams(C.Structure):
+    """struct kg_align_params (kg_proteins_align* / kg_proteins_cluster_aligned*)."""
+    _fields_ = [("min_ratio_pct", C.c_int32), ("ref", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32),
+                ("max_cells", C.c_int64), ("matrix", C.c_void_p), ("reserved", C.c_int64)]
+
+
+class KgAlignStats(C.Structure):
+    """struct kg_align_stats."""
+    _fields_ = [("aligned", C.c_int64), ("cut", C.c_int64), ("skipped", C.c_int64), ("cells", C.c_int64), ("ms_align", C.c_float),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 class KgVoteParams(C.Structure):
     """struct kg_vote_params (kg_result_otu_votes / kg_otu_votes_hits)."""
     _fields_ = [("min_votes", C.c_int32), ("min_share_pct", C.c_int32), ("min_calls", C.c_int32), ("reserved", C.c_int32)]
@@ -465,15 +493,21 @@ def load() -> C.CDLL:
     for name in ("kg_proteins_cluster", "kg_proteins_cluster_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), vp, vp, C.c_int64, C.c_int64, C.POINTER(vp)]
     lib.kg_familyset_stats.argtypes = [vp, C.POINTER(KgClusterStats)]
+    for name in ("kg_proteins_align", "kg_proteins_align_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgAlignParams), vp, vp, C.c_int64, vp, C.c_int64, vp]
+    for name in ("kg_proteins_cluster_aligned", "kg_proteins_cluster_aligned_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
+                                       C.POINTER(vp)]
+    lib.kg_familyset_align_stats.argtypes = [vp, C.POINTER(KgAlignStats)]
     # the sets' accessors, by signature: (set) -> count, (set) -> device address, (set, first, count, dst), (set, dst), (set)
-    for name in ("kg_sigset_count", "kg_familyset_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
+    for name in ("kg_sigset_count", "kg_familyset_count", "kg_familyset_edges_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
                  "kg_selectset_count", "kg_voteset_count", "kg_voteset_bins", "kg_compset_rows", "kg_compset_models"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = C.c_int64
     for name in ("kg_sigset_device", "kg_regionset_device", "kg_orfset_device", "kg_selectset_device"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = vp
-    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
+    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
                  "kg_orfset_junctions_copy", "kg_orfset_coding_scores", "kg_orfset_start_shifts", "kg_selectset_copy",
                  "kg_voteset_copy_votes", "kg_voteset_copy_classes", "kg_voteset_copy_bins", "kg_compset_copy_classes",
                  "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores"):

@@ -1,7 +1,8 @@
 // kg_host_cluster.hpp -- kg_proteins_cluster / kg_proteins_cluster_device: proteins -> families by shared 8-mers (kernels:
 // kg_cluster.hpp; the window encode, the sort and the collapse are the derive call's, kg_derive.hpp).
+// kg_proteins_cluster_aligned / _device: the same with the alignment step of kg_host_align.hpp between the edge test and the rounds.
 // Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_derive.hpp (it uses the derive call's block
-// counts, its histogram and its bytes-per-window figure).
+// counts, its histogram and its bytes-per-window figure) and kg_host_align.hpp.
 #pragma once
 
 struct kg_familyset {
@@ -9,15 +10,22 @@ struct kg_familyset {
     uint8_t *d_fam = nullptr;           // count * 16 bytes (hipMalloc, owned)
     int64_t count = 0;
     kg_cluster_stats st = {};
+    // a set made with alignment: one record per link that passed the 8-mer tests
+    bool aligned = false;
+    uint8_t *d_edges = nullptr;         // n_edges * 32 bytes (hipMalloc, owned)
+    int64_t n_edges = 0;
+    kg_align_stats ast = {};
 };
 
 static_assert(sizeof(kg_family) == 16 && sizeof(kg_cluster_params) == 12, "record layouts of include/kmerguts_hip.h");
 
 namespace {
 
-int cluster_impl(kg_table *t, const kg_cluster_params *prm, const uint8_t *h_seq, const uint8_t *d_seq_in, const int64_t *offsets,
-                 int64_t n_prot, int64_t max_windows, kg_familyset *set)
+// al: null for kg_proteins_cluster; else the links that pass the 8-mer tests are aligned and the cut ones lose their edge
+int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq_in,
+                 const int64_t *offsets, int64_t n_prot, int64_t max_windows, kg_familyset *set)
 {
+    set->aligned = al != nullptr;
     kg_cluster_stats &st = set->st;
     std::vector<uint32_t> ibase;
     uint64_t nblocks = 0, windows = 0;
@@ -28,7 +36,7 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const uint8_t *h_seq
     hipStream_t s = t->stream;
 
     Scratch sc(t);
-    Events<8> ev;
+    Events<10> ev;
     if ((rc = ev.create())) return rc;
     const uint8_t *d_seq = d_seq_in;
     const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
@@ -47,9 +55,9 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const uint8_t *h_seq
     uint8_t *d_out = nullptr;
     if ((rc = dalloc_detached(t, &d_out, std::max<uint64_t>((uint64_t)n_prot * 16, 16)))) return rc;
     struct OutGuard {                   // (detached: the cache does not give it back on a failure)
-        uint8_t *p;
-        ~OutGuard() { if (p) (void)hipFree(p); }
-    } guard{d_out};
+        uint8_t *p, *edges;
+        ~OutGuard() { if (p) (void)hipFree(p); if (edges) (void)hipFree(edges); }
+    } guard{d_out, nullptr};
     if (n_prot == 0) {
         HIP_TRY(hipEventRecord(ev[5], s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -102,6 +110,7 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const uint8_t *h_seq
 
     uint64_t P = 0, K = 0, NL = 0, ND = 0;
     uint64_t *edge = nullptr;
+    const uint32_t *lstart_all = nullptr;
     HIP_TRY(hipEventRecord(ev[1], s));
     HIP_TRY(hipEventRecord(ev[2], s));
     HIP_TRY(hipEventRecord(ev[3], s));
@@ -175,6 +184,7 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const uint8_t *h_seq
             HIP_TRY(hipMemcpyAsync(&ND, d_tot + 3, 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             if ((rc = sc.get(&lstart, ND + 1)) || (rc = sc.get(&edge, ND))) return rc;
+            lstart_all = lstart;
             hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(NL)), dim3(256), 0, s, lh, lr, NL, d_tot + 3, lstart);
             hipLaunchKernelGGL(kg::cluster_edge_kernel, dim3(grid_of(ND)), dim3(256), 0, s, lk.keys(), lstart, ND, np, d_cnt,
                                (int64_t)prm->min_shared, (int64_t)prm->min_cover_pct, edge, best, words);
@@ -182,6 +192,49 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const uint8_t *h_seq
         }
     }
     HIP_TRY(hipEventRecord(ev[4], s));
+
+    // ---- the alignment step: the passing links compacted (ascending (m, c): the links' order), aligned, cut; best made again ----
+    unsigned long long *tally = nullptr;
+    AlignTotals atot;
+    uint64_t NP = 0;
+    if (al && ND > 0) {
+        std::vector<uint64_t> h_edge(ND);
+        std::vector<uint32_t> h_lstart(ND + 1);
+        HIP_TRY(hipMemcpyAsync(h_edge.data(), edge, ND * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h_lstart.data(), lstart_all, (ND + 1) * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        std::vector<int32_t> h_pairs, h_shared;
+        std::vector<uint32_t> h_ridx;
+        for (uint64_t r = 0; r < ND; r++) {
+            if (h_edge[r] == kg::kClusterNoEdge) continue;
+            h_pairs.push_back((int32_t)(h_edge[r] >> 32));
+            h_pairs.push_back((int32_t)(uint32_t)h_edge[r]);
+            h_shared.push_back((int32_t)(h_lstart[r + 1] - h_lstart[r]));
+            h_ridx.push_back((uint32_t)r);
+        }
+        NP = h_ridx.size();
+        if (NP > 0) {
+            const int32_t *d_pairs = nullptr;
+            kg::AlignRec *d_aln = nullptr;
+            int32_t *d_shared = nullptr;
+            uint32_t *d_ridx = nullptr;
+            if ((rc = align_run(t, sc, al, d_seq, d_off, offsets, h_pairs.data(), NP, &d_pairs, &d_aln, &atot))) return rc;
+            if ((rc = sc.get(&d_shared, NP)) || (rc = sc.get(&d_ridx, NP)) || (rc = sc.get(&tally, 2)) ||
+                (rc = dalloc_detached(t, &guard.edges, NP * sizeof(kg_family_edge))))
+                return rc;
+            HIP_TRY(hipMemcpyAsync(d_shared, h_shared.data(), NP * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(d_ridx, h_ridx.data(), NP * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemsetAsync(best, 0, (size_t)n_prot * 8, s));
+            HIP_TRY(hipMemsetAsync(words + kg::kClusterEdges, 0, 8, s));
+            HIP_TRY(hipMemsetAsync(tally, 0, 16, s));
+            hipLaunchKernelGGL(kg::align_cut_kernel, dim3(grid_of(NP)), dim3(256), 0, s, d_pairs, d_aln, d_shared, d_ridx, NP,
+                               (int64_t)al->min_ratio_pct, (int)(al->ref == KG_ALIGN_REF_MEMBER), edge, best, words, tally,
+                               (int4 *)guard.edges);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(s));           // (the host vectors above are the copies' sources)
+        }
+    }
+    if (al) HIP_TRY(hipEventRecord(ev[8], s));
 
     // ---- connected components: hook and jump while the flag says something changed ----
     uint32_t rounds = 0;
@@ -203,9 +256,10 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const uint8_t *h_seq
     hipLaunchKernelGGL(kg::cluster_emit_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, np, root, fx, size, best, (int4 *)d_out, words);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev[5], s));
-    unsigned long long hw[kg::kClusterWords] = {};
+    unsigned long long hw[kg::kClusterWords] = {}, ht[2] = {};
     uint64_t families = 0;
     HIP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, s));
+    if (tally) HIP_TRY(hipMemcpyAsync(ht, tally, sizeof ht, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&families, d_tot, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     st.pairs = (int64_t)P;
@@ -219,15 +273,25 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const uint8_t *h_seq
     st.ms_encode = dv.ms_hist + ev.ms(1, 2);
     st.ms_sort = ev.ms(2, 3);
     st.ms_link = ev.ms(3, 4);
-    st.ms_components = ev.ms(4, 5);
+    st.ms_components = ev.ms(al ? 8 : 4, 5);
     st.ms_total = ev.ms(0, 5);
+    if (al) {
+        if ((int64_t)ht[1] != atot.skipped) return fail(KG_ERR_DEVICE, "internal: the device and the host skipped different pairs");
+        set->ast.aligned = (int64_t)NP - atot.skipped;
+        set->ast.cut = (int64_t)ht[0];
+        set->ast.skipped = atot.skipped;
+        set->ast.cells = atot.cells;
+        set->ast.ms_align = ev.ms(4, 8);
+        set->d_edges = guard.edges; guard.edges = nullptr;
+        set->n_edges = (int64_t)NP;
+    }
     set->d_fam = d_out; guard.p = nullptr;
     set->count = n_prot;
     return KG_OK;
 }
 
-int cluster_entry(int device, const kg_cluster_params *prm, const uint8_t *h_seq, const uint8_t *d_seq, const int64_t *offsets,
-                  int64_t n_prot, int64_t max_windows, kg_familyset **out)
+int cluster_entry(int device, const kg_cluster_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq,
+                  const int64_t *offsets, int64_t n_prot, int64_t max_windows, kg_familyset **out)
 {
     if (!out) return fail(KG_ERR_ARG, "null argument");
     *out = nullptr;
@@ -235,6 +299,7 @@ int cluster_entry(int device, const kg_cluster_params *prm, const uint8_t *h_seq
     if (prm->min_shared < 1) return fail(KG_ERR_ARG, "min_shared must be >= 1");
     if (prm->min_cover_pct < 0 || prm->min_cover_pct > 100) return fail(KG_ERR_ARG, "min_cover_pct must be in 0..100");
     if (prm->reserved != 0) return fail(KG_ERR_ARG, "kg_cluster_params.reserved must be 0");
+    if (al) if (int rc = align_check_params(al)) return rc;
     if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
     if (n_prot < 0) return fail(KG_ERR_ARG, "n_prot < 0");
     if (n_prot >= (1ll << 29)) return fail(KG_ERR_LIMIT, "2^29 or more proteins in one call");
@@ -244,6 +309,7 @@ int cluster_entry(int device, const kg_cluster_params *prm, const uint8_t *h_seq
         const int64_t L = offsets[k + 1] - offsets[k];
         if (L < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": offsets decrease (offsets[p+1] < offsets[p])");
         if (L >= (1ll << 31)) return fail(KG_ERR_LIMIT, "protein " + kmer_text(k) + ": 2^31 or more characters");
+        if (al && L >= (int64_t)kg::kAlignMaxLen) return fail(KG_ERR_LIMIT, "protein " + kmer_text(k) + ": 2^24 or more characters");
     }
     const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
     if (seq_bytes && !h_seq && !d_seq) return fail(KG_ERR_ARG, "null sequence");
@@ -253,7 +319,7 @@ int cluster_entry(int device, const kg_cluster_params *prm, const uint8_t *h_seq
     if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
     set->device = device;
     int rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
-    if (!rc) rc = cluster_impl(cs.t, prm, h_seq, d_seq, offsets, n_prot, max_windows, set);
+    if (!rc) rc = cluster_impl(cs.t, prm, al, h_seq, d_seq, offsets, n_prot, max_windows, set);
     cs.t->cache.release_all();                          // scratch goes back to the driver
     if (rc) { std::string keep = g_err; kg_familyset_free(set); g_err = keep; return rc; }
     if (getenv("KG_DEBUG"))
@@ -273,16 +339,42 @@ extern "C" {
 int kg_proteins_cluster(int device, const kg_cluster_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
                         int64_t max_windows, kg_familyset **out)
 {
-    return cluster_entry(device, p, seq, nullptr, offsets, n_prot, max_windows, out);
+    return cluster_entry(device, p, nullptr, seq, nullptr, offsets, n_prot, max_windows, out);
 }
 
 int kg_proteins_cluster_device(int device, const kg_cluster_params *p, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
                                int64_t max_windows, kg_familyset **out)
 {
-    return cluster_entry(device, p, nullptr, d_seq, offsets, n_prot, max_windows, out);
+    return cluster_entry(device, p, nullptr, nullptr, d_seq, offsets, n_prot, max_windows, out);
+}
+
+int kg_proteins_cluster_aligned(int device, const kg_cluster_params *p, const kg_align_params *align, const uint8_t *seq,
+                                const int64_t *offsets, int64_t n_prot, int64_t max_windows, kg_familyset **out)
+{
+    return cluster_entry(device, p, align, seq, nullptr, offsets, n_prot, max_windows, out);
+}
+
+int kg_proteins_cluster_aligned_device(int device, const kg_cluster_params *p, const kg_align_params *align, const uint8_t *d_seq,
+                                       const int64_t *offsets, int64_t n_prot, int64_t max_windows, kg_familyset **out)
+{
+    return cluster_entry(device, p, align, nullptr, d_seq, offsets, n_prot, max_windows, out);
 }
 
 int64_t kg_familyset_count(const kg_familyset *s) { return s ? s->count : 0; }
+
+int64_t kg_familyset_edges_count(const kg_familyset *s) { return s ? s->n_edges : 0; }
+
+int kg_familyset_edges_copy(const kg_familyset *s, int64_t first, int64_t count, kg_family_edge *dst)
+{
+    return copy_records(s, s ? s->device : 0, s ? (const kg_family_edge *)s->d_edges : nullptr, 1, s ? s->n_edges : 0, first, count, dst,
+                        "kg_familyset_edges_copy");
+}
+
+int kg_familyset_align_stats(const kg_familyset *s, kg_align_stats *out)
+{
+    if (s && !s->aligned) return fail(KG_ERR_ARG, "kg_familyset_align_stats: the set was made without alignment");
+    return copy_stats(s, s ? &s->ast : nullptr, out);
+}
 
 int kg_familyset_copy(const kg_familyset *s, int64_t first, int64_t count, kg_family *dst)
 {
@@ -294,9 +386,10 @@ int kg_familyset_stats(const kg_familyset *s, kg_cluster_stats *out) { return co
 void kg_familyset_free(kg_familyset *s)
 {
     if (!s) return;
-    if (s->d_fam) {
+    if (s->d_fam || s->d_edges) {
         (void)hipSetDevice(s->device);
-        (void)hipFree(s->d_fam);
+        if (s->d_fam) (void)hipFree(s->d_fam);
+        if (s->d_edges) (void)hipFree(s->d_edges);
     }
     delete s;
 }

@@ -15,6 +15,7 @@
 #include "kg_merge.hpp"
 #include "kg_derive.hpp"
 #include "kg_cluster.hpp"
+#include "kg_align.hpp"
 #include "kg_assign.hpp"
 #include "kg_regions.hpp"
 #include "kg_orfs.hpp"
@@ -45,6 +46,7 @@
 #include "kg_host_build.hpp"
 #include "kg_host_derive.hpp"
 #include "kg_host_merge.hpp"
+#include "kg_host_align.hpp"
 #include "kg_host_cluster.hpp"
 #include "kg_host_assign.hpp"
 #include "kg_host_regions.hpp"

@@ -735,13 +735,60 @@ def derive_signatures(seq, offsets, fn, otu, min_proteins: int = 2, purity_pct: 
     return SignatureSet(out.value, device)
 
 
+def _align_params(min_ratio_pct: int = 50, ref="longer", gap_open: int = 11, gap_extend: int = 1,
+                  max_cells: int = N.ALIGN_DEFAULT_MAX_CELLS, matrix=None):
+    """-> (KgAlignParams, the matrix array it points into: keep it alive for the call)."""
+    if isinstance(ref, str):
+        if ref not in N.ALIGN_REFS:
+            raise ValueError("ref must be 'longer' or 'member'")
+        ref = N.ALIGN_REFS[ref]
+    mat = None
+    if matrix is not None:
+        mat = np.ascontiguousarray(np.asarray(matrix, dtype=np.int64))
+        if mat.shape != (21, 21) or mat.min() < -128 or mat.max() > 127:
+            raise ValueError("matrix must be 21 x 21 and fit int8")
+        mat = np.ascontiguousarray(mat.astype(np.int8))
+    return N.KgAlignParams(int(min_ratio_pct), int(ref), int(gap_open), int(gap_extend), int(max_cells),
+                           mat.ctypes.data if mat is not None else None, 0), mat
+
+
+def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1, max_cells: int = N.ALIGN_DEFAULT_MAX_CELLS, matrix=None,
+                   device: int = 0, device_ptr: Optional[int] = None) -> np.ndarray:
+    """Local alignment scores of protein pairs, on the GPU (include/kmerguts_hip.h kg_proteins_align states the rule): affine
+    gaps, no traceback, the built-in matrix is BLOSUM62 (align_scores.BLOSUM62); matrix: 21 x 21 in code order.  seq / offsets /
+    device_ptr as for cluster_proteins; pairs: int32[n_pairs][2] of (a, b) protein indices, any order, repeats allowed.
+    -> _native.ALIGNMENT_DTYPE[n_pairs] in pair order (status 1 and score -1: more than max_cells cells, not aligned)."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_prot + 1]")
+    n = off.size - 1
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if pr.size and (pr.min() < -2 ** 31 or pr.max() >= 2 ** 31):
+        raise ValueError("pair indices must fit in 32 bits")
+    pr = np.ascontiguousarray(pr.astype(np.int32))
+    p, _keep = _align_params(gap_open=gap_open, gap_extend=gap_extend, max_cells=max_cells, matrix=matrix)
+    out = np.zeros(len(pr), dtype=N.ALIGNMENT_DTYPE)
+    lib = N.load()
+    pp, op = (pr.ctypes.data if len(pr) else None), (out.ctypes.data if len(pr) else None)
+    if device_ptr is not None:
+        N.check(lib.kg_proteins_align_device(device, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, pp, len(pr), op))
+    else:
+        arr = _seq_bytes(seq, off)
+        N.check(lib.kg_proteins_align(device, C.byref(p), arr.ctypes.data if arr.size else None, off.ctypes.data, n, pp, len(pr), op))
+    return out
+
+
 def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20, max_windows: int = 0, device: int = 0,
-                     device_ptr: Optional[int] = None):
+                     device_ptr: Optional[int] = None, align: Optional[dict] = None):
     """Proteins -> families by shared 8-mers, on the GPU (include/kmerguts_hip.h kg_proteins_cluster states the rule): a link
     from every protein of a k-mer to the k-mer's longest protein, an edge where a link's shared k-mers pass min_shared and
     min_cover_pct of the member's distinct k-mers, a family per connected component.  seq: bytes / uint8 ndarray of the
     concatenated protein characters, or None when device_ptr gives their address in HBM; offsets: int64[n_prot + 1].  The
     defaults 5 and 20 are this project's choice; max_windows = 0 sizes the one pass from free device memory.
+    align: None, or a dict of min_ratio_pct (50), ref ("longer" | "member"), gap_open (11), gap_extend (1), max_cells (2^26),
+    matrix (None: BLOSUM62): every link that passed the two tests is aligned (kg_proteins_cluster_aligned) and stays an edge
+    only if 100 * score >= min_ratio_pct * ref; the statistics then also hold "edge_records" (_native.FAMILY_EDGE_DTYPE, one per
+    such link in (member, centre) order) and "align" (aligned, cut, skipped, cells, ms_align).
     -> (numpy records of _native.FAMILY_DTYPE in protein order, the call's statistics)."""
     off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
     if off.ndim != 1 or off.size < 1:
@@ -750,7 +797,16 @@ def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20,
     p = N.KgClusterParams(int(min_shared), int(min_cover_pct), 0)
     h = C.c_void_p()
     lib = N.load()
-    if device_ptr is not None:
+    if align is not None:
+        ap, _keep = _align_params(**align)
+        if device_ptr is not None:
+            N.check(lib.kg_proteins_cluster_aligned_device(device, C.byref(p), C.byref(ap), C.c_void_p(device_ptr), off.ctypes.data, n,
+                                                           int(max_windows), C.byref(h)))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_proteins_cluster_aligned(device, C.byref(p), C.byref(ap), arr.ctypes.data if arr.size else None, off.ctypes.data,
+                                                    n, int(max_windows), C.byref(h)))
+    elif device_ptr is not None:
         N.check(lib.kg_proteins_cluster_device(device, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, int(max_windows), C.byref(h)))
     else:
         arr = _seq_bytes(seq, off)
@@ -759,7 +815,13 @@ def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20,
     try:
         st = N.KgClusterStats()
         N.check(lib.kg_familyset_stats(h, C.byref(st)))
-        return _copy_records(lib.kg_familyset_copy, h, int(lib.kg_familyset_count(h)), N.FAMILY_DTYPE), st.as_dict()
+        stats = st.as_dict()
+        if align is not None:
+            ast = N.KgAlignStats()
+            N.check(lib.kg_familyset_align_stats(h, C.byref(ast)))
+            stats["align"] = ast.as_dict()
+            stats["edge_records"] = _copy_records(lib.kg_familyset_edges_copy, h, int(lib.kg_familyset_edges_count(h)), N.FAMILY_EDGE_DTYPE)
+        return _copy_records(lib.kg_familyset_copy, h, int(lib.kg_familyset_count(h)), N.FAMILY_DTYPE), stats
     finally:
         lib.kg_familyset_free(h)
 
