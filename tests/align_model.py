@@ -136,14 +136,15 @@ def links(seq: bytes, offsets):
 
 def cluster_aligned_model(seq: bytes, offsets, min_shared: int = 5, min_cover_pct: int = 20, min_ratio_pct: int = MIN_RATIO_PCT,
                           ref="longer", gap_open: int = GAP_OPEN, gap_extend: int = GAP_EXTEND,
-                          max_cells: int = N.ALIGN_DEFAULT_MAX_CELLS, matrix=None):
-    """-> (FAMILY_DTYPE records, counts, FAMILY_EDGE_DTYPE records, {aligned, cut, skipped, cells})."""
+                          max_cells: int = N.ALIGN_DEFAULT_MAX_CELLS, matrix=None, sw=sw_numpy):
+    """-> (FAMILY_DTYPE records, counts, FAMILY_EDGE_DTYPE records, {aligned, cut, skipped, cells}).  sw: the form of the
+    recurrence that aligns (a caller that asks for the same pairs many times passes a memoised sw_numpy)."""
     S = S62 if matrix is None else np.asarray(matrix, dtype=np.int64)
     ref = N.ALIGN_REFS.get(ref, ref)
     n = len(offsets) - 1
     s_of, d, counts = links(seq, offsets)
     passing = [(m, c, s) for (m, c), s in sorted(s_of.items()) if s >= min_shared and 100 * s >= min_cover_pct * d[m]]
-    aln = align_model(seq, offsets, [(m, c) for m, c, _ in passing], S, gap_open, gap_extend, max_cells)
+    aln = align_model(seq, offsets, [(m, c) for m, c, _ in passing], S, gap_open, gap_extend, max_cells, sw)
     edges = np.zeros(len(passing), dtype=N.FAMILY_EDGE_DTYPE)
     parent = list(range(n))
 
