@@ -522,6 +522,93 @@ int64_t kg_familyset_edges_count(const kg_familyset *s);
 int kg_familyset_edges_copy(const kg_familyset *s, int64_t first, int64_t count, kg_family_edge *dst);
 int kg_familyset_align_stats(const kg_familyset *s, kg_align_stats *out);
 
+/* ---- searching proteins against a database: 8-mer join, top candidates, alignment (kernels: kg_search.hpp) ----
+ *
+ * The reference only reads signatures; this rule is the project's own.  It answers which known protein a protein is like, and
+ * how much: the prefilter of a protein search (the targets that share exact 8-mers with a query, counted and ranked) in front
+ * of the alignment above.  Integers only.
+ *   Input: one batch of n_prot proteins as for kg_proteins_cluster: seq, offsets[n_prot + 1] (host, non-decreasing), and n_db
+ *   with 0 <= n_db <= n_prot.  Proteins [0, n_db) are the database, the targets; proteins [n_db, n_prot) are the queries, and
+ *   query number q is batch index n_db + q; n_q = n_prot - n_db.
+ *   Windows: exactly the derive windows: toAminoAcidOff codes, positions i in [0, len_p - 8), windows with a code >= 20 skipped;
+ *   the device encode is the scan's own.
+ *   Sets.  D(v) is the set of distinct targets that have a window equal to v, Q(v) the set of distinct queries.
+ *   Masking.  A k-mer v with |D(v)| > max_db_per_kmer takes no part: it is a repeat or a low-complexity k-mer.  It is counted
+ *   in kmers_masked (whether or not a query has it).  max_db_per_kmer >= 1, default 256: this project's choice; it bounds the join.
+ *   Shared count.  s(q, d) is the number of distinct unmasked k-mers v with q in Q(v) and d in D(v).
+ *   Candidates.  The candidates of q are the targets d with s(q, d) >= min_shared (min_shared >= 1, default 2), ordered by
+ *   larger s, then smaller d.  The first max_cand of them are aligned (1 <= max_cand <= 64, default 8).
+ *   Alignment: the rule above with the same kg_align_params (matrix, gaps, max_cells, min_ratio_pct, ref); a is the query and b
+ *   the target.  A pair over max_cells is `skipped`.  An aligned pair is a `hit` iff score >= 1 and
+ *   100 * score >= min_ratio_pct * ref, computed in int64; ref = max(self(q), self(d)) with KG_ALIGN_REF_LONGER, ref = self(q)
+ *   with KG_ALIGN_REF_MEMBER (the member is the query); otherwise the pair is `below`.
+ *   Output order within a query: not-skipped before skipped, then larger score, then larger s, then smaller target.
+ *   Output: one 40-byte kg_search_hit per aligned or skipped candidate, in (query, rank) order, rank counting from 0 within the
+ *   query, and hit_start[n_q + 1]: query q's records are [hit_start[q], hit_start[q + 1]).
+ * Nothing depends on launch geometry, scheduling or where a tile border falls.  A query's records depend only on the query, the
+ * database and the parameters, not on which other queries are in the batch (`query` aside, which is its number in the batch).
+ * The order of the targets matters only under ties: equal s at the max_cand cut, and equal (score, s) in the output order.
+ * One pass.  A call whose valid windows do not fit the device returns KG_ERR_LIMIT and says so, as kg_proteins_cluster does
+ * (max_windows = 0: sized from free device memory).  join_pairs is the sum over the unmasked k-mers of |D(v)| * |Q(v)|: the
+ * items the join writes.  A call whose join_pairs exceed the capacity returns KG_ERR_LIMIT; the message gives the count and
+ * names max_db_per_kmer as the lever.  max_pairs = 0: the capacity is sized from free device memory (about 112 bytes per join
+ * pair, at most 2^32 - 2^22); any other value caps it.
+ * Limits (KG_ERR_LIMIT): n_prot < 2^29, len_p < 2^24, fewer than 2^31 window blocks of 64 windows.  KG_ERR_ARG: decreasing
+ * offsets (the message names the first offending protein), bad parameters (the message names the first), n_db outside
+ * [0, n_prot], max_windows < 0, max_pairs < 0, null pointers (align must not be null).  KG_ERR_NOMEM.  KG_TEST_FAIL_ALLOC
+ * applies to every device allocation of the call; everything but the result goes back to the driver before the call returns.
+ * Zero targets, zero queries, zero proteins and proteins without a window are valid.
+ * kg_proteins_search reads a host sequence, uploaded through pinned pieces; kg_proteins_search_device a device sequence
+ * (complete before the call: the device is synchronised once); offsets is a host array in both. */
+typedef struct kg_search_params { int32_t min_shared; int32_t max_cand; int32_t max_db_per_kmer; int32_t reserved; } kg_search_params;
+typedef struct kg_search_hit {   /* 40 B */
+    int32_t query;         /* q: the protein's batch index is n_db + q                  */
+    int32_t target;        /* d                                                         */
+    int32_t shared;        /* s(q, d)                                                   */
+    int32_t score;         /* -1 when skipped                                           */
+    int32_t self_query;
+    int32_t self_target;
+    int32_t end_query;     /* 0-based, -1 when score <= 0                               */
+    int32_t end_target;
+    int32_t status;        /* 0 hit, 1 below, 2 skipped                                 */
+    int32_t rank;          /* the record's place within its query, from 0               */
+} kg_search_hit;
+typedef struct kg_search_stats {
+    int64_t targets;
+    int64_t queries;
+    int64_t valid_windows;
+    int64_t pairs;         /* distinct (k-mer, protein) pairs of the whole batch        */
+    int64_t kmers;         /* distinct k-mers of the whole batch                        */
+    int64_t kmers_joined;  /* unmasked k-mers with a query and a target                 */
+    int64_t kmers_masked;  /* k-mers with |D(v)| > max_db_per_kmer                      */
+    int64_t join_pairs;    /* sum of |D(v)| * |Q(v)| over the joined k-mers             */
+    int64_t candidates;    /* (q, d) with s >= min_shared, before the max_cand cut      */
+    int64_t aligned;       /* records that were aligned                                 */
+    int64_t hits;
+    int64_t skipped;
+    int64_t queries_hit;   /* queries whose rank-0 record is a hit                      */
+    int64_t cells;         /* n * m summed over the aligned pairs                       */
+    float   ms_encode;     /* the histogram + the encode / emit kernel                  */
+    float   ms_sort;       /* the window sort                                           */
+    float   ms_join;       /* collapse, runs, the join, its sort, the counts, the top candidates */
+    float   ms_align;      /* the candidates to the host, the alignment kernels, the order */
+    float   ms_total;      /* the call, after the upload of the sequence, to its last kernel */
+    int32_t reserved;
+} kg_search_stats;
+typedef struct kg_hitset kg_hitset;
+int kg_proteins_search(int device, const kg_search_params *p, const kg_align_params *align, const uint8_t *seq, const int64_t *offsets,
+                       int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset **out);
+int kg_proteins_search_device(int device, const kg_search_params *p, const kg_align_params *align, const uint8_t *d_seq,
+                              const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs,
+                              kg_hitset **out);
+int64_t kg_hitset_count(const kg_hitset *s);
+/* records [first, first + count) into dst (host or device memory) */
+int kg_hitset_copy(const kg_hitset *s, int64_t first, int64_t count, kg_search_hit *dst);
+/* hit_start: all n_q + 1 entries */
+int kg_hitset_starts_copy(const kg_hitset *s, int64_t *dst);
+int kg_hitset_stats(const kg_hitset *s, kg_search_stats *out);
+void kg_hitset_free(kg_hitset *s);
+
 /* ---- assigning functions: the CALL records of an -a scan -> one function per protein (kernels: kg_assign.hpp) ----
  *
  * The reference stops at the CALL lines (KGJ:398-404, 526-536); this rule is the project's own.

@@ -398,6 +398,36 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_search_params (kg_proteins_search*); this project's defaults: 2, 8 (at most 64), 256 and 0. */
+    class KgSearchParams extends Structure {
+        public int min_shared, max_cand, max_db_per_kmer, reserved;
+        public KgSearchParams() {
+            setFieldOrder(new String[] {"min_shared", "max_cand", "max_db_per_kmer", "reserved"});
+        }
+    }
+
+    /** struct kg_search_hit (40 B): one aligned or skipped candidate of a query; status 0 hit, 1 below, 2 skipped; rank from 0. */
+    class KgSearchHit extends Structure {
+        public int query, target, shared, score, self_query, self_target, end_query, end_target, status, rank;
+        public KgSearchHit() {
+            setFieldOrder(new String[] {"query", "target", "shared", "score", "self_query", "self_target", "end_query", "end_target",
+                    "status", "rank"});
+        }
+    }
+
+    /** struct kg_search_stats. */
+    class KgSearchStats extends Structure {
+        public long targets, queries, valid_windows, pairs, kmers, kmers_joined, kmers_masked, join_pairs, candidates, aligned, hits,
+                skipped, queries_hit, cells;
+        public float ms_encode, ms_sort, ms_join, ms_align, ms_total;
+        public int reserved;
+        public KgSearchStats() {
+            setFieldOrder(new String[] {"targets", "queries", "valid_windows", "pairs", "kmers", "kmers_joined", "kmers_masked",
+                    "join_pairs", "candidates", "aligned", "hits", "skipped", "queries_hit", "cells", "ms_encode", "ms_sort", "ms_join",
+                    "ms_align", "ms_total", "reserved"});
+        }
+    }
+
     /** struct kg_merge_params (kg_table_merge_signatures*): on_conflict = KG_MERGE_KEEP (0), KG_MERGE_REPLACE (1) or KG_MERGE_DROP (2). */
     class KgMergeParams extends Structure {
         public int on_conflict, reserved;
@@ -462,6 +492,17 @@ public interface KmerGutsHip extends Library {
     long kg_familyset_edges_count(Pointer set);
     int kg_familyset_edges_copy(Pointer set, long first, long count, Pointer dst);   // kg_family_edge[count], 32 B each, (member, centre) order
     int kg_familyset_align_stats(Pointer set, KgAlignStats out);
+    /** proteins [nDb, nProt) searched against proteins [0, nDb): shared 8-mers, the best maxCand targets per query aligned; align must
+     *  not be null; maxWindows = 0 and maxPairs = 0 size the one pass and the join from free device memory */
+    int kg_proteins_search(int device, KgSearchParams params, KgAlignParams align, byte[] seq, long[] offsets, long nProt, long nDb,
+                           long maxWindows, long maxPairs, PointerByReference out);
+    int kg_proteins_search_device(int device, KgSearchParams params, KgAlignParams align, Pointer dSeq, long[] offsets, long nProt, long nDb,
+                                  long maxWindows, long maxPairs, PointerByReference out);
+    long kg_hitset_count(Pointer set);
+    int kg_hitset_copy(Pointer set, long first, long count, Pointer dst);   // kg_search_hit[count], 40 B each, (query, rank) order
+    int kg_hitset_starts_copy(Pointer set, long[] dst);                     // hit_start[nQ + 1]
+    int kg_hitset_stats(Pointer set, KgSearchStats out);
+    void kg_hitset_free(Pointer set);
     Pointer kg_table_device_entries(Pointer table);
     long kg_table_records(Pointer table);
     int kg_table_info(Pointer table, long[] numSigs, long[] entrySize, long[] version, long[] occupied);

@@ -39,6 +39,8 @@ EXPORTS = (
     "kg_familyset_free",
     "kg_proteins_align", "kg_proteins_align_device", "kg_proteins_cluster_aligned", "kg_proteins_cluster_aligned_device",
     "kg_familyset_edges_count", "kg_familyset_edges_copy", "kg_familyset_align_stats",
+    "kg_proteins_search", "kg_proteins_search_device", "kg_hitset_count", "kg_hitset_copy", "kg_hitset_starts_copy",
+    "kg_hitset_stats", "kg_hitset_free",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
@@ -140,6 +142,13 @@ ALIGN_DEFAULT_MAX_CELLS = 1 << 26
 ALIGN_ALIGNED, ALIGN_SKIPPED = 0, 1                     # kg_alignment.status
 EDGE_KEPT, EDGE_CUT, EDGE_SKIPPED = 0, 1, 2             # kg_family_edge.status
 ALIGN_LDS_COLS = 1024       # kg_align.hpp kAlignLdsCols: a longer second protein carries its stripes in device memory (tests aim at it)
+# struct kg_search_hit (kg_proteins_search*): one aligned or skipped candidate of a query
+SEARCH_HIT_DTYPE = np.dtype([("query", "<i4"), ("target", "<i4"), ("shared", "<i4"), ("score", "<i4"), ("self_query", "<i4"),
+                             ("self_target", "<i4"), ("end_query", "<i4"), ("end_target", "<i4"), ("status", "<i4"), ("rank", "<i4")])
+assert SEARCH_HIT_DTYPE.itemsize == 40
+SEARCH_HIT, SEARCH_BELOW, SEARCH_SKIPPED = 0, 1, 2      # kg_search_hit.status
+SEARCH_TILE = 2048          # kg_search.hpp kSearchTile: the join items of one workgroup (tests aim at its edges) ...
+SEARCH_MAX_CAND = 64        # ... and kSearchMaxCand: the largest max_cand, one lane per candidate
 assert HIT_DTYPE.itemsize == 24 and CALL_DTYPE.itemsize == 24 and OTU_DTYPE.itemsize == 44
 
 
@@ -355,6 +364,23 @@ class KgAlignStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class KgSearchParams(C.Structure):
+    """struct kg_search_params (kg_proteins_search*)."""
+    _fields_ = [("min_shared", C.c_int32), ("max_cand", C.c_int32), ("max_db_per_kmer", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgSearchStats(C.Structure):
+    """struct kg_search_stats."""
+    _fields_ = [("targets", C.c_int64), ("queries", C.c_int64), ("valid_windows", C.c_int64), ("pairs", C.c_int64),
+                ("kmers", C.c_int64), ("kmers_joined", C.c_int64), ("kmers_masked", C.c_int64), ("join_pairs", C.c_int64),
+                ("candidates", C.c_int64), ("aligned", C.c_int64), ("hits", C.c_int64), ("skipped", C.c_int64),
+                ("queries_hit", C.c_int64), ("cells", C.c_int64), ("ms_encode", C.c_float), ("ms_sort", C.c_float),
+                ("ms_join", C.c_float), ("ms_align", C.c_float), ("ms_total", C.c_float), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 class KgVoteParams(C.Structure):
     """struct kg_vote_params (kg_result_otu_votes / kg_otu_votes_hits)."""
     _fields_ = [("min_votes", C.c_int32), ("min_share_pct", C.c_int32), ("min_calls", C.c_int32), ("reserved", C.c_int32)]
@@ -499,23 +525,27 @@ def load() -> C.CDLL:
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
                                        C.POINTER(vp)]
     lib.kg_familyset_align_stats.argtypes = [vp, C.POINTER(KgAlignStats)]
+    for name in ("kg_proteins_search", "kg_proteins_search_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgSearchParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
+                                       C.c_int64, C.c_int64, C.POINTER(vp)]
+    lib.kg_hitset_stats.argtypes = [vp, C.POINTER(KgSearchStats)]
     # the sets' accessors, by signature: (set) -> count, (set) -> device address, (set, first, count, dst), (set, dst), (set)
-    for name in ("kg_sigset_count", "kg_familyset_count", "kg_familyset_edges_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
+    for name in ("kg_sigset_count", "kg_familyset_count", "kg_familyset_edges_count", "kg_hitset_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
                  "kg_selectset_count", "kg_voteset_count", "kg_voteset_bins", "kg_compset_rows", "kg_compset_models"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = C.c_int64
     for name in ("kg_sigset_device", "kg_regionset_device", "kg_orfset_device", "kg_selectset_device"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = vp
-    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
+    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_hitset_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
                  "kg_orfset_junctions_copy", "kg_orfset_coding_scores", "kg_orfset_start_shifts", "kg_selectset_copy",
                  "kg_voteset_copy_votes", "kg_voteset_copy_classes", "kg_voteset_copy_bins", "kg_compset_copy_classes",
                  "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores"):
         getattr(lib, name).argtypes = [vp, C.c_int64, C.c_int64, vp]
     for name in ("kg_regionset_seq_start", "kg_orfset_prot_start", "kg_orfset_junctions_start", "kg_voteset_seq_start",
-                 "kg_compset_background"):
+                 "kg_compset_background", "kg_hitset_starts_copy"):
         getattr(lib, name).argtypes = [vp, vp]
-    for name in ("kg_sigset_free", "kg_familyset_free", "kg_regionset_free", "kg_orfset_free", "kg_selectset_free",
+    for name in ("kg_sigset_free", "kg_familyset_free", "kg_hitset_free", "kg_regionset_free", "kg_orfset_free", "kg_selectset_free",
                  "kg_voteset_free", "kg_compset_free"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = None

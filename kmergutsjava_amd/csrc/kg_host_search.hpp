@@ -1,0 +1,392 @@
+// kg_host_search.hpp -- kg_proteins_search / kg_proteins_search_device: queries against a database of proteins by shared 8-mers,
+// the best candidates aligned (kernels: kg_search.hpp; the window encode, the sort and the collapse are the derive call's,
+// kg_derive.hpp; the alignment is align_run of kg_host_align.hpp, unchanged).
+// Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_cluster.hpp (it uses the derive call's block counts,
+// its histogram and its bytes-per-window figure as the cluster call does) and kg_host_align.hpp.
+#pragma once
+
+struct kg_hitset {
+    int device = 0;
+    uint8_t *d_block = nullptr;         // hit_start[n_q + 1] (int64), then count * 40 bytes (hipMalloc, owned)
+    int64_t count = 0, n_q = 0;
+    kg_search_stats st = {};
+    const int64_t *starts() const { return (const int64_t *)d_block; }
+    const kg_search_hit *hits() const { return (const kg_search_hit *)(d_block + ((size_t)n_q + 1) * 8); }
+};
+
+static_assert(sizeof(kg_search_hit) == 40 && sizeof(kg_search_params) == 16 && sizeof(kg_search_stats) == 136,
+              "record layouts of include/kmerguts_hip.h");
+
+namespace {
+
+constexpr uint64_t kSearchBytesPerPair = 112;                         // device bytes one join pair needs, at most
+constexpr uint64_t kSearchPairsMax = (1ull << 32) - (1ull << 22);     // the 32-bit scans and indices of the join
+
+int search_impl(kg_table *t, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq_in,
+                const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset *set)
+{
+    kg_search_stats &st = set->st;
+    const int64_t n_q = n_prot - n_db;
+    set->n_q = n_q;
+    st.targets = n_db;
+    st.queries = n_q;
+    std::vector<uint32_t> ibase;
+    uint64_t nblocks = 0, windows = 0;
+    int rc;
+    if ((rc = derive_block_bases(offsets, n_prot, ibase, &nblocks, &windows))) return rc;
+    const uint32_t b = bits_for((uint64_t)n_prot), np = (uint32_t)n_prot, db = bits_for((uint64_t)n_db), ndb = (uint32_t)n_db;
+    hipStream_t s = t->stream;
+
+    Scratch sc(t);
+    Events<8> ev;
+    if ((rc = ev.create())) return rc;
+    const uint8_t *d_seq = d_seq_in;
+    const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
+    if (h_seq && seq_bytes) {
+        uint8_t *d = nullptr;
+        if ((rc = sc.get(&d, seq_bytes))) return rc;
+        if ((rc = upload_pinned(t, h_seq, seq_bytes, d))) return rc;
+        d_seq = d;
+    }
+    HIP_TRY(hipEventRecord(ev[0], s));
+    unsigned long long *words = nullptr;
+    uint64_t *d_tot = nullptr;
+    if ((rc = sc.get(&words, kg::kSearchWords)) || (rc = sc.get(&d_tot, 8))) return rc;
+    HIP_TRY(hipMemsetAsync(words, 0, kg::kSearchWords * 8, s));
+    struct OutGuard {                   // the result block: detached, so the cache does not give it back on a failure
+        uint8_t *p;
+        ~OutGuard() { if (p) (void)hipFree(p); }
+    } guard{nullptr};
+
+    uint64_t n = 0, P = 0, K = 0, R = 0, J = 0, ND = 0, NC = 0, NK = 0;
+    Deriver dv{t, sc, d_seq};
+    int64_t *d_off = nullptr;
+    int32_t *d_kept_pairs = nullptr, *d_shared = nullptr;
+    // the times of a call that ends early: every stage it did not reach is empty
+    for (int k = 1; k <= 4; k++) HIP_TRY(hipEventRecord(ev[k], s));
+
+    if (n_prot > 0) {
+        // ---- per-protein arrays, the window blocks ----
+        dv.ev[0] = ev[6]; dv.ev[1] = ev[7];
+        dv.n_blocks = (uint32_t)nblocks;
+        uint32_t *d_ibase = nullptr, *rank_of = nullptr;
+        if ((rc = sc.get(&dv.d_bins, kg::kDeriveBins)) || (rc = sc.get(&d_off, (size_t)n_prot + 1)) || (rc = sc.get(&d_ibase, (size_t)n_prot + 1)) ||
+            (rc = sc.get(&rank_of, (size_t)n_prot)))
+            return rc;
+        if (nblocks && (rc = sc.get(&dv.d_blocks, nblocks))) return rc;
+        HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)n_prot + 1) * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_ibase, ibase.data(), ((size_t)n_prot + 1) * 4, hipMemcpyHostToDevice, s));
+        if (nblocks) hipLaunchKernelGGL(kg::build_blocks_kernel, dim3(grid_of(nblocks)), dim3(256), 0, s, d_off, d_ibase, np, (uint32_t)nblocks, dv.d_blocks);
+        hipLaunchKernelGGL(kg::search_init_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, np, rank_of);
+        HIP_TRY(hipGetLastError());
+
+        // ---- the valid windows, and whether they fit: one pass ----
+        const uint64_t space = (uint64_t)KG_MAX_ENCODED;
+        std::vector<unsigned long long> bins;
+        if ((rc = dv.histogram(0, space, Deriver::shift_for(space), bins))) return rc;
+        for (auto c : bins) n += c;
+        st.valid_windows = (int64_t)n;
+        {
+            uint64_t cap = (uint64_t)max_windows;
+            if (cap == 0) {
+                size_t free_b = 0, total_b = 0;
+                HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+                cap = std::max<uint64_t>(1u << 20, (uint64_t)(free_b * 0.8) / kDeriveBytesPerWindow);
+            }
+            cap = std::min(cap, kDerivePassMax);
+            if (n > cap)
+                return fail(KG_ERR_LIMIT, kmer_text((int64_t)n) + " valid windows do not fit the one pass of this call, which holds " +
+                                              kmer_text((int64_t)cap) + (max_windows ? " (max_windows)" : " (sized from free device memory)"));
+        }
+        for (int k = 1; k <= 4; k++) HIP_TRY(hipEventRecord(ev[k], s));
+
+        if (n > 0) {
+            // ---- encode and emit (key = v << b | p), sort, collapse to the distinct pairs: the derive call's kernels ----
+            SortPairs sp;
+            unsigned long long *d_cur = nullptr;
+            if ((rc = sp.alloc(sc, n)) || (rc = sc.get(&d_cur, 1))) return rc;
+            HIP_TRY(hipMemsetAsync(d_cur, 0, 8, s));
+            HIP_TRY(hipEventRecord(ev[1], s));
+            {
+                const uint32_t grid = std::min<uint32_t>((dv.n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16);
+                hipLaunchKernelGGL(kg::derive_windows_kernel<true>, dim3(std::max(grid, 1u)), dim3(kg::kDeriveThreads), 0, s, d_seq, dv.d_blocks,
+                                   dv.n_blocks, (uint64_t)0, space, 0u, nullptr, rank_of, b, sp.keys(), sp.vals(), d_cur, n);
+                HIP_TRY(hipGetLastError());
+            }
+            HIP_TRY(hipEventRecord(ev[2], s));
+            if ((rc = sp.sort(t, sc, n, bit_width(space - 1) + b))) return rc;
+            HIP_TRY(hipEventRecord(ev[3], s));
+            const uint64_t nb = n / kg::kScanChunk + 2;
+            uint32_t *flags = nullptr, *pidx = nullptr;
+            uint64_t *partial = nullptr;
+            if ((rc = sc.get(&flags, n + 1)) || (rc = sc.get(&pidx, n + 1)) || (rc = sc.get(&partial, nb + 1))) return rc;
+            hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(n)), dim3(256), 0, s, sp.keys(), n, flags);
+            HIP_TRY(hipGetLastError());
+            if ((rc = prefix_sum(t, flags, n, pidx, partial, d_tot + 0))) return rc;
+            unsigned long long host_cur = 0;
+            HIP_TRY(hipMemcpyAsync(&host_cur, d_cur, 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(&P, d_tot, 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (host_cur != n) return fail(KG_ERR_DEVICE, "internal: the emit pass wrote a different number of windows than the histogram counted");
+            uint64_t *pk = nullptr;
+            uint32_t *pv = nullptr;
+            if ((rc = sc.get(&pk, P)) || (rc = sc.get(&pv, P))) return rc;
+            HIP_TRY(hipMemsetAsync(pv, 0, P * 4, s));
+            hipLaunchKernelGGL(kg::derive_collapse_kernel, dim3(grid_of((n + kg::kDeriveChunk - 1) / kg::kDeriveChunk)), dim3(256), 0, s, sp.keys(),
+                               sp.vals(), n, pidx, pk, pv);
+            HIP_TRY(hipGetLastError());
+
+            // ---- the k-mer runs, their split at n_db and their weights (flags / pidx / partial are reused: K <= P <= n) ----
+            uint32_t *kh = flags, *kx = pidx, *kstart = nullptr, *nd = nullptr, *w = nullptr, *wf = pv, *wpos = nullptr;
+            hipLaunchKernelGGL(kg::search_kmer_heads_kernel, dim3(grid_of(P)), dim3(256), 0, s, pk, P, b, kh);
+            HIP_TRY(hipGetLastError());
+            if ((rc = prefix_sum(t, kh, P, kx, partial, d_tot + 1))) return rc;
+            HIP_TRY(hipMemcpyAsync(&K, d_tot + 1, 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if ((rc = sc.get(&kstart, K + 1)) || (rc = sc.get(&nd, K)) || (rc = sc.get(&w, K)) || (rc = sc.get(&wpos, K))) return rc;
+            hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(P)), dim3(256), 0, s, kh, kx, P, d_tot + 1, kstart);
+            hipLaunchKernelGGL(kg::search_run_weights_kernel, dim3(grid_of(K)), dim3(256), 0, s, pk, kstart, K, b, ndb,
+                               (uint32_t)prm->max_db_per_kmer, nd, w, wf, words);
+            HIP_TRY(hipGetLastError());
+            if ((rc = prefix_sum(t, wf, K, wpos, partial, d_tot + 2))) return rc;
+            unsigned long long hw[3] = {};
+            HIP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(&R, d_tot + 2, 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            J = hw[kg::kSearchJoinPairs];
+            st.kmers_joined = (int64_t)hw[kg::kSearchJoined];
+            st.kmers_masked = (int64_t)hw[kg::kSearchMasked];
+            if (R != hw[kg::kSearchJoined]) return fail(KG_ERR_DEVICE, "internal: the listed runs and the joined k-mers differ");
+
+            // ---- whether the join fits: J is the 64-bit sum, exact whatever the stored weights saturate to ----
+            {
+                uint64_t cap = (uint64_t)max_pairs;
+                if (cap == 0) {
+                    size_t free_b = 0, total_b = 0;
+                    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+                    cap = std::max<uint64_t>(1u << 20, (uint64_t)(free_b * 0.8) / kSearchBytesPerPair);
+                }
+                cap = std::min(cap, kSearchPairsMax);
+                if (J > cap)
+                    return fail(KG_ERR_LIMIT, kmer_text((int64_t)J) + " join pairs do not fit this call, which holds " + kmer_text((int64_t)cap) +
+                                                  (max_pairs ? " (max_pairs)" : " (sized from free device memory)") +
+                                                  "; a smaller max_db_per_kmer masks more of the frequent k-mers");
+            }
+            if (J > 0) {
+                // ---- the runs of weight >= 1, the prefix sum of their weights (J < 2^32: no stored weight is saturated) ----
+                uint32_t *cstart = nullptr, *cnd = nullptr, *cw = nullptr, *wx = nullptr;
+                uint64_t *jpartial = nullptr;
+                if ((rc = sc.get(&cstart, R)) || (rc = sc.get(&cnd, R)) || (rc = sc.get(&cw, R + 1)) || (rc = sc.get(&wx, R + 1)) ||
+                    (rc = sc.get(&jpartial, J / kg::kScanChunk + 3)))
+                    return rc;
+                HIP_TRY(hipMemsetAsync(cw + R, 0, 4, s));
+                hipLaunchKernelGGL(kg::search_run_compact_kernel, dim3(grid_of(K)), dim3(256), 0, s, kstart, nd, w, wf, wpos, K, R, cstart, cnd, cw);
+                HIP_TRY(hipGetLastError());
+                if ((rc = prefix_sum(t, cw, R + 1, wx, partial, d_tot + 3))) return rc;
+                // ---- the join: one key per (query, target) of every listed run ----
+                SortPairs jp;
+                if ((rc = jp.alloc(sc, J))) return rc;
+                hipLaunchKernelGGL(kg::search_join_kernel, dim3(grid_of(J, kg::kSearchTile)), dim3(kg::kSearchThreads), 0, s, pk, wx, cstart, cnd,
+                                   (uint32_t)R, (uint32_t)J, b, ndb, db, jp.keys(), jp.vals());
+                HIP_TRY(hipGetLastError());
+                uint64_t wtot = 0;
+                HIP_TRY(hipMemcpyAsync(&wtot, d_tot + 3, 8, hipMemcpyDeviceToHost, s));
+                if ((rc = jp.sort(t, sc, J, bits_for((uint64_t)n_q) + db))) return rc;
+                // ---- runs of equal keys = distinct (q, d), run length = s(q, d) ----
+                uint32_t *lh = nullptr, *lr = nullptr, *lstart = nullptr, *cf = nullptr, *cx = nullptr;
+                if ((rc = sc.get(&lh, J)) || (rc = sc.get(&lr, J))) return rc;
+                hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(J)), dim3(256), 0, s, jp.keys(), J, lh);
+                HIP_TRY(hipGetLastError());
+                if ((rc = prefix_sum(t, lh, J, lr, jpartial, d_tot + 4))) return rc;
+                HIP_TRY(hipMemcpyAsync(&ND, d_tot + 4, 8, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                if (wtot != J) return fail(KG_ERR_DEVICE, "internal: the prefix sum of the weights and their 64-bit sum differ");
+                if ((rc = sc.get(&lstart, ND + 1))) return rc;
+                cf = lh; cx = lr;                                   // (the heads and their scan are free behind the starts: ND <= J)
+                hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(J)), dim3(256), 0, s, lh, lr, J, d_tot + 4, lstart);
+                hipLaunchKernelGGL(kg::search_cand_flags_kernel, dim3(grid_of(ND)), dim3(256), 0, s, lstart, ND, (uint32_t)prm->min_shared, cf, words);
+                HIP_TRY(hipGetLastError());
+                if ((rc = prefix_sum(t, cf, ND, cx, jpartial, d_tot + 5))) return rc;
+                unsigned long long smax = 0;
+                HIP_TRY(hipMemcpyAsync(&NC, d_tot + 5, 8, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpyAsync(&smax, words + kg::kSearchSmax, 8, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                if (NC > 0) {
+                    // ---- the candidates in (q, d) order, then stably by (q, descending s): ties stay in ascending d ----
+                    const uint32_t sb = bit_width(smax);
+                    uint64_t *ckey = nullptr;
+                    uint32_t *cs = nullptr, *qh = nullptr, *qx = nullptr, *qstart = nullptr, *tf = nullptr, *tx = nullptr;
+                    SortPairs cp;
+                    if ((rc = sc.get(&ckey, NC)) || (rc = sc.get(&cs, NC)) || (rc = cp.alloc(sc, NC)) || (rc = sc.get(&qh, NC)) ||
+                        (rc = sc.get(&qx, NC)) || (rc = sc.get(&tf, NC)) || (rc = sc.get(&tx, NC)))
+                        return rc;
+                    hipLaunchKernelGGL(kg::search_cand_emit_kernel, dim3(grid_of(ND)), dim3(256), 0, s, jp.keys(), lstart, cf, cx, ND, NC, db, sb,
+                                       (uint32_t)smax, ckey, cs, cp.keys(), cp.vals());
+                    HIP_TRY(hipGetLastError());
+                    if ((rc = cp.sort(t, sc, NC, bits_for((uint64_t)n_q) + sb))) return rc;
+                    hipLaunchKernelGGL(kg::search_query_heads_kernel, dim3(grid_of(NC)), dim3(256), 0, s, cp.keys(), NC, sb, qh);
+                    HIP_TRY(hipGetLastError());
+                    if ((rc = prefix_sum(t, qh, NC, qx, jpartial, d_tot + 6))) return rc;
+                    uint64_t NQ = 0;
+                    HIP_TRY(hipMemcpyAsync(&NQ, d_tot + 6, 8, hipMemcpyDeviceToHost, s));
+                    HIP_TRY(hipStreamSynchronize(s));
+                    if ((rc = sc.get(&qstart, NQ + 1))) return rc;
+                    hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(NC)), dim3(256), 0, s, qh, qx, NC, d_tot + 6, qstart);
+                    hipLaunchKernelGGL(kg::search_top_flags_kernel, dim3(grid_of(NC)), dim3(256), 0, s, qh, qx, qstart, NC, (uint32_t)prm->max_cand, tf);
+                    HIP_TRY(hipGetLastError());
+                    if ((rc = prefix_sum(t, tf, NC, tx, jpartial, d_tot + 7))) return rc;
+                    HIP_TRY(hipMemcpyAsync(&NK, d_tot + 7, 8, hipMemcpyDeviceToHost, s));
+                    HIP_TRY(hipStreamSynchronize(s));
+                    if ((rc = sc.get(&d_kept_pairs, 2 * NK)) || (rc = sc.get(&d_shared, NK))) return rc;
+                    hipLaunchKernelGGL(kg::search_top_emit_kernel, dim3(grid_of(NC)), dim3(256), 0, s, cp.vals(), ckey, cs, tf, tx, NC, NK, db, ndb,
+                                       d_kept_pairs, d_shared);
+                    HIP_TRY(hipGetLastError());
+                }
+            }
+            HIP_TRY(hipEventRecord(ev[4], s));
+        }
+    }
+
+    // ---- the result block; the kept candidates to the host, aligned, ordered ----
+    const size_t start_bytes = ((size_t)n_q + 1) * 8;
+    if ((rc = dalloc_detached(t, &guard.p, start_bytes + std::max<uint64_t>(NK, 1) * sizeof(kg_search_hit)))) return rc;
+    std::vector<int64_t> h_start((size_t)n_q + 1, 0);
+    std::vector<int32_t> h_pairs(2 * NK);
+    AlignTotals atot;
+    if (NK > 0) {
+        HIP_TRY(hipMemcpyAsync(h_pairs.data(), d_kept_pairs, NK * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint64_t k = 0; k < NK; k++) {
+            const int64_t q = (int64_t)h_pairs[2 * k] - n_db;
+            if (q < 0 || q >= n_q || h_pairs[2 * k + 1] < 0 || h_pairs[2 * k + 1] >= n_db)
+                return fail(KG_ERR_DEVICE, "internal: a candidate outside the batch");
+            h_start[(size_t)q + 1]++;
+        }
+        for (int64_t q = 0; q < n_q; q++) {
+            if (h_start[(size_t)q + 1] > prm->max_cand) return fail(KG_ERR_DEVICE, "internal: more than max_cand candidates of one query");
+            h_start[(size_t)q + 1] += h_start[(size_t)q];
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(guard.p, h_start.data(), start_bytes, hipMemcpyHostToDevice, s));
+    if (NK > 0) {
+        const int32_t *d_pairs = nullptr;
+        kg::AlignRec *d_aln = nullptr;
+        if ((rc = align_run(t, sc, al, d_seq, d_off, offsets, h_pairs.data(), NK, &d_pairs, &d_aln, &atot))) return rc;
+        hipLaunchKernelGGL(kg::search_order_kernel, dim3(grid_of((uint64_t)n_q, 256 / kg::kWave)), dim3(256), 0, s, d_pairs, d_aln, d_shared,
+                           (const int64_t *)guard.p, (uint32_t)n_q, (int64_t)al->min_ratio_pct, (int)(al->ref == KG_ALIGN_REF_MEMBER),
+                           (int2 *)(guard.p + start_bytes), words);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(ev[5], s));
+    unsigned long long hw[kg::kSearchWords] = {};
+    HIP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((int64_t)hw[kg::kSearchSkipped] != atot.skipped) return fail(KG_ERR_DEVICE, "internal: the device and the host skipped different pairs");
+    if (hw[kg::kSearchHits] + hw[kg::kSearchBelow] + hw[kg::kSearchSkipped] != NK)
+        return fail(KG_ERR_DEVICE, "internal: the ordered records and the kept candidates differ");
+    st.pairs = (int64_t)P;
+    st.kmers = (int64_t)K;
+    st.join_pairs = (int64_t)J;
+    st.candidates = (int64_t)NC;
+    st.aligned = (int64_t)NK - atot.skipped;
+    st.hits = (int64_t)hw[kg::kSearchHits];
+    st.skipped = atot.skipped;
+    st.queries_hit = (int64_t)hw[kg::kSearchQueriesHit];
+    st.cells = atot.cells;
+    st.ms_encode = dv.ms_hist + ev.ms(1, 2);
+    st.ms_sort = ev.ms(2, 3);
+    st.ms_join = ev.ms(3, 4);
+    st.ms_align = ev.ms(4, 5);
+    st.ms_total = ev.ms(0, 5);
+    set->d_block = guard.p; guard.p = nullptr;
+    set->count = (int64_t)NK;
+    return KG_OK;
+}
+
+int search_entry(int device, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq,
+                 const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset **out)
+{
+    if (!out) return fail(KG_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!prm) return fail(KG_ERR_ARG, "null kg_search_params");
+    if (prm->min_shared < 1) return fail(KG_ERR_ARG, "min_shared must be >= 1");
+    if (prm->max_cand < 1 || prm->max_cand > kg::kSearchMaxCand) return fail(KG_ERR_ARG, "max_cand must be in 1..64");
+    if (prm->max_db_per_kmer < 1) return fail(KG_ERR_ARG, "max_db_per_kmer must be >= 1");
+    if (prm->reserved != 0) return fail(KG_ERR_ARG, "kg_search_params.reserved must be 0");
+    if (!al) return fail(KG_ERR_ARG, "null kg_align_params");
+    if (int rc = align_check_params(al)) return rc;
+    if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
+    if (max_pairs < 0) return fail(KG_ERR_ARG, "max_pairs must be >= 0");
+    if (n_prot < 0) return fail(KG_ERR_ARG, "n_prot < 0");
+    if (n_prot >= (1ll << 29)) return fail(KG_ERR_LIMIT, "2^29 or more proteins in one call");
+    if (n_db < 0 || n_db > n_prot) return fail(KG_ERR_ARG, "n_db must be in 0..n_prot");
+    if (!offsets) return fail(KG_ERR_ARG, "null offsets");
+    if (offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
+    for (int64_t k = 0; k < n_prot; k++) {
+        const int64_t L = offsets[k + 1] - offsets[k];
+        if (L < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": offsets decrease (offsets[p+1] < offsets[p])");
+        if (L >= (int64_t)kg::kAlignMaxLen) return fail(KG_ERR_LIMIT, "protein " + kmer_text(k) + ": 2^24 or more characters");
+    }
+    const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
+    if (seq_bytes && !h_seq && !d_seq) return fail(KG_ERR_ARG, "null sequence");
+    CallScope cs(device);               // the call's context: closed when the call returns, the set keeps only its records
+    if (cs.rc) return cs.rc;
+    kg_hitset *set = new (std::nothrow) kg_hitset();
+    if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
+    set->device = device;
+    int rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
+    if (!rc) rc = search_impl(cs.t, prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, set);
+    cs.t->cache.release_all();                          // scratch goes back to the driver
+    if (rc) { std::string keep = g_err; kg_hitset_free(set); g_err = keep; return rc; }
+    if (getenv("KG_DEBUG"))
+        fprintf(stderr, "[kg] kg_proteins_search: targets=%lld queries=%lld valid=%lld pairs=%lld kmers=%lld joined=%lld masked=%lld join_pairs=%lld candidates=%lld aligned=%lld hits=%lld skipped=%lld queries_hit=%lld encode_ms=%.3f sort_ms=%.3f join_ms=%.3f align_ms=%.3f total_ms=%.3f\n",
+                (long long)set->st.targets, (long long)set->st.queries, (long long)set->st.valid_windows, (long long)set->st.pairs,
+                (long long)set->st.kmers, (long long)set->st.kmers_joined, (long long)set->st.kmers_masked, (long long)set->st.join_pairs,
+                (long long)set->st.candidates, (long long)set->st.aligned, (long long)set->st.hits, (long long)set->st.skipped,
+                (long long)set->st.queries_hit, set->st.ms_encode, set->st.ms_sort, set->st.ms_join, set->st.ms_align, set->st.ms_total);
+    *out = set;
+    return KG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kg_proteins_search(int device, const kg_search_params *p, const kg_align_params *align, const uint8_t *seq, const int64_t *offsets,
+                       int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset **out)
+{
+    return search_entry(device, p, align, seq, nullptr, offsets, n_prot, n_db, max_windows, max_pairs, out);
+}
+
+int kg_proteins_search_device(int device, const kg_search_params *p, const kg_align_params *align, const uint8_t *d_seq,
+                              const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs,
+                              kg_hitset **out)
+{
+    return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out);
+}
+
+int64_t kg_hitset_count(const kg_hitset *s) { return s ? s->count : 0; }
+
+int kg_hitset_copy(const kg_hitset *s, int64_t first, int64_t count, kg_search_hit *dst)
+{
+    return copy_records(s, s ? s->device : 0, s ? s->hits() : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_hitset_copy");
+}
+
+int kg_hitset_starts_copy(const kg_hitset *s, int64_t *dst)
+{
+    return copy_starts(s, s ? s->device : 0, s ? s->starts() : nullptr, s ? s->n_q : 0, dst);
+}
+
+int kg_hitset_stats(const kg_hitset *s, kg_search_stats *out) { return copy_stats(s, s ? &s->st : nullptr, out); }
+
+void kg_hitset_free(kg_hitset *s)
+{
+    if (!s) return;
+    if (s->d_block) {
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->d_block);
+    }
+    delete s;
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@
 #include "kg_derive.hpp"
 #include "kg_cluster.hpp"
 #include "kg_align.hpp"
+#include "kg_search.hpp"
 #include "kg_assign.hpp"
 #include "kg_regions.hpp"
 #include "kg_orfs.hpp"
@@ -48,6 +49,7 @@
 #include "kg_host_merge.hpp"
 #include "kg_host_align.hpp"
 #include "kg_host_cluster.hpp"
+#include "kg_host_search.hpp"
 #include "kg_host_assign.hpp"
 #include "kg_host_regions.hpp"
 #include "kg_host_orfs.hpp"

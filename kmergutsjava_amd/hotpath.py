@@ -826,6 +826,40 @@ def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20,
         lib.kg_familyset_free(h)
 
 
+def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256,
+                    align: Optional[dict] = None, max_windows: int = 0, max_pairs: int = 0, device: int = 0,
+                    device_ptr: Optional[int] = None):
+    """Proteins [n_db, n_prot) searched against proteins [0, n_db), on the GPU (include/kmerguts_hip.h kg_proteins_search states
+    the rule): the targets that share at least min_shared distinct unmasked 8-mers with a query, the max_cand with the most
+    aligned, a hit where 100 * score >= min_ratio_pct * ref.  seq / offsets / device_ptr as for cluster_proteins; align: None
+    (the defaults) or a dict as for cluster_proteins; max_windows = 0 and max_pairs = 0 size the one pass and the join from
+    free device memory.  The defaults 2, 8 and 256 are this project's choice.
+    -> (numpy records of _native.SEARCH_HIT_DTYPE in (query, rank) order, hit_start int64[n_q + 1], the call's statistics)."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("offsets must be int64[n_prot + 1]")
+    n = off.size - 1
+    p = N.KgSearchParams(int(min_shared), int(max_cand), int(max_db_per_kmer), 0)
+    ap, _keep = _align_params(**(align or {}))
+    h = C.c_void_p()
+    lib = N.load()
+    if device_ptr is not None:
+        N.check(lib.kg_proteins_search_device(device, C.byref(p), C.byref(ap), C.c_void_p(device_ptr), off.ctypes.data, n, int(n_db),
+                                              int(max_windows), int(max_pairs), C.byref(h)))
+    else:
+        arr = _seq_bytes(seq, off)
+        N.check(lib.kg_proteins_search(device, C.byref(p), C.byref(ap), arr.ctypes.data if arr.size else None, off.ctypes.data, n,
+                                       int(n_db), int(max_windows), int(max_pairs), C.byref(h)))
+    try:
+        st = N.KgSearchStats()
+        N.check(lib.kg_hitset_stats(h, C.byref(st)))
+        starts = np.zeros(int(st.queries) + 1, dtype=np.int64)
+        N.check(lib.kg_hitset_starts_copy(h, starts.ctypes.data))
+        return _copy_records(lib.kg_hitset_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_HIT_DTYPE), starts, st.as_dict()
+    finally:
+        lib.kg_hitset_free(h)
+
+
 def assign_calls(calls, call_start, otu=None, min_score: int = 0, min_share_pct: int = 50, device: int = 0) -> np.ndarray:
     """One function per protein from caller-held CALL lists, on the GPU (kg_assign_calls): calls CALL_DTYPE[call_start[-1]],
     call_start int64[n_prot + 1] (protein p's CALLs are calls[call_start[p] : call_start[p + 1]], in emission order), otu

@@ -1,0 +1,178 @@
+"""Search proteins against a set of known proteins on the GPU (kg_proteins_search): which known protein is this protein like, and
+how much.  The step that names what `annotate` leaves at `none`.
+
+    python -m kmergutsjava_amd.search_proteins -d database.faa[.gz] [-d more.faa ...] -q queries.faa[.gz] [-q more ...] -o hits.tsv
+                                               [--min-shared 2] [--max-cand 8] [--max-hits 1] [--max-db-per-kmer 256]
+                                               [--min-ratio 50] [--align-ref longer|query] [--gap-open 11] [--gap-extend 1]
+                                               [--max-cells N] [--all] [-A db_annotations.tsv [--transfer out.tsv]]
+                                               [--truth query_annotations.tsv]
+
+The proteins of all -d files are the database, those of all -q files the queries, each in the order given (FASTA as
+make_signatures reads it).  An id that occurs twice within the database or within the queries is an error; the same id in both
+is allowed.  include/kmerguts_hip.h states the rule: a target is a candidate of a query when the two share at least --min-shared
+distinct exact 8-mers, not counting the 8-mers that more than --max-db-per-kmer targets have (repeats and low complexity); the
+--max-cand candidates with the most shared 8-mers (on a tie the earlier target) are aligned (BLOSUM62 in align_scores.py, a gap of
+k residues costs --gap-open + k * --gap-extend, no traceback); an aligned pair is a hit when 100 * score >= --min-ratio * ref,
+where ref is the larger of the two proteins' self-scores (--align-ref longer, the default) or the query's own (--align-ref
+query).  A pair of more than --max-cells cells (default 2^26) is not aligned: skipped.  The defaults 2, 8, 256, 50 and longer are
+this project's choice.
+
+-o lines, in query FASTA order and within a query by rank (not skipped first, then larger score, then more shared 8-mers, then
+the earlier target): `query_id<TAB>rank<TAB>target_id<TAB>shared<TAB>score<TAB>ref<TAB>ratio<TAB>query end<TAB>target end<TAB>
+hit|below|skipped`, the ratio in percent (100 * score / ref, rounded down; `-` for a skipped pair), the ends 1-based (0 without
+one).  With -A one more field: the target's function, or `-`.  Only `hit` records of rank below --max-hits (default 1) are
+written; --all writes every record.
+--transfer (needs -A) writes make_signatures' annotation format: one `query_id<TAB>function` line per query whose rank-0 record is
+a hit and whose target has a function in -A.
+--truth (the same format, for the queries) adds `labelled, agree, disagree, missed` to the summary, compared by function name: of
+the labelled queries, those that got their own function, another one, or none.
+The summary line goes to stderr.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+from typing import Optional
+
+import numpy as np
+
+from .cluster_proteins import read_proteins
+from .make_signatures import InputError, _read, parse_annotations
+
+STATUS = (b"hit", b"below", b"skipped")
+HIT = 0
+
+
+def _ref(h, align_ref: str) -> int:
+    return int(h["self_query"]) if align_ref in ("query", "member") else max(int(h["self_query"]), int(h["self_target"]))
+
+
+def format_hits(qids, dids, hits, hit_start, max_hits: int = 1, write_all: bool = False, align_ref: str = "longer", functions=None) -> bytes:
+    """functions: None, or {target id: (function, otu)}: every line gains the target's function or `-`."""
+    out = []
+    for q, qid in enumerate(qids):
+        for h in hits[int(hit_start[q]):int(hit_start[q + 1])]:
+            status = int(h["status"])
+            if not write_all and (status != HIT or int(h["rank"]) >= max_hits):
+                continue
+            ref, score, did = _ref(h, align_ref), int(h["score"]), dids[int(h["target"])]
+            ratio = b"%d" % (100 * score // ref) if score >= 0 and ref > 0 else b"-"
+            line = b"%s\t%d\t%s\t%d\t%d\t%d\t%s\t%d\t%d\t%s" % (qid, int(h["rank"]), did, int(h["shared"]), score, ref, ratio,
+                                                               int(h["end_query"]) + 1, int(h["end_target"]) + 1, STATUS[status])
+            if functions is not None:
+                line += b"\t" + (functions[did][0] if did in functions else b"-")
+            out.append(line + b"\n")
+    return b"".join(out)
+
+
+def transferred(qids, dids, hits, hit_start, functions):
+    """-> {query id: function} of the queries whose rank-0 record is a hit on a target with a function."""
+    out = {}
+    for q, qid in enumerate(qids):
+        if hit_start[q + 1] > hit_start[q]:
+            h = hits[int(hit_start[q])]
+            did = dids[int(h["target"])]
+            if int(h["status"]) == HIT and did in functions:
+                out[qid] = functions[did][0]
+    return out
+
+
+def format_transfer(qids, got) -> bytes:
+    return b"".join(b"%s\t%s\n" % (qid, got[qid]) for qid in qids if qid in got)
+
+
+def compare_truth(qids, got, truth) -> dict:
+    t = {"labelled": 0, "agree": 0, "disagree": 0, "missed": 0}
+    for qid in qids:
+        want = truth.get(qid)
+        if want is None:
+            continue
+        t["labelled"] += 1
+        if qid not in got:
+            t["missed"] += 1
+        elif got[qid] == want[0]:
+            t["agree"] += 1
+        else:
+            t["disagree"] += 1
+    return t
+
+
+def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: int = 8, max_hits: int = 1, max_db_per_kmer: int = 256,
+                    align: Optional[dict] = None, write_all: bool = False, annotations: Optional[str] = None,
+                    transfer: Optional[str] = None, truth: Optional[str] = None, device: int = 0, search=None) -> str:
+    """Write the files; returns the summary line.  `search` replaces hotpath.search_proteins (tests).  align: None, or the
+    alignment parameters of hotpath.search_proteins (ref "query" is its "member")."""
+    if max_hits < 1:
+        raise ValueError("--max-hits must be >= 1")
+    if transfer is not None and annotations is None:
+        raise ValueError("--transfer needs -A")
+    if truth is not None and annotations is None:
+        raise ValueError("--truth needs -A")
+    dids, dseqs = read_proteins(database)
+    qids, qseqs = read_proteins(queries)
+    seqs = dseqs + qseqs
+    offsets = np.zeros(len(seqs) + 1, dtype=np.int64)
+    if seqs:
+        offsets[1:] = np.cumsum([len(s) for s in seqs])
+    align = dict(align or {})
+    align_ref = align.get("ref", "longer")
+    if align_ref == "query":
+        align["ref"] = "member"
+    functions = parse_annotations(_read(annotations), annotations) if annotations is not None else None
+    want = parse_annotations(_read(truth), truth) if truth is not None else None
+    if search is None:
+        from . import hotpath
+        search = hotpath.search_proteins
+    hits, hit_start, st = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
+                                 max_db_per_kmer=max_db_per_kmer, align=align, device=device)
+    with open(out, "wb") as f:
+        f.write(format_hits(qids, dids, hits, hit_start, max_hits, write_all, align_ref, functions))
+    got = transferred(qids, dids, hits, hit_start, functions) if functions is not None else {}
+    if transfer is not None:
+        with open(transfer, "wb") as f:
+            f.write(format_transfer(qids, got))
+    line = ("Queries: %d, targets: %d, candidates: %d, aligned: %d, hits: %d, queries hit: %d, transferred: %d, masked k-mers: %d, "
+            "ms: encode %.3f, sort %.3f, join %.3f, align %.3f, total %.3f") % (
+        st["queries"], st["targets"], st["candidates"], st["aligned"], st["hits"], st["queries_hit"], len(got), st["kmers_masked"],
+        st.get("ms_encode", 0.0), st.get("ms_sort", 0.0), st.get("ms_join", 0.0), st.get("ms_align", 0.0), st.get("ms_total", 0.0))
+    if want is not None:
+        t = compare_truth(qids, got, want)
+        line += ", labelled: %d, agree: %d, disagree: %d, missed: %d" % (t["labelled"], t["agree"], t["disagree"], t["missed"])
+    return line
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m kmergutsjava_amd.search_proteins",
+                                 description="Search proteins against a set of known proteins on the GPU: shared 8-mers, then alignment.")
+    ap.add_argument("-d", required=True, action="append", metavar="DATABASE", help="database protein FASTA (.gz allowed); may be given several times")
+    ap.add_argument("-q", required=True, action="append", metavar="QUERIES", help="query protein FASTA (.gz allowed); may be given several times")
+    ap.add_argument("-o", required=True, metavar="HITS", help="hits TSV to write")
+    ap.add_argument("--min-shared", type=int, default=2, help="distinct unmasked 8-mers a candidate shares at least (default 2, this project's choice)")
+    ap.add_argument("--max-cand", type=int, default=8, help="candidates aligned per query, 1..64 (default 8, this project's choice)")
+    ap.add_argument("--max-hits", type=int, default=1, help="hits written per query (default 1)")
+    ap.add_argument("--max-db-per-kmer", type=int, default=256, help="an 8-mer of more targets takes no part (default 256, this project's choice)")
+    ap.add_argument("--min-ratio", type=int, default=50, help="a hit needs 100 * score >= this * ref (default 50, this project's choice)")
+    ap.add_argument("--align-ref", choices=("longer", "query"), default="longer",
+                    help="ref is the larger self-score of the two proteins (default) or the query's")
+    ap.add_argument("--gap-open", type=int, default=11, help="a gap of k residues costs gap-open + k * gap-extend (default 11)")
+    ap.add_argument("--gap-extend", type=int, default=1, help="(default 1)")
+    ap.add_argument("--max-cells", type=int, default=1 << 26, help="a pair of more cells is not aligned: skipped (default 2^26)")
+    ap.add_argument("--all", action="store_true", help="write every record to -o: below, skipped and every rank")
+    ap.add_argument("-A", default=None, metavar="ANNOTATIONS", help="protein_id<TAB>function[<TAB>otu] lines of the database")
+    ap.add_argument("--transfer", default=None, metavar="OUT", help="with -A: write query_id<TAB>function lines for make_signatures -A")
+    ap.add_argument("--truth", default=None, metavar="ANNOTATIONS", help="with -A: the queries' own annotations to compare with")
+    a = ap.parse_args(argv)
+    from . import _native as N
+    align = dict(min_ratio_pct=a.min_ratio, ref=a.align_ref, gap_open=a.gap_open, gap_extend=a.gap_extend, max_cells=a.max_cells)
+    try:
+        line = search_proteins(a.d, a.q, a.o, a.min_shared, a.max_cand, a.max_hits, a.max_db_per_kmer, align, a.all, a.A, a.transfer,
+                               a.truth)
+    except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
+        print("Error: %s" % e, file=sys.stderr)
+        return 1
+    print(line, file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
