@@ -566,6 +566,18 @@ int read_error_words(kg_table *t, const void *d_words, size_t n_words, int pin, 
     return KG_OK;
 }
 
+// The same for a stage whose first n_err words each hold the first record with their error (what[k]: the text of word k):
+// d_words[n_words] -> the stage's pinned words, then "record N" + what[k] for the first record with any error
+int read_record_errors(kg_table *t, const void *d_words, size_t n_words, int n_err, const char *const *what)
+{
+    int rc;
+    if ((rc = read_error_words(t, d_words, n_words, kPinStage, {}))) return rc;
+    const uint64_t *h = t->h_pin + kPinStage;
+    const int first = (int)(std::min_element(h, h + n_err) - h);
+    if (h[first] != kNoErr) return fail(KG_ERR_ARG, "record " + kmer_text((int64_t)h[first]) + what[first]);
+    return KG_OK;
+}
+
 // Host bytes -> d_dst through pinned pieces: several threads copy disjoint 32 MiB pieces of the caller's (possibly pageable)
 // buffer into two pinned buffers each and hand them to the copy engine, as kg_table_open does.
 int upload_pinned(kg_table *t, const uint8_t *src, size_t bytes, uint8_t *d_dst)

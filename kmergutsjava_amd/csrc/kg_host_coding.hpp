@@ -135,16 +135,14 @@ struct CodingWork {
             ": seq outside [0, n_seqs)", ": strand is neither 0 nor 1", ": outside its contig (0 <= left <= right <= L - 1 does not hold)",
             ": 3 * n_res exceeds right - left + 1"};
         int rc;
-        if ((rc = read_error_words(t, words, kg::kCodingErrWords + kg::kCodingCntWords, kPinStage, {}))) return rc;
-        // every word holds the first record with its error: the message names the first record with any
-        const uint64_t *h = t->h_pin + kPinStage;
-        const int first = (int)(std::min_element(h, h + kg::kCodingErrWords) - h);
-        if (h[first] != kNoErr) return fail(KG_ERR_ARG, "record " + kmer_text((int64_t)h[first]) + what[first]);
+        if ((rc = read_record_errors(t, words, kg::kCodingErrWords + kg::kCodingCntWords, kg::kCodingErrWords, what))) return rc;
         if (counter(kg::kCodingCntPairs) >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more codon pairs in one call");
         return KG_OK;
     }
     uint64_t counter(int k) const { return t->h_pin[kPinStage + kg::kCodingErrWords + k]; }
 };
+
+constexpr const char *kNoScores = "the set has no scores (it is not from kg_orfset_coding)";
 
 int64_t coding_sum(const int64_t *c)
 {
@@ -195,8 +193,7 @@ int kg_orfset_coding(kg_orfset *os, const kg_coding_params *p, const int32_t *ta
     int rc = check_coding_params(p);
     if (rc) return rc;
     uint64_t total = 0;
-    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total))) return rc;
-    if (n_seqs != os->n_seqs) return fail(KG_ERR_ARG, "n_seqs is not the ORF set's");
+    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total, "ORF set's", os->n_seqs))) return rc;
     if (total >= (1ull << 40)) return fail(KG_ERR_LIMIT, "2^40 or more bytes in one call");
     if (os->count >= (1ll << 31)) return fail(KG_ERR_LIMIT, "2^31 or more records in one call");
     std::vector<int32_t> own_table;     // (in front of the scratch, whose destructor waits for the stream that copies it)
@@ -206,7 +203,7 @@ int kg_orfset_coding(kg_orfset *os, const kg_coding_params *p, const int32_t *ta
     kg_table *t = cs.t;
     hipStream_t s = t->stream;
     std::unique_ptr<kg_orfset> set;
-    if ((rc = make_set(cs, set))) return rc;
+    if ((rc = make_set(cs, set)) || (rc = inherit(set.get(), os))) return rc;
     set->coding_model.reset(new (std::nothrow) kg_coding_model());
     if (!set->coding_model) return fail(KG_ERR_NOMEM, "out of host memory");
     if ((rc = ev.create())) return rc;
@@ -261,39 +258,28 @@ int kg_orfset_coding(kg_orfset *os, const kg_coding_params *p, const int32_t *ta
     st.noncoding = (int64_t)w.counter(kg::kCodingCntNoncoding);
     st.ms_count = ev.ms(0, 1);
     st.ms_score = ev.ms(2, 3);
-    // the four arrays of the set leave the scratch: everything else goes back to the cache
-    set->d_orfs = set->keep(w.sc, d_out);
-    set->d_prot_start = set->keep(w.sc, d_start);
-    set->d_res = set->keep(w.sc, d_res);
+    keep_orfs(set.get(), w.sc, d_out, d_start, d_res, n, n_res, (uint64_t)n_seqs);
     set->d_coding = set->keep(w.sc, d_S);
-    set->count = os->count;
-    set->residues = os->residues;
-    set->n_seqs = os->n_seqs;
-    set->l_max = os->l_max;
-    set->st = os->st;
     set->coding_st = st;
     return hand_out(cs, set, out);
 }
 
 int kg_orfset_coding_scores(const kg_orfset *s, int64_t first, int64_t count, int64_t *dst)
 {
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (!s->d_coding) return fail(KG_ERR_ARG, "kg_orfset_coding_scores: the set has no scores (it is not from kg_orfset_coding)");
+    if (int rc = need_of_set(s, count <= 0 || dst, s && s->d_coding, "kg_orfset_coding_scores", kNoScores)) return rc;
     return copy_records(s, device_of(s), s->d_coding, 1, s->count, first, count, dst, "kg_orfset_coding_scores");
 }
 
 int kg_orfset_coding_stats(const kg_orfset *s, kg_coding_stats *out)
 {
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    if (!s->d_coding) return fail(KG_ERR_ARG, "kg_orfset_coding_stats: the set has no scores (it is not from kg_orfset_coding)");
+    if (int rc = need_of_set(s, out, s && s->d_coding, "kg_orfset_coding_stats", kNoScores)) return rc;
     *out = s->coding_st;
     return KG_OK;
 }
 
 int kg_orfset_coding_model(const kg_orfset *s, kg_coding_model *out)
 {
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    if (!s->d_coding || !s->coding_model) return fail(KG_ERR_ARG, "kg_orfset_coding_model: the set has no scores (it is not from kg_orfset_coding)");
+    if (int rc = need_of_set(s, out, s && s->d_coding && s->coding_model, "kg_orfset_coding_model", kNoScores)) return rc;
     *out = *s->coding_model;
     return KG_OK;
 }

@@ -1,6 +1,8 @@
 // kg_host_orfs.hpp -- kg_regionset_orfs / kg_orfs_regions: function regions -> open reading frames and their proteins;
 // kg_orfs_free / kg_orfset_add_free: the evidence-free open reading frames of the six frames (kernels: kg_orfs.hpp).
-// Part of kmerguts_hip.hip's translation unit: the last of the batch stages, behind kg_host_regions.hpp (it reads kg_regionset).
+// Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_regions.hpp (it reads kg_regionset).  The stages that
+// make a kg_orfset follow it (kg_host_repair.hpp, kg_host_coding.hpp, kg_host_starts.hpp) and share its helpers: the batch's
+// checks and bytes, the protein layout, the translation, what a new set keeps and inherits, and the getters' guard.
 #pragma once
 
 struct kg_orfset : SetBase {
@@ -111,6 +113,103 @@ struct OrfPlanes {
     }
 };
 
+// the batch's bytes from (possibly pageable) host memory: large ones through pinned pieces on several threads, as a table's
+// signatures go up (complete on return); small ones as one copy on the call's stream
+int upload_batch(kg_table *t, const uint8_t *src, uint64_t bytes, uint8_t *d_dst)
+{
+    if (bytes >= (64ull << 20)) return upload_pinned(t, src, (size_t)bytes, d_dst);
+    HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, t->stream));
+    return KG_OK;
+}
+
+// the host checks the entry points share; *total = the batch's bytes.  whose ("region set's", "ORF set's"): the call works on a
+// set of parent_n_seqs contigs, and the batch must be that set's
+int check_orf_batch(const uint8_t *seq, const int64_t *offsets, int64_t n_seqs, uint64_t *total, const char *whose = nullptr,
+                    int64_t parent_n_seqs = 0)
+{
+    int64_t l_max = 0;
+    int rc = check_region_offsets(offsets, n_seqs, &l_max);
+    if (rc) return rc;
+    if (n_seqs && offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
+    *total = n_seqs ? (uint64_t)offsets[n_seqs] : 0;
+    if (*total && !seq) return fail(KG_ERR_ARG, "null sequence bytes");
+    if (whose && n_seqs != parent_n_seqs) return fail(KG_ERR_ARG, std::string("n_seqs is not the ") + whose);
+    return KG_OK;
+}
+
+// the batch's bytes where the kernels read them: the caller's device memory, or a copy in the call's scratch
+int batch_on_device(kg_table *t, Scratch &sc, const uint8_t *seq, int seq_on_device, uint64_t total, const uint8_t **d_seq)
+{
+    *d_seq = seq;
+    if (seq_on_device) {
+        HIP_TRY(hipDeviceSynchronize());            // the bytes may have been produced on another stream
+        return KG_OK;
+    }
+    uint8_t *up = nullptr;
+    int rc = sc.get(&up, total ? total : 1);
+    if (rc) return rc;
+    if (total && (rc = upload_batch(t, seq, total, up))) return rc;
+    *d_seq = up;
+    return KG_OK;
+}
+
+// lens[n] -> d_start[n + 1], where every protein begins, and their total -> *d_total (excl[n], partial: the prefix sum's)
+int layout_proteins(kg_table *t, const uint32_t *lens, uint64_t n, uint32_t *excl, uint64_t *partial, uint64_t *d_total, int64_t *d_start)
+{
+    int rc;
+    if (n > 0 && (rc = prefix_sum(t, lens, n, excl, partial, d_total))) return rc;
+    hipLaunchKernelGGL(kg::orf_prot_start_kernel, dim3(grid_of(n + 1)), dim3(256), 0, t->stream, excl, d_total, n, d_start);
+    HIP_TRY(hipGetLastError());
+    return KG_OK;
+}
+
+// the n_res residues of d_orfs[n], laid out by d_start, translated into *d_res (of the scratch; one byte when there are none)
+int translate_orfs(kg_table *t, Scratch &sc, const kg_orf *d_orfs, uint64_t n, const int64_t *d_start, uint64_t n_res, const uint8_t *d_seq,
+                   const int64_t *d_off, uint8_t **d_res)
+{
+    int rc;
+    if ((rc = sc.get(d_res, std::max<uint64_t>(n_res, 1)))) return rc;
+    if (n_res > 0) {
+        hipLaunchKernelGGL(kg::orf_residues_kernel, dim3(grid_of((n_res + kg::kOrfResPerLane - 1) / kg::kOrfResPerLane)), dim3(256), 0,
+                           t->stream, d_orfs, n, d_start, n_res, d_seq, d_off, *d_res);
+        HIP_TRY(hipGetLastError());
+    }
+    return KG_OK;
+}
+
+// the three arrays of every ORF set leave the call's scratch, as a stage's own do beside them: the rest goes back to the cache
+void keep_orfs(kg_orfset *set, Scratch &sc, kg_orf *d_orfs, int64_t *d_start, uint8_t *d_res, uint64_t n, uint64_t n_res, uint64_t n_seqs)
+{
+    set->d_orfs = set->keep(sc, d_orfs);
+    set->d_prot_start = set->keep(sc, d_start);
+    set->d_res = set->keep(sc, d_res);
+    set->count = (int64_t)n;
+    set->residues = (int64_t)n_res;
+    set->n_seqs = (int64_t)n_seqs;
+}
+
+// what a stage that rewrites the records of `os` hands on: the longest contig, the ORF and coding statistics, the coding model
+int inherit(kg_orfset *set, const kg_orfset *os)
+{
+    set->l_max = os->l_max;
+    set->st = os->st;
+    set->coding_st = os->coding_st;
+    if (os->coding_model) {
+        set->coding_model.reset(new (std::nothrow) kg_coding_model(*os->coding_model));
+        if (!set->coding_model) return fail(KG_ERR_NOMEM, "out of host memory");
+    }
+    return KG_OK;
+}
+
+// The checks of a getter of something only some ORF sets have: the arguments (args: the others are there), then `has`, or
+// "<name>: <why not>"
+int need_of_set(const kg_orfset *s, bool args, bool has, const char *name, const char *why_not)
+{
+    if (!s || !args) return fail(KG_ERR_ARG, "null argument");
+    if (!has) return fail(KG_ERR_ARG, std::string(name) + ": " + why_not);
+    return KG_OK;
+}
+
 // d_regions[n]: device array complete on t->stream; d_seq: the batch's bytes on the device (null when there are none);
 // offsets: host, checked.  Fills set (its arrays come out of the cache with the call's scratch and are kept only on success).
 int orfs_impl(kg_table *t, const kg_orf_params *prm, const kg_region *d_regions, uint64_t n, const uint8_t *d_seq,
@@ -146,10 +245,8 @@ int orfs_impl(kg_table *t, const kg_orf_params *prm, const kg_region *d_regions,
         hipLaunchKernelGGL(kg::orf_region_kernel, dim3(grid_of(n)), dim3(256), 0, s, d_regions, n, d_seq, geo, keys, sc_mask,
                            (int)prm->only_kept, d_out, lens, err, cnt);
         HIP_TRY(hipGetLastError());
-        if ((rc = prefix_sum(t, lens, n, excl, partial, d_total))) return rc;
     }
-    hipLaunchKernelGGL(kg::orf_prot_start_kernel, dim3(grid_of(n + 1)), dim3(256), 0, s, excl, d_total, n, d_start);
-    HIP_TRY(hipGetLastError());
+    if ((rc = layout_proteins(t, lens, n, excl, partial, d_total, d_start))) return rc;
     // the one wait of the call: the residue total (and, with it, the error and counter words)
     constexpr int kWords = kg::kOrfErrWords + kg::kOrfCntWords + 1;
     if ((rc = read_error_words(t, words, kWords, kPinStage,                          // (in the order they are reported)
@@ -163,12 +260,7 @@ int orfs_impl(kg_table *t, const kg_orf_params *prm, const kg_region *d_regions,
     const uint64_t n_res = h[kg::kOrfErrWords + kg::kOrfCntWords];
     if (n_res >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more residues in one call");
     uint8_t *d_res = nullptr;
-    if ((rc = sc.get(&d_res, std::max<uint64_t>(n_res, 1)))) return rc;
-    if (n_res > 0) {
-        hipLaunchKernelGGL(kg::orf_residues_kernel, dim3(grid_of((n_res + kg::kOrfResPerLane - 1) / kg::kOrfResPerLane)), dim3(256), 0, s,
-                           d_out, n, d_start, n_res, d_seq, d_off, d_res);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = translate_orfs(t, sc, d_out, n, d_start, n_res, d_seq, d_off, &d_res))) return rc;
     HIP_TRY(hipEventRecord(t->ev[kEvStageEnd], s));
     HIP_TRY(hipStreamSynchronize(s));
     set->st.orfs = (int64_t)n;
@@ -178,34 +270,7 @@ int orfs_impl(kg_table *t, const kg_orf_params *prm, const kg_region *d_regions,
     set->st.residues = (int64_t)n_res;
     set->st.tiles = (int64_t)n_tiles;
     HIP_TRY(hipEventElapsedTime(&set->st.ms, t->ev[kEvStageBegin], t->ev[kEvStageEnd]));
-    // the three arrays of the set leave the scratch: everything else goes back to the cache
-    set->d_orfs = set->keep(sc, d_out);
-    set->d_prot_start = set->keep(sc, d_start);
-    set->d_res = set->keep(sc, d_res);
-    set->count = (int64_t)n;
-    set->residues = (int64_t)n_res;
-    set->n_seqs = (int64_t)n_seqs;
-    return KG_OK;
-}
-
-// the batch's bytes from (possibly pageable) host memory: large ones through pinned pieces on several threads, as a table's
-// signatures go up (complete on return); small ones as one copy on the call's stream
-int upload_batch(kg_table *t, const uint8_t *src, uint64_t bytes, uint8_t *d_dst)
-{
-    if (bytes >= (64ull << 20)) return upload_pinned(t, src, (size_t)bytes, d_dst);
-    HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, t->stream));
-    return KG_OK;
-}
-
-// the host checks both entry points share; *total = the batch's bytes
-int check_orf_batch(const uint8_t *seq, const int64_t *offsets, int64_t n_seqs, uint64_t *total)
-{
-    int64_t l_max = 0;
-    int rc = check_region_offsets(offsets, n_seqs, &l_max);
-    if (rc) return rc;
-    if (n_seqs && offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
-    *total = n_seqs ? (uint64_t)offsets[n_seqs] : 0;
-    if (*total && !seq) return fail(KG_ERR_ARG, "null sequence bytes");
+    keep_orfs(set, sc, d_out, d_start, d_res, n, n_res, n_seqs);
     return KG_OK;
 }
 
@@ -260,20 +325,13 @@ int free_impl(kg_table *t, const kg_free_params *prm, const kg_orfset *parent, c
         hipLaunchKernelGGL(HIP_KERNEL_NAME(kg::orf_free_kernel<true>), dim3(row_grid), dim3(256), 0, s, d_seq, pl.total, geo, pl.n_rows, pl.keys,
                            prm->min_res, sc_mask, slot_first, d_out + n0, lens + n0, words);
     HIP_TRY(hipGetLastError());
-    if (n > 0 && (rc = prefix_sum(t, lens, n, excl, partial, d_total))) return rc;
-    hipLaunchKernelGGL(kg::orf_prot_start_kernel, dim3(grid_of(n + 1)), dim3(256), 0, s, excl, d_total, n, d_start);
-    HIP_TRY(hipGetLastError());
+    if ((rc = layout_proteins(t, lens, n, excl, partial, d_total, d_start))) return rc;
     // the second wait: the residue total and the counters
     if ((rc = read_error_words(t, words, kg::kOrfFreeWords, kPinStage, {}))) return rc;
     const uint64_t n_res = h[kg::kOrfFreeResidues];
     if (n_res >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more residues in one call");
     uint8_t *d_res = nullptr;
-    if ((rc = sc.get(&d_res, std::max<uint64_t>(n_res, 1)))) return rc;
-    if (n_res > 0) {
-        hipLaunchKernelGGL(kg::orf_residues_kernel, dim3(grid_of((n_res + kg::kOrfResPerLane - 1) / kg::kOrfResPerLane)), dim3(256), 0, s,
-                           d_out, n, d_start, n_res, d_seq, pl.d_off, d_res);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = translate_orfs(t, sc, d_out, n, d_start, n_res, d_seq, pl.d_off, &d_res))) return rc;
     HIP_TRY(hipEventRecord(t->ev[kEvStageEnd], s));
     HIP_TRY(hipStreamSynchronize(s));
     if (parent) set->st = parent->st;
@@ -283,29 +341,7 @@ int free_impl(kg_table *t, const kg_free_params *prm, const kg_orfset *parent, c
     set->st.residues = (int64_t)n_res;
     set->st.tiles = (int64_t)pl.n_tiles;
     HIP_TRY(hipEventElapsedTime(&set->st.ms, t->ev[kEvStageBegin], t->ev[kEvStageEnd]));
-    // the three arrays of the set leave the scratch: everything else goes back to the cache
-    set->d_orfs = set->keep(sc, d_out);
-    set->d_prot_start = set->keep(sc, d_start);
-    set->d_res = set->keep(sc, d_res);
-    set->count = (int64_t)n;
-    set->residues = (int64_t)n_res;
-    set->n_seqs = (int64_t)n_seqs;
-    return KG_OK;
-}
-
-// the batch's bytes where the kernels read them: the caller's device memory, or a copy in the call's scratch
-int batch_on_device(kg_table *t, Scratch &sc, const uint8_t *seq, int seq_on_device, uint64_t total, const uint8_t **d_seq)
-{
-    *d_seq = seq;
-    if (seq_on_device) {
-        HIP_TRY(hipDeviceSynchronize());            // the bytes may have been produced on another stream
-        return KG_OK;
-    }
-    uint8_t *up = nullptr;
-    int rc = sc.get(&up, total ? total : 1);
-    if (rc) return rc;
-    if (total && (rc = upload_batch(t, seq, total, up))) return rc;
-    *d_seq = up;
+    keep_orfs(set, sc, d_out, d_start, d_res, n, n_res, n_seqs);
     return KG_OK;
 }
 
@@ -322,8 +358,7 @@ int kg_regionset_orfs(kg_regionset *rs, const kg_orf_params *p, const uint8_t *s
     int rc = check_orf_params(p);
     if (rc) return rc;
     uint64_t total = 0;
-    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total))) return rc;
-    if (n_seqs != rs->n_seqs) return fail(KG_ERR_ARG, "n_seqs is not the region set's");
+    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total, "region set's", rs->n_seqs))) return rc;
     if (rs->count >= (1ll << 31)) return fail(KG_ERR_LIMIT, "2^31 or more regions in one call");
     CallScope cs(rs->tab, "a kg_scan* is in flight on this region set's kg_table");
     if (cs.rc) return cs.rc;
@@ -331,15 +366,8 @@ int kg_regionset_orfs(kg_regionset *rs, const kg_orf_params *p, const uint8_t *s
     std::unique_ptr<kg_orfset> set;
     if ((rc = make_set(cs, set))) return rc;
     Scratch sc(t);
-    const uint8_t *d_seq = seq;
-    if (!seq_on_device && total) {
-        uint8_t *up = nullptr;
-        if ((rc = sc.get(&up, total))) return rc;
-        if ((rc = upload_batch(t, seq, total, up))) return rc;
-        d_seq = up;
-    } else if (seq_on_device) {
-        HIP_TRY(hipDeviceSynchronize());            // the bytes may have been produced on another stream
-    }
+    const uint8_t *d_seq = nullptr;
+    if ((rc = batch_on_device(t, sc, seq, seq_on_device, total, &d_seq))) return rc;
     if ((rc = orfs_impl(t, p, rs->d_regions, (uint64_t)rs->count, d_seq, offsets, (uint64_t)n_seqs, set.get()))) return rc;
     return hand_out(cs, set, out);
 }
@@ -406,8 +434,7 @@ int kg_orfset_add_free(kg_orfset *os, const kg_free_params *p, const uint8_t *se
     int rc = check_free_params(p);
     if (rc) return rc;
     uint64_t total = 0;
-    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total))) return rc;
-    if (n_seqs != os->n_seqs) return fail(KG_ERR_ARG, "n_seqs is not the ORF set's");
+    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total, "ORF set's", os->n_seqs))) return rc;
     CallScope cs(os->tab, "a kg_scan* is in flight on this ORF set's kg_table");
     if (cs.rc) return cs.rc;
     kg_table *t = cs.t;

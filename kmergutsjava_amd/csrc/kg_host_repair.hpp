@@ -11,6 +11,8 @@ enum : int { kRepairWResidues = kg::kRepairErrWords + kg::kRepairCntWords, kRepa
 static_assert(kg::kRepairErrWords + 1 <= kPinStageWords && kg::kRepairCntWords + 2 <= kPinStageWords,
               "stage words must fit their pinned words");
 
+constexpr const char *kNotRepaired = "the set is not from kg_regionset_repair";
+
 int check_repair_params(const kg_repair_params *p)
 {
     if (!p) return fail(KG_ERR_ARG, "null kg_repair_params");
@@ -156,12 +158,11 @@ int repair_impl(kg_table *t, const kg_repair_params *prm, const kg_regionset *rs
         hipLaunchKernelGGL(kg::repair_record_kernel, dim3(grid_of(nr)), dim3(256), 0, s, regions, nr, pl.d_off, S, reg_first, reg_last, max_j, d_out, lens,
                            jcount, cnt);
         HIP_TRY(hipGetLastError());
-        if ((rc = prefix_sum(t, lens, nr, excl, partial, (uint64_t *)(words + kRepairWResidues)))) return rc;
-        if ((rc = prefix_sum(t, jcount, nr, jexcl, partial, (uint64_t *)(words + kRepairWJunctions)))) return rc;
     }
-    hipLaunchKernelGGL(kg::orf_prot_start_kernel, dim3(grid_of(nr + 1)), dim3(256), 0, s, excl, (const uint64_t *)(words + kRepairWResidues), nr, d_start);
-    hipLaunchKernelGGL(kg::orf_prot_start_kernel, dim3(grid_of(nr + 1)), dim3(256), 0, s, jexcl, (const uint64_t *)(words + kRepairWJunctions), nr, d_jstart);
-    HIP_TRY(hipGetLastError());
+    // where every protein and every record's junctions begin
+    if ((rc = layout_proteins(t, lens, nr, excl, partial, (uint64_t *)(words + kRepairWResidues), d_start)) ||
+        (rc = layout_proteins(t, jcount, nr, jexcl, partial, (uint64_t *)(words + kRepairWJunctions), d_jstart)))
+        return rc;
     // the second wait: the residue and junction totals and the counters
     if ((rc = read_error_words(t, cnt, kg::kRepairCntWords + 2, kPinStage, {}))) return rc;
     const uint64_t n_res = h[kg::kRepairCntWords], n_junc = h[kg::kRepairCntWords + 1];
@@ -195,17 +196,11 @@ int repair_impl(kg_table *t, const kg_repair_params *prm, const kg_regionset *rs
     st.junctions = (int64_t)n_junc;
     st.residues = (int64_t)h[kg::kRepairCntResidues];
     HIP_TRY(hipEventElapsedTime(&st.ms, t->ev[kEvStageBegin], t->ev[kEvStageEnd]));
-    // the five arrays of the set leave the scratch: everything else goes back to the cache
-    set->d_orfs = set->keep(sc, d_out);
-    set->d_prot_start = set->keep(sc, d_start);
-    set->d_res = set->keep(sc, d_res);
+    keep_orfs(set, sc, d_out, d_start, d_res, nr, n_res, n_seqs);
     set->d_junctions = set->keep(sc, d_junc);
     set->d_junction_start = set->keep(sc, d_jstart);
     set->junctions = (int64_t)n_junc;
     set->repaired = true;
-    set->count = (int64_t)nr;
-    set->residues = (int64_t)n_res;
-    set->n_seqs = (int64_t)n_seqs;
     set->l_max = std::max(os->l_max, pl.l_max);
     return KG_OK;
 }
@@ -228,8 +223,7 @@ int kg_regionset_repair(kg_regionset *rs, kg_orfset *os, const kg_call *calls, i
     if ((uint64_t)n_calls >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more CALL records in one call");
     if (n_calls && !calls) return fail(KG_ERR_ARG, "null CALL records");
     uint64_t total = 0;
-    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total))) return rc;
-    if (n_seqs != rs->n_seqs) return fail(KG_ERR_ARG, "n_seqs is not the region set's");
+    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total, "region set's", rs->n_seqs))) return rc;
     if (n_calls && n_seqs == 0) return fail(KG_ERR_ARG, "CALL 0: container >= 6 * n_seqs");
     if (os->tab != rs->tab) return fail(KG_ERR_ARG, "the ORF set was not made from this region set (another context)");
     if (os->count != rs->count || os->n_seqs != rs->n_seqs)
@@ -273,22 +267,19 @@ int64_t kg_orfset_junctions_count(const kg_orfset *s) { return s ? s->junctions 
 
 int kg_orfset_junctions_copy(const kg_orfset *s, int64_t first, int64_t count, kg_junction *dst)
 {
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (!s->repaired) return fail(KG_ERR_ARG, "kg_orfset_junctions_copy: the set is not from kg_regionset_repair");
+    if (int rc = need_of_set(s, count <= 0 || dst, s && s->repaired, "kg_orfset_junctions_copy", kNotRepaired)) return rc;
     return copy_records(s, device_of(s), s->d_junctions, 1, s->junctions, first, count, dst, "kg_orfset_junctions_copy", "the list");
 }
 
 int kg_orfset_junctions_start(const kg_orfset *s, int64_t *dst)
 {
-    if (!s || !dst) return fail(KG_ERR_ARG, "null argument");
-    if (!s->repaired) return fail(KG_ERR_ARG, "kg_orfset_junctions_start: the set is not from kg_regionset_repair");
+    if (int rc = need_of_set(s, dst, s && s->repaired, "kg_orfset_junctions_start", kNotRepaired)) return rc;
     return copy_starts(s, device_of(s), s->d_junction_start, s->count, dst);
 }
 
 int kg_orfset_junctions_stats(const kg_orfset *s, kg_repair_stats *out)
 {
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    if (!s->repaired) return fail(KG_ERR_ARG, "kg_orfset_junctions_stats: the set is not from kg_regionset_repair");
+    if (int rc = need_of_set(s, out, s && s->repaired, "kg_orfset_junctions_stats", kNotRepaired)) return rc;
     *out = s->repair_st;
     return KG_OK;
 }

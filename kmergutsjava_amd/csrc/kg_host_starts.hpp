@@ -210,22 +210,30 @@ struct StartsWork {
         static const char *const what[kg::kStartErrWords] = {
             ": seq outside [0, n_seqs)", ": strand is neither 0 nor 1", ": outside its contig (0 <= left <= right <= L - 1 does not hold)",
             ": 3 * n_res exceeds right - left + 1", ": its region has another seq or strand, or begins in front of the record's start"};
-        int rc;
-        if ((rc = read_error_words(t, words, kg::kStartErrWords + kg::kStartCntWords, kPinStage, {}))) return rc;
-        // every word holds the first record with its error: the message names the first record with any
-        const uint64_t *h = t->h_pin + kPinStage;
-        const int first = (int)(std::min_element(h, h + kg::kStartErrWords) - h);
-        if (h[first] != kNoErr) return fail(KG_ERR_ARG, "record " + kmer_text((int64_t)h[first]) + what[first]);
-        return KG_OK;
+        return read_record_errors(t, words, kg::kStartErrWords + kg::kStartCntWords, kg::kStartErrWords, what);
     }
     uint64_t counter(int k) const { return t->h_pin[kPinStage + kg::kStartErrWords + k]; }
-    // trained 0 / 1 / 2 of the statistics
-    int decide(const kg_start_params *p, const kg_start_weights *caller)
+    // behind begin(): trained 0 / 1 / 2 of the statistics, and when it is not 0 list() and choose(); ev[1], ev[2]: the list has
+    // ended, the choices begin
+    int list_and_choose(const kg_start_params *p, const int32_t *T, const kg_start_weights *caller, const Events<4> &ev)
     {
+        int rc;
         st.trained = caller ? 2 : st.training_records >= p->min_train_starts ? 1 : 0;
-        return st.trained;
+        if (st.trained && (rc = list(T))) return rc;
+        HIP_TRY(hipEventRecord(ev[1], t->stream));
+        HIP_TRY(hipEventRecord(ev[2], t->stream));
+        return st.trained ? choose(p, caller) : KG_OK;
+    }
+    // behind the call's last wait: what moved, and the times between ev[0], ev[1] and ev[2], ev[3]
+    void finish(const Events<4> &ev)
+    {
+        st.moved = (int64_t)counter(kg::kStartCntMoved);
+        st.ms_count = ev.ms(0, 1);
+        st.ms_choose = ev.ms(2, 3);
     }
 };
+
+constexpr const char *kNoShifts = "the set has no shifts (it is not from kg_orfset_starts)";
 
 }  // namespace
 
@@ -248,8 +256,7 @@ int kg_orfset_starts(kg_orfset *os, const kg_start_params *p, const int32_t *tab
     if (rc) return rc;
     if (!table) return fail(KG_ERR_ARG, "null coding table");
     uint64_t total = 0;
-    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total))) return rc;
-    if (n_seqs != os->n_seqs) return fail(KG_ERR_ARG, "n_seqs is not the ORF set's");
+    if ((rc = check_orf_batch(seq, offsets, n_seqs, &total, "ORF set's", os->n_seqs))) return rc;
     if (rs && rs->n_seqs != n_seqs) return fail(KG_ERR_ARG, "n_seqs is not the region set's");
     if (rs && rs->count > os->count) return fail(KG_ERR_ARG, "the ORF set is shorter than the region set");
     if (total >= (1ull << 40)) return fail(KG_ERR_LIMIT, "2^40 or more bytes in one call");
@@ -263,10 +270,7 @@ int kg_orfset_starts(kg_orfset *os, const kg_start_params *p, const int32_t *tab
     if ((rc = make_set(cs, set))) return rc;
     set->start_model.reset(new (std::nothrow) kg_start_model());
     if (!set->start_model) return fail(KG_ERR_NOMEM, "out of host memory");
-    if (os->coding_model) {
-        set->coding_model.reset(new (std::nothrow) kg_coding_model(*os->coding_model));
-        if (!set->coding_model) return fail(KG_ERR_NOMEM, "out of host memory");
-    }
+    if ((rc = inherit(set.get(), os))) return rc;
     if ((rc = ev.create())) return rc;
     StartsWork w(t);
     const uint8_t *d_seq = nullptr;
@@ -282,50 +286,23 @@ int kg_orfset_starts(kg_orfset *os, const kg_start_params *p, const int32_t *tab
     HIP_TRY(hipEventRecord(ev[0], s));
     const kg::StartLimits lim = {rs ? rs->d_regions : nullptr, rs ? (uint64_t)rs->count : 0, nullptr};
     if ((rc = w.begin(p, os->d_orfs, n, lim, d_seq, offsets, (uint64_t)n_seqs))) return rc;
-    if (w.decide(p, weights)) {
-        if ((rc = w.list(table))) return rc;
-        HIP_TRY(hipEventRecord(ev[1], s));
-        HIP_TRY(hipEventRecord(ev[2], s));
-        if ((rc = w.choose(p, weights))) return rc;
-    } else {
-        HIP_TRY(hipEventRecord(ev[1], s));
-        HIP_TRY(hipEventRecord(ev[2], s));
-    }
+    if ((rc = w.list_and_choose(p, table, weights, ev))) return rc;
     if (d_S && n > 0) HIP_TRY(hipMemcpyAsync(d_S, os->d_coding, n * 8, hipMemcpyDeviceToDevice, s));
     if ((rc = w.apply(os->d_prot_start, d_out, d_shift, d_S, new_lens))) return rc;
-    uint64_t *d_total = (uint64_t *)(w.cnt + kg::kStartCntResidues);
-    if (n > 0 && (rc = prefix_sum(t, new_lens, n, new_excl, w.partial, d_total))) return rc;
-    hipLaunchKernelGGL(kg::orf_prot_start_kernel, dim3(grid_of(n + 1)), dim3(256), 0, s, new_excl, d_total, n, d_start);
-    HIP_TRY(hipGetLastError());
+    if ((rc = layout_proteins(t, new_lens, n, new_excl, w.partial, (uint64_t *)(w.cnt + kg::kStartCntResidues), d_start))) return rc;
     // the wait for the residue total
     if ((rc = w.check())) return rc;
     const uint64_t n_res = w.counter(kg::kStartCntResidues);
     uint8_t *d_res = nullptr;
-    if ((rc = w.sc.get(&d_res, std::max<uint64_t>(n_res, 1)))) return rc;
-    if (n_res > 0) {
-        // rule 9's "old protein from residue k on, residue 0 = 'M'" is the translation of the new record: rule 5 of the ORF section
-        hipLaunchKernelGGL(kg::orf_residues_kernel, dim3(grid_of((n_res + kg::kOrfResPerLane - 1) / kg::kOrfResPerLane)), dim3(256), 0, s,
-                           d_out, n, d_start, n_res, d_seq, w.d_off, d_res);
-        HIP_TRY(hipGetLastError());
-    }
+    // rule 9's "old protein from residue k on, residue 0 = 'M'" is the translation of the new record: rule 5 of the ORF section
+    if ((rc = translate_orfs(t, w.sc, d_out, n, d_start, n_res, d_seq, w.d_off, &d_res))) return rc;
     HIP_TRY(hipEventRecord(ev[3], s));
     HIP_TRY(hipStreamSynchronize(s));
-    w.st.moved = (int64_t)w.counter(kg::kStartCntMoved);
-    w.st.ms_count = ev.ms(0, 1);
-    w.st.ms_choose = ev.ms(2, 3);
-    // the arrays of the set leave the scratch: everything else goes back to the cache
-    set->d_orfs = set->keep(w.sc, d_out);
-    set->d_prot_start = set->keep(w.sc, d_start);
-    set->d_res = set->keep(w.sc, d_res);
+    w.finish(ev);
+    keep_orfs(set.get(), w.sc, d_out, d_start, d_res, n, n_res, (uint64_t)n_seqs);
     set->d_coding = set->keep(w.sc, d_S);
     set->d_shift = set->keep(w.sc, d_shift);
-    set->count = os->count;
-    set->residues = (int64_t)n_res;
-    set->n_seqs = os->n_seqs;
-    set->l_max = os->l_max;
-    set->st = os->st;
     set->st.residues = (int64_t)n_res;
-    set->coding_st = os->coding_st;
     *set->start_model = w.model;
     set->start_st = w.st;
     return hand_out(cs, set, out);
@@ -333,23 +310,20 @@ int kg_orfset_starts(kg_orfset *os, const kg_start_params *p, const int32_t *tab
 
 int kg_orfset_start_shifts(const kg_orfset *s, int64_t first, int64_t count, int32_t *dst)
 {
-    if (!s || (count > 0 && !dst)) return fail(KG_ERR_ARG, "null argument");
-    if (!s->d_shift) return fail(KG_ERR_ARG, "kg_orfset_start_shifts: the set has no shifts (it is not from kg_orfset_starts)");
+    if (int rc = need_of_set(s, count <= 0 || dst, s && s->d_shift, "kg_orfset_start_shifts", kNoShifts)) return rc;
     return copy_records(s, device_of(s), s->d_shift, 1, s->count, first, count, dst, "kg_orfset_start_shifts");
 }
 
 int kg_orfset_start_stats(const kg_orfset *s, kg_start_stats *out)
 {
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    if (!s->d_shift) return fail(KG_ERR_ARG, "kg_orfset_start_stats: the set has no shifts (it is not from kg_orfset_starts)");
+    if (int rc = need_of_set(s, out, s && s->d_shift, "kg_orfset_start_stats", kNoShifts)) return rc;
     *out = s->start_st;
     return KG_OK;
 }
 
 int kg_orfset_start_model(const kg_orfset *s, kg_start_model *out)
 {
-    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
-    if (!s->d_shift || !s->start_model) return fail(KG_ERR_ARG, "kg_orfset_start_model: the set has no shifts (it is not from kg_orfset_starts)");
+    if (int rc = need_of_set(s, out, s && s->d_shift && s->start_model, "kg_orfset_start_model", kNoShifts)) return rc;
     *out = *s->start_model;
     return KG_OK;
 }
@@ -382,15 +356,7 @@ int kg_starts_orfs(int device, const kg_start_params *p, const int32_t *table, c
     HIP_TRY(hipEventRecord(ev[0], s));
     const kg::StartLimits lim = {nullptr, 0, d_lim};
     if ((rc = w.begin(p, d_orfs, (uint64_t)n, lim, d_seq, offsets, (uint64_t)n_seqs))) return rc;
-    if (w.decide(p, weights)) {
-        if ((rc = w.list(table))) return rc;
-        HIP_TRY(hipEventRecord(ev[1], s));
-        HIP_TRY(hipEventRecord(ev[2], s));
-        if ((rc = w.choose(p, weights))) return rc;
-    } else {
-        HIP_TRY(hipEventRecord(ev[1], s));
-        HIP_TRY(hipEventRecord(ev[2], s));
-    }
+    if ((rc = w.list_and_choose(p, table, weights, ev))) return rc;
     if ((rc = w.apply(nullptr, d_out, d_shift, nullptr, nullptr))) return rc;
     HIP_TRY(hipEventRecord(ev[3], s));
     if (n > 0) {
@@ -398,9 +364,7 @@ int kg_starts_orfs(int device, const kg_start_params *p, const int32_t *table, c
         HIP_TRY(hipMemcpyAsync(shifts, d_shift, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     }
     if ((rc = w.check())) return rc;
-    w.st.moved = (int64_t)w.counter(kg::kStartCntMoved);
-    w.st.ms_count = ev.ms(0, 1);
-    w.st.ms_choose = ev.ms(2, 3);
+    w.finish(ev);
     if (model) *model = w.model;
     if (stats) *stats = w.st;
     return KG_OK;

@@ -57,6 +57,50 @@ def device_tensor(ptr: int, count: int, typestr: str = "|u1", owner=None, device
     return t
 
 
+def _ptr(a):
+    """The address of a numpy array's elements for the library; None for an array of none (and for None)."""
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _offsets(offsets, text: str, n: Optional[int] = None) -> np.ndarray:
+    """offsets as contiguous int64: one-dimensional and not empty, or with n exactly n + 1 entries; `text` says what they must be."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    if (off.ndim != 1 or off.size < 1) if n is None else off.shape != (n + 1,):
+        raise ValueError("offsets must be " + text)
+    return off
+
+
+def _seq_bytes(seq, off, no_sequence_too: bool = False) -> np.ndarray:
+    """The batch's bytes (bytes-like or an ndarray) as contiguous uint8, at least offsets[-1] of them; when there is no sequence
+    offsets[-1] is looked at only with no_sequence_too."""
+    arr = np.frombuffer(seq, dtype=np.uint8) if not isinstance(seq, np.ndarray) else seq
+    arr = np.ascontiguousarray(arr.view(np.uint8).reshape(-1))
+    if (off.size > 1 or no_sequence_too) and arr.size < int(off[-1]):
+        raise ValueError("sequence buffer shorter than offsets[-1]")
+    return arr
+
+
+def _signature_arg(sigs):
+    """The signatures SignatureTable.build / merge_signatures are given: a contiguous CUDA tensor of 24 * n bytes, or a numpy
+    array of _native.SIGNATURE_DTYPE or raw bytes of 24-byte records.  -> (the records are on the device, their address or None
+    for none, n, what keeps them alive for the call)."""
+    if hasattr(sigs, "is_cuda") and sigs.is_cuda:
+        if not sigs.is_contiguous():
+            raise ValueError("the signature tensor must be contiguous")
+        nbytes = sigs.numel() * sigs.element_size()
+        if nbytes % 24:
+            raise ValueError("the signature tensor must hold 24 * n bytes")
+        return True, C.c_void_p(sigs.data_ptr() if nbytes else None), nbytes // 24, sigs
+    arr = sigs if isinstance(sigs, np.ndarray) else np.frombuffer(sigs, dtype=np.uint8)
+    arr = np.ascontiguousarray(arr)
+    if arr.dtype != N.SIGNATURE_DTYPE:
+        arr = arr.reshape(-1).view(np.uint8)
+        if arr.size % 24:
+            raise ValueError("signature bytes must be a multiple of 24")
+    n = arr.nbytes // 24
+    return False, _ptr(arr), n, arr
+
+
 def _copy_records(copy, h, n: int, dtype, shape=(), device_out: bool = False):
     """Records [0, n) of a set, each `shape` elements of `dtype`, through the set's range getter `copy`.  -> a numpy array
     of (n,) + shape; or with device_out a CUDA tensor: uint8 of itemsize bytes per record for a record dtype, the typed
@@ -64,7 +108,7 @@ def _copy_records(copy, h, n: int, dtype, shape=(), device_out: bool = False):
     dtype = np.dtype(dtype)
     if not device_out:
         a = np.zeros((n,) + tuple(shape), dtype=dtype)
-        N.check(copy(h, 0, n, a.ctypes.data if n else None))
+        N.check(copy(h, 0, n, _ptr(a)))
         return a
     import torch
     if dtype.names:
@@ -74,6 +118,32 @@ def _copy_records(copy, h, n: int, dtype, shape=(), device_out: bool = False):
     torch.cuda.synchronize()            # the library works on its own stream
     N.check(copy(h, 0, n, C.c_void_p(a.data_ptr() if n else None)))
     return a
+
+
+class _OrfChain:
+    """Owns the kg_orfset at the head of a chain of ORF steps (`h`, null when there is none).  Every step makes a new set from
+    the current one, which is then freed whether the step failed or not: the new set holds copies and lives in the same
+    context.  release() passes the set on (to _take_orfset, which frees it); close() frees what is still held."""
+
+    def __init__(self, lib):
+        self.lib, self.h = lib, C.c_void_p()
+
+    def step(self, call) -> None:
+        """call(the current set, byref(the new set)) -> the library's return code."""
+        old, self.h = self.h, C.c_void_p()
+        try:
+            N.check(call(old, C.byref(self.h)))
+        finally:
+            if old:
+                self.lib.kg_orfset_free(old)
+
+    def release(self):
+        h, self.h = self.h, C.c_void_p()
+        return h
+
+    def close(self) -> None:
+        if self.h:
+            self.lib.kg_orfset_free(self.release())
 
 
 class ScanResult:
@@ -219,7 +289,7 @@ class ScanResult:
             N.check(lib.kg_result_assign(self._h, C.byref(p), C.c_void_p(out.data_ptr() if n else None), C.byref(ms)))
         else:
             out = np.zeros(n, dtype=N.ASSIGNMENT_DTYPE)
-            N.check(lib.kg_result_assign(self._h, C.byref(p), out.ctypes.data if n else None, C.byref(ms)))
+            N.check(lib.kg_result_assign(self._h, C.byref(p), _ptr(out), C.byref(ms)))
         self.assign_ms = float(ms.value)
         return out
 
@@ -230,9 +300,7 @@ class ScanResult:
         CUDA uint8 tensor of 48 bytes per region; region_start int64[n_seqs + 1], contig s owning records
         [region_start[s], region_start[s + 1]).  The call's counts and device time are left in `region_stats`."""
         lib = self._need()
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-        if off.shape != (self.stats["n_seqs"] + 1,):
-            raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
+        off = _offsets(offsets, "the int64[n_seqs + 1] the scan was given", self.stats["n_seqs"])
         p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
         h = C.c_void_p()
         N.check(lib.kg_result_regions(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
@@ -247,9 +315,7 @@ class ScanResult:
         first).  With device_out=True the three record arrays are CUDA uint8 tensors.  The call's counts and device time are
         left in `vote_stats`."""
         lib = self._need()
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-        if off.shape != (self.stats["n_seqs"] + 1,):
-            raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
+        off = _offsets(offsets, "the int64[n_seqs + 1] the scan was given", self.stats["n_seqs"])
         p = N.KgVoteParams(int(min_votes), int(min_share_pct), int(min_calls), 0)
         h = C.c_void_p()
         N.check(lib.kg_result_otu_votes(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
@@ -287,32 +353,16 @@ class ScanResult:
         lib = self._need()
         coding = _coding_arg(coding)
         starts = _starts_arg(starts, coding)
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-        if off.shape != (self.stats["n_seqs"] + 1,):
-            raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
+        off = _offsets(offsets, "the int64[n_seqs + 1] the scan was given", self.stats["n_seqs"])
         p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
-        h = C.c_void_p()
+        h, chain = C.c_void_p(), _OrfChain(lib)
         N.check(lib.kg_result_regions(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
         try:
-            if device_ptr is not None:
-                ptr, on_device, keep = C.c_void_p(device_ptr), 1, None
-            else:
-                keep = _seq_bytes(seq, off)
-                ptr, on_device = (keep.ctypes.data if keep.size else None), 0
-            op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
-            oh = C.c_void_p()
-            N.check(lib.kg_regionset_orfs(h, C.byref(op), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(oh)))
-            if repair:
-                oh = self._repair(h, oh, start_codons, repair_min_count, max_junctions, ptr, on_device, off)
-            if free_min_res is not None:
-                oh = _add_free(oh, free_min_res, start_codons, ptr, on_device, off)
-            if coding is not None:
-                oh = _coding(oh, coding, min_coding, min_train_pairs, ptr, on_device, off)
-                self.coding_scores, self.coding_stats, self.coding_model = _coding_results(oh)
-            if starts is not None:
-                oh = self._starts(oh, h, coding, starts, start_codons, start_min_res, start_rounds, min_train_starts, ptr, on_device, off)
-            orfs, prot_start, residues, self.orf_stats = _take_orfset(oh, False)
+            self._orf_steps(chain, h, seq, device_ptr, off, start_codons, only_kept, repair, repair_min_count, max_junctions, free_min_res,
+                            coding, min_coding, min_train_pairs, starts, start_min_res, start_rounds, min_train_starts)
+            orfs, prot_start, residues, self.orf_stats = _take_orfset(chain.release(), False)
         except BaseException:
+            chain.close()
             lib.kg_regionset_free(h)
             raise
         regs, start, self.region_stats = _take_regionset(h, self.stats["n_seqs"], False)
@@ -345,45 +395,26 @@ class ScanResult:
         if repair and not orfs:
             raise ValueError("repair needs orfs=True: it rewrites ORFs")
         starts = _starts_arg(starts, coding)
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-        if off.shape != (self.stats["n_seqs"] + 1,):
-            raise ValueError("offsets must be the int64[n_seqs + 1] the scan was given")
+        off = _offsets(offsets, "the int64[n_seqs + 1] the scan was given", self.stats["n_seqs"])
         p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
         sp = N.KgSelectParams(int(max_overlap), int(max_overlap_pct), 0)
-        h, oh, sh = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        h, sh, chain = C.c_void_p(), C.c_void_p(), _OrfChain(lib)
         N.check(lib.kg_result_regions(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
         try:
             if orfs:
-                if device_ptr is not None:
-                    ptr, on_device, keep = C.c_void_p(device_ptr), 1, None
-                else:
-                    keep = _seq_bytes(seq, off)
-                    ptr, on_device = (keep.ctypes.data if keep.size else None), 0
-                op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
-                N.check(lib.kg_regionset_orfs(h, C.byref(op), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(oh)))
-                if repair:
-                    oh = self._repair(h, oh, start_codons, repair_min_count, max_junctions, ptr, on_device, off)
-                if free_min_res is not None:
-                    oh = _add_free(oh, free_min_res, start_codons, ptr, on_device, off)
-                if coding is not None:
-                    oh = _coding(oh, coding, min_coding, min_train_pairs, ptr, on_device, off)
-                    self.coding_scores, self.coding_stats, self.coding_model = _coding_results(oh)
-                if starts is not None:
-                    oh = self._starts(oh, h, coding, starts, start_codons, start_min_res, start_rounds, min_train_starts, ptr,
-                                      on_device, off)
-                N.check(lib.kg_orfset_select(oh, C.byref(sp), C.byref(sh)))
+                self._orf_steps(chain, h, seq, device_ptr, off, start_codons, only_kept, repair, repair_min_count, max_junctions,
+                                free_min_res, coding, min_coding, min_train_pairs, starts, start_min_res, start_rounds, min_train_starts)
+                N.check(lib.kg_orfset_select(chain.h, C.byref(sp), C.byref(sh)))
             else:
                 N.check(lib.kg_regionset_select(h, C.byref(sp), C.byref(sh)))
             taken, sh = sh, C.c_void_p()                # (_take_* frees what it is given, also when it raises)
             sel, self.select_stats = _take_selectset(taken, False)      # a select set is freed before the set it came from
             if orfs:
-                taken, oh = oh, C.c_void_p()
-                orf_recs, prot_start, residues, self.orf_stats = _take_orfset(taken, False)
+                orf_recs, prot_start, residues, self.orf_stats = _take_orfset(chain.release(), False)
         except BaseException:
             if sh:
                 lib.kg_selectset_free(sh)
-            if oh:
-                lib.kg_orfset_free(oh)
+            chain.close()
             lib.kg_regionset_free(h)
             raise
         regs, start, self.region_stats = _take_regionset(h, self.stats["n_seqs"], False)
@@ -391,38 +422,40 @@ class ScanResult:
             return regs, start, orf_recs, prot_start, residues, sel
         return regs, start, sel
 
-    def _repair(self, rh, oh, start_codons, min_count, max_junctions, ptr, on_device, off):
-        """kg_result_repair behind kg_regionset_orfs in orfs() / select(): -> the new set's handle (the given one is freed); the
-        junction list and the statistics into self."""
-        lib = N.load()
-        rp = N.KgRepairParams(int(start_codons), int(min_count), int(max_junctions), 0)
-        new = C.c_void_p()
-        try:
-            N.check(lib.kg_result_repair(self._h, rh, oh, C.byref(rp), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(new)))
-        finally:
-            lib.kg_orfset_free(oh)          # (the new set holds copies: the given one is not needed any more)
-            oh.value = None
-        try:
-            self.junctions, self.junction_start, self.repair_stats = _junctions(new)
-        except BaseException:
-            lib.kg_orfset_free(new)
-            raise
-        return new
-
-    def _starts(self, oh, rh, coding, starts, start_codons, min_res, rounds, min_train_starts, ptr, on_device, off):
-        """kg_orfset_starts behind the coding step of orfs() / select(): -> the new set's handle; the results into self."""
-        if coding is True:
-            # the table the coding step trained and used; none when it was untrained, and then the starts are untrained too
-            trained = self.coding_stats["trained"] != 0
-            table = coding_table(*self.coding_model) if trained else np.zeros(N.CODING_BINS, dtype=np.int32)
-            if not trained and starts is True:
-                min_train_starts = 1 << 62
-        else:
+    def _orf_steps(self, chain, rh, seq, device_ptr, off, start_codons, only_kept, repair, repair_min_count, max_junctions, free_min_res,
+                   coding, min_coding, min_train_pairs, starts, start_min_res, start_rounds, min_train_starts):
+        """The steps of orfs() and select(orfs=True) behind the region set rh, each on the set the one before it left in `chain`:
+        kg_regionset_orfs, then kg_result_repair, kg_orfset_add_free, kg_orfset_coding and kg_orfset_starts where they are asked
+        for (coding and starts: what _coding_arg and _starts_arg gave).  The steps' side results go into self."""
+        lib = chain.lib
+        keep = None if device_ptr is not None else _seq_bytes(seq, off)        # (alive while the steps read it)
+        batch = (C.c_void_p(device_ptr) if keep is None else _ptr(keep), int(keep is None), off.ctypes.data, off.size - 1)
+        op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
+        chain.step(lambda oh, new: lib.kg_regionset_orfs(rh, C.byref(op), *batch, new))
+        if repair:
+            rp = N.KgRepairParams(int(start_codons), int(repair_min_count), int(max_junctions), 0)
+            chain.step(lambda oh, new: lib.kg_result_repair(self._h, rh, oh, C.byref(rp), *batch, new))
+            self.junctions, self.junction_start, self.repair_stats = _junctions(chain.h)
+        if free_min_res is not None:
+            fp = N.KgFreeParams(int(free_min_res), int(start_codons), 0)
+            chain.step(lambda oh, new: lib.kg_orfset_add_free(oh, C.byref(fp), *batch, new))
+        if coding is not None:
+            cp = N.KgCodingParams(int(min_coding), 0, int(min_train_pairs))
+            chain.step(lambda oh, new: lib.kg_orfset_coding(oh, C.byref(cp), None if coding is True else coding.ctypes.data, *batch, new))
+            self.coding_scores, self.coding_stats, self.coding_model = _coding_results(chain.h)
+        if starts is not None:
             table = coding
-        oh = _starts(oh, rh, table, None if starts is True else starts, min_res, start_codons, rounds, min_train_starts, ptr, on_device, off)
-        self.start_shifts, self.start_stats, self.start_model = _starts_results(oh)
-        self.coding_scores = _coding_results(oh)[0]
-        return oh
+            if coding is True:
+                # the table the coding step trained and used; none when it was untrained, and then the starts are untrained too
+                trained = self.coding_stats["trained"] != 0
+                table = coding_table(*self.coding_model) if trained else np.zeros(N.CODING_BINS, dtype=np.int32)
+                if not trained and starts is True:
+                    min_train_starts = 1 << 62
+            sp = N.KgStartParams(int(start_min_res), int(start_codons), int(start_rounds), 0, int(min_train_starts))
+            chain.step(lambda oh, new: lib.kg_orfset_starts(oh, C.byref(sp), table.ctypes.data, None if starts is True else C.addressof(starts),
+                                                            rh, *batch, new))
+            self.start_shifts, self.start_stats, self.start_model = _starts_results(chain.h)
+            self.coding_scores = _coding_results(chain.h)[0]
 
     def close(self) -> None:
         if self._h:
@@ -454,8 +487,8 @@ def aggregate_hits(hits: np.ndarray, container_hit_start, n_seqs: int, params: O
         raise ValueError("container_hit_start must have n_seqs * (1 or 6) + 1 entries")
     init = None if otu_init is None else np.ascontiguousarray(otu_init, dtype=N.OTU_DTYPE)
     out = C.c_void_p()
-    N.check(N.load().kg_aggregate_hits(device, C.byref(p), h.ctypes.data if h.size else None, chs.ctypes.data, n_seqs,
-                                       init.ctypes.data if init is not None and init.size else None, C.byref(out)))
+    N.check(N.load().kg_aggregate_hits(device, C.byref(p), _ptr(h), chs.ctypes.data, n_seqs,
+                                       _ptr(init), C.byref(out)))
     return ScanResult(out.value)
 
 
@@ -499,24 +532,12 @@ class SignatureTable:
         out, placed = C.c_void_p(), C.c_int64()
         lib = N.load()
         dev = device
-        if hasattr(signatures, "is_cuda") and signatures.is_cuda:
-            if not signatures.is_contiguous():
-                raise ValueError("the signature tensor must be contiguous")
-            nbytes = signatures.numel() * signatures.element_size()
-            if nbytes % 24:
-                raise ValueError("the signature tensor must hold 24 * n bytes")
+        on_device, ptr, n, _keep = _signature_arg(signatures)
+        if on_device:
             dev = signatures.device.index if signatures.device.index is not None else device
-            N.check(lib.kg_table_build_device(C.c_void_p(signatures.data_ptr() if nbytes else None), nbytes // 24, int(num_sigs),
-                                              dev, C.byref(placed), C.byref(out)))
+            N.check(lib.kg_table_build_device(ptr, n, int(num_sigs), dev, C.byref(placed), C.byref(out)))
         else:
-            arr = signatures if isinstance(signatures, np.ndarray) else np.frombuffer(signatures, dtype=np.uint8)
-            arr = np.ascontiguousarray(arr)
-            if arr.dtype != N.SIGNATURE_DTYPE:
-                arr = arr.reshape(-1).view(np.uint8)
-                if arr.size % 24:
-                    raise ValueError("signature bytes must be a multiple of 24")
-            n = arr.nbytes // 24
-            N.check(lib.kg_table_build(arr.ctypes.data if n else None, n, int(num_sigs), device, C.byref(placed), C.byref(out)))
+            N.check(lib.kg_table_build(ptr, n, int(num_sigs), device, C.byref(placed), C.byref(out)))
         tab = cls(out.value, device=dev)
         tab.placed = int(placed.value)
         return tab
@@ -549,25 +570,9 @@ class SignatureTable:
         op = None if om is None else (om.ctypes.data if om.size else none.ctypes.data)
         out = C.c_void_p()
         lib = N.load()
-        if sigs is not None and hasattr(sigs, "is_cuda") and sigs.is_cuda:
-            if not sigs.is_contiguous():
-                raise ValueError("the signature tensor must be contiguous")
-            nbytes = sigs.numel() * sigs.element_size()
-            if nbytes % 24:
-                raise ValueError("the signature tensor must hold 24 * n bytes")
-            N.check(lib.kg_table_merge_signatures_device(self._h, C.byref(p), C.c_void_p(sigs.data_ptr() if nbytes else None),
-                                                         nbytes // 24, fp, n_fn, op, n_otu, C.byref(out)))
-        else:
-            arr = np.zeros(0, dtype=N.SIGNATURE_DTYPE) if sigs is None else sigs
-            arr = arr if isinstance(arr, np.ndarray) else np.frombuffer(arr, dtype=np.uint8)
-            arr = np.ascontiguousarray(arr)
-            if arr.dtype != N.SIGNATURE_DTYPE:
-                arr = arr.reshape(-1).view(np.uint8)
-                if arr.size % 24:
-                    raise ValueError("signature bytes must be a multiple of 24")
-            n = arr.nbytes // 24
-            N.check(lib.kg_table_merge_signatures(self._h, C.byref(p), arr.ctypes.data if n else None, n, fp, n_fn, op, n_otu,
-                                                  C.byref(out)))
+        on_device, ptr, n, _keep = _signature_arg(np.zeros(0, dtype=N.SIGNATURE_DTYPE) if sigs is None else sigs)
+        merge = lib.kg_table_merge_signatures_device if on_device else lib.kg_table_merge_signatures
+        N.check(merge(self._h, C.byref(p), ptr, n, fp, n_fn, op, n_otu, C.byref(out)))
         return SignatureSet(out.value, self.device)
 
     def signatures(self) -> "SignatureSet":
@@ -603,21 +608,15 @@ class SignatureTable:
             raise ValueError("SignatureTable is closed")
         params = params or Params()
         p = params.to_native()
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-        if off.ndim != 1 or off.size < 1:
-            raise ValueError("offsets must be int64[n_seqs + 1]")
+        off = _offsets(offsets, "int64[n_seqs + 1]")
         n = off.size - 1
         out = C.c_void_p()
         lib = N.load()
         if device_ptr is not None:
             N.check(lib.kg_scan_device(self._h, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, C.byref(out)))
         else:
-            arr = np.frombuffer(seq, dtype=np.uint8) if not isinstance(seq, np.ndarray) else seq
-            arr = np.ascontiguousarray(arr.view(np.uint8).reshape(-1))
-            if arr.size < int(off[-1]):
-                raise ValueError("sequence buffer shorter than offsets[-1]")
-            ptr = arr.ctypes.data if arr.size else None
-            N.check(lib.kg_scan(self._h, C.byref(p), ptr, off.ctypes.data, n, C.byref(out)))
+            arr = _seq_bytes(seq, off, no_sequence_too=True)
+            N.check(lib.kg_scan(self._h, C.byref(p), _ptr(arr), off.ctypes.data, n, C.byref(out)))
         r = ScanResult(out.value, self)
         self._results.add(r)
         return r
@@ -708,9 +707,7 @@ def derive_signatures(seq, offsets, fn, otu, min_proteins: int = 2, purity_pct: 
     address in HBM; offsets: int64[n_prot + 1]; fn / otu: int32[n_prot] (fn = -1: unannotated).  The defaults
     min_proteins = 2 and purity_pct = 80 are this project's choice (the reference only reads signatures);
     max_windows_per_pass = 0 sizes the passes from free device memory."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_prot + 1]")
+    off = _offsets(offsets, "int64[n_prot + 1]")
     n = off.size - 1
     f = np.ascontiguousarray(np.asarray(fn, dtype=np.int64))
     o = np.ascontiguousarray(np.asarray(otu, dtype=np.int64))
@@ -722,16 +719,12 @@ def derive_signatures(seq, offsets, fn, otu, min_proteins: int = 2, purity_pct: 
     p = N.KgDeriveParams(int(min_proteins), int(purity_pct), int(max_windows_per_pass))
     out = C.c_void_p()
     lib = N.load()
-    fp, op = (f32.ctypes.data if n else None), (o32.ctypes.data if n else None)
+    fp, op = _ptr(f32), _ptr(o32)
     if device_ptr is not None:
         N.check(lib.kg_signatures_derive_device(device, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, fp, op, C.byref(out)))
     else:
-        arr = np.frombuffer(seq, dtype=np.uint8) if not isinstance(seq, np.ndarray) else seq
-        arr = np.ascontiguousarray(arr.view(np.uint8).reshape(-1))
-        if n and arr.size < int(off[-1]):
-            raise ValueError("sequence buffer shorter than offsets[-1]")
-        ptr = arr.ctypes.data if arr.size else None
-        N.check(lib.kg_signatures_derive(device, C.byref(p), ptr, off.ctypes.data, n, fp, op, C.byref(out)))
+        arr = _seq_bytes(seq, off)
+        N.check(lib.kg_signatures_derive(device, C.byref(p), _ptr(arr), off.ctypes.data, n, fp, op, C.byref(out)))
     return SignatureSet(out.value, device)
 
 
@@ -749,7 +742,7 @@ def _align_params(min_ratio_pct: int = 50, ref="longer", gap_open: int = 11, gap
             raise ValueError("matrix must be 21 x 21 and fit int8")
         mat = np.ascontiguousarray(mat.astype(np.int8))
     return N.KgAlignParams(int(min_ratio_pct), int(ref), int(gap_open), int(gap_extend), int(max_cells),
-                           mat.ctypes.data if mat is not None else None, 0), mat
+                           _ptr(mat), 0), mat
 
 
 def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1, max_cells: int = N.ALIGN_DEFAULT_MAX_CELLS, matrix=None,
@@ -758,9 +751,7 @@ def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1,
     gaps, no traceback, the built-in matrix is BLOSUM62 (align_scores.BLOSUM62); matrix: 21 x 21 in code order.  seq / offsets /
     device_ptr as for cluster_proteins; pairs: int32[n_pairs][2] of (a, b) protein indices, any order, repeats allowed.
     -> _native.ALIGNMENT_DTYPE[n_pairs] in pair order (status 1 and score -1: more than max_cells cells, not aligned)."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_prot + 1]")
+    off = _offsets(offsets, "int64[n_prot + 1]")
     n = off.size - 1
     pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
     if pr.size and (pr.min() < -2 ** 31 or pr.max() >= 2 ** 31):
@@ -769,12 +760,12 @@ def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1,
     p, _keep = _align_params(gap_open=gap_open, gap_extend=gap_extend, max_cells=max_cells, matrix=matrix)
     out = np.zeros(len(pr), dtype=N.ALIGNMENT_DTYPE)
     lib = N.load()
-    pp, op = (pr.ctypes.data if len(pr) else None), (out.ctypes.data if len(pr) else None)
+    pp, op = _ptr(pr), _ptr(out)
     if device_ptr is not None:
         N.check(lib.kg_proteins_align_device(device, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, pp, len(pr), op))
     else:
         arr = _seq_bytes(seq, off)
-        N.check(lib.kg_proteins_align(device, C.byref(p), arr.ctypes.data if arr.size else None, off.ctypes.data, n, pp, len(pr), op))
+        N.check(lib.kg_proteins_align(device, C.byref(p), _ptr(arr), off.ctypes.data, n, pp, len(pr), op))
     return out
 
 
@@ -790,9 +781,7 @@ def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20,
     only if 100 * score >= min_ratio_pct * ref; the statistics then also hold "edge_records" (_native.FAMILY_EDGE_DTYPE, one per
     such link in (member, centre) order) and "align" (aligned, cut, skipped, cells, ms_align).
     -> (numpy records of _native.FAMILY_DTYPE in protein order, the call's statistics)."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_prot + 1]")
+    off = _offsets(offsets, "int64[n_prot + 1]")
     n = off.size - 1
     p = N.KgClusterParams(int(min_shared), int(min_cover_pct), 0)
     h = C.c_void_p()
@@ -804,13 +793,13 @@ def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20,
                                                            int(max_windows), C.byref(h)))
         else:
             arr = _seq_bytes(seq, off)
-            N.check(lib.kg_proteins_cluster_aligned(device, C.byref(p), C.byref(ap), arr.ctypes.data if arr.size else None, off.ctypes.data,
+            N.check(lib.kg_proteins_cluster_aligned(device, C.byref(p), C.byref(ap), _ptr(arr), off.ctypes.data,
                                                     n, int(max_windows), C.byref(h)))
     elif device_ptr is not None:
         N.check(lib.kg_proteins_cluster_device(device, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, int(max_windows), C.byref(h)))
     else:
         arr = _seq_bytes(seq, off)
-        N.check(lib.kg_proteins_cluster(device, C.byref(p), arr.ctypes.data if arr.size else None, off.ctypes.data, n, int(max_windows),
+        N.check(lib.kg_proteins_cluster(device, C.byref(p), _ptr(arr), off.ctypes.data, n, int(max_windows),
                                         C.byref(h)))
     try:
         st = N.KgClusterStats()
@@ -835,9 +824,7 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
     (the defaults) or a dict as for cluster_proteins; max_windows = 0 and max_pairs = 0 size the one pass and the join from
     free device memory.  The defaults 2, 8 and 256 are this project's choice.
     -> (numpy records of _native.SEARCH_HIT_DTYPE in (query, rank) order, hit_start int64[n_q + 1], the call's statistics)."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_prot + 1]")
+    off = _offsets(offsets, "int64[n_prot + 1]")
     n = off.size - 1
     p = N.KgSearchParams(int(min_shared), int(max_cand), int(max_db_per_kmer), 0)
     ap, _keep = _align_params(**(align or {}))
@@ -848,7 +835,7 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
                                               int(max_windows), int(max_pairs), C.byref(h)))
     else:
         arr = _seq_bytes(seq, off)
-        N.check(lib.kg_proteins_search(device, C.byref(p), C.byref(ap), arr.ctypes.data if arr.size else None, off.ctypes.data, n,
+        N.check(lib.kg_proteins_search(device, C.byref(p), C.byref(ap), _ptr(arr), off.ctypes.data, n,
                                        int(n_db), int(max_windows), int(max_pairs), C.byref(h)))
     try:
         st = N.KgSearchStats()
@@ -876,8 +863,8 @@ def assign_calls(calls, call_start, otu=None, min_score: int = 0, min_share_pct:
         raise ValueError("otu must hold one record per protein")
     out = np.zeros(n, dtype=N.ASSIGNMENT_DTYPE)
     p = N.KgAssignParams(int(min_score), int(min_share_pct))
-    N.check(N.load().kg_assign_calls(device, C.byref(p), c.ctypes.data if c.size else None, cs.ctypes.data, n,
-                                     o.ctypes.data if o is not None and n else None, out.ctypes.data if n else None))
+    N.check(N.load().kg_assign_calls(device, C.byref(p), _ptr(c), cs.ctypes.data, n,
+                                     _ptr(o), _ptr(out)))
     return out
 
 
@@ -901,13 +888,11 @@ def region_calls(calls, offsets, merge_gap: int = 600, min_score: int = 0, min_l
     """Function regions from caller-held CALL records of a DNA scan, on the GPU (kg_regions_calls): calls CALL_DTYPE in
     non-decreasing container order, offsets int64[n_seqs + 1].  -> (records, region_start) as ScanResult.regions; `stats`, when
     given, receives the call's counts and device time."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_seqs + 1]")
+    off = _offsets(offsets, "int64[n_seqs + 1]")
     c = np.ascontiguousarray(calls, dtype=N.CALL_DTYPE)
     p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
     h = C.c_void_p()
-    N.check(N.load().kg_regions_calls(device, C.byref(p), c.ctypes.data if c.size else None, c.size, off.ctypes.data,
+    N.check(N.load().kg_regions_calls(device, C.byref(p), _ptr(c), c.size, off.ctypes.data,
                                       off.size - 1, C.byref(h)))
     out, start, st = _take_regionset(h, off.size - 1, device_out)
     if stats is not None:
@@ -939,12 +924,10 @@ def otu_votes(hits, container_hit_start, hit_events, calls, container_call_start
     with container_hit_start int64[n_seqs * per + 1], hit_events one KG_EV_* byte per hit, calls CALL_DTYPE with
     container_call_start, per 6 (DNA) or 1 (-a), offsets int64[n_seqs + 1].  -> (votes, vote_start, classes, bins) as
     ScanResult.otu_votes; `stats`, when given, receives the call's counts and device time."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
     chs = np.ascontiguousarray(np.asarray(container_hit_start, dtype=np.int64))
     ccs = np.ascontiguousarray(np.asarray(container_call_start, dtype=np.int64))
     n_seqs, per = int(n_seqs), int(per)
-    if off.shape != (n_seqs + 1,):
-        raise ValueError("offsets must be int64[n_seqs + 1]")
+    off = _offsets(offsets, "int64[n_seqs + 1]", n_seqs)
     n_cont = n_seqs * per if per > 0 else 0
     if chs.shape != (n_cont + 1,) or ccs.shape != (n_cont + 1,):
         raise ValueError("container_hit_start and container_call_start must be int64[n_seqs * per + 1]")
@@ -955,21 +938,13 @@ def otu_votes(hits, container_hit_start, hit_events, calls, container_call_start
         raise ValueError("the start arrays reach beyond the records, or hit_events is not one byte per hit")
     p = N.KgVoteParams(int(min_votes), int(min_share_pct), int(min_calls), 0)
     h = C.c_void_p()
-    N.check(N.load().kg_otu_votes_hits(device, C.byref(p), hh.ctypes.data if hh.size else None, chs.ctypes.data,
-                                       ev.ctypes.data if ev.size else None, c.ctypes.data if c.size else None, ccs.ctypes.data,
+    N.check(N.load().kg_otu_votes_hits(device, C.byref(p), _ptr(hh), chs.ctypes.data,
+                                       _ptr(ev), _ptr(c), ccs.ctypes.data,
                                        n_seqs, per, off.ctypes.data, C.byref(h)))
     votes, start, classes, bins, st = _take_voteset(h, n_seqs, device_out)
     if stats is not None:
         stats.update(st)
     return votes, start, classes, bins
-
-
-def _seq_bytes(seq, off) -> np.ndarray:
-    arr = np.frombuffer(seq, dtype=np.uint8) if not isinstance(seq, np.ndarray) else seq
-    arr = np.ascontiguousarray(arr.view(np.uint8).reshape(-1))
-    if off.size > 1 and arr.size < int(off[-1]):
-        raise ValueError("sequence buffer shorter than offsets[-1]")
-    return arr
 
 
 def compose_contigs(seq, offsets, labels=None, model=None, min_len: int = 1500, min_margin: int = 2560, min_train: int = 200000,
@@ -981,9 +956,7 @@ def compose_contigs(seq, offsets, labels=None, model=None, min_len: int = 1500, 
     "background": int64[256], "model_labels": int32[M]} and with keep_scores "scores": int64[n_seqs][M + 1]; classes, counts and
     scores are CUDA tensors with device_out=True (classes as uint8 of 40 bytes per contig).  `stats`, when given, receives the
     call's counts and device times."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_seqs + 1]")
+    off = _offsets(offsets, "int64[n_seqs + 1]")
     n = off.size - 1
     arr = _seq_bytes(seq, off)
     lab = None
@@ -1002,9 +975,9 @@ def compose_contigs(seq, offsets, labels=None, model=None, min_len: int = 1500, 
     p = N.KgCompParams(int(min_len), int(min_margin), int(min_train), 1 if keep_scores else 0, 0)
     lib = N.load()
     h = C.c_void_p()
-    N.check(lib.kg_contigs_compose(device, C.byref(p), arr.ctypes.data if arr.size else None, 0, off.ctypes.data, n,
-                                   lab.ctypes.data if lab is not None and n else None, ml.ctypes.data if n_models else None,
-                                   mc.ctypes.data if mc is not None else None, n_models, C.byref(h)))
+    N.check(lib.kg_contigs_compose(device, C.byref(p), _ptr(arr), 0, off.ctypes.data, n,
+                                   _ptr(lab), _ptr(ml),
+                                   _ptr(mc), n_models, C.byref(h)))
     try:
         st = N.KgCompStats()
         N.check(lib.kg_compset_stats(h, C.byref(st)))
@@ -1012,7 +985,7 @@ def compose_contigs(seq, offsets, labels=None, model=None, min_len: int = 1500, 
         out = {"row_labels": np.zeros(R, dtype=np.int32), "rows": np.zeros((R, N.COMP_BINS), dtype=np.int64),
                "background": np.zeros(N.COMP_BINS, dtype=np.int64),
                "model_labels": _copy_records(lib.kg_compset_model_labels, h, M, np.int32)}
-        N.check(lib.kg_compset_copy_rows(h, 0, R, out["row_labels"].ctypes.data if R else None, out["rows"].ctypes.data if R else None))
+        N.check(lib.kg_compset_copy_rows(h, 0, R, _ptr(out["row_labels"]), _ptr(out["rows"])))
         N.check(lib.kg_compset_background(h, out["background"].ctypes.data))
         out["classes"] = _copy_records(lib.kg_compset_copy_classes, h, n, N.COMP_CLASS_DTYPE, device_out=device_out)
         out["counts"] = _copy_records(lib.kg_compset_copy_counts, h, n, np.int32, (N.COMP_BINS,), device_out)
@@ -1072,9 +1045,7 @@ def repair_orfs(calls, seq, offsets, merge_gap: int = 600, min_score: int = 0, m
     repair_calls: the CALL list the repair step is given, when it is not `calls` (it must describe the same regions, or the
     call fails with KG_ERR_ARG).  `stats`, when given, receives "regions", "orfs" (the new set's) and "repair"."""
     lib = N.load()
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_seqs + 1]")
+    off = _offsets(offsets, "int64[n_seqs + 1]")
     c = np.ascontiguousarray(calls, dtype=N.CALL_DTYPE)
     rc = c if repair_calls is None else np.ascontiguousarray(repair_calls, dtype=N.CALL_DTYPE)
     keep = _seq_bytes(seq, off)
@@ -1082,12 +1053,11 @@ def repair_orfs(calls, seq, offsets, merge_gap: int = 600, min_score: int = 0, m
     p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
     op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
     rp = N.KgRepairParams(int(start_codons), int(min_count), int(max_junctions), 0)
-    h, oh, new = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    N.check(lib.kg_regions_calls(device, C.byref(p), c.ctypes.data if c.size else None, c.size, off.ctypes.data, n_seqs, C.byref(h)))
+    h, chain = C.c_void_p(), _OrfChain(lib)
+    N.check(lib.kg_regions_calls(device, C.byref(p), _ptr(c), c.size, off.ctypes.data, n_seqs, C.byref(h)))
     try:
-        sptr = keep.ctypes.data if keep.size else None
-        N.check(lib.kg_regionset_orfs(h, C.byref(op), sptr, 0, off.ctypes.data, n_seqs, C.byref(oh)))
-        cptr, on_device = (rc.ctypes.data if rc.size else None), 0
+        chain.step(lambda oh, new: lib.kg_regionset_orfs(h, C.byref(op), _ptr(keep), 0, off.ctypes.data, n_seqs, new))
+        cptr, sptr, on_device = _ptr(rc), _ptr(keep), 0
         if device_inputs:
             import torch
             with torch.cuda.device(device):
@@ -1095,35 +1065,18 @@ def repair_orfs(calls, seq, offsets, merge_gap: int = 600, min_score: int = 0, m
                 d_seq = torch.from_numpy(keep.copy()).cuda()
                 torch.cuda.synchronize()
             cptr, sptr, on_device = C.c_void_p(d_calls.data_ptr() if rc.size else None), C.c_void_p(d_seq.data_ptr() if keep.size else None), 1
-        N.check(lib.kg_regionset_repair(h, oh, cptr, on_device, rc.size, C.byref(rp), sptr, on_device, off.ctypes.data, n_seqs, C.byref(new)))
-        junc, jstart, rst = _junctions(new)
-        taken, new = new, C.c_void_p()              # (_take_* frees what it is given, also when it raises)
-        orfs, prot_start, residues, ost = _take_orfset(taken, False)
+        chain.step(lambda oh, new: lib.kg_regionset_repair(h, oh, cptr, on_device, rc.size, C.byref(rp), sptr, on_device, off.ctypes.data,
+                                                           n_seqs, new))
+        junc, jstart, rst = _junctions(chain.h)
+        orfs, prot_start, residues, ost = _take_orfset(chain.release(), False)
     except BaseException:
-        if new:
-            lib.kg_orfset_free(new)             # (the new set first: it holds blocks of the region set's context)
-        if oh:
-            lib.kg_orfset_free(oh)
+        chain.close()                           # (the ORF set first: it holds blocks of the region set's context)
         lib.kg_regionset_free(h)
         raise
-    lib.kg_orfset_free(oh)
     regs, start, rgst = _take_regionset(h, n_seqs, False)
     if stats is not None:
         stats.update({"regions": rgst, "orfs": ost, "repair": rst})
     return regs, start, orfs, prot_start, residues, junc, jstart
-
-
-def _add_free(oh, min_res: int, start_codons: int, ptr, on_device: int, off):
-    """kg_orfset_add_free on the ORF set oh, which is freed: -> the new set's handle (it lives in the same context)."""
-    lib = N.load()
-    fp = N.KgFreeParams(int(min_res), int(start_codons), 0)
-    both = C.c_void_p()
-    try:
-        N.check(lib.kg_orfset_add_free(oh, C.byref(fp), ptr, on_device, off.ctypes.data, off.size - 1, C.byref(both)))
-    finally:
-        lib.kg_orfset_free(oh)          # (the new set holds copies: the given one is not needed any more)
-        oh.value = None
-    return both
 
 
 def _table_arg(table) -> np.ndarray:
@@ -1139,22 +1092,6 @@ def _coding_arg(coding):
     if coding is None or coding is False:
         return None
     return True if coding is True else _table_arg(coding)
-
-
-def _coding(oh, coding, min_coding: int, min_train_pairs: int, ptr, on_device: int, off):
-    """kg_orfset_coding on the ORF set oh, which is freed: -> the new set's handle (it lives in the same context).  coding: what
-    _coding_arg gave, True or a table."""
-    lib = N.load()
-    table = None if coding is True else coding
-    cp = N.KgCodingParams(int(min_coding), 0, int(min_train_pairs))
-    new = C.c_void_p()
-    try:
-        N.check(lib.kg_orfset_coding(oh, C.byref(cp), None if table is None else table.ctypes.data, ptr, on_device, off.ctypes.data,
-                                     off.size - 1, C.byref(new)))
-    finally:
-        lib.kg_orfset_free(oh)          # (the new set holds copies: the given one is not needed any more)
-        oh.value = None
-    return new
 
 
 def _coding_results(h):
@@ -1205,21 +1142,6 @@ def _start_model_arrays(m):
             np.array(m.type_chosen, dtype=np.int64), np.array(m.type_cand, dtype=np.int64))
 
 
-def _starts(oh, rh, table, weights, min_res: int, start_codons: int, rounds: int, min_train_starts: int, ptr, on_device: int, off):
-    """kg_orfset_starts on the ORF set oh, which is freed: -> the new set's handle (it lives in the same context).  rh: the region
-    set's handle or None; weights: a KgStartWeights or None."""
-    lib = N.load()
-    sp = N.KgStartParams(int(min_res), int(start_codons), int(rounds), 0, int(min_train_starts))
-    new = C.c_void_p()
-    try:
-        N.check(lib.kg_orfset_starts(oh, C.byref(sp), table.ctypes.data, None if weights is None else C.addressof(weights), rh, ptr,
-                                     on_device, off.ctypes.data, off.size - 1, C.byref(new)))
-    finally:
-        lib.kg_orfset_free(oh)          # (the new set holds copies: the given one is not needed any more)
-        oh.value = None
-    return new
-
-
 def _starts_results(h):
     """-> (shifts int32[n], statistics, (chosen, cand, type_chosen, type_cand) counts) of a set made by kg_orfset_starts; the set is
     freed when a call fails."""
@@ -1260,9 +1182,7 @@ def choose_starts(table, orfs, seq, offsets, weights=None, limits=None, min_res:
     records in `rounds` rounds, or a (pos, type) pair; limits: None or int32[n], the largest k of every record, -1 for none.
     -> (orfs, shifts): the records after the move and the shift of each in codons.  `stats`, when given, receives the call's
     counts and device times; `model`, when given, is extended by the last round's (chosen, cand, type_chosen, type_cand)."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_seqs + 1]")
+    off = _offsets(offsets, "int64[n_seqs + 1]")
     t = _table_arg(table)
     o = np.ascontiguousarray(orfs, dtype=N.ORF_DTYPE)
     arr = _seq_bytes(seq, off)
@@ -1277,9 +1197,9 @@ def choose_starts(table, orfs, seq, offsets, weights=None, limits=None, min_res:
     shifts = np.zeros(o.size, dtype=np.int32)
     st, m = N.KgStartStats(), N.KgStartModel()
     N.check(N.load().kg_starts_orfs(device, C.byref(sp), t.ctypes.data, None if w is None else C.addressof(w),
-                                    o.ctypes.data if o.size else None, o.size, lim.ctypes.data if lim is not None and o.size else None,
-                                    arr.ctypes.data if arr.size else None, off.ctypes.data, off.size - 1,
-                                    out.ctypes.data if o.size else None, shifts.ctypes.data if o.size else None, C.byref(m), C.byref(st)))
+                                    _ptr(o), o.size, _ptr(lim),
+                                    _ptr(arr), off.ctypes.data, off.size - 1,
+                                    _ptr(out), _ptr(shifts), C.byref(m), C.byref(st)))
     if stats is not None:
         stats.update(st.as_dict())
     if model is not None:
@@ -1314,13 +1234,11 @@ def coding_counts(orfs, seq, offsets, device: int = 0):
     """The coding and background hexamer counts of caller-held ORF records and their batch, on the GPU and without a table
     (kg_coding_counts_orfs): orfs ORF_DTYPE, seq the batch's bytes, offsets int64[n_seqs + 1].  -> (coding, background), int64[4096]
     each; a record trains when it is kept and neither free nor interrupted."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_seqs + 1]")
+    off = _offsets(offsets, "int64[n_seqs + 1]")
     o = np.ascontiguousarray(orfs, dtype=N.ORF_DTYPE)
     arr = _seq_bytes(seq, off)
     m = N.KgCodingModel()
-    N.check(N.load().kg_coding_counts_orfs(device, o.ctypes.data if o.size else None, o.size, arr.ctypes.data if arr.size else None,
+    N.check(N.load().kg_coding_counts_orfs(device, _ptr(o), o.size, _ptr(arr),
                                            off.ctypes.data, off.size - 1, C.byref(m)))
     return np.array(m.coding, dtype=np.int64), np.array(m.background, dtype=np.int64)
 
@@ -1328,16 +1246,14 @@ def coding_counts(orfs, seq, offsets, device: int = 0):
 def coding_scores(table, orfs, seq, offsets, device: int = 0) -> np.ndarray:
     """The hexamer log-odds score of every caller-held ORF record under an int32[4096] table, on the GPU (kg_coding_score_orfs).
     -> int64[n]."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_seqs + 1]")
+    off = _offsets(offsets, "int64[n_seqs + 1]")
     t = _table_arg(table)
     o = np.ascontiguousarray(orfs, dtype=N.ORF_DTYPE)
     arr = _seq_bytes(seq, off)
     out = np.zeros(o.size, dtype=np.int64)
-    N.check(N.load().kg_coding_score_orfs(device, t.ctypes.data, o.ctypes.data if o.size else None, o.size,
-                                          arr.ctypes.data if arr.size else None, off.ctypes.data, off.size - 1,
-                                          out.ctypes.data if o.size else None))
+    N.check(N.load().kg_coding_score_orfs(device, t.ctypes.data, _ptr(o), o.size,
+                                          _ptr(arr), off.ctypes.data, off.size - 1,
+                                          _ptr(out)))
     return out
 
 
@@ -1347,13 +1263,11 @@ def free_orfs(seq, offsets, min_res: int = 100, start_codons: int = 7, device: i
     include/kmerguts_hip.h states the rule): every stop-free run of the six frames that gives at least min_res residues from
     its first start codon.  seq the batch's bytes, offsets int64[n_seqs + 1].  -> (orfs, prot_start, residues) as orf_regions;
     `stats`, when given, receives the call's counts and device time."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_seqs + 1]")
+    off = _offsets(offsets, "int64[n_seqs + 1]")
     arr = _seq_bytes(seq, off)
     p = N.KgFreeParams(int(min_res), int(start_codons), 0)
     h = C.c_void_p()
-    N.check(N.load().kg_orfs_free(device, C.byref(p), arr.ctypes.data if arr.size else None, 0, off.ctypes.data, off.size - 1,
+    N.check(N.load().kg_orfs_free(device, C.byref(p), _ptr(arr), 0, off.ctypes.data, off.size - 1,
                                   C.byref(h)))
     out, start, res, st = _take_orfset(h, device_out)
     if stats is not None:
@@ -1367,15 +1281,13 @@ def orf_regions(regs, seq, offsets, start_codons: int = 7, only_kept: bool = Tru
     REGION_DTYPE, seq the batch's bytes, offsets int64[n_seqs + 1].  -> (orfs, prot_start, residues): numpy arrays of
     _native.ORF_DTYPE, int64[n + 1] and uint8, or with device_out=True CUDA tensors (uint8 of 48 bytes per ORF, int64, uint8);
     `stats`, when given, receives the call's counts and device time."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    if off.ndim != 1 or off.size < 1:
-        raise ValueError("offsets must be int64[n_seqs + 1]")
+    off = _offsets(offsets, "int64[n_seqs + 1]")
     r = np.ascontiguousarray(regs, dtype=N.REGION_DTYPE)
     arr = _seq_bytes(seq, off)
     p = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
     h = C.c_void_p()
-    N.check(N.load().kg_orfs_regions(device, C.byref(p), r.ctypes.data if r.size else None, r.size,
-                                     arr.ctypes.data if arr.size else None, off.ctypes.data, off.size - 1, C.byref(h)))
+    N.check(N.load().kg_orfs_regions(device, C.byref(p), _ptr(r), r.size,
+                                     _ptr(arr), off.ctypes.data, off.size - 1, C.byref(h)))
     out, start, res, st = _take_orfset(h, device_out)
     if stats is not None:
         stats.update(st)
@@ -1401,7 +1313,7 @@ def select_intervals(iv, n_seqs: int, max_overlap: int = 60, max_overlap_pct: in
     a = np.ascontiguousarray(iv, dtype=N.INTERVAL_DTYPE)
     p = N.KgSelectParams(int(max_overlap), int(max_overlap_pct), 0)
     h = C.c_void_p()
-    N.check(N.load().kg_select_intervals(device, C.byref(p), a.ctypes.data if a.size else None, a.size, int(n_seqs), C.byref(h)))
+    N.check(N.load().kg_select_intervals(device, C.byref(p), _ptr(a), a.size, int(n_seqs), C.byref(h)))
     out, st = _take_selectset(h, device_out)
     if stats is not None:
         stats.update(st)

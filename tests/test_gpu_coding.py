@@ -542,6 +542,41 @@ def test_behind_a_scan_from_host_and_device_bytes():
         assert tab.live_device_bytes() == live0
 
 
+def test_orfs_and_select_run_the_same_steps():
+    """ScanResult.orfs and select(orfs=True) with every step on -- repair, free ORFs, coding, starts -- leave the same five
+    arrays and the same side results, byte for byte (the device times apart)."""
+    from kmergutsjava_amd import hotpath
+    img, dna, off, _ = _workload()
+    sb = np.frombuffer(dna, dtype=np.uint8)
+    kw = dict(repair=True, free_min_res=100, coding=True, min_train_pairs=1000, starts=True, min_train_starts=1)
+    sides = ("coding_scores", "coding_stats", "coding_model", "start_shifts", "start_stats", "start_model", "junctions", "junction_start",
+             "repair_stats", "orf_stats", "region_stats")
+
+    def flat(x):
+        """arrays as their bytes, statistics without their device times"""
+        if isinstance(x, dict):
+            return {k: v for k, v in x.items() if k != "ms" and not k.startswith("ms_")}
+        return x.tobytes() if isinstance(x, np.ndarray) else [flat(y) for y in x]
+
+    with hotpath.SignatureTable.from_bytes(img, 0) as tab:
+        with tab.scan(sb, off, hotpath.Params(min_hits=4)) as r:
+            live1 = tab.live_device_bytes()
+            a = r.orfs(sb, off, 300, 12, 100, **kw)
+            side_a = {k: flat(getattr(r, k)) for k in sides}
+            for k in sides + ("select_stats",):
+                if hasattr(r, k):
+                    delattr(r, k)
+            b = r.select(off, sb, 300, 12, 100, orfs=True, **kw)
+            side_b = {k: flat(getattr(r, k)) for k in sides}
+            assert len(a) == 5 and len(b) == 6 and flat(a) == flat(b[:5])
+            assert side_a == side_b
+            n = len(a[2])
+            assert n > len(a[0]) > 0 and r.repair_stats["repaired"] > 0 and r.coding_stats["trained"] == 1 and r.start_stats["trained"] == 1
+            assert len(r.coding_scores) == len(r.start_shifts) == len(b[5]) == n and r.select_stats["ms"] > 0
+            assert tab.live_device_bytes() == live1
+        assert tab.live_device_bytes() == 0
+
+
 def test_failed_allocations_leave_nothing_behind(monkeypatch):
     """Every allocation of the three calls fails once.  The set call runs beside an open table, on an ORF set made from a scan
     of it: after every failure the table's live bytes are what they were, and 0 when the sets and the result are freed."""
