@@ -1011,16 +1011,23 @@ __device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t x, uint32_t *tota
     return wbase + incl - x;
 }
 
+// partial[chunk] = the sum of the chunk's items in 64 bits: 2048 items of up to 2^32 - 1 each pass 2^32 inside one chunk, and the
+// grand total that scan_top_kernel makes of these sums is what the callers' 2^32 limits are checked against
 __global__ __launch_bounds__(kScanThreads) void scan_partials_kernel(const uint32_t *in, uint64_t n, uint64_t *partial)
 {
-    __shared__ uint32_t lds[8];
+    __shared__ uint64_t wsum[kScanThreads / 64];
     uint64_t base = (uint64_t)blockIdx.x * kScanChunk + (uint64_t)threadIdx.x * kScanPerThread;
-    uint32_t s = 0;
+    uint64_t s = 0;
     for (int k = 0; k < kScanPerThread; k++)
         if (base + k < n) s += in[base + k];
-    uint32_t total;
-    wg_exclusive_scan(s, &total, lds);
-    if (threadIdx.x == 0) partial[blockIdx.x] = total;
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t all = 0;
+        for (int w = 0; w < kScanThreads / 64; w++) all += wsum[w];
+        partial[blockIdx.x] = all;
+    }
 }
 
 // single workgroup: partial[] -> exclusive (in place), grand total to *total_out

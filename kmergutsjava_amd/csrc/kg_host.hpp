@@ -372,7 +372,9 @@ struct CallScope {
     kg_table *disown() { kg_table *out = t; t = nullptr; out->fail_alloc_at = 0; return out; }
 };
 
-// exclusive prefix sum of d_in[n] -> d_out[n], total -> d_total (device uint64)
+// exclusive prefix sum of d_in[n] -> d_out[n], total -> d_total (device uint64).  The total is exact for any input: the chunk
+// sums and their sum are 64 bits.  d_out is the prefix modulo 2^32, so it is exact if and only if the total is below 2^32: a
+// caller whose items are not flags reads the total, and refuses the call at 2^32, before it uses d_out as a layout.
 int prefix_sum(kg_table *t, const uint32_t *d_in, uint64_t n, uint32_t *d_out, uint64_t *d_partial, uint64_t *d_total,
                hipStream_t stream = nullptr)
 {

@@ -105,7 +105,11 @@ int repair_impl(kg_table *t, const kg_repair_params *prm, const kg_regionset *rs
         hipLaunchKernelGGL(kg::repair_calls_kernel, dim3(grid_of(n)), dim3(256), 0, s, regions, nr, pl.d_off, gkeys, perm, sx0, sx1, scount, head,
                            hexcl, run_region, n, prm->min_count, keep, creg, err);
         HIP_TRY(hipGetLastError());
-        // (region_gather_kernel has clamped the counts at 0)
+        // (region_gather_kernel has clamped the counts at 0).  The counts may add up to 2^32 or more, inside one chunk too, and no
+        // limit is needed: repair_sums_kernel compares differences of cexcl, and of the total's low word, modulo 2^32 with the
+        // low word of the region's score.  prefix_sum's d_out is the exact prefix modulo 2^32 whatever the total, and so is the
+        // low word of its total: the check is the one exact 64-bit prefixes would give once reduced, and no chunk's sum can make a
+        // foreign list pass it or a true one fail.
         if ((rc = prefix_sum(t, (const uint32_t *)scount, n, cexcl, partial, (uint64_t *)(words + kRepairWCountSum)))) return rc;
         if (nr > 0) {
             hipLaunchKernelGGL(kg::repair_sums_kernel, dim3(grid_of(nr)), dim3(256), 0, s, regions, nr, n, n_seqs, pos, owner, hexcl, run_start,

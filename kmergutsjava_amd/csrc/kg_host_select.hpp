@@ -65,8 +65,8 @@ int select_impl(kg_table *t, const kg_select_params *prm, const T *d_in, uint64_
                            flag, pos, c);
         hipLaunchKernelGGL(kg::select_count_kernel, dim3(grid_of(n)), dim3(256), 0, s, c.key, c.right, d_E, n, left_bits, count, words);
         HIP_TRY(hipGetLastError());
-        // (the scan adds in 32 bits: its total is not read, P is the count kernel's 64-bit sum, and pair_start is used only
-        // when P < 2^31, where no partial sum can have wrapped)
+        // (the scan's total is exact and equals P, the count kernel's own 64-bit sum, which the limit check reads; pair_start is
+        // the prefix modulo 2^32 and is used only when P < 2^31, where it is exact)
         if ((rc = prefix_sum(t, count, n, pair_start, partial, (uint64_t *)(words + kg::kSelectScanTotal)))) return rc;
         // the one wait before the rounds: the error word, the eligible candidates and the overlapping pairs
         if ((rc = read_error_words(t, words, kg::kSelectWords, kPinStage,

@@ -289,6 +289,8 @@ int kg_orfset_starts(kg_orfset *os, const kg_start_params *p, const int32_t *tab
     if ((rc = w.list_and_choose(p, table, weights, ev))) return rc;
     if (d_S && n > 0) HIP_TRY(hipMemcpyAsync(d_S, os->d_coding, n * 8, hipMemcpyDeviceToDevice, s));
     if ((rc = w.apply(os->d_prot_start, d_out, d_shift, d_S, new_lens))) return rc;
+    // No 2^32-residue limit here: starts_apply_kernel writes new_lens[i] = len - min(k, len), so no record grows, and every chunk's
+    // sum and the total are at most the given set's, which passed that limit when the set was made.
     if ((rc = layout_proteins(t, new_lens, n, new_excl, w.partial, (uint64_t *)(w.cnt + kg::kStartCntResidues), d_start))) return rc;
     // the wait for the residue total
     if ((rc = w.check())) return rc;

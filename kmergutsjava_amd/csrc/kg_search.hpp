@@ -9,8 +9,8 @@
 //   1. search_kmer_heads_kernel     per pair: the k-mer run head flag; a prefix sum and cluster_link_starts_kernel give the runs
 //   2. search_run_weights_kernel    per run: the split nd(v) by a binary search for n_db inside the run, nq = the rest, and
 //                                   w(v) = nd * nq in 64 bits where 1 <= nd <= max_db_per_kmer and nq >= 1, else 0.  The 64-bit sum
-//                                   of the weights is kept by one integer atomic per wave (prefix_sum adds a chunk's 2048 items in
-//                                   32 bits, so its total is exact only below 2^32: the limit check uses this sum instead)
+//                                   of the weights is kept by one integer atomic per wave (the stored weights are saturated at
+//                                   2^32 - 1, so prefix_sum's total, though exact, is not theirs: the limit check uses this sum)
 //   3. search_run_compact_kernel    the runs of weight >= 1 compacted by a prefix sum of their flags: every listed run has
 //                                   weight >= 1, so wx, the prefix sum of the listed weights, is strictly increasing and a tile
 //                                   of kSearchTile items touches at most kSearchTile runs

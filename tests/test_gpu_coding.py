@@ -9,8 +9,12 @@ call_regions front end and the E. coli genome.
 Two of the errors the header names are not provoked here.  KG_ERR_BUSY: no existing hook leaves a kg_scan* in flight on a table
 without a second thread (the busy flag is taken and given back inside one call; tests/test_gpu_hygiene.py races four threads for
 it on 20 Mbp scans, a coding call is too short to lose such a race reliably), so it is left to the code's own reading: the call
-takes the set's table through the CallScope every other set call uses.  KG_ERR_LIMIT: 2^31 records, 2^32 pairs or 2^40 bytes do
-not fit a test of a few seconds; the pair kernels read the pair total first and touch nothing when it is 2^32 or more."""
+takes the set's table through the CallScope every other set call uses.  KG_ERR_LIMIT for 2^31 records or 2^40 bytes: neither
+fits a test of a few seconds.
+
+The 2^32-pair limit does, since the records of a caller's list may overlap: 2048 records over one frame of 2^21 + 1 codons hold
+2^32 pairs and fill one chunk of the prefix sum (tests/scan_model.py); the pair kernels read the pair total first and touch
+nothing when it is 2^32 or more.  Below the limit, 1025 such records carry the pair prefix past the sign bit."""
 import ctypes as C
 import gzip
 import os
@@ -25,6 +29,7 @@ sys.path.insert(0, HERE)
 import coding_model as K  # noqa: E402
 import free_orfs_model as F  # noqa: E402
 import orfs_model as O  # noqa: E402
+import scan_model as SM  # noqa: E402
 import select_model as S  # noqa: E402
 import test_coding_host as TH  # noqa: E402
 import test_orfs_host as HO  # noqa: E402
@@ -492,6 +497,68 @@ def test_errors_and_their_messages():
             lib.kg_orfset_free(h2)
     finally:
         s.close()
+
+
+# ---- the prefix sum under the pairs: the 2^32 limit at the wrap, and a legal prefix past the sign bit -----------------------------------
+
+_LIMIT = {}
+
+
+def _limit_rows():
+    """The batch of tests/scan_model.py with 2^21 + 1 sense codons, and the three records of its lists.  coding_lens_kernel gives
+    a record n_res - 1 pairs whatever its flags: the long record, the first 2^21 + 1 codons of the long contig, has 2^21, the
+    short one, six codons of the short contig, has five, and a record of one codon has none."""
+    if not _LIMIT:
+        seq, off = SM.limit_batch(SM.LONG + 1)
+        L0, L1 = int(off[1]), int(off[2] - off[1])
+        _LIMIT["w"] = (seq, off, K.codon_orf(L1, 0, 0, 0, SM.LONG + 1, seq=1), K.codon_orf(L0, 0, 0, 1, 6, stop=False, seq=0),
+                       K.codon_orf(L0, 0, 0, 2, 1, stop=False, seq=0))
+    return _LIMIT["w"]
+
+
+def test_pair_totals_that_wrap_a_chunk_of_the_prefix_sum_are_refused():
+    """The lists of scan_model.families through kg_coding_counts_orfs and kg_coding_score_orfs: 2048 records of 2^21 pairs
+    alone, behind 2048 short records, in reversed order, and -- the control, refused whatever the chunk sums' width -- half in
+    each of two chunks.  tests/test_scan_model_host.py shows that 32-bit chunk sums gave the first three a total below 2^32.
+    Every call is refused with the stage's own words, leaves no device memory behind, and the next call is an ordinary one."""
+    import torch
+    from kmergutsjava_amd import hotpath
+    seq, off, long_row, short_row, none_row = _limit_rows()
+    rng = np.random.default_rng(6)
+    T = _table(rng)
+    small, small_seq, small_off = K.random_batch(rng, 12, max_len=300)
+    with hotpath.SignatureTable.from_bytes(_workload()[0], 0) as tab:
+        _twins_equal_the_model(small, small_seq, small_off, T)          # once first: what the runtime sets up on first use is not counted
+        torch.cuda.synchronize()
+        free0, live0 = torch.cuda.mem_get_info()[0], tab.live_device_bytes()
+        for name, (lens, _) in SM.families(5).items():
+            orfs = SM.records_of(lens, long_row, short_row, none_row, N.ORF_DTYPE)
+            assert np.maximum(orfs["n_res"].astype(np.int64) - 1, 0).tolist() == lens.tolist() and SM.scan_exact(lens)[1] >= SM.LIMIT
+            for call in (lambda: hotpath.coding_counts(orfs, seq, off), lambda: hotpath.coding_scores(T, orfs, seq, off)):
+                with pytest.raises(N.KmerGutsNativeError) as ei:
+                    call()
+                assert ei.value.code == N.KG_ERR_LIMIT, name
+                assert SM.message_of(ei.value).startswith("2^32 or more codon pairs"), (name, str(ei.value))
+                assert torch.cuda.mem_get_info()[0] == free0 and tab.live_device_bytes() == live0, name
+        _twins_equal_the_model(small, small_seq, small_off, T)
+
+
+def test_1025_records_of_2_21_pairs_carry_the_prefix_past_the_sign_bit():
+    """scan_model.LEGAL: 2^31 + 2^21 pairs, legal, nothing allocated per pair; the last record's prefix is 2^31, inside the
+    prefix sum's first chunk.  All records are the same training record, so the coding counts are 1025 times the model's counts
+    of one, and the background is the batch's.
+    Measured on the MI355X: 0.15 s for the test, the model's counts of one record included; the slowest test of this file,
+    test_call_regions_coding_end_to_end, took 6.6 s in the same suite."""
+    from kmergutsjava_amd import hotpath
+    seq, off, long_row, _, _ = _limit_rows()
+    n = len(SM.LEGAL)
+    orfs = K.records([long_row] * n)
+    assert n == 1025 and (orfs["n_res"].astype(np.int64) - 1).tolist() == SM.LEGAL.tolist()
+    one, B = K.counts_np(orfs[:1], seq, off)
+    assert one.sum() == SM.LONG and K.is_training(orfs[0])
+    Cd, Bd = hotpath.coding_counts(orfs, seq, off)
+    assert Cd.dtype == one.dtype and Cd.tobytes() == (n * one).tobytes(), "coding counts"
+    assert Bd.tobytes() == B.tobytes(), "background counts"
 
 
 # ---- behind a scan ------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,16 @@
 """Open reading frames on the GPU (kg_regionset_orfs / kg_orfs_regions): records, prot_start and residues must equal the numpy
 model of tests/orfs_model.py byte for byte -- at the edges of the tile summaries (T = _native.ORF_TILE_CODONS), on both strands
 and in every frame, across contig borders, on random batches, behind a DNA scan under both strategies, and through the
-call_regions front end and annotate; errors name the region and failed allocations leave nothing behind."""
+call_regions front end and annotate; errors name the region and failed allocations leave nothing behind.
+
+The 2^32-residue limit is met through kg_orfs_regions, whose regions may overlap: 2048 regions inside one stop-free frame of
+2^21 codons are 2048 ORFs of 2^21 residues, which fill one chunk of the prefix sum (tests/scan_model.py) with exactly 2^32.
+prot_start is held to the cumulative sum at the region counts where the prefix sum's chunks and the carry loop over them end.
+
+The free ORFs (kg_orfs_free, kg_orfset_add_free) and kg_regionset_repair have the same limit behind the same prefix sum and are
+left out: their records are found by the kernels, an ORF per closing stop and a repaired protein per region, so at most about
+six of them -- one per frame and strand -- cover any position, and 2048 neighbours that hold 2^32 residues need gigabases of
+input."""
 import os
 import subprocess
 import sys
@@ -14,6 +23,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import orfs_model as O  # noqa: E402
 import regions_model as R  # noqa: E402
+import scan_model as SM  # noqa: E402
 import test_orfs_host as HO  # noqa: E402
 
 from kmergutsjava_amd import _native as N  # noqa: E402
@@ -378,6 +388,94 @@ def test_failed_allocations_leave_nothing_behind(monkeypatch):
         assert tab.live_device_bytes() == live_set
         lib.kg_regionset_free(h)
         assert tab.live_device_bytes() == live0
+
+
+# ---- the prefix sum under prot_start: the 2^32 limit at the wrap, and the chunk and carry borders ------------------------------------
+
+_LIMIT = {}
+
+
+def _limit_rows():
+    """The batch of tests/scan_model.py with 2^21 sense codons, and the three regions of its lists.  Without start codons an
+    ORF runs from behind the stop in front of its region (orf_region_kernel: u + 1, here the contig's first codon) to the stop
+    behind it, so every region inside the long frame is the whole frame, 2^21 residues, and the region of the short contig is
+    its SHORT_CODONS codons; a region that is not kept gives no residues under only_kept."""
+    if not _LIMIT:
+        seq, off = SM.limit_batch(SM.LONG)
+        L0, L1 = int(off[1]), int(off[2] - off[1])
+        _LIMIT["w"] = (seq, off, O.codon_region(L1, 0, 0, 1000, 1003, seq=1), O.codon_region(L0, 0, 0, 3, 3, seq=0),
+                       O.codon_region(L1, 0, 0, 7, 9, seq=1, kept=0))
+    return _LIMIT["w"]
+
+
+def test_residue_totals_that_wrap_a_chunk_of_the_prefix_sum_are_refused():
+    """The lists of scan_model.families: 2048 ORFs of 2^21 residues alone, behind 2048 short ORFs, in reversed order, and --
+    the control, refused whatever the chunk sums' width -- half in each of two chunks.  tests/test_scan_model_host.py shows that
+    32-bit chunk sums gave the first three a total below 2^32.  Every call is refused with the stage's own words, leaves no
+    device memory behind, and the next call is an ordinary one."""
+    from kmergutsjava_amd import hotpath
+    seq, off, long_row, short_row, none_row = _limit_rows()
+    small = O.regions_of([short_row, long_row, none_row, short_row])
+    img = _workload()[0]
+    with hotpath.SignatureTable.from_bytes(img, 0) as tab:
+        want = O.orfs(small, seq, off, 0)
+        _same(_dev(small, seq, off, sc=0), want)        # once first: what the runtime sets up on first use is not counted
+        assert want[0]["n_res"].tolist() == [SM.SHORT_CODONS, SM.LONG, SM.LONG, SM.SHORT_CODONS] and np.diff(want[1])[2] == 0
+        torch.cuda.synchronize()
+        free0, live0 = torch.cuda.mem_get_info()[0], tab.live_device_bytes()
+        for name, (lens, _) in SM.families(SM.SHORT_CODONS).items():
+            regs = SM.records_of(lens, long_row, short_row, none_row, N.REGION_DTYPE)
+            assert len(regs) == len(lens) and SM.scan_exact(lens)[1] >= SM.LIMIT
+            with pytest.raises(N.KmerGutsNativeError) as ei:
+                hotpath.orf_regions(regs, seq, off, 0)
+            assert ei.value.code == N.KG_ERR_LIMIT, name
+            assert SM.message_of(ei.value).startswith("2^32 or more residues"), (name, str(ei.value))
+            assert torch.cuda.mem_get_info()[0] == free0 and tab.live_device_bytes() == live0, name
+        _same(_dev(small, seq, off, sc=0), want)
+
+
+_EXACT = {}
+
+
+def _exact_case():
+    """A contig of three ORFs between stops -- 1, 257 and 300 codons -- behind a short one, one region inside each, and the
+    model's record and protein of each."""
+    if not _EXACT:
+        rng = np.random.default_rng(2048)
+        sense = lambda n: SM._SENSE[rng.integers(0, len(SM._SENSE), size=n)].tobytes()       # noqa: E731
+        contig = b"TAA" + sense(1) + b"TAA" + sense(257) + b"TAA" + sense(300) + b"TAA" + b"G"
+        seq, off = _batch([b"ACGTA", contig])
+        L = len(contig)
+        kinds = O.regions_of([O.codon_region(L, 0, 0, 1, 1, seq=1), O.codon_region(L, 0, 0, 100, 120, seq=1), O.codon_region(L, 0, 0, 300, 301, seq=1)])
+        recs, ps, res = O.orfs(kinds, seq, off, 0)
+        assert recs["n_res"].tolist() == [1, 257, 300]
+        _EXACT["w"] = (seq, off, kinds, recs, ps, res)
+    return _EXACT["w"]
+
+
+@pytest.mark.parametrize("n", [SM.CHUNK - 1, SM.CHUNK, SM.CHUNK + 1, 2 * SM.CHUNK, SM.TOP * SM.CHUNK - 1, SM.TOP * SM.CHUNK,
+                               SM.TOP * SM.CHUNK + 1])
+def test_prot_start_is_the_cumulative_sum_at_the_chunk_and_carry_borders(n):
+    """Region counts that end one short of a chunk of the prefix sum, on it and one behind it, and the same about the 256
+    chunks of one trip of scan_top_kernel's carry loop.  ORFs of one codon, with those of a few hundred at the last slot of
+    every chunk, at the first of the next and at one slot in 300: prot_start is np.cumsum of the lengths, the residues are the
+    model's proteins in that order, the records the model's."""
+    seq, off, kinds, recs, ps, res = _exact_case()
+    rng = np.random.default_rng(n)
+    i = np.arange(n)
+    kind = np.where(rng.integers(0, 300, size=n) == 0, 1, 0)
+    kind[i % SM.CHUNK == SM.CHUNK - 1] = 1
+    kind[i % SM.CHUNK == 0] = 2
+    lens = recs["n_res"].astype(np.int64)[kind]
+    want_start = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens, out=want_start[1:])
+    total = int(want_start[-1])
+    assert n + 256 * (n // SM.CHUNK) < total < 8 << 20
+    at = np.arange(total, dtype=np.int64) - np.repeat(want_start[:-1], lens) + np.repeat(ps[:-1][kind], lens)
+    st = {}
+    got = _dev(kinds[kind], seq, off, sc=0, stats=st)
+    _same(got, (recs[kind], want_start, res[at]))
+    assert st["residues"] == total and st["orfs"] == n
 
 
 def test_call_regions_orfs_faa_and_annotate(oracle, tmp_path):

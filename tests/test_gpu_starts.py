@@ -8,8 +8,12 @@ bytes, the call_regions front end and the E. coli genome.
 
 Two of the errors the header names are not provoked here, as in tests/test_gpu_coding.py.  KG_ERR_BUSY: no hook leaves a
 kg_scan* in flight on a table without a second thread, and the call takes the set's table through the CallScope every other set
-call uses.  KG_ERR_LIMIT: 2^31 records, 2^32 codons or 2^40 bytes do not fit a test of a few seconds; the codon total is read on
-the host before any codon pass is launched."""
+call uses.  KG_ERR_LIMIT for 2^31 records or 2^40 bytes: neither fits a test of a few seconds.
+
+The 2^32-codon limit does, since the records of a caller's list may overlap: 2048 movable records over one frame of 2^21 codons
+hold 2^32 codons and fill one chunk of the prefix sum (tests/scan_model.py); the codon total is read on the host before any
+codon pass is launched.  kg_orfset_starts lays the proteins out again without a limit of its own: no record grows, which
+test_a_set_non_movable_records_proteins_scores_and_a_second_call asserts."""
 import ctypes as C
 import gzip
 import os
@@ -24,6 +28,7 @@ sys.path.insert(0, HERE)
 import coding_model as K  # noqa: E402
 import free_orfs_model as F  # noqa: E402
 import orfs_model as O  # noqa: E402
+import scan_model as SM  # noqa: E402
 import select_model as S  # noqa: E402
 import starts_model as M  # noqa: E402
 import test_coding_host as TH  # noqa: E402
@@ -205,6 +210,41 @@ def test_rounds_the_training_threshold_and_callers_weights():
     assert (again["orfs"]["flags"] & M.MOVED).sum() >= (r4["orfs"]["flags"] & M.MOVED).sum()
 
 
+def test_codon_totals_that_wrap_a_chunk_of_the_prefix_sum_are_refused():
+    """The lists of scan_model.families through kg_starts_orfs.  starts_lens_kernel gives a movable record its n_res codons and
+    any other record none; kcap, min_res and the limits bound the candidates among them, not the codons.  So the long record, the
+    2^21 sense codons of the long contig with a start codon on record, has 2^21, the short one six, and a record that is not
+    kept none: 2048 long ones alone, behind 2048 short ones, in reversed order, and -- the control, refused whatever the chunk
+    sums' width -- half in each of two chunks.  tests/test_scan_model_host.py shows that 32-bit chunk sums gave the first
+    three a total below 2^32.  Every call is refused with the stage's own words, leaves no device memory behind, and the next
+    call is an ordinary one."""
+    import torch
+    from kmergutsjava_amd import hotpath
+    seq, off = SM.limit_batch(SM.LONG)
+    right = 3 * (SM.LONG + 1) - 1                       # the stop codon inside the coordinates
+    long_row, short_row = K.orf(1, 0, 0, right, SM.LONG, start_codon=1), K.orf(0, 0, 3, 3 + 3 * 7 - 1, 6, start_codon=1)
+    none_row = K.orf(1, 0, 0, right, SM.LONG, start_codon=1, kept=0)
+    rng = np.random.default_rng(17)
+    T = _table(rng)
+    genes = [SH.gene(rng, n, {0: b"ATG", 3: b"GTG", 7: b"TTG"}, strand=n % 2, frame=n % 3, random_codons=True) for n in (30, 41, 52, 9)]
+    small, small_seq, small_off = SH.batch(genes)
+    kw = dict(min_res=5, rounds=2, min_train_starts=1)
+    with hotpath.SignatureTable.from_bytes(_workload()[0], 0) as tab:
+        _check(small, small_seq, small_off, T, **kw)    # once first: what the runtime sets up on first use is not counted
+        torch.cuda.synchronize()
+        free0, live0 = torch.cuda.mem_get_info()[0], tab.live_device_bytes()
+        for name, (lens, _) in SM.families(6).items():
+            orfs = SM.records_of(lens, long_row, short_row, none_row, N.ORF_DTYPE)
+            assert np.where(orfs["kept"] != 0, orfs["n_res"], 0).tolist() == lens.tolist() and SM.scan_exact(lens)[1] >= SM.LIMIT
+            with pytest.raises(N.KmerGutsNativeError) as ei:
+                hotpath.choose_starts(T, orfs, seq, off, min_res=100)
+            assert ei.value.code == N.KG_ERR_LIMIT, name
+            assert SM.message_of(ei.value).startswith("2^32 or more codons"), (name, str(ei.value))
+            assert torch.cuda.mem_get_info()[0] == free0 and tab.live_device_bytes() == live0, name
+        want = _check(small, small_seq, small_off, T, **kw)
+        assert want["stats"]["movable"] == 4
+
+
 # ---- sets: kg_orfset_starts -----------------------------------------------------------------------------------------------------------
 
 class _Set:
@@ -308,6 +348,9 @@ def test_a_set_non_movable_records_proteins_scores_and_a_second_call():
         fixed = (recs["kept"] == 0) | (recs["start_codon"] == 0) | ((recs["flags"] & (M.INTERRUPTED | M.NONCODING)) != 0)
         assert fixed.sum() > 5 and got["orfs"][fixed].tobytes() == recs[fixed].tobytes() and not got["shifts"][fixed].any()
         assert ((got["orfs"]["flags"] & M.MOVED) != 0).tolist() == moved.tolist() and (got["orfs"]["first_inner"][moved] == -1).all()
+        # no record grows, so the new set needs no residue limit of its own: record by record and in all, it holds no more
+        # residues than the given set, whose total passed the 2^32 limit when it was made
+        assert (np.diff(got["prot_start"]) <= np.diff(s.ps)).all() and len(got["residues"]) < len(s.res)
         # proteins: the old suffix with M; the scores: a fresh coding_scores of the new records
         for i in np.flatnonzero(moved)[:20]:
             old = s.res[s.ps[i]:s.ps[i + 1]].tobytes()
