@@ -442,8 +442,8 @@ void kg_familyset_free(kg_familyset *s);
  *       score(a, b) = the maximum of H over all cells, 0 for an empty protein
  *   A gap of k residues costs gap_open + k * gap_extend; the defaults are 11 and 1, the usual pairing for this matrix;
  *   gap_open >= 0, gap_extend >= 1.  (end_a, end_b) is the 0-based cell with H = score that has the smallest i, then the
- *   smallest j; (-1, -1) when score = 0.  There is no traceback: the score is a maximum and does not depend on how ties inside
- *   the recurrence are broken; the end has the tie rule above.
+ *   smallest j; (-1, -1) when score = 0.  There is no traceback in this pass (the opt-in pass below traces): the score is a
+ *   maximum and does not depend on how ties inside the recurrence are broken; the end has the tie rule above.
  *   self(p) = the sum of S[x][x] over p's residues with code < 20: what a protein scores against itself, X aside.
  *   Abstaining: a pair with n * m > max_cells is not aligned: score = -1, end = (-1, -1), status skipped.  The default is
  *   2^26 cells (8192 x 8192): this project's choice, it bounds the longest wave.  max_cells >= 1.
@@ -521,6 +521,76 @@ int64_t kg_familyset_edges_count(const kg_familyset *s);
 /* edge records [first, first + count) into dst (host or device memory) */
 int kg_familyset_edges_copy(const kg_familyset *s, int64_t first, int64_t count, kg_family_edge *dst);
 int kg_familyset_align_stats(const kg_familyset *s, kg_align_stats *out);
+
+/* ---- tracing alignments: start, identity and gaps of a pair whose end cell is known (kernel: kg_trace.hpp) ----
+ *
+ * An opt-in second pass behind the alignment above; this rule is the project's own.  Integers only.  H, E, F and S, the gaps,
+ * the codes and (end_a, end_b) are the alignment's; indices below are 1-based as in its recurrence; open and ext are the gap
+ * costs capped as the alignment kernel caps them (at 2^29 each: a gap that costs as much never pays).  The pass runs the
+ * recurrence again over the prefix box that ends in the end cell, rows 0..end_a and columns 0..end_b, which gives the box's
+ * cells the values they have in the whole matrix, and walks back.
+ *   The path is the sequence of columns found by this walk, which starts in state H at the end cell.
+ *   State H at (i, j).  H[i][j] > 0 holds here.
+ *     If H[i][j] == H[i-1][j-1] + S[a_i][b_j]: emit the column (a_i, b_j) and step to (i-1, j-1).  If that cell is on the
+ *     boundary or has H == 0, stop: the start is (i, j).  Otherwise stay in state H.
+ *     Else if H[i][j] == E[i][j]: go to state E at (i, j).
+ *     Else go to state F at (i, j).
+ *     The preference order is diagonal, then E, then F.
+ *   State E at (i, j).  Emit the column (-, b_j).
+ *     If E[i][j] == H[i][j-1] - open - ext: go to state H at (i, j-1).  An opening is preferred to an extension on a tie.
+ *     Else go to state E at (i, j-1).
+ *   State F at (i, j).  Emit the column (a_i, -).
+ *     If F[i][j] == H[i-1][j] - open - ext: go to state H at (i-1, j).
+ *     Else go to state F at (i-1, j).
+ *   A gap never reaches a cell with H == 0, so the walk stops only behind a diagonal step, and the path begins and ends with
+ *   a residue pair.  The record is computed from the column string, not from the state changes: with gap_open = 0 the walk may
+ *   pass through state H inside one gap, which stays one opening.
+ *   Record: start_a, start_b, 0-based, the cell of the walk's last column; identical: residue columns (a_i, b_j) whose codes are
+ *   equal and below 20; positive: residue columns with S[a_i][b_j] > 0; gap_opens: maximal runs of columns of one gap kind
+ *   (a run of (-, b_j) next to a run of (a_i, -) is two); gap_cols_a: columns (-, b_j); gap_cols_b: columns (a_i, -).
+ *   What follows from the record and the end cell:
+ *       residue columns = (end_a - start_a + 1) - gap_cols_b = (end_b - start_b + 1) - gap_cols_a   (always equal)
+ *       columns         = residue columns + gap_cols_a + gap_cols_b
+ *       identity %      = 100 * identical / columns
+ *       coverage of a % = 100 * (end_a - start_a + 1) / len_a, of b likewise
+ *   Abstaining: a pair whose box (end_a + 1) * (end_b + 1) exceeds max_trace_cells is not traced: status 2.  The default is
+ *   2^24 cells (4096 x 4096): this project's choice; with four bits a cell it bounds one pair's direction store at about
+ *   8.5 MB for a box that is not much flatter than a 64-row stripe.  The store is kept per stripe of 64 rows, 32 bytes per column
+ *   whatever the stripe's rows: (ceil((end_a + 1) / 64)) * (end_b + 64) * 32 bytes, so the worst box under the default cap, one
+ *   row of 2^24 columns, takes 537 MB, and a caller who raises the cap raises that in proportion.  One pair's store is not
+ *   bounded otherwise: such a pair runs alone.  max_trace_cells >= 1.
+ * Nothing depends on launch geometry, pair order, scheduling or what a slab of direction bits held before.
+ *
+ * kg_proteins_align_paths / _device: kg_proteins_align's arguments, max_trace_cells, and paths beside out: a host array of
+ * n_pairs kg_alignment_path in pair order.  out is byte for byte kg_proteins_align's.  Errors as there, then
+ * "max_trace_cells must be >= 1" and "null paths".  A walk that leaves the rule or a box that does not reproduce the pair's
+ * score is KG_ERR_DEVICE ("internal: ...").  KG_TEST_FAIL_ALLOC applies; all scratch goes back to the driver. */
+#define KG_TRACE_DEFAULT_MAX_CELLS (1ll << 24)
+#define KG_TRACE_HITS 1
+#define KG_TRACE_ALL 2
+typedef struct kg_alignment_path {   /* 32 B */
+    int32_t start_a;       /* 0-based, -1 without a path                                */
+    int32_t start_b;
+    int32_t identical;
+    int32_t positive;
+    int32_t gap_opens;
+    int32_t gap_cols_a;    /* columns (-, b_j)                                          */
+    int32_t gap_cols_b;    /* columns (a_i, -)                                          */
+    int32_t status;        /* 0 traced, 1 none (pair skipped, not asked for, or score <= 0), 2 untraced (over the cap) */
+} kg_alignment_path;
+typedef struct kg_trace_stats {
+    int64_t traced;
+    int64_t untraced;      /* status 2                                                  */
+    int64_t cells;         /* box cells summed over the traced pairs                    */
+    float   ms_trace;      /* the traceback pass: its uploads and its kernels           */
+    int32_t reserved;
+} kg_trace_stats;
+int kg_proteins_align_paths(int device, const kg_align_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
+                            const int32_t *pairs, int64_t n_pairs, int64_t max_trace_cells, kg_alignment *out,
+                            kg_alignment_path *paths);
+int kg_proteins_align_paths_device(int device, const kg_align_params *p, const uint8_t *d_seq, const int64_t *offsets,
+                                   int64_t n_prot, const int32_t *pairs, int64_t n_pairs, int64_t max_trace_cells,
+                                   kg_alignment *out, kg_alignment_path *paths);
 
 /* ---- searching proteins against a database: 8-mer join, top candidates, alignment (kernels: kg_search.hpp) ----
  *
@@ -608,6 +678,20 @@ int kg_hitset_copy(const kg_hitset *s, int64_t first, int64_t count, kg_search_h
 int kg_hitset_starts_copy(const kg_hitset *s, int64_t *dst);
 int kg_hitset_stats(const kg_hitset *s, kg_search_stats *out);
 void kg_hitset_free(kg_hitset *s);
+/* kg_proteins_search_paths / _device: the search with the traceback pass (above) behind it.  trace = KG_TRACE_HITS traces the
+ * records with status hit only, KG_TRACE_ALL every aligned record with score >= 1; a is the query, b the target.  The hit
+ * records, hit_start and kg_search_stats are kg_proteins_search's, byte for byte; ms_align and ms_total exclude ms_trace.
+ * kg_hitset_paths_copy: one kg_alignment_path per hit record, same index; a record that was not traced has status 1 (not asked
+ * for, skipped) or 2 (over max_trace_cells).  It and kg_hitset_trace_stats return KG_ERR_ARG for a set made by kg_proteins_search.
+ * KG_ERR_ARG also: "trace must be KG_TRACE_HITS or KG_TRACE_ALL", "max_trace_cells must be >= 1". */
+int kg_proteins_search_paths(int device, const kg_search_params *p, const kg_align_params *align, const uint8_t *seq,
+                             const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, int trace,
+                             int64_t max_trace_cells, kg_hitset **out);
+int kg_proteins_search_paths_device(int device, const kg_search_params *p, const kg_align_params *align, const uint8_t *d_seq,
+                                    const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs,
+                                    int trace, int64_t max_trace_cells, kg_hitset **out);
+int kg_hitset_paths_copy(const kg_hitset *s, int64_t first, int64_t count, kg_alignment_path *dst);
+int kg_hitset_trace_stats(const kg_hitset *s, kg_trace_stats *out);
 
 /* ---- assigning functions: the CALL records of an -a scan -> one function per protein (kernels: kg_assign.hpp) ----
  *

@@ -398,6 +398,25 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_alignment_path (32 B): where a traced alignment starts (0-based, -1 without a path) and what its columns are; status
+     *  0 traced, 1 none, 2 untraced (the prefix box has more than max_trace_cells cells; KG_TRACE_DEFAULT_MAX_CELLS is 2^24). */
+    class KgAlignmentPath extends Structure {
+        public int start_a, start_b, identical, positive, gap_opens, gap_cols_a, gap_cols_b, status;
+        public KgAlignmentPath() {
+            setFieldOrder(new String[] {"start_a", "start_b", "identical", "positive", "gap_opens", "gap_cols_a", "gap_cols_b", "status"});
+        }
+    }
+
+    /** struct kg_trace_stats (kg_hitset_trace_stats). */
+    class KgTraceStats extends Structure {
+        public long traced, untraced, cells;
+        public float ms_trace;
+        public int reserved;
+        public KgTraceStats() {
+            setFieldOrder(new String[] {"traced", "untraced", "cells", "ms_trace", "reserved"});
+        }
+    }
+
     /** struct kg_search_params (kg_proteins_search*); this project's defaults: 2, 8 (at most 64), 256 and 0. */
     class KgSearchParams extends Structure {
         public int min_shared, max_cand, max_db_per_kmer, reserved;
@@ -484,6 +503,11 @@ public interface KmerGutsHip extends Library {
     int kg_proteins_align(int device, KgAlignParams params, byte[] seq, long[] offsets, long nProt, int[] pairs, long nPairs, Pointer out);
     int kg_proteins_align_device(int device, KgAlignParams params, Pointer dSeq, long[] offsets, long nProt, int[] pairs, long nPairs,
                                  Pointer out);
+    /** kg_proteins_align with the traceback pass behind it: paths = kg_alignment_path[nPairs], 32 B each, beside out */
+    int kg_proteins_align_paths(int device, KgAlignParams params, byte[] seq, long[] offsets, long nProt, int[] pairs, long nPairs,
+                                long maxTraceCells, Pointer out, Pointer paths);
+    int kg_proteins_align_paths_device(int device, KgAlignParams params, Pointer dSeq, long[] offsets, long nProt, int[] pairs, long nPairs,
+                                       long maxTraceCells, Pointer out, Pointer paths);
     /** kg_proteins_cluster with every link that passed the 8-mer tests verified by alignment; align = null: kg_proteins_cluster */
     int kg_proteins_cluster_aligned(int device, KgClusterParams params, KgAlignParams align, byte[] seq, long[] offsets, long nProt,
                                     long maxWindows, PointerByReference out);
@@ -503,6 +527,14 @@ public interface KmerGutsHip extends Library {
     int kg_hitset_starts_copy(Pointer set, long[] dst);                     // hit_start[nQ + 1]
     int kg_hitset_stats(Pointer set, KgSearchStats out);
     void kg_hitset_free(Pointer set);
+    /** kg_proteins_search with the traceback pass behind it: trace = KG_TRACE_HITS (1: the hit records) or KG_TRACE_ALL (2: every
+     *  aligned record with a score) */
+    int kg_proteins_search_paths(int device, KgSearchParams params, KgAlignParams align, byte[] seq, long[] offsets, long nProt, long nDb,
+                                 long maxWindows, long maxPairs, int trace, long maxTraceCells, PointerByReference out);
+    int kg_proteins_search_paths_device(int device, KgSearchParams params, KgAlignParams align, Pointer dSeq, long[] offsets, long nProt,
+                                        long nDb, long maxWindows, long maxPairs, int trace, long maxTraceCells, PointerByReference out);
+    int kg_hitset_paths_copy(Pointer set, long first, long count, Pointer dst);   // kg_alignment_path[count], 32 B each, same indices
+    int kg_hitset_trace_stats(Pointer set, KgTraceStats out);
     Pointer kg_table_device_entries(Pointer table);
     long kg_table_records(Pointer table);
     int kg_table_info(Pointer table, long[] numSigs, long[] entrySize, long[] version, long[] occupied);

@@ -39,8 +39,10 @@ EXPORTS = (
     "kg_familyset_free",
     "kg_proteins_align", "kg_proteins_align_device", "kg_proteins_cluster_aligned", "kg_proteins_cluster_aligned_device",
     "kg_familyset_edges_count", "kg_familyset_edges_copy", "kg_familyset_align_stats",
+    "kg_proteins_align_paths", "kg_proteins_align_paths_device",
     "kg_proteins_search", "kg_proteins_search_device", "kg_hitset_count", "kg_hitset_copy", "kg_hitset_starts_copy",
     "kg_hitset_stats", "kg_hitset_free",
+    "kg_proteins_search_paths", "kg_proteins_search_paths_device", "kg_hitset_paths_copy", "kg_hitset_trace_stats",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
@@ -142,6 +144,14 @@ ALIGN_DEFAULT_MAX_CELLS = 1 << 26
 ALIGN_ALIGNED, ALIGN_SKIPPED = 0, 1                     # kg_alignment.status
 EDGE_KEPT, EDGE_CUT, EDGE_SKIPPED = 0, 1, 2             # kg_family_edge.status
 ALIGN_LDS_COLS = 1024       # kg_align.hpp kAlignLdsCols: a longer second protein carries its stripes in device memory (tests aim at it)
+# struct kg_alignment_path (kg_proteins_align_paths*): where a traced alignment starts and what its columns are
+ALIGN_PATH_DTYPE = np.dtype([("start_a", "<i4"), ("start_b", "<i4"), ("identical", "<i4"), ("positive", "<i4"), ("gap_opens", "<i4"),
+                             ("gap_cols_a", "<i4"), ("gap_cols_b", "<i4"), ("status", "<i4")])
+assert ALIGN_PATH_DTYPE.itemsize == 32
+PATH_TRACED, PATH_NONE, PATH_UNTRACED = 0, 1, 2         # kg_alignment_path.status
+TRACE_DEFAULT_MAX_CELLS = 1 << 24
+TRACE_HITS, TRACE_ALL = 1, 2
+TRACE_MODES = {"hits": TRACE_HITS, "all": TRACE_ALL}
 # struct kg_search_hit (kg_proteins_search*): one aligned or skipped candidate of a query
 SEARCH_HIT_DTYPE = np.dtype([("query", "<i4"), ("target", "<i4"), ("shared", "<i4"), ("score", "<i4"), ("self_query", "<i4"),
                              ("self_target", "<i4"), ("end_query", "<i4"), ("end_target", "<i4"), ("status", "<i4"), ("rank", "<i4")])
@@ -364,6 +374,14 @@ class KgAlignStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class KgTraceStats(C.Structure):
+    """struct kg_trace_stats."""
+    _fields_ = [("traced", C.c_int64), ("untraced", C.c_int64), ("cells", C.c_int64), ("ms_trace", C.c_float), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 class KgSearchParams(C.Structure):
     """struct kg_search_params (kg_proteins_search*)."""
     _fields_ = [("min_shared", C.c_int32), ("max_cand", C.c_int32), ("max_db_per_kmer", C.c_int32), ("reserved", C.c_int32)]
@@ -521,6 +539,8 @@ def load() -> C.CDLL:
     lib.kg_familyset_stats.argtypes = [vp, C.POINTER(KgClusterStats)]
     for name in ("kg_proteins_align", "kg_proteins_align_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgAlignParams), vp, vp, C.c_int64, vp, C.c_int64, vp]
+    for name in ("kg_proteins_align_paths", "kg_proteins_align_paths_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgAlignParams), vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp]
     for name in ("kg_proteins_cluster_aligned", "kg_proteins_cluster_aligned_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
                                        C.POINTER(vp)]
@@ -529,6 +549,10 @@ def load() -> C.CDLL:
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgSearchParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
                                        C.c_int64, C.c_int64, C.POINTER(vp)]
     lib.kg_hitset_stats.argtypes = [vp, C.POINTER(KgSearchStats)]
+    for name in ("kg_proteins_search_paths", "kg_proteins_search_paths_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgSearchParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
+                                       C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(vp)]
+    lib.kg_hitset_trace_stats.argtypes = [vp, C.POINTER(KgTraceStats)]
     # the sets' accessors, by signature: (set) -> count, (set) -> device address, (set, first, count, dst), (set, dst), (set)
     for name in ("kg_sigset_count", "kg_familyset_count", "kg_familyset_edges_count", "kg_hitset_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
                  "kg_selectset_count", "kg_voteset_count", "kg_voteset_bins", "kg_compset_rows", "kg_compset_models"):
@@ -537,7 +561,7 @@ def load() -> C.CDLL:
     for name in ("kg_sigset_device", "kg_regionset_device", "kg_orfset_device", "kg_selectset_device"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = vp
-    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_hitset_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
+    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_hitset_copy", "kg_hitset_paths_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
                  "kg_orfset_junctions_copy", "kg_orfset_coding_scores", "kg_orfset_start_shifts", "kg_selectset_copy",
                  "kg_voteset_copy_votes", "kg_voteset_copy_classes", "kg_voteset_copy_bins", "kg_compset_copy_classes",
                  "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores"):

@@ -94,8 +94,13 @@ int align_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_
     return KG_OK;
 }
 
+// kg_proteins_align_paths: the paths asked for beside the records (kg_host_trace.hpp runs the pass behind align_run)
+struct AlignPathsAsk { int64_t max_trace_cells; kg_alignment_path *paths; };
+int align_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_t *d_seq, const int64_t *d_off, const int32_t *pairs,
+                       int64_t n_pairs, const kg_alignment *aln, const AlignPathsAsk *ask);
+
 int align_impl(kg_table *t, const kg_align_params *prm, const uint8_t *h_seq, const uint8_t *d_seq_in, const int64_t *offsets, int64_t n_prot,
-               const int32_t *pairs, int64_t n_pairs, kg_alignment *out)
+               const int32_t *pairs, int64_t n_pairs, kg_alignment *out, const AlignPathsAsk *ask)
 {
     if (n_pairs == 0) return KG_OK;
     hipStream_t s = t->stream;
@@ -117,7 +122,7 @@ int align_impl(kg_table *t, const kg_align_params *prm, const uint8_t *h_seq, co
     AlignTotals tot;
     if ((rc = align_run(t, sc, prm, d_seq, d_off, offsets, pairs, (uint64_t)n_pairs, &d_pairs, &d_out, &tot))) return rc;
     HIP_TRY(hipMemcpy(out, d_out, (size_t)n_pairs * sizeof(kg_alignment), hipMemcpyDeviceToHost));
-    return KG_OK;
+    return ask ? align_paths_behind(t, sc, prm, d_seq, d_off, pairs, n_pairs, out, ask) : KG_OK;
 }
 
 // the offsets checks of an alignment call: non-decreasing (KG_ERR_ARG, the first offending protein), len_p < 2^24 (KG_ERR_LIMIT)
@@ -134,7 +139,7 @@ int align_check_offsets(const int64_t *offsets, int64_t n_prot)
 }
 
 int align_entry(int device, const kg_align_params *prm, const uint8_t *h_seq, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
-                const int32_t *pairs, int64_t n_pairs, kg_alignment *out)
+                const int32_t *pairs, int64_t n_pairs, kg_alignment *out, const AlignPathsAsk *ask = nullptr)
 {
     if (!prm) return fail(KG_ERR_ARG, "null kg_align_params");
     int rc;
@@ -145,6 +150,8 @@ int align_entry(int device, const kg_align_params *prm, const uint8_t *h_seq, co
     if (n_pairs >= (1ll << 31)) return fail(KG_ERR_LIMIT, "2^31 or more pairs in one call");
     if ((rc = align_check_offsets(offsets, n_prot))) return rc;
     if (n_pairs && (!pairs || !out)) return fail(KG_ERR_ARG, "null argument");
+    if (ask && ask->max_trace_cells < 1) return fail(KG_ERR_ARG, "max_trace_cells must be >= 1");
+    if (ask && n_pairs && !ask->paths) return fail(KG_ERR_ARG, "null paths");
     for (int64_t k = 0; k < 2 * n_pairs; k++)
         if (pairs[k] < 0 || pairs[k] >= n_prot)
             return fail(KG_ERR_ARG, "pair " + kmer_text(k / 2) + ": protein index " + kmer_text(pairs[k]) + " is outside [0, n_prot)");
@@ -153,7 +160,7 @@ int align_entry(int device, const kg_align_params *prm, const uint8_t *h_seq, co
     CallScope cs(device);
     if (cs.rc) return cs.rc;
     rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
-    if (!rc) rc = align_impl(cs.t, prm, h_seq, d_seq, offsets, n_prot, pairs, n_pairs, out);
+    if (!rc) rc = align_impl(cs.t, prm, h_seq, d_seq, offsets, n_prot, pairs, n_pairs, out, ask);
     cs.t->cache.release_all();                          // scratch goes back to the driver
     return rc;
 }

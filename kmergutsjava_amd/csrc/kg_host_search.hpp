@@ -1,6 +1,7 @@
 // kg_host_search.hpp -- kg_proteins_search / kg_proteins_search_device: queries against a database of proteins by shared 8-mers,
 // the best candidates aligned (kernels: kg_search.hpp; the window encode, the sort and the collapse are the derive call's,
-// kg_derive.hpp; the alignment is align_run of kg_host_align.hpp, unchanged).
+// kg_derive.hpp; the alignment is align_run of kg_host_align.hpp, unchanged), and kg_proteins_search_paths, which traces the
+// ordered records behind it (trace_run of kg_host_trace.hpp).
 // Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_cluster.hpp (it uses the derive call's block counts,
 // its histogram and its bytes-per-window figure as the cluster call does) and kg_host_align.hpp.
 #pragma once
@@ -10,6 +11,9 @@ struct kg_hitset {
     uint8_t *d_block = nullptr;         // hit_start[n_q + 1] (int64), then count * 40 bytes (hipMalloc, owned)
     int64_t count = 0, n_q = 0;
     kg_search_stats st = {};
+    kg_alignment_path *d_paths = nullptr;   // kg_proteins_search_paths only: one record per hit record (hipMalloc, owned)
+    bool has_paths = false;
+    kg_trace_stats tst = {};
     const int64_t *starts() const { return (const int64_t *)d_block; }
     const kg_search_hit *hits() const { return (const kg_search_hit *)(d_block + ((size_t)n_q + 1) * 8); }
 };
@@ -22,8 +26,45 @@ namespace {
 constexpr uint64_t kSearchBytesPerPair = 112;                         // device bytes one join pair needs, at most
 constexpr uint64_t kSearchPairsMax = (1ull << 32) - (1ull << 22);     // the 32-bit scans and indices of the join
 
+// kg_proteins_search_paths: which records are traced, and the cap of a box
+struct SearchPathsAsk { int trace; int64_t max_trace_cells; };
+
+// The ordered records -> one path record each, same index, in a block of the set's own.  KG_TRACE_HITS traces the records with
+// status hit, KG_TRACE_ALL every aligned record with score >= 1; a is the query, b the target.
+int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, const uint8_t *d_seq, const int64_t *d_off, int64_t n_db,
+                        const kg_search_hit *d_hits, uint64_t NK, const SearchPathsAsk *ask, kg_hitset *set)
+{
+    struct Guard { uint8_t *p; ~Guard() { if (p) (void)hipFree(p); } } guard{nullptr};
+    int rc;
+    if ((rc = dalloc_detached(t, &guard.p, std::max<uint64_t>(NK, 1) * sizeof(kg_alignment_path)))) return rc;
+    TraceTotals tot;
+    if (NK > 0) {
+        std::vector<kg_search_hit> hits(NK);
+        HIP_TRY(hipMemcpy(hits.data(), d_hits, NK * sizeof(kg_search_hit), hipMemcpyDeviceToHost));
+        std::vector<int32_t> pairs(2 * NK);
+        std::vector<TraceEnd> ends(NK);
+        for (uint64_t k = 0; k < NK; k++) {
+            const kg_search_hit &h = hits[k];
+            pairs[2 * k] = (int32_t)(n_db + h.query);
+            pairs[2 * k + 1] = h.target;
+            ends[k] = TraceEnd{h.score, h.end_query, h.end_target, ask->trace == KG_TRACE_ALL ? h.status != 2 && h.score >= 1 : h.status == 0};
+        }
+        kg::TracePath *d_paths = nullptr;
+        if ((rc = trace_run(t, sc, al, d_seq, d_off, pairs.data(), ends, NK, ask->max_trace_cells, &d_paths, &tot))) return rc;
+        HIP_TRY(hipMemcpy(guard.p, d_paths, NK * sizeof(kg_alignment_path), hipMemcpyDeviceToDevice));
+    }
+    set->tst.traced = tot.traced;
+    set->tst.untraced = tot.untraced;
+    set->tst.cells = tot.cells;
+    set->tst.ms_trace = tot.ms;
+    set->d_paths = (kg_alignment_path *)guard.p; guard.p = nullptr;
+    set->has_paths = true;
+    return KG_OK;
+}
+
 int search_impl(kg_table *t, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq_in,
-                const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset *set)
+                const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset *set,
+                const SearchPathsAsk *ask)
 {
     kg_search_stats &st = set->st;
     const int64_t n_q = n_prot - n_db;
@@ -300,11 +341,12 @@ int search_impl(kg_table *t, const kg_search_params *prm, const kg_align_params 
     st.ms_total = ev.ms(0, 5);
     set->d_block = guard.p; guard.p = nullptr;
     set->count = (int64_t)NK;
-    return KG_OK;
+    return ask ? search_paths_behind(t, sc, al, d_seq, d_off, n_db, set->hits(), NK, ask, set) : KG_OK;
 }
 
 int search_entry(int device, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq,
-                 const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset **out)
+                 const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset **out,
+                 const SearchPathsAsk *ask = nullptr)
 {
     if (!out) return fail(KG_ERR_ARG, "null argument");
     *out = nullptr;
@@ -317,6 +359,8 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     if (int rc = align_check_params(al)) return rc;
     if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
     if (max_pairs < 0) return fail(KG_ERR_ARG, "max_pairs must be >= 0");
+    if (ask && ask->trace != KG_TRACE_HITS && ask->trace != KG_TRACE_ALL) return fail(KG_ERR_ARG, "trace must be KG_TRACE_HITS or KG_TRACE_ALL");
+    if (ask && ask->max_trace_cells < 1) return fail(KG_ERR_ARG, "max_trace_cells must be >= 1");
     if (n_prot < 0) return fail(KG_ERR_ARG, "n_prot < 0");
     if (n_prot >= (1ll << 29)) return fail(KG_ERR_LIMIT, "2^29 or more proteins in one call");
     if (n_db < 0 || n_db > n_prot) return fail(KG_ERR_ARG, "n_db must be in 0..n_prot");
@@ -335,7 +379,7 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
     set->device = device;
     int rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
-    if (!rc) rc = search_impl(cs.t, prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, set);
+    if (!rc) rc = search_impl(cs.t, prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, set, ask);
     cs.t->cache.release_all();                          // scratch goes back to the driver
     if (rc) { std::string keep = g_err; kg_hitset_free(set); g_err = keep; return rc; }
     if (getenv("KG_DEBUG"))
@@ -365,7 +409,35 @@ int kg_proteins_search_device(int device, const kg_search_params *p, const kg_al
     return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out);
 }
 
+int kg_proteins_search_paths(int device, const kg_search_params *p, const kg_align_params *align, const uint8_t *seq, const int64_t *offsets,
+                             int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, int trace, int64_t max_trace_cells,
+                             kg_hitset **out)
+{
+    const SearchPathsAsk ask{trace, max_trace_cells};
+    return search_entry(device, p, align, seq, nullptr, offsets, n_prot, n_db, max_windows, max_pairs, out, &ask);
+}
+
+int kg_proteins_search_paths_device(int device, const kg_search_params *p, const kg_align_params *align, const uint8_t *d_seq,
+                                    const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, int trace,
+                                    int64_t max_trace_cells, kg_hitset **out)
+{
+    const SearchPathsAsk ask{trace, max_trace_cells};
+    return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, &ask);
+}
+
 int64_t kg_hitset_count(const kg_hitset *s) { return s ? s->count : 0; }
+
+int kg_hitset_paths_copy(const kg_hitset *s, int64_t first, int64_t count, kg_alignment_path *dst)
+{
+    if (s && !s->has_paths) return fail(KG_ERR_ARG, "kg_hitset_paths_copy: the set was made without paths");
+    return copy_records(s, s ? s->device : 0, s ? s->d_paths : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_hitset_paths_copy");
+}
+
+int kg_hitset_trace_stats(const kg_hitset *s, kg_trace_stats *out)
+{
+    if (s && !s->has_paths) return fail(KG_ERR_ARG, "kg_hitset_trace_stats: the set was made without paths");
+    return copy_stats(s, s ? &s->tst : nullptr, out);
+}
 
 int kg_hitset_copy(const kg_hitset *s, int64_t first, int64_t count, kg_search_hit *dst)
 {
@@ -385,6 +457,10 @@ void kg_hitset_free(kg_hitset *s)
     if (s->d_block) {
         (void)hipSetDevice(s->device);
         (void)hipFree(s->d_block);
+    }
+    if (s->d_paths) {
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->d_paths);
     }
     delete s;
 }

@@ -16,6 +16,7 @@
 #include "kg_derive.hpp"
 #include "kg_cluster.hpp"
 #include "kg_align.hpp"
+#include "kg_trace.hpp"
 #include "kg_search.hpp"
 #include "kg_assign.hpp"
 #include "kg_regions.hpp"
@@ -48,6 +49,7 @@
 #include "kg_host_derive.hpp"
 #include "kg_host_merge.hpp"
 #include "kg_host_align.hpp"
+#include "kg_host_trace.hpp"
 #include "kg_host_cluster.hpp"
 #include "kg_host_search.hpp"
 #include "kg_host_assign.hpp"

@@ -746,11 +746,15 @@ def _align_params(min_ratio_pct: int = 50, ref="longer", gap_open: int = 11, gap
 
 
 def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1, max_cells: int = N.ALIGN_DEFAULT_MAX_CELLS, matrix=None,
-                   device: int = 0, device_ptr: Optional[int] = None) -> np.ndarray:
+                   device: int = 0, device_ptr: Optional[int] = None, paths: bool = False,
+                   max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS):
     """Local alignment scores of protein pairs, on the GPU (include/kmerguts_hip.h kg_proteins_align states the rule): affine
-    gaps, no traceback, the built-in matrix is BLOSUM62 (align_scores.BLOSUM62); matrix: 21 x 21 in code order.  seq / offsets /
+    gaps, the built-in matrix is BLOSUM62 (align_scores.BLOSUM62); matrix: 21 x 21 in code order.  seq / offsets /
     device_ptr as for cluster_proteins; pairs: int32[n_pairs][2] of (a, b) protein indices, any order, repeats allowed.
-    -> _native.ALIGNMENT_DTYPE[n_pairs] in pair order (status 1 and score -1: more than max_cells cells, not aligned)."""
+    -> _native.ALIGNMENT_DTYPE[n_pairs] in pair order (status 1 and score -1: more than max_cells cells, not aligned).
+    paths=True: the traceback pass runs behind the scores (kg_proteins_align_paths): -> (the same records,
+    _native.ALIGN_PATH_DTYPE[n_pairs]: start, identical, positive and gap counts; status 2: a box of more than max_trace_cells
+    cells, not traced)."""
     off = _offsets(offsets, "int64[n_prot + 1]")
     n = off.size - 1
     pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
@@ -761,6 +765,16 @@ def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1,
     out = np.zeros(len(pr), dtype=N.ALIGNMENT_DTYPE)
     lib = N.load()
     pp, op = _ptr(pr), _ptr(out)
+    if paths:
+        pth = np.zeros(len(pr), dtype=N.ALIGN_PATH_DTYPE)
+        if device_ptr is not None:
+            N.check(lib.kg_proteins_align_paths_device(device, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, pp, len(pr),
+                                                       int(max_trace_cells), op, _ptr(pth)))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_proteins_align_paths(device, C.byref(p), _ptr(arr), off.ctypes.data, n, pp, len(pr), int(max_trace_cells), op,
+                                                _ptr(pth)))
+        return out, pth
     if device_ptr is not None:
         N.check(lib.kg_proteins_align_device(device, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, pp, len(pr), op))
     else:
@@ -817,20 +831,33 @@ def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20,
 
 def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256,
                     align: Optional[dict] = None, max_windows: int = 0, max_pairs: int = 0, device: int = 0,
-                    device_ptr: Optional[int] = None):
+                    device_ptr: Optional[int] = None, paths: Optional[str] = None, max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS):
     """Proteins [n_db, n_prot) searched against proteins [0, n_db), on the GPU (include/kmerguts_hip.h kg_proteins_search states
     the rule): the targets that share at least min_shared distinct unmasked 8-mers with a query, the max_cand with the most
     aligned, a hit where 100 * score >= min_ratio_pct * ref.  seq / offsets / device_ptr as for cluster_proteins; align: None
     (the defaults) or a dict as for cluster_proteins; max_windows = 0 and max_pairs = 0 size the one pass and the join from
     free device memory.  The defaults 2, 8 and 256 are this project's choice.
-    -> (numpy records of _native.SEARCH_HIT_DTYPE in (query, rank) order, hit_start int64[n_q + 1], the call's statistics)."""
+    -> (numpy records of _native.SEARCH_HIT_DTYPE in (query, rank) order, hit_start int64[n_q + 1], the call's statistics).
+    paths: None, "hits" (the records with status hit are traced) or "all" (every aligned record with score >= 1):
+    kg_proteins_search_paths; -> (records, hit_start, _native.ALIGN_PATH_DTYPE records of the same indices, statistics), the
+    statistics with traced, untraced, trace_cells and ms_trace as well."""
+    if paths is not None and paths not in N.TRACE_MODES:
+        raise ValueError("paths must be None, 'hits' or 'all'")
     off = _offsets(offsets, "int64[n_prot + 1]")
     n = off.size - 1
     p = N.KgSearchParams(int(min_shared), int(max_cand), int(max_db_per_kmer), 0)
     ap, _keep = _align_params(**(align or {}))
     h = C.c_void_p()
     lib = N.load()
-    if device_ptr is not None:
+    if paths is not None:
+        tail = (int(max_windows), int(max_pairs), N.TRACE_MODES[paths], int(max_trace_cells), C.byref(h))
+        if device_ptr is not None:
+            N.check(lib.kg_proteins_search_paths_device(device, C.byref(p), C.byref(ap), C.c_void_p(device_ptr), off.ctypes.data, n,
+                                                        int(n_db), *tail))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_proteins_search_paths(device, C.byref(p), C.byref(ap), _ptr(arr), off.ctypes.data, n, int(n_db), *tail))
+    elif device_ptr is not None:
         N.check(lib.kg_proteins_search_device(device, C.byref(p), C.byref(ap), C.c_void_p(device_ptr), off.ctypes.data, n, int(n_db),
                                               int(max_windows), int(max_pairs), C.byref(h)))
     else:
@@ -842,6 +869,13 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
         N.check(lib.kg_hitset_stats(h, C.byref(st)))
         starts = np.zeros(int(st.queries) + 1, dtype=np.int64)
         N.check(lib.kg_hitset_starts_copy(h, starts.ctypes.data))
+        if paths is not None:
+            tst = N.KgTraceStats()
+            N.check(lib.kg_hitset_trace_stats(h, C.byref(tst)))
+            stats = dict(st.as_dict(), traced=tst.traced, untraced=tst.untraced, trace_cells=tst.cells, ms_trace=tst.ms_trace)
+            count = int(lib.kg_hitset_count(h))
+            return (_copy_records(lib.kg_hitset_copy, h, count, N.SEARCH_HIT_DTYPE), starts,
+                    _copy_records(lib.kg_hitset_paths_copy, h, count, N.ALIGN_PATH_DTYPE), stats)
         return _copy_records(lib.kg_hitset_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_HIT_DTYPE), starts, st.as_dict()
     finally:
         lib.kg_hitset_free(h)

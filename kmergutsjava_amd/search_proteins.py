@@ -6,13 +6,14 @@ how much.  The step that names what `annotate` leaves at `none`.
                                                [--min-ratio 50] [--align-ref longer|query] [--gap-open 11] [--gap-extend 1]
                                                [--max-cells N] [--all] [-A db_annotations.tsv [--transfer out.tsv]]
                                                [--truth query_annotations.tsv]
+                                               [--paths [--trace hits|all] [--max-trace-cells N]]
 
 The proteins of all -d files are the database, those of all -q files the queries, each in the order given (FASTA as
 make_signatures reads it).  An id that occurs twice within the database or within the queries is an error; the same id in both
 is allowed.  include/kmerguts_hip.h states the rule: a target is a candidate of a query when the two share at least --min-shared
 distinct exact 8-mers, not counting the 8-mers that more than --max-db-per-kmer targets have (repeats and low complexity); the
 --max-cand candidates with the most shared 8-mers (on a tie the earlier target) are aligned (BLOSUM62 in align_scores.py, a gap of
-k residues costs --gap-open + k * --gap-extend, no traceback); an aligned pair is a hit when 100 * score >= --min-ratio * ref,
+k residues costs --gap-open + k * --gap-extend, no traceback without --paths); an aligned pair is a hit when 100 * score >= --min-ratio * ref,
 where ref is the larger of the two proteins' self-scores (--align-ref longer, the default) or the query's own (--align-ref
 query).  A pair of more than --max-cells cells (default 2^26) is not aligned: skipped.  The defaults 2, 8, 256, 50 and longer are
 this project's choice.
@@ -26,6 +27,14 @@ written; --all writes every record.
 a hit and whose target has a function in -A.
 --truth (the same format, for the queries) adds `labelled, agree, disagree, missed` to the summary, compared by function name: of
 the labelled queries, those that got their own function, another one, or none.
+--paths runs the traceback pass behind the alignment (kg_proteins_search_paths): where the alignment starts, how many columns it
+has, and how many of them are identical, positive or gaps.  --trace hits (the default) traces the hit records only, --trace all
+every aligned record with a score (the default with --all).  A record whose prefix box (query end * target end) has more than
+--max-trace-cells cells (default 2^24) is not traced.  Every -o line then gains, behind the status and in front of the function
+field of -A: `query start<TAB>target start<TAB>columns<TAB>identical<TAB>identity %<TAB>positive<TAB>gap opens<TAB>gap columns<TAB>
+query cover %<TAB>target cover %`: the starts 1-based, identity % = 100 * identical // columns, the covers 100 * (end - start
++ 1) // length of the protein; each field is `-` for a record without a traced path.  The summary line gains `, traced: N,
+untraced: M, trace ms: X`.  Without --paths every byte is as before.
 The summary line goes to stderr.
 """
 from __future__ import annotations
@@ -47,11 +56,30 @@ def _ref(h, align_ref: str) -> int:
     return int(h["self_query"]) if align_ref in ("query", "member") else max(int(h["self_query"]), int(h["self_target"]))
 
 
-def format_hits(qids, dids, hits, hit_start, max_hits: int = 1, write_all: bool = False, align_ref: str = "longer", functions=None) -> bytes:
-    """functions: None, or {target id: (function, otu)}: every line gains the target's function or `-`."""
+PATH_FIELDS = 10
+TRACED = 0
+
+
+def path_fields(h, p, len_query: int, len_target: int) -> bytes:
+    """The ten fields --paths adds to a line: h the hit record, p its path record."""
+    if int(p["status"]) != TRACED:
+        return b"\t-" * PATH_FIELDS
+    sq, st_, eq, et = int(p["start_a"]), int(p["start_b"]), int(h["end_query"]), int(h["end_target"])
+    ga, gb, ident = int(p["gap_cols_a"]), int(p["gap_cols_b"]), int(p["identical"])
+    columns = (eq - sq + 1) - gb + ga + gb              # residue columns + gap columns
+    return b"\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d" % (sq + 1, st_ + 1, columns, ident, 100 * ident // columns, int(p["positive"]),
+                                                          int(p["gap_opens"]), ga + gb, 100 * (eq - sq + 1) // len_query,
+                                                          100 * (et - st_ + 1) // len_target)
+
+
+def format_hits(qids, dids, hits, hit_start, max_hits: int = 1, write_all: bool = False, align_ref: str = "longer", functions=None,
+                paths=None, qlens=None, dlens=None) -> bytes:
+    """functions: None, or {target id: (function, otu)}: every line gains the target's function or `-`.  paths: None, or one
+    path record per hit record with the proteins' lengths in qlens / dlens: every line gains path_fields in front of it."""
     out = []
     for q, qid in enumerate(qids):
-        for h in hits[int(hit_start[q]):int(hit_start[q + 1])]:
+        for k in range(int(hit_start[q]), int(hit_start[q + 1])):
+            h = hits[k]
             status = int(h["status"])
             if not write_all and (status != HIT or int(h["rank"]) >= max_hits):
                 continue
@@ -59,6 +87,8 @@ def format_hits(qids, dids, hits, hit_start, max_hits: int = 1, write_all: bool 
             ratio = b"%d" % (100 * score // ref) if score >= 0 and ref > 0 else b"-"
             line = b"%s\t%d\t%s\t%d\t%d\t%d\t%s\t%d\t%d\t%s" % (qid, int(h["rank"]), did, int(h["shared"]), score, ref, ratio,
                                                                int(h["end_query"]) + 1, int(h["end_target"]) + 1, STATUS[status])
+            if paths is not None:
+                line += path_fields(h, paths[k], qlens[q], dlens[int(h["target"])])
             if functions is not None:
                 line += b"\t" + (functions[did][0] if did in functions else b"-")
             out.append(line + b"\n")
@@ -99,9 +129,13 @@ def compare_truth(qids, got, truth) -> dict:
 
 def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: int = 8, max_hits: int = 1, max_db_per_kmer: int = 256,
                     align: Optional[dict] = None, write_all: bool = False, annotations: Optional[str] = None,
-                    transfer: Optional[str] = None, truth: Optional[str] = None, device: int = 0, search=None) -> str:
+                    transfer: Optional[str] = None, truth: Optional[str] = None, device: int = 0, search=None,
+                    paths: Optional[str] = None, max_trace_cells: Optional[int] = None) -> str:
     """Write the files; returns the summary line.  `search` replaces hotpath.search_proteins (tests).  align: None, or the
-    alignment parameters of hotpath.search_proteins (ref "query" is its "member")."""
+    alignment parameters of hotpath.search_proteins (ref "query" is its "member").  paths: None, "hits" or "all" (--paths with
+    its --trace); max_trace_cells: None for the library's default."""
+    if paths not in (None, "hits", "all"):
+        raise ValueError("--trace must be hits or all")
     if max_hits < 1:
         raise ValueError("--max-hits must be >= 1")
     if transfer is not None and annotations is None:
@@ -123,10 +157,17 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
     if search is None:
         from . import hotpath
         search = hotpath.search_proteins
-    hits, hit_start, st = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
-                                 max_db_per_kmer=max_db_per_kmer, align=align, device=device)
+    recs = None
+    if paths is None:
+        hits, hit_start, st = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
+                                     max_db_per_kmer=max_db_per_kmer, align=align, device=device)
+    else:
+        more = {} if max_trace_cells is None else {"max_trace_cells": max_trace_cells}
+        hits, hit_start, recs, st = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
+                                           max_db_per_kmer=max_db_per_kmer, align=align, device=device, paths=paths, **more)
     with open(out, "wb") as f:
-        f.write(format_hits(qids, dids, hits, hit_start, max_hits, write_all, align_ref, functions))
+        f.write(format_hits(qids, dids, hits, hit_start, max_hits, write_all, align_ref, functions, recs, [len(x) for x in qseqs],
+                            [len(x) for x in dseqs]))
     got = transferred(qids, dids, hits, hit_start, functions) if functions is not None else {}
     if transfer is not None:
         with open(transfer, "wb") as f:
@@ -138,6 +179,8 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
     if want is not None:
         t = compare_truth(qids, got, want)
         line += ", labelled: %d, agree: %d, disagree: %d, missed: %d" % (t["labelled"], t["agree"], t["disagree"], t["missed"])
+    if paths is not None:
+        line += ", traced: %d, untraced: %d, trace ms: %.3f" % (st["traced"], st["untraced"], st.get("ms_trace", 0.0))
     return line
 
 
@@ -161,12 +204,20 @@ def main(argv=None) -> int:
     ap.add_argument("-A", default=None, metavar="ANNOTATIONS", help="protein_id<TAB>function[<TAB>otu] lines of the database")
     ap.add_argument("--transfer", default=None, metavar="OUT", help="with -A: write query_id<TAB>function lines for make_signatures -A")
     ap.add_argument("--truth", default=None, metavar="ANNOTATIONS", help="with -A: the queries' own annotations to compare with")
+    ap.add_argument("--paths", action="store_true", help="trace the alignments: start, columns, identity, gaps and coverage on every -o line")
+    ap.add_argument("--trace", choices=("hits", "all"), default=None,
+                    help="with --paths: trace the hit records only (default), or every aligned record with a score (default with --all)")
+    ap.add_argument("--max-trace-cells", type=int, default=None,
+                    help="with --paths: a record whose prefix box has more cells is not traced (default 2^24, this project's choice)")
     a = ap.parse_args(argv)
+    if not a.paths and (a.trace is not None or a.max_trace_cells is not None):
+        ap.error("--trace and --max-trace-cells need --paths")
+    paths = (a.trace or ("all" if a.all else "hits")) if a.paths else None
     from . import _native as N
     align = dict(min_ratio_pct=a.min_ratio, ref=a.align_ref, gap_open=a.gap_open, gap_extend=a.gap_extend, max_cells=a.max_cells)
     try:
         line = search_proteins(a.d, a.q, a.o, a.min_shared, a.max_cand, a.max_hits, a.max_db_per_kmer, align, a.all, a.A, a.transfer,
-                               a.truth)
+                               a.truth, paths=paths, max_trace_cells=a.max_trace_cells)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1
