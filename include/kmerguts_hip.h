@@ -693,6 +693,52 @@ int kg_proteins_search_paths_device(int device, const kg_search_params *p, const
 int kg_hitset_paths_copy(const kg_hitset *s, int64_t first, int64_t count, kg_alignment_path *dst);
 int kg_hitset_trace_stats(const kg_hitset *s, kg_trace_stats *out);
 
+/* ---- the search with reduced-alphabet spaced seeds (kernel: kg_seed.hpp) ----
+ *
+ * kg_proteins_search finds a target only where it shares exact 8-mers with the query.  Here the prefilter seeds on a reduced
+ * amino-acid alphabet, in which a substitution inside a class does not break a seed, and on spaced shapes, in which a
+ * substitution on a don't-care position does not break it.  This rule is the project's own.  Integers only.
+ *   The seed set has three parts.
+ *   Class map.  cls[20] in code order ACDEFGHIKLMNPQRSTVWY, with values in 0..A-1.  Every class 0..A-1 is used, and
+ *   2 <= A <= 20 (A is alphabet_size).
+ *   Shapes.  n_shapes in 1..4.  Each shape is a 32-bit mask in which bit j set means position j of the window is a care
+ *   position.  Bit 0 must be set.
+ *   Span and weight.  span_k is the index of the highest set bit plus 1, so 1 <= span_k <= 32.  All shapes have the same
+ *   number w of set bits, the weight.
+ *   Space.  The seed space n_shapes * A^w must be at most 2^35.  The window key id << b | p then fits 64 bits for the
+ *   n_prot < 2^29 the search already allows.
+ *   Windows.  Window i of protein p under shape k is valid iff i + span_k < len_p and every care position i + j has a residue
+ *   code below 20.  The last position is left out, as for the derive windows.  This keeps the rule a superset of the existing
+ *   one.  Don't-care positions may hold any byte.
+ *   Seed id.  The id is k * A^w + value.  value is the base-A number of the classes at the care positions, with the lowest
+ *   position as the most significant digit.
+ *   The rest is unchanged.  Everything behind this is kg_proteins_search's rule with "k-mer v" read as "seed id": D(v), Q(v),
+ *   masking by max_db_per_kmer, s(q, d), candidates, alignment, order and records.  s(q, d) counts the distinct unmasked seed
+ *   ids the two proteins share.  The same value under two shapes counts as two.  kg_search_stats keeps its layout.
+ *   valid_windows counts valid (window, shape) pairs.  pairs counts distinct (seed id, protein) pairs.  kmers, kmers_joined
+ *   and kmers_masked count distinct seed ids.  max_windows and the bytes-per-window figure apply to emitted seeds.
+ *   Identity.  With the identity class map (A = 20) and the one shape 0xFF, the records, hit_start and every count of
+ *   kg_search_stats equal kg_proteins_search's byte for byte.
+ *   Built-in seed set `reduced` (this project's choice, not tuned).  Alphabet reduced11: the classes are AST, C, DEKNQR, F, G,
+ *   H, ILV, M, P, W, Y, numbered in that order.  Two shapes of weight 9, written with the leftmost character as position 0:
+ *   111101101011 (span 12) and 110110011010011 (span 15).  Space 2 * 11^9, about 4.7 * 10^9.
+ * kg_seed_params_builtin fills *out with KG_SEEDS_EXACT (the identity map and 0xFF) or KG_SEEDS_REDUCED.
+ * kg_proteins_search_seeded / _device: kg_proteins_search's arguments, the seed set, and trace: 0 gives no paths, and
+ * max_trace_cells is then ignored; KG_TRACE_HITS and KG_TRACE_ALL behave as in kg_proteins_search_paths.  The result is a
+ * kg_hitset, read with the getters above.  Errors as kg_proteins_search, and KG_ERR_ARG, the message naming the first offender:
+ * null seeds, n_shapes outside 1..4, alphabet_size outside 2..20, a class at or above alphabet_size, an unused class, a shape
+ * without bit 0, unequal weights, shape entries at or above n_shapes not zero, reserved != 0, seed space over 2^35. */
+#define KG_SEEDS_EXACT 0
+#define KG_SEEDS_REDUCED 1
+typedef struct kg_seed_params { int32_t n_shapes; int32_t alphabet_size; uint8_t cls[20]; uint32_t shape[4]; int32_t reserved; } kg_seed_params; /* 48 B */
+int kg_seed_params_builtin(int which, kg_seed_params *out);
+int kg_proteins_search_seeded(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                              const uint8_t *seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                              int64_t max_pairs, int trace, int64_t max_trace_cells, kg_hitset **out);
+int kg_proteins_search_seeded_device(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                                     const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                                     int64_t max_pairs, int trace, int64_t max_trace_cells, kg_hitset **out);
+
 /* ---- assigning functions: the CALL records of an -a scan -> one function per protein (kernels: kg_assign.hpp) ----
  *
  * The reference stops at the CALL lines (KGJ:398-404, 526-536); this rule is the project's own.

@@ -425,6 +425,19 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_seed_params (48 B, kg_proteins_search_seeded*): cls = the class of each residue in code order ACDEFGHIKLMNPQRSTVWY
+     *  (values below alphabet_size, every class used), shape = up to four masks of equal weight, bit j = position j is a care
+     *  position, bit 0 set, entries from n_shapes on zero; reserved 0.  kg_seed_params_builtin fills one. */
+    class KgSeedParams extends Structure {
+        public int n_shapes, alphabet_size;
+        public byte[] cls = new byte[20];
+        public int[] shape = new int[4];
+        public int reserved;
+        public KgSeedParams() {
+            setFieldOrder(new String[] {"n_shapes", "alphabet_size", "cls", "shape", "reserved"});
+        }
+    }
+
     /** struct kg_search_hit (40 B): one aligned or skipped candidate of a query; status 0 hit, 1 below, 2 skipped; rank from 0. */
     class KgSearchHit extends Structure {
         public int query, target, shared, score, self_query, self_target, end_query, end_target, status, rank;
@@ -535,6 +548,15 @@ public interface KmerGutsHip extends Library {
                                         long nDb, long maxWindows, long maxPairs, int trace, long maxTraceCells, PointerByReference out);
     int kg_hitset_paths_copy(Pointer set, long first, long count, Pointer dst);   // kg_alignment_path[count], 32 B each, same indices
     int kg_hitset_trace_stats(Pointer set, KgTraceStats out);
+    /** a built-in seed set into out: which = KG_SEEDS_EXACT (0: the identity map and the shape 0xFF) or KG_SEEDS_REDUCED (1) */
+    int kg_seed_params_builtin(int which, KgSeedParams out);
+    /** kg_proteins_search with reduced-alphabet spaced seeds in the 8-mers' place; trace = 0 (no paths; maxTraceCells is ignored),
+     *  KG_TRACE_HITS or KG_TRACE_ALL; the set is read with the kg_hitset getters */
+    int kg_proteins_search_seeded(int device, KgSearchParams params, KgSeedParams seeds, KgAlignParams align, byte[] seq, long[] offsets,
+                                  long nProt, long nDb, long maxWindows, long maxPairs, int trace, long maxTraceCells, PointerByReference out);
+    int kg_proteins_search_seeded_device(int device, KgSearchParams params, KgSeedParams seeds, KgAlignParams align, Pointer dSeq,
+                                         long[] offsets, long nProt, long nDb, long maxWindows, long maxPairs, int trace, long maxTraceCells,
+                                         PointerByReference out);
     Pointer kg_table_device_entries(Pointer table);
     long kg_table_records(Pointer table);
     int kg_table_info(Pointer table, long[] numSigs, long[] entrySize, long[] version, long[] occupied);

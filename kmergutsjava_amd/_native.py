@@ -43,6 +43,7 @@ EXPORTS = (
     "kg_proteins_search", "kg_proteins_search_device", "kg_hitset_count", "kg_hitset_copy", "kg_hitset_starts_copy",
     "kg_hitset_stats", "kg_hitset_free",
     "kg_proteins_search_paths", "kg_proteins_search_paths_device", "kg_hitset_paths_copy", "kg_hitset_trace_stats",
+    "kg_seed_params_builtin", "kg_proteins_search_seeded", "kg_proteins_search_seeded_device",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
@@ -387,6 +388,15 @@ class KgSearchParams(C.Structure):
     _fields_ = [("min_shared", C.c_int32), ("max_cand", C.c_int32), ("max_db_per_kmer", C.c_int32), ("reserved", C.c_int32)]
 
 
+class KgSeedParams(C.Structure):
+    """struct kg_seed_params (kg_proteins_search_seeded*): the class map in code order ACDEFGHIKLMNPQRSTVWY and up to four shapes."""
+    _fields_ = [("n_shapes", C.c_int32), ("alphabet_size", C.c_int32), ("cls", C.c_uint8 * 20), ("shape", C.c_uint32 * 4),
+                ("reserved", C.c_int32)]
+
+
+SEEDS_EXACT, SEEDS_REDUCED = 0, 1       # KG_SEEDS_*: kg_seed_params_builtin
+
+
 class KgSearchStats(C.Structure):
     """struct kg_search_stats."""
     _fields_ = [("targets", C.c_int64), ("queries", C.c_int64), ("valid_windows", C.c_int64), ("pairs", C.c_int64),
@@ -553,6 +563,10 @@ def load() -> C.CDLL:
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgSearchParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
                                        C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(vp)]
     lib.kg_hitset_trace_stats.argtypes = [vp, C.POINTER(KgTraceStats)]
+    lib.kg_seed_params_builtin.argtypes = [C.c_int, C.POINTER(KgSeedParams)]
+    for name in ("kg_proteins_search_seeded", "kg_proteins_search_seeded_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgSearchParams), C.POINTER(KgSeedParams), C.POINTER(KgAlignParams), vp, vp,
+                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(vp)]
     # the sets' accessors, by signature: (set) -> count, (set) -> device address, (set, first, count, dst), (set, dst), (set)
     for name in ("kg_sigset_count", "kg_familyset_count", "kg_familyset_edges_count", "kg_hitset_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
                  "kg_selectset_count", "kg_voteset_count", "kg_voteset_bins", "kg_compset_rows", "kg_compset_models"):

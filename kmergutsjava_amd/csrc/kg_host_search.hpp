@@ -1,7 +1,8 @@
 // kg_host_search.hpp -- kg_proteins_search / kg_proteins_search_device: queries against a database of proteins by shared 8-mers,
 // the best candidates aligned (kernels: kg_search.hpp; the window encode, the sort and the collapse are the derive call's,
 // kg_derive.hpp; the alignment is align_run of kg_host_align.hpp, unchanged), and kg_proteins_search_paths, which traces the
-// ordered records behind it (trace_run of kg_host_trace.hpp).
+// ordered records behind it (trace_run of kg_host_trace.hpp).  kg_proteins_search_seeded is the same call with the window kernel
+// of kg_seed.hpp in the derive kernel's place: seed ids of a reduced alphabet and spaced shapes where the exact call has 8-mers.
 // Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_cluster.hpp (it uses the derive call's block counts,
 // its histogram and its bytes-per-window figure as the cluster call does) and kg_host_align.hpp.
 #pragma once
@@ -18,7 +19,7 @@ struct kg_hitset {
     const kg_search_hit *hits() const { return (const kg_search_hit *)(d_block + ((size_t)n_q + 1) * 8); }
 };
 
-static_assert(sizeof(kg_search_hit) == 40 && sizeof(kg_search_params) == 16 && sizeof(kg_search_stats) == 136,
+static_assert(sizeof(kg_search_hit) == 40 && sizeof(kg_search_params) == 16 && sizeof(kg_search_stats) == 136 && sizeof(kg_seed_params) == 48,
               "record layouts of include/kmerguts_hip.h");
 
 namespace {
@@ -28,6 +29,100 @@ constexpr uint64_t kSearchPairsMax = (1ull << 32) - (1ull << 22);     // the 32-
 
 // kg_proteins_search_paths: which records are traced, and the cap of a box
 struct SearchPathsAsk { int trace; int64_t max_trace_cells; };
+
+// kg_proteins_search_seeded: a checked kg_seed_params.  space = n_shapes * alphabet^weight <= 2^35
+struct SeedPlan { kg::SeedSpec spec; uint32_t span_min; uint64_t space; };
+
+// the first offender of a kg_seed_params, in the header's order, or the plan
+int seed_plan(const kg_seed_params *sp, SeedPlan *out)
+{
+    if (!sp) return fail(KG_ERR_ARG, "null kg_seed_params");
+    if (sp->n_shapes < 1 || sp->n_shapes > kg::kSeedMaxShapes) return fail(KG_ERR_ARG, "n_shapes must be in 1..4");
+    if (sp->alphabet_size < 2 || sp->alphabet_size > 20) return fail(KG_ERR_ARG, "alphabet_size must be in 2..20");
+    uint32_t used = 0;
+    for (int c = 0; c < 20; c++) {
+        if (sp->cls[c] >= sp->alphabet_size)
+            return fail(KG_ERR_ARG, "cls[" + kmer_text(c) + "] must be below alphabet_size: " + kmer_text(sp->cls[c]) + " is not below " +
+                                        kmer_text(sp->alphabet_size));
+        used |= 1u << sp->cls[c];
+    }
+    for (int a = 0; a < sp->alphabet_size; a++)
+        if (!(used >> a & 1u)) return fail(KG_ERR_ARG, "class " + kmer_text(a) + " is used by no residue: every class below alphabet_size must be");
+    for (int k = 0; k < sp->n_shapes; k++)
+        if (!(sp->shape[k] & 1u)) return fail(KG_ERR_ARG, "shape[" + kmer_text(k) + "] must have bit 0 set");
+    const int w = __builtin_popcount(sp->shape[0]);
+    for (int k = 1; k < sp->n_shapes; k++)
+        if (__builtin_popcount(sp->shape[k]) != w)
+            return fail(KG_ERR_ARG, "shapes must have equal weights: shape[" + kmer_text(k) + "] has " +
+                                        kmer_text(__builtin_popcount(sp->shape[k])) + " care positions, shape[0] has " + kmer_text(w));
+    for (int k = sp->n_shapes; k < kg::kSeedMaxShapes; k++)
+        if (sp->shape[k] != 0) return fail(KG_ERR_ARG, "shape[" + kmer_text(k) + "] must be 0: n_shapes is " + kmer_text(sp->n_shapes));
+    if (sp->reserved != 0) return fail(KG_ERR_ARG, "kg_seed_params.reserved must be 0");
+    uint64_t per = 1;
+    for (int k = 0; k < w && per <= (1ull << 35); k++) per *= (uint64_t)sp->alphabet_size;
+    if (per > (1ull << 35) || per * (uint64_t)sp->n_shapes > (1ull << 35))
+        return fail(KG_ERR_ARG, "seed space over 2^35: n_shapes * alphabet_size^weight = " + kmer_text(sp->n_shapes) + " * " +
+                                    kmer_text(sp->alphabet_size) + "^" + kmer_text(w));
+    SeedPlan pl = {};
+    pl.spec.n_shapes = (uint32_t)sp->n_shapes;
+    pl.spec.alphabet = (uint32_t)sp->alphabet_size;
+    pl.span_min = kg::kSeedMaxSpan;
+    for (int k = 0; k < sp->n_shapes; k++) {
+        const uint32_t span = 32u - (uint32_t)__builtin_clz(sp->shape[k]);
+        pl.spec.shape[k] = sp->shape[k];
+        pl.spec.span_max = std::max(pl.spec.span_max, span);
+        pl.span_min = std::min(pl.span_min, span);
+    }
+    for (int c = 0; c < 20; c++) pl.spec.cls4[c >> 2] |= (uint32_t)sp->cls[c] << (8 * (c & 3));
+    pl.spec.per_shape = per;
+    pl.space = per * (uint64_t)sp->n_shapes;
+    *out = pl;
+    return KG_OK;
+}
+
+// derive_block_bases for a seed set: blocks of 64 over the max(len_p - span_min, 0) window positions of protein p
+int seed_block_bases(const int64_t *offsets, int64_t n_prot, uint32_t span_min, std::vector<uint32_t> &ibase, uint64_t *nblocks_out)
+{
+    ibase.assign((size_t)n_prot + 1, 0);
+    uint64_t nblocks = 0;
+    for (int64_t k = 0; k < n_prot; k++) {
+        const int64_t L = offsets[k + 1] - offsets[k];
+        ibase[(size_t)k] = (uint32_t)nblocks;
+        const uint64_t nwin = L > (int64_t)span_min ? (uint64_t)L - span_min : 0;
+        nblocks += (nwin + kg::kAaWinPerBlock - 1) / kg::kAaWinPerBlock;
+        if (nblocks > 0x7FFFFFFFull) return fail(KG_ERR_LIMIT, "2^31 or more window blocks of 64 windows in one call");
+    }
+    ibase[(size_t)n_prot] = (uint32_t)nblocks;
+    *nblocks_out = nblocks;
+    return KG_OK;
+}
+
+uint32_t seed_grid(uint32_t n_blocks)
+{
+    return std::max(std::min<uint32_t>((n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16), 1u);
+}
+
+// the valid (window, shape) pairs of the batch: the count pass.  Its time goes where the histogram's goes (dv.ms_hist).
+int seed_count(Deriver &dv, const SeedPlan *seed, unsigned long long *d_count, uint64_t *n_out)
+{
+    hipStream_t s = dv.t->stream;
+    HIP_TRY(hipMemsetAsync(d_count, 0, 8, s));
+    HIP_TRY(hipEventRecord(dv.ev[0], s));
+    if (dv.n_blocks) {
+        hipLaunchKernelGGL(kg::seed_windows_kernel<false>, dim3(seed_grid(dv.n_blocks)), dim3(kg::kDeriveThreads), 0, s, dv.d_seq, dv.d_blocks,
+                           dv.n_blocks, seed->spec, d_count, nullptr, 0u, nullptr, nullptr, nullptr, (uint64_t)0);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(dv.ev[1], s));
+    unsigned long long n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, d_count, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, dv.ev[0], dv.ev[1]));
+    dv.ms_hist += ms;
+    *n_out = n;
+    return KG_OK;
+}
 
 // The ordered records -> one path record each, same index, in a block of the set's own.  KG_TRACE_HITS traces the records with
 // status hit, KG_TRACE_ALL every aligned record with score >= 1; a is the query, b the target.
@@ -64,7 +159,7 @@ int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, con
 
 int search_impl(kg_table *t, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq_in,
                 const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset *set,
-                const SearchPathsAsk *ask)
+                const SearchPathsAsk *ask, const SeedPlan *seed = nullptr)
 {
     kg_search_stats &st = set->st;
     const int64_t n_q = n_prot - n_db;
@@ -74,7 +169,9 @@ int search_impl(kg_table *t, const kg_search_params *prm, const kg_align_params 
     std::vector<uint32_t> ibase;
     uint64_t nblocks = 0, windows = 0;
     int rc;
-    if ((rc = derive_block_bases(offsets, n_prot, ibase, &nblocks, &windows))) return rc;
+    if ((rc = seed ? seed_block_bases(offsets, n_prot, seed->span_min, ibase, &nblocks)
+                   : derive_block_bases(offsets, n_prot, ibase, &nblocks, &windows)))
+        return rc;
     const uint32_t b = bits_for((uint64_t)n_prot), np = (uint32_t)n_prot, db = bits_for((uint64_t)n_db), ndb = (uint32_t)n_db;
     hipStream_t s = t->stream;
 
@@ -122,10 +219,14 @@ int search_impl(kg_table *t, const kg_search_params *prm, const kg_align_params 
         HIP_TRY(hipGetLastError());
 
         // ---- the valid windows, and whether they fit: one pass ----
-        const uint64_t space = (uint64_t)KG_MAX_ENCODED;
-        std::vector<unsigned long long> bins;
-        if ((rc = dv.histogram(0, space, Deriver::shift_for(space), bins))) return rc;
-        for (auto c : bins) n += c;
+        const uint64_t space = seed ? seed->space : (uint64_t)KG_MAX_ENCODED;
+        if (seed) {
+            if ((rc = seed_count(dv, seed, dv.d_bins, &n))) return rc;
+        } else {
+            std::vector<unsigned long long> bins;
+            if ((rc = dv.histogram(0, space, Deriver::shift_for(space), bins))) return rc;
+            for (auto c : bins) n += c;
+        }
         st.valid_windows = (int64_t)n;
         {
             uint64_t cap = (uint64_t)max_windows;
@@ -148,7 +249,11 @@ int search_impl(kg_table *t, const kg_search_params *prm, const kg_align_params 
             if ((rc = sp.alloc(sc, n)) || (rc = sc.get(&d_cur, 1))) return rc;
             HIP_TRY(hipMemsetAsync(d_cur, 0, 8, s));
             HIP_TRY(hipEventRecord(ev[1], s));
-            {
+            if (seed) {
+                hipLaunchKernelGGL(kg::seed_windows_kernel<true>, dim3(seed_grid(dv.n_blocks)), dim3(kg::kDeriveThreads), 0, s, d_seq, dv.d_blocks,
+                                   dv.n_blocks, seed->spec, nullptr, rank_of, b, sp.keys(), sp.vals(), d_cur, n);
+                HIP_TRY(hipGetLastError());
+            } else {
                 const uint32_t grid = std::min<uint32_t>((dv.n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16);
                 hipLaunchKernelGGL(kg::derive_windows_kernel<true>, dim3(std::max(grid, 1u)), dim3(kg::kDeriveThreads), 0, s, d_seq, dv.d_blocks,
                                    dv.n_blocks, (uint64_t)0, space, 0u, nullptr, rank_of, b, sp.keys(), sp.vals(), d_cur, n);
@@ -346,7 +451,7 @@ int search_impl(kg_table *t, const kg_search_params *prm, const kg_align_params 
 
 int search_entry(int device, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq,
                  const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset **out,
-                 const SearchPathsAsk *ask = nullptr)
+                 const SearchPathsAsk *ask = nullptr, const kg_seed_params *seeds = nullptr, bool seeded = false)
 {
     if (!out) return fail(KG_ERR_ARG, "null argument");
     *out = nullptr;
@@ -355,6 +460,9 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     if (prm->max_cand < 1 || prm->max_cand > kg::kSearchMaxCand) return fail(KG_ERR_ARG, "max_cand must be in 1..64");
     if (prm->max_db_per_kmer < 1) return fail(KG_ERR_ARG, "max_db_per_kmer must be >= 1");
     if (prm->reserved != 0) return fail(KG_ERR_ARG, "kg_search_params.reserved must be 0");
+    SeedPlan plan;
+    if (seeded)
+        if (int rc = seed_plan(seeds, &plan)) return rc;
     if (!al) return fail(KG_ERR_ARG, "null kg_align_params");
     if (int rc = align_check_params(al)) return rc;
     if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
@@ -379,7 +487,7 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
     set->device = device;
     int rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
-    if (!rc) rc = search_impl(cs.t, prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, set, ask);
+    if (!rc) rc = search_impl(cs.t, prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, set, ask, seeded ? &plan : nullptr);
     cs.t->cache.release_all();                          // scratch goes back to the driver
     if (rc) { std::string keep = g_err; kg_hitset_free(set); g_err = keep; return rc; }
     if (getenv("KG_DEBUG"))
@@ -423,6 +531,53 @@ int kg_proteins_search_paths_device(int device, const kg_search_params *p, const
 {
     const SearchPathsAsk ask{trace, max_trace_cells};
     return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, &ask);
+}
+
+int kg_seed_params_builtin(int which, kg_seed_params *out)
+{
+    if (!out) return fail(KG_ERR_ARG, "null argument");
+    if (which != KG_SEEDS_EXACT && which != KG_SEEDS_REDUCED) return fail(KG_ERR_ARG, "which must be KG_SEEDS_EXACT or KG_SEEDS_REDUCED");
+    kg_seed_params p = {};
+    if (which == KG_SEEDS_EXACT) {
+        p.n_shapes = 1;
+        p.alphabet_size = 20;
+        for (int c = 0; c < 20; c++) p.cls[c] = (uint8_t)c;
+        p.shape[0] = 0xFFu;
+    } else {
+        // reduced11: AST, C, DEKNQR, F, G, H, ILV, M, P, W, Y over the code order ACDEFGHIKLMNPQRSTVWY
+        static const uint8_t cls[20] = {0, 1, 2, 2, 3, 4, 5, 6, 2, 6, 7, 2, 8, 2, 2, 0, 0, 6, 9, 10};
+        p.n_shapes = 2;
+        p.alphabet_size = 11;
+        memcpy(p.cls, cls, 20);
+        p.shape[0] = 0xD6Fu;            // 111101101011, position 0 leftmost = bit 0
+        p.shape[1] = 0x659Bu;           // 110110011010011
+    }
+    *out = p;
+    return KG_OK;
+}
+
+namespace {
+int seeded_entry(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align, const uint8_t *h_seq,
+                 const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, int trace,
+                 int64_t max_trace_cells, kg_hitset **out)
+{
+    const SearchPathsAsk ask{trace, max_trace_cells};
+    return search_entry(device, p, align, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, trace ? &ask : nullptr, seeds, true);
+}
+}  // namespace
+
+int kg_proteins_search_seeded(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                              const uint8_t *seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                              int64_t max_pairs, int trace, int64_t max_trace_cells, kg_hitset **out)
+{
+    return seeded_entry(device, p, seeds, align, seq, nullptr, offsets, n_prot, n_db, max_windows, max_pairs, trace, max_trace_cells, out);
+}
+
+int kg_proteins_search_seeded_device(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                                     const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                                     int64_t max_pairs, int trace, int64_t max_trace_cells, kg_hitset **out)
+{
+    return seeded_entry(device, p, seeds, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, trace, max_trace_cells, out);
 }
 
 int64_t kg_hitset_count(const kg_hitset *s) { return s ? s->count : 0; }

@@ -18,6 +18,7 @@
 #include "kg_align.hpp"
 #include "kg_trace.hpp"
 #include "kg_search.hpp"
+#include "kg_seed.hpp"
 #include "kg_assign.hpp"
 #include "kg_regions.hpp"
 #include "kg_orfs.hpp"

@@ -829,9 +829,20 @@ def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20,
         lib.kg_familyset_free(h)
 
 
+def _seed_params(seeds):
+    """None for the exact call, else the kg_seed_params of a seed set as seeds.resolve reads it."""
+    from . import seeds as SD
+    got = SD.resolve(seeds)
+    if got is None:
+        return None
+    cls, n_cls, masks = got[:3]
+    return N.KgSeedParams(len(masks), n_cls, (C.c_uint8 * 20)(*cls), (C.c_uint32 * 4)(*masks), 0)
+
+
 def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256,
                     align: Optional[dict] = None, max_windows: int = 0, max_pairs: int = 0, device: int = 0,
-                    device_ptr: Optional[int] = None, paths: Optional[str] = None, max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS):
+                    device_ptr: Optional[int] = None, paths: Optional[str] = None, max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS,
+                    seeds=None):
     """Proteins [n_db, n_prot) searched against proteins [0, n_db), on the GPU (include/kmerguts_hip.h kg_proteins_search states
     the rule): the targets that share at least min_shared distinct unmasked 8-mers with a query, the max_cand with the most
     aligned, a hit where 100 * score >= min_ratio_pct * ref.  seq / offsets / device_ptr as for cluster_proteins; align: None
@@ -840,16 +851,29 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
     -> (numpy records of _native.SEARCH_HIT_DTYPE in (query, rank) order, hit_start int64[n_q + 1], the call's statistics).
     paths: None, "hits" (the records with status hit are traced) or "all" (every aligned record with score >= 1):
     kg_proteins_search_paths; -> (records, hit_start, _native.ALIGN_PATH_DTYPE records of the same indices, statistics), the
-    statistics with traced, untraced, trace_cells and ms_trace as well."""
+    statistics with traced, untraced, trace_cells and ms_trace as well.
+    seeds: None (the exact 8-mers: the calls above), "reduced" (the built-in reduced-alphabet spaced seeds) or a
+    dict(alphabet="identity" | "reduced11" | "AST,C,DEKNQR,...", shapes=["1111...", ...]) as seeds.py reads it:
+    kg_proteins_search_seeded, the same results with "seed id" read for "8-mer"."""
     if paths is not None and paths not in N.TRACE_MODES:
         raise ValueError("paths must be None, 'hits' or 'all'")
+    seed_set = _seed_params(seeds)
     off = _offsets(offsets, "int64[n_prot + 1]")
     n = off.size - 1
     p = N.KgSearchParams(int(min_shared), int(max_cand), int(max_db_per_kmer), 0)
     ap, _keep = _align_params(**(align or {}))
     h = C.c_void_p()
     lib = N.load()
-    if paths is not None:
+    if seed_set is not None:
+        tail = (int(max_windows), int(max_pairs), N.TRACE_MODES[paths] if paths is not None else 0, int(max_trace_cells), C.byref(h))
+        if device_ptr is not None:
+            N.check(lib.kg_proteins_search_seeded_device(device, C.byref(p), C.byref(seed_set), C.byref(ap), C.c_void_p(device_ptr),
+                                                         off.ctypes.data, n, int(n_db), *tail))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_proteins_search_seeded(device, C.byref(p), C.byref(seed_set), C.byref(ap), _ptr(arr), off.ctypes.data, n,
+                                                  int(n_db), *tail))
+    elif paths is not None:
         tail = (int(max_windows), int(max_pairs), N.TRACE_MODES[paths], int(max_trace_cells), C.byref(h))
         if device_ptr is not None:
             N.check(lib.kg_proteins_search_paths_device(device, C.byref(p), C.byref(ap), C.c_void_p(device_ptr), off.ctypes.data, n,

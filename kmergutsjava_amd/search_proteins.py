@@ -7,6 +7,7 @@ how much.  The step that names what `annotate` leaves at `none`.
                                                [--max-cells N] [--all] [-A db_annotations.tsv [--transfer out.tsv]]
                                                [--truth query_annotations.tsv]
                                                [--paths [--trace hits|all] [--max-trace-cells N]]
+                                               [--seeds exact|reduced] [--alphabet identity|reduced11|GROUPS] [--shape MASK ...]
 
 The proteins of all -d files are the database, those of all -q files the queries, each in the order given (FASTA as
 make_signatures reads it).  An id that occurs twice within the database or within the queries is an error; the same id in both
@@ -35,6 +36,14 @@ field of -A: `query start<TAB>target start<TAB>columns<TAB>identical<TAB>identit
 query cover %<TAB>target cover %`: the starts 1-based, identity % = 100 * identical // columns, the covers 100 * (end - start
 + 1) // length of the protein; each field is `-` for a record without a traced path.  The summary line gains `, traced: N,
 untraced: M, trace ms: X`.  Without --paths every byte is as before.
+--seeds reduced finds the relatives that share no exact 8-mers with the query (kg_proteins_search_seeded): the prefilter then
+counts shared seeds of a reduced alphabet (reduced11: AST, C, DEKNQR, F, G, H, ILV, M, P, W, Y; a substitution inside a class
+keeps a seed) under two spaced shapes of nine care positions (111101101011 and 110110011010011; a substitution on a `0`
+keeps a seed), and everything behind it, --min-shared and --max-db-per-kmer included, reads "seed" for "8-mer".  --alphabet
+(identity, reduced11, or comma-separated groups of residues such as AST,C,DEKNQR,...) and --shape (a string of 1 and 0, at most
+32 long, first and last 1; up to four, all with the same number of 1) each replace that part of the chosen seed set.  The
+built-in set is this project's choice and is not tuned.  The summary line then gains `, seeds: <alphabet> x <shape,shape>`;
+nothing else in any output changes, and with --seeds exact and neither override every byte is as before.
 The summary line goes to stderr.
 """
 from __future__ import annotations
@@ -130,10 +139,13 @@ def compare_truth(qids, got, truth) -> dict:
 def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: int = 8, max_hits: int = 1, max_db_per_kmer: int = 256,
                     align: Optional[dict] = None, write_all: bool = False, annotations: Optional[str] = None,
                     transfer: Optional[str] = None, truth: Optional[str] = None, device: int = 0, search=None,
-                    paths: Optional[str] = None, max_trace_cells: Optional[int] = None) -> str:
+                    paths: Optional[str] = None, max_trace_cells: Optional[int] = None, seeds=None) -> str:
     """Write the files; returns the summary line.  `search` replaces hotpath.search_proteins (tests).  align: None, or the
     alignment parameters of hotpath.search_proteins (ref "query" is its "member").  paths: None, "hits" or "all" (--paths with
-    its --trace); max_trace_cells: None for the library's default."""
+    its --trace); max_trace_cells: None for the library's default.  seeds: None (the exact 8-mers), "reduced" or a
+    dict(alphabet=..., shapes=[...]) as hotpath.search_proteins takes it."""
+    from . import seeds as SD
+    seed_words = SD.describe(seeds) if SD.resolve(seeds) is not None else None
     if paths not in (None, "hits", "all"):
         raise ValueError("--trace must be hits or all")
     if max_hits < 1:
@@ -158,11 +170,13 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
         from . import hotpath
         search = hotpath.search_proteins
     recs = None
+    more = {} if seed_words is None else {"seeds": seeds}
     if paths is None:
         hits, hit_start, st = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
-                                     max_db_per_kmer=max_db_per_kmer, align=align, device=device)
+                                     max_db_per_kmer=max_db_per_kmer, align=align, device=device, **more)
     else:
-        more = {} if max_trace_cells is None else {"max_trace_cells": max_trace_cells}
+        if max_trace_cells is not None:
+            more["max_trace_cells"] = max_trace_cells
         hits, hit_start, recs, st = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
                                            max_db_per_kmer=max_db_per_kmer, align=align, device=device, paths=paths, **more)
     with open(out, "wb") as f:
@@ -181,6 +195,8 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
         line += ", labelled: %d, agree: %d, disagree: %d, missed: %d" % (t["labelled"], t["agree"], t["disagree"], t["missed"])
     if paths is not None:
         line += ", traced: %d, untraced: %d, trace ms: %.3f" % (st["traced"], st["untraced"], st.get("ms_trace", 0.0))
+    if seed_words is not None:
+        line += ", seeds: " + seed_words
     return line
 
 
@@ -209,15 +225,31 @@ def main(argv=None) -> int:
                     help="with --paths: trace the hit records only (default), or every aligned record with a score (default with --all)")
     ap.add_argument("--max-trace-cells", type=int, default=None,
                     help="with --paths: a record whose prefix box has more cells is not traced (default 2^24, this project's choice)")
+    ap.add_argument("--seeds", choices=("exact", "reduced"), default="exact",
+                    help="what the prefilter counts: exact 8-mers (default), or reduced-alphabet spaced seeds for remote relatives")
+    ap.add_argument("--alphabet", default=None, metavar="identity|reduced11|GROUPS",
+                    help="replaces the seed set's alphabet: comma-separated groups of residues, e.g. AST,C,DEKNQR,F,G,H,ILV,M,P,W,Y")
+    ap.add_argument("--shape", action="append", default=None, metavar="MASK",
+                    help="replaces the seed set's shapes: 1 = care, 0 = don't care, first and last 1; up to four, of equal weight")
     a = ap.parse_args(argv)
+    if a.shape is not None and len(a.shape) > 4:
+        ap.error("at most 4 --shape")
     if not a.paths and (a.trace is not None or a.max_trace_cells is not None):
         ap.error("--trace and --max-trace-cells need --paths")
     paths = (a.trace or ("all" if a.all else "hits")) if a.paths else None
     from . import _native as N
     align = dict(min_ratio_pct=a.min_ratio, ref=a.align_ref, gap_open=a.gap_open, gap_extend=a.gap_extend, max_cells=a.max_cells)
+    from . import seeds as SD
+    seeds = None
+    if a.seeds != "exact" or a.alphabet is not None or a.shape is not None:
+        seeds = dict(SD.BUILTIN[a.seeds])
+        if a.alphabet is not None:
+            seeds["alphabet"] = a.alphabet
+        if a.shape is not None:
+            seeds["shapes"] = a.shape
     try:
         line = search_proteins(a.d, a.q, a.o, a.min_shared, a.max_cand, a.max_hits, a.max_db_per_kmer, align, a.all, a.A, a.transfer,
-                               a.truth, paths=paths, max_trace_cells=a.max_trace_cells)
+                               a.truth, paths=paths, max_trace_cells=a.max_trace_cells, seeds=seeds)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1
