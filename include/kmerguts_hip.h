@@ -592,6 +592,56 @@ int kg_proteins_align_paths_device(int device, const kg_align_params *p, const u
                                    int64_t n_prot, const int32_t *pairs, int64_t n_pairs, int64_t max_trace_cells,
                                    kg_alignment *out, kg_alignment_path *paths);
 
+/* ---- the alignments themselves: ops of the traced path (kernels: kg_trace.hpp, kg_ops.hpp) ----
+ *
+ * Opt-in beside the path records; this rule is the project's own.  Integers only.  The path is the column sequence of the walk
+ * above; a is the query and b the target.  Read from the alignment's start to its end, every column has a kind:
+ *     (a_i, b_j), identical by the record's definition (codes equal and below 20)   '='
+ *     any other (a_i, b_j)                                                          'X'
+ *     (a_i, -), consumes a only                                                     'I'
+ *     (-, b_j), consumes b only                                                     'D'
+ * In mode KG_TRACE_OPS '=' and 'X' are both 'M'; mode KG_TRACE_OPS_EQX keeps them apart.
+ *   An op is a maximal run of columns of one kind, stored as one uint32_t: len << 4 | code, with BAM's codes (KG_OP_M 0, KG_OP_I 1,
+ *   KG_OP_D 2, KG_OP_EQ 7, KG_OP_X 8).  len fits: a traced box has fewer than 2^25 columns under any cap the pass accepts.
+ *   A record's ops are in alignment order, start to end: ops[op_start[r] .. op_start[r + 1]).  A record without a traced path
+ *   (status 1 or 2) has none: op_start[r + 1] == op_start[r].  For every traced record:
+ *     KG_TRACE_OPS:      n_ops <= 2 * gap_opens + 1; the I lengths sum to gap_cols_b, the D lengths to gap_cols_a, the M lengths to
+ *                        the residue columns.
+ *     KG_TRACE_OPS_EQX:  the '=' lengths sum to identical; merging neighbouring '=' and 'X' ops gives exactly the KG_TRACE_OPS ops.
+ * Nothing depends on launch geometry, pair order, scheduling or what scratch held before.
+ *   How: the walk stages two bits per column (at most end_a + end_b + 1 columns a pair, 16 to a word) and counts the kind changes;
+ *   the counts are summed in record order and a second kernel writes the ops.  The staging of one call is scratch and at most 2 GiB
+ *   (the columns of a typical path take about 44 bytes; the region is sized by the box, 152 bytes for a 300 x 300 one): over it
+ *   KG_ERR_LIMIT names the byte count, as 2^32 or more ops in one call are KG_ERR_LIMIT.  The test hook KG_TEST_OPS_STAGE_BYTES=n
+ *   (with KG_ENABLE_TEST_HOOKS=1, as the hooks above) lowers the limit to n bytes.
+ *   The ops block is of the exact size and belongs to the result.
+ *
+ * kg_proteins_align_ops / _device: kg_proteins_align_paths' arguments, ops_mode (KG_TRACE_OPS or KG_TRACE_OPS_EQX, else KG_ERR_ARG
+ * "ops_mode must be ...") and *ops: a set of op_start[n_pairs + 1] and the ops, in pair order.  out and paths are byte for byte
+ * kg_proteins_align_paths'.  KG_TEST_FAIL_ALLOC applies; on a failure *ops is NULL and all device memory is back.
+ * kg_opset_op_starts_copy copies count + 1 values, op_start[first .. first + count]; kg_opset_ops_copy ops [first_op, first_op +
+ * count); dst is host or device memory.  kg_opset_ms_ops: the device time of the ops' own part (prefix sum and fill), ms.
+ * In the search calls below the two modes are OR-ed into `trace`. */
+#define KG_TRACE_OPS 4
+#define KG_TRACE_OPS_EQX 8
+#define KG_OP_M 0
+#define KG_OP_I 1
+#define KG_OP_D 2
+#define KG_OP_EQ 7
+#define KG_OP_X 8
+typedef struct kg_opset kg_opset;
+int kg_proteins_align_ops(int device, const kg_align_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
+                          const int32_t *pairs, int64_t n_pairs, int64_t max_trace_cells, int ops_mode, kg_alignment *out,
+                          kg_alignment_path *paths, kg_opset **ops);
+int kg_proteins_align_ops_device(int device, const kg_align_params *p, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
+                                 const int32_t *pairs, int64_t n_pairs, int64_t max_trace_cells, int ops_mode, kg_alignment *out,
+                                 kg_alignment_path *paths, kg_opset **ops);
+int64_t kg_opset_ops_count(const kg_opset *s);
+int kg_opset_op_starts_copy(const kg_opset *s, int64_t first, int64_t count, int64_t *dst);
+int kg_opset_ops_copy(const kg_opset *s, int64_t first_op, int64_t count, uint32_t *dst);
+int kg_opset_ms_ops(const kg_opset *s, float *out);
+void kg_opset_free(kg_opset *s);
+
 /* ---- searching proteins against a database: 8-mer join, top candidates, alignment (kernels: kg_search.hpp) ----
  *
  * The reference only reads signatures; this rule is the project's own.  It answers which known protein a protein is like, and
@@ -692,6 +742,16 @@ int kg_proteins_search_paths_device(int device, const kg_search_params *p, const
                                     int trace, int64_t max_trace_cells, kg_hitset **out);
 int kg_hitset_paths_copy(const kg_hitset *s, int64_t first, int64_t count, kg_alignment_path *dst);
 int kg_hitset_trace_stats(const kg_hitset *s, kg_trace_stats *out);
+/* The ops of the traced records (the rule: "the alignments themselves" above): trace = mode | KG_TRACE_OPS or mode | KG_TRACE_OPS_EQX
+ * in kg_proteins_search_paths* and kg_proteins_search_seeded*.  trace & 3 is the mode and fails as before; both op bits, or a
+ * bit above 15, are KG_ERR_ARG "trace takes at most one of KG_TRACE_OPS and KG_TRACE_OPS_EQX ...".  Everything else the call
+ * returns is byte for byte the call's without the bit; kg_trace_stats.ms_trace then covers the ops' work (it replaces the plain
+ * trace), kg_hitset_ms_ops is the ops' own part.  One op_start entry per hit record, plus one.  The getters return KG_ERR_ARG
+ * for a set made without ops. */
+int64_t kg_hitset_ops_count(const kg_hitset *s);
+int kg_hitset_op_starts_copy(const kg_hitset *s, int64_t first, int64_t count, int64_t *dst);   /* count + 1 values */
+int kg_hitset_ops_copy(const kg_hitset *s, int64_t first_op, int64_t count, uint32_t *dst);
+int kg_hitset_ms_ops(const kg_hitset *s, float *out);
 
 /* ---- the search with reduced-alphabet spaced seeds (kernel: kg_seed.hpp) ----
  *

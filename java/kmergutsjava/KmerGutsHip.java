@@ -5,6 +5,7 @@ import com.sun.jna.Native;
 import com.sun.jna.Pointer;
 import com.sun.jna.Structure;
 import com.sun.jna.ptr.IntByReference;
+import com.sun.jna.ptr.FloatByReference;
 import com.sun.jna.ptr.PointerByReference;
 
 /**
@@ -521,6 +522,18 @@ public interface KmerGutsHip extends Library {
                                 long maxTraceCells, Pointer out, Pointer paths);
     int kg_proteins_align_paths_device(int device, KgAlignParams params, Pointer dSeq, long[] offsets, long nProt, int[] pairs, long nPairs,
                                        long maxTraceCells, Pointer out, Pointer paths);
+    /** kg_proteins_align_paths with the alignments themselves: opsMode = KG_TRACE_OPS (4: M, I, D) or KG_TRACE_OPS_EQX (8: = and X for
+     *  M); ops receives a kg_opset: opStart[nPairs + 1] and the ops, each len << 4 | code with BAM's codes (M 0, I 1, D 2, = 7, X 8),
+     *  in alignment order; free it with kg_opset_free */
+    int kg_proteins_align_ops(int device, KgAlignParams params, byte[] seq, long[] offsets, long nProt, int[] pairs, long nPairs,
+                              long maxTraceCells, int opsMode, Pointer out, Pointer paths, PointerByReference ops);
+    int kg_proteins_align_ops_device(int device, KgAlignParams params, Pointer dSeq, long[] offsets, long nProt, int[] pairs, long nPairs,
+                                     long maxTraceCells, int opsMode, Pointer out, Pointer paths, PointerByReference ops);
+    long kg_opset_ops_count(Pointer set);
+    int kg_opset_op_starts_copy(Pointer set, long first, long count, Pointer dst);   // long[count + 1]: opStart[first .. first + count]
+    int kg_opset_ops_copy(Pointer set, long firstOp, long count, Pointer dst);       // int[count]
+    int kg_opset_ms_ops(Pointer set, FloatByReference out);                          // the ops' own device time (prefix sum and fill), ms
+    void kg_opset_free(Pointer set);
     /** kg_proteins_cluster with every link that passed the 8-mer tests verified by alignment; align = null: kg_proteins_cluster */
     int kg_proteins_cluster_aligned(int device, KgClusterParams params, KgAlignParams align, byte[] seq, long[] offsets, long nProt,
                                     long maxWindows, PointerByReference out);
@@ -548,6 +561,12 @@ public interface KmerGutsHip extends Library {
                                         long nDb, long maxWindows, long maxPairs, int trace, long maxTraceCells, PointerByReference out);
     int kg_hitset_paths_copy(Pointer set, long first, long count, Pointer dst);   // kg_alignment_path[count], 32 B each, same indices
     int kg_hitset_trace_stats(Pointer set, KgTraceStats out);
+    /** the ops of the traced records, for a set made with trace | KG_TRACE_OPS (4) or trace | KG_TRACE_OPS_EQX (8) in
+     *  kg_proteins_search_paths* or kg_proteins_search_seeded*; one opStart entry per hit record, plus one */
+    long kg_hitset_ops_count(Pointer set);
+    int kg_hitset_op_starts_copy(Pointer set, long first, long count, Pointer dst);  // long[count + 1]
+    int kg_hitset_ops_copy(Pointer set, long firstOp, long count, Pointer dst);      // int[count], len << 4 | code
+    int kg_hitset_ms_ops(Pointer set, FloatByReference out);
     /** a built-in seed set into out: which = KG_SEEDS_EXACT (0: the identity map and the shape 0xFF) or KG_SEEDS_REDUCED (1) */
     int kg_seed_params_builtin(int which, KgSeedParams out);
     /** kg_proteins_search with reduced-alphabet spaced seeds in the 8-mers' place; trace = 0 (no paths; maxTraceCells is ignored),

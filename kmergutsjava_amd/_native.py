@@ -40,6 +40,9 @@ EXPORTS = (
     "kg_proteins_align", "kg_proteins_align_device", "kg_proteins_cluster_aligned", "kg_proteins_cluster_aligned_device",
     "kg_familyset_edges_count", "kg_familyset_edges_copy", "kg_familyset_align_stats",
     "kg_proteins_align_paths", "kg_proteins_align_paths_device",
+    "kg_proteins_align_ops", "kg_proteins_align_ops_device", "kg_opset_ops_count", "kg_opset_op_starts_copy", "kg_opset_ops_copy",
+    "kg_opset_ms_ops", "kg_opset_free",
+    "kg_hitset_ops_count", "kg_hitset_op_starts_copy", "kg_hitset_ops_copy", "kg_hitset_ms_ops",
     "kg_proteins_search", "kg_proteins_search_device", "kg_hitset_count", "kg_hitset_copy", "kg_hitset_starts_copy",
     "kg_hitset_stats", "kg_hitset_free",
     "kg_proteins_search_paths", "kg_proteins_search_paths_device", "kg_hitset_paths_copy", "kg_hitset_trace_stats",
@@ -153,6 +156,10 @@ PATH_TRACED, PATH_NONE, PATH_UNTRACED = 0, 1, 2         # kg_alignment_path.stat
 TRACE_DEFAULT_MAX_CELLS = 1 << 24
 TRACE_HITS, TRACE_ALL = 1, 2
 TRACE_MODES = {"hits": TRACE_HITS, "all": TRACE_ALL}
+TRACE_OPS, TRACE_OPS_EQX = 4, 8                         # OR-ed into a search's trace; kg_proteins_align_ops' ops_mode
+OPS_MODES = {"m": TRACE_OPS, "eqx": TRACE_OPS_EQX}
+OP_M, OP_I, OP_D, OP_EQ, OP_X = 0, 1, 2, 7, 8           # an op is len << 4 | code
+OP_LETTERS = {OP_M: "M", OP_I: "I", OP_D: "D", OP_EQ: "=", OP_X: "X"}
 # struct kg_search_hit (kg_proteins_search*): one aligned or skipped candidate of a query
 SEARCH_HIT_DTYPE = np.dtype([("query", "<i4"), ("target", "<i4"), ("shared", "<i4"), ("score", "<i4"), ("self_query", "<i4"),
                              ("self_target", "<i4"), ("end_query", "<i4"), ("end_target", "<i4"), ("status", "<i4"), ("rank", "<i4")])
@@ -551,6 +558,11 @@ def load() -> C.CDLL:
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgAlignParams), vp, vp, C.c_int64, vp, C.c_int64, vp]
     for name in ("kg_proteins_align_paths", "kg_proteins_align_paths_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgAlignParams), vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp]
+    for name in ("kg_proteins_align_ops", "kg_proteins_align_ops_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgAlignParams), vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int, vp, vp,
+                                       C.POINTER(vp)]
+    for name in ("kg_opset_ms_ops", "kg_hitset_ms_ops"):
+        getattr(lib, name).argtypes = [vp, C.POINTER(C.c_float)]
     for name in ("kg_proteins_cluster_aligned", "kg_proteins_cluster_aligned_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
                                        C.POINTER(vp)]
@@ -568,14 +580,14 @@ def load() -> C.CDLL:
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgSearchParams), C.POINTER(KgSeedParams), C.POINTER(KgAlignParams), vp, vp,
                                        C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(vp)]
     # the sets' accessors, by signature: (set) -> count, (set) -> device address, (set, first, count, dst), (set, dst), (set)
-    for name in ("kg_sigset_count", "kg_familyset_count", "kg_familyset_edges_count", "kg_hitset_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
+    for name in ("kg_sigset_count", "kg_familyset_count", "kg_familyset_edges_count", "kg_hitset_count", "kg_hitset_ops_count", "kg_opset_ops_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
                  "kg_selectset_count", "kg_voteset_count", "kg_voteset_bins", "kg_compset_rows", "kg_compset_models"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = C.c_int64
     for name in ("kg_sigset_device", "kg_regionset_device", "kg_orfset_device", "kg_selectset_device"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = vp
-    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_hitset_copy", "kg_hitset_paths_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
+    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_hitset_copy", "kg_hitset_paths_copy", "kg_hitset_op_starts_copy", "kg_hitset_ops_copy", "kg_opset_op_starts_copy", "kg_opset_ops_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
                  "kg_orfset_junctions_copy", "kg_orfset_coding_scores", "kg_orfset_start_shifts", "kg_selectset_copy",
                  "kg_voteset_copy_votes", "kg_voteset_copy_classes", "kg_voteset_copy_bins", "kg_compset_copy_classes",
                  "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores"):
@@ -583,7 +595,7 @@ def load() -> C.CDLL:
     for name in ("kg_regionset_seq_start", "kg_orfset_prot_start", "kg_orfset_junctions_start", "kg_voteset_seq_start",
                  "kg_compset_background", "kg_hitset_starts_copy"):
         getattr(lib, name).argtypes = [vp, vp]
-    for name in ("kg_sigset_free", "kg_familyset_free", "kg_hitset_free", "kg_regionset_free", "kg_orfset_free", "kg_selectset_free",
+    for name in ("kg_sigset_free", "kg_familyset_free", "kg_hitset_free", "kg_opset_free", "kg_regionset_free", "kg_orfset_free", "kg_selectset_free",
                  "kg_voteset_free", "kg_compset_free"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = None

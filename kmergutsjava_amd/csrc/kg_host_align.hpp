@@ -6,6 +6,15 @@
 static_assert(sizeof(kg_alignment) == 24 && sizeof(kg::AlignRec) == 24 && sizeof(kg_family_edge) == 32 && sizeof(kg_align_params) == 40 &&
               sizeof(kg_align_stats) == 40, "record layouts of include/kmerguts_hip.h");
 
+// kg_proteins_align_ops: op_start[n + 1] (int64), then the ops, in one block of the set's context
+struct kg_opset : SetBase {
+    uint8_t *d_block = nullptr;
+    int64_t n = 0, count = 0;           // records, ops
+    float ms_ops = 0;
+    const int64_t *starts() const { return (const int64_t *)d_block; }
+    const uint32_t *ops() const { return (const uint32_t *)(d_block + ((size_t)n + 1) * 8); }
+};
+
 namespace {
 
 constexpr uint32_t kAlignGrid = 256 * 18;               // workgroups of one wave: what 256 CUs hold at 9 KB of LDS each
@@ -95,14 +104,16 @@ int align_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_
 }
 
 // kg_proteins_align_paths: the paths asked for beside the records (kg_host_trace.hpp runs the pass behind align_run)
-struct AlignPathsAsk { int64_t max_trace_cells; kg_alignment_path *paths; };
+// kg_proteins_align_ops: the ops as well, in `set` (ops_mode: KG_TRACE_OPS or KG_TRACE_OPS_EQX; 0: none)
+struct AlignPathsAsk { int64_t max_trace_cells; kg_alignment_path *paths; int ops_mode = 0; kg_opset *set = nullptr; };
+int align_ops_empty(kg_table *t, kg_opset *set);
 int align_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_t *d_seq, const int64_t *d_off, const int32_t *pairs,
                        int64_t n_pairs, const kg_alignment *aln, const AlignPathsAsk *ask);
 
 int align_impl(kg_table *t, const kg_align_params *prm, const uint8_t *h_seq, const uint8_t *d_seq_in, const int64_t *offsets, int64_t n_prot,
                const int32_t *pairs, int64_t n_pairs, kg_alignment *out, const AlignPathsAsk *ask)
 {
-    if (n_pairs == 0) return KG_OK;
+    if (n_pairs == 0) return ask && ask->set ? align_ops_empty(t, ask->set) : KG_OK;
     hipStream_t s = t->stream;
     Scratch sc(t);
     int rc;
@@ -139,7 +150,7 @@ int align_check_offsets(const int64_t *offsets, int64_t n_prot)
 }
 
 int align_entry(int device, const kg_align_params *prm, const uint8_t *h_seq, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
-                const int32_t *pairs, int64_t n_pairs, kg_alignment *out, const AlignPathsAsk *ask = nullptr)
+                const int32_t *pairs, int64_t n_pairs, kg_alignment *out, const AlignPathsAsk *ask_in = nullptr, kg_opset **ops_out = nullptr)
 {
     if (!prm) return fail(KG_ERR_ARG, "null kg_align_params");
     int rc;
@@ -150,8 +161,8 @@ int align_entry(int device, const kg_align_params *prm, const uint8_t *h_seq, co
     if (n_pairs >= (1ll << 31)) return fail(KG_ERR_LIMIT, "2^31 or more pairs in one call");
     if ((rc = align_check_offsets(offsets, n_prot))) return rc;
     if (n_pairs && (!pairs || !out)) return fail(KG_ERR_ARG, "null argument");
-    if (ask && ask->max_trace_cells < 1) return fail(KG_ERR_ARG, "max_trace_cells must be >= 1");
-    if (ask && n_pairs && !ask->paths) return fail(KG_ERR_ARG, "null paths");
+    if (ask_in && ask_in->max_trace_cells < 1) return fail(KG_ERR_ARG, "max_trace_cells must be >= 1");
+    if (ask_in && n_pairs && !ask_in->paths) return fail(KG_ERR_ARG, "null paths");
     for (int64_t k = 0; k < 2 * n_pairs; k++)
         if (pairs[k] < 0 || pairs[k] >= n_prot)
             return fail(KG_ERR_ARG, "pair " + kmer_text(k / 2) + ": protein index " + kmer_text(pairs[k]) + " is outside [0, n_prot)");
@@ -159,8 +170,18 @@ int align_entry(int device, const kg_align_params *prm, const uint8_t *h_seq, co
     if (seq_bytes && n_pairs && !h_seq && !d_seq) return fail(KG_ERR_ARG, "null sequence");
     CallScope cs(device);
     if (cs.rc) return cs.rc;
+    std::unique_ptr<kg_opset> set;                      // kg_proteins_align_ops only: the set keeps the context and its block
+    AlignPathsAsk with_set;
+    const AlignPathsAsk *ask = ask_in;
+    if (ops_out) {
+        if ((rc = make_set(cs, set))) return rc;
+        with_set = *ask_in;
+        with_set.set = set.get();
+        ask = &with_set;
+    }
     rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
     if (!rc) rc = align_impl(cs.t, prm, h_seq, d_seq, offsets, n_prot, pairs, n_pairs, out, ask);
+    if (!rc && ops_out) return hand_out(cs, set, ops_out);      // (the scratch, back in the cache, goes to the driver there)
     cs.t->cache.release_all();                          // scratch goes back to the driver
     return rc;
 }

@@ -15,6 +15,12 @@ struct kg_hitset {
     kg_alignment_path *d_paths = nullptr;   // kg_proteins_search_paths only: one record per hit record (hipMalloc, owned)
     bool has_paths = false;
     kg_trace_stats tst = {};
+    uint8_t *d_ops = nullptr;           // KG_TRACE_OPS / KG_TRACE_OPS_EQX only: op_start[count + 1] (int64), then the ops (hipMalloc, owned)
+    int64_t ops_count = 0;
+    bool has_ops = false;
+    float ms_ops = 0;
+    const int64_t *op_starts() const { return (const int64_t *)d_ops; }
+    const uint32_t *ops() const { return (const uint32_t *)(d_ops + ((size_t)count + 1) * 8); }
     const int64_t *starts() const { return (const int64_t *)d_block; }
     const kg_search_hit *hits() const { return (const kg_search_hit *)(d_block + ((size_t)n_q + 1) * 8); }
 };
@@ -27,7 +33,8 @@ namespace {
 constexpr uint64_t kSearchBytesPerPair = 112;                         // device bytes one join pair needs, at most
 constexpr uint64_t kSearchPairsMax = (1ull << 32) - (1ull << 22);     // the 32-bit scans and indices of the join
 
-// kg_proteins_search_paths: which records are traced, and the cap of a box
+// kg_proteins_search_paths: which records are traced (trace & 3), whether their ops are written (KG_TRACE_OPS, KG_TRACE_OPS_EQX), and
+// the cap of a box
 struct SearchPathsAsk { int trace; int64_t max_trace_cells; };
 
 // kg_proteins_search_seeded: a checked kg_seed_params.  space = n_shapes * alphabet^weight <= 2^35
@@ -133,6 +140,12 @@ int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, con
     int rc;
     if ((rc = dalloc_detached(t, &guard.p, std::max<uint64_t>(NK, 1) * sizeof(kg_alignment_path)))) return rc;
     TraceTotals tot;
+    const int which = ask->trace & 3;
+    OpsAsk ops{ask->trace & (KG_TRACE_OPS | KG_TRACE_OPS_EQX)};
+    if (NK == 0 && ops.mode) {                          // no records: op_start[0] = 0 and no ops
+        if ((rc = sc.get(&ops.d_block, 16))) return rc;
+        HIP_TRY(hipMemset(ops.d_block, 0, 16));
+    }
     if (NK > 0) {
         std::vector<kg_search_hit> hits(NK);
         HIP_TRY(hipMemcpy(hits.data(), d_hits, NK * sizeof(kg_search_hit), hipMemcpyDeviceToHost));
@@ -142,10 +155,11 @@ int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, con
             const kg_search_hit &h = hits[k];
             pairs[2 * k] = (int32_t)(n_db + h.query);
             pairs[2 * k + 1] = h.target;
-            ends[k] = TraceEnd{h.score, h.end_query, h.end_target, ask->trace == KG_TRACE_ALL ? h.status != 2 && h.score >= 1 : h.status == 0};
+            ends[k] = TraceEnd{h.score, h.end_query, h.end_target, which == KG_TRACE_ALL ? h.status != 2 && h.score >= 1 : h.status == 0};
         }
         kg::TracePath *d_paths = nullptr;
-        if ((rc = trace_run(t, sc, al, d_seq, d_off, pairs.data(), ends, NK, ask->max_trace_cells, &d_paths, &tot))) return rc;
+        if ((rc = trace_run(t, sc, al, d_seq, d_off, pairs.data(), ends, NK, ask->max_trace_cells, &d_paths, &tot, ops.mode ? &ops : nullptr)))
+            return rc;
         HIP_TRY(hipMemcpy(guard.p, d_paths, NK * sizeof(kg_alignment_path), hipMemcpyDeviceToDevice));
     }
     set->tst.traced = tot.traced;
@@ -154,6 +168,14 @@ int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, con
     set->tst.ms_trace = tot.ms;
     set->d_paths = (kg_alignment_path *)guard.p; guard.p = nullptr;
     set->has_paths = true;
+    if (ops.mode) {                                     // the ops block leaves the cache for good, as the path block has
+        sc.release(ops.d_block);
+        t->cache.detach(ops.d_block);
+        set->d_ops = ops.d_block;
+        set->ops_count = ops.count;
+        set->ms_ops = ops.ms;
+        set->has_ops = true;
+    }
     return KG_OK;
 }
 
@@ -467,7 +489,10 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     if (int rc = align_check_params(al)) return rc;
     if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
     if (max_pairs < 0) return fail(KG_ERR_ARG, "max_pairs must be >= 0");
-    if (ask && ask->trace != KG_TRACE_HITS && ask->trace != KG_TRACE_ALL) return fail(KG_ERR_ARG, "trace must be KG_TRACE_HITS or KG_TRACE_ALL");
+    if (ask && (ask->trace & 3) != KG_TRACE_HITS && (ask->trace & 3) != KG_TRACE_ALL)
+        return fail(KG_ERR_ARG, "trace must be KG_TRACE_HITS or KG_TRACE_ALL");
+    if (ask && ((ask->trace & ~15) || (ask->trace & (KG_TRACE_OPS | KG_TRACE_OPS_EQX)) == (KG_TRACE_OPS | KG_TRACE_OPS_EQX)))
+        return fail(KG_ERR_ARG, "trace takes at most one of KG_TRACE_OPS and KG_TRACE_OPS_EQX beside its mode, and no bit above 15");
     if (ask && ask->max_trace_cells < 1) return fail(KG_ERR_ARG, "max_trace_cells must be >= 1");
     if (n_prot < 0) return fail(KG_ERR_ARG, "n_prot < 0");
     if (n_prot >= (1ll << 29)) return fail(KG_ERR_LIMIT, "2^29 or more proteins in one call");
@@ -594,6 +619,28 @@ int kg_hitset_trace_stats(const kg_hitset *s, kg_trace_stats *out)
     return copy_stats(s, s ? &s->tst : nullptr, out);
 }
 
+int64_t kg_hitset_ops_count(const kg_hitset *s) { return s ? s->ops_count : 0; }
+
+int kg_hitset_op_starts_copy(const kg_hitset *s, int64_t first, int64_t count, int64_t *dst)
+{
+    if (s && !s->has_ops) return fail(KG_ERR_ARG, "kg_hitset_op_starts_copy: the set was made without ops");
+    return ops_starts_copy(s, s ? s->device : 0, s ? s->op_starts() : nullptr, s ? s->count : 0, first, count, dst, "kg_hitset_op_starts_copy");
+}
+
+int kg_hitset_ops_copy(const kg_hitset *s, int64_t first_op, int64_t count, uint32_t *dst)
+{
+    if (s && !s->has_ops) return fail(KG_ERR_ARG, "kg_hitset_ops_copy: the set was made without ops");
+    return copy_records(s, s ? s->device : 0, s ? s->ops() : nullptr, 1, s ? s->ops_count : 0, first_op, count, dst, "kg_hitset_ops_copy");
+}
+
+int kg_hitset_ms_ops(const kg_hitset *s, float *out)
+{
+    if (!s || !out) return fail(KG_ERR_ARG, "null argument");
+    if (!s->has_ops) return fail(KG_ERR_ARG, "kg_hitset_ms_ops: the set was made without ops");
+    *out = s->ms_ops;
+    return KG_OK;
+}
+
 int kg_hitset_copy(const kg_hitset *s, int64_t first, int64_t count, kg_search_hit *dst)
 {
     return copy_records(s, s ? s->device : 0, s ? s->hits() : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_hitset_copy");
@@ -616,6 +663,10 @@ void kg_hitset_free(kg_hitset *s)
     if (s->d_paths) {
         (void)hipSetDevice(s->device);
         (void)hipFree(s->d_paths);
+    }
+    if (s->d_ops) {
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->d_ops);
     }
     delete s;
 }

@@ -5,7 +5,10 @@
 //
 //   trace_pairs_kernel<kLong>     one wave per pair, pairs handed out through a counter in descending order of their box cells
 //                                 (the host orders them), exactly as align_pairs_kernel hands its pairs out
+//   trace_columns_kernel<kLong>   the same pass with the walk's columns recorded: two bits a column into the job's staging words,
+//                                 and the record's op count (kg_ops.hpp turns the staged columns into ops)
 //
+// Both are instantiations of trace_pairs_body; the recording is compiled out of trace_pairs_kernel.
 // Forward.  The wave is kg_align.hpp's: lane l owns row i0 + l of a 64-row stripe and stands in column j = t - l at step t, H-up,
 // F-up and the residue come down the lanes by DPP, the stripe's last row is carried in LDS (kLong = false: box columns up to
 // kAlignLdsCols) or in a slab of device memory (kLong = true).  Each cell adds four bits: the source of H (0 none: H = 0,
@@ -21,6 +24,13 @@
 // lane 63 of the stripe above.  The loop is bounded by (end_a + 1) + (end_b + 1) moves; a walk that does not end within them, a gap that reaches a cell
 // with H = 0 or the boundary, a box whose end cell does not reproduce the score, and a pair that does not fit the workgroup's
 // slab set a bit of the launches' error word (the host turns it into KG_ERR_DEVICE), never a spin and never a store outside the slab.
+// Columns (kCols).  Column c of the walk (c = 0 is the alignment's last column) is two bits, 0 '=', 1 'X', 2 (a_i, -), 3 (-, b_j),
+// at bits 2 * (c % 16) of staging word c / 16.  Lane (c / 16) % 64 gathers that word in a vector register, so the walk's scalar
+// state grows by the column count alone, and the wave stores 64 words (1024 columns) with one coalesced instruction; the words
+// of the last, partial block follow behind the loop.  A walk has at most end_a + end_b + 1 columns and the job's staging region
+// has ceil of that over 16 words (the host lays the regions out in hand-out order): a column past it is a walk error, not a store.
+// The op count is the number of kind changes, '=' and 'X' being one kind unless eqx is set; it is kept as the walk's other
+// counts are and is 0 for a record without a path.
 #pragma once
 
 #include "kg_align.hpp"
@@ -35,6 +45,17 @@ constexpr unsigned kTraceErrSlab = 4u;                  //       a traced pair d
 
 // One pair to hand out: the proteins, what the alignment pass found (score 0: no path is asked for) and the record's place
 struct TraceJob { int a, b, score, end_a, end_b, slot; };
+// kg_ops.hpp / trace_columns_kernel: where record `slot`'s staging words begin, and its end cell (in record order)
+struct OpsRec { uint64_t stage_at; int end_a, end_b; };
+// what the recording needs beyond the plain pass, behind one pointer: trace_pairs_kernel<true> leaves two scalar registers free,
+// so the kernel reads these where it uses them (at a block's store and at a record's end), not at its entry.
+// Record `slot`'s staging words are stage[recs[slot].stage_at ..), its op count -> n_ops[slot]; eqx: '=' and 'X' are two kinds.
+struct TraceOpsArgs { const OpsRec *recs; uint32_t *stage; uint32_t *n_ops; int eqx; };
+constexpr int kTraceColsPerWord = 16;                   // columns of the walk in one staging word
+__host__ __device__ constexpr uint64_t trace_stage_words(uint64_t na, uint64_t mb)      // of a traced box: na + mb - 1 columns at most
+{
+    return (na + mb - 1 + kTraceColsPerWord - 1) / kTraceColsPerWord;
+}
 constexpr int kTraceWords = 3;                          // the launches' words: the two hand-out counters, then the error bits
 struct TracePath { int start_a, start_b, identical, positive, gap_opens, gap_cols_a, gap_cols_b, status; };   // kg_alignment_path
 
@@ -47,13 +68,13 @@ __host__ __device__ constexpr uint64_t trace_stripe_words(uint64_t mb)
 // One workgroup = one wave.  jobs[k]: the k-th pair to hand out, record -> out[jobs[k].slot]; words: kTraceWords words, this
 // instantiation's counter first or second.  dirs: workgroup w's direction words are dirs[w * dir_words ..); carry (kLong only):
 // its stripe carry is carry[w * carry_cols ..).
-template <bool kLong>
-__global__ __launch_bounds__(kWave) void trace_pairs_kernel(const uint8_t *__restrict__ seq, const int64_t *__restrict__ off,
-                                                            const TraceJob *__restrict__ jobs, uint32_t n_jobs,
-                                                            unsigned int *__restrict__ words, const int8_t *__restrict__ matrix,
-                                                            int gap_open, int gap_extend, int64_t max_trace_cells,
-                                                            uint32_t *__restrict__ dirs, uint64_t dir_words, int2 *__restrict__ carry,
-                                                            uint64_t carry_cols, TracePath *__restrict__ out)
+// oa (kCols only): where the columns and the op counts go.
+template <bool kLong, bool kCols>
+__device__ __forceinline__ void trace_pairs_body(const uint8_t *__restrict__ seq, const int64_t *__restrict__ off,
+                                                 const TraceJob *__restrict__ jobs, uint32_t n_jobs, unsigned int *__restrict__ words,
+                                                 const int8_t *__restrict__ matrix, int gap_open, int gap_extend, int64_t max_trace_cells,
+                                                 uint32_t *__restrict__ dirs, uint64_t dir_words, int2 *__restrict__ carry, uint64_t carry_cols,
+                                                 TracePath *__restrict__ out, const TraceOpsArgs *oa)
 {
     __shared__ int8_t table[21 * kAlignRowStride];
     __shared__ int2 lds_carry[kLong ? 1 : kAlignLdsCols];
@@ -142,12 +163,13 @@ __global__ __launch_bounds__(kWave) void trace_pairs_kernel(const uint8_t *__res
         // summed at the end.  The start is where the walk stopped: the cell itself behind a diagonal step to the boundary,
         // one down the diagonal when the step reached a cell with H = 0.
         int identical = 0, positive = 0, gap_opens = 0, gap_cols_a = 0, gap_cols_b = 0;
+        [[maybe_unused]] int n_op = 0, n_op_eqx = 0;     // kind changes with '=' and 'X' as one kind, and apart
         int gi = na - 1, j = mb - 1;
         bool at_zero = false;
         if (go) {
             if (__builtin_amdgcn_readlane(end_h, (na - 1) & (kWave - 1)) != score) bad |= kTraceErrScore;
             int state = 0;                              // 0 H, 1 E, 2 F
-            int kind = 3;                               // the column emitted last: 0 a residue pair, 1 (-, b_j), 2 (a_i, -), 3 none yet
+            int kind = 3;                               // the column emitted last: 0 a residue pair (kCols: 4 when not identical), 1 (-, b_j), 2 (a_i, -), 3 none yet
             int ld_s = -1, ld_tb = -1, ld_bc = -1;      // what the lanes hold: stripe, word block, chunk of b
             uint32_t w = 0, w_below = 0;                // the lane's word of block ld_tb, and of the block below it
             int a_codes = 20, b_codes = 20;
@@ -155,6 +177,28 @@ __global__ __launch_bounds__(kWave) void trace_pairs_kernel(const uint8_t *__res
             // At most (end_a + 1) + (end_b + 1) moves: every emitted column is one and lowers the row, the column or both.  An
             // iteration that emits nothing changes the state from H to E or F, and the next one emits: the loop cannot spin.
             int moves = na + mb;
+            // The recording's state beside the walk's is two vector registers: the staging word the lane gathers and the second
+            // count.  The column's number is the moves made; the kind before is `kind`, which here tells a residue pair that is
+            // not identical (4) from one that is (0); the staging region's offset is read again at each of the rare stores.
+            [[maybe_unused]] uint32_t cw = 0;
+            // one emitted column (kCols), in front of its moves--: count a kind change, gather the two bits, store a full block.
+            // code: the staged two bits; next: what `kind` becomes
+            auto record = [&](int code, int next, int mine) {
+                if constexpr (kCols) {
+                    n_op += mine & (int)((next & 3) != (kind & 3));
+                    n_op_eqx += mine & (int)(next != kind);
+                    const int c = na + mb - moves;      // (a box has na + mb - 1 columns at most: the last move never emits)
+                    if (moves >= 2) {
+                        cw |= lane == ((c / kTraceColsPerWord) & (kWave - 1)) ? (uint32_t)code << (2 * (c & (kTraceColsPerWord - 1))) : 0u;
+                        if ((c & (kTraceColsPerWord * kWave - 1)) == kTraceColsPerWord * kWave - 1) {
+                            oa->stage[oa->recs[job.slot].stage_at + (size_t)(c / (kTraceColsPerWord * kWave)) * kWave + lane] = cw;
+                            cw = 0;
+                        }
+                    } else {
+                        bad |= kTraceErrWalk;
+                    }
+                }
+            };
             for (; moves > 0 && !done;) {
                 const int s = gi / kWave, r = gi & (kWave - 1), t = j + r, tb = t / kTraceCellsPerWord;
                 const uint32_t *const src_w = my_dirs + (uint64_t)s * stripe_words + lane;
@@ -180,14 +224,16 @@ __global__ __launch_bounds__(kWave) void trace_pairs_kernel(const uint8_t *__res
                 if (state == 0) {
                     const uint32_t src = bits & 3u;
                     if (src == 0) {                     // H = 0: the path began in the cell before, which a diagonal step left
-                        if (kind != 0) bad |= kTraceErrWalk;
+                        if ((kind & 3) != 0) bad |= kTraceErrWalk;
                         at_zero = true;
                         done = true;
                     } else if (src == 1) {
                         const int ca = __builtin_amdgcn_readlane(a_codes, r), cb = __builtin_amdgcn_readlane(b_codes, j & (kWave - 1));
                         identical += mine & (int)(ca == cb && ca < 20);
                         positive += mine & (int)(table[ca * kAlignRowStride + cb] > 0);
-                        kind = 0;
+                        const int same = (int)(ca == cb && ca < 20);
+                        record(1 - same, 4 - 4 * same, mine);
+                        kind = kCols ? 4 - 4 * same : 0;
                         moves--;
                         if (gi == 0 || j == 0) done = true;
                         else { gi--; j--; }
@@ -197,6 +243,7 @@ __global__ __launch_bounds__(kWave) void trace_pairs_kernel(const uint8_t *__res
                 } else if (state == 1) {
                     gap_cols_a += mine;
                     gap_opens += mine & (int)(kind != 1);
+                    record(3, 1, mine);
                     kind = 1;
                     moves--;
                     if (bits & 4u) state = 0;
@@ -205,6 +252,7 @@ __global__ __launch_bounds__(kWave) void trace_pairs_kernel(const uint8_t *__res
                 } else {
                     gap_cols_b += mine;
                     gap_opens += mine & (int)(kind != 2);
+                    record(2, 2, mine);
                     kind = 2;
                     moves--;
                     if (bits & 8u) state = 0;
@@ -215,6 +263,13 @@ __global__ __launch_bounds__(kWave) void trace_pairs_kernel(const uint8_t *__res
             if (!done) bad |= kTraceErrWalk;
             identical = align_wave_sum(identical); positive = align_wave_sum(positive); gap_opens = align_wave_sum(gap_opens);
             gap_cols_a = align_wave_sum(gap_cols_a); gap_cols_b = align_wave_sum(gap_cols_b);
+            if constexpr (kCols) {
+                n_op = align_wave_sum(oa->eqx ? n_op_eqx : n_op);
+                // the last block's words: word sw of the record holds columns 16 sw .., and exists while 16 sw < n_cols < na + mb
+                const int n_cols = na + mb - moves;
+                const int sw = n_cols / (kTraceColsPerWord * kWave) * kWave + lane;
+                if (sw * kTraceColsPerWord < n_cols && moves >= 1) oa->stage[oa->recs[job.slot].stage_at + sw] = cw;
+            }
         }
         const int start_a = gi + (at_zero ? 1 : 0), start_b = j + (at_zero ? 1 : 0);
         const bool traced = go && bad == 0;
@@ -222,10 +277,35 @@ __global__ __launch_bounds__(kWave) void trace_pairs_kernel(const uint8_t *__res
                             traced ? gap_opens : 0, traced ? gap_cols_a : 0, traced ? gap_cols_b : 0, !want ? 1 : over ? 2 : traced ? 0 : 1};
         if (lane == 0) {
             out[job.slot] = rec;
+            if constexpr (kCols) oa->n_ops[job.slot] = traced ? (uint32_t)n_op : 0u;
             if (bad) atomicOr(words + kTraceWords - 1, bad);
         }
         __builtin_amdgcn_wave_barrier();                // the lanes meet again here, in front of the hand-out
     }
+}
+
+template <bool kLong>
+__global__ __launch_bounds__(kWave) void trace_pairs_kernel(const uint8_t *__restrict__ seq, const int64_t *__restrict__ off,
+                                                            const TraceJob *__restrict__ jobs, uint32_t n_jobs,
+                                                            unsigned int *__restrict__ words, const int8_t *__restrict__ matrix,
+                                                            int gap_open, int gap_extend, int64_t max_trace_cells,
+                                                            uint32_t *__restrict__ dirs, uint64_t dir_words, int2 *__restrict__ carry,
+                                                            uint64_t carry_cols, TracePath *__restrict__ out)
+{
+    trace_pairs_body<kLong, false>(seq, off, jobs, n_jobs, words, matrix, gap_open, gap_extend, max_trace_cells, dirs, dir_words, carry,
+                                   carry_cols, out, nullptr);
+}
+
+template <bool kLong>
+__global__ __launch_bounds__(kWave) void trace_columns_kernel(const uint8_t *__restrict__ seq, const int64_t *__restrict__ off,
+                                                              const TraceJob *__restrict__ jobs, uint32_t n_jobs,
+                                                              unsigned int *__restrict__ words, const int8_t *__restrict__ matrix,
+                                                              int gap_open, int gap_extend, int64_t max_trace_cells,
+                                                              uint32_t *__restrict__ dirs, uint64_t dir_words, int2 *__restrict__ carry,
+                                                              uint64_t carry_cols, TracePath *__restrict__ out, const TraceOpsArgs *oa)
+{
+    trace_pairs_body<kLong, true>(seq, off, jobs, n_jobs, words, matrix, gap_open, gap_extend, max_trace_cells, dirs, dir_words, carry,
+                                  carry_cols, out, oa);
 }
 
 }  // namespace kg

@@ -17,6 +17,7 @@
 #include "kg_cluster.hpp"
 #include "kg_align.hpp"
 #include "kg_trace.hpp"
+#include "kg_ops.hpp"
 #include "kg_search.hpp"
 #include "kg_seed.hpp"
 #include "kg_assign.hpp"

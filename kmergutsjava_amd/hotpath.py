@@ -745,16 +745,83 @@ def _align_params(min_ratio_pct: int = 50, ref="longer", gap_open: int = 11, gap
                            _ptr(mat), 0), mat
 
 
+def _copy_ops(count_of, starts_copy, ops_copy, h, n: int):
+    """(op_start int64[n + 1], ops uint32[op_start[-1]]) of a set made with ops."""
+    starts = np.zeros(n + 1, dtype=np.int64)
+    N.check(starts_copy(h, 0, n, starts.ctypes.data))
+    ops = np.zeros(int(count_of(h)), dtype=np.uint32)
+    N.check(ops_copy(h, 0, ops.size, _ptr(ops)))
+    return starts, ops
+
+
+def cigar(ops) -> str:
+    """The CIGAR string of one record's ops (len << 4 | code, BAM's codes): "12M3D40M", or "12=1X..." from the eqx mode; "*" for
+    none."""
+    return "".join("%d%s" % (int(x) >> 4, N.OP_LETTERS[int(x) & 15]) for x in ops) or "*"
+
+
+def alignment_text(query, target, hit, path, ops, width: int = 60, query_id: str = "query", target_id: str = "target") -> str:
+    """The alignment of one traced record as text, made on the host from its ops and the two sequences.  hit: a record with a
+    score; path: its _native.ALIGN_PATH_DTYPE record; ops in either mode: with
+    M ops the residues are compared here.  A header line ">query_id target_id score=.. identity=..% columns=..", then rows of
+    `width` columns: "Query  <first residue>  <residues / ->  <last residue>", a midline (the letter when identical, "+" when
+    S > 0 under align_scores.BLOSUM62, else a space) and "Target ..." likewise; positions are 1-based."""
+    from .align_scores import ALPHA, BLOSUM62
+
+    def code_of(x: int) -> int:
+        k = ALPHA.find(bytes([x]))
+        return k if k >= 0 else 20
+
+    q, t = bytes(query), bytes(target)
+    i, j = int(path["start_a"]), int(path["start_b"])
+    top, mid, bot = [], [], []
+    for x in ops:
+        ln, code = int(x) >> 4, int(x) & 15
+        for _ in range(ln):
+            if code == N.OP_I:
+                top.append(chr(q[i])); mid.append(" "); bot.append("-"); i += 1
+            elif code == N.OP_D:
+                top.append("-"); mid.append(" "); bot.append(chr(t[j])); j += 1
+            else:
+                ca, cb = code_of(q[i]), code_of(t[j])
+                top.append(chr(q[i])); bot.append(chr(t[j]))
+                mid.append(chr(q[i]) if ca == cb and ca < 20 else "+" if BLOSUM62[ca][cb] > 0 else " ")
+                i += 1; j += 1
+    columns = len(top)
+    lines = [">%s %s score=%d identity=%d%% columns=%d" % (query_id, target_id, int(hit["score"]),
+                                                            100 * int(path["identical"]) // max(columns, 1), columns)]
+    qi, tj = int(path["start_a"]), int(path["start_b"])     # residues consumed so far
+    pw = len(str(max(i, j, 1)))
+    for c0 in range(0, columns, width):
+        qa, ma, ta = "".join(top[c0:c0 + width]), "".join(mid[c0:c0 + width]), "".join(bot[c0:c0 + width])
+        nq, nt = len(qa) - qa.count("-"), len(ta) - ta.count("-")
+        # a row without a residue of one sequence shows the position of the residue before it
+        lines.append("Query  %*d  %s  %d" % (pw, qi + 1 if nq else qi, qa, qi + nq))
+        lines.append("       %*s  %s" % (pw, "", ma))
+        lines.append("Target %*d  %s  %d" % (pw, tj + 1 if nt else tj, ta, tj + nt))
+        lines.append("")
+        qi += nq
+        tj += nt
+    return "\n".join(lines)
+
+
 def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1, max_cells: int = N.ALIGN_DEFAULT_MAX_CELLS, matrix=None,
                    device: int = 0, device_ptr: Optional[int] = None, paths: bool = False,
-                   max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS):
+                   max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS, ops: Optional[str] = None):
     """Local alignment scores of protein pairs, on the GPU (include/kmerguts_hip.h kg_proteins_align states the rule): affine
     gaps, the built-in matrix is BLOSUM62 (align_scores.BLOSUM62); matrix: 21 x 21 in code order.  seq / offsets /
     device_ptr as for cluster_proteins; pairs: int32[n_pairs][2] of (a, b) protein indices, any order, repeats allowed.
     -> _native.ALIGNMENT_DTYPE[n_pairs] in pair order (status 1 and score -1: more than max_cells cells, not aligned).
     paths=True: the traceback pass runs behind the scores (kg_proteins_align_paths): -> (the same records,
     _native.ALIGN_PATH_DTYPE[n_pairs]: start, identical, positive and gap counts; status 2: a box of more than max_trace_cells
-    cells, not traced)."""
+    cells, not traced).
+    ops="m" | "eqx" (needs paths=True): the alignments themselves (kg_proteins_align_ops): -> (records, paths, op_start
+    int64[n_pairs + 1], ops uint32[op_start[-1]]); pair k's ops are ops[op_start[k] : op_start[k + 1]], each len << 4 | code, in
+    alignment order; "m" writes M, I and D, "eqx" writes = and X for M.  cigar() gives the string."""
+    if ops is not None and ops not in N.OPS_MODES:
+        raise ValueError("ops must be None, 'm' or 'eqx'")
+    if ops is not None and not paths:
+        raise ValueError("ops needs paths=True")
     off = _offsets(offsets, "int64[n_prot + 1]")
     n = off.size - 1
     pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
@@ -765,6 +832,20 @@ def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1,
     out = np.zeros(len(pr), dtype=N.ALIGNMENT_DTYPE)
     lib = N.load()
     pp, op = _ptr(pr), _ptr(out)
+    if ops is not None:
+        pth = np.zeros(len(pr), dtype=N.ALIGN_PATH_DTYPE)
+        h = C.c_void_p()
+        if device_ptr is not None:
+            N.check(lib.kg_proteins_align_ops_device(device, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, pp, len(pr),
+                                                     int(max_trace_cells), N.OPS_MODES[ops], op, _ptr(pth), C.byref(h)))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_proteins_align_ops(device, C.byref(p), _ptr(arr), off.ctypes.data, n, pp, len(pr), int(max_trace_cells),
+                                              N.OPS_MODES[ops], op, _ptr(pth), C.byref(h)))
+        try:
+            return (out, pth) + _copy_ops(lib.kg_opset_ops_count, lib.kg_opset_op_starts_copy, lib.kg_opset_ops_copy, h, len(pr))
+        finally:
+            lib.kg_opset_free(h)
     if paths:
         pth = np.zeros(len(pr), dtype=N.ALIGN_PATH_DTYPE)
         if device_ptr is not None:
@@ -842,7 +923,7 @@ def _seed_params(seeds):
 def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256,
                     align: Optional[dict] = None, max_windows: int = 0, max_pairs: int = 0, device: int = 0,
                     device_ptr: Optional[int] = None, paths: Optional[str] = None, max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS,
-                    seeds=None):
+                    seeds=None, ops: Optional[str] = None):
     """Proteins [n_db, n_prot) searched against proteins [0, n_db), on the GPU (include/kmerguts_hip.h kg_proteins_search states
     the rule): the targets that share at least min_shared distinct unmasked 8-mers with a query, the max_cand with the most
     aligned, a hit where 100 * score >= min_ratio_pct * ref.  seq / offsets / device_ptr as for cluster_proteins; align: None
@@ -854,9 +935,16 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
     statistics with traced, untraced, trace_cells and ms_trace as well.
     seeds: None (the exact 8-mers: the calls above), "reduced" (the built-in reduced-alphabet spaced seeds) or a
     dict(alphabet="identity" | "reduced11" | "AST,C,DEKNQR,...", shapes=["1111...", ...]) as seeds.py reads it:
-    kg_proteins_search_seeded, the same results with "seed id" read for "8-mer"."""
+    kg_proteins_search_seeded, the same results with "seed id" read for "8-mer".
+    ops: None, "m" or "eqx" (needs paths): the traced records' ops as in align_proteins; -> (records, hit_start, path records,
+    statistics, op_start int64[count + 1], ops), the statistics with ops and ms_ops as well."""
     if paths is not None and paths not in N.TRACE_MODES:
         raise ValueError("paths must be None, 'hits' or 'all'")
+    if ops is not None and ops not in N.OPS_MODES:
+        raise ValueError("ops must be None, 'm' or 'eqx'")
+    if ops is not None and paths is None:
+        raise ValueError("ops needs paths")
+    trace = (N.TRACE_MODES[paths] if paths is not None else 0) | (N.OPS_MODES[ops] if ops is not None else 0)
     seed_set = _seed_params(seeds)
     off = _offsets(offsets, "int64[n_prot + 1]")
     n = off.size - 1
@@ -865,7 +953,7 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
     h = C.c_void_p()
     lib = N.load()
     if seed_set is not None:
-        tail = (int(max_windows), int(max_pairs), N.TRACE_MODES[paths] if paths is not None else 0, int(max_trace_cells), C.byref(h))
+        tail = (int(max_windows), int(max_pairs), trace, int(max_trace_cells), C.byref(h))
         if device_ptr is not None:
             N.check(lib.kg_proteins_search_seeded_device(device, C.byref(p), C.byref(seed_set), C.byref(ap), C.c_void_p(device_ptr),
                                                          off.ctypes.data, n, int(n_db), *tail))
@@ -874,7 +962,7 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
             N.check(lib.kg_proteins_search_seeded(device, C.byref(p), C.byref(seed_set), C.byref(ap), _ptr(arr), off.ctypes.data, n,
                                                   int(n_db), *tail))
     elif paths is not None:
-        tail = (int(max_windows), int(max_pairs), N.TRACE_MODES[paths], int(max_trace_cells), C.byref(h))
+        tail = (int(max_windows), int(max_pairs), trace, int(max_trace_cells), C.byref(h))
         if device_ptr is not None:
             N.check(lib.kg_proteins_search_paths_device(device, C.byref(p), C.byref(ap), C.c_void_p(device_ptr), off.ctypes.data, n,
                                                         int(n_db), *tail))
@@ -898,8 +986,14 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
             N.check(lib.kg_hitset_trace_stats(h, C.byref(tst)))
             stats = dict(st.as_dict(), traced=tst.traced, untraced=tst.untraced, trace_cells=tst.cells, ms_trace=tst.ms_trace)
             count = int(lib.kg_hitset_count(h))
-            return (_copy_records(lib.kg_hitset_copy, h, count, N.SEARCH_HIT_DTYPE), starts,
-                    _copy_records(lib.kg_hitset_paths_copy, h, count, N.ALIGN_PATH_DTYPE), stats)
+            got = (_copy_records(lib.kg_hitset_copy, h, count, N.SEARCH_HIT_DTYPE), starts,
+                   _copy_records(lib.kg_hitset_paths_copy, h, count, N.ALIGN_PATH_DTYPE), stats)
+            if ops is not None:
+                ms = C.c_float()
+                N.check(lib.kg_hitset_ms_ops(h, C.byref(ms)))
+                stats.update(ops=int(lib.kg_hitset_ops_count(h)), ms_ops=ms.value)
+                got += _copy_ops(lib.kg_hitset_ops_count, lib.kg_hitset_op_starts_copy, lib.kg_hitset_ops_copy, h, count)
+            return got
         return _copy_records(lib.kg_hitset_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_HIT_DTYPE), starts, st.as_dict()
     finally:
         lib.kg_hitset_free(h)

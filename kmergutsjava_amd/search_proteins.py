@@ -6,7 +6,7 @@ how much.  The step that names what `annotate` leaves at `none`.
                                                [--min-ratio 50] [--align-ref longer|query] [--gap-open 11] [--gap-extend 1]
                                                [--max-cells N] [--all] [-A db_annotations.tsv [--transfer out.tsv]]
                                                [--truth query_annotations.tsv]
-                                               [--paths [--trace hits|all] [--max-trace-cells N]]
+                                               [--paths [--trace hits|all] [--max-trace-cells N] [--cigar [m|eqx]] [--alignments FILE]]
                                                [--seeds exact|reduced] [--alphabet identity|reduced11|GROUPS] [--shape MASK ...]
 
 The proteins of all -d files are the database, those of all -q files the queries, each in the order given (FASTA as
@@ -36,6 +36,15 @@ field of -A: `query start<TAB>target start<TAB>columns<TAB>identical<TAB>identit
 query cover %<TAB>target cover %`: the starts 1-based, identity % = 100 * identical // columns, the covers 100 * (end - start
 + 1) // length of the protein; each field is `-` for a record without a traced path.  The summary line gains `, traced: N,
 untraced: M, trace ms: X`.  Without --paths every byte is as before.
+--cigar (needs --paths) writes the alignment itself (the ops of include/kmerguts_hip.h, run-length encoded on the GPU): every -o
+line gains one field behind the ten path fields and in front of the function field of -A, the CIGAR string with the query as the
+read (`I` consumes the query only, `D` the target only), or `-` for a record without a traced path.  --cigar m (the default)
+writes M for every residue column, --cigar eqx `=` for an identical one and `X` for any other.
+--alignments FILE (needs --paths) writes one block per written record that has a path: a header line `>query_id target_id
+score=N identity=N% columns=N`, then the alignment in rows of 60 columns, `Query  <first residue>  <residues and ->  <last
+residue>`, a midline (the letter when identical, `+` when the BLOSUM62 score is positive, else a space) and `Target ...`
+likewise, positions 1-based.  The text is made on the host from the ops and the sequences; the device is asked for `=`/`X` ops
+unless --cigar m was given.  With either flag the summary line gains `, ops: N`; without them every byte is as before.
 --seeds reduced finds the relatives that share no exact 8-mers with the query (kg_proteins_search_seeded): the prefilter then
 counts shared seeds of a reduced alphabet (reduced11: AST, C, DEKNQR, F, G, H, ILV, M, P, W, Y; a substitution inside a class
 keeps a seed) under two spaced shapes of nine care positions (111101101011 and 110110011010011; a substitution on a `0`
@@ -81,10 +90,40 @@ def path_fields(h, p, len_query: int, len_target: int) -> bytes:
                                                           100 * (et - st_ + 1) // len_target)
 
 
+def cigar_field(p, op_start, ops, k: int) -> bytes:
+    """The field --cigar adds to a line: record k's CIGAR, `-` without a traced path."""
+    if int(p["status"]) != TRACED:
+        return b"\t-"
+    from .hotpath import cigar
+    return b"\t" + cigar(ops[int(op_start[k]):int(op_start[k + 1])]).encode()
+
+
+def written(hits, hit_start, q: int, max_hits: int, write_all: bool):
+    """The records of query q that -o writes, as indices into hits."""
+    for k in range(int(hit_start[q]), int(hit_start[q + 1])):
+        if write_all or (int(hits[k]["status"]) == HIT and int(hits[k]["rank"]) < max_hits):
+            yield k
+
+
+def format_alignments(qids, dids, qseqs, dseqs, hits, hit_start, paths, op_start, ops, max_hits: int = 1, write_all: bool = False,
+                      width: int = 60) -> bytes:
+    """--alignments: one block (hotpath.alignment_text) per written record that has a path."""
+    from .hotpath import alignment_text
+    out = []
+    for q, qid in enumerate(qids):
+        for k in written(hits, hit_start, q, max_hits, write_all):
+            if int(paths[k]["status"]) == TRACED:
+                d = int(hits[k]["target"])
+                out.append(alignment_text(qseqs[q], dseqs[d], hits[k], paths[k], ops[int(op_start[k]):int(op_start[k + 1])], width,
+                                          qid.decode(), dids[d].decode()).encode() + b"\n")
+    return b"".join(out)
+
+
 def format_hits(qids, dids, hits, hit_start, max_hits: int = 1, write_all: bool = False, align_ref: str = "longer", functions=None,
-                paths=None, qlens=None, dlens=None) -> bytes:
+                paths=None, qlens=None, dlens=None, cigars=None) -> bytes:
     """functions: None, or {target id: (function, otu)}: every line gains the target's function or `-`.  paths: None, or one
-    path record per hit record with the proteins' lengths in qlens / dlens: every line gains path_fields in front of it."""
+    path record per hit record with the proteins' lengths in qlens / dlens: every line gains path_fields in front of it.
+    cigars: None, or (op_start, ops) of the path records: every line gains cigar_field behind the path fields."""
     out = []
     for q, qid in enumerate(qids):
         for k in range(int(hit_start[q]), int(hit_start[q + 1])):
@@ -98,6 +137,8 @@ def format_hits(qids, dids, hits, hit_start, max_hits: int = 1, write_all: bool 
                                                                int(h["end_query"]) + 1, int(h["end_target"]) + 1, STATUS[status])
             if paths is not None:
                 line += path_fields(h, paths[k], qlens[q], dlens[int(h["target"])])
+            if cigars is not None:
+                line += cigar_field(paths[k], cigars[0], cigars[1], k)
             if functions is not None:
                 line += b"\t" + (functions[did][0] if did in functions else b"-")
             out.append(line + b"\n")
@@ -139,15 +180,22 @@ def compare_truth(qids, got, truth) -> dict:
 def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: int = 8, max_hits: int = 1, max_db_per_kmer: int = 256,
                     align: Optional[dict] = None, write_all: bool = False, annotations: Optional[str] = None,
                     transfer: Optional[str] = None, truth: Optional[str] = None, device: int = 0, search=None,
-                    paths: Optional[str] = None, max_trace_cells: Optional[int] = None, seeds=None) -> str:
+                    paths: Optional[str] = None, max_trace_cells: Optional[int] = None, seeds=None, cigar: Optional[str] = None,
+                    alignments: Optional[str] = None) -> str:
     """Write the files; returns the summary line.  `search` replaces hotpath.search_proteins (tests).  align: None, or the
     alignment parameters of hotpath.search_proteins (ref "query" is its "member").  paths: None, "hits" or "all" (--paths with
     its --trace); max_trace_cells: None for the library's default.  seeds: None (the exact 8-mers), "reduced" or a
-    dict(alphabet=..., shapes=[...]) as hotpath.search_proteins takes it."""
+    dict(alphabet=..., shapes=[...]) as hotpath.search_proteins takes it.  cigar: None, "m" or "eqx" (--cigar); alignments: None
+    or the file --alignments writes; both need paths."""
     from . import seeds as SD
     seed_words = SD.describe(seeds) if SD.resolve(seeds) is not None else None
     if paths not in (None, "hits", "all"):
         raise ValueError("--trace must be hits or all")
+    if cigar not in (None, "m", "eqx"):
+        raise ValueError("--cigar must be m or eqx")
+    if paths is None and (cigar is not None or alignments is not None):
+        raise ValueError("--cigar and --alignments need --paths")
+    ops_mode = cigar if cigar is not None else "eqx" if alignments is not None else None
     if max_hits < 1:
         raise ValueError("--max-hits must be >= 1")
     if transfer is not None and annotations is None:
@@ -169,7 +217,7 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
     if search is None:
         from . import hotpath
         search = hotpath.search_proteins
-    recs = None
+    recs = op_start = ops = None
     more = {} if seed_words is None else {"seeds": seeds}
     if paths is None:
         hits, hit_start, st = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
@@ -177,11 +225,19 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
     else:
         if max_trace_cells is not None:
             more["max_trace_cells"] = max_trace_cells
-        hits, hit_start, recs, st = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
-                                           max_db_per_kmer=max_db_per_kmer, align=align, device=device, paths=paths, **more)
+        if ops_mode is not None:
+            more["ops"] = ops_mode
+        got = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand, max_db_per_kmer=max_db_per_kmer,
+                     align=align, device=device, paths=paths, **more)
+        hits, hit_start, recs, st = got[:4]
+        if ops_mode is not None:
+            op_start, ops = got[4:]
     with open(out, "wb") as f:
         f.write(format_hits(qids, dids, hits, hit_start, max_hits, write_all, align_ref, functions, recs, [len(x) for x in qseqs],
-                            [len(x) for x in dseqs]))
+                            [len(x) for x in dseqs], (op_start, ops) if cigar is not None else None))
+    if alignments is not None:
+        with open(alignments, "wb") as f:
+            f.write(format_alignments(qids, dids, qseqs, dseqs, hits, hit_start, recs, op_start, ops, max_hits, write_all))
     got = transferred(qids, dids, hits, hit_start, functions) if functions is not None else {}
     if transfer is not None:
         with open(transfer, "wb") as f:
@@ -195,6 +251,8 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
         line += ", labelled: %d, agree: %d, disagree: %d, missed: %d" % (t["labelled"], t["agree"], t["disagree"], t["missed"])
     if paths is not None:
         line += ", traced: %d, untraced: %d, trace ms: %.3f" % (st["traced"], st["untraced"], st.get("ms_trace", 0.0))
+    if ops_mode is not None:
+        line += ", ops: %d" % len(ops)
     if seed_words is not None:
         line += ", seeds: " + seed_words
     return line
@@ -225,6 +283,9 @@ def main(argv=None) -> int:
                     help="with --paths: trace the hit records only (default), or every aligned record with a score (default with --all)")
     ap.add_argument("--max-trace-cells", type=int, default=None,
                     help="with --paths: a record whose prefix box has more cells is not traced (default 2^24, this project's choice)")
+    ap.add_argument("--cigar", nargs="?", const="m", choices=("m", "eqx"), default=None,
+                    help="with --paths: one more field on every -o line, the alignment's CIGAR (m: M, I, D, the default; eqx: = and X for M)")
+    ap.add_argument("--alignments", default=None, metavar="FILE", help="with --paths: write the alignments as text, 60 columns a row")
     ap.add_argument("--seeds", choices=("exact", "reduced"), default="exact",
                     help="what the prefilter counts: exact 8-mers (default), or reduced-alphabet spaced seeds for remote relatives")
     ap.add_argument("--alphabet", default=None, metavar="identity|reduced11|GROUPS",
@@ -236,6 +297,8 @@ def main(argv=None) -> int:
         ap.error("at most 4 --shape")
     if not a.paths and (a.trace is not None or a.max_trace_cells is not None):
         ap.error("--trace and --max-trace-cells need --paths")
+    if not a.paths and (a.cigar is not None or a.alignments is not None):
+        ap.error("--cigar and --alignments need --paths")
     paths = (a.trace or ("all" if a.all else "hits")) if a.paths else None
     from . import _native as N
     align = dict(min_ratio_pct=a.min_ratio, ref=a.align_ref, gap_open=a.gap_open, gap_extend=a.gap_extend, max_cells=a.max_cells)
@@ -249,7 +312,7 @@ def main(argv=None) -> int:
             seeds["shapes"] = a.shape
     try:
         line = search_proteins(a.d, a.q, a.o, a.min_shared, a.max_cand, a.max_hits, a.max_db_per_kmer, align, a.all, a.A, a.transfer,
-                               a.truth, paths=paths, max_trace_cells=a.max_trace_cells, seeds=seeds)
+                               a.truth, paths=paths, max_trace_cells=a.max_trace_cells, seeds=seeds, cigar=a.cigar, alignments=a.alignments)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1
