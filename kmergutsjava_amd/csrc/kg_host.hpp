@@ -15,6 +15,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -334,6 +335,16 @@ int dalloc_detached(kg_table *t, uint8_t **p, size_t bytes)
     if (rc == KG_OK) t->cache.detach(*p);
     return rc;
 }
+
+// The owner of one such block (null: none): kg_hitset and kg_familyset hold theirs in it, so a set that is deleted, after a failed
+// call as well, frees what it has.  The sets' *_free functions select the device first.
+struct Detached {
+    uint8_t *p = nullptr;
+    Detached() = default;
+    Detached(const Detached &) = delete;
+    Detached &operator=(const Detached &) = delete;
+    ~Detached() { if (p) (void)hipFree(p); }
+};
 
 int table_new(int device, kg_table **out);       // kg_host_table.hpp, beside kg_table_close
 

@@ -1,6 +1,7 @@
 // kg_host_align.hpp -- kg_proteins_align / kg_proteins_align_device: local alignment scores of protein pairs, and align_run, the
 // step kg_proteins_cluster_aligned puts between its edge test and its component rounds (kernels: kg_align.hpp).
-// Part of kmerguts_hip.hip's translation unit: a batch stage in front of kg_host_cluster.hpp, which calls align_run.
+// Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_derive.hpp (its offsets checks and its sequence
+// staging) and in front of kg_host_cluster.hpp and kg_host_search.hpp, which call align_run.
 #pragma once
 
 static_assert(sizeof(kg_alignment) == 24 && sizeof(kg::AlignRec) == 24 && sizeof(kg_family_edge) == 32 && sizeof(kg_align_params) == 40 &&
@@ -117,14 +118,8 @@ int align_impl(kg_table *t, const kg_align_params *prm, const uint8_t *h_seq, co
     hipStream_t s = t->stream;
     Scratch sc(t);
     int rc;
-    const uint8_t *d_seq = d_seq_in;
-    const uint64_t seq_bytes = (uint64_t)offsets[n_prot];
-    if (h_seq && seq_bytes) {
-        uint8_t *d = nullptr;
-        if ((rc = sc.get(&d, seq_bytes))) return rc;
-        if ((rc = upload_pinned(t, h_seq, seq_bytes, d))) return rc;
-        d_seq = d;
-    }
+    const uint8_t *d_seq = nullptr;
+    if ((rc = stage_sequence(t, sc, h_seq, d_seq_in, (uint64_t)offsets[n_prot], &d_seq))) return rc;
     int64_t *d_off = nullptr;
     if ((rc = sc.get(&d_off, (size_t)n_prot + 1))) return rc;
     HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)n_prot + 1) * 8, hipMemcpyHostToDevice, s));
@@ -134,19 +129,6 @@ int align_impl(kg_table *t, const kg_align_params *prm, const uint8_t *h_seq, co
     if ((rc = align_run(t, sc, prm, d_seq, d_off, offsets, pairs, (uint64_t)n_pairs, &d_pairs, &d_out, &tot))) return rc;
     HIP_TRY(hipMemcpy(out, d_out, (size_t)n_pairs * sizeof(kg_alignment), hipMemcpyDeviceToHost));
     return ask ? align_paths_behind(t, sc, prm, d_seq, d_off, pairs, n_pairs, out, ask) : KG_OK;
-}
-
-// the offsets checks of an alignment call: non-decreasing (KG_ERR_ARG, the first offending protein), len_p < 2^24 (KG_ERR_LIMIT)
-int align_check_offsets(const int64_t *offsets, int64_t n_prot)
-{
-    if (!offsets) return fail(KG_ERR_ARG, "null offsets");
-    if (offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
-    for (int64_t k = 0; k < n_prot; k++) {
-        const int64_t L = offsets[k + 1] - offsets[k];
-        if (L < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": offsets decrease (offsets[p+1] < offsets[p])");
-        if (L >= (int64_t)kg::kAlignMaxLen) return fail(KG_ERR_LIMIT, "protein " + kmer_text(k) + ": 2^24 or more characters");
-    }
-    return KG_OK;
 }
 
 int align_entry(int device, const kg_align_params *prm, const uint8_t *h_seq, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
@@ -159,7 +141,7 @@ int align_entry(int device, const kg_align_params *prm, const uint8_t *h_seq, co
     if (n_prot >= (1ll << 31)) return fail(KG_ERR_LIMIT, "2^31 or more proteins in one call");
     if (n_pairs < 0) return fail(KG_ERR_ARG, "n_pairs < 0");
     if (n_pairs >= (1ll << 31)) return fail(KG_ERR_LIMIT, "2^31 or more pairs in one call");
-    if ((rc = align_check_offsets(offsets, n_prot))) return rc;
+    if ((rc = check_protein_offsets(offsets, n_prot, (int64_t)kg::kAlignMaxLen, "2^24"))) return rc;
     if (n_pairs && (!pairs || !out)) return fail(KG_ERR_ARG, "null argument");
     if (ask_in && ask_in->max_trace_cells < 1) return fail(KG_ERR_ARG, "max_trace_cells must be >= 1");
     if (ask_in && n_pairs && !ask_in->paths) return fail(KG_ERR_ARG, "null paths");

@@ -1,18 +1,18 @@
 // kg_host_cluster.hpp -- kg_proteins_cluster / kg_proteins_cluster_device: proteins -> families by shared 8-mers (kernels:
 // kg_cluster.hpp; the window encode, the sort and the collapse are the derive call's, kg_derive.hpp).
 // kg_proteins_cluster_aligned / _device: the same with the alignment step of kg_host_align.hpp between the edge test and the rounds.
-// Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_derive.hpp (it uses the derive call's block
-// counts, its histogram and its bytes-per-window figure) and kg_host_align.hpp.
+// Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_derive.hpp (its front half is that file's: the block
+// counts, the staging, the histogram, the one-pass cap and the window-pairs pass) and kg_host_align.hpp.
 #pragma once
 
 struct kg_familyset {
     int device = 0;
-    uint8_t *d_fam = nullptr;           // count * 16 bytes (hipMalloc, owned)
+    Detached d_fam;                     // count * 16 bytes
     int64_t count = 0;
     kg_cluster_stats st = {};
     // a set made with alignment: one record per link that passed the 8-mer tests
     bool aligned = false;
-    uint8_t *d_edges = nullptr;         // n_edges * 32 bytes (hipMalloc, owned)
+    Detached d_edges;                   // n_edges * 32 bytes
     int64_t n_edges = 0;
     kg_align_stats ast = {};
 };
@@ -38,53 +38,36 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_param
     Scratch sc(t);
     Events<10> ev;
     if ((rc = ev.create())) return rc;
-    const uint8_t *d_seq = d_seq_in;
-    const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
-    if (h_seq && seq_bytes) {
-        uint8_t *d = nullptr;
-        if ((rc = sc.get(&d, seq_bytes))) return rc;
-        if ((rc = upload_pinned(t, h_seq, seq_bytes, d))) return rc;
-        d_seq = d;
-    }
+    const uint8_t *d_seq = nullptr;
+    if ((rc = stage_sequence(t, sc, h_seq, d_seq_in, n_prot ? (uint64_t)offsets[n_prot] : 0, &d_seq))) return rc;
     HIP_TRY(hipEventRecord(ev[0], s));
     unsigned long long *words = nullptr;
     uint64_t *d_tot = nullptr;
     if ((rc = sc.get(&words, kg::kClusterWords)) || (rc = sc.get(&d_tot, 4))) return rc;
     HIP_TRY(hipMemsetAsync(words, 0, kg::kClusterWords * 8, s));
-    // ---- the result array: with the call's scratch until the call has succeeded ----
-    uint8_t *d_out = nullptr;
-    if ((rc = dalloc_detached(t, &d_out, std::max<uint64_t>((uint64_t)n_prot * 16, 16)))) return rc;
-    struct OutGuard {                   // (detached: the cache does not give it back on a failure)
-        uint8_t *p, *edges;
-        ~OutGuard() { if (p) (void)hipFree(p); if (edges) (void)hipFree(edges); }
-    } guard{d_out, nullptr};
+    // ---- the result array: the set's from here on (detached: a set that is freed after a failure frees it, the cache does not) ----
+    if ((rc = dalloc_detached(t, &set->d_fam.p, std::max<uint64_t>((uint64_t)n_prot * 16, 16)))) return rc;
     if (n_prot == 0) {
         HIP_TRY(hipEventRecord(ev[5], s));
         HIP_TRY(hipStreamSynchronize(s));
         st.ms_total = ev.ms(0, 5);
-        set->d_fam = d_out; guard.p = nullptr;
         return KG_OK;
     }
 
     // ---- per-protein arrays, the window blocks ----
     Deriver dv{t, sc, d_seq};
     dv.ev[0] = ev[6]; dv.ev[1] = ev[7];
-    dv.n_blocks = (uint32_t)nblocks;
     int64_t *d_off = nullptr;
-    uint32_t *d_ibase = nullptr, *rank_of = nullptr, *parent = nullptr, *d_cnt = nullptr, *size = nullptr, *root = nullptr, *rflag = nullptr,
+    uint32_t *rank_of = nullptr, *parent = nullptr, *d_cnt = nullptr, *size = nullptr, *root = nullptr, *rflag = nullptr,
              *fx = nullptr;
     unsigned long long *best = nullptr;
     uint64_t *fpartial = nullptr;
-    if ((rc = sc.get(&dv.d_bins, kg::kDeriveBins)) || (rc = sc.get(&d_off, (size_t)n_prot + 1)) || (rc = sc.get(&d_ibase, (size_t)n_prot + 1)) ||
+    if ((rc = sc.get(&dv.d_bins, kg::kDeriveBins)) || (rc = dv.window_blocks(offsets, ibase, n_prot, nblocks, &d_off)) ||
         (rc = sc.get(&rank_of, (size_t)n_prot)) || (rc = sc.get(&parent, (size_t)n_prot)) || (rc = sc.get(&d_cnt, (size_t)n_prot)) ||
         (rc = sc.get(&size, (size_t)n_prot)) || (rc = sc.get(&root, (size_t)n_prot)) || (rc = sc.get(&rflag, (size_t)n_prot)) ||
         (rc = sc.get(&fx, (size_t)n_prot)) || (rc = sc.get(&best, (size_t)n_prot)) ||
         (rc = sc.get(&fpartial, (size_t)n_prot / kg::kScanChunk + 3)))
         return rc;
-    if (nblocks && (rc = sc.get(&dv.d_blocks, nblocks))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)n_prot + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_ibase, ibase.data(), ((size_t)n_prot + 1) * 4, hipMemcpyHostToDevice, s));
-    if (nblocks) hipLaunchKernelGGL(kg::build_blocks_kernel, dim3(grid_of(nblocks)), dim3(256), 0, s, d_off, d_ibase, np, (uint32_t)nblocks, dv.d_blocks);
     hipLaunchKernelGGL(kg::cluster_init_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, np, rank_of, parent, d_cnt, size, best);
     HIP_TRY(hipGetLastError());
 
@@ -95,18 +78,7 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_param
     uint64_t n = 0;
     for (auto c : bins) n += c;
     st.valid_windows = (int64_t)n;
-    {
-        uint64_t cap = (uint64_t)max_windows;
-        if (cap == 0) {
-            size_t free_b = 0, total_b = 0;
-            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-            cap = std::max<uint64_t>(1u << 20, (uint64_t)(free_b * 0.8) / kDeriveBytesPerWindow);
-        }
-        cap = std::min(cap, kDerivePassMax);
-        if (n > cap)
-            return fail(KG_ERR_LIMIT, kmer_text((int64_t)n) + " valid windows do not fit the one pass of this call, which holds " +
-                                          kmer_text((int64_t)cap) + (max_windows ? " (max_windows)" : " (sized from free device memory)"));
-    }
+    if ((rc = windows_fit_one_pass(n, max_windows))) return rc;
 
     uint64_t P = 0, K = 0, NL = 0, ND = 0;
     uint64_t *edge = nullptr;
@@ -116,41 +88,14 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_param
     HIP_TRY(hipEventRecord(ev[3], s));
     if (n > 0) {
         // ---- encode and emit (key = v << b | p), sort, collapse to the distinct pairs: the derive call's kernels ----
-        SortPairs sp;
+        WindowPairs w;
         unsigned long long *d_cur = nullptr;
-        if ((rc = sp.alloc(sc, n)) || (rc = sc.get(&d_cur, 1))) return rc;
-        HIP_TRY(hipMemsetAsync(d_cur, 0, 8, s));
-        HIP_TRY(hipEventRecord(ev[1], s));
-        {
-            const uint32_t grid = std::min<uint32_t>((dv.n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16);
-            hipLaunchKernelGGL(kg::derive_windows_kernel<true>, dim3(std::max(grid, 1u)), dim3(kg::kDeriveThreads), 0, s, d_seq, dv.d_blocks,
-                               dv.n_blocks, (uint64_t)0, space, 0u, nullptr, rank_of, b, sp.keys(), sp.vals(), d_cur, n);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(ev[2], s));
-        if ((rc = sp.sort(t, sc, n, bit_width(space - 1) + b))) return rc;
-        HIP_TRY(hipEventRecord(ev[3], s));
-        const uint64_t nb = n / kg::kScanChunk + 2;
-        uint32_t *flags = nullptr, *pidx = nullptr;
-        uint64_t *partial = nullptr;
-        if ((rc = sc.get(&flags, n)) || (rc = sc.get(&pidx, n)) || (rc = sc.get(&partial, nb + 1))) return rc;
-        hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(n)), dim3(256), 0, s, sp.keys(), n, flags);
-        HIP_TRY(hipGetLastError());
-        if ((rc = prefix_sum(t, flags, n, pidx, partial, d_tot + 0))) return rc;
-        unsigned long long host_cur = 0;
-        HIP_TRY(hipMemcpyAsync(&host_cur, d_cur, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&P, d_tot, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (host_cur != n) return fail(KG_ERR_DEVICE, "internal: the emit pass wrote a different number of windows than the histogram counted");
-        uint64_t *pk = nullptr;
-        uint32_t *pv = nullptr;
-        if ((rc = sc.get(&pk, P)) || (rc = sc.get(&pv, P))) return rc;
-        HIP_TRY(hipMemsetAsync(pv, 0, P * 4, s));
-        hipLaunchKernelGGL(kg::derive_collapse_kernel, dim3(grid_of((n + kg::kDeriveChunk - 1) / kg::kDeriveChunk)), dim3(256), 0, s, sp.keys(),
-                           sp.vals(), n, pidx, pk, pv);
-        HIP_TRY(hipGetLastError());
+        if ((rc = sc.get(&d_cur, 1)) || (rc = dv.window_pairs(sc, n, 0, space, nullptr, rank_of, b, d_cur, d_tot + 0, ev[1], ev[2], ev[3], &w)))
+            return rc;
+        P = w.P;
+        uint64_t *const pk = w.pk, *const partial = w.partial;
         // ---- d_p, the k-mer runs and their centres (flags / pidx / partial are reused: P <= n) ----
-        uint32_t *kh = flags, *kx = pidx, *lf = pv, *lx = nullptr;
+        uint32_t *kh = w.flags, *kx = w.pidx, *lf = w.pv, *lx = nullptr;
         unsigned long long *kbest = nullptr;
         if ((rc = sc.get(&lx, P))) return rc;
         hipLaunchKernelGGL(kg::cluster_pair_kernel, dim3(grid_of(P)), dim3(256), 0, s, pk, P, b, np, kh, d_cnt);
@@ -171,7 +116,7 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_param
         if (NL > 0) {
             // the window sort's buffers are free: the link keys go there (NL <= P <= n)
             SortPairs lk;
-            lk.k[0] = sp.keys(); lk.v[0] = sp.vals();
+            lk.k[0] = w.sp.keys(); lk.v[0] = w.sp.vals();
             hipLaunchKernelGGL(kg::cluster_link_emit_kernel, dim3(grid_of(P)), dim3(256), 0, s, pk, P, b, kh, kx, kbest, lf, lx, NL, lk.keys(),
                                lk.vals());
             HIP_TRY(hipGetLastError());
@@ -220,7 +165,7 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_param
             uint32_t *d_ridx = nullptr;
             if ((rc = align_run(t, sc, al, d_seq, d_off, offsets, h_pairs.data(), NP, &d_pairs, &d_aln, &atot))) return rc;
             if ((rc = sc.get(&d_shared, NP)) || (rc = sc.get(&d_ridx, NP)) || (rc = sc.get(&tally, 2)) ||
-                (rc = dalloc_detached(t, &guard.edges, NP * sizeof(kg_family_edge))))
+                (rc = dalloc_detached(t, &set->d_edges.p, NP * sizeof(kg_family_edge))))
                 return rc;
             HIP_TRY(hipMemcpyAsync(d_shared, h_shared.data(), NP * 4, hipMemcpyHostToDevice, s));
             HIP_TRY(hipMemcpyAsync(d_ridx, h_ridx.data(), NP * 4, hipMemcpyHostToDevice, s));
@@ -229,7 +174,7 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_param
             HIP_TRY(hipMemsetAsync(tally, 0, 16, s));
             hipLaunchKernelGGL(kg::align_cut_kernel, dim3(grid_of(NP)), dim3(256), 0, s, d_pairs, d_aln, d_shared, d_ridx, NP,
                                (int64_t)al->min_ratio_pct, (int)(al->ref == KG_ALIGN_REF_MEMBER), edge, best, words, tally,
-                               (int4 *)guard.edges);
+                               (int4 *)set->d_edges.p);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(s));           // (the host vectors above are the copies' sources)
         }
@@ -253,7 +198,7 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_param
     hipLaunchKernelGGL(kg::cluster_compress_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, np, parent, root, size, rflag);
     HIP_TRY(hipGetLastError());
     if ((rc = prefix_sum(t, rflag, (uint64_t)n_prot, fx, fpartial, d_tot + 0))) return rc;
-    hipLaunchKernelGGL(kg::cluster_emit_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, np, root, fx, size, best, (int4 *)d_out, words);
+    hipLaunchKernelGGL(kg::cluster_emit_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, np, root, fx, size, best, (int4 *)set->d_fam.p, words);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev[5], s));
     unsigned long long hw[kg::kClusterWords] = {}, ht[2] = {};
@@ -282,10 +227,8 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_param
         set->ast.skipped = atot.skipped;
         set->ast.cells = atot.cells;
         set->ast.ms_align = ev.ms(4, 8);
-        set->d_edges = guard.edges; guard.edges = nullptr;
         set->n_edges = (int64_t)NP;
     }
-    set->d_fam = d_out; guard.p = nullptr;
     set->count = n_prot;
     return KG_OK;
 }
@@ -303,14 +246,9 @@ int cluster_entry(int device, const kg_cluster_params *prm, const kg_align_param
     if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
     if (n_prot < 0) return fail(KG_ERR_ARG, "n_prot < 0");
     if (n_prot >= (1ll << 29)) return fail(KG_ERR_LIMIT, "2^29 or more proteins in one call");
-    if (!offsets) return fail(KG_ERR_ARG, "null offsets");
-    if (offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
-    for (int64_t k = 0; k < n_prot; k++) {
-        const int64_t L = offsets[k + 1] - offsets[k];
-        if (L < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": offsets decrease (offsets[p+1] < offsets[p])");
-        if (L >= (1ll << 31)) return fail(KG_ERR_LIMIT, "protein " + kmer_text(k) + ": 2^31 or more characters");
-        if (al && L >= (int64_t)kg::kAlignMaxLen) return fail(KG_ERR_LIMIT, "protein " + kmer_text(k) + ": 2^24 or more characters");
-    }
+    if (int rc = al ? check_protein_offsets(offsets, n_prot, (int64_t)kg::kAlignMaxLen, "2^24")      // (aligned: the smaller limit)
+                    : check_protein_offsets(offsets, n_prot, 1ll << 31, "2^31"))
+        return rc;
     const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
     if (seq_bytes && !h_seq && !d_seq) return fail(KG_ERR_ARG, "null sequence");
     CallScope cs(device);               // the call's context: closed when the call returns, the set keeps only its records
@@ -366,7 +304,7 @@ int64_t kg_familyset_edges_count(const kg_familyset *s) { return s ? s->n_edges 
 
 int kg_familyset_edges_copy(const kg_familyset *s, int64_t first, int64_t count, kg_family_edge *dst)
 {
-    return copy_records(s, s ? s->device : 0, s ? (const kg_family_edge *)s->d_edges : nullptr, 1, s ? s->n_edges : 0, first, count, dst,
+    return copy_records(s, s ? s->device : 0, s ? (const kg_family_edge *)s->d_edges.p : nullptr, 1, s ? s->n_edges : 0, first, count, dst,
                         "kg_familyset_edges_copy");
 }
 
@@ -378,7 +316,7 @@ int kg_familyset_align_stats(const kg_familyset *s, kg_align_stats *out)
 
 int kg_familyset_copy(const kg_familyset *s, int64_t first, int64_t count, kg_family *dst)
 {
-    return copy_records(s, s ? s->device : 0, s ? (const kg_family *)s->d_fam : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_familyset_copy");
+    return copy_records(s, s ? s->device : 0, s ? (const kg_family *)s->d_fam.p : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_familyset_copy");
 }
 
 int kg_familyset_stats(const kg_familyset *s, kg_cluster_stats *out) { return copy_stats(s, s ? &s->st : nullptr, out); }
@@ -386,12 +324,8 @@ int kg_familyset_stats(const kg_familyset *s, kg_cluster_stats *out) { return co
 void kg_familyset_free(kg_familyset *s)
 {
     if (!s) return;
-    if (s->d_fam || s->d_edges) {
-        (void)hipSetDevice(s->device);
-        if (s->d_fam) (void)hipFree(s->d_fam);
-        if (s->d_edges) (void)hipFree(s->d_edges);
-    }
-    delete s;
+    (void)hipSetDevice(s->device);
+    delete s;                           // (its blocks with it)
 }
 
 }  // extern "C"

@@ -1,5 +1,8 @@
 // kg_host_derive.hpp -- kg_signatures_derive / kg_signatures_derive_device: annotated proteins -> a signature set (kernels:
-// kg_derive.hpp).
+// kg_derive.hpp).  It also holds what the protein hosts behind it share (kg_host_align.hpp, kg_host_cluster.hpp, kg_host_search.hpp):
+// the offsets checks, the sequence staging, the cap of a pass, and Deriver with the window blocks, the histogram and the
+// window-pairs pass (windows -> sorted keys -> distinct (k-mer, protein) pairs), which the derive call runs once per k-mer range
+// and the cluster and search calls once.
 // Part of kmerguts_hip.hip's translation unit: one of the batch stages, included behind the kernel headers, kg_host.hpp and the
 // hosts of the table, the result and the scan.
 #pragma once
@@ -20,7 +23,81 @@ namespace {
 constexpr uint64_t kDeriveBytesPerWindow = 160;                       // device bytes one valid window of a pass needs, at most
 constexpr uint64_t kDerivePassMax = (1ull << 32) - (1ull << 22);      // the 32-bit scans and indices of one pass
 
+// The offsets checks of a protein batch, the first offender first: offsets[0] < 0, then per protein a decrease (KG_ERR_ARG) or
+// max_len or more characters (KG_ERR_LIMIT; max_text says max_len: "2^24" where the proteins are aligned, else "2^31").
+int check_protein_offsets(const int64_t *offsets, int64_t n_prot, int64_t max_len, const char *max_text)
+{
+    if (!offsets) return fail(KG_ERR_ARG, "null offsets");
+    if (offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
+    for (int64_t k = 0; k < n_prot; k++) {
+        const int64_t L = offsets[k + 1] - offsets[k];
+        if (L < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": offsets decrease (offsets[p+1] < offsets[p])");
+        if (L >= max_len) return fail(KG_ERR_LIMIT, "protein " + kmer_text(k) + ": " + max_text + " or more characters");
+    }
+    return KG_OK;
+}
+
+// the sequence on the device: a host sequence goes to the scratch through pinned pieces, a device sequence is used where it lies
+int stage_sequence(kg_table *t, Scratch &sc, const uint8_t *h_seq, const uint8_t *d_seq_in, uint64_t seq_bytes, const uint8_t **d_seq)
+{
+    *d_seq = d_seq_in;
+    if (!h_seq || !seq_bytes) return KG_OK;
+    uint8_t *d = nullptr;
+    int rc;
+    if ((rc = sc.get(&d, seq_bytes)) || (rc = upload_pinned(t, h_seq, seq_bytes, d))) return rc;
+    *d_seq = d;
+    return KG_OK;
+}
+
+// How many items a call holds at once: the caller's max_* figure or, where that is 0, what 0.8 of the free device memory holds at
+// bytes_per_item each (2^20 at least); neither goes over `ceiling`, the 32-bit scans and indices.  how: the words a message says
+// it with, max_words (" (max_windows)", " (max_pairs)") or the other.
+struct Cap { uint64_t items; const char *how; };
+
+int size_cap(int64_t max_items, const char *max_words, uint64_t bytes_per_item, uint64_t ceiling, Cap *out)
+{
+    uint64_t cap = (uint64_t)max_items;
+    if (cap == 0) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        cap = std::max<uint64_t>(1u << 20, (uint64_t)(free_b * 0.8) / bytes_per_item);
+    }
+    *out = Cap{std::min(cap, ceiling), max_items ? max_words : " (sized from free device memory)"};
+    return KG_OK;
+}
+
+// the cluster and search calls run one pass: n valid windows fit it, or the call ends here
+int windows_fit_one_pass(uint64_t n, int64_t max_windows)
+{
+    Cap cap;
+    if (int rc = size_cap(max_windows, " (max_windows)", kDeriveBytesPerWindow, kDerivePassMax, &cap)) return rc;
+    if (n > cap.items)
+        return fail(KG_ERR_LIMIT, kmer_text((int64_t)n) + " valid windows do not fit the one pass of this call, which holds " +
+                                      kmer_text((int64_t)cap.items) + cap.how);
+    return KG_OK;
+}
+
+// Workgroups of a window kernel (derive_windows_kernel, seed_windows_kernel): one wave per block of 64 windows, 16 workgroups per
+// CU at most, one at least.  The count launches (histogram, seed_count) run only where n_blocks is not 0, so the "one at least"
+// changes nothing for them: they and the emit launch have the same grid.
+uint32_t emit_grid(uint32_t n_blocks)
+{
+    return std::max(std::min<uint32_t>((n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16), 1u);
+}
+
 struct DeriveRange { uint64_t lo, hi, count; };
+
+// What the window-pairs pass gives: pair j < P has key pk[j] = v << b | rank (ascending) and pv[j], the largest value of its windows.
+// sp holds the n sorted windows; flags / pidx (n words each) and partial (the chunk sums of a prefix sum over n items) have done
+// their work and are the caller's to use again for anything of at most n items.
+struct WindowPairs {
+    uint64_t n = 0, P = 0;
+    uint64_t *pk = nullptr;
+    uint32_t *pv = nullptr;
+    SortPairs sp;
+    uint32_t *flags = nullptr, *pidx = nullptr;
+    uint64_t *partial = nullptr;
+};
 
 struct Deriver {
     kg_table *t;                        // the call's context: stream, block cache, KG_TEST_FAIL_ALLOC
@@ -40,9 +117,8 @@ struct Deriver {
         HIP_TRY(hipMemsetAsync(d_bins, 0, kg::kDeriveBins * 8, t->stream));
         HIP_TRY(hipEventRecord(ev[0], t->stream));
         if (n_blocks) {
-            const uint32_t grid = std::min<uint32_t>((n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16);
-            hipLaunchKernelGGL(kg::derive_windows_kernel<false>, dim3(grid), dim3(kg::kDeriveThreads), 0, t->stream, d_seq, d_blocks,
-                               n_blocks, lo, hi, shift, d_bins, nullptr, 0u, nullptr, nullptr, nullptr, (uint64_t)0);
+            hipLaunchKernelGGL(kg::derive_windows_kernel<false>, dim3(emit_grid(n_blocks)), dim3(kg::kDeriveThreads), 0, t->stream, d_seq,
+                               d_blocks, n_blocks, lo, hi, shift, d_bins, nullptr, 0u, nullptr, nullptr, nullptr, (uint64_t)0);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(ev[1], t->stream));
@@ -80,10 +156,75 @@ struct Deriver {
         }
         return KG_OK;
     }
+
+    // The per-protein arrays of n_prot >= 1 proteins in the call's scratch: the offsets (*d_off_out) and the block bases (ibase, of
+    // derive_block_bases or seed_block_bases) uploaded, and from them the list of the nblocks window blocks (d_blocks, n_blocks).
+    int window_blocks(const int64_t *offsets, const std::vector<uint32_t> &ibase, int64_t n_prot, uint64_t nblocks, int64_t **d_off_out)
+    {
+        int rc;
+        int64_t *d_off = nullptr;
+        uint32_t *d_ibase = nullptr;
+        if ((rc = sc.get(&d_off, (size_t)n_prot + 1)) || (rc = sc.get(&d_ibase, (size_t)n_prot + 1))) return rc;
+        if (nblocks && (rc = sc.get(&d_blocks, nblocks))) return rc;
+        n_blocks = (uint32_t)nblocks;
+        HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)n_prot + 1) * 8, hipMemcpyHostToDevice, t->stream));
+        HIP_TRY(hipMemcpyAsync(d_ibase, ibase.data(), ((size_t)n_prot + 1) * 4, hipMemcpyHostToDevice, t->stream));
+        if (nblocks) {
+            hipLaunchKernelGGL(kg::build_blocks_kernel, dim3(grid_of(nblocks)), dim3(256), 0, t->stream, d_off, d_ibase, (uint32_t)n_prot,
+                               (uint32_t)nblocks, d_blocks);
+            HIP_TRY(hipGetLastError());
+        }
+        *d_off_out = d_off;
+        return KG_OK;
+    }
+
+    // The window-pairs pass: the n >= 1 valid windows with k-mers in [lo, hi) (seed: with seed ids in [0, hi) of that spec, by
+    // seed_windows_kernel; lo = 0) are emitted as key = v << b | rank_of[p], sorted, and collapsed into the distinct pairs.  n is
+    // what the count pass (the histogram, seed_count) gave for the same range: the emit pass must write as many.  Allocates from
+    // `from` (the derive call: the scratch of the pass); d_cur, d_total: one device word each, the emit cursor and where P is
+    // summed.  Records e_emit in front of the emit launch, e_sort behind it and e_sorted behind the sort.  One host
+    // synchronisation, between the prefix sum and the collapse, where P is read.
+    int window_pairs(Scratch &from, uint64_t n, uint64_t lo, uint64_t hi, const kg::SeedSpec *seed, const uint32_t *rank_of, uint32_t b,
+                     unsigned long long *d_cur, uint64_t *d_total, hipEvent_t e_emit, hipEvent_t e_sort, hipEvent_t e_sorted, WindowPairs *out)
+    {
+        hipStream_t s = t->stream;
+        WindowPairs &w = *out;
+        int rc;
+        w.n = n;
+        if ((rc = w.sp.alloc(from, n))) return rc;
+        HIP_TRY(hipMemsetAsync(d_cur, 0, 8, s));
+        HIP_TRY(hipEventRecord(e_emit, s));
+        if (seed)
+            hipLaunchKernelGGL(kg::seed_windows_kernel<true>, dim3(emit_grid(n_blocks)), dim3(kg::kDeriveThreads), 0, s, d_seq, d_blocks,
+                               n_blocks, *seed, nullptr, rank_of, b, w.sp.keys(), w.sp.vals(), d_cur, n);
+        else
+            hipLaunchKernelGGL(kg::derive_windows_kernel<true>, dim3(emit_grid(n_blocks)), dim3(kg::kDeriveThreads), 0, s, d_seq, d_blocks,
+                               n_blocks, lo, hi, 0u, nullptr, rank_of, b, w.sp.keys(), w.sp.vals(), d_cur, n);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(e_sort, s));
+        if ((rc = w.sp.sort(t, from, n, bit_width(hi - lo - 1) + b))) return rc;
+        HIP_TRY(hipEventRecord(e_sorted, s));
+        // collapse equal keys into (k-mer, protein) pairs.  (No kernel here or in a caller touches element n of flags / pidx.)
+        if ((rc = from.get(&w.flags, n)) || (rc = from.get(&w.pidx, n)) || (rc = from.get(&w.partial, n / kg::kScanChunk + 3))) return rc;
+        hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(n)), dim3(256), 0, s, w.sp.keys(), n, w.flags);
+        HIP_TRY(hipGetLastError());
+        if ((rc = prefix_sum(t, w.flags, n, w.pidx, w.partial, d_total))) return rc;
+        unsigned long long host_cur = 0;
+        HIP_TRY(hipMemcpyAsync(&host_cur, d_cur, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&w.P, d_total, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (host_cur != n) return fail(KG_ERR_DEVICE, "internal: the emit pass wrote a different number of windows than the count pass counted");
+        if ((rc = from.get(&w.pk, w.P)) || (rc = from.get(&w.pv, w.P))) return rc;
+        HIP_TRY(hipMemsetAsync(w.pv, 0, w.P * 4, s));
+        hipLaunchKernelGGL(kg::derive_collapse_kernel, dim3(grid_of((n + kg::kDeriveChunk - 1) / kg::kDeriveChunk)), dim3(256), 0, s,
+                           w.sp.keys(), w.sp.vals(), n, w.pidx, w.pk, w.pv);
+        HIP_TRY(hipGetLastError());
+        return KG_OK;
+    }
 };
 
 // host: block counts (kg_scan's -a trip counts, KGJ:912).  ibase[p] = the first window block of 64 windows of protein p,
-// ibase[n_prot] = *nblocks; *windows = sum of max(len_p - 8, 0).  Shared with kg_host_cluster.hpp.
+// ibase[n_prot] = *nblocks; *windows = sum of max(len_p - 8, 0).  Shared with the cluster and search hosts.
 int derive_block_bases(const int64_t *offsets, int64_t n_prot, std::vector<uint32_t> &ibase, uint64_t *nblocks_out, uint64_t *windows_out)
 {
     ibase.assign((size_t)n_prot + 1, 0);
@@ -118,40 +259,23 @@ int derive_impl(kg_table *t, const kg_derive_params *prm, const uint8_t *h_seq, 
     Events<8> ev;
     if ((rc = ev.create())) return rc;
 
-    // ---- the sequence on the device ----
-    const uint8_t *d_seq = d_seq_in;
-    const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
-    if (h_seq && seq_bytes) {
-        uint8_t *d = nullptr;
-        if ((rc = sc.get(&d, seq_bytes))) return rc;
-        if ((rc = upload_pinned(t, h_seq, seq_bytes, d))) return rc;
-        d_seq = d;
-    }
+    const uint8_t *d_seq = nullptr;
+    if ((rc = stage_sequence(t, sc, h_seq, d_seq_in, n_prot ? (uint64_t)offsets[n_prot] : 0, &d_seq))) return rc;
     HIP_TRY(hipEventRecord(ev[0], t->stream));
 
     Deriver dv{t, sc, d_seq};
     dv.ev[0] = ev[6]; dv.ev[1] = ev[7];
-    dv.n_blocks = (uint32_t)nblocks;
     if ((rc = sc.get(&dv.d_bins, kg::kDeriveBins))) return rc;
     int32_t *d_fn = nullptr, *d_otu = nullptr, *fn_r = nullptr, *otu_r = nullptr;
     uint32_t *rank_of = nullptr;
     if (n_prot) {
         int64_t *d_off = nullptr;
-        uint32_t *d_ibase = nullptr;
-        if ((rc = sc.get(&d_off, (size_t)n_prot + 1)) || (rc = sc.get(&d_ibase, (size_t)n_prot + 1)) ||
-            (rc = sc.get(&d_fn, (size_t)n_prot)) || (rc = sc.get(&d_otu, (size_t)n_prot)) || (rc = sc.get(&fn_r, (size_t)n_prot)) ||
+        if ((rc = sc.get(&d_fn, (size_t)n_prot)) || (rc = sc.get(&d_otu, (size_t)n_prot)) || (rc = sc.get(&fn_r, (size_t)n_prot)) ||
             (rc = sc.get(&otu_r, (size_t)n_prot)) || (rc = sc.get(&rank_of, (size_t)n_prot)))
             return rc;
-        if (nblocks && (rc = sc.get(&dv.d_blocks, nblocks))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)n_prot + 1) * 8, hipMemcpyHostToDevice, t->stream));
-        HIP_TRY(hipMemcpyAsync(d_ibase, ibase.data(), ((size_t)n_prot + 1) * 4, hipMemcpyHostToDevice, t->stream));
         HIP_TRY(hipMemcpyAsync(d_fn, fn, (size_t)n_prot * 4, hipMemcpyHostToDevice, t->stream));
         HIP_TRY(hipMemcpyAsync(d_otu, otu, (size_t)n_prot * 4, hipMemcpyHostToDevice, t->stream));
-        if (nblocks) {
-            hipLaunchKernelGGL(kg::build_blocks_kernel, dim3(grid_of(nblocks)), dim3(256), 0, t->stream, d_off, d_ibase, (uint32_t)n_prot,
-                               (uint32_t)nblocks, dv.d_blocks);
-            HIP_TRY(hipGetLastError());
-        }
+        if ((rc = dv.window_blocks(offsets, ibase, n_prot, nblocks, &d_off))) return rc;
         // ---- rank the proteins by (fn, otu, p): a stable sort of (fn + 1, otu) keys carrying p ----
         HIP_TRY(hipEventRecord(ev[1], t->stream));
         SortPairs sp;
@@ -175,15 +299,9 @@ int derive_impl(kg_table *t, const kg_derive_params *prm, const uint8_t *h_seq, 
     }
 
     // ---- the pass plan: a histogram of the valid windows over the whole k-mer space, bins cut finer where needed ----
-    {
-        uint64_t cap = (uint64_t)prm->max_windows_per_pass;
-        if (cap == 0) {
-            size_t free_b = 0, total_b = 0;
-            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-            cap = std::max<uint64_t>(1u << 20, (uint64_t)(free_b * 0.8) / kDeriveBytesPerWindow);
-        }
-        dv.cap = std::min(cap, kDerivePassMax);
-    }
+    Cap cap;
+    if ((rc = size_cap(prm->max_windows_per_pass, "", kDeriveBytesPerWindow, kDerivePassMax, &cap))) return rc;
+    dv.cap = cap.items;
     std::vector<unsigned long long> bins;
     const uint64_t space = (uint64_t)KG_MAX_ENCODED;
     const uint32_t shift0 = Deriver::shift_for(space);
@@ -216,42 +334,13 @@ int derive_impl(kg_table *t, const kg_derive_params *prm, const uint8_t *h_seq, 
     for (const DeriveRange &ps : passes) {
         const uint64_t n = ps.count;
         Scratch pass(t);                                    // this pass's scratch, back in the cache at its end
-        SortPairs sp;
-        if ((rc = sp.alloc(pass, n))) return rc;
-        HIP_TRY(hipMemsetAsync(d_cur, 0, 8, t->stream));
-        HIP_TRY(hipEventRecord(ev[1], t->stream));
-        {
-            const uint32_t grid = std::min<uint32_t>((dv.n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16);
-            hipLaunchKernelGGL(kg::derive_windows_kernel<true>, dim3(std::max(grid, 1u)), dim3(kg::kDeriveThreads), 0, t->stream, d_seq,
-                               dv.d_blocks, dv.n_blocks, ps.lo, ps.hi, 0u, nullptr, rank_of, b, sp.keys(), sp.vals(), d_cur, n);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(ev[2], t->stream));
-        if ((rc = sp.sort(t, pass, n, bit_width(ps.hi - ps.lo - 1) + b))) return rc;
-        HIP_TRY(hipEventRecord(ev[3], t->stream));
-        // collapse equal keys into (k-mer, protein) pairs
-        const uint64_t nb = n / kg::kScanChunk + 2;
-        uint32_t *flags = nullptr, *pidx = nullptr;
-        uint64_t *partial = nullptr;
-        if ((rc = pass.get(&flags, n)) || (rc = pass.get(&pidx, n)) || (rc = pass.get(&partial, nb + 1))) return rc;
-        hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(n)), dim3(256), 0, t->stream, sp.keys(), n, flags);
-        HIP_TRY(hipGetLastError());
-        if ((rc = prefix_sum(t, flags, n, pidx, partial, d_tot + 0))) return rc;
-        unsigned long long host_cur = 0;
-        uint64_t P = 0;
-        HIP_TRY(hipMemcpyAsync(&host_cur, d_cur, 8, hipMemcpyDeviceToHost, t->stream));
-        HIP_TRY(hipMemcpyAsync(&P, d_tot, 8, hipMemcpyDeviceToHost, t->stream));
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        if (host_cur != n) return fail(KG_ERR_DEVICE, "internal: a pass emitted a different number of windows than its histogram counted");
-        uint64_t *pk = nullptr;
-        uint32_t *pv = nullptr;
-        if ((rc = pass.get(&pk, P)) || (rc = pass.get(&pv, P))) return rc;
-        HIP_TRY(hipMemsetAsync(pv, 0, P * 4, t->stream));
-        hipLaunchKernelGGL(kg::derive_collapse_kernel, dim3(grid_of((n + kg::kDeriveChunk - 1) / kg::kDeriveChunk)), dim3(256), 0, t->stream,
-                           sp.keys(), sp.vals(), n, pidx, pk, pv);
-        HIP_TRY(hipGetLastError());
+        WindowPairs w;
+        if ((rc = dv.window_pairs(pass, n, ps.lo, ps.hi, nullptr, rank_of, b, d_cur, d_tot + 0, ev[1], ev[2], ev[3], &w))) return rc;
+        const uint64_t P = w.P;
+        uint64_t *const pk = w.pk, *const partial = w.partial;
+        uint32_t *const pv = w.pv;
         // run heads and numbers at the three levels (flags / pidx / partial are reused: P <= n)
-        uint32_t *kh = flags, *fh = nullptr, *oh = nullptr, *kx = pidx, *fx = nullptr, *ox = nullptr;
+        uint32_t *kh = w.flags, *fh = nullptr, *oh = nullptr, *kx = w.pidx, *fx = nullptr, *ox = nullptr;
         if ((rc = pass.get(&fh, P)) || (rc = pass.get(&oh, P)) || (rc = pass.get(&fx, P)) || (rc = pass.get(&ox, P))) return rc;
         hipLaunchKernelGGL(kg::derive_run_flags_kernel, dim3(grid_of(P)), dim3(256), 0, t->stream, pk, P, b, fn_r, otu_r, kh, fh, oh);
         HIP_TRY(hipGetLastError());
@@ -337,6 +426,8 @@ int derive_entry(int device, const kg_derive_params *prm, const uint8_t *h_seq, 
     if (!offsets) return fail(KG_ERR_ARG, "null offsets");
     if (n_prot > 0 && (!fn || !otu)) return fail(KG_ERR_ARG, "null fn / otu array");
     if (offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
+    // (not check_protein_offsets: the null fn / otu check stands in front of the offsets, and the first offending protein is reported
+    // whether its offsets or its annotation are wrong, so the four checks share the loop)
     for (int64_t k = 0; k < n_prot; k++) {
         const int64_t L = offsets[k + 1] - offsets[k];
         if (L < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": offsets decrease (offsets[p+1] < offsets[p])");

@@ -3,26 +3,29 @@
 // kg_derive.hpp; the alignment is align_run of kg_host_align.hpp, unchanged), and kg_proteins_search_paths, which traces the
 // ordered records behind it (trace_run of kg_host_trace.hpp).  kg_proteins_search_seeded is the same call with the window kernel
 // of kg_seed.hpp in the derive kernel's place: seed ids of a reduced alphabet and spaced shapes where the exact call has 8-mers.
-// Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_cluster.hpp (it uses the derive call's block counts,
-// its histogram and its bytes-per-window figure as the cluster call does) and kg_host_align.hpp.
+// search_impl is a driver over three stages: search_pairs (the front half the cluster call has too, by the functions of
+// kg_host_derive.hpp: staging, block counts, count pass, one-pass cap, window-pairs pass), search_candidates (the join and the
+// per-query cut) and search_finish (the result block, the alignment, the order, the statistics, the paths).
+// Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_derive.hpp, kg_host_align.hpp, kg_host_trace.hpp and
+// kg_host_cluster.hpp (cluster_link_starts_kernel is launched here as well).
 #pragma once
 
 struct kg_hitset {
     int device = 0;
-    uint8_t *d_block = nullptr;         // hit_start[n_q + 1] (int64), then count * 40 bytes (hipMalloc, owned)
+    Detached d_block;                   // hit_start[n_q + 1] (int64), then count * 40 bytes
     int64_t count = 0, n_q = 0;
     kg_search_stats st = {};
-    kg_alignment_path *d_paths = nullptr;   // kg_proteins_search_paths only: one record per hit record (hipMalloc, owned)
+    Detached d_paths;                   // kg_proteins_search_paths only: one kg_alignment_path per hit record
     bool has_paths = false;
     kg_trace_stats tst = {};
-    uint8_t *d_ops = nullptr;           // KG_TRACE_OPS / KG_TRACE_OPS_EQX only: op_start[count + 1] (int64), then the ops (hipMalloc, owned)
+    Detached d_ops;                     // KG_TRACE_OPS / KG_TRACE_OPS_EQX only: op_start[count + 1] (int64), then the ops
     int64_t ops_count = 0;
     bool has_ops = false;
     float ms_ops = 0;
-    const int64_t *op_starts() const { return (const int64_t *)d_ops; }
-    const uint32_t *ops() const { return (const uint32_t *)(d_ops + ((size_t)count + 1) * 8); }
-    const int64_t *starts() const { return (const int64_t *)d_block; }
-    const kg_search_hit *hits() const { return (const kg_search_hit *)(d_block + ((size_t)n_q + 1) * 8); }
+    const int64_t *op_starts() const { return (const int64_t *)d_ops.p; }
+    const uint32_t *ops() const { return (const uint32_t *)(d_ops.p + ((size_t)count + 1) * 8); }
+    const int64_t *starts() const { return (const int64_t *)d_block.p; }
+    const kg_search_hit *hits() const { return (const kg_search_hit *)(d_block.p + ((size_t)n_q + 1) * 8); }
 };
 
 static_assert(sizeof(kg_search_hit) == 40 && sizeof(kg_search_params) == 16 && sizeof(kg_search_stats) == 136 && sizeof(kg_seed_params) == 48,
@@ -34,8 +37,8 @@ constexpr uint64_t kSearchBytesPerPair = 112;                         // device 
 constexpr uint64_t kSearchPairsMax = (1ull << 32) - (1ull << 22);     // the 32-bit scans and indices of the join
 
 // kg_proteins_search_paths: which records are traced (trace & 3), whether their ops are written (KG_TRACE_OPS, KG_TRACE_OPS_EQX), and
-// the cap of a box
-struct SearchPathsAsk { int trace; int64_t max_trace_cells; };
+// the cap of a box.  trace = 0: no paths are asked for
+struct SearchPathsAsk { int trace = 0; int64_t max_trace_cells = 0; };
 
 // kg_proteins_search_seeded: a checked kg_seed_params.  space = n_shapes * alphabet^weight <= 2^35
 struct SeedPlan { kg::SeedSpec spec; uint32_t span_min; uint64_t space; };
@@ -104,11 +107,6 @@ int seed_block_bases(const int64_t *offsets, int64_t n_prot, uint32_t span_min, 
     return KG_OK;
 }
 
-uint32_t seed_grid(uint32_t n_blocks)
-{
-    return std::max(std::min<uint32_t>((n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16), 1u);
-}
-
 // the valid (window, shape) pairs of the batch: the count pass.  Its time goes where the histogram's goes (dv.ms_hist).
 int seed_count(Deriver &dv, const SeedPlan *seed, unsigned long long *d_count, uint64_t *n_out)
 {
@@ -116,7 +114,7 @@ int seed_count(Deriver &dv, const SeedPlan *seed, unsigned long long *d_count, u
     HIP_TRY(hipMemsetAsync(d_count, 0, 8, s));
     HIP_TRY(hipEventRecord(dv.ev[0], s));
     if (dv.n_blocks) {
-        hipLaunchKernelGGL(kg::seed_windows_kernel<false>, dim3(seed_grid(dv.n_blocks)), dim3(kg::kDeriveThreads), 0, s, dv.d_seq, dv.d_blocks,
+        hipLaunchKernelGGL(kg::seed_windows_kernel<false>, dim3(emit_grid(dv.n_blocks)), dim3(kg::kDeriveThreads), 0, s, dv.d_seq, dv.d_blocks,
                            dv.n_blocks, seed->spec, d_count, nullptr, 0u, nullptr, nullptr, nullptr, (uint64_t)0);
         HIP_TRY(hipGetLastError());
     }
@@ -134,14 +132,13 @@ int seed_count(Deriver &dv, const SeedPlan *seed, unsigned long long *d_count, u
 // The ordered records -> one path record each, same index, in a block of the set's own.  KG_TRACE_HITS traces the records with
 // status hit, KG_TRACE_ALL every aligned record with score >= 1; a is the query, b the target.
 int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, const uint8_t *d_seq, const int64_t *d_off, int64_t n_db,
-                        const kg_search_hit *d_hits, uint64_t NK, const SearchPathsAsk *ask, kg_hitset *set)
+                        const kg_search_hit *d_hits, uint64_t NK, const SearchPathsAsk &ask, kg_hitset *set)
 {
-    struct Guard { uint8_t *p; ~Guard() { if (p) (void)hipFree(p); } } guard{nullptr};
     int rc;
-    if ((rc = dalloc_detached(t, &guard.p, std::max<uint64_t>(NK, 1) * sizeof(kg_alignment_path)))) return rc;
+    if ((rc = dalloc_detached(t, &set->d_paths.p, std::max<uint64_t>(NK, 1) * sizeof(kg_alignment_path)))) return rc;
     TraceTotals tot;
-    const int which = ask->trace & 3;
-    OpsAsk ops{ask->trace & (KG_TRACE_OPS | KG_TRACE_OPS_EQX)};
+    const int which = ask.trace & 3;
+    OpsAsk ops{ask.trace & (KG_TRACE_OPS | KG_TRACE_OPS_EQX)};
     if (NK == 0 && ops.mode) {                          // no records: op_start[0] = 0 and no ops
         if ((rc = sc.get(&ops.d_block, 16))) return rc;
         HIP_TRY(hipMemset(ops.d_block, 0, 16));
@@ -158,20 +155,19 @@ int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, con
             ends[k] = TraceEnd{h.score, h.end_query, h.end_target, which == KG_TRACE_ALL ? h.status != 2 && h.score >= 1 : h.status == 0};
         }
         kg::TracePath *d_paths = nullptr;
-        if ((rc = trace_run(t, sc, al, d_seq, d_off, pairs.data(), ends, NK, ask->max_trace_cells, &d_paths, &tot, ops.mode ? &ops : nullptr)))
+        if ((rc = trace_run(t, sc, al, d_seq, d_off, pairs.data(), ends, NK, ask.max_trace_cells, &d_paths, &tot, ops.mode ? &ops : nullptr)))
             return rc;
-        HIP_TRY(hipMemcpy(guard.p, d_paths, NK * sizeof(kg_alignment_path), hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(set->d_paths.p, d_paths, NK * sizeof(kg_alignment_path), hipMemcpyDeviceToDevice));
     }
     set->tst.traced = tot.traced;
     set->tst.untraced = tot.untraced;
     set->tst.cells = tot.cells;
     set->tst.ms_trace = tot.ms;
-    set->d_paths = (kg_alignment_path *)guard.p; guard.p = nullptr;
     set->has_paths = true;
     if (ops.mode) {                                     // the ops block leaves the cache for good, as the path block has
         sc.release(ops.d_block);
         t->cache.detach(ops.d_block);
-        set->d_ops = ops.d_block;
+        set->d_ops.p = ops.d_block;
         set->ops_count = ops.count;
         set->ms_ops = ops.ms;
         set->has_ops = true;
@@ -179,250 +175,229 @@ int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, con
     return KG_OK;
 }
 
-int search_impl(kg_table *t, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq_in,
-                const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset *set,
-                const SearchPathsAsk *ask, const SeedPlan *seed = nullptr)
+// a checked call.  seed: null for the exact 8-mers; ask.trace = 0: no paths
+struct SearchArgs {
+    const kg_search_params *prm;
+    const kg_align_params *al;
+    const uint8_t *h_seq, *d_seq;
+    const int64_t *offsets;
+    int64_t n_prot, n_db, max_windows, max_pairs;
+    SearchPathsAsk ask;
+    const SeedPlan *seed;
+};
+
+// what search_impl sets up for its stages: they allocate from sc, enqueue on t->stream and record the timing events ev[1 .. 5]
+// (ev[6], ev[7]: the count pass)
+struct SearchCall {
+    const SearchArgs &a;
+    kg_table *t;
+    Scratch &sc;
+    const Events<8> &ev;
+    const uint8_t *d_seq = nullptr;
+    unsigned long long *words = nullptr;        // kSearchWords counters, zeroed
+    uint64_t *d_tot = nullptr;                  // the totals of the eight prefix sums
+};
+
+// search_pairs gives: the n valid windows (seeded: valid (window, shape) pairs) and, where n > 0, their distinct pairs w.P, w.pk,
+// w.pv with the arrays of the pass that are free again; the offsets on the device (null: no proteins); the time of the count pass
+struct SearchPairs {
+    uint64_t n = 0;
+    WindowPairs w;
+    int64_t *d_off = nullptr;
+    float ms_count = 0;
+};
+
+// Stage 1: per-protein arrays and window blocks, the count pass, whether the windows fit, the window-pairs pass
+int search_pairs(SearchCall &c, SearchPairs *out)
 {
-    kg_search_stats &st = set->st;
-    const int64_t n_q = n_prot - n_db;
-    set->n_q = n_q;
-    st.targets = n_db;
-    st.queries = n_q;
+    const SearchArgs &a = c.a;
+    if (a.n_prot == 0) return KG_OK;
+    hipStream_t s = c.t->stream;
+    int rc;
     std::vector<uint32_t> ibase;
     uint64_t nblocks = 0, windows = 0;
-    int rc;
-    if ((rc = seed ? seed_block_bases(offsets, n_prot, seed->span_min, ibase, &nblocks)
-                   : derive_block_bases(offsets, n_prot, ibase, &nblocks, &windows)))
+    if ((rc = a.seed ? seed_block_bases(a.offsets, a.n_prot, a.seed->span_min, ibase, &nblocks)
+                     : derive_block_bases(a.offsets, a.n_prot, ibase, &nblocks, &windows)))
         return rc;
-    const uint32_t b = bits_for((uint64_t)n_prot), np = (uint32_t)n_prot, db = bits_for((uint64_t)n_db), ndb = (uint32_t)n_db;
-    hipStream_t s = t->stream;
+    Deriver dv{c.t, c.sc, c.d_seq};
+    dv.ev[0] = c.ev[6]; dv.ev[1] = c.ev[7];
+    uint32_t *rank_of = nullptr;
+    if ((rc = c.sc.get(&dv.d_bins, kg::kDeriveBins)) || (rc = dv.window_blocks(a.offsets, ibase, a.n_prot, nblocks, &out->d_off)) ||
+        (rc = c.sc.get(&rank_of, (size_t)a.n_prot)))
+        return rc;
+    hipLaunchKernelGGL(kg::search_init_kernel, dim3(grid_of(a.n_prot)), dim3(256), 0, s, (uint32_t)a.n_prot, rank_of);
+    HIP_TRY(hipGetLastError());
 
-    Scratch sc(t);
-    Events<8> ev;
-    if ((rc = ev.create())) return rc;
-    const uint8_t *d_seq = d_seq_in;
-    const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
-    if (h_seq && seq_bytes) {
-        uint8_t *d = nullptr;
-        if ((rc = sc.get(&d, seq_bytes))) return rc;
-        if ((rc = upload_pinned(t, h_seq, seq_bytes, d))) return rc;
-        d_seq = d;
+    // ---- the valid windows, and whether they fit: one pass ----
+    const uint64_t space = a.seed ? a.seed->space : (uint64_t)KG_MAX_ENCODED;
+    if (a.seed) {
+        if ((rc = seed_count(dv, a.seed, dv.d_bins, &out->n))) return rc;
+    } else {
+        std::vector<unsigned long long> bins;
+        if ((rc = dv.histogram(0, space, Deriver::shift_for(space), bins))) return rc;
+        for (auto cnt : bins) out->n += cnt;
     }
-    HIP_TRY(hipEventRecord(ev[0], s));
-    unsigned long long *words = nullptr;
-    uint64_t *d_tot = nullptr;
-    if ((rc = sc.get(&words, kg::kSearchWords)) || (rc = sc.get(&d_tot, 8))) return rc;
-    HIP_TRY(hipMemsetAsync(words, 0, kg::kSearchWords * 8, s));
-    struct OutGuard {                   // the result block: detached, so the cache does not give it back on a failure
-        uint8_t *p;
-        ~OutGuard() { if (p) (void)hipFree(p); }
-    } guard{nullptr};
+    out->ms_count = dv.ms_hist;
+    if ((rc = windows_fit_one_pass(out->n, a.max_windows))) return rc;
+    for (int k = 1; k <= 4; k++) HIP_TRY(hipEventRecord(c.ev[k], s));
+    if (out->n == 0) return KG_OK;
 
-    uint64_t n = 0, P = 0, K = 0, R = 0, J = 0, ND = 0, NC = 0, NK = 0;
-    Deriver dv{t, sc, d_seq};
-    int64_t *d_off = nullptr;
+    // ---- encode and emit (key = v << b | p), sort, collapse to the distinct pairs: the derive call's pass ----
+    unsigned long long *d_cur = nullptr;
+    if ((rc = c.sc.get(&d_cur, 1))) return rc;
+    return dv.window_pairs(c.sc, out->n, 0, space, a.seed ? &a.seed->spec : nullptr, rank_of, bits_for((uint64_t)a.n_prot), d_cur, c.d_tot + 0,
+                           c.ev[1], c.ev[2], c.ev[3], &out->w);
+}
+
+// search_candidates gives: the NK kept candidates, d_kept_pairs[2 NK] = (n_db + q, d) in query order and d_shared[NK] = s(q, d),
+// and the counts of the statistics.  A call that ends early (no windows, no join pair, no candidate) leaves what it did not reach at 0.
+struct SearchCands {
+    uint64_t K = 0, joined = 0, masked = 0, J = 0, NC = 0, NK = 0;
     int32_t *d_kept_pairs = nullptr, *d_shared = nullptr;
-    // the times of a call that ends early: every stage it did not reach is empty
-    for (int k = 1; k <= 4; k++) HIP_TRY(hipEventRecord(ev[k], s));
+};
 
-    if (n_prot > 0) {
-        // ---- per-protein arrays, the window blocks ----
-        dv.ev[0] = ev[6]; dv.ev[1] = ev[7];
-        dv.n_blocks = (uint32_t)nblocks;
-        uint32_t *d_ibase = nullptr, *rank_of = nullptr;
-        if ((rc = sc.get(&dv.d_bins, kg::kDeriveBins)) || (rc = sc.get(&d_off, (size_t)n_prot + 1)) || (rc = sc.get(&d_ibase, (size_t)n_prot + 1)) ||
-            (rc = sc.get(&rank_of, (size_t)n_prot)))
-            return rc;
-        if (nblocks && (rc = sc.get(&dv.d_blocks, nblocks))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_off, offsets, ((size_t)n_prot + 1) * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_ibase, ibase.data(), ((size_t)n_prot + 1) * 4, hipMemcpyHostToDevice, s));
-        if (nblocks) hipLaunchKernelGGL(kg::build_blocks_kernel, dim3(grid_of(nblocks)), dim3(256), 0, s, d_off, d_ibase, np, (uint32_t)nblocks, dv.d_blocks);
-        hipLaunchKernelGGL(kg::search_init_kernel, dim3(grid_of(n_prot)), dim3(256), 0, s, np, rank_of);
-        HIP_TRY(hipGetLastError());
+// Stage 2: the k-mer runs and their weights, whether the join fits, the join and its sort, the (q, d) runs, the candidates, the cut
+// per query
+int search_candidates(SearchCall &c, const SearchPairs &in, SearchCands *out)
+{
+    if (in.n == 0) return KG_OK;
+    const SearchArgs &a = c.a;
+    kg_table *t = c.t;
+    Scratch &sc = c.sc;
+    hipStream_t s = t->stream;
+    unsigned long long *words = c.words;
+    uint64_t *d_tot = c.d_tot;
+    const uint32_t b = bits_for((uint64_t)a.n_prot), db = bits_for((uint64_t)a.n_db), ndb = (uint32_t)a.n_db, qb = bits_for((uint64_t)(a.n_prot - a.n_db));
+    const uint64_t P = in.w.P;
+    uint64_t *const pk = in.w.pk, *const partial = in.w.partial;
+    uint64_t K = 0, R = 0, ND = 0;
+    int rc;
 
-        // ---- the valid windows, and whether they fit: one pass ----
-        const uint64_t space = seed ? seed->space : (uint64_t)KG_MAX_ENCODED;
-        if (seed) {
-            if ((rc = seed_count(dv, seed, dv.d_bins, &n))) return rc;
-        } else {
-            std::vector<unsigned long long> bins;
-            if ((rc = dv.histogram(0, space, Deriver::shift_for(space), bins))) return rc;
-            for (auto c : bins) n += c;
-        }
-        st.valid_windows = (int64_t)n;
-        {
-            uint64_t cap = (uint64_t)max_windows;
-            if (cap == 0) {
-                size_t free_b = 0, total_b = 0;
-                HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-                cap = std::max<uint64_t>(1u << 20, (uint64_t)(free_b * 0.8) / kDeriveBytesPerWindow);
-            }
-            cap = std::min(cap, kDerivePassMax);
-            if (n > cap)
-                return fail(KG_ERR_LIMIT, kmer_text((int64_t)n) + " valid windows do not fit the one pass of this call, which holds " +
-                                              kmer_text((int64_t)cap) + (max_windows ? " (max_windows)" : " (sized from free device memory)"));
-        }
-        for (int k = 1; k <= 4; k++) HIP_TRY(hipEventRecord(ev[k], s));
+    // ---- the k-mer runs, their split at n_db and their weights (flags / pidx / partial are reused: K <= P <= n) ----
+    uint32_t *kh = in.w.flags, *kx = in.w.pidx, *kstart = nullptr, *nd = nullptr, *w = nullptr, *wf = in.w.pv, *wpos = nullptr;
+    hipLaunchKernelGGL(kg::search_kmer_heads_kernel, dim3(grid_of(P)), dim3(256), 0, s, pk, P, b, kh);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, kh, P, kx, partial, d_tot + 1))) return rc;
+    HIP_TRY(hipMemcpyAsync(&K, d_tot + 1, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->K = K;
+    if ((rc = sc.get(&kstart, K + 1)) || (rc = sc.get(&nd, K)) || (rc = sc.get(&w, K)) || (rc = sc.get(&wpos, K))) return rc;
+    hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(P)), dim3(256), 0, s, kh, kx, P, d_tot + 1, kstart);
+    hipLaunchKernelGGL(kg::search_run_weights_kernel, dim3(grid_of(K)), dim3(256), 0, s, pk, kstart, K, b, ndb, (uint32_t)a.prm->max_db_per_kmer,
+                       nd, w, wf, words);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, wf, K, wpos, partial, d_tot + 2))) return rc;
+    unsigned long long hw[3] = {};
+    HIP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&R, d_tot + 2, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint64_t J = out->J = hw[kg::kSearchJoinPairs];
+    out->joined = hw[kg::kSearchJoined];
+    out->masked = hw[kg::kSearchMasked];
+    if (R != hw[kg::kSearchJoined]) return fail(KG_ERR_DEVICE, "internal: the listed runs and the joined k-mers differ");
 
-        if (n > 0) {
-            // ---- encode and emit (key = v << b | p), sort, collapse to the distinct pairs: the derive call's kernels ----
-            SortPairs sp;
-            unsigned long long *d_cur = nullptr;
-            if ((rc = sp.alloc(sc, n)) || (rc = sc.get(&d_cur, 1))) return rc;
-            HIP_TRY(hipMemsetAsync(d_cur, 0, 8, s));
-            HIP_TRY(hipEventRecord(ev[1], s));
-            if (seed) {
-                hipLaunchKernelGGL(kg::seed_windows_kernel<true>, dim3(seed_grid(dv.n_blocks)), dim3(kg::kDeriveThreads), 0, s, d_seq, dv.d_blocks,
-                                   dv.n_blocks, seed->spec, nullptr, rank_of, b, sp.keys(), sp.vals(), d_cur, n);
-                HIP_TRY(hipGetLastError());
-            } else {
-                const uint32_t grid = std::min<uint32_t>((dv.n_blocks + kg::kWavesPerWG - 1) / kg::kWavesPerWG, 256u * 16);
-                hipLaunchKernelGGL(kg::derive_windows_kernel<true>, dim3(std::max(grid, 1u)), dim3(kg::kDeriveThreads), 0, s, d_seq, dv.d_blocks,
-                                   dv.n_blocks, (uint64_t)0, space, 0u, nullptr, rank_of, b, sp.keys(), sp.vals(), d_cur, n);
-                HIP_TRY(hipGetLastError());
-            }
-            HIP_TRY(hipEventRecord(ev[2], s));
-            if ((rc = sp.sort(t, sc, n, bit_width(space - 1) + b))) return rc;
-            HIP_TRY(hipEventRecord(ev[3], s));
-            const uint64_t nb = n / kg::kScanChunk + 2;
-            uint32_t *flags = nullptr, *pidx = nullptr;
-            uint64_t *partial = nullptr;
-            if ((rc = sc.get(&flags, n + 1)) || (rc = sc.get(&pidx, n + 1)) || (rc = sc.get(&partial, nb + 1))) return rc;
-            hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(n)), dim3(256), 0, s, sp.keys(), n, flags);
-            HIP_TRY(hipGetLastError());
-            if ((rc = prefix_sum(t, flags, n, pidx, partial, d_tot + 0))) return rc;
-            unsigned long long host_cur = 0;
-            HIP_TRY(hipMemcpyAsync(&host_cur, d_cur, 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(&P, d_tot, 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (host_cur != n) return fail(KG_ERR_DEVICE, "internal: the emit pass wrote a different number of windows than the histogram counted");
-            uint64_t *pk = nullptr;
-            uint32_t *pv = nullptr;
-            if ((rc = sc.get(&pk, P)) || (rc = sc.get(&pv, P))) return rc;
-            HIP_TRY(hipMemsetAsync(pv, 0, P * 4, s));
-            hipLaunchKernelGGL(kg::derive_collapse_kernel, dim3(grid_of((n + kg::kDeriveChunk - 1) / kg::kDeriveChunk)), dim3(256), 0, s, sp.keys(),
-                               sp.vals(), n, pidx, pk, pv);
-            HIP_TRY(hipGetLastError());
+    // ---- whether the join fits: J is the 64-bit sum, exact whatever the stored weights saturate to ----
+    Cap cap;
+    if ((rc = size_cap(a.max_pairs, " (max_pairs)", kSearchBytesPerPair, kSearchPairsMax, &cap))) return rc;
+    if (J > cap.items)
+        return fail(KG_ERR_LIMIT, kmer_text((int64_t)J) + " join pairs do not fit this call, which holds " + kmer_text((int64_t)cap.items) +
+                                      cap.how + "; a smaller max_db_per_kmer masks more of the frequent k-mers");
+    if (J == 0) return KG_OK;
 
-            // ---- the k-mer runs, their split at n_db and their weights (flags / pidx / partial are reused: K <= P <= n) ----
-            uint32_t *kh = flags, *kx = pidx, *kstart = nullptr, *nd = nullptr, *w = nullptr, *wf = pv, *wpos = nullptr;
-            hipLaunchKernelGGL(kg::search_kmer_heads_kernel, dim3(grid_of(P)), dim3(256), 0, s, pk, P, b, kh);
-            HIP_TRY(hipGetLastError());
-            if ((rc = prefix_sum(t, kh, P, kx, partial, d_tot + 1))) return rc;
-            HIP_TRY(hipMemcpyAsync(&K, d_tot + 1, 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if ((rc = sc.get(&kstart, K + 1)) || (rc = sc.get(&nd, K)) || (rc = sc.get(&w, K)) || (rc = sc.get(&wpos, K))) return rc;
-            hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(P)), dim3(256), 0, s, kh, kx, P, d_tot + 1, kstart);
-            hipLaunchKernelGGL(kg::search_run_weights_kernel, dim3(grid_of(K)), dim3(256), 0, s, pk, kstart, K, b, ndb,
-                               (uint32_t)prm->max_db_per_kmer, nd, w, wf, words);
-            HIP_TRY(hipGetLastError());
-            if ((rc = prefix_sum(t, wf, K, wpos, partial, d_tot + 2))) return rc;
-            unsigned long long hw[3] = {};
-            HIP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(&R, d_tot + 2, 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            J = hw[kg::kSearchJoinPairs];
-            st.kmers_joined = (int64_t)hw[kg::kSearchJoined];
-            st.kmers_masked = (int64_t)hw[kg::kSearchMasked];
-            if (R != hw[kg::kSearchJoined]) return fail(KG_ERR_DEVICE, "internal: the listed runs and the joined k-mers differ");
+    // ---- the runs of weight >= 1, the prefix sum of their weights (J < 2^32: no stored weight is saturated) ----
+    uint32_t *cstart = nullptr, *cnd = nullptr, *cw = nullptr, *wx = nullptr;
+    uint64_t *jpartial = nullptr;
+    if ((rc = sc.get(&cstart, R)) || (rc = sc.get(&cnd, R)) || (rc = sc.get(&cw, R + 1)) || (rc = sc.get(&wx, R + 1)) ||
+        (rc = sc.get(&jpartial, J / kg::kScanChunk + 3)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(cw + R, 0, 4, s));
+    hipLaunchKernelGGL(kg::search_run_compact_kernel, dim3(grid_of(K)), dim3(256), 0, s, kstart, nd, w, wf, wpos, K, R, cstart, cnd, cw);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, cw, R + 1, wx, partial, d_tot + 3))) return rc;
+    // ---- the join: one key per (query, target) of every listed run ----
+    SortPairs jp;
+    if ((rc = jp.alloc(sc, J))) return rc;
+    hipLaunchKernelGGL(kg::search_join_kernel, dim3(grid_of(J, kg::kSearchTile)), dim3(kg::kSearchThreads), 0, s, pk, wx, cstart, cnd, (uint32_t)R,
+                       (uint32_t)J, b, ndb, db, jp.keys(), jp.vals());
+    HIP_TRY(hipGetLastError());
+    uint64_t wtot = 0;
+    HIP_TRY(hipMemcpyAsync(&wtot, d_tot + 3, 8, hipMemcpyDeviceToHost, s));
+    if ((rc = jp.sort(t, sc, J, qb + db))) return rc;
+    // ---- runs of equal keys = distinct (q, d), run length = s(q, d) ----
+    uint32_t *lh = nullptr, *lr = nullptr, *lstart = nullptr;
+    if ((rc = sc.get(&lh, J)) || (rc = sc.get(&lr, J))) return rc;
+    hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(J)), dim3(256), 0, s, jp.keys(), J, lh);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, lh, J, lr, jpartial, d_tot + 4))) return rc;
+    HIP_TRY(hipMemcpyAsync(&ND, d_tot + 4, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (wtot != J) return fail(KG_ERR_DEVICE, "internal: the prefix sum of the weights and their 64-bit sum differ");
+    if ((rc = sc.get(&lstart, ND + 1))) return rc;
+    uint32_t *cf = lh, *cx = lr;                        // (the heads and their scan are free behind the starts: ND <= J)
+    hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(J)), dim3(256), 0, s, lh, lr, J, d_tot + 4, lstart);
+    hipLaunchKernelGGL(kg::search_cand_flags_kernel, dim3(grid_of(ND)), dim3(256), 0, s, lstart, ND, (uint32_t)a.prm->min_shared, cf, words);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, cf, ND, cx, jpartial, d_tot + 5))) return rc;
+    unsigned long long smax = 0;
+    uint64_t NC = 0;
+    HIP_TRY(hipMemcpyAsync(&NC, d_tot + 5, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&smax, words + kg::kSearchSmax, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->NC = NC;
+    if (NC == 0) return KG_OK;
 
-            // ---- whether the join fits: J is the 64-bit sum, exact whatever the stored weights saturate to ----
-            {
-                uint64_t cap = (uint64_t)max_pairs;
-                if (cap == 0) {
-                    size_t free_b = 0, total_b = 0;
-                    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-                    cap = std::max<uint64_t>(1u << 20, (uint64_t)(free_b * 0.8) / kSearchBytesPerPair);
-                }
-                cap = std::min(cap, kSearchPairsMax);
-                if (J > cap)
-                    return fail(KG_ERR_LIMIT, kmer_text((int64_t)J) + " join pairs do not fit this call, which holds " + kmer_text((int64_t)cap) +
-                                                  (max_pairs ? " (max_pairs)" : " (sized from free device memory)") +
-                                                  "; a smaller max_db_per_kmer masks more of the frequent k-mers");
-            }
-            if (J > 0) {
-                // ---- the runs of weight >= 1, the prefix sum of their weights (J < 2^32: no stored weight is saturated) ----
-                uint32_t *cstart = nullptr, *cnd = nullptr, *cw = nullptr, *wx = nullptr;
-                uint64_t *jpartial = nullptr;
-                if ((rc = sc.get(&cstart, R)) || (rc = sc.get(&cnd, R)) || (rc = sc.get(&cw, R + 1)) || (rc = sc.get(&wx, R + 1)) ||
-                    (rc = sc.get(&jpartial, J / kg::kScanChunk + 3)))
-                    return rc;
-                HIP_TRY(hipMemsetAsync(cw + R, 0, 4, s));
-                hipLaunchKernelGGL(kg::search_run_compact_kernel, dim3(grid_of(K)), dim3(256), 0, s, kstart, nd, w, wf, wpos, K, R, cstart, cnd, cw);
-                HIP_TRY(hipGetLastError());
-                if ((rc = prefix_sum(t, cw, R + 1, wx, partial, d_tot + 3))) return rc;
-                // ---- the join: one key per (query, target) of every listed run ----
-                SortPairs jp;
-                if ((rc = jp.alloc(sc, J))) return rc;
-                hipLaunchKernelGGL(kg::search_join_kernel, dim3(grid_of(J, kg::kSearchTile)), dim3(kg::kSearchThreads), 0, s, pk, wx, cstart, cnd,
-                                   (uint32_t)R, (uint32_t)J, b, ndb, db, jp.keys(), jp.vals());
-                HIP_TRY(hipGetLastError());
-                uint64_t wtot = 0;
-                HIP_TRY(hipMemcpyAsync(&wtot, d_tot + 3, 8, hipMemcpyDeviceToHost, s));
-                if ((rc = jp.sort(t, sc, J, bits_for((uint64_t)n_q) + db))) return rc;
-                // ---- runs of equal keys = distinct (q, d), run length = s(q, d) ----
-                uint32_t *lh = nullptr, *lr = nullptr, *lstart = nullptr, *cf = nullptr, *cx = nullptr;
-                if ((rc = sc.get(&lh, J)) || (rc = sc.get(&lr, J))) return rc;
-                hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(J)), dim3(256), 0, s, jp.keys(), J, lh);
-                HIP_TRY(hipGetLastError());
-                if ((rc = prefix_sum(t, lh, J, lr, jpartial, d_tot + 4))) return rc;
-                HIP_TRY(hipMemcpyAsync(&ND, d_tot + 4, 8, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                if (wtot != J) return fail(KG_ERR_DEVICE, "internal: the prefix sum of the weights and their 64-bit sum differ");
-                if ((rc = sc.get(&lstart, ND + 1))) return rc;
-                cf = lh; cx = lr;                                   // (the heads and their scan are free behind the starts: ND <= J)
-                hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(J)), dim3(256), 0, s, lh, lr, J, d_tot + 4, lstart);
-                hipLaunchKernelGGL(kg::search_cand_flags_kernel, dim3(grid_of(ND)), dim3(256), 0, s, lstart, ND, (uint32_t)prm->min_shared, cf, words);
-                HIP_TRY(hipGetLastError());
-                if ((rc = prefix_sum(t, cf, ND, cx, jpartial, d_tot + 5))) return rc;
-                unsigned long long smax = 0;
-                HIP_TRY(hipMemcpyAsync(&NC, d_tot + 5, 8, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipMemcpyAsync(&smax, words + kg::kSearchSmax, 8, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                if (NC > 0) {
-                    // ---- the candidates in (q, d) order, then stably by (q, descending s): ties stay in ascending d ----
-                    const uint32_t sb = bit_width(smax);
-                    uint64_t *ckey = nullptr;
-                    uint32_t *cs = nullptr, *qh = nullptr, *qx = nullptr, *qstart = nullptr, *tf = nullptr, *tx = nullptr;
-                    SortPairs cp;
-                    if ((rc = sc.get(&ckey, NC)) || (rc = sc.get(&cs, NC)) || (rc = cp.alloc(sc, NC)) || (rc = sc.get(&qh, NC)) ||
-                        (rc = sc.get(&qx, NC)) || (rc = sc.get(&tf, NC)) || (rc = sc.get(&tx, NC)))
-                        return rc;
-                    hipLaunchKernelGGL(kg::search_cand_emit_kernel, dim3(grid_of(ND)), dim3(256), 0, s, jp.keys(), lstart, cf, cx, ND, NC, db, sb,
-                                       (uint32_t)smax, ckey, cs, cp.keys(), cp.vals());
-                    HIP_TRY(hipGetLastError());
-                    if ((rc = cp.sort(t, sc, NC, bits_for((uint64_t)n_q) + sb))) return rc;
-                    hipLaunchKernelGGL(kg::search_query_heads_kernel, dim3(grid_of(NC)), dim3(256), 0, s, cp.keys(), NC, sb, qh);
-                    HIP_TRY(hipGetLastError());
-                    if ((rc = prefix_sum(t, qh, NC, qx, jpartial, d_tot + 6))) return rc;
-                    uint64_t NQ = 0;
-                    HIP_TRY(hipMemcpyAsync(&NQ, d_tot + 6, 8, hipMemcpyDeviceToHost, s));
-                    HIP_TRY(hipStreamSynchronize(s));
-                    if ((rc = sc.get(&qstart, NQ + 1))) return rc;
-                    hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(NC)), dim3(256), 0, s, qh, qx, NC, d_tot + 6, qstart);
-                    hipLaunchKernelGGL(kg::search_top_flags_kernel, dim3(grid_of(NC)), dim3(256), 0, s, qh, qx, qstart, NC, (uint32_t)prm->max_cand, tf);
-                    HIP_TRY(hipGetLastError());
-                    if ((rc = prefix_sum(t, tf, NC, tx, jpartial, d_tot + 7))) return rc;
-                    HIP_TRY(hipMemcpyAsync(&NK, d_tot + 7, 8, hipMemcpyDeviceToHost, s));
-                    HIP_TRY(hipStreamSynchronize(s));
-                    if ((rc = sc.get(&d_kept_pairs, 2 * NK)) || (rc = sc.get(&d_shared, NK))) return rc;
-                    hipLaunchKernelGGL(kg::search_top_emit_kernel, dim3(grid_of(NC)), dim3(256), 0, s, cp.vals(), ckey, cs, tf, tx, NC, NK, db, ndb,
-                                       d_kept_pairs, d_shared);
-                    HIP_TRY(hipGetLastError());
-                }
-            }
-            HIP_TRY(hipEventRecord(ev[4], s));
-        }
-    }
+    // ---- the candidates in (q, d) order, then stably by (q, descending s): ties stay in ascending d ----
+    const uint32_t sb = bit_width(smax);
+    uint64_t *ckey = nullptr;
+    uint32_t *cs = nullptr, *qh = nullptr, *qx = nullptr, *qstart = nullptr, *tf = nullptr, *tx = nullptr;
+    SortPairs cp;
+    if ((rc = sc.get(&ckey, NC)) || (rc = sc.get(&cs, NC)) || (rc = cp.alloc(sc, NC)) || (rc = sc.get(&qh, NC)) || (rc = sc.get(&qx, NC)) ||
+        (rc = sc.get(&tf, NC)) || (rc = sc.get(&tx, NC)))
+        return rc;
+    hipLaunchKernelGGL(kg::search_cand_emit_kernel, dim3(grid_of(ND)), dim3(256), 0, s, jp.keys(), lstart, cf, cx, ND, NC, db, sb, (uint32_t)smax,
+                       ckey, cs, cp.keys(), cp.vals());
+    HIP_TRY(hipGetLastError());
+    if ((rc = cp.sort(t, sc, NC, qb + sb))) return rc;
+    hipLaunchKernelGGL(kg::search_query_heads_kernel, dim3(grid_of(NC)), dim3(256), 0, s, cp.keys(), NC, sb, qh);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, qh, NC, qx, jpartial, d_tot + 6))) return rc;
+    uint64_t NQ = 0, NK = 0;
+    HIP_TRY(hipMemcpyAsync(&NQ, d_tot + 6, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = sc.get(&qstart, NQ + 1))) return rc;
+    hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(NC)), dim3(256), 0, s, qh, qx, NC, d_tot + 6, qstart);
+    hipLaunchKernelGGL(kg::search_top_flags_kernel, dim3(grid_of(NC)), dim3(256), 0, s, qh, qx, qstart, NC, (uint32_t)a.prm->max_cand, tf);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, tf, NC, tx, jpartial, d_tot + 7))) return rc;
+    HIP_TRY(hipMemcpyAsync(&NK, d_tot + 7, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->NK = NK;
+    if ((rc = sc.get(&out->d_kept_pairs, 2 * NK)) || (rc = sc.get(&out->d_shared, NK))) return rc;
+    hipLaunchKernelGGL(kg::search_top_emit_kernel, dim3(grid_of(NC)), dim3(256), 0, s, cp.vals(), ckey, cs, tf, tx, NC, NK, db, ndb,
+                       out->d_kept_pairs, out->d_shared);
+    HIP_TRY(hipGetLastError());
+    return KG_OK;
+}
 
-    // ---- the result block; the kept candidates to the host, aligned, ordered ----
+// Stage 3: the result block with hit_start, the kept candidates aligned and ordered, the cross-checks, the statistics, and the
+// paths where the call asks for them.  The set owns its blocks from their allocation on: a set freed after a failure frees them.
+int search_finish(SearchCall &c, const SearchPairs &pairs, const SearchCands &cd, kg_hitset *set)
+{
+    const SearchArgs &a = c.a;
+    kg_table *t = c.t;
+    hipStream_t s = t->stream;
+    const int64_t n_db = a.n_db, n_q = a.n_prot - a.n_db;
+    const uint64_t NK = cd.NK;
+    int rc;
+    set->n_q = n_q;
     const size_t start_bytes = ((size_t)n_q + 1) * 8;
-    if ((rc = dalloc_detached(t, &guard.p, start_bytes + std::max<uint64_t>(NK, 1) * sizeof(kg_search_hit)))) return rc;
+    if ((rc = dalloc_detached(t, &set->d_block.p, start_bytes + std::max<uint64_t>(NK, 1) * sizeof(kg_search_hit)))) return rc;
+    uint8_t *const block = set->d_block.p;
     std::vector<int64_t> h_start((size_t)n_q + 1, 0);
     std::vector<int32_t> h_pairs(2 * NK);
     AlignTotals atot;
     if (NK > 0) {
-        HIP_TRY(hipMemcpyAsync(h_pairs.data(), d_kept_pairs, NK * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h_pairs.data(), cd.d_kept_pairs, NK * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         for (uint64_t k = 0; k < NK; k++) {
             const int64_t q = (int64_t)h_pairs[2 * k] - n_db;
@@ -431,49 +406,76 @@ int search_impl(kg_table *t, const kg_search_params *prm, const kg_align_params 
             h_start[(size_t)q + 1]++;
         }
         for (int64_t q = 0; q < n_q; q++) {
-            if (h_start[(size_t)q + 1] > prm->max_cand) return fail(KG_ERR_DEVICE, "internal: more than max_cand candidates of one query");
+            if (h_start[(size_t)q + 1] > a.prm->max_cand) return fail(KG_ERR_DEVICE, "internal: more than max_cand candidates of one query");
             h_start[(size_t)q + 1] += h_start[(size_t)q];
         }
     }
-    HIP_TRY(hipMemcpyAsync(guard.p, h_start.data(), start_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(block, h_start.data(), start_bytes, hipMemcpyHostToDevice, s));
     if (NK > 0) {
         const int32_t *d_pairs = nullptr;
         kg::AlignRec *d_aln = nullptr;
-        if ((rc = align_run(t, sc, al, d_seq, d_off, offsets, h_pairs.data(), NK, &d_pairs, &d_aln, &atot))) return rc;
-        hipLaunchKernelGGL(kg::search_order_kernel, dim3(grid_of((uint64_t)n_q, 256 / kg::kWave)), dim3(256), 0, s, d_pairs, d_aln, d_shared,
-                           (const int64_t *)guard.p, (uint32_t)n_q, (int64_t)al->min_ratio_pct, (int)(al->ref == KG_ALIGN_REF_MEMBER),
-                           (int2 *)(guard.p + start_bytes), words);
+        if ((rc = align_run(t, c.sc, a.al, c.d_seq, pairs.d_off, a.offsets, h_pairs.data(), NK, &d_pairs, &d_aln, &atot))) return rc;
+        hipLaunchKernelGGL(kg::search_order_kernel, dim3(grid_of((uint64_t)n_q, 256 / kg::kWave)), dim3(256), 0, s, d_pairs, d_aln, cd.d_shared,
+                           (const int64_t *)block, (uint32_t)n_q, (int64_t)a.al->min_ratio_pct, (int)(a.al->ref == KG_ALIGN_REF_MEMBER),
+                           (int2 *)(block + start_bytes), c.words);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(ev[5], s));
+    HIP_TRY(hipEventRecord(c.ev[5], s));
     unsigned long long hw[kg::kSearchWords] = {};
-    HIP_TRY(hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(hw, c.words, sizeof hw, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if ((int64_t)hw[kg::kSearchSkipped] != atot.skipped) return fail(KG_ERR_DEVICE, "internal: the device and the host skipped different pairs");
     if (hw[kg::kSearchHits] + hw[kg::kSearchBelow] + hw[kg::kSearchSkipped] != NK)
         return fail(KG_ERR_DEVICE, "internal: the ordered records and the kept candidates differ");
-    st.pairs = (int64_t)P;
-    st.kmers = (int64_t)K;
-    st.join_pairs = (int64_t)J;
-    st.candidates = (int64_t)NC;
+    kg_search_stats &st = set->st;
+    st.targets = n_db;
+    st.queries = n_q;
+    st.valid_windows = (int64_t)pairs.n;
+    st.pairs = (int64_t)pairs.w.P;
+    st.kmers = (int64_t)cd.K;
+    st.kmers_joined = (int64_t)cd.joined;
+    st.kmers_masked = (int64_t)cd.masked;
+    st.join_pairs = (int64_t)cd.J;
+    st.candidates = (int64_t)cd.NC;
     st.aligned = (int64_t)NK - atot.skipped;
     st.hits = (int64_t)hw[kg::kSearchHits];
     st.skipped = atot.skipped;
     st.queries_hit = (int64_t)hw[kg::kSearchQueriesHit];
     st.cells = atot.cells;
-    st.ms_encode = dv.ms_hist + ev.ms(1, 2);
-    st.ms_sort = ev.ms(2, 3);
-    st.ms_join = ev.ms(3, 4);
-    st.ms_align = ev.ms(4, 5);
-    st.ms_total = ev.ms(0, 5);
-    set->d_block = guard.p; guard.p = nullptr;
+    st.ms_encode = pairs.ms_count + c.ev.ms(1, 2);
+    st.ms_sort = c.ev.ms(2, 3);
+    st.ms_join = c.ev.ms(3, 4);
+    st.ms_align = c.ev.ms(4, 5);
+    st.ms_total = c.ev.ms(0, 5);
     set->count = (int64_t)NK;
-    return ask ? search_paths_behind(t, sc, al, d_seq, d_off, n_db, set->hits(), NK, ask, set) : KG_OK;
+    return a.ask.trace ? search_paths_behind(t, c.sc, a.al, c.d_seq, pairs.d_off, n_db, set->hits(), NK, a.ask, set) : KG_OK;
 }
 
+int search_impl(kg_table *t, const SearchArgs &a, kg_hitset *set)
+{
+    hipStream_t s = t->stream;
+    Scratch sc(t);
+    Events<8> ev;
+    int rc;
+    if ((rc = ev.create())) return rc;
+    SearchCall c{a, t, sc, ev};
+    if ((rc = stage_sequence(t, sc, a.h_seq, a.d_seq, a.n_prot ? (uint64_t)a.offsets[a.n_prot] : 0, &c.d_seq))) return rc;
+    HIP_TRY(hipEventRecord(ev[0], s));
+    if ((rc = sc.get(&c.words, kg::kSearchWords)) || (rc = sc.get(&c.d_tot, 8))) return rc;
+    HIP_TRY(hipMemsetAsync(c.words, 0, kg::kSearchWords * 8, s));
+    // the times of a call that ends early: every stage it did not reach is empty (a stage that is reached records its events again)
+    for (int k = 1; k <= 4; k++) HIP_TRY(hipEventRecord(ev[k], s));
+    SearchPairs pairs;
+    SearchCands cands;
+    if ((rc = search_pairs(c, &pairs)) || (rc = search_candidates(c, pairs, &cands))) return rc;
+    if (pairs.n > 0) HIP_TRY(hipEventRecord(ev[4], s));
+    return search_finish(c, pairs, cands, set);
+}
+
+// seeds: no value for the exact call; of a seeded call the caller's pointer, checked here
 int search_entry(int device, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq,
                  const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset **out,
-                 const SearchPathsAsk *ask = nullptr, const kg_seed_params *seeds = nullptr, bool seeded = false)
+                 SearchPathsAsk ask = {}, std::optional<const kg_seed_params *> seeds = std::nullopt)
 {
     if (!out) return fail(KG_ERR_ARG, "null argument");
     *out = nullptr;
@@ -483,27 +485,21 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     if (prm->max_db_per_kmer < 1) return fail(KG_ERR_ARG, "max_db_per_kmer must be >= 1");
     if (prm->reserved != 0) return fail(KG_ERR_ARG, "kg_search_params.reserved must be 0");
     SeedPlan plan;
-    if (seeded)
-        if (int rc = seed_plan(seeds, &plan)) return rc;
+    if (seeds)
+        if (int rc = seed_plan(*seeds, &plan)) return rc;
     if (!al) return fail(KG_ERR_ARG, "null kg_align_params");
     if (int rc = align_check_params(al)) return rc;
     if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
     if (max_pairs < 0) return fail(KG_ERR_ARG, "max_pairs must be >= 0");
-    if (ask && (ask->trace & 3) != KG_TRACE_HITS && (ask->trace & 3) != KG_TRACE_ALL)
+    if (ask.trace && (ask.trace & 3) != KG_TRACE_HITS && (ask.trace & 3) != KG_TRACE_ALL)
         return fail(KG_ERR_ARG, "trace must be KG_TRACE_HITS or KG_TRACE_ALL");
-    if (ask && ((ask->trace & ~15) || (ask->trace & (KG_TRACE_OPS | KG_TRACE_OPS_EQX)) == (KG_TRACE_OPS | KG_TRACE_OPS_EQX)))
+    if (ask.trace && ((ask.trace & ~15) || (ask.trace & (KG_TRACE_OPS | KG_TRACE_OPS_EQX)) == (KG_TRACE_OPS | KG_TRACE_OPS_EQX)))
         return fail(KG_ERR_ARG, "trace takes at most one of KG_TRACE_OPS and KG_TRACE_OPS_EQX beside its mode, and no bit above 15");
-    if (ask && ask->max_trace_cells < 1) return fail(KG_ERR_ARG, "max_trace_cells must be >= 1");
+    if (ask.trace && ask.max_trace_cells < 1) return fail(KG_ERR_ARG, "max_trace_cells must be >= 1");
     if (n_prot < 0) return fail(KG_ERR_ARG, "n_prot < 0");
     if (n_prot >= (1ll << 29)) return fail(KG_ERR_LIMIT, "2^29 or more proteins in one call");
     if (n_db < 0 || n_db > n_prot) return fail(KG_ERR_ARG, "n_db must be in 0..n_prot");
-    if (!offsets) return fail(KG_ERR_ARG, "null offsets");
-    if (offsets[0] < 0) return fail(KG_ERR_ARG, "offsets[0] < 0");
-    for (int64_t k = 0; k < n_prot; k++) {
-        const int64_t L = offsets[k + 1] - offsets[k];
-        if (L < 0) return fail(KG_ERR_ARG, "protein " + kmer_text(k) + ": offsets decrease (offsets[p+1] < offsets[p])");
-        if (L >= (int64_t)kg::kAlignMaxLen) return fail(KG_ERR_LIMIT, "protein " + kmer_text(k) + ": 2^24 or more characters");
-    }
+    if (int rc = check_protein_offsets(offsets, n_prot, (int64_t)kg::kAlignMaxLen, "2^24")) return rc;
     const uint64_t seq_bytes = n_prot ? (uint64_t)offsets[n_prot] : 0;
     if (seq_bytes && !h_seq && !d_seq) return fail(KG_ERR_ARG, "null sequence");
     CallScope cs(device);               // the call's context: closed when the call returns, the set keeps only its records
@@ -511,8 +507,9 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     kg_hitset *set = new (std::nothrow) kg_hitset();
     if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
     set->device = device;
+    const SearchArgs args{prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, ask, seeds ? &plan : nullptr};
     int rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
-    if (!rc) rc = search_impl(cs.t, prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, set, ask, seeded ? &plan : nullptr);
+    if (!rc) rc = search_impl(cs.t, args, set);
     cs.t->cache.release_all();                          // scratch goes back to the driver
     if (rc) { std::string keep = g_err; kg_hitset_free(set); g_err = keep; return rc; }
     if (getenv("KG_DEBUG"))
@@ -524,6 +521,9 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     *out = set;
     return KG_OK;
 }
+
+// kg_proteins_search_paths must be given a mode: its trace = 0 is refused as trace = 3, neither mode, is, with the same words
+SearchPathsAsk paths_ask(int trace, int64_t max_trace_cells) { return {trace ? trace : KG_TRACE_HITS | KG_TRACE_ALL, max_trace_cells}; }
 
 }  // namespace
 
@@ -546,16 +546,14 @@ int kg_proteins_search_paths(int device, const kg_search_params *p, const kg_ali
                              int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, int trace, int64_t max_trace_cells,
                              kg_hitset **out)
 {
-    const SearchPathsAsk ask{trace, max_trace_cells};
-    return search_entry(device, p, align, seq, nullptr, offsets, n_prot, n_db, max_windows, max_pairs, out, &ask);
+    return search_entry(device, p, align, seq, nullptr, offsets, n_prot, n_db, max_windows, max_pairs, out, paths_ask(trace, max_trace_cells));
 }
 
 int kg_proteins_search_paths_device(int device, const kg_search_params *p, const kg_align_params *align, const uint8_t *d_seq,
                                     const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, int trace,
                                     int64_t max_trace_cells, kg_hitset **out)
 {
-    const SearchPathsAsk ask{trace, max_trace_cells};
-    return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, &ask);
+    return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, paths_ask(trace, max_trace_cells));
 }
 
 int kg_seed_params_builtin(int which, kg_seed_params *out)
@@ -581,28 +579,18 @@ int kg_seed_params_builtin(int which, kg_seed_params *out)
     return KG_OK;
 }
 
-namespace {
-int seeded_entry(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align, const uint8_t *h_seq,
-                 const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, int trace,
-                 int64_t max_trace_cells, kg_hitset **out)
-{
-    const SearchPathsAsk ask{trace, max_trace_cells};
-    return search_entry(device, p, align, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, trace ? &ask : nullptr, seeds, true);
-}
-}  // namespace
-
 int kg_proteins_search_seeded(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
                               const uint8_t *seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
                               int64_t max_pairs, int trace, int64_t max_trace_cells, kg_hitset **out)
 {
-    return seeded_entry(device, p, seeds, align, seq, nullptr, offsets, n_prot, n_db, max_windows, max_pairs, trace, max_trace_cells, out);
+    return search_entry(device, p, align, seq, nullptr, offsets, n_prot, n_db, max_windows, max_pairs, out, {trace, max_trace_cells}, seeds);
 }
 
 int kg_proteins_search_seeded_device(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
                                      const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
                                      int64_t max_pairs, int trace, int64_t max_trace_cells, kg_hitset **out)
 {
-    return seeded_entry(device, p, seeds, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, trace, max_trace_cells, out);
+    return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, {trace, max_trace_cells}, seeds);
 }
 
 int64_t kg_hitset_count(const kg_hitset *s) { return s ? s->count : 0; }
@@ -610,7 +598,7 @@ int64_t kg_hitset_count(const kg_hitset *s) { return s ? s->count : 0; }
 int kg_hitset_paths_copy(const kg_hitset *s, int64_t first, int64_t count, kg_alignment_path *dst)
 {
     if (s && !s->has_paths) return fail(KG_ERR_ARG, "kg_hitset_paths_copy: the set was made without paths");
-    return copy_records(s, s ? s->device : 0, s ? s->d_paths : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_hitset_paths_copy");
+    return copy_records(s, s ? s->device : 0, s ? (const kg_alignment_path *)s->d_paths.p : nullptr, 1, s ? s->count : 0, first, count, dst, "kg_hitset_paths_copy");
 }
 
 int kg_hitset_trace_stats(const kg_hitset *s, kg_trace_stats *out)
@@ -656,19 +644,8 @@ int kg_hitset_stats(const kg_hitset *s, kg_search_stats *out) { return copy_stat
 void kg_hitset_free(kg_hitset *s)
 {
     if (!s) return;
-    if (s->d_block) {
-        (void)hipSetDevice(s->device);
-        (void)hipFree(s->d_block);
-    }
-    if (s->d_paths) {
-        (void)hipSetDevice(s->device);
-        (void)hipFree(s->d_paths);
-    }
-    if (s->d_ops) {
-        (void)hipSetDevice(s->device);
-        (void)hipFree(s->d_ops);
-    }
-    delete s;
+    (void)hipSetDevice(s->device);
+    delete s;                           // (its blocks with it)
 }
 
 }  // extern "C"
