@@ -1,7 +1,9 @@
 """Function assignment on the GPU (kg_result_assign / kg_assign_calls): the device records must equal the numpy model of
 tests/assign_model.py byte for byte, on random CALL lists, known answers, edge shapes, -a scans of family sets and of the
 E. coli proteome under every scan strategy, and through the annotate front end, in one batch and in several; errors name the protein and failed
-allocations leave nothing behind."""
+allocations leave nothing behind.  The stage's internal borders (the split at 16 CALLs, the run walk, the wave merge, the sort's
+widths and the 2^31 limit on both paths) are in tests/test_gpu_assign_edges.py, on the inputs of tests/assign_edge_cases.py that
+tests/test_assign_edges_host.py checks on the CPU."""
 import gzip
 import os
 import subprocess
