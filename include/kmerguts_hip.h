@@ -799,6 +799,93 @@ int kg_proteins_search_seeded_device(int device, const kg_search_params *p, cons
                                      const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
                                      int64_t max_pairs, int trace, int64_t max_trace_cells, kg_hitset **out);
 
+/* ---- low-complexity segments: masking proteins for the search and the families (kernels: kg_mask.hpp) ----
+ *
+ * max_db_per_kmer drops a k-mer only when many targets hold it; a poly-Q, a QEQEQE linker or a charged tail still seeds
+ * candidates, and under a reduced alphabet more so.  This rule follows Wootton and Federhen's SEG, stages one and two: a trigger
+ * window and the extension by a second threshold.  The third stage, the trimming to the least probable sub-segment, is not
+ * done.  The rule is the project's own.  Integers only.
+ *   Parameters: window W, trigger and extend; the thresholds are in units of 1/256 bit, the units of Lg (the procedure of rule 5
+ *   of the coding section).
+ *   Codes.  toAminoAcidOff's codes 0..19; every other byte, lowercase, X and * among them, is letter 20.
+ *   Windows.  Window i of protein p covers residues i .. i + W - 1 and exists for 0 <= i <= len_p - W.  A window never spans
+ *   two proteins; a protein shorter than W has none.
+ *   Deficit.  n_a is the number of positions of the window with letter a, a in 0..20.  C(i) is the sum of n_a * Lg(n_a) over
+ *   the letters with n_a >= 1, and D(i) = W * Lg(W) - C(i) >= 0: 256 * W times the window's entropy in bits, in Lg arithmetic.
+ *   For W = 12: W * Lg(W) = 11004, and Lg(1..12) = 0, 256, 405, 512, 594, 661, 718, 768, 811, 850, 885, 917.  QEQEQEQEQEQE has
+ *   D = 3072, twelve distinct letters have D = 11004, a homopolymer has D = 0.
+ *   Tests.  low(i) iff D(i) <= W * trigger; ext(i) iff D(i) <= W * extend.
+ *   Runs.  A maximal run of consecutive window positions that all have ext qualifies iff at least one of them has low.  Every
+ *   window of a qualifying run is a masking window.
+ *   Mask.  Residue j of p is masked iff some masking window i has i <= j <= i + W - 1.
+ *   Segments.  The maximal runs of masked residues of a protein, in (protein, start) order, 0-based and inclusive.  Two
+ *   qualifying runs whose residues touch or overlap give one segment.
+ *   Limits and defaults.  4 <= window <= 32, 0 <= trigger <= extend < Lg(window), reserved = 0; otherwise KG_ERR_ARG, the message
+ *   naming the first offender.  The defaults are 12, 563 and 640: SEG's 2.2 and 2.5 bits.  They are this project's choice and
+ *   are not tuned.
+ * Nothing depends on launch geometry, on where a tile border falls, or on which other proteins are in the batch.
+ * kg_proteins_mask / _device: seq, offsets and n_prot as for kg_proteins_search, and so are the limits (n_prot < 2^29,
+ * len_p < 2^24, fewer than 2^31 window blocks, fewer than 2^32 segments), the argument errors, KG_ERR_NOMEM and
+ * KG_TEST_FAIL_ALLOC; everything but the result goes back to the driver before the call returns.  Zero proteins and proteins
+ * without a window are valid.  kg_maskset_copy gives segments [first, first + count), kg_maskset_starts_copy seg_start[n_prot + 1]
+ * (protein p's segments are [seg_start[p], seg_start[p + 1])), kg_maskset_flags_copy one 0/1 byte per residue for residues
+ * [first, first + count) of the batch, residue 0 being offsets[0]; dst is host or device memory in all three.
+ * kg_proteins_search_masked / _device: kg_proteins_search_seeded's arguments with seeds nullable (NULL: the exact 8-mers), the
+ * mask parameters and sides: KG_MASK_QUERIES, KG_MASK_TARGETS or both.  Soft masking: the mask of that side's proteins is
+ * computed on the device, and the window pass (and nothing else) reads a copy of the sequence in which every masked residue has
+ * 0x20 set, which makes a letter lowercase and so a non-residue.  The alignment, the self-scores, the trace and the ops read the
+ * original.  kg_search_hit, hit_start and kg_search_stats keep their layout; valid_windows and every count behind it count what
+ * the masked copy gives, and ms_total includes the mask's time.  Under a spaced shape a masked residue on a don't-care position
+ * keeps the seed: that follows from the seed rule.  kg_hitset_mask_stats gives the mask's statistics (of the masked side), and
+ * KG_ERR_ARG for a set made by any other call.  KG_ERR_ARG also: "sides must be KG_MASK_QUERIES, KG_MASK_TARGETS or both".
+ * kg_proteins_cluster_masked / _device: kg_proteins_cluster_aligned's arguments with align nullable (NULL: no alignment step),
+ * and the mask parameters; every protein is masked.  A protein's "distinct 8-mers" in min_cover_pct are those of the masked
+ * copy.  kg_familyset_mask_stats likewise.
+ * The entry points above and their results are unchanged, byte for byte. */
+#define KG_MASK_QUERIES 1
+#define KG_MASK_TARGETS 2
+typedef struct kg_mask_params { int32_t window; int32_t trigger; int32_t extend; int32_t reserved; } kg_mask_params;
+typedef struct kg_mask_segment { int32_t protein; int32_t start; int32_t end; int32_t reserved; } kg_mask_segment;   /* 16 B */
+typedef struct kg_mask_stats {
+    int64_t proteins;
+    int64_t residues;
+    int64_t windows;           /* window positions: the sum of max(len_p - W + 1, 0)        */
+    int64_t low_windows;
+    int64_t ext_windows;
+    int64_t masking_windows;   /* the windows of the qualifying runs                        */
+    int64_t segments;
+    int64_t masked_residues;
+    int64_t proteins_masked;   /* proteins with a segment                                   */
+    float   ms_mask;           /* the mask's kernels; under a search or cluster call the seeding copy too */
+    int32_t reserved;
+} kg_mask_stats;
+typedef struct kg_maskset kg_maskset;
+int kg_proteins_mask(int device, const kg_mask_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot, kg_maskset **out);
+int kg_proteins_mask_device(int device, const kg_mask_params *p, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
+                            kg_maskset **out);
+int64_t kg_maskset_count(const kg_maskset *s);
+int kg_maskset_copy(const kg_maskset *s, int64_t first, int64_t count, kg_mask_segment *dst);
+int kg_maskset_starts_copy(const kg_maskset *s, int64_t *dst);
+int kg_maskset_flags_copy(const kg_maskset *s, int64_t first, int64_t count, uint8_t *dst);
+int kg_maskset_stats(const kg_maskset *s, kg_mask_stats *out);
+void kg_maskset_free(kg_maskset *s);
+int kg_proteins_search_masked(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                              const uint8_t *seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                              int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides,
+                              kg_hitset **out);
+int kg_proteins_search_masked_device(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                                     const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                                     int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides,
+                                     kg_hitset **out);
+int kg_hitset_mask_stats(const kg_hitset *s, kg_mask_stats *out);
+int kg_proteins_cluster_masked(int device, const kg_cluster_params *p, const kg_align_params *align, const uint8_t *seq,
+                               const int64_t *offsets, int64_t n_prot, int64_t max_windows, const kg_mask_params *mask,
+                               kg_familyset **out);
+int kg_proteins_cluster_masked_device(int device, const kg_cluster_params *p, const kg_align_params *align, const uint8_t *d_seq,
+                                      const int64_t *offsets, int64_t n_prot, int64_t max_windows, const kg_mask_params *mask,
+                                      kg_familyset **out);
+int kg_familyset_mask_stats(const kg_familyset *s, kg_mask_stats *out);
+
 /* ---- assigning functions: the CALL records of an -a scan -> one function per protein (kernels: kg_assign.hpp) ----
  *
  * The reference stops at the CALL lines (KGJ:398-404, 526-536); this rule is the project's own.

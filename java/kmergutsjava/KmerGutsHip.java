@@ -461,6 +461,26 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_mask_params (kg_proteins_mask*, kg_proteins_search_masked*, kg_proteins_cluster_masked*): 4 <= window <= 32,
+     *  0 <= trigger <= extend < Lg(window) in units of 1/256 bit; the defaults are 12, 563, 640; reserved 0. */
+    class KgMaskParams extends Structure {
+        public int window, trigger, extend, reserved;
+        public KgMaskParams() {
+            setFieldOrder(new String[] {"window", "trigger", "extend", "reserved"});
+        }
+    }
+
+    /** struct kg_mask_stats. */
+    class KgMaskStats extends Structure {
+        public long proteins, residues, windows, low_windows, ext_windows, masking_windows, segments, masked_residues, proteins_masked;
+        public float ms_mask;
+        public int reserved;
+        public KgMaskStats() {
+            setFieldOrder(new String[] {"proteins", "residues", "windows", "low_windows", "ext_windows", "masking_windows", "segments",
+                    "masked_residues", "proteins_masked", "ms_mask", "reserved"});
+        }
+    }
+
     /** struct kg_merge_params (kg_table_merge_signatures*): on_conflict = KG_MERGE_KEEP (0), KG_MERGE_REPLACE (1) or KG_MERGE_DROP (2). */
     class KgMergeParams extends Structure {
         public int on_conflict, reserved;
@@ -576,6 +596,31 @@ public interface KmerGutsHip extends Library {
     int kg_proteins_search_seeded_device(int device, KgSearchParams params, KgSeedParams seeds, KgAlignParams align, Pointer dSeq,
                                          long[] offsets, long nProt, long nDb, long maxWindows, long maxPairs, int trace, long maxTraceCells,
                                          PointerByReference out);
+    /** proteins -> their low-complexity segments (SEG's trigger window and extension; the header states the rule).  The set holds
+     *  kg_mask_segment[count] (16 B each: protein, start, end inclusive, reserved), segStart[nProt + 1] and one 0/1 byte per residue */
+    int kg_proteins_mask(int device, KgMaskParams params, byte[] seq, long[] offsets, long nProt, PointerByReference out);
+    int kg_proteins_mask_device(int device, KgMaskParams params, Pointer dSeq, long[] offsets, long nProt, PointerByReference out);
+    long kg_maskset_count(Pointer set);
+    int kg_maskset_copy(Pointer set, long first, long count, Pointer dst);         // kg_mask_segment[count]
+    int kg_maskset_starts_copy(Pointer set, long[] dst);                           // segStart[nProt + 1]
+    int kg_maskset_flags_copy(Pointer set, long first, long count, Pointer dst);   // byte[count], residue 0 = offsets[0]
+    int kg_maskset_stats(Pointer set, KgMaskStats out);
+    void kg_maskset_free(Pointer set);
+    /** kg_proteins_search_seeded (seeds = null: the exact 8-mers) with the seeding pass on a soft-masked copy of the sequence:
+     *  sides = KG_MASK_QUERIES (1), KG_MASK_TARGETS (2) or both (3); the alignment reads the original */
+    int kg_proteins_search_masked(int device, KgSearchParams params, KgSeedParams seeds, KgAlignParams align, byte[] seq, long[] offsets,
+                                  long nProt, long nDb, long maxWindows, long maxPairs, int trace, long maxTraceCells, KgMaskParams mask,
+                                  int sides, PointerByReference out);
+    int kg_proteins_search_masked_device(int device, KgSearchParams params, KgSeedParams seeds, KgAlignParams align, Pointer dSeq,
+                                         long[] offsets, long nProt, long nDb, long maxWindows, long maxPairs, int trace, long maxTraceCells,
+                                         KgMaskParams mask, int sides, PointerByReference out);
+    int kg_hitset_mask_stats(Pointer set, KgMaskStats out);
+    /** kg_proteins_cluster_aligned (align = null: no alignment step) with every protein soft-masked for the 8-mer pass */
+    int kg_proteins_cluster_masked(int device, KgClusterParams params, KgAlignParams align, byte[] seq, long[] offsets, long nProt,
+                                   long maxWindows, KgMaskParams mask, PointerByReference out);
+    int kg_proteins_cluster_masked_device(int device, KgClusterParams params, KgAlignParams align, Pointer dSeq, long[] offsets, long nProt,
+                                          long maxWindows, KgMaskParams mask, PointerByReference out);
+    int kg_familyset_mask_stats(Pointer set, KgMaskStats out);
     Pointer kg_table_device_entries(Pointer table);
     long kg_table_records(Pointer table);
     int kg_table_info(Pointer table, long[] numSigs, long[] entrySize, long[] version, long[] occupied);

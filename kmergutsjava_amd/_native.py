@@ -47,6 +47,10 @@ EXPORTS = (
     "kg_hitset_stats", "kg_hitset_free",
     "kg_proteins_search_paths", "kg_proteins_search_paths_device", "kg_hitset_paths_copy", "kg_hitset_trace_stats",
     "kg_seed_params_builtin", "kg_proteins_search_seeded", "kg_proteins_search_seeded_device",
+    "kg_proteins_mask", "kg_proteins_mask_device", "kg_maskset_count", "kg_maskset_copy", "kg_maskset_starts_copy",
+    "kg_maskset_flags_copy", "kg_maskset_stats", "kg_maskset_free",
+    "kg_proteins_search_masked", "kg_proteins_search_masked_device", "kg_hitset_mask_stats",
+    "kg_proteins_cluster_masked", "kg_proteins_cluster_masked_device", "kg_familyset_mask_stats",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
@@ -167,6 +171,13 @@ assert SEARCH_HIT_DTYPE.itemsize == 40
 SEARCH_HIT, SEARCH_BELOW, SEARCH_SKIPPED = 0, 1, 2      # kg_search_hit.status
 SEARCH_TILE = 2048          # kg_search.hpp kSearchTile: the join items of one workgroup (tests aim at its edges) ...
 SEARCH_MAX_CAND = 64        # ... and kSearchMaxCand: the largest max_cand, one lane per candidate
+# struct kg_mask_segment (kg_proteins_mask*): one low-complexity segment, residues start .. end of its protein, inclusive
+MASK_SEGMENT_DTYPE = np.dtype([("protein", "<i4"), ("start", "<i4"), ("end", "<i4"), ("reserved", "<i4")])
+assert MASK_SEGMENT_DTYPE.itemsize == 16
+MASK_WINDOW, MASK_TRIGGER, MASK_EXTEND = 12, 563, 640   # the defaults: SEG's 2.2 and 2.5 bits in units of 1/256 bit
+MASK_QUERIES, MASK_TARGETS = 1, 2                       # KG_MASK_*: the sides of kg_proteins_search_masked
+MASK_SIDES = {"queries": MASK_QUERIES, "targets": MASK_TARGETS, "both": MASK_QUERIES | MASK_TARGETS}
+MASK_TILE = 64              # kg_device.hpp kAaWinPerBlock: the window positions of one block and of one word (tests aim at its edges)
 assert HIT_DTYPE.itemsize == 24 and CALL_DTYPE.itemsize == 24 and OTU_DTYPE.itemsize == 44
 
 
@@ -416,6 +427,26 @@ class KgSearchStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class KgMaskParams(C.Structure):
+    """struct kg_mask_params (kg_proteins_mask*, kg_proteins_search_masked*, kg_proteins_cluster_masked*)."""
+    _fields_ = [("window", C.c_int32), ("trigger", C.c_int32), ("extend", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgMaskSegment(C.Structure):
+    """struct kg_mask_segment."""
+    _fields_ = [("protein", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgMaskStats(C.Structure):
+    """struct kg_mask_stats."""
+    _fields_ = [("proteins", C.c_int64), ("residues", C.c_int64), ("windows", C.c_int64), ("low_windows", C.c_int64),
+                ("ext_windows", C.c_int64), ("masking_windows", C.c_int64), ("segments", C.c_int64), ("masked_residues", C.c_int64),
+                ("proteins_masked", C.c_int64), ("ms_mask", C.c_float), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 class KgVoteParams(C.Structure):
     """struct kg_vote_params (kg_result_otu_votes / kg_otu_votes_hits)."""
     _fields_ = [("min_votes", C.c_int32), ("min_share_pct", C.c_int32), ("min_calls", C.c_int32), ("reserved", C.c_int32)]
@@ -579,23 +610,34 @@ def load() -> C.CDLL:
     for name in ("kg_proteins_search_seeded", "kg_proteins_search_seeded_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgSearchParams), C.POINTER(KgSeedParams), C.POINTER(KgAlignParams), vp, vp,
                                        C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(vp)]
+    for name in ("kg_proteins_mask", "kg_proteins_mask_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgMaskParams), vp, vp, C.c_int64, C.POINTER(vp)]
+    for name in ("kg_maskset_stats", "kg_hitset_mask_stats", "kg_familyset_mask_stats"):
+        getattr(lib, name).argtypes = [vp, C.POINTER(KgMaskStats)]
+    for name in ("kg_proteins_search_masked", "kg_proteins_search_masked_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgSearchParams), C.POINTER(KgSeedParams), C.POINTER(KgAlignParams), vp, vp,
+                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(KgMaskParams), C.c_int,
+                                       C.POINTER(vp)]
+    for name in ("kg_proteins_cluster_masked", "kg_proteins_cluster_masked_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
+                                       C.POINTER(KgMaskParams), C.POINTER(vp)]
     # the sets' accessors, by signature: (set) -> count, (set) -> device address, (set, first, count, dst), (set, dst), (set)
-    for name in ("kg_sigset_count", "kg_familyset_count", "kg_familyset_edges_count", "kg_hitset_count", "kg_hitset_ops_count", "kg_opset_ops_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
+    for name in ("kg_sigset_count", "kg_familyset_count", "kg_familyset_edges_count", "kg_maskset_count", "kg_hitset_count", "kg_hitset_ops_count", "kg_opset_ops_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
                  "kg_selectset_count", "kg_voteset_count", "kg_voteset_bins", "kg_compset_rows", "kg_compset_models"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = C.c_int64
     for name in ("kg_sigset_device", "kg_regionset_device", "kg_orfset_device", "kg_selectset_device"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = vp
-    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_hitset_copy", "kg_hitset_paths_copy", "kg_hitset_op_starts_copy", "kg_hitset_ops_copy", "kg_opset_op_starts_copy", "kg_opset_ops_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
+    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_maskset_copy", "kg_maskset_flags_copy", "kg_hitset_copy", "kg_hitset_paths_copy", "kg_hitset_op_starts_copy", "kg_hitset_ops_copy", "kg_opset_op_starts_copy", "kg_opset_ops_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
                  "kg_orfset_junctions_copy", "kg_orfset_coding_scores", "kg_orfset_start_shifts", "kg_selectset_copy",
                  "kg_voteset_copy_votes", "kg_voteset_copy_classes", "kg_voteset_copy_bins", "kg_compset_copy_classes",
                  "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores"):
         getattr(lib, name).argtypes = [vp, C.c_int64, C.c_int64, vp]
     for name in ("kg_regionset_seq_start", "kg_orfset_prot_start", "kg_orfset_junctions_start", "kg_voteset_seq_start",
-                 "kg_compset_background", "kg_hitset_starts_copy"):
+                 "kg_compset_background", "kg_hitset_starts_copy", "kg_maskset_starts_copy"):
         getattr(lib, name).argtypes = [vp, vp]
-    for name in ("kg_sigset_free", "kg_familyset_free", "kg_hitset_free", "kg_opset_free", "kg_regionset_free", "kg_orfset_free", "kg_selectset_free",
+    for name in ("kg_sigset_free", "kg_familyset_free", "kg_maskset_free", "kg_hitset_free", "kg_opset_free", "kg_regionset_free", "kg_orfset_free", "kg_selectset_free",
                  "kg_voteset_free", "kg_compset_free"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = None

@@ -5,6 +5,7 @@
                                                 [--min-cover 20] [--min-size 2] [--all] [-A annotations.tsv] [--known known.tsv]
                                                 [--align [--min-ratio 50] [--align-ref longer|member] [--gap-open 11]
                                                  [--gap-extend 1] [--max-cells N] [--edges edges.tsv]]
+                                                [--mask [--mask-window 12] [--mask-trigger 563] [--mask-extend 640]]
 
 The proteins of all -p files form one batch, in the order given (FASTA as make_signatures reads it); a protein id that occurs
 twice, in one file or across files, is an error.  include/kmerguts_hip.h states the rule: every protein of a k-mer is linked to
@@ -30,6 +31,11 @@ or when that pair was not aligned.
 (0 without one).
 -A writes make_signatures' annotation format, `protein_id<TAB>function`: first the lines of --known, copied unchanged, then for
 each protein absent from --known and in a family of at least --min-size one line `id<TAB>hypothetical protein family_<root id>`.
+--mask keeps low-complexity segments (a poly-Q, a QEQEQE linker, a charged tail) from linking proteins (kg_proteins_cluster_masked;
+mask_proteins states the rule and writes the same mask to a file): the 8-mer pass reads every protein with its masked residues
+taken for non-residues, so a protein's distinct 8-mers in --min-cover are those outside its segments; --align reads the proteins
+as they are.  --mask-window, --mask-trigger and --mask-extend are mask_proteins' --window, --trigger and --extend.  The summary
+line then gains `, mask: W/T/E, masked residues: N`; without --mask every byte is as before.
 """
 from __future__ import annotations
 
@@ -113,9 +119,10 @@ def format_annotations(ids, rec, known: bytes = b"", min_size: int = 2, known_na
 
 def cluster_proteins(proteins, out: str, min_shared: int = 5, min_cover: int = 20, min_size: int = 2, write_all: bool = False,
                      annotations: Optional[str] = None, known: Optional[str] = None, device: int = 0, cluster=None,
-                     align: Optional[dict] = None, edges: Optional[str] = None) -> str:
+                     align: Optional[dict] = None, edges: Optional[str] = None, mask: Optional[dict] = None) -> str:
     """Write the files; returns the summary line.  `cluster` replaces hotpath.cluster_proteins (tests).  align: None, or the
-    alignment parameters of hotpath.cluster_proteins; edges: the --edges file."""
+    alignment parameters of hotpath.cluster_proteins; edges: the --edges file; mask: None, or a dict of window, trigger, extend as
+    hotpath.cluster_proteins takes it (--mask)."""
     if min_size < 1:
         raise ValueError("--min-size must be >= 1")
     if edges is not None and align is None:
@@ -129,10 +136,11 @@ def cluster_proteins(proteins, out: str, min_shared: int = 5, min_cover: int = 2
     if cluster is None:
         from . import hotpath
         cluster = hotpath.cluster_proteins
+    more = {} if mask is None else {"mask": mask}
     if align is None:
-        rec, st = cluster(b"".join(seqs), offsets, min_shared=min_shared, min_cover_pct=min_cover, device=device)
+        rec, st = cluster(b"".join(seqs), offsets, min_shared=min_shared, min_cover_pct=min_cover, device=device, **more)
     else:
-        rec, st = cluster(b"".join(seqs), offsets, min_shared=min_shared, min_cover_pct=min_cover, device=device, align=align)
+        rec, st = cluster(b"".join(seqs), offsets, min_shared=min_shared, min_cover_pct=min_cover, device=device, align=align, **more)
     with open(out, "wb") as f:
         f.write(format_families(ids, rec, min_size, write_all, st["edge_records"] if align is not None else None))
     if edges is not None:
@@ -147,6 +155,9 @@ def cluster_proteins(proteins, out: str, min_shared: int = 5, min_cover: int = 2
     if align is not None:
         a = st["align"]
         line += ", aligned: %d, cut: %d, skipped: %d, align ms: %.3f" % (a["aligned"], a["cut"], a["skipped"], a.get("ms_align", 0.0))
+    if mask is not None:
+        from .mask_proteins import mask_words
+        line += ", mask: %s, masked residues: %d" % (mask_words(mask), st["mask"]["masked_residues"])
     return line
 
 
@@ -169,12 +180,16 @@ def main(argv=None) -> int:
     ap.add_argument("--gap-extend", type=int, default=1, help="(default 1)")
     ap.add_argument("--max-cells", type=int, default=1 << 26, help="with --align: a pair of more cells is not aligned and its link kept (default 2^26)")
     ap.add_argument("--edges", default=None, metavar="EDGES", help="with --align: write one line per link that passed the 8-mer tests")
+    ap.add_argument("--mask", action="store_true", help="keep low-complexity segments out of the 8-mer pass (mask_proteins states the rule)")
+    from .mask_proteins import add_mask_options, mask_from_options
+    add_mask_options(ap, "--align reads the proteins as they are")
     a = ap.parse_args(argv)
     from . import _native as N
     align = dict(min_ratio_pct=a.min_ratio, ref=a.align_ref, gap_open=a.gap_open, gap_extend=a.gap_extend,
                  max_cells=a.max_cells) if a.align else None
     try:
-        line = cluster_proteins(a.p, a.o, a.min_shared, a.min_cover, a.min_size, a.all, a.A, a.known, align=align, edges=a.edges)
+        line = cluster_proteins(a.p, a.o, a.min_shared, a.min_cover, a.min_size, a.all, a.A, a.known, align=align, edges=a.edges,
+                                mask=mask_from_options(ap, a, None))
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1

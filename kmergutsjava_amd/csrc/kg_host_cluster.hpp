@@ -1,6 +1,7 @@
 // kg_host_cluster.hpp -- kg_proteins_cluster / kg_proteins_cluster_device: proteins -> families by shared 8-mers (kernels:
 // kg_cluster.hpp; the window encode, the sort and the collapse are the derive call's, kg_derive.hpp).
 // kg_proteins_cluster_aligned / _device: the same with the alignment step of kg_host_align.hpp between the edge test and the rounds.
+// kg_proteins_cluster_masked / _device: either of them with the window kernels reading the seeding copy of kg_host_mask.hpp.
 // Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_derive.hpp (its front half is that file's: the block
 // counts, the staging, the histogram, the one-pass cap and the window-pairs pass) and kg_host_align.hpp.
 #pragma once
@@ -15,15 +16,18 @@ struct kg_familyset {
     Detached d_edges;                   // n_edges * 32 bytes
     int64_t n_edges = 0;
     kg_align_stats ast = {};
+    bool has_mask = false;              // kg_proteins_cluster_masked only: the statistics of the mask behind the seeding copy
+    kg_mask_stats mst = {};
 };
 
 static_assert(sizeof(kg_family) == 16 && sizeof(kg_cluster_params) == 12, "record layouts of include/kmerguts_hip.h");
 
 namespace {
 
-// al: null for kg_proteins_cluster; else the links that pass the 8-mer tests are aligned and the cut ones lose their edge
+// al: null for kg_proteins_cluster; else the links that pass the 8-mer tests are aligned and the cut ones lose their edge.
+// mask: null for no masking; else the window kernels read the seeding copy of kg_host_mask.hpp, the alignment the original
 int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq_in,
-                 const int64_t *offsets, int64_t n_prot, int64_t max_windows, kg_familyset *set)
+                 const int64_t *offsets, int64_t n_prot, int64_t max_windows, kg_familyset *set, const MaskPlan *mask = nullptr)
 {
     set->aligned = al != nullptr;
     kg_cluster_stats &st = set->st;
@@ -51,11 +55,18 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_param
         HIP_TRY(hipEventRecord(ev[5], s));
         HIP_TRY(hipStreamSynchronize(s));
         st.ms_total = ev.ms(0, 5);
+        set->has_mask = mask != nullptr;
         return KG_OK;
     }
 
+    const uint8_t *d_seed = d_seq;
+    if (mask) {
+        if ((rc = mask_seeding_copy(t, sc, *mask, d_seq, offsets, 0, n_prot, (uint64_t)offsets[n_prot], &d_seed, &set->mst))) return rc;
+        set->has_mask = true;
+    }
+
     // ---- per-protein arrays, the window blocks ----
-    Deriver dv{t, sc, d_seq};
+    Deriver dv{t, sc, d_seed};
     dv.ev[0] = ev[6]; dv.ev[1] = ev[7];
     int64_t *d_off = nullptr;
     uint32_t *rank_of = nullptr, *parent = nullptr, *d_cnt = nullptr, *size = nullptr, *root = nullptr, *rflag = nullptr,
@@ -234,7 +245,8 @@ int cluster_impl(kg_table *t, const kg_cluster_params *prm, const kg_align_param
 }
 
 int cluster_entry(int device, const kg_cluster_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq,
-                  const int64_t *offsets, int64_t n_prot, int64_t max_windows, kg_familyset **out)
+                  const int64_t *offsets, int64_t n_prot, int64_t max_windows, kg_familyset **out,
+                  std::optional<const kg_mask_params *> mask = std::nullopt)
 {
     if (!out) return fail(KG_ERR_ARG, "null argument");
     *out = nullptr;
@@ -243,6 +255,8 @@ int cluster_entry(int device, const kg_cluster_params *prm, const kg_align_param
     if (prm->min_cover_pct < 0 || prm->min_cover_pct > 100) return fail(KG_ERR_ARG, "min_cover_pct must be in 0..100");
     if (prm->reserved != 0) return fail(KG_ERR_ARG, "kg_cluster_params.reserved must be 0");
     if (al) if (int rc = align_check_params(al)) return rc;
+    MaskPlan mplan;
+    if (mask) if (int rc = mask_plan(*mask, &mplan)) return rc;
     if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
     if (n_prot < 0) return fail(KG_ERR_ARG, "n_prot < 0");
     if (n_prot >= (1ll << 29)) return fail(KG_ERR_LIMIT, "2^29 or more proteins in one call");
@@ -257,7 +271,7 @@ int cluster_entry(int device, const kg_cluster_params *prm, const kg_align_param
     if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
     set->device = device;
     int rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
-    if (!rc) rc = cluster_impl(cs.t, prm, al, h_seq, d_seq, offsets, n_prot, max_windows, set);
+    if (!rc) rc = cluster_impl(cs.t, prm, al, h_seq, d_seq, offsets, n_prot, max_windows, set, mask ? &mplan : nullptr);
     cs.t->cache.release_all();                          // scratch goes back to the driver
     if (rc) { std::string keep = g_err; kg_familyset_free(set); g_err = keep; return rc; }
     if (getenv("KG_DEBUG"))
@@ -296,6 +310,25 @@ int kg_proteins_cluster_aligned_device(int device, const kg_cluster_params *p, c
                                        const int64_t *offsets, int64_t n_prot, int64_t max_windows, kg_familyset **out)
 {
     return cluster_entry(device, p, align, nullptr, d_seq, offsets, n_prot, max_windows, out);
+}
+
+int kg_proteins_cluster_masked(int device, const kg_cluster_params *p, const kg_align_params *align, const uint8_t *seq,
+                               const int64_t *offsets, int64_t n_prot, int64_t max_windows, const kg_mask_params *mask, kg_familyset **out)
+{
+    return cluster_entry(device, p, align, seq, nullptr, offsets, n_prot, max_windows, out, mask);
+}
+
+int kg_proteins_cluster_masked_device(int device, const kg_cluster_params *p, const kg_align_params *align, const uint8_t *d_seq,
+                                      const int64_t *offsets, int64_t n_prot, int64_t max_windows, const kg_mask_params *mask,
+                                      kg_familyset **out)
+{
+    return cluster_entry(device, p, align, nullptr, d_seq, offsets, n_prot, max_windows, out, mask);
+}
+
+int kg_familyset_mask_stats(const kg_familyset *s, kg_mask_stats *out)
+{
+    if (s && !s->has_mask) return fail(KG_ERR_ARG, "kg_familyset_mask_stats: the set was made without a mask");
+    return copy_stats(s, s ? &s->mst : nullptr, out);
 }
 
 int64_t kg_familyset_count(const kg_familyset *s) { return s ? s->count : 0; }

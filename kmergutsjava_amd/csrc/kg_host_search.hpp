@@ -3,6 +3,8 @@
 // kg_derive.hpp; the alignment is align_run of kg_host_align.hpp, unchanged), and kg_proteins_search_paths, which traces the
 // ordered records behind it (trace_run of kg_host_trace.hpp).  kg_proteins_search_seeded is the same call with the window kernel
 // of kg_seed.hpp in the derive kernel's place: seed ids of a reduced alphabet and spaced shapes where the exact call has 8-mers.
+// kg_proteins_search_masked is either call with the window kernels reading the seeding copy of kg_host_mask.hpp (the masked
+// residues of one or both sides turned into non-residues); the alignment and the trace read the original.
 // search_impl is a driver over three stages: search_pairs (the front half the cluster call has too, by the functions of
 // kg_host_derive.hpp: staging, block counts, count pass, one-pass cap, window-pairs pass), search_candidates (the join and the
 // per-query cut) and search_finish (the result block, the alignment, the order, the statistics, the paths).
@@ -22,6 +24,8 @@ struct kg_hitset {
     int64_t ops_count = 0;
     bool has_ops = false;
     float ms_ops = 0;
+    bool has_mask = false;              // kg_proteins_search_masked only: the statistics of the mask behind the seeding copy
+    kg_mask_stats mst = {};
     const int64_t *op_starts() const { return (const int64_t *)d_ops.p; }
     const uint32_t *ops() const { return (const uint32_t *)(d_ops.p + ((size_t)count + 1) * 8); }
     const int64_t *starts() const { return (const int64_t *)d_block.p; }
@@ -175,7 +179,8 @@ int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, con
     return KG_OK;
 }
 
-// a checked call.  seed: null for the exact 8-mers; ask.trace = 0: no paths
+// a checked call.  seed: null for the exact 8-mers; ask.trace = 0: no paths; mask: null for no masking, else `sides` says whose
+// residues the seeding copy masks (KG_MASK_QUERIES | KG_MASK_TARGETS)
 struct SearchArgs {
     const kg_search_params *prm;
     const kg_align_params *al;
@@ -184,6 +189,8 @@ struct SearchArgs {
     int64_t n_prot, n_db, max_windows, max_pairs;
     SearchPathsAsk ask;
     const SeedPlan *seed;
+    const MaskPlan *mask;
+    int sides;
 };
 
 // what search_impl sets up for its stages: they allocate from sc, enqueue on t->stream and record the timing events ev[1 .. 5]
@@ -194,6 +201,7 @@ struct SearchCall {
     Scratch &sc;
     const Events<8> &ev;
     const uint8_t *d_seq = nullptr;
+    const uint8_t *d_seed = nullptr;            // what the window kernels read: d_seq, or under a mask its seeding copy
     unsigned long long *words = nullptr;        // kSearchWords counters, zeroed
     uint64_t *d_tot = nullptr;                  // the totals of the eight prefix sums
 };
@@ -219,7 +227,7 @@ int search_pairs(SearchCall &c, SearchPairs *out)
     if ((rc = a.seed ? seed_block_bases(a.offsets, a.n_prot, a.seed->span_min, ibase, &nblocks)
                      : derive_block_bases(a.offsets, a.n_prot, ibase, &nblocks, &windows)))
         return rc;
-    Deriver dv{c.t, c.sc, c.d_seq};
+    Deriver dv{c.t, c.sc, c.d_seed};
     dv.ev[0] = c.ev[6]; dv.ev[1] = c.ev[7];
     uint32_t *rank_of = nullptr;
     if ((rc = c.sc.get(&dv.d_bins, kg::kDeriveBins)) || (rc = dv.window_blocks(a.offsets, ibase, a.n_prot, nblocks, &out->d_off)) ||
@@ -463,6 +471,14 @@ int search_impl(kg_table *t, const SearchArgs &a, kg_hitset *set)
     HIP_TRY(hipEventRecord(ev[0], s));
     if ((rc = sc.get(&c.words, kg::kSearchWords)) || (rc = sc.get(&c.d_tot, 8))) return rc;
     HIP_TRY(hipMemsetAsync(c.words, 0, kg::kSearchWords * 8, s));
+    c.d_seed = c.d_seq;
+    if (a.mask) {                               // the masked side's proteins: the targets [0, n_db), the queries [n_db, n_prot), or all
+        const int64_t p0 = a.sides & KG_MASK_TARGETS ? 0 : a.n_db, p1 = a.sides & KG_MASK_QUERIES ? a.n_prot : a.n_db;
+        if ((rc = mask_seeding_copy(t, sc, *a.mask, c.d_seq, a.offsets, p0, p1, a.n_prot ? (uint64_t)a.offsets[a.n_prot] : 0, &c.d_seed,
+                                    &set->mst)))
+            return rc;
+        set->has_mask = true;
+    }
     // the times of a call that ends early: every stage it did not reach is empty (a stage that is reached records its events again)
     for (int k = 1; k <= 4; k++) HIP_TRY(hipEventRecord(ev[k], s));
     SearchPairs pairs;
@@ -475,7 +491,8 @@ int search_impl(kg_table *t, const SearchArgs &a, kg_hitset *set)
 // seeds: no value for the exact call; of a seeded call the caller's pointer, checked here
 int search_entry(int device, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq,
                  const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset **out,
-                 SearchPathsAsk ask = {}, std::optional<const kg_seed_params *> seeds = std::nullopt)
+                 SearchPathsAsk ask = {}, std::optional<const kg_seed_params *> seeds = std::nullopt,
+                 std::optional<const kg_mask_params *> mask = std::nullopt, int sides = 0)
 {
     if (!out) return fail(KG_ERR_ARG, "null argument");
     *out = nullptr;
@@ -487,6 +504,11 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     SeedPlan plan;
     if (seeds)
         if (int rc = seed_plan(*seeds, &plan)) return rc;
+    MaskPlan mplan;
+    if (mask) {
+        if (int rc = mask_plan(*mask, &mplan)) return rc;
+        if (sides < 1 || sides > (KG_MASK_QUERIES | KG_MASK_TARGETS)) return fail(KG_ERR_ARG, "sides must be KG_MASK_QUERIES, KG_MASK_TARGETS or both");
+    }
     if (!al) return fail(KG_ERR_ARG, "null kg_align_params");
     if (int rc = align_check_params(al)) return rc;
     if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
@@ -507,7 +529,7 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     kg_hitset *set = new (std::nothrow) kg_hitset();
     if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
     set->device = device;
-    const SearchArgs args{prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, ask, seeds ? &plan : nullptr};
+    const SearchArgs args{prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, ask, seeds ? &plan : nullptr, mask ? &mplan : nullptr, sides};
     int rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
     if (!rc) rc = search_impl(cs.t, args, set);
     cs.t->cache.release_all();                          // scratch goes back to the driver
@@ -591,6 +613,30 @@ int kg_proteins_search_seeded_device(int device, const kg_search_params *p, cons
                                      int64_t max_pairs, int trace, int64_t max_trace_cells, kg_hitset **out)
 {
     return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, {trace, max_trace_cells}, seeds);
+}
+
+// (seeds = NULL: the exact 8-mers, as kg_proteins_search_paths with trace = 0 allowed)
+int kg_proteins_search_masked(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                              const uint8_t *seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                              int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides, kg_hitset **out)
+{
+    return search_entry(device, p, align, seq, nullptr, offsets, n_prot, n_db, max_windows, max_pairs, out, {trace, max_trace_cells},
+                        seeds ? std::optional<const kg_seed_params *>(seeds) : std::nullopt, mask, sides);
+}
+
+int kg_proteins_search_masked_device(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                                     const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                                     int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides,
+                                     kg_hitset **out)
+{
+    return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, {trace, max_trace_cells},
+                        seeds ? std::optional<const kg_seed_params *>(seeds) : std::nullopt, mask, sides);
+}
+
+int kg_hitset_mask_stats(const kg_hitset *s, kg_mask_stats *out)
+{
+    if (s && !s->has_mask) return fail(KG_ERR_ARG, "kg_hitset_mask_stats: the set was made without a mask");
+    return copy_stats(s, s ? &s->mst : nullptr, out);
 }
 
 int64_t kg_hitset_count(const kg_hitset *s) { return s ? s->count : 0; }

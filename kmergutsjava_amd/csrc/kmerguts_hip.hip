@@ -20,6 +20,7 @@
 #include "kg_ops.hpp"
 #include "kg_search.hpp"
 #include "kg_seed.hpp"
+#include "kg_mask.hpp"
 #include "kg_assign.hpp"
 #include "kg_regions.hpp"
 #include "kg_orfs.hpp"
@@ -52,6 +53,7 @@
 #include "kg_host_merge.hpp"
 #include "kg_host_align.hpp"
 #include "kg_host_trace.hpp"
+#include "kg_host_mask.hpp"
 #include "kg_host_cluster.hpp"
 #include "kg_host_search.hpp"
 #include "kg_host_assign.hpp"

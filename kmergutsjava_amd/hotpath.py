@@ -864,8 +864,52 @@ def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1,
     return out
 
 
+def _mask_params(mask, sides_too: bool = False):
+    """mask= of search_proteins / cluster_proteins: None -> None; True or a dict of window, trigger, extend (and, with sides_too,
+    sides: "both" | "queries" | "targets") -> (KgMaskParams, KG_MASK_* sides)."""
+    if mask is None or mask is False:
+        return None
+    m = {} if mask is True else dict(mask)
+    sides = m.pop("sides", "both") if sides_too else "both"
+    unknown = set(m) - {"window", "trigger", "extend"}
+    if unknown:
+        raise ValueError("mask takes window, trigger, extend%s: not %s" % (" and sides" if sides_too else "", ", ".join(sorted(unknown))))
+    if sides not in N.MASK_SIDES:
+        raise ValueError("mask sides must be 'both', 'queries' or 'targets'")
+    return N.KgMaskParams(int(m.get("window", N.MASK_WINDOW)), int(m.get("trigger", N.MASK_TRIGGER)),
+                          int(m.get("extend", N.MASK_EXTEND)), 0), N.MASK_SIDES[sides]
+
+
+def mask_proteins(seq, offsets, window: int = N.MASK_WINDOW, trigger: int = N.MASK_TRIGGER, extend: int = N.MASK_EXTEND, device: int = 0,
+                  device_ptr: Optional[int] = None):
+    """The low-complexity segments of proteins, on the GPU (include/kmerguts_hip.h kg_proteins_mask states the rule: SEG's trigger
+    window and extension, in Lg's integers).  seq / offsets / device_ptr as for cluster_proteins; the thresholds are in units of
+    1/256 bit, and the defaults 12, 563 and 640 (SEG's 2.2 and 2.5 bits) are this project's choice.
+    -> (flags uint8[offsets[-1] - offsets[0]], one 0/1 per residue; segments _native.MASK_SEGMENT_DTYPE in (protein, start) order,
+    0-based and inclusive; seg_start int64[n_prot + 1]; the call's statistics)."""
+    off = _offsets(offsets, "int64[n_prot + 1]")
+    n = off.size - 1
+    p = N.KgMaskParams(int(window), int(trigger), int(extend), 0)
+    h = C.c_void_p()
+    lib = N.load()
+    if device_ptr is not None:
+        N.check(lib.kg_proteins_mask_device(device, C.byref(p), C.c_void_p(device_ptr), off.ctypes.data, n, C.byref(h)))
+    else:
+        arr = _seq_bytes(seq, off)
+        N.check(lib.kg_proteins_mask(device, C.byref(p), _ptr(arr), off.ctypes.data, n, C.byref(h)))
+    try:
+        st = N.KgMaskStats()
+        N.check(lib.kg_maskset_stats(h, C.byref(st)))
+        starts = np.zeros(n + 1, dtype=np.int64)
+        N.check(lib.kg_maskset_starts_copy(h, starts.ctypes.data))
+        return (_copy_records(lib.kg_maskset_flags_copy, h, int(st.residues), np.uint8),
+                _copy_records(lib.kg_maskset_copy, h, int(lib.kg_maskset_count(h)), N.MASK_SEGMENT_DTYPE), starts, st.as_dict())
+    finally:
+        lib.kg_maskset_free(h)
+
+
 def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20, max_windows: int = 0, device: int = 0,
-                     device_ptr: Optional[int] = None, align: Optional[dict] = None):
+                     device_ptr: Optional[int] = None, align: Optional[dict] = None, mask=None):
     """Proteins -> families by shared 8-mers, on the GPU (include/kmerguts_hip.h kg_proteins_cluster states the rule): a link
     from every protein of a k-mer to the k-mer's longest protein, an edge where a link's shared k-mers pass min_shared and
     min_cover_pct of the member's distinct k-mers, a family per connected component.  seq: bytes / uint8 ndarray of the
@@ -875,13 +919,29 @@ def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20,
     matrix (None: BLOSUM62): every link that passed the two tests is aligned (kg_proteins_cluster_aligned) and stays an edge
     only if 100 * score >= min_ratio_pct * ref; the statistics then also hold "edge_records" (_native.FAMILY_EDGE_DTYPE, one per
     such link in (member, centre) order) and "align" (aligned, cut, skipped, cells, ms_align).
+    mask: None, True (the defaults of mask_proteins) or a dict of window, trigger, extend: the 8-mer pass reads a copy of the
+    proteins in which the low-complexity segments are no residues (kg_proteins_cluster_masked; the alignment reads the original);
+    the statistics then also hold "mask" (the statistics of mask_proteins).
     -> (numpy records of _native.FAMILY_DTYPE in protein order, the call's statistics)."""
     off = _offsets(offsets, "int64[n_prot + 1]")
     n = off.size - 1
     p = N.KgClusterParams(int(min_shared), int(min_cover_pct), 0)
     h = C.c_void_p()
     lib = N.load()
-    if align is not None:
+    mp = _mask_params(mask)
+    if mp is not None:
+        ap = None
+        if align is not None:
+            ap, _keep = _align_params(**align)
+        apr = C.byref(ap) if ap is not None else None
+        if device_ptr is not None:
+            N.check(lib.kg_proteins_cluster_masked_device(device, C.byref(p), apr, C.c_void_p(device_ptr), off.ctypes.data, n,
+                                                          int(max_windows), C.byref(mp[0]), C.byref(h)))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_proteins_cluster_masked(device, C.byref(p), apr, _ptr(arr), off.ctypes.data, n, int(max_windows),
+                                                   C.byref(mp[0]), C.byref(h)))
+    elif align is not None:
         ap, _keep = _align_params(**align)
         if device_ptr is not None:
             N.check(lib.kg_proteins_cluster_aligned_device(device, C.byref(p), C.byref(ap), C.c_void_p(device_ptr), off.ctypes.data, n,
@@ -905,6 +965,10 @@ def cluster_proteins(seq, offsets, min_shared: int = 5, min_cover_pct: int = 20,
             N.check(lib.kg_familyset_align_stats(h, C.byref(ast)))
             stats["align"] = ast.as_dict()
             stats["edge_records"] = _copy_records(lib.kg_familyset_edges_copy, h, int(lib.kg_familyset_edges_count(h)), N.FAMILY_EDGE_DTYPE)
+        if mp is not None:
+            mst = N.KgMaskStats()
+            N.check(lib.kg_familyset_mask_stats(h, C.byref(mst)))
+            stats["mask"] = mst.as_dict()
         return _copy_records(lib.kg_familyset_copy, h, int(lib.kg_familyset_count(h)), N.FAMILY_DTYPE), stats
     finally:
         lib.kg_familyset_free(h)
@@ -923,7 +987,7 @@ def _seed_params(seeds):
 def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256,
                     align: Optional[dict] = None, max_windows: int = 0, max_pairs: int = 0, device: int = 0,
                     device_ptr: Optional[int] = None, paths: Optional[str] = None, max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS,
-                    seeds=None, ops: Optional[str] = None):
+                    seeds=None, ops: Optional[str] = None, mask=None):
     """Proteins [n_db, n_prot) searched against proteins [0, n_db), on the GPU (include/kmerguts_hip.h kg_proteins_search states
     the rule): the targets that share at least min_shared distinct unmasked 8-mers with a query, the max_cand with the most
     aligned, a hit where 100 * score >= min_ratio_pct * ref.  seq / offsets / device_ptr as for cluster_proteins; align: None
@@ -937,7 +1001,10 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
     dict(alphabet="identity" | "reduced11" | "AST,C,DEKNQR,...", shapes=["1111...", ...]) as seeds.py reads it:
     kg_proteins_search_seeded, the same results with "seed id" read for "8-mer".
     ops: None, "m" or "eqx" (needs paths): the traced records' ops as in align_proteins; -> (records, hit_start, path records,
-    statistics, op_start int64[count + 1], ops), the statistics with ops and ms_ops as well."""
+    statistics, op_start int64[count + 1], ops), the statistics with ops and ms_ops as well.
+    mask: None, True (the defaults of mask_proteins) or a dict of window, trigger, extend and sides ("both", the default,
+    "queries" or "targets"): the seeding pass reads a copy in which that side's low-complexity segments are no residues
+    (kg_proteins_search_masked); the alignment, the trace and the ops read the original.  The statistics then also hold "mask"."""
     if paths is not None and paths not in N.TRACE_MODES:
         raise ValueError("paths must be None, 'hits' or 'all'")
     if ops is not None and ops not in N.OPS_MODES:
@@ -952,7 +1019,17 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
     ap, _keep = _align_params(**(align or {}))
     h = C.c_void_p()
     lib = N.load()
-    if seed_set is not None:
+    mp = _mask_params(mask, sides_too=True)
+    if mp is not None:
+        sp = C.byref(seed_set) if seed_set is not None else None
+        tail = (int(max_windows), int(max_pairs), trace, int(max_trace_cells), C.byref(mp[0]), mp[1], C.byref(h))
+        if device_ptr is not None:
+            N.check(lib.kg_proteins_search_masked_device(device, C.byref(p), sp, C.byref(ap), C.c_void_p(device_ptr), off.ctypes.data, n,
+                                                         int(n_db), *tail))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_proteins_search_masked(device, C.byref(p), sp, C.byref(ap), _ptr(arr), off.ctypes.data, n, int(n_db), *tail))
+    elif seed_set is not None:
         tail = (int(max_windows), int(max_pairs), trace, int(max_trace_cells), C.byref(h))
         if device_ptr is not None:
             N.check(lib.kg_proteins_search_seeded_device(device, C.byref(p), C.byref(seed_set), C.byref(ap), C.c_void_p(device_ptr),
@@ -981,10 +1058,15 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
         N.check(lib.kg_hitset_stats(h, C.byref(st)))
         starts = np.zeros(int(st.queries) + 1, dtype=np.int64)
         N.check(lib.kg_hitset_starts_copy(h, starts.ctypes.data))
+        more = {}
+        if mp is not None:
+            mst = N.KgMaskStats()
+            N.check(lib.kg_hitset_mask_stats(h, C.byref(mst)))
+            more["mask"] = mst.as_dict()
         if paths is not None:
             tst = N.KgTraceStats()
             N.check(lib.kg_hitset_trace_stats(h, C.byref(tst)))
-            stats = dict(st.as_dict(), traced=tst.traced, untraced=tst.untraced, trace_cells=tst.cells, ms_trace=tst.ms_trace)
+            stats = dict(st.as_dict(), traced=tst.traced, untraced=tst.untraced, trace_cells=tst.cells, ms_trace=tst.ms_trace, **more)
             count = int(lib.kg_hitset_count(h))
             got = (_copy_records(lib.kg_hitset_copy, h, count, N.SEARCH_HIT_DTYPE), starts,
                    _copy_records(lib.kg_hitset_paths_copy, h, count, N.ALIGN_PATH_DTYPE), stats)
@@ -994,7 +1076,7 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
                 stats.update(ops=int(lib.kg_hitset_ops_count(h)), ms_ops=ms.value)
                 got += _copy_ops(lib.kg_hitset_ops_count, lib.kg_hitset_op_starts_copy, lib.kg_hitset_ops_copy, h, count)
             return got
-        return _copy_records(lib.kg_hitset_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_HIT_DTYPE), starts, st.as_dict()
+        return _copy_records(lib.kg_hitset_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_HIT_DTYPE), starts, dict(st.as_dict(), **more)
     finally:
         lib.kg_hitset_free(h)
 

@@ -8,6 +8,7 @@ how much.  The step that names what `annotate` leaves at `none`.
                                                [--truth query_annotations.tsv]
                                                [--paths [--trace hits|all] [--max-trace-cells N] [--cigar [m|eqx]] [--alignments FILE]]
                                                [--seeds exact|reduced] [--alphabet identity|reduced11|GROUPS] [--shape MASK ...]
+                                               [--mask [both|queries|targets]] [--mask-window 12] [--mask-trigger 563] [--mask-extend 640]
 
 The proteins of all -d files are the database, those of all -q files the queries, each in the order given (FASTA as
 make_signatures reads it).  An id that occurs twice within the database or within the queries is an error; the same id in both
@@ -53,6 +54,13 @@ keeps a seed), and everything behind it, --min-shared and --max-db-per-kmer incl
 32 long, first and last 1; up to four, all with the same number of 1) each replace that part of the chosen seed set.  The
 built-in set is this project's choice and is not tuned.  The summary line then gains `, seeds: <alphabet> x <shape,shape>`;
 nothing else in any output changes, and with --seeds exact and neither override every byte is as before.
+--mask keeps low-complexity segments (a poly-Q, a QEQEQE linker, a charged tail) from seeding candidates
+(kg_proteins_search_masked; mask_proteins states the rule and writes the same mask to a file): the prefilter, and nothing else,
+reads the proteins with the masked residues taken for non-residues; the alignment, --paths and --cigar read the proteins as they
+are, so a hit's score is what it is without --mask.  --mask both (the default of the flag) masks the database and the queries,
+--mask queries or --mask targets one side.  --mask-window, --mask-trigger and --mask-extend are mask_proteins' --window, --trigger
+and --extend.  Under a spaced shape a masked residue on a `0` position keeps the seed.  The summary line then gains `, mask:
+W/T/E <sides>, masked residues: N`; without --mask every byte is as before.
 The summary line goes to stderr.
 """
 from __future__ import annotations
@@ -181,12 +189,13 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
                     align: Optional[dict] = None, write_all: bool = False, annotations: Optional[str] = None,
                     transfer: Optional[str] = None, truth: Optional[str] = None, device: int = 0, search=None,
                     paths: Optional[str] = None, max_trace_cells: Optional[int] = None, seeds=None, cigar: Optional[str] = None,
-                    alignments: Optional[str] = None) -> str:
+                    alignments: Optional[str] = None, mask: Optional[dict] = None) -> str:
     """Write the files; returns the summary line.  `search` replaces hotpath.search_proteins (tests).  align: None, or the
     alignment parameters of hotpath.search_proteins (ref "query" is its "member").  paths: None, "hits" or "all" (--paths with
     its --trace); max_trace_cells: None for the library's default.  seeds: None (the exact 8-mers), "reduced" or a
     dict(alphabet=..., shapes=[...]) as hotpath.search_proteins takes it.  cigar: None, "m" or "eqx" (--cigar); alignments: None
-    or the file --alignments writes; both need paths."""
+    or the file --alignments writes; both need paths.  mask: None, or a dict of window, trigger, extend and sides as
+    hotpath.search_proteins takes it (--mask)."""
     from . import seeds as SD
     seed_words = SD.describe(seeds) if SD.resolve(seeds) is not None else None
     if paths not in (None, "hits", "all"):
@@ -219,6 +228,10 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
         search = hotpath.search_proteins
     recs = op_start = ops = None
     more = {} if seed_words is None else {"seeds": seeds}
+    if mask is not None:
+        if mask.get("sides", "both") not in ("both", "queries", "targets"):
+            raise ValueError("--mask must be both, queries or targets")
+        more["mask"] = mask
     if paths is None:
         hits, hit_start, st = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
                                      max_db_per_kmer=max_db_per_kmer, align=align, device=device, **more)
@@ -255,6 +268,9 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
         line += ", ops: %d" % len(ops)
     if seed_words is not None:
         line += ", seeds: " + seed_words
+    if mask is not None:
+        from .mask_proteins import mask_words
+        line += ", mask: %s, masked residues: %d" % (mask_words(mask, mask.get("sides", "both")), st["mask"]["masked_residues"])
     return line
 
 
@@ -292,6 +308,10 @@ def main(argv=None) -> int:
                     help="replaces the seed set's alphabet: comma-separated groups of residues, e.g. AST,C,DEKNQR,F,G,H,ILV,M,P,W,Y")
     ap.add_argument("--shape", action="append", default=None, metavar="MASK",
                     help="replaces the seed set's shapes: 1 = care, 0 = don't care, first and last 1; up to four, of equal weight")
+    ap.add_argument("--mask", nargs="?", const="both", choices=("both", "queries", "targets"), default=None,
+                    help="keep low-complexity segments out of the prefilter: of both sides (default of the flag), the queries or the targets")
+    from .mask_proteins import add_mask_options, mask_from_options
+    add_mask_options(ap, "the alignment reads the proteins as they are")
     a = ap.parse_args(argv)
     if a.shape is not None and len(a.shape) > 4:
         ap.error("at most 4 --shape")
@@ -312,7 +332,8 @@ def main(argv=None) -> int:
             seeds["shapes"] = a.shape
     try:
         line = search_proteins(a.d, a.q, a.o, a.min_shared, a.max_cand, a.max_hits, a.max_db_per_kmer, align, a.all, a.A, a.transfer,
-                               a.truth, paths=paths, max_trace_cells=a.max_trace_cells, seeds=seeds, cigar=a.cigar, alignments=a.alignments)
+                               a.truth, paths=paths, max_trace_cells=a.max_trace_cells, seeds=seeds, cigar=a.cigar, alignments=a.alignments,
+                               mask=mask_from_options(ap, a, a.mask))
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1
