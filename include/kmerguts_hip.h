@@ -886,6 +886,65 @@ int kg_proteins_cluster_masked_device(int device, const kg_cluster_params *p, co
                                       kg_familyset **out);
 int kg_familyset_mask_stats(const kg_familyset *s, kg_mask_stats *out);
 
+/* ---- the search's ungapped filter: candidates ranked by the score of their best seed diagonal (kernels: kg_ungapped.hpp) ----
+ *
+ * The shared count s(q, d) ranks poorly under a reduced alphabet: scattered chance seeds count as much as a collinear run.  This
+ * stage stands between the join and the alignment, opt-in: it chooses each candidate's best seed diagonal, scores that whole
+ * diagonal without gaps, and cuts by the score.  The rule is the project's own.  Integers only.
+ *   Position.  For a protein p and an unmasked seed id v, i_p(v) is the smallest valid window position of v in p.  Under a mask it
+ *   is taken in the masked copy, which has the same coordinates.
+ *   Diagonals.  For a candidate (q, d) with s(q, d) >= min_shared, every shared unmasked seed v has the diagonal
+ *   g(v) = i_q(v) - i_d(v).  m(g) is the number of shared seeds with that diagonal.  g* is the diagonal with the largest m, on a
+ *   tie the smallest g.  on_diagonal = m(g*).  The sum of m over all g is s(q, d).
+ *   Ungapped score.  The cells of diagonal g* are the pairs (a, a - g*) with 0 <= a < len_q and 0 <= a - g* < len_d, in
+ *   increasing a.  A cell's score is the alignment's own: kg_align_params.matrix, or BLOSUM62 when it is null.  It uses the
+ *   alignment's codes, every non-residue being code 20, and is read from the original sequence as the alignment reads it.
+ *   u(q, d) is the largest sum over a non-empty run of consecutive cells, and 0 if every run is negative.  No X-drop and no band:
+ *   the whole diagonal.  The result does not depend on launch geometry.
+ *   Consequence: for every aligned, not-skipped record, u <= score (the run is an alignment without gaps).
+ *   Cut.  A candidate with u < min_ungapped is dropped.  min_ungapped >= 0.  The default is 0, which drops nothing.  The
+ *   remaining candidates of a query are ordered by larger u, then larger s, then smaller d.  The first max_cand are aligned.
+ *   Alignment, hit test, output order within the query and the 40-byte kg_search_hit are unchanged.  kg_search_stats.candidates
+ *   still counts the pairs with s >= min_shared.
+ * kg_proteins_search_filtered / _device: kg_proteins_search_masked's arguments, with mask nullable as well (NULL: no mask, sides
+ * is not read), and the ungapped parameters.  A null `ungapped` is KG_ERR_ARG "null kg_ungapped_params"; so are
+ * "min_ungapped must be >= 0" and "kg_ungapped_params.reserved must be 0".  kg_hitset_ungapped_copy gives one 16-byte
+ * kg_search_ungapped per hit record, same index; kg_hitset_ungapped_stats the stage's counts: scored = candidates,
+ * scored = dropped + cut + the hit records.  ms_ungapped is the time of the scoring kernel; kg_search_stats.ms_join excludes it and
+ * ms_total includes it.  Both getters return KG_ERR_ARG for a set made by any other call.
+ * Limits (KG_ERR_LIMIT) beside the search's: the join key (q, d, g + bias) takes bits(n_q) + bits(n_db) + bits(longest query +
+ * longest target) bits, bits(n) being the bits that write every value below n; over 64 the call says which three widths do not
+ * fit.  The cut key takes bits(n_q) + the bits of the largest u + the bits of the largest s, and is refused over 64 likewise.
+ * max_pairs = 0 sizes the join at about 200 bytes per join pair on this path: per pair the sort's two sides 24, two levels of
+ * heads and scans 16, two levels of run starts 8 and the best-diagonal word 8; per candidate 32; per candidate kept by
+ * min_ungapped 68; per aligned candidate 28; 184 in all, and the sorts' histograms.
+ * The entry points above and their results are unchanged, byte for byte. */
+typedef struct kg_ungapped_params { int32_t min_ungapped; int32_t reserved[3]; } kg_ungapped_params;
+typedef struct kg_search_ungapped {   /* 16 B */
+    int32_t ungapped;      /* u(q, d)                                                   */
+    int32_t diagonal;      /* g*                                                        */
+    int32_t on_diagonal;   /* m(g*)                                                     */
+    int32_t reserved;
+} kg_search_ungapped;
+typedef struct kg_ungapped_stats {
+    int64_t scored;        /* candidates whose diagonal was scored: kg_search_stats.candidates */
+    int64_t dropped;       /* of them, those with u < min_ungapped                      */
+    int64_t cut;           /* of the rest, those behind the first max_cand of their query */
+    int64_t cells;         /* diagonal cells scored                                     */
+    float   ms_ungapped;   /* the scoring kernel                                        */
+    int32_t reserved;
+} kg_ungapped_stats;
+int kg_proteins_search_filtered(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                                const uint8_t *seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                                int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides,
+                                const kg_ungapped_params *ungapped, kg_hitset **out);
+int kg_proteins_search_filtered_device(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                                       const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                                       int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides,
+                                       const kg_ungapped_params *ungapped, kg_hitset **out);
+int kg_hitset_ungapped_copy(const kg_hitset *s, int64_t first, int64_t count, kg_search_ungapped *dst);
+int kg_hitset_ungapped_stats(const kg_hitset *s, kg_ungapped_stats *out);
+
 /* ---- assigning functions: the CALL records of an -a scan -> one function per protein (kernels: kg_assign.hpp) ----
  *
  * The reference stops at the CALL lines (KGJ:398-404, 526-536); this rule is the project's own.

@@ -481,6 +481,34 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_ungapped_params (kg_proteins_search_filtered*): a candidate whose best seed diagonal scores below min_ungapped
+     *  without gaps is not aligned; min_ungapped >= 0, default 0 (rank only); reserved 0. */
+    class KgUngappedParams extends Structure {
+        public int min_ungapped;
+        public int[] reserved = new int[3];
+        public KgUngappedParams() {
+            setFieldOrder(new String[] {"min_ungapped", "reserved"});
+        }
+    }
+
+    /** struct kg_search_ungapped (16 B): one per hit record of a filtered search, same index. */
+    class KgSearchUngapped extends Structure {
+        public int ungapped, diagonal, on_diagonal, reserved;
+        public KgSearchUngapped() {
+            setFieldOrder(new String[] {"ungapped", "diagonal", "on_diagonal", "reserved"});
+        }
+    }
+
+    /** struct kg_ungapped_stats. */
+    class KgUngappedStats extends Structure {
+        public long scored, dropped, cut, cells;
+        public float ms_ungapped;
+        public int reserved;
+        public KgUngappedStats() {
+            setFieldOrder(new String[] {"scored", "dropped", "cut", "cells", "ms_ungapped", "reserved"});
+        }
+    }
+
     /** struct kg_merge_params (kg_table_merge_signatures*): on_conflict = KG_MERGE_KEEP (0), KG_MERGE_REPLACE (1) or KG_MERGE_DROP (2). */
     class KgMergeParams extends Structure {
         public int on_conflict, reserved;
@@ -615,6 +643,17 @@ public interface KmerGutsHip extends Library {
                                          long[] offsets, long nProt, long nDb, long maxWindows, long maxPairs, int trace, long maxTraceCells,
                                          KgMaskParams mask, int sides, PointerByReference out);
     int kg_hitset_mask_stats(Pointer set, KgMaskStats out);
+    /** kg_proteins_search_masked (seeds and mask nullable) with the ungapped stage between the join and the alignment: each
+     *  candidate's best seed diagonal is scored without gaps, and the per-query cut is by (larger score, larger s, smaller target) */
+    int kg_proteins_search_filtered(int device, KgSearchParams params, KgSeedParams seeds, KgAlignParams align, byte[] seq, long[] offsets,
+                                    long nProt, long nDb, long maxWindows, long maxPairs, int trace, long maxTraceCells, KgMaskParams mask,
+                                    int sides, KgUngappedParams ungapped, PointerByReference out);
+    int kg_proteins_search_filtered_device(int device, KgSearchParams params, KgSeedParams seeds, KgAlignParams align, Pointer dSeq,
+                                           long[] offsets, long nProt, long nDb, long maxWindows, long maxPairs, int trace,
+                                           long maxTraceCells, KgMaskParams mask, int sides, KgUngappedParams ungapped,
+                                           PointerByReference out);
+    int kg_hitset_ungapped_copy(Pointer set, long first, long count, Pointer dst);   // kg_search_ungapped[count]
+    int kg_hitset_ungapped_stats(Pointer set, KgUngappedStats out);
     /** kg_proteins_cluster_aligned (align = null: no alignment step) with every protein soft-masked for the 8-mer pass */
     int kg_proteins_cluster_masked(int device, KgClusterParams params, KgAlignParams align, byte[] seq, long[] offsets, long nProt,
                                    long maxWindows, KgMaskParams mask, PointerByReference out);

@@ -51,6 +51,7 @@ EXPORTS = (
     "kg_maskset_flags_copy", "kg_maskset_stats", "kg_maskset_free",
     "kg_proteins_search_masked", "kg_proteins_search_masked_device", "kg_hitset_mask_stats",
     "kg_proteins_cluster_masked", "kg_proteins_cluster_masked_device", "kg_familyset_mask_stats",
+    "kg_proteins_search_filtered", "kg_proteins_search_filtered_device", "kg_hitset_ungapped_copy", "kg_hitset_ungapped_stats",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
@@ -447,6 +448,25 @@ class KgMaskStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class KgUngappedParams(C.Structure):
+    """struct kg_ungapped_params (kg_proteins_search_filtered*)."""
+    _fields_ = [("min_ungapped", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class KgUngappedStats(C.Structure):
+    """struct kg_ungapped_stats."""
+    _fields_ = [("scored", C.c_int64), ("dropped", C.c_int64), ("cut", C.c_int64), ("cells", C.c_int64), ("ms_ungapped", C.c_float),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
+# struct kg_search_ungapped (kg_hitset_ungapped_copy): one per hit record of a filtered search, same index
+SEARCH_UNGAPPED_DTYPE = np.dtype([("ungapped", "<i4"), ("diagonal", "<i4"), ("on_diagonal", "<i4"), ("reserved", "<i4")])
+assert SEARCH_UNGAPPED_DTYPE.itemsize == 16
+
+
 class KgVoteParams(C.Structure):
     """struct kg_vote_params (kg_result_otu_votes / kg_otu_votes_hits)."""
     _fields_ = [("min_votes", C.c_int32), ("min_share_pct", C.c_int32), ("min_calls", C.c_int32), ("reserved", C.c_int32)]
@@ -618,6 +638,11 @@ def load() -> C.CDLL:
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgSearchParams), C.POINTER(KgSeedParams), C.POINTER(KgAlignParams), vp, vp,
                                        C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(KgMaskParams), C.c_int,
                                        C.POINTER(vp)]
+    for name in ("kg_proteins_search_filtered", "kg_proteins_search_filtered_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgSearchParams), C.POINTER(KgSeedParams), C.POINTER(KgAlignParams), vp, vp,
+                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(KgMaskParams), C.c_int,
+                                       C.POINTER(KgUngappedParams), C.POINTER(vp)]
+    lib.kg_hitset_ungapped_stats.argtypes = [vp, C.POINTER(KgUngappedStats)]
     for name in ("kg_proteins_cluster_masked", "kg_proteins_cluster_masked_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
                                        C.POINTER(KgMaskParams), C.POINTER(vp)]
@@ -629,7 +654,7 @@ def load() -> C.CDLL:
     for name in ("kg_sigset_device", "kg_regionset_device", "kg_orfset_device", "kg_selectset_device"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = vp
-    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_maskset_copy", "kg_maskset_flags_copy", "kg_hitset_copy", "kg_hitset_paths_copy", "kg_hitset_op_starts_copy", "kg_hitset_ops_copy", "kg_opset_op_starts_copy", "kg_opset_ops_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
+    for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_maskset_copy", "kg_maskset_flags_copy", "kg_hitset_copy", "kg_hitset_paths_copy", "kg_hitset_ungapped_copy", "kg_hitset_op_starts_copy", "kg_hitset_ops_copy", "kg_opset_op_starts_copy", "kg_opset_ops_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
                  "kg_orfset_junctions_copy", "kg_orfset_coding_scores", "kg_orfset_start_shifts", "kg_selectset_copy",
                  "kg_voteset_copy_votes", "kg_voteset_copy_classes", "kg_voteset_copy_bins", "kg_compset_copy_classes",
                  "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores"):

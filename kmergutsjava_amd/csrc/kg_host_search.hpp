@@ -5,9 +5,12 @@
 // of kg_seed.hpp in the derive kernel's place: seed ids of a reduced alphabet and spaced shapes where the exact call has 8-mers.
 // kg_proteins_search_masked is either call with the window kernels reading the seeding copy of kg_host_mask.hpp (the masked
 // residues of one or both sides turned into non-residues); the alignment and the trace read the original.
+// kg_proteins_search_filtered is any of them with the ungapped stage of kg_ungapped.hpp between the join and the alignment.
 // search_impl is a driver over three stages: search_pairs (the front half the cluster call has too, by the functions of
-// kg_host_derive.hpp: staging, block counts, count pass, one-pass cap, window-pairs pass), search_candidates (the join and the
-// per-query cut) and search_finish (the result block, the alignment, the order, the statistics, the paths).
+// kg_host_derive.hpp: staging, block counts, count pass, one-pass cap, window-pairs pass), search_candidates (search_runs, the
+// join and the per-query cut) or, chosen by the call, search_candidates_ungapped (search_runs, the join with the diagonals, the
+// best diagonal, the ungapped scores, the cut by them) and search_finish (the result block, the alignment, the order, the
+// statistics, the ungapped records' places, the paths).
 // Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_derive.hpp, kg_host_align.hpp, kg_host_trace.hpp and
 // kg_host_cluster.hpp (cluster_link_starts_kernel is launched here as well).
 #pragma once
@@ -26,6 +29,9 @@ struct kg_hitset {
     float ms_ops = 0;
     bool has_mask = false;              // kg_proteins_search_masked only: the statistics of the mask behind the seeding copy
     kg_mask_stats mst = {};
+    Detached d_ung;                     // kg_proteins_search_filtered only: one kg_search_ungapped per hit record
+    bool has_ung = false;
+    kg_ungapped_stats ust = {};
     const int64_t *op_starts() const { return (const int64_t *)d_ops.p; }
     const uint32_t *ops() const { return (const uint32_t *)(d_ops.p + ((size_t)count + 1) * 8); }
     const int64_t *starts() const { return (const int64_t *)d_block.p; }
@@ -34,11 +40,18 @@ struct kg_hitset {
 
 static_assert(sizeof(kg_search_hit) == 40 && sizeof(kg_search_params) == 16 && sizeof(kg_search_stats) == 136 && sizeof(kg_seed_params) == 48,
               "record layouts of include/kmerguts_hip.h");
+static_assert(sizeof(kg_ungapped_params) == 16 && sizeof(kg_search_ungapped) == 16 && sizeof(kg::UngappedRec) == 16 && sizeof(kg_ungapped_stats) == 40,
+              "record layouts of include/kmerguts_hip.h");
 
 namespace {
 
 constexpr uint64_t kSearchBytesPerPair = 112;                         // device bytes one join pair needs, at most
 constexpr uint64_t kSearchPairsMax = (1ull << 32) - (1ull << 22);     // the 32-bit scans and indices of the join
+// The ungapped stage, per join pair at most: the sort's two sides 24, the heads of both levels and their scans 16, the starts of
+// both levels 8, the best words 8; per candidate (at most one per pair) key, s, diagonal, u, flag and scan 32; per kept candidate
+// key, s, record 28, the second sort's two sides 24, heads, scans and top flags 16; per aligned candidate pairs, s and record 28.
+// 184, and the histograms and chunk sums of the sorts and scans on top.
+constexpr uint64_t kUngappedBytesPerPair = 200;
 
 // kg_proteins_search_paths: which records are traced (trace & 3), whether their ops are written (KG_TRACE_OPS, KG_TRACE_OPS_EQX), and
 // the cap of a box.  trace = 0: no paths are asked for
@@ -191,6 +204,7 @@ struct SearchArgs {
     const SeedPlan *seed;
     const MaskPlan *mask;
     int sides;
+    const kg_ungapped_params *ung = nullptr;    // kg_proteins_search_filtered: the ungapped stage in search_candidates' place
 };
 
 // what search_impl sets up for its stages: they allocate from sc, enqueue on t->stream and record the timing events ev[1 .. 5]
@@ -262,23 +276,34 @@ int search_pairs(SearchCall &c, SearchPairs *out)
 struct SearchCands {
     uint64_t K = 0, joined = 0, masked = 0, J = 0, NC = 0, NK = 0;
     int32_t *d_kept_pairs = nullptr, *d_shared = nullptr;
+    // search_candidates_ungapped only: d_ung[NK] beside d_shared, the candidates that passed min_ungapped, the cells and the time
+    kg::UngappedRec *d_ung = nullptr;
+    uint64_t NU = 0, ucells = 0;
+    float ms_ungapped = 0;
 };
 
-// Stage 2: the k-mer runs and their weights, whether the join fits, the join and its sort, the (q, d) runs, the candidates, the cut
-// per query
-int search_candidates(SearchCall &c, const SearchPairs &in, SearchCands *out)
+// what search_runs gives the join: the R listed runs (first pair, targets) and wx[R + 1], the exclusive scan of their weights with
+// wx[R] = J, and the chunk sums of a prefix sum over J items
+struct SearchRuns {
+    uint64_t R = 0, J = 0;
+    uint32_t *cstart = nullptr, *cnd = nullptr, *wx = nullptr;
+    uint64_t *jpartial = nullptr;
+};
+
+// Stage 2, its front: the k-mer runs and their weights, whether the join fits (at bytes_per_pair a pair), the listed runs.  J = 0:
+// nothing to join.  keep_pv: the run flags get words of their own and in.w.pv stays what the window-pairs pass left.
+int search_runs(SearchCall &c, const SearchPairs &in, bool keep_pv, uint64_t bytes_per_pair, SearchCands *out, SearchRuns *runs)
 {
-    if (in.n == 0) return KG_OK;
     const SearchArgs &a = c.a;
     kg_table *t = c.t;
     Scratch &sc = c.sc;
     hipStream_t s = t->stream;
     unsigned long long *words = c.words;
     uint64_t *d_tot = c.d_tot;
-    const uint32_t b = bits_for((uint64_t)a.n_prot), db = bits_for((uint64_t)a.n_db), ndb = (uint32_t)a.n_db, qb = bits_for((uint64_t)(a.n_prot - a.n_db));
+    const uint32_t b = bits_for((uint64_t)a.n_prot), ndb = (uint32_t)a.n_db;
     const uint64_t P = in.w.P;
     uint64_t *const pk = in.w.pk, *const partial = in.w.partial;
-    uint64_t K = 0, R = 0, ND = 0;
+    uint64_t K = 0, R = 0;
     int rc;
 
     // ---- the k-mer runs, their split at n_db and their weights (flags / pidx / partial are reused: K <= P <= n) ----
@@ -290,6 +315,7 @@ int search_candidates(SearchCall &c, const SearchPairs &in, SearchCands *out)
     HIP_TRY(hipStreamSynchronize(s));
     out->K = K;
     if ((rc = sc.get(&kstart, K + 1)) || (rc = sc.get(&nd, K)) || (rc = sc.get(&w, K)) || (rc = sc.get(&wpos, K))) return rc;
+    if (keep_pv && (rc = sc.get(&wf, K))) return rc;
     hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(P)), dim3(256), 0, s, kh, kx, P, d_tot + 1, kstart);
     hipLaunchKernelGGL(kg::search_run_weights_kernel, dim3(grid_of(K)), dim3(256), 0, s, pk, kstart, K, b, ndb, (uint32_t)a.prm->max_db_per_kmer,
                        nd, w, wf, words);
@@ -306,7 +332,7 @@ int search_candidates(SearchCall &c, const SearchPairs &in, SearchCands *out)
 
     // ---- whether the join fits: J is the 64-bit sum, exact whatever the stored weights saturate to ----
     Cap cap;
-    if ((rc = size_cap(a.max_pairs, " (max_pairs)", kSearchBytesPerPair, kSearchPairsMax, &cap))) return rc;
+    if ((rc = size_cap(a.max_pairs, " (max_pairs)", bytes_per_pair, kSearchPairsMax, &cap))) return rc;
     if (J > cap.items)
         return fail(KG_ERR_LIMIT, kmer_text((int64_t)J) + " join pairs do not fit this call, which holds " + kmer_text((int64_t)cap.items) +
                                       cap.how + "; a smaller max_db_per_kmer masks more of the frequent k-mers");
@@ -322,6 +348,30 @@ int search_candidates(SearchCall &c, const SearchPairs &in, SearchCands *out)
     hipLaunchKernelGGL(kg::search_run_compact_kernel, dim3(grid_of(K)), dim3(256), 0, s, kstart, nd, w, wf, wpos, K, R, cstart, cnd, cw);
     HIP_TRY(hipGetLastError());
     if ((rc = prefix_sum(t, cw, R + 1, wx, partial, d_tot + 3))) return rc;
+    *runs = SearchRuns{R, J, cstart, cnd, wx, jpartial};
+    return KG_OK;
+}
+
+// Stage 2: search_runs, the join and its sort, the (q, d) runs, the candidates, the cut per query
+int search_candidates(SearchCall &c, const SearchPairs &in, SearchCands *out)
+{
+    if (in.n == 0) return KG_OK;
+    const SearchArgs &a = c.a;
+    kg_table *t = c.t;
+    Scratch &sc = c.sc;
+    hipStream_t s = t->stream;
+    unsigned long long *words = c.words;
+    uint64_t *d_tot = c.d_tot;
+    const uint32_t b = bits_for((uint64_t)a.n_prot), db = bits_for((uint64_t)a.n_db), ndb = (uint32_t)a.n_db, qb = bits_for((uint64_t)(a.n_prot - a.n_db));
+    uint64_t *const pk = in.w.pk;
+    uint64_t ND = 0;
+    int rc;
+    SearchRuns runs;
+    if ((rc = search_runs(c, in, false, kSearchBytesPerPair, out, &runs))) return rc;
+    const uint64_t R = runs.R, J = runs.J;
+    if (J == 0) return KG_OK;
+    uint32_t *const cstart = runs.cstart, *const cnd = runs.cnd, *const wx = runs.wx;
+    uint64_t *const jpartial = runs.jpartial;
     // ---- the join: one key per (query, target) of every listed run ----
     SortPairs jp;
     if ((rc = jp.alloc(sc, J))) return rc;
@@ -387,6 +437,172 @@ int search_candidates(SearchCall &c, const SearchPairs &in, SearchCands *out)
     return KG_OK;
 }
 
+// the widths of the ungapped stage's join key (q << db | d) << gb | (g + bias): bias = the longest target - 1, gb = the bits of
+// the longest query + the longest target, which is above every g + bias
+struct UngappedWidths { uint32_t qb, db, gb; int32_t bias; };
+
+int ungapped_widths(const SearchArgs &a, UngappedWidths *out)
+{
+    int64_t lq = 0, ld = 0;
+    for (int64_t p = 0; p < a.n_prot; p++) {
+        int64_t &longest = p < a.n_db ? ld : lq;
+        longest = std::max(longest, a.offsets[p + 1] - a.offsets[p]);
+    }
+    const UngappedWidths w{bits_for((uint64_t)(a.n_prot - a.n_db)), bits_for((uint64_t)a.n_db), bits_for((uint64_t)(lq + ld)),
+                           (int32_t)std::max<int64_t>(ld - 1, 0)};
+    if (w.qb + w.db + w.gb > 64)
+        return fail(KG_ERR_LIMIT, "the join key of the ungapped stage does not fit 64 bits: " + kmer_text(w.qb) + " bits of the queries, " +
+                                      kmer_text(w.db) + " of the targets and " + kmer_text(w.gb) +
+                                      " of the diagonals (the longest query plus the longest target)");
+    *out = w;
+    return KG_OK;
+}
+
+// Stage 2 of kg_proteins_search_filtered: search_runs with pv kept, the join with the diagonals, its sort, the (q, d) and
+// (q, d, g) runs, the best diagonal of every candidate, the ungapped scores, the cut by min_ungapped and the cut per query by
+// (u, s, d).  Gives what search_candidates gives, and d_ung beside d_shared.
+int search_candidates_ungapped(SearchCall &c, const SearchPairs &in, SearchCands *out)
+{
+    if (in.n == 0) return KG_OK;
+    const SearchArgs &a = c.a;
+    kg_table *t = c.t;
+    Scratch &sc = c.sc;
+    hipStream_t s = t->stream;
+    unsigned long long *words = c.words;
+    uint64_t *d_tot = c.d_tot;
+    const uint32_t b = bits_for((uint64_t)a.n_prot), ndb = (uint32_t)a.n_db;
+    int rc;
+    UngappedWidths uw;
+    if ((rc = ungapped_widths(a, &uw))) return rc;
+    const uint32_t qb = uw.qb, db = uw.db, gb = uw.gb;
+    SearchRuns runs;
+    if ((rc = search_runs(c, in, true, kUngappedBytesPerPair, out, &runs))) return rc;
+    const uint64_t R = runs.R, J = runs.J;
+    if (J == 0) return KG_OK;
+    uint64_t *const jpartial = runs.jpartial;
+    Events<2> uev;
+    uint64_t *d_tot2 = nullptr;                         // the totals of this stage's own prefix sums
+    unsigned long long *uwords = nullptr;
+    if ((rc = uev.create()) || (rc = sc.get(&d_tot2, 4)) || (rc = sc.get(&uwords, kg::kUngappedWords))) return rc;
+    HIP_TRY(hipMemsetAsync(uwords, 0, kg::kUngappedWords * 8, s));
+
+    // ---- the join with the diagonals, sorted: inside a (q, d) run the diagonals ascend ----
+    SortPairs jp;
+    if ((rc = jp.alloc(sc, J))) return rc;
+    hipLaunchKernelGGL(kg::search_join_diag_kernel, dim3(grid_of(J, kg::kSearchTile)), dim3(kg::kSearchThreads), 0, s, in.w.pk, in.w.pv, in.d_off,
+                       runs.wx, runs.cstart, runs.cnd, (uint32_t)R, (uint32_t)J, b, ndb, db, gb, uw.bias, jp.keys(), jp.vals());
+    HIP_TRY(hipGetLastError());
+    uint64_t wtot = 0, ND = 0, NG = 0;
+    HIP_TRY(hipMemcpyAsync(&wtot, d_tot + 3, 8, hipMemcpyDeviceToHost, s));
+    if ((rc = jp.sort(t, sc, J, qb + db + gb))) return rc;
+    // ---- the (q, d) runs (length s) and inside them the (q, d, g) runs (length m) ----
+    uint32_t *lh = nullptr, *lr = nullptr, *gh = nullptr, *gr = nullptr, *lstart = nullptr, *gstart = nullptr;
+    if ((rc = sc.get(&lh, J)) || (rc = sc.get(&lr, J)) || (rc = sc.get(&gh, J)) || (rc = sc.get(&gr, J))) return rc;
+    hipLaunchKernelGGL(kg::search_query_heads_kernel, dim3(grid_of(J)), dim3(256), 0, s, jp.keys(), J, gb, lh);
+    hipLaunchKernelGGL(kg::derive_key_heads_kernel, dim3(grid_of(J)), dim3(256), 0, s, jp.keys(), J, gh);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, lh, J, lr, jpartial, d_tot + 4)) || (rc = prefix_sum(t, gh, J, gr, jpartial, d_tot2 + 0))) return rc;
+    HIP_TRY(hipMemcpyAsync(&ND, d_tot + 4, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&NG, d_tot2 + 0, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (wtot != J) return fail(KG_ERR_DEVICE, "internal: the prefix sum of the weights and their 64-bit sum differ");
+    unsigned long long *best = nullptr;
+    uint32_t *cf = nullptr, *cx = nullptr;
+    if ((rc = sc.get(&lstart, ND + 1)) || (rc = sc.get(&gstart, NG + 1)) || (rc = sc.get(&best, ND)) || (rc = sc.get(&cf, ND)) ||
+        (rc = sc.get(&cx, ND)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(best, 0, ND * 8, s));
+    hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(J)), dim3(256), 0, s, lh, lr, J, d_tot + 4, lstart);
+    hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(J)), dim3(256), 0, s, gh, gr, J, d_tot2 + 0, gstart);
+    hipLaunchKernelGGL(kg::ungapped_best_kernel, dim3(grid_of(NG)), dim3(256), 0, s, jp.keys(), gstart, NG, lh, lr, gb, best);
+    hipLaunchKernelGGL(kg::search_cand_flags_kernel, dim3(grid_of(ND)), dim3(256), 0, s, lstart, ND, (uint32_t)a.prm->min_shared, cf, words);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, cf, ND, cx, jpartial, d_tot + 5))) return rc;
+    unsigned long long smax = 0;
+    uint64_t NC = 0;
+    HIP_TRY(hipMemcpyAsync(&NC, d_tot + 5, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&smax, words + kg::kSearchSmax, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->NC = NC;
+    if (NC == 0) return KG_OK;
+
+    // ---- the candidates in (q, d) order with s, g* and m(g*); their ungapped scores ----
+    uint64_t *ckey = nullptr;
+    uint32_t *cs = nullptr, *kf = nullptr, *kx = nullptr;
+    uint2 *cdiag = nullptr;
+    int32_t *cu = nullptr;
+    int8_t *d_matrix = nullptr;
+    if ((rc = sc.get(&ckey, NC)) || (rc = sc.get(&cs, NC)) || (rc = sc.get(&cdiag, NC)) || (rc = sc.get(&cu, NC)) || (rc = sc.get(&kf, NC)) ||
+        (rc = sc.get(&kx, NC)))
+        return rc;
+    if (a.al->matrix) {
+        if ((rc = sc.get(&d_matrix, 21 * 21))) return rc;
+        HIP_TRY(hipMemcpyAsync(d_matrix, a.al->matrix, 21 * 21, hipMemcpyHostToDevice, s));
+    }
+    hipLaunchKernelGGL(kg::ungapped_cand_kernel, dim3(grid_of(ND)), dim3(256), 0, s, jp.keys(), lstart, cf, cx, best, ND, NC, gb, ckey, cs, cdiag);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(uev[0], s));
+    {
+        // one wave per 64 candidates and trip; 8 workgroups of 4 waves per CU at most
+        const uint32_t chunks = (uint32_t)((NC + kg::kWave - 1) / kg::kWave);
+        const uint32_t grid = std::max(std::min<uint32_t>((chunks + 3) / 4, 256u * 8), 1u);
+        hipLaunchKernelGGL(kg::search_ungapped_kernel, dim3(grid), dim3(kg::kUngappedThreads), 0, s, c.d_seq, in.d_off, ckey, cdiag, (uint32_t)NC,
+                           ndb, db, uw.bias, d_matrix, cu, uwords);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(uev[1], s));
+    hipLaunchKernelGGL(kg::ungapped_keep_kernel, dim3(grid_of(NC)), dim3(256), 0, s, cu, NC, (int32_t)a.ung->min_ungapped, kf);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, kf, NC, kx, jpartial, d_tot2 + 1))) return rc;
+    unsigned long long huw[kg::kUngappedWords] = {};
+    uint64_t NU = 0;
+    HIP_TRY(hipMemcpyAsync(&NU, d_tot2 + 1, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(huw, uwords, sizeof huw, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->NU = NU;
+    out->ucells = huw[kg::kUngappedCells];
+    out->ms_ungapped = uev.ms(0, 1);
+    if (NU == 0) return KG_OK;
+
+    // ---- the kept candidates, still in (q, d) order, then stably by (q, descending u, descending s): ties stay in ascending d ----
+    const uint64_t umax = huw[kg::kUngappedUmax];
+    const uint32_t sb = bit_width(smax), ub = bit_width(umax);
+    if (qb + ub + sb > 64)
+        return fail(KG_ERR_LIMIT, "the cut key of the ungapped stage does not fit 64 bits: " + kmer_text(qb) + " bits of the queries, " +
+                                      kmer_text(ub) + " of the ungapped scores and " + kmer_text(sb) + " of the shared counts");
+    uint64_t *kkey = nullptr;
+    uint32_t *ks = nullptr, *qh = nullptr, *qx = nullptr, *qstart = nullptr, *tf = nullptr, *tx = nullptr;
+    kg::UngappedRec *krec = nullptr;
+    SortPairs cp;
+    if ((rc = sc.get(&kkey, NU)) || (rc = sc.get(&ks, NU)) || (rc = sc.get(&krec, NU)) || (rc = cp.alloc(sc, NU)) || (rc = sc.get(&qh, NU)) ||
+        (rc = sc.get(&qx, NU)) || (rc = sc.get(&tf, NU)) || (rc = sc.get(&tx, NU)))
+        return rc;
+    hipLaunchKernelGGL(kg::ungapped_emit_kernel, dim3(grid_of(NC)), dim3(256), 0, s, ckey, cs, cdiag, cu, kf, kx, NC, NU, db, sb, ub, (uint32_t)smax,
+                       (uint32_t)umax, uw.bias, kkey, ks, krec, cp.keys(), cp.vals());
+    HIP_TRY(hipGetLastError());
+    if ((rc = cp.sort(t, sc, NU, qb + ub + sb))) return rc;
+    hipLaunchKernelGGL(kg::search_query_heads_kernel, dim3(grid_of(NU)), dim3(256), 0, s, cp.keys(), NU, ub + sb, qh);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, qh, NU, qx, jpartial, d_tot + 6))) return rc;
+    uint64_t NQ = 0, NK = 0;
+    HIP_TRY(hipMemcpyAsync(&NQ, d_tot + 6, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = sc.get(&qstart, NQ + 1))) return rc;
+    hipLaunchKernelGGL(kg::cluster_link_starts_kernel, dim3(grid_of(NU)), dim3(256), 0, s, qh, qx, NU, d_tot + 6, qstart);
+    hipLaunchKernelGGL(kg::search_top_flags_kernel, dim3(grid_of(NU)), dim3(256), 0, s, qh, qx, qstart, NU, (uint32_t)a.prm->max_cand, tf);
+    HIP_TRY(hipGetLastError());
+    if ((rc = prefix_sum(t, tf, NU, tx, jpartial, d_tot + 7))) return rc;
+    HIP_TRY(hipMemcpyAsync(&NK, d_tot + 7, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->NK = NK;
+    if ((rc = sc.get(&out->d_kept_pairs, 2 * NK)) || (rc = sc.get(&out->d_shared, NK)) || (rc = sc.get(&out->d_ung, NK))) return rc;
+    hipLaunchKernelGGL(kg::search_top_emit_kernel, dim3(grid_of(NU)), dim3(256), 0, s, cp.vals(), kkey, ks, tf, tx, NU, NK, db, ndb,
+                       out->d_kept_pairs, out->d_shared);
+    hipLaunchKernelGGL(kg::ungapped_top_emit_kernel, dim3(grid_of(NU)), dim3(256), 0, s, cp.vals(), krec, tf, tx, NU, NK, out->d_ung);
+    HIP_TRY(hipGetLastError());
+    return KG_OK;
+}
+
 // Stage 3: the result block with hit_start, the kept candidates aligned and ordered, the cross-checks, the statistics, and the
 // paths where the call asks for them.  The set owns its blocks from their allocation on: a set freed after a failure frees them.
 int search_finish(SearchCall &c, const SearchPairs &pairs, const SearchCands &cd, kg_hitset *set)
@@ -428,6 +644,14 @@ int search_finish(SearchCall &c, const SearchPairs &pairs, const SearchCands &cd
                            (int2 *)(block + start_bytes), c.words);
         HIP_TRY(hipGetLastError());
     }
+    if (a.ung) {                                        // the 16-byte records to the places the order gave their candidates
+        if ((rc = dalloc_detached(t, &set->d_ung.p, std::max<uint64_t>(NK, 1) * sizeof(kg_search_ungapped)))) return rc;
+        if (NK > 0) {
+            hipLaunchKernelGGL(kg::ungapped_place_kernel, dim3(grid_of(NK)), dim3(256), 0, s, (const int2 *)(block + start_bytes),
+                               (const int64_t *)block, cd.d_kept_pairs, cd.d_ung, NK, (uint32_t)n_q, (kg::UngappedRec *)set->d_ung.p);
+            HIP_TRY(hipGetLastError());
+        }
+    }
     HIP_TRY(hipEventRecord(c.ev[5], s));
     unsigned long long hw[kg::kSearchWords] = {};
     HIP_TRY(hipMemcpyAsync(hw, c.words, sizeof hw, hipMemcpyDeviceToHost, s));
@@ -455,6 +679,15 @@ int search_finish(SearchCall &c, const SearchPairs &pairs, const SearchCands &cd
     st.ms_join = c.ev.ms(3, 4);
     st.ms_align = c.ev.ms(4, 5);
     st.ms_total = c.ev.ms(0, 5);
+    if (a.ung) {
+        st.ms_join = std::max(st.ms_join - cd.ms_ungapped, 0.0f);
+        set->ust.scored = (int64_t)cd.NC;
+        set->ust.dropped = (int64_t)(cd.NC - cd.NU);
+        set->ust.cut = (int64_t)(cd.NU - NK);
+        set->ust.cells = (int64_t)cd.ucells;
+        set->ust.ms_ungapped = cd.ms_ungapped;
+        set->has_ung = true;
+    }
     set->count = (int64_t)NK;
     return a.ask.trace ? search_paths_behind(t, c.sc, a.al, c.d_seq, pairs.d_off, n_db, set->hits(), NK, a.ask, set) : KG_OK;
 }
@@ -483,7 +716,10 @@ int search_impl(kg_table *t, const SearchArgs &a, kg_hitset *set)
     for (int k = 1; k <= 4; k++) HIP_TRY(hipEventRecord(ev[k], s));
     SearchPairs pairs;
     SearchCands cands;
-    if ((rc = search_pairs(c, &pairs)) || (rc = search_candidates(c, pairs, &cands))) return rc;
+    UngappedWidths fits;                        // (a call whose diagonals do not fit its join key ends before the window pass)
+    if (a.ung && (rc = ungapped_widths(a, &fits))) return rc;
+    if ((rc = search_pairs(c, &pairs)) || (rc = a.ung ? search_candidates_ungapped(c, pairs, &cands) : search_candidates(c, pairs, &cands)))
+        return rc;
     if (pairs.n > 0) HIP_TRY(hipEventRecord(ev[4], s));
     return search_finish(c, pairs, cands, set);
 }
@@ -492,7 +728,8 @@ int search_impl(kg_table *t, const SearchArgs &a, kg_hitset *set)
 int search_entry(int device, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq,
                  const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset **out,
                  SearchPathsAsk ask = {}, std::optional<const kg_seed_params *> seeds = std::nullopt,
-                 std::optional<const kg_mask_params *> mask = std::nullopt, int sides = 0)
+                 std::optional<const kg_mask_params *> mask = std::nullopt, int sides = 0,
+                 std::optional<const kg_ungapped_params *> ung = std::nullopt)
 {
     if (!out) return fail(KG_ERR_ARG, "null argument");
     *out = nullptr;
@@ -508,6 +745,12 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     if (mask) {
         if (int rc = mask_plan(*mask, &mplan)) return rc;
         if (sides < 1 || sides > (KG_MASK_QUERIES | KG_MASK_TARGETS)) return fail(KG_ERR_ARG, "sides must be KG_MASK_QUERIES, KG_MASK_TARGETS or both");
+    }
+    if (ung) {
+        if (!*ung) return fail(KG_ERR_ARG, "null kg_ungapped_params");
+        if ((*ung)->min_ungapped < 0) return fail(KG_ERR_ARG, "min_ungapped must be >= 0");
+        if ((*ung)->reserved[0] != 0 || (*ung)->reserved[1] != 0 || (*ung)->reserved[2] != 0)
+            return fail(KG_ERR_ARG, "kg_ungapped_params.reserved must be 0");
     }
     if (!al) return fail(KG_ERR_ARG, "null kg_align_params");
     if (int rc = align_check_params(al)) return rc;
@@ -529,7 +772,8 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     kg_hitset *set = new (std::nothrow) kg_hitset();
     if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
     set->device = device;
-    const SearchArgs args{prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, ask, seeds ? &plan : nullptr, mask ? &mplan : nullptr, sides};
+    const SearchArgs args{prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, ask, seeds ? &plan : nullptr, mask ? &mplan : nullptr, sides,
+                          ung ? *ung : nullptr};
     int rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
     if (!rc) rc = search_impl(cs.t, args, set);
     cs.t->cache.release_all();                          // scratch goes back to the driver
@@ -631,6 +875,40 @@ int kg_proteins_search_masked_device(int device, const kg_search_params *p, cons
 {
     return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, {trace, max_trace_cells},
                         seeds ? std::optional<const kg_seed_params *>(seeds) : std::nullopt, mask, sides);
+}
+
+// (seeds = NULL: the exact 8-mers; mask = NULL: no mask, and sides is not read)
+int kg_proteins_search_filtered(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                                const uint8_t *seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                                int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides,
+                                const kg_ungapped_params *ungapped, kg_hitset **out)
+{
+    return search_entry(device, p, align, seq, nullptr, offsets, n_prot, n_db, max_windows, max_pairs, out, {trace, max_trace_cells},
+                        seeds ? std::optional<const kg_seed_params *>(seeds) : std::nullopt,
+                        mask ? std::optional<const kg_mask_params *>(mask) : std::nullopt, sides, ungapped);
+}
+
+int kg_proteins_search_filtered_device(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                                       const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                                       int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides,
+                                       const kg_ungapped_params *ungapped, kg_hitset **out)
+{
+    return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, {trace, max_trace_cells},
+                        seeds ? std::optional<const kg_seed_params *>(seeds) : std::nullopt,
+                        mask ? std::optional<const kg_mask_params *>(mask) : std::nullopt, sides, ungapped);
+}
+
+int kg_hitset_ungapped_copy(const kg_hitset *s, int64_t first, int64_t count, kg_search_ungapped *dst)
+{
+    if (s && !s->has_ung) return fail(KG_ERR_ARG, "kg_hitset_ungapped_copy: the set was made without the ungapped stage");
+    return copy_records(s, s ? s->device : 0, s ? (const kg_search_ungapped *)s->d_ung.p : nullptr, 1, s ? s->count : 0, first, count, dst,
+                        "kg_hitset_ungapped_copy");
+}
+
+int kg_hitset_ungapped_stats(const kg_hitset *s, kg_ungapped_stats *out)
+{
+    if (s && !s->has_ung) return fail(KG_ERR_ARG, "kg_hitset_ungapped_stats: the set was made without the ungapped stage");
+    return copy_stats(s, s ? &s->ust : nullptr, out);
 }
 
 int kg_hitset_mask_stats(const kg_hitset *s, kg_mask_stats *out)

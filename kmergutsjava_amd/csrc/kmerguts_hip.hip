@@ -19,6 +19,7 @@
 #include "kg_trace.hpp"
 #include "kg_ops.hpp"
 #include "kg_search.hpp"
+#include "kg_ungapped.hpp"
 #include "kg_seed.hpp"
 #include "kg_mask.hpp"
 #include "kg_assign.hpp"

@@ -987,7 +987,7 @@ def _seed_params(seeds):
 def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256,
                     align: Optional[dict] = None, max_windows: int = 0, max_pairs: int = 0, device: int = 0,
                     device_ptr: Optional[int] = None, paths: Optional[str] = None, max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS,
-                    seeds=None, ops: Optional[str] = None, mask=None):
+                    seeds=None, ops: Optional[str] = None, mask=None, ungapped=None):
     """Proteins [n_db, n_prot) searched against proteins [0, n_db), on the GPU (include/kmerguts_hip.h kg_proteins_search states
     the rule): the targets that share at least min_shared distinct unmasked 8-mers with a query, the max_cand with the most
     aligned, a hit where 100 * score >= min_ratio_pct * ref.  seq / offsets / device_ptr as for cluster_proteins; align: None
@@ -1004,7 +1004,19 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
     statistics, op_start int64[count + 1], ops), the statistics with ops and ms_ops as well.
     mask: None, True (the defaults of mask_proteins) or a dict of window, trigger, extend and sides ("both", the default,
     "queries" or "targets"): the seeding pass reads a copy in which that side's low-complexity segments are no residues
-    (kg_proteins_search_masked); the alignment, the trace and the ops read the original.  The statistics then also hold "mask"."""
+    (kg_proteins_search_masked); the alignment, the trace and the ops read the original.  The statistics then also hold "mask".
+    ungapped: None, True (min_score 0: rank only) or {"min_score": N}: kg_proteins_search_filtered, with seeds and mask as above.
+    Every candidate's best seed diagonal is scored without gaps, candidates with a score below N are dropped and a query's
+    candidates are cut by (larger ungapped score, larger s, smaller target).  The result tuple then ends with one more array,
+    _native.SEARCH_UNGAPPED_DTYPE records of the hit records' indices, and the statistics hold "ungapped" (scored, dropped,
+    cut, cells, ms_ungapped)."""
+    up = None
+    if ungapped is not None and ungapped is not False:
+        if ungapped is True:
+            ungapped = {}
+        if not isinstance(ungapped, dict) or set(ungapped) - {"min_score"}:
+            raise ValueError("ungapped must be None, True or {'min_score': N}")
+        up = N.KgUngappedParams(int(ungapped.get("min_score", 0)), (C.c_int32 * 3)(0, 0, 0))
     if paths is not None and paths not in N.TRACE_MODES:
         raise ValueError("paths must be None, 'hits' or 'all'")
     if ops is not None and ops not in N.OPS_MODES:
@@ -1020,7 +1032,17 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
     h = C.c_void_p()
     lib = N.load()
     mp = _mask_params(mask, sides_too=True)
-    if mp is not None:
+    if up is not None:
+        sp = C.byref(seed_set) if seed_set is not None else None
+        tail = (int(max_windows), int(max_pairs), trace, int(max_trace_cells), C.byref(mp[0]) if mp is not None else None,
+                mp[1] if mp is not None else 0, C.byref(up), C.byref(h))
+        if device_ptr is not None:
+            N.check(lib.kg_proteins_search_filtered_device(device, C.byref(p), sp, C.byref(ap), C.c_void_p(device_ptr), off.ctypes.data, n,
+                                                           int(n_db), *tail))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_proteins_search_filtered(device, C.byref(p), sp, C.byref(ap), _ptr(arr), off.ctypes.data, n, int(n_db), *tail))
+    elif mp is not None:
         sp = C.byref(seed_set) if seed_set is not None else None
         tail = (int(max_windows), int(max_pairs), trace, int(max_trace_cells), C.byref(mp[0]), mp[1], C.byref(h))
         if device_ptr is not None:
@@ -1063,6 +1085,12 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
             mst = N.KgMaskStats()
             N.check(lib.kg_hitset_mask_stats(h, C.byref(mst)))
             more["mask"] = mst.as_dict()
+        extra = ()
+        if up is not None:
+            ust = N.KgUngappedStats()
+            N.check(lib.kg_hitset_ungapped_stats(h, C.byref(ust)))
+            more["ungapped"] = ust.as_dict()
+            extra = (_copy_records(lib.kg_hitset_ungapped_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_UNGAPPED_DTYPE),)
         if paths is not None:
             tst = N.KgTraceStats()
             N.check(lib.kg_hitset_trace_stats(h, C.byref(tst)))
@@ -1075,8 +1103,8 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
                 N.check(lib.kg_hitset_ms_ops(h, C.byref(ms)))
                 stats.update(ops=int(lib.kg_hitset_ops_count(h)), ms_ops=ms.value)
                 got += _copy_ops(lib.kg_hitset_ops_count, lib.kg_hitset_op_starts_copy, lib.kg_hitset_ops_copy, h, count)
-            return got
-        return _copy_records(lib.kg_hitset_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_HIT_DTYPE), starts, dict(st.as_dict(), **more)
+            return got + extra
+        return (_copy_records(lib.kg_hitset_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_HIT_DTYPE), starts, dict(st.as_dict(), **more)) + extra
     finally:
         lib.kg_hitset_free(h)
 

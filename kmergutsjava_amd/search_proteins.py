@@ -128,10 +128,11 @@ def format_alignments(qids, dids, qseqs, dseqs, hits, hit_start, paths, op_start
 
 
 def format_hits(qids, dids, hits, hit_start, max_hits: int = 1, write_all: bool = False, align_ref: str = "longer", functions=None,
-                paths=None, qlens=None, dlens=None, cigars=None) -> bytes:
+                paths=None, qlens=None, dlens=None, cigars=None, ungapped=None) -> bytes:
     """functions: None, or {target id: (function, otu)}: every line gains the target's function or `-`.  paths: None, or one
     path record per hit record with the proteins' lengths in qlens / dlens: every line gains path_fields in front of it.
-    cigars: None, or (op_start, ops) of the path records: every line gains cigar_field behind the path fields."""
+    cigars: None, or (op_start, ops) of the path records: every line gains cigar_field behind the path fields.  ungapped: None,
+    or one ungapped record per hit record: every line gains ungapped, diagonal and on diagonal in front of the function."""
     out = []
     for q, qid in enumerate(qids):
         for k in range(int(hit_start[q]), int(hit_start[q + 1])):
@@ -147,6 +148,9 @@ def format_hits(qids, dids, hits, hit_start, max_hits: int = 1, write_all: bool 
                 line += path_fields(h, paths[k], qlens[q], dlens[int(h["target"])])
             if cigars is not None:
                 line += cigar_field(paths[k], cigars[0], cigars[1], k)
+            if ungapped is not None:
+                u = ungapped[k]
+                line += b"\t%d\t%d\t%d" % (int(u["ungapped"]), int(u["diagonal"]), int(u["on_diagonal"]))
             if functions is not None:
                 line += b"\t" + (functions[did][0] if did in functions else b"-")
             out.append(line + b"\n")
@@ -189,14 +193,17 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
                     align: Optional[dict] = None, write_all: bool = False, annotations: Optional[str] = None,
                     transfer: Optional[str] = None, truth: Optional[str] = None, device: int = 0, search=None,
                     paths: Optional[str] = None, max_trace_cells: Optional[int] = None, seeds=None, cigar: Optional[str] = None,
-                    alignments: Optional[str] = None, mask: Optional[dict] = None) -> str:
+                    alignments: Optional[str] = None, mask: Optional[dict] = None, ungapped: Optional[dict] = None) -> str:
     """Write the files; returns the summary line.  `search` replaces hotpath.search_proteins (tests).  align: None, or the
     alignment parameters of hotpath.search_proteins (ref "query" is its "member").  paths: None, "hits" or "all" (--paths with
     its --trace); max_trace_cells: None for the library's default.  seeds: None (the exact 8-mers), "reduced" or a
     dict(alphabet=..., shapes=[...]) as hotpath.search_proteins takes it.  cigar: None, "m" or "eqx" (--cigar); alignments: None
     or the file --alignments writes; both need paths.  mask: None, or a dict of window, trigger, extend and sides as
-    hotpath.search_proteins takes it (--mask)."""
+    hotpath.search_proteins takes it (--mask).  ungapped: None, or {"min_score": N} (--ungapped, --min-ungapped): the candidates
+    are ranked by the ungapped score of their best seed diagonal and those below N dropped."""
     from . import seeds as SD
+    if ungapped is not None and int(ungapped.get("min_score", 0)) < 0:
+        raise ValueError("--min-ungapped must be >= 0")
     seed_words = SD.describe(seeds) if SD.resolve(seeds) is not None else None
     if paths not in (None, "hits", "all"):
         raise ValueError("--trace must be hits or all")
@@ -232,9 +239,13 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
         if mask.get("sides", "both") not in ("both", "queries", "targets"):
             raise ValueError("--mask must be both, queries or targets")
         more["mask"] = mask
+    urecs = None
+    if ungapped is not None:
+        more["ungapped"] = dict(ungapped)
     if paths is None:
-        hits, hit_start, st = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
-                                     max_db_per_kmer=max_db_per_kmer, align=align, device=device, **more)
+        got = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
+                     max_db_per_kmer=max_db_per_kmer, align=align, device=device, **more)
+        hits, hit_start, st = got[:3]
     else:
         if max_trace_cells is not None:
             more["max_trace_cells"] = max_trace_cells
@@ -244,10 +255,12 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
                      align=align, device=device, paths=paths, **more)
         hits, hit_start, recs, st = got[:4]
         if ops_mode is not None:
-            op_start, ops = got[4:]
+            op_start, ops = got[4:6]
+    if ungapped is not None:
+        urecs = got[-1]                     # (the ungapped records end the tuple)
     with open(out, "wb") as f:
         f.write(format_hits(qids, dids, hits, hit_start, max_hits, write_all, align_ref, functions, recs, [len(x) for x in qseqs],
-                            [len(x) for x in dseqs], (op_start, ops) if cigar is not None else None))
+                            [len(x) for x in dseqs], (op_start, ops) if cigar is not None else None, urecs))
     if alignments is not None:
         with open(alignments, "wb") as f:
             f.write(format_alignments(qids, dids, qseqs, dseqs, hits, hit_start, recs, op_start, ops, max_hits, write_all))
@@ -271,6 +284,9 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
     if mask is not None:
         from .mask_proteins import mask_words
         line += ", mask: %s, masked residues: %d" % (mask_words(mask, mask.get("sides", "both")), st["mask"]["masked_residues"])
+    if ungapped is not None:
+        u = st["ungapped"]
+        line += ", ungapped: scored %d, dropped %d, cut %d, ungapped ms: %.3f" % (u["scored"], u["dropped"], u["cut"], u.get("ms_ungapped", 0.0))
     return line
 
 
@@ -312,7 +328,16 @@ def main(argv=None) -> int:
                     help="keep low-complexity segments out of the prefilter: of both sides (default of the flag), the queries or the targets")
     from .mask_proteins import add_mask_options, mask_from_options
     add_mask_options(ap, "the alignment reads the proteins as they are")
+    ap.add_argument("--ungapped", action="store_true",
+                    help="rank a query's candidates by the ungapped score of their best seed diagonal, not by shared seeds alone; every -o "
+                         "line gains ungapped, diagonal and on diagonal")
+    ap.add_argument("--min-ungapped", type=int, default=None, metavar="N",
+                    help="with --ungapped: a candidate whose ungapped score is below N is not aligned (default 0: none is dropped)")
     a = ap.parse_args(argv)
+    if a.min_ungapped is not None and not a.ungapped:
+        ap.error("--min-ungapped needs --ungapped")
+    if a.min_ungapped is not None and a.min_ungapped < 0:
+        ap.error("--min-ungapped must be >= 0")
     if a.shape is not None and len(a.shape) > 4:
         ap.error("at most 4 --shape")
     if not a.paths and (a.trace is not None or a.max_trace_cells is not None):
@@ -333,7 +358,8 @@ def main(argv=None) -> int:
     try:
         line = search_proteins(a.d, a.q, a.o, a.min_shared, a.max_cand, a.max_hits, a.max_db_per_kmer, align, a.all, a.A, a.transfer,
                                a.truth, paths=paths, max_trace_cells=a.max_trace_cells, seeds=seeds, cigar=a.cigar, alignments=a.alignments,
-                               mask=mask_from_options(ap, a, a.mask))
+                               mask=mask_from_options(ap, a, a.mask),
+                               ungapped=dict(min_score=a.min_ungapped or 0) if a.ungapped else None)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1
