@@ -945,6 +945,62 @@ int kg_proteins_search_filtered_device(int device, const kg_search_params *p, co
 int kg_hitset_ungapped_copy(const kg_hitset *s, int64_t first, int64_t count, kg_search_ungapped *dst);
 int kg_hitset_ungapped_stats(const kg_hitset *s, kg_ungapped_stats *out);
 
+/* ---- banded alignment: the cells of a band around one diagonal per pair (kernels: kg_band.hpp, kg_trace.hpp) ----
+ *
+ * kg_proteins_align fills all n * m cells of a pair.  A search candidate carries the diagonal g* on which its seeds lie, and an
+ * alignment that follows them stays near it.  Opt-in; the rule is the project's own.  Integers only.
+ *   Everything is kg_proteins_align's rule: H, E, F, S, the gap costs and their caps, the codes, self, and 0-based end_a and end_b.
+ *   One thing is added.  For a pair (a, b) with diagonal g and half-width W, the cell (i, j) (0-based, a_i against b_j) is in the
+ *   band iff |(i - j) - g| <= W.  A cell outside the band has H = 0, exactly as a cell outside the matrix has; E and F follow from
+ *   the unchanged recurrence.  So the banded score is the best local alignment whose every column, gap columns included, lies in
+ *   the band: a diagonal step never leaves it, and a positive E or F never has a source outside it.
+ *   score is the maximum of H over the in-band cells; (end_a, end_b) is the in-band cell with that H, the smallest i, then the
+ *   smallest j, and (-1, -1) at score 0.  A band that misses the matrix altogether gives score 0.
+ *   0 <= W <= KG_BAND_MAX = 256 (KG_ERR_ARG "band must be in [0, 256]"): a band wider than 513 diagonals is not a band, and the
+ *   limit keeps one 64-row stripe's carry, at most 2 W + 64 columns, in the workgroup's LDS.  g is any int32.
+ *   Abstaining.  band_cells = min(n * m, min(n, m) * (2 W + 1)) in int64; the pair is skipped iff band_cells > max_cells.  A pair
+ *   that kg_proteins_align skips can therefore be aligned under a band.
+ *   Consequences: the banded score is <= the full score; with W >= max(n - 1 - g, m - 1 + g) every record is byte for byte
+ *   kg_proteins_align's; with W = 0 the score is the ungapped score u of diagonal g (the rule above); in the search u <= score
+ *   still holds for every aligned record.
+ *   Tracing under a band is the walk of kg_proteins_align_paths, word for word, over the same prefix box with the cells outside
+ *   the band forced to H = 0.  max_trace_cells still caps the whole box (end_a + 1) * (end_b + 1); a box that does not reproduce
+ *   the record's score stays KG_ERR_DEVICE, which is what proves that the two passes agree about the band.  The ops follow from
+ *   the walk unchanged.
+ * kg_band_params: a null pointer is KG_ERR_ARG "null kg_band_params", non-zero reserved "kg_band_params.reserved must be 0".
+ * kg_proteins_align_banded / _device: kg_proteins_align_ops' arguments, then the band and `diagonals` (host memory, one per pair,
+ * "null diagonals" when n_pairs > 0).  paths and ops may both be null (the records only); ops without paths is KG_ERR_ARG "ops
+ * without paths"; without ops, ops_mode must be 0 ("ops_mode must be 0 without ops"); max_trace_cells is read only with paths.
+ * kg_proteins_search_banded / _device: kg_proteins_search_filtered's arguments, then the band.  Every aligned candidate is aligned
+ * in the band around its g*.  The prefilter, the ungapped stage, the cut, the hit test, the record order, kg_search_hit,
+ * kg_search_ungapped and trace (paths and ops) are otherwise unchanged; kg_search_stats.cells keeps its definition (n * m of the
+ * aligned pairs).  kg_hitset_band_stats gives the band's own counts over the aligned pairs; it is KG_ERR_ARG for a set made by
+ * any other call.
+ * The entry points above and their results are unchanged, byte for byte. */
+#define KG_BAND_MAX 256
+typedef struct kg_band_params { int32_t band; int32_t reserved[3]; } kg_band_params;
+typedef struct kg_band_stats {
+    int64_t band_cells;    /* sum of band_cells over the aligned pairs                  */
+    int64_t full_cells;    /* sum of n * m over the same pairs: kg_search_stats.cells   */
+    int32_t band;          /* W                                                         */
+    int32_t reserved;
+} kg_band_stats;
+int kg_proteins_align_banded(int device, const kg_align_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
+                             const int32_t *pairs, int64_t n_pairs, int64_t max_trace_cells, int ops_mode, kg_alignment *out,
+                             kg_alignment_path *paths, kg_opset **ops, const kg_band_params *band, const int32_t *diagonals);
+int kg_proteins_align_banded_device(int device, const kg_align_params *p, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
+                                    const int32_t *pairs, int64_t n_pairs, int64_t max_trace_cells, int ops_mode, kg_alignment *out,
+                                    kg_alignment_path *paths, kg_opset **ops, const kg_band_params *band, const int32_t *diagonals);
+int kg_proteins_search_banded(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                              const uint8_t *seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                              int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides,
+                              const kg_ungapped_params *ungapped, const kg_band_params *band, kg_hitset **out);
+int kg_proteins_search_banded_device(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                                     const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                                     int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides,
+                                     const kg_ungapped_params *ungapped, const kg_band_params *band, kg_hitset **out);
+int kg_hitset_band_stats(const kg_hitset *s, kg_band_stats *out);
+
 /* ---- assigning functions: the CALL records of an -a scan -> one function per protein (kernels: kg_assign.hpp) ----
  *
  * The reference stops at the CALL lines (KGJ:398-404, 526-536); this rule is the project's own.

@@ -509,6 +509,25 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_band_params (kg_proteins_align_banded*, kg_proteins_search_banded*): only the cells (i, j) with
+     *  |(i - j) - diagonal| <= band are filled; 0 <= band <= KG_BAND_MAX = 256; no default; reserved 0. */
+    class KgBandParams extends Structure {
+        public int band;
+        public int[] reserved = new int[3];
+        public KgBandParams() {
+            setFieldOrder(new String[] {"band", "reserved"});
+        }
+    }
+
+    /** struct kg_band_stats: band cells against full cells over the aligned pairs of a banded search. */
+    class KgBandStats extends Structure {
+        public long band_cells, full_cells;
+        public int band, reserved;
+        public KgBandStats() {
+            setFieldOrder(new String[] {"band_cells", "full_cells", "band", "reserved"});
+        }
+    }
+
     /** struct kg_merge_params (kg_table_merge_signatures*): on_conflict = KG_MERGE_KEEP (0), KG_MERGE_REPLACE (1) or KG_MERGE_DROP (2). */
     class KgMergeParams extends Structure {
         public int on_conflict, reserved;
@@ -577,6 +596,13 @@ public interface KmerGutsHip extends Library {
                               long maxTraceCells, int opsMode, Pointer out, Pointer paths, PointerByReference ops);
     int kg_proteins_align_ops_device(int device, KgAlignParams params, Pointer dSeq, long[] offsets, long nProt, int[] pairs, long nPairs,
                                      long maxTraceCells, int opsMode, Pointer out, Pointer paths, PointerByReference ops);
+    /** kg_proteins_align_ops in a band around one diagonal per pair; paths and ops may both be null (the records alone, opsMode 0) */
+    int kg_proteins_align_banded(int device, KgAlignParams params, byte[] seq, long[] offsets, long nProt, int[] pairs, long nPairs,
+                                 long maxTraceCells, int opsMode, Pointer out, Pointer paths, PointerByReference ops, KgBandParams band,
+                                 int[] diagonals);
+    int kg_proteins_align_banded_device(int device, KgAlignParams params, Pointer dSeq, long[] offsets, long nProt, int[] pairs, long nPairs,
+                                        long maxTraceCells, int opsMode, Pointer out, Pointer paths, PointerByReference ops,
+                                        KgBandParams band, int[] diagonals);
     long kg_opset_ops_count(Pointer set);
     int kg_opset_op_starts_copy(Pointer set, long first, long count, Pointer dst);   // long[count + 1]: opStart[first .. first + count]
     int kg_opset_ops_copy(Pointer set, long firstOp, long count, Pointer dst);       // int[count]
@@ -654,6 +680,15 @@ public interface KmerGutsHip extends Library {
                                            PointerByReference out);
     int kg_hitset_ungapped_copy(Pointer set, long first, long count, Pointer dst);   // kg_search_ungapped[count]
     int kg_hitset_ungapped_stats(Pointer set, KgUngappedStats out);
+    /** kg_proteins_search_filtered with every candidate aligned, and traced, in the band around its best seed diagonal */
+    int kg_proteins_search_banded(int device, KgSearchParams params, KgSeedParams seeds, KgAlignParams align, byte[] seq, long[] offsets,
+                                  long nProt, long nDb, long maxWindows, long maxPairs, int trace, long maxTraceCells, KgMaskParams mask,
+                                  int sides, KgUngappedParams ungapped, KgBandParams band, PointerByReference out);
+    int kg_proteins_search_banded_device(int device, KgSearchParams params, KgSeedParams seeds, KgAlignParams align, Pointer dSeq,
+                                         long[] offsets, long nProt, long nDb, long maxWindows, long maxPairs, int trace,
+                                         long maxTraceCells, KgMaskParams mask, int sides, KgUngappedParams ungapped, KgBandParams band,
+                                         PointerByReference out);
+    int kg_hitset_band_stats(Pointer set, KgBandStats out);
     /** kg_proteins_cluster_aligned (align = null: no alignment step) with every protein soft-masked for the 8-mer pass */
     int kg_proteins_cluster_masked(int device, KgClusterParams params, KgAlignParams align, byte[] seq, long[] offsets, long nProt,
                                    long maxWindows, KgMaskParams mask, PointerByReference out);

@@ -52,6 +52,8 @@ EXPORTS = (
     "kg_proteins_search_masked", "kg_proteins_search_masked_device", "kg_hitset_mask_stats",
     "kg_proteins_cluster_masked", "kg_proteins_cluster_masked_device", "kg_familyset_mask_stats",
     "kg_proteins_search_filtered", "kg_proteins_search_filtered_device", "kg_hitset_ungapped_copy", "kg_hitset_ungapped_stats",
+    "kg_proteins_align_banded", "kg_proteins_align_banded_device", "kg_proteins_search_banded", "kg_proteins_search_banded_device",
+    "kg_hitset_band_stats",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
@@ -462,6 +464,22 @@ class KgUngappedStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+BAND_MAX = 256                          # KG_BAND_MAX
+
+
+class KgBandParams(C.Structure):
+    """struct kg_band_params (kg_proteins_align_banded*, kg_proteins_search_banded*)."""
+    _fields_ = [("band", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class KgBandStats(C.Structure):
+    """struct kg_band_stats."""
+    _fields_ = [("band_cells", C.c_int64), ("full_cells", C.c_int64), ("band", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 # struct kg_search_ungapped (kg_hitset_ungapped_copy): one per hit record of a filtered search, same index
 SEARCH_UNGAPPED_DTYPE = np.dtype([("ungapped", "<i4"), ("diagonal", "<i4"), ("on_diagonal", "<i4"), ("reserved", "<i4")])
 assert SEARCH_UNGAPPED_DTYPE.itemsize == 16
@@ -643,6 +661,14 @@ def load() -> C.CDLL:
                                        C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(KgMaskParams), C.c_int,
                                        C.POINTER(KgUngappedParams), C.POINTER(vp)]
     lib.kg_hitset_ungapped_stats.argtypes = [vp, C.POINTER(KgUngappedStats)]
+    for name in ("kg_proteins_align_banded", "kg_proteins_align_banded_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgAlignParams), vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int, vp, vp,
+                                       C.POINTER(vp), C.POINTER(KgBandParams), vp]
+    for name in ("kg_proteins_search_banded", "kg_proteins_search_banded_device"):
+        getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgSearchParams), C.POINTER(KgSeedParams), C.POINTER(KgAlignParams), vp, vp,
+                                       C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(KgMaskParams), C.c_int,
+                                       C.POINTER(KgUngappedParams), C.POINTER(KgBandParams), C.POINTER(vp)]
+    lib.kg_hitset_band_stats.argtypes = [vp, C.POINTER(KgBandStats)]
     for name in ("kg_proteins_cluster_masked", "kg_proteins_cluster_masked_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
                                        C.POINTER(KgMaskParams), C.POINTER(vp)]

@@ -1,5 +1,6 @@
 // kg_host_align.hpp -- kg_proteins_align / kg_proteins_align_device: local alignment scores of protein pairs, and align_run, the
-// step kg_proteins_cluster_aligned puts between its edge test and its component rounds (kernels: kg_align.hpp).
+// step kg_proteins_cluster_aligned puts between its edge test and its component rounds (kernels: kg_align.hpp).  With a BandAsk
+// align_run is the alignment step of kg_proteins_align_banded and kg_proteins_search_banded (kernel: kg_band.hpp).
 // Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_derive.hpp (its offsets checks and its sequence
 // staging) and in front of kg_host_cluster.hpp and kg_host_search.hpp, which call align_run.
 #pragma once
@@ -44,13 +45,29 @@ int align_check_params(const kg_align_params *p)
     return KG_OK;
 }
 
-struct AlignTotals { int64_t cells = 0, skipped = 0; };
+struct AlignTotals { int64_t cells = 0, skipped = 0, band_cells = 0; };
+
+// kg_proteins_align_banded / kg_proteins_search_banded: one diagonal per pair (host) and the half-width W
+struct BandAsk { const int32_t *diag; int band; };
+
+static_assert(KG_BAND_MAX == kg::kBandMax && sizeof(kg_band_params) == 16 && sizeof(kg_band_stats) == 24, "the band of include/kmerguts_hip.h");
+
+int band_check_params(const kg_band_params *b)
+{
+    if (!b) return fail(KG_ERR_ARG, "null kg_band_params");
+    if (b->band < 0 || b->band > KG_BAND_MAX) return fail(KG_ERR_ARG, "band must be in [0, 256]");
+    if (b->reserved[0] != 0 || b->reserved[1] != 0 || b->reserved[2] != 0) return fail(KG_ERR_ARG, "kg_band_params.reserved must be 0");
+    return KG_OK;
+}
 
 // Pairs (a, b) of the proteins at d_seq / d_off (offsets: the same on the host) -> one AlignRec per pair in the call's scratch,
 // in pair order; *d_pairs_out: the uploaded pairs.  The pairs are handed out in descending order of their cells; a pair whose b
 // is longer than kAlignLdsCols goes to the launch that carries its stripes' last rows in device memory.
+// band: align_band_kernel in their place, one launch (its carry always fits LDS), the order and the cap by the band cells;
+// tot->cells stays the n * m of the aligned pairs and tot->band_cells is their band cells.
 int align_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_t *d_seq, const int64_t *d_off, const int64_t *offsets,
-              const int32_t *h_pairs, uint64_t n_pairs, const int32_t **d_pairs_out, kg::AlignRec **d_out, AlignTotals *tot)
+              const int32_t *h_pairs, uint64_t n_pairs, const int32_t **d_pairs_out, kg::AlignRec **d_out, AlignTotals *tot,
+              const BandAsk *band = nullptr)
 {
     hipStream_t s = t->stream;
     int rc;
@@ -59,12 +76,14 @@ int align_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_
     uint64_t slab_cols = 0;
     for (uint64_t k = 0; k < n_pairs; k++) {
         const int64_t n = offsets[h_pairs[2 * k] + 1] - offsets[h_pairs[2 * k]], m = offsets[h_pairs[2 * k + 1] + 1] - offsets[h_pairs[2 * k + 1]];
-        const bool skip = n * m > prm->max_cells;       // (n, m < 2^24: no overflow)
-        cells[k] = skip ? 0 : (uint64_t)(n * m);
-        if (skip) tot->skipped++; else tot->cells += n * m;
+        const int64_t counted = band ? kg::band_cells(n, m, band->band) : n * m;       // (n, m < 2^24: no overflow)
+        const bool skip = counted > prm->max_cells;
+        cells[k] = skip ? 0 : (uint64_t)counted;
+        if (skip) tot->skipped++; else { tot->cells += n * m; tot->band_cells += counted; }
         const bool lng = !skip && m > kg::kAlignLdsCols;
-        if (lng) slab_cols = std::max<uint64_t>(slab_cols, ((uint64_t)m + 63) / 64 * 64);
-        order[lng].push_back((uint32_t)k);
+        const bool slab = lng && !band;                 // (the band's carry always fits LDS)
+        if (slab) slab_cols = std::max<uint64_t>(slab_cols, ((uint64_t)m + 63) / 64 * 64);
+        order[slab].push_back((uint32_t)k);
     }
     for (auto &o : order) std::stable_sort(o.begin(), o.end(), [&](uint32_t x, uint32_t y) { return cells[x] > cells[y]; });
     const uint64_t n_short = order[0].size(), n_long = order[1].size();
@@ -75,11 +94,13 @@ int align_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_
     unsigned int *d_counter = nullptr;
     int8_t *d_matrix = nullptr;
     int2 *d_slab = nullptr;
+    int32_t *d_diag = nullptr;
     uint32_t long_grid = 0;
     if ((rc = sc.get(&d_pairs, std::max<uint64_t>(2 * n_pairs, 2))) || (rc = sc.get(&d_order, std::max<uint64_t>(n_pairs, 1))) ||
         (rc = sc.get(&d_counter, 2)) || (rc = sc.get(d_out, std::max<uint64_t>(n_pairs, 1))))
         return rc;
     if (prm->matrix && (rc = sc.get(&d_matrix, 21 * 21))) return rc;
+    if (band && (rc = sc.get(&d_diag, std::max<uint64_t>(n_pairs, 1)))) return rc;
     if (n_long) {
         long_grid = (uint32_t)std::min<uint64_t>({n_long, (uint64_t)kAlignLongGrid, std::max<uint64_t>(1, kAlignSlabBytes / (slab_cols * 8))});
         if ((rc = sc.get(&d_slab, (size_t)long_grid * slab_cols))) return rc;
@@ -89,10 +110,15 @@ int align_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_
     if (n_pairs) {
         HIP_TRY(hipMemcpyAsync(d_pairs, h_pairs, n_pairs * 8, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_order, order[0].data(), n_pairs * 4, hipMemcpyHostToDevice, s));
+        if (band) HIP_TRY(hipMemcpyAsync(d_diag, band->diag, n_pairs * 4, hipMemcpyHostToDevice, s));
     }
     if (d_matrix) HIP_TRY(hipMemcpyAsync(d_matrix, prm->matrix, 21 * 21, hipMemcpyHostToDevice, s));
     const int open = std::min(prm->gap_open, kg::kAlignGapCap), ext = std::min(prm->gap_extend, kg::kAlignGapCap);
-    if (n_short)
+    if (band && n_short)
+        hipLaunchKernelGGL(kg::align_band_kernel, dim3((uint32_t)std::min<uint64_t>(n_short, kAlignGrid)), dim3(kg::kWave), 0, s, d_seq, d_off,
+                           d_pairs, d_diag, d_order, (uint32_t)n_short, d_counter, d_matrix, open, ext, (int64_t)prm->max_cells, band->band,
+                           *d_out);
+    if (!band && n_short)
         hipLaunchKernelGGL(kg::align_pairs_kernel<false>, dim3((uint32_t)std::min<uint64_t>(n_short, kAlignGrid)), dim3(kg::kWave), 0, s, d_seq,
                            d_off, d_pairs, d_order, (uint32_t)n_short, d_counter, d_matrix, open, ext, (int64_t)prm->max_cells, nullptr,
                            (uint64_t)0, *d_out);
@@ -109,10 +135,10 @@ int align_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_
 struct AlignPathsAsk { int64_t max_trace_cells; kg_alignment_path *paths; int ops_mode = 0; kg_opset *set = nullptr; };
 int align_ops_empty(kg_table *t, kg_opset *set);
 int align_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_t *d_seq, const int64_t *d_off, const int32_t *pairs,
-                       int64_t n_pairs, const kg_alignment *aln, const AlignPathsAsk *ask);
+                       int64_t n_pairs, const kg_alignment *aln, const AlignPathsAsk *ask, const BandAsk *band);
 
 int align_impl(kg_table *t, const kg_align_params *prm, const uint8_t *h_seq, const uint8_t *d_seq_in, const int64_t *offsets, int64_t n_prot,
-               const int32_t *pairs, int64_t n_pairs, kg_alignment *out, const AlignPathsAsk *ask)
+               const int32_t *pairs, int64_t n_pairs, kg_alignment *out, const AlignPathsAsk *ask, const BandAsk *band)
 {
     if (n_pairs == 0) return ask && ask->set ? align_ops_empty(t, ask->set) : KG_OK;
     hipStream_t s = t->stream;
@@ -126,13 +152,14 @@ int align_impl(kg_table *t, const kg_align_params *prm, const uint8_t *h_seq, co
     const int32_t *d_pairs = nullptr;
     kg::AlignRec *d_out = nullptr;
     AlignTotals tot;
-    if ((rc = align_run(t, sc, prm, d_seq, d_off, offsets, pairs, (uint64_t)n_pairs, &d_pairs, &d_out, &tot))) return rc;
+    if ((rc = align_run(t, sc, prm, d_seq, d_off, offsets, pairs, (uint64_t)n_pairs, &d_pairs, &d_out, &tot, band))) return rc;
     HIP_TRY(hipMemcpy(out, d_out, (size_t)n_pairs * sizeof(kg_alignment), hipMemcpyDeviceToHost));
-    return ask ? align_paths_behind(t, sc, prm, d_seq, d_off, pairs, n_pairs, out, ask) : KG_OK;
+    return ask ? align_paths_behind(t, sc, prm, d_seq, d_off, pairs, n_pairs, out, ask, band) : KG_OK;
 }
 
 int align_entry(int device, const kg_align_params *prm, const uint8_t *h_seq, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
-                const int32_t *pairs, int64_t n_pairs, kg_alignment *out, const AlignPathsAsk *ask_in = nullptr, kg_opset **ops_out = nullptr)
+                const int32_t *pairs, int64_t n_pairs, kg_alignment *out, const AlignPathsAsk *ask_in = nullptr, kg_opset **ops_out = nullptr,
+                const BandAsk *band = nullptr)
 {
     if (!prm) return fail(KG_ERR_ARG, "null kg_align_params");
     int rc;
@@ -145,6 +172,7 @@ int align_entry(int device, const kg_align_params *prm, const uint8_t *h_seq, co
     if (n_pairs && (!pairs || !out)) return fail(KG_ERR_ARG, "null argument");
     if (ask_in && ask_in->max_trace_cells < 1) return fail(KG_ERR_ARG, "max_trace_cells must be >= 1");
     if (ask_in && n_pairs && !ask_in->paths) return fail(KG_ERR_ARG, "null paths");
+    if (band && n_pairs && !band->diag) return fail(KG_ERR_ARG, "null diagonals");
     for (int64_t k = 0; k < 2 * n_pairs; k++)
         if (pairs[k] < 0 || pairs[k] >= n_prot)
             return fail(KG_ERR_ARG, "pair " + kmer_text(k / 2) + ": protein index " + kmer_text(pairs[k]) + " is outside [0, n_prot)");
@@ -162,7 +190,7 @@ int align_entry(int device, const kg_align_params *prm, const uint8_t *h_seq, co
         ask = &with_set;
     }
     rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
-    if (!rc) rc = align_impl(cs.t, prm, h_seq, d_seq, offsets, n_prot, pairs, n_pairs, out, ask);
+    if (!rc) rc = align_impl(cs.t, prm, h_seq, d_seq, offsets, n_prot, pairs, n_pairs, out, ask, band);
     if (!rc && ops_out) return hand_out(cs, set, ops_out);      // (the scratch, back in the cache, goes to the driver there)
     cs.t->cache.release_all();                          // scratch goes back to the driver
     return rc;

@@ -6,6 +6,7 @@
 // kg_proteins_search_masked is either call with the window kernels reading the seeding copy of kg_host_mask.hpp (the masked
 // residues of one or both sides turned into non-residues); the alignment and the trace read the original.
 // kg_proteins_search_filtered is any of them with the ungapped stage of kg_ungapped.hpp between the join and the alignment.
+// kg_proteins_search_banded is that call with every candidate aligned, and traced, in a band around its g* (kg_band.hpp).
 // search_impl is a driver over three stages: search_pairs (the front half the cluster call has too, by the functions of
 // kg_host_derive.hpp: staging, block counts, count pass, one-pass cap, window-pairs pass), search_candidates (search_runs, the
 // join and the per-query cut) or, chosen by the call, search_candidates_ungapped (search_runs, the join with the diagonals, the
@@ -32,6 +33,8 @@ struct kg_hitset {
     Detached d_ung;                     // kg_proteins_search_filtered only: one kg_search_ungapped per hit record
     bool has_ung = false;
     kg_ungapped_stats ust = {};
+    bool has_band = false;              // kg_proteins_search_banded only: the band's counts over the aligned pairs
+    kg_band_stats bst = {};
     const int64_t *op_starts() const { return (const int64_t *)d_ops.p; }
     const uint32_t *ops() const { return (const uint32_t *)(d_ops.p + ((size_t)count + 1) * 8); }
     const int64_t *starts() const { return (const int64_t *)d_block.p; }
@@ -149,7 +152,7 @@ int seed_count(Deriver &dv, const SeedPlan *seed, unsigned long long *d_count, u
 // The ordered records -> one path record each, same index, in a block of the set's own.  KG_TRACE_HITS traces the records with
 // status hit, KG_TRACE_ALL every aligned record with score >= 1; a is the query, b the target.
 int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, const uint8_t *d_seq, const int64_t *d_off, int64_t n_db,
-                        const kg_search_hit *d_hits, uint64_t NK, const SearchPathsAsk &ask, kg_hitset *set)
+                        const kg_search_hit *d_hits, uint64_t NK, const SearchPathsAsk &ask, kg_hitset *set, const kg_band_params *band)
 {
     int rc;
     if ((rc = dalloc_detached(t, &set->d_paths.p, std::max<uint64_t>(NK, 1) * sizeof(kg_alignment_path)))) return rc;
@@ -172,7 +175,16 @@ int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, con
             ends[k] = TraceEnd{h.score, h.end_query, h.end_target, which == KG_TRACE_ALL ? h.status != 2 && h.score >= 1 : h.status == 0};
         }
         kg::TracePath *d_paths = nullptr;
-        if ((rc = trace_run(t, sc, al, d_seq, d_off, pairs.data(), ends, NK, ask.max_trace_cells, &d_paths, &tot, ops.mode ? &ops : nullptr)))
+        std::vector<int32_t> diag;                      // under a band: g* of every ordered record, from its ungapped record
+        if (band) {
+            std::vector<kg_search_ungapped> ung(NK);
+            HIP_TRY(hipMemcpy(ung.data(), set->d_ung.p, NK * sizeof(kg_search_ungapped), hipMemcpyDeviceToHost));
+            diag.resize(NK);
+            for (uint64_t k = 0; k < NK; k++) diag[k] = ung[k].diagonal;
+        }
+        const BandAsk b{diag.data(), band ? band->band : 0};
+        if ((rc = trace_run(t, sc, al, d_seq, d_off, pairs.data(), ends, NK, ask.max_trace_cells, &d_paths, &tot, ops.mode ? &ops : nullptr,
+                            band ? &b : nullptr)))
             return rc;
         HIP_TRY(hipMemcpy(set->d_paths.p, d_paths, NK * sizeof(kg_alignment_path), hipMemcpyDeviceToDevice));
     }
@@ -205,6 +217,7 @@ struct SearchArgs {
     const MaskPlan *mask;
     int sides;
     const kg_ungapped_params *ung = nullptr;    // kg_proteins_search_filtered: the ungapped stage in search_candidates' place
+    const kg_band_params *band = nullptr;       // kg_proteins_search_banded: the alignment and the trace in a band around g*
 };
 
 // what search_impl sets up for its stages: they allocate from sc, enqueue on t->stream and record the timing events ev[1 .. 5]
@@ -638,7 +651,17 @@ int search_finish(SearchCall &c, const SearchPairs &pairs, const SearchCands &cd
     if (NK > 0) {
         const int32_t *d_pairs = nullptr;
         kg::AlignRec *d_aln = nullptr;
-        if ((rc = align_run(t, c.sc, a.al, c.d_seq, pairs.d_off, a.offsets, h_pairs.data(), NK, &d_pairs, &d_aln, &atot))) return rc;
+        std::vector<int32_t> diag;                      // under a band: g* of every kept candidate, in the kept order
+        if (a.band) {
+            std::vector<kg::UngappedRec> ung(NK);
+            HIP_TRY(hipMemcpyAsync(ung.data(), cd.d_ung, NK * sizeof(kg::UngappedRec), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            diag.resize(NK);
+            for (uint64_t k = 0; k < NK; k++) diag[k] = ung[k].diagonal;
+        }
+        const BandAsk b{diag.data(), a.band ? a.band->band : 0};
+        if ((rc = align_run(t, c.sc, a.al, c.d_seq, pairs.d_off, a.offsets, h_pairs.data(), NK, &d_pairs, &d_aln, &atot, a.band ? &b : nullptr)))
+            return rc;
         hipLaunchKernelGGL(kg::search_order_kernel, dim3(grid_of((uint64_t)n_q, 256 / kg::kWave)), dim3(256), 0, s, d_pairs, d_aln, cd.d_shared,
                            (const int64_t *)block, (uint32_t)n_q, (int64_t)a.al->min_ratio_pct, (int)(a.al->ref == KG_ALIGN_REF_MEMBER),
                            (int2 *)(block + start_bytes), c.words);
@@ -688,8 +711,14 @@ int search_finish(SearchCall &c, const SearchPairs &pairs, const SearchCands &cd
         set->ust.ms_ungapped = cd.ms_ungapped;
         set->has_ung = true;
     }
+    if (a.band) {
+        set->bst.band_cells = atot.band_cells;
+        set->bst.full_cells = atot.cells;
+        set->bst.band = a.band->band;
+        set->has_band = true;
+    }
     set->count = (int64_t)NK;
-    return a.ask.trace ? search_paths_behind(t, c.sc, a.al, c.d_seq, pairs.d_off, n_db, set->hits(), NK, a.ask, set) : KG_OK;
+    return a.ask.trace ? search_paths_behind(t, c.sc, a.al, c.d_seq, pairs.d_off, n_db, set->hits(), NK, a.ask, set, a.band) : KG_OK;
 }
 
 int search_impl(kg_table *t, const SearchArgs &a, kg_hitset *set)
@@ -729,7 +758,7 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
                  const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows, int64_t max_pairs, kg_hitset **out,
                  SearchPathsAsk ask = {}, std::optional<const kg_seed_params *> seeds = std::nullopt,
                  std::optional<const kg_mask_params *> mask = std::nullopt, int sides = 0,
-                 std::optional<const kg_ungapped_params *> ung = std::nullopt)
+                 std::optional<const kg_ungapped_params *> ung = std::nullopt, std::optional<const kg_band_params *> band = std::nullopt)
 {
     if (!out) return fail(KG_ERR_ARG, "null argument");
     *out = nullptr;
@@ -752,6 +781,8 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
         if ((*ung)->reserved[0] != 0 || (*ung)->reserved[1] != 0 || (*ung)->reserved[2] != 0)
             return fail(KG_ERR_ARG, "kg_ungapped_params.reserved must be 0");
     }
+    if (band)
+        if (int rc = band_check_params(*band)) return rc;
     if (!al) return fail(KG_ERR_ARG, "null kg_align_params");
     if (int rc = align_check_params(al)) return rc;
     if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
@@ -773,7 +804,7 @@ int search_entry(int device, const kg_search_params *prm, const kg_align_params 
     if (!set) return fail(KG_ERR_NOMEM, "out of host memory");
     set->device = device;
     const SearchArgs args{prm, al, h_seq, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, ask, seeds ? &plan : nullptr, mask ? &mplan : nullptr, sides,
-                          ung ? *ung : nullptr};
+                          ung ? *ung : nullptr, band ? *band : nullptr};
     int rc = d_seq && hipDeviceSynchronize() != hipSuccess ? fail(KG_ERR_DEVICE, "hipDeviceSynchronize failed") : KG_OK;
     if (!rc) rc = search_impl(cs.t, args, set);
     cs.t->cache.release_all();                          // scratch goes back to the driver
@@ -896,6 +927,32 @@ int kg_proteins_search_filtered_device(int device, const kg_search_params *p, co
     return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, {trace, max_trace_cells},
                         seeds ? std::optional<const kg_seed_params *>(seeds) : std::nullopt,
                         mask ? std::optional<const kg_mask_params *>(mask) : std::nullopt, sides, ungapped);
+}
+
+int kg_proteins_search_banded(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                              const uint8_t *seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                              int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides,
+                              const kg_ungapped_params *ungapped, const kg_band_params *band, kg_hitset **out)
+{
+    return search_entry(device, p, align, seq, nullptr, offsets, n_prot, n_db, max_windows, max_pairs, out, {trace, max_trace_cells},
+                        seeds ? std::optional<const kg_seed_params *>(seeds) : std::nullopt,
+                        mask ? std::optional<const kg_mask_params *>(mask) : std::nullopt, sides, ungapped, band);
+}
+
+int kg_proteins_search_banded_device(int device, const kg_search_params *p, const kg_seed_params *seeds, const kg_align_params *align,
+                                     const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot, int64_t n_db, int64_t max_windows,
+                                     int64_t max_pairs, int trace, int64_t max_trace_cells, const kg_mask_params *mask, int sides,
+                                     const kg_ungapped_params *ungapped, const kg_band_params *band, kg_hitset **out)
+{
+    return search_entry(device, p, align, nullptr, d_seq, offsets, n_prot, n_db, max_windows, max_pairs, out, {trace, max_trace_cells},
+                        seeds ? std::optional<const kg_seed_params *>(seeds) : std::nullopt,
+                        mask ? std::optional<const kg_mask_params *>(mask) : std::nullopt, sides, ungapped, band);
+}
+
+int kg_hitset_band_stats(const kg_hitset *s, kg_band_stats *out)
+{
+    if (s && !s->has_band) return fail(KG_ERR_ARG, "kg_hitset_band_stats: the set was made without a band");
+    return copy_stats(s, s ? &s->bst : nullptr, out);
 }
 
 int kg_hitset_ungapped_copy(const kg_hitset *s, int64_t first, int64_t count, kg_search_ungapped *dst)

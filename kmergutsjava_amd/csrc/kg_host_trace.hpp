@@ -38,9 +38,11 @@ struct TraceEnd { int score, end_a, end_b; bool want; };
 // launch, whose few workgroups own large slabs, so that one large pair does not narrow the launch of the small ones.
 // ops: the walk records its columns into staging words (trace_columns_kernel in trace_pairs_kernel's place), the op counts are
 // summed in pair order and ops_fill_kernel writes the ops; tot->ms then covers that work as well.
+// band: the same boxes, launches and slabs with the cells outside the band of pair k's diagonal forced to H = 0
+// (trace_band_kernel, trace_band_columns_kernel).
 int trace_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_t *d_seq, const int64_t *d_off, const int32_t *h_pairs,
               const std::vector<TraceEnd> &ends, uint64_t n_pairs, int64_t max_trace_cells, kg::TracePath **d_out, TraceTotals *tot,
-              OpsAsk *ops = nullptr)
+              OpsAsk *ops = nullptr, const BandAsk *band = nullptr)
 {
     hipStream_t s = t->stream;
     int rc;
@@ -94,6 +96,14 @@ int trace_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_
     unsigned int *d_words = nullptr;                    // the two hand-out counters and the error bits
     int8_t *d_matrix = nullptr;
     int2 *d_carry = nullptr;
+    kg::TraceBandJob *d_bjobs = nullptr;                // under a band the jobs carry their diagonal and W
+    std::vector<kg::TraceBandJob> bjobs;
+    if (band) {
+        bjobs.reserve(n_pairs);
+        for (const kg::TraceJob &j : jobs)
+            bjobs.push_back(kg::TraceBandJob{j.a, j.b, j.score, j.end_a, j.end_b, j.slot, band->diag[j.slot], band->band});
+        if ((rc = sc.get(&d_bjobs, std::max<uint64_t>(n_pairs, 1)))) return rc;
+    }
     if ((rc = sc.get(&d_jobs, std::max<uint64_t>(n_pairs, 1))) || (rc = sc.get(&d_words, kg::kTraceWords + 1)) ||
         (rc = sc.get(d_out, std::max<uint64_t>(n_pairs, 1))) ||
         (rc = sc.get(&d_dirs, std::max<uint64_t>({(uint64_t)short_grid * words[0], (uint64_t)long_grid * words[1], 1}))))
@@ -116,9 +126,25 @@ int trace_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_
     HIP_TRY(hipMemsetAsync(d_words, 0, (kg::kTraceWords + 1) * 4, s));
     if (n_pairs) HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), n_pairs * sizeof(kg::TraceJob), hipMemcpyHostToDevice, s));
     if (d_matrix) HIP_TRY(hipMemcpyAsync(d_matrix, prm->matrix, 21 * 21, hipMemcpyHostToDevice, s));
+    if (band && n_pairs) HIP_TRY(hipMemcpyAsync(d_bjobs, bjobs.data(), n_pairs * sizeof(kg::TraceBandJob), hipMemcpyHostToDevice, s));
     const int open = std::min(prm->gap_open, kg::kAlignGapCap), ext = std::min(prm->gap_extend, kg::kAlignGapCap);
     // (one stream: the second launch starts behind the first, so the two share the direction words)
-    if (ops) {
+    if (band) {
+        if (ops && n_short)
+            hipLaunchKernelGGL(kg::trace_band_columns_kernel<false>, dim3(short_grid), dim3(kg::kWave), 0, s, d_seq, d_off, d_bjobs,
+                               (uint32_t)n_short, d_words, d_matrix, open, ext, max_trace_cells, d_dirs, words[0], nullptr, (uint64_t)0, *d_out,
+                               d_oa);
+        if (ops && n_long)
+            hipLaunchKernelGGL(kg::trace_band_columns_kernel<true>, dim3(long_grid), dim3(kg::kWave), 0, s, d_seq, d_off, d_bjobs + n_short,
+                               (uint32_t)n_long, d_words, d_matrix, open, ext, max_trace_cells, d_dirs, words[1], d_carry, carry_cols, *d_out,
+                               d_oa);
+        if (!ops && n_short)
+            hipLaunchKernelGGL(kg::trace_band_kernel<false>, dim3(short_grid), dim3(kg::kWave), 0, s, d_seq, d_off, d_bjobs, (uint32_t)n_short,
+                               d_words, d_matrix, open, ext, max_trace_cells, d_dirs, words[0], nullptr, (uint64_t)0, *d_out);
+        if (!ops && n_long)
+            hipLaunchKernelGGL(kg::trace_band_kernel<true>, dim3(long_grid), dim3(kg::kWave), 0, s, d_seq, d_off, d_bjobs + n_short,
+                               (uint32_t)n_long, d_words, d_matrix, open, ext, max_trace_cells, d_dirs, words[1], d_carry, carry_cols, *d_out);
+    } else if (ops) {
         if (n_short)
             hipLaunchKernelGGL(kg::trace_columns_kernel<false>, dim3(short_grid), dim3(kg::kWave), 0, s, d_seq, d_off, d_jobs, (uint32_t)n_short,
                                d_words, d_matrix, open, ext, max_trace_cells, d_dirs, words[0], nullptr, (uint64_t)0, *d_out, d_oa);
@@ -129,7 +155,7 @@ int trace_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_
     } else if (n_short)
         hipLaunchKernelGGL(kg::trace_pairs_kernel<false>, dim3(short_grid), dim3(kg::kWave), 0, s, d_seq, d_off, d_jobs, (uint32_t)n_short,
                            d_words, d_matrix, open, ext, max_trace_cells, d_dirs, words[0], nullptr, (uint64_t)0, *d_out);
-    if (!ops && n_long)
+    if (!band && !ops && n_long)
         hipLaunchKernelGGL(kg::trace_pairs_kernel<true>, dim3(long_grid), dim3(kg::kWave), 0, s, d_seq, d_off, d_jobs + n_short,
                            (uint32_t)n_long, d_words, d_matrix, open, ext, max_trace_cells, d_dirs, words[1], d_carry, carry_cols, *d_out);
     HIP_TRY(hipGetLastError());
@@ -172,7 +198,7 @@ int trace_run(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_
 
 // what kg_proteins_align_paths does behind align_run: every aligned pair asks for a path
 int align_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *prm, const uint8_t *d_seq, const int64_t *d_off, const int32_t *pairs,
-                       int64_t n_pairs, const kg_alignment *aln, const AlignPathsAsk *ask)
+                       int64_t n_pairs, const kg_alignment *aln, const AlignPathsAsk *ask, const BandAsk *band)
 {
     std::vector<TraceEnd> ends((size_t)n_pairs);
     for (int64_t k = 0; k < n_pairs; k++) ends[(size_t)k] = TraceEnd{aln[k].score, aln[k].end_a, aln[k].end_b, aln[k].status == 0};
@@ -180,7 +206,7 @@ int align_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *prm, con
     TraceTotals tot;
     OpsAsk ops{ask->ops_mode};
     if (int rc = trace_run(t, sc, prm, d_seq, d_off, pairs, ends, (uint64_t)n_pairs, ask->max_trace_cells, &d_paths, &tot,
-                           ask->set ? &ops : nullptr))
+                           ask->set ? &ops : nullptr, band))
         return rc;
     HIP_TRY(hipMemcpy(ask->paths, d_paths, (size_t)n_pairs * sizeof(kg_alignment_path), hipMemcpyDeviceToHost));
     if (kg_opset *set = ask->set) {
@@ -222,9 +248,43 @@ int align_ops_entry(int device, const kg_align_params *p, const uint8_t *h_seq, 
     return align_entry(device, p, h_seq, d_seq, offsets, n_prot, pairs, n_pairs, out, &ask, ops);
 }
 
+// kg_proteins_align_banded: the records alone, with paths, or with paths and ops
+int align_banded_entry(int device, const kg_align_params *p, const uint8_t *h_seq, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
+                       const int32_t *pairs, int64_t n_pairs, int64_t max_trace_cells, int ops_mode, kg_alignment *out, kg_alignment_path *paths,
+                       kg_opset **ops, const kg_band_params *band, const int32_t *diagonals)
+{
+    if (ops) *ops = nullptr;
+    if (int rc = band_check_params(band)) return rc;
+    if (ops && !paths && n_pairs) return fail(KG_ERR_ARG, "ops without paths");
+    if (!ops && ops_mode != 0) return fail(KG_ERR_ARG, "ops_mode must be 0 without ops");
+    const BandAsk b{diagonals, band->band};
+    if (ops) {
+        if (ops_mode != KG_TRACE_OPS && ops_mode != KG_TRACE_OPS_EQX) return fail(KG_ERR_ARG, "ops_mode must be KG_TRACE_OPS or KG_TRACE_OPS_EQX");
+        const AlignPathsAsk ask{max_trace_cells, paths, ops_mode};
+        return align_entry(device, p, h_seq, d_seq, offsets, n_prot, pairs, n_pairs, out, &ask, ops, &b);
+    }
+    const AlignPathsAsk ask{max_trace_cells, paths};
+    return align_entry(device, p, h_seq, d_seq, offsets, n_prot, pairs, n_pairs, out, paths ? &ask : nullptr, nullptr, &b);
+}
+
 }  // namespace
 
 extern "C" {
+
+int kg_proteins_align_banded(int device, const kg_align_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
+                             const int32_t *pairs, int64_t n_pairs, int64_t max_trace_cells, int ops_mode, kg_alignment *out,
+                             kg_alignment_path *paths, kg_opset **ops, const kg_band_params *band, const int32_t *diagonals)
+{
+    return align_banded_entry(device, p, seq, nullptr, offsets, n_prot, pairs, n_pairs, max_trace_cells, ops_mode, out, paths, ops, band, diagonals);
+}
+
+int kg_proteins_align_banded_device(int device, const kg_align_params *p, const uint8_t *d_seq, const int64_t *offsets, int64_t n_prot,
+                                    const int32_t *pairs, int64_t n_pairs, int64_t max_trace_cells, int ops_mode, kg_alignment *out,
+                                    kg_alignment_path *paths, kg_opset **ops, const kg_band_params *band, const int32_t *diagonals)
+{
+    return align_banded_entry(device, p, nullptr, d_seq, offsets, n_prot, pairs, n_pairs, max_trace_cells, ops_mode, out, paths, ops, band,
+                              diagonals);
+}
 
 int kg_proteins_align_paths(int device, const kg_align_params *p, const uint8_t *seq, const int64_t *offsets, int64_t n_prot,
                             const int32_t *pairs, int64_t n_pairs, int64_t max_trace_cells, kg_alignment *out, kg_alignment_path *paths)

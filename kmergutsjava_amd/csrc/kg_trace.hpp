@@ -8,7 +8,10 @@
 //   trace_columns_kernel<kLong>   the same pass with the walk's columns recorded: two bits a column into the job's staging words,
 //                                 and the record's op count (kg_ops.hpp turns the staged columns into ops)
 //
-// Both are instantiations of trace_pairs_body; the recording is compiled out of trace_pairs_kernel.
+//   trace_band_kernel<kLong>, trace_band_columns_kernel<kLong>   the two under a band (kg_band.hpp): the cells of the box outside
+//                                 the band of the job's diagonal have H = 0
+//
+// All are instantiations of trace_pairs_body; the recording is compiled out of trace_pairs_kernel, the band out of both.
 // Forward.  The wave is kg_align.hpp's: lane l owns row i0 + l of a 64-row stripe and stands in column j = t - l at step t, H-up,
 // F-up and the residue come down the lanes by DPP, the stripe's last row is carried in LDS (kLong = false: box columns up to
 // kAlignLdsCols) or in a slab of device memory (kLong = true).  Each cell adds four bits: the source of H (0 none: H = 0,
@@ -33,6 +36,8 @@
 // counts are and is 0 for a record without a path.
 #pragma once
 
+#include <type_traits>
+
 #include "kg_align.hpp"
 
 namespace kg {
@@ -45,6 +50,7 @@ constexpr unsigned kTraceErrSlab = 4u;                  //       a traced pair d
 
 // One pair to hand out: the proteins, what the alignment pass found (score 0: no path is asked for) and the record's place
 struct TraceJob { int a, b, score, end_a, end_b, slot; };
+struct TraceBandJob { int a, b, score, end_a, end_b, slot, diag, band; };      // the same under a band: diagonal g and half-width W
 // kg_ops.hpp / trace_columns_kernel: where record `slot`'s staging words begin, and its end cell (in record order)
 struct OpsRec { uint64_t stage_at; int end_a, end_b; };
 // what the recording needs beyond the plain pass, behind one pointer: trace_pairs_kernel<true> leaves two scalar registers free,
@@ -69,9 +75,13 @@ __host__ __device__ constexpr uint64_t trace_stripe_words(uint64_t mb)
 // instantiation's counter first or second.  dirs: workgroup w's direction words are dirs[w * dir_words ..); carry (kLong only):
 // its stripe carry is carry[w * carry_cols ..).
 // oa (kCols only): where the columns and the op counts go.
-template <bool kLong, bool kCols>
+// kBand (kg_band.hpp's rule): a job carries its diagonal g and W, and a cell of the box with |(i - j) - g| > W has H = 0 as a cell
+// outside the box has.  Nothing else differs.  The pass has no scalar register to spare (trace_pairs_kernel<true>), so what it
+// keeps of the two values is lane-dependent and lives in vector registers: lane - g - W and lane - g + W.
+template <bool kLong, bool kCols, bool kBand = false>
 __device__ __forceinline__ void trace_pairs_body(const uint8_t *__restrict__ seq, const int64_t *__restrict__ off,
-                                                 const TraceJob *__restrict__ jobs, uint32_t n_jobs, unsigned int *__restrict__ words,
+                                                 const std::conditional_t<kBand, TraceBandJob, TraceJob> *__restrict__ jobs, uint32_t n_jobs,
+                                                 unsigned int *__restrict__ words,
                                                  const int8_t *__restrict__ matrix, int gap_open, int gap_extend, int64_t max_trace_cells,
                                                  uint32_t *__restrict__ dirs, uint64_t dir_words, int2 *__restrict__ carry, uint64_t carry_cols,
                                                  TracePath *__restrict__ out, const TraceOpsArgs *oa)
@@ -87,7 +97,12 @@ __device__ __forceinline__ void trace_pairs_body(const uint8_t *__restrict__ seq
 
     // One exit and one latch, only wave-uniform branches on the way round: see align_pairs_kernel.
     for (uint32_t k = align_next_pair(counter, lane); k < n_jobs; k = align_next_pair(counter, lane)) {
-        const TraceJob job = jobs[k];
+        const auto job = jobs[k];
+        [[maybe_unused]] int band_first = 0, band_last = 0;    // kBand: lane - g - W and lane - g + W (|g| > 2^25 misses every box: clamped)
+        if constexpr (kBand) {
+            band_first = lane - min(max(job.diag, -(1 << 25)), 1 << 25) - job.band;
+            band_last = band_first + 2 * job.band;
+        }
         const int64_t at_a = off[job.a], at_b = off[job.b];
         const int n = (int)(off[job.a + 1] - at_a), m = (int)(off[job.b + 1] - at_b);
         const int score = __builtin_amdgcn_readfirstlane(job.score);
@@ -110,6 +125,14 @@ __device__ __forceinline__ void trace_pairs_body(const uint8_t *__restrict__ seq
             const bool row = i < na, first = i0 == 0, last = i0 + kWave >= na;
             const int row_base = (row ? (int)aa_code_of_rt((char)seq[at_a + i]) : 20) * kAlignRowStride;
             uint32_t *const dst = my_dirs + (uint64_t)(i0 / kWave) * stripe_words + lane;
+            [[maybe_unused]] int band_lo = 0;           // kBand: the row's in-band columns of the box are band_lo .. band_lo + band_width
+            [[maybe_unused]] unsigned band_width = 0;
+            if constexpr (kBand) {
+                const int hi = min(mb - 1, i0 + band_last);
+                band_lo = max(0, i0 + band_first);
+                band_width = hi >= band_lo ? (unsigned)(hi - band_lo) : 0u;
+                if (hi < band_lo) band_lo = kAlignNeg;  // no in-band column: j - band_lo is above every width
+            }
             int h_left = 0, e = kAlignNeg;
             int h_cur = 0, f_cur = kAlignNeg;
             int h_diag = 0;
@@ -138,7 +161,11 @@ __device__ __forceinline__ void trace_pairs_body(const uint8_t *__restrict__ seq
                     const int f = max(f_up, f_from_h) - gap_extend;
                     const int d = h_diag + s_now;
                     int h = max(max(0, d), max(e, f));
-                    const bool inside = row && (unsigned)j < (unsigned)mb;
+                    // in_box: a cell of the box.  Lane 63 carries every one of them, so that the next stripe reads no column that this
+                    // stripe has not written; under a band the ones outside it carry H = 0 and the F the recurrence gives them.
+                    const bool in_box = row && (unsigned)j < (unsigned)mb;
+                    bool inside = in_box;
+                    if constexpr (kBand) inside = row && (unsigned)(j - band_lo) <= band_width;
                     h = inside ? h : 0;
                     const uint32_t src = h == 0 ? 0u : h == d ? 1u : h == e ? 2u : 3u;                          // diagonal, then E, then F
                     word |= (src | e_open | f_open) << (kTraceCellBits * (q & (kTraceCellsPerWord - 1)));
@@ -147,7 +174,7 @@ __device__ __forceinline__ void trace_pairs_body(const uint8_t *__restrict__ seq
                         word = 0;
                     }
                     if (inside && i == na - 1 && j == mb - 1) end_h = h;
-                    if (!last && lane == kWave - 1 && inside) {
+                    if (!last && lane == kWave - 1 && in_box) {
                         if (kLong) carry_g[j] = make_int2(h, f); else lds_carry[j] = make_int2(h, f);
                     }
                     h_diag = h_up;
@@ -306,6 +333,31 @@ __global__ __launch_bounds__(kWave) void trace_columns_kernel(const uint8_t *__r
 {
     trace_pairs_body<kLong, true>(seq, off, jobs, n_jobs, words, matrix, gap_open, gap_extend, max_trace_cells, dirs, dir_words, carry,
                                   carry_cols, out, oa);
+}
+
+// the same two passes under a band: kg_proteins_align_banded and kg_proteins_search_banded
+template <bool kLong>
+__global__ __launch_bounds__(kWave) void trace_band_kernel(const uint8_t *__restrict__ seq, const int64_t *__restrict__ off,
+                                                           const TraceBandJob *__restrict__ jobs, uint32_t n_jobs,
+                                                           unsigned int *__restrict__ words, const int8_t *__restrict__ matrix,
+                                                           int gap_open, int gap_extend, int64_t max_trace_cells,
+                                                           uint32_t *__restrict__ dirs, uint64_t dir_words, int2 *__restrict__ carry,
+                                                           uint64_t carry_cols, TracePath *__restrict__ out)
+{
+    trace_pairs_body<kLong, false, true>(seq, off, jobs, n_jobs, words, matrix, gap_open, gap_extend, max_trace_cells, dirs, dir_words, carry,
+                                         carry_cols, out, nullptr);
+}
+
+template <bool kLong>
+__global__ __launch_bounds__(kWave) void trace_band_columns_kernel(const uint8_t *__restrict__ seq, const int64_t *__restrict__ off,
+                                                                   const TraceBandJob *__restrict__ jobs, uint32_t n_jobs,
+                                                                   unsigned int *__restrict__ words, const int8_t *__restrict__ matrix,
+                                                                   int gap_open, int gap_extend, int64_t max_trace_cells,
+                                                                   uint32_t *__restrict__ dirs, uint64_t dir_words, int2 *__restrict__ carry,
+                                                                   uint64_t carry_cols, TracePath *__restrict__ out, const TraceOpsArgs *oa)
+{
+    trace_pairs_body<kLong, true, true>(seq, off, jobs, n_jobs, words, matrix, gap_open, gap_extend, max_trace_cells, dirs, dir_words, carry,
+                                        carry_cols, out, oa);
 }
 
 }  // namespace kg

@@ -16,6 +16,7 @@
 #include "kg_derive.hpp"
 #include "kg_cluster.hpp"
 #include "kg_align.hpp"
+#include "kg_band.hpp"
 #include "kg_trace.hpp"
 #include "kg_ops.hpp"
 #include "kg_search.hpp"

@@ -807,7 +807,7 @@ def alignment_text(query, target, hit, path, ops, width: int = 60, query_id: str
 
 def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1, max_cells: int = N.ALIGN_DEFAULT_MAX_CELLS, matrix=None,
                    device: int = 0, device_ptr: Optional[int] = None, paths: bool = False,
-                   max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS, ops: Optional[str] = None):
+                   max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS, ops: Optional[str] = None, band: Optional[int] = None, diagonals=None):
     """Local alignment scores of protein pairs, on the GPU (include/kmerguts_hip.h kg_proteins_align states the rule): affine
     gaps, the built-in matrix is BLOSUM62 (align_scores.BLOSUM62); matrix: 21 x 21 in code order.  seq / offsets /
     device_ptr as for cluster_proteins; pairs: int32[n_pairs][2] of (a, b) protein indices, any order, repeats allowed.
@@ -817,7 +817,12 @@ def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1,
     cells, not traced).
     ops="m" | "eqx" (needs paths=True): the alignments themselves (kg_proteins_align_ops): -> (records, paths, op_start
     int64[n_pairs + 1], ops uint32[op_start[-1]]); pair k's ops are ops[op_start[k] : op_start[k + 1]], each len << 4 | code, in
-    alignment order; "m" writes M, I and D, "eqx" writes = and X for M.  cigar() gives the string."""
+    alignment order; "m" writes M, I and D, "eqx" writes = and X for M.  cigar() gives the string.
+    band=W with diagonals=int32[n_pairs] (kg_proteins_align_banded): pair k is aligned, and traced, over the cells (i, j) with
+    |(i - j) - diagonals[k]| <= W only; 0 <= W <= _native.BAND_MAX.  A pair is then skipped iff min(n m, min(n, m) (2 W + 1)) is
+    over max_cells.  The results have the shapes above."""
+    if (band is None) != (diagonals is None):
+        raise ValueError("band and diagonals go together")
     if ops is not None and ops not in N.OPS_MODES:
         raise ValueError("ops must be None, 'm' or 'eqx'")
     if ops is not None and not paths:
@@ -832,6 +837,29 @@ def align_proteins(seq, offsets, pairs, gap_open: int = 11, gap_extend: int = 1,
     out = np.zeros(len(pr), dtype=N.ALIGNMENT_DTYPE)
     lib = N.load()
     pp, op = _ptr(pr), _ptr(out)
+    if band is not None:
+        dg = np.asarray(diagonals, dtype=np.int64).reshape(-1)
+        if dg.size != len(pr):
+            raise ValueError("diagonals must hold one value per pair")
+        if dg.size and (dg.min() < -2 ** 31 or dg.max() >= 2 ** 31):
+            raise ValueError("diagonals must fit in 32 bits")
+        dg = np.ascontiguousarray(dg.astype(np.int32))
+        bp = N.KgBandParams(int(band), (C.c_int32 * 3)(0, 0, 0))
+        pth = np.zeros(len(pr), dtype=N.ALIGN_PATH_DTYPE) if paths else None
+        h = C.c_void_p()
+        tail = (off.ctypes.data, n, pp, len(pr), int(max_trace_cells), N.OPS_MODES[ops] if ops is not None else 0, op,
+                _ptr(pth) if paths else None, C.byref(h) if ops is not None else None, C.byref(bp), _ptr(dg))
+        if device_ptr is not None:
+            N.check(lib.kg_proteins_align_banded_device(device, C.byref(p), C.c_void_p(device_ptr), *tail))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_proteins_align_banded(device, C.byref(p), _ptr(arr), *tail))
+        if ops is None:
+            return (out, pth) if paths else out
+        try:
+            return (out, pth) + _copy_ops(lib.kg_opset_ops_count, lib.kg_opset_op_starts_copy, lib.kg_opset_ops_copy, h, len(pr))
+        finally:
+            lib.kg_opset_free(h)
     if ops is not None:
         pth = np.zeros(len(pr), dtype=N.ALIGN_PATH_DTYPE)
         h = C.c_void_p()
@@ -987,7 +1015,7 @@ def _seed_params(seeds):
 def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256,
                     align: Optional[dict] = None, max_windows: int = 0, max_pairs: int = 0, device: int = 0,
                     device_ptr: Optional[int] = None, paths: Optional[str] = None, max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS,
-                    seeds=None, ops: Optional[str] = None, mask=None, ungapped=None):
+                    seeds=None, ops: Optional[str] = None, mask=None, ungapped=None, band: Optional[int] = None):
     """Proteins [n_db, n_prot) searched against proteins [0, n_db), on the GPU (include/kmerguts_hip.h kg_proteins_search states
     the rule): the targets that share at least min_shared distinct unmasked 8-mers with a query, the max_cand with the most
     aligned, a hit where 100 * score >= min_ratio_pct * ref.  seq / offsets / device_ptr as for cluster_proteins; align: None
@@ -1009,7 +1037,12 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
     Every candidate's best seed diagonal is scored without gaps, candidates with a score below N are dropped and a query's
     candidates are cut by (larger ungapped score, larger s, smaller target).  The result tuple then ends with one more array,
     _native.SEARCH_UNGAPPED_DTYPE records of the hit records' indices, and the statistics hold "ungapped" (scored, dropped,
-    cut, cells, ms_ungapped)."""
+    cut, cells, ms_ungapped).
+    band: None or W (needs ungapped): kg_proteins_search_banded.  Every aligned candidate is aligned, and traced, in the band of
+    half-width W around its best seed diagonal (align_proteins' band).  The results keep their shapes and the statistics hold
+    "band" (band_cells, full_cells, band)."""
+    if band is not None and (ungapped is None or ungapped is False):
+        raise ValueError("band needs ungapped")
     up = None
     if ungapped is not None and ungapped is not False:
         if ungapped is True:
@@ -1032,7 +1065,18 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
     h = C.c_void_p()
     lib = N.load()
     mp = _mask_params(mask, sides_too=True)
-    if up is not None:
+    if up is not None and band is not None:
+        sp = C.byref(seed_set) if seed_set is not None else None
+        bp = N.KgBandParams(int(band), (C.c_int32 * 3)(0, 0, 0))
+        tail = (int(max_windows), int(max_pairs), trace, int(max_trace_cells), C.byref(mp[0]) if mp is not None else None,
+                mp[1] if mp is not None else 0, C.byref(up), C.byref(bp), C.byref(h))
+        if device_ptr is not None:
+            N.check(lib.kg_proteins_search_banded_device(device, C.byref(p), sp, C.byref(ap), C.c_void_p(device_ptr), off.ctypes.data, n,
+                                                         int(n_db), *tail))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_proteins_search_banded(device, C.byref(p), sp, C.byref(ap), _ptr(arr), off.ctypes.data, n, int(n_db), *tail))
+    elif up is not None:
         sp = C.byref(seed_set) if seed_set is not None else None
         tail = (int(max_windows), int(max_pairs), trace, int(max_trace_cells), C.byref(mp[0]) if mp is not None else None,
                 mp[1] if mp is not None else 0, C.byref(up), C.byref(h))
@@ -1091,6 +1135,10 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
             N.check(lib.kg_hitset_ungapped_stats(h, C.byref(ust)))
             more["ungapped"] = ust.as_dict()
             extra = (_copy_records(lib.kg_hitset_ungapped_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_UNGAPPED_DTYPE),)
+        if band is not None:
+            bst = N.KgBandStats()
+            N.check(lib.kg_hitset_band_stats(h, C.byref(bst)))
+            more["band"] = bst.as_dict()
         if paths is not None:
             tst = N.KgTraceStats()
             N.check(lib.kg_hitset_trace_stats(h, C.byref(tst)))

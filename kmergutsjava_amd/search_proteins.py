@@ -193,15 +193,21 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
                     align: Optional[dict] = None, write_all: bool = False, annotations: Optional[str] = None,
                     transfer: Optional[str] = None, truth: Optional[str] = None, device: int = 0, search=None,
                     paths: Optional[str] = None, max_trace_cells: Optional[int] = None, seeds=None, cigar: Optional[str] = None,
-                    alignments: Optional[str] = None, mask: Optional[dict] = None, ungapped: Optional[dict] = None) -> str:
+                    alignments: Optional[str] = None, mask: Optional[dict] = None, ungapped: Optional[dict] = None,
+                    band: Optional[int] = None) -> str:
     """Write the files; returns the summary line.  `search` replaces hotpath.search_proteins (tests).  align: None, or the
     alignment parameters of hotpath.search_proteins (ref "query" is its "member").  paths: None, "hits" or "all" (--paths with
     its --trace); max_trace_cells: None for the library's default.  seeds: None (the exact 8-mers), "reduced" or a
     dict(alphabet=..., shapes=[...]) as hotpath.search_proteins takes it.  cigar: None, "m" or "eqx" (--cigar); alignments: None
     or the file --alignments writes; both need paths.  mask: None, or a dict of window, trigger, extend and sides as
     hotpath.search_proteins takes it (--mask).  ungapped: None, or {"min_score": N} (--ungapped, --min-ungapped): the candidates
-    are ranked by the ungapped score of their best seed diagonal and those below N dropped."""
+    are ranked by the ungapped score of their best seed diagonal and those below N dropped.  band: None, or W (--band): every
+    candidate is aligned in the band of half-width W around that diagonal; needs ungapped."""
     from . import seeds as SD
+    if band is not None and ungapped is None:
+        raise ValueError("--band needs --ungapped")
+    if band is not None and not 0 <= int(band) <= 256:
+        raise ValueError("--band must be in 0..256")
     if ungapped is not None and int(ungapped.get("min_score", 0)) < 0:
         raise ValueError("--min-ungapped must be >= 0")
     seed_words = SD.describe(seeds) if SD.resolve(seeds) is not None else None
@@ -242,6 +248,8 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
     urecs = None
     if ungapped is not None:
         more["ungapped"] = dict(ungapped)
+    if band is not None:
+        more["band"] = int(band)
     if paths is None:
         got = search(b"".join(seqs), offsets, len(dids), min_shared=min_shared, max_cand=max_cand,
                      max_db_per_kmer=max_db_per_kmer, align=align, device=device, **more)
@@ -287,6 +295,9 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
     if ungapped is not None:
         u = st["ungapped"]
         line += ", ungapped: scored %d, dropped %d, cut %d, ungapped ms: %.3f" % (u["scored"], u["dropped"], u["cut"], u.get("ms_ungapped", 0.0))
+    if band is not None:
+        b = st["band"]
+        line += ", band: %d, band cells: %d of %d" % (b["band"], b["band_cells"], b["full_cells"])
     return line
 
 
@@ -333,7 +344,14 @@ def main(argv=None) -> int:
                          "line gains ungapped, diagonal and on diagonal")
     ap.add_argument("--min-ungapped", type=int, default=None, metavar="N",
                     help="with --ungapped: a candidate whose ungapped score is below N is not aligned (default 0: none is dropped)")
+    ap.add_argument("--band", type=int, default=None, metavar="W",
+                    help="with --ungapped: align every candidate only within W diagonals of its best seed diagonal, 0..256 (no default: "
+                         "without the flag the whole matrix is filled)")
     a = ap.parse_args(argv)
+    if a.band is not None and not a.ungapped:
+        ap.error("--band needs --ungapped")
+    if a.band is not None and not 0 <= a.band <= 256:
+        ap.error("--band must be in 0..256")
     if a.min_ungapped is not None and not a.ungapped:
         ap.error("--min-ungapped needs --ungapped")
     if a.min_ungapped is not None and a.min_ungapped < 0:
@@ -359,7 +377,7 @@ def main(argv=None) -> int:
         line = search_proteins(a.d, a.q, a.o, a.min_shared, a.max_cand, a.max_hits, a.max_db_per_kmer, align, a.all, a.A, a.transfer,
                                a.truth, paths=paths, max_trace_cells=a.max_trace_cells, seeds=seeds, cigar=a.cigar, alignments=a.alignments,
                                mask=mask_from_options(ap, a, a.mask),
-                               ungapped=dict(min_score=a.min_ungapped or 0) if a.ungapped else None)
+                               ungapped=dict(min_score=a.min_ungapped or 0) if a.ungapped else None, band=a.band)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1
