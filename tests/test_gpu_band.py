@@ -81,8 +81,11 @@ def _grid_proteins():
     return a_of, b_of
 
 
-@pytest.mark.parametrize("W", [0, 1, 31, 32, 33, 63, 64, 256])
-def test_rows_widths_and_windows(W):
+GRID_WIDTHS = [0, 1, 31, 32, 33, 63, 64, 256]
+
+
+def _grid_case(W):
+    """-> (prots, pairs, diags) of test_rows_widths_and_windows at half-width W."""
     a_of, b_of = _grid_proteins()
     prots, pairs, diags = [], [], []
     for k, (n, m) in enumerate((n, m) for n in ROWS for m in COLS):
@@ -94,6 +97,12 @@ def test_rows_widths_and_windows(W):
             prots += [a_of[n], b_of[m]]
             pairs.append((len(prots) - 2, len(prots) - 1))
             diags.append(g)
+    return prots, pairs, diags
+
+
+@pytest.mark.parametrize("W", GRID_WIDTHS)
+def test_rows_widths_and_windows(W):
+    prots, pairs, diags = _grid_case(W)
     rec = _check(prots, pairs, diags, W)[0]
     for (pa, pb), g, r in zip(pairs, diags, rec):
         n, m = len(prots[pa]), len(prots[pb])
