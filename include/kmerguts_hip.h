@@ -1001,6 +1001,120 @@ int kg_proteins_search_banded_device(int device, const kg_search_params *p, cons
                                      const kg_ungapped_params *ungapped, const kg_band_params *band, kg_hitset **out);
 int kg_hitset_band_stats(const kg_hitset *s, kg_band_stats *out);
 
+/* ---- a resident protein database: build once, save, open, search (kernels: kg_searchdb.hpp) ----
+ *
+ * Every search above takes the targets with the queries and starts from nothing.  A kg_searchdb is the targets' half of that
+ * work kept on the device: a long-lived handle with a context of its own, as kg_table is.  One call at a time runs per handle; a
+ * second concurrent call returns KG_ERR_BUSY.
+ * The rule.  The hit records, hit_start, paths, ops, ungapped records and band statistics of kg_searchdb_search are byte for byte
+ * those of kg_proteins_search_banded / _filtered / _masked / _seeded / _paths / kg_proteins_search (whichever the same options
+ * select) on the batch "the handle's targets, then these queries", with the handle's seeds and with mask / sides describing the
+ * same masking (the handle's mask on the targets, query_mask on the queries; the two must then hold the same values).  The result
+ * is an ordinary kg_hitset and every getter works on it under the same conditions.  kg_hitset_stats has the same values, ms_*
+ * aside: valid_windows and pairs are the sums of the two sides, kmers is the targets' k-mers plus the queries' minus the queries'
+ * k-mers found among the targets', kmers_masked counts the targets' runs longer than max_db_per_kmer whether or not a query has
+ * them; ms_encode and ms_sort cover the queries only.  kg_hitset_mask_stats gives the sums of the masked sides' counts.
+ * kg_searchdb_build / _device: the targets' seq and offsets[n_db + 1] (host; the residues are those from offsets[0] on); seeds
+ * (NULL: the exact 8-mers); mask (NULL: the targets are not masked); names, an opaque blob of names_bytes bytes which the handle
+ * stores and hands back untouched (NULL with names_bytes = 0); max_windows as in the search; query_room, the residues of the
+ * largest query batch a search may bring (0: 2^24).  The handle keeps on the device the targets' residues and offsets with room
+ * for a query batch behind them, the distinct (k-mer, target) pairs in sorted order, each pair's window value, the k-mer run
+ * starts and the distinct k-mers; on the host the seeds, the mask parameters and statistics, and names.  Everything else goes
+ * back to the driver before the call returns.  Limits and errors are the search's: n_db < 2^29, len < 2^24, window blocks,
+ * KG_ERR_LIMIT when the windows do not fit.  n_db = 0 and targets without a window are valid.
+ * kg_searchdb_search / _device: the queries' seq (host / device) and offsets[n_q + 1] (host), the search's parameters, trace
+ * (0: no paths) with max_trace_cells, query_mask (NULL: the queries are not masked), ungapped and band (either may be NULL; a
+ * band without the ungapped stage is KG_ERR_ARG "null kg_ungapped_params", as kg_proteins_search_banded has it).  The other
+ * KG_ERR_ARG words are the one-batch calls'.  max_windows counts the queries' windows alone.  ms_join holds ms_probe.  KG_ERR_LIMIT: n_db + n_q >= 2^29, and a batch of more residues than the room ("... residues of queries do not fit the
+ * room of ..."); kg_searchdb_reserve regrows the room (a device-to-device copy).  kg_hitset_db_stats gives the probe's own
+ * counts and times; it is KG_ERR_ARG for a set made by any other call.
+ * KG_TEST_FAIL_ALLOC applies to every device allocation of build, open, reserve and search.  After a failed search or reserve
+ * the handle is usable and its live bytes are what they were; after a failed build or open nothing is live.
+ * The file (kg_searchdb_save / kg_searchdb_open), the project's own format.  All integers little-endian.
+ *   Header, 448 bytes:
+ *        0  8 bytes   magic "KGSRCHDB"
+ *        8  u32       version = 1
+ *       12  u32       header bytes = 448
+ *       16  i64       n_db            24  i64  residues         32  i64  P, the pairs        40  i64  K, the k-mers
+ *       48  i64       valid windows   56  i64  names_bytes
+ *       64  u32       1 iff built with seeds        68  u32  1 iff built with a mask
+ *       72  48 bytes  kg_seed_params (all 0 without seeds)
+ *      120  16 bytes  kg_mask_params (all 0 without a mask)
+ *      136  80 bytes  kg_mask_stats of the targets with ms_mask = 0 (all 0 without a mask)
+ *      216  6 section entries of 24 bytes: u64 file offset, u64 bytes, u64 checksum
+ *      360  u64       checksum of header bytes [0, 360)
+ *      368  80 bytes  0
+ *   Sections, in this order, each at the next multiple of 64 bytes behind the one before (the first at 448), the gaps and the
+ *   file's end (itself a multiple of 64) zero-filled: 0 offsets, (n_db + 1) * 8 bytes, i64, offsets[0] = 0; 1 residues, one byte
+ *   each; 2 pairs, P * 8, u64 v << bits(n_db) | d ascending; 3 values, P * 4, u32 beside the pairs; 4 run starts, (K + 1) * 4,
+ *   u32; 5 names.  The file's bytes are a function of the build's inputs alone (query_room is not in it).
+ *   Checksum of a byte string: pad it with zero bytes to a multiple of 8, read it as u64 words w_0 .. w_(n-1); the checksum is
+ *   (sum of w_i * (2 i + 1) + the unpadded length) mod 2^64.  A changed byte changes one word by a non-zero amount times an odd
+ *   factor, which is not 0 mod 2^64: any single changed byte is caught.
+ * kg_searchdb_open checks, in this order and before the device is touched: the file's length against the header's, the magic, the
+ * version and header bytes, the header checksum, every count (ranges, the six sections' bytes against the counts, their offsets
+ * against the layout above, the file length), each section's checksum, and the offsets (offsets[0] = 0, non-decreasing, the
+ * last equal to residues, every length < 2^24).  Anything wrong is KG_ERR_FORMAT (an unreadable file KG_ERR_IO) with a message
+ * naming the first thing that is wrong.  No kernel reads a section whose checksum failed.  Beyond that the file is trusted: a
+ * file whose checksums hold but whose pairs are not what a build makes of its residues is not detected.
+ * An opened handle is indistinguishable from a built one (its build times are 0), and kg_searchdb_save of it writes the same bytes.
+ * KG_SEARCHDB_NO_VERIFY=1 in the environment skips the section checksums (a measuring aid, read only with KG_ENABLE_TEST_HOOKS=1).
+ * KG_TEST_SEARCHDB_REENTER=1 (likewise) makes kg_searchdb_search, once it holds the handle, call kg_searchdb_reserve on the same
+ * handle and return that call's answer: KG_ERR_BUSY with its words, without a second thread. */
+#define KG_SEARCHDB_VERSION 1
+#define KG_SEARCHDB_HEADER_BYTES 448
+#define KG_SEARCHDB_DEFAULT_ROOM (1ll << 24)
+typedef struct kg_searchdb kg_searchdb;
+typedef struct kg_searchdb_desc {   /* 240 B */
+    int64_t targets;
+    int64_t residues;
+    int64_t pairs;
+    int64_t kmers;
+    int64_t valid_windows;
+    int64_t names_bytes;
+    int64_t query_room;        /* residues                                                  */
+    int64_t device_bytes;      /* what the handle holds on the device                       */
+    int32_t has_seeds;         /* 0: the exact 8-mers, and `seeds` is all 0                 */
+    int32_t has_mask;
+    kg_seed_params seeds;
+    kg_mask_params mask;
+    kg_mask_stats mask_stats;  /* the targets'; ms_mask is 0 in an opened handle            */
+    float   ms_upload;         /* the build by stage; all 0 in an opened handle             */
+    float   ms_encode;
+    float   ms_sort;
+    float   ms_index;          /* collapse, the runs, the k-mers, the copies into the handle */
+    float   ms_total;
+    int32_t reserved;
+} kg_searchdb_desc;
+typedef struct kg_search_db_stats {   /* 24 B */
+    int64_t query_kmers;       /* distinct k-mers of the queries                            */
+    int64_t found;             /* ... that the targets have too                             */
+    float   ms_probe;
+    float   ms_upload;         /* the queries' residues and offsets into the room           */
+} kg_search_db_stats;
+int kg_searchdb_build(int device, const uint8_t *seq, const int64_t *offsets, int64_t n_db, const kg_seed_params *seeds,
+                      const kg_mask_params *mask, const void *names, int64_t names_bytes, int64_t max_windows, int64_t query_room,
+                      kg_searchdb **out);
+int kg_searchdb_build_device(int device, const uint8_t *d_seq, const int64_t *offsets, int64_t n_db, const kg_seed_params *seeds,
+                             const kg_mask_params *mask, const void *names, int64_t names_bytes, int64_t max_windows,
+                             int64_t query_room, kg_searchdb **out);
+int kg_searchdb_save(kg_searchdb *db, const char *path);
+int kg_searchdb_open(int device, const char *path, int64_t query_room, kg_searchdb **out);
+int kg_searchdb_info(const kg_searchdb *db, kg_searchdb_desc *out);
+/* all names_bytes bytes into dst (host memory) */
+int kg_searchdb_names_copy(const kg_searchdb *db, void *dst);
+int64_t kg_searchdb_live_device_bytes(kg_searchdb *db);
+int kg_searchdb_reserve(kg_searchdb *db, int64_t query_room);
+void kg_searchdb_free(kg_searchdb *db);
+int kg_searchdb_search(kg_searchdb *db, const kg_search_params *p, const kg_align_params *align, const uint8_t *seq,
+                       const int64_t *offsets, int64_t n_q, int64_t max_windows, int64_t max_pairs, int trace, int64_t max_trace_cells,
+                       const kg_mask_params *query_mask, const kg_ungapped_params *ungapped, const kg_band_params *band, kg_hitset **out);
+int kg_searchdb_search_device(kg_searchdb *db, const kg_search_params *p, const kg_align_params *align, const uint8_t *d_seq,
+                              const int64_t *offsets, int64_t n_q, int64_t max_windows, int64_t max_pairs, int trace,
+                              int64_t max_trace_cells, const kg_mask_params *query_mask, const kg_ungapped_params *ungapped,
+                              const kg_band_params *band, kg_hitset **out);
+int kg_hitset_db_stats(const kg_hitset *s, kg_search_db_stats *out);
+
 /* ---- assigning functions: the CALL records of an -a scan -> one function per protein (kernels: kg_assign.hpp) ----
  *
  * The reference stops at the CALL lines (KGJ:398-404, 526-536); this rule is the project's own.

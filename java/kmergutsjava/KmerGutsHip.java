@@ -519,6 +519,32 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_searchdb_desc (240 B, kg_searchdb_info): a resident protein database's counts, parameters, device bytes and
+     *  build times; seeds, mask and mask_stats are nested by value. */
+    class KgSearchDbDesc extends Structure {
+        public long targets, residues, pairs, kmers, valid_windows, names_bytes, query_room, device_bytes;
+        public int has_seeds, has_mask;
+        public KgSeedParams seeds;
+        public KgMaskParams mask;
+        public KgMaskStats mask_stats;
+        public float ms_upload, ms_encode, ms_sort, ms_index, ms_total;
+        public int reserved;
+        public KgSearchDbDesc() {
+            setFieldOrder(new String[] {"targets", "residues", "pairs", "kmers", "valid_windows", "names_bytes", "query_room",
+                    "device_bytes", "has_seeds", "has_mask", "seeds", "mask", "mask_stats", "ms_upload", "ms_encode", "ms_sort",
+                    "ms_index", "ms_total", "reserved"});
+        }
+    }
+
+    /** struct kg_search_db_stats (24 B, kg_hitset_db_stats): the probe's counts and times of a search against a kg_searchdb. */
+    class KgSearchDbStats extends Structure {
+        public long query_kmers, found;
+        public float ms_probe, ms_upload;
+        public KgSearchDbStats() {
+            setFieldOrder(new String[] {"query_kmers", "found", "ms_probe", "ms_upload"});
+        }
+    }
+
     /** struct kg_band_stats: band cells against full cells over the aligned pairs of a banded search. */
     class KgBandStats extends Structure {
         public long band_cells, full_cells;
@@ -689,6 +715,26 @@ public interface KmerGutsHip extends Library {
                                          long maxTraceCells, KgMaskParams mask, int sides, KgUngappedParams ungapped, KgBandParams band,
                                          PointerByReference out);
     int kg_hitset_band_stats(Pointer set, KgBandStats out);
+    /** a resident protein database: built once from the targets (seeds, mask: null for the exact 8-mers / no mask; names: an
+     *  opaque blob), saved, opened, and searched with batches of queries; the records are the one-batch search's, byte for byte */
+    int kg_searchdb_build(int device, byte[] seq, long[] offsets, long nDb, KgSeedParams seeds, KgMaskParams mask, byte[] names,
+                          long namesBytes, long maxWindows, long queryRoom, PointerByReference out);
+    int kg_searchdb_build_device(int device, Pointer dSeq, long[] offsets, long nDb, KgSeedParams seeds, KgMaskParams mask, byte[] names,
+                                 long namesBytes, long maxWindows, long queryRoom, PointerByReference out);
+    int kg_searchdb_save(Pointer db, String path);
+    int kg_searchdb_open(int device, String path, long queryRoom, PointerByReference out);
+    int kg_searchdb_info(Pointer db, KgSearchDbDesc out);
+    int kg_searchdb_names_copy(Pointer db, byte[] dst);
+    long kg_searchdb_live_device_bytes(Pointer db);
+    int kg_searchdb_reserve(Pointer db, long queryRoom);
+    void kg_searchdb_free(Pointer db);
+    int kg_searchdb_search(Pointer db, KgSearchParams params, KgAlignParams align, byte[] seq, long[] offsets, long nQ, long maxWindows,
+                           long maxPairs, int trace, long maxTraceCells, KgMaskParams queryMask, KgUngappedParams ungapped,
+                           KgBandParams band, PointerByReference out);
+    int kg_searchdb_search_device(Pointer db, KgSearchParams params, KgAlignParams align, Pointer dSeq, long[] offsets, long nQ,
+                                  long maxWindows, long maxPairs, int trace, long maxTraceCells, KgMaskParams queryMask,
+                                  KgUngappedParams ungapped, KgBandParams band, PointerByReference out);
+    int kg_hitset_db_stats(Pointer set, KgSearchDbStats out);
     /** kg_proteins_cluster_aligned (align = null: no alignment step) with every protein soft-masked for the 8-mer pass */
     int kg_proteins_cluster_masked(int device, KgClusterParams params, KgAlignParams align, byte[] seq, long[] offsets, long nProt,
                                    long maxWindows, KgMaskParams mask, PointerByReference out);

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("KG_LIB_PATH") or os.path.join(HERE, "libkmerguts_hip.
 KG_OK = 0
 KG_ERR_ARG = -1
 KG_ERR_IO = -2
+KG_ERR_FORMAT = -3
+KG_ERR_DEVICE = -4
 KG_ERR_NOMEM = -5
 KG_ERR_LIMIT = -7
 KG_ERR_BUSY = -8
@@ -54,6 +56,9 @@ EXPORTS = (
     "kg_proteins_search_filtered", "kg_proteins_search_filtered_device", "kg_hitset_ungapped_copy", "kg_hitset_ungapped_stats",
     "kg_proteins_align_banded", "kg_proteins_align_banded_device", "kg_proteins_search_banded", "kg_proteins_search_banded_device",
     "kg_hitset_band_stats",
+    "kg_searchdb_build", "kg_searchdb_build_device", "kg_searchdb_save", "kg_searchdb_open", "kg_searchdb_info",
+    "kg_searchdb_names_copy", "kg_searchdb_live_device_bytes", "kg_searchdb_reserve", "kg_searchdb_free",
+    "kg_searchdb_search", "kg_searchdb_search_device", "kg_hitset_db_stats",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
@@ -480,6 +485,26 @@ class KgBandStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+SEARCHDB_VERSION, SEARCHDB_HEADER_BYTES, SEARCHDB_DEFAULT_ROOM = 1, 448, 1 << 24      # KG_SEARCHDB_*
+
+
+class KgSearchDbDesc(C.Structure):
+    """struct kg_searchdb_desc (kg_searchdb_info)."""
+    _fields_ = [("targets", C.c_int64), ("residues", C.c_int64), ("pairs", C.c_int64), ("kmers", C.c_int64),
+                ("valid_windows", C.c_int64), ("names_bytes", C.c_int64), ("query_room", C.c_int64), ("device_bytes", C.c_int64),
+                ("has_seeds", C.c_int32), ("has_mask", C.c_int32), ("seeds", KgSeedParams), ("mask", KgMaskParams),
+                ("mask_stats", KgMaskStats), ("ms_upload", C.c_float), ("ms_encode", C.c_float), ("ms_sort", C.c_float),
+                ("ms_index", C.c_float), ("ms_total", C.c_float), ("reserved", C.c_int32)]
+
+
+class KgSearchDbStats(C.Structure):
+    """struct kg_search_db_stats (kg_hitset_db_stats)."""
+    _fields_ = [("query_kmers", C.c_int64), ("found", C.c_int64), ("ms_probe", C.c_float), ("ms_upload", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # struct kg_search_ungapped (kg_hitset_ungapped_copy): one per hit record of a filtered search, same index
 SEARCH_UNGAPPED_DTYPE = np.dtype([("ungapped", "<i4"), ("diagonal", "<i4"), ("on_diagonal", "<i4"), ("reserved", "<i4")])
 assert SEARCH_UNGAPPED_DTYPE.itemsize == 16
@@ -669,6 +694,23 @@ def load() -> C.CDLL:
                                        C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(KgMaskParams), C.c_int,
                                        C.POINTER(KgUngappedParams), C.POINTER(KgBandParams), C.POINTER(vp)]
     lib.kg_hitset_band_stats.argtypes = [vp, C.POINTER(KgBandStats)]
+    for name in ("kg_searchdb_build", "kg_searchdb_build_device"):
+        getattr(lib, name).argtypes = [C.c_int, vp, vp, C.c_int64, C.POINTER(KgSeedParams), C.POINTER(KgMaskParams), vp, C.c_int64,
+                                       C.c_int64, C.c_int64, C.POINTER(vp)]
+    lib.kg_searchdb_save.argtypes = [vp, C.c_char_p]
+    lib.kg_searchdb_open.argtypes = [C.c_int, C.c_char_p, C.c_int64, C.POINTER(vp)]
+    lib.kg_searchdb_info.argtypes = [vp, C.POINTER(KgSearchDbDesc)]
+    lib.kg_searchdb_names_copy.argtypes = [vp, vp]
+    lib.kg_searchdb_live_device_bytes.argtypes = [vp]
+    lib.kg_searchdb_live_device_bytes.restype = C.c_int64
+    lib.kg_searchdb_reserve.argtypes = [vp, C.c_int64]
+    lib.kg_searchdb_free.argtypes = [vp]
+    lib.kg_searchdb_free.restype = None
+    for name in ("kg_searchdb_search", "kg_searchdb_search_device"):
+        getattr(lib, name).argtypes = [vp, C.POINTER(KgSearchParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64, C.c_int64,
+                                       C.c_int, C.c_int64, C.POINTER(KgMaskParams), C.POINTER(KgUngappedParams), C.POINTER(KgBandParams),
+                                       C.POINTER(vp)]
+    lib.kg_hitset_db_stats.argtypes = [vp, C.POINTER(KgSearchDbStats)]
     for name in ("kg_proteins_cluster_masked", "kg_proteins_cluster_masked_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
                                        C.POINTER(KgMaskParams), C.POINTER(vp)]

@@ -35,6 +35,8 @@ struct kg_hitset {
     kg_ungapped_stats ust = {};
     bool has_band = false;              // kg_proteins_search_banded only: the band's counts over the aligned pairs
     kg_band_stats bst = {};
+    bool has_db = false;                // kg_searchdb_search only: the probe's counts and times
+    kg_search_db_stats dbst = {};
     const int64_t *op_starts() const { return (const int64_t *)d_ops.p; }
     const uint32_t *ops() const { return (const uint32_t *)(d_ops.p + ((size_t)count + 1) * 8); }
     const int64_t *starts() const { return (const int64_t *)d_block.p; }
@@ -204,6 +206,19 @@ int search_paths_behind(kg_table *t, Scratch &sc, const kg_align_params *al, con
     return KG_OK;
 }
 
+// kg_searchdb_search (kg_host_searchdb.hpp): what a call against a resident index reads of the index.  The targets' pairs, runs
+// and k-mers are the index's and only the queries' are the call's (SearchPairs::w); d_off holds the targets' offsets and behind
+// them the call's queries'.
+struct SearchDbSide {
+    const uint64_t *pk, *dk;            // the (k-mer, target) pairs v << bits(n_db) | d, and the K distinct k-mers
+    const uint32_t *pv, *kstart;        // beside pk; the k-mer run starts, K + 1
+    uint64_t P, K, masked;              // masked: the runs longer than the call's max_db_per_kmer
+    int64_t longest;                    // the longest target
+    unsigned long long *dwords;         // kSearchDbWords counters, zeroed
+    hipEvent_t ev_probe[2];             // round the probe
+    uint64_t q_kmers = 0, found = 0;    // what the probe gives back: the queries' k-mers, and those the targets have
+};
+
 // a checked call.  seed: null for the exact 8-mers; ask.trace = 0: no paths; mask: null for no masking, else `sides` says whose
 // residues the seeding copy masks (KG_MASK_QUERIES | KG_MASK_TARGETS)
 struct SearchArgs {
@@ -218,6 +233,7 @@ struct SearchArgs {
     int sides;
     const kg_ungapped_params *ung = nullptr;    // kg_proteins_search_filtered: the ungapped stage in search_candidates' place
     const kg_band_params *band = nullptr;       // kg_proteins_search_banded: the alignment and the trace in a band around g*
+    SearchDbSide *res = nullptr;        // kg_searchdb_search: the targets' side of the join is a resident index
 };
 
 // what search_impl sets up for its stages: they allocate from sc, enqueue on t->stream and record the timing events ev[1 .. 5]
@@ -301,13 +317,19 @@ struct SearchRuns {
     uint64_t R = 0, J = 0;
     uint32_t *cstart = nullptr, *cnd = nullptr, *wx = nullptr;
     uint64_t *jpartial = nullptr;
+    uint32_t *cqstart = nullptr;        // against a resident index: cstart is a run's first target pair, this its first query pair
 };
+
+// kg_host_searchdb.hpp: search_runs and the two join launches against a resident index
+int searchdb_runs(SearchCall &c, const SearchPairs &in, bool keep_pv, uint64_t bytes_per_pair, SearchCands *out, SearchRuns *runs);
+void searchdb_join(SearchCall &c, const SearchPairs &in, const SearchRuns &runs, const struct UngappedWidths *uw, uint64_t *keys, uint32_t *vals);
 
 // Stage 2, its front: the k-mer runs and their weights, whether the join fits (at bytes_per_pair a pair), the listed runs.  J = 0:
 // nothing to join.  keep_pv: the run flags get words of their own and in.w.pv stays what the window-pairs pass left.
 int search_runs(SearchCall &c, const SearchPairs &in, bool keep_pv, uint64_t bytes_per_pair, SearchCands *out, SearchRuns *runs)
 {
     const SearchArgs &a = c.a;
+    if (a.res) return searchdb_runs(c, in, keep_pv, bytes_per_pair, out, runs);
     kg_table *t = c.t;
     Scratch &sc = c.sc;
     hipStream_t s = t->stream;
@@ -388,8 +410,11 @@ int search_candidates(SearchCall &c, const SearchPairs &in, SearchCands *out)
     // ---- the join: one key per (query, target) of every listed run ----
     SortPairs jp;
     if ((rc = jp.alloc(sc, J))) return rc;
-    hipLaunchKernelGGL(kg::search_join_kernel, dim3(grid_of(J, kg::kSearchTile)), dim3(kg::kSearchThreads), 0, s, pk, wx, cstart, cnd, (uint32_t)R,
-                       (uint32_t)J, b, ndb, db, jp.keys(), jp.vals());
+    if (a.res)
+        searchdb_join(c, in, runs, nullptr, jp.keys(), jp.vals());
+    else
+        hipLaunchKernelGGL(kg::search_join_kernel, dim3(grid_of(J, kg::kSearchTile)), dim3(kg::kSearchThreads), 0, s, pk, wx, cstart, cnd, (uint32_t)R,
+                           (uint32_t)J, b, ndb, db, jp.keys(), jp.vals());
     HIP_TRY(hipGetLastError());
     uint64_t wtot = 0;
     HIP_TRY(hipMemcpyAsync(&wtot, d_tot + 3, 8, hipMemcpyDeviceToHost, s));
@@ -456,8 +481,8 @@ struct UngappedWidths { uint32_t qb, db, gb; int32_t bias; };
 
 int ungapped_widths(const SearchArgs &a, UngappedWidths *out)
 {
-    int64_t lq = 0, ld = 0;
-    for (int64_t p = 0; p < a.n_prot; p++) {
+    int64_t lq = 0, ld = a.res ? a.res->longest : 0;
+    for (int64_t p = a.res ? a.n_db : 0; p < a.n_prot; p++) {
         int64_t &longest = p < a.n_db ? ld : lq;
         longest = std::max(longest, a.offsets[p + 1] - a.offsets[p]);
     }
@@ -502,8 +527,11 @@ int search_candidates_ungapped(SearchCall &c, const SearchPairs &in, SearchCands
     // ---- the join with the diagonals, sorted: inside a (q, d) run the diagonals ascend ----
     SortPairs jp;
     if ((rc = jp.alloc(sc, J))) return rc;
-    hipLaunchKernelGGL(kg::search_join_diag_kernel, dim3(grid_of(J, kg::kSearchTile)), dim3(kg::kSearchThreads), 0, s, in.w.pk, in.w.pv, in.d_off,
-                       runs.wx, runs.cstart, runs.cnd, (uint32_t)R, (uint32_t)J, b, ndb, db, gb, uw.bias, jp.keys(), jp.vals());
+    if (a.res)
+        searchdb_join(c, in, runs, &uw, jp.keys(), jp.vals());
+    else
+        hipLaunchKernelGGL(kg::search_join_diag_kernel, dim3(grid_of(J, kg::kSearchTile)), dim3(kg::kSearchThreads), 0, s, in.w.pk, in.w.pv, in.d_off,
+                           runs.wx, runs.cstart, runs.cnd, (uint32_t)R, (uint32_t)J, b, ndb, db, gb, uw.bias, jp.keys(), jp.vals());
     HIP_TRY(hipGetLastError());
     uint64_t wtot = 0, ND = 0, NG = 0;
     HIP_TRY(hipMemcpyAsync(&wtot, d_tot + 3, 8, hipMemcpyDeviceToHost, s));

@@ -22,6 +22,7 @@
 #include "kg_search.hpp"
 #include "kg_ungapped.hpp"
 #include "kg_seed.hpp"
+#include "kg_searchdb.hpp"
 #include "kg_mask.hpp"
 #include "kg_assign.hpp"
 #include "kg_regions.hpp"
@@ -58,6 +59,7 @@
 #include "kg_host_mask.hpp"
 #include "kg_host_cluster.hpp"
 #include "kg_host_search.hpp"
+#include "kg_host_searchdb.hpp"
 #include "kg_host_assign.hpp"
 #include "kg_host_regions.hpp"
 #include "kg_host_orfs.hpp"

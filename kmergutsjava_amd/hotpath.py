@@ -1012,6 +1012,51 @@ def _seed_params(seeds):
     return N.KgSeedParams(len(masks), n_cls, (C.c_uint8 * 20)(*cls), (C.c_uint32 * 4)(*masks), 0)
 
 
+def _take_hitset(h, has_mask: bool, has_ung: bool, band, paths, ops, db: bool = False):
+    """Copy a kg_hitset out in search_proteins' return shape and free it."""
+    lib = N.load()
+    try:
+        st = N.KgSearchStats()
+        N.check(lib.kg_hitset_stats(h, C.byref(st)))
+        starts = np.zeros(int(st.queries) + 1, dtype=np.int64)
+        N.check(lib.kg_hitset_starts_copy(h, starts.ctypes.data))
+        more = {}
+        if has_mask:
+            mst = N.KgMaskStats()
+            N.check(lib.kg_hitset_mask_stats(h, C.byref(mst)))
+            more["mask"] = mst.as_dict()
+        extra = ()
+        if has_ung:
+            ust = N.KgUngappedStats()
+            N.check(lib.kg_hitset_ungapped_stats(h, C.byref(ust)))
+            more["ungapped"] = ust.as_dict()
+            extra = (_copy_records(lib.kg_hitset_ungapped_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_UNGAPPED_DTYPE),)
+        if db:
+            dst = N.KgSearchDbStats()
+            N.check(lib.kg_hitset_db_stats(h, C.byref(dst)))
+            more["db"] = dst.as_dict()
+        if band is not None:
+            bst = N.KgBandStats()
+            N.check(lib.kg_hitset_band_stats(h, C.byref(bst)))
+            more["band"] = bst.as_dict()
+        if paths is not None:
+            tst = N.KgTraceStats()
+            N.check(lib.kg_hitset_trace_stats(h, C.byref(tst)))
+            stats = dict(st.as_dict(), traced=tst.traced, untraced=tst.untraced, trace_cells=tst.cells, ms_trace=tst.ms_trace, **more)
+            count = int(lib.kg_hitset_count(h))
+            got = (_copy_records(lib.kg_hitset_copy, h, count, N.SEARCH_HIT_DTYPE), starts,
+                   _copy_records(lib.kg_hitset_paths_copy, h, count, N.ALIGN_PATH_DTYPE), stats)
+            if ops is not None:
+                ms = C.c_float()
+                N.check(lib.kg_hitset_ms_ops(h, C.byref(ms)))
+                stats.update(ops=int(lib.kg_hitset_ops_count(h)), ms_ops=ms.value)
+                got += _copy_ops(lib.kg_hitset_ops_count, lib.kg_hitset_op_starts_copy, lib.kg_hitset_ops_copy, h, count)
+            return got + extra
+        return (_copy_records(lib.kg_hitset_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_HIT_DTYPE), starts, dict(st.as_dict(), **more)) + extra
+    finally:
+        lib.kg_hitset_free(h)
+
+
 def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256,
                     align: Optional[dict] = None, max_windows: int = 0, max_pairs: int = 0, device: int = 0,
                     device_ptr: Optional[int] = None, paths: Optional[str] = None, max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS,
@@ -1119,42 +1164,143 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
         arr = _seq_bytes(seq, off)
         N.check(lib.kg_proteins_search(device, C.byref(p), C.byref(ap), _ptr(arr), off.ctypes.data, n,
                                        int(n_db), int(max_windows), int(max_pairs), C.byref(h)))
-    try:
-        st = N.KgSearchStats()
-        N.check(lib.kg_hitset_stats(h, C.byref(st)))
-        starts = np.zeros(int(st.queries) + 1, dtype=np.int64)
-        N.check(lib.kg_hitset_starts_copy(h, starts.ctypes.data))
-        more = {}
-        if mp is not None:
-            mst = N.KgMaskStats()
-            N.check(lib.kg_hitset_mask_stats(h, C.byref(mst)))
-            more["mask"] = mst.as_dict()
-        extra = ()
-        if up is not None:
-            ust = N.KgUngappedStats()
-            N.check(lib.kg_hitset_ungapped_stats(h, C.byref(ust)))
-            more["ungapped"] = ust.as_dict()
-            extra = (_copy_records(lib.kg_hitset_ungapped_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_UNGAPPED_DTYPE),)
-        if band is not None:
-            bst = N.KgBandStats()
-            N.check(lib.kg_hitset_band_stats(h, C.byref(bst)))
-            more["band"] = bst.as_dict()
-        if paths is not None:
-            tst = N.KgTraceStats()
-            N.check(lib.kg_hitset_trace_stats(h, C.byref(tst)))
-            stats = dict(st.as_dict(), traced=tst.traced, untraced=tst.untraced, trace_cells=tst.cells, ms_trace=tst.ms_trace, **more)
-            count = int(lib.kg_hitset_count(h))
-            got = (_copy_records(lib.kg_hitset_copy, h, count, N.SEARCH_HIT_DTYPE), starts,
-                   _copy_records(lib.kg_hitset_paths_copy, h, count, N.ALIGN_PATH_DTYPE), stats)
-            if ops is not None:
-                ms = C.c_float()
-                N.check(lib.kg_hitset_ms_ops(h, C.byref(ms)))
-                stats.update(ops=int(lib.kg_hitset_ops_count(h)), ms_ops=ms.value)
-                got += _copy_ops(lib.kg_hitset_ops_count, lib.kg_hitset_op_starts_copy, lib.kg_hitset_ops_copy, h, count)
-            return got + extra
-        return (_copy_records(lib.kg_hitset_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_HIT_DTYPE), starts, dict(st.as_dict(), **more)) + extra
-    finally:
-        lib.kg_hitset_free(h)
+    return _take_hitset(h, mp is not None, up is not None, band, paths, ops)
+
+
+class SearchDb:
+    """A resident protein database (include/kmerguts_hip.h kg_searchdb): the targets' half of search_proteins' work, made once and
+    kept on the device.  build() makes it from the targets, save() writes its file and open() reads one; search() gives, for a
+    batch of queries, what search_proteins gives for "the targets, then these queries" with the same options, byte for byte.
+    One call at a time per handle.  Use as a context manager or call close()."""
+
+    def __init__(self, handle, path: Optional[str] = None):
+        self._h = handle
+        self._path = path               # open(): the file, which targets() reads
+
+    @classmethod
+    def build(cls, seq, offsets, seeds=None, mask=None, names: bytes = b"", max_windows: int = 0, query_room: int = 0, device: int = 0,
+              device_ptr: Optional[int] = None) -> "SearchDb":
+        """seq / offsets / device_ptr: the targets, as for search_proteins; seeds and mask (window, trigger, extend; no sides: the
+        targets are the masked side) as there; names: an opaque blob handed back by names(); query_room: the residues of the
+        largest query batch (0: the library's default)."""
+        seed_set = _seed_params(seeds)
+        mp = _mask_params(mask)
+        off = _offsets(offsets, "int64[n_db + 1]")
+        blob = np.frombuffer(bytes(names), dtype=np.uint8)
+        h = C.c_void_p()
+        lib = N.load()
+        tail = (off.ctypes.data, off.size - 1, C.byref(seed_set) if seed_set is not None else None,
+                C.byref(mp[0]) if mp is not None else None, _ptr(blob), blob.size, int(max_windows), int(query_room), C.byref(h))
+        if device_ptr is not None:
+            N.check(lib.kg_searchdb_build_device(device, C.c_void_p(device_ptr), *tail))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_searchdb_build(device, _ptr(arr), *tail))
+        return cls(h)
+
+    @classmethod
+    def open(cls, path: str, query_room: int = 0, device: int = 0) -> "SearchDb":
+        h = C.c_void_p()
+        N.check(N.load().kg_searchdb_open(device, os.fsencode(path), int(query_room), C.byref(h)))
+        return cls(h, path)
+
+    def targets(self):
+        """(residues uint8, offsets int64[n_db + 1]) of an opened index, read from its file's first two sections (the file has
+        passed kg_searchdb_open's checks); a front end needs the targets' lengths and residues to write alignments."""
+        if self._path is None:
+            raise ValueError("targets() reads the file of an opened SearchDb")
+        with open(self._path, "rb") as f:
+            hdr = f.read(N.SEARCHDB_HEADER_BYTES)
+            at = np.frombuffer(hdr, dtype="<u8", count=4, offset=216).copy()       # two section entries: offset, bytes, checksum
+            f.seek(int(at[0]))
+            off = np.frombuffer(f.read(int(at[1])), dtype="<i8").astype(np.int64)
+            f.seek(int(at[3]))
+            seq = np.frombuffer(f.read(int(off[-1])), dtype=np.uint8)
+        return seq, off
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the SearchDb is closed")
+        return self._h
+
+    def save(self, path: str) -> None:
+        N.check(N.load().kg_searchdb_save(self._handle(), os.fsencode(path)))
+
+    def info(self) -> dict:
+        """targets, residues, pairs, kmers, valid_windows, names_bytes, query_room, device_bytes, seeds (None: the exact 8-mers, else
+        n_shapes, alphabet_size, cls, shape), mask (None or window, trigger, extend), mask_stats, and the build's ms_* by stage."""
+        d = N.KgSearchDbDesc()
+        N.check(N.load().kg_searchdb_info(self._handle(), C.byref(d)))
+        out = {k: getattr(d, k) for k in ("targets", "residues", "pairs", "kmers", "valid_windows", "names_bytes", "query_room",
+                                          "device_bytes", "ms_upload", "ms_encode", "ms_sort", "ms_index", "ms_total")}
+        out["seeds"] = (dict(n_shapes=d.seeds.n_shapes, alphabet_size=d.seeds.alphabet_size, cls=list(d.seeds.cls),
+                             shape=list(d.seeds.shape)[:d.seeds.n_shapes]) if d.has_seeds else None)
+        out["mask"] = dict(window=d.mask.window, trigger=d.mask.trigger, extend=d.mask.extend) if d.has_mask else None
+        out["mask_stats"] = d.mask_stats.as_dict() if d.has_mask else None
+        return out
+
+    def names(self) -> bytes:
+        n = self.info()["names_bytes"]
+        buf = np.zeros(n, dtype=np.uint8)
+        N.check(N.load().kg_searchdb_names_copy(self._handle(), _ptr(buf)))
+        return buf.tobytes()
+
+    def live_device_bytes(self) -> int:
+        return int(N.load().kg_searchdb_live_device_bytes(self._handle()))
+
+    def reserve(self, query_room: int) -> None:
+        N.check(N.load().kg_searchdb_reserve(self._handle(), int(query_room)))
+
+    def search(self, seq, offsets, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256, align: Optional[dict] = None,
+               max_windows: int = 0, max_pairs: int = 0, device_ptr: Optional[int] = None, paths: Optional[str] = None,
+               max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS, ops: Optional[str] = None, mask=None, ungapped=None,
+               band: Optional[int] = None):
+        """search_proteins' keyword arguments and return shape, with seq / offsets the queries alone; the seeds are the handle's and
+        mask (window, trigger, extend) masks the queries.  The statistics also hold "db" (query_kmers, found, ms_probe, ms_upload)."""
+        if band is not None and (ungapped is None or ungapped is False):
+            raise ValueError("band needs ungapped")
+        up = None
+        if ungapped is not None and ungapped is not False:
+            if ungapped is True:
+                ungapped = {}
+            if not isinstance(ungapped, dict) or set(ungapped) - {"min_score"}:
+                raise ValueError("ungapped must be None, True or {'min_score': N}")
+            up = N.KgUngappedParams(int(ungapped.get("min_score", 0)), (C.c_int32 * 3)(0, 0, 0))
+        if paths is not None and paths not in N.TRACE_MODES:
+            raise ValueError("paths must be None, 'hits' or 'all'")
+        if ops is not None and ops not in N.OPS_MODES:
+            raise ValueError("ops must be None, 'm' or 'eqx'")
+        if ops is not None and paths is None:
+            raise ValueError("ops needs paths")
+        trace = (N.TRACE_MODES[paths] if paths is not None else 0) | (N.OPS_MODES[ops] if ops is not None else 0)
+        off = _offsets(offsets, "int64[n_q + 1]")
+        p = N.KgSearchParams(int(min_shared), int(max_cand), int(max_db_per_kmer), 0)
+        ap, _keep = _align_params(**(align or {}))
+        mp = _mask_params(mask)
+        bp = N.KgBandParams(int(band), (C.c_int32 * 3)(0, 0, 0)) if band is not None else None
+        h = C.c_void_p()
+        lib = N.load()
+        tail = (off.ctypes.data, off.size - 1, int(max_windows), int(max_pairs), trace, int(max_trace_cells),
+                C.byref(mp[0]) if mp is not None else None, C.byref(up) if up is not None else None,
+                C.byref(bp) if bp is not None else None, C.byref(h))
+        if device_ptr is not None:
+            N.check(lib.kg_searchdb_search_device(self._handle(), C.byref(p), C.byref(ap), C.c_void_p(device_ptr), *tail))
+        else:
+            arr = _seq_bytes(seq, off)
+            N.check(lib.kg_searchdb_search(self._handle(), C.byref(p), C.byref(ap), _ptr(arr), *tail))
+        has_mask = mp is not None or self.info()["mask"] is not None
+        return _take_hitset(h, has_mask, up is not None, band, paths, ops, db=True)
+
+    def close(self) -> None:
+        if self._h is not None:
+            N.load().kg_searchdb_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def assign_calls(calls, call_start, otu=None, min_score: int = 0, min_share_pct: int = 50, device: int = 0) -> np.ndarray:

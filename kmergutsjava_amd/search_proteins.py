@@ -1,7 +1,8 @@
 """Search proteins against a set of known proteins on the GPU (kg_proteins_search): which known protein is this protein like, and
 how much.  The step that names what `annotate` leaves at `none`.
 
-    python -m kmergutsjava_amd.search_proteins -d database.faa[.gz] [-d more.faa ...] -q queries.faa[.gz] [-q more ...] -o hits.tsv
+    python -m kmergutsjava_amd.search_proteins (-d database.faa[.gz] [-d more.faa ...] | --db DB.kgsdb [--batch-residues N])
+                                               -q queries.faa[.gz] [-q more ...] -o hits.tsv
                                                [--min-shared 2] [--max-cand 8] [--max-hits 1] [--max-db-per-kmer 256]
                                                [--min-ratio 50] [--align-ref longer|query] [--gap-open 11] [--gap-extend 1]
                                                [--max-cells N] [--all] [-A db_annotations.tsv [--transfer out.tsv]]
@@ -61,6 +62,15 @@ are, so a hit's score is what it is without --mask.  --mask both (the default of
 --mask queries or --mask targets one side.  --mask-window, --mask-trigger and --mask-extend are mask_proteins' --window, --trigger
 and --extend.  Under a spaced shape a masked residue on a `0` position keeps the seed.  The summary line then gains `, mask:
 W/T/E <sides>, masked residues: N`; without --mask every byte is as before.
+--db DB.kgsdb in place of -d searches an index that make_search_db has prepared once (kg_searchdb_open, kg_searchdb_search):
+the targets' residues, their sorted seeds and their ids are the index's and are not made again, and the queries are searched in
+batches of at most --batch-residues residues (default: the index's query room), so that the database and all queries need not fit
+one call.  Giving both -d and --db is an error.  The seeds and the targets' mask are the index's: --seeds, --alphabet, --shape,
+--mask both and --mask targets beside --db are errors that name the flag.  --mask queries masks the queries, with the index's
+mask values when it has them, else with the flags'.  -A is optional when the index carries functions (make_search_db -A).  With
+the same options the -o, --transfer and --alignments bytes are those of the -d run on the same FASTA files, wherever the batches
+are cut.  The summary line sums the batches' counts (the database's and the masked k-mers are counted once) and gains `, db:
+index (N targets)`.  Without --db every byte is as before.
 The summary line goes to stderr.
 """
 from __future__ import annotations
@@ -189,12 +199,85 @@ def compare_truth(qids, got, truth) -> dict:
     return t
 
 
+def batch_cuts(lengths, batch_residues: int):
+    """Cuts [0, .., n] of the queries into consecutive batches of at most batch_residues residues, one query at least each."""
+    cuts, total = [0], 0
+    for k, n in enumerate(lengths):
+        if k > cuts[-1] and total + n > batch_residues:
+            cuts.append(k)
+            total = 0
+        total += n
+    if len(lengths) > cuts[-1] or len(cuts) == 1:
+        cuts.append(len(lengths))
+    return cuts
+
+
+def _sum_stats(parts, index_mask):
+    """The batches' statistics as one call's: counts and times summed; the targets, the masked k-mers and the index's share of the
+    mask's counts once; the band as it is."""
+    st = {}
+    for part in parts:
+        for k, v in part.items():
+            if isinstance(v, dict):
+                d = st.setdefault(k, {})
+                for kk, vv in v.items():
+                    d[kk] = vv if (k, kk) == ("band", "band") else d.get(kk, 0) + vv
+            else:
+                st[k] = v if k in ("targets", "kmers_masked") else st.get(k, 0) + v
+    if "mask" in st and index_mask is not None:
+        for kk, vv in index_mask.items():
+            if kk in st["mask"] and not kk.startswith("ms_"):
+                st["mask"][kk] -= (len(parts) - 1) * vv
+    return st
+
+
+def _search_index(handle, qseqs, batch_residues, paths, ops_mode, ungapped, kw):
+    """The queries against an opened index, batch by batch -> what one call gives: (hits, hit_start, path records or None,
+    statistics, op_start or None, ops or None, ungapped records or None), `query` counted over all queries."""
+    info = handle.info()
+    lengths = [len(s) for s in qseqs]
+    room = int(info["query_room"])
+    if batch_residues is None:
+        batch_residues = room
+    if batch_residues < 1:
+        raise ValueError("--batch-residues must be >= 1")
+    need = max([min(batch_residues, room)] + lengths)        # (a query longer than the batch is a batch of its own)
+    if need > room:
+        handle.reserve(need)
+    cuts = batch_cuts(lengths, min(batch_residues, need))
+    hits, starts, recs, op_starts, opsv, urecs, stats = [], [np.zeros(1, dtype=np.int64)], [], [np.zeros(1, dtype=np.int64)], [], [], []
+    n_hits = n_ops = 0
+    for a, b in zip(cuts, cuts[1:]):
+        off = np.zeros(b - a + 1, dtype=np.int64)
+        off[1:] = np.cumsum(lengths[a:b])
+        got = handle.search(b"".join(qseqs[a:b]), off, paths=paths, **kw)
+        h = got[0].copy()
+        h["query"] += a
+        hits.append(h)
+        starts.append(got[1][1:] + n_hits)
+        n_hits += len(h)
+        if paths is None:
+            stats.append(got[2])
+        else:
+            recs.append(got[2])
+            stats.append(got[3])
+            if ops_mode is not None:
+                op_starts.append(got[4][1:] + n_ops)
+                opsv.append(got[5])
+                n_ops += len(got[5])
+        if ungapped is not None:
+            urecs.append(got[-1])
+    return (np.concatenate(hits), np.concatenate(starts), np.concatenate(recs) if paths is not None else None,
+            _sum_stats(stats, info.get("mask_stats")), np.concatenate(op_starts) if ops_mode is not None else None,
+            np.concatenate(opsv) if ops_mode is not None else None, np.concatenate(urecs) if ungapped is not None else None)
+
+
 def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: int = 8, max_hits: int = 1, max_db_per_kmer: int = 256,
                     align: Optional[dict] = None, write_all: bool = False, annotations: Optional[str] = None,
                     transfer: Optional[str] = None, truth: Optional[str] = None, device: int = 0, search=None,
                     paths: Optional[str] = None, max_trace_cells: Optional[int] = None, seeds=None, cigar: Optional[str] = None,
                     alignments: Optional[str] = None, mask: Optional[dict] = None, ungapped: Optional[dict] = None,
-                    band: Optional[int] = None) -> str:
+                    band: Optional[int] = None, db: Optional[str] = None, batch_residues: Optional[int] = None, open_db=None) -> str:
     """Write the files; returns the summary line.  `search` replaces hotpath.search_proteins (tests).  align: None, or the
     alignment parameters of hotpath.search_proteins (ref "query" is its "member").  paths: None, "hits" or "all" (--paths with
     its --trace); max_trace_cells: None for the library's default.  seeds: None (the exact 8-mers), "reduced" or a
@@ -202,7 +285,10 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
     or the file --alignments writes; both need paths.  mask: None, or a dict of window, trigger, extend and sides as
     hotpath.search_proteins takes it (--mask).  ungapped: None, or {"min_score": N} (--ungapped, --min-ungapped): the candidates
     are ranked by the ungapped score of their best seed diagonal and those below N dropped.  band: None, or W (--band): every
-    candidate is aligned in the band of half-width W around that diagonal; needs ungapped."""
+    candidate is aligned in the band of half-width W around that diagonal; needs ungapped.  db: None, or the file of an index
+    (--db) in the database's place: `database` must then be empty, seeds None and mask None or of sides "queries";
+    batch_residues: None (the index's query room) or the residues of a batch of queries; `open_db` replaces
+    hotpath.SearchDb.open (tests)."""
     from . import seeds as SD
     if band is not None and ungapped is None:
         raise ValueError("--band needs --ungapped")
@@ -220,10 +306,22 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
     ops_mode = cigar if cigar is not None else "eqx" if alignments is not None else None
     if max_hits < 1:
         raise ValueError("--max-hits must be >= 1")
-    if transfer is not None and annotations is None:
+    if transfer is not None and annotations is None and db is None:
         raise ValueError("--transfer needs -A")
-    if truth is not None and annotations is None:
+    if truth is not None and annotations is None and db is None:
         raise ValueError("--truth needs -A")
+    if db is not None and database:
+        raise ValueError("give -d or --db, not both")
+    if db is None and batch_residues is not None:
+        raise ValueError("--batch-residues needs --db")
+    if db is not None and seeds is not None:
+        raise ValueError("--seeds beside --db: the seeds are the index's")
+    if db is not None and mask is not None and mask.get("sides", "both") != "queries":
+        raise ValueError("--mask %s beside --db: the targets' mask is the index's; --mask queries masks the queries" % mask.get("sides", "both"))
+    if db is not None:
+        return _search_proteins_index(db, queries, out, min_shared, max_cand, max_hits, max_db_per_kmer, align, write_all, annotations,
+                                      transfer, truth, device, paths, max_trace_cells, cigar, alignments, mask, ungapped, band,
+                                      batch_residues, open_db, ops_mode)
     dids, dseqs = read_proteins(database)
     qids, qseqs = read_proteins(queries)
     seqs = dseqs + qseqs
@@ -266,6 +364,13 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
             op_start, ops = got[4:6]
     if ungapped is not None:
         urecs = got[-1]                     # (the ungapped records end the tuple)
+    return _write_and_summarise(out, qids, dids, qseqs, dseqs, hits, hit_start, st, recs, op_start, ops, urecs, max_hits, write_all, align_ref,
+                                functions, want, transfer, alignments, cigar, paths, ops_mode, seed_words, mask, ungapped, band)
+
+
+def _write_and_summarise(out, qids, dids, qseqs, dseqs, hits, hit_start, st, recs, op_start, ops, urecs, max_hits, write_all, align_ref,
+                         functions, want, transfer, alignments, cigar, paths, ops_mode, seed_words, mask, ungapped, band) -> str:
+    """The files of a search and its summary line, from one call's results or from the batches' put together."""
     with open(out, "wb") as f:
         f.write(format_hits(qids, dids, hits, hit_start, max_hits, write_all, align_ref, functions, recs, [len(x) for x in qseqs],
                             [len(x) for x in dseqs], (op_start, ops) if cigar is not None else None, urecs))
@@ -301,12 +406,64 @@ def search_proteins(database, queries, out: str, min_shared: int = 2, max_cand: 
     return line
 
 
+def _search_proteins_index(db, queries, out, min_shared, max_cand, max_hits, max_db_per_kmer, align, write_all, annotations, transfer,
+                           truth, device, paths, max_trace_cells, cigar, alignments, mask, ungapped, band, batch_residues, open_db,
+                           ops_mode) -> str:
+    """search_proteins with --db: the checked arguments of search_proteins, the index in the database's place."""
+    from . import seeds as SD
+    from .make_search_db import seeds_of, unpack_names
+    if open_db is None:
+        from . import hotpath
+        open_db = hotpath.SearchDb.open
+    qids, qseqs = read_proteins(queries)
+    align = dict(align or {})
+    align_ref = align.get("ref", "longer")
+    if align_ref == "query":
+        align["ref"] = "member"
+    want = parse_annotations(_read(truth), truth) if truth is not None else None
+    with open_db(db, device=device) as handle:
+        info = handle.info()
+        dids, functions = unpack_names(handle.names(), int(info["targets"]))
+        if annotations is not None:
+            functions = parse_annotations(_read(annotations), annotations)
+        if functions is None and (transfer is not None or truth is not None):
+            raise ValueError("--transfer and --truth need -A, or an index made with make_search_db -A")
+        dseq, doff = handle.targets()
+        dseqs = [bytes(dseq[int(doff[k]):int(doff[k + 1])]) for k in range(len(doff) - 1)]
+        kw = dict(min_shared=min_shared, max_cand=max_cand, max_db_per_kmer=max_db_per_kmer, align=align)
+        qmask = None
+        if mask is not None:                            # --mask queries: the index's values when it has them, else the flags'
+            qmask = dict(info["mask"]) if info["mask"] is not None else {k: v for k, v in mask.items() if k != "sides"}
+            kw["mask"] = qmask
+        if ungapped is not None:
+            kw["ungapped"] = dict(ungapped)
+        if band is not None:
+            kw["band"] = int(band)
+        if paths is not None and max_trace_cells is not None:
+            kw["max_trace_cells"] = max_trace_cells
+        if paths is not None and ops_mode is not None:
+            kw["ops"] = ops_mode
+        hits, hit_start, recs, st, op_start, ops, urecs = _search_index(handle, qseqs, batch_residues, paths, ops_mode, ungapped, kw)
+    seeds = seeds_of(info["seeds"])
+    seed_words = SD.describe(seeds) if seeds is not None else None
+    words = None                                        # what the summary says of the mask: the values and whose residues
+    if info["mask"] is not None or qmask is not None:
+        sides = "both" if info["mask"] is not None and qmask is not None else "targets" if qmask is None else "queries"
+        words = dict(info["mask"] if info["mask"] is not None else qmask, sides=sides)
+    line = _write_and_summarise(out, qids, dids, qseqs, dseqs, hits, hit_start, st, recs, op_start, ops, urecs, max_hits, write_all, align_ref,
+                                functions, want, transfer, alignments, cigar, paths, ops_mode, seed_words, words, ungapped, band)
+    return line + ", db: index (%d targets)" % int(info["targets"])
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m kmergutsjava_amd.search_proteins",
                                  description="Search proteins against a set of known proteins on the GPU: shared 8-mers, then alignment.")
-    ap.add_argument("-d", required=True, action="append", metavar="DATABASE", help="database protein FASTA (.gz allowed); may be given several times")
+    ap.add_argument("-d", default=None, action="append", metavar="DATABASE", help="database protein FASTA (.gz allowed); may be given several times")
     ap.add_argument("-q", required=True, action="append", metavar="QUERIES", help="query protein FASTA (.gz allowed); may be given several times")
     ap.add_argument("-o", required=True, metavar="HITS", help="hits TSV to write")
+    ap.add_argument("--db", default=None, metavar="DB", help="in place of -d: the index file make_search_db wrote; its seeds and target mask hold")
+    ap.add_argument("--batch-residues", type=int, default=None, metavar="N",
+                    help="with --db: search the queries in batches of at most N residues (default: the index's query room)")
     ap.add_argument("--min-shared", type=int, default=2, help="distinct unmasked 8-mers a candidate shares at least (default 2, this project's choice)")
     ap.add_argument("--max-cand", type=int, default=8, help="candidates aligned per query, 1..64 (default 8, this project's choice)")
     ap.add_argument("--max-hits", type=int, default=1, help="hits written per query (default 1)")
@@ -348,6 +505,20 @@ def main(argv=None) -> int:
                     help="with --ungapped: align every candidate only within W diagonals of its best seed diagonal, 0..256 (no default: "
                          "without the flag the whole matrix is filled)")
     a = ap.parse_args(argv)
+    if a.db is not None and a.d is not None:
+        ap.error("give -d or --db, not both")
+    if a.db is None and a.d is None:
+        ap.error("one of -d and --db is required")
+    if a.db is None and a.batch_residues is not None:
+        ap.error("--batch-residues needs --db")
+    if a.batch_residues is not None and a.batch_residues < 1:
+        ap.error("--batch-residues must be >= 1")
+    if a.db is not None:
+        for flag, given in (("--seeds", a.seeds != "exact"), ("--alphabet", a.alphabet is not None), ("--shape", a.shape is not None)):
+            if given:
+                ap.error("%s beside --db: the seeds are the index's" % flag)
+        if a.mask in ("both", "targets"):
+            ap.error("--mask %s beside --db: the targets' mask is the index's; --mask queries masks the queries" % a.mask)
     if a.band is not None and not a.ungapped:
         ap.error("--band needs --ungapped")
     if a.band is not None and not 0 <= a.band <= 256:
@@ -374,10 +545,11 @@ def main(argv=None) -> int:
         if a.shape is not None:
             seeds["shapes"] = a.shape
     try:
-        line = search_proteins(a.d, a.q, a.o, a.min_shared, a.max_cand, a.max_hits, a.max_db_per_kmer, align, a.all, a.A, a.transfer,
+        line = search_proteins(a.d or [], a.q, a.o, a.min_shared, a.max_cand, a.max_hits, a.max_db_per_kmer, align, a.all, a.A, a.transfer,
                                a.truth, paths=paths, max_trace_cells=a.max_trace_cells, seeds=seeds, cigar=a.cigar, alignments=a.alignments,
                                mask=mask_from_options(ap, a, a.mask),
-                               ungapped=dict(min_score=a.min_ungapped or 0) if a.ungapped else None, band=a.band)
+                               ungapped=dict(min_score=a.min_ungapped or 0) if a.ungapped else None, band=a.band, db=a.db,
+                               batch_residues=a.batch_residues)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1
