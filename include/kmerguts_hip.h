@@ -1870,6 +1870,87 @@ int kg_compset_copy_scores(const kg_compset *s, int64_t first, int64_t count, in
 int kg_compset_stats(const kg_compset *s, kg_comp_stats *out);
 void kg_compset_free(kg_compset *s);
 
+/* ---- genes by homology: a translated search of contigs whose hits are CALL records (kernels: kg_evidence.hpp) ----
+ *
+ * The reference stops at the CALL lines, and its CALLs come from the signature table; this rule is the project's own.  Integers
+ * only.  It gives the region, ORF, repair, coding, start and selection stages above CALLs made from protein homology instead: a
+ * caller with contigs and a kg_searchdb of labelled proteins, and no table, locates genes.  fI is a target (or the function
+ * target_fn gives it) where the signature path has a function index; everything behind the CALL list is unchanged.
+ *   1. Fragments.  The fragments of a batch of contigs are exactly the records, prot_start and residues of kg_orfs_free with
+ *      kg_free_params { min_res, start_codons = 0, 0 }, in that call's order: every stop-to-stop run of the six frames (a run
+ *      that reaches a contig's end included) of at least min_res residues, by contig, strand, frame and increasing first codon,
+ *      the scan's container order.  Fragment q is query q of the search.  For a fragment F on a contig of length L,
+ *      b = (x - F.frame) / 3 with x = F.left on '+' and x = L - 1 - F.right on '-': the fragment's first codon in its frame, so
+ *      residue i of its protein is codon b + i (with start_codons = 0 no residue is rewritten to 'M').
+ *   2. Search.  The hit records, hit_start, paths (and ops, ungapped records and band statistics when asked for) are byte for
+ *      byte those of kg_searchdb_search_device on the fragments' proteins as queries, with the same options and `trace` as
+ *      given, except that trace & 3 == 0 means KG_TRACE_HITS: a CALL needs the path's start.
+ *   3. CALLs.  Hit record r with path p, of fragment F, becomes a CALL iff r.status == 0 (a hit), r.rank < max_hits and
+ *      p.status == 0 (traced).  The first of the three tests that fails names the drop: status, rank, untraced.  The CALL:
+ *      container = 6 * F.seq + 3 * F.strand + F.frame; start = b + p.start_a; end = b + r.end_query; count = r.score;
+ *      fI = target_fn ? target_fn[r.target] : r.target; weightedHits = (float) r.score.  CALLs keep the hit records' order,
+ *      which is the fragments' order, so containers are non-decreasing as kg_regions_calls wants.  call_hit[k] is the hit
+ *      record of CALL k.
+ *   4. Rule 1 of the regions section holds for every such CALL.  F is codons b .. b + n_res - 1 of frame f, all of them whole
+ *      codons inside the contig (n_f counts whole codons only), and a traced path has 0 <= start_a <= end_query <= n_res - 1.
+ *      So x0 = f + 3 (b + start_a) >= 0, x0 <= x1, and x1 = f + 3 (b + end_query) + 2 <= f + 3 (b + n_res - 1) + 2 <= L - 1.
+ *      Two halves of a frameshifted gene hit one target in two frames of one strand: one group, one multi-frame region when
+ *      they lie within merge_gap, and kg_regionset_repair joins them.
+ *   5. Nothing depends on launch geometry or batch neighbours: a contig's fragments, a fragment's hit records and a record's
+ *      CALL depend on the contig, the database and the parameters alone (`query`, call_hit and seq aside, which count within
+ *      the batch).
+ * Parameters kg_translate_params { min_res (>= 1, default 30), max_hits (1..64, default 1), reserved[2] == 0 }; anything else
+ * is KG_ERR_ARG.  Both defaults are this project's choice and are not tuned: 30 residues is about the shortest piece the 8-mer
+ * prefilter and a ratio test against the fragment can place, and one hit per fragment keeps one gene from being called under
+ * every paralogue's name.  target_fn is a host int32[n_db] or NULL; a negative value is KG_ERR_ARG (the message names the
+ * first).
+ * kg_contigs_search_translated: seq, the batch's bytes exactly as a scan gets them, in device memory when seq_on_device != 0;
+ * offsets[n_seqs + 1], host.  The other arguments are kg_searchdb_search's and their KG_ERR_ARG words are its words.
+ * The fragments' residues go from the ORF set into the handle's room device to device; only prot_start travels to the host,
+ * because the search takes host offsets.
+ * Limits (KG_ERR_LIMIT): a fragment of 2^24 residues or more (a long run of N is a run), as the search has it; fragments whose
+ * residues exceed the handle's query room ("... residues of queries do not fit the room of ... residues"; kg_searchdb_reserve
+ * regrows it).  2 * (the nucleotides of the batch) is an upper bound on the fragments' residues: six frames of a third each.
+ * A caller can reserve that beforehand.  Also the limits of kg_orfs_free and of the search, 2^32 or more hit records, and so
+ * many contigs that a container index reaches 2^32.
+ * KG_ERR_BUSY, KG_ERR_NOMEM and KG_TEST_FAIL_ALLOC behave as in kg_searchdb_search; the hook applies to every device allocation
+ * of the three stages, each counted from 1.  After any failure the handle is usable and its live bytes are what they were.
+ * Zero contigs, zero fragments, zero hit records and zero CALLs are valid.
+ * The kg_evidence lends out the fragments as an ordinary kg_orfset and the hits as an ordinary kg_hitset, on which every getter
+ * works (kg_hitset_db_stats too); both are valid until kg_evidence_free and must not be freed by the caller.  Its own arrays
+ * live in the fragments' context, not in the handle's: an evidence may outlive the kg_searchdb. */
+typedef struct kg_translate_params { int32_t min_res; int32_t max_hits; int32_t reserved[2]; } kg_translate_params;
+typedef struct kg_translate_stats {   /* 72 B */
+    int64_t fragments;
+    int64_t fragment_residues;
+    int64_t records;           /* hit records of the search                                */
+    int64_t calls;
+    int64_t dropped_status;    /* records that are not hits (below, skipped)               */
+    int64_t dropped_rank;      /* hits of rank >= max_hits                                 */
+    int64_t dropped_untraced;  /* hits of a kept rank whose path is over max_trace_cells   */
+    float   ms_fragments;      /* device time of kg_orfs_free's kernels                    */
+    float   ms_search;         /* ... of the search and its trace                          */
+    float   ms_calls;          /* ... of flag, prefix sum and emit                         */
+    float   ms_total;          /* the three together                                       */
+} kg_translate_stats;
+typedef struct kg_evidence kg_evidence;
+int kg_contigs_search_translated(kg_searchdb *db, const kg_search_params *p, const kg_align_params *align,
+                                 const kg_translate_params *tp, const uint8_t *seq, int seq_on_device, const int64_t *offsets,
+                                 int64_t n_seqs, int64_t max_windows, int64_t max_pairs, int trace, int64_t max_trace_cells,
+                                 const kg_mask_params *query_mask, const kg_ungapped_params *ungapped, const kg_band_params *band,
+                                 const int32_t *target_fn, kg_evidence **out);
+const kg_orfset *kg_evidence_fragments(const kg_evidence *e);
+const kg_hitset *kg_evidence_hits(const kg_evidence *e);
+int64_t kg_evidence_calls_count(const kg_evidence *e);
+/* records [first, first + count) into dst (host or device memory) */
+int kg_evidence_calls_copy(const kg_evidence *e, int64_t first, int64_t count, kg_call *dst);
+/* device array of kg_evidence_calls_count(e) kg_call records, valid until kg_evidence_free: what kg_regionset_repair takes
+   with calls_on_device = 1 */
+const kg_call *kg_evidence_calls_device(const kg_evidence *e);
+int kg_evidence_call_hits_copy(const kg_evidence *e, int64_t first, int64_t count, int64_t *dst);
+int kg_evidence_stats(const kg_evidence *e, kg_translate_stats *out);
+void kg_evidence_free(kg_evidence *e);
+
 /* the resident 24-byte records, valid until kg_table_close, and how many there are: num_sigs for a built or adopted table, the
  * whole records of the file for an opened one (fewer than num_sigs for a truncated file, more for a longer one) */
 const void *kg_table_device_entries(const kg_table *t);

@@ -545,6 +545,26 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_translate_params (16 B, kg_contigs_search_translated): fragments of at least min_res residues (default 30), the
+     *  hits of rank below max_hits become CALLs (1..64, default 1); reserved 0. */
+    class KgTranslateParams extends Structure {
+        public int min_res, max_hits;
+        public int[] reserved = new int[2];
+        public KgTranslateParams() {
+            setFieldOrder(new String[] {"min_res", "max_hits", "reserved"});
+        }
+    }
+
+    /** struct kg_translate_stats (72 B, kg_evidence_stats): the counts of a translated search and its device times by stage. */
+    class KgTranslateStats extends Structure {
+        public long fragments, fragment_residues, records, calls, dropped_status, dropped_rank, dropped_untraced;
+        public float ms_fragments, ms_search, ms_calls, ms_total;
+        public KgTranslateStats() {
+            setFieldOrder(new String[] {"fragments", "fragment_residues", "records", "calls", "dropped_status", "dropped_rank",
+                    "dropped_untraced", "ms_fragments", "ms_search", "ms_calls", "ms_total"});
+        }
+    }
+
     /** struct kg_band_stats: band cells against full cells over the aligned pairs of a banded search. */
     class KgBandStats extends Structure {
         public long band_cells, full_cells;
@@ -735,6 +755,20 @@ public interface KmerGutsHip extends Library {
                                   long maxWindows, long maxPairs, int trace, long maxTraceCells, KgMaskParams queryMask,
                                   KgUngappedParams ungapped, KgBandParams band, PointerByReference out);
     int kg_hitset_db_stats(Pointer set, KgSearchDbStats out);
+    /** genes by homology: the stop-to-stop fragments of a batch of contigs searched against a kg_searchdb and the hits made
+     *  into CALL records (targetFn: int[n_db] or null); the evidence lends its fragments (a kg_orfset) and hits (a kg_hitset) */
+    int kg_contigs_search_translated(Pointer db, KgSearchParams params, KgAlignParams align, KgTranslateParams translate, Pointer seq,
+                                     int seqOnDevice, long[] offsets, long nSeqs, long maxWindows, long maxPairs, int trace,
+                                     long maxTraceCells, KgMaskParams queryMask, KgUngappedParams ungapped, KgBandParams band,
+                                     int[] targetFn, PointerByReference out);
+    Pointer kg_evidence_fragments(Pointer evidence);
+    Pointer kg_evidence_hits(Pointer evidence);
+    long kg_evidence_calls_count(Pointer evidence);
+    int kg_evidence_calls_copy(Pointer evidence, long first, long count, Pointer dst);
+    Pointer kg_evidence_calls_device(Pointer evidence);
+    int kg_evidence_call_hits_copy(Pointer evidence, long first, long count, long[] dst);
+    int kg_evidence_stats(Pointer evidence, KgTranslateStats out);
+    void kg_evidence_free(Pointer evidence);
     /** kg_proteins_cluster_aligned (align = null: no alignment step) with every protein soft-masked for the 8-mer pass */
     int kg_proteins_cluster_masked(int device, KgClusterParams params, KgAlignParams align, byte[] seq, long[] offsets, long nProt,
                                    long maxWindows, KgMaskParams mask, PointerByReference out);

@@ -59,6 +59,8 @@ EXPORTS = (
     "kg_searchdb_build", "kg_searchdb_build_device", "kg_searchdb_save", "kg_searchdb_open", "kg_searchdb_info",
     "kg_searchdb_names_copy", "kg_searchdb_live_device_bytes", "kg_searchdb_reserve", "kg_searchdb_free",
     "kg_searchdb_search", "kg_searchdb_search_device", "kg_hitset_db_stats",
+    "kg_contigs_search_translated", "kg_evidence_fragments", "kg_evidence_hits", "kg_evidence_calls_count", "kg_evidence_calls_copy",
+    "kg_evidence_calls_device", "kg_evidence_call_hits_copy", "kg_evidence_stats", "kg_evidence_free",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
@@ -505,6 +507,24 @@ class KgSearchDbStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KgTranslateParams(C.Structure):
+    """struct kg_translate_params (kg_contigs_search_translated)."""
+    _fields_ = [("min_res", C.c_int32), ("max_hits", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class KgTranslateStats(C.Structure):
+    """struct kg_translate_stats (kg_evidence_stats)."""
+    _fields_ = [("fragments", C.c_int64), ("fragment_residues", C.c_int64), ("records", C.c_int64), ("calls", C.c_int64),
+                ("dropped_status", C.c_int64), ("dropped_rank", C.c_int64), ("dropped_untraced", C.c_int64),
+                ("ms_fragments", C.c_float), ("ms_search", C.c_float), ("ms_calls", C.c_float), ("ms_total", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+TRANSLATE_MIN_RES, TRANSLATE_MAX_HITS = 30, 1       # the defaults of kg_translate_params
+
+
 # struct kg_search_ungapped (kg_hitset_ungapped_copy): one per hit record of a filtered search, same index
 SEARCH_UNGAPPED_DTYPE = np.dtype([("ungapped", "<i4"), ("diagonal", "<i4"), ("on_diagonal", "<i4"), ("reserved", "<i4")])
 assert SEARCH_UNGAPPED_DTYPE.itemsize == 16
@@ -711,12 +731,20 @@ def load() -> C.CDLL:
                                        C.c_int, C.c_int64, C.POINTER(KgMaskParams), C.POINTER(KgUngappedParams), C.POINTER(KgBandParams),
                                        C.POINTER(vp)]
     lib.kg_hitset_db_stats.argtypes = [vp, C.POINTER(KgSearchDbStats)]
+    lib.kg_contigs_search_translated.argtypes = [vp, C.POINTER(KgSearchParams), C.POINTER(KgAlignParams), C.POINTER(KgTranslateParams), vp,
+                                                  C.c_int, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(KgMaskParams),
+                                                  C.POINTER(KgUngappedParams), C.POINTER(KgBandParams), vp, C.POINTER(vp)]
+    for name in ("kg_evidence_fragments", "kg_evidence_hits", "kg_evidence_calls_device"):
+        getattr(lib, name).argtypes = [vp]
+        getattr(lib, name).restype = vp
+    lib.kg_evidence_stats.argtypes = [vp, C.POINTER(KgTranslateStats)]
     for name in ("kg_proteins_cluster_masked", "kg_proteins_cluster_masked_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
                                        C.POINTER(KgMaskParams), C.POINTER(vp)]
     # the sets' accessors, by signature: (set) -> count, (set) -> device address, (set, first, count, dst), (set, dst), (set)
     for name in ("kg_sigset_count", "kg_familyset_count", "kg_familyset_edges_count", "kg_maskset_count", "kg_hitset_count", "kg_hitset_ops_count", "kg_opset_ops_count", "kg_regionset_count", "kg_orfset_count", "kg_orfset_junctions_count",
-                 "kg_selectset_count", "kg_voteset_count", "kg_voteset_bins", "kg_compset_rows", "kg_compset_models"):
+                 "kg_selectset_count", "kg_voteset_count", "kg_voteset_bins", "kg_compset_rows", "kg_compset_models",
+                 "kg_evidence_calls_count"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = C.c_int64
     for name in ("kg_sigset_device", "kg_regionset_device", "kg_orfset_device", "kg_selectset_device"):
@@ -725,13 +753,14 @@ def load() -> C.CDLL:
     for name in ("kg_sigset_copy", "kg_familyset_copy", "kg_familyset_edges_copy", "kg_maskset_copy", "kg_maskset_flags_copy", "kg_hitset_copy", "kg_hitset_paths_copy", "kg_hitset_ungapped_copy", "kg_hitset_op_starts_copy", "kg_hitset_ops_copy", "kg_opset_op_starts_copy", "kg_opset_ops_copy", "kg_regionset_copy", "kg_orfset_copy", "kg_orfset_residues",
                  "kg_orfset_junctions_copy", "kg_orfset_coding_scores", "kg_orfset_start_shifts", "kg_selectset_copy",
                  "kg_voteset_copy_votes", "kg_voteset_copy_classes", "kg_voteset_copy_bins", "kg_compset_copy_classes",
-                 "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores"):
+                 "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores", "kg_evidence_calls_copy",
+                 "kg_evidence_call_hits_copy"):
         getattr(lib, name).argtypes = [vp, C.c_int64, C.c_int64, vp]
     for name in ("kg_regionset_seq_start", "kg_orfset_prot_start", "kg_orfset_junctions_start", "kg_voteset_seq_start",
                  "kg_compset_background", "kg_hitset_starts_copy", "kg_maskset_starts_copy"):
         getattr(lib, name).argtypes = [vp, vp]
     for name in ("kg_sigset_free", "kg_familyset_free", "kg_maskset_free", "kg_hitset_free", "kg_opset_free", "kg_regionset_free", "kg_orfset_free", "kg_selectset_free",
-                 "kg_voteset_free", "kg_compset_free"):
+                 "kg_voteset_free", "kg_compset_free", "kg_evidence_free"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = None
     lib.kg_last_error.restype = C.c_char_p

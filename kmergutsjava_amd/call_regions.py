@@ -2,6 +2,8 @@
 (kg_result_regions).
 
     python -m kmergutsjava_amd.call_regions -D KmerData -q contigs.fna[.gz] -o regions.tsv [-m 5] [-M 0] [-g 200] [-O]
+                                            | --db DB.kgsdb [--min-frag 30] [--max-hits 1] [--batch-nt N] [--hits HITS.tsv]
+                                              [the search's flags]
                                             [--merge-gap 600] [--min-score 0] [--min-len 0] [--all] [--gff]
                                             [--orfs ORFS.tsv] [--faa PROTEINS.faa] [--start-codons ATG,GTG,TTG]
                                             [--repair [--repair-min-count 0] [--max-junctions 4] [--shifts SHIFTS.tsv]]
@@ -90,6 +92,26 @@ type<TAB>ATG|GTG|TTG<TAB>chosen<TAB>candidates.  --start-model reads such a file
 (kg_start_weights_from) instead of training.  Every line of the ORF file gains the ORF's shift in codons as its last field, and
 a moved ORF the flag word `moved`; the protein file and --select see the new extents.  The summary line gains
 `, starts: own|model|untrained, moved: N`.  Without --starts every output is byte for byte what it was.
+
+--db DB.kgsdb in place of -D calls genes by homology, without a signature table: every stop-to-stop run of the six frames with at
+least --min-frag residues (default 30) is searched against the index of make_search_db on the GPU, and a fragment's best
+--max-hits hits (default 1) are the CALLs (kg_contigs_search_translated; include/kmerguts_hip.h states the rule).  Exactly one
+of -D and --db is given; -m, -M, -g and -O belong to the table scan and are errors beside --db.  A region's function is the
+target's function where the index carries functions (make_search_db -A), targets of one function sharing it, and the target's
+id otherwise; its score is a sum of alignment scores, so --min-score is then in alignment-score units.  The search takes
+--min-shared, --max-cand, --max-db-per-kmer, --min-ratio, --align-ref, --gap-open, --gap-extend, --max-cells, --ungapped,
+--min-ungapped and --band as search_proteins does, except that --align-ref defaults to `query`: a fragment is often a piece of a
+gene, so it is the fragment that must be covered (this project's choice).  Contigs are searched in batches of at most --batch-nt
+nucleotides (default: half the index's query room, since a batch's fragments hold at most two residues per nucleotide); a longer
+contig is a batch of its own and the room is reserved for it.  Without --coding and --starts, which train per batch, no byte of
+-o, --orfs, --faa and --shifts depends on where the batches are cut.  --hits FILE writes one line per hit record that became a
+CALL:
+    contig_id<TAB>left+1<TAB>right+1<TAB>strand<TAB>frame<TAB>fragment<TAB>rank<TAB>target<TAB>shared<TAB>score<TAB>ref<TAB>ratio
+    <TAB>end in fragment<TAB>end in target<TAB>status[<TAB>function]
+with left and right the aligned stretch in nucleotides, the fragment named contig_left+1_right+1_strand and the fields behind it
+those of search_proteins -o.  Every other flag works as with -D: a gene whose halves hit one target in two frames is a
+multi-frame region, and --repair joins it.  The summary line gains `, db: index (N targets), fragments: F, translated hits: H,
+calls: C` (H: the records with status hit).  Without --db every byte of every output is as before.
 """
 from __future__ import annotations
 
@@ -387,6 +409,46 @@ def format_faa(ids, regs, orfs, prot_start, residues, fnames, write_all: bool = 
     return b"".join(_by_contig(out, fout))
 
 
+def function_names(dids, functions):
+    """What --db names its regions by: the targets' functions where the index carries them, else their ids.
+    -> (fnames, target_fn): target_fn[d] indexes fnames; targets of one function share an index, numbered by first appearance."""
+    fnames, index_of = [], {}
+    target_fn = np.zeros(len(dids), dtype=np.int32)
+    for d, did in enumerate(dids):
+        name = functions[did][0] if functions is not None and did in functions else did
+        if name not in index_of:
+            index_of[name] = len(fnames)
+            fnames.append(name)
+        target_fn[d] = index_of[name]
+    return fnames, target_fn
+
+
+def format_call_hits(ids, dids, ev, off, align_ref: str = "longer", functions=None) -> bytes:
+    """--hits: one line per CALL of an evidence (hotpath.Evidence; ids: the batch's contig ids; off: its offsets): the contig, the
+    aligned stretch left+1 and right+1 in nucleotides, strand and frame, then the fields of search_proteins -o for the hit record,
+    the fragment named contig_left+1_right+1_strand as --faa names a protein."""
+    from .search_proteins import STATUS, _ref
+    hits, frags = ev.search[0], ev.fragments[0]
+    out = []
+    for c, r in zip(ev.calls, ev.call_hits):
+        h = hits[int(r)]
+        fr = frags[int(h["query"])]
+        s, strand, frame = int(c["container"]) // 6, int(c["container"]) % 6 // 3, int(c["container"]) % 3
+        L = int(off[s + 1] - off[s])
+        x0, x1 = frame + 3 * int(c["start"]), frame + 3 * int(c["end"]) + 2
+        left, right = (x0, x1) if strand == 0 else (L - 1 - x1, L - 1 - x0)
+        sign = b"-" if strand else b"+"
+        ref, score, did = _ref(h, align_ref), int(h["score"]), dids[int(h["target"])]
+        line = b"%s\t%d\t%d\t%s\t%d\t%s_%d_%d_%s\t%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%s" % (
+            ids[s], left + 1, right + 1, sign, frame, ids[s], int(fr["left"]) + 1, int(fr["right"]) + 1, sign, int(h["rank"]), did,
+            int(h["shared"]), score, ref, 100 * score // ref if ref > 0 else 0, int(h["end_query"]) + 1, int(h["end_target"]) + 1,
+            STATUS[int(h["status"])])
+        if functions is not None:
+            line += b"\t" + (functions[did][0] if did in functions else b"-")
+        out.append(line + b"\n")
+    return b"".join(out)
+
+
 def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_weighted_hits: int = 0, max_gap: int = 200,
                  order_constraint: bool = False, merge_gap: int = 600, min_score: int = 0, min_len: int = 0,
                  write_all: bool = False, gff: bool = False, device: int = 0, orfs_out: str = None, faa_out: str = None,
@@ -394,11 +456,19 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                  free_min_res: int = None, coding: bool = False, min_coding: int = 0, min_train: int = 100000,
                  coding_model_in: str = None, save_coding_model: str = None, starts: bool = False, start_rounds: int = 4,
                  min_train_starts: int = 200, start_model_in: str = None, save_start_model: str = None, repair: bool = False,
-                 repair_min_count: int = 0, max_junctions: int = 4, shifts_out: str = None) -> str:
+                 repair_min_count: int = 0, max_junctions: int = 4, shifts_out: str = None, db: str = None, min_frag: int = 30,
+                 max_hits: int = 1, batch_nt: int = None, hits_out: str = None, search: dict = None, open_db=None) -> str:
     """Write the regions (and, with orfs_out / faa_out, their open reading frames and proteins; with free_min_res also the
     evidence-free ORFs of at least that many residues; with coding the ORFs' coding scores, the non-coding free ORFs dropped;
     with starts the start codons chosen by the start-site score; with repair the multi-frame regions' ORFs joined across their
-    frames first, and their junctions written to shifts_out); returns the summary line."""
+    frames first, and their junctions written to shifts_out); returns the summary line.
+    db: in place of data_dir, the index file of make_search_db: the CALLs are translated search hits (SearchDb.search_contigs with
+    min_frag, max_hits and the keywords of `search`), batches hold at most batch_nt nucleotides and hits_out gets one line per
+    CALL.  open_db replaces hotpath.SearchDb.open (tests)."""
+    if (data_dir is None) == (db is None):
+        raise ValueError("exactly one of -D and --db must be given")
+    if db is None and hits_out is not None:
+        raise ValueError("--hits needs --db")
     want_orfs = orfs_out is not None or faa_out is not None
     if free_min_res is not None and not want_orfs:
         raise ValueError("--free-orfs needs --orfs or --faa: free ORFs are written to those files only")
@@ -416,15 +486,73 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         raise ValueError("--start-model and --save-start-model need --starts")
     from . import hotpath
     from .kmer_guts_java import KmerGutsJava, _resident_table
-    table_path = _data_file(data_dir, "kmer.table.mem_map")
-    fn_path = _data_file(data_dir, "function.index")
-    if table_path is None or fn_path is None:
-        raise FileNotFoundError("%s holds no kmer.table.mem_map[.gz] or function.index[.gz]" % data_dir)
-    fnames = parse_index(_read(fn_path), fn_path)
     ids, seqs = parse_fasta(_read(contigs), contigs)
-    tab = _resident_table(table_path, device)
-    params = hotpath.Params(aa=False, order_constraint=order_constraint, min_hits=min_hits, min_weighted_hits=min_weighted_hits,
-                            max_gap=max_gap)
+    index = None
+    if db is None:
+        table_path = _data_file(data_dir, "kmer.table.mem_map")
+        fn_path = _data_file(data_dir, "function.index")
+        if table_path is None or fn_path is None:
+            raise FileNotFoundError("%s holds no kmer.table.mem_map[.gz] or function.index[.gz]" % data_dir)
+        fnames = parse_index(_read(fn_path), fn_path)
+        tab = _resident_table(table_path, device)
+        params = hotpath.Params(aa=False, order_constraint=order_constraint, min_hits=min_hits, min_weighted_hits=min_weighted_hits,
+                                max_gap=max_gap)
+        batch_limit = KmerGutsJava.MAX_BATCH_CHARS
+
+        def scan(batch, off, k):
+            return tab.scan(batch, off, params)
+    else:
+        index = (open_db or hotpath.SearchDb.open)(db, device=device)
+    try:
+        if index is not None:
+            from .make_search_db import unpack_names
+            info = index.info()
+            dids, functions = unpack_names(index.names(), int(info["targets"]))
+            fnames, target_fn = function_names(dids, functions)
+            room = [int(info["query_room"])]
+            batch_limit = max(room[0] // 2, 1) if batch_nt is None else int(batch_nt)
+            skw = dict(search or {})
+            if skw.get("align", {}).get("ref") == "query":
+                skw["align"] = dict(skw["align"], ref="member")
+            ev_sum = dict(fragments=0, hits=0, calls=0)
+            hit_lines = []
+
+            def scan(batch, off, k):
+                # 2 * nucleotides bounds the fragments' residues: a batch over half the room has the room reserved for it
+                if 2 * len(batch) > room[0]:
+                    index.reserve(2 * len(batch))
+                    room[0] = 2 * len(batch)
+                ev = index.search_contigs(batch, off, min_res=min_frag, max_hits=max_hits, target_fn=target_fn, **skw)
+                ev_sum["fragments"] += ev.stats["fragments"]
+                ev_sum["hits"] += ev.search[3]["hits"]
+                ev_sum["calls"] += ev.stats["calls"]
+                if hits_out is not None:
+                    hit_lines.append(format_call_hits(ids[k:], dids, ev, off, skw.get("align", {}).get("ref", "longer"), functions))
+                return ev
+        line = _call_regions(ids, seqs, scan, batch_limit, fnames, out, merge_gap, min_score, min_len, write_all, gff, orfs_out, faa_out,
+                             start_codons, select, max_overlap, max_overlap_pct, free_min_res, coding, min_coding, min_train,
+                             coding_model_in, save_coding_model, starts, start_rounds, min_train_starts, start_model_in,
+                             save_start_model, repair, repair_min_count, max_junctions, shifts_out)
+        if index is not None:
+            if hits_out is not None:
+                with open(hits_out, "wb") as f:
+                    f.write(b"".join(hit_lines))
+            line += ", db: index (%d targets), fragments: %d, translated hits: %d, calls: %d" % (
+                int(info["targets"]), ev_sum["fragments"], ev_sum["hits"], ev_sum["calls"])
+        return line
+    finally:
+        if index is not None:
+            index.close()
+
+
+def _call_regions(ids, seqs, scan, batch_limit, fnames, out, merge_gap, min_score, min_len, write_all, gff, orfs_out, faa_out, start_codons,
+                  select, max_overlap, max_overlap_pct, free_min_res, coding, min_coding, min_train, coding_model_in, save_coding_model,
+                  starts, start_rounds, min_train_starts, start_model_in, save_start_model, repair, repair_min_count, max_junctions,
+                  shifts_out) -> str:
+    """call_regions behind its source of CALLs: scan(batch, off) gives what holds a batch's CALLs (a ScanResult or an Evidence:
+    regions(), orfs() and select() with the same arguments; k: the batch's first contig), batch_limit the characters a batch holds at most."""
+    from . import hotpath
+    want_orfs = orfs_out is not None or faa_out is not None
     coding_arg = None                   # what ScanResult.orfs / select take: None, True (own training) or a score table
     if coding:
         coding_arg = True
@@ -450,13 +578,13 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
     k = n_before = n_free = 0
     while k < len(ids):
         j, size = k, 0
-        while j < len(ids) and (j == k or size + len(seqs[j]) <= KmerGutsJava.MAX_BATCH_CHARS):
+        while j < len(ids) and (j == k or size + len(seqs[j]) <= batch_limit):
             size += len(seqs[j])
             j += 1
         off = np.zeros(j - k + 1, dtype=np.int64)
         off[1:] = np.cumsum([len(s) for s in seqs[k:j]])
         batch = b"".join(seqs[k:j])
-        with tab.scan(batch, off, params) as r:
+        with scan(batch, off, k) as r:
             if select:
                 got = r.select(off, batch, merge_gap, min_score, min_len, want_orfs, start_codons, not write_all,
                                max_overlap=max_overlap, max_overlap_pct=max_overlap_pct, free_min_res=free_min_res, **ckw)
@@ -585,15 +713,17 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m kmergutsjava_amd.call_regions",
                                  description="Merge the CALLs of a DNA scan into function regions on the contigs, on the GPU.")
-    ap.add_argument("-D", required=True, metavar="DATADIR", help="data directory (kmer.table.mem_map[.gz], function.index[.gz])")
+    ap.add_argument("-D", default=None, metavar="DATADIR", help="data directory (kmer.table.mem_map[.gz], function.index[.gz])")
+    ap.add_argument("--db", default=None, metavar="DB.kgsdb",
+                    help="in place of -D: the index file make_search_db wrote; the CALLs are the hits of a translated search against it")
     ap.add_argument("-q", required=True, metavar="CONTIGS", help="contig FASTA (.gz allowed)")
     ap.add_argument("-o", required=True, metavar="OUT", help="regions TSV (or GFF3) to write")
-    ap.add_argument("-m", type=int, default=5, help="minHits (default 5)")
-    ap.add_argument("-M", type=int, default=0, help="minWeightedHits (default 0)")
-    ap.add_argument("-g", type=int, default=200, help="maxGap (default 200)")
+    ap.add_argument("-m", type=int, default=None, help="minHits (default 5)")
+    ap.add_argument("-M", type=int, default=None, help="minWeightedHits (default 0)")
+    ap.add_argument("-g", type=int, default=None, help="maxGap (default 200)")
     ap.add_argument("-O", action="store_true", help="order constraint")
     ap.add_argument("--merge-gap", type=int, default=600, help="nucleotides two CALLs of one function may lie apart (default 600, this project's choice)")
-    ap.add_argument("--min-score", type=int, default=0, help="a region is kept with score >= this (default 0)")
+    ap.add_argument("--min-score", type=int, default=0, help="a region is kept with score >= this (default 0); with --db the score is in alignment-score units")
     ap.add_argument("--min-len", type=int, default=0, help="... and at least this many nucleotides long (default 0)")
     ap.add_argument("--all", action="store_true", help="write every region, not only the kept ones")
     ap.add_argument("--gff", action="store_true", help="write GFF3 instead of TSV")
@@ -625,7 +755,58 @@ def main(argv=None) -> int:
                     help="evidence ORFs a batch needs to train the start model (default 200, this project's choice); below: untrained, nothing moved")
     ap.add_argument("--start-model", metavar="IN", help="choose with the counts of this file (--save-start-model of a relative) instead of training")
     ap.add_argument("--save-start-model", metavar="OUT", help="write the start model's counts of the last round, summed over the batches")
+    ap.add_argument("--min-frag", type=int, default=None, metavar="N",
+                    help="with --db: residues a stop-to-stop fragment has at least to be searched (default 30, this project's choice, not tuned)")
+    ap.add_argument("--max-hits", type=int, default=None, metavar="N",
+                    help="with --db: hits of a fragment that become CALLs, 1..64 (default 1, this project's choice)")
+    ap.add_argument("--batch-nt", type=int, default=None, metavar="N",
+                    help="with --db: contigs are searched in batches of at most N nucleotides (default: half the index's query room); a longer "
+                         "contig is a batch of its own")
+    ap.add_argument("--hits", default=None, metavar="FILE", help="with --db: write one line per hit record that became a CALL")
+    ap.add_argument("--min-shared", type=int, default=None, help="with --db: as in search_proteins (default 2)")
+    ap.add_argument("--max-cand", type=int, default=None, help="with --db: as in search_proteins (default 8)")
+    ap.add_argument("--max-db-per-kmer", type=int, default=None, help="with --db: as in search_proteins (default 256)")
+    ap.add_argument("--min-ratio", type=int, default=None, help="with --db: a hit needs 100 * score >= this * ref (default 50)")
+    ap.add_argument("--align-ref", choices=("longer", "query"), default=None,
+                    help="with --db: ref is the fragment's self-score (query, the default here: a fragment is often a piece of a gene, so "
+                         "it is the fragment that must be covered; this project's choice) or the larger of the two (longer)")
+    ap.add_argument("--gap-open", type=int, default=None, help="with --db: as in search_proteins (default 11)")
+    ap.add_argument("--gap-extend", type=int, default=None, help="with --db: as in search_proteins (default 1)")
+    ap.add_argument("--max-cells", type=int, default=None, help="with --db: as in search_proteins (default 2^26)")
+    ap.add_argument("--ungapped", action="store_true", help="with --db: as in search_proteins")
+    ap.add_argument("--min-ungapped", type=int, default=None, metavar="N", help="with --ungapped: as in search_proteins")
+    ap.add_argument("--band", type=int, default=None, metavar="W", help="with --ungapped: as in search_proteins, 0..256")
     a = ap.parse_args(argv)
+    if a.D is not None and a.db is not None:
+        ap.error("give -D or --db, not both")
+    if a.D is None and a.db is None:
+        ap.error("one of -D and --db is required")
+    search_flags = (("--min-frag", a.min_frag), ("--max-hits", a.max_hits), ("--batch-nt", a.batch_nt), ("--hits", a.hits),
+                    ("--min-shared", a.min_shared), ("--max-cand", a.max_cand), ("--max-db-per-kmer", a.max_db_per_kmer),
+                    ("--min-ratio", a.min_ratio), ("--align-ref", a.align_ref), ("--gap-open", a.gap_open), ("--gap-extend", a.gap_extend),
+                    ("--max-cells", a.max_cells), ("--ungapped", a.ungapped or None), ("--min-ungapped", a.min_ungapped), ("--band", a.band))
+    if a.db is None:
+        for flag, given in search_flags:
+            if given is not None:
+                ap.error("%s needs --db" % flag)
+    else:
+        for flag, given in (("-m", a.m), ("-M", a.M), ("-g", a.g), ("-O", a.O or None)):
+            if given is not None:
+                ap.error("%s beside --db: it belongs to the table scan of -D" % flag)
+        if a.min_frag is not None and a.min_frag < 1:
+            ap.error("--min-frag must be >= 1")
+        if a.max_hits is not None and not 1 <= a.max_hits <= 64:
+            ap.error("--max-hits must be in 1..64")
+        if a.batch_nt is not None and a.batch_nt < 1:
+            ap.error("--batch-nt must be >= 1")
+        if a.band is not None and not a.ungapped:
+            ap.error("--band needs --ungapped")
+        if a.band is not None and not 0 <= a.band <= 256:
+            ap.error("--band must be in 0..256")
+        if a.min_ungapped is not None and not a.ungapped:
+            ap.error("--min-ungapped needs --ungapped")
+        if a.min_ungapped is not None and a.min_ungapped < 0:
+            ap.error("--min-ungapped must be >= 0")
     if a.free_orfs and a.orfs is None and a.faa is None:
         ap.error("--free-orfs needs --orfs or --faa")
     if a.coding and a.orfs is None and a.faa is None:
@@ -642,14 +823,25 @@ def main(argv=None) -> int:
         ap.error("--start-rounds, --min-train-starts, --start-model and --save-start-model need --starts")
     from . import _native as N
     try:
-        line = call_regions(a.D, a.q, a.o, a.m, a.M, a.g, a.O, a.merge_gap, a.min_score, a.min_len, a.all, a.gff,
+        dflt = lambda v, d: d if v is None else v      # noqa: E731
+        search = None
+        if a.db is not None:
+            search = dict(min_shared=dflt(a.min_shared, 2), max_cand=dflt(a.max_cand, 8), max_db_per_kmer=dflt(a.max_db_per_kmer, 256),
+                          align=dict(min_ratio_pct=dflt(a.min_ratio, 50), ref=dflt(a.align_ref, "query"), gap_open=dflt(a.gap_open, 11),
+                                     gap_extend=dflt(a.gap_extend, 1), max_cells=dflt(a.max_cells, 1 << 26)))
+            if a.ungapped:
+                search["ungapped"] = dict(min_score=a.min_ungapped or 0)
+            if a.band is not None:
+                search["band"] = a.band
+        line = call_regions(a.D, a.q, a.o, dflt(a.m, 5), dflt(a.M, 0), dflt(a.g, 200), a.O, a.merge_gap, a.min_score, a.min_len, a.all, a.gff,
                             orfs_out=a.orfs, faa_out=a.faa, start_codons=parse_start_codons(a.start_codons), select=a.select,
                             max_overlap=a.max_overlap, max_overlap_pct=a.max_overlap_pct,
                             free_min_res=a.min_res if a.free_orfs else None, coding=a.coding, min_coding=a.min_coding,
                             min_train=a.min_train, coding_model_in=a.coding_model, save_coding_model=a.save_coding_model,
                             starts=a.starts, start_rounds=a.start_rounds, min_train_starts=a.min_train_starts,
                             start_model_in=a.start_model, save_start_model=a.save_start_model, repair=a.repair,
-                            repair_min_count=a.repair_min_count, max_junctions=a.max_junctions, shifts_out=a.shifts)
+                            repair_min_count=a.repair_min_count, max_junctions=a.max_junctions, shifts_out=a.shifts, db=a.db,
+                            min_frag=dflt(a.min_frag, 30), max_hits=dflt(a.max_hits, 1), batch_nt=a.batch_nt, hits_out=a.hits, search=search)
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1

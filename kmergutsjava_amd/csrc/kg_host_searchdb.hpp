@@ -473,21 +473,20 @@ int searchdb_search_impl(kg_searchdb *db, const SearchDbAsk &q, kg_hitset *set)
     return KG_OK;
 }
 
-int searchdb_search_entry(kg_searchdb *db, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq,
-                          const int64_t *offsets, int64_t n_q, int64_t max_windows, int64_t max_pairs, int trace, int64_t max_trace_cells,
-                          const kg_mask_params *query_mask, const kg_ungapped_params *ung, const kg_band_params *band, kg_hitset **out)
+// the checks of what a search is asked beside its queries, in the order their words are reported (qplan: the queries' mask plan,
+// filled when query_mask is given)
+int searchdb_check_ask(const kg_searchdb *db, const kg_search_params *prm, const kg_align_params *al, int64_t max_windows, int64_t max_pairs,
+                       const SearchPathsAsk &ask, const kg_mask_params *query_mask, const kg_ungapped_params *ung, const kg_band_params *band,
+                       MaskPlan *qplan)
 {
-    if (!out) return fail(KG_ERR_ARG, "null argument");
-    *out = nullptr;
     if (!db) return fail(KG_ERR_ARG, "null kg_searchdb");
     if (!prm) return fail(KG_ERR_ARG, "null kg_search_params");
     if (prm->min_shared < 1) return fail(KG_ERR_ARG, "min_shared must be >= 1");
     if (prm->max_cand < 1 || prm->max_cand > kg::kSearchMaxCand) return fail(KG_ERR_ARG, "max_cand must be in 1..64");
     if (prm->max_db_per_kmer < 1) return fail(KG_ERR_ARG, "max_db_per_kmer must be >= 1");
     if (prm->reserved != 0) return fail(KG_ERR_ARG, "kg_search_params.reserved must be 0");
-    MaskPlan qplan;
     if (query_mask)
-        if (int rc = mask_plan(query_mask, &qplan)) return rc;
+        if (int rc = mask_plan(query_mask, qplan)) return rc;
     if (band && !ung) return fail(KG_ERR_ARG, "null kg_ungapped_params");
     if (ung) {
         if (ung->min_ungapped < 0) return fail(KG_ERR_ARG, "min_ungapped must be >= 0");
@@ -499,12 +498,23 @@ int searchdb_search_entry(kg_searchdb *db, const kg_search_params *prm, const kg
     if (int rc = align_check_params(al)) return rc;
     if (max_windows < 0) return fail(KG_ERR_ARG, "max_windows must be >= 0");
     if (max_pairs < 0) return fail(KG_ERR_ARG, "max_pairs must be >= 0");
-    const SearchPathsAsk ask{trace, max_trace_cells};
     if (ask.trace && (ask.trace & 3) != KG_TRACE_HITS && (ask.trace & 3) != KG_TRACE_ALL)
         return fail(KG_ERR_ARG, "trace must be KG_TRACE_HITS or KG_TRACE_ALL");
     if (ask.trace && ((ask.trace & ~15) || (ask.trace & (KG_TRACE_OPS | KG_TRACE_OPS_EQX)) == (KG_TRACE_OPS | KG_TRACE_OPS_EQX)))
         return fail(KG_ERR_ARG, "trace takes at most one of KG_TRACE_OPS and KG_TRACE_OPS_EQX beside its mode, and no bit above 15");
     if (ask.trace && ask.max_trace_cells < 1) return fail(KG_ERR_ARG, "max_trace_cells must be >= 1");
+    return KG_OK;
+}
+
+int searchdb_search_entry(kg_searchdb *db, const kg_search_params *prm, const kg_align_params *al, const uint8_t *h_seq, const uint8_t *d_seq,
+                          const int64_t *offsets, int64_t n_q, int64_t max_windows, int64_t max_pairs, int trace, int64_t max_trace_cells,
+                          const kg_mask_params *query_mask, const kg_ungapped_params *ung, const kg_band_params *band, kg_hitset **out)
+{
+    if (!out) return fail(KG_ERR_ARG, "null argument");
+    *out = nullptr;
+    const SearchPathsAsk ask{trace, max_trace_cells};
+    MaskPlan qplan;
+    if (int rc = searchdb_check_ask(db, prm, al, max_windows, max_pairs, ask, query_mask, ung, band, &qplan)) return rc;
     if (n_q < 0) return fail(KG_ERR_ARG, "n_q < 0");
     if (db->n_db + n_q >= (1ll << 29)) return fail(KG_ERR_LIMIT, "2^29 or more proteins in one call");
     if (int rc = check_protein_offsets(offsets, n_q, (int64_t)kg::kAlignMaxLen, "2^24")) return rc;

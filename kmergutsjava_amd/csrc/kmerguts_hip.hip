@@ -33,6 +33,7 @@
 #include "kg_select.hpp"
 #include "kg_votes.hpp"
 #include "kg_compose.hpp"
+#include "kg_evidence.hpp"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -69,3 +70,4 @@
 #include "kg_host_select.hpp"
 #include "kg_host_votes.hpp"
 #include "kg_host_compose.hpp"
+#include "kg_host_evidence.hpp"

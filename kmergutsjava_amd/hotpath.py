@@ -146,7 +146,162 @@ class _OrfChain:
             self.lib.kg_orfset_free(self.release())
 
 
-class ScanResult:
+class _GeneSteps:
+    """regions(), orfs() and select() of a holder of DNA CALL records, and the ORF steps the latter two share.  A subclass says
+    where the CALLs are: _need() (the library, or an error when the holder is closed), _n_seqs(), _regions_call (the region set
+    of its CALLs) and _repair_call (kg_regionset_repair, or its twin, with its CALLs)."""
+
+    def regions(self, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, device_out: bool = False):
+        """The CALL records of a DNA result merged into function regions in contig coordinates, on the GPU
+        (include/kmerguts_hip.h kg_result_regions states the rule).  offsets: the int64[n_seqs + 1] the scan was given.
+        -> (records, region_start): records a numpy array of _native.REGION_DTYPE in output order, or with device_out=True a
+        CUDA uint8 tensor of 48 bytes per region; region_start int64[n_seqs + 1], contig s owning records
+        [region_start[s], region_start[s + 1]).  The call's counts and device time are left in `region_stats`."""
+        lib = self._need()
+        off = _offsets(offsets, "the int64[n_seqs + 1] the scan was given", self._n_seqs())
+        p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
+        h = C.c_void_p()
+        N.check(self._regions_call(lib, p, off, h))
+        out, start, self.region_stats = _take_regionset(h, self._n_seqs(), device_out)
+        return out, start
+
+    def orfs(self, seq, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, start_codons: int = 7,
+             only_kept: bool = True, device_ptr: Optional[int] = None, free_min_res: Optional[int] = None, coding=None,
+             min_coding: int = 0, min_train_pairs: int = 100000, starts=None, start_min_res: int = 100, start_rounds: int = 4,
+             min_train_starts: int = 200, repair: bool = False, repair_min_count: int = 0, max_junctions: int = 4):
+        """regions() and then the open reading frame around every region with its translated protein, on the GPU, without a
+        host trip between the two (include/kmerguts_hip.h kg_regionset_orfs states the rule).  seq / offsets: what the scan was
+        given; device_ptr: the address of the bytes in HBM instead of seq.
+        -> (regions, region_start, orfs, prot_start, residues): orfs a numpy array of _native.ORF_DTYPE, index-aligned with
+        regions; the protein of ORF i is residues[prot_start[i] : prot_start[i + 1]] (uint8).  The two calls' counts and device
+        times are left in `region_stats` and `orf_stats`.
+        free_min_res: when given, the evidence-free candidates of at least that many residues (kg_orfset_add_free, flag
+        _native.ORF_FREE) follow the regions' ORFs in orfs, prot_start and residues; `orf_stats` is then the whole set's.
+        coding: None (or False: off), True or an int32[4096] score table (coding_table): every record is scored by its in-frame hexamer
+        log-odds and a free ORF below min_coding loses kept and gains _native.ORF_NONCODING (kg_orfset_coding, after
+        free_min_res); True trains on the set's own evidence ORFs when they have min_train_pairs codon pairs.  The scores
+        (int64 per record), the statistics and the counts of an own training are left in `coding_scores`, `coding_stats` and
+        `coding_model`.
+        starts: None (or False: off), True or a (pos int32[20][4], type int32[4]) weights pair (start_weights): the start codon of
+        every movable record is chosen by the start-site score (kg_orfset_starts, after coding, which it needs: the score's
+        coding half is the coding step's table).  True trains on the set's own evidence ORFs in start_rounds rounds when there
+        are min_train_starts of them; when the coding step was untrained, so are the starts.  The regions bound the evidence
+        ORFs' moves, start_min_res everything else.  The shifts in codons (int32 per record), the statistics and the last
+        round's counts are left in `start_shifts`, `start_stats` and `start_model`; `coding_scores` are then the new set's.
+        repair: the record and protein of every kept multi-frame region are replaced by the chain through its frames
+        (kg_result_repair, before free_min_res, so every later step sees the new extents; flag _native.ORF_REPAIRED).  CALLs
+        below repair_min_count take no part in a chain; a region of more than max_junctions + 1 segments is left alone.  The
+        junction records (_native.JUNCTION_DTYPE), junction_start int64[n_regions + 1] and the statistics are left in
+        `junctions`, `junction_start` and `repair_stats`."""
+        lib = self._need()
+        coding = _coding_arg(coding)
+        starts = _starts_arg(starts, coding)
+        off = _offsets(offsets, "the int64[n_seqs + 1] the scan was given", self._n_seqs())
+        p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
+        h, chain = C.c_void_p(), _OrfChain(lib)
+        N.check(self._regions_call(lib, p, off, h))
+        try:
+            self._orf_steps(chain, h, seq, device_ptr, off, start_codons, only_kept, repair, repair_min_count, max_junctions, free_min_res,
+                            coding, min_coding, min_train_pairs, starts, start_min_res, start_rounds, min_train_starts)
+            orfs, prot_start, residues, self.orf_stats = _take_orfset(chain.release(), False)
+        except BaseException:
+            chain.close()
+            lib.kg_regionset_free(h)
+            raise
+        regs, start, self.region_stats = _take_regionset(h, self._n_seqs(), False)
+        return regs, start, orfs, prot_start, residues
+
+    def select(self, offsets, seq=None, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, orfs: bool = False,
+               start_codons: int = 7, only_kept: bool = True, device_ptr: Optional[int] = None, max_overlap: int = 60,
+               max_overlap_pct: int = 50, free_min_res: Optional[int] = None, coding=None, min_coding: int = 0,
+               min_train_pairs: int = 100000, starts=None, start_min_res: int = 100, start_rounds: int = 4,
+               min_train_starts: int = 200, repair: bool = False, repair_min_count: int = 0, max_junctions: int = 4):
+        """regions() -- with orfs=True, orfs() -- and then the non-overlapping selection among the kept records, on the GPU and
+        without a host trip or a second scan in between (include/kmerguts_hip.h kg_regionset_select states the rule).  The
+        candidates are the regions' extents, or with orfs=True the ORFs' extents.
+        -> (regions, region_start, selection), or with orfs=True (regions, region_start, orfs, prot_start, residues, selection):
+        selection a numpy array of _native.SELECTION_DTYPE, index-aligned with the regions (and the ORFs).  The calls' counts and
+        device times are left in `region_stats`, `orf_stats` and `select_stats`.
+        free_min_res (with orfs=True): the evidence-free candidates are appended on the device before the selection, as orfs()
+        appends them; orfs, prot_start, residues and selection then hold them behind the regions' records.
+        coding, min_coding, min_train_pairs (with orfs=True): as orfs() takes them, applied after free_min_res and before the
+        selection, so a non-coding free ORF is not eligible and suppresses nothing.
+        starts, start_min_res, start_rounds, min_train_starts (with coding): as orfs() takes them, applied after coding and before
+        the selection, which therefore sees the new extents.
+        repair, repair_min_count, max_junctions (with orfs=True): as orfs() takes them, applied before free_min_res."""
+        lib = self._need()
+        if free_min_res is not None and not orfs:
+            raise ValueError("free_min_res needs orfs=True: the free candidates are ORFs")
+        coding = _coding_arg(coding)
+        if coding is not None and not orfs:
+            raise ValueError("coding needs orfs=True: the scores are the ORFs'")
+        if repair and not orfs:
+            raise ValueError("repair needs orfs=True: it rewrites ORFs")
+        starts = _starts_arg(starts, coding)
+        off = _offsets(offsets, "the int64[n_seqs + 1] the scan was given", self._n_seqs())
+        p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
+        sp = N.KgSelectParams(int(max_overlap), int(max_overlap_pct), 0)
+        h, sh, chain = C.c_void_p(), C.c_void_p(), _OrfChain(lib)
+        N.check(self._regions_call(lib, p, off, h))
+        try:
+            if orfs:
+                self._orf_steps(chain, h, seq, device_ptr, off, start_codons, only_kept, repair, repair_min_count, max_junctions,
+                                free_min_res, coding, min_coding, min_train_pairs, starts, start_min_res, start_rounds, min_train_starts)
+                N.check(lib.kg_orfset_select(chain.h, C.byref(sp), C.byref(sh)))
+            else:
+                N.check(lib.kg_regionset_select(h, C.byref(sp), C.byref(sh)))
+            taken, sh = sh, C.c_void_p()                # (_take_* frees what it is given, also when it raises)
+            sel, self.select_stats = _take_selectset(taken, False)      # a select set is freed before the set it came from
+            if orfs:
+                orf_recs, prot_start, residues, self.orf_stats = _take_orfset(chain.release(), False)
+        except BaseException:
+            if sh:
+                lib.kg_selectset_free(sh)
+            chain.close()
+            lib.kg_regionset_free(h)
+            raise
+        regs, start, self.region_stats = _take_regionset(h, self._n_seqs(), False)
+        if orfs:
+            return regs, start, orf_recs, prot_start, residues, sel
+        return regs, start, sel
+
+    def _orf_steps(self, chain, rh, seq, device_ptr, off, start_codons, only_kept, repair, repair_min_count, max_junctions, free_min_res,
+                   coding, min_coding, min_train_pairs, starts, start_min_res, start_rounds, min_train_starts):
+        """The steps of orfs() and select(orfs=True) behind the region set rh, each on the set the one before it left in `chain`:
+        kg_regionset_orfs, then kg_result_repair, kg_orfset_add_free, kg_orfset_coding and kg_orfset_starts where they are asked
+        for (coding and starts: what _coding_arg and _starts_arg gave).  The steps' side results go into self."""
+        lib = chain.lib
+        keep = None if device_ptr is not None else _seq_bytes(seq, off)        # (alive while the steps read it)
+        batch = (C.c_void_p(device_ptr) if keep is None else _ptr(keep), int(keep is None), off.ctypes.data, off.size - 1)
+        op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
+        chain.step(lambda oh, new: lib.kg_regionset_orfs(rh, C.byref(op), *batch, new))
+        if repair:
+            rp = N.KgRepairParams(int(start_codons), int(repair_min_count), int(max_junctions), 0)
+            chain.step(lambda oh, new: self._repair_call(lib, rh, oh, rp, batch, new))
+            self.junctions, self.junction_start, self.repair_stats = _junctions(chain.h)
+        if free_min_res is not None:
+            fp = N.KgFreeParams(int(free_min_res), int(start_codons), 0)
+            chain.step(lambda oh, new: lib.kg_orfset_add_free(oh, C.byref(fp), *batch, new))
+        if coding is not None:
+            cp = N.KgCodingParams(int(min_coding), 0, int(min_train_pairs))
+            chain.step(lambda oh, new: lib.kg_orfset_coding(oh, C.byref(cp), None if coding is True else coding.ctypes.data, *batch, new))
+            self.coding_scores, self.coding_stats, self.coding_model = _coding_results(chain.h)
+        if starts is not None:
+            table = coding
+            if coding is True:
+                # the table the coding step trained and used; none when it was untrained, and then the starts are untrained too
+                trained = self.coding_stats["trained"] != 0
+                table = coding_table(*self.coding_model) if trained else np.zeros(N.CODING_BINS, dtype=np.int32)
+                if not trained and starts is True:
+                    min_train_starts = 1 << 62
+            sp = N.KgStartParams(int(start_min_res), int(start_codons), int(start_rounds), 0, int(min_train_starts))
+            chain.step(lambda oh, new: lib.kg_orfset_starts(oh, C.byref(sp), table.ctypes.data, None if starts is True else C.addressof(starts),
+                                                            rh, *batch, new))
+            self.start_shifts, self.start_stats, self.start_model = _starts_results(chain.h)
+            self.coding_scores = _coding_results(chain.h)[0]
+
+
+class ScanResult(_GeneSteps):
     """Owns one kg_result.  Record arrays are numpy structured arrays (copies)."""
 
     def __init__(self, handle: int, table=None):
@@ -155,6 +310,15 @@ class ScanResult:
         st = N.KgStats()
         N.check(N.load().kg_result_stats(self._h, C.byref(st)))
         self.stats = st.as_dict()
+
+    def _n_seqs(self) -> int:
+        return self.stats["n_seqs"]
+
+    def _regions_call(self, lib, p, off, h):
+        return lib.kg_result_regions(self._h, C.byref(p), off.ctypes.data, C.byref(h))
+
+    def _repair_call(self, lib, rh, oh, rp, batch, new):
+        return lib.kg_result_repair(self._h, rh, oh, C.byref(rp), *batch, new)
 
     def _need(self):
         if not self._h:
@@ -293,20 +457,6 @@ class ScanResult:
         self.assign_ms = float(ms.value)
         return out
 
-    def regions(self, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, device_out: bool = False):
-        """The CALL records of a DNA result merged into function regions in contig coordinates, on the GPU
-        (include/kmerguts_hip.h kg_result_regions states the rule).  offsets: the int64[n_seqs + 1] the scan was given.
-        -> (records, region_start): records a numpy array of _native.REGION_DTYPE in output order, or with device_out=True a
-        CUDA uint8 tensor of 48 bytes per region; region_start int64[n_seqs + 1], contig s owning records
-        [region_start[s], region_start[s + 1]).  The call's counts and device time are left in `region_stats`."""
-        lib = self._need()
-        off = _offsets(offsets, "the int64[n_seqs + 1] the scan was given", self.stats["n_seqs"])
-        p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
-        h = C.c_void_p()
-        N.check(lib.kg_result_regions(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
-        out, start, self.region_stats = _take_regionset(h, self.stats["n_seqs"], device_out)
-        return out, start
-
     def otu_votes(self, offsets, min_votes: int = 10, min_share_pct: int = 50, min_calls: int = 1, device_out: bool = False):
         """Every OTU vote of the result tallied per sequence, one OTU per sequence and the batch's bins, on the GPU
         (include/kmerguts_hip.h kg_result_otu_votes states the rule).  offsets: the int64[n_seqs + 1] the scan was given.
@@ -321,141 +471,6 @@ class ScanResult:
         N.check(lib.kg_result_otu_votes(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
         votes, start, classes, bins, self.vote_stats = _take_voteset(h, self.stats["n_seqs"], device_out)
         return votes, start, classes, bins
-
-    def orfs(self, seq, offsets, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, start_codons: int = 7,
-             only_kept: bool = True, device_ptr: Optional[int] = None, free_min_res: Optional[int] = None, coding=None,
-             min_coding: int = 0, min_train_pairs: int = 100000, starts=None, start_min_res: int = 100, start_rounds: int = 4,
-             min_train_starts: int = 200, repair: bool = False, repair_min_count: int = 0, max_junctions: int = 4):
-        """regions() and then the open reading frame around every region with its translated protein, on the GPU, without a
-        host trip between the two (include/kmerguts_hip.h kg_regionset_orfs states the rule).  seq / offsets: what the scan was
-        given; device_ptr: the address of the bytes in HBM instead of seq.
-        -> (regions, region_start, orfs, prot_start, residues): orfs a numpy array of _native.ORF_DTYPE, index-aligned with
-        regions; the protein of ORF i is residues[prot_start[i] : prot_start[i + 1]] (uint8).  The two calls' counts and device
-        times are left in `region_stats` and `orf_stats`.
-        free_min_res: when given, the evidence-free candidates of at least that many residues (kg_orfset_add_free, flag
-        _native.ORF_FREE) follow the regions' ORFs in orfs, prot_start and residues; `orf_stats` is then the whole set's.
-        coding: None (or False: off), True or an int32[4096] score table (coding_table): every record is scored by its in-frame hexamer
-        log-odds and a free ORF below min_coding loses kept and gains _native.ORF_NONCODING (kg_orfset_coding, after
-        free_min_res); True trains on the set's own evidence ORFs when they have min_train_pairs codon pairs.  The scores
-        (int64 per record), the statistics and the counts of an own training are left in `coding_scores`, `coding_stats` and
-        `coding_model`.
-        starts: None (or False: off), True or a (pos int32[20][4], type int32[4]) weights pair (start_weights): the start codon of
-        every movable record is chosen by the start-site score (kg_orfset_starts, after coding, which it needs: the score's
-        coding half is the coding step's table).  True trains on the set's own evidence ORFs in start_rounds rounds when there
-        are min_train_starts of them; when the coding step was untrained, so are the starts.  The regions bound the evidence
-        ORFs' moves, start_min_res everything else.  The shifts in codons (int32 per record), the statistics and the last
-        round's counts are left in `start_shifts`, `start_stats` and `start_model`; `coding_scores` are then the new set's.
-        repair: the record and protein of every kept multi-frame region are replaced by the chain through its frames
-        (kg_result_repair, before free_min_res, so every later step sees the new extents; flag _native.ORF_REPAIRED).  CALLs
-        below repair_min_count take no part in a chain; a region of more than max_junctions + 1 segments is left alone.  The
-        junction records (_native.JUNCTION_DTYPE), junction_start int64[n_regions + 1] and the statistics are left in
-        `junctions`, `junction_start` and `repair_stats`."""
-        lib = self._need()
-        coding = _coding_arg(coding)
-        starts = _starts_arg(starts, coding)
-        off = _offsets(offsets, "the int64[n_seqs + 1] the scan was given", self.stats["n_seqs"])
-        p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
-        h, chain = C.c_void_p(), _OrfChain(lib)
-        N.check(lib.kg_result_regions(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
-        try:
-            self._orf_steps(chain, h, seq, device_ptr, off, start_codons, only_kept, repair, repair_min_count, max_junctions, free_min_res,
-                            coding, min_coding, min_train_pairs, starts, start_min_res, start_rounds, min_train_starts)
-            orfs, prot_start, residues, self.orf_stats = _take_orfset(chain.release(), False)
-        except BaseException:
-            chain.close()
-            lib.kg_regionset_free(h)
-            raise
-        regs, start, self.region_stats = _take_regionset(h, self.stats["n_seqs"], False)
-        return regs, start, orfs, prot_start, residues
-
-    def select(self, offsets, seq=None, merge_gap: int = 600, min_score: int = 0, min_len: int = 0, orfs: bool = False,
-               start_codons: int = 7, only_kept: bool = True, device_ptr: Optional[int] = None, max_overlap: int = 60,
-               max_overlap_pct: int = 50, free_min_res: Optional[int] = None, coding=None, min_coding: int = 0,
-               min_train_pairs: int = 100000, starts=None, start_min_res: int = 100, start_rounds: int = 4,
-               min_train_starts: int = 200, repair: bool = False, repair_min_count: int = 0, max_junctions: int = 4):
-        """regions() -- with orfs=True, orfs() -- and then the non-overlapping selection among the kept records, on the GPU and
-        without a host trip or a second scan in between (include/kmerguts_hip.h kg_regionset_select states the rule).  The
-        candidates are the regions' extents, or with orfs=True the ORFs' extents.
-        -> (regions, region_start, selection), or with orfs=True (regions, region_start, orfs, prot_start, residues, selection):
-        selection a numpy array of _native.SELECTION_DTYPE, index-aligned with the regions (and the ORFs).  The calls' counts and
-        device times are left in `region_stats`, `orf_stats` and `select_stats`.
-        free_min_res (with orfs=True): the evidence-free candidates are appended on the device before the selection, as orfs()
-        appends them; orfs, prot_start, residues and selection then hold them behind the regions' records.
-        coding, min_coding, min_train_pairs (with orfs=True): as orfs() takes them, applied after free_min_res and before the
-        selection, so a non-coding free ORF is not eligible and suppresses nothing.
-        starts, start_min_res, start_rounds, min_train_starts (with coding): as orfs() takes them, applied after coding and before
-        the selection, which therefore sees the new extents.
-        repair, repair_min_count, max_junctions (with orfs=True): as orfs() takes them, applied before free_min_res."""
-        lib = self._need()
-        if free_min_res is not None and not orfs:
-            raise ValueError("free_min_res needs orfs=True: the free candidates are ORFs")
-        coding = _coding_arg(coding)
-        if coding is not None and not orfs:
-            raise ValueError("coding needs orfs=True: the scores are the ORFs'")
-        if repair and not orfs:
-            raise ValueError("repair needs orfs=True: it rewrites ORFs")
-        starts = _starts_arg(starts, coding)
-        off = _offsets(offsets, "the int64[n_seqs + 1] the scan was given", self.stats["n_seqs"])
-        p = N.KgRegionParams(int(merge_gap), int(min_score), int(min_len))
-        sp = N.KgSelectParams(int(max_overlap), int(max_overlap_pct), 0)
-        h, sh, chain = C.c_void_p(), C.c_void_p(), _OrfChain(lib)
-        N.check(lib.kg_result_regions(self._h, C.byref(p), off.ctypes.data, C.byref(h)))
-        try:
-            if orfs:
-                self._orf_steps(chain, h, seq, device_ptr, off, start_codons, only_kept, repair, repair_min_count, max_junctions,
-                                free_min_res, coding, min_coding, min_train_pairs, starts, start_min_res, start_rounds, min_train_starts)
-                N.check(lib.kg_orfset_select(chain.h, C.byref(sp), C.byref(sh)))
-            else:
-                N.check(lib.kg_regionset_select(h, C.byref(sp), C.byref(sh)))
-            taken, sh = sh, C.c_void_p()                # (_take_* frees what it is given, also when it raises)
-            sel, self.select_stats = _take_selectset(taken, False)      # a select set is freed before the set it came from
-            if orfs:
-                orf_recs, prot_start, residues, self.orf_stats = _take_orfset(chain.release(), False)
-        except BaseException:
-            if sh:
-                lib.kg_selectset_free(sh)
-            chain.close()
-            lib.kg_regionset_free(h)
-            raise
-        regs, start, self.region_stats = _take_regionset(h, self.stats["n_seqs"], False)
-        if orfs:
-            return regs, start, orf_recs, prot_start, residues, sel
-        return regs, start, sel
-
-    def _orf_steps(self, chain, rh, seq, device_ptr, off, start_codons, only_kept, repair, repair_min_count, max_junctions, free_min_res,
-                   coding, min_coding, min_train_pairs, starts, start_min_res, start_rounds, min_train_starts):
-        """The steps of orfs() and select(orfs=True) behind the region set rh, each on the set the one before it left in `chain`:
-        kg_regionset_orfs, then kg_result_repair, kg_orfset_add_free, kg_orfset_coding and kg_orfset_starts where they are asked
-        for (coding and starts: what _coding_arg and _starts_arg gave).  The steps' side results go into self."""
-        lib = chain.lib
-        keep = None if device_ptr is not None else _seq_bytes(seq, off)        # (alive while the steps read it)
-        batch = (C.c_void_p(device_ptr) if keep is None else _ptr(keep), int(keep is None), off.ctypes.data, off.size - 1)
-        op = N.KgOrfParams(int(start_codons), int(bool(only_kept)), 0)
-        chain.step(lambda oh, new: lib.kg_regionset_orfs(rh, C.byref(op), *batch, new))
-        if repair:
-            rp = N.KgRepairParams(int(start_codons), int(repair_min_count), int(max_junctions), 0)
-            chain.step(lambda oh, new: lib.kg_result_repair(self._h, rh, oh, C.byref(rp), *batch, new))
-            self.junctions, self.junction_start, self.repair_stats = _junctions(chain.h)
-        if free_min_res is not None:
-            fp = N.KgFreeParams(int(free_min_res), int(start_codons), 0)
-            chain.step(lambda oh, new: lib.kg_orfset_add_free(oh, C.byref(fp), *batch, new))
-        if coding is not None:
-            cp = N.KgCodingParams(int(min_coding), 0, int(min_train_pairs))
-            chain.step(lambda oh, new: lib.kg_orfset_coding(oh, C.byref(cp), None if coding is True else coding.ctypes.data, *batch, new))
-            self.coding_scores, self.coding_stats, self.coding_model = _coding_results(chain.h)
-        if starts is not None:
-            table = coding
-            if coding is True:
-                # the table the coding step trained and used; none when it was untrained, and then the starts are untrained too
-                trained = self.coding_stats["trained"] != 0
-                table = coding_table(*self.coding_model) if trained else np.zeros(N.CODING_BINS, dtype=np.int32)
-                if not trained and starts is True:
-                    min_train_starts = 1 << 62
-            sp = N.KgStartParams(int(start_min_res), int(start_codons), int(start_rounds), 0, int(min_train_starts))
-            chain.step(lambda oh, new: lib.kg_orfset_starts(oh, C.byref(sp), table.ctypes.data, None if starts is True else C.addressof(starts),
-                                                            rh, *batch, new))
-            self.start_shifts, self.start_stats, self.start_model = _starts_results(chain.h)
-            self.coding_scores = _coding_results(chain.h)[0]
 
     def close(self) -> None:
         if self._h:
@@ -1012,8 +1027,8 @@ def _seed_params(seeds):
     return N.KgSeedParams(len(masks), n_cls, (C.c_uint8 * 20)(*cls), (C.c_uint32 * 4)(*masks), 0)
 
 
-def _take_hitset(h, has_mask: bool, has_ung: bool, band, paths, ops, db: bool = False):
-    """Copy a kg_hitset out in search_proteins' return shape and free it."""
+def _take_hitset(h, has_mask: bool, has_ung: bool, band, paths, ops, db: bool = False, free: bool = True):
+    """Copy a kg_hitset out in search_proteins' return shape and free it (free=False: the set is lent, and stays)."""
     lib = N.load()
     try:
         st = N.KgSearchStats()
@@ -1054,7 +1069,8 @@ def _take_hitset(h, has_mask: bool, has_ung: bool, band, paths, ops, db: bool = 
             return got + extra
         return (_copy_records(lib.kg_hitset_copy, h, int(lib.kg_hitset_count(h)), N.SEARCH_HIT_DTYPE), starts, dict(st.as_dict(), **more)) + extra
     finally:
-        lib.kg_hitset_free(h)
+        if free:
+            lib.kg_hitset_free(h)
 
 
 def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256,
@@ -1167,15 +1183,37 @@ def search_proteins(seq, offsets, n_db: int, min_shared: int = 2, max_cand: int 
     return _take_hitset(h, mp is not None, up is not None, band, paths, ops)
 
 
+def _search_options(ungapped, band, paths, ops):
+    """The checks SearchDb.search and search_contigs share -> (kg_ungapped_params or None, the trace word)."""
+    if band is not None and (ungapped is None or ungapped is False):
+        raise ValueError("band needs ungapped")
+    up = None
+    if ungapped is not None and ungapped is not False:
+        if ungapped is True:
+            ungapped = {}
+        if not isinstance(ungapped, dict) or set(ungapped) - {"min_score"}:
+            raise ValueError("ungapped must be None, True or {'min_score': N}")
+        up = N.KgUngappedParams(int(ungapped.get("min_score", 0)), (C.c_int32 * 3)(0, 0, 0))
+    if paths is not None and paths not in N.TRACE_MODES:
+        raise ValueError("paths must be None, 'hits' or 'all'")
+    if ops is not None and ops not in N.OPS_MODES:
+        raise ValueError("ops must be None, 'm' or 'eqx'")
+    if ops is not None and paths is None:
+        raise ValueError("ops needs paths")
+    trace = (N.TRACE_MODES[paths] if paths is not None else 0) | (N.OPS_MODES[ops] if ops is not None else 0)
+    return up, trace
+
+
 class SearchDb:
     """A resident protein database (include/kmerguts_hip.h kg_searchdb): the targets' half of search_proteins' work, made once and
     kept on the device.  build() makes it from the targets, save() writes its file and open() reads one; search() gives, for a
     batch of queries, what search_proteins gives for "the targets, then these queries" with the same options, byte for byte.
     One call at a time per handle.  Use as a context manager or call close()."""
 
-    def __init__(self, handle, path: Optional[str] = None):
+    def __init__(self, handle, path: Optional[str] = None, device: int = 0):
         self._h = handle
         self._path = path               # open(): the file, which targets() reads
+        self._device = int(device)      # search_contigs: the device the evidence's table-less stages run on
 
     @classmethod
     def build(cls, seq, offsets, seeds=None, mask=None, names: bytes = b"", max_windows: int = 0, query_room: int = 0, device: int = 0,
@@ -1196,13 +1234,13 @@ class SearchDb:
         else:
             arr = _seq_bytes(seq, off)
             N.check(lib.kg_searchdb_build(device, _ptr(arr), *tail))
-        return cls(h)
+        return cls(h, device=device)
 
     @classmethod
     def open(cls, path: str, query_room: int = 0, device: int = 0) -> "SearchDb":
         h = C.c_void_p()
         N.check(N.load().kg_searchdb_open(device, os.fsencode(path), int(query_room), C.byref(h)))
-        return cls(h, path)
+        return cls(h, path, device)
 
     def targets(self):
         """(residues uint8, offsets int64[n_db + 1]) of an opened index, read from its file's first two sections (the file has
@@ -1257,22 +1295,7 @@ class SearchDb:
                band: Optional[int] = None):
         """search_proteins' keyword arguments and return shape, with seq / offsets the queries alone; the seeds are the handle's and
         mask (window, trigger, extend) masks the queries.  The statistics also hold "db" (query_kmers, found, ms_probe, ms_upload)."""
-        if band is not None and (ungapped is None or ungapped is False):
-            raise ValueError("band needs ungapped")
-        up = None
-        if ungapped is not None and ungapped is not False:
-            if ungapped is True:
-                ungapped = {}
-            if not isinstance(ungapped, dict) or set(ungapped) - {"min_score"}:
-                raise ValueError("ungapped must be None, True or {'min_score': N}")
-            up = N.KgUngappedParams(int(ungapped.get("min_score", 0)), (C.c_int32 * 3)(0, 0, 0))
-        if paths is not None and paths not in N.TRACE_MODES:
-            raise ValueError("paths must be None, 'hits' or 'all'")
-        if ops is not None and ops not in N.OPS_MODES:
-            raise ValueError("ops must be None, 'm' or 'eqx'")
-        if ops is not None and paths is None:
-            raise ValueError("ops needs paths")
-        trace = (N.TRACE_MODES[paths] if paths is not None else 0) | (N.OPS_MODES[ops] if ops is not None else 0)
+        up, trace = _search_options(ungapped, band, paths, ops)
         off = _offsets(offsets, "int64[n_q + 1]")
         p = N.KgSearchParams(int(min_shared), int(max_cand), int(max_db_per_kmer), 0)
         ap, _keep = _align_params(**(align or {}))
@@ -1291,6 +1314,45 @@ class SearchDb:
         has_mask = mp is not None or self.info()["mask"] is not None
         return _take_hitset(h, has_mask, up is not None, band, paths, ops, db=True)
 
+    def search_contigs(self, seq, offsets, min_res: int = N.TRANSLATE_MIN_RES, max_hits: int = N.TRANSLATE_MAX_HITS, target_fn=None,
+                       device_ptr: Optional[int] = None, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256,
+                       align: Optional[dict] = None, max_windows: int = 0, max_pairs: int = 0, paths: Optional[str] = None,
+                       max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS, ops: Optional[str] = None, mask=None, ungapped=None,
+                       band: Optional[int] = None) -> "Evidence":
+        """Genes by homology (include/kmerguts_hip.h kg_contigs_search_translated states the rule): every stop-to-stop run of the
+        six frames of the contigs with at least min_res residues is a query of search(); a hit of rank below max_hits with a
+        traced path becomes a CALL record in contig coordinates whose fI is the target, or target_fn[target] (int32[n_db]).
+        seq / offsets: the contigs, as a scan takes them; device_ptr: the address of the bytes in HBM instead of seq.  The other
+        keywords are search()'s; paths=None is read as "hits", since a CALL needs the path's start.  -> an Evidence."""
+        hd = self._handle()
+        up, trace = _search_options(ungapped, band, "hits" if paths is None else paths, ops)
+        if int(min_res) < 1:
+            raise ValueError("min_res must be >= 1")
+        if not 1 <= int(max_hits) <= 64:
+            raise ValueError("max_hits must be in 1..64")
+        off = _offsets(offsets, "int64[n_seqs + 1]")
+        fn = None
+        if target_fn is not None:
+            fn = np.ascontiguousarray(np.asarray(target_fn, dtype=np.int32))
+            if fn.shape != (self.info()["targets"],):
+                raise ValueError("target_fn must hold one function per target")
+            if fn.size and int(fn.min()) < 0:
+                raise ValueError("target_fn must be >= 0")
+        p = N.KgSearchParams(int(min_shared), int(max_cand), int(max_db_per_kmer), 0)
+        ap, _keep = _align_params(**(align or {}))
+        tp = N.KgTranslateParams(int(min_res), int(max_hits), (C.c_int32 * 2)(0, 0))
+        mp = _mask_params(mask)
+        bp = N.KgBandParams(int(band), (C.c_int32 * 3)(0, 0, 0)) if band is not None else None
+        keep = None if device_ptr is not None else _seq_bytes(seq, off)
+        h = C.c_void_p()
+        N.check(N.load().kg_contigs_search_translated(
+            hd, C.byref(p), C.byref(ap), C.byref(tp), C.c_void_p(device_ptr) if keep is None else _ptr(keep), int(keep is None),
+            off.ctypes.data, off.size - 1, int(max_windows), int(max_pairs), trace, int(max_trace_cells),
+            C.byref(mp[0]) if mp is not None else None, C.byref(up) if up is not None else None, C.byref(bp) if bp is not None else None,
+            _ptr(fn), C.byref(h)))
+        has_mask = mp is not None or self.info()["mask"] is not None
+        return Evidence(h, off.size - 1, self._device, has_mask, up is not None, band, "hits" if paths is None else paths, ops)
+
     def close(self) -> None:
         if self._h is not None:
             N.load().kg_searchdb_free(self._h)
@@ -1301,6 +1363,65 @@ class SearchDb:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class Evidence(_GeneSteps):
+    """Owns one kg_evidence, what SearchDb.search_contigs returns: `calls` (_native.CALL_DTYPE, in the hit records' order),
+    `call_hits` (int64: the hit record of every CALL), `fragments` ((records _native.ORF_DTYPE, prot_start, residues), what
+    free_orfs(start_codons=0) gives), `search` (what SearchDb.search returns for the fragments' proteins) and `stats`
+    (fragments, fragment_residues, records, calls, dropped_status, dropped_rank, dropped_untraced, ms_*).
+    regions(), orfs() and select() are ScanResult's, arguments, results and side attributes, on these CALLs; the repair step is
+    kg_regionset_repair with the evidence's device CALLs.  Use as a context manager or call close(); the evidence may outlive
+    its SearchDb."""
+
+    def __init__(self, handle, n_seqs: int, device: int, has_mask: bool, has_ung: bool, band, paths, ops):
+        self._h = handle
+        self._seqs, self._dev = int(n_seqs), int(device)
+        lib = N.load()
+        try:
+            st = N.KgTranslateStats()
+            N.check(lib.kg_evidence_stats(self._h, C.byref(st)))
+            self.stats = st.as_dict()
+            n = int(lib.kg_evidence_calls_count(self._h))
+            self.calls = _copy_records(lib.kg_evidence_calls_copy, self._h, n, N.CALL_DTYPE)
+            self.call_hits = _copy_records(lib.kg_evidence_call_hits_copy, self._h, n, np.int64)
+            frags = _take_orfset(C.c_void_p(lib.kg_evidence_fragments(self._h)), False, free=False)
+            self.fragments, self.fragment_stats = frags[:3], frags[3]
+            self.search = _take_hitset(C.c_void_p(lib.kg_evidence_hits(self._h)), has_mask, has_ung, band, paths, ops, db=True, free=False)
+        except BaseException:
+            self.close()
+            raise
+
+    def _need(self):
+        if not self._h:
+            raise ValueError("the Evidence is closed")
+        return N.load()
+
+    def _n_seqs(self) -> int:
+        return self._seqs
+
+    def _regions_call(self, lib, p, off, h):
+        return lib.kg_regions_calls(self._dev, C.byref(p), _ptr(self.calls), self.calls.size, off.ctypes.data, off.size - 1, C.byref(h))
+
+    def _repair_call(self, lib, rh, oh, rp, batch, new):
+        return lib.kg_regionset_repair(rh, oh, C.c_void_p(lib.kg_evidence_calls_device(self._h)), 1, self.calls.size, C.byref(rp), *batch, new)
+
+    def close(self) -> None:
+        if self._h:
+            N.load().kg_evidence_free(self._h)
+            self._h = C.c_void_p(None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def assign_calls(calls, call_start, otu=None, min_score: int = 0, min_share_pct: int = 50, device: int = 0) -> np.ndarray:
@@ -1454,8 +1575,9 @@ def compose_contigs(seq, offsets, labels=None, model=None, min_len: int = 1500, 
         lib.kg_compset_free(h)
 
 
-def _take_orfset(h, device_out: bool):
-    """Copy a kg_orfset out (to the host, or into CUDA tensors) and free it.  -> (records, prot_start, residues, statistics)."""
+def _take_orfset(h, device_out: bool, free: bool = True):
+    """Copy a kg_orfset out (to the host, or into CUDA tensors) and free it (free=False: the set is lent, and stays).
+    -> (records, prot_start, residues, statistics)."""
     lib = N.load()
     try:
         st = N.KgOrfStats()
@@ -1473,7 +1595,8 @@ def _take_orfset(h, device_out: bool):
             N.check(lib.kg_orfset_prot_start(h, start.ctypes.data))
         return out, start, res, st.as_dict()
     finally:
-        lib.kg_orfset_free(h)
+        if free:
+            lib.kg_orfset_free(h)
 
 
 def _junctions(h):
