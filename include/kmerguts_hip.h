@@ -1369,7 +1369,9 @@ void kg_orfset_free(kg_orfset *s);
  * unchanged byte for byte.  The given sets stay valid; the new one is freed before them.  It runs before kg_orfset_add_free:
  * the ORF set must have exactly the region set's records.  kg_orfset_stats of the new set is the given set's with residues,
  * complete, interrupted and partial5 brought up to date.  The junction list stays with the new set only: the sets that
- * kg_orfset_add_free, kg_orfset_coding and kg_orfset_starts make from it keep the records' indices but not the list.
+ * kg_orfset_add_free, kg_orfset_coding and kg_orfset_starts make from it keep the records' indices, the repaired records and
+ * their proteins, but not the list.  A given set may carry KG_ORF_REPAIRED records (it is one of those sets, or an earlier
+ * call's): they are kept, record and protein, unless this call repairs them again, and the junction list is this call's alone.
  * kg_result_repair passes the result's device CALLs.  The coding score of a repaired record (rule 2 of the coding section) is
  * that of its first frame read straight through its extent.
  * Validation.  The CALL list must be the set's: every CALL has to fall inside exactly one region of its group, and every

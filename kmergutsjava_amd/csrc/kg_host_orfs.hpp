@@ -177,6 +177,17 @@ int translate_orfs(kg_table *t, Scratch &sc, const kg_orf *d_orfs, uint64_t n, c
     return KG_OK;
 }
 
+// ... and over them the given set's bytes where a record is a repaired one (kg_repair.hpp: it does not read in one frame).  The
+// given set's record i is d_orfs[i] and has kept its length; records behind the given set's are never repaired ones.
+int keep_repaired(kg_table *t, const kg_orf *d_orfs, uint64_t n, const int64_t *d_start, uint64_t n_res, const kg_orfset *given, uint8_t *d_res)
+{
+    if (n_res == 0 || !given || given->count == 0) return KG_OK;
+    hipLaunchKernelGGL(kg::orf_keep_repaired_kernel, dim3(grid_of((n_res + kg::kOrfResPerLane - 1) / kg::kOrfResPerLane)), dim3(256), 0,
+                       t->stream, d_orfs, n, d_start, n_res, given->d_prot_start, given->d_res, d_res);
+    HIP_TRY(hipGetLastError());
+    return KG_OK;
+}
+
 // the three arrays of every ORF set leave the call's scratch, as a stage's own do beside them: the rest goes back to the cache
 void keep_orfs(kg_orfset *set, Scratch &sc, kg_orf *d_orfs, int64_t *d_start, uint8_t *d_res, uint64_t n, uint64_t n_res, uint64_t n_seqs)
 {
@@ -331,7 +342,9 @@ int free_impl(kg_table *t, const kg_free_params *prm, const kg_orfset *parent, c
     const uint64_t n_res = h[kg::kOrfFreeResidues];
     if (n_res >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more residues in one call");
     uint8_t *d_res = nullptr;
-    if ((rc = translate_orfs(t, sc, d_out, n, d_start, n_res, d_seq, pl.d_off, &d_res))) return rc;
+    if ((rc = translate_orfs(t, sc, d_out, n, d_start, n_res, d_seq, pl.d_off, &d_res)) ||
+        (rc = keep_repaired(t, d_out, n, d_start, n_res, parent, d_res)))
+        return rc;
     HIP_TRY(hipEventRecord(t->ev[kEvStageEnd], s));
     HIP_TRY(hipStreamSynchronize(s));
     if (parent) set->st = parent->st;

@@ -297,7 +297,10 @@ int kg_orfset_starts(kg_orfset *os, const kg_start_params *p, const int32_t *tab
     const uint64_t n_res = w.counter(kg::kStartCntResidues);
     uint8_t *d_res = nullptr;
     // rule 9's "old protein from residue k on, residue 0 = 'M'" is the translation of the new record: rule 5 of the ORF section
-    if ((rc = translate_orfs(t, w.sc, d_out, n, d_start, n_res, d_seq, w.d_off, &d_res))) return rc;
+    // ... but for a repaired record, whose protein is not its extent read through: it has not moved, and keeps the given bytes
+    if ((rc = translate_orfs(t, w.sc, d_out, n, d_start, n_res, d_seq, w.d_off, &d_res)) ||
+        (rc = keep_repaired(t, d_out, n, d_start, n_res, os, d_res)))
+        return rc;
     HIP_TRY(hipEventRecord(ev[3], s));
     HIP_TRY(hipStreamSynchronize(s));
     w.finish(ev);

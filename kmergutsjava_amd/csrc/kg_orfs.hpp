@@ -623,4 +623,30 @@ __global__ __launch_bounds__(256) void orf_residues_kernel(const kg_orf *__restr
     }
 }
 
+// A repaired record (kg_repair.hpp) does not read in one frame, so orf_residues_kernel cannot rebuild its protein from the record.
+// A stage that makes a set from a given one never changes such a record (it is KG_ORF_INTERRUPTED: not movable), so record i keeps
+// its index and its length, and its protein is the given set's bytes.  A lane owns residues [kOrfResPerLane * q, + kOrfResPerLane)
+// of the new proteins, as there, and writes those of repaired records only.
+__global__ __launch_bounds__(256) void orf_keep_repaired_kernel(const kg_orf *__restrict__ orfs, uint64_t n,
+                                                                const int64_t *__restrict__ prot_start, uint64_t total,
+                                                                const int64_t *__restrict__ old_start, const uint8_t *__restrict__ old_res,
+                                                                uint8_t *__restrict__ res)
+{
+    const uint64_t first = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * kOrfResPerLane;
+    if (first >= total) return;
+    uint64_t i = orf_owner(prot_start, n, (int64_t)first);
+    int64_t begin = prot_start[i], end = prot_start[i + 1];
+    bool repaired = (orfs[i].flags & KG_ORF_REPAIRED) != 0;
+    for (int k = 0; k < kOrfResPerLane && first + k < total; k++) {
+        const int64_t pos = (int64_t)(first + k);
+        if (pos >= end) {
+            i = (i + 2 <= n && prot_start[i + 1] <= pos && pos < prot_start[i + 2]) ? i + 1 : orf_owner(prot_start, n, pos);
+            begin = prot_start[i];
+            end = prot_start[i + 1];
+            repaired = (orfs[i].flags & KG_ORF_REPAIRED) != 0;
+        }
+        if (repaired) res[pos] = old_res[old_start[i] + (pos - begin)];
+    }
+}
+
 }  // namespace kg

@@ -428,8 +428,9 @@ __global__ __launch_bounds__(256) void repair_junction_records_kernel(const kg_o
     const uint64_t sg = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (sg >= *n_segments) return;
     const uint32_t i = S.reg[sg], first = reg_first[i], last = reg_last[i];
+    // (not by KG_ORF_REPAIRED: a given record may carry the flag of an earlier call, and this call has left it alone)
+    if (sg >= last || junction_start[i + 1] == junction_start[i]) return;
     const kg_orf o = out[i];
-    if (sg >= last || !(o.flags & KG_ORF_REPAIRED)) return;
     const int64_t L = offsets[o.seq + 1] - offsets[o.seq], J = S.J[sg];
     kg_junction j;
     j.orf = (int32_t)i;
@@ -441,8 +442,9 @@ __global__ __launch_bounds__(256) void repair_junction_records_kernel(const kg_o
     junctions[junction_start[i] + (sg - first)] = j;
 }
 
-// A lane owns residues [kOrfResPerLane * q, + kOrfResPerLane) of the new proteins.  A repaired ORF's residue is translated from
-// its part's frame; every other one is the given set's byte.
+// A lane owns residues [kOrfResPerLane * q, + kOrfResPerLane) of the new proteins.  The residue of an ORF repaired in this call
+// (it has junctions: a chain that holds has at least one) is translated from its part's frame; every other one is the given
+// set's byte, also where the given record carries KG_ORF_REPAIRED from an earlier call.
 __global__ __launch_bounds__(256) void repair_residues_kernel(const kg_orf *__restrict__ orfs, uint64_t n,
                                                               const int64_t *__restrict__ prot_start, uint64_t total,
                                                               const int64_t *__restrict__ old_start, const uint8_t *__restrict__ old_res,
@@ -467,12 +469,12 @@ __global__ __launch_bounds__(256) void repair_residues_kernel(const kg_orf *__re
             o = orfs[i];
         }
         const int64_t q = pos - begin;                                  // residue of ORF i
+        const int64_t js = junction_start[i], je = junction_start[i + 1];
         uint32_t ch;
-        if (!(o.flags & KG_ORF_REPAIRED)) {
+        if (je == js) {                                                 // not repaired in this call, whatever its flags say
             ch = old_res[old_start[i] + q];
         } else {
             const int64_t off = offsets[o.seq], L = offsets[o.seq + 1] - off;
-            const int64_t js = junction_start[i], je = junction_start[i + 1];
             int64_t part = 0;
             for (int64_t t = js; t < je && t < js + kRepairMaxJunctions; t++) part += junctions[t].res <= q ? 1 : 0;
             int64_t x;                                                  // the codon's first strand position

@@ -22,7 +22,8 @@
 //                             record; starts_choose_kernel<true>: the smallest k among the candidates that equal the maximum, the
 //                             same way.
 //   5. starts_chosen_kernel   one lane per candidate: Suf and the type of every record's chosen k > 0;
-//      starts_apply_kernel    one lane per record: rule 9.  The proteins are then written by orf_residues_kernel from the new records.
+//      starts_apply_kernel    one lane per record: rule 9.  The proteins are then written by orf_residues_kernel from the new records,
+//      and orf_keep_repaired_kernel puts the given bytes back where a record is a repaired one: it does not read in one frame.
 // No lane walks a record: a 10^4-codon ORF is 10^4 lanes like any others, and its 10^4 candidates are 10^4 lanes of the rounds.
 // A histogram add whose active lanes all hold one bin is one add of the lane count by one lane (coding_hist_add).
 #pragma once
