@@ -1953,6 +1953,90 @@ int kg_evidence_call_hits_copy(const kg_evidence *e, int64_t first, int64_t coun
 int kg_evidence_stats(const kg_evidence *e, kg_translate_stats *out);
 void kg_evidence_free(kg_evidence *e);
 
+/* ---- signature and homology evidence in one run: the database fills what the table left unnamed (kernels: kg_residual.hpp) ----
+ *
+ * This rule is the project's own.  Integers only.  A caller with a signature table and a kg_searchdb has two sources of CALLs;
+ * this call takes the CALLs of the first, searches only the fragments they do not explain, and hands back one CALL list.
+ * Inputs: a batch of contigs (seq, offsets); a kg_searchdb; the signature CALLs of that batch in non-decreasing container order,
+ * either the CALLs of a DNA kg_result or a caller-held array in host or device memory; target_fn, host int32[n_db], required
+ * here (NULL is KG_ERR_ARG): the two kinds of CALL share one fI space, and only the caller can build that.
+ *   1. Fragments.  Exactly those of kg_contigs_search_translated: the records, prot_start and residues of kg_orfs_free with
+ *      { min_res, start_codons = 0 }.  For a fragment F, c(F) = 6 F.seq + 3 F.strand + F.frame, and b(F) as in that rule:
+ *      (x - F.frame) / 3 with x = F.left on '+' and x = L - 1 - F.right on '-'.  F covers codons b .. b + n_res - 1 of its
+ *      container.  Fragments are sorted by (c, b) and disjoint within a container.
+ *   2. Explained.  A signature CALL s touches F iff s.container == c(F), s.start <= b(F) + F.n_res - 1 and s.end >= b(F); a CALL's
+ *      start and end are residues of its frame, which are the same codon indices (rule 1 of the regions section).  explain[F] is
+ *      an int64: the sum of s.count over the CALLs that touch F.  F is explained iff explain[F] >= explain_min.  A CALL may touch
+ *      several fragments, because a CALL can span a stop; it explains each of them.  A CALL that touches no listed fragment
+ *      changes nothing (it may lie in a run shorter than min_res).
+ *   3. Searched fragments.  The fragments that are not explained, in fragment order.  Their kg_orf records, a new prot_start and
+ *      their residues are compacted on the device into an ordinary, lendable ORF set in the fragments' context (its statistics
+ *      hold orfs and residues alone).  Searched fragment q is query q; searched[q] is its index among all fragments.
+ *   4. Search.  The hit records, hit_start, paths (and ops, ungapped records and band statistics when asked for) are byte for
+ *      byte those of kg_searchdb_search_device on the searched fragments' proteins, with the same options; trace & 3 == 0 reads
+ *      as KG_TRACE_HITS.  With zero searched fragments the search is not launched: the hit set is a valid empty one (zero
+ *      queries, zero records, hit_start = {0}, statistics zero but for `targets`), and ms_search is 0.
+ *   5. Homology CALLs.  The CALLs of rule 3 of "genes by homology" over the searched fragments' records and these hits (a hit's
+ *      `query` indexes the compacted records).  A CALL whose count < min_db_count is then left out and counted.
+ *   6. Merged list.  By container; inside a container the signature CALLs come first in their given order, then the homology
+ *      CALLs in theirs.  Three arrays run parallel to it: call_kind[k], 0 for signature and 1 for homology; call_source[k], for a
+ *      signature CALL its index in the signature list, for a homology CALL its index in the homology list before the
+ *      min_db_count cut; call_hit[k], the hit record, or -1 for a signature CALL.  The list's containers are non-decreasing, as
+ *      kg_regions_calls requires.  Counts stay in their own units, k-mer hits for a signature CALL and alignment score for a
+ *      homology CALL, so the score of a region that holds both kinds is the plain sum of the two units: it ranks such a region
+ *      against others only roughly.  A common unit is out of scope.
+ *   7. Nothing depends on launch geometry or batch neighbours: explain[] is a sum of integers, and every compacted byte and
+ *      every merged CALL has one writer.
+ * Parameters kg_residual_params { explain_min (>= 1, default 1: any CALL explains, a scan's CALLs already have count >= minHits),
+ * min_db_count (>= 0, default 0), reserved == 0 }; anything else is KG_ERR_ARG.  Both defaults are this project's choice and are
+ * not tuned.
+ * The caller-held list (KG_ERR_ARG, the message names the first offender as "CALL N: ..."): a container below its
+ * predecessor's; a container >= 6 * n_seqs; a negative count; start > end; a record outside its contig.  A bad record is clamped
+ * before it indexes anything and marks nothing.  kg_result_search_residual reads the result's device CALLs where they lie and
+ * gives exactly the bytes of kg_contigs_search_residual on kg_result_calls(r); KG_ERR_ARG for a protein (-a) or
+ * KG_F_SKIP_AGGREGATE result, for a result on another device than the index, or of another number of sequences than n_seqs;
+ * KG_ERR_BUSY while a scan is in flight on its table.
+ * Limits, KG_ERR_NOMEM, KG_TEST_FAIL_ALLOC and "after any failure the handle's live bytes are what they were" are those of
+ * kg_contigs_search_translated; the room check counts the searched fragments' residues only, before they are copied.
+ * The kg_evidence: kg_evidence_calls_* and kg_evidence_calls_device give the merged list, kg_evidence_call_hits_copy the hit
+ * record or -1, kg_evidence_fragments all fragments, kg_evidence_hits the hit set of the searched ones.  kg_translate_stats keeps
+ * its meaning: fragments counts all of them, calls the homology CALLs before the min_db_count cut, ms_total excludes the new
+ * stages.  The getters below are KG_ERR_ARG (or NULL) on an evidence of kg_contigs_search_translated. */
+typedef struct kg_residual_params { int64_t explain_min; int32_t min_db_count; int32_t reserved; } kg_residual_params;
+typedef struct kg_residual_stats {   /* 80 B */
+    int64_t sig_calls;
+    int64_t explained;           /* fragments with explain >= explain_min                     */
+    int64_t explained_residues;
+    int64_t searched;            /* the others: the queries                                   */
+    int64_t searched_residues;
+    int64_t db_calls;            /* homology CALLs before the min_db_count cut                */
+    int64_t dropped_min_count;
+    int64_t merged;              /* sig_calls + db_calls - dropped_min_count                  */
+    float   ms_explain;          /* device time of keys, mark, choose and the two sums        */
+    float   ms_compact;          /* ... of the layout and the residues' copy                  */
+    float   ms_merge;            /* ... of keep, its sum and the merge                        */
+    float   ms_total;            /* kg_translate_stats.ms_total and the three together        */
+} kg_residual_stats;
+int kg_contigs_search_residual(kg_searchdb *db, const kg_search_params *p, const kg_align_params *align,
+                               const kg_translate_params *tp, const uint8_t *seq, int seq_on_device, const int64_t *offsets,
+                               int64_t n_seqs, int64_t max_windows, int64_t max_pairs, int trace, int64_t max_trace_cells,
+                               const kg_mask_params *query_mask, const kg_ungapped_params *ungapped, const kg_band_params *band,
+                               const int32_t *target_fn, const kg_call *sig_calls, int calls_on_device, int64_t n_sig_calls,
+                               const kg_residual_params *rp, kg_evidence **out);
+int kg_result_search_residual(kg_result *r, kg_searchdb *db, const kg_search_params *p, const kg_align_params *align,
+                              const kg_translate_params *tp, const uint8_t *seq, int seq_on_device, const int64_t *offsets,
+                              int64_t n_seqs, int64_t max_windows, int64_t max_pairs, int trace, int64_t max_trace_cells,
+                              const kg_mask_params *query_mask, const kg_ungapped_params *ungapped, const kg_band_params *band,
+                              const int32_t *target_fn, const kg_residual_params *rp, kg_evidence **out);
+const kg_orfset *kg_residual_searched_fragments(const kg_evidence *e);
+/* searched[first, first + count): every query's index among the fragments */
+int kg_residual_searched_copy(const kg_evidence *e, int64_t first, int64_t count, int64_t *dst);
+/* explain[first, first + count), one per fragment */
+int kg_residual_explain_copy(const kg_evidence *e, int64_t first, int64_t count, int64_t *dst);
+int kg_residual_call_kinds_copy(const kg_evidence *e, int64_t first, int64_t count, uint8_t *dst);
+int kg_residual_call_sources_copy(const kg_evidence *e, int64_t first, int64_t count, int64_t *dst);
+int kg_residual_stats_of(const kg_evidence *e, kg_residual_stats *out);
+
 /* the resident 24-byte records, valid until kg_table_close, and how many there are: num_sigs for a built or adopted table, the
  * whole records of the file for an opened one (fewer than num_sigs for a truncated file, more for a longer one) */
 const void *kg_table_device_entries(const kg_table *t);

@@ -555,6 +555,26 @@ public interface KmerGutsHip extends Library {
         }
     }
 
+    /** struct kg_residual_params (16 B, kg_contigs_search_residual): a fragment is explained when the counts of the signature
+     *  CALLs that touch it sum to explain_min or more (default 1); homology CALLs below min_db_count are left out (default 0). */
+    class KgResidualParams extends Structure {
+        public long explain_min;
+        public int min_db_count, reserved;
+        public KgResidualParams() {
+            setFieldOrder(new String[] {"explain_min", "min_db_count", "reserved"});
+        }
+    }
+
+    /** struct kg_residual_stats (80 B, kg_residual_stats_of): the counts of the new stages and their device times. */
+    class KgResidualStats extends Structure {
+        public long sig_calls, explained, explained_residues, searched, searched_residues, db_calls, dropped_min_count, merged;
+        public float ms_explain, ms_compact, ms_merge, ms_total;
+        public KgResidualStats() {
+            setFieldOrder(new String[] {"sig_calls", "explained", "explained_residues", "searched", "searched_residues", "db_calls",
+                    "dropped_min_count", "merged", "ms_explain", "ms_compact", "ms_merge", "ms_total"});
+        }
+    }
+
     /** struct kg_translate_stats (72 B, kg_evidence_stats): the counts of a translated search and its device times by stage. */
     class KgTranslateStats extends Structure {
         public long fragments, fragment_residues, records, calls, dropped_status, dropped_rank, dropped_untraced;
@@ -769,6 +789,24 @@ public interface KmerGutsHip extends Library {
     int kg_evidence_call_hits_copy(Pointer evidence, long first, long count, long[] dst);
     int kg_evidence_stats(Pointer evidence, KgTranslateStats out);
     void kg_evidence_free(Pointer evidence);
+    /** signature and homology evidence in one run: the fragments the signature CALLs (sigCalls: host or device kg_call records in
+     *  container order) do not explain are searched, and the two kinds of CALL are merged by container; targetFn is required */
+    int kg_contigs_search_residual(Pointer db, KgSearchParams params, KgAlignParams align, KgTranslateParams translate, Pointer seq,
+                                   int seqOnDevice, long[] offsets, long nSeqs, long maxWindows, long maxPairs, int trace,
+                                   long maxTraceCells, KgMaskParams queryMask, KgUngappedParams ungapped, KgBandParams band,
+                                   int[] targetFn, Pointer sigCalls, int callsOnDevice, long nSigCalls, KgResidualParams residual,
+                                   PointerByReference out);
+    /** the same with the CALLs of a DNA scan's result, read where they lie on the device */
+    int kg_result_search_residual(Pointer result, Pointer db, KgSearchParams params, KgAlignParams align, KgTranslateParams translate,
+                                  Pointer seq, int seqOnDevice, long[] offsets, long nSeqs, long maxWindows, long maxPairs, int trace,
+                                  long maxTraceCells, KgMaskParams queryMask, KgUngappedParams ungapped, KgBandParams band,
+                                  int[] targetFn, KgResidualParams residual, PointerByReference out);
+    Pointer kg_residual_searched_fragments(Pointer evidence);
+    int kg_residual_searched_copy(Pointer evidence, long first, long count, long[] dst);
+    int kg_residual_explain_copy(Pointer evidence, long first, long count, long[] dst);
+    int kg_residual_call_kinds_copy(Pointer evidence, long first, long count, byte[] dst);
+    int kg_residual_call_sources_copy(Pointer evidence, long first, long count, long[] dst);
+    int kg_residual_stats_of(Pointer evidence, KgResidualStats out);
     /** kg_proteins_cluster_aligned (align = null: no alignment step) with every protein soft-masked for the 8-mer pass */
     int kg_proteins_cluster_masked(int device, KgClusterParams params, KgAlignParams align, byte[] seq, long[] offsets, long nProt,
                                    long maxWindows, KgMaskParams mask, PointerByReference out);

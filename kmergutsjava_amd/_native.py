@@ -61,6 +61,8 @@ EXPORTS = (
     "kg_searchdb_search", "kg_searchdb_search_device", "kg_hitset_db_stats",
     "kg_contigs_search_translated", "kg_evidence_fragments", "kg_evidence_hits", "kg_evidence_calls_count", "kg_evidence_calls_copy",
     "kg_evidence_calls_device", "kg_evidence_call_hits_copy", "kg_evidence_stats", "kg_evidence_free",
+    "kg_contigs_search_residual", "kg_result_search_residual", "kg_residual_searched_fragments", "kg_residual_searched_copy",
+    "kg_residual_explain_copy", "kg_residual_call_kinds_copy", "kg_residual_call_sources_copy", "kg_residual_stats_of",
     "kg_result_regions", "kg_regions_calls", "kg_regionset_count", "kg_regionset_device", "kg_regionset_copy",
     "kg_regionset_seq_start", "kg_regionset_stats", "kg_regionset_free",
     "kg_regionset_orfs", "kg_orfs_regions", "kg_orfset_count", "kg_orfset_device", "kg_orfset_copy", "kg_orfset_prot_start",
@@ -525,6 +527,24 @@ class KgTranslateStats(C.Structure):
 TRANSLATE_MIN_RES, TRANSLATE_MAX_HITS = 30, 1       # the defaults of kg_translate_params
 
 
+class KgResidualParams(C.Structure):
+    """struct kg_residual_params (kg_contigs_search_residual / kg_result_search_residual)."""
+    _fields_ = [("explain_min", C.c_int64), ("min_db_count", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgResidualStats(C.Structure):
+    """struct kg_residual_stats (kg_residual_stats_of)."""
+    _fields_ = [("sig_calls", C.c_int64), ("explained", C.c_int64), ("explained_residues", C.c_int64), ("searched", C.c_int64),
+                ("searched_residues", C.c_int64), ("db_calls", C.c_int64), ("dropped_min_count", C.c_int64), ("merged", C.c_int64),
+                ("ms_explain", C.c_float), ("ms_compact", C.c_float), ("ms_merge", C.c_float), ("ms_total", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+RESIDUAL_CHUNK = 16         # kg_residual.hpp kResidualChunk: the destination bytes of one lane of the residues' copy (tests aim at its edges)
+
+
 # struct kg_search_ungapped (kg_hitset_ungapped_copy): one per hit record of a filtered search, same index
 SEARCH_UNGAPPED_DTYPE = np.dtype([("ungapped", "<i4"), ("diagonal", "<i4"), ("on_diagonal", "<i4"), ("reserved", "<i4")])
 assert SEARCH_UNGAPPED_DTYPE.itemsize == 16
@@ -734,10 +754,14 @@ def load() -> C.CDLL:
     lib.kg_contigs_search_translated.argtypes = [vp, C.POINTER(KgSearchParams), C.POINTER(KgAlignParams), C.POINTER(KgTranslateParams), vp,
                                                   C.c_int, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(KgMaskParams),
                                                   C.POINTER(KgUngappedParams), C.POINTER(KgBandParams), vp, C.POINTER(vp)]
-    for name in ("kg_evidence_fragments", "kg_evidence_hits", "kg_evidence_calls_device"):
+    for name in ("kg_evidence_fragments", "kg_evidence_hits", "kg_evidence_calls_device", "kg_residual_searched_fragments"):
         getattr(lib, name).argtypes = [vp]
         getattr(lib, name).restype = vp
     lib.kg_evidence_stats.argtypes = [vp, C.POINTER(KgTranslateStats)]
+    translated = list(lib.kg_contigs_search_translated.argtypes)
+    lib.kg_contigs_search_residual.argtypes = translated[:-1] + [vp, C.c_int, C.c_int64, C.POINTER(KgResidualParams), C.POINTER(vp)]
+    lib.kg_result_search_residual.argtypes = [vp] + translated[:-1] + [C.POINTER(KgResidualParams), C.POINTER(vp)]
+    lib.kg_residual_stats_of.argtypes = [vp, C.POINTER(KgResidualStats)]
     for name in ("kg_proteins_cluster_masked", "kg_proteins_cluster_masked_device"):
         getattr(lib, name).argtypes = [C.c_int, C.POINTER(KgClusterParams), C.POINTER(KgAlignParams), vp, vp, C.c_int64, C.c_int64,
                                        C.POINTER(KgMaskParams), C.POINTER(vp)]
@@ -754,7 +778,8 @@ def load() -> C.CDLL:
                  "kg_orfset_junctions_copy", "kg_orfset_coding_scores", "kg_orfset_start_shifts", "kg_selectset_copy",
                  "kg_voteset_copy_votes", "kg_voteset_copy_classes", "kg_voteset_copy_bins", "kg_compset_copy_classes",
                  "kg_compset_copy_counts", "kg_compset_model_labels", "kg_compset_copy_scores", "kg_evidence_calls_copy",
-                 "kg_evidence_call_hits_copy"):
+                 "kg_evidence_call_hits_copy", "kg_residual_searched_copy", "kg_residual_explain_copy", "kg_residual_call_kinds_copy",
+                 "kg_residual_call_sources_copy"):
         getattr(lib, name).argtypes = [vp, C.c_int64, C.c_int64, vp]
     for name in ("kg_regionset_seq_start", "kg_orfset_prot_start", "kg_orfset_junctions_start", "kg_voteset_seq_start",
                  "kg_compset_background", "kg_hitset_starts_copy", "kg_maskset_starts_copy"):

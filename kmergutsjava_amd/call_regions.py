@@ -112,6 +112,18 @@ with left and right the aligned stretch in nucleotides, the fragment named conti
 those of search_proteins -o.  Every other flag works as with -D: a gene whose halves hit one target in two frames is a
 multi-frame region, and --repair joins it.  The summary line gains `, db: index (N targets), fragments: F, translated hits: H,
 calls: C` (H: the records with status hit).  Without --db every byte of every output is as before.
+
+-D KmerData --fill-db DB.kgsdb uses both sources in one run (include/kmerguts_hip.h, "signature and homology evidence in one run"):
+every batch is scanned against the table (-m/-M/-g/-O), a stop-to-stop fragment that a table CALL touches is explained (the
+touching CALLs' hits sum to --explain-min or more, default 1), only the other fragments are searched against the index (the --db
+flags above, --min-frag, --max-hits, --batch-nt and --hits among them), homology CALLs of a score below --fill-min-score (default
+0) are left out, and the regions are those of the two kinds of CALL merged.  function.index keeps its indices; a database function
+whose name equals a table name takes the table's first index for it, the others are appended by first appearance, and a target
+without a function is named by its id.  A region's score is the plain sum of its CALLs' counts, k-mer hits for a table CALL and
+alignment score for a homology CALL: the two units are not brought to a common one.  Every regions line gains a last field,
+`table`, `db` or `table+db` (GFF: the attribute evidence=), in front of what --select adds; --hits writes the homology CALLs; the
+summary line gains `, fill: index (N targets), fragments: F, explained: E, searched: S, translated hits: H, db calls: C`.  A
+batch holds at most the smaller of the scan's and the index's limit.  Without --fill-db every byte of every output is as before.
 """
 from __future__ import annotations
 
@@ -167,9 +179,10 @@ def _winner(sel, i: int, cands) -> bytes:
     return b"%d..%d:%s" % (w["left"] + 1, w["right"] + 1, b"-" if w["strand"] else b"+")
 
 
-def format_regions(ids, regs, fnames, write_all: bool = False, gff: bool = False, sel=None, cands=None) -> bytes:
+def format_regions(ids, regs, fnames, write_all: bool = False, gff: bool = False, sel=None, cands=None, evidence=None) -> bytes:
     """Region records (REGION_DTYPE, `seq` indexing ids) as text, in the order given.  sel: the selection records of --select,
-    index-aligned with regs; cands: the records the selection ran on (the ORFs, default the regions)."""
+    index-aligned with regs; cands: the records the selection ran on (the ORFs, default the regions); evidence (--fill-db): per
+    region b"table", b"db" or b"table+db", a last field in front of what the selection adds (GFF: the attribute evidence=)."""
     lines = [b"##gff-version 3\n"] if gff else []
     cands = regs if cands is None else cands
     for i, r in enumerate(regs):
@@ -178,6 +191,8 @@ def format_regions(ids, regs, fnames, write_all: bool = False, gff: bool = False
         status = b"kept" if r["kept"] else b"below"
         if sel is not None and sel["state"][i] == 2:
             status = b"overlapped"
+        if evidence is not None:
+            status += (b";evidence=" if gff else b"\t") + evidence[i]
         if sel is not None and write_all:
             status += (b";overlapped_by=" if gff else b"\t") + _winner(sel, i, cands)
         strand = b"-" if r["strand"] else b"+"
@@ -423,14 +438,54 @@ def function_names(dids, functions):
     return fnames, target_fn
 
 
+def fill_function_names(table_fnames, dids, functions):
+    """What --fill-db names its regions by: function.index keeps its indices; a database function whose name equals a table name
+    takes the table's first index for it, the others are appended by first appearance (as merge_tables does), and a target
+    without a function is named by its id.  -> (fnames, target_fn)."""
+    fnames = list(table_fnames)
+    index_of = {}
+    for f, name in enumerate(fnames):
+        index_of.setdefault(name, f)
+    target_fn = np.zeros(len(dids), dtype=np.int32)
+    for d, did in enumerate(dids):
+        name = functions[did][0] if functions is not None and did in functions else did
+        if name not in index_of:
+            index_of[name] = len(fnames)
+            fnames.append(name)
+        target_fn[d] = index_of[name]
+    return fnames, target_fn
+
+
+def region_evidence(regs, calls, call_kind, off):
+    """The `evidence` field of a batch's regions (REGION_DTYPE, seq within the batch) from the merged CALLs and their kinds: a CALL
+    belongs to the region of its (seq, strand, fI) group that contains its x0.  -> a list of b"table", b"db" or b"table+db"."""
+    groups = {}
+    for i, r in enumerate(regs):
+        groups.setdefault((int(r["seq"]), int(r["strand"]), int(r["fI"])), []).append((int(r["left"]), int(r["right"]), i))
+    seen = [0] * len(regs)
+    for c, kind in zip(calls, call_kind):
+        cont = int(c["container"])
+        s, strand, frame = cont // 6, cont % 6 // 3, cont % 3
+        x0 = frame + 3 * int(c["start"])
+        pos = x0 if strand == 0 else int(off[s + 1] - off[s]) - 1 - x0
+        for left, right, i in groups.get((s, strand, int(c["fI"])), ()):
+            if left <= pos <= right:
+                seen[i] |= 2 if kind else 1
+                break
+    return [(b"table", b"table", b"db", b"table+db")[k] for k in seen]
+
+
 def format_call_hits(ids, dids, ev, off, align_ref: str = "longer", functions=None) -> bytes:
     """--hits: one line per CALL of an evidence (hotpath.Evidence; ids: the batch's contig ids; off: its offsets): the contig, the
     aligned stretch left+1 and right+1 in nucleotides, strand and frame, then the fields of search_proteins -o for the hit record,
-    the fragment named contig_left+1_right+1_strand as --faa names a protein."""
+    the fragment named contig_left+1_right+1_strand as --faa names a protein.  Of a merged list (--fill-db) the homology CALLs are
+    written, whose hit records name the searched fragments."""
     from .search_proteins import STATUS, _ref
-    hits, frags = ev.search[0], ev.fragments[0]
+    hits, frags = ev.search[0], getattr(ev, "searched_fragments", ev.fragments)[0]
     out = []
     for c, r in zip(ev.calls, ev.call_hits):
+        if int(r) < 0:
+            continue
         h = hits[int(r)]
         fr = frags[int(h["query"])]
         s, strand, frame = int(c["container"]) // 6, int(c["container"]) % 6 // 3, int(c["container"]) % 3
@@ -457,18 +512,33 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
                  coding_model_in: str = None, save_coding_model: str = None, starts: bool = False, start_rounds: int = 4,
                  min_train_starts: int = 200, start_model_in: str = None, save_start_model: str = None, repair: bool = False,
                  repair_min_count: int = 0, max_junctions: int = 4, shifts_out: str = None, db: str = None, min_frag: int = 30,
-                 max_hits: int = 1, batch_nt: int = None, hits_out: str = None, search: dict = None, open_db=None) -> str:
+                 max_hits: int = 1, batch_nt: int = None, hits_out: str = None, search: dict = None, open_db=None, fill_db: str = None,
+                 explain_min: int = 1, fill_min_score: int = 0, open_table=None) -> str:
     """Write the regions (and, with orfs_out / faa_out, their open reading frames and proteins; with free_min_res also the
     evidence-free ORFs of at least that many residues; with coding the ORFs' coding scores, the non-coding free ORFs dropped;
     with starts the start codons chosen by the start-site score; with repair the multi-frame regions' ORFs joined across their
     frames first, and their junctions written to shifts_out); returns the summary line.
     db: in place of data_dir, the index file of make_search_db: the CALLs are translated search hits (SearchDb.search_contigs with
     min_frag, max_hits and the keywords of `search`), batches hold at most batch_nt nucleotides and hits_out gets one line per
-    CALL.  open_db replaces hotpath.SearchDb.open (tests)."""
+    CALL.  open_db replaces hotpath.SearchDb.open (tests).
+    fill_db: beside data_dir, the index file whose targets fill what the table left unnamed: every batch is scanned, the fragments
+    its CALLs do not explain (explain_min) are searched (SearchDb.search_contigs with explained_by), homology CALLs of a score
+    below fill_min_score are left out, and the regions are those of the merged CALLs, each with an `evidence` field.
+    open_table(path, device) replaces the resident table (tests)."""
+    if fill_db is not None and db is not None:
+        raise ValueError("--fill-db beside --db: --db searches every fragment, --fill-db only what the table of -D left unnamed")
+    if fill_db is not None and data_dir is None:
+        raise ValueError("--fill-db needs -D: it fills the unnamed stretches of a table scan")
     if (data_dir is None) == (db is None):
         raise ValueError("exactly one of -D and --db must be given")
-    if db is None and hits_out is not None:
+    if db is None and fill_db is None and hits_out is not None:
         raise ValueError("--hits needs --db")
+    if fill_db is None and (explain_min != 1 or fill_min_score != 0):
+        raise ValueError("--explain-min and --fill-min-score need --fill-db")
+    if explain_min < 1:
+        raise ValueError("--explain-min must be >= 1")
+    if fill_min_score < 0:
+        raise ValueError("--fill-min-score must be >= 0")
     want_orfs = orfs_out is not None or faa_out is not None
     if free_min_res is not None and not want_orfs:
         raise ValueError("--free-orfs needs --orfs or --faa: free ORFs are written to those files only")
@@ -494,17 +564,54 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         if table_path is None or fn_path is None:
             raise FileNotFoundError("%s holds no kmer.table.mem_map[.gz] or function.index[.gz]" % data_dir)
         fnames = parse_index(_read(fn_path), fn_path)
-        tab = _resident_table(table_path, device)
+        tab = (open_table or _resident_table)(table_path, device)
         params = hotpath.Params(aa=False, order_constraint=order_constraint, min_hits=min_hits, min_weighted_hits=min_weighted_hits,
                                 max_gap=max_gap)
         batch_limit = KmerGutsJava.MAX_BATCH_CHARS
 
         def scan(batch, off, k):
             return tab.scan(batch, off, params)
+        if fill_db is not None:
+            index = (open_db or hotpath.SearchDb.open)(fill_db, device=device)
     else:
         index = (open_db or hotpath.SearchDb.open)(db, device=device)
+    note = None
     try:
-        if index is not None:
+        if fill_db is not None:
+            from .make_search_db import unpack_names
+            info = index.info()
+            dids, functions = unpack_names(index.names(), int(info["targets"]))
+            fnames, target_fn = fill_function_names(fnames, dids, functions)
+            room = [int(info["query_room"])]
+            batch_limit = min(batch_limit, max(room[0] // 2, 1) if batch_nt is None else int(batch_nt))
+            skw = dict(search or {})
+            if skw.get("align", {}).get("ref") == "query":
+                skw["align"] = dict(skw["align"], ref="member")
+            ev_sum = dict(fragments=0, explained=0, searched=0, hits=0, calls=0)
+            hit_lines = []
+            scan_table = scan
+
+            def scan(batch, off, k):        # noqa: F811
+                # a fill batch reserves the unfiltered bound, 2 * nucleotides, as the --db path does
+                if 2 * len(batch) > room[0]:
+                    index.reserve(2 * len(batch))
+                    room[0] = 2 * len(batch)
+                with scan_table(batch, off, k) as r:
+                    ev = index.search_contigs(batch, off, min_res=min_frag, max_hits=max_hits, target_fn=target_fn, explained_by=r,
+                                              explain_min=explain_min, min_db_count=fill_min_score, **skw)
+                rs = ev.residual_stats
+                ev_sum["fragments"] += ev.stats["fragments"]
+                ev_sum["explained"] += rs["explained"]
+                ev_sum["searched"] += rs["searched"]
+                ev_sum["hits"] += ev.search[3]["hits"]
+                ev_sum["calls"] += rs["db_calls"] - rs["dropped_min_count"]
+                if hits_out is not None:
+                    hit_lines.append(format_call_hits(ids[k:], dids, ev, off, skw.get("align", {}).get("ref", "longer"), functions))
+                return ev
+
+            def note(ev, regs, off):
+                return region_evidence(regs, ev.calls, ev.call_kind, off)
+        elif index is not None:
             from .make_search_db import unpack_names
             info = index.info()
             dids, functions = unpack_names(index.names(), int(info["targets"]))
@@ -532,11 +639,14 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
         line = _call_regions(ids, seqs, scan, batch_limit, fnames, out, merge_gap, min_score, min_len, write_all, gff, orfs_out, faa_out,
                              start_codons, select, max_overlap, max_overlap_pct, free_min_res, coding, min_coding, min_train,
                              coding_model_in, save_coding_model, starts, start_rounds, min_train_starts, start_model_in,
-                             save_start_model, repair, repair_min_count, max_junctions, shifts_out)
-        if index is not None:
-            if hits_out is not None:
-                with open(hits_out, "wb") as f:
-                    f.write(b"".join(hit_lines))
+                             save_start_model, repair, repair_min_count, max_junctions, shifts_out, note)
+        if index is not None and hits_out is not None:
+            with open(hits_out, "wb") as f:
+                f.write(b"".join(hit_lines))
+        if fill_db is not None:
+            line += ", fill: index (%d targets), fragments: %d, explained: %d, searched: %d, translated hits: %d, db calls: %d" % (
+                int(info["targets"]), ev_sum["fragments"], ev_sum["explained"], ev_sum["searched"], ev_sum["hits"], ev_sum["calls"])
+        elif index is not None:
             line += ", db: index (%d targets), fragments: %d, translated hits: %d, calls: %d" % (
                 int(info["targets"]), ev_sum["fragments"], ev_sum["hits"], ev_sum["calls"])
         return line
@@ -548,9 +658,10 @@ def call_regions(data_dir: str, contigs: str, out: str, min_hits: int = 5, min_w
 def _call_regions(ids, seqs, scan, batch_limit, fnames, out, merge_gap, min_score, min_len, write_all, gff, orfs_out, faa_out, start_codons,
                   select, max_overlap, max_overlap_pct, free_min_res, coding, min_coding, min_train, coding_model_in, save_coding_model,
                   starts, start_rounds, min_train_starts, start_model_in, save_start_model, repair, repair_min_count, max_junctions,
-                  shifts_out) -> str:
+                  shifts_out, note=None) -> str:
     """call_regions behind its source of CALLs: scan(batch, off) gives what holds a batch's CALLs (a ScanResult or an Evidence:
-    regions(), orfs() and select() with the same arguments; k: the batch's first contig), batch_limit the characters a batch holds at most."""
+    regions(), orfs() and select() with the same arguments; k: the batch's first contig), batch_limit the characters a batch holds at most.
+    note(r, regs, off): the `evidence` field of a batch's regions (--fill-db), or None."""
     from . import hotpath
     want_orfs = orfs_out is not None or faa_out is not None
     coding_arg = None                   # what ScanResult.orfs / select take: None, True (own training) or a score table
@@ -575,6 +686,7 @@ def _call_regions(ids, seqs, scan, batch_limit, fnames, out, merge_gap, min_scor
     parts, rstarts = [], [np.zeros(1, dtype=np.int64)]
     oparts, lens, residues, sparts = [], [], [], []
     fparts, flens, fresidues, fsparts = [], [], [], []          # the free ORFs, and per batch (selection, first free record)
+    notes = []
     k = n_before = n_free = 0
     while k < len(ids):
         j, size = k, 0
@@ -637,6 +749,8 @@ def _call_regions(ids, seqs, scan, batch_limit, fnames, out, merge_gap, min_scor
                               file=sys.stderr)
             else:
                 regs, start = r.regions(off, merge_gap, min_score, min_len)
+            if note is not None:
+                notes += note(r, regs, off)
         regs["seq"] += k
         n_before += len(regs)
         parts.append(regs)
@@ -658,7 +772,7 @@ def _call_regions(ids, seqs, scan, batch_limit, fnames, out, merge_gap, min_scor
                 by = part["by"]
                 by[by <= -2] = len(orfs) + (-2 - by[by <= -2])
     with open(out, "wb") as f:
-        f.write(format_regions(ids, regs, fnames, write_all, gff, sel, cands))
+        f.write(format_regions(ids, regs, fnames, write_all, gff, sel, cands, notes if note is not None else None))
     line = summary_of(regs, np.concatenate(rstarts))
     if want_orfs:
         pstart = np.zeros(len(orfs) + 1, dtype=np.int64)
@@ -755,6 +869,14 @@ def main(argv=None) -> int:
                     help="evidence ORFs a batch needs to train the start model (default 200, this project's choice); below: untrained, nothing moved")
     ap.add_argument("--start-model", metavar="IN", help="choose with the counts of this file (--save-start-model of a relative) instead of training")
     ap.add_argument("--save-start-model", metavar="OUT", help="write the start model's counts of the last round, summed over the batches")
+    ap.add_argument("--fill-db", default=None, metavar="DB.kgsdb",
+                    help="beside -D: the index file make_search_db wrote; the fragments the table's CALLs do not explain are searched against "
+                         "it and both kinds of CALL make the regions (the --db flags below govern the search)")
+    ap.add_argument("--explain-min", type=int, default=None, metavar="N",
+                    help="with --fill-db: a fragment is explained when the hits of the table CALLs that touch it sum to N or more "
+                         "(default 1, this project's choice, not tuned)")
+    ap.add_argument("--fill-min-score", type=int, default=None, metavar="N",
+                    help="with --fill-db: a homology CALL with an alignment score below N is left out (default 0)")
     ap.add_argument("--min-frag", type=int, default=None, metavar="N",
                     help="with --db: residues a stop-to-stop fragment has at least to be searched (default 30, this project's choice, not tuned)")
     ap.add_argument("--max-hits", type=int, default=None, metavar="N",
@@ -779,19 +901,29 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.D is not None and a.db is not None:
         ap.error("give -D or --db, not both")
+    if a.fill_db is not None and a.db is not None:
+        ap.error("--fill-db beside --db: --db searches every fragment, --fill-db only what the table of -D left unnamed")
+    if a.fill_db is not None and a.D is None:
+        ap.error("--fill-db needs -D")
     if a.D is None and a.db is None:
         ap.error("one of -D and --db is required")
+    if a.fill_db is None and (a.explain_min is not None or a.fill_min_score is not None):
+        ap.error("--explain-min and --fill-min-score need --fill-db")
+    if a.explain_min is not None and a.explain_min < 1:
+        ap.error("--explain-min must be >= 1")
+    if a.fill_min_score is not None and a.fill_min_score < 0:
+        ap.error("--fill-min-score must be >= 0")
     search_flags = (("--min-frag", a.min_frag), ("--max-hits", a.max_hits), ("--batch-nt", a.batch_nt), ("--hits", a.hits),
                     ("--min-shared", a.min_shared), ("--max-cand", a.max_cand), ("--max-db-per-kmer", a.max_db_per_kmer),
                     ("--min-ratio", a.min_ratio), ("--align-ref", a.align_ref), ("--gap-open", a.gap_open), ("--gap-extend", a.gap_extend),
                     ("--max-cells", a.max_cells), ("--ungapped", a.ungapped or None), ("--min-ungapped", a.min_ungapped), ("--band", a.band))
-    if a.db is None:
+    if a.db is None and a.fill_db is None:
         for flag, given in search_flags:
             if given is not None:
                 ap.error("%s needs --db" % flag)
     else:
         for flag, given in (("-m", a.m), ("-M", a.M), ("-g", a.g), ("-O", a.O or None)):
-            if given is not None:
+            if given is not None and a.db is not None:
                 ap.error("%s beside --db: it belongs to the table scan of -D" % flag)
         if a.min_frag is not None and a.min_frag < 1:
             ap.error("--min-frag must be >= 1")
@@ -825,7 +957,7 @@ def main(argv=None) -> int:
     try:
         dflt = lambda v, d: d if v is None else v      # noqa: E731
         search = None
-        if a.db is not None:
+        if a.db is not None or a.fill_db is not None:
             search = dict(min_shared=dflt(a.min_shared, 2), max_cand=dflt(a.max_cand, 8), max_db_per_kmer=dflt(a.max_db_per_kmer, 256),
                           align=dict(min_ratio_pct=dflt(a.min_ratio, 50), ref=dflt(a.align_ref, "query"), gap_open=dflt(a.gap_open, 11),
                                      gap_extend=dflt(a.gap_extend, 1), max_cells=dflt(a.max_cells, 1 << 26)))
@@ -841,7 +973,8 @@ def main(argv=None) -> int:
                             starts=a.starts, start_rounds=a.start_rounds, min_train_starts=a.min_train_starts,
                             start_model_in=a.start_model, save_start_model=a.save_start_model, repair=a.repair,
                             repair_min_count=a.repair_min_count, max_junctions=a.max_junctions, shifts_out=a.shifts, db=a.db,
-                            min_frag=dflt(a.min_frag, 30), max_hits=dflt(a.max_hits, 1), batch_nt=a.batch_nt, hits_out=a.hits, search=search)
+                            min_frag=dflt(a.min_frag, 30), max_hits=dflt(a.max_hits, 1), batch_nt=a.batch_nt, hits_out=a.hits, search=search,
+                            fill_db=a.fill_db, explain_min=dflt(a.explain_min, 1), fill_min_score=dflt(a.fill_min_score, 0))
     except (N.KmerGutsNativeError, InputError, OSError, ValueError) as e:
         print("Error: %s" % e, file=sys.stderr)
         return 1

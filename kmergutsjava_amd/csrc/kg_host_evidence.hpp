@@ -4,7 +4,8 @@
 // set in a context of its own; searchdb_search_entry (kg_host_searchdb.hpp) takes that set's residues where they lie on the
 // device, with prot_start brought to the host for its offsets; evidence_calls flags, sums and emits over the hit records.
 // The kg_evidence a call hands out owns the ORF set and the hit set and lends them; its own two arrays, the CALLs and call_hit,
-// are blocks of the ORF set's context, so they are given back before that set is freed.
+// are blocks of the ORF set's context, so they are given back before that set is freed.  kg_contigs_search_residual
+// (kg_host_residual.hpp) hands out the same kg_evidence with a second ORF set, the searched fragments, between the two.
 // Part of kmerguts_hip.hip's translation unit: a batch stage behind kg_host_searchdb.hpp and kg_host_orfs.hpp.
 #pragma once
 
@@ -15,6 +16,15 @@ struct kg_evidence : SetBase {
     int64_t *d_call_hit = nullptr;      // n_calls
     int64_t n_calls = 0;
     kg_translate_stats st = {};
+    // kg_contigs_search_residual (kg_host_residual.hpp): the hits are those of `searched`, the CALLs the merged list
+    bool residual = false;
+    kg_orfset *searched = nullptr;      // owned: the fragments that were searched, an ORF set in the fragments' context
+    int64_t *d_searched = nullptr;      // searched->count: every query's index among the fragments
+    int64_t *d_explain = nullptr;       // frags->count
+    uint8_t *d_call_kind = nullptr;     // n_calls
+    int64_t *d_call_source = nullptr;   // n_calls
+    kg_call *d_sig = nullptr;           // the call's own device copy of a host list of signature CALLs, until the merge
+    kg_residual_stats rst = {};
 };
 
 static_assert(sizeof(kg_translate_params) == 16 && sizeof(kg_translate_stats) == 72, "record layouts of include/kmerguts_hip.h");
@@ -26,10 +36,11 @@ namespace {
 void evidence_delete(kg_evidence *e)
 {
     if (!e) return;
-    kg_orfset *frags = e->frags;
+    kg_orfset *frags = e->frags, *searched = e->searched;
     kg_hitset *hits = e->hits;
     delete e;
     kg_hitset_free(hits);
+    kg_orfset_free(searched);
     kg_orfset_free(frags);
 }
 
@@ -56,14 +67,15 @@ int check_translate_params(const kg_translate_params *p)
 }
 
 // The CALLs of e->hits over e->frags, in the ORF set's context t (held by the caller): flag, the shared prefix sum, emit.
-// offsets: the contigs', host, checked; target_fn: host int32[n_db] or null, checked.
+// offsets: the contigs', host, checked; target_fn: host int32[n_db] or null, checked.  queries: the ORF set whose proteins were
+// searched, e->frags or a subset of it in the same context (kg_host_residual.hpp); the statistics count e->frags either way.
 int evidence_calls(kg_table *t, kg_evidence *e, const kg_translate_params *prm, const int64_t *offsets, uint64_t n_seqs,
-                   const int32_t *target_fn, uint64_t n_db)
+                   const int32_t *target_fn, uint64_t n_db, const kg_orfset *queries)
 {
     Scratch sc(t);
     hipStream_t s = t->stream;
     const kg_hitset *hs = e->hits;
-    const uint64_t n = (uint64_t)hs->count, n_frags = (uint64_t)e->frags->count;
+    const uint64_t n = (uint64_t)hs->count, n_frags = (uint64_t)queries->count;
     int rc;
     if (n >= (1ull << 32)) return fail(KG_ERR_LIMIT, "2^32 or more hit records in one call");
     if (n && (!hs->has_paths || n_frags == 0 || n_seqs == 0 || n_db == 0))
@@ -100,14 +112,14 @@ int evidence_calls(kg_table *t, kg_evidence *e, const kg_translate_params *prm, 
     int64_t *d_call_hit = nullptr;
     if ((rc = sc.get(&d_calls, std::max<uint64_t>(n_calls, 1))) || (rc = sc.get(&d_call_hit, std::max<uint64_t>(n_calls, 1)))) return rc;
     if (n_calls) {
-        hipLaunchKernelGGL(kg::evidence_emit_kernel, dim3(grid_of(n)), dim3(256), 0, s, d_hits, d_paths, n, keep, pos, e->frags->d_orfs,
+        hipLaunchKernelGGL(kg::evidence_emit_kernel, dim3(grid_of(n)), dim3(256), 0, s, d_hits, d_paths, n, keep, pos, queries->d_orfs,
                            (uint32_t)n_frags, d_off, (uint32_t)n_seqs, d_fn, (uint32_t)n_db, d_calls, d_call_hit);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(t->ev[kEvStageEnd], s));
     HIP_TRY(hipStreamSynchronize(s));
     kg_translate_stats &st = e->st;
-    st.fragments = (int64_t)n_frags;
+    st.fragments = e->frags->count;
     st.fragment_residues = e->frags->residues;
     st.records = (int64_t)n;
     st.calls = (int64_t)n_calls;
@@ -163,7 +175,7 @@ int kg_contigs_search_translated(kg_searchdb *db, const kg_search_params *p, con
     {
         CallScope cs(frags->tab, "a call is in flight on the fragments' context");
         if (cs.rc) return cs.rc;
-        if ((rc = evidence_calls(cs.t, g.e, tp, offsets, (uint64_t)n_seqs, target_fn, (uint64_t)db->n_db))) return rc;
+        if ((rc = evidence_calls(cs.t, g.e, tp, offsets, (uint64_t)n_seqs, target_fn, (uint64_t)db->n_db, frags))) return rc;
         cs.t->cache.release_free();                     // the stage's scratch goes back to the driver, the two arrays stay
     }
     if (getenv("KG_DEBUG"))

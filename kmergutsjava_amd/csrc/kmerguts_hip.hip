@@ -34,6 +34,7 @@
 #include "kg_votes.hpp"
 #include "kg_compose.hpp"
 #include "kg_evidence.hpp"
+#include "kg_residual.hpp"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -71,3 +72,4 @@
 #include "kg_host_votes.hpp"
 #include "kg_host_compose.hpp"
 #include "kg_host_evidence.hpp"
+#include "kg_host_residual.hpp"

@@ -1318,13 +1318,26 @@ class SearchDb:
                        device_ptr: Optional[int] = None, min_shared: int = 2, max_cand: int = 8, max_db_per_kmer: int = 256,
                        align: Optional[dict] = None, max_windows: int = 0, max_pairs: int = 0, paths: Optional[str] = None,
                        max_trace_cells: int = N.TRACE_DEFAULT_MAX_CELLS, ops: Optional[str] = None, mask=None, ungapped=None,
-                       band: Optional[int] = None) -> "Evidence":
+                       band: Optional[int] = None, explained_by=None, explain_min: int = 1, min_db_count: int = 0) -> "Evidence":
         """Genes by homology (include/kmerguts_hip.h kg_contigs_search_translated states the rule): every stop-to-stop run of the
         six frames of the contigs with at least min_res residues is a query of search(); a hit of rank below max_hits with a
         traced path becomes a CALL record in contig coordinates whose fI is the target, or target_fn[target] (int32[n_db]).
         seq / offsets: the contigs, as a scan takes them; device_ptr: the address of the bytes in HBM instead of seq.  The other
-        keywords are search()'s; paths=None is read as "hits", since a CALL needs the path's start.  -> an Evidence."""
+        keywords are search()'s; paths=None is read as "hits", since a CALL needs the path's start.  -> an Evidence.
+        explained_by: the signature CALLs of the same batch, a ScanResult of a DNA scan (read where its CALLs lie on the device)
+        or a _native.CALL_DTYPE array in container order (kg_contigs_search_residual states the rule; target_fn is then
+        required).  Only the fragments whose touching CALLs' counts sum to less than explain_min are searched, homology CALLs of
+        a count below min_db_count are left out, and the Evidence's calls are the two kinds merged by container."""
         hd = self._handle()
+        if explained_by is None and (int(explain_min) != 1 or int(min_db_count) != 0):
+            raise ValueError("explain_min and min_db_count need explained_by")
+        if explained_by is not None:
+            if target_fn is None:
+                raise ValueError("explained_by needs target_fn: the two kinds of CALL share one function index space")
+            if int(explain_min) < 1:
+                raise ValueError("explain_min must be >= 1")
+            if int(min_db_count) < 0:
+                raise ValueError("min_db_count must be >= 0")
         up, trace = _search_options(ungapped, band, "hits" if paths is None else paths, ops)
         if int(min_res) < 1:
             raise ValueError("min_res must be >= 1")
@@ -1345,13 +1358,26 @@ class SearchDb:
         bp = N.KgBandParams(int(band), (C.c_int32 * 3)(0, 0, 0)) if band is not None else None
         keep = None if device_ptr is not None else _seq_bytes(seq, off)
         h = C.c_void_p()
-        N.check(N.load().kg_contigs_search_translated(
-            hd, C.byref(p), C.byref(ap), C.byref(tp), C.c_void_p(device_ptr) if keep is None else _ptr(keep), int(keep is None),
-            off.ctypes.data, off.size - 1, int(max_windows), int(max_pairs), trace, int(max_trace_cells),
-            C.byref(mp[0]) if mp is not None else None, C.byref(up) if up is not None else None, C.byref(bp) if bp is not None else None,
-            _ptr(fn), C.byref(h)))
+        lib = N.load()
+        args = (hd, C.byref(p), C.byref(ap), C.byref(tp), C.c_void_p(device_ptr) if keep is None else _ptr(keep), int(keep is None),
+                off.ctypes.data, off.size - 1, int(max_windows), int(max_pairs), trace, int(max_trace_cells),
+                C.byref(mp[0]) if mp is not None else None, C.byref(up) if up is not None else None, C.byref(bp) if bp is not None else None,
+                _ptr(fn))
+        if explained_by is None:
+            N.check(lib.kg_contigs_search_translated(*args, C.byref(h)))
+        else:
+            rp = N.KgResidualParams(int(explain_min), int(min_db_count), 0)
+            if isinstance(explained_by, ScanResult):
+                explained_by._need()
+                N.check(lib.kg_result_search_residual(explained_by._h, *args, C.byref(rp), C.byref(h)))
+            else:
+                sig = np.ascontiguousarray(explained_by)
+                if sig.dtype != N.CALL_DTYPE or sig.ndim != 1:
+                    raise ValueError("explained_by must be a ScanResult or a _native.CALL_DTYPE array")
+                N.check(lib.kg_contigs_search_residual(*args, _ptr(sig), 0, sig.size, C.byref(rp), C.byref(h)))
         has_mask = mp is not None or self.info()["mask"] is not None
-        return Evidence(h, off.size - 1, self._device, has_mask, up is not None, band, "hits" if paths is None else paths, ops)
+        return Evidence(h, off.size - 1, self._device, has_mask, up is not None, band, "hits" if paths is None else paths, ops,
+                        residual=explained_by is not None)
 
     def close(self) -> None:
         if self._h is not None:
@@ -1372,9 +1398,15 @@ class Evidence(_GeneSteps):
     (fragments, fragment_residues, records, calls, dropped_status, dropped_rank, dropped_untraced, ms_*).
     regions(), orfs() and select() are ScanResult's, arguments, results and side attributes, on these CALLs; the repair step is
     kg_regionset_repair with the evidence's device CALLs.  Use as a context manager or call close(); the evidence may outlive
-    its SearchDb."""
+    its SearchDb.
+    With explained_by (kg_contigs_search_residual) `calls` is the merged list, `call_hits` holds -1 for a signature CALL,
+    `fragments` are all fragments and `search` is the search of the searched ones; there are also `explain` (int64 per
+    fragment), `searched` (int64: every query's index among the fragments), `searched_fragments` (records, prot_start, residues),
+    `call_kind` (uint8: 0 signature, 1 homology), `call_source` (int64: the CALL's index in its own list) and `residual_stats`
+    (sig_calls, explained, explained_residues, searched, searched_residues, db_calls, dropped_min_count, merged, ms_*).
+    Without it none of these attributes exists."""
 
-    def __init__(self, handle, n_seqs: int, device: int, has_mask: bool, has_ung: bool, band, paths, ops):
+    def __init__(self, handle, n_seqs: int, device: int, has_mask: bool, has_ung: bool, band, paths, ops, residual: bool = False):
         self._h = handle
         self._seqs, self._dev = int(n_seqs), int(device)
         lib = N.load()
@@ -1388,6 +1420,15 @@ class Evidence(_GeneSteps):
             frags = _take_orfset(C.c_void_p(lib.kg_evidence_fragments(self._h)), False, free=False)
             self.fragments, self.fragment_stats = frags[:3], frags[3]
             self.search = _take_hitset(C.c_void_p(lib.kg_evidence_hits(self._h)), has_mask, has_ung, band, paths, ops, db=True, free=False)
+            if residual:
+                rst = N.KgResidualStats()
+                N.check(lib.kg_residual_stats_of(self._h, C.byref(rst)))
+                self.residual_stats = rst.as_dict()
+                self.explain = _copy_records(lib.kg_residual_explain_copy, self._h, len(self.fragments[0]), np.int64)
+                self.searched = _copy_records(lib.kg_residual_searched_copy, self._h, int(rst.searched), np.int64)
+                self.searched_fragments = _take_orfset(C.c_void_p(lib.kg_residual_searched_fragments(self._h)), False, free=False)[:3]
+                self.call_kind = _copy_records(lib.kg_residual_call_kinds_copy, self._h, n, np.uint8)
+                self.call_source = _copy_records(lib.kg_residual_call_sources_copy, self._h, n, np.int64)
         except BaseException:
             self.close()
             raise
